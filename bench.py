@@ -3,12 +3,16 @@
     python bench.py --gpus 1 --steps 50 --warmup 10
     python bench.py --gpus N ...                 # starts its own N ranks (child processes, before the parent touches a GPU)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...     # or under a launcher
-    python bench.py --config dense_351 --batch 32        # SURVEY 8(d)'s stress shape: temporal attention over 351 tokens
+    python bench.py --config dense_351 --batch 32 --full # SURVEY 8(d)'s stress shape: temporal attention over 351 tokens
+    python bench.py --full                       # + per-kernel timing / roofline, CPU baseline, parity vs the oracle, secondary workloads
+    python bench.py --dump-outputs DIR           # + the last timed step's outputs as DIR/<name>.npy
 
 One step = one forward of `--batch` sequences per rank (inputs resident in HBM) + the
 per-joint MPJPE kernel; with N > 1 ranks the batch is sharded (weak scaling: every rank
 runs `--batch` sequences) and each step all-gathers the (B_local, 17) f64 error block over
-RCCL.  Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").
+RCCL.  Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").  A plain run sets up,
+warms up, times `--steps` steps and prints the line; everything else it can measure or
+check runs only under `--full`.
 """
 import argparse
 import json
@@ -143,27 +147,58 @@ def run_pipelined_steps(pipe, n, depth, gather):
     `gather`; the collective of gather mode "end" closes the loop.  (`pipe`: launch() -> ticket, result(ticket) -> (full, central, err),
     after(ticket, fn) -> fn(full, central, err) on the slot's stream, join().)  Gather mode "end" keeps the block with a copy ON THE SLOT'S
     STREAM (pipe.after: no wait on the caller's stream, whose hardware queue a quarter of the slots share); the caller's stream joins the
-    slots before the collective.  Mode "step" needs the block on the caller's stream every step (pipe.result)."""
+    slots before the collective.  Mode "step" needs the block on the caller's stream every step (pipe.result).
+    Returns (full, central, err) of the last step: the slot's buffers, valid until the pipeline launches again."""
     gather.reset()
     on_slot = gather.mode == "end"
-    keep = lambda full, central, e: gather.step(e)
+
+    def keep(full, central, e):
+        gather.step(e)
+        return full, central, e
+
+    def take(t):
+        return pipe.after(t, keep) if on_slot else keep(*pipe.result(t))
     tickets = []
+    last = None
     free = on_slot and not os.environ.get("UU3D_BENCH_WAIT_CALLER")      # (inputs resident in the slots, consumer on the slot's stream: nothing on the caller's stream to wait for)
     for _ in range(n):
         tickets.append(pipe.launch(wait_caller=False) if free else pipe.launch())
         if len(tickets) == depth:
-            t = tickets.pop(0)
-            if on_slot:
-                pipe.after(t, keep)
-            else:
-                gather.step(pipe.result(t)[2])
+            last = take(tickets.pop(0))
     for t in tickets:
-        if on_slot:
-            pipe.after(t, keep)
-        else:
-            gather.step(pipe.result(t)[2])
+        last = take(t)
     pipe.join()
     gather.finish()
+    return last
+
+
+# --dump-outputs: at most this many bytes of .npy files in all
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays, seed=0):
+    """--dump-outputs: every array of `arrays` (name -> numpy array or None) as <path>/<name>.npy in float32 / float64 (other dtypes are
+    widened to float64), in order.  An array that would take the total past DUMP_LIMIT_BYTES is replaced by a fixed, seeded sample of its
+    flattened elements (same size and seed: same indices), so that two builds run with the same arguments compare output for output.
+    Returns {name: shape written}."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    left, header = DUMP_LIMIT_BYTES, 128                     # (np.save writes a header of 128 bytes in front of the data)
+    written = {}
+    for name, a in arrays.items():
+        if a is None:
+            continue
+        a = np.ascontiguousarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        if a.nbytes + header > left:
+            k = min(a.size, max(0, (left - header) // a.itemsize))
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, size=k, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes + header
+        written[name] = list(a.shape)
+    return written
 
 
 def parity_vs_oracle(cfg, arch, weights, x, m, full, central, gt, n=8, idx=None):
@@ -228,6 +263,9 @@ def train_bench(args, world, rank, local_rank, use_dist):
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        # what the last timed step hands back: its loss and the weights it updated
+        dump_outputs(args.dump_outputs, {"loss": loss.double().cpu().numpy(), "params": tr.params.cpu().numpy()})
     if rank == 0:
         fl = pkg.flops_per_sequence(arch)["total"] * 3.0       # forward + backward ~ 3x forward GEMM FLOPs
         seqs = world * B * args.steps
@@ -489,6 +527,60 @@ def attention_roofline(agg, n_tokens, label):
             "arithmetic": "f16x3 (3 f16 MFMA passes, f32 accumulate; frac of pipe = 3 x frac)" if h3 else "exact f32 MFMA"}
 
 
+def kernel_blocks(args, pkg, arch, agg, reps, prof_schedule, under_load, B, N, seqs, world, elapsed):
+    """--full: the `roofline`, `kernel_ms_per_forward`, `kernel_ms_schedule` and `sum_kernel_ms` blocks of the bench line, from the
+    per-kernel HIP-event records `agg` of `reps` quiet forwards and the timed region (`seqs` sequences in `elapsed` seconds)."""
+    fl = pkg.flops_per_sequence(arch)
+    total_ms = sum(a["ms"] for a in agg.values()) / reps
+    # GEMM kernels by SYMBOL (the profile records carry the distinguishing part of the symbol: "gemm_panel8<BiasSplitQ>", "mlp_fused", ...):
+    # the dominant kernel is the symbol with the most time per forward, whatever labels its launches carry
+    is_gemm = (lambda k: k.startswith(("gemm_h3", "gemm_panel", "mlp_fused", "gemm_wt", "tchain"))) if args.precision == "f16x3" else (lambda k: k.startswith("gemm_f32"))
+    peak = PEAK_F16_MFMA_TFLOPS if args.precision == "f16x3" else PEAK_F32_MFMA_TFLOPS
+    by_sym = {}
+    for k, a in agg.items():
+        if is_gemm(a["kernel"]):
+            bs = by_sym.setdefault(a["kernel"], dict(ms=0.0, flops=0.0, n=0, labels=[]))
+            bs["ms"] += a["ms"]; bs["flops"] += a["flops"]; bs["n"] += a["n"]; bs["labels"].append(k)
+    gk = max(by_sym, key=lambda k: by_sym[k]["ms"])
+    dom = by_sym[gk]
+    dom_key = "+".join(sorted(dom["labels"]))
+    ach = dom["flops"] / (dom["ms"] * 1e-3) / 1e12
+    gemm_fl = sum(bs["flops"] for bs in by_sym.values())
+    gemm_ms = sum(bs["ms"] for bs in by_sym.values())
+    return {
+        "roofline": {"bound": "mfma", "bound_measured": BOUND_MEASURED if gk == "tchain" else None, "kernel": f"{gk} [{dom_key}]",
+                     "achieved": round(ach, 2), "peak": peak, "unit": "TFLOP/s",
+                     "frac": round(ach / peak, 4), "traffic": pmc_traffic(gk, pmc_summary_for(args.config, B), grid=((B * N + TC_ROWS - 1) // TC_ROWS) * TC_THREADS if gk == "tchain" else None),
+                     "note": ("algorithmic 2*M*N*K FLOPs (tchain: every Dense layer the launch walks -- projection, fc1, fc2, the next block's QKV; mlp_fused: both Dense layers of the MLP, 4*M*d*h); the f16x3 kernels issue 3 f16 "
+                              "MFMA passes per product, so the matrix pipe does 3x this work (frac of pipe = 3 * frac)") if args.precision == "f16x3" else
+                             "exact f32-input MFMA",
+                     "traffic_note": "`traffic` is read from the committed counter run of this workload (profiles/, separate --pmc passes, launched eagerly under the same schedule) -- not measured in this process, which runs several hipGraphs in flight",
+                     "avg_launch_ms": round(dom["ms"] / dom["n"], 5),
+                     **({"workgroups_per_launch": (B * N + TC_ROWS - 1) // TC_ROWS, "cus": 256,
+                         "frac_of_occupied_cus": round(ach / (peak * min(256, (B * N + TC_ROWS - 1) // TC_ROWS) / 256.0), 4),
+                         "occupancy_note": f"the temporal chain runs ONE workgroup per {TC_ROWS} token rows and CU (64 rows: eight waves on 16-token panels, 157 KiB of LDS): a launch of this batch occupies "
+                                           "that many of the 256 CUs, `achieved` / `frac` are the launch measured ALONE against the whole chip's peak (`under_load`: the same launch with "
+                                           "every CU busy); the timed path runs several forwards' launches side by side"}
+                        if gk == "tchain" else {}),
+                     "attention": attention_roofline(agg, N, "synthetic dense-351 (NOT a shipped config)" if args.config == "dense_351" else f"config/{args.config}.json"),
+                     # the four largest GEMM launch classes (the first two are within a microsecond per launch of each
+                     # other, so which one is "dominant" changes from box to box)
+                     "gemm_symbols": [{"kernel": f"{k} [{'+'.join(sorted(bs['labels']))}]", "ms_per_forward": round(bs["ms"] / reps, 4),
+                                       "launches_per_forward": bs["n"] // reps,
+                                       "achieved": round(bs["flops"] / (bs["ms"] * 1e-3) / 1e12, 2),
+                                       "frac": round(bs["flops"] / (bs["ms"] * 1e-3) / 1e12 / peak, 4)}
+                                      for k, bs in sorted(by_sym.items(), key=lambda kv: -kv[1]["ms"])[:4]],
+                     "all_gemm_tflops": round(gemm_fl / (gemm_ms * 1e-3) / 1e12, 2),
+                     "under_load": under_load,
+                     "model_tflops": round(fl["total"] * seqs / world / elapsed / 1e12, 2),
+                     "model_frac": round(fl["total"] * seqs / world / elapsed / 1e12 / peak, 4),
+                     "model_frac_note": "whole-forward algorithmic FLOPs per second of the TIMED region (driver-clocked) over the dense peak of the arithmetic: the one figure of this block that no solo launch flatters"},
+        "kernel_ms_per_forward": {k: round(a["ms"] / reps, 4) for k, a in sorted(agg.items(), key=lambda kv: -kv[1]["ms"])},
+        "kernel_ms_schedule": prof_schedule + " (one quiet forward per sample, HIP events around every launch: the launches the timed path ran)",
+        "sum_kernel_ms": round(total_ms, 4),
+    }
+
+
 def spawn_ranks(n, argv):
     """One process per GPU under torch.distributed.run on 127.0.0.1 (the container hostname may not resolve)."""
     import socket
@@ -510,8 +602,12 @@ def main():
     ap.add_argument("--batch", type=int, default=128, help="sequences per GPU per step")
     ap.add_argument("--config", default="h36m_351")
     ap.add_argument("--mask-stride", type=int, default=None, help="s_in; default = first MASK_STRIDE")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the short secondary workloads (other configs, eager, train step) appended to the JSON line at N = 1")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the parity check against the oracle")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the short secondary workloads (other configs, eager, train step) appended to the JSON line at N = 1")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline does not need: per-kernel timing and roofline, the CPU baseline, parity against "
+                    "the oracle, the secondary workloads and, with N > 1, the other gather mode (a plain run: set-up, warm-up, the timed steps, the result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                    "(float32 / float64, at most 64 MB in all; the inputs are seeded: the same arguments give the same inputs)")
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of replaying a hipGraph")
     ap.add_argument("--streams", type=int, default=0, help="independent batches in flight (pipeline.ForwardPipeline: one HIP stream, workspace and hipGraph each); 1 = one batch after the other; 0 (default) = two per HIP hardware queue (8; pipeline.distinct_queue_streams)")
     ap.add_argument("--precision", default="f16x3", choices=["f16x3", "f32"], help="GEMM arithmetic of the forward (both hold the 1e-4 parity bar)")
@@ -523,6 +619,8 @@ def main():
     ap.add_argument("--timing-experiment", action="store_true", help="tools/ only: accept a timing build of the library (UU3D_LIB=.../libuu3d_timing.so) and UU3D_SKIP; the line is labelled INVALID (launches skipped, results wrong)")
     ap.add_argument("--spawn-check", action="store_true", help="ranks print their rank / world size and exit (no GPU): checks the self-spawn path")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     switches = env_switches(args.timing_experiment)        # (raises under UU3D_SKIP / UU3D_TIMING_PARTS)
 
     # `python bench.py --gpus N` without a launcher: start N ranks as CHILD processes here, before this process has
@@ -606,9 +704,12 @@ def main():
         return per_joint_error(central, gt, cfg.ROOT_KEYTPOINT, out=errs[i])
 
     if args.halves and not args.no_halves:             # legacy option: two half-batch chains inside one call (no pipeline object)
+        halves_out = {}
+
         def compute():
             full, central = model([x, m], training=False)
             per_joint_error(central, gt, cfg.ROOT_KEYTPOINT, out=err)
+            halves_out["last"] = (full, central, err)   # (under a hipGraph: the graph's own output tensors, rewritten by every replay)
         run_compute = compute
         if use_graph:
             for _ in range(2):
@@ -625,6 +726,7 @@ def main():
                 run_compute()
                 gather.step(err)
             gather.finish()
+            return halves_out.get("last")
     else:
         try:
             if auto:                                    # two slots per HIP hardware queue (pipeline.distinct_queue_streams finds which streams share one)
@@ -644,12 +746,12 @@ def main():
         pipe.preload(x, m)
 
         def run_steps(n):
-            run_pipelined_steps(pipe, n, S, gather)
+            return run_pipelined_steps(pipe, n, S, gather)
 
     run_steps(args.warmup)
     sync_all()
     t0 = time.perf_counter()
-    run_steps(args.steps)
+    last = run_steps(args.steps)
     sync_all()
     elapsed = time.perf_counter() - t0
     if use_dist:
@@ -657,10 +759,22 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    # ---- --dump-outputs: what the timed path handed its caller in the last timed step (read before anything launches again) ----
+    if rank == 0 and args.dump_outputs:
+        full_l, central_l, err_l = last
+        arrays = {"full": full_l.cpu().numpy() if full_l is not None else None, "central": central_l.cpu().numpy(),
+                  "per_joint_error": err_l.cpu().numpy()}
+        if use_dist:                                     # N > 1: every rank's error block of that step, rank-major
+            every = (gather.step_out.view(world, B, J) if gather.mode == "step" else
+                     gather.gathered.view((world,) + tuple(gather.local.shape))[:, (gather.k - 1) % gather.local.shape[0]])
+            arrays["per_joint_error_all_ranks"] = every.cpu().numpy()
+        shapes = dump_outputs(args.dump_outputs, arrays)
+        print(f"[bench] outputs of the last timed step in {args.dump_outputs}: {shapes}", file=sys.stderr, flush=True)
+
     # ---- N > 1: the same loop once more with the OTHER gather mode (one all-gather per step on the caller's stream, what rounds 1-4 timed), so that
     # scaling numbers stay comparable across rounds: reported beside the headline, never instead of it ----
     other_gather = None
-    if use_dist and world > 1 and pipe is not None:
+    if args.full and use_dist and world > 1 and pipe is not None:
         other_mode = "step" if args.gather == "end" else "end"
         g2 = ErrorGather(other_mode, args.steps, B, J, world, "cuda", use_dist)
         run_pipelined_steps(pipe, args.warmup, S, g2)
@@ -674,50 +788,49 @@ def main():
         e2 = float(t.item())
         other_gather = {"mode": other_mode, "value": round(world * B * args.steps / e2, 2), "unit": "pose-sequences/s", "ms_per_step": round(e2 / args.steps * 1e3, 4)}
 
-    # ---- what the timed path produced for the resident batch (parity block of the JSON line; outside the timed region) ----
+    # ---- --full: what the timed path produced for the resident batch (parity block of the JSON line; outside the timed region) ----
     hip_full = hip_central = None
-    if pipe is not None and rank == 0:
+    if args.full and pipe is not None and rank == 0:
         f_, c_, _ = pipe.result(pipe.launch())
         torch.cuda.synchronize()
         hip_full, hip_central = (f_.cpu().numpy() if f_ is not None else None), c_.cpu().numpy()
 
-    # ---- per-kernel timing with HIP events on the launch stream (outside the timed region) ----
-    model.set_profiling(True)
-    agg = {}
-    reps = 5
+    # ---- --full: per-kernel timing with HIP events on the launch stream (outside the timed region) ----
+    agg, reps, under_load = {}, 5, None
     prof_schedule = "throughput" if (pipe is not None and S > 1) else "latency"       # the launches the timed path ran
-    for _ in range(reps):
-        model.call_scheduled([x, m], prof_schedule)
-        for e in model.read_profile():
-            # temporal blocks share one shape class ("t.<op>"); strided blocks keep their index
-            nm = e["name"]
-            key = ("t." + nm.split(".", 1)[1]) if (nm[0] == "t" and "." in nm) else nm
-            a = agg.setdefault(key, dict(ms=0.0, flops=0.0, bytes=0.0, n=0, kernel=e["kernel"]))
-            a["ms"] += e["ms"]; a["flops"] += e["flops"]; a["bytes"] += e["bytes"]; a["n"] += 1
-    # ---- the temporal chain's launch when it FILLS the chip (what the timed path runs: several forwards' 71-workgroup launches side by side):
-    # one quiet forward of the batch that makes 256 row tiles, HIP events around its launches ----
-    under_load = None
-    if rank == 0 and prof_schedule == "throughput" and any(a["kernel"] == "tchain" for a in agg.values()):
-        try:
-            b_full = (256 * 128) // N
-            reps_x = (b_full + B - 1) // B
-            xl, ml = x.repeat((reps_x, 1, 1, 1))[:b_full].contiguous(), m.repeat((reps_x, 1))[:b_full].contiguous()
-            ms, fls, n = 0.0, 0.0, 0
-            for it in range(4):
-                model.call_scheduled([xl, ml], "throughput")
-                for e in model.read_profile():
-                    if it > 0 and e["kernel"] == "tchain" and e["name"][0] == "t" and e["name"].endswith(".chain"):
-                        ms += e["ms"]; fls += e["flops"]; n += 1
-            if n:
-                under_load = {"workgroups": (b_full * N + TC_ROWS - 1) // TC_ROWS, "rows": b_full * N, "batch": b_full, "avg_launch_ms": round(ms / n, 5),
-                              "achieved": round(fls / (ms * 1e-3) / 1e12, 2), "unit": "TFLOP/s",
-                              "frac": round(fls / (ms * 1e-3) / 1e12 / PEAK_F16_MFMA_TFLOPS, 4),
-                              "note": "one temporal-block launch of the chain (projection .. next block's QKV) over 256 x 128 token rows = every CU busy for the whole launch: HIP events around the "
-                                      f"launches of a quiet forward of {b_full} sequences, same kernel and schedule as the timed path"}
-            del xl, ml
-        except Exception as e:  # pragma: no cover
-            under_load = {"error": f"{type(e).__name__}: {e}"}
-    model.set_profiling(False)
+    if args.full:
+        model.set_profiling(True)
+        for _ in range(reps):
+            model.call_scheduled([x, m], prof_schedule)
+            for e in model.read_profile():
+                # temporal blocks share one shape class ("t.<op>"); strided blocks keep their index
+                nm = e["name"]
+                key = ("t." + nm.split(".", 1)[1]) if (nm[0] == "t" and "." in nm) else nm
+                a = agg.setdefault(key, dict(ms=0.0, flops=0.0, bytes=0.0, n=0, kernel=e["kernel"]))
+                a["ms"] += e["ms"]; a["flops"] += e["flops"]; a["bytes"] += e["bytes"]; a["n"] += 1
+        # ---- the temporal chain's launch when it FILLS the chip (what the timed path runs: several forwards' 71-workgroup launches side by side):
+        # one quiet forward of the batch that makes 256 row tiles, HIP events around its launches ----
+        if rank == 0 and prof_schedule == "throughput" and any(a["kernel"] == "tchain" for a in agg.values()):
+            try:
+                b_full = (256 * 128) // N
+                reps_x = (b_full + B - 1) // B
+                xl, ml = x.repeat((reps_x, 1, 1, 1))[:b_full].contiguous(), m.repeat((reps_x, 1))[:b_full].contiguous()
+                ms, fls, n = 0.0, 0.0, 0
+                for it in range(4):
+                    model.call_scheduled([xl, ml], "throughput")
+                    for e in model.read_profile():
+                        if it > 0 and e["kernel"] == "tchain" and e["name"][0] == "t" and e["name"].endswith(".chain"):
+                            ms += e["ms"]; fls += e["flops"]; n += 1
+                if n:
+                    under_load = {"workgroups": (b_full * N + TC_ROWS - 1) // TC_ROWS, "rows": b_full * N, "batch": b_full, "avg_launch_ms": round(ms / n, 5),
+                                  "achieved": round(fls / (ms * 1e-3) / 1e12, 2), "unit": "TFLOP/s",
+                                  "frac": round(fls / (ms * 1e-3) / 1e12 / PEAK_F16_MFMA_TFLOPS, 4),
+                                  "note": "one temporal-block launch of the chain (projection .. next block's QKV) over 256 x 128 token rows = every CU busy for the whole launch: HIP events around the "
+                                          f"launches of a quiet forward of {b_full} sequences, same kernel and schedule as the timed path"}
+                del xl, ml
+            except Exception as e:  # pragma: no cover
+                under_load = {"error": f"{type(e).__name__}: {e}"}
+        model.set_profiling(False)
 
     if use_dist:                                         # every rank's buffered C stdio (RCCL's banner) out BEFORE rank 0's line
         try:
@@ -727,23 +840,6 @@ def main():
             pass
         dist.barrier()
     if rank == 0:
-        fl = pkg.flops_per_sequence(arch)
-        total_ms = sum(a["ms"] for a in agg.values()) / reps
-        # GEMM kernels by SYMBOL (the profile records carry the distinguishing part of the symbol: "gemm_panel8<BiasSplitQ>", "mlp_fused", ...):
-        # the dominant kernel is the symbol with the most time per forward, whatever labels its launches carry
-        is_gemm = (lambda k: k.startswith(("gemm_h3", "gemm_panel", "mlp_fused", "gemm_wt", "tchain"))) if args.precision == "f16x3" else (lambda k: k.startswith("gemm_f32"))
-        peak = PEAK_F16_MFMA_TFLOPS if args.precision == "f16x3" else PEAK_F32_MFMA_TFLOPS
-        by_sym = {}
-        for k, a in agg.items():
-            if is_gemm(a["kernel"]):
-                bs = by_sym.setdefault(a["kernel"], dict(ms=0.0, flops=0.0, n=0, labels=[]))
-                bs["ms"] += a["ms"]; bs["flops"] += a["flops"]; bs["n"] += a["n"]; bs["labels"].append(k)
-        gk = max(by_sym, key=lambda k: by_sym[k]["ms"])
-        dom = by_sym[gk]
-        dom_key = "+".join(sorted(dom["labels"]))
-        ach = dom["flops"] / (dom["ms"] * 1e-3) / 1e12
-        gemm_fl = sum(bs["flops"] for bs in by_sym.values())
-        gemm_ms = sum(bs["ms"] for bs in by_sym.values())
         seqs = world * B * args.steps
         out = {
             "metric": "pose-sequences/sec",
@@ -765,42 +861,14 @@ def main():
                                       ", each replaying its own hipGraph of forward + error "
                                       "kernel with its own workspace (uplift-upsample-3dhpe_amd/pipeline.py; the same path eval.run_eval uses)") if S > 1
                                      else "one batch after the other"},
-            "roofline": {"bound": "mfma", "bound_measured": BOUND_MEASURED if gk == "tchain" else None, "kernel": f"{gk} [{dom_key}]",
-                         "achieved": round(ach, 2), "peak": peak, "unit": "TFLOP/s",
-                         "frac": round(ach / peak, 4), "traffic": pmc_traffic(gk, pmc_summary_for(args.config, B), grid=((B * N + TC_ROWS - 1) // TC_ROWS) * TC_THREADS if gk == "tchain" else None),
-                         "note": ("algorithmic 2*M*N*K FLOPs (tchain: every Dense layer the launch walks -- projection, fc1, fc2, the next block's QKV; mlp_fused: both Dense layers of the MLP, 4*M*d*h); the f16x3 kernels issue 3 f16 "
-                                  "MFMA passes per product, so the matrix pipe does 3x this work (frac of pipe = 3 * frac)") if args.precision == "f16x3" else
-                                 "exact f32-input MFMA",
-                         "traffic_note": "`traffic` is read from the committed counter run of this workload (profiles/, separate --pmc passes, launched eagerly under the same schedule) -- not measured in this process, which runs several hipGraphs in flight",
-                         "avg_launch_ms": round(dom["ms"] / dom["n"], 5),
-                         **({"workgroups_per_launch": (B * N + TC_ROWS - 1) // TC_ROWS, "cus": 256,
-                             "frac_of_occupied_cus": round(ach / (peak * min(256, (B * N + TC_ROWS - 1) // TC_ROWS) / 256.0), 4),
-                             "occupancy_note": f"the temporal chain runs ONE workgroup per {TC_ROWS} token rows and CU (64 rows: eight waves on 16-token panels, 157 KiB of LDS): a launch of this batch occupies "
-                                               "that many of the 256 CUs, `achieved` / `frac` are the launch measured ALONE against the whole chip's peak (`under_load`: the same launch with "
-                                               "every CU busy); the timed path runs several forwards' launches side by side"}
-                            if gk == "tchain" else {}),
-                         "attention": attention_roofline(agg, N, "synthetic dense-351 (NOT a shipped config)" if args.config == "dense_351" else f"config/{args.config}.json"),
-                         # the four largest GEMM launch classes (the first two are within a microsecond per launch of each
-                         # other, so which one is "dominant" changes from box to box)
-                         "gemm_symbols": [{"kernel": f"{k} [{'+'.join(sorted(bs['labels']))}]", "ms_per_forward": round(bs["ms"] / reps, 4),
-                                           "launches_per_forward": bs["n"] // reps,
-                                           "achieved": round(bs["flops"] / (bs["ms"] * 1e-3) / 1e12, 2),
-                                           "frac": round(bs["flops"] / (bs["ms"] * 1e-3) / 1e12 / peak, 4)}
-                                          for k, bs in sorted(by_sym.items(), key=lambda kv: -kv[1]["ms"])[:4]],
-                         "all_gemm_tflops": round(gemm_fl / (gemm_ms * 1e-3) / 1e12, 2),
-                         "under_load": under_load,
-                         "model_tflops": round(fl["total"] * seqs / world / elapsed / 1e12, 2),
-                         "model_frac": round(fl["total"] * seqs / world / elapsed / 1e12 / peak, 4),
-                         "model_frac_note": "whole-forward algorithmic FLOPs per second of the TIMED region (driver-clocked) over the dense peak of the arithmetic: the one figure of this block that no solo launch flatters"},
-            "kernel_ms_per_forward": {k: round(a["ms"] / reps, 4) for k, a in sorted(agg.items(), key=lambda kv: -kv[1]["ms"])},
-            "kernel_ms_schedule": prof_schedule + " (one quiet forward per sample, HIP events around every launch: the launches the timed path ran)",
-            "sum_kernel_ms": round(total_ms, 4),
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full:
+            out.update(kernel_blocks(args, pkg, arch, agg, reps, prof_schedule, under_load, B, N, seqs, world, elapsed))
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(cfg, arch, weights, x_np, m_np)
         else:
             out["cpu_baseline"] = None
-        if not args.no_cpu_baseline and hip_central is not None:
+        if args.full and not args.no_cpu_baseline and hip_central is not None:
             try:
                 out["parity"] = parity_vs_oracle(cfg, arch, weights, x_np, m_np, hip_full, hip_central, gt_np)
             except Exception as e:  # pragma: no cover
@@ -815,7 +883,7 @@ def main():
             out["config"]["gather"] = ("one all-gather of every step's (B_local, J) f64 error block behind the loop's last result, inside the timed region" if args.gather == "end"
                                        else "one all-gather per step on the caller's stream")
             out["other_gather_mode"] = other_gather           # (the same loop with the other mode: rounds 1-4 timed "step")
-        if world == 1 and not args.no_secondary and args.config == "h36m_351":
+        if args.full and world == 1 and not args.no_secondary and args.config == "h36m_351":
             pipe = None
             args.streams_used = S
             out["secondary"] = secondary_benchmarks(args)

@@ -1,7 +1,8 @@
 """Keras .h5 weight I/O: the pure-Python HDF5 subset reader / writer against files written
 by a real HDF5 library, the reference loader's by-name / by-position semantics, and the model-sized round trip."""
+import hashlib
+import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,7 +16,6 @@ SPEC = [("embed/kernel", (2, 8)), ("embed/bias", (8,)),
         ("block_1/norm1/gamma", (8,)), ("block_1/norm1/beta", (8,)), ("block_1/attn/wq/kernel", (8, 8)),
         ("block_1/mlp/strided_conv/kernel", (3, 16, 8)),
         ("token/learnable_masked_token", (8,))]
-H5PY = "/opt/conda/bin/python3.9"
 
 
 def _values():
@@ -59,8 +59,11 @@ def test_loader_semantics_follow_the_reference(tmp_path):
         f = tmp_path / "not.h5"; f.write_bytes(b"hello world, definitely not hdf5"); weight_io.load_keras_h5(str(f), SPEC)
 
 
-@pytest.mark.parametrize("cfgname", ["h36m_81", "h36m_351", "h36m_81+bn", "h36m_351+mtoken"])
-def test_model_sized_roundtrip_and_h5py_reads_our_files(cfgname, tmp_path):
+ROUNDTRIP_CASES = ["h36m_81", "h36m_351", "h36m_81+bn", "h36m_351+mtoken"]
+
+
+def write_model_h5(cfgname, path):
+    """The model-sized file of a ROUNDTRIP_CASES entry, written by save_keras_h5 -> (spec, weights)."""
     cfg = util.load_config(cfgname.split("+")[0])
     if cfgname.endswith("+bn"):                        # OUTPUT_BN: two BatchNormalization layers, four weights each (gamma, beta, moving mean / variance)
         cfg.OUTPUT_BN = True
@@ -68,10 +71,16 @@ def test_model_sized_roundtrip_and_h5py_reads_our_files(cfgname, tmp_path):
         cfg.TOKEN_MASK_RATE, cfg.LEARNABLE_MASKED_TOKEN = 0.1, True
     arch = pkg.arch_from_config(cfg)
     spec = pkg.weight_spec(arch)
-    assert ("learnable_masked_token_layer/learnable_masked_token" in dict(spec)) == cfgname.endswith("+mtoken")
     w = pkg.init_weights(arch, seed=5, perturb=0.1)
-    path = str(tmp_path / "w.h5")
     weight_io.save_keras_h5(path, w, spec)
+    return spec, w
+
+
+@pytest.mark.parametrize("cfgname", ROUNDTRIP_CASES)
+def test_model_sized_roundtrip_and_h5py_reads_our_files(cfgname, tmp_path):
+    path = str(tmp_path / "w.h5")
+    spec, w = write_model_h5(cfgname, path)
+    assert ("learnable_masked_token_layer/learnable_masked_token" in dict(spec)) == cfgname.endswith("+mtoken")
     back, rep = weight_io.load_keras_h5(path, spec)
     assert all(np.array_equal(back[n], w[n]) for n, _ in spec) and not rep["unassigned_layers"]
     layers = []
@@ -79,18 +88,11 @@ def test_model_sized_roundtrip_and_h5py_reads_our_files(cfgname, tmp_path):
         if n.split("/")[0] not in layers:
             layers.append(n.split("/")[0])
     assert [x.decode() for x in hdf5_min.read_hdf5(path).attrs["layer_names"]] == layers      # SURVEY 8(f)-1 names
-    if not os.path.exists(H5PY):
-        pytest.skip("no interpreter with h5py on this machine: libhdf5 cross-check skipped")
-    code = ("import h5py, numpy as np, sys\n"
-            "f = h5py.File(sys.argv[1], 'r'); n = 0; s = 0.0\n"
-            "for l in f.attrs['layer_names']:\n"
-            "    g = f[l.decode()]\n"
-            "    for wn in g.attrs['weight_names']:\n"
-            "        a = np.asarray(g[wn.decode()]); n += a.size; s += float(np.abs(a.astype(np.float64)).sum())\n"
-            "print(n, repr(s))\n")
-    out = subprocess.run([H5PY, "-c", code, path], capture_output=True, text=True, check=True).stdout.split()
-    assert int(out[0]) == sum(int(np.prod(s)) for _, s in spec)
-    assert abs(float(out[1]) - sum(float(np.abs(w[n].astype(np.float64)).sum()) for n, _ in spec)) < 1e-6
+    # libhdf5 cross-check: h5py read THESE bytes (same sha256) when tests/golden/make_h5_readback_golden.py recorded what it found
+    exp = json.load(open(os.path.join(GOLD, "h5_readback_expected.json")))[cfgname]
+    assert hashlib.sha256(open(path, "rb").read()).hexdigest() == exp["sha256"], "the writer's bytes changed: re-run make_h5_readback_golden.py"
+    assert exp["h5py_elements"] == sum(int(np.prod(s)) for _, s in spec)
+    assert abs(exp["h5py_abs_sum"] - sum(float(np.abs(w[n].astype(np.float64)).sum()) for n, _ in spec)) < 1e-6
 
 
 def test_callbacks_can_adjust_or_drop_weights():

@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 V=${1:-UU3D_PANEL4}
 for r in 1 2; do
   for v in 1 0; do
-    env $V=$v python3 bench.py --steps 30 --warmup 5 --streams 1 --no-secondary --no-cpu-baseline 2>/dev/null | python3 -c "
+    env $V=$v python3 bench.py --steps 30 --warmup 5 --streams 1 --full --no-secondary --no-cpu-baseline 2>/dev/null | python3 -c "
 import sys,json; d=json.loads(sys.stdin.readline()); k=d['kernel_ms_per_forward']
 print('$V=$v', d['value'], 'sum_kernel_ms', d['sum_kernel_ms'], ' '.join(f'{n}={k[n]*1e3:.1f}' for n in list(k)[:14]))"
   done

@@ -7,7 +7,7 @@ RUNS = [("h36m_351", 128, 5), ("h36m_351", 128, 10), ("h36m_351", 128, 20),
         ("h36m_81", 256, 4), ("h36m_81", 256, 10), ("h36m_81", 256, 20)]
 for cfg, batch, ms in RUNS:
     out = subprocess.run([sys.executable, "bench.py", "--config", cfg, "--batch", str(batch), "--mask-stride", str(ms),
-                          "--steps", "30", "--warmup", "5", "--no-cpu-baseline"], capture_output=True, text=True)
+                          "--steps", "30", "--warmup", "5", "--full", "--no-cpu-baseline"], capture_output=True, text=True)
     line = [l for l in out.stdout.splitlines() if l.startswith("{")]
     if not line:
         print(cfg, ms, "FAILED", out.stderr[-500:])
