@@ -373,6 +373,39 @@ int uu3d_train_forward_backward_masked(uu3d_model* model, const float* params_de
                                        float* loss_out_dev, float* full_out_dev, float* central_out_dev,
                                        float* grads_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/*
+ * GradientTape -- the training step with the loss left to the caller (autograd: `loss.backward()` through model(..., training=True)).
+ *   uu3d_train_forward_tape: the training-mode forward of uu3d_train_forward_backward_masked (same arguments, same draws and Dropout)
+ *       that keeps its activations in the workspace and returns a tape instead of running a loss.  It makes every up-front check of
+ *       the backward pass (token limits, LDS of the backward attention kernels), so the tape's backward is never refused.  The models
+ *       the training step refuses are refused with the same messages.
+ *   uu3d_train_backward_tape: the backward pass of that forward, seeded with d loss / d full_output (B,N,J,3) and
+ *       d loss / d central_output (B,J,3) supplied by the caller (NULL = 0).  grads_dev (uu3d_num_params floats, inventory order) is
+ *       OVERWRITTEN with d loss / d params; NULL = not wanted.  grad_kp2d_dev (B,N,J,2), or NULL, receives d loss / d kp2d_dev; rows of
+ *       frames the stride mask (or the token mask) discards are exactly 0.  The cotangents are multiplied on the device by a power of
+ *       two that puts their largest magnitude into (0.5, 1] (loss scaling without a host synchronisation) and the results unscaled.
+ *       A non-finite cotangent or gradient RAISES the model's non-finite word (uu3d_train_nonfinite_flag); it is never cleared here, so
+ *       several backward passes before one optimizer step accumulate it.  uu3d_train_clear_nonfinite clears it.  The grad-ready
+ *       callback is not called.  A backward may run once or several times per tape.
+ *   The caller keeps params_dev, kp2d_dev, stride_mask_dev, the draws and the WORKSPACE alive and unchanged from the forward until the
+ *       last backward of a tape (the saved activations live in the workspace): one workspace per open tape; several tapes with
+ *       separate workspaces may be open at once.  The tape records batch, buffers and the Dropout rates and seed of its forward
+ *       (uu3d_train_set_dropout may change them before the backward).  If another call has regenerated the operand packs from a
+ *       different parameter buffer in between, the backward regenerates them first.
+ *   uu3d_tape_destroy frees the tape (not the caller's buffers); call it when no backward will follow.
+ */
+typedef struct uu3d_tape uu3d_tape;
+int uu3d_train_forward_tape(uu3d_model* model, const float* params_dev, const float* kp2d_dev, const uint8_t* stride_mask_dev, int32_t batch,
+                            const float* drop_path_rates, const float* drop_path_uniform_dev,
+                            const float* token_mask_uniform_dev, float token_mask_rate,
+                            float* full_out_dev, float* central_out_dev,
+                            void* workspace_dev, size_t workspace_bytes, uu3d_tape** out_tape, void* stream);
+int uu3d_train_backward_tape(uu3d_model* model, uu3d_tape* tape, const float* grad_full_dev, const float* grad_central_dev,
+                             float* grads_dev, float* grad_kp2d_dev, void* stream);
+void uu3d_tape_destroy(uu3d_tape* tape);
+/* Clears the model's non-finite-gradient word on `stream` (what a new accumulation of tape backward passes starts from). */
+int uu3d_train_clear_nonfinite(uu3d_model* model, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -433,14 +433,72 @@ struct TnLoadGelu {
 // loss-scaled activation gradient beyond the f16 range makes the hi plane of the f16x3 split infinite -- raises *flag, which
 // the guarded AdamW update (uu3d_adamw_update_guarded) reads on the device: the step is then skipped, no host sync.
 static __global__ void __launch_bounds__(256)
-scale_flat_kernel(float* __restrict__ x, const long long n, const float s, unsigned* __restrict__ flag)
+scale_flat_kernel(float* __restrict__ x, const long long n, const float s, const float* __restrict__ s_dev, unsigned* __restrict__ flag)
 {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i < n) {
-        const float v = x[i] * s;
+        const float v = x[i] * (s_dev != nullptr ? *s_dev : s);      // s_dev: the factor the cotangent pass left on the device (tape backward)
         x[i] = v;
         if (flag != nullptr && !(fabsf(v) <= 3.4e38f)) atomicOr(flag, 1u);
     }
+}
+
+// ---- seeding a backward pass from caller-supplied output gradients (uu3d_train_backward_tape) ------------------------------------
+// words[0]: max |g| over both cotangents as the bits of a non-negative float (unsigned order = float order, NaN above +Inf);
+// zeroed by the caller before cot_absmax_kernel, read by cot_seed_kernel, which writes words[1] = scale, words[2] = 1 / scale.
+static __global__ void __launch_bounds__(256)
+cot_absmax_kernel(const float* __restrict__ gf, const long long nf, const float* __restrict__ gc, const long long nc, unsigned* __restrict__ words)
+{
+    unsigned best = 0u;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nf + nc; i += (long long)gridDim.x * 256)
+        best = max(best, __float_as_uint(fabsf(i < nf ? gf[i] : gc[i - nf])));
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) best = max(best, (unsigned)__shfl_xor((int)best, o));
+    __shared__ unsigned red[4];
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = best;
+    __syncthreads();
+    if (threadIdx.x == 0) atomicMax(words, max(max(red[0], red[1]), max(red[2], red[3])));
+}
+// dFull = scale * grad_full (0 where NULL), dCentral = scale * grad_central: a power of two that puts max |g| into (0.5, 1] (1 when every
+// cotangent is 0; clamped to [2^-126, 2^126]) -- the f16x3 gradient GEMMs see the magnitudes the built-in loss hands them.  A non-finite
+// cotangent raises the non-finite word (never cleared here) and leaves the scale at 1.
+static __global__ void __launch_bounds__(256)
+cot_seed_kernel(const float* __restrict__ gf, const long long nf, const float* __restrict__ gc, const long long nc,
+                float* __restrict__ dF, float* __restrict__ dC, float* __restrict__ words, unsigned* __restrict__ nonfinite)
+{
+    const unsigned mb = reinterpret_cast<const unsigned*>(words)[0];
+    float s = 1.f;
+    if (mb >= 0x7f800000u) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(nonfinite, 1u);
+    } else if (mb != 0u) {
+        int e;
+        const float f = frexpf(__uint_as_float(mb), &e);          // max = f 2^e, f in [0.5, 1)
+        if (f == 0.5f) e -= 1;                                      // a power of two goes to 1
+        s = ldexpf(1.f, min(max(-e, -126), 126));
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) { words[1] = s; words[2] = 1.f / s; }
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nf + nc; i += (long long)gridDim.x * 256) {
+        if (i < nf) dF[i] = gf != nullptr ? gf[i] * s : 0.f;
+        else dC[i - nf] = gc != nullptr ? gc[i - nf] * s : 0.f;
+    }
+}
+// d kp2d (rows x 2) = g (rows x DS) . W_emb^T (W_emb: (2, DS), Keras layout) times inv_scale[0]: g is d(embedding output) behind the
+// token_dropout mask.  Rows of frames whose keep byte is 0 (stride mask, or the token-mask rows that fold it in) are exactly 0: the
+// token blend discards them.
+static __global__ void __launch_bounds__(256)
+embed_input_grad_kernel(const float* __restrict__ g, const float* __restrict__ We, const int rows, const int J, const int DS,
+                        const uint8_t* __restrict__ frame_keep, const float* __restrict__ inv_scale, float* __restrict__ out)
+{
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= rows) return;
+    float ax = 0.f, ay = 0.f;
+    if (frame_keep == nullptr || frame_keep[r / J] != 0) {
+        const float* gr = g + (size_t)r * DS;
+        for (int c = 0; c < DS; ++c) { const float v = gr[c]; ax = fmaf(v, We[c], ax); ay = fmaf(v, We[DS + c], ay); }
+        const float is = *inv_scale;
+        ax *= is; ay *= is;
+    }
+    out[2 * (size_t)r] = ax; out[2 * (size_t)r + 1] = ay;
 }
 
 }  // namespace uu3d

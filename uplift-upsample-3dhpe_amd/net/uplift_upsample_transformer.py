@@ -11,6 +11,14 @@ and ``central`` (B, J, 3).  ``training=True`` (train.py:478) runs the training-m
 DropPath with draws from the model's (or its Trainer's) generator, on the LIVE weights of
 the Trainer when one is attached.  ``model.weights`` / ``model.trainable_variables``
 (train.py:496,503) are name -> array views in the reference's creation order.
+
+Autograd (the role of tf.GradientTape, train.py:477-498): ``model.parameters()`` yields ONE
+``torch.nn.Parameter``, the flat float32 master buffer (inventory order, Keras layouts; an
+attached Trainer's ``params``).  After ``model.requires_grad_()`` (off by default), a
+``training=True`` call under grad mode returns outputs with a ``grad_fn`` and ``loss.backward()``
+runs the library's backward pass from the output gradients.  In-place changes of the parameter
+(``torch.optim.*.step()``, in-place ops under ``torch.no_grad()``) are picked up by the next call;
+writes through ``p.data`` do not bump torch's version counter and need ``model.parameters_changed()``.
 PyTorch is used for device memory and streams only; every FLOP runs in
 ``csrc/libuu3d.so``.  There is no CPU fallback.
 """
@@ -109,7 +117,9 @@ class UpliftUpsampleTransformer(object):
         self._trainer = None              # a trainer.Trainer owns the live weights once attached
         self._weights_dirty = False       # live (trainer) weights newer than the host / inference copies
         self._holds_ema = False           # Trainer.export_to_model(use_ema=True): the model holds the EMA weights until the next step
-        self._train_params = None         # master buffer of a training-mode forward without a Trainer
+        self._train_params = None         # master buffer of a training-mode forward without a Trainer (torch.nn.Parameter)
+        self._requires_grad = False       # model.requires_grad_(): training=True calls under grad mode record a tape
+        self._param_seen = None           # (parameter, its _version at the last repack): in-place changes are picked up by the next call
         self._train_ws = None
         self._seed = seed
         self._rng = None
@@ -141,17 +151,90 @@ class UpliftUpsampleTransformer(object):
     # ---- live weights of an attached Trainer -------------------------------------------------
     def _attach_trainer(self, trainer):
         self._trainer, self._train_params = trainer, None
+        self._param_seen = (trainer.params, trainer.params._version)
+
+    def _export_live(self):
+        """The live weights (an attached Trainer's, or the model's own parameter after an in-place change) into the host / inference copies."""
+        if not self._weights_dirty:
+            return
+        if self._trainer is not None:
+            self._trainer.export_to_model()
+        elif self._train_params is not None:
+            torch = self._torch
+            with torch.cuda.device(self.device):
+                stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+                _capi.check(self._lib, self._lib.uu3d_train_export(self._h, C.c_void_p(self._train_params.data_ptr()), stream), self._h)
+            self._weights_dirty = False
 
     def _sync_from_trainer(self):
         """save_weights / get_weights / inference calls see the trained weights (train.py:393,706,719 use the live model)."""
-        if self._trainer is not None and self._weights_dirty:
-            self._trainer.export_to_model()
+        self._check_param_version()
+        self._export_live()
         self._flush_assigns()
+
+    # ---- the parameter of autograd (torch.nn.Module-style access) -------------------------------
+    def _live_param(self):
+        """The flat master buffer as a torch.nn.Parameter: the Trainer's when one is attached, else the model's own (created here)."""
+        if self._trainer is not None:
+            return self._trainer.params
+        if self._train_params is None:
+            torch = self._torch
+            p = torch.nn.Parameter(torch.empty(int(self._lib.uu3d_num_params(self._h)), dtype=torch.float32, device=self.device),
+                                   requires_grad=self._requires_grad)
+            stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            _capi.check(self._lib, self._lib.uu3d_train_init(self._h, C.c_void_p(p.data_ptr()), stream), self._h)
+            self._train_params = p
+            self._param_seen = (p, p._version)
+        return self._train_params
+
+    def parameters(self, recurse=True):
+        """Yields the one parameter: the flat float32 master buffer in inventory order and Keras layouts."""
+        yield self._live_param()
+
+    def named_parameters(self, prefix="", recurse=True):
+        """Yields (name, view) for every weight of the inventory: views of the parameter's storage (writes through them are
+        in-place changes of the parameter)."""
+        flat = self._live_param().detach()
+        o = 0
+        for name, shape in self._spec:
+            n = int(np.prod(shape))
+            yield prefix + name, flat[o:o + n].view(shape)
+            o += n
+
+    def requires_grad_(self, requires_grad=True):
+        """Switches gradients of the parameter on (off by default): training=True calls under grad mode then run through autograd."""
+        self._requires_grad = bool(requires_grad)
+        self._live_param().requires_grad_(self._requires_grad)
+        return self
+
+    def parameters_changed(self):
+        """Declares the parameter changed outside torch's version counter (writes through ``p.data``, or into its storage from
+        native code): the operand packs are regenerated and the inference weights refreshed before the next call."""
+        self._param_changed(self._live_param())
+
+    def _param_changed(self, p):
+        torch = self._torch
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        _capi.check(self._lib, self._lib.uu3d_train_repack(self._h, C.c_void_p(p.data_ptr()), stream), self._h)
+        self._param_seen = (p, p._version)
+        self._weights_dirty = True            # the host / inference weights are stale (as after Trainer.apply_gradients)
+        self._holds_ema = False
+
+    def _check_param_version(self):
+        """An in-place change of the parameter since the last repack (torch.optim step, in-place op under no_grad) is picked up here."""
+        p = self._trainer.params if self._trainer is not None else self._train_params
+        if p is None:
+            return
+        seen = self._param_seen
+        if seen is None or seen[0] is not p:
+            self._param_seen = (p, p._version)
+        elif p._version != seen[1]:
+            self._param_changed(p)
 
     # ---- single-variable access (WeightView) ----------------------------------------------------
     def _get_one(self, name, shape):
-        if self._trainer is not None and self._weights_dirty:   # (a model that holds the EMA weights reads them: that is what was asked for)
-            self._trainer.export_to_model()
+        self._check_param_version()
+        self._export_live()                                     # (a model that holds the EMA weights reads them: that is what was asked for)
         a = np.empty(shape, np.float32)
         _capi.check(self._lib, self._lib.uu3d_get_weight(self._h, name.encode(), a.ctypes.data_as(C.c_void_p), a.size), self._h)
         return a
@@ -160,8 +243,10 @@ class UpliftUpsampleTransformer(object):
         # the other variables keep their TRAINED values: a stale model is refreshed first, and so is a model that holds the EMA
         # weights after Trainer.export_to_model(use_ema=True) -- otherwise the flush below would reload the master buffer with
         # "EMA weights + the one assigned tensor" and the trained weights would be gone
+        self._check_param_version()
         if self._trainer is not None and (self._weights_dirty or self._holds_ema):
             self._trainer.export_to_model()
+        self._export_live()
         a = np.ascontiguousarray(np.asarray(value, dtype=np.float32).reshape(shape))
         _capi.check(self._lib, self._lib.uu3d_set_weight(self._h, name.encode(), a.ctypes.data_as(C.c_void_p), a.size), self._h)
         self._pending_assigns = True
@@ -169,13 +254,24 @@ class UpliftUpsampleTransformer(object):
     def _flush_assigns(self):
         """Deferred half of WeightView.assign: one commit (+ one reload of an attached Trainer's master buffer) for any number of
         assigned variables."""
+        self._check_param_version()
         if getattr(self, "_pending_assigns", False):
             self._pending_assigns = False
             self._commit()
             self._holds_ema = False
             if self._trainer is not None:
                 self._trainer.reload_from_model()
-            self._train_params = None
+            self._reload_own_params()
+
+    def _reload_own_params(self):
+        """The model's weights were replaced: its own parameter (if it has one) takes them, in place, so a parameter handed out by
+        parameters() stays the live one."""
+        if self._train_params is not None:
+            torch = self._torch
+            p = self._train_params
+            stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            _capi.check(self._lib, self._lib.uu3d_train_init(self._h, C.c_void_p(p.data_ptr()), stream), self._h)
+            self._param_seen = (p, p._version)
 
     @property
     def weights(self):
@@ -201,7 +297,7 @@ class UpliftUpsampleTransformer(object):
         self._holds_ema = False
         if self._trainer is not None:       # the trainer's master buffer follows (Adam moments are kept, like tf.Variable.assign)
             self._trainer.reload_from_model()
-        self._train_params = None
+        self._reload_own_params()
 
     def set_weights(self, weight_list):
         if len(weight_list) != len(self._spec):
@@ -308,36 +404,42 @@ class UpliftUpsampleTransformer(object):
         self.last_dropout_seed = seed                           # (what a test needs to evaluate the same masks on the CPU)
         return seed
 
-    def _training_forward(self, x, stride_mask, full, central):
-        """model(inputs, training=True) (train.py:478): DropPath active, live weights.  Without a Trainer the model keeps
-        its own master buffer (uu3d_train_init) and generator."""
+    def _training_draws(self, B):
+        """The live parameter and this training-mode call's draws (DropPath uniforms, token-mask uniforms, Dropout seed), from the
+        Trainer's generator when one is attached, else from the model's own."""
         from ..arch import training_unsupported
         torch = self._torch
         bad = training_unsupported(self.arch)
         if bad:
             raise NotImplementedError("training=True with " + "; ".join(bad) + " is not implemented")
-        a, B = self.arch, x.shape[0]
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        a = self.arch
+        params = self._live_param()
         if self._trainer is not None:
-            params, rng, rates = self._trainer.params, self._trainer._rng, self._trainer.drop_path_rates
+            rng, rates = self._trainer._rng, self._trainer.drop_path_rates
         else:
-            if self._train_params is None:
-                self._train_params = torch.empty(int(self._lib.uu3d_num_params(self._h)), dtype=torch.float32, device=self.device)
-                _capi.check(self._lib, self._lib.uu3d_train_init(self._h, C.c_void_p(self._train_params.data_ptr()), stream), self._h)
             if self._rng is None:
                 self._rng = torch.Generator(device=self.device)
                 self._rng.manual_seed(int(self._seed))
-            params, rng, rates = self._train_params, self._rng, np.asarray(a.drop_path_rate, np.float32)
+            rng, rates = self._rng, np.asarray(a.drop_path_rate, np.float32)
         n_draws = a.spatial_depth * 2 * B * a.num_frames + a.temporal_depth * 2 * B
         if float(rates[2]) > 0.0:
             n_draws += len(a.strides) * 2 * B
         u = torch.rand(n_draws, generator=rng, device=self.device, dtype=torch.float32)
-        nbytes = int(self._lib.uu3d_train_workspace_bytes(self._h, B))
-        if self._train_ws is None or self._train_ws.numel() < nbytes:
-            self._train_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         r3 = (C.c_float * 3)(*[float(r) for r in rates])
         tm = torch.rand((B, a.num_frames), generator=rng, device=self.device, dtype=torch.float32) if a.token_mask_rate > 0.0 else None   # u_u_t.py:299
         self._set_dropout(rng)
+        return params, u, r3, tm
+
+    def _training_forward(self, x, stride_mask, full, central):
+        """model(inputs, training=True) (train.py:478): DropPath active, live weights.  Without a Trainer the model keeps
+        its own master buffer (uu3d_train_init) and generator."""
+        torch = self._torch
+        a, B = self.arch, x.shape[0]
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        params, u, r3, tm = self._training_draws(B)
+        nbytes = int(self._lib.uu3d_train_workspace_bytes(self._h, B))
+        if self._train_ws is None or self._train_ws.numel() < nbytes:
+            self._train_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         st = self._lib.uu3d_train_forward_backward_masked(
             self._h, C.c_void_p(params.data_ptr()), C.c_void_p(x.data_ptr()),
             C.c_void_p(stride_mask.data_ptr()) if stride_mask is not None else None, None, B, int(a.batch_size), 0.0, 0.0, 0,
@@ -345,6 +447,42 @@ class UpliftUpsampleTransformer(object):
             None, C.c_void_p(full.data_ptr()) if full is not None else None,
             C.c_void_p(central.data_ptr()), None, C.c_void_p(self._train_ws.data_ptr()), self._train_ws.numel(), stream)
         _capi.check(self._lib, st, self._h)
+
+    # ---- autograd: the training-mode forward with a tape, the backward from the output gradients ------------------------
+    def _tape_forward(self, x, stride_mask):
+        """uu3d_train_forward_tape with this call's draws and a workspace of its own (it holds the saved activations until the
+        tape is freed): returns (full, central, tape holder)."""
+        torch = self._torch
+        a, B = self.arch, x.shape[0]
+        full = torch.empty((B, a.num_frames, a.num_keypoints, 3), dtype=torch.float32, device=self.device)
+        central = torch.empty((B, a.num_keypoints, 3), dtype=torch.float32, device=self.device)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        params, u, r3, tm = self._training_draws(B)
+        ws = torch.empty(int(self._lib.uu3d_train_workspace_bytes(self._h, B)), dtype=torch.uint8, device=self.device)
+        tape = C.c_void_p()
+        st = self._lib.uu3d_train_forward_tape(
+            self._h, C.c_void_p(params.data_ptr()), C.c_void_p(x.data_ptr()),
+            C.c_void_p(stride_mask.data_ptr()) if stride_mask is not None else None, B,
+            r3, C.c_void_p(u.data_ptr()), C.c_void_p(tm.data_ptr()) if tm is not None else None, float(self.arch.token_mask_rate),
+            C.c_void_p(full.data_ptr()), C.c_void_p(central.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(), C.byref(tape), stream)
+        _capi.check(self._lib, st, self._h)
+        return full, central, _Tape(self, tape, (params, x, stride_mask, u, tm, ws))
+
+    def _tape_backward(self, tape, grad_full, grad_central, want_x, want_params):
+        """uu3d_train_backward_tape: (d x or None, d params or None) from the output gradients (None = 0)."""
+        torch = self._torch
+        params, x = tape.keep[0], tape.keep[1]
+        gp = torch.empty_like(params, memory_format=torch.contiguous_format).detach() if want_params else None
+        gx = torch.empty(x.shape, dtype=torch.float32, device=self.device) if want_x else None
+        gF = grad_full.to(torch.float32).contiguous() if grad_full is not None else None
+        gC = grad_central.to(torch.float32).contiguous() if grad_central is not None else None
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None          # noqa: E731
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        st = self._lib.uu3d_train_backward_tape(self._h, tape.handle, ptr(gF), ptr(gC), ptr(gp), ptr(gx), stream)
+        _capi.check(self._lib, st, self._h)
+        if self._trainer is not None:
+            self._trainer._autograd_backward = True
+        return gx, gp
 
     def __call__(self, inputs, training=None, mask=None):
         torch = self._torch
@@ -370,6 +508,8 @@ class UpliftUpsampleTransformer(object):
             if self.return_attention:
                 raise NotImplementedError("return_attention=True with training=True")
             self._flush_assigns()
+            if torch.is_grad_enabled() and (x.requires_grad or self._live_param().requires_grad):
+                return _training_call().apply(self, x, self._live_param(), stride_mask)
             self._training_forward(x, stride_mask, full, central)
             return full, central
         self._sync_from_trainer()
@@ -476,3 +616,49 @@ class UpliftUpsampleTransformer(object):
                 self._h = None
         except Exception:
             pass
+
+
+class _Tape(object):
+    """A tape of the library (uu3d_train_forward_tape) and the buffers its backward reads; freed with the autograd graph."""
+
+    def __init__(self, model, handle, keep):
+        self.lib, self.handle, self.keep = model._lib, handle, keep
+
+    def __del__(self):
+        try:
+            if self.handle:
+                self.lib.uu3d_tape_destroy(self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+
+_TRAINING_CALL = []
+
+
+def _training_call():
+    """The torch.autograd.Function of a training-mode call (built on first use: torch is imported lazily in this module)."""
+    if _TRAINING_CALL:
+        return _TRAINING_CALL[0]
+    import torch
+
+    class TrainingCall(torch.autograd.Function):
+
+        @staticmethod
+        def forward(ctx, model, x, param, stride_mask):
+            full, central, tape = model._tape_forward(x.detach(), stride_mask)
+            ctx.set_materialize_grads(False)                  # a None output gradient reaches the library as NULL
+            ctx.save_for_backward(param)                       # an in-place change before backward() trips torch's version check
+            ctx.model, ctx.tape = model, tape
+            return full, central
+
+        @staticmethod
+        def backward(ctx, grad_full, grad_central):
+            if torch.is_grad_enabled():
+                raise RuntimeError("model(..., training=True): higher-order gradients (create_graph=True) are not supported")
+            ctx.saved_tensors
+            gx, gp = ctx.model._tape_backward(ctx.tape, grad_full, grad_central, ctx.needs_input_grad[1], ctx.needs_input_grad[2])
+            return None, gx, gp, None
+
+    _TRAINING_CALL.append(TrainingCall)
+    return TrainingCall

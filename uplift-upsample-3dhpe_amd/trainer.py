@@ -3,6 +3,14 @@
     trainer = Trainer(model, config)                 # uploads the model's weights into a flat master buffer
     loss = trainer.train_step(kp2d, kp3d, stride_masks, drop_path_uniform=None)   # fwd + bwd + AdamW (+ EMA)
 
+Any PyTorch loss (autograd, the role of tf.GradientTape): ``params`` is the model's parameter and ``grads`` its ``.grad``,
+
+    model.requires_grad_()
+    trainer.zero_grad()
+    full, central = model([x, stride_mask], training=True)
+    my_loss(full, central).backward()                # accumulates into trainer.grads
+    trainer.apply_gradients()                        # AdamW, EMA, skip on non-finite gradients, repack
+
 All arithmetic runs in csrc/libuu3d.so (uu3d_train_forward_backward, uu3d_adamw_update, uu3d_ema_update);
 PyTorch holds the device buffers and, with more than one rank, all-reduces the flat gradient over RCCL.
 """
@@ -29,8 +37,10 @@ class Trainer(object):
         lib = self._lib
         self.n_params = int(lib.uu3d_num_params(model._h))
         dev = model.device
-        self.params = torch.empty(self.n_params, dtype=torch.float32, device=dev)
+        # the model's parameter while this trainer is attached (model.parameters()); loss.backward() accumulates into grads = params.grad
+        self.params = torch.nn.Parameter(torch.empty(self.n_params, dtype=torch.float32, device=dev), requires_grad=False)
         self.grads = torch.zeros(self.n_params, dtype=torch.float32, device=dev)
+        self._autograd_backward = False                      # an autograd backward pass wrote gradients since the last step
         self.loss = torch.zeros(3, dtype=torch.float32, device=dev)
         self._ws = None
         self._ws_batch = 0
@@ -73,6 +83,8 @@ class Trainer(object):
         self._ready_cb = _capi.GRAD_READY_FN(lambda user, first, count, stream: self._buckets.ready(first, count, stream))
         _capi.check(lib, lib.uu3d_train_set_grad_callback(model._h, self._ready_cb, None), model._h)
         model._attach_trainer(self)
+        self.params.grad = self.grads
+        self.params.requires_grad_(model._requires_grad)
 
     def _workspace(self, batch):
         if self._ws is None or batch > self._ws_batch:
@@ -122,6 +134,7 @@ class Trainer(object):
         rates = (C.c_float * 3)(*[float(r) for r in self.drop_path_rates])
         self.last_dropout_seed = self.model._set_dropout(self._rng, dropout_seed)
         self._buckets.begin()                                               # a previous pass without apply_gradients leaves nothing behind
+        self._autograd_backward = False
         st = self._lib.uu3d_train_forward_backward_masked(
             self.model._h, C.c_void_p(self.params.data_ptr()), C.c_void_p(x.data_ptr()), m_ptr, C.c_void_p(gt.data_ptr()), B,
             int(cfg.BATCH_SIZE), float(cfg.LOSS_WEIGHT_CENTER), float(cfg.LOSS_WEIGHT_SEQUENCE), int(cfg.ROOT_KEYTPOINT),
@@ -138,6 +151,15 @@ class Trainer(object):
     def apply_gradients(self):
         """optimizer.apply_gradients (+ EMA), then refresh the operand packs.  With more than one rank the gradient buckets
         were started by forward_backward while the backward pass ran; here the stream only waits for them."""
+        if self._autograd_backward:
+            if self._world() > 1:
+                raise NotImplementedError("apply_gradients after an autograd backward (loss.backward()) with more than one rank: the "
+                                          "gradients of autograd are not all-reduced; use forward_backward / train_step")
+            g = self.params.grad
+            if g is not None and g.data_ptr() != self.grads.data_ptr():      # .grad was replaced (e.g. torch's zero_grad(set_to_none=True))
+                self.grads.copy_(g)
+            self.params.grad = self.grads
+            self._autograd_backward = False
         self._buckets.wait()                                                 # loss normaliser is the GLOBAL batch size: sums, no rescale
         # a backward pass that produced non-finite gradients (loss-scaled f16x3 overflow) leaves weights and moments alone:
         # the flag is read on the device, the host never waits (nonfinite() reads it back for logging).  With several ranks the
@@ -156,7 +178,7 @@ class Trainer(object):
             # OUTPUT_BN: every rank moved the running statistics with ITS shard's batch statistics; the mean over ranks keeps the
             # replicas (and with them inference weights, EMA and the sharded evaluation) identical.  Batch statistics stay per replica.
             import torch.distributed as dist
-            tail = self.params[self.n_trainable:]
+            tail = self.params.detach()[self.n_trainable:]
             dist.all_reduce(tail, op=dist.ReduceOp.SUM, group=self._buckets.group)
             tail.div_(float(world))
         if self.ema is not None:
@@ -165,6 +187,13 @@ class Trainer(object):
         self.global_step += 1
         self.model._weights_dirty = True                                      # the model's host / inference weights are now stale
         self.model._holds_ema = False
+
+    def zero_grad(self):
+        """Before the loss.backward() calls of a custom-loss step: zeroes ``grads`` (the parameter's ``.grad``) and the non-finite
+        word that autograd backward passes raise and apply_gradients reads."""
+        self.grads.zero_()
+        self.params.grad = self.grads
+        _capi.check(self._lib, self._lib.uu3d_train_clear_nonfinite(self.model._h, self._stream()), self.model._h)
 
     def _world(self):
         import torch.distributed as dist
@@ -203,7 +232,7 @@ class Trainer(object):
     def state_dict(self):
         """Everything a resumed run needs to continue bit-identically: master weights, Adam moments, iteration counters,
         EMA weights and the DropPath generator state (host numpy arrays)."""
-        sd = {"params": self.params.cpu().numpy(), "adam_m": self.optimizer.m.cpu().numpy(), "adam_v": self.optimizer.v.cpu().numpy(),
+        sd = {"params": self.params.detach().cpu().numpy(), "adam_m": self.optimizer.m.cpu().numpy(), "adam_v": self.optimizer.v.cpu().numpy(),
               "iterations": np.int64(self.optimizer.iterations), "global_step": np.int64(self.global_step),
               "rng_state": self._rng.get_state().cpu().numpy()}
         if self.ema is not None:
@@ -216,7 +245,8 @@ class Trainer(object):
         torch = self._torch
         if sd["params"].shape != (self.n_params,):
             raise ValueError(f"checkpoint holds {sd['params'].shape[0]} parameters, the model has {self.n_params}")
-        self.params.copy_(torch.from_numpy(np.asarray(sd["params"], np.float32)))
+        with torch.no_grad():
+            self.params.copy_(torch.from_numpy(np.asarray(sd["params"], np.float32)))
         self.optimizer.m.copy_(torch.from_numpy(np.asarray(sd["adam_m"], np.float32)))
         self.optimizer.v.copy_(torch.from_numpy(np.asarray(sd["adam_v"], np.float32)))
         if self.optimizer.amsgrad:
@@ -253,7 +283,7 @@ class Trainer(object):
     def params_dict(self):
         """The live master weights by name (Keras layouts), moving statistics of OUTPUT_BN included."""
         out, o = {}, 0
-        flat = self.params.cpu().numpy()
+        flat = self.params.detach().cpu().numpy()
         for name, shape in self.model._spec:
             n = int(np.prod(shape))
             out[name] = flat[o:o + n].reshape(shape)
