@@ -106,6 +106,9 @@ const char* uu3d_last_error(const uu3d_model* model);
  * block, the full-sequence head.  The generic attention keeps a head in LDS: the FORWARD holds 2 L (d_h + 4) floats (fits every legal shape), the training
  * step's BACKWARD 4 L (d_h + 4) + 2 L (L + 1) floats <= 160 KiB -- i.e. up to 128 frames only for head dims <= 8 (and 48, which has an MFMA backward;
  * 96 with ATTENTION_DROP_RATE > 0), 127 at 12, 124 at 16, 117 at 24, 111 at 32, 90 at 64; uu3d_train_forward_backward refuses longer sequences up front.  Outside that: UU3D_ERR_UNSUPPORTED.
+ * Training-step token limits (every handle): attention layers of head dim 48 without ATTENTION_DROP_RATE train up to 416 tokens -- up to 128
+ * on the register-resident kernels, 129 .. 416 on the tiled exact-f32 pair of csrc/uu3d_attn_long.h (row statistics saved by the forward, P
+ * recomputed by the backward, deterministic); other head dims up to 128 (and the LDS bound above); ATTENTION_DROP_RATE > 0 up to 96.
  */
 int uu3d_create(const uu3d_config* config, int device, uu3d_model** out_model);
 void uu3d_destroy(uu3d_model* model);
@@ -377,7 +380,7 @@ int uu3d_train_forward_backward_masked(uu3d_model* model, const float* params_de
  * GradientTape -- the training step with the loss left to the caller (autograd: `loss.backward()` through model(..., training=True)).
  *   uu3d_train_forward_tape: the training-mode forward of uu3d_train_forward_backward_masked (same arguments, same draws and Dropout)
  *       that keeps its activations in the workspace and returns a tape instead of running a loss.  It makes every up-front check of
- *       the backward pass (token limits, LDS of the backward attention kernels), so the tape's backward is never refused.  The models
+ *       the backward pass (token limits -- 416 at head dim 48, see uu3d_create --, LDS of the backward attention kernels), so the tape's backward is never refused.  The models
  *       the training step refuses are refused with the same messages.
  *   uu3d_train_backward_tape: the backward pass of that forward, seeded with d loss / d full_output (B,N,J,3) and
  *       d loss / d central_output (B,J,3) supplied by the caller (NULL = 0).  grads_dev (uu3d_num_params floats, inventory order) is

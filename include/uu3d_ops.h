@@ -38,11 +38,21 @@ int uu3d_op_ln_bwd(const float* x_dev, const float* dy_dev, const float* stats_d
                    int32_t D, int32_t M, float* dx_dev, int32_t accumulate, float* dgamma_dev, float* dbeta_dev,
                    float* scratch_dev, size_t scratch_floats, void* stream);
 /* softmax attention over rows [q|k|v] (ld floats per row, head h at channels h*dh..), head dim 4 or 48,
- * L <= 128 forward, L <= 96 backward (UU3D_ERR_UNSUPPORTED beyond: P and dS of a head live in LDS) */
+ * L <= 128 forward, L <= 96 backward (UU3D_ERR_UNSUPPORTED beyond: P and dS of a head live in LDS; 129 .. 416 tokens at head
+ * dim 48: uu3d_op_attn_long_fwd / _bwd below) */
 int uu3d_op_attn_fwd(const float* qkv_dev, int32_t ld, int32_t D, int32_t B, int32_t L, int32_t H, int32_t head_dim,
                      const uint8_t* key_mask_dev, float* out_dev, int32_t ldo, void* stream);
 int uu3d_op_attn_bwd(const float* qkv_dev, const float* dout_dev, int32_t ld, int32_t D, int32_t B, int32_t L, int32_t H,
                      int32_t head_dim, const uint8_t* key_mask_dev, float* dqkv_dev, int32_t ldo, void* stream);
+/* The training step's exact-f32 attention for 1 .. 416 tokens, head dim 48 (D == 48 H; UU3D_ERR_UNSUPPORTED otherwise), no attention
+ * Dropout.  Forward: out (row stride ldo) and stats_dev, 2 B H L floats: per (sequence, head, query) row the softmax row max and row
+ * sum, [B][H][L][2].  Backward: dQ, dK, dV into dqkv_dev in the layout and row stride ld of qkv, from out and dout (row stride ldo)
+ * and the forward's stats.  Deterministic: every output element has one writer.  ld and ldo multiples of 4 and every pointer 16-byte
+ * aligned (rows move as 16-byte pieces); UU3D_ERR_INVALID_ARGUMENT otherwise. */
+int uu3d_op_attn_long_fwd(const float* qkv_dev, int32_t ld, int32_t D, int32_t B, int32_t L, int32_t H, const uint8_t* key_mask_dev,
+                          float* out_dev, int32_t ldo, float* stats_dev, void* stream);
+int uu3d_op_attn_long_bwd(const float* qkv_dev, const float* out_dev, const float* dout_dev, const float* stats_dev, int32_t ld, int32_t D,
+                          int32_t B, int32_t L, int32_t H, const uint8_t* key_mask_dev, float* dqkv_dev, int32_t ldo, void* stream);
 size_t uu3d_op_scratch_floats(void);
 
 /* The forward's row-panel path for a LayerNorm-fed Dense layer on its own (csrc/uu3d_gemm_panel.h; in the model:

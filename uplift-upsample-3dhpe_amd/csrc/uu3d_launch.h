@@ -7,6 +7,7 @@
 #include "uu3d_gemm.h"
 #include "uu3d_gemm_h3.h"
 #include "uu3d_bwd.h"
+#include "uu3d_attn_long.h"
 
 namespace uu3d {
 
@@ -242,6 +243,22 @@ inline int launch_attn_generic(bool backward, const float* qkv, const float* dO,
             if (!donef) { (void)hipFuncSetAttribute((const void*)attn_generic_fwd_kernel<48>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); donef = true; }
             hipLaunchKernelGGL(attn_generic_fwd_kernel<48>, grid, block, lds, stream, qkv, ld, D, L, H, mask, out, ldo, 1, total, drop);
         }
+    }
+    return hip_status();
+}
+
+// Exact-f32 attention over 1 .. ATTN_LONG_MAX_L tokens, head dim 48, without attention Dropout (uu3d_attn_long.h): the training step's
+// layers of more than 128 tokens.  Forward: O (row stride ldo) and the row statistics stats[B][H][L] = {max, sum}.  Backward: dQ, dK, dV
+// into dqkv in the layout and row stride ld of qkv, from O and dO (both row stride ldo) and the forward's statistics.
+inline int launch_attn_long(bool backward, const float* qkv, const float* O, const float* dO, const float2* stats, int ld, int D, int B, int L,
+                            int H, const uint8_t* mask, float* out, float2* stats_out, int ldo, hipStream_t stream) {
+    if (B < 1 || H < 1 || L < 1 || L > ATTN_LONG_MAX_L || D != 48 * H) return UU3D_ERR_UNSUPPORTED;
+    const dim3 grid(B * H, (L + 16 * ATTN_LONG_WAVES - 1) / (16 * ATTN_LONG_WAVES)), block(64 * ATTN_LONG_WAVES);
+    if (!backward) {
+        hipLaunchKernelGGL(attn_long_fwd_kernel<48>, grid, block, 0, stream, qkv, ld, D, L, H, mask, out, ldo, stats_out);
+    } else {
+        hipLaunchKernelGGL(attn_long_dq_kernel<48>, grid, block, 0, stream, qkv, O, dO, stats, ld, D, L, H, mask, out, ldo);
+        hipLaunchKernelGGL(attn_long_dkv_kernel<48>, grid, block, 0, stream, qkv, O, dO, stats, ld, D, L, H, mask, out, ldo);
     }
     return hip_status();
 }

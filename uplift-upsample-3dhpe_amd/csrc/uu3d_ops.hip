@@ -9,6 +9,7 @@
 #include "uu3d_launch.h"
 #include "uu3d_gemm_panel.h"
 #include <vector>
+#include <initializer_list>
 
 using namespace uu3d;
 
@@ -65,6 +66,26 @@ int uu3d_op_attn_bwd(const float* qkv, const float* dout, int32_t ld, int32_t D,
     if (!qkv || !dout || !dqkv || L < 1 || (dh != 4 && dh != 48)) return UU3D_ERR_INVALID_ARGUMENT;
     if (L > 96) return UU3D_ERR_UNSUPPORTED;      // P and dS matrices of one head must fit the 160 KiB LDS
     return launch_attn_generic(true, qkv, dout, ld, D, B, L, H, dh, mask, dqkv, ldo, (hipStream_t)stream);
+}
+
+// the kernels move rows as 16-byte pieces (q / k / v, O, dO; statistics as 8-byte pairs): leading dimensions multiples of 4 floats,
+// base pointers 16-byte aligned
+static bool attn_long_aligned(int32_t ld, int32_t ldo, std::initializer_list<const void*> ptrs) {
+    if (ld < 1 || ldo < 1 || (ld & 3) || (ldo & 3)) return false;
+    for (const void* p : ptrs) if ((uintptr_t)p & 15) return false;
+    return true;
+}
+int uu3d_op_attn_long_fwd(const float* qkv, int32_t ld, int32_t D, int32_t B, int32_t L, int32_t H, const uint8_t* mask, float* out,
+                          int32_t ldo, float* stats, void* stream) {
+    if (!qkv || !out || !stats || B < 1 || H < 1 || !attn_long_aligned(ld, ldo, {qkv, out, stats})) return UU3D_ERR_INVALID_ARGUMENT;
+    if (D != 48 * H || L < 1 || L > ATTN_LONG_MAX_L) return UU3D_ERR_UNSUPPORTED;
+    return launch_attn_long(false, qkv, nullptr, nullptr, nullptr, ld, D, B, L, H, mask, out, (float2*)stats, ldo, (hipStream_t)stream);
+}
+int uu3d_op_attn_long_bwd(const float* qkv, const float* out, const float* dout, const float* stats, int32_t ld, int32_t D, int32_t B, int32_t L,
+                          int32_t H, const uint8_t* mask, float* dqkv, int32_t ldo, void* stream) {
+    if (!qkv || !out || !dout || !stats || !dqkv || B < 1 || H < 1 || !attn_long_aligned(ld, ldo, {qkv, out, dout, stats, dqkv})) return UU3D_ERR_INVALID_ARGUMENT;
+    if (D != 48 * H || L < 1 || L > ATTN_LONG_MAX_L) return UU3D_ERR_UNSUPPORTED;
+    return launch_attn_long(true, qkv, out, dout, (const float2*)stats, ld, D, B, L, H, mask, dqkv, nullptr, ldo, (hipStream_t)stream);
 }
 
 // ---- row-panel path of a LayerNorm-fed Dense layer (uu3d_gemm_panel.h) --------------------------------------------
