@@ -408,6 +408,26 @@ int uu3d_train_backward_tape(uu3d_model* model, uu3d_tape* tape, const float* gr
 void uu3d_tape_destroy(uu3d_tape* tape);
 /* Clears the model's non-finite-gradient word on `stream` (what a new accumulation of tape backward passes starts from). */
 int uu3d_train_clear_nonfinite(uu3d_model* model, void* stream);
+/* Copies the model's non-finite-gradient word into the caller's device word out_dev on `stream` (no host synchronisation): what a
+ * data-parallel caller combines over ranks before the guarded optimizer update. */
+int uu3d_train_copy_nonfinite(uu3d_model* model, uint32_t* out_dev, void* stream);
+
+/*
+ * GradientTape over several ranks -- the tape backward for data-parallel training (DDP-like: collectives start while it runs).
+ *   uu3d_train_backward_tape_accumulate: the backward pass of uu3d_train_backward_tape (same tape rules, same kernels, same
+ *       cotangent scaling).  It writes the loss-scaled parameter gradients into grads_scratch_dev (uu3d_num_params floats, contents
+ *       undefined afterwards) and, as each contiguous range of the inventory is final, ADDS that range unscaled into
+ *       grads_accum_dev: grads_accum[i] = grads_accum[i] + g[i] * s, multiply and add rounded separately, so the result is bit for
+ *       bit what uu3d_train_backward_tape's gradients added to grads_accum afterwards give.  A non-finite unscaled gradient or
+ *       cotangent raises the non-finite word as there.  report_ranges != 0: after each range's add the grad-ready callback
+ *       (uu3d_train_set_grad_callback) receives (first, count) and the stream the add ran on, as in uu3d_train_forward_backward;
+ *       the reported ranges tile [0, uu3d_num_params) exactly once per call.  report_ranges == 0: no callback (local accumulation
+ *       of micro-batches).  grad_kp2d_dev as in uu3d_train_backward_tape.  A NULL handle, tape, grads_scratch_dev or
+ *       grads_accum_dev, or the two buffers overlapping, is refused with UU3D_ERR_INVALID_ARGUMENT before anything is enqueued.
+ */
+int uu3d_train_backward_tape_accumulate(uu3d_model* model, uu3d_tape* tape, const float* grad_full_dev, const float* grad_central_dev,
+                                        float* grads_scratch_dev, float* grads_accum_dev, float* grad_kp2d_dev,
+                                        int32_t report_ranges, void* stream);
 
 #ifdef __cplusplus
 }

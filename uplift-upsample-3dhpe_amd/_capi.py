@@ -28,6 +28,7 @@ EXPORTED_SYMBOLS = (
     "uu3d_num_params", "uu3d_train_init", "uu3d_train_repack", "uu3d_train_export",
     "uu3d_train_workspace_bytes", "uu3d_train_forward_backward", "uu3d_train_forward_backward_masked", "uu3d_train_set_grad_callback", "uu3d_train_set_dropout",
     "uu3d_train_forward_tape", "uu3d_train_backward_tape", "uu3d_tape_destroy", "uu3d_train_clear_nonfinite",
+    "uu3d_train_backward_tape_accumulate", "uu3d_train_copy_nonfinite",
 )
 # include/uu3d_ops.h
 OPS_SYMBOLS = (
@@ -175,6 +176,10 @@ def load_library(path=None):
     lib.uu3d_tape_destroy.argtypes = [vp]
     lib.uu3d_train_clear_nonfinite.restype = C.c_int
     lib.uu3d_train_clear_nonfinite.argtypes = [vp, vp]
+    lib.uu3d_train_backward_tape_accumulate.restype = C.c_int
+    lib.uu3d_train_backward_tape_accumulate.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, vp]
+    lib.uu3d_train_copy_nonfinite.restype = C.c_int
+    lib.uu3d_train_copy_nonfinite.argtypes = [vp, vp, vp]
     lib.uu3d_op_scratch_floats.restype = sz
     lib.uu3d_op_scratch_floats.argtypes = []
     lib.uu3d_op_gemm_tn.restype = C.c_int

@@ -443,6 +443,47 @@ scale_flat_kernel(float* __restrict__ x, const long long n, const float s, const
     }
 }
 
+// acc[i] += g[i] * *s_dev over a finished range (uu3d_train_backward_tape_accumulate): the unscaling of scale_flat_kernel and the
+// add of torch's AccumulateGrad in one pass, each rounded on its own, so the sum is bit for bit what unscaling in place and adding
+// afterwards gives.  Contraction is off where the two operations are written: the headers' __fmul_rn / __fadd_rn are plain
+// operators that the default fp-contract would fuse into v_fma across inlining.  A non-finite g * s raises *flag as
+// scale_flat_kernel does.  HBM-bound (three 4-byte streams per element): 16-byte accesses on the aligned body; the scalar head and
+// tail cover ranges that start or end between 16-byte boundaries, and a pair of buffers misaligned against each other runs scalar.
+static __device__ __forceinline__ float add_unscaled(float a, float x, float s, bool& bad)
+{
+#pragma clang fp contract(off)
+    const float v = x * s;                                // (s is a power of two: exact but for subnormal results)
+    bad |= !(fabsf(v) <= 3.4e38f);
+    return a + v;
+}
+
+static __global__ void __launch_bounds__(256)
+scale_accumulate_kernel(float* __restrict__ acc, const float* __restrict__ g, const long long n, const float* __restrict__ s_dev,
+                        unsigned* __restrict__ flag)
+{
+    const float s = *s_dev;
+    const bool vec = (((uintptr_t)acc ^ (uintptr_t)g) & 15) == 0;
+    const long long head = vec ? min(n, (long long)(((16 - ((uintptr_t)acc & 15)) & 15) >> 2)) : n;
+    const long long nv = (n - head) >> 2;                 // 16-byte chunks of the body
+    const long long tail = head + 4 * nv;                 // [0, head) and [tail, n) run scalar
+    const long long stride = (long long)gridDim.x * 256;
+    bool bad = false;
+    f32x4* __restrict__ a4 = reinterpret_cast<f32x4*>(acc + head);
+    const f32x4* __restrict__ g4 = reinterpret_cast<const f32x4*>(g + head);
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nv; i += stride) {
+        const f32x4 x = g4[i];
+        f32x4 a = a4[i];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) a[e] = add_unscaled(a[e], x[e], s, bad);
+        a4[i] = a;
+    }
+    for (long long j = (long long)blockIdx.x * 256 + threadIdx.x; j < head + (n - tail); j += stride) {
+        const long long i = j < head ? j : tail + (j - head);
+        acc[i] = add_unscaled(acc[i], g[i], s, bad);
+    }
+    if (bad) atomicOr(flag, 1u);
+}
+
 // ---- seeding a backward pass from caller-supplied output gradients (uu3d_train_backward_tape) ------------------------------------
 // words[0]: max |g| over both cotangents as the bits of a non-negative float (unsigned order = float order, NaN above +Inf);
 // zeroed by the caller before cot_absmax_kernel, read by cot_seed_kernel, which writes words[1] = scale, words[2] = 1 / scale.

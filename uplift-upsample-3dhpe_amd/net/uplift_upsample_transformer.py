@@ -469,15 +469,20 @@ class UpliftUpsampleTransformer(object):
         return full, central, _Tape(self, tape, (params, x, stride_mask, u, tm, ws))
 
     def _tape_backward(self, tape, grad_full, grad_central, want_x, want_params):
-        """uu3d_train_backward_tape: (d x or None, d params or None) from the output gradients (None = 0)."""
+        """uu3d_train_backward_tape: (d x or None, d params or None) from the output gradients (None = 0).  With a Trainer attached
+        and more than one rank, d params goes straight into the trainer's gradient buffer (Trainer._accumulate_backward: summed over
+        the ranks while the backward pass runs) and None is returned for it."""
         torch = self._torch
         params, x = tape.keep[0], tape.keep[1]
-        gp = torch.empty_like(params, memory_format=torch.contiguous_format).detach() if want_params else None
         gx = torch.empty(x.shape, dtype=torch.float32, device=self.device) if want_x else None
         gF = grad_full.to(torch.float32).contiguous() if grad_full is not None else None
         gC = grad_central.to(torch.float32).contiguous() if grad_central is not None else None
         ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None          # noqa: E731
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        if want_params and self._trainer is not None and self._trainer._world() > 1:
+            self._trainer._accumulate_backward(tape.handle, ptr(gF), ptr(gC), ptr(gx), stream)
+            return gx, None
+        gp = torch.empty_like(params, memory_format=torch.contiguous_format).detach() if want_params else None
         st = self._lib.uu3d_train_backward_tape(self._h, tape.handle, ptr(gF), ptr(gC), ptr(gp), ptr(gx), stream)
         _capi.check(self._lib, st, self._h)
         if self._trainer is not None:

@@ -25,6 +25,7 @@ Results are bit-identical to ONE quiet call under the same schedule (depth 1: th
 schedule, ``model.call_scheduled(inputs, "throughput")`` -- from 1024 token rows on that is the temporal chain, within 3e-5 of ``model(...)``): the
 same launches on the same data, only on another stream.  Latency of ONE batch does not improve (0.9 ms); use ``model(...)`` for that.
 """
+import gc
 import os
 import ctypes as C
 
@@ -137,14 +138,24 @@ class ForwardPipeline(object):
             s.graph, s.done, s.busy, s.n, s.extra = None, torch.cuda.Event(), False, 0, None
             self._slots.append(s)
         if graph:
-            for i, s in enumerate(self._slots):
-                with torch.cuda.stream(s.stream):
-                    self._launch(i, batch)                         # warm-up outside the capture (lazy attribute calls, allocations)
-                s.stream.synchronize()
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, stream=s.stream):
-                    self._launch(i, batch)
-                s.graph = g
+            # A garbage collection inside a capture can finalise unreachable library objects (models, tapes, trainers in reference
+            # cycles), whose hipFree invalidates the capture (global capture mode; torch no longer collects before capturing).
+            # Collect first and keep the collector off while capturing.
+            gc.collect()
+            gc_was_on = gc.isenabled()
+            gc.disable()
+            try:
+                for i, s in enumerate(self._slots):
+                    with torch.cuda.stream(s.stream):
+                        self._launch(i, batch)                     # warm-up outside the capture (lazy attribute calls, allocations)
+                    s.stream.synchronize()
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g, stream=s.stream):
+                        self._launch(i, batch)
+                    s.graph = g
+            finally:
+                if gc_was_on:
+                    gc.enable()
             torch.cuda.synchronize(dev)
 
     def _launch(self, i, n):

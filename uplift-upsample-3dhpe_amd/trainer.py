@@ -11,9 +11,16 @@ Any PyTorch loss (autograd, the role of tf.GradientTape): ``params`` is the mode
     my_loss(full, central).backward()                # accumulates into trainer.grads
     trainer.apply_gradients()                        # AdamW, EMA, skip on non-finite gradients, repack
 
+With more than one rank the same three lines train data-parallel, like DDP but with one difference: rank gradients are SUMMED,
+not averaged, as in the built-in step -- normalise the loss by the GLOBAL ``config.BATCH_SIZE`` (train.py:482,488-489) and the
+ranks reproduce the one-rank step.  The backward pass adds each finished gradient range into ``grads`` and starts its all-reduce
+while the rest of the pass runs; ``with trainer.no_sync():`` accumulates micro-batches locally first (one reporting backward pass
+per step, outside it).
+
 All arithmetic runs in csrc/libuu3d.so (uu3d_train_forward_backward, uu3d_adamw_update, uu3d_ema_update);
 PyTorch holds the device buffers and, with more than one rank, all-reduces the flat gradient over RCCL.
 """
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -41,6 +48,9 @@ class Trainer(object):
         self.params = torch.nn.Parameter(torch.empty(self.n_params, dtype=torch.float32, device=dev), requires_grad=False)
         self.grads = torch.zeros(self.n_params, dtype=torch.float32, device=dev)
         self._autograd_backward = False                      # an autograd backward pass wrote gradients since the last step
+        self._no_sync = 0                                    # depth of `with no_sync():` (world size > 1: local accumulation only)
+        self._reported = False                               # a backward pass of this step reported its ranges (they are all-reduced)
+        self._grad_scratch = None                            # the loss-scaled gradients of an accumulating backward pass
         self.loss = torch.zeros(3, dtype=torch.float32, device=dev)
         self._ws = None
         self._ws_batch = 0
@@ -80,6 +90,7 @@ class Trainer(object):
         self._buckets = BucketedAllReduce(self.grads)
         # world size > 1: the skip decision of a non-finite step is taken on the REDUCED gradients (identical on every rank)
         self._skip_word = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._rank_word = torch.zeros(1, dtype=torch.int32, device=dev)    # this rank's non-finite word (autograd steps, world size > 1)
         self._ready_cb = _capi.GRAD_READY_FN(lambda user, first, count, stream: self._buckets.ready(first, count, stream))
         _capi.check(lib, lib.uu3d_train_set_grad_callback(model._h, self._ready_cb, None), model._h)
         model._attach_trainer(self)
@@ -135,6 +146,7 @@ class Trainer(object):
         self.last_dropout_seed = self.model._set_dropout(self._rng, dropout_seed)
         self._buckets.begin()                                               # a previous pass without apply_gradients leaves nothing behind
         self._autograd_backward = False
+        self._reported = False
         st = self._lib.uu3d_train_forward_backward_masked(
             self.model._h, C.c_void_p(self.params.data_ptr()), C.c_void_p(x.data_ptr()), m_ptr, C.c_void_p(gt.data_ptr()), B,
             int(cfg.BATCH_SIZE), float(cfg.LOSS_WEIGHT_CENTER), float(cfg.LOSS_WEIGHT_SEQUENCE), int(cfg.ROOT_KEYTPOINT),
@@ -150,26 +162,38 @@ class Trainer(object):
 
     def apply_gradients(self):
         """optimizer.apply_gradients (+ EMA), then refresh the operand packs.  With more than one rank the gradient buckets
-        were started by forward_backward while the backward pass ran; here the stream only waits for them."""
+        were started by forward_backward (or the reporting loss.backward()) while the backward pass ran; here the stream only
+        waits for them.  After autograd backward passes that all ran inside no_sync(), the whole buffer is all-reduced here, once."""
+        multi_autograd = self._autograd_backward and self._world() > 1
         if self._autograd_backward:
-            if self._world() > 1:
-                raise NotImplementedError("apply_gradients after an autograd backward (loss.backward()) with more than one rank: the "
-                                          "gradients of autograd are not all-reduced; use forward_backward / train_step")
             g = self.params.grad
             if g is not None and g.data_ptr() != self.grads.data_ptr():      # .grad was replaced (e.g. torch's zero_grad(set_to_none=True))
                 self.grads.copy_(g)
             self.params.grad = self.grads
             self._autograd_backward = False
+        if multi_autograd and not self._reported:
+            # (after taking a replaced .grad: what this rank contributes to the sum is what the user left in .grad)
+            import torch.distributed as dist
+            self._buckets.wait()
+            dist.all_reduce(self.grads, op=dist.ReduceOp.SUM, group=self._buckets.group)
         self._buckets.wait()                                                 # loss normaliser is the GLOBAL batch size: sums, no rescale
         # a backward pass that produced non-finite gradients (loss-scaled f16x3 overflow) leaves weights and moments alone:
         # the flag is read on the device, the host never waits (nonfinite() reads it back for logging).  With several ranks the
         # library's flag only knows THIS rank's gradients, raised before the all-reduce: a rank whose shard was finite would
         # apply the Inf / NaN sum it received and diverge from the one that skipped (ADVICE round 3).  The decision is therefore
         # taken on the reduced buffer, which is bit-identical on every rank: all ranks skip or none does.
+        # After autograd backward passes the cotangents can be non-finite where the gradients are not (a zero loss scale): each
+        # rank's own non-finite word then joins the decision through a MAX over the ranks.
         world = self._world()
         if world > 1:
             torch = self._torch
             self._skip_word.copy_((~torch.isfinite(self.grads).all()).to(torch.int32).reshape(1))
+            if multi_autograd:
+                import torch.distributed as dist
+                _capi.check(self._lib, self._lib.uu3d_train_copy_nonfinite(self.model._h, C.c_void_p(self._rank_word.data_ptr()), self._stream()),
+                            self.model._h)
+                dist.all_reduce(self._rank_word, op=dist.ReduceOp.MAX, group=self._buckets.group)
+                torch.maximum(self._skip_word, self._rank_word, out=self._skip_word)
             flag_ptr = self._skip_word.data_ptr()
         else:
             flag_ptr = self._lib.uu3d_train_nonfinite_flag(self.model._h)
@@ -185,15 +209,60 @@ class Trainer(object):
             optim.ema_update(self.ema, self.params, optim.ema_decay_value(self.config.EMA_DECAY, self.global_step))
         _capi.check(self._lib, self._lib.uu3d_train_repack(self.model._h, C.c_void_p(self.params.data_ptr()), self._stream()), self.model._h)
         self.global_step += 1
+        self._reported = False
         self.model._weights_dirty = True                                      # the model's host / inference weights are now stale
         self.model._holds_ema = False
 
     def zero_grad(self):
         """Before the loss.backward() calls of a custom-loss step: zeroes ``grads`` (the parameter's ``.grad``) and the non-finite
-        word that autograd backward passes raise and apply_gradients reads."""
+        word that autograd backward passes raise and apply_gradients reads, and forgets the gradient buckets of the step."""
+        self._buckets.begin()
+        self._reported = False
         self.grads.zero_()
         self.params.grad = self.grads
         _capi.check(self._lib, self._lib.uu3d_train_clear_nonfinite(self.model._h, self._stream()), self.model._h)
+
+    @contextlib.contextmanager
+    def no_sync(self):
+        """DDP's no_sync(): loss.backward() calls inside only add into this rank's ``grads`` (gradient accumulation over
+        micro-batches); the first one after the block reports its ranges and starts their all-reduce over the ranks, which then sums
+        everything accumulated.  With no reporting pass in a step, apply_gradients all-reduces the buffer once.  After the reporting pass
+        the buffer holds the sum over the ranks: any further backward pass in that step, inside no_sync() or not, raises.  World size 1:
+        no effect."""
+        self._no_sync += 1
+        try:
+            yield
+        finally:
+            self._no_sync -= 1
+
+    def _accumulate_backward(self, tape, grad_full, grad_central, grad_kp2d, stream):
+        """The backward pass of one tape with more than one rank (uu3d_train_backward_tape_accumulate): every finished range of the
+        parameter gradient is added into ``grads``; outside no_sync() it is also handed to the bucketed all-reduce as it completes.
+        Returns once the stream has been made to wait for the collectives: ``.grad`` then holds the sum over the ranks, as with DDP."""
+        torch = self._torch
+        report = self._no_sync == 0
+        if self._reported:
+            raise RuntimeError("a loss.backward() after the reporting one (the first outside no_sync()) in one step: the gradients were "
+                               "already summed over the ranks and would be added to that sum locally; run the earlier passes inside "
+                               "trainer.no_sync(), or call apply_gradients() / zero_grad() first")
+        g = self.params.grad
+        if g is None:                                  # torch's zero_grad(set_to_none=True): a fresh accumulation
+            self.grads.zero_()
+        elif g.data_ptr() != self.grads.data_ptr():    # .grad replaced since the last pass: the accumulation continues from it
+            self.grads.copy_(g)
+        self.params.grad = self.grads
+        if self._grad_scratch is None:
+            self._grad_scratch = torch.empty(self.n_params, dtype=torch.float32, device=self.model.device)
+        if report:
+            self._buckets.begin()
+        st = self._lib.uu3d_train_backward_tape_accumulate(self.model._h, tape, grad_full, grad_central,
+                                                           C.c_void_p(self._grad_scratch.data_ptr()), C.c_void_p(self.grads.data_ptr()),
+                                                           grad_kp2d, int(report), stream)
+        _capi.check(self._lib, st, self.model._h)
+        self._autograd_backward = True
+        if report:
+            self._reported = True
+            self._buckets.wait()                       # (raises what the grad-ready callback caught; checks that the ranges tiled the buffer)
 
     def _world(self):
         import torch.distributed as dist
