@@ -238,6 +238,42 @@ int uu3d_forward_ex(uu3d_model* model, const float* kp2d_dev, const uint8_t* str
 int uu3d_set_schedule(uu3d_model* model, int32_t schedule);
 
 /*
+ * FRAMES FORM of the forward (evaluation over overlapping windows; compiled dims only -- handles with generic dims return
+ * UU3D_ERR_UNSUPPORTED).  The spatial stack and spatial_to_temporal_fc work on one frame at a time: a frame's d_t features do not depend
+ * on the window it sits in, only the token blend and the temporal PE that follow do.  So features are computed once per frame and every
+ * window reads them from a table:
+ *
+ *   uu3d_frame_features(model, frames_dev (F, J, 2) f32, F, features_dev (F, d_t) f32, workspace, bytes, schedule, stream)
+ *       the spatial stack and spatial_to_temporal_fc with its bias on F frames -- no blend, no PE.  The kernel choice of the forward
+ *       (f16x3 / exact-f32 spatial kernel by frame count, f16 operand planes of the s2t GEMM); UU3D_SCHEDULE_EXACT_F32 in `schedule` runs
+ *       the exact-f32 kernels.  In f16x3 non-finite features set the model's sticky range word (RANGE CONTRACT above).
+ *       The workspace (256-byte aligned) holds uu3d_frame_features_bytes(model, F) bytes.
+ *   uu3d_gather_window_frames(video_start_dev, video_len_dev, windows_dev (B) uu3d_window, B, N, pad_edge, zero_masked, frame_base, zero_row,
+ *                             rows_dev (B, N) int32, stride_mask_dev (B, N), pad_mask_dev (B, N) or NULL, stream)
+ *       the windows of uu3d_gather_windows with exactly its frame and mask rules (one device helper states them for both kernels), but
+ *       a feature-table row per token instead of coordinates: -1 where zero_masked is set and the stride mask drops the token (the forward
+ *       writes the masked token), zero_row where zero padding reads no frame (the caller stores the features of an all-zero frame there),
+ *       else video_start[video] + source frame (the edge frame for copy padding), + frame_base for a flipped window (the flipped half of
+ *       the table: features of frames flipped like the window).  video_start may be shifted so that a table covers part of a pose table.
+ *   uu3d_forward_frames_ex(model, features_dev (R, d_t) f32, R, rows_dev (B, N) int32, stride_mask_dev, B, full_out, central_out,
+ *                          attention_out, workspace, bytes, schedule, stream)
+ *       the forward of uu3d_forward_ex from its stage 3 on (temporal chain under the throughput schedule, attention_out, the range check,
+ *       UU3D_SCHEDULE_EXACT_F32 -- one shared body), its input x = (masked ? token : features[rows]) + temporal PE written by one kernel.
+ *       features_dev 16-byte aligned; a real token whose row is outside [0, R) comes out NaN and trips the range check.  Workspace:
+ *       uu3d_workspace_bytes(batch).  Capturable into a hipGraph like uu3d_forward_ex.
+ * Results agree with uu3d_forward_ex on the same windows to ~3e-5 (the s2t GEMM sums in another split-K order at another row count).
+ */
+size_t uu3d_frame_features_bytes(const uu3d_model* model, int32_t frames);
+int uu3d_frame_features(uu3d_model* model, const float* frames_dev, int32_t frames, float* features_dev, void* workspace_dev,
+                        size_t workspace_bytes, int32_t schedule, void* stream);
+int uu3d_gather_window_frames(const int64_t* video_start_dev, const int32_t* video_len_dev, const uu3d_window* windows_dev,
+                              int32_t batch, int32_t num_frames, int32_t pad_edge, int32_t zero_masked, int64_t frame_base, int64_t zero_row,
+                              int32_t* rows_dev, uint8_t* stride_mask_dev, uint8_t* pad_mask_dev, void* stream);
+int uu3d_forward_frames_ex(uu3d_model* model, const float* features_dev, int64_t num_rows, const int32_t* rows_dev,
+                           const uint8_t* stride_mask_dev, int32_t batch, float* full_out_dev, float* central_out_dev,
+                           float* const* attention_out, void* workspace_dev, size_t workspace_bytes, int32_t schedule, void* stream);
+
+/*
  * Per-kernel timing of the next uu3d_forward calls with HIP events on the launch stream.
  * When enabled, uu3d_forward records an event pair around every launch; uu3d_profile_read
  * synchronises those events and returns the per-launch records of the LAST forward.

@@ -29,6 +29,7 @@ EXPORTED_SYMBOLS = (
     "uu3d_train_workspace_bytes", "uu3d_train_forward_backward", "uu3d_train_forward_backward_masked", "uu3d_train_set_grad_callback", "uu3d_train_set_dropout",
     "uu3d_train_forward_tape", "uu3d_train_backward_tape", "uu3d_tape_destroy", "uu3d_train_clear_nonfinite",
     "uu3d_train_backward_tape_accumulate", "uu3d_train_copy_nonfinite",
+    "uu3d_frame_features_bytes", "uu3d_frame_features", "uu3d_gather_window_frames", "uu3d_forward_frames_ex",
 )
 # include/uu3d_ops.h
 OPS_SYMBOLS = (
@@ -128,6 +129,14 @@ def load_library(path=None):
     lib.uu3d_mpjpe.argtypes = [vp, vp, i32, i32, i32, vp, vp]
     lib.uu3d_gather_windows.restype = C.c_int
     lib.uu3d_gather_windows.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp]
+    lib.uu3d_frame_features_bytes.restype = sz
+    lib.uu3d_frame_features_bytes.argtypes = [vp, i32]
+    lib.uu3d_frame_features.restype = C.c_int
+    lib.uu3d_frame_features.argtypes = [vp, vp, i32, vp, vp, sz, i32, vp]
+    lib.uu3d_gather_window_frames.restype = C.c_int
+    lib.uu3d_gather_window_frames.argtypes = [vp, vp, vp, i32, i32, i32, i32, i64, i64, vp, vp, vp, vp]
+    lib.uu3d_forward_frames_ex.restype = C.c_int
+    lib.uu3d_forward_frames_ex.argtypes = [vp, vp, i64, vp, vp, i32, vp, vp, C.POINTER(vp), vp, sz, i32, vp]
     lib.uu3d_world_to_cam_2d.restype = C.c_int
     lib.uu3d_world_to_cam_2d.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
     lib.uu3d_set_schedule.restype = C.c_int

@@ -1337,8 +1337,14 @@ int uu3d_forward_attention(uu3d_model* m, const float* kp2d, const uint8_t* mask
                            m->throughput ? UU3D_SCHEDULE_THROUGHPUT : UU3D_SCHEDULE_LATENCY, stream_);
 }
 
-int uu3d_forward_ex(uu3d_model* m, const float* kp2d, const uint8_t* mask, int32_t B, float* full_out,
-                    float* central_out, float* const* attn_out, void* workspace, size_t workspace_bytes, int32_t schedule, void* stream_) {
+namespace {
+// The input of uu3d_forward_frames_ex: the spatial stack's output per frame (uu3d_frame_features) and a table row per token.
+struct FramesIn { const float* features; long num_rows; const int32_t* rows; };
+
+// The forward of uu3d_forward_ex and uu3d_forward_frames_ex: stages 1-2 from the 2D windows (kp2d) or from a feature table (frames),
+// everything from the temporal blocks on shared.
+int forward_impl(uu3d_model* m, const float* kp2d, const FramesIn* frames, const uint8_t* mask, int32_t B, float* full_out,
+                 float* central_out, float* const* attn_out, void* workspace, size_t workspace_bytes, int32_t schedule, void* stream_) {
     if (!m) return UU3D_ERR_INVALID_ARGUMENT;
     const bool exact_f32 = (schedule & UU3D_SCHEDULE_EXACT_F32) != 0;
     schedule &= ~UU3D_SCHEDULE_EXACT_F32;
@@ -1353,7 +1359,12 @@ int uu3d_forward_ex(uu3d_model* m, const float* kp2d, const uint8_t* mask, int32
     if (parts_ok) schedule &= ~0x600;
     if (schedule != UU3D_SCHEDULE_LATENCY && schedule != UU3D_SCHEDULE_THROUGHPUT) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "schedule must be UU3D_SCHEDULE_LATENCY or UU3D_SCHEDULE_THROUGHPUT");
     if (!m->committed) return fail(m, UU3D_ERR_NOT_READY, "uu3d_commit_weights has not been called");
-    if (!kp2d || !central_out || !workspace || B < 1) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "null buffer or batch < 1");
+    if ((!kp2d && !frames) || !central_out || !workspace || B < 1) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "null buffer or batch < 1");
+    if (frames != nullptr) {
+        if (m->generic) return fail(m, UU3D_ERR_UNSUPPORTED, "uu3d_forward_frames_ex: handles with generic dims have no frames form (compiled dims only)");
+        if (!frames->features || !frames->rows || frames->num_rows < 1) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_forward_frames_ex: null features / rows or no feature rows");
+        if (((uintptr_t)frames->features & 15) != 0 || (m->cfg.d_temporal % 4) != 0) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_forward_frames_ex: features must be 16-byte aligned");
+    }
     uu3d_config c = m->cfg;                                // (a copy: UU3D_SCHEDULE_EXACT_F32 changes THIS call's arithmetic, not the handle's)
     if (exact_f32) {
         if (m->generic) return fail(m, UU3D_ERR_UNSUPPORTED, "UU3D_SCHEDULE_EXACT_F32: handles with generic dims have no exact-f32 forward");
@@ -1388,11 +1399,18 @@ int uu3d_forward_ex(uu3d_model* m, const float* kp2d, const uint8_t* mask, int32
     const int M = B * N;
     char nm[48];
 
+    // 1-2 from a feature table (uu3d_forward_frames_ex): the token blend and the temporal PE, nothing else
+    if (frames != nullptr && !part_tail) {
+        Lh.begin("frames_to_tokens", "frames_to_tokens", 0.0, 4.0 * 3.0 * M * dt);
+        hipLaunchKernelGGL(frames_to_tokens_kernel, dim3((unsigned)(((size_t)M * (dt / 4) + 255) / 256)), dim3(256), 0, Lh.stream,
+                           frames->features, frames->num_rows, frames->rows, mask, m->token, m->pe_t, (long)M, N, dt, w.X);
+        Lh.end();
+    }
     // 1. spatial stack
     // the f16x3 spatial kernel writes its output as the two f16 planes spatial_to_temporal_fc reads (LDS-DMA GEMM, no split in
     // the GEMM's loader): 32.6 -> 29.6 us for the GEMM, the spatial kernel unchanged (round 1's kernel paid 1-2 us for the split stores)
     const bool s2t_planes = !m->no_planes && c.precision == UU3D_PREC_F16X3 && !m->spatial_valu && !m->spatial_f32 && (m->spatial_h3_always || spatial_h3_pays(B * c.num_frames)) && ((c.num_keypoints * c.d_spatial) % 32 == 0);
-    if (!part_tail) {
+    if (frames == nullptr && !part_tail) {
         SpatialParams sp = m->sp;
         sp.total_frames = M;
         sp.frame_list = nullptr;
@@ -1430,7 +1448,7 @@ int uu3d_forward_ex(uu3d_model* m, const float* kp2d, const uint8_t* mask, int32
         }
     }
     // 2. spatial_to_temporal_fc + token blend + temporal PE
-    if (!part_tail) {
+    if (frames == nullptr && !part_tail) {
         EpSpatialToTemporal ep{w.X, m->s2t_b, dt, mask, m->token, m->pe_t, N};
         if (s2t_planes) {
             Lh.gemm_g("s2t", GLoadPlain{reinterpret_cast<const _Float16*>(w.S), reinterpret_cast<const _Float16*>(w.S) + (size_t)M * J * ds, J * ds, M}, m->s2t_wt, M, dt, J * ds, ep);
@@ -1637,6 +1655,104 @@ int uu3d_forward_ex(uu3d_model* m, const float* kp2d, const uint8_t* mask, int32
     if (Lh.status != UU3D_OK) return Lh.status;
     return UU3D_OK;
 }
+}  // namespace
+
+int uu3d_forward_ex(uu3d_model* m, const float* kp2d, const uint8_t* mask, int32_t B, float* full_out,
+                    float* central_out, float* const* attn_out, void* workspace, size_t workspace_bytes, int32_t schedule, void* stream_) {
+    return forward_impl(m, kp2d, nullptr, mask, B, full_out, central_out, attn_out, workspace, workspace_bytes, schedule, stream_);
+}
+
+int uu3d_forward_frames_ex(uu3d_model* m, const float* features, int64_t num_rows, const int32_t* rows, const uint8_t* mask, int32_t B,
+                           float* full_out, float* central_out, float* const* attn_out, void* workspace, size_t workspace_bytes,
+                           int32_t schedule, void* stream_) {
+    if (!m) return UU3D_ERR_INVALID_ARGUMENT;
+    const FramesIn fin{features, (long)num_rows, rows};
+    return forward_impl(m, nullptr, &fin, mask, B, full_out, central_out, attn_out, workspace, workspace_bytes, schedule, stream_);
+}
+
+// ---- per-frame features (spatial stack + spatial_to_temporal_fc, no blend, no PE) ---------------
+namespace {
+struct FrameWorkspace { float *S, *slab; size_t slab_floats, bytes; };
+FrameWorkspace carve_frames(const uu3d_model* m, long F, char* base) {
+    const uu3d_config& c = m->cfg;
+    size_t off = 0;
+    auto take = [&](size_t n) { size_t o = off; off = align_up(off + n, 256); return o; };
+    FrameWorkspace w{};
+    const size_t oS = take((size_t)F * c.num_keypoints * c.d_spatial * 4);
+    w.slab_floats = (size_t)1536 * 4096;                           // split-K partial sums of the s2t GEMM (as carve())
+    const size_t oSl = take(w.slab_floats * 4);
+    w.bytes = off;
+    if (base) { w.S = (float*)(base + oS); w.slab = (float*)(base + oSl); }
+    return w;
+}
+}  // namespace
+
+size_t uu3d_frame_features_bytes(const uu3d_model* m, int32_t frames) {
+    if (!m || frames < 1 || m->generic) return 0;
+    return carve_frames(m, frames, nullptr).bytes;
+}
+
+int uu3d_frame_features(uu3d_model* m, const float* frames_dev, int32_t F, float* features, void* workspace, size_t workspace_bytes,
+                        int32_t schedule, void* stream_) {
+    if (!m) return UU3D_ERR_INVALID_ARGUMENT;
+    const bool exact_f32 = (schedule & UU3D_SCHEDULE_EXACT_F32) != 0;
+    schedule &= ~UU3D_SCHEDULE_EXACT_F32;
+    if (schedule != UU3D_SCHEDULE_LATENCY && schedule != UU3D_SCHEDULE_THROUGHPUT) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "schedule must be UU3D_SCHEDULE_LATENCY or UU3D_SCHEDULE_THROUGHPUT");
+    if (m->generic) return fail(m, UU3D_ERR_UNSUPPORTED, "uu3d_frame_features: handles with generic dims have no frames form (compiled dims only)");
+    if (!m->committed) return fail(m, UU3D_ERR_NOT_READY, "uu3d_commit_weights has not been called");
+    if (!frames_dev || !features || !workspace || F < 1) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "null buffer or frames < 1");
+    if ((long)F * m->cfg.num_keypoints > (1L << 30)) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "too many frames");
+    if (((uintptr_t)workspace & 255) != 0) return fail(m, UU3D_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+    const FrameWorkspace w = carve_frames(m, F, (char*)workspace);
+    if (workspace_bytes < w.bytes) return fail(m, UU3D_ERR_WORKSPACE, "workspace smaller than uu3d_frame_features_bytes(frames)");
+    uu3d_config c = m->cfg;
+    if (exact_f32) c.precision = UU3D_PREC_F32;
+    HIPCHK(m, hipSetDevice(m->device));
+    Launcher Lh{m, (hipStream_t)stream_, w.slab, w.slab_floats, schedule == UU3D_SCHEDULE_THROUGHPUT, c.precision};
+    m->prof_used = 0;
+    const int J = c.num_keypoints, ds = c.d_spatial, dt = c.d_temporal;
+    const int M = F;
+    // the kernel choice of forward_impl's stages 1-2, on a list of frames instead of B windows of N
+    const bool h3 = c.precision == UU3D_PREC_F16X3 && !m->spatial_valu && !m->spatial_f32 && (m->spatial_h3_always || spatial_h3_pays(M));
+    const bool s2t_planes = h3 && !m->no_planes && ((J * ds) % 32 == 0);
+    SpatialParams sp = m->sp;
+    sp.total_frames = M;
+    sp.frame_list = nullptr;
+    const double fl = (double)M * (2.0 * J * 2 * ds + c.spatial_depth * (4.0 * 2 * J * ds * ds + 8.0 * 4 * J * J * (ds / 8) + 2.0 * 2 * J * ds * kHS));
+    if (m->spatial_valu) {
+        constexpr int FPW = 256 / kJ;
+        sp.blocks = m->sp_blocks_v1;
+        auto kern = spatial_stack_kernel<kJ, kDS, kHS, kHeads>;
+        static bool attr_done = false;
+        if (!attr_done) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)spatial_lds_bytes(kDS)); attr_done = true; }
+        Lh.begin("spatial_stack", "spatial_valu", fl, 4.0 * M * J * (2.0 + ds));
+        hipLaunchKernelGGL(kern, dim3((M + FPW - 1) / FPW), dim3(256), spatial_lds_bytes(kDS), Lh.stream, frames_dev, sp, w.S);
+        Lh.end();
+    } else if (h3) {
+        sp.blocks = m->sp_blocks_v2;
+        auto kern = spatial_stack_h3_kernel<kJ, kFR, kSpatialMT>;
+        Lh.begin("spatial_stack", "spatial_h3", fl, 4.0 * M * J * (2.0 + ds));
+        hipLaunchKernelGGL(kern, dim3((M + kFR - 1) / kFR), dim3(64 * (2 / kSpatialMT)), sh3::lds_bytes(), Lh.stream, frames_dev, sp,
+                           m->harena + m->sp_frag_off, w.S, s2t_planes ? reinterpret_cast<_Float16*>(w.S) : (_Float16*)nullptr,
+                           s2t_planes ? reinterpret_cast<_Float16*>(w.S) + (size_t)M * J * ds : (_Float16*)nullptr, SpatialTrainIO{});
+        Lh.end();
+    } else {
+        sp.blocks = m->sp_blocks_v2;
+        auto kern = spatial_stack_mfma_kernel<kJ, kFR>;
+        Lh.begin("spatial_stack", "spatial_mfma", fl, 4.0 * M * J * (2.0 + ds));
+        hipLaunchKernelGGL(kern, dim3((M + kFR - 1) / kFR), dim3(64), spatial_v2_lds_bytes(), Lh.stream, frames_dev, sp, w.S);
+        Lh.end();
+    }
+    const EpBias ep{features, m->s2t_b, dt};
+    if (s2t_planes) Lh.gemm_g("s2t", GLoadPlain{reinterpret_cast<const _Float16*>(w.S), reinterpret_cast<const _Float16*>(w.S) + (size_t)M * J * ds, J * ds, M}, m->s2t_wt, M, dt, J * ds, ep);
+    else { ALoadPlain al{w.S, J * ds, M, J * ds}; Lh.gemm("s2t", al, m->s2t_wt, M, dt, J * ds, ep); }
+    if (c.precision == UU3D_PREC_F16X3) {           // range guard (include/uu3d.h): non-finite features set the model's sticky word
+        Lh.begin("range_check", "range_check", 0.0, 4.0 * (double)M * dt);
+        hipLaunchKernelGGL(range_check_kernel, dim3(256), dim3(256), 0, Lh.stream, features, (long)M * dt, features, 0L, m->d_range);
+        Lh.end();
+    }
+    return Lh.status;
+}
 
 int uu3d_range_status(uu3d_model* m, void* stream, int32_t* out_flag) {
     if (!m) return UU3D_ERR_INVALID_ARGUMENT;
@@ -1667,6 +1783,18 @@ int uu3d_gather_windows(const float* poses, const int64_t* video_start, const in
     hipLaunchKernelGGL(gather_windows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        poses, video_start, video_len, reinterpret_cast<const WindowDesc*>(windows), flip_order,
                        B, N, J, Cc, pad_edge, zero_masked, out, stride_mask, pad_mask);
+    return hipGetLastError() == hipSuccess ? UU3D_OK : UU3D_ERR_HIP;
+}
+
+int uu3d_gather_window_frames(const int64_t* video_start, const int32_t* video_len, const uu3d_window* windows, int32_t B, int32_t N,
+                              int32_t pad_edge, int32_t zero_masked, int64_t frame_base, int64_t zero_row, int32_t* rows,
+                              uint8_t* stride_mask, uint8_t* pad_mask, void* stream) {
+    if (!video_start || !video_len || !windows || !rows || !stride_mask || B < 1 || N < 1 || frame_base < 0 || zero_row < 0 || zero_row > INT32_MAX)
+        return UU3D_ERR_INVALID_ARGUMENT;
+    const long total = (long)B * N;
+    hipLaunchKernelGGL(gather_window_frames_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       video_start, video_len, reinterpret_cast<const WindowDesc*>(windows), B, N, pad_edge, zero_masked,
+                       frame_base, zero_row, rows, stride_mask, pad_mask);
     return hipGetLastError() == hipSuccess ? UU3D_OK : UU3D_ERR_HIP;
 }
 

@@ -207,6 +207,25 @@ compact_frames_kernel(const uint8_t* __restrict__ mask, const int total, int* __
 // multiple of the stride in training, :386-392).  zero_masked also applies x * stride_mask (eval.py:67, train.py:474).
 // flip: joints permuted by flip_order, channel 0 negated (:403-407).  One thread per (window, frame, joint).
 struct WindowDesc { int32_t video, center, stride, mask_stride, mask_shift, flip; };
+// Token n of window d: which frame of its video it reads and how it is masked -- the one statement of these rules, shared by
+// gather_windows_kernel (coordinates) and gather_window_frames_kernel (feature-table rows) so that the two cannot drift.
+//   src: the frame read (the token's own frame f when inside, else the nearest sampled in-range frame); inside: 0 <= f < len;
+//   have: a frame is read at all (inside, or copy padding with an in-range source); sm: the stride mask bit.
+struct WindowFrame { int src; bool inside, have, sm; };
+__device__ __forceinline__ WindowFrame window_frame(const WindowDesc& d, const int len, const int N, const int n, const int pad_edge)
+{
+    WindowFrame t;
+    const int f = d.center - ((N - 1) * d.stride) / 2 + n * d.stride;
+    t.src = f;
+    if (f < 0) t.src = f + ((-f + d.stride - 1) / d.stride) * d.stride;                 // first sampled frame >= 0
+    else if (f >= len) t.src = f - ((f - len + d.stride) / d.stride) * d.stride;        // last sampled frame < len
+    t.inside = (f >= 0) && (f < len);
+    t.have = t.inside || (pad_edge != 0 && t.src >= 0 && t.src < len);
+    const int rel = (n - N / 2) * d.stride + d.mask_shift;
+    int mod = rel % d.mask_stride; if (mod < 0) mod += d.mask_stride;                   // python's % on negative numbers
+    t.sm = (mod == 0);
+    return t;
+}
 static __global__ void __launch_bounds__(256)
 gather_windows_kernel(const float* __restrict__ poses, const int64_t* __restrict__ video_start, const int32_t* __restrict__ video_len,
                       const WindowDesc* __restrict__ win, const int32_t* __restrict__ flip_order,
@@ -219,29 +238,67 @@ gather_windows_kernel(const float* __restrict__ poses, const int64_t* __restrict
     const int n = (int)((idx / J) % N);
     const int w = (int)(idx / ((long)J * N));
     const WindowDesc d = win[w];
-    const int len = video_len[d.video];
-    const int f = d.center - ((N - 1) * d.stride) / 2 + n * d.stride;
-    int src = f;
-    if (f < 0) src = f + ((-f + d.stride - 1) / d.stride) * d.stride;                   // first sampled frame >= 0
-    else if (f >= len) src = f - ((f - len + d.stride) / d.stride) * d.stride;          // last sampled frame < len
-    const bool inside = (f >= 0) && (f < len);
-    const bool have = inside || (pad_edge != 0 && src >= 0 && src < len);
-    const int rel = (n - N / 2) * d.stride + d.mask_shift;
-    int mod = rel % d.mask_stride; if (mod < 0) mod += d.mask_stride;                   // python's % on negative numbers
-    const bool sm = (mod == 0);
+    const WindowFrame t = window_frame(d, video_len[d.video], N, n, pad_edge);
+    const bool sm = t.sm;
     if (j == 0) {
         stride_mask[(long)w * N + n] = sm ? 1 : 0;
-        if (pad_mask != nullptr) pad_mask[(long)w * N + n] = inside ? 1 : 0;
+        if (pad_mask != nullptr) pad_mask[(long)w * N + n] = t.inside ? 1 : 0;
     }
     const int js = (d.flip && flip_order != nullptr) ? flip_order[j] : j;
-    const float* p = poses + ((video_start[d.video] + (have ? src : 0)) * J + js) * C;
+    const float* p = poses + ((video_start[d.video] + (t.have ? t.src : 0)) * J + js) * C;
     float* o = out + idx * C;
-    const bool keep = have && (!zero_masked || sm);
+    const bool keep = t.have && (!zero_masked || sm);
     for (int c = 0; c < C; ++c) {
         float v = keep ? p[c] : 0.f;
         if (c == 0 && d.flip) v = -v;
         o[c] = v;
     }
+}
+
+// The same windows as rows of a per-frame feature table (uu3d_gather_window_frames, include/uu3d.h): one thread per (window, token).
+// rows = -1 where the stride mask drops the token and zero_masked is set (the forward writes the masked token there), zero_row where no
+// frame is read (zero padding: the features of an all-zero frame), else video_start[video] + src, + frame_base for a flipped window.
+static __global__ void __launch_bounds__(256)
+gather_window_frames_kernel(const int64_t* __restrict__ video_start, const int32_t* __restrict__ video_len, const WindowDesc* __restrict__ win,
+                            const int B, const int N, const int pad_edge, const int zero_masked, const int64_t frame_base, const int64_t zero_row,
+                            int32_t* __restrict__ rows, uint8_t* __restrict__ stride_mask, uint8_t* __restrict__ pad_mask)
+{
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long)B * N) return;
+    const int n = (int)(idx % N);
+    const int w = (int)(idx / N);
+    const WindowDesc d = win[w];
+    const WindowFrame t = window_frame(d, video_len[d.video], N, n, pad_edge);
+    stride_mask[idx] = t.sm ? 1 : 0;
+    if (pad_mask != nullptr) pad_mask[idx] = t.inside ? 1 : 0;
+    int64_t r;
+    if (zero_masked && !t.sm) r = -1;
+    else if (!t.have) r = zero_row;
+    else r = video_start[d.video] + t.src + (d.flip ? frame_base : 0);
+    rows[idx] = (int32_t)r;
+}
+
+// Stage 2 of uu3d_forward_frames_ex: x[row] = (masked ? token : features[rows[row]]) + pe[row % N] -- the blend and PE of EpSpatialToTemporal with
+// the spatial stack's output read from a per-frame table.  One thread per 4 floats (16-byte loads and stores; D % 4 == 0).  A real token whose
+// row lies outside [0, num_rows) gets NaN: the range check at the end of the forward reports it instead of a read out of bounds.
+static __global__ void __launch_bounds__(256)
+frames_to_tokens_kernel(const float* __restrict__ feat, const long num_rows, const int32_t* __restrict__ rows, const uint8_t* __restrict__ mask,
+                        const float* __restrict__ token, const float* __restrict__ pe, const long M, const int N, const int D, float* __restrict__ x)
+{
+    const int q = D / 4;
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= M * q) return;
+    const long r = idx / q;
+    const int c = (int)(idx - r * q) * 4;
+    const float4 p = *reinterpret_cast<const float4*>(pe + (size_t)(r % N) * D + c);
+    float4 v;
+    if (mask != nullptr && mask[r] == 0) v = *reinterpret_cast<const float4*>(token + c);
+    else {
+        const long fr = rows[r];
+        if (fr >= 0 && fr < num_rows) v = *reinterpret_cast<const float4*>(feat + (size_t)fr * D + c);
+        else v = make_float4(__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf(""), __builtin_nanf(""));
+    }
+    *reinterpret_cast<float4*>(x + (size_t)r * D + c) = make_float4(v.x + p.x, v.y + p.y, v.z + p.z, v.w + p.w);
 }
 
 // World -> camera -> 2D of every joint of a batch of windows, one camera per window: the device form of

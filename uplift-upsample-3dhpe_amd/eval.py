@@ -42,7 +42,171 @@ def needed_windows(frame_indices, config):
     return np.equal(np.mod(idx, stride), 0)
 
 
-def predict_windows(model, generator, descriptors, config, batch_size, flip=True, depth=None, graph=True):
+# reuse_frames=True: upper bound of the per-frame feature table (d_t float32 per row) that predict_windows keeps on the device; the windows
+# are run in chunks whose frames fit (h36m, d_t = 384: ~350 k frame rows per chunk, plain and flipped together)
+FRAME_TABLE_BYTES = 1 << 30
+
+
+def window_frames(desc, seq_len, starts, lens, pad_edge, zero_masked=True):
+    """The frames a set of window descriptors (W, 6) reads, by the rules of uu3d_gather_windows / uu3d_gather_window_frames (a numpy
+    restatement of ``window_frame`` in csrc/uu3d_misc.h): (plain, flipped, zero) = sorted unique pose-table rows (``starts[video] + frame``)
+    read by unflipped / flipped windows, and whether some token reads no frame at all (zero padding: the all-zero frame).  Tokens that the
+    stride mask drops are not read when ``zero_masked`` (they become the masked token)."""
+    d = np.asarray(desc, np.int64).reshape(-1, 6)
+    N = int(seq_len)
+    starts, lens = np.asarray(starts, np.int64), np.asarray(lens, np.int64)
+    plain, flipped, zero = [], [], False
+    for lo in range(0, len(d), 4096):                                  # (W x N index arrays: bounded)
+        b = d[lo:lo + 4096]
+        v, c, s, ms, sh, fl = (b[:, k:k + 1] for k in range(6))
+        n = np.arange(N, dtype=np.int64)[None, :]
+        f = c - ((N - 1) * s) // 2 + n * s
+        ln = lens[v]
+        src = np.where(f < 0, f + ((-f + s - 1) // s) * s, np.where(f >= ln, f - ((f - ln + s) // s) * s, f))
+        inside = (f >= 0) & (f < ln)
+        have = inside | (bool(pad_edge) & (src >= 0) & (src < ln))
+        sm = np.mod((n - N // 2) * s + sh, ms) == 0
+        read = sm | (not zero_masked)
+        zero = zero or bool((read & ~have).any())
+        g = starts[v] + src
+        take = read & have
+        plain.append(g[take & (fl == 0)])
+        flipped.append(g[take & (fl != 0)])
+    return np.unique(np.concatenate(plain or [np.zeros(0, np.int64)])), np.unique(np.concatenate(flipped or [np.zeros(0, np.int64)])), zero
+
+
+def _window_spans(desc, seq_len, starts, lens):
+    """First and last pose-table row any token of each window can read (padding reads frames inside these bounds too)."""
+    d = np.asarray(desc, np.int64)
+    v, c, s = d[:, 0], d[:, 1], d[:, 2]
+    first = c - ((int(seq_len) - 1) * s) // 2
+    last = first + (int(seq_len) - 1) * s
+    hi = np.asarray(lens, np.int64)[v] - 1
+    base = np.asarray(starts, np.int64)[v]
+    return base + np.clip(first, 0, hi), base + np.clip(last, 0, hi)
+
+
+def _predict_windows_reuse(model, generator, descriptors, batch_size, flip, depth, graph, finish, table_bytes):
+    """predict_windows(reuse_frames=True): the spatial stack and spatial_to_temporal_fc once per frame the windows read (uu3d_frame_features),
+    the windows forwarded from that table (uu3d_gather_window_frames + uu3d_forward_frames_ex in a ForwardPipeline of the frames form).
+
+    The table holds the frames of a contiguous range of the pose table, once plain and once flipped, plus the all-zero frame; windows run in
+    chunks of whole batches whose range fits ``table_bytes``.  Rows of a chunk are pose-table rows shifted by the chunk's first row (the
+    video starts handed to the gather kernel are shifted likewise); only the rows the chunk reads are computed -- the set ``window_frames``
+    states on the host, found on the device from the chunk's own rows."""
+    import torch
+    import ctypes as C
+    from . import _capi
+    lib = _capi.load_library()
+    t = generator.table
+    dev = t.device
+    N, J, dt = generator.seq_len, t.J, model.arch.d_temporal
+    W = len(descriptors)
+    halves = 2 if (flip or bool(np.any(np.asarray(descriptors)[:, 5]))) else 1
+    cap = max(1, (int(table_bytes) // (4 * dt) - 1) // halves)         # frame rows per half
+    lo_w, hi_w = _window_spans(descriptors, N, t.starts, t.lens)
+    chunks = []                                                        # (first window, end window, first row, rows)
+    w0 = 0
+    while w0 < W:
+        w1 = min(w0 + batch_size, W)
+        lo, hi = int(lo_w[w0:w1].min()), int(hi_w[w0:w1].max())
+        while w1 < W:
+            e = min(w1 + batch_size, W)
+            nlo, nhi = min(lo, int(lo_w[w1:e].min())), max(hi, int(hi_w[w1:e].max()))
+            if nhi - nlo + 1 > cap:
+                break
+            lo, hi, w1 = nlo, nhi, e
+        chunks.append((w0, w1, lo, hi - lo + 1))
+        w0 = w1
+    S = max(c[3] for c in chunks)
+    zero_row = halves * S
+    table = torch.zeros((zero_row + 1, dt), dtype=torch.float32, device=dev)   # (zeros: the pipeline's warm-up forwards read it)
+    rows = min(batch_size, W) * halves
+    pipe = model.pipeline(rows, depth=depth, graph=graph, features=table)
+    depth = pipe.depth
+    d_vs = torch.empty(len(t.starts), dtype=torch.int64, device=dev)
+    fb = 16384                                                         # frames per uu3d_frame_features call
+    kp = torch.empty((fb, J, 2), dtype=torch.float32, device=dev)
+    feats = torch.empty((fb, dt), dtype=torch.float32, device=dev)
+    fl_order = C.c_void_p(generator._d_flip.data_ptr()) if generator._d_flip is not None else None
+    cur = torch.cuda.current_stream(dev)
+
+    def features_of_chunk(d, lo):
+        """The rows the chunk's windows read (uu3d_gather_window_frames over all of them, marked on the device: the same rules as the
+        forwards' own gathers), then uu3d_frame_features on those frames only, written into their table rows."""
+        db = np.concatenate([d, d.copy()], 0) if flip else d
+        if flip:
+            db[len(d):, 5] = 1 - db[len(d):, 5]
+        d_desc = torch.from_numpy(np.ascontiguousarray(db, np.int32)).pin_memory().to(dev, non_blocking=True)
+        rb = torch.empty((len(db), N), dtype=torch.int32, device=dev)
+        mk = torch.empty((len(db), N), dtype=torch.uint8, device=dev)
+        _capi.check(lib, lib.uu3d_gather_window_frames(C.c_void_p(d_vs.data_ptr()), C.c_void_p(t.d_lens.data_ptr()), C.c_void_p(d_desc.data_ptr()),
+                                                       len(db), N, int(generator.pad_edge), 1, S, zero_row, C.c_void_p(rb.data_ptr()),
+                                                       C.c_void_p(mk.data_ptr()), None, C.c_void_p(cur.cuda_stream)), None)
+        mark = torch.zeros(zero_row, dtype=torch.bool, device=dev)
+        r = rb[(rb >= 0) & (rb < zero_row)]
+        mark[r.long()] = True
+        ids = mark.nonzero().flatten()                                 # (one host synchronisation per chunk: the frame count)
+        for a in range(0, len(ids), fb):
+            rid = ids[a:a + fb]
+            n = len(rid)
+            fl = rid >= S
+            g = rid - torch.where(fl, S, 0) + lo
+            v = torch.searchsorted(t.d_starts, g, right=True) - 1
+            fd = torch.stack([v, g - t.d_starts[v], torch.ones_like(v), torch.ones_like(v), torch.zeros_like(v), fl.long()], -1).to(torch.int32).contiguous()
+            sm = torch.empty((n,), dtype=torch.uint8, device=dev)
+            _capi.check(lib, lib.uu3d_gather_windows(C.c_void_p(t.kp2d.data_ptr()), C.c_void_p(t.d_starts.data_ptr()), C.c_void_p(t.d_lens.data_ptr()),
+                                                     C.c_void_p(fd.data_ptr()), fl_order, n, 1, J, 2, 0, 0, C.c_void_p(kp.data_ptr()),
+                                                     C.c_void_p(sm.data_ptr()), None, C.c_void_p(cur.cuda_stream)), None)
+            model._frame_features(kp[:n], feats[:n], cur)
+            table.index_copy_(0, rid, feats[:n])
+
+    # the all-zero frame (zero padding), once: its row is the table's last
+    kp[:1].zero_()
+    model._frame_features(kp[:1], table[zero_row:], cur)
+
+    def take(lo, n, ticket):
+        pipe.after(ticket, lambda full, cen: finish(lo, n, cen))
+
+    pending = []
+    try:
+        for w0, w1, lo, _ in chunks:
+            for p in pending:
+                take(*p)
+            pending = []
+            pipe.join()                                                # (the forwards that read the previous chunk's table are enqueued before the rewrite)
+            d_vs.copy_(torch.from_numpy(t.starts - lo))
+            features_of_chunk(np.asarray(descriptors[w0:w1]), lo)
+            pipe.wait_caller()
+            for b0 in range(w0, w1, batch_size):
+                db = np.ascontiguousarray(descriptors[b0:min(b0 + batch_size, w1)])
+                n = len(db)
+                if flip:
+                    df = db.copy(); df[:, 5] = 1 - df[:, 5]
+                    db = np.concatenate([db, df], 0)
+                rb, mb, sstream = pipe.acquire(len(db), wait_caller=False)
+                with torch.cuda.stream(sstream):
+                    d_desc = torch.from_numpy(np.ascontiguousarray(db, np.int32)).pin_memory().to(dev, non_blocking=True)
+                    mk = mb if mb is not None else torch.empty((len(db), N), dtype=torch.uint8, device=dev)
+                    _capi.check(lib, lib.uu3d_gather_window_frames(C.c_void_p(d_vs.data_ptr()), C.c_void_p(t.d_lens.data_ptr()), C.c_void_p(d_desc.data_ptr()),
+                                                                   len(db), N, int(generator.pad_edge), 1, S, zero_row, C.c_void_p(rb.data_ptr()),
+                                                                   C.c_void_p(mk.data_ptr()), None, C.c_void_p(sstream.cuda_stream)), None)
+                    if mb is None:                                     # (no strided input: a dropped frame is read as zeros, eval.py:67)
+                        rb.masked_fill_(rb < 0, zero_row)
+                pending.append((b0, n, pipe.launch(len(db), wait_caller=False)))
+                if len(pending) == depth:
+                    take(*pending.pop(0))
+        for p in pending:
+            take(*p)
+        pipe.join()
+        torch.cuda.current_stream(dev).synchronize()
+        pipe.check_range()                                             # f16x3 range guard: once per evaluation (features and forwards)
+    finally:
+        pipe.close()
+
+
+def predict_windows(model, generator, descriptors, config, batch_size, flip=True, depth=None, graph=True, reuse_frames=False,
+                    frame_table_bytes=FRAME_TABLE_BYTES):
     """Central 3D predictions (W, J, 3) float32 on the device for the given window descriptors: batches of ``batch_size``
     windows, each forwarded together with its mirrored copy when ``flip`` (one launch chain over 2B sequences).
 
@@ -50,7 +214,12 @@ def predict_windows(model, generator, descriptors, config, batch_size, flip=True
     (pipeline.ForwardPipeline: batch k + 1's big kernels run beside batch k's latency-bound tail; the window gather of a batch
     writes into its slot's input buffers on the slot's stream).  depth = 1, graph = False is the reference's loop: one eager call after the other.
     depth = 1 runs the LATENCY schedule, depth > 1 the THROUGHPUT schedule (the temporal chain, other split-K depths): the same arithmetic in another
-    summation order -- predictions agree to ~3e-5 (tests/test_tchain_gpu.py), each schedule is bitwise reproducible run to run."""
+    summation order -- predictions agree to ~3e-5 (tests/test_tchain_gpu.py), each schedule is bitwise reproducible run to run.
+
+    ``reuse_frames=True``: every frame the windows read goes through the spatial stack and spatial_to_temporal_fc ONCE (uu3d_frame_features)
+    instead of once per window it sits in; the windows are forwarded from that feature table (uu3d_forward_frames_ex, always through a
+    pipeline, graphs as ``graph`` says).  Within ~3e-5 of the default (the s2t GEMM sums in another split-K order).  The table is bounded by
+    ``frame_table_bytes``: windows run in chunks whose frames fit."""
     import torch
     W = len(descriptors)
     J = generator.table.J
@@ -65,12 +234,16 @@ def predict_windows(model, generator, descriptors, config, batch_size, flip=True
         # one slot per hardware queue measured best END TO END (round 5, tools/eval_throughput_exp.py: descriptor upload + window gather + forward + copy per slot;
         # 128 sequences per batch: 142 / 170 / 180 / 172 k sequences/s with 2 / 3 / 4 / 8 slots, 512 per batch: 185 / 188 / 185 / 171 k)
         depth = 4
-    pipe = model.pipeline(rows, depth=depth, graph=graph) if (depth is None or depth > 1 or graph) else None
-    if pipe is not None:
-        depth = pipe.depth
 
     def finish(lo, n, cen):
         raw[:, lo:lo + n].copy_(cen.view(raw.shape[0], n, J, 3))
+
+    if reuse_frames:
+        _predict_windows_reuse(model, generator, descriptors, batch_size, flip, depth, graph, finish, frame_table_bytes)
+        return _unflip(raw, config, flip)
+    pipe = model.pipeline(rows, depth=depth, graph=graph) if (depth is None or depth > 1 or graph) else None
+    if pipe is not None:
+        depth = pipe.depth
 
     def take(lo, n, ticket):
         # the copy into `raw` goes on the slot's stream (pipe.after): the caller's stream never waits inside the loop
@@ -109,20 +282,26 @@ def predict_windows(model, generator, descriptors, config, batch_size, flip=True
             pipe.check_range()                                     # f16x3 range guard (include/uu3d.h): once per evaluation, never per batch
         finally:
             pipe.close()
+    return _unflip(raw, config, flip)
+
+
+def _unflip(raw, config, flip):
+    import torch
     if not flip:
         return raw[0]
-    order = torch.as_tensor(np.asarray(config.AUGM_FLIP_KEYPOINT_ORDER), dtype=torch.long, device=dev)
+    order = torch.as_tensor(np.asarray(config.AUGM_FLIP_KEYPOINT_ORDER), dtype=torch.long, device=raw.device)
     f = raw[1]
     f = torch.cat([f[..., :1] * -1.0, f[..., 1:]], dim=-1).index_select(1, order)              # eval.py:163-166
     return (raw[0] + f) / 2.0
 
 
 def run_eval(config, dataset_name, dataset_path, dataset2d_path, test_subset, weights_path=None, model=None, action_wise=True,
-             batch_size=None, skip_unused_windows=True, log=_log, depth=None, graph=True):
+             batch_size=None, skip_unused_windows=True, log=_log, depth=None, graph=True, reuse_frames=False):
     """eval.py:34-253.  Returns ``evaluation.evaluate_predictions``'s dict (+ "num_windows", "num_forwarded", "seconds").
 
     ``batch_size`` defaults to ``config.BATCH_SIZE``; ``depth`` / ``graph``: batches in flight and hipGraph replay of the forward
-    (``predict_windows``; depth 1 without graph = the reference's eager loop, same numbers).  With torch.distributed initialised, the windows to run are split
+    (``predict_windows``; depth 1 without graph = the reference's eager loop, same numbers); ``reuse_frames``: each frame's spatial
+    features computed once (``predict_windows``).  With torch.distributed initialised, the windows to run are split
     contiguously over the ranks and the predictions all-gathered; every rank returns the same report."""
     import torch
     from .net.uplift_upsample_transformer_constructor import build_uplift_upsample_transformer
@@ -159,7 +338,8 @@ def run_eval(config, dataset_name, dataset_path, dataset2d_path, test_subset, we
         rank, world = tdist.get_rank(), tdist.get_world_size()
     lo, hi = udist.shard_bounds(len(run), rank, world)
     bs = int(batch_size or config.BATCH_SIZE)
-    local = predict_windows(model, gen, desc[run[lo:hi]], config, bs, flip=bool(config.EVAL_FLIP), depth=depth, graph=graph)
+    local = predict_windows(model, gen, desc[run[lo:hi]], config, bs, flip=bool(config.EVAL_FLIP), depth=depth, graph=graph,
+                            reuse_frames=reuse_frames)
     allp = udist.allgather_errors(local)                             # (len(run), J, 3) in rank order: the payload is a few KB per rank
     pred = np.zeros((W, table.J, 3), np.float64)
     pred[run] = allp.detach().cpu().numpy().astype(np.float64)

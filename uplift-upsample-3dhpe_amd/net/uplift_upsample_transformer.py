@@ -522,23 +522,8 @@ class UpliftUpsampleTransformer(object):
         # Range guard (include/uu3d.h): the f16x3 products cannot represent activations of magnitude >= 65504 (the reference is float32 end to
         # end).  A direct call checks its own result -- one stream synchronisation, skipped inside a stream capture and with range_guard=False --
         # and repeats an overflowed batch on the exact-f32 kernels; where those do not exist it raises.  Pipelines check once (check_range()).
-        guard = self.range_guard and self.precision == "f16x3" and not torch.cuda.is_current_stream_capturing()
-
         def guarded(run):
-            run(False)
-            if guard and self.check_range(main, raise_error=False):
-                if not self._exact_f32_available():
-                    raise _capi.Uu3dRangeError(_capi.UU3D_ERR_RANGE, "activations beyond the f16 range of the f16x3 products (or non-finite inputs), and "
-                                               "this model has no exact-f32 forward to fall back to (generic dims or > 128 tokens)")
-                if not self._range_warned:
-                    self._range_warned = True
-                    import warnings
-                    warnings.warn("uu3d: a batch left the f16 range of the f16x3 products (|activation| >= 65504) and was repeated on the exact-f32 "
-                                  "kernels; build the model with precision='f32' if this is the rule for these weights", RuntimeWarning)
-                run(True)
-                torch.cuda.current_stream(self.device).synchronize()
-                if not bool(torch.isfinite(central).all()) or (full is not None and not bool(torch.isfinite(full).all())):
-                    raise _capi.Uu3dRangeError(_capi.UU3D_ERR_RANGE, "non-finite outputs even in exact f32: the inputs or weights are not finite")
+            self._guarded(run, full, central, main)
         if self.return_attention:
             att = [torch.empty((B, a.num_heads, a.num_frames, a.num_frames), dtype=torch.float32, device=self.device)
                    for _ in range(a.temporal_depth)]
@@ -566,6 +551,102 @@ class UpliftUpsampleTransformer(object):
         guarded(run_halves)                                # (the range guard covers both halves: the sticky word is the model's)
         return full, central
 
+    def _guarded(self, run, full, central, main):
+        """``run(exact_f32)`` once; when the range word says it overflowed, once more on the exact-f32 kernels (see ``__call__``)."""
+        torch = self._torch
+        guard = self.range_guard and self.precision == "f16x3" and not torch.cuda.is_current_stream_capturing()
+        run(False)
+        if guard and self.check_range(main, raise_error=False):
+            if not self._exact_f32_available():
+                raise _capi.Uu3dRangeError(_capi.UU3D_ERR_RANGE, "activations beyond the f16 range of the f16x3 products (or non-finite inputs), and "
+                                           "this model has no exact-f32 forward to fall back to (generic dims or > 128 tokens)")
+            if not self._range_warned:
+                self._range_warned = True
+                import warnings
+                warnings.warn("uu3d: a batch left the f16 range of the f16x3 products (|activation| >= 65504) and was repeated on the exact-f32 "
+                              "kernels; build the model with precision='f32' if this is the rule for these weights", RuntimeWarning)
+            run(True)
+            torch.cuda.current_stream(self.device).synchronize()
+            if not bool(torch.isfinite(central).all()) or (full is not None and not bool(torch.isfinite(full).all())):
+                raise _capi.Uu3dRangeError(_capi.UU3D_ERR_RANGE, "non-finite outputs even in exact f32: the inputs or weights are not finite")
+
+    # ---- frames form (include/uu3d.h, FRAMES FORM): features once per frame, windows read them from a table -------------------
+    def _frame_features(self, frames, out, stream, exact_f32=False):
+        """One uu3d_frame_features call: (F, J, 2) float32 frames -> ``out`` (F, d_t) float32, on ``stream``."""
+        torch = self._torch
+        F = int(frames.shape[0])
+        nbytes = int(self._lib.uu3d_frame_features_bytes(self._h, F))
+        ws = self._ws.get("frames")
+        if ws is None or ws.numel() < nbytes:
+            with torch.cuda.stream(stream):
+                ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self._ws["frames"] = ws
+        schedule = _capi.UU3D_SCHEDULE_EXACT_F32 if exact_f32 else 0
+        st = self._lib.uu3d_frame_features(self._h, C.c_void_p(frames.data_ptr()), F, C.c_void_p(out.data_ptr()), C.c_void_p(ws.data_ptr()),
+                                           C.c_size_t(ws.numel()), int(schedule), C.c_void_p(stream.cuda_stream))
+        _capi.check(self._lib, st, self._h)
+
+    def frame_features(self, frames, exact_f32=False):
+        """The spatial stack and spatial_to_temporal_fc (with its bias) of each frame on its own: (F, J, 2) -> (F, d_t) float32 on the device.
+        No token blend, no temporal PE -- what ``forward_frames`` reads through its ``rows``.  No range guard (``check_range()`` afterwards)."""
+        torch = self._torch
+        a = self.arch
+        if frames.dim() != 3 or tuple(frames.shape[1:]) != (a.num_keypoints, 2):
+            raise ValueError(f"frames must be (F, {a.num_keypoints}, 2), got {tuple(frames.shape)}")
+        if frames.device != self.device:
+            raise ValueError(f"frames are on {frames.device}, model is on {self.device}")
+        self._sync_from_trainer()
+        frames = frames.to(torch.float32).contiguous()
+        out = torch.empty((frames.shape[0], a.d_temporal), dtype=torch.float32, device=self.device)
+        self._frame_features(frames, out, torch.cuda.current_stream(self.device), exact_f32=exact_f32)
+        return out
+
+    def _forward_frames(self, features, rows, stride_mask, full, central, slot, stream, attn=None, schedule=0, exact_f32=False):
+        """One uu3d_forward_frames_ex call (the frames form of ``_forward``)."""
+        if exact_f32:
+            schedule = int(schedule) | _capi.UU3D_SCHEDULE_EXACT_F32
+        B = rows.shape[0]
+        ws = self._workspace(B, slot)
+        ptrs = None
+        if attn is not None:
+            ptrs = (C.c_void_p * max(len(attn), 1))(*[t.data_ptr() for t in attn])
+        st = self._lib.uu3d_forward_frames_ex(self._h, C.c_void_p(features.data_ptr()), int(features.shape[0]), C.c_void_p(rows.data_ptr()),
+                                              C.c_void_p(stride_mask.data_ptr()) if stride_mask is not None else None, B,
+                                              C.c_void_p(full.data_ptr()) if full is not None else None,
+                                              C.c_void_p(central.data_ptr()), ptrs, C.c_void_p(ws.data_ptr()),
+                                              C.c_size_t(ws.numel()), int(schedule), C.c_void_p(stream.cuda_stream))
+        _capi.check(self._lib, st, self._h)
+
+    def forward_frames(self, features, rows, stride_mask=None):
+        """``model([x, stride_mask])`` with the windows given as rows of a per-frame feature table (``frame_features``): ``rows`` (B, N) int32,
+        -1 for a masked token; ``features`` (R, d_t) float32.  Same range guard as ``model(...)`` (an overflowed batch is repeated from
+        the temporal blocks on in exact f32).  Returns (full, central) or, with return_attention, (full, central, att_list)."""
+        torch = self._torch
+        a = self.arch
+        if rows.dim() != 2 or rows.shape[1] != a.num_frames or rows.dtype != torch.int32:
+            raise ValueError(f"rows must be (B, {a.num_frames}) int32")
+        if features.dim() != 2 or features.shape[1] != a.d_temporal or features.dtype != torch.float32:
+            raise ValueError(f"features must be (R, {a.d_temporal}) float32")
+        if self.has_strided_input != (stride_mask is not None):
+            raise ValueError("stride_mask must be given iff the model has strided input")
+        B = rows.shape[0]
+        rows, features = rows.contiguous(), features.contiguous()
+        if stride_mask is not None:
+            if tuple(stride_mask.shape) != (B, a.num_frames):
+                raise ValueError(f"stride_mask must be (B, {a.num_frames})")
+            stride_mask = self._mask_u8(stride_mask)
+        self._sync_from_trainer()
+        main = torch.cuda.current_stream(self.device)
+        full = torch.empty((B, a.num_frames, a.num_keypoints, 3), dtype=torch.float32, device=self.device) if self._returns_full else None
+        central = torch.empty((B, a.num_keypoints, 3), dtype=torch.float32, device=self.device)
+        att = None
+        if self.return_attention:
+            att = [torch.empty((B, a.num_heads, a.num_frames, a.num_frames), dtype=torch.float32, device=self.device)
+                   for _ in range(a.temporal_depth)]
+        self._guarded(lambda f32: self._forward_frames(features, rows, stride_mask, full, central, 0, main, attn=att, exact_f32=f32),
+                      full, central, main)
+        return (full, central, att) if self.return_attention else (full, central)
+
     def call_scheduled(self, inputs, schedule):
         """One inference call on the current stream under a NAMED launch schedule of include/uu3d.h: "latency" (what ``model(...)`` runs) or
         "throughput" (what a pipeline's slots run: launches shaped for CU-microseconds, the temporal chain from 1024 token rows on) ->
@@ -585,11 +666,12 @@ class UpliftUpsampleTransformer(object):
         return full, central
 
     # ---- graph replay / several batches in flight ------------------------------------------------
-    def pipeline(self, batch, depth=None, graph=True, post=None):
+    def pipeline(self, batch, depth=None, graph=True, post=None, features=None):
         """``depth`` independent batches in flight on ``depth`` HIP streams, each replaying its own hipGraph of the forward
-        (pipeline.ForwardPipeline): the throughput path of an evaluation loop (eval.py:147-152)."""
+        (pipeline.ForwardPipeline): the throughput path of an evaluation loop (eval.py:147-152).  ``features``: the frames form
+        (a per-frame feature table, fixed for the pipeline's life; the slots take rows instead of 2D windows)."""
         from ..pipeline import ForwardPipeline
-        return ForwardPipeline(self, batch, depth=depth, graph=graph, post=post)
+        return ForwardPipeline(self, batch, depth=depth, graph=graph, post=post, features=features)
 
     def capture(self, batch):
         """One forward at a fixed batch size as a hipGraph: ``f = model.capture(128); full, central = f([x, mask])`` replays

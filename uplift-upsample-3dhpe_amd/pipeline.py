@@ -90,19 +90,23 @@ def distinct_queue_streams(device, want=4, pool=16, spin_ms=2.0, per_queue=1):
 
 
 class _Slot(object):
-    __slots__ = ("stream", "x", "m", "full", "central", "graph", "done", "busy", "n", "extra")
+    __slots__ = ("stream", "x", "m", "full", "central", "graph", "done", "busy", "n", "extra")      # (frames form: x holds the (batch, N) int32 rows)
 
 
 class ForwardPipeline(object):
 
-    def __init__(self, model, batch, depth=None, graph=True, post=None, streams=None):
+    def __init__(self, model, batch, depth=None, graph=True, post=None, streams=None, features=None):
         """``depth``: batches in flight; None = TWO per HIP hardware queue for batches up to 128 sequences, one above (``distinct_queue_streams(per_queue=2)``: 8 / 4 -- round 5: with the temporal
         chain's launches of one workgroup per 128 rows, eight forwards in flight keep the chip full where four do not: 187 k against 181 k
         sequences/s at batch 128; the round-4 launches measure the same with four and eight), an int up to that number takes that many of
         those streams (class-major: the first four sit on four different queues), more falls back to fresh pool streams.
         ``post(full, central, slot_index)``: optional device work appended to every forward ON THE SLOT'S STREAM (and into its
         graph), e.g. the per-joint error kernel; what it returns is handed out by ``result`` as a third element.
-        ``streams``: the slots' streams (``depth`` of them), whatever queues they are on."""
+        ``streams``: the slots' streams (``depth`` of them), whatever queues they are on.
+        ``features``: the FRAMES FORM (include/uu3d.h, uu3d_forward_frames_ex): a (R, d_t) float32 table of per-frame features
+        (``model.frame_features``), fixed for the pipeline's life -- the graphs hold its address; its contents may be rewritten between
+        batches on a stream the slots wait for.  The slots' static inputs are then (batch, N) int32 table rows (``uu3d_gather_window_frames``)
+        and the stride masks: ``acquire`` / ``preload`` / ``submit`` take rows where the 2D form takes windows."""
         import torch
         if depth is not None and depth < 1:
             raise ValueError("depth >= 1")
@@ -118,6 +122,10 @@ class ForwardPipeline(object):
             depth = len(streams)
         self._torch = torch
         self.model, self.batch, self.depth, self.post = model, int(batch), int(depth), post
+        if features is not None and (features.dim() != 2 or features.shape[1] != model.arch.d_temporal or features.dtype != torch.float32
+                                     or not features.is_contiguous() or features.device != model.device):
+            raise ValueError(f"features must be a contiguous (R, {model.arch.d_temporal}) float32 tensor on {model.device}")
+        self.features = features
         a = model.arch
         dev = model.device
         self._slots = []
@@ -131,7 +139,10 @@ class ForwardPipeline(object):
             s = _Slot()
             s.stream = streams[i] if streams is not None else torch.cuda.Stream(device=dev)
             s.stream.wait_stream(cur)
-            s.x = torch.zeros((batch, a.num_frames, a.num_keypoints, 2), dtype=torch.float32, device=dev)
+            if features is None:
+                s.x = torch.zeros((batch, a.num_frames, a.num_keypoints, 2), dtype=torch.float32, device=dev)
+            else:
+                s.x = torch.zeros((batch, a.num_frames), dtype=torch.int32, device=dev)            # (row 0: a valid row for the warm-up)
             s.m = torch.ones((batch, a.num_frames), dtype=torch.uint8, device=dev) if model.has_strided_input else None
             s.full = torch.empty((batch, a.num_frames, a.num_keypoints, 3), dtype=torch.float32, device=dev) if model._returns_full else None
             s.central = torch.empty((batch, a.num_keypoints, 3), dtype=torch.float32, device=dev)
@@ -162,8 +173,12 @@ class ForwardPipeline(object):
         s = self._slots[i]
         # launches shaped for CU-microseconds, not latency, when the forwards in flight share the chip: an ARGUMENT of the call
         # (include/uu3d.h, uu3d_forward_ex), so a model(...) call on another thread keeps its own schedule
-        self.model._forward(s.x[:n], s.m[:n] if s.m is not None else None, s.full[:n] if s.full is not None else None,
-                            s.central[:n], self._keys[i], s.stream, schedule=1 if self.depth > 1 else 0)
+        if self.features is not None:
+            self.model._forward_frames(self.features, s.x[:n], s.m[:n] if s.m is not None else None, s.full[:n] if s.full is not None else None,
+                                       s.central[:n], self._keys[i], s.stream, schedule=1 if self.depth > 1 else 0)
+        else:
+            self.model._forward(s.x[:n], s.m[:n] if s.m is not None else None, s.full[:n] if s.full is not None else None,
+                                s.central[:n], self._keys[i], s.stream, schedule=1 if self.depth > 1 else 0)
         if self.post is not None:
             s.extra = self.post(s.full[:n] if s.full is not None else None, s.central[:n], i)
 
@@ -186,7 +201,7 @@ class ForwardPipeline(object):
     def acquire(self, n=None, wait_caller=True):
         """The next slot's STATIC input buffers, for a producer that writes the batch in place (no copy, no temporaries):
 
-            x_buf, m_buf, stream = pipe.acquire(n)      # (n, N, J, 2) float32, (n, N) uint8 or None, the slot's torch stream
+            x_buf, m_buf, stream = pipe.acquire(n)      # (n, N, J, 2) float32 (frames form: (n, N) int32 rows), (n, N) uint8 or None, the slot's torch stream
             generator.gather(desc, out=(x_buf, m_buf), stream=stream)
             ticket = pipe.launch(n)
 
@@ -260,6 +275,13 @@ class ForwardPipeline(object):
                         stride_mask.record_stream(stream)
                 mb.copy_(mu, non_blocking=True)
         return self.launch(n)
+
+    def wait_caller(self):
+        """Every slot's stream waits for what the caller's current stream has enqueued so far (e.g. a rewrite of the feature table of the
+        frames form, after ``join()`` made the caller wait for the forwards that read the old contents)."""
+        cur = self._torch.cuda.current_stream(self.model.device)
+        for s in self._slots:
+            s.stream.wait_stream(cur)
 
     def check_range(self):
         """Range guard of precision f16x3 (include/uu3d.h, RANGE CONTRACT) for everything submitted so far: waits for every slot, then raises
