@@ -109,6 +109,10 @@ const char* uu3d_last_error(const uu3d_model* model);
  * Training-step token limits (every handle): attention layers of head dim 48 without ATTENTION_DROP_RATE train up to 416 tokens -- up to 128
  * on the register-resident kernels, 129 .. 416 on the tiled exact-f32 pair of csrc/uu3d_attn_long.h (row statistics saved by the forward, P
  * recomputed by the backward, deterministic); other head dims up to 128 (and the LDS bound above); ATTENTION_DROP_RATE > 0 up to 96.
+ * Training-step structures (compiled dims): temporal_depth == 0 (no full-sequence head; strided block 1 takes the key mask when the model has
+ * strided input), num_strided == 0 (head2 reads the central token x[:, N // 2] of the temporal stack's output) and both at once train
+ * like the shipped structure.  Refused with UU3D_ERR_UNSUPPORTED: full_output == 0 with temporal blocks (USE_REFINE), and generic-dims
+ * handles without a temporal or a strided block (uu3d_create refuses those already).
  */
 int uu3d_create(const uu3d_config* config, int device, uu3d_model** out_model);
 void uu3d_destroy(uu3d_model* model);
@@ -358,7 +362,8 @@ int uu3d_ema_update(float* ema_dev, const float* w_dev, int64_t n, float decay, 
  *       drop_path_rates[3] = DROP_PATH_RATE (spatial, temporal, strided); per block rate linspace(0, rate, depth)
  *       drop_path_uniform_dev: U[0,1) draws, layout [spatial blocks][2][B*N] then [temporal blocks][2][B]
  *                              (two draws per block: attention branch, MLP branch); NULL disables DropPath.
- *       full_out_dev / central_out_dev may be NULL.  loss_out_dev[3] = {loss, central, sequence}.
+ *       full_out_dev / central_out_dev may be NULL.  loss_out_dev[3] = {loss, central, sequence}.  Without the full-sequence head
+ *       (temporal_depth == 0) full_out_dev is not written, loss = (w_center + w_seq) * central (train.py:491-494) and sequence = 0.
  *       gt3d_dev == NULL: training-mode FORWARD ONLY (model(inputs, training=True) outside a tape, train.py:478);
  *       loss_out_dev / grads_dev may then be NULL.  drop_path_rates[2] != 0: DropPath inside the strided blocks, its draws behind the
  *       temporal stack's ([strided blocks][2][B]).
@@ -419,7 +424,8 @@ int uu3d_train_forward_backward_masked(uu3d_model* model, const float* params_de
  *       the backward pass (token limits -- 416 at head dim 48, see uu3d_create --, LDS of the backward attention kernels), so the tape's backward is never refused.  The models
  *       the training step refuses are refused with the same messages.
  *   uu3d_train_backward_tape: the backward pass of that forward, seeded with d loss / d full_output (B,N,J,3) and
- *       d loss / d central_output (B,J,3) supplied by the caller (NULL = 0).  grads_dev (uu3d_num_params floats, inventory order) is
+ *       d loss / d central_output (B,J,3) supplied by the caller (NULL = 0; without the full-sequence head -- temporal_depth == 0, where the
+ *       tape's forward takes full_out_dev == NULL -- grad_full_dev must be NULL: UU3D_ERR_INVALID_ARGUMENT otherwise).  grads_dev (uu3d_num_params floats, inventory order) is
  *       OVERWRITTEN with d loss / d params; NULL = not wanted.  grad_kp2d_dev (B,N,J,2), or NULL, receives d loss / d kp2d_dev; rows of
  *       frames the stride mask (or the token mask) discards are exactly 0.  The cotangents are multiplied on the device by a power of
  *       two that puts their largest magnitude into (0.5, 1] (loss scaling without a host synchronisation) and the results unscaled.

@@ -250,13 +250,17 @@ identity_bwd_kernel(const float* __restrict__ dout, const int B, const int L_in,
 // ---- BatchNormalization in training mode (OUTPUT_BN heads, u_u_t.py:275-285,400-404,414-416; kl.BatchNormalization(momentum=0.1,
 // epsilon=1e-5) on rank-3 / rank-2 inputs = Keras' non-fused path: batch mean and BIASED variance over every axis but the last, the same
 // biased variance in the moving-average update, moving = moving * momentum + batch * (1 - momentum)).  Column statistics are two
-// launch_colsum passes (sum, then sum of squared deviations: two-pass like tf.nn.moments) around these elementwise kernels.
+// launch_colsum passes (sum, then sum of squared deviations: two-pass like tf.nn.moments) around these elementwise kernels.  x: rows ldx
+// apart (d_t, or N d_t for the central tokens x[:, N // 2] that strided_temporal_norm normalises without strided blocks); the other
+// operands are dense (rows x D).
 static __global__ void __launch_bounds__(256)
-bn_sqdev_kernel(const float* __restrict__ x, const float* __restrict__ sum, const float inv_rows, const long long n, const int D, float* __restrict__ out)
+bn_sqdev_kernel(const float* __restrict__ x, const float* __restrict__ sum, const float inv_rows, const long long n, const int D, float* __restrict__ out,
+                const int ldx)
 {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const float d = x[i] - sum[i % D] * inv_rows;
+    const long long r = i / D; const int c = (int)(i - r * D);
+    const float d = x[r * ldx + c] - sum[c] * inv_rows;
     out[i] = d * d;
 }
 // mean, 1 / sqrt(var + eps) of the batch; moving statistics updated in place (the only weights a training-mode forward writes)
@@ -282,35 +286,36 @@ bn_moving_stats_kernel(const float* __restrict__ moving_mean, const float* __res
 }
 static __global__ void __launch_bounds__(256)
 bn_apply_kernel(const float* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ rstd, const float* __restrict__ gamma,
-                const float* __restrict__ beta, const long long n, const int D, float* __restrict__ y)
+                const float* __restrict__ beta, const long long n, const int D, float* __restrict__ y, const int ldx)
 {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const int c = (int)(i % D);
-    y[i] = (x[i] - mean[c]) * rstd[c] * gamma[c] + beta[c];
+    const long long r = i / D; const int c = (int)(i - r * D);
+    y[i] = (x[r * ldx + c] - mean[c]) * rstd[c] * gamma[c] + beta[c];
 }
 // out = dy * xhat  (its column sum is d gamma; the column sum of dy is d beta)
 static __global__ void __launch_bounds__(256)
 bn_bwd_prod_kernel(const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ rstd,
-                   const long long n, const int D, float* __restrict__ out)
+                   const long long n, const int D, float* __restrict__ out, const int ldx)
 {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const int c = (int)(i % D);
-    out[i] = dy[i] * ((x[i] - mean[c]) * rstd[c]);
+    const long long r = i / D; const int c = (int)(i - r * D);
+    out[i] = dy[i] * ((x[r * ldx + c] - mean[c]) * rstd[c]);
 }
-// dx (+)= gamma * rstd * (dy - dbeta / R - xhat * dgamma / R)
+// dx (+)= gamma * rstd * (dy - dbeta / R - xhat * dgamma / R); x and dx rows ldx apart
 static __global__ void __launch_bounds__(256)
 bn_bwd_dx_kernel(const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ rstd,
                  const float* __restrict__ gamma, const float* __restrict__ dgamma, const float* __restrict__ dbeta, const float inv_rows,
-                 const long long n, const int D, const int accumulate, float* __restrict__ dx)
+                 const long long n, const int D, const int accumulate, float* __restrict__ dx, const int ldx)
 {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const int c = (int)(i % D);
-    const float xh = (x[i] - mean[c]) * rstd[c];
+    const long long r = i / D; const int c = (int)(i - r * D);
+    const long long o = r * ldx + c;
+    const float xh = (x[o] - mean[c]) * rstd[c];
     const float v = gamma[c] * rstd[c] * (dy[i] - dbeta[c] * inv_rows - xh * dgamma[c] * inv_rows);
-    dx[i] = accumulate ? dx[i] + v : v;
+    dx[o] = accumulate ? dx[o] + v : v;
 }
 
 // out[r][0..ldo) = in[r][0..C) followed by zeros   (head gradients: 51 -> 64 columns)

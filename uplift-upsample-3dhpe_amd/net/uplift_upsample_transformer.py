@@ -451,10 +451,10 @@ class UpliftUpsampleTransformer(object):
     # ---- autograd: the training-mode forward with a tape, the backward from the output gradients ------------------------
     def _tape_forward(self, x, stride_mask):
         """uu3d_train_forward_tape with this call's draws and a workspace of its own (it holds the saved activations until the
-        tape is freed): returns (full, central, tape holder)."""
+        tape is freed): returns (full, central, tape holder); full is None without the full-sequence head (no temporal blocks)."""
         torch = self._torch
         a, B = self.arch, x.shape[0]
-        full = torch.empty((B, a.num_frames, a.num_keypoints, 3), dtype=torch.float32, device=self.device)
+        full = torch.empty((B, a.num_frames, a.num_keypoints, 3), dtype=torch.float32, device=self.device) if self._returns_full else None
         central = torch.empty((B, a.num_keypoints, 3), dtype=torch.float32, device=self.device)
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         params, u, r3, tm = self._training_draws(B)
@@ -464,7 +464,8 @@ class UpliftUpsampleTransformer(object):
             self._h, C.c_void_p(params.data_ptr()), C.c_void_p(x.data_ptr()),
             C.c_void_p(stride_mask.data_ptr()) if stride_mask is not None else None, B,
             r3, C.c_void_p(u.data_ptr()), C.c_void_p(tm.data_ptr()) if tm is not None else None, float(self.arch.token_mask_rate),
-            C.c_void_p(full.data_ptr()), C.c_void_p(central.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(), C.byref(tape), stream)
+            C.c_void_p(full.data_ptr()) if full is not None else None, C.c_void_p(central.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(),
+            C.byref(tape), stream)
         _capi.check(self._lib, st, self._h)
         return full, central, _Tape(self, tape, (params, x, stride_mask, u, tm, ws))
 
@@ -733,7 +734,7 @@ def _training_call():
 
         @staticmethod
         def forward(ctx, model, x, param, stride_mask):
-            full, central, tape = model._tape_forward(x.detach(), stride_mask)
+            full, central, tape = model._tape_forward(x.detach(), stride_mask)     # (full None without temporal blocks: its gradient is None too)
             ctx.set_materialize_grads(False)                  # a None output gradient reaches the library as NULL
             ctx.save_for_backward(param)                       # an in-place change before backward() trips torch's version check
             ctx.model, ctx.tape = model, tape

@@ -112,7 +112,9 @@ class Trainer(object):
         return n
 
     def forward_backward(self, keypoints2d, keypoints3d, stride_masks, drop_path_uniform="draw", token_mask_uniform="draw", dropout_seed=None):
-        """Training-mode forward + loss + backward.  Returns (loss[3] tensor, full, central); gradients in self.grads.
+        """Training-mode forward + loss + backward.  Returns (loss[3] tensor, full, central); gradients in self.grads.  Without temporal
+        blocks there is no full-sequence output: full is None and the loss is (LOSS_WEIGHT_CENTER + LOSS_WEIGHT_SEQUENCE) * central
+        (train.py:491-494), loss[2] = 0.
 
         drop_path_uniform: "draw" = fresh U[0,1) draws, None = DropPath disabled, or a flat tensor of draws.
         token_mask_uniform (TOKEN_MASK_RATE > 0, u_u_t.py:287-311): "draw", None = no token masking, or a (B, N) tensor of draws.
@@ -139,7 +141,7 @@ class Trainer(object):
         if a.token_mask_rate > 0.0 and token_mask_uniform is not None:
             tm = (torch.rand((B, a.num_frames), generator=self._rng, device=dev, dtype=torch.float32) if isinstance(token_mask_uniform, str)
                   else token_mask_uniform.to(device=dev, dtype=torch.float32).contiguous())
-        full = torch.empty((B, a.num_frames, a.num_keypoints, 3), dtype=torch.float32, device=dev)
+        full = torch.empty((B, a.num_frames, a.num_keypoints, 3), dtype=torch.float32, device=dev) if self.model._returns_full else None
         central = torch.empty((B, a.num_keypoints, 3), dtype=torch.float32, device=dev)
         ws = self._workspace(B)
         rates = (C.c_float * 3)(*[float(r) for r in self.drop_path_rates])
@@ -152,7 +154,7 @@ class Trainer(object):
             int(cfg.BATCH_SIZE), float(cfg.LOSS_WEIGHT_CENTER), float(cfg.LOSS_WEIGHT_SEQUENCE), int(cfg.ROOT_KEYTPOINT),
             rates, None if u is None else C.c_void_p(u.data_ptr()),
             None if tm is None else C.c_void_p(tm.data_ptr()), float(a.token_mask_rate), C.c_void_p(self.loss.data_ptr()),
-            C.c_void_p(full.data_ptr()), C.c_void_p(central.data_ptr()), C.c_void_p(self.grads.data_ptr()),
+            None if full is None else C.c_void_p(full.data_ptr()), C.c_void_p(central.data_ptr()), C.c_void_p(self.grads.data_ptr()),
             C.c_void_p(ws.data_ptr()), self._ws_bytes, self._stream())
         _capi.check(self._lib, st, self.model._h)
         self._buckets.raise_pending()                                       # an exception inside the gradient-ready callback (ctypes only prints it)
