@@ -7,6 +7,7 @@ shuffling and random draws as the reference, in the same order) and ``uu3d_gathe
 device: 2D windows already multiplied by their stride mask (eval.py:67, train.py:474), the masks, and the 3D targets.
 """
 import ctypes as C
+import json
 
 import numpy as np
 
@@ -202,7 +203,7 @@ class AmassSequenceGenerator(SequenceGenerator):
         lib = _capi.load_library()
         desc = np.ascontiguousarray(desc, np.int32)
         B, N, J = len(desc), self.seq_len, t.J
-        d_desc = torch.from_numpy(desc).to(t.device)
+        d_desc = torch.from_numpy(desc).pin_memory().to(t.device, non_blocking=True)    # (pinned: the host never waits for the stream)
         stream = torch.cuda.current_stream(t.device).cuda_stream
         kp3d = torch.empty((B, N, J, 3), dtype=torch.float32, device=t.device)
         smask = torch.empty((B, N), dtype=torch.uint8, device=t.device)
@@ -215,7 +216,7 @@ class AmassSequenceGenerator(SequenceGenerator):
         _capi.check(lib, st, None)
         out = {"kp3d": kp3d, "stride_mask": smask, "mask": pmask, "index": desc[:, 1].copy()}
         if camera_indices is not None:
-            out["cams"] = torch.from_numpy(self.cameras[np.asarray(camera_indices, np.int64)]).to(t.device)
+            out["cams"] = torch.from_numpy(self.cameras[np.asarray(camera_indices, np.int64)]).pin_memory().to(t.device, non_blocking=True)
         return out
 
     def batches(self, batch_size, drop_remainder=False):
@@ -225,6 +226,117 @@ class AmassSequenceGenerator(SequenceGenerator):
             if drop_remainder and len(desc) - b < batch_size:
                 break
             yield self.gather(desc[b:b + batch_size], cams[b:b + batch_size])
+
+
+class DescriptorStream(object):
+    """``dataset.repeat().batch(B)`` of the training split (train.py:104-108, 173-177) as window descriptors: successive generator
+    epochs, one ``descriptors()`` call each, back to back and cut into consecutive blocks of ``batch_size`` -- a block may straddle
+    two generator epochs.  ``next()`` -> (descriptors (B, 6) int32, camera indices (B,) int64 for an ``AmassSequenceGenerator``, else
+    None).  Host numpy only: the caller gathers the batch on the device.
+
+    ``state_dict()`` / ``load_state_dict()`` hold the position in the stream: the generator epochs started, the offset into the
+    current one and the generator's three random states at the START of that epoch.  Restoring replays that one ``descriptors()``
+    call (same shuffle, same mask-stride / shift / camera draws), so a resumed stream continues exactly where the saved one stood."""
+
+    RNGS = ("rng", "stride_shift_rng", "mask_stride_rng")
+
+    def __init__(self, generator, batch_size, prefetch=True):
+        if int(batch_size) < 1:
+            raise ValueError("batch_size must be positive")
+        self.generator, self.batch_size = generator, int(batch_size)
+        self.epochs = 0                      # generator epochs started
+        self.offset = 0                      # windows of the current generator epoch already handed out
+        self._desc = self._cams = None
+        self._epoch_rngs = None              # the generator's random states before the current epoch's descriptors() call
+        # prefetch: the NEXT generator epoch's descriptors are built on a worker thread while this one is consumed (a Human3.6M
+        # training epoch is millions of windows, seconds of host work that would otherwise stall the step loop at the boundary);
+        # the calls still run one after the other, so the random draws are those of the plain sequence
+        self._pool = None
+        if prefetch:
+            from concurrent.futures import ThreadPoolExecutor
+            self._pool = ThreadPoolExecutor(max_workers=1)
+        self._next = None
+
+    def _rng_states(self):
+        return {k: getattr(self.generator, k).bit_generator.state for k in self.RNGS}
+
+    def _set_rng_states(self, states):
+        for k in self.RNGS:
+            r = np.random.default_rng()
+            r.bit_generator.state = states[k]
+            setattr(self.generator, k, r)
+
+    def _build_epoch(self):
+        rngs = self._rng_states()
+        desc = self.generator.descriptors()
+        cams = np.asarray(self.generator.camera_indices, np.int64) if isinstance(self.generator, AmassSequenceGenerator) else None
+        return rngs, desc, cams
+
+    def _drop_prefetch(self):
+        if self._next is not None:
+            self._next.result()
+            self._next = None
+
+    def _start_epoch(self):
+        if self._next is not None:
+            built, self._next = self._next.result(), None
+        else:
+            built = self._build_epoch()
+        self._epoch_rngs, self._desc, self._cams = built
+        if len(self._desc) == 0:
+            raise ValueError("the generator yields no windows")
+        self.epochs += 1
+        self.offset = 0
+        if self._pool is not None:
+            self._next = self._pool.submit(self._build_epoch)
+
+    def next(self):
+        parts, cams, need = [], [], self.batch_size
+        while need > 0:
+            if self._desc is None or self.offset == len(self._desc):
+                self._start_epoch()
+            take = min(need, len(self._desc) - self.offset)
+            parts.append(self._desc[self.offset:self.offset + take])
+            if self._cams is not None:
+                cams.append(self._cams[self.offset:self.offset + take])
+            self.offset += take
+            need -= take
+        return np.concatenate(parts, 0), (np.concatenate(cams, 0) if self._cams is not None else None)
+
+    def state_dict(self):
+        """JSON-serialisable (the random states hold 128-bit integers)."""
+        if self._desc is None:
+            self._drop_prefetch()
+        rngs = self._epoch_rngs if self._desc is not None else self._rng_states()
+        return {"epochs": int(self.epochs), "offset": int(self.offset), "rngs": json.loads(json.dumps(rngs))}
+
+    def load_state_dict(self, sd):
+        self._drop_prefetch()
+        self._set_rng_states(sd["rngs"])
+        self._desc = self._cams = None
+        self.epochs, self.offset = 0, 0
+        if int(sd["epochs"]) > 0:
+            self.epochs = int(sd["epochs"]) - 1
+            self._start_epoch()
+            if not 0 <= int(sd["offset"]) <= len(self._desc):
+                raise ValueError("stream offset beyond its generator epoch: the state belongs to another data set")
+            self.offset = int(sd["offset"])
+
+
+def validation_descriptors(generator, batch_size, examples):
+    """``dataset.repeat(2).batch(B).take(ceil(VE / B))`` (train.py:110-120, 179-189) as descriptors: the windows of two generator epochs
+    (an unshuffled generator repeats itself) cut to ``ceil(VE / B)`` batches, so the last batch wraps to the first windows.  ``examples``
+    = VALIDATION_EXAMPLES (-1: every window).  Returns (descriptors (rows, 6), camera indices or None, number of batches, examples)."""
+    desc = generator.descriptors()
+    cams = np.asarray(generator.camera_indices, np.int64) if isinstance(generator, AmassSequenceGenerator) else None
+    examples = len(desc) if int(examples) < 0 else int(examples)
+    if examples > len(desc):
+        raise ValueError(f"VALIDATION_EXAMPLES {examples} exceeds the {len(desc)} validation windows")
+    n_batches = int(np.ceil(examples / float(batch_size)))
+    rows = n_batches * int(batch_size)
+    desc2 = np.concatenate([desc, desc], 0)[:rows]
+    cams2 = None if cams is None else np.concatenate([cams, cams], 0)[:rows]
+    return desc2, cams2, n_batches, examples
 
 
 def world_to_cam_and_2d(sequences_3d, cams):

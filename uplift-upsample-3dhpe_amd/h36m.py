@@ -24,6 +24,9 @@ import numpy as np
 
 _TABLES = None
 
+# H36MOrder17P.flip_lr_indices() of the reference (common/dataset/keypoint_order.py): left / right joints swapped (train.py:323)
+FLIP_LR_INDICES = [5, 4, 3, 2, 1, 0, 6, 7, 8, 9, 10, 16, 15, 14, 13, 12, 11]
+
 
 def tables():
     """Calibration tables, joint orders, subject / action lists (utils/h36m_cameras.json)."""

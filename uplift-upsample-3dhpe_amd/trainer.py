@@ -91,6 +91,7 @@ class Trainer(object):
         # world size > 1: the skip decision of a non-finite step is taken on the REDUCED gradients (identical on every rank)
         self._skip_word = torch.zeros(1, dtype=torch.int32, device=dev)
         self._rank_word = torch.zeros(1, dtype=torch.int32, device=dev)    # this rank's non-finite word (autograd steps, world size > 1)
+        self._flag_copy = None                                             # count_skipped(), world size 1: the library's word, copied
         self._ready_cb = _capi.GRAD_READY_FN(lambda user, first, count, stream: self._buckets.ready(first, count, stream))
         _capi.check(lib, lib.uu3d_train_set_grad_callback(model._h, self._ready_cb, None), model._h)
         model._attach_trainer(self)
@@ -278,6 +279,19 @@ class Trainer(object):
         out = C.c_int32()
         _capi.check(self._lib, self._lib.uu3d_train_nonfinite(self.model._h, C.byref(out)), self.model._h)
         return out.value != 0
+
+    def count_skipped(self, counter):
+        """Adds the last step's skip decision (1 = the optimizer step was skipped for non-finite gradients, see apply_gradients) into
+        ``counter``, a one-element int32 device tensor, on the current stream: a device-side count of skipped steps, no host
+        synchronisation."""
+        if self._world() > 1:
+            counter.add_(self._skip_word)
+            return
+        if self._flag_copy is None:
+            self._flag_copy = self._torch.zeros(1, dtype=self._torch.int32, device=self.model.device)
+        _capi.check(self._lib, self._lib.uu3d_train_copy_nonfinite(self.model._h, C.c_void_p(self._flag_copy.data_ptr()), self._stream()),
+                    self.model._h)
+        counter.add_(self._flag_copy)
 
     def train_step(self, keypoints2d, keypoints3d, stride_masks, drop_path_uniform="draw", token_mask_uniform="draw", dropout_seed=None):
         loss, _, _ = self.forward_backward(keypoints2d, keypoints3d, stride_masks, drop_path_uniform, token_mask_uniform, dropout_seed)

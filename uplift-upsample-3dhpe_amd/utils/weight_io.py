@@ -13,6 +13,7 @@ The top-level layer names and the order inside each layer are those of ``weights
 the order inside a block is the Keras attribute-tracking order and is unverified against a real checkpoint --
 no ``.h5`` exists offline).
 """
+import os
 from collections import OrderedDict
 
 import numpy as np
@@ -20,6 +21,21 @@ import numpy as np
 from .hdf5_min import HDF5Error, read_hdf5, write_hdf5
 
 KERAS_VERSION = b"2.4.0"          # tensorflow==2.4.3 (reference requirements.txt:3)
+
+
+def resolve_weight_selector(weight_path, target_extension=".h5"):
+    """``--weights`` of train.py (weight_io.py:28-51): a path with an extension is taken as it is; a path without one is a prefix
+    ("out/checkpoints/best_weights") and resolves to the first file of its directory, in sorted order, whose name starts with the
+    prefix and ends with ``target_extension``.  None stays None; no match raises FileNotFoundError."""
+    if weight_path is None:
+        return None
+    if os.path.splitext(weight_path)[1]:
+        return weight_path
+    folder, prefix = os.path.split(weight_path)
+    found = sorted(f for f in os.listdir(folder) if f.startswith(prefix) and f.endswith(target_extension))
+    if not found:
+        raise FileNotFoundError(f"Found no weights that match: {weight_path} and extension {target_extension}")
+    return os.path.join(folder, found[0])
 
 
 def _layers_of(spec):
