@@ -40,6 +40,7 @@
 #include "uu3d_attn_h3.h"
 #include "uu3d_spatial.h"
 #include "uu3d_spatial_h3.h"
+#include "uu3d_spatial_p16.h"
 #include "uu3d_misc.h"
 #include "uu3d_train.h"
 #include "uu3d_bwd.h"
@@ -57,6 +58,7 @@ constexpr int kFR = 3;   // frames per wave in the MFMA spatial kernel (3 * 17 =
 #ifndef UU3D_SPATIAL_MT
 #define UU3D_SPATIAL_MT 1
 #endif
+constexpr int kP16FR = 7, kP16PW = 1;   // spatial_stack_p16_kernel: 7 frames = 119 tokens on 8 waves of one 16-token panel (uu3d_spatial_p16.h)
 constexpr int kSpatialMT = UU3D_SPATIAL_MT;   // token tiles per wave of the f16x3 spatial kernel: 1 = two waves per 3 frames (see uu3d_spatial_h3.h)
 
 std::string g_create_error;
@@ -143,6 +145,8 @@ struct uu3d_model {
     bool spatial_f32 = false;      // UU3D_SPATIAL=f32: exact-f32 MFMA spatial stack even in f16x3 mode
     bool spatial_h3_always = false;   // UU3D_SPATIAL=h3: f16x3 spatial stack for every launch size
     size_t sp_frag_off = 0;        // offset (halfs) of the spatial f16 fragment planes in harena
+    size_t sp_frag16_off = 0;      // the same in the 16-token-panel order of spatial_stack_p16_kernel
+    bool spatial_h3_tiles = false; // UU3D_SPATIAL=h3tiles: inference on the 32-token-tile kernel spatial_stack_h3_kernel (A/B runs)
     const float *s2t_wt = nullptr, *s2t_b = nullptr, *token = nullptr, *pe_t = nullptr;
     std::vector<BlockDev> tblocks, sblocks;
     const float *h1_wt = nullptr, *h1_b = nullptr, *h2_wt = nullptr, *h2_b = nullptr;
@@ -368,7 +372,8 @@ int uu3d_create(const uu3d_config* c, int device, uu3d_model** out) {
     }
     build_inventory(m);
     { const char* e = getenv("UU3D_SPATIAL"); m->spatial_valu = (e != nullptr && std::string(e) == "valu");
-      m->spatial_f32 = (e != nullptr && std::string(e) == "f32"); m->spatial_h3_always = (e != nullptr && std::string(e) == "h3"); }
+      m->spatial_f32 = (e != nullptr && std::string(e) == "f32"); m->spatial_h3_always = (e != nullptr && std::string(e) == "h3");
+      m->spatial_h3_tiles = (e != nullptr && std::string(e) == "h3tiles"); }
     { const char* e = getenv("UU3D_NO_PLANES"); m->no_planes = (e != nullptr && e[0] == '1'); }
     { const char* e = getenv("UU3D_ATTN_WG"); m->attn_wg = (e != nullptr && e[0] == '1'); }
     { const char* e = getenv("UU3D_NO_MLPF"); m->no_mlpf = (e != nullptr && e[0] == '1'); }
@@ -723,6 +728,31 @@ int uu3d_commit_weights(uu3d_model* m, void* stream_) {
                                     const float x = s[(size_t)(16 * kk + 8 * (lane >> 5) + e) * Nn + 32 * nt + (lane & 31)];
                                     const _Float16 h = h3_hi(x);
                                     const size_t at = (size_t)off + (((size_t)(nt * (K / 16) + kk) * 2) * 64 + lane) * 8 + e;
+                                    d[at] = h;
+                                    d[at + 64 * 8] = (_Float16)((x - (float)h) * H3_SCALE);
+                                }
+                };
+                frag(FL::fq, "/attn/wq/kernel", ds, ds); frag(FL::fk, "/attn/wk/kernel", ds, ds);
+                frag(FL::fv, "/attn/wv/kernel", ds, ds); frag(FL::fp, "/attn/projection/kernel", ds, ds);
+                frag(FL::f1, "/mlp/fc1/kernel", ds, kHS); frag(FL::f2, "/mlp/fc2/kernel", kHS, ds);
+            }
+        }
+        {   // the same matrices for spatial_stack_p16_kernel (uu3d_spatial_p16.h): [n-tile 16][k-step 32][plane][lane][8], k in p16_kch order
+            using FL = SpatialFragLayoutP16;
+            m->sp_frag16_off = align_up(hb.size(), 64);
+            hb.resize(m->sp_frag16_off + (size_t)c.spatial_depth * FL::size);
+            for (int i = 0; i < c.spatial_depth; ++i) {
+                const std::string p = "spatial_block_" + std::to_string(i + 1);
+                _Float16* d = hb.data() + m->sp_frag16_off + (size_t)i * FL::size;
+                auto frag = [&](int off, const std::string& nm, int K, int Nn) {
+                    const float* s = W(m, p + nm);
+                    for (int nt = 0; nt < Nn / 16; ++nt)
+                        for (int ks = 0; ks < K / 32; ++ks)
+                            for (int lane = 0; lane < 64; ++lane)
+                                for (int j = 0; j < 8; ++j) {
+                                    const float x = s[(size_t)p16_kch(ks, lane >> 4, j) * Nn + 16 * nt + (lane & 15)];
+                                    const _Float16 h = h3_hi(x);
+                                    const size_t at = (size_t)off + (((size_t)(nt * (K / 32) + ks) * 2) * 64 + lane) * 8 + j;
                                     d[at] = h;
                                     d[at + 64 * 8] = (_Float16)((x - (float)h) * H3_SCALE);
                                 }
@@ -1432,13 +1462,23 @@ int forward_impl(uu3d_model* m, const float* kp2d, const FramesIn* frames, const
             Lh.end();
         } else if (c.precision == UU3D_PREC_F16X3 && !m->spatial_f32 && (m->spatial_h3_always || spatial_h3_pays(M))) {
             sp.blocks = m->sp_blocks_v2;             // LayerNorm parameters and biases
-            auto kern = spatial_stack_h3_kernel<kJ, kFR, kSpatialMT>;
-            Lh.begin("spatial_stack", "spatial_h3", fl, 4.0 * M * J * (2.0 + ds));
-            if (!(skip_mask() & 1))
-            hipLaunchKernelGGL(kern, dim3((M + kFR - 1) / kFR), dim3(64 * (2 / kSpatialMT)), sh3::lds_bytes(), Lh.stream, kp2d, sp,
-                               m->harena + m->sp_frag_off, w.S, s2t_planes ? reinterpret_cast<_Float16*>(w.S) : (_Float16*)nullptr,
-                               s2t_planes ? reinterpret_cast<_Float16*>(w.S) + (size_t)M * J * ds : (_Float16*)nullptr, SpatialTrainIO{});
-            Lh.end();
+            _Float16* s_hi = s2t_planes ? reinterpret_cast<_Float16*>(w.S) : (_Float16*)nullptr;
+            _Float16* s_lo = s2t_planes ? reinterpret_cast<_Float16*>(w.S) + (size_t)M * J * ds : (_Float16*)nullptr;
+            if (m->spatial_h3_tiles) {
+                auto kern = spatial_stack_h3_kernel<kJ, kFR, kSpatialMT>;
+                Lh.begin("spatial_stack", "spatial_h3", fl, 4.0 * M * J * (2.0 + ds));
+                if (!(skip_mask() & 1))
+                hipLaunchKernelGGL(kern, dim3((M + kFR - 1) / kFR), dim3(64 * (2 / kSpatialMT)), sh3::lds_bytes(), Lh.stream, kp2d, sp,
+                                   m->harena + m->sp_frag_off, w.S, s_hi, s_lo, SpatialTrainIO{});
+                Lh.end();
+            } else {
+                auto kern = spatial_stack_p16_kernel<kJ, kP16FR, kP16PW>;
+                Lh.begin("spatial_stack", "spatial_p16", fl, 4.0 * M * J * (2.0 + ds));
+                if (!(skip_mask() & 1))
+                hipLaunchKernelGGL(kern, dim3((M + kP16FR - 1) / kP16FR), dim3(64 * p16_waves(kJ, kP16FR, kP16PW)), sp16::lds_bytes<kP16FR>(c.spatial_depth),
+                                   Lh.stream, kp2d, sp, m->harena + m->sp_frag16_off, w.S, s_hi, s_lo);
+                Lh.end();
+            }
         } else {
             sp.blocks = m->sp_blocks_v2;
             auto kern = spatial_stack_mfma_kernel<kJ, kFR>;
@@ -1730,12 +1770,21 @@ int uu3d_frame_features(uu3d_model* m, const float* frames_dev, int32_t F, float
         Lh.end();
     } else if (h3) {
         sp.blocks = m->sp_blocks_v2;
-        auto kern = spatial_stack_h3_kernel<kJ, kFR, kSpatialMT>;
-        Lh.begin("spatial_stack", "spatial_h3", fl, 4.0 * M * J * (2.0 + ds));
-        hipLaunchKernelGGL(kern, dim3((M + kFR - 1) / kFR), dim3(64 * (2 / kSpatialMT)), sh3::lds_bytes(), Lh.stream, frames_dev, sp,
-                           m->harena + m->sp_frag_off, w.S, s2t_planes ? reinterpret_cast<_Float16*>(w.S) : (_Float16*)nullptr,
-                           s2t_planes ? reinterpret_cast<_Float16*>(w.S) + (size_t)M * J * ds : (_Float16*)nullptr, SpatialTrainIO{});
-        Lh.end();
+        _Float16* s_hi = s2t_planes ? reinterpret_cast<_Float16*>(w.S) : (_Float16*)nullptr;
+        _Float16* s_lo = s2t_planes ? reinterpret_cast<_Float16*>(w.S) + (size_t)M * J * ds : (_Float16*)nullptr;
+        if (m->spatial_h3_tiles) {
+            auto kern = spatial_stack_h3_kernel<kJ, kFR, kSpatialMT>;
+            Lh.begin("spatial_stack", "spatial_h3", fl, 4.0 * M * J * (2.0 + ds));
+            hipLaunchKernelGGL(kern, dim3((M + kFR - 1) / kFR), dim3(64 * (2 / kSpatialMT)), sh3::lds_bytes(), Lh.stream, frames_dev, sp,
+                               m->harena + m->sp_frag_off, w.S, s_hi, s_lo, SpatialTrainIO{});
+            Lh.end();
+        } else {
+            auto kern = spatial_stack_p16_kernel<kJ, kP16FR, kP16PW>;
+            Lh.begin("spatial_stack", "spatial_p16", fl, 4.0 * M * J * (2.0 + ds));
+            hipLaunchKernelGGL(kern, dim3((M + kP16FR - 1) / kP16FR), dim3(64 * p16_waves(kJ, kP16FR, kP16PW)), sp16::lds_bytes<kP16FR>(c.spatial_depth),
+                               Lh.stream, frames_dev, sp, m->harena + m->sp_frag16_off, w.S, s_hi, s_lo);
+            Lh.end();
+        }
     } else {
         sp.blocks = m->sp_blocks_v2;
         auto kern = spatial_stack_mfma_kernel<kJ, kFR>;
