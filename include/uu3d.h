@@ -173,6 +173,44 @@ int uu3d_mpjpe(const float* pred_dev, const float* gt_dev, int32_t batch, int32_
                int32_t root_index, double* out_dev, void* stream);
 
 /*
+ * The evaluation report on the device.  Replaces evaluation._frame_metrics (metrics.mpjpe, metrics.nmpjpe(alignment="root"),
+ * metrics.pmpjpe, all normalize=False; common/dataset/metrics.py:13-201), interpolate_between_keyframes
+ * (common/dataset/action_wise_eval.py:77-100) and the sums behind h36_action_wise_eval / frame_wise_eval (:17-74), in float64.
+ * Stream-ordered, no host synchronisation.
+ *
+ *   pred_dev (num_rows, J, 3), gt_dev (num_poses, J, gt_channels): float32 (inputs_f64 = 0: the product path; run_eval and
+ *     run_train never pass anything else), widened exactly.  inputs_f64 = 1 reads both as float64: a verification aid, there so that
+ *     poses which exist in float64 only (the reference's own metric fixtures) can be held to the 1e-9 m bounds without rounding the
+ *     inputs first; it runs the same kernel source with another load type.  gt_channels 3: every joint valid; 4: (x, y, z, valid), a joint with valid <= 0 gives -1.  J <= 32.
+ *   left_dev / right_dev (num_poses) int32, weight_dev (num_poses) float64: pose i is
+ *     pred[left[i]] * (1 - weight[i]) + pred[right[i]] * weight[i], formed in float64 and never written to memory
+ *     (evaluation.keyframe_plan builds the three arrays).  weight_dev NULL: pose i is pred[left[i]]; left_dev NULL as well: row i.
+ *     A row index outside [0, num_rows) makes the pose NaN: it drops out of every sum.
+ *   errors_out_dev (num_poses, J, 3) float64 or NULL: (mpjpe, nmpjpe, pmpjpe) per joint in metres.
+ *   sums_out_dev (num_actions + 1, 3, 2) float64 or NULL: per action and metric the sum of the errors >= 0 and their count; the last
+ *     row is over all poses.  actions_dev (num_poses) int32 (NULL with num_actions = 0); an action outside [0, num_actions) counts in
+ *     the last row only.  num_actions <= 63.  Partial sums per workgroup in a fixed order and one ordered combine: no floating-point
+ *     atomics, two calls give the same bits.  Needs scratch of uu3d_error_sums_scratch_bytes(num_poses, num_actions) bytes.
+ *   select_dev (num_poses) uint8 or NULL: poses with 0 are not evaluated (their rows are not read, their errors are -1, they are in
+ *     no sum) -- the KEYFRAMES report.
+ * At least one of errors_out_dev / sums_out_dev.  The sums of the fused call and of uu3d_error_sums on its error array agree bit for bit
+ * only while a tile holds 64 poses (J = 17 in float32 does); larger poses are tiled smaller and summed in another order.
+ */
+int uu3d_pose_errors(const void* pred_dev, int64_t num_rows, const int32_t* left_dev, const int32_t* right_dev,
+                     const double* weight_dev, const void* gt_dev, int64_t num_poses, int32_t num_keypoints, int32_t gt_channels,
+                     int32_t root_index, int32_t inputs_f64, double* errors_out_dev, const int32_t* actions_dev,
+                     int32_t num_actions, const uint8_t* select_dev, double* sums_out_dev, void* scratch, size_t scratch_bytes,
+                     void* stream);
+
+/* The sums table of uu3d_pose_errors from an error array (num_poses, J, 3) float64 that is already in memory (any number of joints). */
+int uu3d_error_sums(const double* errors_dev, int64_t num_poses, int32_t num_keypoints, const int32_t* actions_dev,
+                    int32_t num_actions, const uint8_t* select_dev, double* sums_out_dev, void* scratch, size_t scratch_bytes,
+                    void* stream);
+
+/* Scratch bytes of the two calls above (0 for arguments they would refuse). */
+size_t uu3d_error_sums_scratch_bytes(int64_t num_poses, int32_t num_actions);
+
+/*
  * "Next" row 3 of the scope table: the window / stride-mask generator as a gather over a RESIDENT pose table.
  * Replaces the per-sample slicing, padding, stride mask and flip of H36mSequenceGenerator
  * (common/dataset/uplifiting_dataset.py:322-407) plus the harness's `x * stride_mask` (eval.py:67, train.py:474).

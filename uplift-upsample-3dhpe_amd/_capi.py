@@ -30,6 +30,7 @@ EXPORTED_SYMBOLS = (
     "uu3d_train_forward_tape", "uu3d_train_backward_tape", "uu3d_tape_destroy", "uu3d_train_clear_nonfinite",
     "uu3d_train_backward_tape_accumulate", "uu3d_train_copy_nonfinite",
     "uu3d_frame_features_bytes", "uu3d_frame_features", "uu3d_gather_window_frames", "uu3d_forward_frames_ex",
+    "uu3d_pose_errors", "uu3d_error_sums", "uu3d_error_sums_scratch_bytes",
 )
 # include/uu3d_ops.h
 OPS_SYMBOLS = (
@@ -127,6 +128,12 @@ def load_library(path=None):
     lib.uu3d_range_status.argtypes = [vp, vp, C.POINTER(i32)]
     lib.uu3d_mpjpe.restype = C.c_int
     lib.uu3d_mpjpe.argtypes = [vp, vp, i32, i32, i32, vp, vp]
+    lib.uu3d_pose_errors.restype = C.c_int
+    lib.uu3d_pose_errors.argtypes = [vp, i64, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, sz, vp]
+    lib.uu3d_error_sums.restype = C.c_int
+    lib.uu3d_error_sums.argtypes = [vp, i64, i32, vp, i32, vp, vp, vp, sz, vp]
+    lib.uu3d_error_sums_scratch_bytes.restype = sz
+    lib.uu3d_error_sums_scratch_bytes.argtypes = [i64, i32]
     lib.uu3d_gather_windows.restype = C.c_int
     lib.uu3d_gather_windows.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp]
     lib.uu3d_frame_features_bytes.restype = sz

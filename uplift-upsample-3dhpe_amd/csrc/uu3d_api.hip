@@ -42,6 +42,7 @@
 #include "uu3d_spatial_h3.h"
 #include "uu3d_spatial_p16.h"
 #include "uu3d_misc.h"
+#include "uu3d_metrics.h"
 #include "uu3d_train.h"
 #include "uu3d_bwd.h"
 #include "uu3d_launch.h"
@@ -1819,6 +1820,60 @@ int uu3d_range_status(uu3d_model* m, void* stream, int32_t* out_flag) {
 int uu3d_mpjpe(const float* pred, const float* gt, int32_t B, int32_t J, int32_t root, double* out, void* stream) {
     if (!pred || !gt || !out || B < 1 || J < 1 || root < 0 || root >= J) return UU3D_ERR_INVALID_ARGUMENT;
     hipLaunchKernelGGL(mpjpe_kernel, dim3((B * J + 255) / 256), dim3(256), 0, (hipStream_t)stream, pred, gt, B, J, root, out);
+    return hipGetLastError() == hipSuccess ? UU3D_OK : UU3D_ERR_HIP;
+}
+
+// ---- evaluation report on the device (uu3d_metrics.h) ----
+size_t uu3d_error_sums_scratch_bytes(int64_t num_poses, int32_t num_actions) {
+    if (num_poses < 1 || num_actions < 0 || num_actions > kMetMaxActions) return 0;
+    return (size_t)kMetMaxGrid * (size_t)(num_actions + 1) * 6 * sizeof(double);
+}
+
+static bool met_sums_args_ok(int64_t P, const int32_t* actions, int32_t A, double* sums, void* scratch, size_t scratch_bytes) {
+    if (A < 0 || A > kMetMaxActions || (A > 0 && !actions) || !sums || !scratch || ((uintptr_t)scratch & 7) != 0) return false;
+    return scratch_bytes >= uu3d_error_sums_scratch_bytes(P, A);
+}
+
+int uu3d_pose_errors(const void* pred, int64_t R, const int32_t* left, const int32_t* right, const double* weight, const void* gt,
+                     int64_t P, int32_t J, int32_t Cg, int32_t root, int32_t inputs_f64, double* errors, const int32_t* actions,
+                     int32_t A, const uint8_t* select, double* sums, void* scratch, size_t scratch_bytes, void* stream_) {
+    if (!pred || !gt || R < 1 || P < 1 || J < 1 || J > kMetMaxJoints || (Cg != 3 && Cg != 4) || root < 0 || root >= J ||
+        (inputs_f64 != 0 && inputs_f64 != 1) || (!errors && !sums) || (weight && (!left || !right)) || (!left && P > R) ||
+        P > (int64_t)1 << 40 || R > INT32_MAX)
+        return UU3D_ERR_INVALID_ARGUMENT;
+    if (sums && !met_sums_args_ok(P, actions, A, sums, scratch, scratch_bytes)) return UU3D_ERR_INVALID_ARGUMENT;
+    hipStream_t stream = (hipStream_t)stream_;
+    const int elem = inputs_f64 ? 8 : 4;
+    const int gstride = (J * Cg) | 1;
+    const int per_pose = ((J * 3) | 1) * 8 + gstride * elem;
+    const int ppb = std::min(kMetLanes, kMetLdsBudget / per_pose);
+    const long tiles = (P + ppb - 1) / ppb;
+    const int grid = (int)std::min<long>(tiles, kMetMaxGrid);
+    double* partial = sums ? (double*)scratch : nullptr;
+    if (inputs_f64)
+        hipLaunchKernelGGL(pose_errors_kernel<double>, dim3(grid), dim3(kMetLanes), (size_t)ppb * per_pose, stream, (const double*)pred, (long)R, left,
+                           right, weight, (const double*)gt, (long)P, J, Cg, root, ppb, gstride, errors, actions, A, select, partial);
+    else
+        hipLaunchKernelGGL(pose_errors_kernel<float>, dim3(grid), dim3(kMetLanes), (size_t)ppb * per_pose, stream, (const float*)pred, (long)R, left,
+                           right, weight, (const float*)gt, (long)P, J, Cg, root, ppb, gstride, errors, actions, A, select, partial);
+    if (hipGetLastError() != hipSuccess) return UU3D_ERR_HIP;
+    if (sums) {
+        hipLaunchKernelGGL(error_sums_combine_kernel, dim3(1), dim3(64), 0, stream, partial, grid, (A + 1) * 6, sums);
+        if (hipGetLastError() != hipSuccess) return UU3D_ERR_HIP;
+    }
+    return UU3D_OK;
+}
+
+int uu3d_error_sums(const double* errors, int64_t P, int32_t J, const int32_t* actions, int32_t A, const uint8_t* select, double* sums,
+                    void* scratch, size_t scratch_bytes, void* stream_) {
+    if (!errors || P < 1 || P > (int64_t)1 << 40 || J < 1 || !met_sums_args_ok(P, actions, A, sums, scratch, scratch_bytes))
+        return UU3D_ERR_INVALID_ARGUMENT;
+    hipStream_t stream = (hipStream_t)stream_;
+    const long tiles = (P + kMetLanes - 1) / kMetLanes;
+    const int grid = (int)std::min<long>(tiles, kMetMaxGrid);
+    hipLaunchKernelGGL(error_sums_kernel, dim3(grid), dim3(kMetLanes), 0, stream, errors, (long)P, J, actions, A, select, (double*)scratch);
+    if (hipGetLastError() != hipSuccess) return UU3D_ERR_HIP;
+    hipLaunchKernelGGL(error_sums_combine_kernel, dim3(1), dim3(64), 0, stream, (const double*)scratch, grid, (A + 1) * 6, sums);
     return hipGetLastError() == hipSuccess ? UU3D_OK : UU3D_ERR_HIP;
 }
 

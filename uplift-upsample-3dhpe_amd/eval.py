@@ -295,15 +295,71 @@ def _unflip(raw, config, flip):
     return (raw[0] + f) / 2.0
 
 
+def evaluate_windows(model, generator, desc, config, action_wise=True, batch_size=None, skip_unused_windows=True, log=_log, depth=None,
+                     graph=True, reuse_frames=False, device_metrics=False):
+    """The timed part of ``run_eval``: the windows ``desc`` of ``generator`` (whose table holds the 3D ground truth) forwarded, gathered over
+    the ranks and reported.  -> the report dict with "num_windows", "num_forwarded" and "seconds" (this function's wall time)."""
+    import torch
+    gen, table = generator, generator.table
+    W = len(desc)
+    start = time.time()
+    frame_idx = desc[:, 1].copy()
+    need = needed_windows(frame_idx, config) if skip_unused_windows else np.ones(W, bool)
+    run = np.flatnonzero(need)
+    rank, world = 0, 1
+    import torch.distributed as tdist
+    if tdist.is_available() and tdist.is_initialized():
+        rank, world = tdist.get_rank(), tdist.get_world_size()
+    lo, hi = udist.shard_bounds(len(run), rank, world)
+    bs = int(batch_size or config.BATCH_SIZE)
+    local = predict_windows(model, gen, desc[run[lo:hi]], config, bs, flip=bool(config.EVAL_FLIP), depth=depth, graph=graph,
+                            reuse_frames=reuse_frames)
+    allp = udist.allgather_errors(local)                             # (len(run), J, 3) in rank order: the payload is a few KB per rank
+    # ground truth of the window centres, root shifted (eval.py:183-186); the centre of a window is frame `index` of its video
+    mid = desc[:, 1].astype(np.int64) + table.starts[desc[:, 0]]
+    actions = table.actions[desc[:, 0]]
+    if config.SEQUENCE_STRIDE > 1 and config.TEST_STRIDED_EVAL is True:
+        log("Performing strided eval: Interpolating between keyframes")
+    if device_metrics:
+        # predictions and ground truth stay in HBM: interpolation, metrics and the report sums in csrc/uu3d_metrics.h (the metrics root-align
+        # or centre the ground truth themselves)
+        from . import evaluation_device
+        rows = np.full(W, -1, np.int64)
+        rows[run] = np.arange(len(run))
+        gt_dev = table.kp3d[torch.as_tensor(mid, device=table.device)]
+        res = evaluation_device.evaluate_predictions_device(allp, gt_dev, actions, frame_idx, config, action_wise=action_wise, rows=rows)
+    else:
+        pred = np.zeros((W, table.J, 3), np.float64)
+        pred[run] = allp.detach().cpu().numpy().astype(np.float64)
+        gt = table.kp3d[torch.as_tensor(mid, device=table.device)].cpu().numpy().astype(np.float64)
+        gt = gt - gt[:, config.ROOT_KEYTPOINT:config.ROOT_KEYTPOINT + 1, :]
+        res = evaluation.evaluate_predictions(pred, gt, actions, frame_idx, config, action_wise=action_wise)
+    res["num_windows"], res["num_forwarded"] = int(W), int(len(run))
+    res["seconds"] = time.time() - start
+    for title, key in (("ALL FRAMES", "all_frames"), ("KEYFRAMES", "keyframes")):
+        if res[key] is None:
+            continue
+        log("")
+        log(f"### Evaluation on {title} ####")
+        log("")
+        fr = res[key][0] if action_wise else res[key]
+        log("  ".join(f"{k}: {v:.2f}" for k, v in fr.items()))
+    log(f"Finished evaluation in {res['seconds']:.1f} s ({len(run)} of {W} windows forwarded)")
+    return res
+
+
 def run_eval(config, dataset_name, dataset_path, dataset2d_path, test_subset, weights_path=None, model=None, action_wise=True,
-             batch_size=None, skip_unused_windows=True, log=_log, depth=None, graph=True, reuse_frames=False):
+             batch_size=None, skip_unused_windows=True, log=_log, depth=None, graph=True, reuse_frames=False, device_metrics=False):
     """eval.py:34-253.  Returns ``evaluation.evaluate_predictions``'s dict (+ "num_windows", "num_forwarded", "seconds").
+
+    ``device_metrics=True``: the report (keyframe interpolation, MPJPE / N-MPJPE / P-MPJPE, per-action means) is computed on the device
+    from the predictions where they lie (``evaluation_device.evaluate_predictions_device``; with several ranks each evaluates a shard
+    of the poses) instead of in float64 numpy on the host: the same dict within 1e-5 mm.
 
     ``batch_size`` defaults to ``config.BATCH_SIZE``; ``depth`` / ``graph``: batches in flight and hipGraph replay of the forward
     (``predict_windows``; depth 1 without graph = the reference's eager loop, same numbers); ``reuse_frames``: each frame's spatial
     features computed once (``predict_windows``).  With torch.distributed initialised, the windows to run are split
     contiguously over the ranks and the predictions all-gathered; every rank returns the same report."""
-    import torch
     from .net.uplift_upsample_transformer_constructor import build_uplift_upsample_transformer
     assert not (weights_path is None and model is None)
     if model is None:
@@ -325,44 +381,10 @@ def run_eval(config, dataset_name, dataset_path, dataset2d_path, test_subset, we
                             flip_lr_indices=config.AUGM_FLIP_KEYPOINT_ORDER, mask_stride=config.MASK_STRIDE,
                             stride_mask_align_global=True, rand_shift_stride_mask=False, shuffle=False)
     desc = gen.descriptors()
-    W = len(desc)
-    log(f"Sequences: {W}")
-    log(f"Running evaluation on '{test_subset}' with {W} examples")
-    start = time.time()
-    frame_idx = desc[:, 1].copy()
-    need = needed_windows(frame_idx, config) if skip_unused_windows else np.ones(W, bool)
-    run = np.flatnonzero(need)
-    rank, world = 0, 1
-    import torch.distributed as tdist
-    if tdist.is_available() and tdist.is_initialized():
-        rank, world = tdist.get_rank(), tdist.get_world_size()
-    lo, hi = udist.shard_bounds(len(run), rank, world)
-    bs = int(batch_size or config.BATCH_SIZE)
-    local = predict_windows(model, gen, desc[run[lo:hi]], config, bs, flip=bool(config.EVAL_FLIP), depth=depth, graph=graph,
-                            reuse_frames=reuse_frames)
-    allp = udist.allgather_errors(local)                             # (len(run), J, 3) in rank order: the payload is a few KB per rank
-    pred = np.zeros((W, table.J, 3), np.float64)
-    pred[run] = allp.detach().cpu().numpy().astype(np.float64)
-    # ground truth of the window centres, root shifted (eval.py:183-186); the centre of a window is frame `index` of its video
-    mid = desc[:, 1].astype(np.int64) + table.starts[desc[:, 0]]
-    gt = table.kp3d[torch.as_tensor(mid, device=table.device)].cpu().numpy().astype(np.float64)
-    gt = gt - gt[:, config.ROOT_KEYTPOINT:config.ROOT_KEYTPOINT + 1, :]
-    actions = table.actions[desc[:, 0]]
-    if config.SEQUENCE_STRIDE > 1 and config.TEST_STRIDED_EVAL is True:
-        log("Performing strided eval: Interpolating between keyframes")
-    res = evaluation.evaluate_predictions(pred, gt, actions, frame_idx, config, action_wise=action_wise)
-    res["num_windows"], res["num_forwarded"] = int(W), int(len(run))
-    res["seconds"] = time.time() - start
-    for title, key in (("ALL FRAMES", "all_frames"), ("KEYFRAMES", "keyframes")):
-        if res[key] is None:
-            continue
-        log("")
-        log(f"### Evaluation on {title} ####")
-        log("")
-        fr = res[key][0] if action_wise else res[key]
-        log("  ".join(f"{k}: {v:.2f}" for k, v in fr.items()))
-    log(f"Finished evaluation in {res['seconds']:.1f} s ({len(run)} of {W} windows forwarded)")
-    return res
+    log(f"Sequences: {len(desc)}")
+    log(f"Running evaluation on '{test_subset}' with {len(desc)} examples")
+    return evaluate_windows(model, gen, desc, config, action_wise=action_wise, batch_size=batch_size, skip_unused_windows=skip_unused_windows,
+                            log=log, depth=depth, graph=graph, reuse_frames=reuse_frames, device_metrics=device_metrics)
 
 
 def run_eval_multi_mask_stride(config, *args, log=_log, **kwargs):

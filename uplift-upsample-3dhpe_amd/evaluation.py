@@ -125,6 +125,60 @@ def interpolate_between_keyframes(pred3d, frame_indices, keyframe_stride):
     return interp, keyframes
 
 
+def keyframe_plan(frame_indices, keyframe_stride, rows=None):
+    """``interpolate_between_keyframes`` as a gather plan, without a loop over frames: -> (left, right, weight, keyframes) with
+    ``interp[i] = pred3d[left[i]] * (1 - weight[i]) + pred3d[right[i]] * weight[i]``.  A keyframe, a frame in front of its video's first
+    keyframe and a frame behind its last one have ``left == right`` and weight 0 (their own prediction, or the last keyframe's); the
+    weight counts positions, not frame numbers.
+
+    ``rows`` (positions -> row of the array that holds the forwarded predictions, -1: not forwarded): left / right are returned as
+    rows of that array, and a position whose plan needs a row that was not forwarded raises ValueError."""
+    f = np.asarray(frame_indices).astype(np.int64)
+    n = len(f)
+    pos = np.arange(n, dtype=np.int64)
+    key = np.equal(np.mod(f, keyframe_stride), 0)
+    new = np.ones(n, bool)
+    new[1:] = f[1:] <= f[:-1]                                        # a drop (or repeat) of the frame index starts a new video
+    video = np.cumsum(new) - 1
+    start = np.maximum.accumulate(np.where(new, pos, 0)) if n else pos
+    last = np.maximum.accumulate(np.where(key, pos, -1)) if n else pos
+    has_last = last >= start
+    nxt = np.minimum.accumulate(np.where(key, pos, n)[::-1])[::-1] if n else pos
+    has_next = nxt < n
+    has_next[has_next] = video[nxt[has_next]] == video[has_next]
+    between = ~key & has_last & has_next
+    tail = ~key & has_last & ~has_next
+    left, right, weight = pos.copy(), pos.copy(), np.zeros(n, np.float64)
+    left[between], right[between] = last[between], nxt[between]
+    weight[between] = (pos[between] - last[between]) / (nxt[between] - last[between]).astype(np.float64)
+    left[tail] = right[tail] = last[tail]
+    if rows is not None:
+        rows = np.asarray(rows).astype(np.int64)
+        left, right = rows[left], rows[right]
+        missing = np.flatnonzero((left < 0) | (right < 0))
+        if len(missing):
+            raise ValueError(f"{len(missing)} positions need a prediction that was not forwarded (first: position {int(missing[0])}, "
+                             f"frame {int(f[missing[0]])})")
+    return left, right, weight, key
+
+
+def report_from_sums(sums, action_wise=True, action_set=None):
+    """The report of ``h36_action_wise_eval`` / ``frame_wise_eval`` from a table ``sums[a, m] = (sum of the errors >= 0 in metres, their
+    count)`` with the actions of ``action_set`` in rows 0 .. A-1 and all poses in the last row (uu3d_pose_errors / uu3d_error_sums):
+    means over entries >= 0 in millimetres; average_results is the plain mean of the per-action means."""
+    sums = np.asarray(sums, np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = sums[..., 0] / sums[..., 1] * 1000.
+    frame_results = {k: mean[-1, m] for m, k in enumerate(METRICS)}
+    if not action_wise:
+        return frame_results
+    action_set = H36M_ACTIONS if action_set is None else action_set
+    assert len(mean) == len(action_set) + 1
+    per_action = {name: {k: mean[a, m] for m, k in enumerate(METRICS)} for a, name in enumerate(action_set)}
+    average_results = {k: np.mean([d[k] for d in per_action.values()]) for k in METRICS}
+    return frame_results, average_results, per_action
+
+
 def evaluate_predictions(pred3d, gt3d, actions, frame_indices, config, action_wise=True):
     """The bookkeeping of eval.py:195-251 on a finished run: pred3d (B,K,3), gt3d (B,K,3) root-relative, actions (B,),
     frame_indices (B,).  -> {"all_frames": ..., "keyframes": ... or None}; each entry is

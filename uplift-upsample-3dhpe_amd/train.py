@@ -116,9 +116,10 @@ class Validation(object):
     """The validation set of a run: descriptors of ``ceil(VE / B)`` full batches (the last one wraps), each rank's contiguous shard of
     every batch, and the eval-mode forwards of val_step (train.py:509-538) with EVAL_FLIP."""
 
-    def __init__(self, config, generator, is_h36m):
+    def __init__(self, config, generator, is_h36m, device_metrics=False):
         import torch
         self.config, self.gen, self.is_h36m = config, generator, is_h36m
+        self.device_metrics = bool(device_metrics)
         self.B = int(config.BATCH_SIZE)
         self.desc, self.cams, self.n_batches, self.examples = validation_descriptors(generator, self.B, config.VALIDATION_EXAMPLES)
         self.order = torch.as_tensor(np.asarray(config.AUGM_FLIP_KEYPOINT_ORDER), dtype=torch.long, device=generator.table.device)
@@ -137,7 +138,8 @@ class Validation(object):
 
     def run(self, model):
         """-> (val loss, metrics dict of the reference's names, per-window predictions (examples, J, 3) float64).  ``model`` holds the
-        weights to validate (val_model: the EMA weights when EMA_ENABLED)."""
+        weights to validate (val_model: the EMA weights when EMA_ENABLED).  With ``device_metrics`` the metrics come from
+        csrc/uu3d_metrics.h; the returned predictions are the same host array either way."""
         import torch
         rank, world = _rank_world()
         cfg = self.config
@@ -186,12 +188,25 @@ class Validation(object):
                     parts.append(allp[at[r]:at[r] + hi - lo])
                     at[r] += hi - lo
             local = torch.cat(parts, 0)
-        res = local[:self.examples].cpu().numpy().astype(np.float64)               # predictions trimmed to VALIDATION_EXAMPLES (:629-639)
-        pred, gt = res[..., :3], res[..., 3:]
-        gt = np.concatenate([gt, np.ones(gt.shape[:-1] + (1,))], axis=-1)         # dummy valid flag (:643-644)
         n_calls = self.n_batches * (2 if flip else 1)
         loss = float(loss_sum.item()) / n_calls
         metrics = {"loss": loss}
+        if self.device_metrics:
+            # the metrics where the predictions lie (csrc/uu3d_metrics.h); with several ranks each evaluates a shard of the examples
+            from . import evaluation_device
+            dpred, dgt = local[:self.examples, :, :3].contiguous(), local[:self.examples, :, 3:].contiguous()
+            A = len(evaluation.H36M_ACTIONS) if self.is_h36m else 0
+            actions = self.gen.table.actions[self.desc[:self.examples, 0]].astype(np.int32) if self.is_h36m else None
+            sums = evaluation_device.report_sums(dpred, dgt, root, [{}], num_actions=A, actions=actions)[0]
+            rep = evaluation.report_from_sums(sums, action_wise=self.is_h36m)
+            frame, aw = rep[:2] if self.is_h36m else (rep, None)
+            metrics.update({"MPJPE": float(frame["mpjpe"]), "NMPJPE": float(frame["nmpjpe"]), "PAMPJPE": float(frame["pampjpe"])})
+            if aw is not None:
+                metrics.update({"AW-MPJPE": float(aw["mpjpe"]), "AW-NMPJPE": float(aw["nmpjpe"]), "AW-PAMPJPE": float(aw["pampjpe"])})
+            return loss, metrics, dpred.cpu().numpy().astype(np.float64)
+        res = local[:self.examples].cpu().numpy().astype(np.float64)               # predictions trimmed to VALIDATION_EXAMPLES (:629-639)
+        pred, gt = res[..., :3], res[..., 3:]
+        gt = np.concatenate([gt, np.ones(gt.shape[:-1] + (1,))], axis=-1)         # dummy valid flag (:643-644)
         if self.is_h36m:
             actions = self.gen.table.actions[self.desc[:self.examples, 0]]
             frame, aw, _ = evaluation.h36_action_wise_eval(pred, gt, actions, root)
@@ -277,10 +292,13 @@ def run_epoch(trainer, stream, generator, steps, shard, loss_sum, skipped, snaps
 
 def run_train(config, dataset="h36m", dataset_val=None, h36m_path="./data/data_3d_h36m.npz",
               dataset_2d_path="./data/data_2d_h36m_cpn_ft_h36m_dbb.npz", amass_path=None, amass_frame_rate=50, train_subset="train",
-              val_subset="val", test_subset=None, weights=None, continue_training=False, out_dir="out", log=_log, config_file=None):
+              val_subset="val", test_subset=None, weights=None, continue_training=False, out_dir="out", log=_log, config_file=None,
+              device_metrics=False):
     """train.py:264-749.  ``config``: a config object or the path of a config file (``config_file``: the file an object came from,
     which names the dumped ``<stem>_complete.json``).  Returns {"history": {metric: [(epoch, value), ...]},
     "best_weights": path or None, "last_weights": path, "test_report": eval.run_eval_multi_mask_stride(...) or None}.
+    ``device_metrics``: the validation metrics and the test report are computed on the device (evaluation_device.py) instead of in numpy
+    on the host: the same history within 1e-5 mm, the same weights and checkpoints.
 
     With torch.distributed initialised: every rank builds the same descriptor stream and trains on its contiguous shard of each global
     batch (gradients summed over the ranks, normalised by the global BATCH_SIZE: the one-rank step), validates its shard of each val
@@ -333,7 +351,7 @@ def run_train(config, dataset="h36m", dataset_val=None, h36m_path="./data/data_3
         val_gen = h36m_generator(config, h36m_data, val_subset, "val", device, log)
     elif dataset_val == "amass" and val_subset is not None:
         val_gen, cameras = amass_generator(config, amass_path, h36m_path, val_subset, "val", amass_frame_rate, cameras, device, log)
-    validation = Validation(config, val_gen, val_dataset_name == "h36m") if val_gen is not None else None
+    validation = Validation(config, val_gen, val_dataset_name == "h36m", device_metrics=device_metrics) if val_gen is not None else None
     if validation is not None:
         log(f"val batches {validation.n_batches}")
     stream = DescriptorStream(train_gen, B)
@@ -453,7 +471,7 @@ def run_train(config, dataset="h36m", dataset_val=None, h36m_path="./data/data_3
             import torch.distributed as tdist
             tdist.barrier()                                                      # rank 0 wrote the file
         test_report = run_eval_multi_mask_stride(config, "h36m", h36m_path, dataset_2d_path, test_subset, weights_path=eval_path,
-                                                 model=None, action_wise=True, log=log)
+                                                 model=None, action_wise=True, log=log, device_metrics=device_metrics)
     log("Done.")
     return {"history": {m: list(hist.history[m]) for m in hist.metrics}, "best_weights": best_path, "last_weights": last_path,
             "test_report": test_report}
@@ -462,7 +480,8 @@ def run_train(config, dataset="h36m", dataset_val=None, h36m_path="./data/data_3
 # ---------------------------------------------------------------------------------------------------------------------------------
 # command line (train.py:194-305)
 # ---------------------------------------------------------------------------------------------------------------------------------
-def build_parser():
+def build_parser(extensions=False):
+    """The reference's flags (train.py:200-263); ``extensions``: plus the flags this package adds (``--device_metrics``)."""
     p = argparse.ArgumentParser(description="2D-to-3D uplifting training for strided poseformer.")
     p.add_argument("--config", required=False, default=None, metavar="/path/to/config.json",
                    help="Path to the config file. Overwrites the default configs in the code.")
@@ -487,12 +506,15 @@ def build_parser():
                    help="Continue a previously started training from its latest checkpoint in out_dir.")
     p.add_argument("--out_dir", required=True, metavar="/path/to/output_directory",
                    help="Logs and checkpoint directory. Also used to search for checkpoints if continue_training is set.")
+    if extensions:
+        p.add_argument("--device_metrics", required=False, default=False, action="store_true",
+                       help="Compute the validation and test metrics on the GPU instead of in numpy on the host (same numbers within 1e-5 mm).")
     return p
 
 
 def parse_args(argv=None):
     """The reference's argument clean-up (train.py:261-265, 291)."""
-    args = build_parser().parse_args(argv)
+    args = build_parser(extensions=True).parse_args(argv)
     args.continue_training = args.continue_training not in [False, "False", "false", "f", "n", "0"]
     args.val_subset = None if args.val_subset in ["none", "None", "", 0] else args.val_subset
     args.test_subset = None if args.test_subset in ["none", "None", "", 0] else args.test_subset
@@ -515,7 +537,8 @@ def main(argv=None):
     run_train(config, dataset=args.dataset, dataset_val=args.dataset_val, h36m_path=expand(args.h36m_path),
               dataset_2d_path=expand(args.dataset_2d_path), amass_path=expand(args.amass_path), amass_frame_rate=args.amass_frame_rate,
               train_subset=args.train_subset, val_subset=args.val_subset, test_subset=args.test_subset, weights=expand(args.weights),
-              continue_training=args.continue_training, out_dir=expand(args.out_dir), config_file=expand(args.config))
+              continue_training=args.continue_training, out_dir=expand(args.out_dir), config_file=expand(args.config),
+              device_metrics=args.device_metrics)
     return 0
 
 
