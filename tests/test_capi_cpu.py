@@ -92,3 +92,47 @@ def test_build_is_keyed_by_content_not_by_file_times(tmp_path):
         assert b._stale(b.LIB)                                                 # a binary of other sources passes for stale whatever its mtime
     finally:
         open(stamp, "w").write(good)
+
+
+def test_environment_switches_live_in_one_table():
+    """Every UU3D_* variable the library reads is read by one of the two reader functions of csrc/uu3d_switches.h (read_switches: per
+    handle, process_switches: per process), nowhere else, and INTEGRATION.md section 5 lists exactly those names."""
+    import glob
+    import re
+    csrc = os.path.join(util.ROOT, "uplift-upsample-3dhpe_amd", "csrc")
+    sources = [f for f in glob.glob(os.path.join(csrc, "*")) if f.endswith((".hip", ".h", ".inc"))]
+    sources += glob.glob(os.path.join(util.ROOT, "include", "*.h"))
+    assert len(sources) > 20
+    for f in sources:
+        if os.path.basename(f) != "uu3d_switches.h":
+            assert "getenv(" not in open(f).read(), f
+
+    def body(text, signature):                      # the brace-balanced body behind a function's signature
+        start = text.index("{", text.index(signature))
+        depth = 0
+        for i in range(start, len(text)):
+            depth += {"{": 1, "}": -1}.get(text[i], 0)
+            if depth == 0:
+                return text[start:i + 1]
+        raise AssertionError(signature)
+    text = open(os.path.join(csrc, "uu3d_switches.h")).read()
+    readers = body(text, "inline Switches read_switches()") + body(text, "inline const ProcessSwitches& process_switches()")
+    assert text.count("getenv(") == readers.count("getenv(") > 0
+    read = set(re.findall(r'"(UU3D_[A-Z0-9_]+)"', readers))
+    assert len(read) >= 29 and {"UU3D_SKIP", "UU3D_TIMING_PARTS", "UU3D_TCHAIN", "UU3D_TRAIN_F32"} <= read
+    doc = open(os.path.join(util.ROOT, "INTEGRATION.md")).read()
+    table = doc[doc.index("<!-- switch-table -->"):doc.index("<!-- /switch-table -->")]
+    listed = re.findall(r"^\| `(UU3D_[A-Z0-9_]+)", table, re.M)
+    assert len(listed) == len(set(listed))
+    assert set(listed) == read
+    # the table is in the structs' order: the order in which the readers take the variables
+    order = []
+    for name in re.findall(r'"(UU3D_[A-Z0-9_]+)"', readers):
+        if name not in order:
+            order.append(name)
+    assert listed == order
+    # the timing hooks stay behind the timing build inside the per-process reader
+    proc = body(text, "inline const ProcessSwitches& process_switches()")
+    guarded = proc[proc.index("#ifdef UU3D_TIMING_BUILD"):proc.index("#endif")]
+    assert "UU3D_SKIP" in guarded and "UU3D_TIMING_PARTS" in guarded
+    assert "UU3D_SKIP" not in proc.replace(guarded, "") and "UU3D_TIMING_PARTS" not in proc.replace(guarded, "")

@@ -222,7 +222,7 @@ def test_optional_kernel_paths_agree(env, monkeypatch):
 def test_throughput_schedule_matches_and_is_an_argument():
     """The schedules of include/uu3d.h.  Below 1024 token rows, and with the temporal chain switched off, the throughput schedule only reshapes
     launches (the projection as 71 workgroups x 12 column chunks with LayerNorm 2 in the same launch): bit-identical outputs.  From 1024 rows
-    on it runs the temporal chain (csrc/uu3d_tchain.h): other summation orders -- within 3e-5 of the latency schedule, bit-identical run to
+    on it runs the temporal chain (csrc/uu3d_tchain16.h): other summation orders -- within 3e-5 of the latency schedule, bit-identical run to
     run.  Either way the schedule may arrive as the argument of uu3d_forward_ex (what the pipeline does) or as the model's default
     (uu3d_set_schedule + uu3d_forward); an unknown schedule is refused."""
     import ctypes as C

@@ -1,5 +1,5 @@
-"""Compile-time guards on spatial_stack_p16_kernel (csrc/uu3d_spatial_p16.h), the shape the library launches (uu3d_api.hip:
-7 frames on 8 waves of one 16-token panel): no scratch, packed f32 without op_sel, the register budget of four waves per SIMD,
+"""Compile-time guards on spatial_stack_p16_kernel (csrc/uu3d_spatial_p16.h), the shape the library launches (spatial_stage in
+uu3d_forward.inc: 7 frames on 8 waves of one 16-token panel): no scratch, packed f32 without op_sel, the register budget of four waves per SIMD,
 the 16x16x32 MFMA form, and LDS stores only for K / V, the parameter table and the spare key slots."""
 import os
 import re

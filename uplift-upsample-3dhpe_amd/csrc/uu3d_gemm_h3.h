@@ -22,6 +22,7 @@
 #include <hip/hip_fp16.h>
 #include <stdint.h>
 #include "uu3d_gemm.h"
+#include "uu3d_switches.h"
 
 namespace uu3d {
 
@@ -65,8 +66,7 @@ __device__ __forceinline__ void h3_split(const f32x4 x, h16x4& hi, h16x4& lo) {
 }
 
 inline bool gemm_h3_deep(int workgroups) {
-    static const int limit = getenv("UU3D_GEMM_DEEP_WGS") ? atoi(getenv("UU3D_GEMM_DEEP_WGS")) : 640;      // 0: never
-    return workgroups <= limit;
+    return workgroups <= process_switches().gemm_deep_wgs;      // (UU3D_GEMM_DEEP_WGS, default 640; 0: never)
 }
 
 template <int TM, int TN, class AL, class EP, int DEEP = 0>

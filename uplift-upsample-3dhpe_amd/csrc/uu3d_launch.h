@@ -1,6 +1,5 @@
 // uu3d_launch.h -- host-side launch helpers shared by the ops ABI and the training step.
 #pragma once
-#include <cstdlib>
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include "../../include/uu3d.h"
@@ -10,6 +9,30 @@
 #include "uu3d_attn_long.h"
 
 namespace uu3d {
+
+// Dynamic LDS beyond the 64 KiB default needs hipFuncAttributeMaxDynamicSharedMemorySize on the kernel: set once per process for
+// every instantiation that is launched (one device per process).  allow_lds<kernel<...>>(bytes) in front of the launch.
+template <auto Kern>
+inline void allow_lds(size_t bytes) {
+    static const bool once = (hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess);
+    (void)once;
+}
+
+// Split-K of the tiled forward GEMMs (64 x 64 tiles, k-tiles of 32): problems with too few tiles to fill the chip are cut along K into
+// slabs and combined in order (splitk_reduce_kernel).  Returns {slices, k-tiles per slice}; {1, KT} = unsplit.
+//   target: workgroups the launch aims for;  slab_floats: capacity of the partial-sum buffer (0: none, never split);
+//   full_chip_exception: >= 200 tiles with a short contraction fill the chip unsplit (strided block 2's projection, 276 tiles x 12 k-tiles,
+//   13.3 us against 12.6 + 6.5 us split three ways + reduce; the heads and the K = 2304 convolutions measured faster split)
+struct SplitK { int slices, kps; };
+inline SplitK splitk_rule(int M, int N, int KT, int target, size_t slab_floats, bool full_chip_exception) {
+    const int tiles = ((M + 63) / 64) * ((N + 63) / 64);
+    int slices = 1;
+    if (tiles < 384 && KT >= 8 && !(full_chip_exception && tiles >= 200 && KT <= 16)) slices = std::max(1, std::min(KT / 4, (target + tiles / 2) / tiles));
+    int kps = (KT + slices - 1) / slices;
+    slices = (KT + kps - 1) / kps;
+    if (slices > 1 && (size_t)slices * M * ((N + 3) / 4 * 4) > slab_floats) { slices = 1; kps = KT; }
+    return {slices, kps};
+}
 
 constexpr size_t kOpScratchFloats = (size_t)1536 * 4096;
 
@@ -23,13 +46,8 @@ template <class AL, class EP>
 int launch_gemm(const AL& al, const float* Bt, int M, int N, int K, const EP& ep, float* slab, size_t slab_floats, hipStream_t stream,
                 const _Float16* Bh = nullptr, const _Float16* Bl = nullptr) {
     const int Kp = ru(K, 32), KT = Kp / 32;
-    const int tiles = ((M + 63) / 64) * ((N + 63) / 64);
-    int slices = 1;
-    if (tiles < 384 && KT >= 8) slices = std::max(1, std::min(KT / 4, (768 + tiles / 2) / tiles));     // (training step: 384 / 1536 target workgroups measure +0.5 %, no split +6 %)
-    int kps = (KT + slices - 1) / slices;
-    slices = (KT + kps - 1) / kps;
+    const auto [slices, kps] = splitk_rule(M, N, KT, 768, slab == nullptr ? 0 : slab_floats, false);     // (training step: 384 / 1536 target workgroups measure +0.5 %, no split +6 %)
     const int ldslab = ru(N, 4);
-    if (slices > 1 && (slab == nullptr || (size_t)slices * M * ldslab > slab_floats)) { slices = 1; kps = KT; }
     const int mt = (M + 63) / 64, nt = (N + 63) / 64;
     const int grid = ru(mt, 8) * nt;
     if (Bh != nullptr && Bl != nullptr) {
@@ -58,7 +76,7 @@ int launch_gemm(const AL& al, const float* Bt, int M, int N, int K, const EP& ep
     return hip_status();
 }
 
-inline int tnh_target_wgs() { static const int v = getenv("UU3D_TNH_WGS") ? atoi(getenv("UU3D_TNH_WGS")) : 192; return v; }     // these GEMMs share the chip with the activation-gradient chain: fewer, longer workgroups and half the combine traffic (384: 3.74 ms per step, 192: 3.60, 128: 3.61, 96: 3.65)
+inline int tnh_target_wgs() { return process_switches().tnh_wgs; }     // (UU3D_TNH_WGS, default 192) these GEMMs share the chip with the activation-gradient chain: fewer, longer workgroups and half the combine traffic (384: 3.74 ms per step, 192: 3.60, 128: 3.61, 96: 3.65)
 // C[P][Q] = A^T B over R rows, split over R into slabs, combined in order.
 template <class AL, class EP>
 int launch_gemm_tn(const AL& al, const float* B, int ldb, int R, int P, int Q, const EP& ep, float* slab, size_t slab_floats, hipStream_t stream,
@@ -72,11 +90,7 @@ int launch_gemm_tn(const AL& al, const float* B, int ldb, int R, int P, int Q, c
         const int kps = (KT + slices - 1) / slices;
         slices = (KT + kps - 1) / kps;
         auto k1 = gemm_tn_h3_kernel<AL, EP>; auto ks = gemm_tn_h3_kernel<AL, EpSlab>;
-        static const bool attr_set = [&] {            // once per instantiation (one device per process)
-            (void)hipFuncSetAttribute((const void*)k1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TNH_LDS_BYTES);
-            (void)hipFuncSetAttribute((const void*)ks, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TNH_LDS_BYTES);
-            return true; }();
-        (void)attr_set;
+        allow_lds<gemm_tn_h3_kernel<AL, EP>>(TNH_LDS_BYTES); allow_lds<gemm_tn_h3_kernel<AL, EpSlab>>(TNH_LDS_BYTES);
         if (slices == 1) {
             hipLaunchKernelGGL(k1, dim3(tiles, 1), dim3(256), TNH_LDS_BYTES, stream, al, B, ldb, R, P, Q, pt, qt, KT, ep);
         } else {
@@ -191,17 +205,16 @@ inline bool attn_generic_head_dim_ok(int dh) { return dh == 2 || dh == 4 || dh =
 
 // drop: Dropout on the attention weights (training with ATTENTION_DROP_RATE > 0) -- only the generic kernels implement it, so the
 // unrolled / MFMA backward kernels are not taken then
+// bwd_generic (UU3D_ATTN_BWD_GENERIC): the backward stays on the generic kernel for every shape
 inline int launch_attn_generic(bool backward, const float* qkv, const float* dO, int ld, int D, int B, int L, int H, int dh,
-                               const uint8_t* mask, float* out, int ldo, hipStream_t stream, const DropCfg drop = DropCfg{}) {
+                               const uint8_t* mask, float* out, int ldo, hipStream_t stream, const DropCfg drop = DropCfg{}, bool bwd_generic = false) {
     const int total = B * H;
     const dim3 block(128);
     if (dh != 4 && dh != 48) {
         // other head dims (generic-dims models, uu3d_create): thread = query row, one (sequence, head) per workgroup
         if (L > 128) return UU3D_ERR_UNSUPPORTED;
         const dim3 grid(total);
-#define UU3D_ATTNG_CASE(d) case d: { static bool done##d = false; \
-            if (!done##d) { (void)hipFuncSetAttribute((const void*)attn_generic_fwd_kernel<d>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-                            (void)hipFuncSetAttribute((const void*)attn_generic_bwd_kernel<d>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); done##d = true; } \
+#define UU3D_ATTNG_CASE(d) case d: { allow_lds<attn_generic_fwd_kernel<d>>(160 * 1024); allow_lds<attn_generic_bwd_kernel<d>>(160 * 1024); \
             if (attn_generic_lds_bytes<d>(L, backward) > (size_t)160 * 1024) return UU3D_ERR_UNSUPPORTED; \
             if (backward) hipLaunchKernelGGL(attn_generic_bwd_kernel<d>, grid, block, attn_generic_lds_bytes<d>(L, true), stream, qkv, dO, ld, D, L, H, mask, out, ldo, 1, total, drop); \
             else hipLaunchKernelGGL(attn_generic_fwd_kernel<d>, grid, block, attn_generic_lds_bytes<d>(L, false), stream, qkv, ld, D, L, H, mask, out, ldo, 1, total, drop); } break;
@@ -216,18 +229,18 @@ inline int launch_attn_generic(bool backward, const float* qkv, const float* dO,
         const int pack = std::max(1, 128 / L);                         // (sequence, head) pairs per workgroup
         const dim3 grid((total + pack - 1) / pack);
         const size_t lds = attn_generic_lds_bytes<4>(L, backward) * pack;
-        if (backward && L == 17 && mask == nullptr && !drop.on() && !getenv("UU3D_ATTN_BWD_GENERIC"))     // the spatial stack's shape: unrolled, rows in registers
+        if (backward && L == 17 && mask == nullptr && !drop.on() && !bwd_generic)     // the spatial stack's shape: unrolled, rows in registers
             hipLaunchKernelGGL(attn_small_bwd_kernel<17>, grid, block, attn_small_bwd_lds_bytes<17>() * pack, stream, qkv, dO, ld, D, H, out, ldo, pack, total);
         else if (backward) hipLaunchKernelGGL(attn_generic_bwd_kernel<4>, grid, block, lds, stream, qkv, dO, ld, D, L, H, mask, out, ldo, pack, total, drop);
         else hipLaunchKernelGGL(attn_generic_fwd_kernel<4>, grid, block, lds, stream, qkv, ld, D, L, H, mask, out, ldo, pack, total, drop);
     } else {
         const dim3 grid(total);
         const size_t lds = attn_generic_lds_bytes<48>(L, backward);
-        if (backward && L <= 128 && !drop.on() && !getenv("UU3D_ATTN_BWD_GENERIC")) {
+        if (backward && L <= 128 && !drop.on() && !bwd_generic) {
             // MFMA backward, tiles in registers (attn_bwd_mfma_kernel); dqkv has the layout (and leading dimension) of qkv
             const int NT = (L + 15) / 16;
             const size_t l2 = attn_bwd_mfma_lds_bytes<48>(NT);
-#define UU3D_ATTNB_CASE(nt) case nt: { static bool d2 = false; if (!d2) { (void)hipFuncSetAttribute((const void*)attn_bwd_mfma_kernel<nt, 48>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_bwd_mfma_lds_bytes<48>(nt)); d2 = true; } \
+#define UU3D_ATTNB_CASE(nt) case nt: { allow_lds<attn_bwd_mfma_kernel<nt, 48>>(attn_bwd_mfma_lds_bytes<48>(nt)); \
             hipLaunchKernelGGL((attn_bwd_mfma_kernel<nt, 48>), grid, dim3(64 * nt), l2, stream, qkv, dO, ld, D, L, H, mask, out, ldo); } break;
             switch (NT) {
                 UU3D_ATTNB_CASE(1) UU3D_ATTNB_CASE(2) UU3D_ATTNB_CASE(3) UU3D_ATTNB_CASE(4)
@@ -235,12 +248,10 @@ inline int launch_attn_generic(bool backward, const float* qkv, const float* dO,
             }
 #undef UU3D_ATTNB_CASE
         } else if (backward) {
-            static bool done = false;
-            if (!done) { (void)hipFuncSetAttribute((const void*)attn_generic_bwd_kernel<48>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); done = true; }
+            allow_lds<attn_generic_bwd_kernel<48>>(160 * 1024);
             hipLaunchKernelGGL(attn_generic_bwd_kernel<48>, grid, block, lds, stream, qkv, dO, ld, D, L, H, mask, out, ldo, 1, total, drop);
         } else {
-            static bool donef = false;
-            if (!donef) { (void)hipFuncSetAttribute((const void*)attn_generic_fwd_kernel<48>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); donef = true; }
+            allow_lds<attn_generic_fwd_kernel<48>>(160 * 1024);
             hipLaunchKernelGGL(attn_generic_fwd_kernel<48>, grid, block, lds, stream, qkv, ld, D, L, H, mask, out, ldo, 1, total, drop);
         }
     }

@@ -65,7 +65,7 @@ int uu3d_op_attn_bwd(const float* qkv, const float* dout, int32_t ld, int32_t D,
                      const uint8_t* mask, float* dqkv, int32_t ldo, void* stream) {
     if (!qkv || !dout || !dqkv || L < 1 || (dh != 4 && dh != 48)) return UU3D_ERR_INVALID_ARGUMENT;
     if (L > 96) return UU3D_ERR_UNSUPPORTED;      // P and dS matrices of one head must fit the 160 KiB LDS
-    return launch_attn_generic(true, qkv, dout, ld, D, B, L, H, dh, mask, dqkv, ldo, (hipStream_t)stream);
+    return launch_attn_generic(true, qkv, dout, ld, D, B, L, H, dh, mask, dqkv, ldo, (hipStream_t)stream, DropCfg{}, read_switches().train.attn_bwd_generic);
 }
 
 // the kernels move rows as 16-byte pieces (q / k / v, O, dO; statistics as 8-byte pairs): leading dimensions multiples of 4 floats,
@@ -122,12 +122,12 @@ int uu3d_op_ln_dense_panel(const float* x, int32_t ldx, int32_t M, const float* 
     const _Float16* Bf = reinterpret_cast<const _Float16*>(operand);
     if (relu) {
         auto kern = gemm_h3_panel_kernel<24, PanelEpBiasReluSplit>;
-        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PANEL_LDS_TOTAL);
+        allow_lds<gemm_h3_panel_kernel<24, PanelEpBiasReluSplit>>(PANEL_LDS_TOTAL);
         _Float16* oh = reinterpret_cast<_Float16*>(out);
         hipLaunchKernelGGL(kern, grid, dim3(256), PANEL_LDS_TOTAL, stream, Af, Bf, bias, M, mt, S, chunks / S, PanelEpBiasReluSplit{oh, oh + (size_t)M * N, N});
     } else {
         auto kern = gemm_h3_panel_kernel<24, PanelEpBias>;
-        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PANEL_LDS_TOTAL);
+        allow_lds<gemm_h3_panel_kernel<24, PanelEpBias>>(PANEL_LDS_TOTAL);
         hipLaunchKernelGGL(kern, grid, dim3(256), PANEL_LDS_TOTAL, stream, Af, Bf, bias, M, mt, S, chunks / S, PanelEpBias{reinterpret_cast<float*>(out), ldo});
     }
     return hipGetLastError() == hipSuccess ? UU3D_OK : UU3D_ERR_HIP;
