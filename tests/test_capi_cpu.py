@@ -94,6 +94,20 @@ def test_build_is_keyed_by_content_not_by_file_times(tmp_path):
         open(stamp, "w").write(good)
 
 
+def test_every_included_piece_of_the_api_unit_is_fingerprinted():
+    """uu3d_api.hip is one translation unit made of .inc pieces: each `#include "uu3d_*.inc"` names a file that exists, is included
+    once, and is in build.HEADERS -- so an edit to any piece rebuilds the library."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("uu3d_build_i", os.path.join(util.ROOT, "uplift-upsample-3dhpe_amd", "build.py"))
+    b = importlib.util.module_from_spec(spec); spec.loader.exec_module(b)
+    pieces = re.findall(r'^#include "(uu3d_\w+\.inc)"', open(os.path.join(b.CSRC, "uu3d_api.hip")).read(), re.M)
+    assert len(pieces) >= 6 and len(pieces) == len(set(pieces))
+    for f in pieces:
+        assert os.path.isfile(os.path.join(b.CSRC, f)), f
+        assert f in b.HEADERS, f
+    assert set(pieces) == {f for f in os.listdir(b.CSRC) if f.endswith(".inc")}       # and no piece is left lying around unincluded
+
+
 def test_environment_switches_live_in_one_table():
     """Every UU3D_* variable the library reads is read by one of the two reader functions of csrc/uu3d_switches.h (read_switches: per
     handle, process_switches: per process), nowhere else, and INTEGRATION.md section 5 lists exactly those names."""

@@ -90,7 +90,7 @@ def _bucket_worker(rank, world, port, q):
     ud.allreduce_gradients(flat)                                   # the one-collective form
     b = g.clone()
     br = ud.BucketedAllReduce(b)
-    # ranges in the order the backward pass finishes them: tail of the buffer first, the front last (uu3d_train_step.inc)
+    # ranges in the order the backward pass finishes them: tail of the buffer first, the front last (uu3d_train_backward.inc)
     for first, count in [(7000, 3007), (4000, 3000), (1500, 2500), (0, 1500)]:
         br.ready(first, count)
     br.wait()

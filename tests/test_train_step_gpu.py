@@ -34,7 +34,7 @@ _MASKS = [(0, 0), (1, 0), (2, 0)]
 def test_gradients_match_autograd(cfgname, droppath, batch_norm):
     """Every gradient tensor against float64 autograd through the oracle, <= 1e-4 of its scale.  batch_norm = 512 is the
     PRODUCTION loss normaliser (config BATCH_SIZE): d loss / d joint is 8e-7 there, which the f16x3 gradient GEMMs only
-    resolve because the backward pass runs loss-scaled (uu3d_train_step.inc, gscale)."""
+    resolve because the backward pass runs loss-scaled (uu3d_train_entry.inc, gscale)."""
     from oracle import train_oracle as T
     from uplift_upsample_3dhpe_amd.trainer import Trainer
     B = 12 if droppath == "bn" else 3      # (BatchNorm over 3 samples: 1 / sqrt(var + eps) reaches 300 and multiplies every f32 rounding of the backward pass)
@@ -220,7 +220,7 @@ def test_checkpoint_resume_is_bit_identical(tmp_path):
 
 @pytest.mark.parametrize("cfgname,B", [("h36m_351", 16), ("h36m_81", 5)])
 def test_side_stream_schedule_is_bit_identical_to_in_order(cfgname, B, monkeypatch):
-    """The backward pass runs the parameter-gradient work on a second stream (uu3d_train_step.inc).  Both schedules launch
+    """The backward pass runs the parameter-gradient work on a second stream (uu3d_train_backward.inc).  Both schedules launch
     the same kernels on the same data, so every gradient must agree BIT FOR BIT with the in-order run -- a missing
     dependency between the streams shows up here as a mismatch (repeated: a race need not lose every time)."""
     from uplift_upsample_3dhpe_amd.trainer import Trainer

@@ -2,7 +2,8 @@
 // get / set and the small entry points.  One translation unit with
 //   uu3d_commit.inc      uu3d_commit_weights: host weights -> packed device operands
 //   uu3d_forward.inc     workspace, Launcher, the forward launch schedule (uu3d_forward*, uu3d_frame_features)
-//   uu3d_train_step.inc  the training step
+//   uu3d_train_state.inc, uu3d_train_forward.inc, uu3d_train_backward.inc, uu3d_train_entry.inc
+//                        the training step: state / init / repack / carve, the forward, the backward with its side streams, the entry points and the tape
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -92,7 +93,7 @@ struct uu3d_model {
     Switches sw;                   // the environment switches of this handle (uu3d_switches.h), read by uu3d_create
     bool committed = false;
     // Dims other than the compiled ones (J = 17, d_s = 32, h_s = 64, 8 heads, d_t = 384): the forward runs on the GENERIC kernels of the
-    // training-mode chain (uu3d_train_step.inc: tiled GEMMs with LayerNorm / GELU loaders, attn_generic_fwd_kernel, one launch per layer)
+    // training-mode chain (uu3d_train_forward.inc: tiled GEMMs with LayerNorm / GELU loaders, attn_generic_fwd_kernel, one launch per layer)
     // from a master buffer the model owns -- correct and an order of magnitude slower than the specialised path; no backward pass.
     bool generic = false;
     float* gparams = nullptr;      // generic: master parameter buffer (uu3d_train_init layout)
@@ -105,7 +106,7 @@ struct uu3d_model {
     struct TcLaunch { int flags; size_t w_off /* halfs, harena */; size_t p_off /* floats, arena */; };
     std::vector<TcLaunch> tchain;
     int num_cus = 256;
-    std::recursive_mutex train_mu; // the training-mode chain keeps per-call options in the handle's training state (uu3d_train_step.inc): one call at a time
+    std::recursive_mutex train_mu; // the training-mode chain keeps per-call options in the handle's training state (uu3d_train_state.inc): one call at a time
     bool in_commit = false;        // uu3d_commit_weights is calling uu3d_train_init (generic dims): the training step's skip flag is not its to clear
     int* d_range = nullptr;        // sticky device word of the range guard (include/uu3d.h: uu3d_range_status)
     _Float16* harena = nullptr;    // f16 hi/lo planes of every GEMM operand (f16x3 mode)
@@ -335,7 +336,7 @@ int uu3d_create(const uu3d_config* c, int device, uu3d_model** out) {
 
 static void train_free(uu3d_model* m);
 static int generic_forward(uu3d_model* m, const float* kp2d, const uint8_t* mask, int32_t B, float* full_out, float* central_out,
-                           float* const* attn_out, void* workspace, size_t workspace_bytes, void* stream);      // uu3d_train_step.inc
+                           float* const* attn_out, void* workspace, size_t workspace_bytes, void* stream);      // uu3d_train_entry.inc
 void uu3d_destroy(uu3d_model* m) {
     if (!m) return;
     (void)hipSetDevice(m->device);
@@ -577,5 +578,8 @@ int uu3d_ema_update(float* ema, const float* w, int64_t n, float decay, void* st
     return hipGetLastError() == hipSuccess ? UU3D_OK : UU3D_ERR_HIP;
 }
 
-#include "uu3d_train_step.inc"
+#include "uu3d_train_state.inc"
+#include "uu3d_train_forward.inc"
+#include "uu3d_train_backward.inc"
+#include "uu3d_train_entry.inc"
 

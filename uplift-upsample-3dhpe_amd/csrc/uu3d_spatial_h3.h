@@ -368,7 +368,7 @@ __device__ unsigned long long spatial_clk[12];   // tools/spatial_stamp_exp: s_m
 #define UU3D_SPATIAL_H3_WAVES 2     // 3 (168 VGPRs) spills into the block loop: 0.30 ms instead of 0.20
 #endif
 // (UU3D_PK_TARGET: uu3d_pk.h -- this kernel switches the packed-fp32-ops target feature back on for itself)
-// Training-mode forward (TRAIN = true; uu3d_train_step.inc): the same kernel also writes what the backward pass reads -- per block
+// Training-mode forward (TRAIN = true; uu3d_train_forward.inc): the same kernel also writes what the backward pass reads -- per block
 // its input, both LayerNorms' row statistics (mean, 1 / sqrt(var + eps)), q | k | v with bias, the attention output, the stream
 // after the attention residual and the pre-GELU hidden activations; at the end the stack's output before spatial_norm and that
 // LayerNorm's statistics -- and applies the DropPath gates of vision_transformer.py:16-43 (per frame, scaled by 1 / keep) to the
