@@ -229,6 +229,37 @@ int uu3d_gather_windows(const float* poses_dev, const int64_t* video_start_dev, 
                         float* out_dev, uint8_t* stride_mask_dev, uint8_t* pad_mask_dev, void* stream);
 
 /*
+ * YOUR OWN 2D TRACKS (predict.predict_tracks): the front and the back of the chain pose table -> uu3d_gather_windows -> forward, for keypoint
+ * tracks that come from the caller's detector instead of a dataset.  One launch per call for all tracks, every output element written by one
+ * thread (no atomics: bitwise repeatable), 16-byte stores; stream-ordered, all buffers are the caller's.
+ *
+ *   uu3d_normalize_tracks: pixel coordinates -> the model's normalised screen coordinates in the pose table table_dev (rows, J, 2) f32,
+ *   16-byte aligned: x / w * 2 - 1, y / w * 2 - h / w (common/dataset/camera.py:15-20) in numpy's float32 / float64 operation order, so
+ *   the result equals h36m.normalize_screen_coordinates on float32 input bit for bit.  row_track_dev (rows) i32: the track of every table
+ *   row; resolution_dev (num_tracks, 2) f64 = (w, h) per track, or NULL: coordinates are taken as they are.
+ *     key_stride == 0: src_dev holds the rows of the table (src_rows == rows; src_dev == table_dev converts in place);
+ *     key_stride > 0 (keyframes only): src_dev (src_rows, J, 2), 8-byte aligned and not the table, holds frames 0, key_stride, 2 key_stride, ...
+ *     of every track back to back; track t starts at row track_start_dev[t] of the table and at row src_start_dev[t] of src_dev (i64 each).
+ *     The same launch scatters the keyframes to their table rows and writes zeros to every other row.
+ *   A track id or source row out of range yields NaN rows, never a read out of bounds.
+ *
+ *   uu3d_assemble_tracks: the central predictions of the forwarded windows as the pipeline leaves them -- plain_dev (num_windows, J, 3) and,
+ *   with flip test-time augmentation, flipped_dev (num_windows, J, 3) of the mirrored windows with flip_order_dev (J) i32 (both NULL: no flip)
+ *   -- to the dense out_dev (num_frames, J, 3) f32, 16-byte aligned: un-flip (x negated, joints permuted) and average in float32 as
+ *   eval.py:163-166, then per frame f the plan (left_dev, right_dev (num_frames) i32 rows of the prediction arrays, weight_dev f64) of
+ *   evaluation.keyframe_plan: pred[left] where left == right, else pred[left] * (1 - weight) + pred[right] * weight in float64 with every
+ *   operation rounded, stored as float32 -- evaluation.interpolate_between_keyframes on float32 predictions bit for bit.  root_index >= 0:
+ *   that joint of the frame is subtracted in float32 afterwards (it comes out exactly 0); -1: absolute predictions.  A plan row outside
+ *   [0, num_windows) yields NaN.
+ */
+int uu3d_normalize_tracks(const float* src_dev, int64_t src_rows, float* table_dev, int64_t rows, int32_t num_keypoints,
+                          const int32_t* row_track_dev, int32_t num_tracks, const double* resolution_dev,
+                          const int64_t* track_start_dev, const int64_t* src_start_dev, int32_t key_stride, void* stream);
+int uu3d_assemble_tracks(const float* plain_dev, const float* flipped_dev, int64_t num_windows, const int32_t* flip_order_dev,
+                         const int32_t* left_dev, const int32_t* right_dev, const double* weight_dev, int64_t num_frames,
+                         int32_t num_keypoints, int32_t root_index, float* out_dev, void* stream);
+
+/*
  * World -> camera coordinates -> 2D projection with the Human3.6M camera model, one camera per window: replaces
  * tf_world_to_cam_and_2d (common/dataset/uplifiting_dataset.py:669-761), the on-the-fly AMASS projection of training.
  *   world_dev (B, N, J, 3) f32; cams_dev (B, 18) f32 = quaternion wxyz | translation | 11 intrinsics (res, focal,

@@ -1,0 +1,83 @@
+"""predict.predict_tracks end to end on seeded synthetic pixel tracks (no dataset), against the same tracks pushed through the public
+pieces that existed before it: host normalisation (h36m.normalize_screen_coordinates), PoseTable / SequenceGenerator,
+eval.predict_windows, then .cpu() + evaluation.interpolate_between_keyframes in numpy.  Both start from host arrays of pixel coordinates;
+predict_tracks ends with the dense poses on the device (also reported: with their copy to the host), the composition with them on the host.
+Median of --reps calls after one warm-up call each; frames/s = all frames of all tracks / seconds.
+   python tools/predict_tracks_bench.py [--tracks 40] [--frames 2500] [--batch 512] [--reps 3] [--cases h36m_351:5,h36m_81:4]"""
+import argparse, json, os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--tracks", type=int, default=40)
+    ap.add_argument("--frames", type=int, default=2500)
+    ap.add_argument("--batch", type=int, default=512, help="windows per batch (x 2 sequences with the flip)")
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--cases", default="h36m_351:5,h36m_81:4")
+    ap.add_argument("--no_reuse", action="store_true", help="the window forward instead of the frames form, in both paths")
+    args = ap.parse_args()
+    import numpy as np, torch
+    import uplift_upsample_3dhpe_amd as pkg
+    from uplift_upsample_3dhpe_amd import synthetic as util
+    from uplift_upsample_3dhpe_amd import eval as ev
+    from uplift_upsample_3dhpe_amd import evaluation, h36m, predict
+    from uplift_upsample_3dhpe_amd.data import PoseTable, SequenceGenerator
+    rng = np.random.default_rng(0)
+    W, H = 1920, 1080
+    # smooth tracks in pixels: a random walk per joint around a random place in the image
+    px = [(np.cumsum(rng.normal(0, 2.0, size=(args.frames, 17, 2)), 0) + rng.uniform(0.25, 0.75, size=(1, 17, 2)) * [W, H]).astype(np.float32)
+          for _ in range(args.tracks)]
+    total = args.tracks * args.frames
+    reuse = not args.no_reuse
+    results = []
+    for case in args.cases.split(","):
+        name, msv = case.split(":")
+        cfg = util.load_config(name)
+        cfg.MASK_STRIDE = int(msv)
+        arch = pkg.arch_from_config(cfg)
+        model = pkg.build_uplift_upsample_transformer(cfg, weights=pkg.init_weights(arch, seed=0, perturb=0.1))
+
+        def new_path(to_host=False):
+            out = predict.predict_tracks(model, cfg, px, resolutions=(W, H), mask_stride=int(msv), flip=True, reuse_frames=reuse, batch_size=args.batch)
+            return [o.cpu() for o in out] if to_host else out
+
+        def composition():
+            p2 = [h36m.normalize_screen_coordinates(t, w=W, h=H).astype(np.float32) for t in px]
+            gen = SequenceGenerator(PoseTable(p2, device=model.device), seq_len=cfg.SEQUENCE_LENGTH, stride=cfg.SEQUENCE_STRIDE,
+                                    padding_type=cfg.PADDING_TYPE, flip_augment=False, flip_lr_indices=cfg.AUGM_FLIP_KEYPOINT_ORDER,
+                                    mask_stride=cfg.MASK_STRIDE, stride_mask_align_global=True, shuffle=False)
+            desc = gen.descriptors()
+            run = np.flatnonzero(ev.needed_windows(desc[:, 1], cfg))
+            cen = ev.predict_windows(model, gen, desc[run], cfg, args.batch, flip=True, reuse_frames=reuse)
+            pred = np.zeros((len(desc), 17, 3), np.float32)
+            pred[run] = cen.cpu().numpy()
+            pred, _ = evaluation.interpolate_between_keyframes(pred, desc[:, 1], cfg.SEQUENCE_STRIDE)
+            pred = pred - pred[:, cfg.ROOT_KEYTPOINT:cfg.ROOT_KEYTPOINT + 1]
+            return np.split(pred, np.cumsum([len(t) for t in px])[:-1])
+
+        row = dict(config=name, mask_stride=int(msv), tracks=args.tracks, frames=total, batch=args.batch, reuse_frames=reuse)
+        outs = {}
+        for key, fn in (("predict_tracks", new_path), ("predict_tracks_to_host", lambda: new_path(True)), ("composition", composition)):
+            fn()
+            torch.cuda.synchronize()
+            ts = []
+            for _ in range(args.reps):
+                t0 = time.perf_counter()
+                outs[key] = fn()
+                torch.cuda.synchronize()
+                ts.append(time.perf_counter() - t0)
+            t = float(np.median(ts))
+            row[key + "_ms"] = round(1e3 * t, 1)
+            row[key + "_frames_per_s"] = round(total / t, 1)
+        row["speedup"] = round(row["composition_ms"] / row["predict_tracks_ms"], 3)
+        row["max_abs_diff"] = float(max(np.abs(a.numpy() - b).max() for a, b in zip(outs["predict_tracks_to_host"], outs["composition"])))
+        row["device"] = torch.cuda.get_device_name(0)
+        print(json.dumps(row), flush=True)
+        results.append(row)
+        del model
+    return results
+
+
+if __name__ == "__main__":
+    main()

@@ -22,3 +22,9 @@ def library_version():
     """``uu3d_version()`` of the loaded HIP library (a timing build, csrc/libuu3d_timing.so through UU3D_LIB, says so: bench.py refuses it)."""
     from . import _capi
     return _capi.load_library().uu3d_version().decode()
+
+
+def predict_tracks(model, config, tracks, **kwargs):
+    """3D poses for your own 2D keypoint tracks, one per frame (``predict.predict_tracks``)."""
+    from .predict import predict_tracks as _p
+    return _p(model, config, tracks, **kwargs)

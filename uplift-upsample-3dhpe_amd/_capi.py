@@ -31,6 +31,7 @@ EXPORTED_SYMBOLS = (
     "uu3d_train_backward_tape_accumulate", "uu3d_train_copy_nonfinite",
     "uu3d_frame_features_bytes", "uu3d_frame_features", "uu3d_gather_window_frames", "uu3d_forward_frames_ex",
     "uu3d_pose_errors", "uu3d_error_sums", "uu3d_error_sums_scratch_bytes",
+    "uu3d_normalize_tracks", "uu3d_assemble_tracks",
 )
 # include/uu3d_ops.h
 OPS_SYMBOLS = (
@@ -136,6 +137,10 @@ def load_library(path=None):
     lib.uu3d_error_sums_scratch_bytes.argtypes = [i64, i32]
     lib.uu3d_gather_windows.restype = C.c_int
     lib.uu3d_gather_windows.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp]
+    lib.uu3d_normalize_tracks.restype = C.c_int
+    lib.uu3d_normalize_tracks.argtypes = [vp, i64, vp, i64, i32, vp, i32, vp, vp, vp, i32, vp]
+    lib.uu3d_assemble_tracks.restype = C.c_int
+    lib.uu3d_assemble_tracks.argtypes = [vp, vp, i64, vp, vp, vp, vp, i64, i32, i32, vp, vp]
     lib.uu3d_frame_features_bytes.restype = sz
     lib.uu3d_frame_features_bytes.argtypes = [vp, i32]
     lib.uu3d_frame_features.restype = C.c_int

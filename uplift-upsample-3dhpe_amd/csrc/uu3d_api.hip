@@ -33,6 +33,7 @@
 #include "uu3d_spatial_p16.h"
 #include "uu3d_misc.h"
 #include "uu3d_metrics.h"
+#include "uu3d_tracks.h"
 #include "uu3d_train.h"
 #include "uu3d_bwd.h"
 #include "uu3d_launch.h"
@@ -484,6 +485,29 @@ int uu3d_gather_window_frames(const int64_t* video_start, const int32_t* video_l
     hipLaunchKernelGGL(gather_window_frames_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        video_start, video_len, reinterpret_cast<const WindowDesc*>(windows), B, N, pad_edge, zero_masked,
                        frame_base, zero_row, rows, stride_mask, pad_mask);
+    return hipGetLastError() == hipSuccess ? UU3D_OK : UU3D_ERR_HIP;
+}
+
+int uu3d_normalize_tracks(const float* src, int64_t src_rows, float* table, int64_t rows, int32_t J, const int32_t* row_track, int32_t num_tracks,
+                          const double* resolution, const int64_t* track_start, const int64_t* src_start, int32_t key_stride, void* stream) {
+    if (!src || !table || !row_track || src_rows < 1 || rows < 1 || J < 1 || num_tracks < 1 || key_stride < 0) return UU3D_ERR_INVALID_ARGUMENT;
+    if (key_stride > 0 && (!track_start || !src_start || src == table)) return UU3D_ERR_INVALID_ARGUMENT;
+    if (key_stride == 0 && src_rows != rows) return UU3D_ERR_INVALID_ARGUMENT;
+    if (((uintptr_t)table & 15) != 0 || ((uintptr_t)src & 7) != 0) return UU3D_ERR_INVALID_ARGUMENT;
+    const long threads = ((long)rows * J + 1) / 2;
+    hipLaunchKernelGGL(normalize_tracks_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       src, (long)src_rows, table, (long)rows, J, row_track, num_tracks, resolution, track_start, src_start, key_stride);
+    return hipGetLastError() == hipSuccess ? UU3D_OK : UU3D_ERR_HIP;
+}
+
+int uu3d_assemble_tracks(const float* plain, const float* flipped, int64_t num_windows, const int32_t* flip_order, const int32_t* left,
+                         const int32_t* right, const double* weight, int64_t num_frames, int32_t J, int32_t root_index, float* out, void* stream) {
+    if (!plain || !left || !right || !weight || !out || num_windows < 1 || num_frames < 1 || J < 1 || root_index >= J) return UU3D_ERR_INVALID_ARGUMENT;
+    if (flipped != nullptr && !flip_order) return UU3D_ERR_INVALID_ARGUMENT;
+    if (((uintptr_t)out & 15) != 0) return UU3D_ERR_INVALID_ARGUMENT;
+    const long threads = ((long)num_frames * J * 3 + 3) / 4;
+    hipLaunchKernelGGL(assemble_tracks_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       plain, flipped, (long)num_windows, flip_order, left, right, weight, (long)num_frames, J, root_index < 0 ? -1 : root_index, out);
     return hipGetLastError() == hipSuccess ? UU3D_OK : UU3D_ERR_HIP;
 }
 

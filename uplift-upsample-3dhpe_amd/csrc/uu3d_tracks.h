@@ -1,0 +1,113 @@
+// uu3d_tracks.h -- the front and the back of predict.predict_tracks (include/uu3d.h, "YOUR OWN 2D TRACKS"): pixel coordinates of the
+// caller's keypoint tracks -> the pose table the window gather reads, and the central predictions of the forwarded windows -> one 3D pose
+// per frame of every track.  Both kernels: one launch for all tracks of a call, one thread per 16 bytes of the flattened output, every
+// output element written by exactly one thread from inputs nobody writes (bitwise repeatable; the in-place form of the first kernel
+// reads only what the same thread overwrites).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace uu3d {
+
+// h36m.normalize_screen_coordinates (common/dataset/camera.py:15-20: X / w * 2 - [1, h / w]) on float32 coordinates, in numpy's types
+// and order: the quotient and the doubling in float32 (w rounded to float32), then the subtraction of the float64 list [1, h / w] in
+// float64, rounded once to float32 when it is stored.
+__device__ __forceinline__ float2 normalize_pair(const float2 p, const float wf, const double h_over_w)
+{
+    const float x = __fdiv_rn(p.x, wf) * 2.0f, y = __fdiv_rn(p.y, wf) * 2.0f;
+    return make_float2((float)((double)x - 1.0), (float)((double)y - h_over_w));
+}
+
+// table (rows, J, 2): row r belongs to track row_track[r].  key_stride == 0: the table's own rows are normalised (src == table allowed).
+// key_stride > 0: src holds only the frames 0, key_stride, 2 key_stride, ... of every track back to back (track t from row src_start[t]);
+// frame f of track t (table row track_start[t] + f) takes source row src_start[t] + f / key_stride when f % key_stride == 0 and is zero
+// otherwise.  res (T, 2) float64 = (w, h) per track, or nullptr: the coordinates are copied as they are.  A track id or a source row out
+// of range writes NaN instead of reading out of bounds.
+static __global__ void __launch_bounds__(256)
+normalize_tracks_kernel(const float* src, const long src_rows, float* table, const long rows, const int J, const int32_t* __restrict__ row_track,
+                        const int num_tracks, const double* __restrict__ res, const int64_t* __restrict__ track_start,
+                        const int64_t* __restrict__ src_start, const int key_stride)
+{
+    const long pairs = rows * J;
+    const long p0 = ((long)blockIdx.x * 256 + threadIdx.x) * 2;         // two (x, y) pairs = one 16-byte store
+    if (p0 >= pairs) return;
+    float2 v[2];
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        const long p = (p0 + e < pairs) ? p0 + e : p0;
+        const long row = p / J;
+        const int j = (int)(p - row * J);
+        const int t = row_track[row];
+        const float nan = __builtin_nanf("");
+        v[e] = make_float2(nan, nan);
+        if (t < 0 || t >= num_tracks) continue;
+        long srow = row;
+        if (key_stride > 0) {
+            const long f = row - track_start[t];
+            if (f < 0) continue;
+            if (f % key_stride != 0) { v[e] = make_float2(0.f, 0.f); continue; }
+            srow = src_start[t] + f / key_stride;
+        }
+        if (srow < 0 || srow >= src_rows) continue;
+        const float2 x = *reinterpret_cast<const float2*>(src + (srow * J + j) * 2);
+        v[e] = (res != nullptr) ? normalize_pair(x, (float)res[2 * t], res[2 * t + 1] / res[2 * t]) : x;
+    }
+    if (p0 + 1 < pairs) *reinterpret_cast<float4*>(table + p0 * 2) = make_float4(v[0].x, v[0].y, v[1].x, v[1].y);
+    else *reinterpret_cast<float2*>(table + p0 * 2) = v[0];
+}
+
+// The prediction of one window: the plain central prediction, or its mean with the un-flipped mirrored one (eval.py:163-166: x negated,
+// joints permuted by AUGM_FLIP_KEYPOINT_ORDER, (a + b) / 2 in float32 -- eval._unflip).
+__device__ __forceinline__ float window_prediction(const float* __restrict__ plain, const float* __restrict__ flipped, const int32_t* __restrict__ order,
+                                                   const long row, const int J, const int j, const int c)
+{
+    const float p = plain[(row * J + j) * 3 + c];
+    if (flipped == nullptr) return p;
+    float q = flipped[(row * J + order[j]) * 3 + c];
+    if (c == 0) q = q * -1.0f;
+    return (p + q) / 2.0f;
+}
+
+// Coordinate c of joint j of frame f by the plan of evaluation.keyframe_plan: the prediction of window left[f] where left == right (a
+// predicted frame, or a frame behind its track's last predicted one), else evaluation.interpolate_between_keyframes' own expression
+// pred[left] * (1.0 - w) + pred[right] * w in float64 -- two products and one sum, each rounded (no fused multiply-add), then rounded to
+// float32 as numpy stores it into the float32 array.  A row outside [0, num_windows) gives NaN.
+__device__ __forceinline__ float frame_value(const float* __restrict__ plain, const float* __restrict__ flipped, const int32_t* __restrict__ order,
+                                             const long num_windows, const long l, const long r, const double w, const int J, const int j, const int c)
+{
+#pragma clang fp contract(off)
+    if (l < 0 || l >= num_windows || r < 0 || r >= num_windows) return __builtin_nanf("");
+    const float a = window_prediction(plain, flipped, order, l, J, j, c);
+    if (l == r) return a;
+    const float b = window_prediction(plain, flipped, order, r, J, j, c);
+    const double pa = (double)a * (1.0 - w);
+    const double pb = (double)b * w;
+    return (float)(pa + pb);
+}
+
+// out (frames, J, 3), flattened: one thread per four consecutive floats.  root >= 0: the frame's root joint is subtracted in float32
+// (that joint comes out exactly 0).
+static __global__ void __launch_bounds__(256)
+assemble_tracks_kernel(const float* __restrict__ plain, const float* __restrict__ flipped, const long num_windows, const int32_t* __restrict__ order,
+                       const int32_t* __restrict__ left, const int32_t* __restrict__ right, const double* __restrict__ weight, const long frames,
+                       const int J, const int root, float* __restrict__ out)
+{
+    const long per = (long)J * 3, total = frames * per;
+    const long e0 = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (e0 >= total) return;
+    float v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const long e = (e0 + k < total) ? e0 + k : e0;
+        const long f = e / per;
+        const int r = (int)(e - f * per), j = r / 3, c = r - j * 3;
+        const long l = left[f], rr = right[f];
+        const double w = weight[f];
+        v[k] = frame_value(plain, flipped, order, num_windows, l, rr, w, J, j, c);
+        if (root >= 0) v[k] = v[k] - frame_value(plain, flipped, order, num_windows, l, rr, w, J, root, c);
+    }
+    if (e0 + 4 <= total) *reinterpret_cast<float4*>(out + e0) = make_float4(v[0], v[1], v[2], v[3]);
+    else for (int k = 0; e0 + k < total; ++k) out[e0 + k] = v[k];
+}
+
+}  // namespace uu3d

@@ -37,6 +37,26 @@ class PoseTable(object):
         self.actions = np.asarray(actions if actions is not None else np.zeros(n, np.int64))
         self.frame_rates = np.asarray(frame_rates if frame_rates is not None else np.full(n, 50), np.int64)
 
+    @classmethod
+    def from_device(cls, kp2d, lens):
+        """A table without 3D data around 2D poses that already lie on the device: ``kp2d`` (sum(lens), J, 2) float32, contiguous, the videos
+        back to back; ``lens`` the frames of each video (host).  Nothing is copied but the two small index arrays."""
+        import torch
+        self = cls.__new__(cls)
+        self.torch = torch
+        self.device = kp2d.device
+        self.lens = np.asarray(lens, np.int32)
+        self.starts = np.concatenate([[0], np.cumsum(self.lens)[:-1]]).astype(np.int64)
+        if kp2d.dim() != 3 or kp2d.shape[2] != 2 or kp2d.dtype != torch.float32 or not kp2d.is_contiguous() or int(kp2d.shape[0]) != int(self.lens.sum()):
+            raise ValueError("kp2d must be a contiguous (sum(lens), J, 2) float32 tensor")
+        self.J = int(kp2d.shape[1])
+        self.kp2d, self.kp3d = kp2d, None
+        self.d_starts = torch.from_numpy(self.starts).pin_memory().to(self.device, non_blocking=True)
+        self.d_lens = torch.from_numpy(self.lens).pin_memory().to(self.device, non_blocking=True)
+        n = len(self.lens)
+        self.subjects, self.actions, self.frame_rates = np.zeros(n, np.int64), np.zeros(n, np.int64), np.full(n, 50, np.int64)
+        return self
+
 
 class SequenceGenerator(object):
     """Same constructor vocabulary as the reference class (uplifiting_dataset.py:215-219)."""

@@ -27,15 +27,23 @@ def _log(*args):
     print(*args, flush=True)
 
 
+def prediction_stride(config):
+    """The keyframe stride of eval.py:195-251 (``evaluation.evaluate_predictions``): frames whose index is a multiple of it keep their own
+    prediction, the others are interpolated.  None: no strided evaluation, every frame keeps its own."""
+    if not (config.SEQUENCE_STRIDE > 1 and config.TEST_STRIDED_EVAL is True):
+        return None
+    mask_stride = config.MASK_STRIDE[0] if isinstance(config.MASK_STRIDE, (list, tuple)) else config.MASK_STRIDE
+    if getattr(config, "EVAL_DISABLE_LEARNED_UPSAMPLING", False) and mask_stride is not None:
+        return mask_stride
+    return config.SEQUENCE_STRIDE
+
+
 def needed_windows(frame_indices, config):
     """Boolean mask of the windows whose central prediction is read by the reports of eval.py:195-251."""
     idx = np.asarray(frame_indices)
-    if not (config.SEQUENCE_STRIDE > 1 and config.TEST_STRIDED_EVAL is True):
+    stride = prediction_stride(config)
+    if stride is None:
         return np.ones(len(idx), bool)
-    mask_stride = config.MASK_STRIDE[0] if isinstance(config.MASK_STRIDE, (list, tuple)) else config.MASK_STRIDE
-    stride = config.SEQUENCE_STRIDE
-    if getattr(config, "EVAL_DISABLE_LEARNED_UPSAMPLING", False) and mask_stride is not None:
-        stride = mask_stride
     # interpolate_between_keyframes overwrites every non-keyframe that has a keyframe before it in its video; frame 0 of a
     # video is always a keyframe, so every non-keyframe is overwritten.  The KEYFRAMES report reads keyframes of the (coarser
     # or equal) input stride only.
@@ -221,11 +229,20 @@ def predict_windows(model, generator, descriptors, config, batch_size, flip=True
     pipeline, graphs as ``graph`` says).  Within ~3e-5 of the default (the s2t GEMM sums in another split-K order).  The table is bounded by
     ``frame_table_bytes``: windows run in chunks whose frames fit."""
     import torch
+    if len(descriptors) == 0:
+        return torch.empty((0, generator.table.J, 3), dtype=torch.float32, device=generator.table.device)
+    raw = _predict_windows_raw(model, generator, descriptors, batch_size, flip, depth, graph, reuse_frames, frame_table_bytes)
+    return _unflip(raw, config, flip)
+
+
+def _predict_windows_raw(model, generator, descriptors, batch_size, flip, depth, graph, reuse_frames, frame_table_bytes=FRAME_TABLE_BYTES):
+    """The body of ``predict_windows`` up to its un-flip: the central predictions as the pipeline leaves them, (1 | 2, W, J, 3) float32 on the
+    device -- [0] of the windows, [1] (``flip``) of their mirrored copies, still mirrored.  ``predict.predict_tracks`` un-flips, averages and
+    interpolates them in one kernel (uu3d_assemble_tracks).  W >= 1."""
+    import torch
     W = len(descriptors)
     J = generator.table.J
     dev = generator.table.device
-    if W == 0:
-        return torch.empty((0, J, 3), dtype=torch.float32, device=dev)
     # raw central predictions of the windows (and of their mirrored copies): the un-flip / average of eval.py:163-166 runs ONCE over
     # all windows at the end instead of five small launches per batch
     raw = torch.empty((2 if flip else 1, W, J, 3), dtype=torch.float32, device=dev)
@@ -240,7 +257,7 @@ def predict_windows(model, generator, descriptors, config, batch_size, flip=True
 
     if reuse_frames:
         _predict_windows_reuse(model, generator, descriptors, batch_size, flip, depth, graph, finish, frame_table_bytes)
-        return _unflip(raw, config, flip)
+        return raw
     pipe = model.pipeline(rows, depth=depth, graph=graph) if (depth is None or depth > 1 or graph) else None
     if pipe is not None:
         depth = pipe.depth
@@ -282,7 +299,7 @@ def predict_windows(model, generator, descriptors, config, batch_size, flip=True
             pipe.check_range()                                     # f16x3 range guard (include/uu3d.h): once per evaluation, never per batch
         finally:
             pipe.close()
-    return _unflip(raw, config, flip)
+    return raw
 
 
 def _unflip(raw, config, flip):

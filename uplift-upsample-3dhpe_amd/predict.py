@@ -1,0 +1,253 @@
+"""3D poses for your own 2D keypoint tracks: ``predict_tracks`` takes the 2D keypoints of any number of videos -- from any detector, given
+for every frame or only for every ``s_in``-th one -- and returns one 3D pose per frame of every video, on the device.
+
+    pixel coordinates  ->  uu3d_normalize_tracks (normalised screen coordinates, keyframes scattered into the dense pose table)
+    ->  data.PoseTable / data.SequenceGenerator with the evaluation settings  ->  the windows ``eval.needed_windows`` keeps
+    ->  eval.predict_windows' pipeline (device window gather, stride masks, flip in the same forward, ``reuse_frames``)
+    ->  uu3d_assemble_tracks (un-flip, average, linear interpolation between predicted frames by ``evaluation.keyframe_plan``, root shift)
+
+The tracks are taken at the frame rate the config was trained for (Human3.6M: 50 Hz); nothing is resampled.  Between the first window
+gather and the return nothing is copied to the host.  What still waits for the device inside the call: ``eval.predict_windows``
+synchronises the stream once after the last forward (its pipeline's buffers go away) and reads the f16x3 range flag; with
+``reuse_frames`` it also reads one frame count per chunk of the feature table.  The two kernels of this module and their uploads
+(pinned, asynchronous) never wait.
+
+    python -m uplift_upsample_3dhpe_amd.predict --config C --weights W.h5 --input tracks.npz --output out.npz \\
+        [--resolution W H] [--mask_stride S] [--keyframes_only]
+"""
+import argparse
+import ctypes as C
+
+import numpy as np
+
+from . import _capi, evaluation
+from . import eval as ev
+from .data import PoseTable, SequenceGenerator
+
+
+def _ptr(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _upload(a, dtype, device):
+    """Host array -> device tensor through pinned memory, asynchronously: the host never waits for the stream."""
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a, dtype)).pin_memory().to(device, non_blocking=True)
+
+
+def normalize_tracks(src, table, lens, resolutions=None, key_stride=0, src_lens=None):
+    """uu3d_normalize_tracks on the current stream.  ``src`` (R, J, 2) float32 on the device; ``table`` (sum(lens), J, 2) float32 (may be
+    ``src`` when ``key_stride`` is 0); ``lens``: frames per track; ``resolutions`` (T, 2) (w, h) per track or None (no conversion);
+    ``key_stride`` > 0: ``src`` holds ``src_lens[t]`` keyframes of track t (frames 0, key_stride, ...), scattered into the zero-filled table."""
+    import torch
+    lib = _capi.load_library()
+    dev = table.device
+    lens = np.asarray(lens, np.int64)
+    T, rows, J = len(lens), int(lens.sum()), int(table.shape[1])
+    row_track = _upload(np.repeat(np.arange(T, dtype=np.int32), lens), np.int32, dev)
+    res = None if resolutions is None else _upload(np.asarray(resolutions, np.float64).reshape(T, 2), np.float64, dev)
+    tstart = sstart = None
+    if key_stride > 0:
+        src_lens = np.asarray(src_lens, np.int64)
+        tstart = _upload(np.concatenate([[0], np.cumsum(lens)[:-1]]), np.int64, dev)
+        sstart = _upload(np.concatenate([[0], np.cumsum(src_lens)[:-1]]), np.int64, dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _capi.check(lib, lib.uu3d_normalize_tracks(_ptr(src), int(src.shape[0]), _ptr(table), rows, J, _ptr(row_track), T, _ptr(res),
+                                                   _ptr(tstart), _ptr(sstart), int(key_stride), C.c_void_p(stream)), None)
+    return table
+
+
+def assemble_tracks(plain, flipped, left, right, weight, flip_order=None, root=-1):
+    """uu3d_assemble_tracks on the current stream.  ``plain`` / ``flipped`` (W, J, 3) float32 on the device (``flipped`` None: no flip);
+    ``left`` / ``right`` / ``weight``: the plan of ``evaluation.keyframe_plan`` with rows of those arrays (host arrays of F entries);
+    ``root`` >= 0: that joint is subtracted.  -> (F, J, 3) float32 on the device."""
+    import torch
+    lib = _capi.load_library()
+    dev = plain.device
+    W, J = int(plain.shape[0]), int(plain.shape[1])
+    F = len(left)
+    if plain.dtype != torch.float32 or not plain.is_contiguous() or plain.dim() != 3 or plain.shape[2] != 3:
+        raise ValueError("plain must be a contiguous (W, J, 3) float32 device tensor")
+    if flipped is not None and (flipped.shape != plain.shape or flipped.dtype != torch.float32 or not flipped.is_contiguous()):
+        raise ValueError("flipped must match plain")
+    if flipped is not None and (flip_order is None or len(flip_order) != J):
+        raise ValueError("flipped predictions need the J entries of AUGM_FLIP_KEYPOINT_ORDER")
+    d_left, d_right = _upload(left, np.int32, dev), _upload(right, np.int32, dev)
+    d_weight = _upload(weight, np.float64, dev)
+    d_order = None if flipped is None else _upload(flip_order, np.int32, dev)
+    out = torch.empty((F, J, 3), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _capi.check(lib, lib.uu3d_assemble_tracks(_ptr(plain), _ptr(flipped), W, _ptr(d_order), _ptr(d_left), _ptr(d_right), _ptr(d_weight),
+                                                  F, J, int(root), _ptr(out), C.c_void_p(stream)), None)
+    return out
+
+
+def _device_track(t, device):
+    import torch
+    if isinstance(t, torch.Tensor):
+        t = t.to(device=device, dtype=torch.float32)
+    else:
+        t = _upload(np.asarray(t), np.float32, device)
+    if t.dim() != 3 or t.shape[2] != 2:
+        raise ValueError(f"a track must be (T, J, 2), got {tuple(t.shape)}")
+    return t
+
+
+def keyframe_count(length, stride):
+    """Frames 0, stride, 2 stride, ... of a track of ``length`` frames."""
+    return (int(length) + int(stride) - 1) // int(stride)
+
+
+def pose_table(tracks, device, resolutions=None, key_stride=0, lengths=None):
+    """The dense, normalised ``data.PoseTable`` of the tracks (uu3d_normalize_tracks) -> (table, frames per track)."""
+    import torch
+    tr = [_device_track(t, device) for t in tracks]
+    if not tr:
+        raise ValueError("no tracks")
+    J = int(tr[0].shape[1])
+    if any(int(t.shape[1]) != J for t in tr):
+        raise ValueError("all tracks must have the same number of keypoints")
+    given = np.array([int(t.shape[0]) for t in tr], np.int64)
+    if key_stride > 0:
+        if lengths is None or len(lengths) != len(tr):
+            raise ValueError("keyframes_only needs `lengths`: the number of frames of every track")
+        lens = np.asarray(lengths, np.int64)
+        want = np.array([keyframe_count(n, key_stride) for n in lens], np.int64)
+        if (given != want).any():
+            i = int(np.flatnonzero(given != want)[0])
+            raise ValueError(f"track {i}: {int(lens[i])} frames at keyframe stride {key_stride} are {int(want[i])} keyframes, got {int(given[i])}")
+    else:
+        lens = given
+    if (lens < 1).any():
+        raise ValueError("every track needs at least one frame")
+    if resolutions is not None:
+        resolutions = np.asarray(resolutions, np.float64)
+        if resolutions.shape == (2,):
+            resolutions = np.tile(resolutions, (len(tr), 1))
+        if resolutions.shape != (len(tr), 2) or not (resolutions > 0).all():
+            raise ValueError("resolutions must be one positive (w, h) or one per track")
+    src = torch.cat(tr, 0).contiguous() if len(tr) > 1 else tr[0].contiguous()
+    if key_stride > 0 or resolutions is not None:
+        kp = torch.empty((int(lens.sum()), J, 2), dtype=torch.float32, device=src.device)      # (never in the caller's own memory)
+        normalize_tracks(src, kp, lens, resolutions, key_stride, given)
+    else:
+        kp = src
+    return PoseTable.from_device(kp, lens), lens
+
+
+def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, flip=None, keyframes_only=False, reuse_frames=True,
+                   batch_size=None, root_relative=True, depth=None, lengths=None, graph=True):
+    """One 3D pose per frame for each 2D keypoint track -> list of (T_i, J, 3) float32 tensors on the model's device (views of one buffer).
+
+    ``tracks``: list of (T_i, J, 2) arrays or tensors, on the host or the device, at the frame rate the config was trained for (nothing is
+    resampled).  ``resolutions``: None = the coordinates are normalised already (``h36m.normalize_screen_coordinates``), else one (w, h) in
+    pixels or one per track.  ``mask_stride`` (default: the config's first MASK_STRIDE) is the input stride s_in: the network sees frames
+    0, s_in, 2 s_in, ... of a track only.  ``flip`` (default config.EVAL_FLIP): mirrored copy in the same forward, averaged.
+    ``root_relative``: joint config.ROOT_KEYTPOINT is subtracted (it comes out exactly 0), as the evaluation compares poses.
+
+    ``keyframes_only=True``: ``tracks[i]`` holds only the frames 0, s_in, 2 s_in, ... and ``lengths[i]`` says how many frames T_i the video
+    has.  All other frames are masked and never reach the network, so the result equals the full-track call bit for bit -- with one
+    exception that the window rules of the reference bring: "copy" padding behind the end of a track repeats the last frame whose index is
+    a multiple of SEQUENCE_STRIDE, and when s_in > SEQUENCE_STRIDE that frame need not be one of the given ones.  It is read as zeros
+    then, and the frames whose window reaches beyond the end of their track (the last SEQUENCE_LENGTH // 2 * SEQUENCE_STRIDE) may differ
+    from the full-track call; all earlier frames are still bit-identical (``padding_source_is_keyframe`` tells which case a track is).
+
+    Frames are predicted by the model where ``eval.needed_windows`` keeps their window (every SEQUENCE_STRIDE-th with TEST_STRIDED_EVAL) and
+    interpolated linearly in between by the rules of ``evaluation.interpolate_between_keyframes``; frames behind the last predicted one
+    repeat it.  ``reuse_frames`` / ``batch_size`` (default config.BATCH_SIZE) / ``depth`` / ``graph`` go to ``eval.predict_windows``; a
+    model with generic dimensions has no frames form and runs the window forward.  One rank only."""
+    import torch
+    dev = model.device
+    cfg = config.copy()
+    if mask_stride is None:
+        mask_stride = cfg.MASK_STRIDE[0] if isinstance(cfg.MASK_STRIDE, (list, tuple)) else cfg.MASK_STRIDE
+    cfg.MASK_STRIDE = mask_stride
+    flip = bool(cfg.EVAL_FLIP) if flip is None else bool(flip)
+    if keyframes_only and mask_stride is None:
+        raise ValueError("keyframes_only needs a mask stride")
+    table, lens = pose_table(tracks, dev, resolutions, int(mask_stride) if keyframes_only else 0, lengths)
+    gen = SequenceGenerator(table, seq_len=cfg.SEQUENCE_LENGTH, target_frame_rate=50, subsample=1, stride=cfg.SEQUENCE_STRIDE,
+                            padding_type=cfg.PADDING_TYPE, flip_augment=False, flip_lr_indices=cfg.AUGM_FLIP_KEYPOINT_ORDER,
+                            mask_stride=mask_stride, stride_mask_align_global=True, rand_shift_stride_mask=False, shuffle=False)
+    desc = gen.descriptors()                                         # one window per frame, in table order: position p is table row p
+    frame_idx = desc[:, 1]
+    run = np.flatnonzero(ev.needed_windows(frame_idx, cfg))
+    raw = ev._predict_windows_raw(model, gen, desc[run], int(batch_size or cfg.BATCH_SIZE), flip, depth, graph,
+                                  bool(reuse_frames) and bool(model.arch.compiled_dims))
+    rows = np.full(len(desc), -1, np.int64)
+    rows[run] = np.arange(len(run))
+    stride = ev.prediction_stride(cfg)
+    if stride is None:
+        left = right = rows
+        weight = np.zeros(len(desc), np.float64)
+    else:
+        left, right, weight, _ = evaluation.keyframe_plan(frame_idx, stride, rows=rows)
+    out = assemble_tracks(raw[0], raw[1] if flip else None, left, right, weight, flip_order=cfg.AUGM_FLIP_KEYPOINT_ORDER,
+                          root=int(cfg.ROOT_KEYTPOINT) if root_relative else -1)
+    return list(torch.split(out, [int(n) for n in lens], 0))
+
+
+def padding_source_is_keyframe(length, config, mask_stride):
+    """Whether the frame that "copy" padding repeats behind the end of a track of ``length`` frames (the last one whose index is a multiple
+    of SEQUENCE_STRIDE: the windows that are run are centred on such frames) is a multiple of ``mask_stride`` too -- then
+    ``keyframes_only`` input gives the bits of the full track on every frame.  True for zero padding."""
+    if config.PADDING_TYPE != "copy":
+        return True
+    s = int(config.SEQUENCE_STRIDE)
+    return ((int(length) - 1) // s * s) % int(mask_stride) == 0
+
+
+def _load_model(config, weights_path):
+    from .net.uplift_upsample_transformer_constructor import build_uplift_upsample_transformer
+    model = build_uplift_upsample_transformer(config)
+    model.load_weights(weights_path, skip_mismatch=False, verbose=False)
+    return model
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(prog="python -m uplift_upsample_3dhpe_amd.predict", description="3D poses for the 2D keypoint tracks of an .npz file "
+                                "(one (T, J, 2) array per track) -> an .npz with the same keys and (T, J, 3) float32 arrays.")
+    p.add_argument("--config", required=True, help="model config (.json)")
+    p.add_argument("--weights", required=True, help="weights (.h5)")
+    p.add_argument("--input", required=True, help=".npz with one (T, J, 2) array per track")
+    p.add_argument("--output", required=True, help=".npz to write")
+    p.add_argument("--resolution", type=float, nargs=2, metavar=("W", "H"), default=None,
+                   help="image size in pixels of all tracks; without it the coordinates are taken as normalised already")
+    p.add_argument("--mask_stride", type=int, default=None, help="input stride s_in (default: the config's first MASK_STRIDE)")
+    p.add_argument("--keyframes_only", action="store_true",
+                   help="the arrays hold frames 0, s_in, 2 s_in, ... only; a track of K keyframes is taken to have (K - 1) * s_in + 1 frames")
+    return p.parse_args(argv)
+
+
+def main(argv=None):
+    from .net.uplift_upsample_transformer_config import UpliftUpsampleConfig
+    args = parse_args(argv)
+    config = UpliftUpsampleConfig(args.config)
+    with np.load(args.input) as z:
+        names = list(z.files)
+        tracks = [np.asarray(z[k], np.float32) for k in names]
+    if not names:
+        raise SystemExit(f"{args.input} holds no arrays")
+    for k, t in zip(names, tracks):
+        if t.ndim != 3 or t.shape[2] != 2 or t.shape[1] != config.NUM_KEYPOINTS:
+            raise SystemExit(f"{args.input}[{k}] has shape {t.shape}, expected (T, {config.NUM_KEYPOINTS}, 2)")
+    ms = args.mask_stride
+    if ms is None:
+        ms = config.MASK_STRIDE[0] if isinstance(config.MASK_STRIDE, (list, tuple)) else config.MASK_STRIDE
+    lengths = None
+    if args.keyframes_only:
+        if ms is None:
+            raise SystemExit("--keyframes_only needs a mask stride")
+        lengths = [(len(t) - 1) * int(ms) + 1 for t in tracks]
+    model = _load_model(config, args.weights)
+    poses = predict_tracks(model, config, tracks, resolutions=None if args.resolution is None else tuple(args.resolution), mask_stride=ms,
+                           keyframes_only=args.keyframes_only, lengths=lengths)
+    np.savez(args.output, **{k: np.asarray(p.detach().cpu().numpy(), np.float32) for k, p in zip(names, poses)})
+    print(f"wrote {args.output}: {len(names)} tracks, {sum(int(p.shape[0]) for p in poses)} frames", flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())
