@@ -347,6 +347,57 @@ int uu3d_forward_frames_ex(uu3d_model* model, const float* features_dev, int64_t
                            float* const* attention_out, void* workspace_dev, size_t workspace_bytes, int32_t schedule, void* stream);
 
 /*
+ * LIVE TRACKS (stream.StreamSession; compiled dims only -- handles with generic dims return UU3D_ERR_UNSUPPORTED).  `slots` tracks grow by
+ * one frame of 2D keypoints per tick; after the push that made frame t the newest of a slot, the pose of frame c = t - lookahead comes out
+ * when c >= 0 and c % pred_stride == 0 (the windows eval.needed_windows keeps), computed from the window uu3d_gather_window_frames writes
+ * for a video of t + 1 frames centred on c with a globally aligned stride mask: frames that do not exist yet are padded as the end of a
+ * video is.  Per tick, on one stream, in this order:
+ *
+ *   uu3d_stream_stage(model, cfg, kp_dev (slots, J, 2) f32, resolution_dev (slots, 2) f64 (w, h) or NULL, active_dev (slots) u8,
+ *                     flip_order_dev (J) i32 (NULL without flip), frames_out_dev (halves * slots, J, 2) f32, stream)
+ *       the pushed frames in normalised screen coordinates (the bits of uu3d_normalize_tracks: one device helper) and, with flip, behind
+ *       them their mirrored copies (x negated, joints permuted); halves = flip ? 2 : 1.  An inactive slot's frames are zeros.
+ *   uu3d_frame_features on frames_out_dev (halves * slots frames) -> features_dev (halves * slots, d_t)
+ *   uu3d_stream_commit(model, cfg, state_dev, features_dev, active_dev, rows_dev (halves * slots, N) i32, stride_mask_dev (halves * slots, N)
+ *                      u8, fresh_dev (slots) u8, stream)
+ *       one launch, one workgroup per slot.  An active slot's frame counter advances (new frame index f = the old count); the features are
+ *       stored as the slot's edge row when f % seq_stride == 0 and in ring place (f / mask_stride) % ring_capacity when f % mask_stride == 0.
+ *       Then the window of this tick as rows of the state block's feature table: -1 for a token the stride mask drops (the zero row for a
+ *       model without strided input), the zero row where zero padding reads no frame, the ring place of a keyframe, the edge row for copy
+ *       padding behind the newest frame (that frame is a multiple of seq_stride, not necessarily of mask_stride), the flipped half of the
+ *       table for the mirrored windows.  fresh = 1 where a pose comes out at this tick; any other slot gets an all-masked window (finite,
+ *       discarded).  The frame and mask rules are the device helper uu3d_gather_windows and uu3d_gather_window_frames share.
+ *   uu3d_forward_frames_ex with features_dev = state_dev + table_offset, num_rows = table_rows, batch = halves * slots
+ *   uu3d_stream_emit(model, cfg, state_dev, central_dev (halves * slots, J, 3), flip_order_dev, fresh_dev, out_dev (slots, J, 3) f32, stream)
+ *       un-flip and average in float32 as uu3d_assemble_tracks (one device helper), root_index >= 0: that joint subtracted.  A fresh slot's
+ *       pose goes to out_dev and to the held poses of the state block; any other slot's out_dev row is its held pose.
+ *
+ *   uu3d_stream_reset(model, cfg, state_dev, slot_mask_dev (slots) u8 or NULL = every slot, stream): those slots start a new track
+ *   (zero frames, held pose 0).
+ *
+ * The state block (256-byte aligned, uu3d_stream_state_bytes; all zeros = every slot empty, except that the caller stores the features of
+ * an all-zero frame in the table's row zero_row) is laid out by uu3d_stream_state_layout: frame counters (slots) i32 at frames_offset, held
+ * poses (slots, J, 3) f32 at held_offset, the feature table (table_rows, d_t) f32 at table_offset = per half and slot ring_capacity ring
+ * rows and one edge row, then the zero row.  ring_capacity = (lookahead + (N / 2) * seq_stride) / mask_stride + 1 covers every keyframe a
+ * window reaches, so no ring place a window reads has been overwritten.  0 <= lookahead <= (N / 2) * seq_stride; mask_stride a multiple of
+ * seq_stride.  No atomics, one writer per output element, 16-byte stores where rows allow; every launch has the same arguments at every
+ * tick (the counters live on the device), so the five steps replay from ONE captured hipGraph, a linear chain.
+ */
+typedef struct uu3d_stream_config {
+    int32_t slots, seq_stride, mask_stride, pred_stride, lookahead, flip, pad_edge /* 1 = "copy" padding */, root_index /* < 0: absolute */;
+} uu3d_stream_config;
+typedef struct uu3d_stream_layout { int64_t ring_capacity, table_rows, zero_row, frames_offset, held_offset, table_offset, bytes; } uu3d_stream_layout;
+size_t uu3d_stream_state_bytes(const uu3d_model* model, const uu3d_stream_config* cfg);
+int uu3d_stream_state_layout(const uu3d_model* model, const uu3d_stream_config* cfg, uu3d_stream_layout* out);
+int uu3d_stream_stage(uu3d_model* model, const uu3d_stream_config* cfg, const float* kp_dev, const double* resolution_dev,
+                      const uint8_t* active_dev, const int32_t* flip_order_dev, float* frames_out_dev, void* stream);
+int uu3d_stream_commit(uu3d_model* model, const uu3d_stream_config* cfg, void* state_dev, const float* features_dev,
+                       const uint8_t* active_dev, int32_t* rows_dev, uint8_t* stride_mask_dev, uint8_t* fresh_dev, void* stream);
+int uu3d_stream_emit(uu3d_model* model, const uu3d_stream_config* cfg, void* state_dev, const float* central_dev,
+                     const int32_t* flip_order_dev, const uint8_t* fresh_dev, float* out_dev, void* stream);
+int uu3d_stream_reset(uu3d_model* model, const uu3d_stream_config* cfg, void* state_dev, const uint8_t* slot_mask_dev, void* stream);
+
+/*
  * Per-kernel timing of the next uu3d_forward calls with HIP events on the launch stream.
  * When enabled, uu3d_forward records an event pair around every launch; uu3d_profile_read
  * synchronises those events and returns the per-launch records of the LAST forward.

@@ -1,0 +1,95 @@
+"""Microseconds per tick of stream.StreamSession (one frame of 2D keypoints per slot in, one 3D pose per slot out), flip on, against the
+way to get the same pose without it: the host builds this tick's window and stride mask for every slot from the frames so far (numpy),
+uploads them with their mirrored copies and calls ``model([x, mask])`` once -- the spatial stack over all frames of every window, every tick.
+A tick = host clock from the call to the synchronised result (a live consumer reads every pose); host input in all three variants.
+Median (and 90th percentile) over --ticks ticks after --warmup ticks, per config and slot count.
+   python tools/stream_bench.py [--slots 1,8,64] [--cases h36m_81:4,h36m_351:5] [--ticks 300] [--warmup 60] [--lookahead 0]"""
+import argparse, json, os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--slots", default="1,8,64")
+    ap.add_argument("--cases", default="h36m_81:4,h36m_351:5")
+    ap.add_argument("--ticks", type=int, default=300)
+    ap.add_argument("--warmup", type=int, default=60)
+    ap.add_argument("--lookahead", type=int, default=0)
+    args = ap.parse_args()
+    import numpy as np, torch
+    import uplift_upsample_3dhpe_amd as pkg
+    from uplift_upsample_3dhpe_amd import synthetic as util
+    from uplift_upsample_3dhpe_amd import h36m, stream
+    if not torch.cuda.is_available():
+        raise SystemExit("stream_bench needs the GPU: nothing is measured without one")
+    W, H = 1920, 1080
+    total = args.warmup + args.ticks
+    results = []
+    for case in args.cases.split(","):
+        name, msv = case.split(":")
+        ms = int(msv)
+        cfg = util.load_config(name)
+        arch = pkg.arch_from_config(cfg)
+        model = pkg.build_uplift_upsample_transformer(cfg, weights=pkg.init_weights(arch, seed=0, perturb=0.1))
+        N, S, J = cfg.SEQUENCE_LENGTH, cfg.SEQUENCE_STRIDE, 17
+        order = np.asarray(cfg.AUGM_FLIP_KEYPOINT_ORDER)
+        d_order = torch.as_tensor(order, dtype=torch.long, device=model.device)
+        for T in (int(v) for v in args.slots.split(",")):
+            rng = np.random.default_rng(0)
+            px = (np.cumsum(rng.normal(0, 2.0, size=(total, T, J, 2)), 0) + rng.uniform(0.25, 0.75, size=(1, T, J, 2)) * [W, H]).astype(np.float32)
+
+            def session(graph):
+                s = stream.StreamSession(model, cfg, slots=T, resolutions=(W, H), mask_stride=ms, flip=True, lookahead=args.lookahead, graph=graph)
+                ts = []
+                for k in range(total):
+                    t0 = time.perf_counter()
+                    poses, fresh = s.push(px[k])
+                    torch.cuda.synchronize()
+                    ts.append(time.perf_counter() - t0)
+                s.check_range()
+                s.close()
+                return ts[args.warmup:]
+
+            def baseline():
+                hist = np.zeros((total, T, J, 2), np.float32)
+                ts = []
+                n = np.arange(N)
+                for k in range(total):
+                    t0 = time.perf_counter()
+                    hist[k] = h36m.normalize_screen_coordinates(px[k], w=W, h=H)
+                    L, c = k + 1, k - args.lookahead
+                    if c >= 0:
+                        f = c + (n - N // 2) * S
+                        lo, hi = c % S, (L - 1 - c % S) // S * S + c % S
+                        inside = (f >= 0) & (f < L)
+                        src = np.clip(f, lo, hi)
+                        m = (f % ms == 0)
+                        if cfg.PADDING_TYPE != "copy":
+                            m = m & inside
+                        x = hist[src].transpose(1, 0, 2, 3) * m[None, :, None, None]                      # (T, N, J, 2), masked frames zeroed
+                        xf = x[:, :, order].copy(); xf[..., 0] *= -1.0
+                        xb = torch.from_numpy(np.ascontiguousarray(np.concatenate([x, xf], 0), np.float32)).pin_memory().to(model.device, non_blocking=True)
+                        mb = torch.from_numpy(np.tile((f % ms == 0)[None], (2 * T, 1))).pin_memory().to(model.device, non_blocking=True)
+                        _, cen = model([xb, mb], training=False)
+                        fl = torch.cat([cen[T:, :, :1] * -1.0, cen[T:, :, 1:]], -1).index_select(1, d_order)
+                        pose = (cen[:T] + fl) / 2.0
+                        pose = pose - pose[:, cfg.ROOT_KEYTPOINT:cfg.ROOT_KEYTPOINT + 1]
+                    torch.cuda.synchronize()
+                    ts.append(time.perf_counter() - t0)
+                return ts[args.warmup:]
+
+            row = dict(config=name, mask_stride=ms, slots=T, lookahead=args.lookahead, ticks=args.ticks)
+            for key, fn in (("graph", lambda: session(True)), ("no_graph", lambda: session(False)), ("baseline", baseline)):
+                ts = np.asarray(fn())
+                row[key + "_us"] = round(1e6 * float(np.median(ts)), 1)
+                row[key + "_p90_us"] = round(1e6 * float(np.percentile(ts, 90)), 1)
+            row["speedup_vs_baseline"] = round(row["baseline_us"] / row["graph_us"], 2)
+            row["device"] = torch.cuda.get_device_name(0)
+            print(json.dumps(row), flush=True)
+            results.append(row)
+        del model
+    return results
+
+
+if __name__ == "__main__":
+    main()

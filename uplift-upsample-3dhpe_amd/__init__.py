@@ -28,3 +28,10 @@ def predict_tracks(model, config, tracks, **kwargs):
     """3D poses for your own 2D keypoint tracks, one per frame (``predict.predict_tracks``)."""
     from .predict import predict_tracks as _p
     return _p(model, config, tracks, **kwargs)
+
+
+def __getattr__(name):
+    if name == "StreamSession":                     # live tracks, one pose per pushed frame (``stream.StreamSession``)
+        from .stream import StreamSession
+        return StreamSession
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -32,6 +32,7 @@ EXPORTED_SYMBOLS = (
     "uu3d_frame_features_bytes", "uu3d_frame_features", "uu3d_gather_window_frames", "uu3d_forward_frames_ex",
     "uu3d_pose_errors", "uu3d_error_sums", "uu3d_error_sums_scratch_bytes",
     "uu3d_normalize_tracks", "uu3d_assemble_tracks",
+    "uu3d_stream_state_bytes", "uu3d_stream_state_layout", "uu3d_stream_stage", "uu3d_stream_commit", "uu3d_stream_emit", "uu3d_stream_reset",
 )
 # include/uu3d_ops.h
 OPS_SYMBOLS = (
@@ -74,6 +75,14 @@ class Uu3dConfig(C.Structure):
 class Uu3dProfileEntry(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("kernel", C.c_char * 32), ("ms", C.c_float),
                 ("flops", C.c_double), ("bytes", C.c_double)]
+
+
+class Uu3dStreamConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("slots", "seq_stride", "mask_stride", "pred_stride", "lookahead", "flip", "pad_edge", "root_index")]
+
+
+class Uu3dStreamLayout(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("ring_capacity", "table_rows", "zero_row", "frames_offset", "held_offset", "table_offset", "bytes")]
 
 
 # void (*uu3d_grad_ready_fn)(void* user, int64_t first, int64_t count, void* stream)
@@ -149,6 +158,19 @@ def load_library(path=None):
     lib.uu3d_gather_window_frames.argtypes = [vp, vp, vp, i32, i32, i32, i32, i64, i64, vp, vp, vp, vp]
     lib.uu3d_forward_frames_ex.restype = C.c_int
     lib.uu3d_forward_frames_ex.argtypes = [vp, vp, i64, vp, vp, i32, vp, vp, C.POINTER(vp), vp, sz, i32, vp]
+    scfg = C.POINTER(Uu3dStreamConfig)
+    lib.uu3d_stream_state_bytes.restype = sz
+    lib.uu3d_stream_state_bytes.argtypes = [vp, scfg]
+    lib.uu3d_stream_state_layout.restype = C.c_int
+    lib.uu3d_stream_state_layout.argtypes = [vp, scfg, C.POINTER(Uu3dStreamLayout)]
+    lib.uu3d_stream_stage.restype = C.c_int
+    lib.uu3d_stream_stage.argtypes = [vp, scfg, vp, vp, vp, vp, vp, vp]
+    lib.uu3d_stream_commit.restype = C.c_int
+    lib.uu3d_stream_commit.argtypes = [vp, scfg, vp, vp, vp, vp, vp, vp, vp]
+    lib.uu3d_stream_emit.restype = C.c_int
+    lib.uu3d_stream_emit.argtypes = [vp, scfg, vp, vp, vp, vp, vp, vp]
+    lib.uu3d_stream_reset.restype = C.c_int
+    lib.uu3d_stream_reset.argtypes = [vp, scfg, vp, vp, vp]
     lib.uu3d_world_to_cam_2d.restype = C.c_int
     lib.uu3d_world_to_cam_2d.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
     lib.uu3d_set_schedule.restype = C.c_int

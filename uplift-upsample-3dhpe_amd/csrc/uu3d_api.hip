@@ -34,6 +34,7 @@
 #include "uu3d_misc.h"
 #include "uu3d_metrics.h"
 #include "uu3d_tracks.h"
+#include "uu3d_stream.h"
 #include "uu3d_train.h"
 #include "uu3d_bwd.h"
 #include "uu3d_launch.h"
@@ -509,6 +510,105 @@ int uu3d_assemble_tracks(const float* plain, const float* flipped, int64_t num_w
     hipLaunchKernelGGL(assemble_tracks_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        plain, flipped, (long)num_windows, flip_order, left, right, weight, (long)num_frames, J, root_index < 0 ? -1 : root_index, out);
     return hipGetLastError() == hipSuccess ? UU3D_OK : UU3D_ERR_HIP;
+}
+
+// ---- live tracks (uu3d_stream.h): the session's state block and the four launches around uu3d_frame_features / uu3d_forward_frames_ex ----
+namespace {
+// the session's settings checked against the model; nullptr = fine, else what is wrong
+const char* stream_config_error(const uu3d_model* m, const uu3d_stream_config* s) {
+    if (!s) return "null uu3d_stream_config";
+    const uu3d_config& c = m->cfg;
+    if (s->slots < 1 || s->slots > (1 << 20)) return "slots must be in [1, 2^20]";
+    if (s->seq_stride < 1 || s->pred_stride < 1) return "seq_stride and pred_stride must be >= 1";
+    if (s->mask_stride < s->seq_stride || s->mask_stride % s->seq_stride != 0) return "mask_stride must be a multiple of seq_stride";
+    if (s->lookahead < 0 || (int64_t)s->lookahead > (int64_t)(c.num_frames / 2) * s->seq_stride) return "lookahead must be in [0, (num_frames / 2) * seq_stride]";
+    if (s->root_index >= c.num_keypoints) return "root_index must be below num_keypoints (negative: absolute poses)";
+    if ((int64_t)s->seq_stride * c.num_frames > (1 << 28)) return "seq_stride too large";
+    const StreamLayout L = stream_layout(s->slots, c.num_frames, c.num_keypoints, c.d_temporal, s->seq_stride, s->mask_stride, s->lookahead, s->flip);
+    if (L.table_rows > INT32_MAX / 2 || (int64_t)L.halves * s->slots * c.num_frames > INT32_MAX / 2) return "slots x ring capacity too large";
+    return nullptr;
+}
+StreamLayout stream_layout_of(const uu3d_model* m, const uu3d_stream_config* s) {
+    const uu3d_config& c = m->cfg;
+    return stream_layout(s->slots, c.num_frames, c.num_keypoints, c.d_temporal, s->seq_stride, s->mask_stride, s->lookahead, s->flip);
+}
+int stream_check(uu3d_model* m, const uu3d_stream_config* s, const char* who) {
+    if (m->generic) return fail(m, UU3D_ERR_UNSUPPORTED, std::string(who) + ": handles with generic dims have no frames form (compiled dims only)");
+    if (const char* e = stream_config_error(m, s)) return fail(m, UU3D_ERR_INVALID_ARGUMENT, std::string(who) + ": " + e);
+    return UU3D_OK;
+}
+}  // namespace
+
+int uu3d_stream_state_layout(const uu3d_model* mc, const uu3d_stream_config* s, uu3d_stream_layout* out) {
+    auto* m = const_cast<uu3d_model*>(mc);
+    if (!m || !out) return UU3D_ERR_INVALID_ARGUMENT;
+    if (const int st = stream_check(m, s, "uu3d_stream_state_layout")) return st;
+    const StreamLayout L = stream_layout_of(m, s);
+    out->ring_capacity = L.cap; out->table_rows = L.table_rows; out->zero_row = L.zero_row;
+    out->frames_offset = (int64_t)L.off_frames; out->held_offset = (int64_t)L.off_held; out->table_offset = (int64_t)L.off_table;
+    out->bytes = (int64_t)L.bytes;
+    return UU3D_OK;
+}
+
+size_t uu3d_stream_state_bytes(const uu3d_model* m, const uu3d_stream_config* s) {
+    uu3d_stream_layout l;
+    return uu3d_stream_state_layout(m, s, &l) == UU3D_OK ? (size_t)l.bytes : 0;
+}
+
+int uu3d_stream_stage(uu3d_model* m, const uu3d_stream_config* s, const float* kp, const double* resolution, const uint8_t* active,
+                      const int32_t* flip_order, float* frames_out, void* stream) {
+    if (!m) return UU3D_ERR_INVALID_ARGUMENT;
+    if (const int st = stream_check(m, s, "uu3d_stream_stage")) return st;
+    if (!kp || !active || !frames_out || (s->flip && !flip_order)) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_stage: null buffer");
+    if (((uintptr_t)frames_out & 15) != 0 || ((uintptr_t)kp & 7) != 0) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_stage: frames_out must be 16-byte, kp 8-byte aligned");
+    const int halves = s->flip ? 2 : 1;
+    const long threads = ((long)halves * s->slots * m->cfg.num_keypoints + 1) / 2;
+    hipLaunchKernelGGL(stream_stage_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       kp, resolution, active, flip_order, s->slots, m->cfg.num_keypoints, halves, frames_out);
+    return hipGetLastError() == hipSuccess ? UU3D_OK : fail(m, UU3D_ERR_HIP, "uu3d_stream_stage: launch failed");
+}
+
+int uu3d_stream_commit(uu3d_model* m, const uu3d_stream_config* s, void* state, const float* features, const uint8_t* active,
+                       int32_t* rows, uint8_t* stride_mask, uint8_t* fresh, void* stream) {
+    if (!m) return UU3D_ERR_INVALID_ARGUMENT;
+    if (const int st = stream_check(m, s, "uu3d_stream_commit")) return st;
+    if (!state || !features || !active || !rows || !stride_mask || !fresh) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_commit: null buffer");
+    if (((uintptr_t)state & 255) != 0 || ((uintptr_t)features & 15) != 0) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_commit: state must be 256-byte, features 16-byte aligned");
+    const StreamLayout L = stream_layout_of(m, s);
+    StreamParams p{};
+    p.slots = s->slots; p.N = m->cfg.num_frames; p.dt = m->cfg.d_temporal; p.seq_stride = s->seq_stride; p.s_in = s->mask_stride;
+    p.pred_stride = s->pred_stride; p.lookahead = s->lookahead; p.cap = L.cap; p.halves = L.halves; p.pad_edge = s->pad_edge != 0;
+    p.zero_row = (int)L.zero_row;
+    p.masked_row = m->cfg.has_strided_input ? -1 : (int)L.zero_row;      // (no strided input: a dropped frame is read as zeros, eval.py:67)
+    char* base = (char*)state;
+    hipLaunchKernelGGL(stream_commit_kernel, dim3(s->slots), dim3(256), 0, (hipStream_t)stream, p, features, active,
+                       (int32_t*)(base + L.off_frames), (float*)(base + L.off_table), rows, stride_mask, fresh);
+    return hipGetLastError() == hipSuccess ? UU3D_OK : fail(m, UU3D_ERR_HIP, "uu3d_stream_commit: launch failed");
+}
+
+int uu3d_stream_emit(uu3d_model* m, const uu3d_stream_config* s, void* state, const float* central, const int32_t* flip_order,
+                     const uint8_t* fresh, float* out, void* stream) {
+    if (!m) return UU3D_ERR_INVALID_ARGUMENT;
+    if (const int st = stream_check(m, s, "uu3d_stream_emit")) return st;
+    if (!state || !central || !fresh || !out || (s->flip && !flip_order)) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_emit: null buffer");
+    if (((uintptr_t)state & 255) != 0 || ((uintptr_t)out & 15) != 0) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_emit: state must be 256-byte, out 16-byte aligned");
+    const StreamLayout L = stream_layout_of(m, s);
+    const long threads = ((long)s->slots * L.per_pose + 3) / 4;
+    hipLaunchKernelGGL(stream_emit_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, central, L.halves,
+                       flip_order, fresh, s->slots, m->cfg.num_keypoints, s->root_index < 0 ? -1 : s->root_index,
+                       (float*)((char*)state + L.off_held), out);
+    return hipGetLastError() == hipSuccess ? UU3D_OK : fail(m, UU3D_ERR_HIP, "uu3d_stream_emit: launch failed");
+}
+
+int uu3d_stream_reset(uu3d_model* m, const uu3d_stream_config* s, void* state, const uint8_t* slot_mask, void* stream) {
+    if (!m) return UU3D_ERR_INVALID_ARGUMENT;
+    if (const int st = stream_check(m, s, "uu3d_stream_reset")) return st;
+    if (!state || ((uintptr_t)state & 255) != 0) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_reset: state must be a 256-byte aligned block");
+    const StreamLayout L = stream_layout_of(m, s);
+    const long threads = (long)s->slots * L.per_pose;
+    hipLaunchKernelGGL(stream_reset_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, slot_mask, s->slots,
+                       L.per_pose, (int32_t*)((char*)state + L.off_frames), (float*)((char*)state + L.off_held));
+    return hipGetLastError() == hipSuccess ? UU3D_OK : fail(m, UU3D_ERR_HIP, "uu3d_stream_reset: launch failed");
 }
 
 int uu3d_world_to_cam_2d(const float* world, const float* cams, int32_t B, int32_t N, int32_t J, float* cam3d, float* kp2d, void* stream) {

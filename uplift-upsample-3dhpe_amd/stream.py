@@ -1,0 +1,377 @@
+"""Live uplifting: ``StreamSession`` takes one frame of 2D keypoints per track and tick and returns one 3D pose per track, on the device.
+
+    s = StreamSession(model, config, slots=T, resolutions=(1920, 1080), lookahead=0)
+    poses, fresh = s.push(kp2d)            # (T, J, 2) host or device -> (T, J, 3) float32, (T,) bool, both on the device
+
+The one rule (the truncation identity): after the push that made frame t the newest of a track, the session emits the pose of frame
+c = t - lookahead -- when c >= 0 and ``eval.needed_windows`` keeps the window centred on c (TEST_STRIDED_EVAL: c % SEQUENCE_STRIDE == 0) --
+and that pose is what ``predict.predict_tracks`` returns for frame c of the track cut to its first t + 1 frames (same ``mask_stride``,
+``flip``, ``resolutions``, ``root_relative``).  Frames of the window that do not exist yet are padded by the config's PADDING_TYPE, as the
+end of a video is.  On every other push the slot's previous pose is held and reported as not fresh; nothing is interpolated.
+
+Per tick (include/uu3d.h, LIVE TRACKS): uu3d_stream_stage -> uu3d_frame_features on the ``slots`` (x 2 with flip) new
+frames -> uu3d_stream_commit (counters, keyframe ring, edge row, this tick's window rows and masks) -> uu3d_forward_frames_ex from the
+session's resident feature table -> uu3d_stream_emit.  The spatial stack runs once per pushed frame, not once per frame of the window.  The
+per-track counters live on the device, so the five steps are ONE captured hipGraph (``graph=True``) replayed at every tick; ``push`` never
+waits for the device.
+
+    python -m uplift_upsample_3dhpe_amd.stream --config C --weights W.h5 --input tracks.npz --output out.npz [--lookahead A] [--resolution W H]
+"""
+import argparse
+import ctypes as C
+import gc
+
+import numpy as np
+
+from . import _capi
+from . import eval as ev
+
+
+def _ptr(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def session_strides(config, mask_stride=None):
+    """(SEQUENCE_STRIDE, input stride s_in, prediction stride) of a session: ``mask_stride`` defaults to the config's first MASK_STRIDE (no
+    mask stride at all: every sampled frame is input); a pose comes out for centres that are multiples of the prediction stride."""
+    cfg = config.copy()
+    if mask_stride is None:
+        mask_stride = cfg.MASK_STRIDE[0] if isinstance(cfg.MASK_STRIDE, (list, tuple)) else cfg.MASK_STRIDE
+    cfg.MASK_STRIDE = mask_stride
+    S = int(cfg.SEQUENCE_STRIDE)
+    s_in = S if mask_stride is None else int(mask_stride)
+    if s_in < S or s_in % S != 0:
+        raise ValueError("the mask stride must be a multiple of the sequence stride")
+    return S, s_in, int(ev.prediction_stride(cfg) or 1)
+
+
+def max_lookahead(config):
+    return (int(config.SEQUENCE_LENGTH) // 2) * int(config.SEQUENCE_STRIDE)
+
+
+def ring_capacity(config, mask_stride=None, lookahead=0):
+    """Keyframes kept per slot: a window centred on newest - lookahead reads frames from (SEQUENCE_LENGTH // 2) * SEQUENCE_STRIDE before its
+    centre up to the newest one -- lookahead + half span + 1 consecutive indices, at most this many multiples of s_in."""
+    S, s_in, _ = session_strides(config, mask_stride)
+    return (int(lookahead) + max_lookahead(config)) // s_in + 1
+
+
+def emits(frames, lookahead, config, mask_stride=None):
+    """Whether the push that brought a track to ``frames`` frames emits a pose (of frame ``frames - 1 - lookahead``)."""
+    _, _, pred = session_strides(config, mask_stride)
+    c = int(frames) - 1 - int(lookahead)
+    return int(frames) >= 1 and c >= 0 and c % pred == 0
+
+
+def window_plan(frames, lookahead, config, mask_stride=None):
+    """The host mirror of uu3d_stream_commit's row rule for a track of ``frames`` frames: None when no pose comes out, else a dict of (N,)
+    arrays over the window centred on ``frames - 1 - lookahead`` --
+        "mask": the stride mask bit; "src": the frame a real token reads (-1: none -- a masked token, or zero padding);
+        "kind": 0 masked token, 1 zero row, 2 keyframe ring, 3 edge row; "place": the ring place of kind 2 (-1 otherwise)
+    -- and "centre"."""
+    if not emits(frames, lookahead, config, mask_stride):
+        return None
+    S, s_in, _ = session_strides(config, mask_stride)
+    N, L = int(config.SEQUENCE_LENGTH), int(frames)
+    cap = ring_capacity(config, mask_stride, lookahead)
+    pad_edge = config.PADDING_TYPE == "copy"
+    c = L - 1 - int(lookahead)
+    n = np.arange(N, dtype=np.int64)
+    f = c - ((N - 1) * S) // 2 + n * S
+    src = np.where(f < 0, f + ((-f + S - 1) // S) * S, np.where(f >= L, f - ((f - L + S) // S) * S, f))
+    inside = (f >= 0) & (f < L)
+    have = inside | (pad_edge & (src >= 0) & (src < L))
+    mask = np.mod((n - N // 2) * S + c, s_in) == 0
+    edge_frame = (L - 1) // S * S
+    kind = np.zeros(N, np.int64)
+    kind[mask & ~have] = 1
+    is_edge = mask & have & ~inside & (src == edge_frame)
+    kind[is_edge] = 3
+    ring = mask & have & ~is_edge
+    if (np.mod(src[ring], s_in) != 0).any() or (src[ring] < c - (N // 2) * S).any():
+        raise AssertionError("a window token reads a frame that is neither a kept keyframe nor the edge frame")
+    kind[ring] = 2
+    return {"centre": c, "mask": mask, "src": np.where(kind >= 2, src, -1), "kind": kind,
+            "place": np.where(kind == 2, (src // s_in) % cap, -1)}
+
+
+def _check_resolutions(resolutions, slots):
+    if resolutions is None:
+        return None
+    r = np.asarray(resolutions, np.float64)
+    if r.shape == (2,):
+        r = np.tile(r, (slots, 1))
+    if r.shape != (slots, 2) or not np.isfinite(r).all() or not (r > 0).all():
+        raise ValueError("resolutions must be one positive (w, h) or one per slot")
+    return np.ascontiguousarray(r)
+
+
+class StreamSession(object):
+
+    def __init__(self, model, config, slots, resolutions=None, mask_stride=None, flip=None, lookahead=0, root_relative=True, graph=True):
+        """``slots``: tracks served side by side (a slot is a track: ``reset`` starts a new one).  ``resolutions``: None = the coordinates
+        are normalised already, else one (w, h) in pixels or one per slot.  ``mask_stride`` / ``flip`` / ``root_relative`` as
+        ``predict.predict_tracks``.  ``lookahead`` = a: frames the answer may lag behind the newest one, 0 <= a <=
+        (SEQUENCE_LENGTH // 2) * SEQUENCE_STRIDE; with a at its maximum every window is complete.  ``graph``: replay one captured hipGraph
+        per tick instead of enqueueing the five steps.  Models with generic dims have no frames form: NotImplementedError."""
+        slots, lookahead = int(slots), int(lookahead)
+        if slots < 1:
+            raise ValueError("slots >= 1")
+        S, s_in, pred = session_strides(config, mask_stride)
+        if not 0 <= lookahead <= max_lookahead(config):
+            raise ValueError(f"lookahead must be in [0, {max_lookahead(config)}] = (SEQUENCE_LENGTH // 2) * SEQUENCE_STRIDE, got {lookahead}")
+        res = _check_resolutions(resolutions, slots)
+        if not model.arch.compiled_dims:
+            raise NotImplementedError("StreamSession needs the frames form of the forward (uu3d_frame_features / uu3d_forward_frames_ex), "
+                                      "which models with generic dims do not have")
+        import torch
+        self._torch = torch
+        self.model, self.slots, self.lookahead, self.graph = model, slots, lookahead, bool(graph)
+        self.seq_stride, self.mask_stride, self.pred_stride = S, s_in, pred
+        self.flip = bool(config.EVAL_FLIP) if flip is None else bool(flip)
+        self.captures = 0                                             # hipGraph captures so far (graph=True: 1 for the session's whole life)
+        a, dev = model.arch, model.device
+        self._lib = lib = _capi.load_library()
+        self._cfg = _capi.Uu3dStreamConfig(slots, S, s_in, pred, lookahead, int(self.flip), int(config.PADDING_TYPE == "copy"),
+                                           int(config.ROOT_KEYTPOINT) if root_relative else -1)
+        model._sync_from_trainer()
+        lay = _capi.Uu3dStreamLayout()
+        _capi.check(lib, lib.uu3d_stream_state_layout(model._h, C.byref(self._cfg), C.byref(lay)), model._h)
+        self.ring_capacity = int(lay.ring_capacity)
+        T, J, N, dt, H = slots, a.num_keypoints, a.num_frames, a.d_temporal, 2 if self.flip else 1
+        self._key = ("stream", id(self))
+        with torch.cuda.device(dev):
+            self._state = torch.zeros(int(lay.bytes), dtype=torch.uint8, device=dev)
+            view = lambda off, n, dtype: self._state[off:off + n * 4].view(dtype)
+            self._frames = view(int(lay.frames_offset), T, torch.int32)
+            self._table = view(int(lay.table_offset), int(lay.table_rows) * dt, torch.float32).view(int(lay.table_rows), dt)
+            self._zero_row = int(lay.zero_row)
+            self._kp = torch.zeros((T, J, 2), dtype=torch.float32, device=dev)
+            self._active = torch.ones((T,), dtype=torch.uint8, device=dev)
+            self._active_all = True
+            self._res = None if res is None else torch.from_numpy(res).pin_memory().to(dev, non_blocking=True)
+            self._order = torch.from_numpy(np.ascontiguousarray(config.AUGM_FLIP_KEYPOINT_ORDER, np.int32)).to(dev) if self.flip else None
+            self._staged = torch.zeros((H * T, J, 2), dtype=torch.float32, device=dev)
+            self._feats = torch.zeros((H * T, dt), dtype=torch.float32, device=dev)
+            self._rows = torch.full((H * T, N), -1, dtype=torch.int32, device=dev)
+            self._mask = torch.zeros((H * T, N), dtype=torch.uint8, device=dev)
+            self._fresh = torch.zeros((T,), dtype=torch.uint8, device=dev)
+            self._full = torch.empty((H * T, N, J, 3), dtype=torch.float32, device=dev) if model._returns_full else None
+            self._central = torch.zeros((H * T, J, 3), dtype=torch.float32, device=dev)
+            self._out = torch.zeros((T, J, 3), dtype=torch.float32, device=dev)
+            # a workspace of the session's own for uu3d_frame_features: the graph holds its address
+            self._fws = torch.empty(max(int(lib.uu3d_frame_features_bytes(model._h, H * T)), int(lib.uu3d_frame_features_bytes(model._h, 1))),
+                                    dtype=torch.uint8, device=dev)
+            self._zero_features()
+            if self.graph:
+                self._capture()
+
+    # ---- the five steps of a tick, on ``stream`` ----------------------------------------------------------------------------------
+    def _features(self, frames, out, stream):
+        m = self.model
+        _capi.check(self._lib, self._lib.uu3d_frame_features(m._h, _ptr(frames), int(frames.shape[0]), _ptr(out), _ptr(self._fws),
+                                                             C.c_size_t(self._fws.numel()), 0, C.c_void_p(stream.cuda_stream)), m._h)
+
+    def _zero_features(self):
+        """The features of an all-zero frame (zero padding) into the table's zero row."""
+        torch = self._torch
+        cur = torch.cuda.current_stream(self.model.device)
+        zero = torch.zeros((1,) + tuple(self._kp.shape[1:]), dtype=torch.float32, device=self.model.device)
+        self._features(zero, self._table[self._zero_row:], cur)
+
+    def _tick(self, stream):
+        lib, m, cfg, st = self._lib, self.model, C.byref(self._cfg), C.c_void_p(stream.cuda_stream)
+        _capi.check(lib, lib.uu3d_stream_stage(m._h, cfg, _ptr(self._kp), _ptr(self._res), _ptr(self._active), _ptr(self._order),
+                                               _ptr(self._staged), st), m._h)
+        self._features(self._staged, self._feats, stream)
+        _capi.check(lib, lib.uu3d_stream_commit(m._h, cfg, _ptr(self._state), _ptr(self._feats), _ptr(self._active), _ptr(self._rows),
+                                                _ptr(self._mask), _ptr(self._fresh), st), m._h)
+        # the latency schedule: what model.forward_frames takes (below 1024 token rows both schedules give the same bits)
+        m._forward_frames(self._table, self._rows, self._mask if m.has_strided_input else None, self._full, self._central, self._key, stream)
+        _capi.check(lib, lib.uu3d_stream_emit(m._h, cfg, _ptr(self._state), _ptr(self._central), _ptr(self._order), _ptr(self._fresh),
+                                              _ptr(self._out), st), m._h)
+
+    def _capture(self):
+        """One warm-up tick with every slot inactive (nothing advances), then the capture: a linear chain on one stream."""
+        torch = self._torch
+        dev = self.model.device
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        gc.collect()                                                  # (a collection inside a capture may free device memory: pipeline.py)
+        gc_was_on = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.stream(side):
+                self._active.zero_()
+                self._tick(side)
+                self._active.fill_(1)
+            side.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, stream=side):
+                self._tick(side)
+            self._graph = g
+            self.captures += 1
+        finally:
+            if gc_was_on:
+                gc.enable()
+        torch.cuda.current_stream(dev).wait_stream(side)
+        self.reset()
+
+    # ---- public ---------------------------------------------------------------------------------------------------------------------
+    def push(self, kp2d, active=None):
+        """One tick: ``kp2d`` (slots, J, 2), a host array or a tensor on the host or the device; ``active`` (slots,) bools or None = every slot
+        (an inactive slot's row of ``kp2d`` is ignored and its track does not grow).  -> (poses (slots, J, 3) float32, fresh (slots,) bool)
+        on the device: the session's own buffers, valid until the next ``push``.  ``fresh[i]``: slot i's pose is new at this tick -- the
+        pose of its frame ``frames[i] - 1 - lookahead``; otherwise ``poses[i]`` is the slot's previous pose (zeros before its first).
+        Enqueues on the current stream and returns; never waits for the device."""
+        torch = self._torch
+        m = self.model
+        dev = m.device
+        if m._weights_dirty or getattr(m, "_pending_assigns", False):
+            m._sync_from_trainer()                                    # (weights changed: the packs are rewritten on this stream)
+            with torch.cuda.device(dev):
+                self._zero_features()
+        if not isinstance(kp2d, torch.Tensor):
+            kp2d = torch.from_numpy(np.ascontiguousarray(kp2d, np.float32))
+        if tuple(kp2d.shape) != tuple(self._kp.shape):
+            raise ValueError(f"kp2d must be {tuple(self._kp.shape)}, got {tuple(kp2d.shape)}")
+        with torch.cuda.device(dev):
+            if not kp2d.is_cuda:
+                kp2d = kp2d.to(torch.float32).contiguous().pin_memory()       # host input goes through pinned memory, asynchronously
+            self._kp.copy_(kp2d, non_blocking=True)
+            if active is None:
+                if not self._active_all:
+                    self._active.fill_(1)
+                    self._active_all = True
+            else:
+                if isinstance(active, torch.Tensor):
+                    act = active.to(torch.uint8) if active.dtype != torch.bool else active.view(torch.uint8)
+                else:
+                    act = torch.from_numpy(np.ascontiguousarray(np.asarray(active) != 0).view(np.uint8))
+                if tuple(act.shape) != (self.slots,):
+                    raise ValueError(f"active must be ({self.slots},)")
+                if not act.is_cuda:
+                    act = act.contiguous().pin_memory()
+                self._active.copy_(act, non_blocking=True)
+                self._active_all = False
+            if self.graph:
+                self._graph.replay()
+            else:
+                self._tick(torch.cuda.current_stream(dev))
+        return self._out, self._fresh.view(torch.bool)
+
+    def reset(self, slots=None):
+        """The given slots (indices; None = all) start a new track: zero frames, held pose 0.  Stream-ordered like ``push``."""
+        torch = self._torch
+        m = self.model
+        mask = None
+        with torch.cuda.device(m.device):
+            if slots is not None:
+                h = np.zeros(self.slots, np.uint8)
+                h[np.asarray(slots, np.int64).reshape(-1)] = 1
+                mask = torch.from_numpy(h).pin_memory().to(m.device, non_blocking=True)
+            st = C.c_void_p(torch.cuda.current_stream(m.device).cuda_stream)
+            _capi.check(self._lib, self._lib.uu3d_stream_reset(m._h, C.byref(self._cfg), _ptr(self._state), _ptr(mask), st), m._h)
+
+    @property
+    def frames(self):
+        """Frames pushed per slot since its last reset: the device counters themselves, (slots,) int32."""
+        return self._frames
+
+    def check_range(self):
+        """Range guard of precision f16x3 for everything pushed so far, as ``ForwardPipeline.check_range()``: waits for the current stream,
+        then raises ``Uu3dRangeError`` if a tick produced non-finite values."""
+        self._torch.cuda.current_stream(self.model.device).synchronize()
+        return self.model.check_range()
+
+    def close(self):
+        """Wait for what is in flight and give the session's workspace back."""
+        if getattr(self, "_state", None) is not None:
+            self._torch.cuda.synchronize(self.model.device)
+            self._graph = None
+            self.model._ws.pop(self._key, None)
+            self._state = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def replay_tracks(model, config, tracks, resolutions=None, mask_stride=None, flip=None, lookahead=0, root_relative=True, graph=True):
+    """Push complete tracks tick by tick, one slot per track (a slot is inactive once its track has ended) -> per track the pose the
+    session returned at each of its ticks, (T_i, J, 3) float32, and the fresh flags (T_i,) bool, as host arrays.  One copy to the host,
+    at the end."""
+    import torch
+    lens = [int(len(t)) for t in tracks]
+    T, ticks = len(tracks), max(lens)
+    s = StreamSession(model, config, T, resolutions=resolutions, mask_stride=mask_stride, flip=flip, lookahead=lookahead,
+                      root_relative=root_relative, graph=graph)
+    J = int(np.asarray(tracks[0]).shape[1])
+    poses = torch.zeros((ticks, T, J, 3), dtype=torch.float32, device=model.device)
+    fresh = torch.zeros((ticks, T), dtype=torch.bool, device=model.device)
+    kp = np.zeros((T, J, 2), np.float32)
+    try:
+        for k in range(ticks):
+            act = np.array([k < n for n in lens])
+            for i, t in enumerate(tracks):
+                if act[i]:
+                    kp[i] = t[k]
+            p, f = s.push(kp, None if act.all() else act)
+            poses[k].copy_(p)
+            fresh[k].copy_(f)
+        s.check_range()
+    finally:
+        s.close()
+    poses, fresh = poses.cpu().numpy(), fresh.cpu().numpy()
+    return [poses[:n, i] for i, n in enumerate(lens)], [fresh[:n, i] for i, n in enumerate(lens)]
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(prog="python -m uplift_upsample_3dhpe_amd.stream", description="Replay the 2D keypoint tracks of an .npz file (one "
+                                "(T, J, 2) array per track) tick by tick through a StreamSession -> an .npz with, per track NAME, the pose returned at "
+                                "every tick (NAME: (T, J, 3) float32; the pose of frame tick - lookahead where NAME_fresh is set, else the held one).")
+    p.add_argument("--config", required=True, help="model config (.json)")
+    p.add_argument("--weights", required=True, help="weights (.h5)")
+    p.add_argument("--input", required=True, help=".npz with one (T, J, 2) array per track")
+    p.add_argument("--output", required=True, help=".npz to write")
+    p.add_argument("--lookahead", type=int, default=0, help="frames the answer may lag behind the newest one (default 0)")
+    p.add_argument("--resolution", type=float, nargs=2, metavar=("W", "H"), default=None,
+                   help="image size in pixels of all tracks; without it the coordinates are taken as normalised already")
+    return p.parse_args(argv)
+
+
+def _load_model(config, weights_path):
+    from .predict import _load_model as load
+    return load(config, weights_path)
+
+
+def main(argv=None):
+    from .net.uplift_upsample_transformer_config import UpliftUpsampleConfig
+    args = parse_args(argv)
+    config = UpliftUpsampleConfig(args.config)
+    with np.load(args.input) as z:
+        names = list(z.files)
+        tracks = [np.asarray(z[k], np.float32) for k in names]
+    if not names:
+        raise SystemExit(f"{args.input} holds no arrays")
+    for k, t in zip(names, tracks):
+        if t.ndim != 3 or t.shape[2] != 2 or t.shape[1] != config.NUM_KEYPOINTS or t.shape[0] < 1:
+            raise SystemExit(f"{args.input}[{k}] has shape {t.shape}, expected (T >= 1, {config.NUM_KEYPOINTS}, 2)")
+    if not 0 <= args.lookahead <= max_lookahead(config):
+        raise SystemExit(f"--lookahead must be in [0, {max_lookahead(config)}]")
+    model = _load_model(config, args.weights)
+    poses, fresh = replay_tracks(model, config, tracks, resolutions=None if args.resolution is None else tuple(args.resolution),
+                                 lookahead=args.lookahead)
+    out = {}
+    for k, p, f in zip(names, poses, fresh):
+        out[k] = np.asarray(p, np.float32)
+        out[k + "_fresh"] = np.asarray(f, bool)
+    np.savez(args.output, **out)
+    print(f"wrote {args.output}: {len(names)} tracks, {sum(len(p) for p in poses)} ticks, {int(sum(f.sum() for f in fresh))} fresh poses", flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())
