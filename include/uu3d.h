@@ -398,6 +398,59 @@ int uu3d_stream_emit(uu3d_model* model, const uu3d_stream_config* cfg, void* sta
 int uu3d_stream_reset(uu3d_model* model, const uu3d_stream_config* cfg, void* state_dev, const uint8_t* slot_mask_dev, void* stream);
 
 /*
+ * MISSED DETECTIONS (predict.predict_tracks(valid=...), stream.StreamSession(missed_detections=True)): a frame of a track is VALID or
+ * MISSING (the detector found nobody: occlusion, blur, the person left the image).  A missing frame is never an observation: its token
+ * is the learned strided-input token, hidden as a key in the first temporal block(s), exactly like a frame the stride mask drops.
+ * THE RULE, stated once on the device (window_token_real next to window_frame, csrc/uu3d_misc.h) and shared by every kernel below: token n
+ * of a window reads source frame src (its own frame, or under copy padding the nearest sampled in-range frame); with a validity table
+ * (one byte per frame, 0 = missing) its stride-mask bit becomes
+ *     sm' = sm && (!have || valid[video_start + src])
+ * Zero padding (!have: no frame is read) is untouched; a copy-padded token whose source frame is missing is masked; a flipped window uses
+ * the entry of its plain twin.  Everything downstream follows from the bit as before (zero_masked, rows = -1, the key mask).  Missing
+ * frames are written to the pose table as ZEROS, so their features are finite and nothing non-finite can reach the network or the range
+ * word.  Needs a model with strided input (the masked token); the stream calls return UU3D_ERR_UNSUPPORTED otherwise.
+ * Every function above is its _valid form with the validity pointers NULL: one kernel source, a NULL check.  No atomics, one writer per
+ * output element.
+ *
+ *   uu3d_normalize_tracks_valid = uu3d_normalize_tracks + valid_in_dev (src_rows) u8 or NULL, valid_out_dev (rows) u8.  A source frame is
+ *       valid iff valid_in (when given) is non-zero AND all 2 J of its coordinates are finite; valid_out[row] holds that flag and the
+ *       table row of a missing frame is all zeros.  key_stride > 0: rows that are not given keep valid_out = 1 and zeros (they behave as
+ *       before; the copy-padding exception of keyframes_only is unchanged).  Two launches on the stream: the flags (one wave per frame,
+ *       reading src only), then uu3d_normalize_tracks' own kernel reading them -- so the in-place form (src == table) stays legal.
+ *   uu3d_gather_windows_valid / uu3d_gather_window_frames_valid = the two gathers + frame_valid_dev (F) u8 indexed like the pose table
+ *       (video_start[video] + frame; with shifted video starts pass the pointer shifted back), NULL = the old function.  pad_mask is
+ *       unchanged: it says whether a frame exists, not whether it is valid.
+ *   uu3d_stream_stage_valid = uu3d_stream_stage + valid_in_dev (slots) u8 or NULL, valid_out_dev (slots) u8:
+ *       valid_out[slot] = active && valid_in && all coordinates finite; a missing slot's staged frames, both halves, are zeros.
+ *   uu3d_stream_commit_valid = uu3d_stream_commit + valid_dev (slots) u8 (the stage's valid_out) and valid_state_dev: a caller-allocated
+ *       block of uu3d_stream_valid_bytes(model, cfg) bytes = (slots, ring_capacity + 1) u8, one byte per ring place and one for the edge
+ *       row, the same for both halves, filed where the features are filed.  All zeros is a legal initial state (a window never reads a
+ *       place its counter has not reached), so uu3d_stream_reset needs no change.  A missing frame still advances the slot's counter --
+ *       time passes; that is the difference from active = 0.  The window of the tick applies the rule with the byte of the ring place or
+ *       edge row it points to; fresh is unchanged.  A tick stays a linear chain of five launches with unchanging arguments.
+ */
+int uu3d_normalize_tracks_valid(const float* src_dev, int64_t src_rows, float* table_dev, int64_t rows, int32_t num_keypoints,
+                                const int32_t* row_track_dev, int32_t num_tracks, const double* resolution_dev,
+                                const int64_t* track_start_dev, const int64_t* src_start_dev, int32_t key_stride,
+                                const uint8_t* valid_in_dev, uint8_t* valid_out_dev, void* stream);
+int uu3d_gather_windows_valid(const float* poses_dev, const int64_t* video_start_dev, const int32_t* video_len_dev,
+                              const uu3d_window* windows_dev, const int32_t* flip_order_dev,
+                              int32_t batch, int32_t num_frames, int32_t num_keypoints, int32_t channels,
+                              int32_t pad_edge, int32_t zero_masked, const uint8_t* frame_valid_dev,
+                              float* out_dev, uint8_t* stride_mask_dev, uint8_t* pad_mask_dev, void* stream);
+int uu3d_gather_window_frames_valid(const int64_t* video_start_dev, const int32_t* video_len_dev, const uu3d_window* windows_dev,
+                                    int32_t batch, int32_t num_frames, int32_t pad_edge, int32_t zero_masked, int64_t frame_base,
+                                    int64_t zero_row, const uint8_t* frame_valid_dev, int32_t* rows_dev, uint8_t* stride_mask_dev,
+                                    uint8_t* pad_mask_dev, void* stream);
+size_t uu3d_stream_valid_bytes(const uu3d_model* model, const uu3d_stream_config* cfg);
+int uu3d_stream_stage_valid(uu3d_model* model, const uu3d_stream_config* cfg, const float* kp_dev, const double* resolution_dev,
+                            const uint8_t* active_dev, const int32_t* flip_order_dev, const uint8_t* valid_in_dev,
+                            uint8_t* valid_out_dev, float* frames_out_dev, void* stream);
+int uu3d_stream_commit_valid(uu3d_model* model, const uu3d_stream_config* cfg, void* state_dev, const float* features_dev,
+                             const uint8_t* active_dev, const uint8_t* valid_dev, void* valid_state_dev, int32_t* rows_dev,
+                             uint8_t* stride_mask_dev, uint8_t* fresh_dev, void* stream);
+
+/*
  * Per-kernel timing of the next uu3d_forward calls with HIP events on the launch stream.
  * When enabled, uu3d_forward records an event pair around every launch; uu3d_profile_read
  * synchronises those events and returns the per-launch records of the LAST forward.

@@ -3,7 +3,8 @@ pieces that existed before it: host normalisation (h36m.normalize_screen_coordin
 eval.predict_windows, then .cpu() + evaluation.interpolate_between_keyframes in numpy.  Both start from host arrays of pixel coordinates;
 predict_tracks ends with the dense poses on the device (also reported: with their copy to the host), the composition with them on the host.
 Median of --reps calls after one warm-up call each; frames/s = all frames of all tracks / seconds.
-   python tools/predict_tracks_bench.py [--tracks 40] [--frames 2500] [--batch 512] [--reps 3] [--cases h36m_351:5,h36m_81:4]"""
+--missing P: also predict_tracks(valid=flags) with a seeded fraction P of the frames missing (missed detections), same tracks.
+   python tools/predict_tracks_bench.py [--tracks 40] [--frames 2500] [--batch 512] [--reps 3] [--cases h36m_351:5,h36m_81:4] [--missing 0.3]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -16,6 +17,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--cases", default="h36m_351:5,h36m_81:4")
     ap.add_argument("--no_reuse", action="store_true", help="the window forward instead of the frames form, in both paths")
+    ap.add_argument("--missing", type=float, default=0.0, help="also time predict_tracks(valid=...) with this fraction of the frames missing")
     args = ap.parse_args()
     import numpy as np, torch
     import uplift_upsample_3dhpe_amd as pkg
@@ -29,6 +31,7 @@ def main():
     px = [(np.cumsum(rng.normal(0, 2.0, size=(args.frames, 17, 2)), 0) + rng.uniform(0.25, 0.75, size=(1, 17, 2)) * [W, H]).astype(np.float32)
           for _ in range(args.tracks)]
     total = args.tracks * args.frames
+    flags = [rng.random(args.frames) >= args.missing for _ in range(args.tracks)] if args.missing > 0 else None
     reuse = not args.no_reuse
     results = []
     for case in args.cases.split(","):
@@ -41,6 +44,10 @@ def main():
         def new_path(to_host=False):
             out = predict.predict_tracks(model, cfg, px, resolutions=(W, H), mask_stride=int(msv), flip=True, reuse_frames=reuse, batch_size=args.batch)
             return [o.cpu() for o in out] if to_host else out
+
+        def missing_path():
+            return predict.predict_tracks(model, cfg, px, resolutions=(W, H), mask_stride=int(msv), flip=True, reuse_frames=reuse, batch_size=args.batch,
+                                          valid=flags)
 
         def composition():
             p2 = [h36m.normalize_screen_coordinates(t, w=W, h=H).astype(np.float32) for t in px]
@@ -58,7 +65,11 @@ def main():
 
         row = dict(config=name, mask_stride=int(msv), tracks=args.tracks, frames=total, batch=args.batch, reuse_frames=reuse)
         outs = {}
-        for key, fn in (("predict_tracks", new_path), ("predict_tracks_to_host", lambda: new_path(True)), ("composition", composition)):
+        cases = [("predict_tracks", new_path), ("predict_tracks_to_host", lambda: new_path(True)), ("composition", composition)]
+        if flags is not None:
+            row["missing"] = args.missing
+            cases.append(("predict_tracks_valid", missing_path))
+        for key, fn in cases:
             fn()
             torch.cuda.synchronize()
             ts = []

@@ -33,6 +33,8 @@ EXPORTED_SYMBOLS = (
     "uu3d_pose_errors", "uu3d_error_sums", "uu3d_error_sums_scratch_bytes",
     "uu3d_normalize_tracks", "uu3d_assemble_tracks",
     "uu3d_stream_state_bytes", "uu3d_stream_state_layout", "uu3d_stream_stage", "uu3d_stream_commit", "uu3d_stream_emit", "uu3d_stream_reset",
+    "uu3d_normalize_tracks_valid", "uu3d_gather_windows_valid", "uu3d_gather_window_frames_valid", "uu3d_stream_valid_bytes",
+    "uu3d_stream_stage_valid", "uu3d_stream_commit_valid",
 )
 # include/uu3d_ops.h
 OPS_SYMBOLS = (
@@ -171,6 +173,19 @@ def load_library(path=None):
     lib.uu3d_stream_emit.argtypes = [vp, scfg, vp, vp, vp, vp, vp, vp]
     lib.uu3d_stream_reset.restype = C.c_int
     lib.uu3d_stream_reset.argtypes = [vp, scfg, vp, vp, vp]
+    # missed detections: the same calls with the validity pointers
+    lib.uu3d_normalize_tracks_valid.restype = C.c_int
+    lib.uu3d_normalize_tracks_valid.argtypes = [vp, i64, vp, i64, i32, vp, i32, vp, vp, vp, i32, vp, vp, vp]
+    lib.uu3d_gather_windows_valid.restype = C.c_int
+    lib.uu3d_gather_windows_valid.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]
+    lib.uu3d_gather_window_frames_valid.restype = C.c_int
+    lib.uu3d_gather_window_frames_valid.argtypes = [vp, vp, vp, i32, i32, i32, i32, i64, i64, vp, vp, vp, vp, vp]
+    lib.uu3d_stream_valid_bytes.restype = sz
+    lib.uu3d_stream_valid_bytes.argtypes = [vp, scfg]
+    lib.uu3d_stream_stage_valid.restype = C.c_int
+    lib.uu3d_stream_stage_valid.argtypes = [vp, scfg, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.uu3d_stream_commit_valid.restype = C.c_int
+    lib.uu3d_stream_commit_valid.argtypes = [vp, scfg, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.uu3d_world_to_cam_2d.restype = C.c_int
     lib.uu3d_world_to_cam_2d.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
     lib.uu3d_set_schedule.restype = C.c_int

@@ -464,41 +464,77 @@ int uu3d_error_sums(const double* errors, int64_t P, int32_t J, const int32_t* a
     return hipGetLastError() == hipSuccess ? UU3D_OK : UU3D_ERR_HIP;
 }
 
-int uu3d_gather_windows(const float* poses, const int64_t* video_start, const int32_t* video_len, const uu3d_window* windows,
-                        const int32_t* flip_order, int32_t B, int32_t N, int32_t J, int32_t Cc, int32_t pad_edge,
-                        int32_t zero_masked, float* out, uint8_t* stride_mask, uint8_t* pad_mask, void* stream) {
+int uu3d_gather_windows_valid(const float* poses, const int64_t* video_start, const int32_t* video_len, const uu3d_window* windows,
+                              const int32_t* flip_order, int32_t B, int32_t N, int32_t J, int32_t Cc, int32_t pad_edge,
+                              int32_t zero_masked, const uint8_t* frame_valid, float* out, uint8_t* stride_mask, uint8_t* pad_mask, void* stream) {
     if (!poses || !video_start || !video_len || !windows || !out || !stride_mask || B < 1 || N < 1 || J < 1 || Cc < 1 || Cc > 4)
         return UU3D_ERR_INVALID_ARGUMENT;
     static_assert(sizeof(uu3d_window) == sizeof(WindowDesc), "descriptor layouts must agree");
     const long total = (long)B * N * J;
     hipLaunchKernelGGL(gather_windows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        poses, video_start, video_len, reinterpret_cast<const WindowDesc*>(windows), flip_order,
-                       B, N, J, Cc, pad_edge, zero_masked, out, stride_mask, pad_mask);
+                       B, N, J, Cc, pad_edge, zero_masked, frame_valid, out, stride_mask, pad_mask);
+    return hipGetLastError() == hipSuccess ? UU3D_OK : UU3D_ERR_HIP;
+}
+
+int uu3d_gather_windows(const float* poses, const int64_t* video_start, const int32_t* video_len, const uu3d_window* windows,
+                        const int32_t* flip_order, int32_t B, int32_t N, int32_t J, int32_t Cc, int32_t pad_edge,
+                        int32_t zero_masked, float* out, uint8_t* stride_mask, uint8_t* pad_mask, void* stream) {
+    return uu3d_gather_windows_valid(poses, video_start, video_len, windows, flip_order, B, N, J, Cc, pad_edge, zero_masked, nullptr, out,
+                                     stride_mask, pad_mask, stream);
+}
+
+int uu3d_gather_window_frames_valid(const int64_t* video_start, const int32_t* video_len, const uu3d_window* windows, int32_t B, int32_t N,
+                                    int32_t pad_edge, int32_t zero_masked, int64_t frame_base, int64_t zero_row, const uint8_t* frame_valid,
+                                    int32_t* rows, uint8_t* stride_mask, uint8_t* pad_mask, void* stream) {
+    if (!video_start || !video_len || !windows || !rows || !stride_mask || B < 1 || N < 1 || frame_base < 0 || zero_row < 0 || zero_row > INT32_MAX)
+        return UU3D_ERR_INVALID_ARGUMENT;
+    const long total = (long)B * N;
+    hipLaunchKernelGGL(gather_window_frames_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       video_start, video_len, reinterpret_cast<const WindowDesc*>(windows), B, N, pad_edge, zero_masked,
+                       frame_base, zero_row, frame_valid, rows, stride_mask, pad_mask);
     return hipGetLastError() == hipSuccess ? UU3D_OK : UU3D_ERR_HIP;
 }
 
 int uu3d_gather_window_frames(const int64_t* video_start, const int32_t* video_len, const uu3d_window* windows, int32_t B, int32_t N,
                               int32_t pad_edge, int32_t zero_masked, int64_t frame_base, int64_t zero_row, int32_t* rows,
                               uint8_t* stride_mask, uint8_t* pad_mask, void* stream) {
-    if (!video_start || !video_len || !windows || !rows || !stride_mask || B < 1 || N < 1 || frame_base < 0 || zero_row < 0 || zero_row > INT32_MAX)
-        return UU3D_ERR_INVALID_ARGUMENT;
-    const long total = (long)B * N;
-    hipLaunchKernelGGL(gather_window_frames_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       video_start, video_len, reinterpret_cast<const WindowDesc*>(windows), B, N, pad_edge, zero_masked,
-                       frame_base, zero_row, rows, stride_mask, pad_mask);
-    return hipGetLastError() == hipSuccess ? UU3D_OK : UU3D_ERR_HIP;
+    return uu3d_gather_window_frames_valid(video_start, video_len, windows, B, N, pad_edge, zero_masked, frame_base, zero_row, nullptr, rows,
+                                           stride_mask, pad_mask, stream);
 }
 
-int uu3d_normalize_tracks(const float* src, int64_t src_rows, float* table, int64_t rows, int32_t J, const int32_t* row_track, int32_t num_tracks,
-                          const double* resolution, const int64_t* track_start, const int64_t* src_start, int32_t key_stride, void* stream) {
+namespace {
+// uu3d_normalize_tracks (valid_out == nullptr: one launch) and uu3d_normalize_tracks_valid (the validity launch in front of it)
+int normalize_tracks(const float* src, int64_t src_rows, float* table, int64_t rows, int32_t J, const int32_t* row_track, int32_t num_tracks,
+                     const double* resolution, const int64_t* track_start, const int64_t* src_start, int32_t key_stride, const uint8_t* valid_in,
+                     uint8_t* valid_out, void* stream) {
     if (!src || !table || !row_track || src_rows < 1 || rows < 1 || J < 1 || num_tracks < 1 || key_stride < 0) return UU3D_ERR_INVALID_ARGUMENT;
     if (key_stride > 0 && (!track_start || !src_start || src == table)) return UU3D_ERR_INVALID_ARGUMENT;
     if (key_stride == 0 && src_rows != rows) return UU3D_ERR_INVALID_ARGUMENT;
     if (((uintptr_t)table & 15) != 0 || ((uintptr_t)src & 7) != 0) return UU3D_ERR_INVALID_ARGUMENT;
+    if (valid_out != nullptr) {
+        hipLaunchKernelGGL(track_valid_kernel, dim3((unsigned)(((long)rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                           src, (long)src_rows, (long)rows, J, row_track, num_tracks, track_start, src_start, key_stride, valid_in, valid_out);
+        if (hipGetLastError() != hipSuccess) return UU3D_ERR_HIP;
+    }
     const long threads = ((long)rows * J + 1) / 2;
     hipLaunchKernelGGL(normalize_tracks_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       src, (long)src_rows, table, (long)rows, J, row_track, num_tracks, resolution, track_start, src_start, key_stride);
+                       src, (long)src_rows, table, (long)rows, J, row_track, num_tracks, resolution, track_start, src_start, key_stride,
+                       (const uint8_t*)valid_out);
     return hipGetLastError() == hipSuccess ? UU3D_OK : UU3D_ERR_HIP;
+}
+}  // namespace
+
+int uu3d_normalize_tracks(const float* src, int64_t src_rows, float* table, int64_t rows, int32_t J, const int32_t* row_track, int32_t num_tracks,
+                          const double* resolution, const int64_t* track_start, const int64_t* src_start, int32_t key_stride, void* stream) {
+    return normalize_tracks(src, src_rows, table, rows, J, row_track, num_tracks, resolution, track_start, src_start, key_stride, nullptr, nullptr, stream);
+}
+
+int uu3d_normalize_tracks_valid(const float* src, int64_t src_rows, float* table, int64_t rows, int32_t J, const int32_t* row_track,
+                                int32_t num_tracks, const double* resolution, const int64_t* track_start, const int64_t* src_start,
+                                int32_t key_stride, const uint8_t* valid_in, uint8_t* valid_out, void* stream) {
+    if (!valid_out) return UU3D_ERR_INVALID_ARGUMENT;
+    return normalize_tracks(src, src_rows, table, rows, J, row_track, num_tracks, resolution, track_start, src_start, key_stride, valid_in, valid_out, stream);
 }
 
 int uu3d_assemble_tracks(const float* plain, const float* flipped, int64_t num_windows, const int32_t* flip_order, const int32_t* left,
@@ -555,23 +591,43 @@ size_t uu3d_stream_state_bytes(const uu3d_model* m, const uu3d_stream_config* s)
     return uu3d_stream_state_layout(m, s, &l) == UU3D_OK ? (size_t)l.bytes : 0;
 }
 
-int uu3d_stream_stage(uu3d_model* m, const uu3d_stream_config* s, const float* kp, const double* resolution, const uint8_t* active,
-                      const int32_t* flip_order, float* frames_out, void* stream) {
-    if (!m) return UU3D_ERR_INVALID_ARGUMENT;
-    if (const int st = stream_check(m, s, "uu3d_stream_stage")) return st;
+namespace {
+// MISSED DETECTIONS need the masked token: a model without strided input has none
+int stream_valid_check(uu3d_model* m, const char* who) {
+    if (!m->cfg.has_strided_input) return fail(m, UU3D_ERR_UNSUPPORTED, std::string(who) + ": frame validity needs a model with strided input (the masked token)");
+    return UU3D_OK;
+}
+int stream_stage(uu3d_model* m, const uu3d_stream_config* s, const float* kp, const double* resolution, const uint8_t* active,
+                 const int32_t* flip_order, const uint8_t* valid_in, uint8_t* valid_out, float* frames_out, void* stream) {
     if (!kp || !active || !frames_out || (s->flip && !flip_order)) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_stage: null buffer");
     if (((uintptr_t)frames_out & 15) != 0 || ((uintptr_t)kp & 7) != 0) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_stage: frames_out must be 16-byte, kp 8-byte aligned");
     const int halves = s->flip ? 2 : 1;
     const long threads = ((long)halves * s->slots * m->cfg.num_keypoints + 1) / 2;
     hipLaunchKernelGGL(stream_stage_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       kp, resolution, active, flip_order, s->slots, m->cfg.num_keypoints, halves, frames_out);
+                       kp, resolution, active, flip_order, s->slots, m->cfg.num_keypoints, halves, valid_in, valid_out, frames_out);
     return hipGetLastError() == hipSuccess ? UU3D_OK : fail(m, UU3D_ERR_HIP, "uu3d_stream_stage: launch failed");
 }
+}  // namespace
 
-int uu3d_stream_commit(uu3d_model* m, const uu3d_stream_config* s, void* state, const float* features, const uint8_t* active,
-                       int32_t* rows, uint8_t* stride_mask, uint8_t* fresh, void* stream) {
+int uu3d_stream_stage(uu3d_model* m, const uu3d_stream_config* s, const float* kp, const double* resolution, const uint8_t* active,
+                      const int32_t* flip_order, float* frames_out, void* stream) {
     if (!m) return UU3D_ERR_INVALID_ARGUMENT;
-    if (const int st = stream_check(m, s, "uu3d_stream_commit")) return st;
+    if (const int st = stream_check(m, s, "uu3d_stream_stage")) return st;
+    return stream_stage(m, s, kp, resolution, active, flip_order, nullptr, nullptr, frames_out, stream);
+}
+
+int uu3d_stream_stage_valid(uu3d_model* m, const uu3d_stream_config* s, const float* kp, const double* resolution, const uint8_t* active,
+                            const int32_t* flip_order, const uint8_t* valid_in, uint8_t* valid_out, float* frames_out, void* stream) {
+    if (!m) return UU3D_ERR_INVALID_ARGUMENT;
+    if (const int st = stream_check(m, s, "uu3d_stream_stage_valid")) return st;
+    if (const int st = stream_valid_check(m, "uu3d_stream_stage_valid")) return st;
+    if (!valid_out) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_stage_valid: null valid_out");
+    return stream_stage(m, s, kp, resolution, active, flip_order, valid_in, valid_out, frames_out, stream);
+}
+
+namespace {
+int stream_commit(uu3d_model* m, const uu3d_stream_config* s, void* state, const float* features, const uint8_t* active, const uint8_t* valid,
+                  uint8_t* valid_state, int32_t* rows, uint8_t* stride_mask, uint8_t* fresh, void* stream) {
     if (!state || !features || !active || !rows || !stride_mask || !fresh) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_commit: null buffer");
     if (((uintptr_t)state & 255) != 0 || ((uintptr_t)features & 15) != 0) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_commit: state must be 256-byte, features 16-byte aligned");
     const StreamLayout L = stream_layout_of(m, s);
@@ -582,8 +638,31 @@ int uu3d_stream_commit(uu3d_model* m, const uu3d_stream_config* s, void* state, 
     p.masked_row = m->cfg.has_strided_input ? -1 : (int)L.zero_row;      // (no strided input: a dropped frame is read as zeros, eval.py:67)
     char* base = (char*)state;
     hipLaunchKernelGGL(stream_commit_kernel, dim3(s->slots), dim3(256), 0, (hipStream_t)stream, p, features, active,
-                       (int32_t*)(base + L.off_frames), (float*)(base + L.off_table), rows, stride_mask, fresh);
+                       (int32_t*)(base + L.off_frames), (float*)(base + L.off_table), rows, stride_mask, fresh, valid, valid_state);
     return hipGetLastError() == hipSuccess ? UU3D_OK : fail(m, UU3D_ERR_HIP, "uu3d_stream_commit: launch failed");
+}
+}  // namespace
+
+int uu3d_stream_commit(uu3d_model* m, const uu3d_stream_config* s, void* state, const float* features, const uint8_t* active,
+                       int32_t* rows, uint8_t* stride_mask, uint8_t* fresh, void* stream) {
+    if (!m) return UU3D_ERR_INVALID_ARGUMENT;
+    if (const int st = stream_check(m, s, "uu3d_stream_commit")) return st;
+    return stream_commit(m, s, state, features, active, nullptr, nullptr, rows, stride_mask, fresh, stream);
+}
+
+size_t uu3d_stream_valid_bytes(const uu3d_model* mc, const uu3d_stream_config* s) {
+    auto* m = const_cast<uu3d_model*>(mc);
+    if (!m || stream_check(m, s, "uu3d_stream_valid_bytes") != UU3D_OK) return 0;
+    return (size_t)s->slots * (size_t)(stream_layout_of(m, s).cap + 1);
+}
+
+int uu3d_stream_commit_valid(uu3d_model* m, const uu3d_stream_config* s, void* state, const float* features, const uint8_t* active,
+                             const uint8_t* valid, void* valid_state, int32_t* rows, uint8_t* stride_mask, uint8_t* fresh, void* stream) {
+    if (!m) return UU3D_ERR_INVALID_ARGUMENT;
+    if (const int st = stream_check(m, s, "uu3d_stream_commit_valid")) return st;
+    if (const int st = stream_valid_check(m, "uu3d_stream_commit_valid")) return st;
+    if (!valid || !valid_state) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_commit_valid: null validity buffer");
+    return stream_commit(m, s, state, features, active, valid, (uint8_t*)valid_state, rows, stride_mask, fresh, stream);
 }
 
 int uu3d_stream_emit(uu3d_model* m, const uu3d_stream_config* s, void* state, const float* central, const int32_t* flip_order,

@@ -206,6 +206,7 @@ compact_frames_kernel(const uint8_t* __restrict__ mask, const int total, int* __
 // % mask_stride == 0 with the caller's shift (the centre frame index for globally aligned masks, :381-384; a random
 // multiple of the stride in training, :386-392).  zero_masked also applies x * stride_mask (eval.py:67, train.py:474).
 // flip: joints permuted by flip_order, channel 0 negated (:403-407).  One thread per (window, frame, joint).
+// frame_valid (F) u8 or nullptr: one byte per row of the pose table, 0 = a missing frame -- window_token_real below.
 struct WindowDesc { int32_t video, center, stride, mask_stride, mask_shift, flip; };
 // Token n of window d: which frame of its video it reads and how it is masked -- the one statement of these rules, shared by
 // gather_windows_kernel (coordinates) and gather_window_frames_kernel (feature-table rows) so that the two cannot drift.
@@ -226,11 +227,22 @@ __device__ __forceinline__ WindowFrame window_frame(const WindowDesc& d, const i
     t.sm = (mod == 0);
     return t;
 }
+// MISSED DETECTIONS (include/uu3d.h): the one statement of the validity rule, shared by the two gather kernels and stream_commit_kernel.
+// `valid` holds one byte per frame (0 = missing), `index` is the entry of the frame the token reads (t.src): the token stays real input iff
+//     sm' = sm && (!have || valid[index])
+// -- zero padding (!have) is untouched, a copy-padded token whose source frame is missing is masked.  valid == nullptr: no table, sm' = sm.
+// The byte is loaded only for a token that reads a frame, so `index` needs to be in range only then.
+__device__ __forceinline__ bool window_token_real(const WindowFrame& t, const uint8_t* valid, const long index)
+{
+    if (!t.sm) return false;
+    if (valid == nullptr || !t.have) return true;
+    return valid[index] != 0;
+}
 static __global__ void __launch_bounds__(256)
 gather_windows_kernel(const float* __restrict__ poses, const int64_t* __restrict__ video_start, const int32_t* __restrict__ video_len,
                       const WindowDesc* __restrict__ win, const int32_t* __restrict__ flip_order,
                       const int B, const int N, const int J, const int C, const int pad_edge, const int zero_masked,
-                      float* __restrict__ out, uint8_t* __restrict__ stride_mask, uint8_t* __restrict__ pad_mask)
+                      const uint8_t* __restrict__ frame_valid, float* __restrict__ out, uint8_t* __restrict__ stride_mask, uint8_t* __restrict__ pad_mask)
 {
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (long)B * N * J) return;
@@ -239,7 +251,7 @@ gather_windows_kernel(const float* __restrict__ poses, const int64_t* __restrict
     const int w = (int)(idx / ((long)J * N));
     const WindowDesc d = win[w];
     const WindowFrame t = window_frame(d, video_len[d.video], N, n, pad_edge);
-    const bool sm = t.sm;
+    const bool sm = window_token_real(t, frame_valid, video_start[d.video] + t.src);
     if (j == 0) {
         stride_mask[(long)w * N + n] = sm ? 1 : 0;
         if (pad_mask != nullptr) pad_mask[(long)w * N + n] = t.inside ? 1 : 0;
@@ -261,7 +273,7 @@ gather_windows_kernel(const float* __restrict__ poses, const int64_t* __restrict
 static __global__ void __launch_bounds__(256)
 gather_window_frames_kernel(const int64_t* __restrict__ video_start, const int32_t* __restrict__ video_len, const WindowDesc* __restrict__ win,
                             const int B, const int N, const int pad_edge, const int zero_masked, const int64_t frame_base, const int64_t zero_row,
-                            int32_t* __restrict__ rows, uint8_t* __restrict__ stride_mask, uint8_t* __restrict__ pad_mask)
+                            const uint8_t* __restrict__ frame_valid, int32_t* __restrict__ rows, uint8_t* __restrict__ stride_mask, uint8_t* __restrict__ pad_mask)
 {
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (long)B * N) return;
@@ -269,10 +281,11 @@ gather_window_frames_kernel(const int64_t* __restrict__ video_start, const int32
     const int w = (int)(idx / N);
     const WindowDesc d = win[w];
     const WindowFrame t = window_frame(d, video_len[d.video], N, n, pad_edge);
-    stride_mask[idx] = t.sm ? 1 : 0;
+    const bool sm = window_token_real(t, frame_valid, video_start[d.video] + t.src);
+    stride_mask[idx] = sm ? 1 : 0;
     if (pad_mask != nullptr) pad_mask[idx] = t.inside ? 1 : 0;
     int64_t r;
-    if (zero_masked && !t.sm) r = -1;
+    if (zero_masked && !sm) r = -1;
     else if (!t.have) r = zero_row;
     else r = video_start[d.video] + t.src + (d.flip ? frame_base : 0);
     rows[idx] = (int32_t)r;

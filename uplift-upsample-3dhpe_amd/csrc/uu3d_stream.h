@@ -59,9 +59,13 @@ __device__ __forceinline__ int stream_edge_row(const StreamParams& p, const int 
 // kp (T, J, 2) pixel (or already normalised: res == nullptr) coordinates of this tick -> out (halves * T, J, 2): the normalised frames and,
 // behind them, their mirrored copies (joints permuted by `order`, x negated -- gather_windows_kernel's flip).  An inactive slot's frames
 // are zeros.  One thread per two (x, y) pairs = one 16-byte store.
+// MISSED DETECTIONS (valid_out != nullptr): valid_out[slot] = active && valid_in[slot] (nullptr: 1) && all 2 J coordinates of the slot's row
+// are finite; a slot whose frame is missing stages zeros in both halves, like an inactive one.  Every thread re-reads its slot's row of kp
+// (which nobody writes); the thread of joint 0 of the plain half writes the slot's byte.
 static __global__ void __launch_bounds__(256)
 stream_stage_kernel(const float* __restrict__ kp, const double* __restrict__ res, const uint8_t* __restrict__ active,
-                    const int32_t* __restrict__ order, const int T, const int J, const int halves, float* __restrict__ out)
+                    const int32_t* __restrict__ order, const int T, const int J, const int halves, const uint8_t* __restrict__ valid_in,
+                    uint8_t* __restrict__ valid_out, float* __restrict__ out)
 {
     const long pairs = (long)halves * T * J;
     const long p0 = ((long)blockIdx.x * 256 + threadIdx.x) * 2;
@@ -73,7 +77,13 @@ stream_stage_kernel(const float* __restrict__ kp, const double* __restrict__ res
         const int row = (int)(p / J), j = (int)(p - (long)row * J);
         const int half = row / T, t = row - half * T;
         v[e] = make_float2(0.f, 0.f);
-        if (active[t] == 0) continue;
+        bool real = active[t] != 0;
+        if (valid_out != nullptr) {
+            real = real && (valid_in == nullptr || valid_in[t] != 0);
+            for (int k = 0; k < J && real; ++k) real = finite_pair(*reinterpret_cast<const float2*>(kp + ((long)t * J + k) * 2));
+            if (p == p0 + e && half == 0 && j == 0) valid_out[t] = real ? 1 : 0;
+        }
+        if (!real) continue;
         int js = j;
         if (half != 0) { js = order[j]; if (js < 0 || js >= J) { v[e] = make_float2(__builtin_nanf(""), __builtin_nanf("")); continue; } }
         const float2 x = *reinterpret_cast<const float2*>(kp + ((long)t * J + js) * 2);
@@ -89,9 +99,14 @@ stream_stage_kernel(const float* __restrict__ kp, const double* __restrict__ res
 // thread of ITS workgroup only, and written by one of them behind a barrier.  Rows written: rows (halves * T, N), stride_mask likewise,
 // fresh (T).  The window is the one uu3d_gather_window_frames writes for a video of `frames` frames centred on frames - 1 - lookahead with
 // a globally aligned mask; only where its frames live differs (ring place / edge row instead of video_start + frame).
+// MISSED DETECTIONS (valid_state != nullptr): valid (T) u8 says whether this tick's frame of a slot is a real observation (stream_stage_kernel's
+// valid_out); valid_state (T, cap + 1) u8 keeps that byte per ring place and for the edge row, filed where the features are filed, the same
+// for both halves.  A missing frame advances the counter like any other (time passes) and the window applies window_token_real with the
+// byte of the place it points to.
 static __global__ void __launch_bounds__(256)
 stream_commit_kernel(const StreamParams p, const float* __restrict__ feats, const uint8_t* __restrict__ active, int32_t* __restrict__ frames,
-                     float* __restrict__ table, int32_t* __restrict__ rows, uint8_t* __restrict__ stride_mask, uint8_t* __restrict__ fresh)
+                     float* __restrict__ table, int32_t* __restrict__ rows, uint8_t* __restrict__ stride_mask, uint8_t* __restrict__ fresh,
+                     const uint8_t* __restrict__ valid, uint8_t* valid_state)
 {
     const int slot = blockIdx.x, tid = threadIdx.x;
     const int before = frames[slot];
@@ -108,7 +123,13 @@ stream_commit_kernel(const StreamParams p, const float* __restrict__ feats, cons
             if (edge) *reinterpret_cast<float4*>(table + (size_t)stream_edge_row(p, half, slot) * p.dt + c) = v;
             if (key) *reinterpret_cast<float4*>(table + (size_t)stream_ring_row(p, half, slot, before) * p.dt + c) = v;
         }
+        if (valid_state != nullptr && tid == 0) {                        // (stream_ring_row / stream_edge_row of half 0 and `slot` = the slot's (cap + 1) bytes)
+            const uint8_t b = valid[slot] != 0 ? 1 : 0;
+            if (edge) valid_state[stream_edge_row(p, 0, slot)] = b;
+            if (key) valid_state[stream_ring_row(p, 0, slot, before)] = b;
+        }
     }
+    if (valid_state != nullptr) __syncthreads();                         // (uniform: the bytes filed above are read below by other threads)
     const int centre = len - 1 - p.lookahead;
     const bool is_fresh = act && centre >= 0 && centre % p.pred_stride == 0;
     if (tid == 0) fresh[slot] = is_fresh ? 1 : 0;
@@ -121,11 +142,16 @@ stream_commit_kernel(const StreamParams p, const float* __restrict__ feats, cons
         if (is_fresh) {                                                  // (a slot that is not fresh: an all-masked window, finite and discarded)
             const WindowDesc d{0, centre, p.seq_stride, p.s_in, centre, half};
             const WindowFrame t = window_frame(d, len, p.N, n, p.pad_edge);
-            sm = t.sm ? 1 : 0;
-            if (!t.sm) r = p.masked_row;
+            int place = -1;                                              // where the frame the token reads is kept, in half 0 of the table
+            if (t.sm && t.have) {
+                if (!t.inside && t.src == (len - 1) / p.seq_stride * p.seq_stride) place = stream_edge_row(p, 0, slot);
+                else if (t.src % p.s_in == 0 && t.src >= oldest && t.src >= 0 && t.src < len) place = stream_ring_row(p, 0, slot, t.src);
+            }
+            const bool real = window_token_real(t, place >= 0 ? valid_state : nullptr, place);
+            sm = real ? 1 : 0;
+            if (!real) r = p.masked_row;
             else if (!t.have) r = p.zero_row;
-            else if (!t.inside && t.src == (len - 1) / p.seq_stride * p.seq_stride) r = stream_edge_row(p, half, slot);
-            else if (t.src % p.s_in == 0 && t.src >= oldest && t.src >= 0 && t.src < len) r = stream_ring_row(p, half, slot, t.src);
+            else if (place >= 0) r = place + half * p.slots * (p.cap + 1);
             else r = -1;                                                 // no such frame is kept: NaN in the forward, reported by its range check
         }
         rows[o] = r;

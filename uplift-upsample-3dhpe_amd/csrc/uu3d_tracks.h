@@ -18,15 +18,40 @@ __device__ __forceinline__ float2 normalize_pair(const float2 p, const float wf,
     return make_float2((float)((double)x - 1.0), (float)((double)y - h_over_w));
 }
 
-// table (rows, J, 2): row r belongs to track row_track[r].  key_stride == 0: the table's own rows are normalised (src == table allowed).
-// key_stride > 0: src holds only the frames 0, key_stride, 2 key_stride, ... of every track back to back (track t from row src_start[t]);
-// frame f of track t (table row track_start[t] + f) takes source row src_start[t] + f / key_stride when f % key_stride == 0 and is zero
-// otherwise.  res (T, 2) float64 = (w, h) per track, or nullptr: the coordinates are copied as they are.  A track id or a source row out
-// of range writes NaN instead of reading out of bounds.
+// Neither coordinate is NaN or +-Inf (the exponent bits: no floating-point compare a compiler flag could fold away).
+__device__ __forceinline__ bool finite_pair(const float2 p)
+{
+    return (__float_as_uint(p.x) & 0x7f800000u) != 0x7f800000u && (__float_as_uint(p.y) & 0x7f800000u) != 0x7f800000u;
+}
+
+// Which source row a table row takes.  key_stride == 0: its own.  key_stride > 0: src holds only the frames 0, key_stride, 2 key_stride, ...
+// of every track back to back (track t from row src_start[t]); frame f of track t (table row track_start[t] + f) takes source row
+// src_start[t] + f / key_stride when f % key_stride == 0.  kTrackRowNotGiven: a frame between two keyframes; kTrackRowBad: a track id or a
+// source row out of range.  One statement for normalize_tracks_kernel and track_valid_kernel.
+static constexpr long kTrackRowNotGiven = -1, kTrackRowBad = -2;
+__device__ __forceinline__ long track_source_row(const long row, const long src_rows, const int32_t* __restrict__ row_track, const int num_tracks,
+                                                 const int64_t* __restrict__ track_start, const int64_t* __restrict__ src_start, const int key_stride)
+{
+    const int t = row_track[row];
+    if (t < 0 || t >= num_tracks) return kTrackRowBad;
+    long srow = row;
+    if (key_stride > 0) {
+        const long f = row - track_start[t];
+        if (f < 0) return kTrackRowBad;
+        if (f % key_stride != 0) return kTrackRowNotGiven;
+        srow = src_start[t] + f / key_stride;
+    }
+    return (srow < 0 || srow >= src_rows) ? kTrackRowBad : srow;
+}
+
+// table (rows, J, 2): row r belongs to track row_track[r] and takes the source row track_source_row names: normalised with res (T, 2)
+// float64 = (w, h) per track, or copied as it is (res == nullptr; src == table allowed when key_stride == 0).  A row that is not given is
+// zero; a track id or a source row out of range writes NaN instead of reading out of bounds.  valid (rows) u8 or nullptr: a row whose byte
+// is 0 (a missing frame, track_valid_kernel) is written as zeros whatever its source holds.
 static __global__ void __launch_bounds__(256)
 normalize_tracks_kernel(const float* src, const long src_rows, float* table, const long rows, const int J, const int32_t* __restrict__ row_track,
                         const int num_tracks, const double* __restrict__ res, const int64_t* __restrict__ track_start,
-                        const int64_t* __restrict__ src_start, const int key_stride)
+                        const int64_t* __restrict__ src_start, const int key_stride, const uint8_t* __restrict__ valid)
 {
     const long pairs = rows * J;
     const long p0 = ((long)blockIdx.x * 256 + threadIdx.x) * 2;         // two (x, y) pairs = one 16-byte store
@@ -37,23 +62,42 @@ normalize_tracks_kernel(const float* src, const long src_rows, float* table, con
         const long p = (p0 + e < pairs) ? p0 + e : p0;
         const long row = p / J;
         const int j = (int)(p - row * J);
-        const int t = row_track[row];
         const float nan = __builtin_nanf("");
         v[e] = make_float2(nan, nan);
-        if (t < 0 || t >= num_tracks) continue;
-        long srow = row;
-        if (key_stride > 0) {
-            const long f = row - track_start[t];
-            if (f < 0) continue;
-            if (f % key_stride != 0) { v[e] = make_float2(0.f, 0.f); continue; }
-            srow = src_start[t] + f / key_stride;
-        }
-        if (srow < 0 || srow >= src_rows) continue;
+        const long srow = track_source_row(row, src_rows, row_track, num_tracks, track_start, src_start, key_stride);
+        if (srow == kTrackRowBad) continue;
+        if (srow == kTrackRowNotGiven || (valid != nullptr && valid[row] == 0)) { v[e] = make_float2(0.f, 0.f); continue; }
+        const int t = row_track[row];
         const float2 x = *reinterpret_cast<const float2*>(src + (srow * J + j) * 2);
         v[e] = (res != nullptr) ? normalize_pair(x, (float)res[2 * t], res[2 * t + 1] / res[2 * t]) : x;
     }
     if (p0 + 1 < pairs) *reinterpret_cast<float4*>(table + p0 * 2) = make_float4(v[0].x, v[0].y, v[1].x, v[1].y);
     else *reinterpret_cast<float2*>(table + p0 * 2) = v[0];
+}
+
+// MISSED DETECTIONS: valid_out[row] = the frame of table row `row` is a real observation -- its source row's byte of valid_in (src_rows, or
+// nullptr = all given as valid) is non-zero AND all 2 J coordinates of the source row are finite.  A row that is not given (between two
+// keyframes) and a row out of range keep 1: they behave as without validity (zeros / NaN).  One wave per table row, four rows per
+// workgroup; lane 0 writes the row's byte.  It runs BEFORE normalize_tracks_kernel on the same stream and only reads src, so the
+// in-place form (src == table) sees the caller's coordinates, not rows that are already rewritten.
+static __global__ void __launch_bounds__(256)
+track_valid_kernel(const float* __restrict__ src, const long src_rows, const long rows, const int J, const int32_t* __restrict__ row_track,
+                   const int num_tracks, const int64_t* __restrict__ track_start, const int64_t* __restrict__ src_start, const int key_stride,
+                   const uint8_t* __restrict__ valid_in, uint8_t* __restrict__ valid_out)
+{
+    const int lane = threadIdx.x & 63;
+    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;                                             // (whole waves leave: `row` is uniform in a wave)
+    const long srow = track_source_row(row, src_rows, row_track, num_tracks, track_start, src_start, key_stride);
+    bool ok = true;
+    if (srow >= 0) {
+        for (int j = lane; j < J; j += 64) {
+            const float2 x = *reinterpret_cast<const float2*>(src + (srow * J + j) * 2);
+            ok = ok && finite_pair(x);
+        }
+        ok = __all(ok) != 0 && (valid_in == nullptr || valid_in[srow] != 0);
+    }
+    if (lane == 0) valid_out[row] = ok ? 1 : 0;
 }
 
 // The prediction of one window: the plain central prediction, or its mean with the un-flipped mirrored one (eval.py:163-166: x negated,

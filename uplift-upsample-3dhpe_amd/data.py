@@ -27,6 +27,7 @@ class PoseTable(object):
         self.J = main[0].shape[1]
         self.kp2d = None if poses_2d is None else torch.from_numpy(np.concatenate(poses_2d, 0).astype(np.float32)).to(self.device)
         self.kp3d = None
+        self.valid = None                                              # (frame validity: from_device only)
         if poses_3d is not None:
             assert all(len(a) == len(b) for a, b in zip(main, poses_3d))
             self.kp3d = torch.from_numpy(np.concatenate(poses_3d, 0).astype(np.float32)).to(self.device)
@@ -38,9 +39,10 @@ class PoseTable(object):
         self.frame_rates = np.asarray(frame_rates if frame_rates is not None else np.full(n, 50), np.int64)
 
     @classmethod
-    def from_device(cls, kp2d, lens):
+    def from_device(cls, kp2d, lens, valid=None):
         """A table without 3D data around 2D poses that already lie on the device: ``kp2d`` (sum(lens), J, 2) float32, contiguous, the videos
-        back to back; ``lens`` the frames of each video (host).  Nothing is copied but the two small index arrays."""
+        back to back; ``lens`` the frames of each video (host).  Nothing is copied but the two small index arrays.  ``valid``: (sum(lens),)
+        uint8 on the device, 0 = a missing frame (missed detections, include/uu3d.h): the window gathers mask the tokens that read one."""
         import torch
         self = cls.__new__(cls)
         self.torch = torch
@@ -51,6 +53,10 @@ class PoseTable(object):
             raise ValueError("kp2d must be a contiguous (sum(lens), J, 2) float32 tensor")
         self.J = int(kp2d.shape[1])
         self.kp2d, self.kp3d = kp2d, None
+        if valid is not None and (valid.dim() != 1 or valid.dtype != torch.uint8 or not valid.is_contiguous() or valid.device != kp2d.device
+                                  or int(valid.shape[0]) != int(kp2d.shape[0])):
+            raise ValueError("valid must be a contiguous (sum(lens),) uint8 tensor on the device of kp2d")
+        self.valid = valid
         self.d_starts = torch.from_numpy(self.starts).pin_memory().to(self.device, non_blocking=True)
         self.d_lens = torch.from_numpy(self.lens).pin_memory().to(self.device, non_blocking=True)
         n = len(self.lens)
@@ -171,10 +177,17 @@ class SequenceGenerator(object):
                 tuple(smask.shape) != (B, N) or smask.dtype != torch.uint8 or not smask.is_contiguous():
             raise ValueError("out buffers must be contiguous (B, N, J, 2) float32 and (B, N) uint8")
         fl = C.c_void_p(self._d_flip.data_ptr()) if self._d_flip is not None else None
-        st = lib.uu3d_gather_windows(C.c_void_p(t.kp2d.data_ptr()), C.c_void_p(t.d_starts.data_ptr()), C.c_void_p(t.d_lens.data_ptr()),
-                                     C.c_void_p(d_desc.data_ptr()), fl, B, N, J, 2, int(self.pad_edge), int(zero_masked),
-                                     C.c_void_p(kp2d.data_ptr()), C.c_void_p(smask.data_ptr()), C.c_void_p(pmask.data_ptr()),
-                                     C.c_void_p(stream))
+        valid = getattr(t, "valid", None)
+        if valid is None:
+            st = lib.uu3d_gather_windows(C.c_void_p(t.kp2d.data_ptr()), C.c_void_p(t.d_starts.data_ptr()), C.c_void_p(t.d_lens.data_ptr()),
+                                         C.c_void_p(d_desc.data_ptr()), fl, B, N, J, 2, int(self.pad_edge), int(zero_masked),
+                                         C.c_void_p(kp2d.data_ptr()), C.c_void_p(smask.data_ptr()), C.c_void_p(pmask.data_ptr()),
+                                         C.c_void_p(stream))
+        else:                                                          # missed detections: a token that reads a missing frame is masked
+            st = lib.uu3d_gather_windows_valid(C.c_void_p(t.kp2d.data_ptr()), C.c_void_p(t.d_starts.data_ptr()), C.c_void_p(t.d_lens.data_ptr()),
+                                               C.c_void_p(d_desc.data_ptr()), fl, B, N, J, 2, int(self.pad_edge), int(zero_masked),
+                                               C.c_void_p(valid.data_ptr()), C.c_void_p(kp2d.data_ptr()), C.c_void_p(smask.data_ptr()),
+                                               C.c_void_p(pmask.data_ptr()), C.c_void_p(stream))
         _capi.check(lib, st, None)
         out = {"kp2d": kp2d, "stride_mask": smask, "mask": pmask, "subjects": t.subjects[desc[:, 0]],
                "actions": t.actions[desc[:, 0]], "index": desc[:, 1].copy()}

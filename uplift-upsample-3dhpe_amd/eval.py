@@ -138,6 +138,17 @@ def _predict_windows_reuse(model, generator, descriptors, batch_size, flip, dept
     feats = torch.empty((fb, dt), dtype=torch.float32, device=dev)
     fl_order = C.c_void_p(generator._d_flip.data_ptr()) if generator._d_flip is not None else None
     cur = torch.cuda.current_stream(dev)
+    valid = getattr(t, "valid", None)                                  # missed detections: one byte per pose-table row, or None
+
+    def gather_rows(d_desc, n, lo, rb, mk, stream):
+        """uu3d_gather_window_frames for the chunk whose first pose-table row is ``lo``; with a validity table its _valid form (the video
+        starts are shifted by ``lo``, so the table's pointer is shifted back by as much)."""
+        args = (C.c_void_p(d_vs.data_ptr()), C.c_void_p(t.d_lens.data_ptr()), C.c_void_p(d_desc.data_ptr()), n, N, int(generator.pad_edge), 1, S, zero_row)
+        tail = (C.c_void_p(rb.data_ptr()), C.c_void_p(mk.data_ptr()), None, C.c_void_p(stream.cuda_stream))
+        if valid is None:
+            _capi.check(lib, lib.uu3d_gather_window_frames(*args, *tail), None)
+        else:
+            _capi.check(lib, lib.uu3d_gather_window_frames_valid(*args, C.c_void_p(valid.data_ptr() + int(lo)), *tail), None)
 
     def features_of_chunk(d, lo):
         """The rows the chunk's windows read (uu3d_gather_window_frames over all of them, marked on the device: the same rules as the
@@ -148,9 +159,7 @@ def _predict_windows_reuse(model, generator, descriptors, batch_size, flip, dept
         d_desc = torch.from_numpy(np.ascontiguousarray(db, np.int32)).pin_memory().to(dev, non_blocking=True)
         rb = torch.empty((len(db), N), dtype=torch.int32, device=dev)
         mk = torch.empty((len(db), N), dtype=torch.uint8, device=dev)
-        _capi.check(lib, lib.uu3d_gather_window_frames(C.c_void_p(d_vs.data_ptr()), C.c_void_p(t.d_lens.data_ptr()), C.c_void_p(d_desc.data_ptr()),
-                                                       len(db), N, int(generator.pad_edge), 1, S, zero_row, C.c_void_p(rb.data_ptr()),
-                                                       C.c_void_p(mk.data_ptr()), None, C.c_void_p(cur.cuda_stream)), None)
+        gather_rows(d_desc, len(db), lo, rb, mk, cur)
         mark = torch.zeros(zero_row, dtype=torch.bool, device=dev)
         r = rb[(rb >= 0) & (rb < zero_row)]
         mark[r.long()] = True
@@ -196,9 +205,7 @@ def _predict_windows_reuse(model, generator, descriptors, batch_size, flip, dept
                 with torch.cuda.stream(sstream):
                     d_desc = torch.from_numpy(np.ascontiguousarray(db, np.int32)).pin_memory().to(dev, non_blocking=True)
                     mk = mb if mb is not None else torch.empty((len(db), N), dtype=torch.uint8, device=dev)
-                    _capi.check(lib, lib.uu3d_gather_window_frames(C.c_void_p(d_vs.data_ptr()), C.c_void_p(t.d_lens.data_ptr()), C.c_void_p(d_desc.data_ptr()),
-                                                                   len(db), N, int(generator.pad_edge), 1, S, zero_row, C.c_void_p(rb.data_ptr()),
-                                                                   C.c_void_p(mk.data_ptr()), None, C.c_void_p(sstream.cuda_stream)), None)
+                    gather_rows(d_desc, len(db), lo, rb, mk, sstream)
                     if mb is None:                                     # (no strided input: a dropped frame is read as zeros, eval.py:67)
                         rb.masked_fill_(rb < 0, zero_row)
                 pending.append((b0, n, pipe.launch(len(db), wait_caller=False)))

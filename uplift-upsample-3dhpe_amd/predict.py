@@ -13,7 +13,7 @@ synchronises the stream once after the last forward (its pipeline's buffers go a
 (pinned, asynchronous) never wait.
 
     python -m uplift_upsample_3dhpe_amd.predict --config C --weights W.h5 --input tracks.npz --output out.npz \\
-        [--resolution W H] [--mask_stride S] [--keyframes_only]
+        [--resolution W H] [--mask_stride S] [--keyframes_only] [--mask_missing]
 """
 import argparse
 import ctypes as C
@@ -35,10 +35,12 @@ def _upload(a, dtype, device):
     return torch.from_numpy(np.ascontiguousarray(a, dtype)).pin_memory().to(device, non_blocking=True)
 
 
-def normalize_tracks(src, table, lens, resolutions=None, key_stride=0, src_lens=None):
+def normalize_tracks(src, table, lens, resolutions=None, key_stride=0, src_lens=None, valid_in=None, valid_out=None):
     """uu3d_normalize_tracks on the current stream.  ``src`` (R, J, 2) float32 on the device; ``table`` (sum(lens), J, 2) float32 (may be
     ``src`` when ``key_stride`` is 0); ``lens``: frames per track; ``resolutions`` (T, 2) (w, h) per track or None (no conversion);
-    ``key_stride`` > 0: ``src`` holds ``src_lens[t]`` keyframes of track t (frames 0, key_stride, ...), scattered into the zero-filled table."""
+    ``key_stride`` > 0: ``src`` holds ``src_lens[t]`` keyframes of track t (frames 0, key_stride, ...), scattered into the zero-filled table.
+    ``valid_out`` (sum(lens),) uint8 on the device: uu3d_normalize_tracks_valid -- it receives the per-frame flags (``valid_in`` (R,) uint8 or
+    None AND all coordinates finite) and the table rows of missing frames are zeros."""
     import torch
     lib = _capi.load_library()
     dev = table.device
@@ -53,8 +55,13 @@ def normalize_tracks(src, table, lens, resolutions=None, key_stride=0, src_lens=
         sstart = _upload(np.concatenate([[0], np.cumsum(src_lens)[:-1]]), np.int64, dev)
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
-        _capi.check(lib, lib.uu3d_normalize_tracks(_ptr(src), int(src.shape[0]), _ptr(table), rows, J, _ptr(row_track), T, _ptr(res),
-                                                   _ptr(tstart), _ptr(sstart), int(key_stride), C.c_void_p(stream)), None)
+        if valid_out is None:
+            _capi.check(lib, lib.uu3d_normalize_tracks(_ptr(src), int(src.shape[0]), _ptr(table), rows, J, _ptr(row_track), T, _ptr(res),
+                                                       _ptr(tstart), _ptr(sstart), int(key_stride), C.c_void_p(stream)), None)
+        else:
+            _capi.check(lib, lib.uu3d_normalize_tracks_valid(_ptr(src), int(src.shape[0]), _ptr(table), rows, J, _ptr(row_track), T, _ptr(res),
+                                                             _ptr(tstart), _ptr(sstart), int(key_stride), _ptr(valid_in), _ptr(valid_out),
+                                                             C.c_void_p(stream)), None)
     return table
 
 
@@ -100,9 +107,41 @@ def keyframe_count(length, stride):
     return (int(length) + int(stride) - 1) // int(stride)
 
 
-def pose_table(tracks, device, resolutions=None, key_stride=0, lengths=None):
-    """The dense, normalised ``data.PoseTable`` of the tracks (uu3d_normalize_tracks) -> (table, frames per track)."""
+def check_valid(valid, given):
+    """``predict_tracks``' ``valid`` argument against the frames given per track (``given``; keyframes with ``keyframes_only``): None,
+    "finite" or one (T_i,) array / tensor per track.  Shapes only: nothing touches a device."""
+    if valid is None or (isinstance(valid, str) and valid == "finite"):
+        return
+    if isinstance(valid, str) or not isinstance(valid, (list, tuple)):
+        raise ValueError('valid must be None, "finite" or a list with one (T_i,) array per track')
+    if len(valid) != len(given):
+        raise ValueError(f"valid must have one entry per track: {len(given)} tracks, {len(valid)} entries")
+    for i, (v, n) in enumerate(zip(valid, given)):
+        shape = tuple(v.shape) if hasattr(v, "shape") else np.asarray(v).shape
+        if shape != (int(n),):
+            raise ValueError(f"valid[{i}] must be ({int(n)},): one flag per given frame of track {i}, got {shape}")
+
+
+def _device_valid(valid, device):
+    """The list form of ``valid`` -> one (sum of given frames,) uint8 device tensor; host arrays go up in one pinned, asynchronous copy."""
     import torch
+    if not any(isinstance(v, torch.Tensor) for v in valid):
+        return _upload(np.concatenate([np.asarray(v).reshape(-1) != 0 for v in valid]).view(np.uint8), np.uint8, device)
+    parts = []
+    for v in valid:
+        if isinstance(v, torch.Tensor):
+            v = v if v.is_cuda else v.contiguous().pin_memory().to(device, non_blocking=True)
+            parts.append((v != 0).to(device=device, dtype=torch.uint8))
+        else:
+            parts.append(_upload((np.asarray(v) != 0).view(np.uint8), np.uint8, device))
+    return torch.cat(parts, 0)
+
+
+def pose_table(tracks, device, resolutions=None, key_stride=0, lengths=None, valid=None):
+    """The dense, normalised ``data.PoseTable`` of the tracks (uu3d_normalize_tracks) -> (table, frames per track).  ``valid`` as in
+    ``predict_tracks`` (not None: uu3d_normalize_tracks_valid into a fresh buffer; the table carries the per-frame flags)."""
+    import torch
+    check_valid(valid, [len(t) for t in tracks])
     tr = [_device_track(t, device) for t in tracks]
     if not tr:
         raise ValueError("no tracks")
@@ -129,16 +168,22 @@ def pose_table(tracks, device, resolutions=None, key_stride=0, lengths=None):
         if resolutions.shape != (len(tr), 2) or not (resolutions > 0).all():
             raise ValueError("resolutions must be one positive (w, h) or one per track")
     src = torch.cat(tr, 0).contiguous() if len(tr) > 1 else tr[0].contiguous()
-    if key_stride > 0 or resolutions is not None:
+    flags = None
+    if valid is not None:
+        kp = torch.empty((int(lens.sum()), J, 2), dtype=torch.float32, device=src.device)      # (never in the caller's own memory)
+        flags = torch.empty((int(lens.sum()),), dtype=torch.uint8, device=src.device)
+        normalize_tracks(src, kp, lens, resolutions, key_stride, given, valid_in=None if isinstance(valid, str) else _device_valid(valid, src.device),
+                         valid_out=flags)
+    elif key_stride > 0 or resolutions is not None:
         kp = torch.empty((int(lens.sum()), J, 2), dtype=torch.float32, device=src.device)      # (never in the caller's own memory)
         normalize_tracks(src, kp, lens, resolutions, key_stride, given)
     else:
         kp = src
-    return PoseTable.from_device(kp, lens), lens
+    return PoseTable.from_device(kp, lens, valid=flags), lens
 
 
 def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, flip=None, keyframes_only=False, reuse_frames=True,
-                   batch_size=None, root_relative=True, depth=None, lengths=None, graph=True):
+                   batch_size=None, root_relative=True, depth=None, lengths=None, graph=True, valid=None, return_valid=False):
     """One 3D pose per frame for each 2D keypoint track -> list of (T_i, J, 3) float32 tensors on the model's device (views of one buffer).
 
     ``tracks``: list of (T_i, J, 2) arrays or tensors, on the host or the device, at the frame rate the config was trained for (nothing is
@@ -157,8 +202,20 @@ def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, fl
     Frames are predicted by the model where ``eval.needed_windows`` keeps their window (every SEQUENCE_STRIDE-th with TEST_STRIDED_EVAL) and
     interpolated linearly in between by the rules of ``evaluation.interpolate_between_keyframes``; frames behind the last predicted one
     repeat it.  ``reuse_frames`` / ``batch_size`` (default config.BATCH_SIZE) / ``depth`` / ``graph`` go to ``eval.predict_windows``; a
-    model with generic dimensions has no frames form and runs the window forward.  One rank only."""
+    model with generic dimensions has no frames form and runs the window forward.  One rank only.
+
+    Missed detections -- ``valid``: None = every frame is an observation (today's call, the same bits).  "finite": a frame with a NaN or
+    Inf coordinate is MISSING.  A list with one (T_i,) array or tensor per track (host or device; with ``keyframes_only`` one entry per given
+    keyframe): 0 = missing, ANDed with the finite test.  A missing frame is never shown to the network: every window token that would read
+    it becomes the learned masked token, exactly like a frame the mask stride drops (also where "copy" padding would repeat it), and its
+    row of the pose table is zeros -- whatever its coordinates were, they change no bit of the result.  Its 3D pose is still returned: the
+    network upsamples over it as it does between keyframes.  The pose table is then a fresh buffer, the caller's memory is never written.
+    Needs a model with strided input (ValueError otherwise).  ``return_valid=True``: -> (poses, flags), flags a list of (T_i,) bool device
+    tensors with the effective per-frame flags (frames between keyframes that were not given: True)."""
     import torch
+    if valid is not None and not model.has_strided_input:
+        raise ValueError("valid needs a model with strided input: a missing frame becomes the learned masked token, which this model does not have")
+    check_valid(valid, [len(t) for t in tracks])
     dev = model.device
     cfg = config.copy()
     if mask_stride is None:
@@ -167,7 +224,7 @@ def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, fl
     flip = bool(cfg.EVAL_FLIP) if flip is None else bool(flip)
     if keyframes_only and mask_stride is None:
         raise ValueError("keyframes_only needs a mask stride")
-    table, lens = pose_table(tracks, dev, resolutions, int(mask_stride) if keyframes_only else 0, lengths)
+    table, lens = pose_table(tracks, dev, resolutions, int(mask_stride) if keyframes_only else 0, lengths, valid=valid)
     gen = SequenceGenerator(table, seq_len=cfg.SEQUENCE_LENGTH, target_frame_rate=50, subsample=1, stride=cfg.SEQUENCE_STRIDE,
                             padding_type=cfg.PADDING_TYPE, flip_augment=False, flip_lr_indices=cfg.AUGM_FLIP_KEYPOINT_ORDER,
                             mask_stride=mask_stride, stride_mask_align_global=True, rand_shift_stride_mask=False, shuffle=False)
@@ -186,7 +243,11 @@ def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, fl
         left, right, weight, _ = evaluation.keyframe_plan(frame_idx, stride, rows=rows)
     out = assemble_tracks(raw[0], raw[1] if flip else None, left, right, weight, flip_order=cfg.AUGM_FLIP_KEYPOINT_ORDER,
                           root=int(cfg.ROOT_KEYTPOINT) if root_relative else -1)
-    return list(torch.split(out, [int(n) for n in lens], 0))
+    poses = list(torch.split(out, [int(n) for n in lens], 0))
+    if not return_valid:
+        return poses
+    flags = table.valid.view(torch.bool) if table.valid is not None else torch.ones((int(lens.sum()),), dtype=torch.bool, device=out.device)
+    return poses, list(torch.split(flags, [int(n) for n in lens], 0))
 
 
 def padding_source_is_keyframe(length, config, mask_stride):
@@ -218,6 +279,8 @@ def parse_args(argv=None):
     p.add_argument("--mask_stride", type=int, default=None, help="input stride s_in (default: the config's first MASK_STRIDE)")
     p.add_argument("--keyframes_only", action="store_true",
                    help="the arrays hold frames 0, s_in, 2 s_in, ... only; a track of K keyframes is taken to have (K - 1) * s_in + 1 frames")
+    p.add_argument("--mask_missing", action="store_true",
+                   help="a frame with a NaN or Inf coordinate is a missed detection: never shown to the network, its pose is still predicted")
     return p.parse_args(argv)
 
 
@@ -243,7 +306,7 @@ def main(argv=None):
         lengths = [(len(t) - 1) * int(ms) + 1 for t in tracks]
     model = _load_model(config, args.weights)
     poses = predict_tracks(model, config, tracks, resolutions=None if args.resolution is None else tuple(args.resolution), mask_stride=ms,
-                           keyframes_only=args.keyframes_only, lengths=lengths)
+                           keyframes_only=args.keyframes_only, lengths=lengths, **({"valid": "finite"} if args.mask_missing else {}))
     np.savez(args.output, **{k: np.asarray(p.detach().cpu().numpy(), np.float32) for k, p in zip(names, poses)})
     print(f"wrote {args.output}: {len(names)} tracks, {sum(int(p.shape[0]) for p in poses)} frames", flush=True)
     return 0

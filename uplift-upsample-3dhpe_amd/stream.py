@@ -16,6 +16,7 @@ per-track counters live on the device, so the five steps are ONE captured hipGra
 waits for the device.
 
     python -m uplift_upsample_3dhpe_amd.stream --config C --weights W.h5 --input tracks.npz --output out.npz [--lookahead A] [--resolution W H]
+                                                 [--mask_missing]
 """
 import argparse
 import ctypes as C
@@ -63,12 +64,13 @@ def emits(frames, lookahead, config, mask_stride=None):
     return int(frames) >= 1 and c >= 0 and c % pred == 0
 
 
-def window_plan(frames, lookahead, config, mask_stride=None):
+def window_plan(frames, lookahead, config, mask_stride=None, valid=None):
     """The host mirror of uu3d_stream_commit's row rule for a track of ``frames`` frames: None when no pose comes out, else a dict of (N,)
     arrays over the window centred on ``frames - 1 - lookahead`` --
         "mask": the stride mask bit; "src": the frame a real token reads (-1: none -- a masked token, or zero padding);
         "kind": 0 masked token, 1 zero row, 2 keyframe ring, 3 edge row; "place": the ring place of kind 2 (-1 otherwise)
-    -- and "centre"."""
+    -- and "centre".  ``valid``: (frames,) flags, 0 = a missing frame (uu3d_stream_commit_valid): a token that reads one is masked --
+    mask' = mask and (no frame is read or valid[the frame read])."""
     if not emits(frames, lookahead, config, mask_stride):
         return None
     S, s_in, _ = session_strides(config, mask_stride)
@@ -82,6 +84,11 @@ def window_plan(frames, lookahead, config, mask_stride=None):
     inside = (f >= 0) & (f < L)
     have = inside | (pad_edge & (src >= 0) & (src < L))
     mask = np.mod((n - N // 2) * S + c, s_in) == 0
+    if valid is not None:
+        v = np.asarray(valid).reshape(-1) != 0
+        if len(v) != L:
+            raise ValueError(f"valid must have one flag per frame: {L} frames, {len(v)} flags")
+        mask = mask & (~have | v[np.clip(src, 0, L - 1)])
     edge_frame = (L - 1) // S * S
     kind = np.zeros(N, np.int64)
     kind[mask & ~have] = 1
@@ -108,12 +115,16 @@ def _check_resolutions(resolutions, slots):
 
 class StreamSession(object):
 
-    def __init__(self, model, config, slots, resolutions=None, mask_stride=None, flip=None, lookahead=0, root_relative=True, graph=True):
+    def __init__(self, model, config, slots, resolutions=None, mask_stride=None, flip=None, lookahead=0, root_relative=True, graph=True,
+                 missed_detections=False):
         """``slots``: tracks served side by side (a slot is a track: ``reset`` starts a new one).  ``resolutions``: None = the coordinates
         are normalised already, else one (w, h) in pixels or one per slot.  ``mask_stride`` / ``flip`` / ``root_relative`` as
         ``predict.predict_tracks``.  ``lookahead`` = a: frames the answer may lag behind the newest one, 0 <= a <=
         (SEQUENCE_LENGTH // 2) * SEQUENCE_STRIDE; with a at its maximum every window is complete.  ``graph``: replay one captured hipGraph
-        per tick instead of enqueueing the five steps.  Models with generic dims have no frames form: NotImplementedError."""
+        per tick instead of enqueueing the five steps.  Models with generic dims have no frames form: NotImplementedError.
+        ``missed_detections=True``: a pushed frame may be MISSING (``push(valid=...)``, or a row with a NaN / Inf coordinate) -- the slot's
+        track still grows by that frame, but no window ever shows it to the network (``predict.predict_tracks(valid=...)``); the tick runs
+        uu3d_stream_stage_valid / uu3d_stream_commit_valid.  Needs a model with strided input (ValueError).  False: today's session."""
         slots, lookahead = int(slots), int(lookahead)
         if slots < 1:
             raise ValueError("slots >= 1")
@@ -124,6 +135,9 @@ class StreamSession(object):
         if not model.arch.compiled_dims:
             raise NotImplementedError("StreamSession needs the frames form of the forward (uu3d_frame_features / uu3d_forward_frames_ex), "
                                       "which models with generic dims do not have")
+        self.missed_detections = bool(missed_detections)
+        if self.missed_detections and not model.has_strided_input:
+            raise ValueError("missed_detections needs a model with strided input: a missing frame becomes the learned masked token")
         import torch
         self._torch = torch
         self.model, self.slots, self.lookahead, self.graph = model, slots, lookahead, bool(graph)
@@ -149,6 +163,12 @@ class StreamSession(object):
             self._kp = torch.zeros((T, J, 2), dtype=torch.float32, device=dev)
             self._active = torch.ones((T,), dtype=torch.uint8, device=dev)
             self._active_all = True
+            self._valid_in = self._valid = self._valid_state = None
+            if self.missed_detections:
+                self._valid_in = torch.ones((T,), dtype=torch.uint8, device=dev)       # the caller's flags of this tick
+                self._valid_in_all = True
+                self._valid = torch.zeros((T,), dtype=torch.uint8, device=dev)         # ... ANDed with active and the finite test (stage)
+                self._valid_state = torch.zeros(int(lib.uu3d_stream_valid_bytes(model._h, C.byref(self._cfg))), dtype=torch.uint8, device=dev)
             self._res = None if res is None else torch.from_numpy(res).pin_memory().to(dev, non_blocking=True)
             self._order = torch.from_numpy(np.ascontiguousarray(config.AUGM_FLIP_KEYPOINT_ORDER, np.int32)).to(dev) if self.flip else None
             self._staged = torch.zeros((H * T, J, 2), dtype=torch.float32, device=dev)
@@ -181,11 +201,19 @@ class StreamSession(object):
 
     def _tick(self, stream):
         lib, m, cfg, st = self._lib, self.model, C.byref(self._cfg), C.c_void_p(stream.cuda_stream)
-        _capi.check(lib, lib.uu3d_stream_stage(m._h, cfg, _ptr(self._kp), _ptr(self._res), _ptr(self._active), _ptr(self._order),
-                                               _ptr(self._staged), st), m._h)
+        if self.missed_detections:
+            _capi.check(lib, lib.uu3d_stream_stage_valid(m._h, cfg, _ptr(self._kp), _ptr(self._res), _ptr(self._active), _ptr(self._order),
+                                                         _ptr(self._valid_in), _ptr(self._valid), _ptr(self._staged), st), m._h)
+        else:
+            _capi.check(lib, lib.uu3d_stream_stage(m._h, cfg, _ptr(self._kp), _ptr(self._res), _ptr(self._active), _ptr(self._order),
+                                                   _ptr(self._staged), st), m._h)
         self._features(self._staged, self._feats, stream)
-        _capi.check(lib, lib.uu3d_stream_commit(m._h, cfg, _ptr(self._state), _ptr(self._feats), _ptr(self._active), _ptr(self._rows),
-                                                _ptr(self._mask), _ptr(self._fresh), st), m._h)
+        if self.missed_detections:
+            _capi.check(lib, lib.uu3d_stream_commit_valid(m._h, cfg, _ptr(self._state), _ptr(self._feats), _ptr(self._active), _ptr(self._valid),
+                                                          _ptr(self._valid_state), _ptr(self._rows), _ptr(self._mask), _ptr(self._fresh), st), m._h)
+        else:
+            _capi.check(lib, lib.uu3d_stream_commit(m._h, cfg, _ptr(self._state), _ptr(self._feats), _ptr(self._active), _ptr(self._rows),
+                                                    _ptr(self._mask), _ptr(self._fresh), st), m._h)
         # the latency schedule: what model.forward_frames takes (below 1024 token rows both schedules give the same bits)
         m._forward_frames(self._table, self._rows, self._mask if m.has_strided_input else None, self._full, self._central, self._key, stream)
         _capi.check(lib, lib.uu3d_stream_emit(m._h, cfg, _ptr(self._state), _ptr(self._central), _ptr(self._order), _ptr(self._fresh),
@@ -218,15 +246,31 @@ class StreamSession(object):
         self.reset()
 
     # ---- public ---------------------------------------------------------------------------------------------------------------------
-    def push(self, kp2d, active=None):
+    def _flags(self, flags, name):
+        """(slots,) flags from the host or the device -> a uint8 tensor, pinned when it is on the host."""
+        torch = self._torch
+        if isinstance(flags, torch.Tensor):
+            f = flags.to(torch.uint8) if flags.dtype != torch.bool else flags.view(torch.uint8)
+        else:
+            f = torch.from_numpy(np.ascontiguousarray(np.asarray(flags) != 0).view(np.uint8))
+        if tuple(f.shape) != (self.slots,):
+            raise ValueError(f"{name} must be ({self.slots},)")
+        return f if f.is_cuda else f.contiguous().pin_memory()
+
+    def push(self, kp2d, active=None, valid=None):
         """One tick: ``kp2d`` (slots, J, 2), a host array or a tensor on the host or the device; ``active`` (slots,) bools or None = every slot
         (an inactive slot's row of ``kp2d`` is ignored and its track does not grow).  -> (poses (slots, J, 3) float32, fresh (slots,) bool)
         on the device: the session's own buffers, valid until the next ``push``.  ``fresh[i]``: slot i's pose is new at this tick -- the
         pose of its frame ``frames[i] - 1 - lookahead``; otherwise ``poses[i]`` is the slot's previous pose (zeros before its first).
+        ``valid`` (slots,) flags or None (sessions built with ``missed_detections=True`` only): 0 = slot i's frame of this tick is MISSING, as
+        is a row of ``kp2d`` with a NaN or Inf coordinate.  The slot's track grows by the frame all the same (``frames`` counts it; with
+        ``active[i] == 0`` it would not) and a pose comes out by the usual rule, from windows that never read the missing frame.
         Enqueues on the current stream and returns; never waits for the device."""
         torch = self._torch
         m = self.model
         dev = m.device
+        if valid is not None and not self.missed_detections:
+            raise ValueError("push(valid=...) needs a session built with missed_detections=True")
         if m._weights_dirty or getattr(m, "_pending_assigns", False):
             m._sync_from_trainer()                                    # (weights changed: the packs are rewritten on this stream)
             with torch.cuda.device(dev):
@@ -244,16 +288,14 @@ class StreamSession(object):
                     self._active.fill_(1)
                     self._active_all = True
             else:
-                if isinstance(active, torch.Tensor):
-                    act = active.to(torch.uint8) if active.dtype != torch.bool else active.view(torch.uint8)
-                else:
-                    act = torch.from_numpy(np.ascontiguousarray(np.asarray(active) != 0).view(np.uint8))
-                if tuple(act.shape) != (self.slots,):
-                    raise ValueError(f"active must be ({self.slots},)")
-                if not act.is_cuda:
-                    act = act.contiguous().pin_memory()
-                self._active.copy_(act, non_blocking=True)
+                self._active.copy_(self._flags(active, "active"), non_blocking=True)
                 self._active_all = False
+            if valid is not None:
+                self._valid_in.copy_(self._flags(valid, "valid"), non_blocking=True)
+                self._valid_in_all = False
+            elif self.missed_detections and not self._valid_in_all:
+                self._valid_in.fill_(1)
+                self._valid_in_all = True
             if self.graph:
                 self._graph.replay()
             else:
@@ -299,15 +341,23 @@ class StreamSession(object):
             pass
 
 
-def replay_tracks(model, config, tracks, resolutions=None, mask_stride=None, flip=None, lookahead=0, root_relative=True, graph=True):
+def replay_tracks(model, config, tracks, resolutions=None, mask_stride=None, flip=None, lookahead=0, root_relative=True, graph=True, valid=None):
     """Push complete tracks tick by tick, one slot per track (a slot is inactive once its track has ended) -> per track the pose the
     session returned at each of its ticks, (T_i, J, 3) float32, and the fresh flags (T_i,) bool, as host arrays.  One copy to the host,
-    at the end."""
+    at the end.  ``valid`` as ``predict.predict_tracks``: None, "finite" (rows with a NaN / Inf coordinate are missing frames) or one (T_i,)
+    host array per track -- a session with ``missed_detections=True``."""
     import torch
     lens = [int(len(t)) for t in tracks]
     T, ticks = len(tracks), max(lens)
+    flags = None
+    if valid is not None and not isinstance(valid, str):
+        from .predict import check_valid
+        check_valid(valid, lens)
+        flags = [np.asarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v).reshape(-1) != 0 for v in valid]
+    elif valid is not None and valid != "finite":
+        raise ValueError('valid must be None, "finite" or a list with one (T_i,) array per track')
     s = StreamSession(model, config, T, resolutions=resolutions, mask_stride=mask_stride, flip=flip, lookahead=lookahead,
-                      root_relative=root_relative, graph=graph)
+                      root_relative=root_relative, graph=graph, **({} if valid is None else {"missed_detections": True}))
     J = int(np.asarray(tracks[0]).shape[1])
     poses = torch.zeros((ticks, T, J, 3), dtype=torch.float32, device=model.device)
     fresh = torch.zeros((ticks, T), dtype=torch.bool, device=model.device)
@@ -318,7 +368,10 @@ def replay_tracks(model, config, tracks, resolutions=None, mask_stride=None, fli
             for i, t in enumerate(tracks):
                 if act[i]:
                     kp[i] = t[k]
-            p, f = s.push(kp, None if act.all() else act)
+            if flags is None:
+                p, f = s.push(kp, None if act.all() else act)
+            else:
+                p, f = s.push(kp, None if act.all() else act, valid=np.array([bool(act[i]) and bool(flags[i][k]) for i in range(T)]))
             poses[k].copy_(p)
             fresh[k].copy_(f)
         s.check_range()
@@ -339,6 +392,8 @@ def parse_args(argv=None):
     p.add_argument("--lookahead", type=int, default=0, help="frames the answer may lag behind the newest one (default 0)")
     p.add_argument("--resolution", type=float, nargs=2, metavar=("W", "H"), default=None,
                    help="image size in pixels of all tracks; without it the coordinates are taken as normalised already")
+    p.add_argument("--mask_missing", action="store_true",
+                   help="a frame with a NaN or Inf coordinate is a missed detection: the track grows by it, the network never sees it")
     return p.parse_args(argv)
 
 
@@ -363,7 +418,7 @@ def main(argv=None):
         raise SystemExit(f"--lookahead must be in [0, {max_lookahead(config)}]")
     model = _load_model(config, args.weights)
     poses, fresh = replay_tracks(model, config, tracks, resolutions=None if args.resolution is None else tuple(args.resolution),
-                                 lookahead=args.lookahead)
+                                 lookahead=args.lookahead, **({"valid": "finite"} if args.mask_missing else {}))
     out = {}
     for k, p, f in zip(names, poses, fresh):
         out[k] = np.asarray(p, np.float32)
