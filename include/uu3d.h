@@ -451,6 +451,30 @@ int uu3d_stream_commit_valid(uu3d_model* model, const uu3d_stream_config* cfg, v
                              uint8_t* stride_mask_dev, uint8_t* fresh_dev, void* stream);
 
 /*
+ * ANY FRAME RATE (predict.predict_tracks(fps=...)): the front of YOUR OWN 2D TRACKS for tracks that were not filmed at the rate the model
+ * was trained for.  The table holds the MODEL's time grid: row `row` (track row_track_dev[row]) is model frame k of its track, which sits at
+ * source position p_k = k * fps / model_fps.  The host works the positions out in exact integer arithmetic (predict.resample_plan) and
+ * hands over, per table row, left_dev / right_dev (rows) i64 = rows of src_dev (src_rows, J, 2) f32, 8-byte aligned, and weight_dev (rows)
+ * f64 = p_k - floor(p_k):
+ *     left == right: the table row is source row left, normalised as uu3d_normalize_tracks does (resolution_dev (num_tracks, 2) f64, or NULL:
+ *         taken as it is) -- the same bits; the right row is not read.  Model frames that coincide with a source frame (30 fps and input
+ *         stride 5: every 5th model frame is every 3rd video frame) are therefore exact, not approximately so.
+ *     else: both rows normalised the same way, then per coordinate (float)((double)a * (1.0 - w) + (double)b * w): two products and one
+ *         sum in float64, each rounded, no fused multiply-add.
+ * table_dev (rows, J, 2) f32, 16-byte aligned, is never src_dev (UU3D_ERR_INVALID_ARGUMENT: there is no in-place form).  A track id or a
+ * plan row outside [0, src_rows) yields a NaN row, never a read out of bounds.  One launch for all tracks, one thread per 16 bytes of the
+ * table, one writer per element, no atomics: bitwise repeatable.
+ * valid_out_dev (rows) u8 or NULL; not NULL: a wave-per-row launch in front on the same stream writes valid_out[row] = the left source
+ * frame is valid (valid_in_dev (src_rows) u8 non-zero, NULL = all) with all 2 J coordinates finite and, where left != right, the right one
+ * too; a row whose byte is 0 is written as zeros (MISSED DETECTIONS above: hand valid_out to the _valid gathers).  valid_in_dev without
+ * valid_out_dev is UU3D_ERR_INVALID_ARGUMENT.
+ */
+int uu3d_resample_tracks(const float* src_dev, int64_t src_rows, float* table_dev, int64_t rows, int32_t num_keypoints,
+                         const int32_t* row_track_dev, int32_t num_tracks, const double* resolution_dev,
+                         const int64_t* left_dev, const int64_t* right_dev, const double* weight_dev,
+                         const uint8_t* valid_in_dev, uint8_t* valid_out_dev, void* stream);
+
+/*
  * Per-kernel timing of the next uu3d_forward calls with HIP events on the launch stream.
  * When enabled, uu3d_forward records an event pair around every launch; uu3d_profile_read
  * synchronises those events and returns the per-launch records of the LAST forward.

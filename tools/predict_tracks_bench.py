@@ -4,7 +4,11 @@ eval.predict_windows, then .cpu() + evaluation.interpolate_between_keyframes in 
 predict_tracks ends with the dense poses on the device (also reported: with their copy to the host), the composition with them on the host.
 Median of --reps calls after one warm-up call each; frames/s = all frames of all tracks / seconds.
 --missing P: also predict_tracks(valid=flags) with a seeded fraction P of the frames missing (missed detections), same tracks.
-   python tools/predict_tracks_bench.py [--tracks 40] [--frames 2500] [--batch 512] [--reps 3] [--cases h36m_351:5,h36m_81:4] [--missing 0.3]"""
+--fps F: also the same tracks taken as filmed at F frames per second (a float or NUM/DEN): predict_tracks(fps=F) against the host route --
+numpy normalisation and resampling to the model's rate by predict.resample_plan, the plain call, .cpu() and numpy interpolation back to the
+tracks' own frames.
+   python tools/predict_tracks_bench.py [--tracks 40] [--frames 2500] [--batch 512] [--reps 3] [--cases h36m_351:5,h36m_81:4] [--missing 0.3]
+                                        [--fps 30]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -18,6 +22,7 @@ def main():
     ap.add_argument("--cases", default="h36m_351:5,h36m_81:4")
     ap.add_argument("--no_reuse", action="store_true", help="the window forward instead of the frames form, in both paths")
     ap.add_argument("--missing", type=float, default=0.0, help="also time predict_tracks(valid=...) with this fraction of the frames missing")
+    ap.add_argument("--fps", default=None, help="also time predict_tracks(fps=F) against numpy resampling on the host; a float or NUM/DEN")
     args = ap.parse_args()
     import numpy as np, torch
     import uplift_upsample_3dhpe_amd as pkg
@@ -33,6 +38,7 @@ def main():
     total = args.tracks * args.frames
     flags = [rng.random(args.frames) >= args.missing for _ in range(args.tracks)] if args.missing > 0 else None
     reuse = not args.no_reuse
+    fps = None if args.fps is None else predict.frame_rate(args.fps)
     results = []
     for case in args.cases.split(","):
         name, msv = case.split(":")
@@ -63,12 +69,35 @@ def main():
             pred = pred - pred[:, cfg.ROOT_KEYTPOINT:cfg.ROOT_KEYTPOINT + 1]
             return np.split(pred, np.cumsum([len(t) for t in px])[:-1])
 
+        def fps_path():
+            return predict.predict_tracks(model, cfg, px, resolutions=(W, H), mask_stride=int(msv), flip=True, reuse_frames=reuse, batch_size=args.batch,
+                                          fps=fps)
+
+        def fps_host():
+            p2 = np.concatenate([h36m.normalize_screen_coordinates(t, w=W, h=H).astype(np.float32) for t in px], 0)
+            model_lens, left, right, weight = predict.resample_plan([len(t) for t in px], fps)
+            w = weight[:, None, None]
+            table = np.where((left == right)[:, None, None], p2[left], (p2[left].astype(np.float64) * (1.0 - w) + p2[right].astype(np.float64) * w).astype(np.float32))
+            out = predict.predict_tracks(model, cfg, np.split(table, np.cumsum(model_lens)[:-1]), mask_stride=int(msv), flip=True, reuse_frames=reuse,
+                                         batch_size=args.batch)
+            res = []
+            for o, t in zip(out, px):                                  # back to the tracks' own frames: linear between the bracketing model frames
+                o = o.cpu().numpy()
+                num = np.arange(len(t)) * (50 * fps.denominator)
+                p = num // fps.numerator
+                fr = ((num - p * fps.numerator) / fps.numerator)[:, None, None]
+                res.append((o[p] * (1.0 - fr) + o[np.minimum(p + 1, len(o) - 1)] * fr).astype(np.float32))
+            return res
+
         row = dict(config=name, mask_stride=int(msv), tracks=args.tracks, frames=total, batch=args.batch, reuse_frames=reuse)
         outs = {}
         cases = [("predict_tracks", new_path), ("predict_tracks_to_host", lambda: new_path(True)), ("composition", composition)]
         if flags is not None:
             row["missing"] = args.missing
             cases.append(("predict_tracks_valid", missing_path))
+        if fps is not None:
+            row["fps"] = str(fps)
+            cases += [("predict_tracks_fps", fps_path), ("host_resample", fps_host)]
         for key, fn in cases:
             fn()
             torch.cuda.synchronize()
@@ -83,6 +112,9 @@ def main():
             row[key + "_frames_per_s"] = round(total / t, 1)
         row["speedup"] = round(row["composition_ms"] / row["predict_tracks_ms"], 3)
         row["max_abs_diff"] = float(max(np.abs(a.numpy() - b).max() for a, b in zip(outs["predict_tracks_to_host"], outs["composition"])))
+        if fps is not None:
+            row["fps_speedup"] = round(row["host_resample_ms"] / row["predict_tracks_fps_ms"], 3)
+            row["fps_max_abs_diff"] = float(max(np.abs(a.cpu().numpy() - b).max() for a, b in zip(outs["predict_tracks_fps"], outs["host_resample"])))
         row["device"] = torch.cuda.get_device_name(0)
         print(json.dumps(row), flush=True)
         results.append(row)

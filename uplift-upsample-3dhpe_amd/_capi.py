@@ -35,6 +35,7 @@ EXPORTED_SYMBOLS = (
     "uu3d_stream_state_bytes", "uu3d_stream_state_layout", "uu3d_stream_stage", "uu3d_stream_commit", "uu3d_stream_emit", "uu3d_stream_reset",
     "uu3d_normalize_tracks_valid", "uu3d_gather_windows_valid", "uu3d_gather_window_frames_valid", "uu3d_stream_valid_bytes",
     "uu3d_stream_stage_valid", "uu3d_stream_commit_valid",
+    "uu3d_resample_tracks",
 )
 # include/uu3d_ops.h
 OPS_SYMBOLS = (
@@ -186,6 +187,9 @@ def load_library(path=None):
     lib.uu3d_stream_stage_valid.argtypes = [vp, scfg, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.uu3d_stream_commit_valid.restype = C.c_int
     lib.uu3d_stream_commit_valid.argtypes = [vp, scfg, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    # any frame rate: the pose table on the model's time grid
+    lib.uu3d_resample_tracks.restype = C.c_int
+    lib.uu3d_resample_tracks.argtypes = [vp, i64, vp, i64, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp]
     lib.uu3d_world_to_cam_2d.restype = C.c_int
     lib.uu3d_world_to_cam_2d.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
     lib.uu3d_set_schedule.restype = C.c_int

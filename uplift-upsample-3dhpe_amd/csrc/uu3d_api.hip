@@ -537,6 +537,24 @@ int uu3d_normalize_tracks_valid(const float* src, int64_t src_rows, float* table
     return normalize_tracks(src, src_rows, table, rows, J, row_track, num_tracks, resolution, track_start, src_start, key_stride, valid_in, valid_out, stream);
 }
 
+int uu3d_resample_tracks(const float* src, int64_t src_rows, float* table, int64_t rows, int32_t J, const int32_t* row_track, int32_t num_tracks,
+                         const double* resolution, const int64_t* left, const int64_t* right, const double* weight, const uint8_t* valid_in,
+                         uint8_t* valid_out, void* stream) {
+    if (!src || !table || !row_track || !left || !right || !weight || src_rows < 1 || rows < 1 || J < 1 || num_tracks < 1) return UU3D_ERR_INVALID_ARGUMENT;
+    if (src == table || (valid_in != nullptr && valid_out == nullptr)) return UU3D_ERR_INVALID_ARGUMENT;
+    if (((uintptr_t)table & 15) != 0 || ((uintptr_t)src & 7) != 0) return UU3D_ERR_INVALID_ARGUMENT;
+    if (src_rows > (INT64_MAX >> 4) / J || rows > (INT64_MAX >> 4) / J) return UU3D_ERR_INVALID_ARGUMENT;
+    if (valid_out != nullptr) {
+        hipLaunchKernelGGL(resample_valid_kernel, dim3((unsigned)(((long)rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                           src, (long)src_rows, (long)rows, J, row_track, num_tracks, left, right, valid_in, valid_out);
+        if (hipGetLastError() != hipSuccess) return UU3D_ERR_HIP;
+    }
+    const long threads = ((long)rows * J + 1) / 2;
+    hipLaunchKernelGGL(resample_tracks_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       src, (long)src_rows, table, (long)rows, J, row_track, num_tracks, resolution, left, right, weight, (const uint8_t*)valid_out);
+    return hipGetLastError() == hipSuccess ? UU3D_OK : UU3D_ERR_HIP;
+}
+
 int uu3d_assemble_tracks(const float* plain, const float* flipped, int64_t num_windows, const int32_t* flip_order, const int32_t* left,
                          const int32_t* right, const double* weight, int64_t num_frames, int32_t J, int32_t root_index, float* out, void* stream) {
     if (!plain || !left || !right || !weight || !out || num_windows < 1 || num_frames < 1 || J < 1 || root_index >= J) return UU3D_ERR_INVALID_ARGUMENT;

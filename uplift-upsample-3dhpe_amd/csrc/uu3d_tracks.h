@@ -1,8 +1,8 @@
 // uu3d_tracks.h -- the front and the back of predict.predict_tracks (include/uu3d.h, "YOUR OWN 2D TRACKS"): pixel coordinates of the
 // caller's keypoint tracks -> the pose table the window gather reads, and the central predictions of the forwarded windows -> one 3D pose
-// per frame of every track.  Both kernels: one launch for all tracks of a call, one thread per 16 bytes of the flattened output, every
-// output element written by exactly one thread from inputs nobody writes (bitwise repeatable; the in-place form of the first kernel
-// reads only what the same thread overwrites).
+// per frame of every track; resample_tracks_kernel is the front for tracks at another frame rate.  All three: one launch for all tracks of
+// a call, one thread per 16 bytes of the flattened output, every output element written by exactly one thread from inputs nobody writes
+// (bitwise repeatable; the in-place form of the first kernel reads only what the same thread overwrites).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -96,6 +96,88 @@ track_valid_kernel(const float* __restrict__ src, const long src_rows, const lon
             ok = ok && finite_pair(x);
         }
         ok = __all(ok) != 0 && (valid_in == nullptr || valid_in[srow] != 0);
+    }
+    if (lane == 0) valid_out[row] = ok ? 1 : 0;
+}
+
+// ANY FRAME RATE (predict.resample_plan): table row `row` -- a frame of the model's time grid -- is source row left[row] where
+// left == right, else the two source rows mixed with weight[row] in float64.  One source pair as the table takes it: normalised with the
+// track's (w, h), or as it is.
+__device__ __forceinline__ float2 resample_source_pair(const float* src, const long srow, const int J, const int j, const bool normalise, const float wf,
+                                                       const double h_over_w)
+{
+    const float2 x = *reinterpret_cast<const float2*>(src + (srow * J + j) * 2);
+    return normalise ? normalize_pair(x, wf, h_over_w) : x;
+}
+
+// a * (1.0 - w) + b * w in float64: two products and one sum, each rounded (no fused multiply-add), then rounded to float32 -- the
+// expression of frame_value, so that a numpy restatement gives the same bits.
+__device__ __forceinline__ float resample_mix(const float a, const float b, const double w)
+{
+#pragma clang fp contract(off)
+    const double pa = (double)a * (1.0 - w);
+    const double pb = (double)b * w;
+    return (float)(pa + pb);
+}
+
+// table (rows, J, 2) from src (src_rows, J, 2), never in place: one thread per two (x, y) pairs = one 16-byte store.  A track id or a
+// plan row out of range writes NaN instead of reading out of bounds; a row whose byte of valid (rows, or nullptr) is 0 is written as
+// zeros.  Where left == right the right row is not read.
+static __global__ void __launch_bounds__(256)
+resample_tracks_kernel(const float* __restrict__ src, const long src_rows, float* __restrict__ table, const long rows, const int J,
+                       const int32_t* __restrict__ row_track, const int num_tracks, const double* __restrict__ res, const int64_t* __restrict__ left,
+                       const int64_t* __restrict__ right, const double* __restrict__ weight, const uint8_t* __restrict__ valid)
+{
+    const long pairs = rows * J;
+    const long p0 = ((long)blockIdx.x * 256 + threadIdx.x) * 2;
+    if (p0 >= pairs) return;
+    float2 v[2];
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        const long p = (p0 + e < pairs) ? p0 + e : p0;
+        const long row = p / J;
+        const int j = (int)(p - row * J);
+        const float nan = __builtin_nanf("");
+        v[e] = make_float2(nan, nan);
+        const int t = row_track[row];
+        const long l = left[row], r = right[row];
+        if (t < 0 || t >= num_tracks || l < 0 || l >= src_rows || r < 0 || r >= src_rows) continue;
+        if (valid != nullptr && valid[row] == 0) { v[e] = make_float2(0.f, 0.f); continue; }
+        const bool normalise = res != nullptr;
+        const float wf = normalise ? (float)res[2 * t] : 1.0f;
+        const double h_over_w = normalise ? res[2 * t + 1] / res[2 * t] : 1.0;
+        const float2 a = resample_source_pair(src, l, J, j, normalise, wf, h_over_w);
+        v[e] = a;
+        if (l == r) continue;
+        const float2 b = resample_source_pair(src, r, J, j, normalise, wf, h_over_w);
+        const double w = weight[row];
+        v[e] = make_float2(resample_mix(a.x, b.x, w), resample_mix(a.y, b.y, w));
+    }
+    if (p0 + 1 < pairs) *reinterpret_cast<float4*>(table + p0 * 2) = make_float4(v[0].x, v[0].y, v[1].x, v[1].y);
+    else *reinterpret_cast<float2*>(table + p0 * 2) = v[0];
+}
+
+// valid_out[row] = the model frame of table row `row` is a real observation: its left source row is valid (valid_in (src_rows) non-zero,
+// nullptr = all) with all 2 J coordinates finite, and where left != right the right one too.  A row whose plan or track id is out of range
+// keeps 1: it behaves as without validity (NaN).  One wave per table row, four rows per workgroup, lane 0 writes the byte, as
+// track_valid_kernel; it runs before resample_tracks_kernel on the same stream.
+static __global__ void __launch_bounds__(256)
+resample_valid_kernel(const float* __restrict__ src, const long src_rows, const long rows, const int J, const int32_t* __restrict__ row_track,
+                      const int num_tracks, const int64_t* __restrict__ left, const int64_t* __restrict__ right,
+                      const uint8_t* __restrict__ valid_in, uint8_t* __restrict__ valid_out)
+{
+    const int lane = threadIdx.x & 63;
+    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;                                             // (whole waves leave: `row` is uniform in a wave)
+    const int t = row_track[row];
+    const long l = left[row], r = right[row];
+    bool ok = true;
+    if (t >= 0 && t < num_tracks && l >= 0 && l < src_rows && r >= 0 && r < src_rows) {
+        for (int j = lane; j < J; j += 64) {
+            ok = ok && finite_pair(*reinterpret_cast<const float2*>(src + (l * J + j) * 2));
+            if (l != r) ok = ok && finite_pair(*reinterpret_cast<const float2*>(src + (r * J + j) * 2));
+        }
+        ok = __all(ok) != 0 && (valid_in == nullptr || (valid_in[l] != 0 && (l == r || valid_in[r] != 0)));
     }
     if (lane == 0) valid_out[row] = ok ? 1 : 0;
 }

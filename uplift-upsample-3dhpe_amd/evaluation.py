@@ -162,6 +162,69 @@ def keyframe_plan(frame_indices, keyframe_stride, rows=None):
     return left, right, weight, key
 
 
+def keyframe_plan_at(frame_indices, keyframe_stride, positions, rows=None):
+    """``keyframe_plan`` at rational positions: a video's motion is the piecewise-linear function through its keyframes (frames behind the
+    last keyframe repeat it), and this reads it anywhere, not only at whole frames -> (left, right, weight), one entry per position.
+
+    ``positions`` = (video, num, den), three integer arrays: entry i asks for position ``num[i] / den[i]`` (in frames, counted from the
+    first frame of the video, exact) of video ``video[i]``; videos are numbered as ``frame_indices`` lists them (a drop of the frame index
+    starts the next one).  Positions lie in [0, frames of the video - 1].  An integral position gives ``keyframe_plan``'s own entry for that
+    frame: the same rows and the same bits of the weight (the same integer / integer float64 division).  A fractional position between
+    frames p and p + 1 lies between the last keyframe L at or before p and the first keyframe N behind p; its weight is
+    ``((p - L) * den + num - p * den) / ((N - L) * den)``, one float64 division of two integers below 2^53.  Without N it repeats L, and
+    without L (in front of the video's first keyframe, where every frame keeps its own prediction) it takes frame p.  ``rows`` as in
+    ``keyframe_plan``.  ``keyframe_stride`` 1: every frame is a keyframe."""
+    f = np.asarray(frame_indices).astype(np.int64)
+    n = len(f)
+    video, num, den = (np.asarray(a).astype(np.int64).reshape(-1) for a in positions)
+    if not (len(video) == len(num) == len(den)):
+        raise ValueError("positions must be three arrays of one length: video, numerator, denominator")
+    pl, pr, pw, key = keyframe_plan(f, keyframe_stride)
+    new = np.ones(n, bool)
+    new[1:] = f[1:] <= f[:-1]
+    starts = np.flatnonzero(new)
+    lens = np.diff(np.append(starts, n))
+    if len(video) and (video.min() < 0 or video.max() >= len(starts)):
+        raise ValueError(f"positions name video {int(video.max() if video.max() >= len(starts) else video.min())}, there are {len(starts)}")
+    if (den < 1).any() or (num < 0).any():
+        raise ValueError("positions must be num / den with num >= 0 and den >= 1")
+    p = num // den
+    frac = num - p * den
+    if (p + (frac > 0) > lens[video] - 1).any():
+        i = int(np.flatnonzero(p + (frac > 0) > lens[video] - 1)[0])
+        raise ValueError(f"position {int(num[i])}/{int(den[i])} lies behind the last frame of video {int(video[i])} ({int(lens[video[i]])} frames)")
+    g = starts[video] + p                                              # the frame at or before the position, as a place in frame_indices
+    left, right, weight = pl[g].copy(), pr[g].copy(), pw[g].copy()     # integral positions: keyframe_plan's entries
+    pos = np.arange(n, dtype=np.int64)
+    vid = np.cumsum(new) - 1
+    last = np.maximum.accumulate(np.where(key, pos, -1)) if n else pos
+    nxt = np.append(np.minimum.accumulate(np.where(key, pos, n)[::-1])[::-1], n)[1:] if n else pos      # first keyframe BEHIND a place
+    fr = frac > 0
+    L, N = last[g], nxt[g]
+    has_last = L >= starts[video]
+    has_next = N < n
+    has_next[has_next] = vid[N[has_next]] == video[has_next]
+    between, tail = fr & has_last & has_next, fr & has_last & ~has_next
+    wn, wd = (g - L) * den + frac, (N - L) * den
+    if between.any() and max(int(wn[between].max()), int(wd[between].max())) >= 2 ** 53:
+        raise ValueError("position too fine: the weight's integers must stay below 2^53")
+    left[between], right[between] = L[between], N[between]
+    weight[between] = wn[between] / wd[between].astype(np.float64)
+    left[tail] = right[tail] = L[tail]
+    weight[tail] = 0.0
+    own = fr & ~has_last
+    left[own] = right[own] = g[own]
+    weight[own] = 0.0
+    if rows is not None:
+        rows = np.asarray(rows).astype(np.int64)
+        left, right = rows[left], rows[right]
+        missing = np.flatnonzero((left < 0) | (right < 0))
+        if len(missing):
+            raise ValueError(f"{len(missing)} positions need a prediction that was not forwarded (first: position {int(num[missing[0]])}/"
+                             f"{int(den[missing[0]])} of video {int(video[missing[0]])})")
+    return left, right, weight
+
+
 def report_from_sums(sums, action_wise=True, action_set=None):
     """The report of ``h36_action_wise_eval`` / ``frame_wise_eval`` from a table ``sums[a, m] = (sum of the errors >= 0 in metres, their
     count)`` with the actions of ``action_set`` in rows 0 .. A-1 and all poses in the last row (uu3d_pose_errors / uu3d_error_sums):

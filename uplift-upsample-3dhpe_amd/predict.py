@@ -6,17 +6,28 @@ for every frame or only for every ``s_in``-th one -- and returns one 3D pose per
     ->  eval.predict_windows' pipeline (device window gather, stride masks, flip in the same forward, ``reuse_frames``)
     ->  uu3d_assemble_tracks (un-flip, average, linear interpolation between predicted frames by ``evaluation.keyframe_plan``, root shift)
 
-The tracks are taken at the frame rate the config was trained for (Human3.6M: 50 Hz); nothing is resampled.  Between the first window
+Any frame rate: the model was trained at one rate (Human3.6M: 50 Hz).  ``predict_tracks(..., fps=F)`` takes tracks filmed at F frames per
+second -- 24, 25, 29.97, 30, 60, one rate per track if need be -- and returns the poses at the tracks' own frames (or at ``out_fps``):
+
+    pixel coordinates  ->  uu3d_resample_tracks (the pose table on the MODEL's time grid: ``resample_plan`` places model frame k at source
+    position k F / 50 in exact integer arithmetic; a model frame that coincides with a source frame is that frame's bits, the others are
+    mixed from their two neighbours in float64)  ->  the same windows and forwards  ->  uu3d_assemble_tracks with the plan of
+    ``evaluation.keyframe_plan_at`` (the piecewise-linear motion through the predicted model frames, read at the times of the output frames)
+
+The network only reads model frames whose index is a multiple of the input stride s_in; at 30 fps and s_in = 5 these are the video frames
+0, 3, 6, ..., at 25 fps every video frame (s_in even), at 60 fps and s_in = 5 the video frames 0, 6, 12, ...: nothing is interpolated on
+the input side then.  Without ``fps`` the tracks are taken at the model's rate and nothing is resampled.  Between the first window
 gather and the return nothing is copied to the host.  What still waits for the device inside the call: ``eval.predict_windows``
 synchronises the stream once after the last forward (its pipeline's buffers go away) and reads the f16x3 range flag; with
-``reuse_frames`` it also reads one frame count per chunk of the feature table.  The two kernels of this module and their uploads
+``reuse_frames`` it also reads one frame count per chunk of the feature table.  The kernels of this module and their uploads
 (pinned, asynchronous) never wait.
 
     python -m uplift_upsample_3dhpe_amd.predict --config C --weights W.h5 --input tracks.npz --output out.npz \\
-        [--resolution W H] [--mask_stride S] [--keyframes_only] [--mask_missing]
+        [--resolution W H] [--mask_stride S] [--keyframes_only] [--mask_missing] [--fps F] [--out_fps F]
 """
 import argparse
 import ctypes as C
+from fractions import Fraction
 
 import numpy as np
 
@@ -62,6 +73,121 @@ def normalize_tracks(src, table, lens, resolutions=None, key_stride=0, src_lens=
             _capi.check(lib, lib.uu3d_normalize_tracks_valid(_ptr(src), int(src.shape[0]), _ptr(table), rows, J, _ptr(row_track), T, _ptr(res),
                                                              _ptr(tstart), _ptr(sstart), int(key_stride), _ptr(valid_in), _ptr(valid_out),
                                                              C.c_void_p(stream)), None)
+    return table
+
+
+def frame_rate(value):
+    """One frame rate as an exact ``Fraction``: an int, a ``Fraction``, a ``(num, den)`` tuple of two integers, or a float, which becomes
+    ``Fraction(f).limit_denominator(1001)`` (29.97 -> 2997/100, 23.976 -> 2997/125, 30000 / 1001 stays itself).  A string is "NUM/DEN" or
+    a float, as the command line gives it.  Anything non-finite or <= 0 raises ValueError."""
+    if isinstance(value, str):
+        num, _, den = value.partition("/")
+        try:
+            value = (int(num), int(den)) if den else float(num)
+        except ValueError:
+            raise ValueError(f"a frame rate is a number or NUM/DEN, got {value!r}") from None
+    if isinstance(value, tuple) and len(value) == 2 and all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in value):
+        if value[1] == 0:
+            raise ValueError(f"a frame rate must be finite, got {value}")
+        rate = Fraction(int(value[0]), int(value[1]))
+    elif isinstance(value, bool):
+        raise ValueError(f"a frame rate is a number, got {value!r}")
+    elif isinstance(value, (int, np.integer, Fraction)):
+        rate = Fraction(value)
+    elif isinstance(value, (float, np.floating)):
+        if not np.isfinite(value):
+            raise ValueError(f"a frame rate must be finite, got {value}")
+        rate = Fraction(float(value)).limit_denominator(1001)
+    else:
+        raise ValueError(f"a frame rate is an int, a Fraction, a (num, den) tuple or a float, got {value!r}")
+    if rate <= 0:
+        raise ValueError(f"a frame rate must be > 0, got {value}")
+    return rate
+
+
+def frame_rates(fps, num_tracks):
+    """``predict_tracks``' ``fps`` / ``out_fps`` -> one ``Fraction`` per track.  One rate for all tracks (see ``frame_rate``; a tuple of two
+    integers is ONE rate num / den) or a list / array with one rate per track."""
+    if isinstance(fps, (list, np.ndarray)) or (isinstance(fps, tuple) and not (len(fps) == 2 and all(isinstance(v, (int, np.integer)) for v in fps))):
+        if len(fps) != num_tracks:
+            raise ValueError(f"fps must be one rate or one per track: {num_tracks} tracks, {len(fps)} rates")
+        return [frame_rate(v) for v in fps]
+    return [frame_rate(fps)] * num_tracks
+
+
+def resample_plan(lens, fps, model_fps=50):
+    """Where the frames of the model's time grid lie in tracks filmed at another rate -> (model_lens, left, right, weight); exact integer
+    arithmetic in numpy and Python integers, nothing touches a device.
+
+    A track of T source frames at rate f becomes ``T' = ceil((T - 1) * model_fps / f) + 1`` model frames (``model_lens``); model frame k
+    sits at source position ``p_k = k * f / model_fps``.  ``left`` / ``right`` (sum(model_lens),) int64: the two source frames around it
+    as GLOBAL source rows (all tracks back to back), ``weight`` float64 = p_k - floor(p_k), one division of two integers below 2^53.
+    weight == 0 has right == left; a position at or behind the last source frame (only a track's final model frame can be) repeats it:
+    left == right == T - 1, weight 0.  ``fps``: as ``frame_rates``; ``model_fps``: one rate."""
+    lens = np.asarray(lens, np.int64).reshape(-1)
+    if (lens < 1).any():
+        raise ValueError("every track needs at least one frame")
+    rates, mf = frame_rates(fps, len(lens)), frame_rate(model_fps)
+    model_lens, left, right, weight = [], [], [], []
+    start = 0
+    for T, f in zip((int(n) for n in lens), rates):
+        step = f / mf                                                  # source frames per model frame, exact
+        N, D = step.numerator, step.denominator
+        span = (T - 1) * D
+        Tm = -(-span // N) + 1                                         # ceil((T - 1) * model_fps / f) + 1
+        if max(Tm * N, D) >= 2 ** 53:
+            raise ValueError(f"a track of {T} frames at {f} fps: the plan's integers must stay below 2^53")
+        pos = np.arange(Tm, dtype=np.int64) * N
+        l, rem = pos // D, pos % D
+        rem[l >= T - 1] = 0
+        l = np.minimum(l, T - 1)
+        model_lens.append(Tm)
+        left.append(start + l)
+        right.append(start + l + (rem > 0))
+        weight.append(rem / np.float64(D))
+        start += T
+    return np.array(model_lens, np.int64), np.concatenate(left), np.concatenate(right), np.concatenate(weight)
+
+
+def output_positions(lens, fps, out_fps, model_fps=50):
+    """The model positions of the frames ``predict_tracks(fps=..., out_fps=...)`` returns -> (out_lens, (track, num, den)) for
+    ``evaluation.keyframe_plan_at``: a track of T frames at rate f has ``floor((T - 1) * out_fps / f) + 1`` output frames, frame i at time
+    i / out_fps, which is model position ``i * model_fps / out_fps`` (never behind the last model frame of ``resample_plan``)."""
+    lens = np.asarray(lens, np.int64).reshape(-1)
+    rates, outs, mf = frame_rates(fps, len(lens)), frame_rates(out_fps, len(lens)), frame_rate(model_fps)
+    out_lens, track, num, den = [], [], [], []
+    for t, (T, f, o) in enumerate(zip((int(n) for n in lens), rates, outs)):
+        n = ((T - 1) * o.numerator * f.denominator) // (o.denominator * f.numerator) + 1
+        q = mf / o
+        if max(n * q.numerator, q.denominator) >= 2 ** 53:
+            raise ValueError(f"a track of {T} frames at {f} fps returned at {o} fps: the plan's integers must stay below 2^53")
+        out_lens.append(n)
+        track.append(np.full(n, t, np.int64))
+        num.append(np.arange(n, dtype=np.int64) * q.numerator)
+        den.append(np.full(n, q.denominator, np.int64))
+    return np.array(out_lens, np.int64), (np.concatenate(track), np.concatenate(num), np.concatenate(den))
+
+
+def resample_tracks(src, table, model_lens, left, right, weight, resolutions=None, valid_in=None, valid_out=None):
+    """uu3d_resample_tracks on the current stream.  ``src`` (R, J, 2) float32 on the device; ``table`` (sum(model_lens), J, 2) float32, never
+    ``src``; ``left`` / ``right`` / ``weight``: the plan of ``resample_plan`` (host arrays); ``resolutions`` (T, 2) (w, h) per track or None
+    (no conversion).  ``valid_out`` (sum(model_lens),) uint8 on the device receives the per-model-frame flags (``valid_in`` (R,) uint8 or
+    None, ANDed with all coordinates finite, of the left source frame and, where weight > 0, the right one) and the table rows of missing
+    frames are zeros."""
+    import torch
+    lib = _capi.load_library()
+    dev = table.device
+    model_lens = np.asarray(model_lens, np.int64)
+    T, rows, J = len(model_lens), int(model_lens.sum()), int(table.shape[1])
+    if not (len(left) == len(right) == len(weight) == rows == int(table.shape[0])):
+        raise ValueError("the plan must have one entry per table row")
+    row_track = _upload(np.repeat(np.arange(T, dtype=np.int32), model_lens), np.int32, dev)
+    res = None if resolutions is None else _upload(np.asarray(resolutions, np.float64).reshape(T, 2), np.float64, dev)
+    d_left, d_right, d_weight = _upload(left, np.int64, dev), _upload(right, np.int64, dev), _upload(weight, np.float64, dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _capi.check(lib, lib.uu3d_resample_tracks(_ptr(src), int(src.shape[0]), _ptr(table), rows, J, _ptr(row_track), T, _ptr(res), _ptr(d_left),
+                                                  _ptr(d_right), _ptr(d_weight), _ptr(valid_in), _ptr(valid_out), C.c_void_p(stream)), None)
     return table
 
 
@@ -137,18 +263,35 @@ def _device_valid(valid, device):
     return torch.cat(parts, 0)
 
 
-def pose_table(tracks, device, resolutions=None, key_stride=0, lengths=None, valid=None):
-    """The dense, normalised ``data.PoseTable`` of the tracks (uu3d_normalize_tracks) -> (table, frames per track).  ``valid`` as in
-    ``predict_tracks`` (not None: uu3d_normalize_tracks_valid into a fresh buffer; the table carries the per-frame flags)."""
-    import torch
-    check_valid(valid, [len(t) for t in tracks])
+def _device_tracks(tracks, device):
+    """The tracks on the device -> (list of (T_i, J, 2) tensors, J, frames given per track)."""
     tr = [_device_track(t, device) for t in tracks]
     if not tr:
         raise ValueError("no tracks")
     J = int(tr[0].shape[1])
     if any(int(t.shape[1]) != J for t in tr):
         raise ValueError("all tracks must have the same number of keypoints")
-    given = np.array([int(t.shape[0]) for t in tr], np.int64)
+    return tr, J, np.array([int(t.shape[0]) for t in tr], np.int64)
+
+
+def _track_resolutions(resolutions, num_tracks):
+    """None, one (w, h) or one per track -> None or (num_tracks, 2) float64."""
+    if resolutions is None:
+        return None
+    resolutions = np.asarray(resolutions, np.float64)
+    if resolutions.shape == (2,):
+        resolutions = np.tile(resolutions, (num_tracks, 1))
+    if resolutions.shape != (num_tracks, 2) or not (resolutions > 0).all():
+        raise ValueError("resolutions must be one positive (w, h) or one per track")
+    return resolutions
+
+
+def pose_table(tracks, device, resolutions=None, key_stride=0, lengths=None, valid=None):
+    """The dense, normalised ``data.PoseTable`` of the tracks (uu3d_normalize_tracks) -> (table, frames per track).  ``valid`` as in
+    ``predict_tracks`` (not None: uu3d_normalize_tracks_valid into a fresh buffer; the table carries the per-frame flags)."""
+    import torch
+    check_valid(valid, [len(t) for t in tracks])
+    tr, J, given = _device_tracks(tracks, device)
     if key_stride > 0:
         if lengths is None or len(lengths) != len(tr):
             raise ValueError("keyframes_only needs `lengths`: the number of frames of every track")
@@ -161,12 +304,7 @@ def pose_table(tracks, device, resolutions=None, key_stride=0, lengths=None, val
         lens = given
     if (lens < 1).any():
         raise ValueError("every track needs at least one frame")
-    if resolutions is not None:
-        resolutions = np.asarray(resolutions, np.float64)
-        if resolutions.shape == (2,):
-            resolutions = np.tile(resolutions, (len(tr), 1))
-        if resolutions.shape != (len(tr), 2) or not (resolutions > 0).all():
-            raise ValueError("resolutions must be one positive (w, h) or one per track")
+    resolutions = _track_resolutions(resolutions, len(tr))
     src = torch.cat(tr, 0).contiguous() if len(tr) > 1 else tr[0].contiguous()
     flags = None
     if valid is not None:
@@ -182,12 +320,32 @@ def pose_table(tracks, device, resolutions=None, key_stride=0, lengths=None, val
     return PoseTable.from_device(kp, lens, valid=flags), lens
 
 
+def resampled_pose_table(tracks, device, fps, resolutions=None, valid=None, model_fps=50):
+    """``pose_table`` for tracks at ``fps`` frames per second: the dense, normalised table on the MODEL's time grid (``resample_plan``,
+    uu3d_resample_tracks; always a fresh buffer) -> (table, model frames per track, source frames per track).  With ``valid`` the table
+    carries one flag per model frame."""
+    import torch
+    check_valid(valid, [len(t) for t in tracks])
+    tr, J, lens = _device_tracks(tracks, device)
+    if (lens < 1).any():
+        raise ValueError("every track needs at least one frame")
+    resolutions = _track_resolutions(resolutions, len(tr))
+    model_lens, left, right, weight = resample_plan(lens, fps, model_fps)
+    src = torch.cat(tr, 0).contiguous() if len(tr) > 1 else tr[0].contiguous()
+    kp = torch.empty((int(model_lens.sum()), J, 2), dtype=torch.float32, device=src.device)
+    flags = None if valid is None else torch.empty((int(model_lens.sum()),), dtype=torch.uint8, device=src.device)
+    resample_tracks(src, kp, model_lens, left, right, weight, resolutions,
+                    valid_in=None if valid is None or isinstance(valid, str) else _device_valid(valid, src.device), valid_out=flags)
+    return PoseTable.from_device(kp, model_lens, valid=flags), model_lens, lens
+
+
 def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, flip=None, keyframes_only=False, reuse_frames=True,
-                   batch_size=None, root_relative=True, depth=None, lengths=None, graph=True, valid=None, return_valid=False):
+                   batch_size=None, root_relative=True, depth=None, lengths=None, graph=True, valid=None, return_valid=False, fps=None, out_fps=None,
+                   model_fps=50):
     """One 3D pose per frame for each 2D keypoint track -> list of (T_i, J, 3) float32 tensors on the model's device (views of one buffer).
 
     ``tracks``: list of (T_i, J, 2) arrays or tensors, on the host or the device, at the frame rate the config was trained for (nothing is
-    resampled).  ``resolutions``: None = the coordinates are normalised already (``h36m.normalize_screen_coordinates``), else one (w, h) in
+    resampled) unless ``fps`` says otherwise.  ``resolutions``: None = the coordinates are normalised already (``h36m.normalize_screen_coordinates``), else one (w, h) in
     pixels or one per track.  ``mask_stride`` (default: the config's first MASK_STRIDE) is the input stride s_in: the network sees frames
     0, s_in, 2 s_in, ... of a track only.  ``flip`` (default config.EVAL_FLIP): mirrored copy in the same forward, averaged.
     ``root_relative``: joint config.ROOT_KEYTPOINT is subtracted (it comes out exactly 0), as the evaluation compares poses.
@@ -211,8 +369,28 @@ def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, fl
     row of the pose table is zeros -- whatever its coordinates were, they change no bit of the result.  Its 3D pose is still returned: the
     network upsamples over it as it does between keyframes.  The pose table is then a fresh buffer, the caller's memory is never written.
     Needs a model with strided input (ValueError otherwise).  ``return_valid=True``: -> (poses, flags), flags a list of (T_i,) bool device
-    tensors with the effective per-frame flags (frames between keyframes that were not given: True)."""
+    tensors with the effective per-frame flags (frames between keyframes that were not given: True).
+
+    Any frame rate -- ``fps``: None = the tracks are at ``model_fps`` (today's call, the same bits, no further launch or buffer).  Else the
+    rate the tracks were filmed at: one for all tracks or a list with one per track, each an int, a ``fractions.Fraction``, a
+    ``(num, den)`` tuple of two integers (a tuple of two integers is always ONE rate; give two per-track rates as a list) or a float, which
+    is taken as ``Fraction(f).limit_denominator(1001)`` (29.97 -> 2997/100, 23.976 -> 2997/125, 30000 / 1001 itself); non-finite or <= 0:
+    ValueError.  The pose table is built on the model's time grid on the device (``resample_plan``, uu3d_resample_tracks): a track of T
+    frames becomes T' = ceil((T - 1) model_fps / fps) + 1 model frames, model frame k at source position k fps / model_fps -- exactly a
+    source frame where that is a whole number (its bits, nothing interpolated), else mixed linearly from its two neighbours; a position
+    behind the last source frame repeats it.  ``out_fps`` (default ``fps``) is the rate of the returned poses: output frame i is the pose
+    at time i / out_fps, read from the piecewise-linear motion through the predicted model frames (``evaluation.keyframe_plan_at``), and a
+    track has floor((T - 1) out_fps / fps) + 1 of them -- T by default.  A detector that ran on every k-th frame of a video: fps =
+    video rate / k, out_fps = video rate.  ``valid`` stays per SOURCE frame; a model frame is a real observation iff its left source frame
+    is valid and finite and, where it is mixed from two, its right one too.  ``return_valid=True`` with ``fps`` returns the flags on the
+    MODEL's grid, (T'_i,) tensors, not per returned pose.  ``fps`` with ``keyframes_only=True`` raises ValueError: say
+    ``fps=video rate / s_in, out_fps=video rate`` instead."""
     import torch
+    if fps is None and out_fps is not None:
+        raise ValueError("out_fps needs fps: the rate the tracks were filmed at")
+    if fps is not None and keyframes_only:
+        raise ValueError("fps and keyframes_only exclude each other: for a detector that ran on every k-th frame pass the given frames with "
+                         "fps=video_rate / k and out_fps=video_rate")
     if valid is not None and not model.has_strided_input:
         raise ValueError("valid needs a model with strided input: a missing frame becomes the learned masked token, which this model does not have")
     check_valid(valid, [len(t) for t in tracks])
@@ -224,7 +402,13 @@ def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, fl
     flip = bool(cfg.EVAL_FLIP) if flip is None else bool(flip)
     if keyframes_only and mask_stride is None:
         raise ValueError("keyframes_only needs a mask stride")
-    table, lens = pose_table(tracks, dev, resolutions, int(mask_stride) if keyframes_only else 0, lengths, valid=valid)
+    if fps is None:
+        table, lens = pose_table(tracks, dev, resolutions, int(mask_stride) if keyframes_only else 0, lengths, valid=valid)
+        model_lens = lens
+    else:
+        rates = frame_rates(fps, len(tracks))
+        table, model_lens, src_lens = resampled_pose_table(tracks, dev, rates, resolutions, valid=valid, model_fps=model_fps)
+        lens, positions = output_positions(src_lens, rates, rates if out_fps is None else out_fps, model_fps)
     gen = SequenceGenerator(table, seq_len=cfg.SEQUENCE_LENGTH, target_frame_rate=50, subsample=1, stride=cfg.SEQUENCE_STRIDE,
                             padding_type=cfg.PADDING_TYPE, flip_augment=False, flip_lr_indices=cfg.AUGM_FLIP_KEYPOINT_ORDER,
                             mask_stride=mask_stride, stride_mask_align_global=True, rand_shift_stride_mask=False, shuffle=False)
@@ -236,7 +420,9 @@ def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, fl
     rows = np.full(len(desc), -1, np.int64)
     rows[run] = np.arange(len(run))
     stride = ev.prediction_stride(cfg)
-    if stride is None:
+    if fps is not None:
+        left, right, weight = evaluation.keyframe_plan_at(frame_idx, 1 if stride is None else stride, positions, rows=rows)
+    elif stride is None:
         left = right = rows
         weight = np.zeros(len(desc), np.float64)
     else:
@@ -246,8 +432,8 @@ def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, fl
     poses = list(torch.split(out, [int(n) for n in lens], 0))
     if not return_valid:
         return poses
-    flags = table.valid.view(torch.bool) if table.valid is not None else torch.ones((int(lens.sum()),), dtype=torch.bool, device=out.device)
-    return poses, list(torch.split(flags, [int(n) for n in lens], 0))
+    flags = table.valid.view(torch.bool) if table.valid is not None else torch.ones((int(model_lens.sum()),), dtype=torch.bool, device=out.device)
+    return poses, list(torch.split(flags, [int(n) for n in model_lens], 0))
 
 
 def padding_source_is_keyframe(length, config, mask_stride):
@@ -267,6 +453,14 @@ def _load_model(config, weights_path):
     return model
 
 
+def _rate_argument(text):
+    """--fps / --out_fps: "NUM/DEN" or a float -> the exact rate."""
+    try:
+        return frame_rate(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+
+
 def parse_args(argv=None):
     p = argparse.ArgumentParser(prog="python -m uplift_upsample_3dhpe_amd.predict", description="3D poses for the 2D keypoint tracks of an .npz file "
                                 "(one (T, J, 2) array per track) -> an .npz with the same keys and (T, J, 3) float32 arrays.")
@@ -281,6 +475,9 @@ def parse_args(argv=None):
                    help="the arrays hold frames 0, s_in, 2 s_in, ... only; a track of K keyframes is taken to have (K - 1) * s_in + 1 frames")
     p.add_argument("--mask_missing", action="store_true",
                    help="a frame with a NaN or Inf coordinate is a missed detection: never shown to the network, its pose is still predicted")
+    p.add_argument("--fps", type=_rate_argument, default=None, metavar="F",
+                   help="frame rate of the tracks, a float or NUM/DEN (29.97, 30000/1001); without it they are taken at the model's rate")
+    p.add_argument("--out_fps", type=_rate_argument, default=None, metavar="F", help="frame rate of the poses written (default: --fps)")
     return p.parse_args(argv)
 
 
@@ -305,8 +502,11 @@ def main(argv=None):
             raise SystemExit("--keyframes_only needs a mask stride")
         lengths = [(len(t) - 1) * int(ms) + 1 for t in tracks]
     model = _load_model(config, args.weights)
+    if args.out_fps is not None and args.fps is None:
+        raise SystemExit("--out_fps needs --fps")
+    rate = {} if args.fps is None else {"fps": args.fps, **({} if args.out_fps is None else {"out_fps": args.out_fps})}
     poses = predict_tracks(model, config, tracks, resolutions=None if args.resolution is None else tuple(args.resolution), mask_stride=ms,
-                           keyframes_only=args.keyframes_only, lengths=lengths, **({"valid": "finite"} if args.mask_missing else {}))
+                           keyframes_only=args.keyframes_only, lengths=lengths, **({"valid": "finite"} if args.mask_missing else {}), **rate)
     np.savez(args.output, **{k: np.asarray(p.detach().cpu().numpy(), np.float32) for k, p in zip(names, poses)})
     print(f"wrote {args.output}: {len(names)} tracks, {sum(int(p.shape[0]) for p in poses)} frames", flush=True)
     return 0
