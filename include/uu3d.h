@@ -475,6 +475,78 @@ int uu3d_resample_tracks(const float* src_dev, int64_t src_rows, float* table_de
                          const uint8_t* valid_in_dev, uint8_t* valid_out_dev, void* stream);
 
 /*
+ * LIVE TRACKS AT ANY FRAME RATE (stream.StreamSession(fps=F)): LIVE TRACKS for a camera that does not run at the model's rate.  One SOURCE
+ * frame per slot and push in, at F frames per second; one pose per slot and push out, at the source frame's own time.  Let
+ * model_fps / F = a / b in lowest terms (uu3d_stream_rate; a, b < 2^20, so every product with a 31-bit counter is exact in int64).
+ *
+ * Input side.  Model frame k sits at source position k b / a -- predict.resample_plan's definition -- and is made the moment source frame
+ * ceil(k b / a) has been pushed.  Where the position is a whole number the model frame is that source frame (normalised as
+ * uu3d_stream_stage does: the same bits); otherwise its two neighbours are normalised first and then mixed in float64 with weight
+ * (double)((k b) % a) / (double)a, the double resample_plan computes, by the device functions of uu3d_resample_tracks.  The two newest raw
+ * source frames of a slot are all the history this needs.  After a slot's j-th push (0-based) its newest model frame is K = floor(j a / b);
+ * the push made K - floor((j - 1) a / b) of them: 1 at j = 0, then between 0 and ceil(a / b).
+ * Model side.  Every new model frame is one tick of LIVE TRACKS at cfg->lookahead = a_m (below), a SUB-TICK, with the stage replaced:
+ *   uu3d_stream_resample_stage -> uu3d_frame_features -> uu3d_stream_commit with active_dev = sub_active_dev -> uu3d_forward_frames_ex ->
+ *   uu3d_stream_emit (into a buffer of the caller's, not the session's output) -> uu3d_stream_file_keyframe
+ * A slot whose next model frame is not due yet is inactive in the sub-tick, so a sub-tick in which no slot is due changes no byte of the
+ * state and a push may be followed by more sub-ticks than it needs (at most ceil(a / b) are ever needed).  The session with a rate IS a
+ * plain session at lookahead a_m fed the resampled model-rate frames.
+ * Output side.  After the sub-ticks of a push, uu3d_stream_timed_emit: a slot that took its j-th frame at this push gets the pose of
+ * source frame q = j - rate->lookahead (in SOURCE frames) once q >= 0 -- at EVERY such push, not only at keyframes.  It is read at model
+ * position u = q a / b from the piecewise-linear motion through the emitted keyframes (centres that are multiples of P = cfg->pred_stride),
+ * the rule of evaluation.keyframe_plan_at: k0 = floor(u / P) P, k1 = k0 where u == k0, else k0 + P.  u == k0: keyframe k0's bits.
+ * Elsewhere (float)((double)p0 * (1.0 - w) + (double)p1 * w) with w = (double)(q a - k0 b) / (double)(P b), rounded once to float32; both
+ * keyframes are already un-flipped, averaged and root-shifted.  Any other slot keeps its previous pose (zeros before its first) and is
+ * reported as not fresh.
+ * The lookahead.  a_m is the largest integer in [0, (N / 2) * seq_stride] with k1(j - lookahead) <= floor(j a / b) - a_m for every
+ * j >= lookahead (periodic in j with period b P; the host enumerates one period: stream.rate_plan), so that k1 has been emitted when it is
+ * read.  The emitted keyframes are kept per slot in a ring of key_ring = D poses, centre c at place (c / P) % D, where D - 1 is the largest
+ * distance, in keyframes, from the newest emitted centre back to k0 over the same period.
+ *
+ * Per push, on one stream:
+ *   uu3d_stream_source_push(model, cfg, rate, state_dev, kp_dev (slots, J, 2) f32 raw, active_dev (slots) u8, valid_in_dev (slots) u8 or
+ *                           NULL, track_valid, stream)
+ *       one workgroup per slot.  An active slot's source counter advances and the frame is filed in ring place (index & 1), with its
+ *       validity byte: 1, or with track_valid != 0 (MISSED DETECTIONS, per SOURCE frame) valid_in && all 2 J coordinates finite.
+ *   n sub-ticks (above), n >= the largest number of model frames an active slot makes at this push.
+ *       uu3d_stream_resample_stage(model, cfg, rate, state_dev, resolution_dev or NULL, flip_order_dev, sub_active_dev (slots) u8,
+ *                                  valid_out_dev (slots) u8 or NULL, frames_out_dev (halves * slots, J, 2) f32, stream)
+ *           per slot: model frame k = the model counter is due iff ceil(k b / a) <= newest source index.  Due: the frame, its mirrored
+ *           copy, sub_active = 1; not due: zeros, sub_active = 0.  valid_out_dev not NULL: valid_out = the left source frame's byte and,
+ *           where the frame is mixed from two, the right one's -- the rule of uu3d_resample_tracks' valid_out_dev; a missing frame stages
+ *           zeros and flows through uu3d_stream_commit_valid as a missing frame of LIVE TRACKS does.
+ *       uu3d_stream_file_keyframe(model, cfg, rate, state_dev, fresh_dev, stream): behind uu3d_stream_emit, a fresh slot's pose (the held
+ *           pose of the state block) goes to its keyframe ring.
+ *   uu3d_stream_timed_emit(model, cfg, rate, state_dev, out_dev (slots, J, 3) f32, fresh_out_dev (slots) u8, stream)
+ *
+ *   uu3d_stream_rate_reset(model, cfg, rate, state_dev, slot_mask_dev or NULL, stream) = uu3d_stream_reset and, for the same slots, source
+ *   counter 0 and held output pose 0.
+ *
+ * The state block is the one of LIVE TRACKS with more behind it (uu3d_stream_rate_state_layout; bytes is the size of the WHOLE block, all
+ * zeros = every slot empty): source counters (slots) i32, pushed (slots) u8, source validity (slots, 2) u8, raw source frames
+ * (slots, 2, J, 2) f32, the keyframe ring (slots, key_ring, key_stride) f32 with key_stride = J * 3 rounded up to 4 floats, held output
+ * poses (slots, J, 3) f32.  No atomics, one writer per output element, all counters read and advanced on the device, every launch with the
+ * same arguments at every push: the sub-tick replays from ONE captured hipGraph, a linear chain, as the tick of LIVE TRACKS does.
+ */
+typedef struct uu3d_stream_rate { int32_t a, b, lookahead /* source frames */, key_ring /* D */; } uu3d_stream_rate;
+typedef struct uu3d_stream_rate_layout {
+    int64_t source_frames_offset, pushed_offset, source_valid_offset, source_offset, keys_offset, key_stride, out_held_offset, bytes;
+} uu3d_stream_rate_layout;
+int uu3d_stream_rate_state_layout(const uu3d_model* model, const uu3d_stream_config* cfg, const uu3d_stream_rate* rate,
+                                  uu3d_stream_rate_layout* out);
+int uu3d_stream_source_push(uu3d_model* model, const uu3d_stream_config* cfg, const uu3d_stream_rate* rate, void* state_dev,
+                            const float* kp_dev, const uint8_t* active_dev, const uint8_t* valid_in_dev, int32_t track_valid, void* stream);
+int uu3d_stream_resample_stage(uu3d_model* model, const uu3d_stream_config* cfg, const uu3d_stream_rate* rate, const void* state_dev,
+                               const double* resolution_dev, const int32_t* flip_order_dev, uint8_t* sub_active_dev,
+                               uint8_t* valid_out_dev, float* frames_out_dev, void* stream);
+int uu3d_stream_file_keyframe(uu3d_model* model, const uu3d_stream_config* cfg, const uu3d_stream_rate* rate, void* state_dev,
+                              const uint8_t* fresh_dev, void* stream);
+int uu3d_stream_timed_emit(uu3d_model* model, const uu3d_stream_config* cfg, const uu3d_stream_rate* rate, void* state_dev,
+                           float* out_dev, uint8_t* fresh_out_dev, void* stream);
+int uu3d_stream_rate_reset(uu3d_model* model, const uu3d_stream_config* cfg, const uu3d_stream_rate* rate, void* state_dev,
+                           const uint8_t* slot_mask_dev, void* stream);
+
+/*
  * Per-kernel timing of the next uu3d_forward calls with HIP events on the launch stream.
  * When enabled, uu3d_forward records an event pair around every launch; uu3d_profile_read
  * synchronises those events and returns the per-launch records of the LAST forward.

@@ -3,7 +3,10 @@ way to get the same pose without it: the host builds this tick's window and stri
 uploads them with their mirrored copies and calls ``model([x, mask])`` once -- the spatial stack over all frames of every window, every tick.
 A tick = host clock from the call to the synchronised result (a live consumer reads every pose); host input in all three variants.
 Median (and 90th percentile) over --ticks ticks after --warmup ticks, per config and slot count.
-   python tools/stream_bench.py [--slots 1,8,64] [--cases h36m_81:4,h36m_351:5] [--ticks 300] [--warmup 60] [--lookahead 0]"""
+   python tools/stream_bench.py [--slots 1,8,64] [--cases h36m_81:4,h36m_351:5] [--ticks 300] [--warmup 60] [--lookahead 0] [--fps F]
+--fps F (a float or NUM/DEN): microseconds per PUSH of StreamSession(fps=F) -- one source frame in, one pose out, on average
+model_fps / F sub-ticks -- next to the plain session pushed at the model's rate (the cost of one model tick); the lookahead is raised to
+the smallest one the rate allows.  The numpy baseline is left out."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -15,6 +18,7 @@ def main():
     ap.add_argument("--ticks", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=60)
     ap.add_argument("--lookahead", type=int, default=0)
+    ap.add_argument("--fps", default=None)
     args = ap.parse_args()
     import numpy as np, torch
     import uplift_upsample_3dhpe_amd as pkg
@@ -38,8 +42,9 @@ def main():
             rng = np.random.default_rng(0)
             px = (np.cumsum(rng.normal(0, 2.0, size=(total, T, J, 2)), 0) + rng.uniform(0.25, 0.75, size=(1, T, J, 2)) * [W, H]).astype(np.float32)
 
-            def session(graph):
-                s = stream.StreamSession(model, cfg, slots=T, resolutions=(W, H), mask_stride=ms, flip=True, lookahead=args.lookahead, graph=graph)
+            def session(graph, **rate):
+                s = stream.StreamSession(model, cfg, slots=T, resolutions=(W, H), mask_stride=ms, flip=True, graph=graph,
+                                         **({"lookahead": args.lookahead} if not rate else rate))
                 ts = []
                 for k in range(total):
                     t0 = time.perf_counter()
@@ -79,11 +84,20 @@ def main():
                 return ts[args.warmup:]
 
             row = dict(config=name, mask_stride=ms, slots=T, lookahead=args.lookahead, ticks=args.ticks)
-            for key, fn in (("graph", lambda: session(True)), ("no_graph", lambda: session(False)), ("baseline", baseline)):
+            variants = (("graph", lambda: session(True)), ("no_graph", lambda: session(False)), ("baseline", baseline))
+            if args.fps is not None:
+                la = max(args.lookahead, stream.rate_plan(cfg, args.fps, None, ms).min_lookahead)
+                plan = stream.rate_plan(cfg, args.fps, la, ms)
+                row.update(fps=args.fps, lookahead=la, model_lookahead=plan.a_m, sub_ticks_per_push=round(plan.A / plan.B, 4))
+                variants = (("fps_graph", lambda: session(True, fps=args.fps, lookahead=la)), ("graph", lambda: session(True)))
+            for key, fn in variants:
                 ts = np.asarray(fn())
                 row[key + "_us"] = round(1e6 * float(np.median(ts)), 1)
                 row[key + "_p90_us"] = round(1e6 * float(np.percentile(ts, 90)), 1)
-            row["speedup_vs_baseline"] = round(row["baseline_us"] / row["graph_us"], 2)
+            if args.fps is None:
+                row["speedup_vs_baseline"] = round(row["baseline_us"] / row["graph_us"], 2)
+            else:
+                row["push_over_model_tick"] = round(row["fps_graph_us"] / row["graph_us"], 2)
             row["device"] = torch.cuda.get_device_name(0)
             print(json.dumps(row), flush=True)
             results.append(row)

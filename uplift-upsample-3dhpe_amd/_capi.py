@@ -36,6 +36,8 @@ EXPORTED_SYMBOLS = (
     "uu3d_normalize_tracks_valid", "uu3d_gather_windows_valid", "uu3d_gather_window_frames_valid", "uu3d_stream_valid_bytes",
     "uu3d_stream_stage_valid", "uu3d_stream_commit_valid",
     "uu3d_resample_tracks",
+    "uu3d_stream_rate_state_layout", "uu3d_stream_source_push", "uu3d_stream_resample_stage", "uu3d_stream_file_keyframe",
+    "uu3d_stream_timed_emit", "uu3d_stream_rate_reset",
 )
 # include/uu3d_ops.h
 OPS_SYMBOLS = (
@@ -86,6 +88,15 @@ class Uu3dStreamConfig(C.Structure):
 
 class Uu3dStreamLayout(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("ring_capacity", "table_rows", "zero_row", "frames_offset", "held_offset", "table_offset", "bytes")]
+
+
+class Uu3dStreamRate(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("a", "b", "lookahead", "key_ring")]
+
+
+class Uu3dStreamRateLayout(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("source_frames_offset", "pushed_offset", "source_valid_offset", "source_offset", "keys_offset",
+                                         "key_stride", "out_held_offset", "bytes")]
 
 
 # void (*uu3d_grad_ready_fn)(void* user, int64_t first, int64_t count, void* stream)
@@ -181,6 +192,19 @@ def load_library(path=None):
     lib.uu3d_gather_windows_valid.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]
     lib.uu3d_gather_window_frames_valid.restype = C.c_int
     lib.uu3d_gather_window_frames_valid.argtypes = [vp, vp, vp, i32, i32, i32, i32, i64, i64, vp, vp, vp, vp, vp]
+    srate = C.POINTER(Uu3dStreamRate)
+    lib.uu3d_stream_rate_state_layout.restype = C.c_int
+    lib.uu3d_stream_rate_state_layout.argtypes = [vp, scfg, srate, C.POINTER(Uu3dStreamRateLayout)]
+    lib.uu3d_stream_source_push.restype = C.c_int
+    lib.uu3d_stream_source_push.argtypes = [vp, scfg, srate, vp, vp, vp, vp, C.c_int32, vp]
+    lib.uu3d_stream_resample_stage.restype = C.c_int
+    lib.uu3d_stream_resample_stage.argtypes = [vp, scfg, srate, vp, vp, vp, vp, vp, vp, vp]
+    lib.uu3d_stream_file_keyframe.restype = C.c_int
+    lib.uu3d_stream_file_keyframe.argtypes = [vp, scfg, srate, vp, vp, vp]
+    lib.uu3d_stream_timed_emit.restype = C.c_int
+    lib.uu3d_stream_timed_emit.argtypes = [vp, scfg, srate, vp, vp, vp, vp]
+    lib.uu3d_stream_rate_reset.restype = C.c_int
+    lib.uu3d_stream_rate_reset.argtypes = [vp, scfg, srate, vp, vp, vp]
     lib.uu3d_stream_valid_bytes.restype = sz
     lib.uu3d_stream_valid_bytes.argtypes = [vp, scfg]
     lib.uu3d_stream_stage_valid.restype = C.c_int

@@ -35,6 +35,7 @@
 #include "uu3d_metrics.h"
 #include "uu3d_tracks.h"
 #include "uu3d_stream.h"
+#include "uu3d_stream_rate.h"
 #include "uu3d_train.h"
 #include "uu3d_bwd.h"
 #include "uu3d_launch.h"
@@ -706,6 +707,115 @@ int uu3d_stream_reset(uu3d_model* m, const uu3d_stream_config* s, void* state, c
     hipLaunchKernelGGL(stream_reset_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, slot_mask, s->slots,
                        L.per_pose, (int32_t*)((char*)state + L.off_frames), (float*)((char*)state + L.off_held));
     return hipGetLastError() == hipSuccess ? UU3D_OK : fail(m, UU3D_ERR_HIP, "uu3d_stream_reset: launch failed");
+}
+
+// ---- live tracks at any frame rate (uu3d_stream_rate.h): the state behind the plain session's and the launches around its sub-ticks ----
+namespace {
+const char* stream_rate_error(const uu3d_stream_rate* r) {
+    if (!r) return "null uu3d_stream_rate";
+    if (r->a < 1 || r->a >= (1 << 20) || r->b < 1 || r->b >= (1 << 20)) return "a and b must be in [1, 2^20)";
+    if (r->lookahead < 0 || r->lookahead > (1 << 24)) return "the source lookahead must be in [0, 2^24]";
+    if (r->key_ring < 1 || r->key_ring > 4096) return "key_ring must be in [1, 4096]";
+    return nullptr;
+}
+int stream_rate_check(uu3d_model* m, const uu3d_stream_config* s, const uu3d_stream_rate* r, const void* state, const char* who) {
+    if (const int st = stream_check(m, s, who)) return st;
+    if (const char* e = stream_rate_error(r)) return fail(m, UU3D_ERR_INVALID_ARGUMENT, std::string(who) + ": " + e);
+    if (!state || ((uintptr_t)state & 255) != 0) return fail(m, UU3D_ERR_INVALID_ARGUMENT, std::string(who) + ": state must be a 256-byte aligned block");
+    return UU3D_OK;
+}
+RateParams rate_params(const uu3d_model* m, const uu3d_stream_config* s, const uu3d_stream_rate* r, const StreamLayout& L, const RateLayout& R) {
+    RateParams p{};
+    p.slots = s->slots; p.J = m->cfg.num_keypoints; p.halves = L.halves; p.per_pose = L.per_pose; p.a = r->a; p.b = r->b;
+    p.lookahead = r->lookahead; p.model_lookahead = s->lookahead; p.pred_stride = s->pred_stride; p.key_ring = R.key_ring; p.key_stride = R.key_stride;
+    return p;
+}
+}  // namespace
+
+int uu3d_stream_rate_state_layout(const uu3d_model* mc, const uu3d_stream_config* s, const uu3d_stream_rate* r, uu3d_stream_rate_layout* out) {
+    auto* m = const_cast<uu3d_model*>(mc);
+    if (!m || !out) return UU3D_ERR_INVALID_ARGUMENT;
+    if (const int st = stream_check(m, s, "uu3d_stream_rate_state_layout")) return st;
+    if (const char* e = stream_rate_error(r)) return fail(m, UU3D_ERR_INVALID_ARGUMENT, std::string("uu3d_stream_rate_state_layout: ") + e);
+    const RateLayout R = rate_layout(stream_layout_of(m, s), m->cfg.num_keypoints, r->key_ring);
+    out->source_frames_offset = (int64_t)R.off_source_frames; out->pushed_offset = (int64_t)R.off_pushed;
+    out->source_valid_offset = (int64_t)R.off_source_valid; out->source_offset = (int64_t)R.off_source; out->keys_offset = (int64_t)R.off_keys;
+    out->key_stride = R.key_stride; out->out_held_offset = (int64_t)R.off_out_held; out->bytes = (int64_t)R.bytes;
+    return UU3D_OK;
+}
+
+int uu3d_stream_source_push(uu3d_model* m, const uu3d_stream_config* s, const uu3d_stream_rate* r, void* state, const float* kp,
+                            const uint8_t* active, const uint8_t* valid_in, int32_t track_valid, void* stream) {
+    if (!m) return UU3D_ERR_INVALID_ARGUMENT;
+    if (const int st = stream_rate_check(m, s, r, state, "uu3d_stream_source_push")) return st;
+    if (!kp || !active || ((uintptr_t)kp & 7) != 0) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_source_push: kp (8-byte aligned) and active must be given");
+    if (track_valid) if (const int st = stream_valid_check(m, "uu3d_stream_source_push")) return st;
+    const RateLayout R = rate_layout(stream_layout_of(m, s), m->cfg.num_keypoints, r->key_ring);
+    char* base = (char*)state;
+    hipLaunchKernelGGL(stream_source_push_kernel, dim3(s->slots), dim3(64), 0, (hipStream_t)stream, kp, active, valid_in, track_valid ? 1 : 0,
+                       m->cfg.num_keypoints, (int32_t*)(base + R.off_source_frames), (uint8_t*)(base + R.off_pushed),
+                       (uint8_t*)(base + R.off_source_valid), (float*)(base + R.off_source));
+    return hipGetLastError() == hipSuccess ? UU3D_OK : fail(m, UU3D_ERR_HIP, "uu3d_stream_source_push: launch failed");
+}
+
+int uu3d_stream_resample_stage(uu3d_model* m, const uu3d_stream_config* s, const uu3d_stream_rate* r, const void* state, const double* resolution,
+                               const int32_t* flip_order, uint8_t* sub_active, uint8_t* valid_out, float* frames_out, void* stream) {
+    if (!m) return UU3D_ERR_INVALID_ARGUMENT;
+    if (const int st = stream_rate_check(m, s, r, state, "uu3d_stream_resample_stage")) return st;
+    if (!sub_active || !frames_out || (s->flip && !flip_order)) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_resample_stage: null buffer");
+    if (((uintptr_t)frames_out & 15) != 0) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_resample_stage: frames_out must be 16-byte aligned");
+    if (valid_out) if (const int st = stream_valid_check(m, "uu3d_stream_resample_stage")) return st;
+    const StreamLayout L = stream_layout_of(m, s);
+    const RateLayout R = rate_layout(L, m->cfg.num_keypoints, r->key_ring);
+    const char* base = (const char*)state;
+    const long threads = ((long)L.halves * s->slots * m->cfg.num_keypoints + 1) / 2;
+    hipLaunchKernelGGL(stream_resample_stage_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       rate_params(m, s, r, L, R), (const int32_t*)(base + R.off_source_frames), (const int32_t*)(base + L.off_frames),
+                       (const uint8_t*)(base + R.off_source_valid), (const float*)(base + R.off_source), resolution, flip_order, sub_active,
+                       valid_out, frames_out);
+    return hipGetLastError() == hipSuccess ? UU3D_OK : fail(m, UU3D_ERR_HIP, "uu3d_stream_resample_stage: launch failed");
+}
+
+int uu3d_stream_file_keyframe(uu3d_model* m, const uu3d_stream_config* s, const uu3d_stream_rate* r, void* state, const uint8_t* fresh, void* stream) {
+    if (!m) return UU3D_ERR_INVALID_ARGUMENT;
+    if (const int st = stream_rate_check(m, s, r, state, "uu3d_stream_file_keyframe")) return st;
+    if (!fresh) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_file_keyframe: null fresh");
+    const StreamLayout L = stream_layout_of(m, s);
+    const RateLayout R = rate_layout(L, m->cfg.num_keypoints, r->key_ring);
+    char* base = (char*)state;
+    const long threads = (long)s->slots * (R.key_stride / 4);
+    hipLaunchKernelGGL(stream_file_keyframe_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       rate_params(m, s, r, L, R), (const int32_t*)(base + L.off_frames), fresh, (const float*)(base + L.off_held),
+                       (float*)(base + R.off_keys));
+    return hipGetLastError() == hipSuccess ? UU3D_OK : fail(m, UU3D_ERR_HIP, "uu3d_stream_file_keyframe: launch failed");
+}
+
+int uu3d_stream_timed_emit(uu3d_model* m, const uu3d_stream_config* s, const uu3d_stream_rate* r, void* state, float* out, uint8_t* fresh_out,
+                           void* stream) {
+    if (!m) return UU3D_ERR_INVALID_ARGUMENT;
+    if (const int st = stream_rate_check(m, s, r, state, "uu3d_stream_timed_emit")) return st;
+    if (!out || !fresh_out || ((uintptr_t)out & 15) != 0) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_timed_emit: out (16-byte aligned) and fresh_out must be given");
+    const StreamLayout L = stream_layout_of(m, s);
+    const RateLayout R = rate_layout(L, m->cfg.num_keypoints, r->key_ring);
+    char* base = (char*)state;
+    const long threads = ((long)s->slots * L.per_pose + 3) / 4;
+    hipLaunchKernelGGL(stream_timed_emit_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       rate_params(m, s, r, L, R), (const int32_t*)(base + R.off_source_frames), (const uint8_t*)(base + R.off_pushed),
+                       (const float*)(base + R.off_keys), (float*)(base + R.off_out_held), out, fresh_out);
+    return hipGetLastError() == hipSuccess ? UU3D_OK : fail(m, UU3D_ERR_HIP, "uu3d_stream_timed_emit: launch failed");
+}
+
+int uu3d_stream_rate_reset(uu3d_model* m, const uu3d_stream_config* s, const uu3d_stream_rate* r, void* state, const uint8_t* slot_mask, void* stream) {
+    if (!m) return UU3D_ERR_INVALID_ARGUMENT;
+    if (const int st = stream_rate_check(m, s, r, state, "uu3d_stream_rate_reset")) return st;
+    if (const int st = uu3d_stream_reset(m, s, state, slot_mask, stream)) return st;
+    const StreamLayout L = stream_layout_of(m, s);
+    const RateLayout R = rate_layout(L, m->cfg.num_keypoints, r->key_ring);
+    char* base = (char*)state;
+    const long threads = (long)s->slots * L.per_pose;
+    hipLaunchKernelGGL(stream_rate_reset_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, slot_mask, s->slots,
+                       L.per_pose, (int32_t*)(base + R.off_source_frames), (uint8_t*)(base + R.off_pushed), (float*)(base + R.off_out_held));
+    return hipGetLastError() == hipSuccess ? UU3D_OK : fail(m, UU3D_ERR_HIP, "uu3d_stream_rate_reset: launch failed");
 }
 
 int uu3d_world_to_cam_2d(const float* world, const float* cams, int32_t B, int32_t N, int32_t J, float* cam3d, float* kp2d, void* stream) {

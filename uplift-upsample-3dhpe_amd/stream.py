@@ -15,10 +15,33 @@ session's resident feature table -> uu3d_stream_emit.  The spatial stack runs on
 per-track counters live on the device, so the five steps are ONE captured hipGraph (``graph=True``) replayed at every tick; ``push`` never
 waits for the device.
 
+Any frame rate -- ``StreamSession(..., fps=F, model_fps=50)``: one SOURCE frame per slot and push, at F frames per second, and one pose per
+slot and push, at the source frame's own time; everything on the device, ``push`` still never waits.  With model_fps / F = A / B in lowest
+terms (exact integers; ``rate_plan``, ``push_plan``):
+  input   model frame k sits at source position k B / A (``predict.resample_plan``'s definition) and is made the moment source frame
+          ceil(k B / A) has been pushed: that source frame's bits where the position is whole, else the two neighbours normalised and then
+          mixed in float64 with resample_plan's own weight (the device functions of uu3d_resample_tracks).  After a slot's j-th push
+          (0-based) its newest model frame is K = floor(j A / B); the push made K - floor((j - 1) A / B) model frames -- 1 at j = 0, then
+          0 .. ceil(A / B).
+  model   every new model frame is one tick of the plain session (a SUB-TICK: uu3d_stream_resample_stage in place of uu3d_stream_stage,
+          then features, commit, forward, emit as above, then uu3d_stream_file_keyframe) at the model lookahead a_m: the session with ``fps``
+          IS a plain session at lookahead a_m fed the resampled model-rate frames.
+  output  ``poses[i]`` is the pose of source frame q = j - lookahead of slot i (``lookahead`` counts SOURCE frames), read at model position
+          u = q A / B from the piecewise-linear motion through the emitted keyframes (centres that are multiples of the prediction stride
+          P; the rule of ``evaluation.keyframe_plan_at``, as ``predict_tracks(fps=F)``): k0 = floor(u / P) P, k1 = k0 where u == k0, else
+          k0 + P; u == k0 gives that keyframe's bits, anything else float32(p0 (1 - w) + p1 w) in float64, w = (q A - k0 B) / (P B).
+          ``fresh[i]`` is set on EVERY push with q >= 0 of an active slot, not only at keyframes; otherwise the previous pose is held.
+  a_m     the largest integer in [0, max_lookahead(config)] with k1(j - lookahead) <= floor(j A / B) - a_m for every j >= lookahead: k1 has
+          been emitted when it is read.  The condition repeats in j with period B P and is enumerated exactly; when no a_m >= 0 exists
+          the constructor raises ValueError naming the smallest sufficient ``lookahead``.  The emitted keyframes live per slot in a ring of
+          D poses, centre c at place (c / P) % D, D - 1 = the largest distance in keyframes from the newest emitted centre back to k0.
+``fps=None`` is the session above, bit for bit: the same launches, the same buffers, the same single captured graph.
+
     python -m uplift_upsample_3dhpe_amd.stream --config C --weights W.h5 --input tracks.npz --output out.npz [--lookahead A] [--resolution W H]
-                                                 [--mask_missing]
+                                                 [--mask_missing] [--fps F]
 """
 import argparse
+import collections
 import ctypes as C
 import gc
 
@@ -102,6 +125,72 @@ def window_plan(frames, lookahead, config, mask_stride=None, valid=None):
             "place": np.where(kind == 2, (src // s_in) % cap, -1)}
 
 
+RatePlan = collections.namedtuple("RatePlan", "A B n_max a_m D min_lookahead pred_stride lookahead")
+
+
+def _newest_model_frame(j, A, B):
+    """K(j) = floor(j A / B): the newest model frame after a slot's j-th push (0-based)."""
+    return (j * A) // B
+
+
+def _output_keyframes(q, A, B, P):
+    """(k0, k1, numerator, denominator of the weight) of source frame q: model position u = q A / B, k0 = floor(u / P) P, k1 = k0 where
+    u == k0, else k0 + P; the weight is (q A - k0 B) / (P B)."""
+    num = q * A
+    k0 = num // B // P * P
+    off = num - k0 * B
+    return k0, (k0 if off == 0 else k0 + P), off, P * B
+
+
+def rate_plan(config, fps, lookahead, mask_stride=None, model_fps=50):
+    """The plan of ``StreamSession(fps=fps, lookahead=lookahead)`` -> RatePlan(A, B, n_max, a_m, D, min_lookahead, pred_stride, lookahead);
+    integers and ``Fraction`` only.  A / B = model_fps / fps in lowest terms; n_max = ceil(A / B), the most model frames one push makes;
+    a_m the model lookahead and D the places of the keyframe ring (the module docstring), both by exact enumeration over one period B P
+    of j; min_lookahead the smallest ``lookahead`` (in source frames) for which an a_m >= 0 exists.  A smaller ``lookahead`` raises
+    ValueError naming it; ``lookahead=None`` plans for min_lookahead itself."""
+    from .predict import frame_rate
+    rho = frame_rate(model_fps) / frame_rate(fps)
+    A, B = rho.numerator, rho.denominator
+    if max(A, B) >= 2 ** 20:
+        raise ValueError(f"model_fps / fps = {A}/{B}: numerator and denominator must stay below 2^20")
+    _, _, P = session_strides(config, mask_stride)
+    period = B * P
+    keys = [_output_keyframes(q, A, B, P) for q in range(period)]
+
+    def slack(L):                                                      # min over one period of K(q + L) - k1(q)
+        return min(_newest_model_frame(q + L, A, B) - k[1] for q, k in enumerate(keys))
+    min_lookahead = 0
+    while slack(min_lookahead) < 0:
+        min_lookahead += 1
+    lookahead = min_lookahead if lookahead is None else int(lookahead)
+    if lookahead < min_lookahead:
+        raise ValueError(f"lookahead {lookahead} is too small at {frame_rate(fps)} fps: the pose of a source frame is read between two model "
+                         f"keyframes {P} model frames apart, which needs a lookahead of at least {min_lookahead} source frames")
+    a_m = min(max_lookahead(config), slack(lookahead))
+    D = 1 + max(((_newest_model_frame(q + lookahead, A, B) - a_m) // P * P - k[0]) // P for q, k in enumerate(keys))
+    if D > 4096:
+        raise ValueError(f"lookahead {lookahead} would keep {D} keyframes per slot; at most 4096")
+    return RatePlan(A, B, -(-A // B), a_m, D, min_lookahead, P, lookahead)
+
+
+def push_plan(j, plan):
+    """The host mirror of what a slot's j-th push (0-based) does under ``plan``: {"model": [(k, left, right, weight), ...] -- the model
+    frames the push makes, each with its two source frames and resample_plan's float64 weight (left == right: weight 0.0) --, "q": the
+    source frame whose pose comes out (None while j < lookahead), "k0", "k1": its two keyframes, "weight": the float64 output weight}."""
+    A, B, P = plan.A, plan.B, plan.pred_stride
+    j = int(j)
+    first = 0 if j == 0 else _newest_model_frame(j - 1, A, B) + 1
+    model = []
+    for k in range(first, _newest_model_frame(j, A, B) + 1):
+        left, rem = divmod(k * B, A)
+        model.append((k, left, left + (rem > 0), float(np.float64(rem) / np.float64(A))))
+    q = j - plan.lookahead
+    if q < 0:
+        return {"model": model, "q": None, "k0": None, "k1": None, "weight": None}
+    k0, k1, off, den = _output_keyframes(q, A, B, P)
+    return {"model": model, "q": q, "k0": k0, "k1": k1, "weight": float(np.float64(off) / np.float64(den))}
+
+
 def _check_resolutions(resolutions, slots):
     if resolutions is None:
         return None
@@ -116,7 +205,7 @@ def _check_resolutions(resolutions, slots):
 class StreamSession(object):
 
     def __init__(self, model, config, slots, resolutions=None, mask_stride=None, flip=None, lookahead=0, root_relative=True, graph=True,
-                 missed_detections=False):
+                 missed_detections=False, fps=None, model_fps=50):
         """``slots``: tracks served side by side (a slot is a track: ``reset`` starts a new one).  ``resolutions``: None = the coordinates
         are normalised already, else one (w, h) in pixels or one per slot.  ``mask_stride`` / ``flip`` / ``root_relative`` as
         ``predict.predict_tracks``.  ``lookahead`` = a: frames the answer may lag behind the newest one, 0 <= a <=
@@ -124,12 +213,20 @@ class StreamSession(object):
         per tick instead of enqueueing the five steps.  Models with generic dims have no frames form: NotImplementedError.
         ``missed_detections=True``: a pushed frame may be MISSING (``push(valid=...)``, or a row with a NaN / Inf coordinate) -- the slot's
         track still grows by that frame, but no window ever shows it to the network (``predict.predict_tracks(valid=...)``); the tick runs
-        uu3d_stream_stage_valid / uu3d_stream_commit_valid.  Needs a model with strided input (ValueError).  False: today's session."""
+        uu3d_stream_stage_valid / uu3d_stream_commit_valid.  Needs a model with strided input (ValueError).  False: today's session.
+        ``fps``: None = the pushed frames are at the model's rate (today's session, bit for bit).  Else the ONE rate of the session's source
+        frames, parsed by ``predict.frame_rate`` (int, ``Fraction``, ``(num, den)``, or a float read as
+        ``Fraction(f).limit_denominator(1001)``), against ``model_fps``: the module docstring's "Any frame rate".  ``lookahead`` then counts
+        SOURCE frames and must be at least ``rate_plan(...).min_lookahead`` (ValueError naming it); ``missed_detections`` flags are per
+        source frame, and a model frame is missing under uu3d_resample_tracks' rule: its left source frame is missing or, where it is mixed
+        from two, its right one.  ``captures`` counts captures of the sub-tick graph: 1 for the session's whole life -- the source push and
+        the timed emit around the replays are two plain launches, not captured."""
         slots, lookahead = int(slots), int(lookahead)
         if slots < 1:
             raise ValueError("slots >= 1")
         S, s_in, pred = session_strides(config, mask_stride)
-        if not 0 <= lookahead <= max_lookahead(config):
+        self.rate = None if fps is None else rate_plan(config, fps, lookahead, mask_stride, model_fps)
+        if self.rate is None and not 0 <= lookahead <= max_lookahead(config):
             raise ValueError(f"lookahead must be in [0, {max_lookahead(config)}] = (SEQUENCE_LENGTH // 2) * SEQUENCE_STRIDE, got {lookahead}")
         res = _check_resolutions(resolutions, slots)
         if not model.arch.compiled_dims:
@@ -146,7 +243,8 @@ class StreamSession(object):
         self.captures = 0                                             # hipGraph captures so far (graph=True: 1 for the session's whole life)
         a, dev = model.arch, model.device
         self._lib = lib = _capi.load_library()
-        self._cfg = _capi.Uu3dStreamConfig(slots, S, s_in, pred, lookahead, int(self.flip), int(config.PADDING_TYPE == "copy"),
+        self.model_lookahead = lookahead if self.rate is None else self.rate.a_m       # the lookahead of a (sub-)tick, in model frames
+        self._cfg = _capi.Uu3dStreamConfig(slots, S, s_in, pred, self.model_lookahead, int(self.flip), int(config.PADDING_TYPE == "copy"),
                                            int(config.ROOT_KEYTPOINT) if root_relative else -1)
         model._sync_from_trainer()
         lay = _capi.Uu3dStreamLayout()
@@ -154,8 +252,16 @@ class StreamSession(object):
         self.ring_capacity = int(lay.ring_capacity)
         T, J, N, dt, H = slots, a.num_keypoints, a.num_frames, a.d_temporal, 2 if self.flip else 1
         self._key = ("stream", id(self))
+        state_bytes = int(lay.bytes)
+        if self.rate is not None:
+            self._rate = _capi.Uu3dStreamRate(self.rate.A, self.rate.B, lookahead, self.rate.D)
+            rlay = _capi.Uu3dStreamRateLayout()
+            _capi.check(lib, lib.uu3d_stream_rate_state_layout(model._h, C.byref(self._cfg), C.byref(self._rate), C.byref(rlay)), model._h)
+            state_bytes = int(rlay.bytes)
+            self._src_host = np.zeros(slots, np.int64)                # host mirror of the source counters; exact where _src_known
+            self._src_known = np.ones(slots, bool)
         with torch.cuda.device(dev):
-            self._state = torch.zeros(int(lay.bytes), dtype=torch.uint8, device=dev)
+            self._state = torch.zeros(state_bytes, dtype=torch.uint8, device=dev)
             view = lambda off, n, dtype: self._state[off:off + n * 4].view(dtype)
             self._frames = view(int(lay.frames_offset), T, torch.int32)
             self._table = view(int(lay.table_offset), int(lay.table_rows) * dt, torch.float32).view(int(lay.table_rows), dt)
@@ -179,6 +285,13 @@ class StreamSession(object):
             self._full = torch.empty((H * T, N, J, 3), dtype=torch.float32, device=dev) if model._returns_full else None
             self._central = torch.zeros((H * T, J, 3), dtype=torch.float32, device=dev)
             self._out = torch.zeros((T, J, 3), dtype=torch.float32, device=dev)
+            # what a (sub-)tick takes as `active` and where its emit writes: with a rate the sub-ticks' own buffers, else the session's
+            self._tick_active, self._emit_out, self._emit_fresh = self._active, self._out, self._fresh
+            if self.rate is not None:
+                self._source_frames = view(int(rlay.source_frames_offset), T, torch.int32)
+                self._tick_active = torch.zeros((T,), dtype=torch.uint8, device=dev)
+                self._emit_out = torch.zeros((T, J, 3), dtype=torch.float32, device=dev)
+                self._emit_fresh = torch.zeros((T,), dtype=torch.uint8, device=dev)
             # a workspace of the session's own for uu3d_frame_features: the graph holds its address
             self._fws = torch.empty(max(int(lib.uu3d_frame_features_bytes(model._h, H * T)), int(lib.uu3d_frame_features_bytes(model._h, 1))),
                                     dtype=torch.uint8, device=dev)
@@ -201,7 +314,10 @@ class StreamSession(object):
 
     def _tick(self, stream):
         lib, m, cfg, st = self._lib, self.model, C.byref(self._cfg), C.c_void_p(stream.cuda_stream)
-        if self.missed_detections:
+        if self.rate is not None:
+            _capi.check(lib, lib.uu3d_stream_resample_stage(m._h, cfg, C.byref(self._rate), _ptr(self._state), _ptr(self._res), _ptr(self._order),
+                                                            _ptr(self._tick_active), _ptr(self._valid), _ptr(self._staged), st), m._h)
+        elif self.missed_detections:
             _capi.check(lib, lib.uu3d_stream_stage_valid(m._h, cfg, _ptr(self._kp), _ptr(self._res), _ptr(self._active), _ptr(self._order),
                                                          _ptr(self._valid_in), _ptr(self._valid), _ptr(self._staged), st), m._h)
         else:
@@ -209,15 +325,17 @@ class StreamSession(object):
                                                    _ptr(self._staged), st), m._h)
         self._features(self._staged, self._feats, stream)
         if self.missed_detections:
-            _capi.check(lib, lib.uu3d_stream_commit_valid(m._h, cfg, _ptr(self._state), _ptr(self._feats), _ptr(self._active), _ptr(self._valid),
-                                                          _ptr(self._valid_state), _ptr(self._rows), _ptr(self._mask), _ptr(self._fresh), st), m._h)
+            _capi.check(lib, lib.uu3d_stream_commit_valid(m._h, cfg, _ptr(self._state), _ptr(self._feats), _ptr(self._tick_active), _ptr(self._valid),
+                                                          _ptr(self._valid_state), _ptr(self._rows), _ptr(self._mask), _ptr(self._emit_fresh), st), m._h)
         else:
-            _capi.check(lib, lib.uu3d_stream_commit(m._h, cfg, _ptr(self._state), _ptr(self._feats), _ptr(self._active), _ptr(self._rows),
-                                                    _ptr(self._mask), _ptr(self._fresh), st), m._h)
+            _capi.check(lib, lib.uu3d_stream_commit(m._h, cfg, _ptr(self._state), _ptr(self._feats), _ptr(self._tick_active), _ptr(self._rows),
+                                                    _ptr(self._mask), _ptr(self._emit_fresh), st), m._h)
         # the latency schedule: what model.forward_frames takes (below 1024 token rows both schedules give the same bits)
         m._forward_frames(self._table, self._rows, self._mask if m.has_strided_input else None, self._full, self._central, self._key, stream)
-        _capi.check(lib, lib.uu3d_stream_emit(m._h, cfg, _ptr(self._state), _ptr(self._central), _ptr(self._order), _ptr(self._fresh),
-                                              _ptr(self._out), st), m._h)
+        _capi.check(lib, lib.uu3d_stream_emit(m._h, cfg, _ptr(self._state), _ptr(self._central), _ptr(self._order), _ptr(self._emit_fresh),
+                                              _ptr(self._emit_out), st), m._h)
+        if self.rate is not None:
+            _capi.check(lib, lib.uu3d_stream_file_keyframe(m._h, cfg, C.byref(self._rate), _ptr(self._state), _ptr(self._emit_fresh), st), m._h)
 
     def _capture(self):
         """One warm-up tick with every slot inactive (nothing advances), then the capture: a linear chain on one stream."""
@@ -265,6 +383,11 @@ class StreamSession(object):
         ``valid`` (slots,) flags or None (sessions built with ``missed_detections=True`` only): 0 = slot i's frame of this tick is MISSING, as
         is a row of ``kp2d`` with a NaN or Inf coordinate.  The slot's track grows by the frame all the same (``frames`` counts it; with
         ``active[i] == 0`` it would not) and a pose comes out by the usual rule, from windows that never read the missing frame.
+        A session with ``fps``: ``kp2d`` holds one SOURCE frame per slot; ``poses[i]`` is the pose of slot i's source frame
+        ``source_frames[i] - 1 - lookahead`` and ``fresh[i]`` is set at every push of an active slot once that index is >= 0.  The push
+        enqueues uu3d_stream_source_push, n replays of the one sub-tick graph and uu3d_stream_timed_emit; n is the largest number of model
+        frames an active slot makes at this push, known from a host mirror of the source counters.  ``active`` as a DEVICE tensor leaves the
+        mirror unknown: ceil(A / B) sub-ticks are replayed per push (the surplus ones change nothing) until every such slot has been reset.
         Enqueues on the current stream and returns; never waits for the device."""
         torch = self._torch
         m = self.model
@@ -296,11 +419,42 @@ class StreamSession(object):
             elif self.missed_detections and not self._valid_in_all:
                 self._valid_in.fill_(1)
                 self._valid_in_all = True
-            if self.graph:
+            if self.rate is not None:
+                self._push_source(active)
+            elif self.graph:
                 self._graph.replay()
             else:
                 self._tick(torch.cuda.current_stream(dev))
         return self._out, self._fresh.view(torch.bool)
+
+    def _sub_ticks(self, active):
+        """How many sub-ticks this push needs, advancing the host mirror of the source counters."""
+        torch = self._torch
+        r = self.rate
+        if isinstance(active, torch.Tensor) and active.is_cuda:
+            self._src_known[:] = False
+            return r.n_max
+        act = np.ones(self.slots, bool) if active is None else np.asarray(active.numpy() if isinstance(active, torch.Tensor) else active) != 0
+        n = r.n_max if (act & ~self._src_known).any() else 0
+        for i in np.flatnonzero(act & self._src_known):
+            j = int(self._src_host[i])
+            n = max(n, 1 if j == 0 else _newest_model_frame(j, r.A, r.B) - _newest_model_frame(j - 1, r.A, r.B))
+            self._src_host[i] = j + 1
+        return n
+
+    def _push_source(self, active):
+        """The push of a session with a rate: file the source frames, make the model frames that are due, read the poses."""
+        lib, m, cfg, rate = self._lib, self.model, C.byref(self._cfg), C.byref(self._rate)
+        cur = self._torch.cuda.current_stream(m.device)
+        st = C.c_void_p(cur.cuda_stream)
+        _capi.check(lib, lib.uu3d_stream_source_push(m._h, cfg, rate, _ptr(self._state), _ptr(self._kp), _ptr(self._active), _ptr(self._valid_in),
+                                                     int(self.missed_detections), st), m._h)
+        for _ in range(self._sub_ticks(active)):
+            if self.graph:
+                self._graph.replay()
+            else:
+                self._tick(cur)
+        _capi.check(lib, lib.uu3d_stream_timed_emit(m._h, cfg, rate, _ptr(self._state), _ptr(self._out), _ptr(self._fresh), st), m._h)
 
     def reset(self, slots=None):
         """The given slots (indices; None = all) start a new track: zero frames, held pose 0.  Stream-ordered like ``push``."""
@@ -313,12 +467,24 @@ class StreamSession(object):
                 h[np.asarray(slots, np.int64).reshape(-1)] = 1
                 mask = torch.from_numpy(h).pin_memory().to(m.device, non_blocking=True)
             st = C.c_void_p(torch.cuda.current_stream(m.device).cuda_stream)
-            _capi.check(self._lib, self._lib.uu3d_stream_reset(m._h, C.byref(self._cfg), _ptr(self._state), _ptr(mask), st), m._h)
+            if self.rate is None:
+                _capi.check(self._lib, self._lib.uu3d_stream_reset(m._h, C.byref(self._cfg), _ptr(self._state), _ptr(mask), st), m._h)
+                return
+            _capi.check(self._lib, self._lib.uu3d_stream_rate_reset(m._h, C.byref(self._cfg), C.byref(self._rate), _ptr(self._state), _ptr(mask), st),
+                        m._h)
+            which = slice(None) if slots is None else np.asarray(slots, np.int64).reshape(-1)
+            self._src_host[which] = 0
+            self._src_known[which] = True
 
     @property
     def frames(self):
-        """Frames pushed per slot since its last reset: the device counters themselves, (slots,) int32."""
+        """MODEL frames per slot since its last reset (without ``fps``: the frames pushed): the device counters themselves, (slots,) int32."""
         return self._frames
+
+    @property
+    def source_frames(self):
+        """Source frames pushed per slot since its last reset, (slots,) int32 on the device; without ``fps`` the same tensor as ``frames``."""
+        return self._frames if self.rate is None else self._source_frames
 
     def check_range(self):
         """Range guard of precision f16x3 for everything pushed so far, as ``ForwardPipeline.check_range()``: waits for the current stream,
@@ -341,11 +507,12 @@ class StreamSession(object):
             pass
 
 
-def replay_tracks(model, config, tracks, resolutions=None, mask_stride=None, flip=None, lookahead=0, root_relative=True, graph=True, valid=None):
+def replay_tracks(model, config, tracks, resolutions=None, mask_stride=None, flip=None, lookahead=0, root_relative=True, graph=True, valid=None, fps=None,
+                  model_fps=50):
     """Push complete tracks tick by tick, one slot per track (a slot is inactive once its track has ended) -> per track the pose the
     session returned at each of its ticks, (T_i, J, 3) float32, and the fresh flags (T_i,) bool, as host arrays.  One copy to the host,
     at the end.  ``valid`` as ``predict.predict_tracks``: None, "finite" (rows with a NaN / Inf coordinate are missing frames) or one (T_i,)
-    host array per track -- a session with ``missed_detections=True``."""
+    host array per track -- a session with ``missed_detections=True``.  ``fps`` / ``model_fps``: the rate of the tracks, as ``StreamSession``."""
     import torch
     lens = [int(len(t)) for t in tracks]
     T, ticks = len(tracks), max(lens)
@@ -357,7 +524,8 @@ def replay_tracks(model, config, tracks, resolutions=None, mask_stride=None, fli
     elif valid is not None and valid != "finite":
         raise ValueError('valid must be None, "finite" or a list with one (T_i,) array per track')
     s = StreamSession(model, config, T, resolutions=resolutions, mask_stride=mask_stride, flip=flip, lookahead=lookahead,
-                      root_relative=root_relative, graph=graph, **({} if valid is None else {"missed_detections": True}))
+                      root_relative=root_relative, graph=graph, **({} if valid is None else {"missed_detections": True}),
+                      **({} if fps is None else {"fps": fps, "model_fps": model_fps}))
     J = int(np.asarray(tracks[0]).shape[1])
     poses = torch.zeros((ticks, T, J, 3), dtype=torch.float32, device=model.device)
     fresh = torch.zeros((ticks, T), dtype=torch.bool, device=model.device)
@@ -394,7 +562,15 @@ def parse_args(argv=None):
                    help="image size in pixels of all tracks; without it the coordinates are taken as normalised already")
     p.add_argument("--mask_missing", action="store_true",
                    help="a frame with a NaN or Inf coordinate is a missed detection: the track grows by it, the network never sees it")
+    p.add_argument("--fps", type=_rate_argument, default=None, metavar="F",
+                   help="frame rate of the tracks, a float or NUM/DEN (29.97, 30000/1001); without it they are taken at the model's rate.  "
+                        "--lookahead then counts frames of the tracks")
     return p.parse_args(argv)
+
+
+def _rate_argument(text):
+    from .predict import _rate_argument as parse
+    return parse(text)
 
 
 def _load_model(config, weights_path):
@@ -414,11 +590,17 @@ def main(argv=None):
     for k, t in zip(names, tracks):
         if t.ndim != 3 or t.shape[2] != 2 or t.shape[1] != config.NUM_KEYPOINTS or t.shape[0] < 1:
             raise SystemExit(f"{args.input}[{k}] has shape {t.shape}, expected (T >= 1, {config.NUM_KEYPOINTS}, 2)")
-    if not 0 <= args.lookahead <= max_lookahead(config):
+    if args.fps is None and not 0 <= args.lookahead <= max_lookahead(config):
         raise SystemExit(f"--lookahead must be in [0, {max_lookahead(config)}]")
+    if args.fps is not None:
+        try:
+            rate_plan(config, args.fps, args.lookahead)
+        except ValueError as e:
+            raise SystemExit(f"--fps / --lookahead: {e}") from None
     model = _load_model(config, args.weights)
     poses, fresh = replay_tracks(model, config, tracks, resolutions=None if args.resolution is None else tuple(args.resolution),
-                                 lookahead=args.lookahead, **({"valid": "finite"} if args.mask_missing else {}))
+                                 lookahead=args.lookahead, **({"valid": "finite"} if args.mask_missing else {}),
+                                 **({} if args.fps is None else {"fps": args.fps}))
     out = {}
     for k, p, f in zip(names, poses, fresh):
         out[k] = np.asarray(p, np.float32)
