@@ -547,6 +547,41 @@ int uu3d_stream_rate_reset(uu3d_model* model, const uu3d_stream_config* cfg, con
                            const uint8_t* slot_mask_dev, void* stream);
 
 /*
+ * ... with an output rate of its own (stream.StreamSession(fps=F, out_fps=G)): every push returns EVERY output frame that became due, not
+ * one pose.  Output frame i of a slot lies at time i / G, model position u = i * model_fps / G = i pos_num / pos_den, and is read from
+ * the piecewise-linear motion through the emitted keyframes exactly as uu3d_stream_timed_emit reads a source frame: k0 = floor(u / P) P,
+ * u == k0 gives keyframe k0's bits, anything else (float)((double)p0 * (1.0 - w) + (double)p1 * w), w = (double)(i pos_num - k0 pos_den) /
+ * (double)(P pos_den).  With G / F = c / d in lowest terms: after the push that made source frame j the newest of a slot, q = j -
+ * rate->lookahead >= 0, the slot has emitted every output frame i <= floor(q c / d) -- the frames whose time is not later than that of
+ * source frame q.  A push returns the ones that became due at it, oldest first: frame 0 alone at q == 0, afterwards floor(q c / d) -
+ * floor((q - 1) c / d) of them, at most max_out = ceil(c / d) <= 64, possibly none when G < F; a slot that took no frame returns none.
+ * uu3d_stream_out holds c, d, pos_num, pos_den (all in [1, 2^20)) and max_out.  The input and model sides, the lookahead a_m and the
+ * rule of the keyframe ring are those above; the ring depth rate->key_ring must also cover the OLDEST output frame of a push, whose k0 can
+ * be one keyframe older than that of source frame q (stream.rate_plan enumerates one common period of the three grids).
+ *
+ * Per push: uu3d_stream_source_push, the sub-ticks, then IN PLACE OF uu3d_stream_timed_emit
+ *   uu3d_stream_timed_emit_multi(model, cfg, rate, out, state_dev, poses_dev (slots, max_out, J, 3) f32, 16-byte aligned,
+ *                                count_dev (slots) i32, stream)
+ *       one workgroup per slot; the slot's output counter is read by that workgroup only and advanced by one lane behind a barrier.
+ *       n = floor(q c / d) + 1 - counter, clamped to [0, max_out] (0 for a slot that took no frame or with q < 0); rows r < n of the
+ *       slot are output frames counter + r, rows r >= n are zeros, count[slot] = n, counter += n (it stops at INT32_MAX instead of
+ *       wrapping).  16-byte stores wherever a quad of floats lies inside the slot's rows.  No atomics, one writer per output element.
+ *   uu3d_stream_out_reset(model, cfg, rate, out, state_dev, slot_mask_dev or NULL, stream) = uu3d_stream_rate_reset and, for the same
+ *       slots, output counter 0.
+ * State: uu3d_stream_out_state_layout -- the block of uu3d_stream_rate_state_layout, unchanged, with the output counters (slots) i32
+ * behind it at out_frames_offset; bytes is the size of the WHOLE block, all zeros = every slot empty.  A session without an output rate
+ * needs none of this and its layout is the one above.
+ */
+typedef struct uu3d_stream_out { int32_t c, d /* G / F */, pos_num, pos_den /* model_fps / G */, max_out /* R */; } uu3d_stream_out;
+typedef struct uu3d_stream_out_layout { int64_t out_frames_offset, bytes; } uu3d_stream_out_layout;
+int uu3d_stream_out_state_layout(const uu3d_model* model, const uu3d_stream_config* cfg, const uu3d_stream_rate* rate,
+                                 const uu3d_stream_out* out, uu3d_stream_out_layout* layout);
+int uu3d_stream_timed_emit_multi(uu3d_model* model, const uu3d_stream_config* cfg, const uu3d_stream_rate* rate, const uu3d_stream_out* out,
+                                 void* state_dev, float* poses_dev, int32_t* count_dev, void* stream);
+int uu3d_stream_out_reset(uu3d_model* model, const uu3d_stream_config* cfg, const uu3d_stream_rate* rate, const uu3d_stream_out* out,
+                          void* state_dev, const uint8_t* slot_mask_dev, void* stream);
+
+/*
  * Per-kernel timing of the next uu3d_forward calls with HIP events on the launch stream.
  * When enabled, uu3d_forward records an event pair around every launch; uu3d_profile_read
  * synchronises those events and returns the per-launch records of the LAST forward.

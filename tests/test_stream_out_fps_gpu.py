@@ -1,0 +1,325 @@
+"""GPU: stream.StreamSession(fps=F, out_fps=G) -- one source frame in, EVERY due pose out -- against what it is defined to be: the
+piecewise-linear motion through the keyframes a plain session at the model lookahead a_m emits for the model-rate frames, read on the
+output grid by stream.out_push_plan (evaluation.keyframe_plan_at's rule).  Three slots, flip on, pixel tracks at three resolutions, seeded
+weights.  A keyframe's pose must come back bit for bit; a mixed one within one float32 ulp of the float64 mix rounded to float32 -- the
+device rounds once, and a float64 contraction in front of that rounding can move the float32 result by at most one ulp."""
+import math
+
+import numpy as np
+import pytest
+
+import uplift_upsample_3dhpe_amd as pkg
+from tests import util
+
+torch = pytest.importorskip("torch")
+pytestmark = pytest.mark.gpu
+RES = [(1000, 1002), (1920, 1080), (640, 480)]
+T, J = 3, 17
+_MODELS = {}
+
+
+def _bits(a):
+    a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def _pixel_tracks(lens, seed):
+    rng = np.random.default_rng(seed)
+    return [(rng.uniform(0.0, 1.0, size=(n, J, 2)) * np.array(RES[i % len(RES)], np.float64)).astype(np.float32) for i, n in enumerate(lens)]
+
+
+def _model(cfgname, seed=2):
+    if cfgname not in _MODELS:
+        cfg = util.load_config(cfgname)
+        cfg.BATCH_SIZE = 64
+        arch = pkg.arch_from_config(cfg)
+        w = pkg.init_weights(arch, seed=seed, perturb=0.1)
+        _MODELS[cfgname] = (cfg, arch, w, pkg.build_uplift_upsample_transformer(cfg, weights=w))
+    return _MODELS[cfgname]
+
+
+def _run(session, tracks, ticks, active=None, before_tick=None, valid=None, device_active=False):
+    """Push ``tracks[i][k]`` into slot i at push k; a slot's frame is the next one of ITS track.  ``active(k)`` -> (T,) bools or None;
+    ``valid[i]``: per-frame flags of track i.  One copy to the host at the end.  A session without ``out_fps`` -> (poses (ticks, T, J, 3),
+    fresh (ticks, T)); with it -> (poses (ticks, T, R, J, 3), count (ticks, T), out_frames after the push (ticks, T)); ``check_range()`` is
+    False and ``captures`` is 1 throughout."""
+    multi = session.max_out is not None
+    poses = torch.zeros((ticks, T) + ((session.max_out,) if multi else ()) + (J, 3), dtype=torch.float32, device="cuda")
+    flags = torch.zeros((ticks, T), dtype=torch.int32 if multi else torch.bool, device="cuda")
+    total = torch.zeros((ticks, T), dtype=torch.int32, device="cuda")
+    used = [0] * T
+    for k in range(ticks):
+        if before_tick is not None:
+            before_tick(k, used)
+        act = None if active is None else np.asarray(active(k), bool)
+        kp = np.zeros((T, J, 2), np.float32)
+        ok = np.ones(T, bool)
+        for i in range(T):
+            if act is None or act[i]:
+                kp[i] = tracks[i][used[i]]
+                if valid is not None:
+                    ok[i] = bool(valid[i][used[i]])
+                used[i] += 1
+        a = act if act is None or not device_active else torch.from_numpy(act).cuda()
+        p, f = session.push(kp, a, **({} if valid is None else {"valid": ok}))
+        assert tuple(p.shape) == tuple(poses.shape[1:]) and p.is_cuda and f.is_cuda and session.captures == 1
+        poses[k].copy_(p)
+        flags[k].copy_(f)
+        if multi:
+            total[k].copy_(session.out_frames)
+        if k % 64 == 63:
+            assert session.check_range() is False
+    assert session.check_range() is False and session.captures == 1
+    return (poses.cpu().numpy(), flags.cpu().numpy()) + ((total.cpu().numpy(),) if multi else ())
+
+
+def _model_rate_frames(tracks, fps, n_model, valid=None):
+    """The first ``n_model`` model-rate frames of every track (uu3d_resample_tracks), normalised -> list of (n_model, J, 2) host arrays
+    (and, with ``valid``, their flags)."""
+    from uplift_upsample_3dhpe_amd import predict
+    table, model_lens, _ = predict.resampled_pose_table(tracks, torch.device("cuda", 0), fps, resolutions=RES[:len(tracks)], valid=valid)
+    assert (model_lens >= n_model).all()
+    kp = torch.split(table.kp2d, [int(n) for n in model_lens], 0)
+    frames = [t[:n_model].cpu().numpy() for t in kp]
+    if valid is None:
+        return frames
+    return frames, [v[:n_model].cpu().numpy() != 0 for v in torch.split(table.valid, [int(n) for n in model_lens], 0)]
+
+
+def _plain_keyframes(model, cfg, ms, a_m, frames):
+    """The model-rate frames through a plain session at lookahead a_m -> {centre: (T, J, 3) pose}."""
+    from uplift_upsample_3dhpe_amd import stream
+    s = stream.StreamSession(model, cfg, slots=T, resolutions=None, mask_stride=ms, flip=True, lookahead=a_m)
+    n = len(frames[0])
+    poses, fresh = _run(s, frames, n)
+    s.close()
+    keys = {}
+    for t in range(n):
+        if fresh[t].all():
+            keys[t - a_m] = poses[t]
+        else:
+            assert not fresh[t].any()
+    return keys
+
+
+def _check_slot(plan, keys, slot, ticks, poses, counts, total, first_push=0):
+    """Slot ``slot`` took its pushes first_push, first_push + 1, ... (counted since its last reset) at the ticks ``ticks``: count, out_frames
+    and every row against out_push_plan and the keyframes ``keys[centre][slot]`` -> (rows that are a keyframe's bits, mixed rows, the
+    worst error of a mixed row in ulps, the counts seen)."""
+    from uplift_upsample_3dhpe_amd import stream
+    exact = mixed = 0
+    worst, seen = 0.0, set()
+    for j, k in enumerate(ticks, first_push):
+        frames = stream.out_push_plan(j, plan)
+        seen.add(len(frames))
+        assert counts[k, slot] == len(frames) <= plan.max_out, (j, k)
+        assert total[k, slot] == (0 if j < plan.lookahead else ((j - plan.lookahead) * plan.out_c) // plan.out_d + 1), (j, k)
+        assert not poses[k, slot, len(frames):].any()                    # rows r >= count are zeros
+        for r, (i, k0, k1, w) in enumerate(frames):
+            assert i == total[k, slot] - counts[k, slot] + r
+            got = poses[k, slot, r]
+            if k0 == k1:
+                exact += 1
+                assert np.array_equal(_bits(got), _bits(keys[k0][slot])), (j, i)
+            else:
+                mixed += 1
+                a, b = keys[k0][slot].astype(np.float64), keys[k1][slot].astype(np.float64)
+                want = (a * (1.0 - np.float64(w)) + b * np.float64(w)).astype(np.float32)
+                err = np.abs(got.astype(np.float64) - want.astype(np.float64)) / np.spacing(np.abs(want))
+                worst = max(worst, float(err.max()))
+                assert (err <= 1.0).all(), (j, i)
+    return exact, mixed, worst, seen
+
+
+def _source_frames_for(cfg, ms, plan):
+    """Enough source frames that the session's keyframe ring (D poses) and the plain session's feature ring both wrap at least twice."""
+    from uplift_upsample_3dhpe_amd import stream
+    cap = stream.ring_capacity(cfg, ms, plan.a_m)
+    model = max(2 * cap * ms + 12, 2 * plan.D * plan.pred_stride + plan.a_m + 12)
+    return plan.lookahead + math.ceil(model * plan.B / plan.A) + 1
+
+
+@pytest.mark.parametrize("fps", [30, 24])
+def test_equal_rates_are_the_fps_only_session(fps):
+    """out_fps == fps on h36m_81: count is 1 exactly where the fps-only session's fresh is set, and row 0 is its pose, bit for bit."""
+    from uplift_upsample_3dhpe_amd import stream
+    cfg, arch, w, model = _model("h36m_81")
+    ms = 4
+    L = stream.rate_plan(cfg, fps, None, ms).min_lookahead + 2
+    plan = stream.rate_plan(cfg, fps, L, ms, out_fps=fps)
+    n_src = max(150, _source_frames_for(cfg, ms, plan))
+    tracks = _pixel_tracks([n_src] * T, seed=161)
+    active = lambda k: [True, not 40 <= k < 44, True]
+    a = stream.StreamSession(model, cfg, slots=T, resolutions=RES, mask_stride=ms, flip=True, lookahead=L, fps=fps)
+    pa, fa = _run(a, tracks, n_src, active=active)
+    a.close()
+    b = stream.StreamSession(model, cfg, slots=T, resolutions=RES, mask_stride=ms, flip=True, lookahead=L, fps=fps, out_fps=fps)
+    assert b.rate == plan and b.max_out == 1 and 2 * plan.D * plan.pred_stride < b.rate.A * n_src // b.rate.B
+    pb, cb, tb = _run(b, tracks, n_src, active=active)
+    assert b.source_frames.cpu().tolist() == [n_src, n_src - 4, n_src] and b.out_frames.cpu().tolist() == [n_src - L, n_src - 4 - L, n_src - L]
+    b.close()
+    assert np.array_equal(cb == 1, fa) and np.array_equal(cb != 0, fa) and fa.sum() == 3 * (n_src - L) - 4
+    assert np.array_equal(_bits(pb[:, :, 0][fa]), _bits(pa[fa])) and not pb[:, :, 0][~fa].any()
+    assert np.abs(pa[fa]).max() > 1e-3
+
+
+def test_pure_upsampling_10_to_50():
+    """h36m_351 at input stride 5 (s_in F / 50 = 1: every source frame IS an input keyframe), 10 fps in, 50 out: 5 poses per push."""
+    from uplift_upsample_3dhpe_amd import stream
+    cfgname, ms, fps, out_fps = "h36m_351", 5, 10, 50
+    cfg, arch, w, model = _model(cfgname)
+    L = stream.rate_plan(cfg, fps, None, ms).min_lookahead + 1
+    plan = stream.rate_plan(cfg, fps, L, ms, out_fps=out_fps)
+    assert (plan.A, plan.B, plan.out_c, plan.out_d, plan.pos_num, plan.pos_den, plan.max_out, plan.pred_stride) == (5, 1, 5, 1, 1, 1, 5, 5)
+    n_src = _source_frames_for(cfg, ms, plan)
+    n_model = (n_src - 1) * 5 + 1
+    tracks = _pixel_tracks([n_src] * T, seed=171)
+    keys = _plain_keyframes(model, cfg, ms, plan.a_m, _model_rate_frames(tracks, fps, n_model))
+    s = stream.StreamSession(model, cfg, slots=T, resolutions=RES, mask_stride=ms, flip=True, lookahead=L, fps=fps, out_fps=out_fps)
+    assert s.rate == plan and s.max_out == 5 and 2 * plan.D * plan.pred_stride < n_model
+    poses, counts, total = _run(s, tracks, n_src)
+    assert s.source_frames.cpu().tolist() == [n_src] * T and s.frames.cpu().tolist() == [n_model] * T
+    s.close()
+    assert not counts[:L].any() and (counts[L] == 1).all() and (counts[L + 1:] == 5).all() and n_src - L - 1 >= 60
+    assert np.isfinite(poses).all() and not poses[:, :, :, cfg.ROOT_KEYTPOINT].any()
+    for slot in range(T):
+        exact, mixed, worst, _ = _check_slot(plan, keys, slot, range(n_src), poses, counts, total)
+        assert exact == n_src - L and mixed == 4 * (n_src - L - 1)      # (every fifth output frame is a keyframe)
+    print(f"{cfgname} s_in {ms}, {fps} -> {out_fps} fps, lookahead {L} (a_m {plan.a_m}, D {plan.D}): {n_src} pushes, {exact} keyframe rows "
+          f"bit-identical, {mixed} mixed rows within {worst:.2f} ulp")
+
+
+@pytest.mark.parametrize("fps,out_fps,want_counts", [(25, 30, {0, 1, 2}), (30, 24, {0, 1})])
+def test_mixed_and_downsampling_rates(fps, out_fps, want_counts):
+    """h36m_81 at input stride 4: 25 -> 30 fps returns 1 or 2 poses per push, 30 -> 24 fps returns 1 or none (and none before the
+    lookahead has passed)."""
+    from uplift_upsample_3dhpe_amd import stream
+    cfgname, ms = "h36m_81", 4
+    cfg, arch, w, model = _model(cfgname)
+    L = stream.rate_plan(cfg, fps, None, ms).min_lookahead + 3
+    plan = stream.rate_plan(cfg, fps, L, ms, out_fps=out_fps)
+    n_src = max(150, _source_frames_for(cfg, ms, plan))
+    n_model = (n_src - 1) * plan.A // plan.B + 1
+    tracks = _pixel_tracks([n_src] * T, seed=181)
+    keys = _plain_keyframes(model, cfg, ms, plan.a_m, _model_rate_frames(tracks, fps, n_model))
+    s = stream.StreamSession(model, cfg, slots=T, resolutions=RES, mask_stride=ms, flip=True, lookahead=L, fps=fps, out_fps=out_fps)
+    assert s.rate == plan and s.max_out == plan.max_out == math.ceil(out_fps / fps) and 2 * plan.D * plan.pred_stride < n_model
+    poses, counts, total = _run(s, tracks, n_src)
+    s.close()
+    assert np.isfinite(poses).all()
+    for slot in range(T):
+        exact, mixed, worst, seen = _check_slot(plan, keys, slot, range(n_src), poses, counts, total)
+        assert seen == want_counts and exact >= 4 and mixed >= 20
+        if out_fps < fps:
+            assert 0 in set(counts[L:, slot].tolist())                  # a push past the lookahead that returns none
+    assert total[-1].tolist() == [(n_src - 1 - L) * out_fps // fps + 1] * T
+    print(f"{cfgname} s_in {ms}, {fps} -> {out_fps} fps, lookahead {L} (a_m {plan.a_m}, D {plan.D}): {n_src} pushes, {exact} keyframe rows "
+          f"bit-identical, {mixed} mixed rows within {worst:.2f} ulp")
+
+
+@pytest.mark.parametrize("cfgname,ms,fps,out_fps", [("h36m_81", 4, 30, 60), ("h36m_351", 5, 10, 50)])
+def test_against_predict_tracks(cfgname, ms, fps, out_fps):
+    """replay_tracks(out_fps=G) against predict_tracks(fps=F, out_fps=G) on the whole track, at the smallest lookahead for which
+    a_m = (SEQUENCE_LENGTH // 2) * SEQUENCE_STRIDE: every window of the session is complete.  Every frame the session emits has
+    k1 + a_m <= the newest model frame, so the offline windows of its two keyframes end inside the track as well: no padded window at the
+    track's end is involved, and the comparison covers everything the session returned."""
+    from uplift_upsample_3dhpe_amd import predict, stream
+    cfg, arch, w, model = _model(cfgname)
+    lo = stream.rate_plan(cfg, fps, None, ms).min_lookahead
+    L = next(la for la in range(lo, lo + 400) if stream.rate_plan(cfg, fps, la, ms).a_m == stream.max_lookahead(cfg))
+    plan = stream.rate_plan(cfg, fps, L, ms, out_fps=out_fps)
+    lens = [L + 45, L + 38, L + 30]
+    tracks = _pixel_tracks(lens, seed=191)
+    got, counts = stream.replay_tracks(model, cfg, tracks, resolutions=RES, mask_stride=ms, flip=True, lookahead=L, fps=fps, out_fps=out_fps)
+    want = predict.predict_tracks(model, cfg, tracks, resolutions=RES, mask_stride=ms, flip=True, fps=fps, out_fps=out_fps)
+    worst = 0.0
+    for i, n in enumerate(lens):
+        n_out = (n - 1 - L) * out_fps // fps + 1
+        assert got[i].shape == (n_out, J, 3) and counts[i].shape == (n,) and counts[i].sum() == n_out and n_out >= 50
+        assert counts[i].tolist() == [len(stream.out_push_plan(j, plan)) for j in range(n)]
+        ref = want[i][:n_out].cpu().numpy()
+        worst = max(worst, float(np.abs(got[i] - ref).max()))
+        assert float(np.abs(got[i]).max()) > 1e-3 and got[i].any(axis=(1, 2)).all()      # (poses, not zeros)
+    print(f"{cfgname} {fps} -> {out_fps} fps, lookahead {L} (a_m {plan.a_m}): max-abs to predict_tracks {worst:.3e} (bar {util.TOL_MAX_ABS})")
+    assert worst <= util.TOL_MAX_ABS
+
+
+def test_staggered_slots_pause_and_reset():
+    """h36m_81, 25 -> 30 fps: slot 2 starts at push 23, slot 1 pauses for pushes 50 .. 56 (count 0, zero rows), slot 0 is reset at push 71
+    (out_frames restarts at 0).  Every slot's output equals, bit for bit, that of a fresh session of the same shape in which its track
+    runs alone in the same slot -- one slot live, the others never active -- and the run with ``active`` as a device tensor gives the
+    bits of the run with host flags."""
+    from uplift_upsample_3dhpe_amd import stream
+    cfg, arch, w, model = _model("h36m_81")
+    ticks, start2, reset0 = 120, 23, 71
+    pause1 = lambda k: 50 <= k < 57
+    tracks = _pixel_tracks([ticks] * T, seed=201)
+    new = lambda: stream.StreamSession(model, cfg, slots=T, resolutions=RES, mask_stride=4, flip=True, lookahead=6, fps=25, out_fps=30)
+    active = lambda k: [True, not pause1(k), k >= start2]
+    runs = []
+    for device_active in (False, True):
+        s = new()
+        plan = s.rate
+
+        def before(k, used):
+            if k == reset0:
+                s.reset([0])
+        runs.append(_run(s, tracks, ticks, active=active, before_tick=before, device_active=device_active))
+        assert s.source_frames.cpu().tolist() == [ticks - reset0, ticks - 7, ticks - start2]
+        assert s.out_frames.cpu().tolist() == [(n - 1 - 6) * 6 // 5 + 1 for n in (ticks - reset0, ticks - 7, ticks - start2)]
+        s.close()
+    (poses, counts, total), (pd, cd, td) = runs
+    assert np.array_equal(cd, counts) and np.array_equal(td, total) and np.array_equal(_bits(pd), _bits(poses))
+    assert not counts[:start2, 2].any() and not poses[:start2, 2].any() and not total[:start2, 2].any()
+    assert not counts[50:57, 1].any() and not poses[50:57, 1].any() and (total[50:57, 1] == total[49, 1]).all() and total[49, 1] > 40
+    assert total[reset0 - 1, 0] == (reset0 - 1 - 6) * 6 // 5 + 1 and not total[reset0:reset0 + 6, 0].any() and total[reset0 + 6, 0] == 1
+    for slot, when, f0 in ((0, range(0, reset0), 0), (0, range(reset0, ticks), reset0), (1, [k for k in range(ticks) if not pause1(k)], 0),
+                           (2, range(start2, ticks), 0)):
+        when = list(when)
+        alone = new()
+        tr = [None] * T
+        tr[slot] = tracks[slot][f0:f0 + len(when)]
+        p, c, t = _run(alone, tr, len(when), active=lambda k: [i == slot for i in range(T)])
+        alone.close()
+        others = [i for i in range(T) if i != slot]
+        assert np.array_equal(c[:, slot], counts[when, slot]) and np.array_equal(t[:, slot], total[when, slot]) and c[:, slot].sum() > 30
+        assert not c[:, others].any() and not p[:, others].any()
+        assert set(c[6:, slot].tolist()) == {1, 2}
+        assert np.array_equal(_bits(p[:, slot]), _bits(poses[when, slot])), slot
+
+
+def test_missed_detections_30_to_60():
+    """h36m_351 at 30 fps (A / B = 5 / 3, P = 5: every keyframe is the pose of a source frame, so the fps=30 session with
+    missed_detections=True returns every keyframe's bits), NaN rows and explicit flags per SOURCE frame.  The 60 fps session's rows are
+    those keyframes, interpolated by the two rules."""
+    from uplift_upsample_3dhpe_amd import stream
+    cfgname, ms, fps, out_fps = "h36m_351", 5, 30, 60
+    cfg, arch, w, model = _model(cfgname)
+    L = stream.rate_plan(cfg, fps, None, ms).min_lookahead + 2
+    plan = stream.rate_plan(cfg, fps, L, ms, out_fps=out_fps)
+    assert (plan.A, plan.B, plan.pred_stride, plan.max_out) == (5, 3, 5, 2)
+    n_src, more = 200, 9                                                  # (the reference runs `more` pushes longer: it returns k1 later)
+    tracks = _pixel_tracks([n_src + more] * T, seed=211)
+    rng = np.random.default_rng(212)
+    flags = [rng.uniform(size=n_src + more) > 0.15 for _ in range(T)]
+    for i in range(T):
+        flags[i][[0, 3 + i]] = [i != 1, False]
+        tracks[i][rng.choice(n_src, 12, replace=False), rng.integers(0, J, 12), 0] = np.nan      # missing by the finite test alone
+    ref = stream.StreamSession(model, cfg, slots=T, resolutions=RES, mask_stride=ms, flip=True, lookahead=L, fps=fps, missed_detections=True)
+    rp, rf = _run(ref, tracks, n_src + more, valid=flags)
+    ref.close()
+    keys = {}
+    for j in range(L, n_src + more):
+        pp = stream.push_plan(j, plan)
+        assert rf[j].all()
+        if pp["k0"] == pp["k1"]:
+            keys[pp["k0"]] = rp[j]
+    assert sorted(keys) == list(range(0, 5 * len(keys), 5))
+    s = stream.StreamSession(model, cfg, slots=T, resolutions=RES, mask_stride=ms, flip=True, lookahead=L, fps=fps, out_fps=out_fps,
+                             missed_detections=True)
+    poses, counts, total = _run(s, tracks, n_src, valid=flags)
+    s.close()
+    assert np.isfinite(poses).all() and (counts[L + 1:] == 2).all()
+    for slot in range(T):
+        exact, mixed, worst, _ = _check_slot(plan, keys, slot, range(n_src), poses, counts, total)
+        assert exact >= 60 and mixed >= 250

@@ -3,10 +3,12 @@ way to get the same pose without it: the host builds this tick's window and stri
 uploads them with their mirrored copies and calls ``model([x, mask])`` once -- the spatial stack over all frames of every window, every tick.
 A tick = host clock from the call to the synchronised result (a live consumer reads every pose); host input in all three variants.
 Median (and 90th percentile) over --ticks ticks after --warmup ticks, per config and slot count.
-   python tools/stream_bench.py [--slots 1,8,64] [--cases h36m_81:4,h36m_351:5] [--ticks 300] [--warmup 60] [--lookahead 0] [--fps F]
+   python tools/stream_bench.py [--slots 1,8,64] [--cases h36m_81:4,h36m_351:5] [--ticks 300] [--warmup 60] [--lookahead 0] [--fps F [--out_fps G]]
 --fps F (a float or NUM/DEN): microseconds per PUSH of StreamSession(fps=F) -- one source frame in, one pose out, on average
 model_fps / F sub-ticks -- next to the plain session pushed at the model's rate (the cost of one model tick); the lookahead is raised to
-the smallest one the rate allows.  The numpy baseline is left out."""
+the smallest one the rate allows.  The numpy baseline is left out.
+--out_fps G (with --fps): the push of StreamSession(fps=F, out_fps=G) -- every due pose per push, up to ceil(G / F) -- as out_fps_graph_us,
+next to the fps-only push (one pose per push) and the plain session."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -19,7 +21,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=60)
     ap.add_argument("--lookahead", type=int, default=0)
     ap.add_argument("--fps", default=None)
+    ap.add_argument("--out_fps", default=None)
     args = ap.parse_args()
+    if args.out_fps is not None and args.fps is None:
+        ap.error("--out_fps needs --fps")
     import numpy as np, torch
     import uplift_upsample_3dhpe_amd as pkg
     from uplift_upsample_3dhpe_amd import synthetic as util
@@ -90,6 +95,10 @@ def main():
                 plan = stream.rate_plan(cfg, args.fps, la, ms)
                 row.update(fps=args.fps, lookahead=la, model_lookahead=plan.a_m, sub_ticks_per_push=round(plan.A / plan.B, 4))
                 variants = (("fps_graph", lambda: session(True, fps=args.fps, lookahead=la)), ("graph", lambda: session(True)))
+                if args.out_fps is not None:
+                    out_plan = stream.rate_plan(cfg, args.fps, la, ms, out_fps=args.out_fps)
+                    row.update(out_fps=args.out_fps, max_out=out_plan.max_out, key_ring=out_plan.D)
+                    variants = (("out_fps_graph", lambda: session(True, fps=args.fps, out_fps=args.out_fps, lookahead=la)),) + variants
             for key, fn in variants:
                 ts = np.asarray(fn())
                 row[key + "_us"] = round(1e6 * float(np.median(ts)), 1)
@@ -98,6 +107,8 @@ def main():
                 row["speedup_vs_baseline"] = round(row["baseline_us"] / row["graph_us"], 2)
             else:
                 row["push_over_model_tick"] = round(row["fps_graph_us"] / row["graph_us"], 2)
+                if args.out_fps is not None:
+                    row["out_fps_minus_fps_us"] = round(row["out_fps_graph_us"] - row["fps_graph_us"], 1)
             row["device"] = torch.cuda.get_device_name(0)
             print(json.dumps(row), flush=True)
             results.append(row)

@@ -38,6 +38,7 @@ EXPORTED_SYMBOLS = (
     "uu3d_resample_tracks",
     "uu3d_stream_rate_state_layout", "uu3d_stream_source_push", "uu3d_stream_resample_stage", "uu3d_stream_file_keyframe",
     "uu3d_stream_timed_emit", "uu3d_stream_rate_reset",
+    "uu3d_stream_out_state_layout", "uu3d_stream_timed_emit_multi", "uu3d_stream_out_reset",
 )
 # include/uu3d_ops.h
 OPS_SYMBOLS = (
@@ -97,6 +98,14 @@ class Uu3dStreamRate(C.Structure):
 class Uu3dStreamRateLayout(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("source_frames_offset", "pushed_offset", "source_valid_offset", "source_offset", "keys_offset",
                                          "key_stride", "out_held_offset", "bytes")]
+
+
+class Uu3dStreamOut(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("c", "d", "pos_num", "pos_den", "max_out")]
+
+
+class Uu3dStreamOutLayout(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("out_frames_offset", "bytes")]
 
 
 # void (*uu3d_grad_ready_fn)(void* user, int64_t first, int64_t count, void* stream)
@@ -205,6 +214,13 @@ def load_library(path=None):
     lib.uu3d_stream_timed_emit.argtypes = [vp, scfg, srate, vp, vp, vp, vp]
     lib.uu3d_stream_rate_reset.restype = C.c_int
     lib.uu3d_stream_rate_reset.argtypes = [vp, scfg, srate, vp, vp, vp]
+    sout = C.POINTER(Uu3dStreamOut)
+    lib.uu3d_stream_out_state_layout.restype = C.c_int
+    lib.uu3d_stream_out_state_layout.argtypes = [vp, scfg, srate, sout, C.POINTER(Uu3dStreamOutLayout)]
+    lib.uu3d_stream_timed_emit_multi.restype = C.c_int
+    lib.uu3d_stream_timed_emit_multi.argtypes = [vp, scfg, srate, sout, vp, vp, vp, vp]
+    lib.uu3d_stream_out_reset.restype = C.c_int
+    lib.uu3d_stream_out_reset.argtypes = [vp, scfg, srate, sout, vp, vp, vp]
     lib.uu3d_stream_valid_bytes.restype = sz
     lib.uu3d_stream_valid_bytes.argtypes = [vp, scfg]
     lib.uu3d_stream_stage_valid.restype = C.c_int

@@ -818,6 +818,57 @@ int uu3d_stream_rate_reset(uu3d_model* m, const uu3d_stream_config* s, const uu3
     return hipGetLastError() == hipSuccess ? UU3D_OK : fail(m, UU3D_ERR_HIP, "uu3d_stream_rate_reset: launch failed");
 }
 
+// ---- a live session with an output rate of its own (StreamSession(fps=F, out_fps=G)): every due pose per push ----
+namespace {
+const char* stream_out_error(const uu3d_stream_out* o) {
+    if (!o) return "null uu3d_stream_out";
+    if (o->c < 1 || o->c >= (1 << 20) || o->d < 1 || o->d >= (1 << 20)) return "c and d must be in [1, 2^20)";
+    if (o->pos_num < 1 || o->pos_num >= (1 << 20) || o->pos_den < 1 || o->pos_den >= (1 << 20)) return "pos_num and pos_den must be in [1, 2^20)";
+    if (o->max_out < 1 || o->max_out > 64 || (long)o->max_out * o->d < o->c) return "max_out must be in [ceil(c / d), 64]";
+    return nullptr;
+}
+OutParams out_params(const uu3d_stream_out* o) { return OutParams{o->c, o->d, o->pos_num, o->pos_den, o->max_out}; }
+}  // namespace
+
+int uu3d_stream_out_state_layout(const uu3d_model* mc, const uu3d_stream_config* s, const uu3d_stream_rate* r, const uu3d_stream_out* o,
+                                 uu3d_stream_out_layout* out) {
+    auto* m = const_cast<uu3d_model*>(mc);
+    if (!m || !out) return UU3D_ERR_INVALID_ARGUMENT;
+    if (const int st = stream_check(m, s, "uu3d_stream_out_state_layout")) return st;
+    if (const char* e = stream_rate_error(r)) return fail(m, UU3D_ERR_INVALID_ARGUMENT, std::string("uu3d_stream_out_state_layout: ") + e);
+    if (const char* e = stream_out_error(o)) return fail(m, UU3D_ERR_INVALID_ARGUMENT, std::string("uu3d_stream_out_state_layout: ") + e);
+    const RateLayout R = rate_layout(stream_layout_of(m, s), m->cfg.num_keypoints, r->key_ring);
+    out->out_frames_offset = (int64_t)out_frames_offset(R); out->bytes = (int64_t)out_layout_bytes(R, s->slots);
+    return UU3D_OK;
+}
+
+int uu3d_stream_timed_emit_multi(uu3d_model* m, const uu3d_stream_config* s, const uu3d_stream_rate* r, const uu3d_stream_out* o, void* state,
+                                 float* poses, int32_t* count, void* stream) {
+    if (!m) return UU3D_ERR_INVALID_ARGUMENT;
+    if (const int st = stream_rate_check(m, s, r, state, "uu3d_stream_timed_emit_multi")) return st;
+    if (const char* e = stream_out_error(o)) return fail(m, UU3D_ERR_INVALID_ARGUMENT, std::string("uu3d_stream_timed_emit_multi: ") + e);
+    if (!poses || !count || ((uintptr_t)poses & 15) != 0) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_timed_emit_multi: poses (16-byte aligned) and count must be given");
+    const StreamLayout L = stream_layout_of(m, s);
+    const RateLayout R = rate_layout(L, m->cfg.num_keypoints, r->key_ring);
+    char* base = (char*)state;
+    hipLaunchKernelGGL(stream_timed_emit_multi_kernel, dim3(s->slots), dim3(256), 0, (hipStream_t)stream, rate_params(m, s, r, L, R), out_params(o),
+                       (const int32_t*)(base + R.off_source_frames), (const uint8_t*)(base + R.off_pushed), (const float*)(base + R.off_keys),
+                       (int32_t*)(base + out_frames_offset(R)), poses, count);
+    return hipGetLastError() == hipSuccess ? UU3D_OK : fail(m, UU3D_ERR_HIP, "uu3d_stream_timed_emit_multi: launch failed");
+}
+
+int uu3d_stream_out_reset(uu3d_model* m, const uu3d_stream_config* s, const uu3d_stream_rate* r, const uu3d_stream_out* o, void* state,
+                          const uint8_t* slot_mask, void* stream) {
+    if (!m) return UU3D_ERR_INVALID_ARGUMENT;
+    if (const int st = stream_rate_check(m, s, r, state, "uu3d_stream_out_reset")) return st;
+    if (const char* e = stream_out_error(o)) return fail(m, UU3D_ERR_INVALID_ARGUMENT, std::string("uu3d_stream_out_reset: ") + e);
+    if (const int st = uu3d_stream_rate_reset(m, s, r, state, slot_mask, stream)) return st;
+    const RateLayout R = rate_layout(stream_layout_of(m, s), m->cfg.num_keypoints, r->key_ring);
+    hipLaunchKernelGGL(stream_out_reset_kernel, dim3((unsigned)((s->slots + 255) / 256)), dim3(256), 0, (hipStream_t)stream, slot_mask, s->slots,
+                       (int32_t*)((char*)state + out_frames_offset(R)));
+    return hipGetLastError() == hipSuccess ? UU3D_OK : fail(m, UU3D_ERR_HIP, "uu3d_stream_out_reset: launch failed");
+}
+
 int uu3d_world_to_cam_2d(const float* world, const float* cams, int32_t B, int32_t N, int32_t J, float* cam3d, float* kp2d, void* stream) {
     if (!world || !cams || B < 1 || N < 1 || J < 1 || (!cam3d && !kp2d)) return UU3D_ERR_INVALID_ARGUMENT;
     const long per = (long)N * J, total = per * B;

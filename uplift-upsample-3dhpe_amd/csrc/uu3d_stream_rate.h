@@ -9,6 +9,9 @@
 //   stream_timed_emit_kernel      once per push: the pose of source frame q = newest - lookahead, read at model position q a / b from the
 //                                 piecewise-linear motion through the kept keyframes (evaluation.keyframe_plan_at's rule)
 //   stream_rate_reset_kernel      chosen slots: source counter 0, held output pose 0
+// and, for a session with an output rate of its own (StreamSession(fps=F, out_fps=G)), in place of stream_timed_emit_kernel:
+//   stream_timed_emit_multi_kernel  once per push: EVERY output frame that became due at this push, up to R = ceil(G / F) poses per slot
+//   stream_out_reset_kernel         chosen slots: output counter 0
 // The new state lies behind the plain session's (StreamLayout) in the same caller-allocated block.  No atomics, one writer per output
 // element, every counter is read and advanced on the device, all arguments are the same at every push: a sub-tick in which no slot is due
 // changes no byte of the state and none of the outputs of the push.
@@ -42,6 +45,10 @@ inline RateLayout rate_layout(const StreamLayout& L, const int J, const int key_
     R.bytes = R.off_out_held + stream_align(T * L.per_pose * sizeof(float));
     return R;
 }
+
+// Behind RateLayout::bytes, for a session with an output rate of its own: the output counters (T) i32.
+inline size_t out_frames_offset(const RateLayout& R) { return R.bytes; }
+inline size_t out_layout_bytes(const RateLayout& R, const int slots) { return R.bytes + stream_align((size_t)slots * sizeof(int32_t)); }
 
 struct RateParams {
     int slots, J, halves, per_pose;
@@ -222,6 +229,74 @@ stream_rate_reset_kernel(const uint8_t* __restrict__ slot_mask, const int T, con
     if (slot_mask != nullptr && slot_mask[t] == 0) return;
     out_held[i] = 0.f;
     if (i - (long)t * per_pose == 0) { source_frames[t] = 0; pushed[t] = 0; }
+}
+
+// The output rate of a session, next to RateParams: G / F = c / d and model_fps / G = un / ud, both in lowest terms with terms below 2^20
+// (every product with a 31-bit counter fits int64); max_out = R = ceil(c / d), the most poses one push returns.
+struct OutParams { int c, d, un, ud, max_out; };
+
+// Once per push, behind its sub-ticks, in place of stream_timed_emit_kernel.  One workgroup per slot: the slot's output counter is read by
+// that workgroup only and advanced by lane 0 behind a barrier (the discipline of stream_source_push_kernel).  A slot that took a frame
+// at this push and whose q = newest source frame - lookahead is >= 0 has, after the push, emitted every output frame i <= hi =
+// floor(q c / d): the frames whose time i / G is not later than q / F.  n = hi + 1 - out_frames[slot], clamped to [0, R], of them are new;
+// any other slot has n = 0.  Row r < n of poses (T, R, J * 3) is output frame i = out_frames[slot] + r, read at model position
+// u = i un / ud by stream_timed_emit_kernel's rule: k0 = floor(u / P) P; u == k0 gives keyframe k0's bits, anything else
+// resample_mix(k0, k0 + P, w), w = (i un - k0 ud) / (P ud), one float64 division of two integers.  The host's plan (stream.rate_plan)
+// guarantees that both keyframes of every due frame have been emitted and are still in the ring; the place is taken modulo the ring
+// whatever the counters hold.  Rows r >= n are zeros; count[slot] = n.  The counter stops at INT32_MAX instead of wrapping.
+// A slot's R rows are R * J * 3 consecutive floats, 16-byte aligned only where slot * R * J * 3 is a multiple of four: the workgroup walks
+// the 16-byte quads of poses that overlap its rows, stores a quad that lies wholly inside them at once and the floats of a quad it shares
+// with a neighbouring slot one by one -- every element has one writer.
+static __global__ void __launch_bounds__(256)
+stream_timed_emit_multi_kernel(const RateParams p, const OutParams o, const int32_t* __restrict__ source_frames, const uint8_t* __restrict__ pushed,
+                               const float* __restrict__ keys, int32_t* __restrict__ out_frames, float* __restrict__ poses, int32_t* __restrict__ count)
+{
+    const int slot = blockIdx.x;
+    const long done = out_frames[slot];
+    const long q = (long)source_frames[slot] - 1 - p.lookahead;
+    long n = 0;
+    if (pushed[slot] != 0 && q >= 0 && done >= 0) {
+        n = q * o.c / o.d + 1 - done;
+        n = n < 0 ? 0 : (n > o.max_out ? o.max_out : n);
+        if (n > (long)INT32_MAX - done) n = (long)INT32_MAX - done;
+    }
+    __syncthreads();                                                     // every read of the counter is done
+    if (threadIdx.x == 0) { out_frames[slot] = (int32_t)(done + n); count[slot] = (int32_t)n; }
+    const long per = p.per_pose, P = p.pred_stride;
+    const long start = (long)slot * o.max_out * per, end = start + (long)o.max_out * per;
+    const float* ring = keys + (long)slot * p.key_ring * p.key_stride;
+    for (long quad = start / 4 + threadIdx.x; quad * 4 < end; quad += 256) {
+        const long e0 = quad * 4;
+        float v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            v[k] = 0.f;
+            const long rel = e0 + k - start;
+            if (rel < 0 || e0 + k >= end) continue;
+            const long r = rel / per;
+            if (r >= n) continue;
+            const int col = (int)(rel - r * per);
+            const long num = (done + r) * o.un;
+            const long k0 = num / o.ud / P * P;
+            const long off = num - k0 * o.ud;                             // (u - k0) ud, in [0, P ud)
+            const float a = ring[(k0 / P) % p.key_ring * p.key_stride + col];
+            if (off == 0) { v[k] = a; continue; }
+            const float b = ring[(k0 / P + 1) % p.key_ring * p.key_stride + col];
+            v[k] = resample_mix(a, b, (double)off / (double)(P * o.ud));
+        }
+        if (e0 >= start && e0 + 4 <= end) *reinterpret_cast<float4*>(poses + e0) = make_float4(v[0], v[1], v[2], v[3]);
+        else for (int k = 0; k < 4; ++k) if (e0 + k >= start && e0 + k < end) poses[e0 + k] = v[k];
+    }
+}
+
+// slot_mask (T) u8 or nullptr (every slot): the chosen slots' output counters go back to 0 (behind stream_rate_reset_kernel).
+static __global__ void __launch_bounds__(256)
+stream_out_reset_kernel(const uint8_t* __restrict__ slot_mask, const int T, int32_t* __restrict__ out_frames)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= T) return;
+    if (slot_mask != nullptr && slot_mask[t] == 0) return;
+    out_frames[t] = 0;
 }
 
 }  // namespace uu3d

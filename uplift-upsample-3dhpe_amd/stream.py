@@ -37,8 +37,25 @@ terms (exact integers; ``rate_plan``, ``push_plan``):
           D poses, centre c at place (c / P) % D, D - 1 = the largest distance in keyframes from the newest emitted centre back to k0.
 ``fps=None`` is the session above, bit for bit: the same launches, the same buffers, the same single captured graph.
 
+Live upsampling -- ``StreamSession(..., fps=F, out_fps=G, model_fps=50)``: the session returns poses on a time grid of its own, G per second,
+EVERY one that has become due per push -- a camera at 50 fps whose detector runs on every fifth frame (fps=10, out_fps=50) gets its 50
+poses a second, five per push.  Input and model sides, ``lookahead`` (SOURCE frames), a_m and ``missed_detections`` as above; the rules are
+``predict.output_positions``' and ``evaluation.keyframe_plan_at``'s, as ``predict_tracks(fps=F, out_fps=G)``:
+  grid    output frame i of a slot lies at time i / G, model position u = i model_fps / G, and is read like a source frame above:
+          k0 = floor(u / P) P; u == k0 gives that keyframe's bits, anything else float32(p0 (1 - w) + p1 w) in float64, w one float64
+          division of two integers.
+  push    after the push that made source frame j the newest of a slot, q = j - lookahead >= 0, the slot has emitted every output frame
+          i <= floor(q G / F): the frames whose time is not later than source frame q's.  The push returns the ones that became due at it,
+          oldest first -- frame 0 alone at q == 0, then floor(q G / F) - floor((q - 1) G / F): at most R = ceil(G / F) (``max_out``),
+          possibly none when G < F; an inactive slot returns none.  ``push`` -> (poses (slots, R, J, 3), count (slots,) int32); rows
+          r >= count[i] are zeros; ``out_frames`` counts the output frames per slot on the device.
+  ring    the oldest output frame of a push lies just behind source frame q - 1, so its k0 can be one keyframe older than k0(q): D is
+          enumerated over one common period of the three grids (source frames, output frames, keyframes); a_m needs no change -- no due
+          frame is later than source frame q -- which the enumeration checks as well (``rate_plan``, ``out_push_plan``).
+One launch (uu3d_stream_timed_emit_multi) in place of uu3d_stream_timed_emit; ``out_fps=None`` is the session above, bit for bit.
+
     python -m uplift_upsample_3dhpe_amd.stream --config C --weights W.h5 --input tracks.npz --output out.npz [--lookahead A] [--resolution W H]
-                                                 [--mask_missing] [--fps F]
+                                                 [--mask_missing] [--fps F [--out_fps G]]
 """
 import argparse
 import collections
@@ -125,7 +142,8 @@ def window_plan(frames, lookahead, config, mask_stride=None, valid=None):
             "place": np.where(kind == 2, (src // s_in) % cap, -1)}
 
 
-RatePlan = collections.namedtuple("RatePlan", "A B n_max a_m D min_lookahead pred_stride lookahead")
+RatePlan = collections.namedtuple("RatePlan", "A B n_max a_m D min_lookahead pred_stride lookahead out_c out_d pos_num pos_den max_out",
+                                  defaults=(None, None, None, None, None))
 
 
 def _newest_model_frame(j, A, B):
@@ -142,18 +160,65 @@ def _output_keyframes(q, A, B, P):
     return k0, (k0 if off == 0 else k0 + P), off, P * B
 
 
-def rate_plan(config, fps, lookahead, mask_stride=None, model_fps=50):
-    """The plan of ``StreamSession(fps=fps, lookahead=lookahead)`` -> RatePlan(A, B, n_max, a_m, D, min_lookahead, pred_stride, lookahead);
-    integers and ``Fraction`` only.  A / B = model_fps / fps in lowest terms; n_max = ceil(A / B), the most model frames one push makes;
+def _fraction_lcm(*values):
+    """The smallest positive Fraction that is a whole multiple of every given one: lcm of the numerators over gcd of the denominators."""
+    import math
+    from fractions import Fraction
+    return Fraction(math.lcm(*(v.numerator for v in values)), math.gcd(*(v.denominator for v in values)))
+
+
+def _output_ring_depth(A, B, c, d, un, ud, P, lookahead, a_m, period):
+    """D for a session with an output rate, by exact enumeration in numpy int64 over the pushes q + lookahead, q = 0 .. period (one common
+    period of source frames, output frames and keyframes, and the push that closes it): the push returns output frames i_lo .. i_hi,
+    the newest emitted centre is ((K(q + lookahead) - a_m) // P) P; the oldest k0 read is k0(i_lo), the newest k1 read is k1(i_hi).
+    -> (D, the smallest newest centre - k1(i_hi): >= 0 means every keyframe read has been emitted)."""
+    q = np.arange(period + 1, dtype=np.int64)
+    hi = q * c // d
+    lo = np.where(q == 0, 0, (q - 1) * c // d + 1)
+    due = hi >= lo
+    newest = ((q + lookahead) * A // B - a_m) // P * P
+    k0_lo = lo * un // ud // P * P
+    num_hi = hi * un
+    k0_hi = num_hi // ud // P * P
+    k1_hi = np.where(num_hi == k0_hi * ud, k0_hi, k0_hi + P)
+    return 1 + int(((newest - k0_lo) // P)[due].max()), int((newest - k1_hi)[due].min())
+
+
+def rate_plan(config, fps, lookahead, mask_stride=None, model_fps=50, out_fps=None):
+    """The plan of ``StreamSession(fps=fps, lookahead=lookahead)`` -> RatePlan(A, B, n_max, a_m, D, min_lookahead, pred_stride, lookahead,
+    ...); integers and ``Fraction`` only.  A / B = model_fps / fps in lowest terms; n_max = ceil(A / B), the most model frames one push makes;
     a_m the model lookahead and D the places of the keyframe ring (the module docstring), both by exact enumeration over one period B P
     of j; min_lookahead the smallest ``lookahead`` (in source frames) for which an a_m >= 0 exists.  A smaller ``lookahead`` raises
-    ValueError naming it; ``lookahead=None`` plans for min_lookahead itself."""
+    ValueError naming it; ``lookahead=None`` plans for min_lookahead itself.
+    ``out_fps=G`` (None: the five further fields are None and the others are what they were): out_c / out_d = G / fps and
+    pos_num / pos_den = model_fps / G in lowest terms, max_out = R = ceil(G / fps) poses per push at most.  a_m and min_lookahead are
+    unchanged -- an output frame due at a push is never later than the push's source frame q -- and D is enumerated over one common
+    period of the source frames, the output frames and the keyframes (an lcm of Fractions), the oldest output frame of every push
+    included; the enumeration also checks the claim about a_m.  ValueError, naming the quantity: more than 2^24 source frames per
+    period, a term of out_fps / fps or of model_fps / out_fps >= 2^20, more than 64 poses per push."""
     from .predict import frame_rate
     rho = frame_rate(model_fps) / frame_rate(fps)
     A, B = rho.numerator, rho.denominator
     if max(A, B) >= 2 ** 20:
         raise ValueError(f"model_fps / fps = {A}/{B}: numerator and denominator must stay below 2^20")
     _, _, P = session_strides(config, mask_stride)
+    out = ()
+    if out_fps is not None:
+        up, pos = frame_rate(out_fps) / frame_rate(fps), frame_rate(model_fps) / frame_rate(out_fps)
+        c, d, un, ud = up.numerator, up.denominator, pos.numerator, pos.denominator
+        if max(c, d) >= 2 ** 20:
+            raise ValueError(f"out_fps / fps = {c}/{d}: numerator and denominator must stay below 2^20")
+        if max(un, ud) >= 2 ** 20:
+            raise ValueError(f"model_fps / out_fps = {un}/{ud}: numerator and denominator must stay below 2^20")
+        R = -(-c // d)
+        if R > 64:
+            raise ValueError(f"out_fps / fps = {c}/{d} would return up to {R} poses per push; at most 64")
+        span = _fraction_lcm(1 / frame_rate(fps), 1 / frame_rate(out_fps), P / frame_rate(model_fps)) * frame_rate(fps)
+        assert span.denominator == 1
+        if span > 2 ** 24:
+            raise ValueError(f"fps {frame_rate(fps)}, out_fps {frame_rate(out_fps)} and keyframes {P} model frames apart repeat only after {int(span)} "
+                             f"source frames per period; at most 2^24")
+        out = (c, d, un, ud, R, int(span))
     period = B * P
     keys = [_output_keyframes(q, A, B, P) for q in range(period)]
 
@@ -167,10 +232,15 @@ def rate_plan(config, fps, lookahead, mask_stride=None, model_fps=50):
         raise ValueError(f"lookahead {lookahead} is too small at {frame_rate(fps)} fps: the pose of a source frame is read between two model "
                          f"keyframes {P} model frames apart, which needs a lookahead of at least {min_lookahead} source frames")
     a_m = min(max_lookahead(config), slack(lookahead))
-    D = 1 + max(((_newest_model_frame(q + lookahead, A, B) - a_m) // P * P - k[0]) // P for q, k in enumerate(keys))
+    if out:
+        D, spare = _output_ring_depth(A, B, *out[:4], P, lookahead, a_m, out[5])
+        if spare < 0:
+            raise AssertionError("an output frame due at a push reads a keyframe that has not been emitted")
+    else:
+        D = 1 + max(((_newest_model_frame(q + lookahead, A, B) - a_m) // P * P - k[0]) // P for q, k in enumerate(keys))
     if D > 4096:
         raise ValueError(f"lookahead {lookahead} would keep {D} keyframes per slot; at most 4096")
-    return RatePlan(A, B, -(-A // B), a_m, D, min_lookahead, P, lookahead)
+    return RatePlan(A, B, -(-A // B), a_m, D, min_lookahead, P, lookahead, *out[:5])
 
 
 def push_plan(j, plan):
@@ -191,6 +261,24 @@ def push_plan(j, plan):
     return {"model": model, "q": q, "k0": k0, "k1": k1, "weight": float(np.float64(off) / np.float64(den))}
 
 
+def out_push_plan(j, plan):
+    """The host mirror of what a slot's j-th push (0-based) RETURNS under a ``plan`` with an output rate: [(i, k0, k1, weight), ...], the
+    output frames that became due at the push, oldest first -- none while q = j - lookahead < 0, frame 0 alone at q == 0, then
+    floor((q - 1) G / F) + 1 .. floor(q G / F); k0, k1 the two keyframes frame i is read between (k1 == k0 on a keyframe) and weight the
+    float64 (i pos_num - k0 pos_den) / (P pos_den), ``keyframe_plan_at``'s."""
+    if plan.max_out is None:
+        raise ValueError("the plan has no output rate: rate_plan(..., out_fps=G)")
+    q = int(j) - plan.lookahead
+    if q < 0:
+        return []
+    first = 0 if q == 0 else ((q - 1) * plan.out_c) // plan.out_d + 1
+    frames = []
+    for i in range(first, (q * plan.out_c) // plan.out_d + 1):
+        k0, k1, off, den = _output_keyframes(i, plan.pos_num, plan.pos_den, plan.pred_stride)
+        frames.append((i, k0, k1, float(np.float64(off) / np.float64(den))))
+    return frames
+
+
 def _check_resolutions(resolutions, slots):
     if resolutions is None:
         return None
@@ -205,7 +293,7 @@ def _check_resolutions(resolutions, slots):
 class StreamSession(object):
 
     def __init__(self, model, config, slots, resolutions=None, mask_stride=None, flip=None, lookahead=0, root_relative=True, graph=True,
-                 missed_detections=False, fps=None, model_fps=50):
+                 missed_detections=False, fps=None, model_fps=50, out_fps=None):
         """``slots``: tracks served side by side (a slot is a track: ``reset`` starts a new one).  ``resolutions``: None = the coordinates
         are normalised already, else one (w, h) in pixels or one per slot.  ``mask_stride`` / ``flip`` / ``root_relative`` as
         ``predict.predict_tracks``.  ``lookahead`` = a: frames the answer may lag behind the newest one, 0 <= a <=
@@ -220,12 +308,19 @@ class StreamSession(object):
         SOURCE frames and must be at least ``rate_plan(...).min_lookahead`` (ValueError naming it); ``missed_detections`` flags are per
         source frame, and a model frame is missing under uu3d_resample_tracks' rule: its left source frame is missing or, where it is mixed
         from two, its right one.  ``captures`` counts captures of the sub-tick graph: 1 for the session's whole life -- the source push and
-        the timed emit around the replays are two plain launches, not captured."""
+        the timed emit around the replays are two plain launches, not captured.
+        ``out_fps``: None = one pose per push, at the source frame's own time (the session above, bit for bit).  Else the rate of the poses
+        the session returns, parsed like ``fps`` (which it needs: ValueError without): the module docstring's "Live upsampling".  ``push``
+        then returns (poses (slots, max_out, J, 3), count (slots,) int32), ``max_out`` = ceil(out_fps / fps) <= 64, and ``out_frames``
+        counts the output frames per slot."""
         slots, lookahead = int(slots), int(lookahead)
         if slots < 1:
             raise ValueError("slots >= 1")
+        if out_fps is not None and fps is None:
+            raise ValueError("out_fps needs fps: the rate of the pushed frames")
         S, s_in, pred = session_strides(config, mask_stride)
-        self.rate = None if fps is None else rate_plan(config, fps, lookahead, mask_stride, model_fps)
+        self.rate = None if fps is None else rate_plan(config, fps, lookahead, mask_stride, model_fps, out_fps)
+        self.max_out = None if out_fps is None else self.rate.max_out
         if self.rate is None and not 0 <= lookahead <= max_lookahead(config):
             raise ValueError(f"lookahead must be in [0, {max_lookahead(config)}] = (SEQUENCE_LENGTH // 2) * SEQUENCE_STRIDE, got {lookahead}")
         res = _check_resolutions(resolutions, slots)
@@ -258,6 +353,13 @@ class StreamSession(object):
             rlay = _capi.Uu3dStreamRateLayout()
             _capi.check(lib, lib.uu3d_stream_rate_state_layout(model._h, C.byref(self._cfg), C.byref(self._rate), C.byref(rlay)), model._h)
             state_bytes = int(rlay.bytes)
+            if self.max_out is not None:
+                r = self.rate
+                self._outp = _capi.Uu3dStreamOut(r.out_c, r.out_d, r.pos_num, r.pos_den, r.max_out)
+                olay = _capi.Uu3dStreamOutLayout()
+                _capi.check(lib, lib.uu3d_stream_out_state_layout(model._h, C.byref(self._cfg), C.byref(self._rate), C.byref(self._outp),
+                                                                  C.byref(olay)), model._h)
+                state_bytes = int(olay.bytes)
             self._src_host = np.zeros(slots, np.int64)                # host mirror of the source counters; exact where _src_known
             self._src_known = np.ones(slots, bool)
         with torch.cuda.device(dev):
@@ -292,6 +394,10 @@ class StreamSession(object):
                 self._tick_active = torch.zeros((T,), dtype=torch.uint8, device=dev)
                 self._emit_out = torch.zeros((T, J, 3), dtype=torch.float32, device=dev)
                 self._emit_fresh = torch.zeros((T,), dtype=torch.uint8, device=dev)
+            if self.max_out is not None:
+                self._out_frames = view(int(olay.out_frames_offset), T, torch.int32)
+                self._poses = torch.zeros((T, self.max_out, J, 3), dtype=torch.float32, device=dev)
+                self._count = torch.zeros((T,), dtype=torch.int32, device=dev)
             # a workspace of the session's own for uu3d_frame_features: the graph holds its address
             self._fws = torch.empty(max(int(lib.uu3d_frame_features_bytes(model._h, H * T)), int(lib.uu3d_frame_features_bytes(model._h, 1))),
                                     dtype=torch.uint8, device=dev)
@@ -388,6 +494,10 @@ class StreamSession(object):
         enqueues uu3d_stream_source_push, n replays of the one sub-tick graph and uu3d_stream_timed_emit; n is the largest number of model
         frames an active slot makes at this push, known from a host mirror of the source counters.  ``active`` as a DEVICE tensor leaves the
         mirror unknown: ceil(A / B) sub-ticks are replayed per push (the surplus ones change nothing) until every such slot has been reset.
+        A session with ``out_fps``: -> (poses (slots, max_out, J, 3) float32, count (slots,) int32) on the device, the session's own buffers,
+        valid until the next ``push``: rows r < count[i] of slot i are the output frames that became due at this push, oldest first (the
+        first is output frame ``out_frames[i] - count[i]``), rows r >= count[i] are zeros; an inactive slot has count 0.
+        uu3d_stream_timed_emit_multi takes uu3d_stream_timed_emit's place.
         Enqueues on the current stream and returns; never waits for the device."""
         torch = self._torch
         m = self.model
@@ -425,6 +535,8 @@ class StreamSession(object):
                 self._graph.replay()
             else:
                 self._tick(torch.cuda.current_stream(dev))
+        if self.max_out is not None:
+            return self._poses, self._count
         return self._out, self._fresh.view(torch.bool)
 
     def _sub_ticks(self, active):
@@ -454,10 +566,15 @@ class StreamSession(object):
                 self._graph.replay()
             else:
                 self._tick(cur)
+        if self.max_out is not None:
+            _capi.check(lib, lib.uu3d_stream_timed_emit_multi(m._h, cfg, rate, C.byref(self._outp), _ptr(self._state), _ptr(self._poses),
+                                                              _ptr(self._count), st), m._h)
+            return
         _capi.check(lib, lib.uu3d_stream_timed_emit(m._h, cfg, rate, _ptr(self._state), _ptr(self._out), _ptr(self._fresh), st), m._h)
 
     def reset(self, slots=None):
-        """The given slots (indices; None = all) start a new track: zero frames, held pose 0.  Stream-ordered like ``push``."""
+        """The given slots (indices; None = all) start a new track: zero frames, held pose 0, with ``out_fps`` output counter 0.  Stream-ordered
+        like ``push``."""
         torch = self._torch
         m = self.model
         mask = None
@@ -470,8 +587,12 @@ class StreamSession(object):
             if self.rate is None:
                 _capi.check(self._lib, self._lib.uu3d_stream_reset(m._h, C.byref(self._cfg), _ptr(self._state), _ptr(mask), st), m._h)
                 return
-            _capi.check(self._lib, self._lib.uu3d_stream_rate_reset(m._h, C.byref(self._cfg), C.byref(self._rate), _ptr(self._state), _ptr(mask), st),
-                        m._h)
+            if self.max_out is not None:
+                _capi.check(self._lib, self._lib.uu3d_stream_out_reset(m._h, C.byref(self._cfg), C.byref(self._rate), C.byref(self._outp),
+                                                                       _ptr(self._state), _ptr(mask), st), m._h)
+            else:
+                _capi.check(self._lib, self._lib.uu3d_stream_rate_reset(m._h, C.byref(self._cfg), C.byref(self._rate), _ptr(self._state), _ptr(mask),
+                                                                        st), m._h)
             which = slice(None) if slots is None else np.asarray(slots, np.int64).reshape(-1)
             self._src_host[which] = 0
             self._src_known[which] = True
@@ -485,6 +606,13 @@ class StreamSession(object):
     def source_frames(self):
         """Source frames pushed per slot since its last reset, (slots,) int32 on the device; without ``fps`` the same tensor as ``frames``."""
         return self._frames if self.rate is None else self._source_frames
+
+    @property
+    def out_frames(self):
+        """Output frames emitted per slot since its last reset (sessions with ``out_fps``), (slots,) int32 on the device."""
+        if self.max_out is None:
+            raise AttributeError("out_frames needs a session with out_fps")
+        return self._out_frames
 
     def check_range(self):
         """Range guard of precision f16x3 for everything pushed so far, as ``ForwardPipeline.check_range()``: waits for the current stream,
@@ -508,11 +636,13 @@ class StreamSession(object):
 
 
 def replay_tracks(model, config, tracks, resolutions=None, mask_stride=None, flip=None, lookahead=0, root_relative=True, graph=True, valid=None, fps=None,
-                  model_fps=50):
+                  model_fps=50, out_fps=None):
     """Push complete tracks tick by tick, one slot per track (a slot is inactive once its track has ended) -> per track the pose the
     session returned at each of its ticks, (T_i, J, 3) float32, and the fresh flags (T_i,) bool, as host arrays.  One copy to the host,
     at the end.  ``valid`` as ``predict.predict_tracks``: None, "finite" (rows with a NaN / Inf coordinate are missing frames) or one (T_i,)
-    host array per track -- a session with ``missed_detections=True``.  ``fps`` / ``model_fps``: the rate of the tracks, as ``StreamSession``."""
+    host array per track -- a session with ``missed_detections=True``.  ``fps`` / ``model_fps``: the rate of the tracks, as ``StreamSession``.
+    ``out_fps=G``: -> per track the poses the session emitted, concatenated in order, (n_out_i, J, 3) float32 -- output frames
+    0 .. n_out_i - 1 at G per second --, and the number each of its ticks returned, (T_i,) int32; still one copy to the host, at the end."""
     import torch
     lens = [int(len(t)) for t in tracks]
     T, ticks = len(tracks), max(lens)
@@ -525,10 +655,14 @@ def replay_tracks(model, config, tracks, resolutions=None, mask_stride=None, fli
         raise ValueError('valid must be None, "finite" or a list with one (T_i,) array per track')
     s = StreamSession(model, config, T, resolutions=resolutions, mask_stride=mask_stride, flip=flip, lookahead=lookahead,
                       root_relative=root_relative, graph=graph, **({} if valid is None else {"missed_detections": True}),
-                      **({} if fps is None else {"fps": fps, "model_fps": model_fps}))
+                      **({} if fps is None else {"fps": fps, "model_fps": model_fps}), **({} if out_fps is None else {"out_fps": out_fps}))
     J = int(np.asarray(tracks[0]).shape[1])
-    poses = torch.zeros((ticks, T, J, 3), dtype=torch.float32, device=model.device)
-    fresh = torch.zeros((ticks, T), dtype=torch.bool, device=model.device)
+    if out_fps is None:
+        poses = torch.zeros((ticks, T, J, 3), dtype=torch.float32, device=model.device)
+        fresh = torch.zeros((ticks, T), dtype=torch.bool, device=model.device)
+    else:                                                             # one block of 32-bit words per tick and slot: the count, then the rows' bits
+        R = s.max_out
+        words = torch.zeros((ticks, T, 1 + R * J * 3), dtype=torch.int32, device=model.device)
     kp = np.zeros((T, J, 2), np.float32)
     try:
         for k in range(ticks):
@@ -540,11 +674,21 @@ def replay_tracks(model, config, tracks, resolutions=None, mask_stride=None, fli
                 p, f = s.push(kp, None if act.all() else act)
             else:
                 p, f = s.push(kp, None if act.all() else act, valid=np.array([bool(act[i]) and bool(flags[i][k]) for i in range(T)]))
-            poses[k].copy_(p)
-            fresh[k].copy_(f)
+            if out_fps is None:
+                poses[k].copy_(p)
+                fresh[k].copy_(f)
+            else:
+                words[k, :, 0].copy_(f)
+                words[k, :, 1:].copy_(p.view(torch.int32).view(T, -1))
         s.check_range()
     finally:
         s.close()
+    if out_fps is not None:
+        words = words.cpu().numpy()
+        counts = words[:, :, 0]
+        rows = np.ascontiguousarray(words[:, :, 1:]).view(np.float32).reshape(ticks, T, R, J, 3)
+        return ([np.concatenate([rows[k, i, :counts[k, i]] for k in range(n)] + [np.zeros((0, J, 3), np.float32)]) for i, n in enumerate(lens)],
+                [counts[:n, i].astype(np.int32) for i, n in enumerate(lens)])
     poses, fresh = poses.cpu().numpy(), fresh.cpu().numpy()
     return [poses[:n, i] for i, n in enumerate(lens)], [fresh[:n, i] for i, n in enumerate(lens)]
 
@@ -565,7 +709,13 @@ def parse_args(argv=None):
     p.add_argument("--fps", type=_rate_argument, default=None, metavar="F",
                    help="frame rate of the tracks, a float or NUM/DEN (29.97, 30000/1001); without it they are taken at the model's rate.  "
                         "--lookahead then counts frames of the tracks")
-    return p.parse_args(argv)
+    p.add_argument("--out_fps", type=_rate_argument, default=None, metavar="G",
+                   help="rate of the poses written, a float or NUM/DEN (needs --fps): NAME then holds every pose the session emitted, in order "
+                        "(n_out, J, 3), and NAME_count the number each tick returned")
+    args = p.parse_args(argv)
+    if args.out_fps is not None and args.fps is None:
+        p.error("--out_fps needs --fps")
+    return args
 
 
 def _rate_argument(text):
@@ -594,18 +744,24 @@ def main(argv=None):
         raise SystemExit(f"--lookahead must be in [0, {max_lookahead(config)}]")
     if args.fps is not None:
         try:
-            rate_plan(config, args.fps, args.lookahead)
+            rate_plan(config, args.fps, args.lookahead, out_fps=args.out_fps)
         except ValueError as e:
-            raise SystemExit(f"--fps / --lookahead: {e}") from None
+            raise SystemExit(f"--fps / --out_fps / --lookahead: {e}") from None
     model = _load_model(config, args.weights)
     poses, fresh = replay_tracks(model, config, tracks, resolutions=None if args.resolution is None else tuple(args.resolution),
                                  lookahead=args.lookahead, **({"valid": "finite"} if args.mask_missing else {}),
-                                 **({} if args.fps is None else {"fps": args.fps}))
+                                 **({} if args.fps is None else {"fps": args.fps}), **({} if args.out_fps is None else {"out_fps": args.out_fps}))
     out = {}
     for k, p, f in zip(names, poses, fresh):
         out[k] = np.asarray(p, np.float32)
-        out[k + "_fresh"] = np.asarray(f, bool)
+        if args.out_fps is None:
+            out[k + "_fresh"] = np.asarray(f, bool)
+        else:
+            out[k + "_count"] = np.asarray(f, np.int32)
     np.savez(args.output, **out)
+    if args.out_fps is not None:
+        print(f"wrote {args.output}: {len(names)} tracks, {sum(len(f) for f in fresh)} ticks, {sum(len(p) for p in poses)} poses at {args.out_fps} fps", flush=True)
+        return 0
     print(f"wrote {args.output}: {len(names)} tracks, {sum(len(p) for p in poses)} ticks, {int(sum(f.sum() for f in fresh))} fresh poses", flush=True)
     return 0
 
