@@ -10,47 +10,14 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import uplift_upsample_3dhpe_amd as pkg
-from tests import util
+from tests import tracks_util, util
+from tests.tracks_util import RES, _bits, _host_normalised, _model, _pixel_tracks, _same_bits
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
-RES = [(1000, 1002), (1920, 1080), (640, 480)]
 MASK_STRIDE = {"h36m_351": 5, "h36m_81": 4}
 LENS = [1, 7, 50, 203]
 PATTERNS = ("all_valid", "all_missing", "first_missing", "edge_missing", "random30")
-_MODELS = {}
-
-
-def _bits(a):
-    a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _same_bits(a, b):
-    a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a
-    b = b.detach().cpu().numpy() if isinstance(b, torch.Tensor) else b
-    return a.shape == b.shape and np.array_equal(_bits(a), _bits(b))
-
-
-def _pixel_tracks(lens, seed, J=17):
-    rng = np.random.default_rng(seed)
-    return [(rng.uniform(0.0, 1.0, size=(n, J, 2)) * np.array(RES[i % len(RES)], np.float64)).astype(np.float32) for i, n in enumerate(lens)]
-
-
-def _host_normalised(tracks):
-    from uplift_upsample_3dhpe_amd import h36m
-    return [h36m.normalize_screen_coordinates(t, w=RES[i % len(RES)][0], h=RES[i % len(RES)][1]).astype(np.float32) for i, t in enumerate(tracks)]
-
-
-def _model(cfgname, seed=2):
-    if cfgname not in _MODELS:
-        cfg = util.load_config(cfgname)
-        cfg.BATCH_SIZE = 64
-        arch = pkg.arch_from_config(cfg)
-        w = pkg.init_weights(arch, seed=seed, perturb=0.1)
-        _MODELS[cfgname] = (cfg, arch, w, pkg.build_uplift_upsample_transformer(cfg, weights=w))
-    return _MODELS[cfgname]
 
 
 def _pattern(name, L, S, seed=0):
@@ -263,27 +230,10 @@ def test_gathers_equal_the_rule_exactly(cfgname, padding):
 
 # ---- 3. predict_tracks against the oracle --------------------------------------------------------------------------------------------
 def _oracle_tracks(cfg, arch, w, norm_tracks, ms, valid):
-    """tests/test_predict_tracks_gpu.py::_oracle_tracks' recipe with the host mask ANDed with validity and the missing frames zeroed."""
-    from oracle import uplift_oracle as O
-    from uplift_upsample_3dhpe_amd import eval as ev
-    from uplift_upsample_3dhpe_amd import evaluation
-    from uplift_upsample_3dhpe_amd.data import PoseTable, SequenceGenerator
-    c = cfg.copy(); c.MASK_STRIDE = ms
+    """tracks_util._oracle_tracks with the host mask ANDed with validity and the missing frames zeroed."""
     zeroed = [np.where(v[:, None, None], t, np.float32(0.0)).astype(np.float32) for t, v in zip(norm_tracks, valid)]
-    table = PoseTable(zeroed)
-    gen = SequenceGenerator(table, seq_len=c.SEQUENCE_LENGTH, subsample=1, stride=c.SEQUENCE_STRIDE, padding_type=c.PADDING_TYPE,
-                            flip_augment=False, mask_stride=ms, stride_mask_align_global=True, shuffle=False)
-    desc = gen.descriptors()
-    run = np.flatnonzero(ev.needed_windows(desc[:, 1], c))
-    b = gen.gather(desc[run], zero_masked=False, with_3d=False)
-    x, m = b["kp2d"].cpu().numpy(), b["stride_mask"].cpu().numpy().astype(bool)
-    _, _, _, sm = _np_windows(desc[run], c.SEQUENCE_LENGTH, table.starts, table.lens, c.PADDING_TYPE == "copy", np.concatenate(valid))
-    assert not (sm & ~m).any()
-    _, cen = O.eval_step_with_flip(util.hp_from_arch(arch), w, x, m & sm, c.AUGM_FLIP_KEYPOINT_ORDER)
-    pred = np.zeros((len(desc), 17, 3), np.float64)
-    pred[run] = cen
-    pred, _ = evaluation.interpolate_between_keyframes(pred, desc[:, 1], c.SEQUENCE_STRIDE)
-    return pred - pred[:, c.ROOT_KEYTPOINT:c.ROOT_KEYTPOINT + 1]
+    return tracks_util._oracle_tracks(cfg, arch, w, zeroed, ms, window_valid=lambda desc, c, table: _np_windows(
+        desc, c.SEQUENCE_LENGTH, table.starts, table.lens, c.PADDING_TYPE == "copy", np.concatenate(valid))[3])
 
 
 def _missing_30(lens, seed):

@@ -10,40 +10,12 @@ import pytest
 
 import uplift_upsample_3dhpe_amd as pkg
 from tests import util
+from tests.tracks_util import RES, _bits, _host_normalised, _model, _oracle_tracks, _pixel_tracks, _same_bits  # noqa: F401 (test_track_fps_gpu reads them here)
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 G = os.path.join(util.ROOT, "tests", "golden")
 MASK_STRIDE = {"h36m_351": 5, "h36m_81": 4}
-RES = [(1000, 1002), (1920, 1080), (640, 480)]                        # Human3.6M's near-square camera, two non-square ones
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _same_bits(a, b):
-    a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a
-    b = b.detach().cpu().numpy() if isinstance(b, torch.Tensor) else b
-    return a.shape == b.shape and np.array_equal(_bits(a), _bits(b))
-
-
-def _pixel_tracks(lens, seed, J=17):
-    rng = np.random.default_rng(seed)
-    return [(rng.uniform(0.0, 1.0, size=(n, J, 2)) * np.array(RES[i % len(RES)], np.float64)).astype(np.float32) for i, n in enumerate(lens)]
-
-
-def _host_normalised(tracks):
-    from uplift_upsample_3dhpe_amd import h36m
-    return [h36m.normalize_screen_coordinates(t, w=RES[i % len(RES)][0], h=RES[i % len(RES)][1]).astype(np.float32) for i, t in enumerate(tracks)]
-
-
-def _model(cfgname, seed=2):
-    cfg = util.load_config(cfgname)
-    cfg.BATCH_SIZE = 64
-    arch = pkg.arch_from_config(cfg)
-    w = pkg.init_weights(arch, seed=seed, perturb=0.1)
-    return cfg, arch, w, pkg.build_uplift_upsample_transformer(cfg, weights=w)
 
 
 def test_normalize_tracks_equals_the_host_rule_bitwise():
@@ -115,26 +87,6 @@ def test_assemble_tracks_alone(stride, flip):
     bad = left.copy(); bad[5] = W
     out = predict.assemble_tracks(dp, df, bad, right, weight, flip_order=order).cpu().numpy()
     assert np.isnan(out[5]).all() and _same_bits(np.delete(out, 5, 0), np.delete(want, 5, 0))
-
-
-def _oracle_tracks(cfg, arch, w, norm_tracks, ms):
-    """The same pipeline with the CPU oracle as the model: windows of the needed frames, flip as a second call, host interpolation."""
-    from oracle import uplift_oracle as O
-    from uplift_upsample_3dhpe_amd import eval as ev
-    from uplift_upsample_3dhpe_amd import evaluation
-    from uplift_upsample_3dhpe_amd.data import PoseTable, SequenceGenerator
-    c = cfg.copy(); c.MASK_STRIDE = ms
-    gen = SequenceGenerator(PoseTable(norm_tracks), seq_len=c.SEQUENCE_LENGTH, subsample=1, stride=c.SEQUENCE_STRIDE, padding_type=c.PADDING_TYPE,
-                            flip_augment=False, mask_stride=ms, stride_mask_align_global=True, shuffle=False)
-    desc = gen.descriptors()
-    run = np.flatnonzero(ev.needed_windows(desc[:, 1], c))
-    b = gen.gather(desc[run], zero_masked=False, with_3d=False)
-    x, m = b["kp2d"].cpu().numpy(), b["stride_mask"].cpu().numpy().astype(bool)
-    _, cen = O.eval_step_with_flip(util.hp_from_arch(arch), w, x, m, c.AUGM_FLIP_KEYPOINT_ORDER)
-    pred = np.zeros((len(desc), 17, 3), np.float64)
-    pred[run] = cen
-    pred, _ = evaluation.interpolate_between_keyframes(pred, desc[:, 1], c.SEQUENCE_STRIDE)
-    return pred - pred[:, c.ROOT_KEYTPOINT:c.ROOT_KEYTPOINT + 1]
 
 
 @pytest.mark.parametrize("cfgname", ["h36m_351", "h36m_81"])

@@ -222,3 +222,25 @@ def test_source_has_no_atomics_and_shares_the_helpers():
         assert re.search(r"__device__ __forceinline__ \w+ " + helper + r"\(", open(os.path.join(csrc, "uu3d_tracks.h")).read()), helper
         assert not re.search(r"__device__[^\n]*\b" + helper + r"\(", code), helper
     assert "resample_mix(" in code and "resample_source_pair(" in code and "finite_pair(" in code
+
+
+def test_the_bracket_rule_is_stated_once_for_ints_and_arrays():
+    """rates.keyframe_bracket against the scalar formula of the plans (restated here), on the rates the tests use against 50 both ways
+    round, P in {1, 2, 5}, the first 2000 positions of each: once on Python ints, once on one int64 array, equal element for element."""
+    from uplift_upsample_3dhpe_amd import rates
+
+    def scalar(q, A, B, P):
+        k0 = q * A // B // P * P
+        off = q * A - k0 * B
+        return k0, (k0 if off == 0 else k0 + P), off, P * B
+    q = np.arange(2000, dtype=np.int64)
+    for fps in (24, 25, 30, 60, (2997, 100), (30000, 1001)):
+        for rho in (Fraction(50) / rates.frame_rate(fps), rates.frame_rate(fps) / Fraction(50)):
+            A, B = rho.numerator, rho.denominator
+            for P in (1, 2, 5):
+                want = [scalar(int(i), A, B, P) for i in q]
+                got = [rates.keyframe_bracket(int(i) * A, B, P) for i in q]
+                assert got == want and all(type(v) is int for g in got for v in g)
+                k0, k1, off, den = rates.keyframe_bracket(q * A, B, P)
+                assert k0.dtype == k1.dtype == off.dtype == np.int64 and den == P * B
+                assert np.array_equal(np.stack([k0, k1, off, np.full_like(q, den)], 1), np.array(want, np.int64))

@@ -6,91 +6,12 @@ import math
 import numpy as np
 import pytest
 
-import uplift_upsample_3dhpe_amd as pkg
 from tests import util
+from tests.tracks_util import RES, _bits, _model, _model_rate_frames, _pixel_tracks, _plain_keyframes, _run
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
-RES = [(1000, 1002), (1920, 1080), (640, 480)]
 T, J = 3, 17
-_MODELS = {}
-
-
-def _bits(a):
-    a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _pixel_tracks(lens, seed):
-    rng = np.random.default_rng(seed)
-    return [(rng.uniform(0.0, 1.0, size=(n, J, 2)) * np.array(RES[i % len(RES)], np.float64)).astype(np.float32) for i, n in enumerate(lens)]
-
-
-def _model(cfgname, seed=2):
-    if cfgname not in _MODELS:
-        cfg = util.load_config(cfgname)
-        cfg.BATCH_SIZE = 64
-        arch = pkg.arch_from_config(cfg)
-        w = pkg.init_weights(arch, seed=seed, perturb=0.1)
-        _MODELS[cfgname] = (cfg, arch, w, pkg.build_uplift_upsample_transformer(cfg, weights=w))
-    return _MODELS[cfgname]
-
-
-def _run(session, tracks, ticks, active=None, before_tick=None, valid=None, device_active=False):
-    """Push ``tracks[i][k]`` into slot i at push k -> (poses (ticks, T, J, 3), fresh (ticks, T)) as host arrays: one copy at the end.
-    ``active(k)`` -> (T,) bools or None; a slot's frame is the next one of ITS track.  ``valid[i]``: per-frame flags of track i."""
-    poses = torch.zeros((ticks, T, J, 3), dtype=torch.float32, device="cuda")
-    fresh = torch.zeros((ticks, T), dtype=torch.bool, device="cuda")
-    used = [0] * T
-    for k in range(ticks):
-        if before_tick is not None:
-            before_tick(k, used)
-        act = None if active is None else np.asarray(active(k), bool)
-        kp = np.zeros((T, J, 2), np.float32)
-        flags = np.ones(T, bool)
-        for i in range(T):
-            if act is None or act[i]:
-                kp[i] = tracks[i][used[i]]
-                if valid is not None:
-                    flags[i] = bool(valid[i][used[i]])
-                used[i] += 1
-        a = act if act is None or not device_active else torch.from_numpy(act).cuda()
-        p, f = session.push(kp, a, **({} if valid is None else {"valid": flags}))
-        poses[k].copy_(p)
-        fresh[k].copy_(f)
-    return poses.cpu().numpy(), fresh.cpu().numpy()
-
-
-def _model_rate_frames(tracks, fps, n_model, valid=None):
-    """The first ``n_model`` model-rate frames of every track (uu3d_resample_tracks), normalised -> list of (n_model, J, 2) host arrays
-    (and, with ``valid``, their flags)."""
-    from uplift_upsample_3dhpe_amd import predict
-    table, model_lens, _ = predict.resampled_pose_table(tracks, torch.device("cuda", 0), fps, resolutions=RES[:len(tracks)], valid=valid)
-    assert (model_lens >= n_model).all()
-    kp = torch.split(table.kp2d, [int(n) for n in model_lens], 0)
-    frames = [t[:n_model].cpu().numpy() for t in kp]
-    if valid is None:
-        return frames
-    return frames, [v[:n_model].cpu().numpy() != 0 for v in torch.split(table.valid, [int(n) for n in model_lens], 0)]
-
-
-def _plain_keyframes(model, cfg, ms, a_m, frames, valid=None):
-    """The model-rate frames through a plain session at lookahead a_m -> ({centre: (T, J, 3) pose}, the session's ring capacity)."""
-    from uplift_upsample_3dhpe_amd import stream
-    s = stream.StreamSession(model, cfg, slots=T, resolutions=None, mask_stride=ms, flip=True, lookahead=a_m,
-                             **({} if valid is None else {"missed_detections": True}))
-    n = len(frames[0])
-    poses, fresh = _run(s, frames, n, valid=valid)
-    assert s.check_range() is False
-    cap = s.ring_capacity
-    s.close()
-    keys = {}
-    for t in range(n):
-        if fresh[t].all():
-            keys[t - a_m] = poses[t]
-        else:
-            assert not fresh[t].any()
-    return keys, cap
 
 
 def _expected(plan, keys, j):
@@ -118,7 +39,7 @@ def test_identity_with_the_plain_session(cfgname, ms, fps, extra):
     n_src = max(150, math.ceil((2 * cap * ms + 12) * plan.B / plan.A))
     n_model = (n_src - 1) * plan.A // plan.B + 1
     tracks = _pixel_tracks([n_src] * T, seed=61)
-    keys, plain_cap = _plain_keyframes(model, cfg, ms, plan.a_m, _model_rate_frames(tracks, fps, n_model))
+    keys, plain_cap = _plain_keyframes(model, cfg, ms, plan.a_m, _model_rate_frames(tracks, fps, n_model), with_capacity=True)
     s = stream.StreamSession(model, cfg, slots=T, resolutions=RES, mask_stride=ms, flip=True, lookahead=L, fps=fps)
     assert s.rate == plan and s.model_lookahead == plan.a_m and s.ring_capacity == plain_cap == cap
     assert s.ring_capacity * ms < n_model // 2                            # the ring wraps at least twice
@@ -314,7 +235,7 @@ def test_missed_detections_at_30_fps():
         tracks[i][rng.choice(n_src, 12, replace=False), rng.integers(0, J, 12), 0] = np.nan      # missing by the finite test alone
     frames, model_valid = _model_rate_frames(tracks, fps, n_model, valid=[f.astype(np.uint8) for f in flags])
     assert all(0.3 < v.mean() < 0.95 for v in model_valid)
-    keys, _ = _plain_keyframes(model, cfg, ms, plan.a_m, frames, valid=model_valid)
+    keys = _plain_keyframes(model, cfg, ms, plan.a_m, frames, valid=model_valid)
     outs = []
     for variant in range(2):
         tr = [t.copy() for t in tracks]

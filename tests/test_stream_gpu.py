@@ -4,74 +4,12 @@ to its first t + 1 frames.  Three slots, flip on, pixel tracks at three resoluti
 import numpy as np
 import pytest
 
-import uplift_upsample_3dhpe_amd as pkg
 from tests import util
+from tests.tracks_util import RES, _bits, _model, _oracle_poses, _pixel_tracks, _run
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
-RES = [(1000, 1002), (1920, 1080), (640, 480)]
 T = 3
-_MODELS = {}
-
-
-def _bits(a):
-    a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _pixel_tracks(lens, seed, J=17):
-    rng = np.random.default_rng(seed)
-    return [(rng.uniform(0.0, 1.0, size=(n, J, 2)) * np.array(RES[i % len(RES)], np.float64)).astype(np.float32) for i, n in enumerate(lens)]
-
-
-def _model(cfgname, seed=2):
-    if cfgname not in _MODELS:
-        cfg = util.load_config(cfgname)
-        cfg.BATCH_SIZE = 64
-        arch = pkg.arch_from_config(cfg)
-        w = pkg.init_weights(arch, seed=seed, perturb=0.1)
-        _MODELS[cfgname] = (cfg, arch, w, pkg.build_uplift_upsample_transformer(cfg, weights=w))
-    return _MODELS[cfgname]
-
-
-def _run(session, tracks, ticks, active=None, before_tick=None):
-    """Push ``tracks[i][k]`` into slot i at tick k -> (poses (ticks, T, J, 3), fresh (ticks, T)) as host arrays: one copy at the end.
-    ``active(k)`` -> (T,) bools or None; a slot's frame at tick k is the next one of ITS track (tracks are consumed per slot)."""
-    poses = torch.zeros((ticks, T, 17, 3), dtype=torch.float32, device="cuda")
-    fresh = torch.zeros((ticks, T), dtype=torch.bool, device="cuda")
-    used = [0] * T
-    for k in range(ticks):
-        if before_tick is not None:
-            before_tick(k, used)
-        act = None if active is None else np.asarray(active(k), bool)
-        kp = np.zeros((T, 17, 2), np.float32)
-        for i in range(T):
-            if act is None or act[i]:
-                kp[i] = tracks[i][used[i]]
-                used[i] += 1
-        p, f = session.push(kp, act)
-        poses[k].copy_(p)
-        fresh[k].copy_(f)
-    return poses.cpu().numpy(), fresh.cpu().numpy()
-
-
-def _oracle_poses(cfg, arch, w, norm_tracks, centres, ms):
-    """The CPU oracle as the model, in the manner of the predict_tracks test: the window of frame ``centres[k]`` of track k by the sequence
-    generator (stride masks aligned globally, the config's padding), flip as a second call, averaged; root-relative."""
-    from oracle import uplift_oracle as O
-    from uplift_upsample_3dhpe_amd.data import PoseTable, SequenceGenerator
-    c = cfg.copy(); c.MASK_STRIDE = ms
-    gen = SequenceGenerator(PoseTable(norm_tracks), seq_len=c.SEQUENCE_LENGTH, subsample=1, stride=c.SEQUENCE_STRIDE, padding_type=c.PADDING_TYPE,
-                            flip_augment=False, mask_stride=ms, stride_mask_align_global=True, shuffle=False)
-    desc = gen.descriptors()
-    starts = np.concatenate([[0], np.cumsum([len(t) for t in norm_tracks])[:-1]])
-    run = starts + np.asarray(centres)
-    assert np.array_equal(desc[run, 0], np.arange(len(norm_tracks))) and np.array_equal(desc[run, 1], centres)
-    b = gen.gather(desc[run], zero_masked=False, with_3d=False)
-    x, m = b["kp2d"].cpu().numpy(), b["stride_mask"].cpu().numpy().astype(bool)
-    _, cen = O.eval_step_with_flip(util.hp_from_arch(arch), w, x, m, c.AUGM_FLIP_KEYPOINT_ORDER)
-    cen = np.asarray(cen, np.float64)
-    return cen - cen[:, c.ROOT_KEYTPOINT:c.ROOT_KEYTPOINT + 1]
 
 
 def _checked_ticks(L, a, S, cap, s_in):

@@ -181,12 +181,12 @@ def test_refusals_name_the_quantity():
 
 def test_a_long_period_is_enumerated_in_numpy():
     """29.97 fps in, 50 out: 2997 source frames per period; 30000/1001 in, 60 out: 3000.  The plan comes from one vectorised pass."""
-    from uplift_upsample_3dhpe_amd import stream
+    from uplift_upsample_3dhpe_amd import rates, stream
     cfg = util.load_config("h36m_351")
     assert _period(29.97, 50, 5) == 2997 and _period((30000, 1001), 60, 5) == 3000
     plan = stream.rate_plan(cfg, (30000, 1001), None, 5, out_fps=60)
     assert (plan.out_c, plan.out_d, plan.max_out) == (1001, 500, 3) and plan.D >= 2
-    src = inspect.getsource(stream._output_ring_depth)
+    src = inspect.getsource(rates._output_ring_depth)
     assert "np.arange" in src and "for " not in src.split('"""')[2]
 
 
@@ -239,7 +239,7 @@ def test_source_has_one_kernel_per_push_no_atomics_and_shares_the_mix():
     csrc = os.path.join(util.ROOT, "uplift-upsample-3dhpe_amd", "csrc")
     code = re.sub(r"//[^\n]*", "", open(os.path.join(csrc, "uu3d_stream_rate.h")).read())
     assert "atomic" not in code.lower()
-    assert "stream_timed_emit_multi_kernel(" in code and "stream_out_reset_kernel(" in code
+    assert "stream_timed_emit_multi_kernel(" in code and "stream_rate_reset_kernel(" in code
     assert not re.search(r"__device__[^\n]*\bresample_mix\(", code) and code.count("resample_mix(") >= 3
-    body = code[code.index("stream_timed_emit_multi_kernel("):code.index("stream_out_reset_kernel(")]
+    body = code[code.index("stream_timed_emit_multi_kernel("):code.index("stream_rate_reset_kernel(")]
     assert "__syncthreads()" in body and "INT32_MAX" in body and "float4" in body

@@ -8,98 +8,12 @@ import math
 import numpy as np
 import pytest
 
-import uplift_upsample_3dhpe_amd as pkg
 from tests import util
+from tests.tracks_util import RES, _bits, _model, _model_rate_frames, _pixel_tracks, _plain_keyframes, _run
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
-RES = [(1000, 1002), (1920, 1080), (640, 480)]
 T, J = 3, 17
-_MODELS = {}
-
-
-def _bits(a):
-    a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _pixel_tracks(lens, seed):
-    rng = np.random.default_rng(seed)
-    return [(rng.uniform(0.0, 1.0, size=(n, J, 2)) * np.array(RES[i % len(RES)], np.float64)).astype(np.float32) for i, n in enumerate(lens)]
-
-
-def _model(cfgname, seed=2):
-    if cfgname not in _MODELS:
-        cfg = util.load_config(cfgname)
-        cfg.BATCH_SIZE = 64
-        arch = pkg.arch_from_config(cfg)
-        w = pkg.init_weights(arch, seed=seed, perturb=0.1)
-        _MODELS[cfgname] = (cfg, arch, w, pkg.build_uplift_upsample_transformer(cfg, weights=w))
-    return _MODELS[cfgname]
-
-
-def _run(session, tracks, ticks, active=None, before_tick=None, valid=None, device_active=False):
-    """Push ``tracks[i][k]`` into slot i at push k; a slot's frame is the next one of ITS track.  ``active(k)`` -> (T,) bools or None;
-    ``valid[i]``: per-frame flags of track i.  One copy to the host at the end.  A session without ``out_fps`` -> (poses (ticks, T, J, 3),
-    fresh (ticks, T)); with it -> (poses (ticks, T, R, J, 3), count (ticks, T), out_frames after the push (ticks, T)); ``check_range()`` is
-    False and ``captures`` is 1 throughout."""
-    multi = session.max_out is not None
-    poses = torch.zeros((ticks, T) + ((session.max_out,) if multi else ()) + (J, 3), dtype=torch.float32, device="cuda")
-    flags = torch.zeros((ticks, T), dtype=torch.int32 if multi else torch.bool, device="cuda")
-    total = torch.zeros((ticks, T), dtype=torch.int32, device="cuda")
-    used = [0] * T
-    for k in range(ticks):
-        if before_tick is not None:
-            before_tick(k, used)
-        act = None if active is None else np.asarray(active(k), bool)
-        kp = np.zeros((T, J, 2), np.float32)
-        ok = np.ones(T, bool)
-        for i in range(T):
-            if act is None or act[i]:
-                kp[i] = tracks[i][used[i]]
-                if valid is not None:
-                    ok[i] = bool(valid[i][used[i]])
-                used[i] += 1
-        a = act if act is None or not device_active else torch.from_numpy(act).cuda()
-        p, f = session.push(kp, a, **({} if valid is None else {"valid": ok}))
-        assert tuple(p.shape) == tuple(poses.shape[1:]) and p.is_cuda and f.is_cuda and session.captures == 1
-        poses[k].copy_(p)
-        flags[k].copy_(f)
-        if multi:
-            total[k].copy_(session.out_frames)
-        if k % 64 == 63:
-            assert session.check_range() is False
-    assert session.check_range() is False and session.captures == 1
-    return (poses.cpu().numpy(), flags.cpu().numpy()) + ((total.cpu().numpy(),) if multi else ())
-
-
-def _model_rate_frames(tracks, fps, n_model, valid=None):
-    """The first ``n_model`` model-rate frames of every track (uu3d_resample_tracks), normalised -> list of (n_model, J, 2) host arrays
-    (and, with ``valid``, their flags)."""
-    from uplift_upsample_3dhpe_amd import predict
-    table, model_lens, _ = predict.resampled_pose_table(tracks, torch.device("cuda", 0), fps, resolutions=RES[:len(tracks)], valid=valid)
-    assert (model_lens >= n_model).all()
-    kp = torch.split(table.kp2d, [int(n) for n in model_lens], 0)
-    frames = [t[:n_model].cpu().numpy() for t in kp]
-    if valid is None:
-        return frames
-    return frames, [v[:n_model].cpu().numpy() != 0 for v in torch.split(table.valid, [int(n) for n in model_lens], 0)]
-
-
-def _plain_keyframes(model, cfg, ms, a_m, frames):
-    """The model-rate frames through a plain session at lookahead a_m -> {centre: (T, J, 3) pose}."""
-    from uplift_upsample_3dhpe_amd import stream
-    s = stream.StreamSession(model, cfg, slots=T, resolutions=None, mask_stride=ms, flip=True, lookahead=a_m)
-    n = len(frames[0])
-    poses, fresh = _run(s, frames, n)
-    s.close()
-    keys = {}
-    for t in range(n):
-        if fresh[t].all():
-            keys[t - a_m] = poses[t]
-        else:
-            assert not fresh[t].any()
-    return keys
 
 
 def _check_slot(plan, keys, slot, ticks, poses, counts, total, first_push=0):

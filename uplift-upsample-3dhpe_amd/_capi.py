@@ -322,3 +322,8 @@ def check(lib, status, handle=None):
         detail = lib.uu3d_last_error(handle).decode() if True else ""
         base = lib.uu3d_status_string(status).decode()
         raise Uu3dError(status, f"{base}: {detail}" if detail else base)
+
+
+def ptr(t):
+    """The device (or pinned host) address of a tensor as a ctypes argument; None stays None (a null pointer)."""
+    return None if t is None else C.c_void_p(t.data_ptr())

@@ -567,307 +567,7 @@ int uu3d_assemble_tracks(const float* plain, const float* flipped, int64_t num_w
     return hipGetLastError() == hipSuccess ? UU3D_OK : UU3D_ERR_HIP;
 }
 
-// ---- live tracks (uu3d_stream.h): the session's state block and the four launches around uu3d_frame_features / uu3d_forward_frames_ex ----
-namespace {
-// the session's settings checked against the model; nullptr = fine, else what is wrong
-const char* stream_config_error(const uu3d_model* m, const uu3d_stream_config* s) {
-    if (!s) return "null uu3d_stream_config";
-    const uu3d_config& c = m->cfg;
-    if (s->slots < 1 || s->slots > (1 << 20)) return "slots must be in [1, 2^20]";
-    if (s->seq_stride < 1 || s->pred_stride < 1) return "seq_stride and pred_stride must be >= 1";
-    if (s->mask_stride < s->seq_stride || s->mask_stride % s->seq_stride != 0) return "mask_stride must be a multiple of seq_stride";
-    if (s->lookahead < 0 || (int64_t)s->lookahead > (int64_t)(c.num_frames / 2) * s->seq_stride) return "lookahead must be in [0, (num_frames / 2) * seq_stride]";
-    if (s->root_index >= c.num_keypoints) return "root_index must be below num_keypoints (negative: absolute poses)";
-    if ((int64_t)s->seq_stride * c.num_frames > (1 << 28)) return "seq_stride too large";
-    const StreamLayout L = stream_layout(s->slots, c.num_frames, c.num_keypoints, c.d_temporal, s->seq_stride, s->mask_stride, s->lookahead, s->flip);
-    if (L.table_rows > INT32_MAX / 2 || (int64_t)L.halves * s->slots * c.num_frames > INT32_MAX / 2) return "slots x ring capacity too large";
-    return nullptr;
-}
-StreamLayout stream_layout_of(const uu3d_model* m, const uu3d_stream_config* s) {
-    const uu3d_config& c = m->cfg;
-    return stream_layout(s->slots, c.num_frames, c.num_keypoints, c.d_temporal, s->seq_stride, s->mask_stride, s->lookahead, s->flip);
-}
-int stream_check(uu3d_model* m, const uu3d_stream_config* s, const char* who) {
-    if (m->generic) return fail(m, UU3D_ERR_UNSUPPORTED, std::string(who) + ": handles with generic dims have no frames form (compiled dims only)");
-    if (const char* e = stream_config_error(m, s)) return fail(m, UU3D_ERR_INVALID_ARGUMENT, std::string(who) + ": " + e);
-    return UU3D_OK;
-}
-}  // namespace
-
-int uu3d_stream_state_layout(const uu3d_model* mc, const uu3d_stream_config* s, uu3d_stream_layout* out) {
-    auto* m = const_cast<uu3d_model*>(mc);
-    if (!m || !out) return UU3D_ERR_INVALID_ARGUMENT;
-    if (const int st = stream_check(m, s, "uu3d_stream_state_layout")) return st;
-    const StreamLayout L = stream_layout_of(m, s);
-    out->ring_capacity = L.cap; out->table_rows = L.table_rows; out->zero_row = L.zero_row;
-    out->frames_offset = (int64_t)L.off_frames; out->held_offset = (int64_t)L.off_held; out->table_offset = (int64_t)L.off_table;
-    out->bytes = (int64_t)L.bytes;
-    return UU3D_OK;
-}
-
-size_t uu3d_stream_state_bytes(const uu3d_model* m, const uu3d_stream_config* s) {
-    uu3d_stream_layout l;
-    return uu3d_stream_state_layout(m, s, &l) == UU3D_OK ? (size_t)l.bytes : 0;
-}
-
-namespace {
-// MISSED DETECTIONS need the masked token: a model without strided input has none
-int stream_valid_check(uu3d_model* m, const char* who) {
-    if (!m->cfg.has_strided_input) return fail(m, UU3D_ERR_UNSUPPORTED, std::string(who) + ": frame validity needs a model with strided input (the masked token)");
-    return UU3D_OK;
-}
-int stream_stage(uu3d_model* m, const uu3d_stream_config* s, const float* kp, const double* resolution, const uint8_t* active,
-                 const int32_t* flip_order, const uint8_t* valid_in, uint8_t* valid_out, float* frames_out, void* stream) {
-    if (!kp || !active || !frames_out || (s->flip && !flip_order)) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_stage: null buffer");
-    if (((uintptr_t)frames_out & 15) != 0 || ((uintptr_t)kp & 7) != 0) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_stage: frames_out must be 16-byte, kp 8-byte aligned");
-    const int halves = s->flip ? 2 : 1;
-    const long threads = ((long)halves * s->slots * m->cfg.num_keypoints + 1) / 2;
-    hipLaunchKernelGGL(stream_stage_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       kp, resolution, active, flip_order, s->slots, m->cfg.num_keypoints, halves, valid_in, valid_out, frames_out);
-    return hipGetLastError() == hipSuccess ? UU3D_OK : fail(m, UU3D_ERR_HIP, "uu3d_stream_stage: launch failed");
-}
-}  // namespace
-
-int uu3d_stream_stage(uu3d_model* m, const uu3d_stream_config* s, const float* kp, const double* resolution, const uint8_t* active,
-                      const int32_t* flip_order, float* frames_out, void* stream) {
-    if (!m) return UU3D_ERR_INVALID_ARGUMENT;
-    if (const int st = stream_check(m, s, "uu3d_stream_stage")) return st;
-    return stream_stage(m, s, kp, resolution, active, flip_order, nullptr, nullptr, frames_out, stream);
-}
-
-int uu3d_stream_stage_valid(uu3d_model* m, const uu3d_stream_config* s, const float* kp, const double* resolution, const uint8_t* active,
-                            const int32_t* flip_order, const uint8_t* valid_in, uint8_t* valid_out, float* frames_out, void* stream) {
-    if (!m) return UU3D_ERR_INVALID_ARGUMENT;
-    if (const int st = stream_check(m, s, "uu3d_stream_stage_valid")) return st;
-    if (const int st = stream_valid_check(m, "uu3d_stream_stage_valid")) return st;
-    if (!valid_out) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_stage_valid: null valid_out");
-    return stream_stage(m, s, kp, resolution, active, flip_order, valid_in, valid_out, frames_out, stream);
-}
-
-namespace {
-int stream_commit(uu3d_model* m, const uu3d_stream_config* s, void* state, const float* features, const uint8_t* active, const uint8_t* valid,
-                  uint8_t* valid_state, int32_t* rows, uint8_t* stride_mask, uint8_t* fresh, void* stream) {
-    if (!state || !features || !active || !rows || !stride_mask || !fresh) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_commit: null buffer");
-    if (((uintptr_t)state & 255) != 0 || ((uintptr_t)features & 15) != 0) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_commit: state must be 256-byte, features 16-byte aligned");
-    const StreamLayout L = stream_layout_of(m, s);
-    StreamParams p{};
-    p.slots = s->slots; p.N = m->cfg.num_frames; p.dt = m->cfg.d_temporal; p.seq_stride = s->seq_stride; p.s_in = s->mask_stride;
-    p.pred_stride = s->pred_stride; p.lookahead = s->lookahead; p.cap = L.cap; p.halves = L.halves; p.pad_edge = s->pad_edge != 0;
-    p.zero_row = (int)L.zero_row;
-    p.masked_row = m->cfg.has_strided_input ? -1 : (int)L.zero_row;      // (no strided input: a dropped frame is read as zeros, eval.py:67)
-    char* base = (char*)state;
-    hipLaunchKernelGGL(stream_commit_kernel, dim3(s->slots), dim3(256), 0, (hipStream_t)stream, p, features, active,
-                       (int32_t*)(base + L.off_frames), (float*)(base + L.off_table), rows, stride_mask, fresh, valid, valid_state);
-    return hipGetLastError() == hipSuccess ? UU3D_OK : fail(m, UU3D_ERR_HIP, "uu3d_stream_commit: launch failed");
-}
-}  // namespace
-
-int uu3d_stream_commit(uu3d_model* m, const uu3d_stream_config* s, void* state, const float* features, const uint8_t* active,
-                       int32_t* rows, uint8_t* stride_mask, uint8_t* fresh, void* stream) {
-    if (!m) return UU3D_ERR_INVALID_ARGUMENT;
-    if (const int st = stream_check(m, s, "uu3d_stream_commit")) return st;
-    return stream_commit(m, s, state, features, active, nullptr, nullptr, rows, stride_mask, fresh, stream);
-}
-
-size_t uu3d_stream_valid_bytes(const uu3d_model* mc, const uu3d_stream_config* s) {
-    auto* m = const_cast<uu3d_model*>(mc);
-    if (!m || stream_check(m, s, "uu3d_stream_valid_bytes") != UU3D_OK) return 0;
-    return (size_t)s->slots * (size_t)(stream_layout_of(m, s).cap + 1);
-}
-
-int uu3d_stream_commit_valid(uu3d_model* m, const uu3d_stream_config* s, void* state, const float* features, const uint8_t* active,
-                             const uint8_t* valid, void* valid_state, int32_t* rows, uint8_t* stride_mask, uint8_t* fresh, void* stream) {
-    if (!m) return UU3D_ERR_INVALID_ARGUMENT;
-    if (const int st = stream_check(m, s, "uu3d_stream_commit_valid")) return st;
-    if (const int st = stream_valid_check(m, "uu3d_stream_commit_valid")) return st;
-    if (!valid || !valid_state) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_commit_valid: null validity buffer");
-    return stream_commit(m, s, state, features, active, valid, (uint8_t*)valid_state, rows, stride_mask, fresh, stream);
-}
-
-int uu3d_stream_emit(uu3d_model* m, const uu3d_stream_config* s, void* state, const float* central, const int32_t* flip_order,
-                     const uint8_t* fresh, float* out, void* stream) {
-    if (!m) return UU3D_ERR_INVALID_ARGUMENT;
-    if (const int st = stream_check(m, s, "uu3d_stream_emit")) return st;
-    if (!state || !central || !fresh || !out || (s->flip && !flip_order)) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_emit: null buffer");
-    if (((uintptr_t)state & 255) != 0 || ((uintptr_t)out & 15) != 0) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_emit: state must be 256-byte, out 16-byte aligned");
-    const StreamLayout L = stream_layout_of(m, s);
-    const long threads = ((long)s->slots * L.per_pose + 3) / 4;
-    hipLaunchKernelGGL(stream_emit_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, central, L.halves,
-                       flip_order, fresh, s->slots, m->cfg.num_keypoints, s->root_index < 0 ? -1 : s->root_index,
-                       (float*)((char*)state + L.off_held), out);
-    return hipGetLastError() == hipSuccess ? UU3D_OK : fail(m, UU3D_ERR_HIP, "uu3d_stream_emit: launch failed");
-}
-
-int uu3d_stream_reset(uu3d_model* m, const uu3d_stream_config* s, void* state, const uint8_t* slot_mask, void* stream) {
-    if (!m) return UU3D_ERR_INVALID_ARGUMENT;
-    if (const int st = stream_check(m, s, "uu3d_stream_reset")) return st;
-    if (!state || ((uintptr_t)state & 255) != 0) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_reset: state must be a 256-byte aligned block");
-    const StreamLayout L = stream_layout_of(m, s);
-    const long threads = (long)s->slots * L.per_pose;
-    hipLaunchKernelGGL(stream_reset_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, slot_mask, s->slots,
-                       L.per_pose, (int32_t*)((char*)state + L.off_frames), (float*)((char*)state + L.off_held));
-    return hipGetLastError() == hipSuccess ? UU3D_OK : fail(m, UU3D_ERR_HIP, "uu3d_stream_reset: launch failed");
-}
-
-// ---- live tracks at any frame rate (uu3d_stream_rate.h): the state behind the plain session's and the launches around its sub-ticks ----
-namespace {
-const char* stream_rate_error(const uu3d_stream_rate* r) {
-    if (!r) return "null uu3d_stream_rate";
-    if (r->a < 1 || r->a >= (1 << 20) || r->b < 1 || r->b >= (1 << 20)) return "a and b must be in [1, 2^20)";
-    if (r->lookahead < 0 || r->lookahead > (1 << 24)) return "the source lookahead must be in [0, 2^24]";
-    if (r->key_ring < 1 || r->key_ring > 4096) return "key_ring must be in [1, 4096]";
-    return nullptr;
-}
-int stream_rate_check(uu3d_model* m, const uu3d_stream_config* s, const uu3d_stream_rate* r, const void* state, const char* who) {
-    if (const int st = stream_check(m, s, who)) return st;
-    if (const char* e = stream_rate_error(r)) return fail(m, UU3D_ERR_INVALID_ARGUMENT, std::string(who) + ": " + e);
-    if (!state || ((uintptr_t)state & 255) != 0) return fail(m, UU3D_ERR_INVALID_ARGUMENT, std::string(who) + ": state must be a 256-byte aligned block");
-    return UU3D_OK;
-}
-RateParams rate_params(const uu3d_model* m, const uu3d_stream_config* s, const uu3d_stream_rate* r, const StreamLayout& L, const RateLayout& R) {
-    RateParams p{};
-    p.slots = s->slots; p.J = m->cfg.num_keypoints; p.halves = L.halves; p.per_pose = L.per_pose; p.a = r->a; p.b = r->b;
-    p.lookahead = r->lookahead; p.model_lookahead = s->lookahead; p.pred_stride = s->pred_stride; p.key_ring = R.key_ring; p.key_stride = R.key_stride;
-    return p;
-}
-}  // namespace
-
-int uu3d_stream_rate_state_layout(const uu3d_model* mc, const uu3d_stream_config* s, const uu3d_stream_rate* r, uu3d_stream_rate_layout* out) {
-    auto* m = const_cast<uu3d_model*>(mc);
-    if (!m || !out) return UU3D_ERR_INVALID_ARGUMENT;
-    if (const int st = stream_check(m, s, "uu3d_stream_rate_state_layout")) return st;
-    if (const char* e = stream_rate_error(r)) return fail(m, UU3D_ERR_INVALID_ARGUMENT, std::string("uu3d_stream_rate_state_layout: ") + e);
-    const RateLayout R = rate_layout(stream_layout_of(m, s), m->cfg.num_keypoints, r->key_ring);
-    out->source_frames_offset = (int64_t)R.off_source_frames; out->pushed_offset = (int64_t)R.off_pushed;
-    out->source_valid_offset = (int64_t)R.off_source_valid; out->source_offset = (int64_t)R.off_source; out->keys_offset = (int64_t)R.off_keys;
-    out->key_stride = R.key_stride; out->out_held_offset = (int64_t)R.off_out_held; out->bytes = (int64_t)R.bytes;
-    return UU3D_OK;
-}
-
-int uu3d_stream_source_push(uu3d_model* m, const uu3d_stream_config* s, const uu3d_stream_rate* r, void* state, const float* kp,
-                            const uint8_t* active, const uint8_t* valid_in, int32_t track_valid, void* stream) {
-    if (!m) return UU3D_ERR_INVALID_ARGUMENT;
-    if (const int st = stream_rate_check(m, s, r, state, "uu3d_stream_source_push")) return st;
-    if (!kp || !active || ((uintptr_t)kp & 7) != 0) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_source_push: kp (8-byte aligned) and active must be given");
-    if (track_valid) if (const int st = stream_valid_check(m, "uu3d_stream_source_push")) return st;
-    const RateLayout R = rate_layout(stream_layout_of(m, s), m->cfg.num_keypoints, r->key_ring);
-    char* base = (char*)state;
-    hipLaunchKernelGGL(stream_source_push_kernel, dim3(s->slots), dim3(64), 0, (hipStream_t)stream, kp, active, valid_in, track_valid ? 1 : 0,
-                       m->cfg.num_keypoints, (int32_t*)(base + R.off_source_frames), (uint8_t*)(base + R.off_pushed),
-                       (uint8_t*)(base + R.off_source_valid), (float*)(base + R.off_source));
-    return hipGetLastError() == hipSuccess ? UU3D_OK : fail(m, UU3D_ERR_HIP, "uu3d_stream_source_push: launch failed");
-}
-
-int uu3d_stream_resample_stage(uu3d_model* m, const uu3d_stream_config* s, const uu3d_stream_rate* r, const void* state, const double* resolution,
-                               const int32_t* flip_order, uint8_t* sub_active, uint8_t* valid_out, float* frames_out, void* stream) {
-    if (!m) return UU3D_ERR_INVALID_ARGUMENT;
-    if (const int st = stream_rate_check(m, s, r, state, "uu3d_stream_resample_stage")) return st;
-    if (!sub_active || !frames_out || (s->flip && !flip_order)) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_resample_stage: null buffer");
-    if (((uintptr_t)frames_out & 15) != 0) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_resample_stage: frames_out must be 16-byte aligned");
-    if (valid_out) if (const int st = stream_valid_check(m, "uu3d_stream_resample_stage")) return st;
-    const StreamLayout L = stream_layout_of(m, s);
-    const RateLayout R = rate_layout(L, m->cfg.num_keypoints, r->key_ring);
-    const char* base = (const char*)state;
-    const long threads = ((long)L.halves * s->slots * m->cfg.num_keypoints + 1) / 2;
-    hipLaunchKernelGGL(stream_resample_stage_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       rate_params(m, s, r, L, R), (const int32_t*)(base + R.off_source_frames), (const int32_t*)(base + L.off_frames),
-                       (const uint8_t*)(base + R.off_source_valid), (const float*)(base + R.off_source), resolution, flip_order, sub_active,
-                       valid_out, frames_out);
-    return hipGetLastError() == hipSuccess ? UU3D_OK : fail(m, UU3D_ERR_HIP, "uu3d_stream_resample_stage: launch failed");
-}
-
-int uu3d_stream_file_keyframe(uu3d_model* m, const uu3d_stream_config* s, const uu3d_stream_rate* r, void* state, const uint8_t* fresh, void* stream) {
-    if (!m) return UU3D_ERR_INVALID_ARGUMENT;
-    if (const int st = stream_rate_check(m, s, r, state, "uu3d_stream_file_keyframe")) return st;
-    if (!fresh) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_file_keyframe: null fresh");
-    const StreamLayout L = stream_layout_of(m, s);
-    const RateLayout R = rate_layout(L, m->cfg.num_keypoints, r->key_ring);
-    char* base = (char*)state;
-    const long threads = (long)s->slots * (R.key_stride / 4);
-    hipLaunchKernelGGL(stream_file_keyframe_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       rate_params(m, s, r, L, R), (const int32_t*)(base + L.off_frames), fresh, (const float*)(base + L.off_held),
-                       (float*)(base + R.off_keys));
-    return hipGetLastError() == hipSuccess ? UU3D_OK : fail(m, UU3D_ERR_HIP, "uu3d_stream_file_keyframe: launch failed");
-}
-
-int uu3d_stream_timed_emit(uu3d_model* m, const uu3d_stream_config* s, const uu3d_stream_rate* r, void* state, float* out, uint8_t* fresh_out,
-                           void* stream) {
-    if (!m) return UU3D_ERR_INVALID_ARGUMENT;
-    if (const int st = stream_rate_check(m, s, r, state, "uu3d_stream_timed_emit")) return st;
-    if (!out || !fresh_out || ((uintptr_t)out & 15) != 0) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_timed_emit: out (16-byte aligned) and fresh_out must be given");
-    const StreamLayout L = stream_layout_of(m, s);
-    const RateLayout R = rate_layout(L, m->cfg.num_keypoints, r->key_ring);
-    char* base = (char*)state;
-    const long threads = ((long)s->slots * L.per_pose + 3) / 4;
-    hipLaunchKernelGGL(stream_timed_emit_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       rate_params(m, s, r, L, R), (const int32_t*)(base + R.off_source_frames), (const uint8_t*)(base + R.off_pushed),
-                       (const float*)(base + R.off_keys), (float*)(base + R.off_out_held), out, fresh_out);
-    return hipGetLastError() == hipSuccess ? UU3D_OK : fail(m, UU3D_ERR_HIP, "uu3d_stream_timed_emit: launch failed");
-}
-
-int uu3d_stream_rate_reset(uu3d_model* m, const uu3d_stream_config* s, const uu3d_stream_rate* r, void* state, const uint8_t* slot_mask, void* stream) {
-    if (!m) return UU3D_ERR_INVALID_ARGUMENT;
-    if (const int st = stream_rate_check(m, s, r, state, "uu3d_stream_rate_reset")) return st;
-    if (const int st = uu3d_stream_reset(m, s, state, slot_mask, stream)) return st;
-    const StreamLayout L = stream_layout_of(m, s);
-    const RateLayout R = rate_layout(L, m->cfg.num_keypoints, r->key_ring);
-    char* base = (char*)state;
-    const long threads = (long)s->slots * L.per_pose;
-    hipLaunchKernelGGL(stream_rate_reset_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, slot_mask, s->slots,
-                       L.per_pose, (int32_t*)(base + R.off_source_frames), (uint8_t*)(base + R.off_pushed), (float*)(base + R.off_out_held));
-    return hipGetLastError() == hipSuccess ? UU3D_OK : fail(m, UU3D_ERR_HIP, "uu3d_stream_rate_reset: launch failed");
-}
-
-// ---- a live session with an output rate of its own (StreamSession(fps=F, out_fps=G)): every due pose per push ----
-namespace {
-const char* stream_out_error(const uu3d_stream_out* o) {
-    if (!o) return "null uu3d_stream_out";
-    if (o->c < 1 || o->c >= (1 << 20) || o->d < 1 || o->d >= (1 << 20)) return "c and d must be in [1, 2^20)";
-    if (o->pos_num < 1 || o->pos_num >= (1 << 20) || o->pos_den < 1 || o->pos_den >= (1 << 20)) return "pos_num and pos_den must be in [1, 2^20)";
-    if (o->max_out < 1 || o->max_out > 64 || (long)o->max_out * o->d < o->c) return "max_out must be in [ceil(c / d), 64]";
-    return nullptr;
-}
-OutParams out_params(const uu3d_stream_out* o) { return OutParams{o->c, o->d, o->pos_num, o->pos_den, o->max_out}; }
-}  // namespace
-
-int uu3d_stream_out_state_layout(const uu3d_model* mc, const uu3d_stream_config* s, const uu3d_stream_rate* r, const uu3d_stream_out* o,
-                                 uu3d_stream_out_layout* out) {
-    auto* m = const_cast<uu3d_model*>(mc);
-    if (!m || !out) return UU3D_ERR_INVALID_ARGUMENT;
-    if (const int st = stream_check(m, s, "uu3d_stream_out_state_layout")) return st;
-    if (const char* e = stream_rate_error(r)) return fail(m, UU3D_ERR_INVALID_ARGUMENT, std::string("uu3d_stream_out_state_layout: ") + e);
-    if (const char* e = stream_out_error(o)) return fail(m, UU3D_ERR_INVALID_ARGUMENT, std::string("uu3d_stream_out_state_layout: ") + e);
-    const RateLayout R = rate_layout(stream_layout_of(m, s), m->cfg.num_keypoints, r->key_ring);
-    out->out_frames_offset = (int64_t)out_frames_offset(R); out->bytes = (int64_t)out_layout_bytes(R, s->slots);
-    return UU3D_OK;
-}
-
-int uu3d_stream_timed_emit_multi(uu3d_model* m, const uu3d_stream_config* s, const uu3d_stream_rate* r, const uu3d_stream_out* o, void* state,
-                                 float* poses, int32_t* count, void* stream) {
-    if (!m) return UU3D_ERR_INVALID_ARGUMENT;
-    if (const int st = stream_rate_check(m, s, r, state, "uu3d_stream_timed_emit_multi")) return st;
-    if (const char* e = stream_out_error(o)) return fail(m, UU3D_ERR_INVALID_ARGUMENT, std::string("uu3d_stream_timed_emit_multi: ") + e);
-    if (!poses || !count || ((uintptr_t)poses & 15) != 0) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_timed_emit_multi: poses (16-byte aligned) and count must be given");
-    const StreamLayout L = stream_layout_of(m, s);
-    const RateLayout R = rate_layout(L, m->cfg.num_keypoints, r->key_ring);
-    char* base = (char*)state;
-    hipLaunchKernelGGL(stream_timed_emit_multi_kernel, dim3(s->slots), dim3(256), 0, (hipStream_t)stream, rate_params(m, s, r, L, R), out_params(o),
-                       (const int32_t*)(base + R.off_source_frames), (const uint8_t*)(base + R.off_pushed), (const float*)(base + R.off_keys),
-                       (int32_t*)(base + out_frames_offset(R)), poses, count);
-    return hipGetLastError() == hipSuccess ? UU3D_OK : fail(m, UU3D_ERR_HIP, "uu3d_stream_timed_emit_multi: launch failed");
-}
-
-int uu3d_stream_out_reset(uu3d_model* m, const uu3d_stream_config* s, const uu3d_stream_rate* r, const uu3d_stream_out* o, void* state,
-                          const uint8_t* slot_mask, void* stream) {
-    if (!m) return UU3D_ERR_INVALID_ARGUMENT;
-    if (const int st = stream_rate_check(m, s, r, state, "uu3d_stream_out_reset")) return st;
-    if (const char* e = stream_out_error(o)) return fail(m, UU3D_ERR_INVALID_ARGUMENT, std::string("uu3d_stream_out_reset: ") + e);
-    if (const int st = uu3d_stream_rate_reset(m, s, r, state, slot_mask, stream)) return st;
-    const RateLayout R = rate_layout(stream_layout_of(m, s), m->cfg.num_keypoints, r->key_ring);
-    hipLaunchKernelGGL(stream_out_reset_kernel, dim3((unsigned)((s->slots + 255) / 256)), dim3(256), 0, (hipStream_t)stream, slot_mask, s->slots,
-                       (int32_t*)((char*)state + out_frames_offset(R)));
-    return hipGetLastError() == hipSuccess ? UU3D_OK : fail(m, UU3D_ERR_HIP, "uu3d_stream_out_reset: launch failed");
-}
+#include "uu3d_stream_api.inc"
 
 int uu3d_world_to_cam_2d(const float* world, const float* cams, int32_t B, int32_t N, int32_t J, float* cam3d, float* kp2d, void* stream) {
     if (!world || !cams || B < 1 || N < 1 || J < 1 || (!cam3d && !kp2d)) return UU3D_ERR_INVALID_ARGUMENT;

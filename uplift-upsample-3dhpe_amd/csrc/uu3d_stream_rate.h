@@ -8,10 +8,10 @@
 //   stream_file_keyframe_kernel   after stream_emit_kernel: a fresh central pose into the slot's keyframe ring, place (centre / P) % D
 //   stream_timed_emit_kernel      once per push: the pose of source frame q = newest - lookahead, read at model position q a / b from the
 //                                 piecewise-linear motion through the kept keyframes (evaluation.keyframe_plan_at's rule)
-//   stream_rate_reset_kernel      chosen slots: source counter 0, held output pose 0
 // and, for a session with an output rate of its own (StreamSession(fps=F, out_fps=G)), in place of stream_timed_emit_kernel:
 //   stream_timed_emit_multi_kernel  once per push: EVERY output frame that became due at this push, up to R = ceil(G / F) poses per slot
-//   stream_out_reset_kernel         chosen slots: output counter 0
+// Both read a pose from the kept keyframes with keyframe_read.  For either kind of session:
+//   stream_rate_reset_kernel      chosen slots: every counter 0 (model, source, output), both held poses 0
 // The new state lies behind the plain session's (StreamLayout) in the same caller-allocated block.  No atomics, one writer per output
 // element, every counter is read and advanced on the device, all arguments are the same at every push: a sub-tick in which no slot is due
 // changes no byte of the state and none of the outputs of the push.
@@ -176,10 +176,23 @@ stream_file_keyframe_kernel(const RateParams p, const int32_t* __restrict__ fram
     *reinterpret_cast<float4*>(keys + ((long)t * p.key_ring + place) * p.key_stride + c) = make_float4(v[0], v[1], v[2], v[3]);
 }
 
+// Column `col` of a slot's pose at model position u = num / den, read from the slot's keyframe ring (`ring`: its first float) through the
+// piecewise-linear motion through the kept keyframes, P model frames apart (rates.keyframe_bracket on the host): k0 = floor(u / P) P;
+// u == k0 gives keyframe k0's bits, anything else resample_mix(k0, k0 + P, w) -- float64, rounded once to float32 -- with
+// w = (num - k0 den) / (P den), one float64 division of two integers (keyframe_plan_at's weight).  The place is taken modulo the ring.
+__device__ __forceinline__ float keyframe_read(const float* __restrict__ ring, const int key_ring, const int key_stride, const long P, const long num,
+                                               const long den, const int col)
+{
+    const long k0 = num / den / P * P;
+    const long off = num - k0 * den;                                      // (u - k0) den, in [0, P den)
+    const float a = ring[(k0 / P) % key_ring * key_stride + col];
+    if (off == 0) return a;
+    const float b = ring[(k0 / P + 1) % key_ring * key_stride + col];
+    return resample_mix(a, b, (double)off / (double)(P * den));
+}
+
 // Once per push, behind its sub-ticks.  A slot that took a frame at this push (pushed) and whose q = newest source frame - lookahead is
-// >= 0 gets the pose at model position u = q a / b: keyframes k0 = floor(u / P) P and k1 = k0 where u == k0, else k0 + P; u == k0 gives
-// keyframe k0's bits, anything else resample_mix(k0, k1, w) -- float64, rounded once to float32 -- with w = (q a - k0 b) / (P b), one
-// float64 division of two integers (keyframe_plan_at's weight).  The host's plan (stream.rate_plan) guarantees that both keyframes have
+// >= 0 gets the pose at model position u = q a / b (keyframe_read).  The host's plan (rates.rate_plan) guarantees that both keyframes have
 // been emitted and are still in the ring.  Any other slot keeps its held pose; fresh_out says which is which.  out (T, J * 3) and
 // out_held likewise: one thread per four consecutive floats, as stream_emit_kernel.
 static __global__ void __launch_bounds__(256)
@@ -201,34 +214,12 @@ stream_timed_emit_kernel(const RateParams p, const int32_t* __restrict__ source_
         if (e == e0 + k && r == 0) fresh_out[t] = is_fresh ? 1 : 0;
         if (!is_fresh) { v[k] = out_held[e]; continue; }
         any_fresh = true;
-        const long num = q * p.a, P = p.pred_stride;
-        const long k0 = num / p.b / P * P;
-        const long off = num - k0 * p.b;                                  // (u - k0) b, in [0, P b)
-        const float* ring = keys + t * p.key_ring * p.key_stride + r;
-        const float a = ring[(k0 / P) % p.key_ring * p.key_stride];
-        if (off == 0) { v[k] = a; continue; }
-        const float b = ring[(k0 / P + 1) % p.key_ring * p.key_stride];
-        v[k] = resample_mix(a, b, (double)off / (double)(P * p.b));
+        v[k] = keyframe_read(keys + t * p.key_ring * p.key_stride, p.key_ring, p.key_stride, p.pred_stride, q * p.a, p.b, r);
     }
     if (e0 + 4 <= total) {
         *reinterpret_cast<float4*>(out + e0) = make_float4(v[0], v[1], v[2], v[3]);
         if (any_fresh) *reinterpret_cast<float4*>(out_held + e0) = make_float4(v[0], v[1], v[2], v[3]);
     } else for (int k = 0; e0 + k < total; ++k) { out[e0 + k] = v[k]; if (any_fresh) out_held[e0 + k] = v[k]; }
-}
-
-// slot_mask (T) u8 or nullptr (every slot): the chosen slots' source counters and pushed bytes go back to 0 and their held output poses to
-// zeros (stream_reset_kernel does the same to the model counters and the sub-ticks' held poses).  The rings stay: nothing reads a source
-// frame or a keyframe its slot's counters have not reached.
-static __global__ void __launch_bounds__(256)
-stream_rate_reset_kernel(const uint8_t* __restrict__ slot_mask, const int T, const int per_pose, int32_t* __restrict__ source_frames,
-                         uint8_t* __restrict__ pushed, float* __restrict__ out_held)
-{
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (long)T * per_pose) return;
-    const int t = (int)(i / per_pose);
-    if (slot_mask != nullptr && slot_mask[t] == 0) return;
-    out_held[i] = 0.f;
-    if (i - (long)t * per_pose == 0) { source_frames[t] = 0; pushed[t] = 0; }
 }
 
 // The output rate of a session, next to RateParams: G / F = c / d and model_fps / G = un / ud, both in lowest terms with terms below 2^20
@@ -240,10 +231,8 @@ struct OutParams { int c, d, un, ud, max_out; };
 // at this push and whose q = newest source frame - lookahead is >= 0 has, after the push, emitted every output frame i <= hi =
 // floor(q c / d): the frames whose time i / G is not later than q / F.  n = hi + 1 - out_frames[slot], clamped to [0, R], of them are new;
 // any other slot has n = 0.  Row r < n of poses (T, R, J * 3) is output frame i = out_frames[slot] + r, read at model position
-// u = i un / ud by stream_timed_emit_kernel's rule: k0 = floor(u / P) P; u == k0 gives keyframe k0's bits, anything else
-// resample_mix(k0, k0 + P, w), w = (i un - k0 ud) / (P ud), one float64 division of two integers.  The host's plan (stream.rate_plan)
-// guarantees that both keyframes of every due frame have been emitted and are still in the ring; the place is taken modulo the ring
-// whatever the counters hold.  Rows r >= n are zeros; count[slot] = n.  The counter stops at INT32_MAX instead of wrapping.
+// u = i un / ud (keyframe_read).  The host's plan (rates.rate_plan) guarantees that both keyframes of every due frame have been emitted
+// and are still in the ring; the place is taken modulo the ring whatever the counters hold.  Rows r >= n are zeros; count[slot] = n.  The counter stops at INT32_MAX instead of wrapping.
 // A slot's R rows are R * J * 3 consecutive floats, 16-byte aligned only where slot * R * J * 3 is a multiple of four: the workgroup walks
 // the 16-byte quads of poses that overlap its rows, stores a quad that lies wholly inside them at once and the floats of a quad it shares
 // with a neighbouring slot one by one -- every element has one writer.
@@ -262,7 +251,7 @@ stream_timed_emit_multi_kernel(const RateParams p, const OutParams o, const int3
     }
     __syncthreads();                                                     // every read of the counter is done
     if (threadIdx.x == 0) { out_frames[slot] = (int32_t)(done + n); count[slot] = (int32_t)n; }
-    const long per = p.per_pose, P = p.pred_stride;
+    const long per = p.per_pose;
     const long start = (long)slot * o.max_out * per, end = start + (long)o.max_out * per;
     const float* ring = keys + (long)slot * p.key_ring * p.key_stride;
     for (long quad = start / 4 + threadIdx.x; quad * 4 < end; quad += 256) {
@@ -275,28 +264,32 @@ stream_timed_emit_multi_kernel(const RateParams p, const OutParams o, const int3
             if (rel < 0 || e0 + k >= end) continue;
             const long r = rel / per;
             if (r >= n) continue;
-            const int col = (int)(rel - r * per);
-            const long num = (done + r) * o.un;
-            const long k0 = num / o.ud / P * P;
-            const long off = num - k0 * o.ud;                             // (u - k0) ud, in [0, P ud)
-            const float a = ring[(k0 / P) % p.key_ring * p.key_stride + col];
-            if (off == 0) { v[k] = a; continue; }
-            const float b = ring[(k0 / P + 1) % p.key_ring * p.key_stride + col];
-            v[k] = resample_mix(a, b, (double)off / (double)(P * o.ud));
+            v[k] = keyframe_read(ring, p.key_ring, p.key_stride, p.pred_stride, (done + r) * o.un, o.ud, (int)(rel - r * per));
         }
         if (e0 >= start && e0 + 4 <= end) *reinterpret_cast<float4*>(poses + e0) = make_float4(v[0], v[1], v[2], v[3]);
         else for (int k = 0; k < 4; ++k) if (e0 + k >= start && e0 + k < end) poses[e0 + k] = v[k];
     }
 }
 
-// slot_mask (T) u8 or nullptr (every slot): the chosen slots' output counters go back to 0 (behind stream_rate_reset_kernel).
+// slot_mask (T) u8 or nullptr (every slot): the chosen slots start a new track -- the model counter and the sub-ticks' held pose (what
+// stream_reset_kernel zeroes in a plain session), the source counter, the pushed byte and the held output pose go back to 0, and with
+// out_frames (nullptr: the session has no output rate) the output counter.  The rings stay: nothing reads a source frame or a keyframe
+// its slot's counters have not reached.  One thread per float of a held pose; the thread of a slot's first float writes its counters.
 static __global__ void __launch_bounds__(256)
-stream_out_reset_kernel(const uint8_t* __restrict__ slot_mask, const int T, int32_t* __restrict__ out_frames)
+stream_rate_reset_kernel(const uint8_t* __restrict__ slot_mask, const int T, const int per_pose, int32_t* __restrict__ frames, float* __restrict__ held,
+                         int32_t* __restrict__ source_frames, uint8_t* __restrict__ pushed, float* __restrict__ out_held, int32_t* __restrict__ out_frames)
 {
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= T) return;
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)T * per_pose) return;
+    const int t = (int)(i / per_pose);
     if (slot_mask != nullptr && slot_mask[t] == 0) return;
-    out_frames[t] = 0;
+    held[i] = 0.f;
+    out_held[i] = 0.f;
+    if (i - (long)t * per_pose != 0) return;
+    frames[t] = 0;
+    source_frames[t] = 0;
+    pushed[t] = 0;
+    if (out_frames != nullptr) out_frames[t] = 0;
 }
 
 }  // namespace uu3d

@@ -110,8 +110,8 @@ __device__ __forceinline__ float2 resample_source_pair(const float* src, const l
     return normalise ? normalize_pair(x, wf, h_over_w) : x;
 }
 
-// a * (1.0 - w) + b * w in float64: two products and one sum, each rounded (no fused multiply-add), then rounded to float32 -- the
-// expression of frame_value, so that a numpy restatement gives the same bits.
+// a * (1.0 - w) + b * w in float64: two products and one sum, each rounded (no fused multiply-add), then rounded to float32 -- numpy's
+// own expression (evaluation.interpolate_between_keyframes), so that a numpy restatement gives the same bits.
 __device__ __forceinline__ float resample_mix(const float a, const float b, const double w)
 {
 #pragma clang fp contract(off)
@@ -196,19 +196,15 @@ __device__ __forceinline__ float window_prediction(const float* __restrict__ pla
 
 // Coordinate c of joint j of frame f by the plan of evaluation.keyframe_plan: the prediction of window left[f] where left == right (a
 // predicted frame, or a frame behind its track's last predicted one), else evaluation.interpolate_between_keyframes' own expression
-// pred[left] * (1.0 - w) + pred[right] * w in float64 -- two products and one sum, each rounded (no fused multiply-add), then rounded to
-// float32 as numpy stores it into the float32 array.  A row outside [0, num_windows) gives NaN.
+// pred[left] * (1.0 - w) + pred[right] * w in float64, rounded to float32 as numpy stores it into the float32 array (resample_mix).  A row
+// outside [0, num_windows) gives NaN.
 __device__ __forceinline__ float frame_value(const float* __restrict__ plain, const float* __restrict__ flipped, const int32_t* __restrict__ order,
                                              const long num_windows, const long l, const long r, const double w, const int J, const int j, const int c)
 {
-#pragma clang fp contract(off)
     if (l < 0 || l >= num_windows || r < 0 || r >= num_windows) return __builtin_nanf("");
     const float a = window_prediction(plain, flipped, order, l, J, j, c);
     if (l == r) return a;
-    const float b = window_prediction(plain, flipped, order, r, J, j, c);
-    const double pa = (double)a * (1.0 - w);
-    const double pb = (double)b * w;
-    return (float)(pa + pb);
+    return resample_mix(a, window_prediction(plain, flipped, order, r, J, j, c), w);
 }
 
 // out (frames, J, 3), flattened: one thread per four consecutive floats.  root >= 0: the frame's root joint is subtracted in float32

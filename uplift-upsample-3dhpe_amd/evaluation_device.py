@@ -12,10 +12,7 @@ import numpy as np
 from . import _capi
 from . import dist as udist
 from . import evaluation
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
+from ._capi import ptr as _ptr
 
 
 def _dev(a, dtype, device):

@@ -27,17 +27,14 @@ synchronises the stream once after the last forward (its pipeline's buffers go a
 """
 import argparse
 import ctypes as C
-from fractions import Fraction
 
 import numpy as np
 
 from . import _capi, evaluation
 from . import eval as ev
+from ._capi import ptr as _ptr
 from .data import PoseTable, SequenceGenerator
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
+from .rates import _rate_argument, default_mask_stride, frame_rate, frame_rates, output_positions, resample_plan  # noqa: F401 (re-exported)
 
 
 def _upload(a, dtype, device):
@@ -74,98 +71,6 @@ def normalize_tracks(src, table, lens, resolutions=None, key_stride=0, src_lens=
                                                              _ptr(tstart), _ptr(sstart), int(key_stride), _ptr(valid_in), _ptr(valid_out),
                                                              C.c_void_p(stream)), None)
     return table
-
-
-def frame_rate(value):
-    """One frame rate as an exact ``Fraction``: an int, a ``Fraction``, a ``(num, den)`` tuple of two integers, or a float, which becomes
-    ``Fraction(f).limit_denominator(1001)`` (29.97 -> 2997/100, 23.976 -> 2997/125, 30000 / 1001 stays itself).  A string is "NUM/DEN" or
-    a float, as the command line gives it.  Anything non-finite or <= 0 raises ValueError."""
-    if isinstance(value, str):
-        num, _, den = value.partition("/")
-        try:
-            value = (int(num), int(den)) if den else float(num)
-        except ValueError:
-            raise ValueError(f"a frame rate is a number or NUM/DEN, got {value!r}") from None
-    if isinstance(value, tuple) and len(value) == 2 and all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in value):
-        if value[1] == 0:
-            raise ValueError(f"a frame rate must be finite, got {value}")
-        rate = Fraction(int(value[0]), int(value[1]))
-    elif isinstance(value, bool):
-        raise ValueError(f"a frame rate is a number, got {value!r}")
-    elif isinstance(value, (int, np.integer, Fraction)):
-        rate = Fraction(value)
-    elif isinstance(value, (float, np.floating)):
-        if not np.isfinite(value):
-            raise ValueError(f"a frame rate must be finite, got {value}")
-        rate = Fraction(float(value)).limit_denominator(1001)
-    else:
-        raise ValueError(f"a frame rate is an int, a Fraction, a (num, den) tuple or a float, got {value!r}")
-    if rate <= 0:
-        raise ValueError(f"a frame rate must be > 0, got {value}")
-    return rate
-
-
-def frame_rates(fps, num_tracks):
-    """``predict_tracks``' ``fps`` / ``out_fps`` -> one ``Fraction`` per track.  One rate for all tracks (see ``frame_rate``; a tuple of two
-    integers is ONE rate num / den) or a list / array with one rate per track."""
-    if isinstance(fps, (list, np.ndarray)) or (isinstance(fps, tuple) and not (len(fps) == 2 and all(isinstance(v, (int, np.integer)) for v in fps))):
-        if len(fps) != num_tracks:
-            raise ValueError(f"fps must be one rate or one per track: {num_tracks} tracks, {len(fps)} rates")
-        return [frame_rate(v) for v in fps]
-    return [frame_rate(fps)] * num_tracks
-
-
-def resample_plan(lens, fps, model_fps=50):
-    """Where the frames of the model's time grid lie in tracks filmed at another rate -> (model_lens, left, right, weight); exact integer
-    arithmetic in numpy and Python integers, nothing touches a device.
-
-    A track of T source frames at rate f becomes ``T' = ceil((T - 1) * model_fps / f) + 1`` model frames (``model_lens``); model frame k
-    sits at source position ``p_k = k * f / model_fps``.  ``left`` / ``right`` (sum(model_lens),) int64: the two source frames around it
-    as GLOBAL source rows (all tracks back to back), ``weight`` float64 = p_k - floor(p_k), one division of two integers below 2^53.
-    weight == 0 has right == left; a position at or behind the last source frame (only a track's final model frame can be) repeats it:
-    left == right == T - 1, weight 0.  ``fps``: as ``frame_rates``; ``model_fps``: one rate."""
-    lens = np.asarray(lens, np.int64).reshape(-1)
-    if (lens < 1).any():
-        raise ValueError("every track needs at least one frame")
-    rates, mf = frame_rates(fps, len(lens)), frame_rate(model_fps)
-    model_lens, left, right, weight = [], [], [], []
-    start = 0
-    for T, f in zip((int(n) for n in lens), rates):
-        step = f / mf                                                  # source frames per model frame, exact
-        N, D = step.numerator, step.denominator
-        span = (T - 1) * D
-        Tm = -(-span // N) + 1                                         # ceil((T - 1) * model_fps / f) + 1
-        if max(Tm * N, D) >= 2 ** 53:
-            raise ValueError(f"a track of {T} frames at {f} fps: the plan's integers must stay below 2^53")
-        pos = np.arange(Tm, dtype=np.int64) * N
-        l, rem = pos // D, pos % D
-        rem[l >= T - 1] = 0
-        l = np.minimum(l, T - 1)
-        model_lens.append(Tm)
-        left.append(start + l)
-        right.append(start + l + (rem > 0))
-        weight.append(rem / np.float64(D))
-        start += T
-    return np.array(model_lens, np.int64), np.concatenate(left), np.concatenate(right), np.concatenate(weight)
-
-
-def output_positions(lens, fps, out_fps, model_fps=50):
-    """The model positions of the frames ``predict_tracks(fps=..., out_fps=...)`` returns -> (out_lens, (track, num, den)) for
-    ``evaluation.keyframe_plan_at``: a track of T frames at rate f has ``floor((T - 1) * out_fps / f) + 1`` output frames, frame i at time
-    i / out_fps, which is model position ``i * model_fps / out_fps`` (never behind the last model frame of ``resample_plan``)."""
-    lens = np.asarray(lens, np.int64).reshape(-1)
-    rates, outs, mf = frame_rates(fps, len(lens)), frame_rates(out_fps, len(lens)), frame_rate(model_fps)
-    out_lens, track, num, den = [], [], [], []
-    for t, (T, f, o) in enumerate(zip((int(n) for n in lens), rates, outs)):
-        n = ((T - 1) * o.numerator * f.denominator) // (o.denominator * f.numerator) + 1
-        q = mf / o
-        if max(n * q.numerator, q.denominator) >= 2 ** 53:
-            raise ValueError(f"a track of {T} frames at {f} fps returned at {o} fps: the plan's integers must stay below 2^53")
-        out_lens.append(n)
-        track.append(np.full(n, t, np.int64))
-        num.append(np.arange(n, dtype=np.int64) * q.numerator)
-        den.append(np.full(n, q.denominator, np.int64))
-    return np.array(out_lens, np.int64), (np.concatenate(track), np.concatenate(num), np.concatenate(den))
 
 
 def resample_tracks(src, table, model_lens, left, right, weight, resolutions=None, valid_in=None, valid_out=None):
@@ -274,16 +179,16 @@ def _device_tracks(tracks, device):
     return tr, J, np.array([int(t.shape[0]) for t in tr], np.int64)
 
 
-def _track_resolutions(resolutions, num_tracks):
-    """None, one (w, h) or one per track -> None or (num_tracks, 2) float64."""
+def check_resolutions(resolutions, count, per="track"):
+    """None, one (w, h) or one per track (per slot, for a session) -> None or (count, 2) float64, contiguous."""
     if resolutions is None:
         return None
-    resolutions = np.asarray(resolutions, np.float64)
-    if resolutions.shape == (2,):
-        resolutions = np.tile(resolutions, (num_tracks, 1))
-    if resolutions.shape != (num_tracks, 2) or not (resolutions > 0).all():
-        raise ValueError("resolutions must be one positive (w, h) or one per track")
-    return resolutions
+    r = np.asarray(resolutions, np.float64)
+    if r.shape == (2,):
+        r = np.tile(r, (count, 1))
+    if r.shape != (count, 2) or not np.isfinite(r).all() or not (r > 0).all():
+        raise ValueError(f"resolutions must be one positive (w, h) or one per {per}")
+    return np.ascontiguousarray(r)
 
 
 def pose_table(tracks, device, resolutions=None, key_stride=0, lengths=None, valid=None):
@@ -304,7 +209,7 @@ def pose_table(tracks, device, resolutions=None, key_stride=0, lengths=None, val
         lens = given
     if (lens < 1).any():
         raise ValueError("every track needs at least one frame")
-    resolutions = _track_resolutions(resolutions, len(tr))
+    resolutions = check_resolutions(resolutions, len(tr))
     src = torch.cat(tr, 0).contiguous() if len(tr) > 1 else tr[0].contiguous()
     flags = None
     if valid is not None:
@@ -329,7 +234,7 @@ def resampled_pose_table(tracks, device, fps, resolutions=None, valid=None, mode
     tr, J, lens = _device_tracks(tracks, device)
     if (lens < 1).any():
         raise ValueError("every track needs at least one frame")
-    resolutions = _track_resolutions(resolutions, len(tr))
+    resolutions = check_resolutions(resolutions, len(tr))
     model_lens, left, right, weight = resample_plan(lens, fps, model_fps)
     src = torch.cat(tr, 0).contiguous() if len(tr) > 1 else tr[0].contiguous()
     kp = torch.empty((int(model_lens.sum()), J, 2), dtype=torch.float32, device=src.device)
@@ -397,7 +302,7 @@ def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, fl
     dev = model.device
     cfg = config.copy()
     if mask_stride is None:
-        mask_stride = cfg.MASK_STRIDE[0] if isinstance(cfg.MASK_STRIDE, (list, tuple)) else cfg.MASK_STRIDE
+        mask_stride = default_mask_stride(cfg)
     cfg.MASK_STRIDE = mask_stride
     flip = bool(cfg.EVAL_FLIP) if flip is None else bool(flip)
     if keyframes_only and mask_stride is None:
@@ -453,14 +358,6 @@ def _load_model(config, weights_path):
     return model
 
 
-def _rate_argument(text):
-    """--fps / --out_fps: "NUM/DEN" or a float -> the exact rate."""
-    try:
-        return frame_rate(text)
-    except ValueError as e:
-        raise argparse.ArgumentTypeError(str(e)) from None
-
-
 def parse_args(argv=None):
     p = argparse.ArgumentParser(prog="python -m uplift_upsample_3dhpe_amd.predict", description="3D poses for the 2D keypoint tracks of an .npz file "
                                 "(one (T, J, 2) array per track) -> an .npz with the same keys and (T, J, 3) float32 arrays.")
@@ -493,9 +390,7 @@ def main(argv=None):
     for k, t in zip(names, tracks):
         if t.ndim != 3 or t.shape[2] != 2 or t.shape[1] != config.NUM_KEYPOINTS:
             raise SystemExit(f"{args.input}[{k}] has shape {t.shape}, expected (T, {config.NUM_KEYPOINTS}, 2)")
-    ms = args.mask_stride
-    if ms is None:
-        ms = config.MASK_STRIDE[0] if isinstance(config.MASK_STRIDE, (list, tuple)) else config.MASK_STRIDE
+    ms = default_mask_stride(config) if args.mask_stride is None else args.mask_stride
     lengths = None
     if args.keyframes_only:
         if ms is None:

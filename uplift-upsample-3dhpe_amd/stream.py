@@ -14,11 +14,14 @@ frames -> uu3d_stream_commit (counters, keyframe ring, edge row, this tick's win
 session's resident feature table -> uu3d_stream_emit.  The spatial stack runs once per pushed frame, not once per frame of the window.  The
 per-track counters live on the device, so the five steps are ONE captured hipGraph (``graph=True``) replayed at every tick; ``push`` never
 waits for the device.
+All arguments are the same at every push, so the constructor decides the session's mode once and builds its launch tables (the steps of a
+tick, the launches of a push around them, the reset: library functions with their prebuilt arguments); ``push`` and ``reset`` walk them.
+The integer planning of rates and strides (``rate_plan``, ``push_plan``, ``out_push_plan``, ``session_strides``) is ``rates.py``.
 
 Any frame rate -- ``StreamSession(..., fps=F, model_fps=50)``: one SOURCE frame per slot and push, at F frames per second, and one pose per
 slot and push, at the source frame's own time; everything on the device, ``push`` still never waits.  With model_fps / F = A / B in lowest
-terms (exact integers; ``rate_plan``, ``push_plan``):
-  input   model frame k sits at source position k B / A (``predict.resample_plan``'s definition) and is made the moment source frame
+terms (exact integers; ``rates.rate_plan``, ``rates.push_plan``):
+  input   model frame k sits at source position k B / A (``rates.resample_plan``'s definition) and is made the moment source frame
           ceil(k B / A) has been pushed: that source frame's bits where the position is whole, else the two neighbours normalised and then
           mixed in float64 with resample_plan's own weight (the device functions of uu3d_resample_tracks).  After a slot's j-th push
           (0-based) its newest model frame is K = floor(j A / B); the push made K - floor((j - 1) A / B) model frames -- 1 at j = 0, then
@@ -40,7 +43,7 @@ terms (exact integers; ``rate_plan``, ``push_plan``):
 Live upsampling -- ``StreamSession(..., fps=F, out_fps=G, model_fps=50)``: the session returns poses on a time grid of its own, G per second,
 EVERY one that has become due per push -- a camera at 50 fps whose detector runs on every fifth frame (fps=10, out_fps=50) gets its 50
 poses a second, five per push.  Input and model sides, ``lookahead`` (SOURCE frames), a_m and ``missed_detections`` as above; the rules are
-``predict.output_positions``' and ``evaluation.keyframe_plan_at``'s, as ``predict_tracks(fps=F, out_fps=G)``:
+``rates.output_positions``' and ``evaluation.keyframe_plan_at``'s, as ``predict_tracks(fps=F, out_fps=G)``:
   grid    output frame i of a slot lies at time i / G, model position u = i model_fps / G, and is read like a source frame above:
           k0 = floor(u / P) P; u == k0 gives that keyframe's bits, anything else float32(p0 (1 - w) + p1 w) in float64, w one float64
           division of two integers.
@@ -58,36 +61,17 @@ One launch (uu3d_stream_timed_emit_multi) in place of uu3d_stream_timed_emit; ``
                                                  [--mask_missing] [--fps F [--out_fps G]]
 """
 import argparse
-import collections
 import ctypes as C
+import functools
 import gc
 
 import numpy as np
 
 from . import _capi
-from . import eval as ev
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def session_strides(config, mask_stride=None):
-    """(SEQUENCE_STRIDE, input stride s_in, prediction stride) of a session: ``mask_stride`` defaults to the config's first MASK_STRIDE (no
-    mask stride at all: every sampled frame is input); a pose comes out for centres that are multiples of the prediction stride."""
-    cfg = config.copy()
-    if mask_stride is None:
-        mask_stride = cfg.MASK_STRIDE[0] if isinstance(cfg.MASK_STRIDE, (list, tuple)) else cfg.MASK_STRIDE
-    cfg.MASK_STRIDE = mask_stride
-    S = int(cfg.SEQUENCE_STRIDE)
-    s_in = S if mask_stride is None else int(mask_stride)
-    if s_in < S or s_in % S != 0:
-        raise ValueError("the mask stride must be a multiple of the sequence stride")
-    return S, s_in, int(ev.prediction_stride(cfg) or 1)
-
-
-def max_lookahead(config):
-    return (int(config.SEQUENCE_LENGTH) // 2) * int(config.SEQUENCE_STRIDE)
+from ._capi import ptr as _ptr
+from .predict import _load_model, check_resolutions, check_valid
+from .rates import (RatePlan, _rate_argument, max_lookahead, newest_model_frame, out_push_plan, push_plan,  # noqa: F401 (re-exported)
+                    rate_plan, session_strides)
 
 
 def ring_capacity(config, mask_stride=None, lookahead=0):
@@ -142,154 +126,6 @@ def window_plan(frames, lookahead, config, mask_stride=None, valid=None):
             "place": np.where(kind == 2, (src // s_in) % cap, -1)}
 
 
-RatePlan = collections.namedtuple("RatePlan", "A B n_max a_m D min_lookahead pred_stride lookahead out_c out_d pos_num pos_den max_out",
-                                  defaults=(None, None, None, None, None))
-
-
-def _newest_model_frame(j, A, B):
-    """K(j) = floor(j A / B): the newest model frame after a slot's j-th push (0-based)."""
-    return (j * A) // B
-
-
-def _output_keyframes(q, A, B, P):
-    """(k0, k1, numerator, denominator of the weight) of source frame q: model position u = q A / B, k0 = floor(u / P) P, k1 = k0 where
-    u == k0, else k0 + P; the weight is (q A - k0 B) / (P B)."""
-    num = q * A
-    k0 = num // B // P * P
-    off = num - k0 * B
-    return k0, (k0 if off == 0 else k0 + P), off, P * B
-
-
-def _fraction_lcm(*values):
-    """The smallest positive Fraction that is a whole multiple of every given one: lcm of the numerators over gcd of the denominators."""
-    import math
-    from fractions import Fraction
-    return Fraction(math.lcm(*(v.numerator for v in values)), math.gcd(*(v.denominator for v in values)))
-
-
-def _output_ring_depth(A, B, c, d, un, ud, P, lookahead, a_m, period):
-    """D for a session with an output rate, by exact enumeration in numpy int64 over the pushes q + lookahead, q = 0 .. period (one common
-    period of source frames, output frames and keyframes, and the push that closes it): the push returns output frames i_lo .. i_hi,
-    the newest emitted centre is ((K(q + lookahead) - a_m) // P) P; the oldest k0 read is k0(i_lo), the newest k1 read is k1(i_hi).
-    -> (D, the smallest newest centre - k1(i_hi): >= 0 means every keyframe read has been emitted)."""
-    q = np.arange(period + 1, dtype=np.int64)
-    hi = q * c // d
-    lo = np.where(q == 0, 0, (q - 1) * c // d + 1)
-    due = hi >= lo
-    newest = ((q + lookahead) * A // B - a_m) // P * P
-    k0_lo = lo * un // ud // P * P
-    num_hi = hi * un
-    k0_hi = num_hi // ud // P * P
-    k1_hi = np.where(num_hi == k0_hi * ud, k0_hi, k0_hi + P)
-    return 1 + int(((newest - k0_lo) // P)[due].max()), int((newest - k1_hi)[due].min())
-
-
-def rate_plan(config, fps, lookahead, mask_stride=None, model_fps=50, out_fps=None):
-    """The plan of ``StreamSession(fps=fps, lookahead=lookahead)`` -> RatePlan(A, B, n_max, a_m, D, min_lookahead, pred_stride, lookahead,
-    ...); integers and ``Fraction`` only.  A / B = model_fps / fps in lowest terms; n_max = ceil(A / B), the most model frames one push makes;
-    a_m the model lookahead and D the places of the keyframe ring (the module docstring), both by exact enumeration over one period B P
-    of j; min_lookahead the smallest ``lookahead`` (in source frames) for which an a_m >= 0 exists.  A smaller ``lookahead`` raises
-    ValueError naming it; ``lookahead=None`` plans for min_lookahead itself.
-    ``out_fps=G`` (None: the five further fields are None and the others are what they were): out_c / out_d = G / fps and
-    pos_num / pos_den = model_fps / G in lowest terms, max_out = R = ceil(G / fps) poses per push at most.  a_m and min_lookahead are
-    unchanged -- an output frame due at a push is never later than the push's source frame q -- and D is enumerated over one common
-    period of the source frames, the output frames and the keyframes (an lcm of Fractions), the oldest output frame of every push
-    included; the enumeration also checks the claim about a_m.  ValueError, naming the quantity: more than 2^24 source frames per
-    period, a term of out_fps / fps or of model_fps / out_fps >= 2^20, more than 64 poses per push."""
-    from .predict import frame_rate
-    rho = frame_rate(model_fps) / frame_rate(fps)
-    A, B = rho.numerator, rho.denominator
-    if max(A, B) >= 2 ** 20:
-        raise ValueError(f"model_fps / fps = {A}/{B}: numerator and denominator must stay below 2^20")
-    _, _, P = session_strides(config, mask_stride)
-    out = ()
-    if out_fps is not None:
-        up, pos = frame_rate(out_fps) / frame_rate(fps), frame_rate(model_fps) / frame_rate(out_fps)
-        c, d, un, ud = up.numerator, up.denominator, pos.numerator, pos.denominator
-        if max(c, d) >= 2 ** 20:
-            raise ValueError(f"out_fps / fps = {c}/{d}: numerator and denominator must stay below 2^20")
-        if max(un, ud) >= 2 ** 20:
-            raise ValueError(f"model_fps / out_fps = {un}/{ud}: numerator and denominator must stay below 2^20")
-        R = -(-c // d)
-        if R > 64:
-            raise ValueError(f"out_fps / fps = {c}/{d} would return up to {R} poses per push; at most 64")
-        span = _fraction_lcm(1 / frame_rate(fps), 1 / frame_rate(out_fps), P / frame_rate(model_fps)) * frame_rate(fps)
-        assert span.denominator == 1
-        if span > 2 ** 24:
-            raise ValueError(f"fps {frame_rate(fps)}, out_fps {frame_rate(out_fps)} and keyframes {P} model frames apart repeat only after {int(span)} "
-                             f"source frames per period; at most 2^24")
-        out = (c, d, un, ud, R, int(span))
-    period = B * P
-    keys = [_output_keyframes(q, A, B, P) for q in range(period)]
-
-    def slack(L):                                                      # min over one period of K(q + L) - k1(q)
-        return min(_newest_model_frame(q + L, A, B) - k[1] for q, k in enumerate(keys))
-    min_lookahead = 0
-    while slack(min_lookahead) < 0:
-        min_lookahead += 1
-    lookahead = min_lookahead if lookahead is None else int(lookahead)
-    if lookahead < min_lookahead:
-        raise ValueError(f"lookahead {lookahead} is too small at {frame_rate(fps)} fps: the pose of a source frame is read between two model "
-                         f"keyframes {P} model frames apart, which needs a lookahead of at least {min_lookahead} source frames")
-    a_m = min(max_lookahead(config), slack(lookahead))
-    if out:
-        D, spare = _output_ring_depth(A, B, *out[:4], P, lookahead, a_m, out[5])
-        if spare < 0:
-            raise AssertionError("an output frame due at a push reads a keyframe that has not been emitted")
-    else:
-        D = 1 + max(((_newest_model_frame(q + lookahead, A, B) - a_m) // P * P - k[0]) // P for q, k in enumerate(keys))
-    if D > 4096:
-        raise ValueError(f"lookahead {lookahead} would keep {D} keyframes per slot; at most 4096")
-    return RatePlan(A, B, -(-A // B), a_m, D, min_lookahead, P, lookahead, *out[:5])
-
-
-def push_plan(j, plan):
-    """The host mirror of what a slot's j-th push (0-based) does under ``plan``: {"model": [(k, left, right, weight), ...] -- the model
-    frames the push makes, each with its two source frames and resample_plan's float64 weight (left == right: weight 0.0) --, "q": the
-    source frame whose pose comes out (None while j < lookahead), "k0", "k1": its two keyframes, "weight": the float64 output weight}."""
-    A, B, P = plan.A, plan.B, plan.pred_stride
-    j = int(j)
-    first = 0 if j == 0 else _newest_model_frame(j - 1, A, B) + 1
-    model = []
-    for k in range(first, _newest_model_frame(j, A, B) + 1):
-        left, rem = divmod(k * B, A)
-        model.append((k, left, left + (rem > 0), float(np.float64(rem) / np.float64(A))))
-    q = j - plan.lookahead
-    if q < 0:
-        return {"model": model, "q": None, "k0": None, "k1": None, "weight": None}
-    k0, k1, off, den = _output_keyframes(q, A, B, P)
-    return {"model": model, "q": q, "k0": k0, "k1": k1, "weight": float(np.float64(off) / np.float64(den))}
-
-
-def out_push_plan(j, plan):
-    """The host mirror of what a slot's j-th push (0-based) RETURNS under a ``plan`` with an output rate: [(i, k0, k1, weight), ...], the
-    output frames that became due at the push, oldest first -- none while q = j - lookahead < 0, frame 0 alone at q == 0, then
-    floor((q - 1) G / F) + 1 .. floor(q G / F); k0, k1 the two keyframes frame i is read between (k1 == k0 on a keyframe) and weight the
-    float64 (i pos_num - k0 pos_den) / (P pos_den), ``keyframe_plan_at``'s."""
-    if plan.max_out is None:
-        raise ValueError("the plan has no output rate: rate_plan(..., out_fps=G)")
-    q = int(j) - plan.lookahead
-    if q < 0:
-        return []
-    first = 0 if q == 0 else ((q - 1) * plan.out_c) // plan.out_d + 1
-    frames = []
-    for i in range(first, (q * plan.out_c) // plan.out_d + 1):
-        k0, k1, off, den = _output_keyframes(i, plan.pos_num, plan.pos_den, plan.pred_stride)
-        frames.append((i, k0, k1, float(np.float64(off) / np.float64(den))))
-    return frames
-
-
-def _check_resolutions(resolutions, slots):
-    if resolutions is None:
-        return None
-    r = np.asarray(resolutions, np.float64)
-    if r.shape == (2,):
-        r = np.tile(r, (slots, 1))
-    if r.shape != (slots, 2) or not np.isfinite(r).all() or not (r > 0).all():
-        raise ValueError("resolutions must be one positive (w, h) or one per slot")
-    return np.ascontiguousarray(r)
-
-
 class StreamSession(object):
 
     def __init__(self, model, config, slots, resolutions=None, mask_stride=None, flip=None, lookahead=0, root_relative=True, graph=True,
@@ -303,7 +139,7 @@ class StreamSession(object):
         track still grows by that frame, but no window ever shows it to the network (``predict.predict_tracks(valid=...)``); the tick runs
         uu3d_stream_stage_valid / uu3d_stream_commit_valid.  Needs a model with strided input (ValueError).  False: today's session.
         ``fps``: None = the pushed frames are at the model's rate (today's session, bit for bit).  Else the ONE rate of the session's source
-        frames, parsed by ``predict.frame_rate`` (int, ``Fraction``, ``(num, den)``, or a float read as
+        frames, parsed by ``rates.frame_rate`` (int, ``Fraction``, ``(num, den)``, or a float read as
         ``Fraction(f).limit_denominator(1001)``), against ``model_fps``: the module docstring's "Any frame rate".  ``lookahead`` then counts
         SOURCE frames and must be at least ``rate_plan(...).min_lookahead`` (ValueError naming it); ``missed_detections`` flags are per
         source frame, and a model frame is missing under uu3d_resample_tracks' rule: its left source frame is missing or, where it is mixed
@@ -313,6 +149,21 @@ class StreamSession(object):
         the session returns, parsed like ``fps`` (which it needs: ValueError without): the module docstring's "Live upsampling".  ``push``
         then returns (poses (slots, max_out, J, 3), count (slots,) int32), ``max_out`` = ceil(out_fps / fps) <= 64, and ``out_frames``
         counts the output frames per slot."""
+        res = self._init_plan(model, config, slots, resolutions, mask_stride, flip, lookahead, graph, missed_detections, fps, model_fps, out_fps)
+        import torch
+        self._torch = torch
+        self._lib = _capi.load_library()
+        layouts = self._init_layout(config, root_relative)
+        with torch.cuda.device(model.device):
+            self._init_buffers(config, res, *layouts)
+            self._init_launch_tables()
+            self._zero_features()
+            if self.graph:
+                self._capture()
+
+    # ---- construction: checks and plan, layout and state, buffers, launch tables (then the capture) ---------------------------------
+    def _init_plan(self, model, config, slots, resolutions, mask_stride, flip, lookahead, graph, missed_detections, fps, model_fps, out_fps):
+        """Every refusal that needs no device, and the session's plan.  -> the checked resolutions."""
         slots, lookahead = int(slots), int(lookahead)
         if slots < 1:
             raise ValueError("slots >= 1")
@@ -323,125 +174,148 @@ class StreamSession(object):
         self.max_out = None if out_fps is None else self.rate.max_out
         if self.rate is None and not 0 <= lookahead <= max_lookahead(config):
             raise ValueError(f"lookahead must be in [0, {max_lookahead(config)}] = (SEQUENCE_LENGTH // 2) * SEQUENCE_STRIDE, got {lookahead}")
-        res = _check_resolutions(resolutions, slots)
+        res = check_resolutions(resolutions, slots, per="slot")
         if not model.arch.compiled_dims:
             raise NotImplementedError("StreamSession needs the frames form of the forward (uu3d_frame_features / uu3d_forward_frames_ex), "
                                       "which models with generic dims do not have")
         self.missed_detections = bool(missed_detections)
         if self.missed_detections and not model.has_strided_input:
             raise ValueError("missed_detections needs a model with strided input: a missing frame becomes the learned masked token")
-        import torch
-        self._torch = torch
         self.model, self.slots, self.lookahead, self.graph = model, slots, lookahead, bool(graph)
         self.seq_stride, self.mask_stride, self.pred_stride = S, s_in, pred
         self.flip = bool(config.EVAL_FLIP) if flip is None else bool(flip)
         self.captures = 0                                             # hipGraph captures so far (graph=True: 1 for the session's whole life)
-        a, dev = model.arch, model.device
-        self._lib = lib = _capi.load_library()
         self.model_lookahead = lookahead if self.rate is None else self.rate.a_m       # the lookahead of a (sub-)tick, in model frames
-        self._cfg = _capi.Uu3dStreamConfig(slots, S, s_in, pred, self.model_lookahead, int(self.flip), int(config.PADDING_TYPE == "copy"),
-                                           int(config.ROOT_KEYTPOINT) if root_relative else -1)
-        model._sync_from_trainer()
-        lay = _capi.Uu3dStreamLayout()
-        _capi.check(lib, lib.uu3d_stream_state_layout(model._h, C.byref(self._cfg), C.byref(lay)), model._h)
-        self.ring_capacity = int(lay.ring_capacity)
-        T, J, N, dt, H = slots, a.num_keypoints, a.num_frames, a.d_temporal, 2 if self.flip else 1
         self._key = ("stream", id(self))
-        state_bytes = int(lay.bytes)
-        if self.rate is not None:
-            self._rate = _capi.Uu3dStreamRate(self.rate.A, self.rate.B, lookahead, self.rate.D)
-            rlay = _capi.Uu3dStreamRateLayout()
-            _capi.check(lib, lib.uu3d_stream_rate_state_layout(model._h, C.byref(self._cfg), C.byref(self._rate), C.byref(rlay)), model._h)
-            state_bytes = int(rlay.bytes)
-            if self.max_out is not None:
-                r = self.rate
-                self._outp = _capi.Uu3dStreamOut(r.out_c, r.out_d, r.pos_num, r.pos_den, r.max_out)
-                olay = _capi.Uu3dStreamOutLayout()
-                _capi.check(lib, lib.uu3d_stream_out_state_layout(model._h, C.byref(self._cfg), C.byref(self._rate), C.byref(self._outp),
-                                                                  C.byref(olay)), model._h)
-                state_bytes = int(olay.bytes)
-            self._src_host = np.zeros(slots, np.int64)                # host mirror of the source counters; exact where _src_known
-            self._src_known = np.ones(slots, bool)
-        with torch.cuda.device(dev):
-            self._state = torch.zeros(state_bytes, dtype=torch.uint8, device=dev)
-            view = lambda off, n, dtype: self._state[off:off + n * 4].view(dtype)
-            self._frames = view(int(lay.frames_offset), T, torch.int32)
-            self._table = view(int(lay.table_offset), int(lay.table_rows) * dt, torch.float32).view(int(lay.table_rows), dt)
-            self._zero_row = int(lay.zero_row)
-            self._kp = torch.zeros((T, J, 2), dtype=torch.float32, device=dev)
-            self._active = torch.ones((T,), dtype=torch.uint8, device=dev)
-            self._active_all = True
-            self._valid_in = self._valid = self._valid_state = None
-            if self.missed_detections:
-                self._valid_in = torch.ones((T,), dtype=torch.uint8, device=dev)       # the caller's flags of this tick
-                self._valid_in_all = True
-                self._valid = torch.zeros((T,), dtype=torch.uint8, device=dev)         # ... ANDed with active and the finite test (stage)
-                self._valid_state = torch.zeros(int(lib.uu3d_stream_valid_bytes(model._h, C.byref(self._cfg))), dtype=torch.uint8, device=dev)
-            self._res = None if res is None else torch.from_numpy(res).pin_memory().to(dev, non_blocking=True)
-            self._order = torch.from_numpy(np.ascontiguousarray(config.AUGM_FLIP_KEYPOINT_ORDER, np.int32)).to(dev) if self.flip else None
-            self._staged = torch.zeros((H * T, J, 2), dtype=torch.float32, device=dev)
-            self._feats = torch.zeros((H * T, dt), dtype=torch.float32, device=dev)
-            self._rows = torch.full((H * T, N), -1, dtype=torch.int32, device=dev)
-            self._mask = torch.zeros((H * T, N), dtype=torch.uint8, device=dev)
-            self._fresh = torch.zeros((T,), dtype=torch.uint8, device=dev)
-            self._full = torch.empty((H * T, N, J, 3), dtype=torch.float32, device=dev) if model._returns_full else None
-            self._central = torch.zeros((H * T, J, 3), dtype=torch.float32, device=dev)
-            self._out = torch.zeros((T, J, 3), dtype=torch.float32, device=dev)
-            # what a (sub-)tick takes as `active` and where its emit writes: with a rate the sub-ticks' own buffers, else the session's
-            self._tick_active, self._emit_out, self._emit_fresh = self._active, self._out, self._fresh
-            if self.rate is not None:
-                self._source_frames = view(int(rlay.source_frames_offset), T, torch.int32)
-                self._tick_active = torch.zeros((T,), dtype=torch.uint8, device=dev)
-                self._emit_out = torch.zeros((T, J, 3), dtype=torch.float32, device=dev)
-                self._emit_fresh = torch.zeros((T,), dtype=torch.uint8, device=dev)
-            if self.max_out is not None:
-                self._out_frames = view(int(olay.out_frames_offset), T, torch.int32)
-                self._poses = torch.zeros((T, self.max_out, J, 3), dtype=torch.float32, device=dev)
-                self._count = torch.zeros((T,), dtype=torch.int32, device=dev)
-            # a workspace of the session's own for uu3d_frame_features: the graph holds its address
-            self._fws = torch.empty(max(int(lib.uu3d_frame_features_bytes(model._h, H * T)), int(lib.uu3d_frame_features_bytes(model._h, 1))),
-                                    dtype=torch.uint8, device=dev)
-            self._zero_features()
-            if self.graph:
-                self._capture()
+        return res
 
-    # ---- the five steps of a tick, on ``stream`` ----------------------------------------------------------------------------------
-    def _features(self, frames, out, stream):
-        m = self.model
-        _capi.check(self._lib, self._lib.uu3d_frame_features(m._h, _ptr(frames), int(frames.shape[0]), _ptr(out), _ptr(self._fws),
-                                                             C.c_size_t(self._fws.numel()), 0, C.c_void_p(stream.cuda_stream)), m._h)
+    def _init_layout(self, config, root_relative):
+        """The C structs of the session and the layouts of its state block -> (plain, rate, out), None where the session has no such part."""
+        lib, h, r = self._lib, self.model._h, self.rate
+        self._cfg = _capi.Uu3dStreamConfig(self.slots, self.seq_stride, self.mask_stride, self.pred_stride, self.model_lookahead, int(self.flip),
+                                           int(config.PADDING_TYPE == "copy"), int(config.ROOT_KEYTPOINT) if root_relative else -1)
+        self.model._sync_from_trainer()
+        lay, rlay, olay = _capi.Uu3dStreamLayout(), None, None
+        _capi.check(lib, lib.uu3d_stream_state_layout(h, C.byref(self._cfg), C.byref(lay)), h)
+        self.ring_capacity = int(lay.ring_capacity)
+        if r is not None:
+            self._rate, rlay = _capi.Uu3dStreamRate(r.A, r.B, self.lookahead, r.D), _capi.Uu3dStreamRateLayout()
+            _capi.check(lib, lib.uu3d_stream_rate_state_layout(h, C.byref(self._cfg), C.byref(self._rate), C.byref(rlay)), h)
+        if self.max_out is not None:
+            self._outp, olay = _capi.Uu3dStreamOut(r.out_c, r.out_d, r.pos_num, r.pos_den, r.max_out), _capi.Uu3dStreamOutLayout()
+            _capi.check(lib, lib.uu3d_stream_out_state_layout(h, C.byref(self._cfg), C.byref(self._rate), C.byref(self._outp), C.byref(olay)), h)
+        return lay, rlay, olay
+
+    def _init_buffers(self, config, res, lay, rlay, olay):
+        """The state block and the buffers of a tick; then what a session with missed detections, with a rate and with an output rate adds."""
+        torch, lib, m = self._torch, self._lib, self.model
+        a, dev = m.arch, m.device
+        T, J, N, dt, H = self.slots, a.num_keypoints, a.num_frames, a.d_temporal, 2 if self.flip else 1
+        zeros = functools.partial(torch.zeros, device=dev)
+        self._state = zeros(int((olay or rlay or lay).bytes), dtype=torch.uint8)
+        view = lambda off, n, dtype: self._state[off:off + n * 4].view(dtype)
+        self._frames = view(int(lay.frames_offset), T, torch.int32)
+        self._table = view(int(lay.table_offset), int(lay.table_rows) * dt, torch.float32).view(int(lay.table_rows), dt)
+        self._zero_row = int(lay.zero_row)
+        self._kp = zeros((T, J, 2), dtype=torch.float32)
+        self._active = torch.ones((T,), dtype=torch.uint8, device=dev)
+        self._active_all = True
+        self._res = None if res is None else torch.from_numpy(res).pin_memory().to(dev, non_blocking=True)
+        self._order = torch.from_numpy(np.ascontiguousarray(config.AUGM_FLIP_KEYPOINT_ORDER, np.int32)).to(dev) if self.flip else None
+        self._staged = zeros((H * T, J, 2), dtype=torch.float32)
+        self._feats = zeros((H * T, dt), dtype=torch.float32)
+        self._rows = torch.full((H * T, N), -1, dtype=torch.int32, device=dev)
+        self._mask = zeros((H * T, N), dtype=torch.uint8)
+        self._fresh = zeros((T,), dtype=torch.uint8)
+        self._full = torch.empty((H * T, N, J, 3), dtype=torch.float32, device=dev) if m._returns_full else None
+        self._central = zeros((H * T, J, 3), dtype=torch.float32)
+        self._out = zeros((T, J, 3), dtype=torch.float32)
+        # a workspace of the session's own for uu3d_frame_features: the graph holds its address
+        self._fws = torch.empty(max(int(lib.uu3d_frame_features_bytes(m._h, H * T)), int(lib.uu3d_frame_features_bytes(m._h, 1))),
+                                dtype=torch.uint8, device=dev)
+        # missed detections: the caller's flags of this tick, the same ANDed with active and the finite test (stage), the flags kept per slot
+        self._valid_in = self._valid = self._valid_state = None
+        self._valid_in_all = True
+        if self.missed_detections:
+            self._valid_in = torch.ones((T,), dtype=torch.uint8, device=dev)
+            self._valid = zeros((T,), dtype=torch.uint8)
+            self._valid_state = zeros(int(lib.uu3d_stream_valid_bytes(m._h, C.byref(self._cfg))), dtype=torch.uint8)
+        # what a (sub-)tick takes as `active` and where its emit writes: with a rate the sub-ticks' own buffers, else the session's
+        self._tick_active, self._emit_out, self._emit_fresh = self._active, self._out, self._fresh
+        self._source_frames, self._src_host, self._src_known = self._frames, None, None
+        if rlay is not None:
+            self._source_frames = view(int(rlay.source_frames_offset), T, torch.int32)
+            self._tick_active = zeros((T,), dtype=torch.uint8)
+            self._emit_out = zeros((T, J, 3), dtype=torch.float32)
+            self._emit_fresh = zeros((T,), dtype=torch.uint8)
+            self._src_host = np.zeros(T, np.int64)                    # host mirror of the source counters; exact where _src_known
+            self._src_known = np.ones(T, bool)
+        self._result = self._out, self._fresh.view(torch.bool)        # what push returns: the session's own buffers
+        if olay is not None:
+            self._out_frames = view(int(olay.out_frames_offset), T, torch.int32)
+            self._poses = zeros((T, self.max_out, J, 3), dtype=torch.float32)
+            self._count = zeros((T,), dtype=torch.int32)
+            self._result = self._poses, self._count
+
+    def _init_launch_tables(self):
+        """All arguments are the same at every push (the buffers never move), so the mode is decided here, once: every launch of the
+        session as (library function, its arguments up to the stream); a step whose arguments are None is a Python callable of the stream.
+          _tick_steps   the steps of one (sub-)tick, in order -- what the graph captures
+          _push_before  / _push_after   the launches of a push around its sub-ticks (a session with a rate; not captured)
+          _reset_call   the reset of the session's kind; the slot mask and the stream follow its arguments"""
+        lib, m = self._lib, self.model
+        h, cfg, state = m._h, C.byref(self._cfg), _ptr(self._state)
+        kp, res, order, active, staged = _ptr(self._kp), _ptr(self._res), _ptr(self._order), _ptr(self._active), _ptr(self._staged)
+        tick_active, valid, feats, rows, mask = _ptr(self._tick_active), _ptr(self._valid), _ptr(self._feats), _ptr(self._rows), _ptr(self._mask)
+        emit_fresh = _ptr(self._emit_fresh)
+        if self.rate is not None:
+            rate = C.byref(self._rate)
+            stage = (lib.uu3d_stream_resample_stage, (h, cfg, rate, state, res, order, tick_active, valid, staged))
+        elif self.missed_detections:
+            stage = (lib.uu3d_stream_stage_valid, (h, cfg, kp, res, active, order, _ptr(self._valid_in), valid, staged))
+        else:
+            stage = (lib.uu3d_stream_stage, (h, cfg, kp, res, active, order, staged))
+        features = (lib.uu3d_frame_features, (h, staged, int(self._staged.shape[0]), feats, _ptr(self._fws), C.c_size_t(self._fws.numel()), 0))
+        if self.missed_detections:
+            commit = (lib.uu3d_stream_commit_valid, (h, cfg, state, feats, tick_active, valid, _ptr(self._valid_state), rows, mask, emit_fresh))
+        else:
+            commit = (lib.uu3d_stream_commit, (h, cfg, state, feats, tick_active, rows, mask, emit_fresh))
+        # the latency schedule: what model.forward_frames takes (below 1024 token rows both schedules give the same bits)
+        forward = (functools.partial(m._forward_frames, self._table, self._rows, self._mask if m.has_strided_input else None, self._full,
+                                     self._central, self._key), None)
+        emit = (lib.uu3d_stream_emit, (h, cfg, state, _ptr(self._central), order, emit_fresh, _ptr(self._emit_out)))
+        self._tick_steps = [stage, features, commit, forward, emit]
+        self._push_before, self._push_after = [], []
+        self._reset_call = (lib.uu3d_stream_reset, (h, cfg, state))
+        if self.rate is not None:
+            self._tick_steps.append((lib.uu3d_stream_file_keyframe, (h, cfg, rate, state, emit_fresh)))
+            self._push_before = [(lib.uu3d_stream_source_push, (h, cfg, rate, state, kp, active, _ptr(self._valid_in), int(self.missed_detections)))]
+            self._push_after = [(lib.uu3d_stream_timed_emit, (h, cfg, rate, state, _ptr(self._out), _ptr(self._fresh)))]
+            self._reset_call = (lib.uu3d_stream_rate_reset, (h, cfg, rate, state))
+        if self.max_out is not None:
+            outp = C.byref(self._outp)
+            self._push_after = [(lib.uu3d_stream_timed_emit_multi, (h, cfg, rate, outp, state, _ptr(self._poses), _ptr(self._count)))]
+            self._reset_call = (lib.uu3d_stream_out_reset, (h, cfg, rate, outp, state))
+
+    # ---- the steps of a tick, on ``stream`` ------------------------------------------------------------------------------------------
+    def _run(self, steps, stream):
+        """Enqueue the steps of a launch table on ``stream``, in order."""
+        st = C.c_void_p(stream.cuda_stream)
+        for fn, args in steps:
+            if args is None:
+                fn(stream)
+            else:
+                _capi.check(self._lib, fn(*args, st), self.model._h)
 
     def _zero_features(self):
         """The features of an all-zero frame (zero padding) into the table's zero row."""
-        torch = self._torch
-        cur = torch.cuda.current_stream(self.model.device)
-        zero = torch.zeros((1,) + tuple(self._kp.shape[1:]), dtype=torch.float32, device=self.model.device)
-        self._features(zero, self._table[self._zero_row:], cur)
+        torch, lib, m = self._torch, self._lib, self.model
+        zero = torch.zeros((1,) + tuple(self._kp.shape[1:]), dtype=torch.float32, device=m.device)
+        self._run([(lib.uu3d_frame_features, (m._h, _ptr(zero), 1, _ptr(self._table[self._zero_row:]), _ptr(self._fws),
+                                              C.c_size_t(self._fws.numel()), 0))], torch.cuda.current_stream(m.device))
 
     def _tick(self, stream):
-        lib, m, cfg, st = self._lib, self.model, C.byref(self._cfg), C.c_void_p(stream.cuda_stream)
-        if self.rate is not None:
-            _capi.check(lib, lib.uu3d_stream_resample_stage(m._h, cfg, C.byref(self._rate), _ptr(self._state), _ptr(self._res), _ptr(self._order),
-                                                            _ptr(self._tick_active), _ptr(self._valid), _ptr(self._staged), st), m._h)
-        elif self.missed_detections:
-            _capi.check(lib, lib.uu3d_stream_stage_valid(m._h, cfg, _ptr(self._kp), _ptr(self._res), _ptr(self._active), _ptr(self._order),
-                                                         _ptr(self._valid_in), _ptr(self._valid), _ptr(self._staged), st), m._h)
-        else:
-            _capi.check(lib, lib.uu3d_stream_stage(m._h, cfg, _ptr(self._kp), _ptr(self._res), _ptr(self._active), _ptr(self._order),
-                                                   _ptr(self._staged), st), m._h)
-        self._features(self._staged, self._feats, stream)
-        if self.missed_detections:
-            _capi.check(lib, lib.uu3d_stream_commit_valid(m._h, cfg, _ptr(self._state), _ptr(self._feats), _ptr(self._tick_active), _ptr(self._valid),
-                                                          _ptr(self._valid_state), _ptr(self._rows), _ptr(self._mask), _ptr(self._emit_fresh), st), m._h)
-        else:
-            _capi.check(lib, lib.uu3d_stream_commit(m._h, cfg, _ptr(self._state), _ptr(self._feats), _ptr(self._tick_active), _ptr(self._rows),
-                                                    _ptr(self._mask), _ptr(self._emit_fresh), st), m._h)
-        # the latency schedule: what model.forward_frames takes (below 1024 token rows both schedules give the same bits)
-        m._forward_frames(self._table, self._rows, self._mask if m.has_strided_input else None, self._full, self._central, self._key, stream)
-        _capi.check(lib, lib.uu3d_stream_emit(m._h, cfg, _ptr(self._state), _ptr(self._central), _ptr(self._order), _ptr(self._emit_fresh),
-                                              _ptr(self._emit_out), st), m._h)
-        if self.rate is not None:
-            _capi.check(lib, lib.uu3d_stream_file_keyframe(m._h, cfg, C.byref(self._rate), _ptr(self._state), _ptr(self._emit_fresh), st), m._h)
+        self._run(self._tick_steps, stream)
 
     def _capture(self):
         """One warm-up tick with every slot inactive (nothing advances), then the capture: a linear chain on one stream."""
@@ -526,21 +400,23 @@ class StreamSession(object):
             if valid is not None:
                 self._valid_in.copy_(self._flags(valid, "valid"), non_blocking=True)
                 self._valid_in_all = False
-            elif self.missed_detections and not self._valid_in_all:
+            elif not self._valid_in_all:
                 self._valid_in.fill_(1)
                 self._valid_in_all = True
-            if self.rate is not None:
-                self._push_source(active)
-            elif self.graph:
-                self._graph.replay()
-            else:
-                self._tick(torch.cuda.current_stream(dev))
-        if self.max_out is not None:
-            return self._poses, self._count
-        return self._out, self._fresh.view(torch.bool)
+            cur = torch.cuda.current_stream(dev)
+            self._run(self._push_before, cur)                         # (with a rate: file the source frames)
+            for _ in range(self._sub_ticks(active)):                  # make the model frames that are due
+                if self.graph:
+                    self._graph.replay()
+                else:
+                    self._tick(cur)
+            self._run(self._push_after, cur)                          # (with a rate: read the poses)
+        return self._result
 
     def _sub_ticks(self, active):
-        """How many sub-ticks this push needs, advancing the host mirror of the source counters."""
+        """How many (sub-)ticks this push needs, advancing the host mirror of the source counters (no rate: none, and one tick per push)."""
+        if self._src_host is None:
+            return 1
         torch = self._torch
         r = self.rate
         if isinstance(active, torch.Tensor) and active.is_cuda:
@@ -550,27 +426,9 @@ class StreamSession(object):
         n = r.n_max if (act & ~self._src_known).any() else 0
         for i in np.flatnonzero(act & self._src_known):
             j = int(self._src_host[i])
-            n = max(n, 1 if j == 0 else _newest_model_frame(j, r.A, r.B) - _newest_model_frame(j - 1, r.A, r.B))
+            n = max(n, 1 if j == 0 else newest_model_frame(j, r.A, r.B) - newest_model_frame(j - 1, r.A, r.B))
             self._src_host[i] = j + 1
         return n
-
-    def _push_source(self, active):
-        """The push of a session with a rate: file the source frames, make the model frames that are due, read the poses."""
-        lib, m, cfg, rate = self._lib, self.model, C.byref(self._cfg), C.byref(self._rate)
-        cur = self._torch.cuda.current_stream(m.device)
-        st = C.c_void_p(cur.cuda_stream)
-        _capi.check(lib, lib.uu3d_stream_source_push(m._h, cfg, rate, _ptr(self._state), _ptr(self._kp), _ptr(self._active), _ptr(self._valid_in),
-                                                     int(self.missed_detections), st), m._h)
-        for _ in range(self._sub_ticks(active)):
-            if self.graph:
-                self._graph.replay()
-            else:
-                self._tick(cur)
-        if self.max_out is not None:
-            _capi.check(lib, lib.uu3d_stream_timed_emit_multi(m._h, cfg, rate, C.byref(self._outp), _ptr(self._state), _ptr(self._poses),
-                                                              _ptr(self._count), st), m._h)
-            return
-        _capi.check(lib, lib.uu3d_stream_timed_emit(m._h, cfg, rate, _ptr(self._state), _ptr(self._out), _ptr(self._fresh), st), m._h)
 
     def reset(self, slots=None):
         """The given slots (indices; None = all) start a new track: zero frames, held pose 0, with ``out_fps`` output counter 0.  Stream-ordered
@@ -583,19 +441,17 @@ class StreamSession(object):
                 h = np.zeros(self.slots, np.uint8)
                 h[np.asarray(slots, np.int64).reshape(-1)] = 1
                 mask = torch.from_numpy(h).pin_memory().to(m.device, non_blocking=True)
-            st = C.c_void_p(torch.cuda.current_stream(m.device).cuda_stream)
-            if self.rate is None:
-                _capi.check(self._lib, self._lib.uu3d_stream_reset(m._h, C.byref(self._cfg), _ptr(self._state), _ptr(mask), st), m._h)
-                return
-            if self.max_out is not None:
-                _capi.check(self._lib, self._lib.uu3d_stream_out_reset(m._h, C.byref(self._cfg), C.byref(self._rate), C.byref(self._outp),
-                                                                       _ptr(self._state), _ptr(mask), st), m._h)
-            else:
-                _capi.check(self._lib, self._lib.uu3d_stream_rate_reset(m._h, C.byref(self._cfg), C.byref(self._rate), _ptr(self._state), _ptr(mask),
-                                                                        st), m._h)
-            which = slice(None) if slots is None else np.asarray(slots, np.int64).reshape(-1)
-            self._src_host[which] = 0
-            self._src_known[which] = True
+            fn, args = self._reset_call
+            self._run([(fn, args + (_ptr(mask),))], torch.cuda.current_stream(m.device))
+        self._mirror_reset(slots)
+
+    def _mirror_reset(self, slots):
+        """The host mirror of the source counters after a reset: the chosen slots are at zero, and known to be."""
+        if self._src_host is None:
+            return
+        which = slice(None) if slots is None else np.asarray(slots, np.int64).reshape(-1)
+        self._src_host[which] = 0
+        self._src_known[which] = True
 
     @property
     def frames(self):
@@ -605,7 +461,7 @@ class StreamSession(object):
     @property
     def source_frames(self):
         """Source frames pushed per slot since its last reset, (slots,) int32 on the device; without ``fps`` the same tensor as ``frames``."""
-        return self._frames if self.rate is None else self._source_frames
+        return self._source_frames
 
     @property
     def out_frames(self):
@@ -648,14 +504,12 @@ def replay_tracks(model, config, tracks, resolutions=None, mask_stride=None, fli
     T, ticks = len(tracks), max(lens)
     flags = None
     if valid is not None and not isinstance(valid, str):
-        from .predict import check_valid
         check_valid(valid, lens)
         flags = [np.asarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v).reshape(-1) != 0 for v in valid]
     elif valid is not None and valid != "finite":
         raise ValueError('valid must be None, "finite" or a list with one (T_i,) array per track')
     s = StreamSession(model, config, T, resolutions=resolutions, mask_stride=mask_stride, flip=flip, lookahead=lookahead,
-                      root_relative=root_relative, graph=graph, **({} if valid is None else {"missed_detections": True}),
-                      **({} if fps is None else {"fps": fps, "model_fps": model_fps}), **({} if out_fps is None else {"out_fps": out_fps}))
+                      root_relative=root_relative, graph=graph, missed_detections=valid is not None, fps=fps, model_fps=model_fps, out_fps=out_fps)
     J = int(np.asarray(tracks[0]).shape[1])
     if out_fps is None:
         poses = torch.zeros((ticks, T, J, 3), dtype=torch.float32, device=model.device)
@@ -716,16 +570,6 @@ def parse_args(argv=None):
     if args.out_fps is not None and args.fps is None:
         p.error("--out_fps needs --fps")
     return args
-
-
-def _rate_argument(text):
-    from .predict import _rate_argument as parse
-    return parse(text)
-
-
-def _load_model(config, weights_path):
-    from .predict import _load_model as load
-    return load(config, weights_path)
 
 
 def main(argv=None):
