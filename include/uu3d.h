@@ -451,6 +451,37 @@ int uu3d_stream_commit_valid(uu3d_model* model, const uu3d_stream_config* cfg, v
                              uint8_t* stride_mask_dev, uint8_t* fresh_dev, void* stream);
 
 /*
+ * PER-JOINT MISSED DETECTIONS (predict.predict_tracks(valid=..., repair_joints=G)): a detector rarely loses a whole frame; it loses a wrist
+ * or an ankle for a few frames.  uu3d_repair_joints fills such joints on the device, in front of uu3d_normalize_tracks_valid or
+ * uu3d_resample_tracks, which take its output as their src_dev and its frame flags as their valid_in_dev.
+ * src_dev (rows, J, 2) f32, 8-byte aligned: the frames as given (raw coordinates; source frames, or the given keyframes), all tracks back to
+ * back; track t is rows [track_start_dev[t], track_start_dev[t + 1]), track_start_dev (num_tracks + 1) i64.  Nothing crosses a track boundary.
+ * THE RULE.  Joint j of frame t is OBSERVED, a(t, j), iff its byte of joint_flags_dev (rows, J) u8 is non-zero (NULL: no flags given) AND
+ * both of its coordinates are finite.  max_gap = G >= 1 is the longest run of consecutive unobserved frames of one joint that is filled.
+ * For an unobserved (t, j) let l be the largest t' < t with a(t', j) and r the smallest t' > t with a(t', j), inside the track:
+ *     l and r exist and r - l - 1 <= G:  per coordinate (float)((double)src[l] * (1.0 - w) + (double)src[r] * w), w = (double)(t - l) /
+ *         (double)(r - l): two products and one sum in float64, each rounded, no fused multiply-add, rounded once to float32 -- the
+ *         expression of uu3d_resample_tracks, so a numpy restatement (predict.repair_joints_host) gives the same bits;
+ *     only r exists (before the joint's first observation) and r - t <= G:  the bits of src[r, j];
+ *     only l exists (behind its last observation) and t - l <= G:  the bits of src[l, j];
+ *     otherwise the joint is UNREPAIRABLE.
+ * A frame is a real observation iff at least one of its joints is observed and every other one was filled.  A frame without an observed
+ * joint is never filled and a frame with an unrepairable joint is missing too: both stay MISSING in the sense of MISSED DETECTIONS above.
+ * Outputs, each element with one writer, no atomics, bitwise repeatable:
+ *     out_dev (rows, J, 2) f32, 16-byte aligned, never src_dev (UU3D_ERR_INVALID_ARGUMENT): observed joints keep their bits, filled joints
+ *         hold the value above, everything else is zeros -- nothing non-finite leaves the call.  src_dev is only read.
+ *     frame_valid_dev (rows) u8: 1 = a real observation.        joint_state_dev (rows, J) u8, 2-byte aligned: 1 observed, 2 filled, 0 neither.
+ * l and r come from two segmented scans along the frames of every track and joint, so the cost does not depend on G.  They pass through
+ * scratch_dev, 4-byte aligned, of at least uu3d_repair_joints_scratch_bytes bytes = two (rows, J) i32 planes; 0 for arguments out of range:
+ * rows < 2^31, num_tracks * J < 2^31.  A row that track_start_dev does not cover gets NaN and state 0 for its unobserved joints, never a read
+ * out of bounds.  Three launches on the stream, no host synchronisation.
+ */
+size_t uu3d_repair_joints_scratch_bytes(int64_t rows, int32_t num_keypoints);
+int uu3d_repair_joints(const float* src_dev, int64_t rows, int32_t num_keypoints, const uint8_t* joint_flags_dev,
+                       const int64_t* track_start_dev, int32_t num_tracks, int32_t max_gap, float* out_dev, uint8_t* frame_valid_dev,
+                       uint8_t* joint_state_dev, void* scratch_dev, size_t scratch_bytes, void* stream);
+
+/*
  * ANY FRAME RATE (predict.predict_tracks(fps=...)): the front of YOUR OWN 2D TRACKS for tracks that were not filmed at the rate the model
  * was trained for.  The table holds the MODEL's time grid: row `row` (track row_track_dev[row]) is model frame k of its track, which sits at
  * source position p_k = k * fps / model_fps.  The host works the positions out in exact integer arithmetic (predict.resample_plan) and

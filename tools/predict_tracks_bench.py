@@ -7,8 +7,11 @@ Median of --reps calls after one warm-up call each; frames/s = all frames of all
 --fps F: also the same tracks taken as filmed at F frames per second (a float or NUM/DEN): predict_tracks(fps=F) against the host route --
 numpy normalisation and resampling to the model's rate by predict.resample_plan, the plain call, .cpu() and numpy interpolation back to the
 tracks' own frames.
+--repair_joints G [--missing_joints P]: also predict_tracks(valid=joint flags, repair_joints=G) with every joint dropped independently with
+probability P (NaN coordinates, flag 0), against the same call with predict.repair_joints_host -- the rule in numpy, written to be read, not
+to be fast -- run on the host in front of it; the two must agree bit for bit.
    python tools/predict_tracks_bench.py [--tracks 40] [--frames 2500] [--batch 512] [--reps 3] [--cases h36m_351:5,h36m_81:4] [--missing 0.3]
-                                        [--fps 30]"""
+                                        [--fps 30] [--repair_joints 5 --missing_joints 0.1]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -23,6 +26,8 @@ def main():
     ap.add_argument("--no_reuse", action="store_true", help="the window forward instead of the frames form, in both paths")
     ap.add_argument("--missing", type=float, default=0.0, help="also time predict_tracks(valid=...) with this fraction of the frames missing")
     ap.add_argument("--fps", default=None, help="also time predict_tracks(fps=F) against numpy resampling on the host; a float or NUM/DEN")
+    ap.add_argument("--repair_joints", type=int, default=None, metavar="G", help="also time predict_tracks(valid=joint flags, repair_joints=G)")
+    ap.add_argument("--missing_joints", type=float, default=0.1, metavar="P", help="with --repair_joints: every joint is dropped with probability P")
     args = ap.parse_args()
     import numpy as np, torch
     import uplift_upsample_3dhpe_amd as pkg
@@ -37,6 +42,10 @@ def main():
           for _ in range(args.tracks)]
     total = args.tracks * args.frames
     flags = [rng.random(args.frames) >= args.missing for _ in range(args.tracks)] if args.missing > 0 else None
+    jflags = broken = None
+    if args.repair_joints is not None:
+        jflags = [rng.random((args.frames, 17)) >= args.missing_joints for _ in range(args.tracks)]
+        broken = [np.where(f[:, :, None], t, np.float32(np.nan)).astype(np.float32) for t, f in zip(px, jflags)]
     reuse = not args.no_reuse
     fps = None if args.fps is None else predict.frame_rate(args.fps)
     results = []
@@ -89,6 +98,15 @@ def main():
                 res.append((o[p] * (1.0 - fr) + o[np.minimum(p + 1, len(o) - 1)] * fr).astype(np.float32))
             return res
 
+        def repair_path():
+            return predict.predict_tracks(model, cfg, broken, resolutions=(W, H), mask_stride=int(msv), flip=True, reuse_frames=reuse, batch_size=args.batch,
+                                          valid=jflags, repair_joints=args.repair_joints)
+
+        def repair_host():
+            repaired, frame_flags, _ = predict.repair_joints_host(broken, jflags, args.repair_joints)
+            return predict.predict_tracks(model, cfg, repaired, resolutions=(W, H), mask_stride=int(msv), flip=True, reuse_frames=reuse, batch_size=args.batch,
+                                          valid=frame_flags)
+
         row = dict(config=name, mask_stride=int(msv), tracks=args.tracks, frames=total, batch=args.batch, reuse_frames=reuse)
         outs = {}
         cases = [("predict_tracks", new_path), ("predict_tracks_to_host", lambda: new_path(True)), ("composition", composition)]
@@ -98,6 +116,9 @@ def main():
         if fps is not None:
             row["fps"] = str(fps)
             cases += [("predict_tracks_fps", fps_path), ("host_resample", fps_host)]
+        if jflags is not None:
+            row["repair_joints"], row["missing_joints"] = args.repair_joints, args.missing_joints
+            cases += [("predict_tracks_repair", repair_path), ("host_repair", repair_host)]
         for key, fn in cases:
             fn()
             torch.cuda.synchronize()
@@ -115,6 +136,10 @@ def main():
         if fps is not None:
             row["fps_speedup"] = round(row["host_resample_ms"] / row["predict_tracks_fps_ms"], 3)
             row["fps_max_abs_diff"] = float(max(np.abs(a.cpu().numpy() - b).max() for a, b in zip(outs["predict_tracks_fps"], outs["host_resample"])))
+        if jflags is not None:
+            row["repair_speedup"] = round(row["host_repair_ms"] / row["predict_tracks_repair_ms"], 3)
+            row["repair_bits_equal"] = bool(all(torch.equal(a.view(torch.int32), b.view(torch.int32))
+                                                for a, b in zip(outs["predict_tracks_repair"], outs["host_repair"])))
         row["device"] = torch.cuda.get_device_name(0)
         print(json.dumps(row), flush=True)
         results.append(row)

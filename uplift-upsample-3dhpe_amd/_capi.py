@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = (
     "uu3d_normalize_tracks_valid", "uu3d_gather_windows_valid", "uu3d_gather_window_frames_valid", "uu3d_stream_valid_bytes",
     "uu3d_stream_stage_valid", "uu3d_stream_commit_valid",
     "uu3d_resample_tracks",
+    "uu3d_repair_joints", "uu3d_repair_joints_scratch_bytes",
     "uu3d_stream_rate_state_layout", "uu3d_stream_source_push", "uu3d_stream_resample_stage", "uu3d_stream_file_keyframe",
     "uu3d_stream_timed_emit", "uu3d_stream_rate_reset",
     "uu3d_stream_out_state_layout", "uu3d_stream_timed_emit_multi", "uu3d_stream_out_reset",
@@ -230,6 +231,11 @@ def load_library(path=None):
     # any frame rate: the pose table on the model's time grid
     lib.uu3d_resample_tracks.restype = C.c_int
     lib.uu3d_resample_tracks.argtypes = [vp, i64, vp, i64, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    # per-joint missed detections: joints filled on the device in front of the two calls above
+    lib.uu3d_repair_joints_scratch_bytes.restype = sz
+    lib.uu3d_repair_joints_scratch_bytes.argtypes = [i64, i32]
+    lib.uu3d_repair_joints.restype = C.c_int
+    lib.uu3d_repair_joints.argtypes = [vp, i64, i32, vp, vp, i32, i32, vp, vp, vp, vp, sz, vp]
     lib.uu3d_world_to_cam_2d.restype = C.c_int
     lib.uu3d_world_to_cam_2d.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
     lib.uu3d_set_schedule.restype = C.c_int

@@ -34,6 +34,7 @@
 #include "uu3d_misc.h"
 #include "uu3d_metrics.h"
 #include "uu3d_tracks.h"
+#include "uu3d_repair.h"
 #include "uu3d_stream.h"
 #include "uu3d_stream_rate.h"
 #include "uu3d_train.h"
@@ -553,6 +554,34 @@ int uu3d_resample_tracks(const float* src, int64_t src_rows, float* table, int64
     const long threads = ((long)rows * J + 1) / 2;
     hipLaunchKernelGGL(resample_tracks_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        src, (long)src_rows, table, (long)rows, J, row_track, num_tracks, resolution, left, right, weight, (const uint8_t*)valid_out);
+    return hipGetLastError() == hipSuccess ? UU3D_OK : UU3D_ERR_HIP;
+}
+
+size_t uu3d_repair_joints_scratch_bytes(int64_t rows, int32_t J) {
+    if (rows < 1 || rows > INT32_MAX || J < 1 || rows > (INT64_MAX >> 4) / J) return 0;
+    return (size_t)rows * (size_t)J * 2 * sizeof(int32_t);
+}
+
+int uu3d_repair_joints(const float* src, int64_t rows, int32_t J, const uint8_t* joint_flags, const int64_t* track_start, int32_t num_tracks,
+                       int32_t max_gap, float* out, uint8_t* frame_valid, uint8_t* joint_state, void* scratch, size_t scratch_bytes, void* stream) {
+    if (!src || !track_start || !out || !frame_valid || !joint_state || !scratch || rows < 1 || J < 1 || num_tracks < 1 || max_gap < 1)
+        return UU3D_ERR_INVALID_ARGUMENT;
+    if (src == out) return UU3D_ERR_INVALID_ARGUMENT;
+    if (((uintptr_t)out & 15) != 0 || ((uintptr_t)src & 7) != 0 || ((uintptr_t)joint_state & 1) != 0 || ((uintptr_t)scratch & 3) != 0) return UU3D_ERR_INVALID_ARGUMENT;
+    // rows index the plan as int32; rows * J and the grid of the plan launch (one workgroup per track and joint) stay in range
+    if (rows > INT32_MAX || rows > (INT64_MAX >> 4) / J || (int64_t)num_tracks * J > INT32_MAX) return UU3D_ERR_INVALID_ARGUMENT;
+    if (scratch_bytes < uu3d_repair_joints_scratch_bytes(rows, J)) return UU3D_ERR_INVALID_ARGUMENT;
+    int32_t* left = static_cast<int32_t*>(scratch);
+    int32_t* right = left + (long)rows * J;
+    hipLaunchKernelGGL(repair_plan_kernel, dim3((unsigned)((long)num_tracks * J)), dim3(kRepairChunk), 0, (hipStream_t)stream,
+                       src, joint_flags, (long)rows, J, track_start, left, right);
+    if (hipGetLastError() != hipSuccess) return UU3D_ERR_HIP;
+    const long threads = ((long)rows * J + 1) / 2;
+    hipLaunchKernelGGL(repair_apply_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       src, joint_flags, (long)rows, J, (const int32_t*)left, (const int32_t*)right, max_gap, out, joint_state);
+    if (hipGetLastError() != hipSuccess) return UU3D_ERR_HIP;
+    hipLaunchKernelGGL(repair_flag_kernel, dim3((unsigned)(((long)rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                       (const uint8_t*)joint_state, (long)rows, J, frame_valid);
     return hipGetLastError() == hipSuccess ? UU3D_OK : UU3D_ERR_HIP;
 }
 

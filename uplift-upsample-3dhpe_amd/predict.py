@@ -23,7 +23,11 @@ synchronises the stream once after the last forward (its pipeline's buffers go a
 (pinned, asynchronous) never wait.
 
     python -m uplift_upsample_3dhpe_amd.predict --config C --weights W.h5 --input tracks.npz --output out.npz \\
-        [--resolution W H] [--mask_stride S] [--keyframes_only] [--mask_missing] [--fps F] [--out_fps F]
+        [--resolution W H] [--mask_stride S] [--keyframes_only] [--mask_missing] [--fps F] [--out_fps F] [--repair_joints G] [--min_score S]
+
+Per-joint missed detections: ``predict_tracks(..., valid=..., repair_joints=G)`` fills a joint the detector lost for up to G frames by
+linear interpolation between the nearest frames where it was seen (uu3d_repair_joints, in front of the two front kernels above; the rule
+in numpy: ``repair_joints_host``) instead of giving up the whole frame.
 """
 import argparse
 import ctypes as C
@@ -138,9 +142,14 @@ def keyframe_count(length, stride):
     return (int(length) + int(stride) - 1) // int(stride)
 
 
-def check_valid(valid, given):
+def _shape(a):
+    return tuple(a.shape) if hasattr(a, "shape") else np.asarray(a).shape
+
+
+def check_valid(valid, given, joints=None):
     """``predict_tracks``' ``valid`` argument against the frames given per track (``given``; keyframes with ``keyframes_only``): None,
-    "finite" or one (T_i,) array / tensor per track.  Shapes only: nothing touches a device."""
+    "finite" or one (T_i,) array / tensor per track -- with ``joints`` = J (``predict_tracks``) an entry may also be (T_i, J), one flag per
+    joint; without it (a session, ``replay_tracks``) only (T_i,) passes.  Shapes only: nothing touches a device."""
     if valid is None or (isinstance(valid, str) and valid == "finite"):
         return
     if isinstance(valid, str) or not isinstance(valid, (list, tuple)):
@@ -148,24 +157,140 @@ def check_valid(valid, given):
     if len(valid) != len(given):
         raise ValueError(f"valid must have one entry per track: {len(given)} tracks, {len(valid)} entries")
     for i, (v, n) in enumerate(zip(valid, given)):
-        shape = tuple(v.shape) if hasattr(v, "shape") else np.asarray(v).shape
-        if shape != (int(n),):
-            raise ValueError(f"valid[{i}] must be ({int(n)},): one flag per given frame of track {i}, got {shape}")
+        shape = _shape(v)
+        if shape != (int(n),) and (joints is None or shape != (int(n), int(joints))):
+            per_joint = "" if joints is None else f" or ({int(n)}, {int(joints)}): one per joint"
+            raise ValueError(f"valid[{i}] must be ({int(n)},): one flag per given frame of track {i}{per_joint}, got {shape}")
+
+
+def check_repair_joints(repair_joints, valid):
+    """``predict_tracks``' ``repair_joints`` argument: None, or an int G >= 1 together with ``valid``."""
+    if repair_joints is None:
+        return
+    if isinstance(repair_joints, bool) or not isinstance(repair_joints, (int, np.integer)) or int(repair_joints) < 1:
+        raise ValueError(f"repair_joints must be None or an int >= 1: the longest run of frames a joint is filled over, got {repair_joints!r}")
+    if valid is None:
+        raise ValueError('repair_joints needs valid: "finite" or per-frame / per-joint flags say which joints were observed')
 
 
 def _device_valid(valid, device):
-    """The list form of ``valid`` -> one (sum of given frames,) uint8 device tensor; host arrays go up in one pinned, asynchronous copy."""
+    """The list form of ``valid`` -> one (sum of given frames,) uint8 device tensor; host arrays go up in one pinned, asynchronous copy.
+    A (T_i, J) entry counts per frame here: all of its joints."""
     import torch
+
+    def frames(v):
+        v = np.asarray(v) != 0
+        return v.all(axis=1) if v.ndim == 2 else v.reshape(-1)
     if not any(isinstance(v, torch.Tensor) for v in valid):
-        return _upload(np.concatenate([np.asarray(v).reshape(-1) != 0 for v in valid]).view(np.uint8), np.uint8, device)
+        return _upload(np.concatenate([frames(v) for v in valid]).view(np.uint8), np.uint8, device)
     parts = []
     for v in valid:
         if isinstance(v, torch.Tensor):
             v = v if v.is_cuda else v.contiguous().pin_memory().to(device, non_blocking=True)
-            parts.append((v != 0).to(device=device, dtype=torch.uint8))
+            v = v != 0
+            parts.append((v.all(dim=1) if v.dim() == 2 else v).to(device=device, dtype=torch.uint8))
         else:
-            parts.append(_upload((np.asarray(v) != 0).view(np.uint8), np.uint8, device))
+            parts.append(_upload(frames(v).view(np.uint8), np.uint8, device))
     return torch.cat(parts, 0)
+
+
+def _device_joint_flags(valid, J, device):
+    """The list form of ``valid`` -> one (sum of given frames, J) uint8 device tensor, one flag per joint; a (T_i,) entry stands for all
+    joints of its frames.  Host arrays go up in one pinned, asynchronous copy."""
+    import torch
+
+    def joints(v):
+        v = np.asarray(v) != 0
+        return v if v.ndim == 2 else np.repeat(v.reshape(-1, 1), J, axis=1)
+    if not any(isinstance(v, torch.Tensor) for v in valid):
+        return _upload(np.concatenate([joints(v) for v in valid], 0).view(np.uint8), np.uint8, device)
+    parts = []
+    for v in valid:
+        if isinstance(v, torch.Tensor):
+            v = v if v.is_cuda else v.contiguous().pin_memory().to(device, non_blocking=True)
+            v = (v != 0).to(device=device, dtype=torch.uint8)
+            parts.append(v if v.dim() == 2 else v.reshape(-1, 1).expand(-1, J))
+        else:
+            parts.append(_upload(joints(v).view(np.uint8), np.uint8, device))
+    return torch.cat(parts, 0).contiguous()
+
+
+def repair_joints_host(tracks, joint_flags, G):
+    """The rule of ``predict_tracks(repair_joints=G)`` (include/uu3d.h, PER-JOINT MISSED DETECTIONS) in numpy, written to be read: what
+    uu3d_repair_joints computes, bit for bit.  ``tracks``: list of (T_i, J, 2) arrays; ``joint_flags``: None (no flags given: the finite test
+    alone) or a list with one (T_i,) or (T_i, J) array per track -> (repaired, frame_flags, state): per track (T_i, J, 2) float32,
+    (T_i,) bool and (T_i, J) uint8 (1 observed, 2 filled, 0 neither).  Nothing crosses a track boundary."""
+    G = int(G)
+    if G < 1:
+        raise ValueError("G must be >= 1")
+    repaired, frame_flags, states = [], [], []
+    for i, track in enumerate(tracks):
+        src = np.asarray(track, np.float32)
+        T, J = src.shape[:2]
+        observed = np.isfinite(src).all(axis=2)
+        if joint_flags is not None:
+            f = np.asarray(joint_flags[i]) != 0
+            observed &= f if f.ndim == 2 else f[:, None]
+        out = np.zeros((T, J, 2), np.float32)
+        state = np.zeros((T, J), np.uint8)
+        for j in range(J):
+            seen = np.flatnonzero(observed[:, j])
+            for t in range(T):
+                if observed[t, j]:
+                    out[t, j], state[t, j] = src[t, j], 1
+                    continue
+                before, after = seen[seen < t], seen[seen > t]
+                l = int(before[-1]) if len(before) else None
+                r = int(after[0]) if len(after) else None
+                if l is not None and r is not None:
+                    if r - l - 1 <= G:
+                        w = np.float64(t - l) / np.float64(r - l)
+                        out[t, j] = (src[l, j].astype(np.float64) * (1.0 - w) + src[r, j].astype(np.float64) * w).astype(np.float32)
+                        state[t, j] = 2
+                elif r is not None:
+                    if r - t <= G:
+                        out[t, j], state[t, j] = src[r, j], 2
+                elif l is not None:
+                    if t - l <= G:
+                        out[t, j], state[t, j] = src[l, j], 2
+        repaired.append(out)
+        states.append(state)
+        frame_flags.append((state == 1).any(axis=1) & (state != 0).all(axis=1))
+    return repaired, frame_flags, states
+
+
+def repair_joints(src, lens, G, joint_flags=None):
+    """uu3d_repair_joints on the current stream.  ``src`` (R, J, 2) float32 on the device, the given frames of all tracks back to back
+    (only read); ``lens``: given frames per track; ``joint_flags`` (R, J) uint8 on the device or None -> (repaired (R, J, 2) float32,
+    frame flags (R,) uint8, joint state (R, J) uint8), fresh device buffers."""
+    import torch
+    lib = _capi.load_library()
+    dev = src.device
+    lens = np.asarray(lens, np.int64)
+    R, J = int(src.shape[0]), int(src.shape[1])
+    if int(lens.sum()) != R:
+        raise ValueError("lens must add up to the rows of src")
+    track_start = _upload(np.concatenate([[0], np.cumsum(lens)]), np.int64, dev)
+    out = torch.empty((R, J, 2), dtype=torch.float32, device=dev)
+    frame_flags = torch.empty((R,), dtype=torch.uint8, device=dev)
+    state = torch.empty((R, J), dtype=torch.uint8, device=dev)
+    nbytes = int(lib.uu3d_repair_joints_scratch_bytes(R, J))
+    if nbytes == 0:
+        raise ValueError(f"{R} frames of {J} joints are out of uu3d_repair_joints' range")
+    scratch = torch.empty((nbytes // 4,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _capi.check(lib, lib.uu3d_repair_joints(_ptr(src), R, J, _ptr(joint_flags), _ptr(track_start), len(lens), min(int(G), 2 ** 31 - 1), _ptr(out),
+                                                _ptr(frame_flags), _ptr(state), _ptr(scratch), nbytes, C.c_void_p(stream)), None)
+    return out, frame_flags, state
+
+
+def _front_validity(src, given, J, valid, repair):
+    """What the front kernels take as source and ``valid_in``: as they are, or with ``repair`` = G the repaired source and the frame
+    flags of uu3d_repair_joints -> (src, valid_in, joint state or None)."""
+    if repair is None:
+        return src, None if valid is None or isinstance(valid, str) else _device_valid(valid, src.device), None
+    return repair_joints(src, given, repair, None if isinstance(valid, str) else _device_joint_flags(valid, J, src.device))
 
 
 def _device_tracks(tracks, device):
@@ -191,12 +316,14 @@ def check_resolutions(resolutions, count, per="track"):
     return np.ascontiguousarray(r)
 
 
-def pose_table(tracks, device, resolutions=None, key_stride=0, lengths=None, valid=None):
+def pose_table(tracks, device, resolutions=None, key_stride=0, lengths=None, valid=None, repair_joints=None):
     """The dense, normalised ``data.PoseTable`` of the tracks (uu3d_normalize_tracks) -> (table, frames per track).  ``valid`` as in
-    ``predict_tracks`` (not None: uu3d_normalize_tracks_valid into a fresh buffer; the table carries the per-frame flags)."""
+    ``predict_tracks`` (not None: uu3d_normalize_tracks_valid into a fresh buffer; the table carries the per-frame flags).
+    ``repair_joints`` = G: uu3d_repair_joints runs on the given frames first; ``table.joint_state`` is its (given frames, J) uint8 state."""
     import torch
-    check_valid(valid, [len(t) for t in tracks])
+    check_repair_joints(repair_joints, valid)
     tr, J, given = _device_tracks(tracks, device)
+    check_valid(valid, given, joints=J)
     if key_stride > 0:
         if lengths is None or len(lengths) != len(tr):
             raise ValueError("keyframes_only needs `lengths`: the number of frames of every track")
@@ -211,27 +338,31 @@ def pose_table(tracks, device, resolutions=None, key_stride=0, lengths=None, val
         raise ValueError("every track needs at least one frame")
     resolutions = check_resolutions(resolutions, len(tr))
     src = torch.cat(tr, 0).contiguous() if len(tr) > 1 else tr[0].contiguous()
-    flags = None
+    flags = state = None
     if valid is not None:
+        src, valid_in, state = _front_validity(src, given, J, valid, repair_joints)
         kp = torch.empty((int(lens.sum()), J, 2), dtype=torch.float32, device=src.device)      # (never in the caller's own memory)
         flags = torch.empty((int(lens.sum()),), dtype=torch.uint8, device=src.device)
-        normalize_tracks(src, kp, lens, resolutions, key_stride, given, valid_in=None if isinstance(valid, str) else _device_valid(valid, src.device),
-                         valid_out=flags)
+        normalize_tracks(src, kp, lens, resolutions, key_stride, given, valid_in=valid_in, valid_out=flags)
     elif key_stride > 0 or resolutions is not None:
         kp = torch.empty((int(lens.sum()), J, 2), dtype=torch.float32, device=src.device)      # (never in the caller's own memory)
         normalize_tracks(src, kp, lens, resolutions, key_stride, given)
     else:
         kp = src
-    return PoseTable.from_device(kp, lens, valid=flags), lens
+    table = PoseTable.from_device(kp, lens, valid=flags)
+    table.joint_state = state
+    return table, lens
 
 
-def resampled_pose_table(tracks, device, fps, resolutions=None, valid=None, model_fps=50):
+def resampled_pose_table(tracks, device, fps, resolutions=None, valid=None, model_fps=50, repair_joints=None):
     """``pose_table`` for tracks at ``fps`` frames per second: the dense, normalised table on the MODEL's time grid (``resample_plan``,
     uu3d_resample_tracks; always a fresh buffer) -> (table, model frames per track, source frames per track).  With ``valid`` the table
-    carries one flag per model frame."""
+    carries one flag per model frame.  ``repair_joints`` = G: uu3d_repair_joints runs on the source frames first; ``table.joint_state`` is
+    its (source frames, J) uint8 state."""
     import torch
-    check_valid(valid, [len(t) for t in tracks])
+    check_repair_joints(repair_joints, valid)
     tr, J, lens = _device_tracks(tracks, device)
+    check_valid(valid, lens, joints=J)
     if (lens < 1).any():
         raise ValueError("every track needs at least one frame")
     resolutions = check_resolutions(resolutions, len(tr))
@@ -239,14 +370,16 @@ def resampled_pose_table(tracks, device, fps, resolutions=None, valid=None, mode
     src = torch.cat(tr, 0).contiguous() if len(tr) > 1 else tr[0].contiguous()
     kp = torch.empty((int(model_lens.sum()), J, 2), dtype=torch.float32, device=src.device)
     flags = None if valid is None else torch.empty((int(model_lens.sum()),), dtype=torch.uint8, device=src.device)
-    resample_tracks(src, kp, model_lens, left, right, weight, resolutions,
-                    valid_in=None if valid is None or isinstance(valid, str) else _device_valid(valid, src.device), valid_out=flags)
-    return PoseTable.from_device(kp, model_lens, valid=flags), model_lens, lens
+    src, valid_in, state = _front_validity(src, lens, J, valid, repair_joints)
+    resample_tracks(src, kp, model_lens, left, right, weight, resolutions, valid_in=valid_in, valid_out=flags)
+    table = PoseTable.from_device(kp, model_lens, valid=flags)
+    table.joint_state = state
+    return table, model_lens, lens
 
 
 def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, flip=None, keyframes_only=False, reuse_frames=True,
                    batch_size=None, root_relative=True, depth=None, lengths=None, graph=True, valid=None, return_valid=False, fps=None, out_fps=None,
-                   model_fps=50):
+                   model_fps=50, repair_joints=None):
     """One 3D pose per frame for each 2D keypoint track -> list of (T_i, J, 3) float32 tensors on the model's device (views of one buffer).
 
     ``tracks``: list of (T_i, J, 2) arrays or tensors, on the host or the device, at the frame rate the config was trained for (nothing is
@@ -289,7 +422,23 @@ def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, fl
     video rate / k, out_fps = video rate.  ``valid`` stays per SOURCE frame; a model frame is a real observation iff its left source frame
     is valid and finite and, where it is mixed from two, its right one too.  ``return_valid=True`` with ``fps`` returns the flags on the
     MODEL's grid, (T'_i,) tensors, not per returned pose.  ``fps`` with ``keyframes_only=True`` raises ValueError: say
-    ``fps=video rate / s_in, out_fps=video rate`` instead."""
+    ``fps=video rate / s_in, out_fps=video rate`` instead.
+
+    Per-joint missed detections -- ``repair_joints``: None = today's call, the same bits, no further launch or buffer; an entry of ``valid``
+    may then also be (T_i, J) and counts per frame, all of its joints.  An int G >= 1 (needs ``valid``; ValueError otherwise): a joint the
+    detector lost for up to G consecutive given frames -- source frames with ``fps``, given keyframes with ``keyframes_only`` -- is filled
+    on the device (uu3d_repair_joints) before anything else looks at the track.  A joint is OBSERVED when its flag is non-zero (``valid``
+    "finite": no flags; a (T_i,) entry: the frame's flag for all joints; a (T_i, J) entry, e.g. ``scores >= 0.3``: its own) and both
+    coordinates are finite.  An unobserved joint between two observations l < t < r of the same joint with r - l - 1 <= G becomes
+    ``src[l] * (1.0 - w) + src[r] * w``, w = (t - l) / (r - l), in float64 on the raw coordinates, rounded once to float32; before the
+    joint's first observation r (r - t <= G) or behind its last one l (t - l <= G) it is held.  A frame with at least one observed joint
+    and all others filled is a real observation; a frame with no observed joint is never filled, and a frame with a joint that cannot be
+    filled is missing as well -- the network upsamples over both as over any missing frame.  The result equals, bit for bit,
+    ``predict_tracks(repaired, valid=frame_flags)`` with the output of ``repair_joints_host``, the rule in numpy.
+    ``return_valid=True`` then returns (poses, flags, joint_state): joint_state a list of (given frames of track i, J) uint8 device tensors,
+    1 observed, 2 filled, 0 neither.  ``StreamSession`` and ``replay_tracks`` have no such option and keep refusing anything but (T_i,)
+    flags: a session computes a frame's spatial features once, at its push, when the joint's right neighbour is not known yet, so a causal
+    fill would break the session's contract (the pose of ``predict_tracks`` on the track cut at that frame)."""
     import torch
     if fps is None and out_fps is not None:
         raise ValueError("out_fps needs fps: the rate the tracks were filmed at")
@@ -298,7 +447,8 @@ def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, fl
                          "fps=video_rate / k and out_fps=video_rate")
     if valid is not None and not model.has_strided_input:
         raise ValueError("valid needs a model with strided input: a missing frame becomes the learned masked token, which this model does not have")
-    check_valid(valid, [len(t) for t in tracks])
+    check_repair_joints(repair_joints, valid)
+    check_valid(valid, [len(t) for t in tracks], joints=_shape(tracks[0])[1] if len(tracks) and len(_shape(tracks[0])) == 3 else None)
     dev = model.device
     cfg = config.copy()
     if mask_stride is None:
@@ -308,11 +458,13 @@ def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, fl
     if keyframes_only and mask_stride is None:
         raise ValueError("keyframes_only needs a mask stride")
     if fps is None:
-        table, lens = pose_table(tracks, dev, resolutions, int(mask_stride) if keyframes_only else 0, lengths, valid=valid)
+        table, lens = pose_table(tracks, dev, resolutions, int(mask_stride) if keyframes_only else 0, lengths, valid=valid,
+                                 repair_joints=repair_joints)
         model_lens = lens
     else:
         rates = frame_rates(fps, len(tracks))
-        table, model_lens, src_lens = resampled_pose_table(tracks, dev, rates, resolutions, valid=valid, model_fps=model_fps)
+        table, model_lens, src_lens = resampled_pose_table(tracks, dev, rates, resolutions, valid=valid, model_fps=model_fps,
+                                                           repair_joints=repair_joints)
         lens, positions = output_positions(src_lens, rates, rates if out_fps is None else out_fps, model_fps)
     gen = SequenceGenerator(table, seq_len=cfg.SEQUENCE_LENGTH, target_frame_rate=50, subsample=1, stride=cfg.SEQUENCE_STRIDE,
                             padding_type=cfg.PADDING_TYPE, flip_augment=False, flip_lr_indices=cfg.AUGM_FLIP_KEYPOINT_ORDER,
@@ -338,7 +490,10 @@ def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, fl
     if not return_valid:
         return poses
     flags = table.valid.view(torch.bool) if table.valid is not None else torch.ones((int(model_lens.sum()),), dtype=torch.bool, device=out.device)
-    return poses, list(torch.split(flags, [int(n) for n in model_lens], 0))
+    flags = list(torch.split(flags, [int(n) for n in model_lens], 0))
+    if repair_joints is None:
+        return poses, flags
+    return poses, flags, list(torch.split(table.joint_state, [int(len(t)) for t in tracks], 0))
 
 
 def padding_source_is_keyframe(length, config, mask_stride):
@@ -372,10 +527,27 @@ def parse_args(argv=None):
                    help="the arrays hold frames 0, s_in, 2 s_in, ... only; a track of K keyframes is taken to have (K - 1) * s_in + 1 frames")
     p.add_argument("--mask_missing", action="store_true",
                    help="a frame with a NaN or Inf coordinate is a missed detection: never shown to the network, its pose is still predicted")
+    p.add_argument("--repair_joints", type=int, default=None, metavar="G",
+                   help="fill a joint that is missing for up to G consecutive frames from the nearest frames where it was seen; implies --mask_missing")
+    p.add_argument("--min_score", type=float, default=None, metavar="S",
+                   help="the arrays may be (T, J, 3) with the detector's score in the third channel: a joint counts as seen when score >= S")
     p.add_argument("--fps", type=_rate_argument, default=None, metavar="F",
                    help="frame rate of the tracks, a float or NUM/DEN (29.97, 30000/1001); without it they are taken at the model's rate")
     p.add_argument("--out_fps", type=_rate_argument, default=None, metavar="F", help="frame rate of the poses written (default: --fps)")
     return p.parse_args(argv)
+
+
+def split_scores(names, tracks, J, min_score, source="input"):
+    """The arrays of the command line -> (list of (T, J, 2) tracks, per-joint flags or None).  With ``min_score`` = S an array may be
+    (T, J, 3), the detector's score in the third channel: the joint is flagged when score >= S (a NaN score fails) and the score is
+    stripped; a (T, J, 2) array next to it has every joint flagged.  Without it only (T, J, 2) passes."""
+    for k, t in zip(names, tracks):
+        if t.ndim != 3 or t.shape[1] != J or t.shape[2] not in ((2,) if min_score is None else (2, 3)):
+            raise SystemExit(f"{source}[{k}] has shape {t.shape}, expected (T, {J}, 2)" + ("" if min_score is None else f" or (T, {J}, 3)"))
+    if min_score is None:
+        return tracks, None
+    flags = [t[:, :, 2] >= min_score if t.shape[2] == 3 else np.ones(t.shape[:2], bool) for t in tracks]
+    return [np.ascontiguousarray(t[:, :, :2]) for t in tracks], flags
 
 
 def main(argv=None):
@@ -387,9 +559,7 @@ def main(argv=None):
         tracks = [np.asarray(z[k], np.float32) for k in names]
     if not names:
         raise SystemExit(f"{args.input} holds no arrays")
-    for k, t in zip(names, tracks):
-        if t.ndim != 3 or t.shape[2] != 2 or t.shape[1] != config.NUM_KEYPOINTS:
-            raise SystemExit(f"{args.input}[{k}] has shape {t.shape}, expected (T, {config.NUM_KEYPOINTS}, 2)")
+    tracks, joint_flags = split_scores(names, tracks, config.NUM_KEYPOINTS, args.min_score, args.input)
     ms = default_mask_stride(config) if args.mask_stride is None else args.mask_stride
     lengths = None
     if args.keyframes_only:
@@ -400,8 +570,15 @@ def main(argv=None):
     if args.out_fps is not None and args.fps is None:
         raise SystemExit("--out_fps needs --fps")
     rate = {} if args.fps is None else {"fps": args.fps, **({} if args.out_fps is None else {"out_fps": args.out_fps})}
+    missing = {}
+    if joint_flags is not None:
+        missing = {"valid": joint_flags}
+    elif args.mask_missing or args.repair_joints is not None:
+        missing = {"valid": "finite"}
+    if args.repair_joints is not None:
+        missing["repair_joints"] = args.repair_joints
     poses = predict_tracks(model, config, tracks, resolutions=None if args.resolution is None else tuple(args.resolution), mask_stride=ms,
-                           keyframes_only=args.keyframes_only, lengths=lengths, **({"valid": "finite"} if args.mask_missing else {}), **rate)
+                           keyframes_only=args.keyframes_only, lengths=lengths, **missing, **rate)
     np.savez(args.output, **{k: np.asarray(p.detach().cpu().numpy(), np.float32) for k, p in zip(names, poses)})
     print(f"wrote {args.output}: {len(names)} tracks, {sum(int(p.shape[0]) for p in poses)} frames", flush=True)
     return 0
