@@ -613,6 +613,66 @@ int uu3d_stream_out_reset(uu3d_model* model, const uu3d_stream_config* cfg, cons
                           void* state_dev, const uint8_t* slot_mask_dev, void* stream);
 
 /*
+ * LIVE PER-JOINT MISSED DETECTIONS (stream.StreamSession(repair_joints=G)): PER-JOINT MISSED DETECTIONS for LIVE TRACKS.  The contract of
+ * LIVE TRACKS is unchanged: after the push that made frame t the newest of a slot, the pose of frame t - lookahead is the one of the track
+ * cut at t with uu3d_repair_joints (max_gap = G) in front.  The rule looks ahead (a gap is interpolated once it has closed), so a push may
+ * REVISE frames the session has filed.  The revisions are bounded:
+ *     coordinates change only for frames t - G .. t -- a gap of at most G frames closes at t (held -> interpolated), or a joint is seen for
+ *         the first time at t (unfilled -> held from t).  Of those the session keeps the multiples of mask_stride and the edge frame: at
+ *         most K = G / mask_stride + 2 frames per slot and tick;
+ *     an older frame only ever goes from valid to MISSING -- a gap longer than G closes at t and the up to G frames that were held from
+ *         its left end become unfillable: a byte of valid_state_dev, no features.  These frames are the FAR LIST of the tick.
+ * 1 <= max_gap <= 32 (a declared cap of the live form: K and every buffer are fixed when the session is made); needs a model with strided
+ * input (UU3D_ERR_UNSUPPORTED).  Per tick, on one stream, a linear chain with unchanging arguments that replays from ONE captured hipGraph:
+ *
+ *   uu3d_stream_repair_stage(model, cfg, max_gap, state_dev, repair_state_dev, kp_dev (slots, J, 2) f32 raw, resolution_dev or NULL,
+ *                            active_dev, flip_order_dev, joint_flags_dev (slots, J) u8 or NULL, frames_out_dev (halves * slots * K, J, 2) f32,
+ *                            stage_frame_dev (slots, K) i32, stage_valid_dev (slots, K) u8, far_frames_dev (slots, max_gap) i32,
+ *                            joint_state_dev (slots, J) u8, stream)
+ *       one workgroup per slot, one lane per joint.  A joint is observed iff its flag is non-zero (NULL: none given) and both coordinates
+ *       are finite.  Files the raw frame and flags of an active slot (frame t = the slot's counter in state_dev, which it only reads), then
+ *       writes: the K frames to re-stage -- the multiples of mask_stride in [max(0, t - G), t], oldest first, then the edge frame where it
+ *       lies in that range and is no multiple of mask_stride; stage_frame = -1 for an unused entry --, each repaired by THE RULE of
+ *       uu3d_repair_joints (the same float64 expression: the same bits), normalised as uu3d_stream_stage does, with its mirrored copy in
+ *       the second half; stage_valid = the frame is a real observation (a missing or unused entry stages zeros); the far list (-1 for an
+ *       unused entry); joint_state of frame t (1 observed, 2 filled, 0 neither).  An inactive slot changes nothing of its state, marks every
+ *       entry unused and keeps its joint_state.
+ *   uu3d_frame_features on frames_out_dev (halves * slots * K frames) -> features_dev (halves * slots * K, d_t)
+ *   uu3d_stream_commit_repair(model, cfg, max_gap, state_dev, features_dev, active_dev, stage_frame_dev, stage_valid_dev, far_frames_dev,
+ *                             valid_state_dev, rows_dev, stride_mask_dev, fresh_dev, stream)
+ *       uu3d_stream_commit_valid with another filing step: staged frame f goes, features and valid byte, into ring place
+ *       (f / mask_stride) % ring_capacity where that place still holds it (f a multiple of mask_stride, f > t - ring_capacity * mask_stride)
+ *       and into the edge row where f is the edge frame of t; the frames of the far list get valid byte 0 under the same test.  The
+ *       counter, the window, its masks and fresh are uu3d_stream_commit_valid's, from the same device code.
+ *   uu3d_forward_frames_ex and uu3d_stream_emit as in LIVE TRACKS.
+ *
+ *   uu3d_stream_repair_reset(model, cfg, max_gap, repair_state_dev, slot_mask_dev or NULL, stream): beside uu3d_stream_reset, the same slots
+ *   forget their observations.
+ *
+ * repair_state_dev: a caller-allocated, 256-byte aligned block of uu3d_stream_repair_bytes bytes, all zeros = every slot empty, laid out by
+ * uu3d_stream_repair_layout: the raw frames t - G .. t (slots, window = G + 1, J, 2) f32 and their observed flags (slots, window, J) u8, frame
+ * g at place g % window; per joint the last observation that has left that window, last (slots, J) i32 = its index + 1 (0: none) and
+ * last_xy (slots, J, 2) f32; held (slots, J) u32: bit k = frame last + 1 + k has left the window as a valid frame in which the joint was
+ * held from that observation -- what a long gap turns missing when it closes.  A slot's state is read and written by its own workgroup
+ * only; no atomics, one writer per output element.
+ */
+typedef struct uu3d_stream_repair_state_layout {
+    int64_t window, staged_frames /* K */, raw_offset, last_xy_offset, last_offset, held_offset, observed_offset, bytes;
+} uu3d_stream_repair_state_layout;
+size_t uu3d_stream_repair_bytes(const uu3d_model* model, const uu3d_stream_config* cfg, int32_t max_gap);
+int uu3d_stream_repair_layout(const uu3d_model* model, const uu3d_stream_config* cfg, int32_t max_gap, uu3d_stream_repair_state_layout* out);
+int uu3d_stream_repair_stage(uu3d_model* model, const uu3d_stream_config* cfg, int32_t max_gap, const void* state_dev, void* repair_state_dev,
+                             const float* kp_dev, const double* resolution_dev, const uint8_t* active_dev, const int32_t* flip_order_dev,
+                             const uint8_t* joint_flags_dev, float* frames_out_dev, int32_t* stage_frame_dev, uint8_t* stage_valid_dev,
+                             int32_t* far_frames_dev, uint8_t* joint_state_dev, void* stream);
+int uu3d_stream_commit_repair(uu3d_model* model, const uu3d_stream_config* cfg, int32_t max_gap, void* state_dev, const float* features_dev,
+                              const uint8_t* active_dev, const int32_t* stage_frame_dev, const uint8_t* stage_valid_dev,
+                              const int32_t* far_frames_dev, void* valid_state_dev, int32_t* rows_dev, uint8_t* stride_mask_dev,
+                              uint8_t* fresh_dev, void* stream);
+int uu3d_stream_repair_reset(uu3d_model* model, const uu3d_stream_config* cfg, int32_t max_gap, void* repair_state_dev,
+                             const uint8_t* slot_mask_dev, void* stream);
+
+/*
  * Per-kernel timing of the next uu3d_forward calls with HIP events on the launch stream.
  * When enabled, uu3d_forward records an event pair around every launch; uu3d_profile_read
  * synchronises those events and returns the per-launch records of the LAST forward.

@@ -8,7 +8,11 @@ Median (and 90th percentile) over --ticks ticks after --warmup ticks, per config
 model_fps / F sub-ticks -- next to the plain session pushed at the model's rate (the cost of one model tick); the lookahead is raised to
 the smallest one the rate allows.  The numpy baseline is left out.
 --out_fps G (with --fps): the push of StreamSession(fps=F, out_fps=G) -- every due pose per push, up to ceil(G / F) -- as out_fps_graph_us,
-next to the fps-only push (one pose per push) and the plain session."""
+next to the fps-only push (one pose per push) and the plain session.
+--repair_joints G [--missing_joints P] (not with --fps): the tick of StreamSession(repair_joints=G) as repair_graph_us -- per-joint flags
+with a share P (default 0.1) of the joints unobserved, K = G // s_in + 2 frames of spatial features per slot and tick -- next to the
+tick of StreamSession(missed_detections=True) fed the same frames with the per-frame flags those joints imply (md_graph_us).  The numpy
+baseline is left out."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -22,7 +26,11 @@ def main():
     ap.add_argument("--lookahead", type=int, default=0)
     ap.add_argument("--fps", default=None)
     ap.add_argument("--out_fps", default=None)
+    ap.add_argument("--repair_joints", type=int, default=None)
+    ap.add_argument("--missing_joints", type=float, default=0.1)
     args = ap.parse_args()
+    if args.repair_joints is not None and args.fps is not None:
+        ap.error("--repair_joints is not measured together with --fps")
     if args.out_fps is not None and args.fps is None:
         ap.error("--out_fps needs --fps")
     import numpy as np, torch
@@ -47,13 +55,15 @@ def main():
             rng = np.random.default_rng(0)
             px = (np.cumsum(rng.normal(0, 2.0, size=(total, T, J, 2)), 0) + rng.uniform(0.25, 0.75, size=(1, T, J, 2)) * [W, H]).astype(np.float32)
 
-            def session(graph, **rate):
+            seen = rng.uniform(size=(total, T, J)) >= args.missing_joints      # per-joint flags of --repair_joints
+
+            def session(graph, valid=None, **rate):
                 s = stream.StreamSession(model, cfg, slots=T, resolutions=(W, H), mask_stride=ms, flip=True, graph=graph,
-                                         **({"lookahead": args.lookahead} if not rate else rate))
+                                         **({"lookahead": args.lookahead} if "lookahead" not in rate else {}), **rate)
                 ts = []
                 for k in range(total):
                     t0 = time.perf_counter()
-                    poses, fresh = s.push(px[k])
+                    poses, fresh = s.push(px[k], **({} if valid is None else {"valid": valid[k]}))
                     torch.cuda.synchronize()
                     ts.append(time.perf_counter() - t0)
                 s.check_range()
@@ -99,11 +109,18 @@ def main():
                     out_plan = stream.rate_plan(cfg, args.fps, la, ms, out_fps=args.out_fps)
                     row.update(out_fps=args.out_fps, max_out=out_plan.max_out, key_ring=out_plan.D)
                     variants = (("out_fps_graph", lambda: session(True, fps=args.fps, out_fps=args.out_fps, lookahead=la)),) + variants
+            if args.repair_joints is not None:
+                row.update(repair_joints=args.repair_joints, missing_joints=args.missing_joints,
+                           staged_frames=stream.staged_frames(args.repair_joints, ms))
+                variants = (("repair_graph", lambda: session(True, valid=seen, repair_joints=args.repair_joints)),
+                            ("md_graph", lambda: session(True, valid=seen.all(axis=2), missed_detections=True)))
             for key, fn in variants:
                 ts = np.asarray(fn())
                 row[key + "_us"] = round(1e6 * float(np.median(ts)), 1)
                 row[key + "_p90_us"] = round(1e6 * float(np.percentile(ts, 90)), 1)
-            if args.fps is None:
+            if args.repair_joints is not None:
+                row["repair_minus_md_us"] = round(row["repair_graph_us"] - row["md_graph_us"], 1)
+            elif args.fps is None:
                 row["speedup_vs_baseline"] = round(row["baseline_us"] / row["graph_us"], 2)
             else:
                 row["push_over_model_tick"] = round(row["fps_graph_us"] / row["graph_us"], 2)

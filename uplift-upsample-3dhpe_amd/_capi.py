@@ -40,6 +40,7 @@ EXPORTED_SYMBOLS = (
     "uu3d_stream_rate_state_layout", "uu3d_stream_source_push", "uu3d_stream_resample_stage", "uu3d_stream_file_keyframe",
     "uu3d_stream_timed_emit", "uu3d_stream_rate_reset",
     "uu3d_stream_out_state_layout", "uu3d_stream_timed_emit_multi", "uu3d_stream_out_reset",
+    "uu3d_stream_repair_bytes", "uu3d_stream_repair_layout", "uu3d_stream_repair_stage", "uu3d_stream_commit_repair", "uu3d_stream_repair_reset",
 )
 # include/uu3d_ops.h
 OPS_SYMBOLS = (
@@ -107,6 +108,11 @@ class Uu3dStreamOut(C.Structure):
 
 class Uu3dStreamOutLayout(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("out_frames_offset", "bytes")]
+
+
+class Uu3dStreamRepairLayout(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("window", "staged_frames", "raw_offset", "last_xy_offset", "last_offset", "held_offset", "observed_offset",
+                                         "bytes")]
 
 
 # void (*uu3d_grad_ready_fn)(void* user, int64_t first, int64_t count, void* stream)
@@ -222,6 +228,16 @@ def load_library(path=None):
     lib.uu3d_stream_timed_emit_multi.argtypes = [vp, scfg, srate, sout, vp, vp, vp, vp]
     lib.uu3d_stream_out_reset.restype = C.c_int
     lib.uu3d_stream_out_reset.argtypes = [vp, scfg, srate, sout, vp, vp, vp]
+    lib.uu3d_stream_repair_bytes.restype = sz
+    lib.uu3d_stream_repair_bytes.argtypes = [vp, scfg, C.c_int32]
+    lib.uu3d_stream_repair_layout.restype = C.c_int
+    lib.uu3d_stream_repair_layout.argtypes = [vp, scfg, C.c_int32, C.POINTER(Uu3dStreamRepairLayout)]
+    lib.uu3d_stream_repair_stage.restype = C.c_int
+    lib.uu3d_stream_repair_stage.argtypes = [vp, scfg, C.c_int32] + [vp] * 13
+    lib.uu3d_stream_commit_repair.restype = C.c_int
+    lib.uu3d_stream_commit_repair.argtypes = [vp, scfg, C.c_int32] + [vp] * 11
+    lib.uu3d_stream_repair_reset.restype = C.c_int
+    lib.uu3d_stream_repair_reset.argtypes = [vp, scfg, C.c_int32, vp, vp, vp]
     lib.uu3d_stream_valid_bytes.restype = sz
     lib.uu3d_stream_valid_bytes.argtypes = [vp, scfg]
     lib.uu3d_stream_stage_valid.restype = C.c_int

@@ -2,7 +2,8 @@
 // the pose of frame `newest - lookahead` out.  Four small kernels around uu3d_frame_features and uu3d_forward_frames_ex:
 //   stream_stage_kernel   pushed pixel frames -> normalised frames and their mirrored copies (normalize_pair of uu3d_tracks.h)
 //   stream_commit_kernel  per slot: advance the frame counter, file the new frame's features (edge row, keyframe ring), write this tick's
-//                         window as feature-table rows and stride masks (window_frame of uu3d_misc.h: the one statement of the rules)
+//                         window as feature-table rows and stride masks (stream_write_window, shared with uu3d_stream_repair.h; window_frame
+//                         of uu3d_misc.h: the one statement of the rules)
 //   stream_emit_kernel    un-flip / average (window_prediction of uu3d_tracks.h), root shift, fresh slots written, the others held
 //   stream_reset_kernel   chosen slots back to zero frames and a zero held pose
 // All per-slot state sits in one caller-allocated block (StreamLayout).  No atomics, every output element has one writer, the counters are
@@ -95,6 +96,41 @@ stream_stage_kernel(const float* __restrict__ kp, const double* __restrict__ res
     else *reinterpret_cast<float2*>(out + p0 * 2) = v[0];
 }
 
+// The window of a tick, for stream_commit_kernel and stream_commit_repair_kernel (uu3d_stream_repair.h): slot `slot` has `len` frames after
+// this tick (act: it took one).  Writes the slot's rows (halves, N), stride masks and fresh byte; valid_state as in stream_commit_kernel.
+__device__ __forceinline__ void stream_write_window(const StreamParams& p, const int slot, const int tid, const int len, const bool act,
+                                                    const uint8_t* valid_state, int32_t* __restrict__ rows, uint8_t* __restrict__ stride_mask,
+                                                    uint8_t* __restrict__ fresh)
+{
+    const int centre = len - 1 - p.lookahead;
+    const bool is_fresh = act && centre >= 0 && centre % p.pred_stride == 0;
+    if (tid == 0) fresh[slot] = is_fresh ? 1 : 0;
+    const int oldest = centre - (p.N / 2) * p.seq_stride;               // nothing older is still in the ring for certain
+    for (int i = tid; i < p.halves * p.N; i += 256) {
+        const int half = i / p.N, n = i - half * p.N;
+        const size_t o = ((size_t)half * p.slots + slot) * p.N + n;
+        int r = p.masked_row;
+        uint8_t sm = 0;
+        if (is_fresh) {                                                  // (a slot that is not fresh: an all-masked window, finite and discarded)
+            const WindowDesc d{0, centre, p.seq_stride, p.s_in, centre, half};
+            const WindowFrame t = window_frame(d, len, p.N, n, p.pad_edge);
+            int place = -1;                                              // where the frame the token reads is kept, in half 0 of the table
+            if (t.sm && t.have) {
+                if (!t.inside && t.src == (len - 1) / p.seq_stride * p.seq_stride) place = stream_edge_row(p, 0, slot);
+                else if (t.src % p.s_in == 0 && t.src >= oldest && t.src >= 0 && t.src < len) place = stream_ring_row(p, 0, slot, t.src);
+            }
+            const bool real = window_token_real(t, place >= 0 ? valid_state : nullptr, place);
+            sm = real ? 1 : 0;
+            if (!real) r = p.masked_row;
+            else if (!t.have) r = p.zero_row;
+            else if (place >= 0) r = place + half * p.slots * (p.cap + 1);
+            else r = -1;                                                 // no such frame is kept: NaN in the forward, reported by its range check
+        }
+        rows[o] = r;
+        stride_mask[o] = sm;
+    }
+}
+
 // One workgroup per slot.  feats (halves * T, d_t): the features of this tick's staged frames.  The slot's counter is read by every
 // thread of ITS workgroup only, and written by one of them behind a barrier.  Rows written: rows (halves * T, N), stride_mask likewise,
 // fresh (T).  The window is the one uu3d_gather_window_frames writes for a video of `frames` frames centred on frames - 1 - lookahead with
@@ -130,33 +166,7 @@ stream_commit_kernel(const StreamParams p, const float* __restrict__ feats, cons
         }
     }
     if (valid_state != nullptr) __syncthreads();                         // (uniform: the bytes filed above are read below by other threads)
-    const int centre = len - 1 - p.lookahead;
-    const bool is_fresh = act && centre >= 0 && centre % p.pred_stride == 0;
-    if (tid == 0) fresh[slot] = is_fresh ? 1 : 0;
-    const int oldest = centre - (p.N / 2) * p.seq_stride;               // nothing older is still in the ring for certain
-    for (int i = tid; i < p.halves * p.N; i += 256) {
-        const int half = i / p.N, n = i - half * p.N;
-        const size_t o = ((size_t)half * p.slots + slot) * p.N + n;
-        int r = p.masked_row;
-        uint8_t sm = 0;
-        if (is_fresh) {                                                  // (a slot that is not fresh: an all-masked window, finite and discarded)
-            const WindowDesc d{0, centre, p.seq_stride, p.s_in, centre, half};
-            const WindowFrame t = window_frame(d, len, p.N, n, p.pad_edge);
-            int place = -1;                                              // where the frame the token reads is kept, in half 0 of the table
-            if (t.sm && t.have) {
-                if (!t.inside && t.src == (len - 1) / p.seq_stride * p.seq_stride) place = stream_edge_row(p, 0, slot);
-                else if (t.src % p.s_in == 0 && t.src >= oldest && t.src >= 0 && t.src < len) place = stream_ring_row(p, 0, slot, t.src);
-            }
-            const bool real = window_token_real(t, place >= 0 ? valid_state : nullptr, place);
-            sm = real ? 1 : 0;
-            if (!real) r = p.masked_row;
-            else if (!t.have) r = p.zero_row;
-            else if (place >= 0) r = place + half * p.slots * (p.cap + 1);
-            else r = -1;                                                 // no such frame is kept: NaN in the forward, reported by its range check
-        }
-        rows[o] = r;
-        stride_mask[o] = sm;
-    }
+    stream_write_window(p, slot, tid, len, act, valid_state, rows, stride_mask, fresh);
 }
 
 // central (halves * T, J, 3): the forward's central predictions of this tick's windows.  out (T, J, 3) and held (T, J, 3, in the state

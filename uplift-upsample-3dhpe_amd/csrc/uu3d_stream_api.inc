@@ -107,17 +107,22 @@ int stream_stage(uu3d_model* m, const uu3d_stream_config* s, const float* kp, co
                        kp, resolution, active, flip_order, s->slots, m->cfg.num_keypoints, halves, valid_in, valid_out, frames_out);
     return launched(m, "uu3d_stream_stage");
 }
+// what the commit kernels need to know about the session
+StreamParams stream_params(const uu3d_model* m, const uu3d_stream_config* s, const StreamLayout& L) {
+    StreamParams p{};
+    p.slots = s->slots; p.N = m->cfg.num_frames; p.dt = m->cfg.d_temporal; p.seq_stride = s->seq_stride; p.s_in = s->mask_stride;
+    p.pred_stride = s->pred_stride; p.lookahead = s->lookahead; p.cap = L.cap; p.halves = L.halves; p.pad_edge = s->pad_edge != 0;
+    p.zero_row = (int)L.zero_row;
+    p.masked_row = m->cfg.has_strided_input ? -1 : (int)L.zero_row;      // (no strided input: a dropped frame is read as zeros, eval.py:67)
+    return p;
+}
 // uu3d_stream_commit (valid == valid_state == nullptr) and uu3d_stream_commit_valid
 int stream_commit(uu3d_model* m, const uu3d_stream_config* s, const StreamCall& c, const float* features, const uint8_t* active, const uint8_t* valid,
                   uint8_t* valid_state, int32_t* rows, uint8_t* stride_mask, uint8_t* fresh, void* stream) {
     if (!c.base || !features || !active || !rows || !stride_mask || !fresh) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_commit: null buffer");
     if (((uintptr_t)c.base & 255) != 0 || ((uintptr_t)features & 15) != 0) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_commit: state must be 256-byte, features 16-byte aligned");
     const StreamLayout& L = c.L;
-    StreamParams p{};
-    p.slots = s->slots; p.N = m->cfg.num_frames; p.dt = m->cfg.d_temporal; p.seq_stride = s->seq_stride; p.s_in = s->mask_stride;
-    p.pred_stride = s->pred_stride; p.lookahead = s->lookahead; p.cap = L.cap; p.halves = L.halves; p.pad_edge = s->pad_edge != 0;
-    p.zero_row = (int)L.zero_row;
-    p.masked_row = m->cfg.has_strided_input ? -1 : (int)L.zero_row;      // (no strided input: a dropped frame is read as zeros, eval.py:67)
+    const StreamParams p = stream_params(m, s, L);
     hipLaunchKernelGGL(stream_commit_kernel, dim3(s->slots), dim3(256), 0, (hipStream_t)stream, p, features, active,
                        (int32_t*)(c.base + L.off_frames), (float*)(c.base + L.off_table), rows, stride_mask, fresh, valid, valid_state);
     return launched(m, "uu3d_stream_commit");
@@ -180,6 +185,83 @@ int uu3d_stream_reset(uu3d_model* m, const uu3d_stream_config* s, void* state, c
     hipLaunchKernelGGL(stream_reset_kernel, blocks_of((long)s->slots * c.L.per_pose), dim3(256), 0, (hipStream_t)stream, slot_mask, s->slots,
                        c.L.per_pose, (int32_t*)(c.base + c.L.off_frames), (float*)(c.base + c.L.off_held));
     return launched(m, "uu3d_stream_reset");
+}
+
+// ---- live per-joint missed detections (uu3d_stream_repair.h): the repair state and the two launches that replace stage and commit ----
+namespace {
+// max_gap and the model behind stream_resolve -> the layout of the repair state and the stage kernel's parameters
+int stream_repair_resolve(uu3d_model* m, const uu3d_stream_config* s, const int32_t max_gap, const char* who, StreamCall& c, RepairLayout& R, RepairParams& p) {
+    if (const int st = stream_resolve(m, s, nullptr, nullptr, nullptr, 0, who, c)) return st;
+    if (const int st = stream_valid_check(m, who)) return st;
+    if (max_gap < 1 || max_gap > kLiveRepairMaxGap) return fail(m, UU3D_ERR_INVALID_ARGUMENT, std::string(who) + ": max_gap must be in [1, 32]");
+    R = repair_layout(s->slots, m->cfg.num_keypoints, s->mask_stride, max_gap);
+    if ((int64_t)c.L.halves * s->slots * R.K > INT32_MAX / 2) return fail(m, UU3D_ERR_INVALID_ARGUMENT, std::string(who) + ": slots x staged frames too large");
+    p = RepairParams{s->slots, m->cfg.num_keypoints, max_gap, R.W, R.K, s->mask_stride, s->seq_stride, c.L.halves};
+    return UU3D_OK;
+}
+}  // namespace
+
+int uu3d_stream_repair_layout(const uu3d_model* mc, const uu3d_stream_config* s, int32_t max_gap, uu3d_stream_repair_state_layout* out) {
+    auto* m = const_cast<uu3d_model*>(mc);
+    if (!m || !out) return UU3D_ERR_INVALID_ARGUMENT;
+    StreamCall c; RepairLayout R; RepairParams p;
+    if (const int st = stream_repair_resolve(m, s, max_gap, "uu3d_stream_repair_layout", c, R, p)) return st;
+    out->window = R.W; out->staged_frames = R.K; out->raw_offset = (int64_t)R.off_raw; out->last_xy_offset = (int64_t)R.off_last_xy;
+    out->last_offset = (int64_t)R.off_last; out->held_offset = (int64_t)R.off_held; out->observed_offset = (int64_t)R.off_observed;
+    out->bytes = (int64_t)R.bytes;
+    return UU3D_OK;
+}
+
+size_t uu3d_stream_repair_bytes(const uu3d_model* m, const uu3d_stream_config* s, int32_t max_gap) {
+    uu3d_stream_repair_state_layout l;
+    return uu3d_stream_repair_layout(m, s, max_gap, &l) == UU3D_OK ? (size_t)l.bytes : 0;
+}
+
+int uu3d_stream_repair_stage(uu3d_model* m, const uu3d_stream_config* s, int32_t max_gap, const void* state, void* repair_state, const float* kp,
+                             const double* resolution, const uint8_t* active, const int32_t* flip_order, const uint8_t* joint_flags,
+                             float* frames_out, int32_t* stage_frame, uint8_t* stage_valid, int32_t* far_frames, uint8_t* joint_state, void* stream) {
+    if (!m) return UU3D_ERR_INVALID_ARGUMENT;
+    StreamCall c; RepairLayout R; RepairParams p;
+    if (const int st = stream_repair_resolve(m, s, max_gap, "uu3d_stream_repair_stage", c, R, p)) return st;
+    if (!state || !repair_state || !kp || !active || !frames_out || !stage_frame || !stage_valid || !far_frames || !joint_state || (s->flip && !flip_order))
+        return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_repair_stage: null buffer");
+    if (((uintptr_t)state & 255) != 0 || ((uintptr_t)repair_state & 255) != 0 || ((uintptr_t)frames_out & 15) != 0 || ((uintptr_t)kp & 7) != 0)
+        return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_repair_stage: state and repair_state must be 256-byte, frames_out 16-byte, kp 8-byte aligned");
+    char* rb = (char*)repair_state;
+    hipLaunchKernelGGL(stream_repair_stage_kernel, dim3(s->slots), dim3(64), 0, (hipStream_t)stream, p, kp, resolution, active, flip_order, joint_flags,
+                       (const int32_t*)((const char*)state + c.L.off_frames), (float*)(rb + R.off_raw), (float*)(rb + R.off_last_xy),
+                       (int32_t*)(rb + R.off_last), (uint32_t*)(rb + R.off_held), (uint8_t*)(rb + R.off_observed), frames_out, stage_frame,
+                       stage_valid, far_frames, joint_state);
+    return launched(m, "uu3d_stream_repair_stage");
+}
+
+int uu3d_stream_commit_repair(uu3d_model* m, const uu3d_stream_config* s, int32_t max_gap, void* state, const float* features, const uint8_t* active,
+                              const int32_t* stage_frame, const uint8_t* stage_valid, const int32_t* far_frames, void* valid_state, int32_t* rows,
+                              uint8_t* stride_mask, uint8_t* fresh, void* stream) {
+    if (!m) return UU3D_ERR_INVALID_ARGUMENT;
+    StreamCall c; RepairLayout R; RepairParams rp;
+    if (const int st = stream_repair_resolve(m, s, max_gap, "uu3d_stream_commit_repair", c, R, rp)) return st;
+    if (!state || !features || !active || !stage_frame || !stage_valid || !far_frames || !valid_state || !rows || !stride_mask || !fresh)
+        return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_commit_repair: null buffer");
+    if (((uintptr_t)state & 255) != 0 || ((uintptr_t)features & 15) != 0)
+        return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_commit_repair: state must be 256-byte, features 16-byte aligned");
+    c.base = (char*)state;
+    const StreamParams p = stream_params(m, s, c.L);
+    hipLaunchKernelGGL(stream_commit_repair_kernel, dim3(s->slots), dim3(256), 0, (hipStream_t)stream, p, R.K, max_gap, features, active,
+                       (int32_t*)(c.base + c.L.off_frames), (float*)(c.base + c.L.off_table), stage_frame, stage_valid, far_frames, rows, stride_mask,
+                       fresh, (uint8_t*)valid_state);
+    return launched(m, "uu3d_stream_commit_repair");
+}
+
+int uu3d_stream_repair_reset(uu3d_model* m, const uu3d_stream_config* s, int32_t max_gap, void* repair_state, const uint8_t* slot_mask, void* stream) {
+    if (!m) return UU3D_ERR_INVALID_ARGUMENT;
+    StreamCall c; RepairLayout R; RepairParams p;
+    if (const int st = stream_repair_resolve(m, s, max_gap, "uu3d_stream_repair_reset", c, R, p)) return st;
+    if (!repair_state || ((uintptr_t)repair_state & 255) != 0) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_repair_reset: repair_state must be a 256-byte aligned block");
+    char* rb = (char*)repair_state;
+    hipLaunchKernelGGL(stream_repair_reset_kernel, blocks_of((long)s->slots * p.J), dim3(256), 0, (hipStream_t)stream, slot_mask, s->slots, p.J,
+                       (int32_t*)(rb + R.off_last), (uint32_t*)(rb + R.off_held));
+    return launched(m, "uu3d_stream_repair_reset");
 }
 
 // ---- a session with a frame rate (uu3d_stream_rate.h): the state behind the plain session's and the launches around its sub-ticks ----

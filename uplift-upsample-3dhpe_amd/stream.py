@@ -57,8 +57,22 @@ poses a second, five per push.  Input and model sides, ``lookahead`` (SOURCE fra
           frame is later than source frame q -- which the enumeration checks as well (``rate_plan``, ``out_push_plan``).
 One launch (uu3d_stream_timed_emit_multi) in place of uu3d_stream_timed_emit; ``out_fps=None`` is the session above, bit for bit.
 
+Live per-joint missed detections -- ``StreamSession(..., repair_joints=G)``: ``push(valid=...)`` takes one flag per JOINT and a joint the
+detector lost is filled by the rule of ``predict.repair_joints_host``.  The one rule above is unchanged: the pose of frame t - lookahead is
+what ``predict_tracks(track[:t + 1], valid=flags[:t + 1], repair_joints=G)`` gives for it -- a closed gap interpolated, a trailing or leading
+gap held for up to G frames.  The rule looks ahead, so a push may REVISE frames the session has filed, within bounds:
+  near    coordinates change only for frames t - G .. t (a gap of at most G frames closes at t: held -> interpolated; a joint is seen for
+          the first time at t: unfilled -> held from t).  Of those the ring keeps the multiples of s_in and the edge frame, at most
+          K = G // s_in + 2 frames: the tick re-stages them (uu3d_stream_repair_stage), runs uu3d_frame_features over slots x K (x 2
+          with flip) frames and files K rows (uu3d_stream_commit_repair).
+  far     an older frame only ever goes from valid to missing (a gap longer than G closes at t: the frames held from its left end become
+          unfillable): a byte of the validity state, no features.
+The state this needs is bounded; ``LiveRepairHost`` is the state machine the device runs, in numpy.  G <= 32 (``MAX_LIVE_REPAIR``: K and
+the buffers are fixed at construction).  Not together with ``fps`` / ``out_fps``: a revised source frame would re-make model frames that
+were filed already (a later change).  ``repair_joints=None`` is the session above, bit for bit.
+
     python -m uplift_upsample_3dhpe_amd.stream --config C --weights W.h5 --input tracks.npz --output out.npz [--lookahead A] [--resolution W H]
-                                                 [--mask_missing] [--fps F [--out_fps G]]
+                                                 [--mask_missing] [--fps F [--out_fps G]] [--repair_joints G [--min_score S]]
 """
 import argparse
 import ctypes as C
@@ -69,7 +83,7 @@ import numpy as np
 
 from . import _capi
 from ._capi import ptr as _ptr
-from .predict import _load_model, check_resolutions, check_valid
+from .predict import _load_model, check_repair_joints, check_resolutions, check_valid, split_scores
 from .rates import (RatePlan, _rate_argument, max_lookahead, newest_model_frame, out_push_plan, push_plan,  # noqa: F401 (re-exported)
                     rate_plan, session_strides)
 
@@ -126,10 +140,122 @@ def window_plan(frames, lookahead, config, mask_stride=None, valid=None):
             "place": np.where(kind == 2, (src // s_in) % cap, -1)}
 
 
+MAX_LIVE_REPAIR = 32                                                  # the largest repair_joints of a live session (kLiveRepairMaxGap)
+
+
+def staged_frames(repair_joints, mask_stride):
+    """K: frames a session with ``repair_joints`` re-stages per slot and tick -- the multiples of s_in among G + 1 consecutive frames and
+    the edge frame."""
+    return int(repair_joints) // int(mask_stride) + 2
+
+
+def _live_option(options, name, who):
+    """The one keyword ``name`` out of the ``**options`` of ``who`` (None when it is not given); any other keyword is the TypeError Python
+    itself raises for an unknown argument."""
+    unknown = sorted(k for k in options if k != name)
+    if unknown:
+        raise TypeError(f"{who}() got an unexpected keyword argument {unknown[0]!r}")
+    return options.get(name)
+
+
+class LiveRepairHost(object):
+    """The incremental state machine of uu3d_stream_repair_stage for ONE slot, in numpy, written to be read: ``predict.repair_joints_host``
+    on the growing track, one frame per ``step``, from a bounded state --
+        raw, observed   the raw coordinates and observed flags of the newest G + 1 frames (frame f at place f % (G + 1));
+        last, last_xy   per joint the last observation that has LEFT that window, as index (-1: the joint was not seen before the window)
+                        and coordinates;
+        held            per joint G bits: bit k = frame last + 1 + k has left the window as a valid frame in which the joint was held
+                        from ``last`` -- the frames a gap longer than G turns missing when it closes.
+    ``step(frame (J, 2) float32, flags (J,) bool)`` -> (staged, far): ``staged`` lists (frame index, repaired raw (J, 2) float32,
+    frame_valid, state (J,) uint8) for the frames this tick re-stages -- with t the frame pushed, the multiples of ``s_in`` in
+    [max(0, t - G), t], oldest first, then the edge frame (t // seq_stride * seq_stride) where it lies in that range and is no multiple
+    of ``s_in``; with s_in = 1 every frame of the range --, ``far`` the older frames that this tick turns from valid to missing, ascending.
+    The repaired frame is ``repair_joints_host``'s (zeros for a joint it cannot fill); the device stages zeros for a frame that is not valid."""
+
+    def __init__(self, J, G, s_in=1, seq_stride=1):
+        self.J, self.G, self.W, self.s_in, self.seq_stride = int(J), int(G), int(G) + 1, int(s_in), int(seq_stride)
+        if not 1 <= self.G <= MAX_LIVE_REPAIR:
+            raise ValueError(f"G must be in [1, {MAX_LIVE_REPAIR}]")
+        self.frames = 0
+        self.raw = np.zeros((self.W, self.J, 2), np.float32)
+        self.observed = np.zeros((self.W, self.J), bool)
+        self.last = np.full(self.J, -1, np.int64)
+        self.last_xy = np.zeros((self.J, 2), np.float32)
+        self.held = [0] * self.J
+
+    def _joint(self, f, j, lo, newest):
+        """Joint j of frame f under the rule, seen from the frames lo .. newest of the window and ``last`` -> (xy, state)."""
+        G, W, src = self.G, self.W, self.raw
+        if self.observed[f % W, j]:
+            return src[f % W, j], 1
+        before = [g for g in range(lo, f) if self.observed[g % W, j]]
+        after = [g for g in range(f + 1, newest + 1) if self.observed[g % W, j]]
+        l, a = (before[-1], src[before[-1] % W, j]) if before else (int(self.last[j]), self.last_xy[j])
+        r = after[0] if after else None
+        if l >= 0 and r is not None:
+            if r - l - 1 <= G:
+                w = np.float64(f - l) / np.float64(r - l)
+                return (a.astype(np.float64) * (1.0 - w) + src[r % W, j].astype(np.float64) * w).astype(np.float32), 2
+        elif r is not None:
+            if r - f <= G:
+                return src[r % W, j], 2
+        elif l >= 0:
+            if f - l <= G:
+                return a, 2
+        return np.zeros(2, np.float32), 0
+
+    def _frame(self, f, lo, newest):
+        """Frame f under the rule -> (repaired (J, 2) float32, frame_valid, state (J,) uint8)."""
+        out, state = np.zeros((self.J, 2), np.float32), np.zeros(self.J, np.uint8)
+        for j in range(self.J):
+            out[j], state[j] = self._joint(f, j, lo, newest)
+        valid = bool((state == 1).any() and (state != 0).all())
+        return out, valid, state
+
+    def step(self, frame, flags):
+        G, W, J, t = self.G, self.W, self.J, self.frames
+        frame = np.asarray(frame, np.float32).reshape(J, 2)
+        seen_now = (np.asarray(flags).reshape(J) != 0) & np.isfinite(frame).all(axis=1)
+        # 1. frame e leaves the window: what it is under the frames up to t - 1 stays, but for the far list
+        e = t - G - 1
+        if e >= 0:
+            _, valid_e, _ = self._frame(e, e, t - 1)
+            for j in range(J):
+                if self.observed[e % W, j]:
+                    self.last[j], self.last_xy[j], self.held[j] = e, self.raw[e % W, j], 0
+                elif valid_e and self.last[j] >= 0 and e - self.last[j] <= G:
+                    self.held[j] |= 1 << (e - int(self.last[j]) - 1)
+        # 2. file the pushed frame (the place frame e had)
+        self.raw[t % W], self.observed[t % W] = frame, seen_now
+        # 3. a joint seen again after more than G frames: the frames it was held in turn missing
+        lo = max(0, t - G)
+        far = set()
+        for j in range(J):
+            if seen_now[j] and self.last[j] >= 0 and t - self.last[j] - 1 > G and not self.observed[[g % W for g in range(lo, t)], j].any():
+                far |= {int(self.last[j]) + 1 + k for k in range(G) if self.held[j] >> k & 1}
+                self.held[j] = 0
+        for f in far:                                                 # no longer valid frames, for any joint's bits
+            for j in range(J):
+                if self.last[j] >= 0 and 0 <= f - self.last[j] - 1 < G:
+                    self.held[j] &= ~(1 << (f - int(self.last[j]) - 1))
+        # 4. the frames to re-stage
+        cand = [f for f in range(lo, t + 1) if f % self.s_in == 0]
+        edge = t // self.seq_stride * self.seq_stride
+        if edge >= lo and edge % self.s_in != 0:
+            cand.append(edge)
+        self.frames = t + 1
+        return [(f,) + self._frame(f, lo, t) for f in cand], sorted(far)
+
+    def newest_state(self):
+        """(J,) uint8: the state of the newest frame (``StreamSession.joint_state``)."""
+        t = self.frames - 1
+        return self._frame(t, max(0, t - self.G), t)[2]
+
+
 class StreamSession(object):
 
     def __init__(self, model, config, slots, resolutions=None, mask_stride=None, flip=None, lookahead=0, root_relative=True, graph=True,
-                 missed_detections=False, fps=None, model_fps=50, out_fps=None):
+                 missed_detections=False, fps=None, model_fps=50, out_fps=None, **options):
         """``slots``: tracks served side by side (a slot is a track: ``reset`` starts a new one).  ``resolutions``: None = the coordinates
         are normalised already, else one (w, h) in pixels or one per slot.  ``mask_stride`` / ``flip`` / ``root_relative`` as
         ``predict.predict_tracks``.  ``lookahead`` = a: frames the answer may lag behind the newest one, 0 <= a <=
@@ -148,8 +274,13 @@ class StreamSession(object):
         ``out_fps``: None = one pose per push, at the source frame's own time (the session above, bit for bit).  Else the rate of the poses
         the session returns, parsed like ``fps`` (which it needs: ValueError without): the module docstring's "Live upsampling".  ``push``
         then returns (poses (slots, max_out, J, 3), count (slots,) int32), ``max_out`` = ceil(out_fps / fps) <= 64, and ``out_frames``
-        counts the output frames per slot."""
-        res = self._init_plan(model, config, slots, resolutions, mask_stride, flip, lookahead, graph, missed_detections, fps, model_fps, out_fps)
+        counts the output frames per slot.
+        ``repair_joints`` (keyword only, taken from ``options``; any other name there is a TypeError): None = a missing joint makes its frame missing (the session above, bit for bit).  Else G, an int in
+        [1, ``MAX_LIVE_REPAIR``]: the module docstring's "Live per-joint missed detections".  Implies ``missed_detections=True``;
+        ``push(valid=...)`` may then hold one flag per joint and ``joint_state`` tells what became of the newest frame's joints.  Not
+        together with ``fps`` / ``out_fps`` (ValueError)."""
+        res = self._init_plan(model, config, slots, resolutions, mask_stride, flip, lookahead, graph, missed_detections, fps, model_fps, out_fps,
+                              _live_option(options, "repair_joints", "StreamSession"))
         import torch
         self._torch = torch
         self._lib = _capi.load_library()
@@ -162,11 +293,19 @@ class StreamSession(object):
                 self._capture()
 
     # ---- construction: checks and plan, layout and state, buffers, launch tables (then the capture) ---------------------------------
-    def _init_plan(self, model, config, slots, resolutions, mask_stride, flip, lookahead, graph, missed_detections, fps, model_fps, out_fps):
+    def _init_plan(self, model, config, slots, resolutions, mask_stride, flip, lookahead, graph, missed_detections, fps, model_fps, out_fps,
+                   repair_joints=None):
         """Every refusal that needs no device, and the session's plan.  -> the checked resolutions."""
         slots, lookahead = int(slots), int(lookahead)
         if slots < 1:
             raise ValueError("slots >= 1")
+        check_repair_joints(repair_joints, "finite")
+        if repair_joints is not None and int(repair_joints) > MAX_LIVE_REPAIR:
+            raise ValueError(f"repair_joints must be at most {MAX_LIVE_REPAIR} in a live session (the frames a tick re-stages and its buffers are "
+                             f"fixed when the session is made), got {repair_joints}")
+        if repair_joints is not None and (fps is not None or out_fps is not None):
+            raise ValueError("repair_joints together with fps / out_fps is not supported yet: a revised source frame would re-make model frames "
+                             "that were filed already")
         if out_fps is not None and fps is None:
             raise ValueError("out_fps needs fps: the rate of the pushed frames")
         S, s_in, pred = session_strides(config, mask_stride)
@@ -178,7 +317,9 @@ class StreamSession(object):
         if not model.arch.compiled_dims:
             raise NotImplementedError("StreamSession needs the frames form of the forward (uu3d_frame_features / uu3d_forward_frames_ex), "
                                       "which models with generic dims do not have")
-        self.missed_detections = bool(missed_detections)
+        self.repair_joints = None if repair_joints is None else int(repair_joints)
+        self.staged_frames = 1 if repair_joints is None else staged_frames(repair_joints, s_in)     # K: frames staged per slot and tick
+        self.missed_detections = bool(missed_detections) or repair_joints is not None
         if self.missed_detections and not model.has_strided_input:
             raise ValueError("missed_detections needs a model with strided input: a missing frame becomes the learned masked token")
         self.model, self.slots, self.lookahead, self.graph = model, slots, lookahead, bool(graph)
@@ -204,13 +345,20 @@ class StreamSession(object):
         if self.max_out is not None:
             self._outp, olay = _capi.Uu3dStreamOut(r.out_c, r.out_d, r.pos_num, r.pos_den, r.max_out), _capi.Uu3dStreamOutLayout()
             _capi.check(lib, lib.uu3d_stream_out_state_layout(h, C.byref(self._cfg), C.byref(self._rate), C.byref(self._outp), C.byref(olay)), h)
+        self._repair_bytes = 0
+        if self.repair_joints is not None:
+            play = _capi.Uu3dStreamRepairLayout()
+            _capi.check(lib, lib.uu3d_stream_repair_layout(h, C.byref(self._cfg), self.repair_joints, C.byref(play)), h)
+            if int(play.staged_frames) != self.staged_frames:
+                raise AssertionError("the library and stream.staged_frames disagree")
+            self._repair_bytes = int(play.bytes)
         return lay, rlay, olay
 
     def _init_buffers(self, config, res, lay, rlay, olay):
         """The state block and the buffers of a tick; then what a session with missed detections, with a rate and with an output rate adds."""
         torch, lib, m = self._torch, self._lib, self.model
         a, dev = m.arch, m.device
-        T, J, N, dt, H = self.slots, a.num_keypoints, a.num_frames, a.d_temporal, 2 if self.flip else 1
+        T, J, N, dt, H, K = self.slots, a.num_keypoints, a.num_frames, a.d_temporal, 2 if self.flip else 1, self.staged_frames
         zeros = functools.partial(torch.zeros, device=dev)
         self._state = zeros(int((olay or rlay or lay).bytes), dtype=torch.uint8)
         view = lambda off, n, dtype: self._state[off:off + n * 4].view(dtype)
@@ -222,8 +370,8 @@ class StreamSession(object):
         self._active_all = True
         self._res = None if res is None else torch.from_numpy(res).pin_memory().to(dev, non_blocking=True)
         self._order = torch.from_numpy(np.ascontiguousarray(config.AUGM_FLIP_KEYPOINT_ORDER, np.int32)).to(dev) if self.flip else None
-        self._staged = zeros((H * T, J, 2), dtype=torch.float32)
-        self._feats = zeros((H * T, dt), dtype=torch.float32)
+        self._staged = zeros((H * T * K, J, 2), dtype=torch.float32)   # (K = 1 without repair_joints)
+        self._feats = zeros((H * T * K, dt), dtype=torch.float32)
         self._rows = torch.full((H * T, N), -1, dtype=torch.int32, device=dev)
         self._mask = zeros((H * T, N), dtype=torch.uint8)
         self._fresh = zeros((T,), dtype=torch.uint8)
@@ -231,15 +379,23 @@ class StreamSession(object):
         self._central = zeros((H * T, J, 3), dtype=torch.float32)
         self._out = zeros((T, J, 3), dtype=torch.float32)
         # a workspace of the session's own for uu3d_frame_features: the graph holds its address
-        self._fws = torch.empty(max(int(lib.uu3d_frame_features_bytes(m._h, H * T)), int(lib.uu3d_frame_features_bytes(m._h, 1))),
+        self._fws = torch.empty(max(int(lib.uu3d_frame_features_bytes(m._h, H * T * K)), int(lib.uu3d_frame_features_bytes(m._h, 1))),
                                 dtype=torch.uint8, device=dev)
         # missed detections: the caller's flags of this tick, the same ANDed with active and the finite test (stage), the flags kept per slot
         self._valid_in = self._valid = self._valid_state = None
         self._valid_in_all = True
         if self.missed_detections:
-            self._valid_in = torch.ones((T,), dtype=torch.uint8, device=dev)
+            self._valid_in = torch.ones((T, J) if self.repair_joints is not None else (T,), dtype=torch.uint8, device=dev)
             self._valid = zeros((T,), dtype=torch.uint8)
             self._valid_state = zeros(int(lib.uu3d_stream_valid_bytes(m._h, C.byref(self._cfg))), dtype=torch.uint8)
+        # repair_joints: the repair state, what the stage hands to the commit (frames staged, their flags, the far list), the joint states
+        if self.repair_joints is not None:
+            G = self.repair_joints
+            self._repair_state = zeros(self._repair_bytes, dtype=torch.uint8)
+            self._stage_frame = torch.full((T, K), -1, dtype=torch.int32, device=dev)
+            self._stage_valid = zeros((T, K), dtype=torch.uint8)
+            self._far = torch.full((T, G), -1, dtype=torch.int32, device=dev)
+            self._joint_state = zeros((T, J), dtype=torch.uint8)
         # what a (sub-)tick takes as `active` and where its emit writes: with a rate the sub-ticks' own buffers, else the session's
         self._tick_active, self._emit_out, self._emit_fresh = self._active, self._out, self._fresh
         self._source_frames, self._src_host, self._src_known = self._frames, None, None
@@ -262,7 +418,8 @@ class StreamSession(object):
         session as (library function, its arguments up to the stream); a step whose arguments are None is a Python callable of the stream.
           _tick_steps   the steps of one (sub-)tick, in order -- what the graph captures
           _push_before  / _push_after   the launches of a push around its sub-ticks (a session with a rate; not captured)
-          _reset_call   the reset of the session's kind; the slot mask and the stream follow its arguments"""
+          _reset_call   the reset of the session's kind; the slot mask and the stream follow its arguments (_reset_more: what a session
+                        with repair_joints resets beside it)"""
         lib, m = self._lib, self.model
         h, cfg, state = m._h, C.byref(self._cfg), _ptr(self._state)
         kp, res, order, active, staged = _ptr(self._kp), _ptr(self._res), _ptr(self._order), _ptr(self._active), _ptr(self._staged)
@@ -271,12 +428,18 @@ class StreamSession(object):
         if self.rate is not None:
             rate = C.byref(self._rate)
             stage = (lib.uu3d_stream_resample_stage, (h, cfg, rate, state, res, order, tick_active, valid, staged))
+        elif self.repair_joints is not None:
+            G, handed = self.repair_joints, (_ptr(self._stage_frame), _ptr(self._stage_valid), _ptr(self._far))
+            stage = (lib.uu3d_stream_repair_stage, (h, cfg, G, state, _ptr(self._repair_state), kp, res, active, order, _ptr(self._valid_in), staged)
+                     + handed + (_ptr(self._joint_state),))
         elif self.missed_detections:
             stage = (lib.uu3d_stream_stage_valid, (h, cfg, kp, res, active, order, _ptr(self._valid_in), valid, staged))
         else:
             stage = (lib.uu3d_stream_stage, (h, cfg, kp, res, active, order, staged))
         features = (lib.uu3d_frame_features, (h, staged, int(self._staged.shape[0]), feats, _ptr(self._fws), C.c_size_t(self._fws.numel()), 0))
-        if self.missed_detections:
+        if self.repair_joints is not None:
+            commit = (lib.uu3d_stream_commit_repair, (h, cfg, G, state, feats, tick_active) + handed + (_ptr(self._valid_state), rows, mask, emit_fresh))
+        elif self.missed_detections:
             commit = (lib.uu3d_stream_commit_valid, (h, cfg, state, feats, tick_active, valid, _ptr(self._valid_state), rows, mask, emit_fresh))
         else:
             commit = (lib.uu3d_stream_commit, (h, cfg, state, feats, tick_active, rows, mask, emit_fresh))
@@ -287,6 +450,7 @@ class StreamSession(object):
         self._tick_steps = [stage, features, commit, forward, emit]
         self._push_before, self._push_after = [], []
         self._reset_call = (lib.uu3d_stream_reset, (h, cfg, state))
+        self._reset_more = [] if self.repair_joints is None else [(lib.uu3d_stream_repair_reset, (h, cfg, self.repair_joints, _ptr(self._repair_state)))]
         if self.rate is not None:
             self._tick_steps.append((lib.uu3d_stream_file_keyframe, (h, cfg, rate, state, emit_fresh)))
             self._push_before = [(lib.uu3d_stream_source_push, (h, cfg, rate, state, kp, active, _ptr(self._valid_in), int(self.missed_detections)))]
@@ -344,15 +508,18 @@ class StreamSession(object):
         self.reset()
 
     # ---- public ---------------------------------------------------------------------------------------------------------------------
-    def _flags(self, flags, name):
-        """(slots,) flags from the host or the device -> a uint8 tensor, pinned when it is on the host."""
+    def _flags(self, flags, name, joints=None):
+        """(slots,) flags from the host or the device -> a uint8 tensor, pinned when it is on the host.  ``joints`` = J: (slots, J) passes as
+        well and (slots,) comes back as (slots, 1) -- one flag for all joints of a slot, for a copy that broadcasts on the device."""
         torch = self._torch
         if isinstance(flags, torch.Tensor):
             f = flags.to(torch.uint8) if flags.dtype != torch.bool else flags.view(torch.uint8)
         else:
             f = torch.from_numpy(np.ascontiguousarray(np.asarray(flags) != 0).view(np.uint8))
-        if tuple(f.shape) != (self.slots,):
-            raise ValueError(f"{name} must be ({self.slots},)")
+        if tuple(f.shape) != (self.slots,) and (joints is None or tuple(f.shape) != (self.slots, joints)):
+            raise ValueError(f"{name} must be ({self.slots},)" + ("" if joints is None else f" or ({self.slots}, {joints})"))
+        if joints is not None and f.dim() == 1:
+            f = f.reshape(self.slots, 1) if f.is_cuda else f.reshape(self.slots, 1).repeat(1, joints)
         return f if f.is_cuda else f.contiguous().pin_memory()
 
     def push(self, kp2d, active=None, valid=None):
@@ -363,6 +530,8 @@ class StreamSession(object):
         ``valid`` (slots,) flags or None (sessions built with ``missed_detections=True`` only): 0 = slot i's frame of this tick is MISSING, as
         is a row of ``kp2d`` with a NaN or Inf coordinate.  The slot's track grows by the frame all the same (``frames`` counts it; with
         ``active[i] == 0`` it would not) and a pose comes out by the usual rule, from windows that never read the missing frame.
+        A session with ``repair_joints``: ``valid`` may also be (slots, J), one flag per joint, ANDed with the finite test per joint; a
+        joint that is not observed is filled by the rule where it can be, and only a frame with a joint that cannot is missing.
         A session with ``fps``: ``kp2d`` holds one SOURCE frame per slot; ``poses[i]`` is the pose of slot i's source frame
         ``source_frames[i] - 1 - lookahead`` and ``fresh[i]`` is set at every push of an active slot once that index is >= 0.  The push
         enqueues uu3d_stream_source_push, n replays of the one sub-tick graph and uu3d_stream_timed_emit; n is the largest number of model
@@ -398,7 +567,7 @@ class StreamSession(object):
                 self._active.copy_(self._flags(active, "active"), non_blocking=True)
                 self._active_all = False
             if valid is not None:
-                self._valid_in.copy_(self._flags(valid, "valid"), non_blocking=True)
+                self._valid_in.copy_(self._flags(valid, "valid", None if self.repair_joints is None else self._kp.shape[1]), non_blocking=True)
                 self._valid_in_all = False
             elif not self._valid_in_all:
                 self._valid_in.fill_(1)
@@ -431,8 +600,8 @@ class StreamSession(object):
         return n
 
     def reset(self, slots=None):
-        """The given slots (indices; None = all) start a new track: zero frames, held pose 0, with ``out_fps`` output counter 0.  Stream-ordered
-        like ``push``."""
+        """The given slots (indices; None = all) start a new track: zero frames, held pose 0, with ``out_fps`` output counter 0, with
+        ``repair_joints`` no observation of any joint.  Stream-ordered like ``push``."""
         torch = self._torch
         m = self.model
         mask = None
@@ -441,8 +610,7 @@ class StreamSession(object):
                 h = np.zeros(self.slots, np.uint8)
                 h[np.asarray(slots, np.int64).reshape(-1)] = 1
                 mask = torch.from_numpy(h).pin_memory().to(m.device, non_blocking=True)
-            fn, args = self._reset_call
-            self._run([(fn, args + (_ptr(mask),))], torch.cuda.current_stream(m.device))
+            self._run([(fn, args + (_ptr(mask),)) for fn, args in [self._reset_call] + self._reset_more], torch.cuda.current_stream(m.device))
         self._mirror_reset(slots)
 
     def _mirror_reset(self, slots):
@@ -462,6 +630,14 @@ class StreamSession(object):
     def source_frames(self):
         """Source frames pushed per slot since its last reset, (slots,) int32 on the device; without ``fps`` the same tensor as ``frames``."""
         return self._source_frames
+
+    @property
+    def joint_state(self):
+        """(slots, J) uint8 on the device (sessions with ``repair_joints``): what became of the joints of each slot's newest frame, in the
+        coding of ``predict_tracks(return_valid=True)`` -- 1 observed, 2 filled (held from its last observation), 0 neither."""
+        if self.repair_joints is None:
+            raise AttributeError("joint_state needs a session with repair_joints")
+        return self._joint_state
 
     @property
     def out_frames(self):
@@ -492,25 +668,32 @@ class StreamSession(object):
 
 
 def replay_tracks(model, config, tracks, resolutions=None, mask_stride=None, flip=None, lookahead=0, root_relative=True, graph=True, valid=None, fps=None,
-                  model_fps=50, out_fps=None):
+                  model_fps=50, out_fps=None, **options):
     """Push complete tracks tick by tick, one slot per track (a slot is inactive once its track has ended) -> per track the pose the
     session returned at each of its ticks, (T_i, J, 3) float32, and the fresh flags (T_i,) bool, as host arrays.  One copy to the host,
     at the end.  ``valid`` as ``predict.predict_tracks``: None, "finite" (rows with a NaN / Inf coordinate are missing frames) or one (T_i,)
     host array per track -- a session with ``missed_detections=True``.  ``fps`` / ``model_fps``: the rate of the tracks, as ``StreamSession``.
     ``out_fps=G``: -> per track the poses the session emitted, concatenated in order, (n_out_i, J, 3) float32 -- output frames
-    0 .. n_out_i - 1 at G per second --, and the number each of its ticks returned, (T_i,) int32; still one copy to the host, at the end."""
+    0 .. n_out_i - 1 at G per second --, and the number each of its ticks returned, (T_i,) int32; still one copy to the host, at the end.
+    ``repair_joints=G`` (keyword only, taken from ``options``): a session with ``repair_joints`` (it needs ``valid``); an entry of ``valid`` may
+    then be (T_i, J), one flag per joint."""
     import torch
+    repair_joints = _live_option(options, "repair_joints", "replay_tracks")
     lens = [int(len(t)) for t in tracks]
     T, ticks = len(tracks), max(lens)
+    J = int(np.asarray(tracks[0]).shape[1])
+    check_repair_joints(repair_joints, valid)
     flags = None
     if valid is not None and not isinstance(valid, str):
-        check_valid(valid, lens)
-        flags = [np.asarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v).reshape(-1) != 0 for v in valid]
+        check_valid(valid, lens, joints=None if repair_joints is None else J)
+        flags = [np.asarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v) != 0 for v in valid]
+        if repair_joints is not None:                                # one flag per joint: a (T_i,) entry stands for all joints of its frames
+            flags = [f if f.ndim == 2 else np.repeat(f.reshape(-1, 1), J, axis=1) for f in flags]
     elif valid is not None and valid != "finite":
         raise ValueError('valid must be None, "finite" or a list with one (T_i,) array per track')
     s = StreamSession(model, config, T, resolutions=resolutions, mask_stride=mask_stride, flip=flip, lookahead=lookahead,
-                      root_relative=root_relative, graph=graph, missed_detections=valid is not None, fps=fps, model_fps=model_fps, out_fps=out_fps)
-    J = int(np.asarray(tracks[0]).shape[1])
+                      root_relative=root_relative, graph=graph, missed_detections=valid is not None, fps=fps, model_fps=model_fps, out_fps=out_fps,
+                      repair_joints=repair_joints)
     if out_fps is None:
         poses = torch.zeros((ticks, T, J, 3), dtype=torch.float32, device=model.device)
         fresh = torch.zeros((ticks, T), dtype=torch.bool, device=model.device)
@@ -527,7 +710,7 @@ def replay_tracks(model, config, tracks, resolutions=None, mask_stride=None, fli
             if flags is None:
                 p, f = s.push(kp, None if act.all() else act)
             else:
-                p, f = s.push(kp, None if act.all() else act, valid=np.array([bool(act[i]) and bool(flags[i][k]) for i in range(T)]))
+                p, f = s.push(kp, None if act.all() else act, valid=np.array([flags[i][k] & True if act[i] else flags[i][0] & False for i in range(T)]))
             if out_fps is None:
                 poses[k].copy_(p)
                 fresh[k].copy_(f)
@@ -566,9 +749,19 @@ def parse_args(argv=None):
     p.add_argument("--out_fps", type=_rate_argument, default=None, metavar="G",
                    help="rate of the poses written, a float or NUM/DEN (needs --fps): NAME then holds every pose the session emitted, in order "
                         "(n_out, J, 3), and NAME_count the number each tick returned")
+    p.add_argument("--repair_joints", type=int, default=None, metavar="G",
+                   help="fill a joint that is missing for up to G <= 32 consecutive frames from the nearest frames where it was seen, as "
+                        "predict --repair_joints on the track so far; implies --mask_missing; not with --fps")
+    p.add_argument("--min_score", type=float, default=None, metavar="S",
+                   help="with --repair_joints the arrays may be (T, J, 3) with the detector's score in the third channel: a joint counts as "
+                        "seen when score >= S")
     args = p.parse_args(argv)
     if args.out_fps is not None and args.fps is None:
         p.error("--out_fps needs --fps")
+    if args.min_score is not None and args.repair_joints is None:
+        p.error("--min_score needs --repair_joints: scores say which joints were seen")
+    if args.repair_joints is not None and args.fps is not None:
+        p.error("--repair_joints with --fps is not supported yet")
     return args
 
 
@@ -581,9 +774,17 @@ def main(argv=None):
         tracks = [np.asarray(z[k], np.float32) for k in names]
     if not names:
         raise SystemExit(f"{args.input} holds no arrays")
+    tracks, joint_flags = split_scores(names, tracks, config.NUM_KEYPOINTS, args.min_score, args.input)
     for k, t in zip(names, tracks):
-        if t.ndim != 3 or t.shape[2] != 2 or t.shape[1] != config.NUM_KEYPOINTS or t.shape[0] < 1:
+        if t.shape[0] < 1:
             raise SystemExit(f"{args.input}[{k}] has shape {t.shape}, expected (T >= 1, {config.NUM_KEYPOINTS}, 2)")
+    missing = {"valid": "finite"} if args.mask_missing or args.repair_joints is not None else {}
+    if joint_flags is not None:
+        missing = {"valid": joint_flags}
+    if args.repair_joints is not None:
+        if not 1 <= args.repair_joints <= MAX_LIVE_REPAIR:
+            raise SystemExit(f"--repair_joints must be in [1, {MAX_LIVE_REPAIR}]")
+        missing["repair_joints"] = args.repair_joints
     if args.fps is None and not 0 <= args.lookahead <= max_lookahead(config):
         raise SystemExit(f"--lookahead must be in [0, {max_lookahead(config)}]")
     if args.fps is not None:
@@ -593,7 +794,7 @@ def main(argv=None):
             raise SystemExit(f"--fps / --out_fps / --lookahead: {e}") from None
     model = _load_model(config, args.weights)
     poses, fresh = replay_tracks(model, config, tracks, resolutions=None if args.resolution is None else tuple(args.resolution),
-                                 lookahead=args.lookahead, **({"valid": "finite"} if args.mask_missing else {}),
+                                 lookahead=args.lookahead, **missing,
                                  **({} if args.fps is None else {"fps": args.fps}), **({} if args.out_fps is None else {"out_fps": args.out_fps}))
     out = {}
     for k, p, f in zip(names, poses, fresh):
