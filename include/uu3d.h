@@ -482,6 +482,42 @@ int uu3d_repair_joints(const float* src_dev, int64_t rows, int32_t num_keypoints
                        uint8_t* joint_state_dev, void* scratch_dev, size_t scratch_bytes, void* stream);
 
 /*
+ * ANY SKELETON (predict.predict_tracks(keypoints=M), stream.StreamSession(keypoints=M)): no detector emits the model's own joint layout
+ * (the shipped configs: Human3.6M's 17 joints).  uu3d_map_keypoints turns the joints a detector does emit -- `inputs` of them, K_in -- into
+ * the J = num_keypoints joints of the handle, on the device, in front of EVERYTHING else that looks at a track: uu3d_repair_joints,
+ * uu3d_normalize_tracks(_valid), uu3d_resample_tracks, the stage of a live tick.  It runs on the raw coordinates as given, pixels or
+ * normalised: the map is affine (every joint's weights sum to 1), so it commutes, mathematically, with the screen normalisation.
+ * THE RULE.  Per model joint j an ordered list of 1 <= n_j <= 8 distinct sources src[j][k] with float64 weights w[j][k], finite, non-zero,
+ * summing to 1 within 1e-12 (negative weights allowed).  For every frame and model joint, per coordinate,
+ *     out[j] = (float)(w[j][0] * (double)in[src[j][0]] + w[j][1] * (double)in[src[j][1]] + ...)
+ * in float64, summed left to right in the listed order, every product and sum rounded, no fused multiply-add, rounded once to float32 -- the
+ * discipline of uu3d_resample_tracks' expression, so a numpy restatement (predict.map_keypoints_host) gives the same bits.  A NaN result is
+ * stored as the quiet NaN 0x7fc00000 (which NaN an invalid sum makes is not the same on every processor).  A joint with one source of
+ * weight 1.0 has that source's bits; only listed sources are read, so an unlisted NaN never reaches a joint.
+ * FLAGS.  flags_in_dev (frames, inputs) u8 and flags_out_dev (frames, J) u8, both or neither (UU3D_ERR_INVALID_ARGUMENT).  Neither: the
+ * expression alone; a NaN source gives a NaN joint.  Both: a source is OBSERVED when its byte is non-zero and both of its coordinates are
+ * finite; a model joint is observed iff every one of its sources is; flags_out holds that (1 / 0) and an unobserved joint's coordinates
+ * are written as zeros -- what uu3d_repair_joints and uu3d_stream_repair_stage take as joint_flags_dev.
+ *
+ *   uu3d_keypoint_map_bytes(inputs, joints): the size of the device-resident table, 0 for arguments out of range.  Fixed stride 8, three
+ *       planes back to back: w (joints, 8) f64 at 0, src (joints, 8) i32 at 64 joints (-1 for an unused entry), n (joints) i32 at 96 joints.
+ *   uu3d_keypoint_map_pack(inputs, joints, counts (joints) i32, sources (joints, 8) i32, weights (joints, 8) f64, out_host, out_bytes): HOST
+ *       memory in, HOST memory out (8-byte aligned): checks the rule's terms and that every listed source lies in [0, inputs)
+ *       (UU3D_ERR_INVALID_ARGUMENT otherwise; entries k >= counts[j] are ignored) and writes the table.  The caller packs once, uploads
+ *       once and keeps the block; no call does host work per frame.  The kernel does NOT re-check the table.
+ *   uu3d_map_keypoints(model, map_dev, inputs, src_dev (frames, inputs, 2) f32, flags_in_dev or NULL, frames, out_dev (frames, J, 2) f32,
+ *       flags_out_dev or NULL, stream): one launch, one lane per (frame, model joint), one 8-byte store of the coordinate pair; every
+ *       element has one writer, no atomics: bitwise repeatable.  map_dev, src_dev and out_dev 8-byte aligned; src_dev is only read and is
+ *       never out_dev.  frames == 0 is a no-op that returns UU3D_OK.  inputs < 1: UU3D_ERR_INVALID_ARGUMENT.  The arguments are the same
+ *       at every tick of a live session, so the launch is the first step of its captured graph.
+ */
+size_t uu3d_keypoint_map_bytes(int32_t inputs, int32_t joints);
+int uu3d_keypoint_map_pack(int32_t inputs, int32_t joints, const int32_t* counts, const int32_t* sources, const double* weights,
+                           void* out_host, size_t out_bytes);
+int uu3d_map_keypoints(uu3d_model* model, const void* map_dev, int32_t inputs, const float* src_dev, const uint8_t* flags_in_dev,
+                       int64_t frames, float* out_dev, uint8_t* flags_out_dev, void* stream);
+
+/*
  * ANY FRAME RATE (predict.predict_tracks(fps=...)): the front of YOUR OWN 2D TRACKS for tracks that were not filmed at the rate the model
  * was trained for.  The table holds the MODEL's time grid: row `row` (track row_track_dev[row]) is model frame k of its track, which sits at
  * source position p_k = k * fps / model_fps.  The host works the positions out in exact integer arithmetic (predict.resample_plan) and

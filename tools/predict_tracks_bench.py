@@ -10,8 +10,11 @@ tracks' own frames.
 --repair_joints G [--missing_joints P]: also predict_tracks(valid=joint flags, repair_joints=G) with every joint dropped independently with
 probability P (NaN coordinates, flag 0), against the same call with predict.repair_joints_host -- the rule in numpy, written to be read, not
 to be fast -- run on the host in front of it; the two must agree bit for bit.
+--keypoints NAME [--missing_joints P]: also the same number of tracks in the layout of the preset NAME ("coco17", "body25"), every detector
+joint dropped with probability P (flag 0): predict_tracks(keypoints=NAME, valid=joint flags, repair_joints=G or 5) against the same tracks
+mapped by predict.map_keypoints_host in front of the plain call; the two must agree bit for bit.
    python tools/predict_tracks_bench.py [--tracks 40] [--frames 2500] [--batch 512] [--reps 3] [--cases h36m_351:5,h36m_81:4] [--missing 0.3]
-                                        [--fps 30] [--repair_joints 5 --missing_joints 0.1]"""
+                                        [--fps 30] [--repair_joints 5 --missing_joints 0.1] [--keypoints coco17]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -28,6 +31,7 @@ def main():
     ap.add_argument("--fps", default=None, help="also time predict_tracks(fps=F) against numpy resampling on the host; a float or NUM/DEN")
     ap.add_argument("--repair_joints", type=int, default=None, metavar="G", help="also time predict_tracks(valid=joint flags, repair_joints=G)")
     ap.add_argument("--missing_joints", type=float, default=0.1, metavar="P", help="with --repair_joints: every joint is dropped with probability P")
+    ap.add_argument("--keypoints", default=None, metavar="NAME", help="also time predict_tracks(keypoints=NAME) against predict.map_keypoints_host in front")
     args = ap.parse_args()
     import numpy as np, torch
     import uplift_upsample_3dhpe_amd as pkg
@@ -46,6 +50,12 @@ def main():
     if args.repair_joints is not None:
         jflags = [rng.random((args.frames, 17)) >= args.missing_joints for _ in range(args.tracks)]
         broken = [np.where(f[:, :, None], t, np.float32(np.nan)).astype(np.float32) for t, f in zip(px, jflags)]
+    kpx = kflags = None
+    if args.keypoints is not None:
+        K = predict.keypoint_map(args.keypoints).inputs
+        kpx = [(np.cumsum(rng.normal(0, 2.0, size=(args.frames, K, 2)), 0) + rng.uniform(0.25, 0.75, size=(1, K, 2)) * [W, H]).astype(np.float32)
+               for _ in range(args.tracks)]
+        kflags = [rng.random((args.frames, K)) >= args.missing_joints for _ in range(args.tracks)]
     reuse = not args.no_reuse
     fps = None if args.fps is None else predict.frame_rate(args.fps)
     results = []
@@ -107,6 +117,15 @@ def main():
             return predict.predict_tracks(model, cfg, repaired, resolutions=(W, H), mask_stride=int(msv), flip=True, reuse_frames=reuse, batch_size=args.batch,
                                           valid=frame_flags)
 
+        def keypoints_path():
+            return predict.predict_tracks(model, cfg, kpx, resolutions=(W, H), mask_stride=int(msv), flip=True, reuse_frames=reuse, batch_size=args.batch,
+                                          valid=kflags, repair_joints=args.repair_joints or 5, keypoints=args.keypoints)
+
+        def keypoints_host():
+            mapped, mapped_flags = predict.map_keypoints_host(args.keypoints, kpx, kflags)
+            return predict.predict_tracks(model, cfg, mapped, resolutions=(W, H), mask_stride=int(msv), flip=True, reuse_frames=reuse, batch_size=args.batch,
+                                          valid=mapped_flags, repair_joints=args.repair_joints or 5)
+
         row = dict(config=name, mask_stride=int(msv), tracks=args.tracks, frames=total, batch=args.batch, reuse_frames=reuse)
         outs = {}
         cases = [("predict_tracks", new_path), ("predict_tracks_to_host", lambda: new_path(True)), ("composition", composition)]
@@ -119,6 +138,9 @@ def main():
         if jflags is not None:
             row["repair_joints"], row["missing_joints"] = args.repair_joints, args.missing_joints
             cases += [("predict_tracks_repair", repair_path), ("host_repair", repair_host)]
+        if kpx is not None:
+            row["keypoints"], row["missing_joints"] = args.keypoints, args.missing_joints
+            cases += [("predict_tracks_keypoints", keypoints_path), ("host_keypoints", keypoints_host)]
         for key, fn in cases:
             fn()
             torch.cuda.synchronize()
@@ -140,6 +162,10 @@ def main():
             row["repair_speedup"] = round(row["host_repair_ms"] / row["predict_tracks_repair_ms"], 3)
             row["repair_bits_equal"] = bool(all(torch.equal(a.view(torch.int32), b.view(torch.int32))
                                                 for a, b in zip(outs["predict_tracks_repair"], outs["host_repair"])))
+        if kpx is not None:
+            row["keypoints_speedup"] = round(row["host_keypoints_ms"] / row["predict_tracks_keypoints_ms"], 3)
+            row["keypoints_bits_equal"] = bool(all(torch.equal(a.view(torch.int32), b.view(torch.int32))
+                                                   for a, b in zip(outs["predict_tracks_keypoints"], outs["host_keypoints"])))
         row["device"] = torch.cuda.get_device_name(0)
         print(json.dumps(row), flush=True)
         results.append(row)

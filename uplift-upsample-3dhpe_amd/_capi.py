@@ -41,6 +41,7 @@ EXPORTED_SYMBOLS = (
     "uu3d_stream_timed_emit", "uu3d_stream_rate_reset",
     "uu3d_stream_out_state_layout", "uu3d_stream_timed_emit_multi", "uu3d_stream_out_reset",
     "uu3d_stream_repair_bytes", "uu3d_stream_repair_layout", "uu3d_stream_repair_stage", "uu3d_stream_commit_repair", "uu3d_stream_repair_reset",
+    "uu3d_keypoint_map_bytes", "uu3d_keypoint_map_pack", "uu3d_map_keypoints",
 )
 # include/uu3d_ops.h
 OPS_SYMBOLS = (
@@ -252,6 +253,13 @@ def load_library(path=None):
     lib.uu3d_repair_joints_scratch_bytes.argtypes = [i64, i32]
     lib.uu3d_repair_joints.restype = C.c_int
     lib.uu3d_repair_joints.argtypes = [vp, i64, i32, vp, vp, i32, i32, vp, vp, vp, vp, sz, vp]
+    # any skeleton: the detector's joints -> the model's, in front of everything above
+    lib.uu3d_keypoint_map_bytes.restype = sz
+    lib.uu3d_keypoint_map_bytes.argtypes = [i32, i32]
+    lib.uu3d_keypoint_map_pack.restype = C.c_int
+    lib.uu3d_keypoint_map_pack.argtypes = [i32, i32, vp, vp, vp, vp, sz]
+    lib.uu3d_map_keypoints.restype = C.c_int
+    lib.uu3d_map_keypoints.argtypes = [vp, vp, i32, vp, vp, i64, vp, vp, vp]
     lib.uu3d_world_to_cam_2d.restype = C.c_int
     lib.uu3d_world_to_cam_2d.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
     lib.uu3d_set_schedule.restype = C.c_int

@@ -35,6 +35,7 @@
 #include "uu3d_metrics.h"
 #include "uu3d_tracks.h"
 #include "uu3d_repair.h"
+#include "uu3d_keypoints.h"
 #include "uu3d_stream.h"
 #include "uu3d_stream_rate.h"
 #include "uu3d_stream_repair.h"
@@ -584,6 +585,39 @@ int uu3d_repair_joints(const float* src, int64_t rows, int32_t J, const uint8_t*
     hipLaunchKernelGGL(repair_flag_kernel, dim3((unsigned)(((long)rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
                        (const uint8_t*)joint_state, (long)rows, J, frame_valid);
     return hipGetLastError() == hipSuccess ? UU3D_OK : UU3D_ERR_HIP;
+}
+
+// ---- ANY SKELETON (uu3d_keypoints.h): the table's size, its host-side packing, the one launch ----
+size_t uu3d_keypoint_map_bytes(int32_t inputs, int32_t joints) {
+    if (inputs < 1 || joints < 1 || joints > (1 << 20)) return 0;
+    return keypoint_table_bytes(joints);
+}
+
+int uu3d_keypoint_map_pack(int32_t inputs, int32_t joints, const int32_t* counts, const int32_t* sources, const double* weights, void* out_host,
+                           size_t out_bytes) {
+    if (!counts || !sources || !weights || !out_host || ((uintptr_t)out_host & 7) != 0) return UU3D_ERR_INVALID_ARGUMENT;
+    const size_t need = uu3d_keypoint_map_bytes(inputs, joints);
+    if (need == 0 || out_bytes < need) return UU3D_ERR_INVALID_ARGUMENT;
+    return keypoint_map_pack(inputs, joints, counts, sources, weights, out_host) == nullptr ? UU3D_OK : UU3D_ERR_INVALID_ARGUMENT;
+}
+
+int uu3d_map_keypoints(uu3d_model* m, const void* map, int32_t inputs, const float* src, const uint8_t* flags_in, int64_t frames, float* out,
+                       uint8_t* flags_out, void* stream) {
+    if (!m) return UU3D_ERR_INVALID_ARGUMENT;
+    const int J = m->cfg.num_keypoints;
+    if (inputs < 1) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_map_keypoints: inputs must be >= 1");
+    if ((flags_in == nullptr) != (flags_out == nullptr))
+        return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_map_keypoints: flags_in_dev and flags_out_dev go together");
+    if (frames < 0 || frames > (INT64_MAX >> 4) / J || frames > (INT64_MAX >> 4) / inputs || (frames * J + 255) / 256 > INT32_MAX)
+        return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_map_keypoints: frames out of range");
+    if (frames == 0) return UU3D_OK;
+    if (!map || !src || !out || (const void*)src == (const void*)out)
+        return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_map_keypoints: null buffer, or out_dev is src_dev");
+    if (((uintptr_t)map & 7) != 0 || ((uintptr_t)src & 7) != 0 || ((uintptr_t)out & 7) != 0)
+        return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_map_keypoints: map_dev, src_dev and out_dev must be 8-byte aligned");
+    hipLaunchKernelGGL(map_keypoints_kernel, dim3((unsigned)((frames * J + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       keypoint_table(map, J), inputs, J, src, flags_in, (long)frames, out, flags_out);
+    return hipGetLastError() == hipSuccess ? UU3D_OK : fail(m, UU3D_ERR_HIP, "uu3d_map_keypoints: launch failed");
 }
 
 int uu3d_assemble_tracks(const float* plain, const float* flipped, int64_t num_windows, const int32_t* flip_order, const int32_t* left,

@@ -24,10 +24,15 @@ synchronises the stream once after the last forward (its pipeline's buffers go a
 
     python -m uplift_upsample_3dhpe_amd.predict --config C --weights W.h5 --input tracks.npz --output out.npz \\
         [--resolution W H] [--mask_stride S] [--keyframes_only] [--mask_missing] [--fps F] [--out_fps F] [--repair_joints G] [--min_score S]
+        [--keypoints NAME]
 
 Per-joint missed detections: ``predict_tracks(..., valid=..., repair_joints=G)`` fills a joint the detector lost for up to G frames by
 linear interpolation between the nearest frames where it was seen (uu3d_repair_joints, in front of the two front kernels above; the rule
 in numpy: ``repair_joints_host``) instead of giving up the whole frame.
+
+Any skeleton: ``predict_tracks(..., keypoints="coco17")`` takes tracks in the DETECTOR's joint layout, (T_i, K_in, 2), and maps them onto the
+model's joints on the device before anything else looks at them (uu3d_map_keypoints; ``KeypointMap``, ``KEYPOINT_PRESETS``; the rule in
+numpy: ``map_keypoints_host``); per-joint flags and scores are then per detector joint.
 """
 import argparse
 import ctypes as C
@@ -285,6 +290,231 @@ def repair_joints(src, lens, G, joint_flags=None):
     return out, frame_flags, state
 
 
+MAX_KEYPOINT_SOURCES = 8                                              # sources per model joint: the fixed stride of the device table
+
+
+class KeypointMap(object):
+    """An affine map from a detector's joints onto the model's (include/uu3d.h, ANY SKELETON): ``inputs`` = K_in joints come in; model joint
+    j is ``sum_k weights[j][k] * in[sources[j][k]]``, summed in the listed order.  ``sources``: per model joint 1 to 8 distinct indices in
+    [0, inputs); ``weights``: as many float64 weights each, finite, non-zero, summing to 1 within 1e-12 (negative ones allowed: the map is
+    affine, so it commutes, mathematically, with the screen normalisation).  Anything else is a ValueError.  ``joints`` = J = len(sources).
+    Immutable; the packed table is made once and uploaded once per device (``device_table``)."""
+
+    def __init__(self, inputs, sources, weights):
+        if isinstance(inputs, bool) or not isinstance(inputs, (int, np.integer)) or int(inputs) < 1:
+            raise ValueError(f"inputs must be an int >= 1: the joints the detector emits, got {inputs!r}")
+        sources, weights = list(sources), list(weights)
+        if len(sources) < 1 or len(sources) != len(weights):
+            raise ValueError(f"sources and weights need one entry per model joint, got {len(sources)} and {len(weights)}")
+        self.inputs, self.joints = int(inputs), len(sources)
+        src, wts = [], []
+        for j, (s, w) in enumerate(zip(sources, weights)):
+            s, w = [int(i) for i in np.asarray(s).reshape(-1)], [float(x) for x in np.asarray(w, np.float64).reshape(-1)]
+            if not 1 <= len(s) <= MAX_KEYPOINT_SOURCES or len(s) != len(w):
+                raise ValueError(f"model joint {j} needs 1 to {MAX_KEYPOINT_SOURCES} sources and as many weights, got {len(s)} and {len(w)}")
+            if len(set(s)) != len(s) or min(s) < 0 or max(s) >= self.inputs:
+                raise ValueError(f"model joint {j}: sources must be distinct indices in [0, {self.inputs}), got {s}")
+            if not all(np.isfinite(x) and x != 0.0 for x in w):
+                raise ValueError(f"model joint {j}: weights must be finite and non-zero, got {w}")
+            total = 0.0
+            for x in w:
+                total = total + x
+            if not abs(total - 1.0) <= 1e-12:
+                raise ValueError(f"model joint {j}: weights must sum to 1 (an affine map), they sum to {total!r}")
+            src.append(tuple(s))
+            wts.append(tuple(w))
+        self.sources, self.weights = tuple(src), tuple(wts)
+        self._packed, self._tables = None, {}
+
+    def planes(self):
+        """-> (counts (J,) int32, sources (J, 8) int32 with -1 behind a joint's last source, weights (J, 8) float64 with 0 there)."""
+        counts = np.array([len(s) for s in self.sources], np.int32)
+        src = np.full((self.joints, MAX_KEYPOINT_SOURCES), -1, np.int32)
+        w = np.zeros((self.joints, MAX_KEYPOINT_SOURCES), np.float64)
+        for j, (s, x) in enumerate(zip(self.sources, self.weights)):
+            src[j, :len(s)], w[j, :len(s)] = s, x
+        return counts, src, w
+
+    def packed(self):
+        """The table of uu3d_keypoint_map_pack as a host uint8 array (the library checks the map once more, the index range included)."""
+        if self._packed is None:
+            lib = _capi.load_library()
+            nbytes = int(lib.uu3d_keypoint_map_bytes(self.inputs, self.joints))
+            if nbytes == 0:
+                raise ValueError(f"a map from {self.inputs} onto {self.joints} joints is out of uu3d_keypoint_map_pack's range")
+            counts, src, w = self.planes()
+            out = np.zeros(nbytes // 8, np.float64)                   # (8-byte aligned)
+            _capi.check(lib, lib.uu3d_keypoint_map_pack(self.inputs, self.joints, counts.ctypes.data, src.ctypes.data, w.ctypes.data,
+                                                        out.ctypes.data, nbytes), None)
+            self._packed = out.view(np.uint8)
+        return self._packed
+
+    def device_table(self, device):
+        """The packed table on ``device``: uploaded at the first call, which waits for the copy once -- whatever stream uses it later finds
+        it there --, and kept for the life of the map: no call does host work per frame."""
+        import torch
+        key = str(torch.device(device))
+        if key not in self._tables:
+            self._tables[key] = _upload(self.packed(), np.uint8, device)
+            torch.cuda.current_stream(device).synchronize()
+        return self._tables[key]
+
+    def __repr__(self):
+        return f"KeypointMap(inputs={self.inputs}, joints={self.joints})"
+
+
+def _h36m17_from(inputs, r_leg, l_leg, r_arm, l_arm, pelvis, neck, torso, head, head_top):
+    """A ``KeypointMap`` onto ``H36MOrder17P``: 0-2 right ankle, knee, hip; 3-5 left hip, knee, ankle; 6 pelvis; 7 neck; 8 torso; 9 head;
+    10 head top; 11-13 right wrist, elbow, shoulder; 14-16 left shoulder, elbow, wrist.  Limbs are (ankle, knee, hip) / (wrist, elbow,
+    shoulder) source indices; the other five are (sources, weights)."""
+    one = lambda i: ((i,), (1.0,))
+    rows = [one(r_leg[0]), one(r_leg[1]), one(r_leg[2]), one(l_leg[2]), one(l_leg[1]), one(l_leg[0]), pelvis, neck, torso, head, head_top,
+            one(r_arm[0]), one(r_arm[1]), one(r_arm[2]), one(l_arm[2]), one(l_arm[1]), one(l_arm[0])]
+    return KeypointMap(inputs, [r[0] for r in rows], [r[1] for r in rows])
+
+
+# Named maps onto H36MOrder17P (J = 17), the layout of the shipped configs.  They are GEOMETRIC APPROXIMATIONS of joints the detector does
+# not emit (a pelvis between the hips, a head top beyond the eyes): the shipped weights were trained on Human3.6M 2D detections and no
+# accuracy figure is claimed for these tables -- the mechanism is the feature, the tables are a convenience.
+# Left-right consistency: mirroring the input (x negated, joints permuted by the detector's own left-right order) and then mapping gives the
+# bits of mapping and then mirroring by AUGM_FLIP_KEYPOINT_ORDER.  The sources are ORDERED for that: a mirrored pair comes first, left then
+# right (its sum, the first one of the expression, is the same either way round: a + b == b + a), unpaired sources behind it -- the nose
+# last in head_top.  The torso of "coco17" sums two pairs; mirrored, the hips arrive in the other order behind the shoulders' sum, which
+# gives the same bits wherever the float64 partial sums are exact -- four float32 coordinates within a factor of 2^26 of each other, or
+# zero -- and elsewhere the same value up to one float64 rounding, which reaches the float32 result about once in 2^29 times.
+KEYPOINT_PRESETS = {
+    # COCO-17: 0 nose, 1 l_eye, 2 r_eye, 3 l_ear, 4 r_ear, 5 l_sho, 6 r_sho, 7 l_elb, 8 r_elb, 9 l_wri, 10 r_wri, 11 l_hip, 12 r_hip,
+    # 13 l_knee, 14 r_knee, 15 l_ank, 16 r_ank
+    "coco17": _h36m17_from(17, r_leg=(16, 14, 12), l_leg=(15, 13, 11), r_arm=(10, 8, 6), l_arm=(9, 7, 5),
+                           pelvis=((11, 12), (0.5, 0.5)), neck=((5, 6), (0.5, 0.5)), torso=((5, 6, 11, 12), (0.25, 0.25, 0.25, 0.25)),
+                           head=((0,), (1.0,)), head_top=((1, 2, 0), (1.0, 1.0, -1.0))),
+    # OpenPose BODY_25: 0 Nose, 1 Neck, 2 RShoulder, 3 RElbow, 4 RWrist, 5 LShoulder, 6 LElbow, 7 LWrist, 8 MidHip, 9 RHip, 10 RKnee,
+    # 11 RAnkle, 12 LHip, 13 LKnee, 14 LAnkle, 15 REye, 16 LEye, 17 REar, 18 LEar, 19 LBigToe, 20 LSmallToe, 21 LHeel, 22 RBigToe,
+    # 23 RSmallToe, 24 RHeel
+    "body25": _h36m17_from(25, r_leg=(11, 10, 9), l_leg=(14, 13, 12), r_arm=(4, 3, 2), l_arm=(7, 6, 5),
+                           pelvis=((8,), (1.0,)), neck=((1,), (1.0,)), torso=((1, 8), (0.5, 0.5)),
+                           head=((0,), (1.0,)), head_top=((16, 15, 0), (1.0, 1.0, -1.0))),
+}
+
+
+def keypoint_map(name_or_map, J=None):
+    """``predict_tracks``' ``keypoints`` argument -> a ``KeypointMap``: a name of ``KEYPOINT_PRESETS`` or a map of your own.  ``J``: the
+    model's joint count; a map onto another number of joints is a ValueError (the presets target 17)."""
+    if isinstance(name_or_map, KeypointMap):
+        M, what = name_or_map, repr(name_or_map)
+    elif isinstance(name_or_map, str):
+        if name_or_map not in KEYPOINT_PRESETS:
+            raise ValueError(f"keypoints must be a KeypointMap or one of {sorted(KEYPOINT_PRESETS)}, got {name_or_map!r}")
+        M, what = KEYPOINT_PRESETS[name_or_map], repr(name_or_map)
+    else:
+        raise ValueError(f"keypoints must be a KeypointMap or one of {sorted(KEYPOINT_PRESETS)}, got {name_or_map!r}")
+    if J is not None and M.joints != int(J):
+        raise ValueError(f"keypoints={what} maps onto {M.joints} joints, the model has {int(J)}")
+    return M
+
+
+def check_keypoint_inputs(M, counts, what="track"):
+    """Every track (slot, array) has the K_in joints ``M`` takes: ValueError naming both numbers otherwise."""
+    for i, k in enumerate(counts):
+        if int(k) != M.inputs:
+            raise ValueError(f"{what} {i} has {int(k)} keypoints, keypoints={M!r} takes {M.inputs}")
+
+
+def _host_array(a):
+    return a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+
+
+def map_keypoints_host(M, tracks, valid=None):
+    """The rule of ``predict_tracks(keypoints=M)`` (include/uu3d.h, ANY SKELETON) in numpy, written to be read: what uu3d_map_keypoints
+    computes, bit for bit.  ``tracks``: list of (T_i, K_in, 2) arrays; ``valid``: None, "finite" or a list with one (T_i,) or (T_i, K_in)
+    entry per track -> (mapped, flags): per track (T_i, J, 2) float32, and ``flags`` as the call behind the map takes them --
+        None            -> None: the expression alone, a NaN source gives a NaN joint;
+        (T_i, K_in)     -> (T_i, J) bool: a source is observed when its flag is non-zero and both coordinates are finite, a model joint iff
+                           every one of its sources is; an unobserved joint's coordinates are zeros ("finite": every flag set);
+        (T_i,)          -> the entry itself, unchanged: frame flags pass through, the coordinates are the expression.
+    So ``predict_tracks(model, cfg, tracks, keypoints=M, valid=V, **kw)`` equals ``predict_tracks(model, cfg, mapped, valid=flags, **kw)``."""
+    M = keypoint_map(M)
+    tracks = [np.asarray(_host_array(t), np.float32) for t in tracks]
+    check_keypoint_inputs(M, [t.shape[1] for t in tracks])
+    if valid is not None and not isinstance(valid, str):
+        check_valid(valid, [len(t) for t in tracks], joints=M.inputs)
+    elif valid is not None and valid != "finite":
+        raise ValueError('valid must be None, "finite" or a list with one entry per track')
+    mapped, flags = [], None if valid is None else []
+    for i, src in enumerate(tracks):
+        T = len(src)
+        v = None if valid is None else np.ones((T, M.inputs), bool) if isinstance(valid, str) else _host_array(valid[i]) != 0
+        per_joint = v is not None and v.ndim == 2
+        if per_joint:
+            observed = v & np.isfinite(src).all(axis=2)
+        out = np.zeros((T, M.joints, 2), np.float32)
+        joint_flags = np.zeros((T, M.joints), bool)
+        for j, (sources, weights) in enumerate(zip(M.sources, M.weights)):
+            with np.errstate(invalid="ignore", over="ignore"):
+                acc = np.float64(weights[0]) * src[:, sources[0]].astype(np.float64)
+                for s, w in zip(sources[1:], weights[1:]):
+                    acc = acc + np.float64(w) * src[:, s].astype(np.float64)
+                r = acc.astype(np.float32)
+            r[np.isnan(r)] = np.float32(np.nan)                       # THE quiet NaN 0x7fc00000, as the device stores it
+            if per_joint:
+                joint_flags[:, j] = observed[:, list(sources)].all(axis=1)
+                r[~joint_flags[:, j]] = 0.0
+            out[:, j] = r
+        mapped.append(out)
+        if flags is not None:
+            flags.append(joint_flags if per_joint else valid[i])
+    return mapped, flags
+
+
+def map_keypoints(src, flags, M, model):
+    """uu3d_map_keypoints on the current stream.  ``src`` (F, K_in, 2) float32 on the device, contiguous (only read); ``flags`` (F, K_in)
+    uint8 on the device or None; ``M``: a ``KeypointMap`` onto the joints of ``model`` (its handle says J) -> (mapped (F, J, 2) float32,
+    joint flags (F, J) uint8 or None), fresh device buffers."""
+    import torch
+    lib = _capi.load_library()
+    dev = src.device
+    F, J = int(src.shape[0]), M.joints
+    if src.dtype != torch.float32 or not src.is_contiguous() or tuple(src.shape) != (F, M.inputs, 2):
+        raise ValueError(f"src must be a contiguous (F, {M.inputs}, 2) float32 device tensor, got {tuple(src.shape)}")
+    if flags is not None and (flags.dtype != torch.uint8 or not flags.is_contiguous() or tuple(flags.shape) != (F, M.inputs)):
+        raise ValueError(f"flags must be a contiguous ({F}, {M.inputs}) uint8 device tensor")
+    if int(model.arch.num_keypoints) != J:
+        raise ValueError(f"keypoints={M!r} maps onto {J} joints, the model has {int(model.arch.num_keypoints)}")
+    table = M.device_table(dev)
+    out = torch.empty((F, J, 2), dtype=torch.float32, device=dev)
+    flags_out = None if flags is None else torch.empty((F, J), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _capi.check(lib, lib.uu3d_map_keypoints(model._h, _ptr(table), M.inputs, _ptr(src), _ptr(flags), F, _ptr(out), _ptr(flags_out),
+                                                C.c_void_p(stream)), model._h)
+    return out, flags_out
+
+
+def _map_front(M, model, src, given, valid):
+    """The map in front of everything else: the given frames of all tracks (R, K_in, 2) and ``valid`` per detector joint -> (the frames
+    (R, J, 2), ``valid`` per model joint, as ``_front_validity`` takes it).  One launch; a list that mixes (T_i, K_in) and (T_i,) entries
+    takes one launch with and one without flags, and every track the rows of its own kind."""
+    import torch
+    if model is None:
+        raise ValueError("keypoints needs the model: its handle says which joints the map must give")
+    K, dev, sizes = M.inputs, src.device, [int(n) for n in given]
+    if valid is None:
+        return map_keypoints(src, None, M, model)[0], None
+    if isinstance(valid, str):                                        # "finite": the finite test per SOURCE joint, every flag set
+        out, flags = map_keypoints(src, torch.ones((int(src.shape[0]), K), dtype=torch.uint8, device=dev), M, model)
+        return out, list(torch.split(flags, sizes, 0))
+    per_joint = [len(_shape(v)) == 2 for v in valid]
+    if not any(per_joint):                                            # frame flags pass through unchanged
+        return map_keypoints(src, None, M, model)[0], valid
+    out, flags = map_keypoints(src, _device_joint_flags(valid, K, dev), M, model)
+    flags = list(torch.split(flags, sizes, 0))
+    if all(per_joint):
+        return out, flags
+    plain = torch.split(map_keypoints(src, None, M, model)[0], sizes, 0)
+    out = torch.cat([a if p else b for p, a, b in zip(per_joint, torch.split(out, sizes, 0), plain)], 0)
+    return out, [f if p else v for p, f, v in zip(per_joint, flags, valid)]
+
+
 def _front_validity(src, given, J, valid, repair):
     """What the front kernels take as source and ``valid_in``: as they are, or with ``repair`` = G the repaired source and the frame
     flags of uu3d_repair_joints -> (src, valid_in, joint state or None)."""
@@ -316,13 +546,18 @@ def check_resolutions(resolutions, count, per="track"):
     return np.ascontiguousarray(r)
 
 
-def pose_table(tracks, device, resolutions=None, key_stride=0, lengths=None, valid=None, repair_joints=None):
+def pose_table(tracks, device, resolutions=None, key_stride=0, lengths=None, valid=None, repair_joints=None, keypoints=None, model=None):
     """The dense, normalised ``data.PoseTable`` of the tracks (uu3d_normalize_tracks) -> (table, frames per track).  ``valid`` as in
     ``predict_tracks`` (not None: uu3d_normalize_tracks_valid into a fresh buffer; the table carries the per-frame flags).
-    ``repair_joints`` = G: uu3d_repair_joints runs on the given frames first; ``table.joint_state`` is its (given frames, J) uint8 state."""
+    ``repair_joints`` = G: uu3d_repair_joints runs on the given frames first; ``table.joint_state`` is its (given frames, J) uint8 state.
+    ``keypoints``: a ``KeypointMap`` or a preset's name (with ``model``): the tracks are (T_i, K_in, 2), per-joint entries of ``valid``
+    (T_i, K_in), and uu3d_map_keypoints runs in front of all of that (``_map_front``)."""
     import torch
     check_repair_joints(repair_joints, valid)
     tr, J, given = _device_tracks(tracks, device)
+    if keypoints is not None:
+        keypoints = keypoint_map(keypoints)
+        check_keypoint_inputs(keypoints, [J])
     check_valid(valid, given, joints=J)
     if key_stride > 0:
         if lengths is None or len(lengths) != len(tr):
@@ -338,6 +573,8 @@ def pose_table(tracks, device, resolutions=None, key_stride=0, lengths=None, val
         raise ValueError("every track needs at least one frame")
     resolutions = check_resolutions(resolutions, len(tr))
     src = torch.cat(tr, 0).contiguous() if len(tr) > 1 else tr[0].contiguous()
+    if keypoints is not None:
+        (src, valid), J = _map_front(keypoints, model, src, given, valid), keypoints.joints
     flags = state = None
     if valid is not None:
         src, valid_in, state = _front_validity(src, given, J, valid, repair_joints)
@@ -354,20 +591,25 @@ def pose_table(tracks, device, resolutions=None, key_stride=0, lengths=None, val
     return table, lens
 
 
-def resampled_pose_table(tracks, device, fps, resolutions=None, valid=None, model_fps=50, repair_joints=None):
+def resampled_pose_table(tracks, device, fps, resolutions=None, valid=None, model_fps=50, repair_joints=None, keypoints=None, model=None):
     """``pose_table`` for tracks at ``fps`` frames per second: the dense, normalised table on the MODEL's time grid (``resample_plan``,
     uu3d_resample_tracks; always a fresh buffer) -> (table, model frames per track, source frames per track).  With ``valid`` the table
     carries one flag per model frame.  ``repair_joints`` = G: uu3d_repair_joints runs on the source frames first; ``table.joint_state`` is
-    its (source frames, J) uint8 state."""
+    its (source frames, J) uint8 state.  ``keypoints`` / ``model`` as ``pose_table``: the map runs on the source frames, in front of the rest."""
     import torch
     check_repair_joints(repair_joints, valid)
     tr, J, lens = _device_tracks(tracks, device)
+    if keypoints is not None:
+        keypoints = keypoint_map(keypoints)
+        check_keypoint_inputs(keypoints, [J])
     check_valid(valid, lens, joints=J)
     if (lens < 1).any():
         raise ValueError("every track needs at least one frame")
     resolutions = check_resolutions(resolutions, len(tr))
     model_lens, left, right, weight = resample_plan(lens, fps, model_fps)
     src = torch.cat(tr, 0).contiguous() if len(tr) > 1 else tr[0].contiguous()
+    if keypoints is not None:
+        (src, valid), J = _map_front(keypoints, model, src, lens, valid), keypoints.joints
     kp = torch.empty((int(model_lens.sum()), J, 2), dtype=torch.float32, device=src.device)
     flags = None if valid is None else torch.empty((int(model_lens.sum()),), dtype=torch.uint8, device=src.device)
     src, valid_in, state = _front_validity(src, lens, J, valid, repair_joints)
@@ -379,7 +621,7 @@ def resampled_pose_table(tracks, device, fps, resolutions=None, valid=None, mode
 
 def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, flip=None, keyframes_only=False, reuse_frames=True,
                    batch_size=None, root_relative=True, depth=None, lengths=None, graph=True, valid=None, return_valid=False, fps=None, out_fps=None,
-                   model_fps=50, repair_joints=None):
+                   model_fps=50, repair_joints=None, keypoints=None):
     """One 3D pose per frame for each 2D keypoint track -> list of (T_i, J, 3) float32 tensors on the model's device (views of one buffer).
 
     ``tracks``: list of (T_i, J, 2) arrays or tensors, on the host or the device, at the frame rate the config was trained for (nothing is
@@ -438,8 +680,22 @@ def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, fl
     ``return_valid=True`` then returns (poses, flags, joint_state): joint_state a list of (given frames of track i, J) uint8 device tensors,
     1 observed, 2 filled, 0 neither.  ``StreamSession`` and ``replay_tracks`` have no such option and keep refusing anything but (T_i,)
     flags: a session computes a frame's spatial features once, at its push, when the joint's right neighbour is not known yet, so a causal
-    fill would break the session's contract (the pose of ``predict_tracks`` on the track cut at that frame)."""
+    fill would break the session's contract (the pose of ``predict_tracks`` on the track cut at that frame).
+
+    Any skeleton -- ``keypoints``: None = the tracks are in the model's own joint layout (today's call, the same bits, no further launch or
+    buffer).  Else a name of ``KEYPOINT_PRESETS`` ("coco17", "body25": onto the 17 Human3.6M joints of the shipped configs; geometric
+    approximations of the joints a detector does not emit, no accuracy figure claimed) or a ``KeypointMap`` of your own onto the model's J
+    joints (ValueError for another J): ``tracks[i]`` is then (T_i, K_in, 2) in the DETECTOR's layout -- a wrong joint count is a ValueError
+    naming both numbers -- and uu3d_map_keypoints turns it into (T_i, J, 2) on the device, on the raw coordinates, before anything else
+    looks at the track: model joint j is ``sum_k w[j][k] * in[src[j][k]]`` in float64, summed in the listed order, rounded once.  Per-joint
+    entries of ``valid`` are (T_i, K_in), one flag (``scores >= 0.3``) per DETECTOR joint, and "finite" is the finite test per source joint:
+    a model joint is observed iff every one of its sources is, and an unobserved one is zeros with flag 0 -- a lost COCO shoulder is a
+    lost neck and a lost torso, and nothing else; (T_i,) frame flags pass through.  ``joint_state`` stays per model joint.  The result
+    equals, bit for bit, ``predict_tracks(mapped, valid=flags)`` with the output of ``map_keypoints_host``, the rule in numpy."""
     import torch
+    if keypoints is not None:
+        keypoints = keypoint_map(keypoints, config.NUM_KEYPOINTS)
+        check_keypoint_inputs(keypoints, [_shape(t)[1] if len(_shape(t)) == 3 else -1 for t in tracks])
     if fps is None and out_fps is not None:
         raise ValueError("out_fps needs fps: the rate the tracks were filmed at")
     if fps is not None and keyframes_only:
@@ -459,12 +715,12 @@ def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, fl
         raise ValueError("keyframes_only needs a mask stride")
     if fps is None:
         table, lens = pose_table(tracks, dev, resolutions, int(mask_stride) if keyframes_only else 0, lengths, valid=valid,
-                                 repair_joints=repair_joints)
+                                 repair_joints=repair_joints, keypoints=keypoints, model=model)
         model_lens = lens
     else:
         rates = frame_rates(fps, len(tracks))
         table, model_lens, src_lens = resampled_pose_table(tracks, dev, rates, resolutions, valid=valid, model_fps=model_fps,
-                                                           repair_joints=repair_joints)
+                                                           repair_joints=repair_joints, keypoints=keypoints, model=model)
         lens, positions = output_positions(src_lens, rates, rates if out_fps is None else out_fps, model_fps)
     gen = SequenceGenerator(table, seq_len=cfg.SEQUENCE_LENGTH, target_frame_rate=50, subsample=1, stride=cfg.SEQUENCE_STRIDE,
                             padding_type=cfg.PADDING_TYPE, flip_augment=False, flip_lr_indices=cfg.AUGM_FLIP_KEYPOINT_ORDER,
@@ -534,6 +790,9 @@ def parse_args(argv=None):
     p.add_argument("--fps", type=_rate_argument, default=None, metavar="F",
                    help="frame rate of the tracks, a float or NUM/DEN (29.97, 30000/1001); without it they are taken at the model's rate")
     p.add_argument("--out_fps", type=_rate_argument, default=None, metavar="F", help="frame rate of the poses written (default: --fps)")
+    p.add_argument("--keypoints", default=None, metavar="NAME", choices=sorted(KEYPOINT_PRESETS),
+                   help="the joint layout of the arrays, (T, K, 2): mapped onto the model's joints on the device; --min_score then reads the "
+                        "score channel of (T, K, 3) arrays, one score per detector joint")
     return p.parse_args(argv)
 
 
@@ -550,6 +809,16 @@ def split_scores(names, tracks, J, min_score, source="input"):
     return [np.ascontiguousarray(t[:, :, :2]) for t in tracks], flags
 
 
+def input_joints(config, keypoints):
+    """The joint count of the command line's arrays -> (K, the keyword for ``predict_tracks`` / ``replay_tracks``)."""
+    if keypoints is None:
+        return config.NUM_KEYPOINTS, {}
+    try:
+        return keypoint_map(keypoints, config.NUM_KEYPOINTS).inputs, {"keypoints": keypoints}
+    except ValueError as e:
+        raise SystemExit(f"--keypoints: {e}") from None
+
+
 def main(argv=None):
     from .net.uplift_upsample_transformer_config import UpliftUpsampleConfig
     args = parse_args(argv)
@@ -559,7 +828,8 @@ def main(argv=None):
         tracks = [np.asarray(z[k], np.float32) for k in names]
     if not names:
         raise SystemExit(f"{args.input} holds no arrays")
-    tracks, joint_flags = split_scores(names, tracks, config.NUM_KEYPOINTS, args.min_score, args.input)
+    K, skeleton = input_joints(config, args.keypoints)
+    tracks, joint_flags = split_scores(names, tracks, K, args.min_score, args.input)
     ms = default_mask_stride(config) if args.mask_stride is None else args.mask_stride
     lengths = None
     if args.keyframes_only:
@@ -578,7 +848,7 @@ def main(argv=None):
     if args.repair_joints is not None:
         missing["repair_joints"] = args.repair_joints
     poses = predict_tracks(model, config, tracks, resolutions=None if args.resolution is None else tuple(args.resolution), mask_stride=ms,
-                           keyframes_only=args.keyframes_only, lengths=lengths, **missing, **rate)
+                           keyframes_only=args.keyframes_only, lengths=lengths, **missing, **rate, **skeleton)
     np.savez(args.output, **{k: np.asarray(p.detach().cpu().numpy(), np.float32) for k, p in zip(names, poses)})
     print(f"wrote {args.output}: {len(names)} tracks, {sum(int(p.shape[0]) for p in poses)} frames", flush=True)
     return 0

@@ -71,8 +71,16 @@ The state this needs is bounded; ``LiveRepairHost`` is the state machine the dev
 the buffers are fixed at construction).  Not together with ``fps`` / ``out_fps``: a revised source frame would re-make model frames that
 were filed already (a later change).  ``repair_joints=None`` is the session above, bit for bit.
 
+Any skeleton -- ``StreamSession(..., keypoints=M)`` (a name of ``predict.KEYPOINT_PRESETS`` or a ``predict.KeypointMap``): ``push`` takes
+frames in the DETECTOR's joint layout, (slots, K_in, 2), and one more launch in front of the stage (uu3d_map_keypoints) writes the session's
+own (slots, J, 2) frame -- with ``repair_joints`` its (slots, J) joint flags as well, from (slots, K_in) flags per detector joint.  In a
+session without ``fps`` that launch is the first step of the ONE captured tick graph; with ``fps`` it sits in front of
+uu3d_stream_source_push, not captured, like the launches around it.  ``captures`` stays 1 and ``push`` still never waits.  The session's
+contract is its usual one with the mapped track: the same session without ``keypoints``, pushed ``predict.map_keypoints_host``'s frames and
+flags, returns the same bits.  ``keypoints=None`` is the session above, bit for bit.
+
     python -m uplift_upsample_3dhpe_amd.stream --config C --weights W.h5 --input tracks.npz --output out.npz [--lookahead A] [--resolution W H]
-                                                 [--mask_missing] [--fps F [--out_fps G]] [--repair_joints G [--min_score S]]
+                                                 [--mask_missing] [--fps F [--out_fps G]] [--repair_joints G [--min_score S]] [--keypoints NAME]
 """
 import argparse
 import ctypes as C
@@ -83,7 +91,8 @@ import numpy as np
 
 from . import _capi
 from ._capi import ptr as _ptr
-from .predict import _load_model, check_repair_joints, check_resolutions, check_valid, split_scores
+from .predict import (KEYPOINT_PRESETS, _load_model, check_keypoint_inputs, check_repair_joints, check_resolutions, check_valid, input_joints,
+                      keypoint_map, split_scores)
 from .rates import (RatePlan, _rate_argument, max_lookahead, newest_model_frame, out_push_plan, push_plan,  # noqa: F401 (re-exported)
                     rate_plan, session_strides)
 
@@ -149,13 +158,16 @@ def staged_frames(repair_joints, mask_stride):
     return int(repair_joints) // int(mask_stride) + 2
 
 
-def _live_option(options, name, who):
-    """The one keyword ``name`` out of the ``**options`` of ``who`` (None when it is not given); any other keyword is the TypeError Python
-    itself raises for an unknown argument."""
-    unknown = sorted(k for k in options if k != name)
+LIVE_OPTIONS = ("repair_joints", "keypoints")                        # the keywords ``StreamSession`` and ``replay_tracks`` take from **options
+
+
+def _live_options(options, who):
+    """The keywords of ``LIVE_OPTIONS`` out of the ``**options`` of ``who``, in that order (None where one is not given); any other keyword
+    is the TypeError Python itself raises for an unknown argument."""
+    unknown = sorted(k for k in options if k not in LIVE_OPTIONS)
     if unknown:
         raise TypeError(f"{who}() got an unexpected keyword argument {unknown[0]!r}")
-    return options.get(name)
+    return tuple(options.get(name) for name in LIVE_OPTIONS)
 
 
 class LiveRepairHost(object):
@@ -278,9 +290,13 @@ class StreamSession(object):
         ``repair_joints`` (keyword only, taken from ``options``; any other name there is a TypeError): None = a missing joint makes its frame missing (the session above, bit for bit).  Else G, an int in
         [1, ``MAX_LIVE_REPAIR``]: the module docstring's "Live per-joint missed detections".  Implies ``missed_detections=True``;
         ``push(valid=...)`` may then hold one flag per joint and ``joint_state`` tells what became of the newest frame's joints.  Not
-        together with ``fps`` / ``out_fps`` (ValueError)."""
+        together with ``fps`` / ``out_fps`` (ValueError).
+        ``keypoints`` (keyword only, from ``options`` as well): None = the pushed frames are in the model's own joint layout (the session
+        above, bit for bit).  Else a name of ``predict.KEYPOINT_PRESETS`` or a ``predict.KeypointMap`` onto the model's joints: the module
+        docstring's "Any skeleton".  ``push`` then takes (slots, K_in, 2) frames and, with ``repair_joints``, (slots, K_in) flags."""
+        repair_joints, keypoints = _live_options(options, "StreamSession")
         res = self._init_plan(model, config, slots, resolutions, mask_stride, flip, lookahead, graph, missed_detections, fps, model_fps, out_fps,
-                              _live_option(options, "repair_joints", "StreamSession"))
+                              repair_joints, keypoints)
         import torch
         self._torch = torch
         self._lib = _capi.load_library()
@@ -294,7 +310,7 @@ class StreamSession(object):
 
     # ---- construction: checks and plan, layout and state, buffers, launch tables (then the capture) ---------------------------------
     def _init_plan(self, model, config, slots, resolutions, mask_stride, flip, lookahead, graph, missed_detections, fps, model_fps, out_fps,
-                   repair_joints=None):
+                   repair_joints=None, keypoints=None):
         """Every refusal that needs no device, and the session's plan.  -> the checked resolutions."""
         slots, lookahead = int(slots), int(lookahead)
         if slots < 1:
@@ -317,6 +333,7 @@ class StreamSession(object):
         if not model.arch.compiled_dims:
             raise NotImplementedError("StreamSession needs the frames form of the forward (uu3d_frame_features / uu3d_forward_frames_ex), "
                                       "which models with generic dims do not have")
+        self.keypoints = None if keypoints is None else keypoint_map(keypoints, config.NUM_KEYPOINTS)
         self.repair_joints = None if repair_joints is None else int(repair_joints)
         self.staged_frames = 1 if repair_joints is None else staged_frames(repair_joints, s_in)     # K: frames staged per slot and tick
         self.missed_detections = bool(missed_detections) or repair_joints is not None
@@ -366,6 +383,10 @@ class StreamSession(object):
         self._table = view(int(lay.table_offset), int(lay.table_rows) * dt, torch.float32).view(int(lay.table_rows), dt)
         self._zero_row = int(lay.zero_row)
         self._kp = zeros((T, J, 2), dtype=torch.float32)
+        self._kp_in = self._kp                                       # where push files the frame: with keypoints the detector's own layout
+        if self.keypoints is not None:
+            self._kp_in = zeros((T, self.keypoints.inputs, 2), dtype=torch.float32)
+            self._map_table = self.keypoints.device_table(dev)
         self._active = torch.ones((T,), dtype=torch.uint8, device=dev)
         self._active_all = True
         self._res = None if res is None else torch.from_numpy(res).pin_memory().to(dev, non_blocking=True)
@@ -396,6 +417,10 @@ class StreamSession(object):
             self._stage_valid = zeros((T, K), dtype=torch.uint8)
             self._far = torch.full((T, G), -1, dtype=torch.int32, device=dev)
             self._joint_state = zeros((T, J), dtype=torch.uint8)
+        # where push files its flags: with keypoints and repair_joints one per DETECTOR joint, mapped onto _valid_in by the tick's first launch
+        self._flags_in = self._valid_in
+        if self.keypoints is not None and self.repair_joints is not None:
+            self._flags_in = torch.ones((T, self.keypoints.inputs), dtype=torch.uint8, device=dev)
         # what a (sub-)tick takes as `active` and where its emit writes: with a rate the sub-ticks' own buffers, else the session's
         self._tick_active, self._emit_out, self._emit_fresh = self._active, self._out, self._fresh
         self._source_frames, self._src_host, self._src_known = self._frames, None, None
@@ -449,11 +474,20 @@ class StreamSession(object):
         emit = (lib.uu3d_stream_emit, (h, cfg, state, _ptr(self._central), order, emit_fresh, _ptr(self._emit_out)))
         self._tick_steps = [stage, features, commit, forward, emit]
         self._push_before, self._push_after = [], []
+        # any skeleton: the detector's joints -> the session's own frame (with repair_joints: and its joint flags), in front of everything
+        mapping = []
+        if self.keypoints is not None:
+            per_joint = self.repair_joints is not None
+            mapping = [(lib.uu3d_map_keypoints, (h, _ptr(self._map_table), self.keypoints.inputs, _ptr(self._kp_in),
+                                                 _ptr(self._flags_in) if per_joint else None, self.slots, kp,
+                                                 _ptr(self._valid_in) if per_joint else None))]
+        if self.rate is None:
+            self._tick_steps = mapping + self._tick_steps
         self._reset_call = (lib.uu3d_stream_reset, (h, cfg, state))
         self._reset_more = [] if self.repair_joints is None else [(lib.uu3d_stream_repair_reset, (h, cfg, self.repair_joints, _ptr(self._repair_state)))]
         if self.rate is not None:
             self._tick_steps.append((lib.uu3d_stream_file_keyframe, (h, cfg, rate, state, emit_fresh)))
-            self._push_before = [(lib.uu3d_stream_source_push, (h, cfg, rate, state, kp, active, _ptr(self._valid_in), int(self.missed_detections)))]
+            self._push_before = mapping + [(lib.uu3d_stream_source_push, (h, cfg, rate, state, kp, active, _ptr(self._valid_in), int(self.missed_detections)))]
             self._push_after = [(lib.uu3d_stream_timed_emit, (h, cfg, rate, state, _ptr(self._out), _ptr(self._fresh)))]
             self._reset_call = (lib.uu3d_stream_rate_reset, (h, cfg, rate, state))
         if self.max_out is not None:
@@ -523,7 +557,7 @@ class StreamSession(object):
         return f if f.is_cuda else f.contiguous().pin_memory()
 
     def push(self, kp2d, active=None, valid=None):
-        """One tick: ``kp2d`` (slots, J, 2), a host array or a tensor on the host or the device; ``active`` (slots,) bools or None = every slot
+        """One tick: ``kp2d`` (slots, J, 2) -- (slots, K_in, 2) in a session with ``keypoints`` --, a host array or a tensor on the host or the device; ``active`` (slots,) bools or None = every slot
         (an inactive slot's row of ``kp2d`` is ignored and its track does not grow).  -> (poses (slots, J, 3) float32, fresh (slots,) bool)
         on the device: the session's own buffers, valid until the next ``push``.  ``fresh[i]``: slot i's pose is new at this tick -- the
         pose of its frame ``frames[i] - 1 - lookahead``; otherwise ``poses[i]`` is the slot's previous pose (zeros before its first).
@@ -532,6 +566,8 @@ class StreamSession(object):
         ``active[i] == 0`` it would not) and a pose comes out by the usual rule, from windows that never read the missing frame.
         A session with ``repair_joints``: ``valid`` may also be (slots, J), one flag per joint, ANDed with the finite test per joint; a
         joint that is not observed is filled by the rule where it can be, and only a frame with a joint that cannot is missing.
+        A session with ``keypoints``: the per-joint form is (slots, K_in), one flag per DETECTOR joint, and a model joint is observed iff
+        every one of its sources is flagged and finite; (slots,) flags stand for all joints of a slot as before.
         A session with ``fps``: ``kp2d`` holds one SOURCE frame per slot; ``poses[i]`` is the pose of slot i's source frame
         ``source_frames[i] - 1 - lookahead`` and ``fresh[i]`` is set at every push of an active slot once that index is >= 0.  The push
         enqueues uu3d_stream_source_push, n replays of the one sub-tick graph and uu3d_stream_timed_emit; n is the largest number of model
@@ -553,12 +589,12 @@ class StreamSession(object):
                 self._zero_features()
         if not isinstance(kp2d, torch.Tensor):
             kp2d = torch.from_numpy(np.ascontiguousarray(kp2d, np.float32))
-        if tuple(kp2d.shape) != tuple(self._kp.shape):
-            raise ValueError(f"kp2d must be {tuple(self._kp.shape)}, got {tuple(kp2d.shape)}")
+        if tuple(kp2d.shape) != tuple(self._kp_in.shape):
+            raise ValueError(f"kp2d must be {tuple(self._kp_in.shape)}, got {tuple(kp2d.shape)}")
         with torch.cuda.device(dev):
             if not kp2d.is_cuda:
                 kp2d = kp2d.to(torch.float32).contiguous().pin_memory()       # host input goes through pinned memory, asynchronously
-            self._kp.copy_(kp2d, non_blocking=True)
+            self._kp_in.copy_(kp2d, non_blocking=True)
             if active is None:
                 if not self._active_all:
                     self._active.fill_(1)
@@ -567,10 +603,10 @@ class StreamSession(object):
                 self._active.copy_(self._flags(active, "active"), non_blocking=True)
                 self._active_all = False
             if valid is not None:
-                self._valid_in.copy_(self._flags(valid, "valid", None if self.repair_joints is None else self._kp.shape[1]), non_blocking=True)
+                self._flags_in.copy_(self._flags(valid, "valid", None if self.repair_joints is None else self._kp_in.shape[1]), non_blocking=True)
                 self._valid_in_all = False
             elif not self._valid_in_all:
-                self._valid_in.fill_(1)
+                self._flags_in.fill_(1)
                 self._valid_in_all = True
             cur = torch.cuda.current_stream(dev)
             self._run(self._push_before, cur)                         # (with a rate: file the source frames)
@@ -676,31 +712,36 @@ def replay_tracks(model, config, tracks, resolutions=None, mask_stride=None, fli
     ``out_fps=G``: -> per track the poses the session emitted, concatenated in order, (n_out_i, J, 3) float32 -- output frames
     0 .. n_out_i - 1 at G per second --, and the number each of its ticks returned, (T_i,) int32; still one copy to the host, at the end.
     ``repair_joints=G`` (keyword only, taken from ``options``): a session with ``repair_joints`` (it needs ``valid``); an entry of ``valid`` may
-    then be (T_i, J), one flag per joint."""
+    then be (T_i, J), one flag per joint.  ``keypoints=M`` (from ``options`` as well): a session with ``keypoints``; the tracks are
+    (T_i, K_in, 2) and per-joint entries of ``valid`` (T_i, K_in)."""
     import torch
-    repair_joints = _live_option(options, "repair_joints", "replay_tracks")
+    repair_joints, keypoints = _live_options(options, "replay_tracks")
     lens = [int(len(t)) for t in tracks]
     T, ticks = len(tracks), max(lens)
-    J = int(np.asarray(tracks[0]).shape[1])
+    K = J = int(np.asarray(tracks[0]).shape[1])                      # joints pushed, joints returned
+    if keypoints is not None:
+        keypoints = keypoint_map(keypoints, config.NUM_KEYPOINTS)
+        check_keypoint_inputs(keypoints, [np.asarray(t).shape[1] for t in tracks])
+        J = keypoints.joints
     check_repair_joints(repair_joints, valid)
     flags = None
     if valid is not None and not isinstance(valid, str):
-        check_valid(valid, lens, joints=None if repair_joints is None else J)
+        check_valid(valid, lens, joints=None if repair_joints is None else K)
         flags = [np.asarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v) != 0 for v in valid]
         if repair_joints is not None:                                # one flag per joint: a (T_i,) entry stands for all joints of its frames
-            flags = [f if f.ndim == 2 else np.repeat(f.reshape(-1, 1), J, axis=1) for f in flags]
+            flags = [f if f.ndim == 2 else np.repeat(f.reshape(-1, 1), K, axis=1) for f in flags]
     elif valid is not None and valid != "finite":
         raise ValueError('valid must be None, "finite" or a list with one (T_i,) array per track')
     s = StreamSession(model, config, T, resolutions=resolutions, mask_stride=mask_stride, flip=flip, lookahead=lookahead,
                       root_relative=root_relative, graph=graph, missed_detections=valid is not None, fps=fps, model_fps=model_fps, out_fps=out_fps,
-                      repair_joints=repair_joints)
+                      repair_joints=repair_joints, keypoints=keypoints)
     if out_fps is None:
         poses = torch.zeros((ticks, T, J, 3), dtype=torch.float32, device=model.device)
         fresh = torch.zeros((ticks, T), dtype=torch.bool, device=model.device)
     else:                                                             # one block of 32-bit words per tick and slot: the count, then the rows' bits
         R = s.max_out
         words = torch.zeros((ticks, T, 1 + R * J * 3), dtype=torch.int32, device=model.device)
-    kp = np.zeros((T, J, 2), np.float32)
+    kp = np.zeros((T, K, 2), np.float32)
     try:
         for k in range(ticks):
             act = np.array([k < n for n in lens])
@@ -755,6 +796,8 @@ def parse_args(argv=None):
     p.add_argument("--min_score", type=float, default=None, metavar="S",
                    help="with --repair_joints the arrays may be (T, J, 3) with the detector's score in the third channel: a joint counts as "
                         "seen when score >= S")
+    p.add_argument("--keypoints", default=None, metavar="NAME", choices=sorted(KEYPOINT_PRESETS),
+                   help="the joint layout of the arrays, (T, K, 2): mapped onto the model's joints on the device; scores are then per detector joint")
     args = p.parse_args(argv)
     if args.out_fps is not None and args.fps is None:
         p.error("--out_fps needs --fps")
@@ -774,10 +817,11 @@ def main(argv=None):
         tracks = [np.asarray(z[k], np.float32) for k in names]
     if not names:
         raise SystemExit(f"{args.input} holds no arrays")
-    tracks, joint_flags = split_scores(names, tracks, config.NUM_KEYPOINTS, args.min_score, args.input)
+    K, skeleton = input_joints(config, args.keypoints)
+    tracks, joint_flags = split_scores(names, tracks, K, args.min_score, args.input)
     for k, t in zip(names, tracks):
         if t.shape[0] < 1:
-            raise SystemExit(f"{args.input}[{k}] has shape {t.shape}, expected (T >= 1, {config.NUM_KEYPOINTS}, 2)")
+            raise SystemExit(f"{args.input}[{k}] has shape {t.shape}, expected (T >= 1, {K}, 2)")
     missing = {"valid": "finite"} if args.mask_missing or args.repair_joints is not None else {}
     if joint_flags is not None:
         missing = {"valid": joint_flags}
@@ -794,7 +838,7 @@ def main(argv=None):
             raise SystemExit(f"--fps / --out_fps / --lookahead: {e}") from None
     model = _load_model(config, args.weights)
     poses, fresh = replay_tracks(model, config, tracks, resolutions=None if args.resolution is None else tuple(args.resolution),
-                                 lookahead=args.lookahead, **missing,
+                                 lookahead=args.lookahead, **missing, **skeleton,
                                  **({} if args.fps is None else {"fps": args.fps}), **({} if args.out_fps is None else {"out_fps": args.out_fps}))
     out = {}
     for k, p, f in zip(names, poses, fresh):
