@@ -518,6 +518,63 @@ int uu3d_map_keypoints(uu3d_model* model, const void* map_dev, int32_t inputs, c
                        int64_t frames, float* out_dev, uint8_t* flags_out_dev, void* stream);
 
 /*
+ * PER-FRAME DETECTIONS (predict.associate_detections / predict_detections, stream.StreamSession(detections=D)): a multi-person detector
+ * emits a list of people per frame, in arbitrary order, with people entering, leaving and being missed.  These calls turn the lists into
+ * tracks (whole videos) and into the slots of a live session (one frame per tick) on the device, by ONE rule; predict.associate_host is
+ * the same rule in numpy and gives the same results bit for bit.  The rule is greedy and has no motion model and no Hungarian step: it is
+ * the simplest rule that can be stated exactly.  Capacities: slots S, detections D and joints K each <= 64 (UU3D_ERR_UNSUPPORTED beyond).
+ * THE RULE.  State per slot: alive, track_id (-1: free), age (consecutive frames without a match), a reference pose ref (K, 2) f32 with
+ * ref_seen (K): the last observed position of each joint since the slot's birth.  Global: next_id, dropped.  Per frame: dets (D, K, 2)
+ * f32, count, optional flags (D) or (D, K) u8.  A joint of a detection is OBSERVED when its flag is non-zero and both coordinates are
+ * finite; detection d is a CANDIDATE when d < count (count is clamped into [0, D]), its frame flag is set and it has >= min_common observed
+ * joints.  Unobserved joints never enter any arithmetic.
+ *   1. cost(alive slot s, candidate d): C = joints with ref_seen[s] that are observed in d; |C| < min_common: not allowed.  d2 = the sum
+ *      over C in ascending j of dx * dx + dy * dy, dx = (double)det.x - (double)ref.x, accumulated left to right in float64, every product
+ *      and sum rounded, no fused multiply-add.  scale2 = w * w + h * h of the bounding box of the slot's seen reference joints, in
+ *      float64; scale2 == 0: not allowed.  cost = d2 / ((double)|C| * scale2), one IEEE division; allowed iff cost <= max_dist * max_dist.
+ *   2. greedy: repeatedly the allowed pair of smallest cost among unmatched slots and unmatched candidates, ties to the smaller s, then
+ *      the smaller d, until no allowed pair is left.
+ *   3. a matched slot: age = 0; ref takes the bits of every joint observed in d and ref_seen = 1 there; d is its frame of this tick.
+ *   4. an unmatched alive slot: age += 1; age > max_age: it dies (alive = 0, track_id = -1); else its frame of this tick is MISSING.
+ *   5. unmatched candidates in ascending d take the lowest free slot each (one that died in step 4 included): BORN -- track_id =
+ *      next_id++, age = 0, ref / ref_seen from the detection, which is its first frame.  No free slot: dropped += 1, assignment -1.
+ *   6. per frame: assignment (D) i32 (slot or -1), track_ids (S) i32 (-1: free), born (S) u8, alive (S) u8.
+ * Causal: frame t's result depends on frames <= t only.
+ *
+ *   uu3d_associate_state_bytes(slots, keypoints): the size of the state block (256-byte aligned), 0 for arguments out of range.
+ *   uu3d_associate_reset(params, state_dev, slot_mask_dev (S) u8 or NULL, stream): the chosen slots become free (their tracks end); NULL =
+ *       every slot, and next_id = dropped = 0.  A fresh block must be reset once (a free slot's track_id is -1, not 0).
+ *   uu3d_associate_detections(params, dets_dev (frames, D, K, 2) f32, counts_dev (frames) i32 or NULL = D, flags_dev or NULL, flag_joints
+ *       (0: flags are (frames, D); else (frames, D, K)), video_start_dev (num_videos + 1) i64, num_videos, frames, state_dev (num_videos
+ *       blocks), assignment_dev (frames, D) i32, track_of_dev (frames, D) i32 = the track id of each detection or -1, track_ids_dev
+ *       (frames, S) i32 / born_dev (frames, S) u8 / alive_dev (frames, S) u8 or NULL each, counters_dev (num_videos, 2) i32 = (next_id,
+ *       dropped), stream): one workgroup per video runs its frames in order from a fresh state and leaves its final state in block v of
+ *       state_dev.  One launch.
+ *   uu3d_stream_associate(params, state_dev, dets_dev (D, K, 2), count_dev (1) i32, flags_dev or NULL, flag_joints, kp_out_dev (S, K, 2)
+ *       f32, flags_out_dev, flags_out_joints, active_out_dev (S) u8, born_out_dev (S) u8, assignment_dev (D) i32, track_ids_dev (S) i32,
+ *       dropped_dev (1) i32, stream): ONE frame, one workgroup -- the first launch of a live tick, in front of uu3d_stream_reset with
+ *       born_out_dev as its slot mask.  kp_out = the slot's detection, zeros for a slot without one; flags_out (S, K) (flags_out_joints
+ *       != 0): 1 iff the joint is observed; (S) otherwise: 1 iff the slot has a detection and every joint flag of it is set (an unmatched
+ *       alive slot's frame is MISSING); active_out = alive.  Same arguments at every tick: it replays from the tick's captured graph.
+ * Every output element has one writer, no atomics, dets_dev is only read (8-byte aligned; never kp_out_dev): bitwise repeatable.
+ */
+typedef struct uu3d_associate_params {
+    int32_t slots, detections, keypoints;  /* S, D, K: each in [1, 64] */
+    int32_t max_age, min_common, reserved; /* >= 0, >= 1, 0 */
+    double max_dist;                       /* >= 0; compared squared */
+} uu3d_associate_params;
+size_t uu3d_associate_state_bytes(int32_t slots, int32_t keypoints);
+int uu3d_associate_reset(const uu3d_associate_params* params, void* state_dev, const uint8_t* slot_mask_dev, void* stream);
+int uu3d_associate_detections(const uu3d_associate_params* params, const float* dets_dev, const int32_t* counts_dev, const uint8_t* flags_dev,
+                              int32_t flag_joints, const int64_t* video_start_dev, int32_t num_videos, int64_t frames, void* state_dev,
+                              int32_t* assignment_dev, int32_t* track_of_dev, int32_t* track_ids_dev, uint8_t* born_dev, uint8_t* alive_dev,
+                              int32_t* counters_dev, void* stream);
+int uu3d_stream_associate(const uu3d_associate_params* params, void* state_dev, const float* dets_dev, const int32_t* count_dev,
+                          const uint8_t* flags_dev, int32_t flag_joints, float* kp_out_dev, uint8_t* flags_out_dev, int32_t flags_out_joints,
+                          uint8_t* active_out_dev, uint8_t* born_out_dev, int32_t* assignment_dev, int32_t* track_ids_dev, int32_t* dropped_dev,
+                          void* stream);
+
+/*
  * ANY FRAME RATE (predict.predict_tracks(fps=...)): the front of YOUR OWN 2D TRACKS for tracks that were not filmed at the rate the model
  * was trained for.  The table holds the MODEL's time grid: row `row` (track row_track_dev[row]) is model frame k of its track, which sits at
  * source position p_k = k * fps / model_fps.  The host works the positions out in exact integer arithmetic (predict.resample_plan) and

@@ -12,7 +12,12 @@ next to the fps-only push (one pose per push) and the plain session.
 --repair_joints G [--missing_joints P] (not with --fps): the tick of StreamSession(repair_joints=G) as repair_graph_us -- per-joint flags
 with a share P (default 0.1) of the joints unobserved, K = G // s_in + 2 frames of spatial features per slot and tick -- next to the
 tick of StreamSession(missed_detections=True) fed the same frames with the per-frame flags those joints imply (md_graph_us).  The numpy
-baseline is left out."""
+baseline is left out.
+--detections D (not with --fps / --repair_joints): a synthetic scene of min(slots, D) people whose rows are shuffled in every frame --
+the tick of StreamSession(detections=D) fed the lists (det_graph_us) next to the tick of StreamSession(missed_detections=True) on the same
+frames in the same process, fed what predict.associate_host makes of them, worked out before the clock starts (md_graph_us), and next to
+the HOST ROUTE a user takes without the option (host_route_us): the detections start on the device, are copied back, matched in numpy
+(predict.AssociationHost), reset() is called for the slots born, then push().  The numpy baseline is left out."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -28,9 +33,12 @@ def main():
     ap.add_argument("--out_fps", default=None)
     ap.add_argument("--repair_joints", type=int, default=None)
     ap.add_argument("--missing_joints", type=float, default=0.1)
+    ap.add_argument("--detections", type=int, default=None)
     args = ap.parse_args()
     if args.repair_joints is not None and args.fps is not None:
         ap.error("--repair_joints is not measured together with --fps")
+    if args.detections is not None and (args.fps is not None or args.repair_joints is not None):
+        ap.error("--detections is not measured together with --fps / --repair_joints")
     if args.out_fps is not None and args.fps is None:
         ap.error("--out_fps needs --fps")
     import numpy as np, torch
@@ -98,6 +106,55 @@ def main():
                     ts.append(time.perf_counter() - t0)
                 return ts[args.warmup:]
 
+            def detections_variants():
+                from uplift_upsample_3dhpe_amd import predict
+                Dn = args.detections
+                P = min(T, Dn)
+                dets = np.zeros((total, Dn, J, 2), np.float32)
+                for k in range(total):
+                    dets[k, :P] = px[k, rng.permutation(P)]
+                host = predict.associate_host(dets, np.full(total, P), slots=T)
+                t_i, s_i = np.nonzero(host.slot_det >= 0)
+                frames = np.zeros((total, T, J, 2), np.float32)
+                frames[t_i, s_i] = dets[t_i, host.slot_det[t_i, s_i]]
+                d_dets = torch.from_numpy(dets).to(model.device)
+
+                def timed(s, tick):
+                    ts = []
+                    for k in range(total):
+                        t0 = time.perf_counter()
+                        tick(s, k)
+                        torch.cuda.synchronize()
+                        ts.append(time.perf_counter() - t0)
+                    s.check_range()
+                    s.close()
+                    return ts[args.warmup:]
+
+                new = lambda **kw: stream.StreamSession(model, cfg, slots=T, resolutions=(W, H), mask_stride=ms, flip=True, lookahead=args.lookahead, **kw)
+
+                def md_tick(s, k):
+                    if host.born[k].any():
+                        s.reset(slots=np.flatnonzero(host.born[k]))
+                    s.push(frames[k], active=host.alive[k] != 0, valid=host.slot_full[k])
+
+                def host_route():
+                    rule = predict.AssociationHost(T, Dn, J)
+                    kp = np.zeros((T, J, 2), np.float32)
+
+                    def tick(s, k):
+                        det = d_dets[k].cpu().numpy()                  # the detector's output sits on the device: copy it back and wait
+                        _, slot_det, born = rule.step(det, P)
+                        kp[:] = 0.0
+                        kp[slot_det >= 0] = det[slot_det[slot_det >= 0]]
+                        if born.any():
+                            s.reset(slots=np.flatnonzero(born))
+                        s.push(kp, active=rule.alive, valid=slot_det >= 0)
+                    return timed(new(missed_detections=True), tick)
+
+                row.update(detections=Dn, people=P, tracks=int(host.num_tracks), dropped=int(host.dropped))
+                return (("det_graph", lambda: timed(new(detections=Dn), lambda s, k: s.push_detections(d_dets[k], P))),
+                        ("md_graph", lambda: timed(new(missed_detections=True), md_tick)), ("host_route", host_route))
+
             row = dict(config=name, mask_stride=ms, slots=T, lookahead=args.lookahead, ticks=args.ticks)
             variants = (("graph", lambda: session(True)), ("no_graph", lambda: session(False)), ("baseline", baseline))
             if args.fps is not None:
@@ -114,11 +171,15 @@ def main():
                            staged_frames=stream.staged_frames(args.repair_joints, ms))
                 variants = (("repair_graph", lambda: session(True, valid=seen, repair_joints=args.repair_joints)),
                             ("md_graph", lambda: session(True, valid=seen.all(axis=2), missed_detections=True)))
+            if args.detections is not None:
+                variants = detections_variants()
             for key, fn in variants:
                 ts = np.asarray(fn())
                 row[key + "_us"] = round(1e6 * float(np.median(ts)), 1)
                 row[key + "_p90_us"] = round(1e6 * float(np.percentile(ts, 90)), 1)
-            if args.repair_joints is not None:
+            if args.detections is not None:
+                row["det_minus_md_us"] = round(row["det_graph_us"] - row["md_graph_us"], 1)
+            elif args.repair_joints is not None:
                 row["repair_minus_md_us"] = round(row["repair_graph_us"] - row["md_graph_us"], 1)
             elif args.fps is None:
                 row["speedup_vs_baseline"] = round(row["baseline_us"] / row["graph_us"], 2)

@@ -42,6 +42,7 @@ EXPORTED_SYMBOLS = (
     "uu3d_stream_out_state_layout", "uu3d_stream_timed_emit_multi", "uu3d_stream_out_reset",
     "uu3d_stream_repair_bytes", "uu3d_stream_repair_layout", "uu3d_stream_repair_stage", "uu3d_stream_commit_repair", "uu3d_stream_repair_reset",
     "uu3d_keypoint_map_bytes", "uu3d_keypoint_map_pack", "uu3d_map_keypoints",
+    "uu3d_associate_state_bytes", "uu3d_associate_reset", "uu3d_associate_detections", "uu3d_stream_associate",
 )
 # include/uu3d_ops.h
 OPS_SYMBOLS = (
@@ -114,6 +115,10 @@ class Uu3dStreamOutLayout(C.Structure):
 class Uu3dStreamRepairLayout(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("window", "staged_frames", "raw_offset", "last_xy_offset", "last_offset", "held_offset", "observed_offset",
                                          "bytes")]
+
+
+class Uu3dAssociateParams(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("slots", "detections", "keypoints", "max_age", "min_common", "reserved")] + [("max_dist", C.c_double)]
 
 
 # void (*uu3d_grad_ready_fn)(void* user, int64_t first, int64_t count, void* stream)
@@ -260,6 +265,16 @@ def load_library(path=None):
     lib.uu3d_keypoint_map_pack.argtypes = [i32, i32, vp, vp, vp, vp, sz]
     lib.uu3d_map_keypoints.restype = C.c_int
     lib.uu3d_map_keypoints.argtypes = [vp, vp, i32, vp, vp, i64, vp, vp, vp]
+    # per-frame detections: people -> tracks and slots, in front of everything above
+    apar = C.POINTER(Uu3dAssociateParams)
+    lib.uu3d_associate_state_bytes.restype = sz
+    lib.uu3d_associate_state_bytes.argtypes = [i32, i32]
+    lib.uu3d_associate_reset.restype = C.c_int
+    lib.uu3d_associate_reset.argtypes = [apar, vp, vp, vp]
+    lib.uu3d_associate_detections.restype = C.c_int
+    lib.uu3d_associate_detections.argtypes = [apar, vp, vp, vp, i32, vp, i32, i64] + [vp] * 8
+    lib.uu3d_stream_associate.restype = C.c_int
+    lib.uu3d_stream_associate.argtypes = [apar, vp, vp, vp, vp, i32, vp, vp, i32] + [vp] * 6
     lib.uu3d_world_to_cam_2d.restype = C.c_int
     lib.uu3d_world_to_cam_2d.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
     lib.uu3d_set_schedule.restype = C.c_int

@@ -36,6 +36,7 @@
 #include "uu3d_tracks.h"
 #include "uu3d_repair.h"
 #include "uu3d_keypoints.h"
+#include "uu3d_associate.h"
 #include "uu3d_stream.h"
 #include "uu3d_stream_rate.h"
 #include "uu3d_stream_repair.h"
@@ -618,6 +619,59 @@ int uu3d_map_keypoints(uu3d_model* m, const void* map, int32_t inputs, const flo
     hipLaunchKernelGGL(map_keypoints_kernel, dim3((unsigned)((frames * J + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        keypoint_table(map, J), inputs, J, src, flags_in, (long)frames, out, flags_out);
     return hipGetLastError() == hipSuccess ? UU3D_OK : fail(m, UU3D_ERR_HIP, "uu3d_map_keypoints: launch failed");
+}
+
+// ---- PER-FRAME DETECTIONS (uu3d_associate.h): the state block, its reset, whole videos, the one frame of a live tick ----
+namespace {
+// the settings of an association call: UU3D_OK, or what is wrong (capacities beyond 64: UU3D_ERR_UNSUPPORTED)
+int associate_resolve(const uu3d_associate_params* a, AssocParams& p) {
+    if (!a || a->slots < 1 || a->detections < 1 || a->keypoints < 1 || a->max_age < 0 || a->min_common < 1 || !(a->max_dist >= 0.0))
+        return UU3D_ERR_INVALID_ARGUMENT;
+    if (a->slots > kAssocMax || a->detections > kAssocMax || a->keypoints > kAssocMax) return UU3D_ERR_UNSUPPORTED;
+    p = AssocParams{a->slots, a->detections, a->keypoints, a->max_age, a->min_common, a->max_dist * a->max_dist};
+    return UU3D_OK;
+}
+}  // namespace
+
+size_t uu3d_associate_state_bytes(int32_t slots, int32_t keypoints) {
+    if (slots < 1 || slots > kAssocMax || keypoints < 1 || keypoints > kAssocMax) return 0;
+    return assoc_layout(slots, keypoints).bytes;
+}
+
+int uu3d_associate_reset(const uu3d_associate_params* a, void* state, const uint8_t* slot_mask, void* stream) {
+    AssocParams p;
+    if (const int st = associate_resolve(a, p)) return st;
+    if (!state || ((uintptr_t)state & 255) != 0) return UU3D_ERR_INVALID_ARGUMENT;
+    hipLaunchKernelGGL(associate_reset_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, p.S, p.K, (char*)state, slot_mask);
+    return hipGetLastError() == hipSuccess ? UU3D_OK : UU3D_ERR_HIP;
+}
+
+int uu3d_associate_detections(const uu3d_associate_params* a, const float* dets, const int32_t* counts, const uint8_t* flags, int32_t flag_joints,
+                              const int64_t* video_start, int32_t num_videos, int64_t frames, void* state, int32_t* assignment, int32_t* track_of,
+                              int32_t* track_ids, uint8_t* born, uint8_t* alive, int32_t* counters, void* stream) {
+    AssocParams p;
+    if (const int st = associate_resolve(a, p)) return st;
+    if (!dets || !video_start || !state || !assignment || !track_of || !counters || num_videos < 1 || num_videos > (1 << 20) || frames < 0 ||
+        frames > ((int64_t)1 << 40))
+        return UU3D_ERR_INVALID_ARGUMENT;
+    if (((uintptr_t)dets & 7) != 0 || ((uintptr_t)state & 255) != 0) return UU3D_ERR_INVALID_ARGUMENT;
+    hipLaunchKernelGGL(associate_video_kernel, dim3((unsigned)num_videos), dim3(kAssocLanes), 0, (hipStream_t)stream, p, dets, counts, flags,
+                       flag_joints != 0 ? 1 : 0, video_start, (long)frames, (char*)state, assignment, track_of, track_ids, born, alive, counters);
+    return hipGetLastError() == hipSuccess ? UU3D_OK : UU3D_ERR_HIP;
+}
+
+int uu3d_stream_associate(const uu3d_associate_params* a, void* state, const float* dets, const int32_t* count, const uint8_t* flags,
+                          int32_t flag_joints, float* kp_out, uint8_t* flags_out, int32_t flags_out_joints, uint8_t* active_out, uint8_t* born_out,
+                          int32_t* assignment, int32_t* track_ids, int32_t* dropped, void* stream) {
+    AssocParams p;
+    if (const int st = associate_resolve(a, p)) return st;
+    if (!state || !dets || !count || !kp_out || !flags_out || !active_out || !born_out || !assignment || !track_ids || !dropped)
+        return UU3D_ERR_INVALID_ARGUMENT;
+    if (((uintptr_t)dets & 7) != 0 || ((uintptr_t)kp_out & 7) != 0 || ((uintptr_t)state & 255) != 0 || (const void*)dets == (const void*)kp_out)
+        return UU3D_ERR_INVALID_ARGUMENT;
+    hipLaunchKernelGGL(associate_step_kernel, dim3(1), dim3(kAssocLanes), 0, (hipStream_t)stream, p, (char*)state, dets, count, flags,
+                       flag_joints != 0 ? 1 : 0, kp_out, flags_out, flags_out_joints != 0 ? 1 : 0, active_out, born_out, assignment, track_ids, dropped);
+    return hipGetLastError() == hipSuccess ? UU3D_OK : UU3D_ERR_HIP;
 }
 
 int uu3d_assemble_tracks(const float* plain, const float* flipped, int64_t num_windows, const int32_t* flip_order, const int32_t* left,

@@ -79,6 +79,18 @@ uu3d_stream_source_push, not captured, like the launches around it.  ``captures`
 contract is its usual one with the mapped track: the same session without ``keypoints``, pushed ``predict.map_keypoints_host``'s frames and
 flags, returns the same bits.  ``keypoints=None`` is the session above, bit for bit.
 
+Per-frame detections -- ``StreamSession(..., detections=D, max_age=, max_dist=, min_common=)``: the session takes what a multi-person
+detector emits, ``push_detections(dets (D, K, 2), count, valid)`` -- per frame a list of people in ANY order, people entering, leaving and
+being missed -- and matches people to slots on the device: ``slots`` is the capacity, a slot is born, fed and freed by the rule of
+``predict.associate_host`` (include/uu3d.h, PER-FRAME DETECTIONS: greedy, no motion model).  The captured tick begins with
+uu3d_stream_associate -- it scatters the detections into the session's frame, flag and ``active`` buffers and writes the ``born`` mask --,
+then uu3d_stream_reset (and uu3d_stream_repair_reset) with that mask ON THE DEVICE, then the steps above unchanged: still ONE linear
+captured graph, ``push_detections`` never waits, ``count`` may be a device tensor.  Implies ``missed_detections=True``: an alive slot
+without a match gets a MISSING frame.  The contract: the session equals, bit for bit, a ``StreamSession(missed_detections=True)`` driven
+by ``associate_host`` -- ``reset(born)``, then ``push(frames, active=alive, valid=matched)``.  Works with ``keypoints`` (the association
+runs on the detector's joints, in front of the map) and ``repair_joints``; NOT together with ``fps`` / ``out_fps`` (ValueError: the host
+mirror of the source counters cannot follow births that happen on the device yet).
+
     python -m uplift_upsample_3dhpe_amd.stream --config C --weights W.h5 --input tracks.npz --output out.npz [--lookahead A] [--resolution W H]
                                                  [--mask_missing] [--fps F [--out_fps G]] [--repair_joints G [--min_score S]] [--keypoints NAME]
 """
@@ -91,8 +103,8 @@ import numpy as np
 
 from . import _capi
 from ._capi import ptr as _ptr
-from .predict import (KEYPOINT_PRESETS, _load_model, check_keypoint_inputs, check_repair_joints, check_resolutions, check_valid, input_joints,
-                      keypoint_map, split_scores)
+from .predict import (ASSOCIATION_DEFAULTS, KEYPOINT_PRESETS, _load_model, check_association, check_keypoint_inputs, check_repair_joints,
+                      check_resolutions, check_valid, input_joints, keypoint_map, split_scores)
 from .rates import (RatePlan, _rate_argument, max_lookahead, newest_model_frame, out_push_plan, push_plan,  # noqa: F401 (re-exported)
                     rate_plan, session_strides)
 
@@ -159,15 +171,16 @@ def staged_frames(repair_joints, mask_stride):
 
 
 LIVE_OPTIONS = ("repair_joints", "keypoints")                        # the keywords ``StreamSession`` and ``replay_tracks`` take from **options
+DETECTION_OPTIONS = ("detections",) + tuple(ASSOCIATION_DEFAULTS)    # ... and the ones only ``StreamSession`` takes: per-frame detections
 
 
-def _live_options(options, who):
-    """The keywords of ``LIVE_OPTIONS`` out of the ``**options`` of ``who``, in that order (None where one is not given); any other keyword
+def _live_options(options, who, names=LIVE_OPTIONS):
+    """The keywords of ``names`` out of the ``**options`` of ``who``, in that order (None where one is not given); any other keyword
     is the TypeError Python itself raises for an unknown argument."""
-    unknown = sorted(k for k in options if k not in LIVE_OPTIONS)
+    unknown = sorted(k for k in options if k not in names)
     if unknown:
         raise TypeError(f"{who}() got an unexpected keyword argument {unknown[0]!r}")
-    return tuple(options.get(name) for name in LIVE_OPTIONS)
+    return tuple(options.get(name) for name in names)
 
 
 class LiveRepairHost(object):
@@ -293,10 +306,15 @@ class StreamSession(object):
         together with ``fps`` / ``out_fps`` (ValueError).
         ``keypoints`` (keyword only, from ``options`` as well): None = the pushed frames are in the model's own joint layout (the session
         above, bit for bit).  Else a name of ``predict.KEYPOINT_PRESETS`` or a ``predict.KeypointMap`` onto the model's joints: the module
-        docstring's "Any skeleton".  ``push`` then takes (slots, K_in, 2) frames and, with ``repair_joints``, (slots, K_in) flags."""
-        repair_joints, keypoints = _live_options(options, "StreamSession")
+        docstring's "Any skeleton".  ``push`` then takes (slots, K_in, 2) frames and, with ``repair_joints``, (slots, K_in) flags.
+        ``detections`` (keyword only, from ``options`` as well): None = the caller pushes tracks (the session above, bit for bit).  Else D in
+        [1, 64], the most people a frame lists: the module docstring's "Per-frame detections" -- ``push_detections`` in place of ``push``,
+        ``slots`` <= 64 is the capacity, the joints the detector emits <= 64.  ``max_age`` / ``max_dist`` / ``min_common``: the rule's
+        parameters (``predict.ASSOCIATION_DEFAULTS``: 10, 0.5, 3 -- conveniences, not tuned values).  Implies ``missed_detections=True``; not
+        together with ``fps`` / ``out_fps`` (ValueError)."""
+        repair_joints, keypoints, detections, *rule = _live_options(options, "StreamSession", LIVE_OPTIONS + DETECTION_OPTIONS)
         res = self._init_plan(model, config, slots, resolutions, mask_stride, flip, lookahead, graph, missed_detections, fps, model_fps, out_fps,
-                              repair_joints, keypoints)
+                              repair_joints, keypoints, detections, dict(zip(ASSOCIATION_DEFAULTS, rule)))
         import torch
         self._torch = torch
         self._lib = _capi.load_library()
@@ -305,16 +323,29 @@ class StreamSession(object):
             self._init_buffers(config, res, *layouts)
             self._init_launch_tables()
             self._zero_features()
+            if self.detections is not None:                          # (a free slot's track id is -1, not 0)
+                self._run([(fn, args + (None,)) for fn, args in self._reset_more[-1:]], torch.cuda.current_stream(model.device))
             if self.graph:
                 self._capture()
 
     # ---- construction: checks and plan, layout and state, buffers, launch tables (then the capture) ---------------------------------
     def _init_plan(self, model, config, slots, resolutions, mask_stride, flip, lookahead, graph, missed_detections, fps, model_fps, out_fps,
-                   repair_joints=None, keypoints=None):
+                   repair_joints=None, keypoints=None, detections=None, rule=None):
         """Every refusal that needs no device, and the session's plan.  -> the checked resolutions."""
         slots, lookahead = int(slots), int(lookahead)
         if slots < 1:
             raise ValueError("slots >= 1")
+        self.detections, self.association = None, None
+        if detections is not None:
+            rule = {k: (v if (rule or {}).get(k) is None else rule[k]) for k, v in ASSOCIATION_DEFAULTS.items()}
+            joints = config.NUM_KEYPOINTS if keypoints is None else keypoint_map(keypoints, config.NUM_KEYPOINTS).inputs
+            check_association(slots, detections, int(joints), **rule)
+            if fps is not None or out_fps is not None:
+                raise ValueError("detections together with fps / out_fps is not supported yet: the host mirror of the source counters cannot "
+                                 "follow births that happen on the device")
+            self.detections, self.association = int(detections), rule
+        elif rule is not None and any(v is not None for v in rule.values()):
+            raise ValueError("max_age / max_dist / min_common need detections=D: they are the parameters of the association")
         check_repair_joints(repair_joints, "finite")
         if repair_joints is not None and int(repair_joints) > MAX_LIVE_REPAIR:
             raise ValueError(f"repair_joints must be at most {MAX_LIVE_REPAIR} in a live session (the frames a tick re-stages and its buffers are "
@@ -336,7 +367,7 @@ class StreamSession(object):
         self.keypoints = None if keypoints is None else keypoint_map(keypoints, config.NUM_KEYPOINTS)
         self.repair_joints = None if repair_joints is None else int(repair_joints)
         self.staged_frames = 1 if repair_joints is None else staged_frames(repair_joints, s_in)     # K: frames staged per slot and tick
-        self.missed_detections = bool(missed_detections) or repair_joints is not None
+        self.missed_detections = bool(missed_detections) or repair_joints is not None or detections is not None
         if self.missed_detections and not model.has_strided_input:
             raise ValueError("missed_detections needs a model with strided input: a missing frame becomes the learned masked token")
         self.model, self.slots, self.lookahead, self.graph = model, slots, lookahead, bool(graph)
@@ -362,6 +393,10 @@ class StreamSession(object):
         if self.max_out is not None:
             self._outp, olay = _capi.Uu3dStreamOut(r.out_c, r.out_d, r.pos_num, r.pos_den, r.max_out), _capi.Uu3dStreamOutLayout()
             _capi.check(lib, lib.uu3d_stream_out_state_layout(h, C.byref(self._cfg), C.byref(self._rate), C.byref(self._outp), C.byref(olay)), h)
+        if self.detections is not None:
+            K = config.NUM_KEYPOINTS if self.keypoints is None else self.keypoints.inputs
+            a = self.association
+            self._assoc = _capi.Uu3dAssociateParams(self.slots, self.detections, int(K), int(a["max_age"]), int(a["min_common"]), 0, float(a["max_dist"]))
         self._repair_bytes = 0
         if self.repair_joints is not None:
             play = _capi.Uu3dStreamRepairLayout()
@@ -421,6 +456,19 @@ class StreamSession(object):
         self._flags_in = self._valid_in
         if self.keypoints is not None and self.repair_joints is not None:
             self._flags_in = torch.ones((T, self.keypoints.inputs), dtype=torch.uint8, device=dev)
+        # per-frame detections: what push_detections files (the frame's list, its count, one flag per detector joint), the association state
+        # and what the tick's first launch writes beside the frame, flag and active buffers above
+        if self.detections is not None:
+            D, Kd = self.detections, int(self._kp_in.shape[1])
+            self._dets = zeros((D, Kd, 2), dtype=torch.float32)
+            self._det_count = torch.full((1,), D, dtype=torch.int32, device=dev)
+            self._det_flags = torch.ones((D, Kd), dtype=torch.uint8, device=dev)
+            self._det_count_full = self._det_flags_all = True
+            self._assoc_state = zeros(int(lib.uu3d_associate_state_bytes(T, Kd)), dtype=torch.uint8)
+            self._born = zeros((T,), dtype=torch.uint8)
+            self._assignment = torch.full((D,), -1, dtype=torch.int32, device=dev)
+            self._track_ids = torch.full((T,), -1, dtype=torch.int32, device=dev)
+            self._dropped = zeros((1,), dtype=torch.int32)
         # what a (sub-)tick takes as `active` and where its emit writes: with a rate the sub-ticks' own buffers, else the session's
         self._tick_active, self._emit_out, self._emit_fresh = self._active, self._out, self._fresh
         self._source_frames, self._src_host, self._src_known = self._frames, None, None
@@ -485,6 +533,16 @@ class StreamSession(object):
             self._tick_steps = mapping + self._tick_steps
         self._reset_call = (lib.uu3d_stream_reset, (h, cfg, state))
         self._reset_more = [] if self.repair_joints is None else [(lib.uu3d_stream_repair_reset, (h, cfg, self.repair_joints, _ptr(self._repair_state)))]
+        # per-frame detections: the association in front of everything -- it writes the frame, the flags, `active` and the born mask --, then
+        # the resets of the slots born at this tick, with the mask on the device
+        if self.detections is not None:
+            assoc, born = C.byref(self._assoc), _ptr(self._born)
+            front = [(lib.uu3d_stream_associate, (assoc, _ptr(self._assoc_state), _ptr(self._dets), _ptr(self._det_count), _ptr(self._det_flags), 1,
+                                                  _ptr(self._kp_in), _ptr(self._flags_in), int(self._flags_in.dim() == 2), active, born,
+                                                  _ptr(self._assignment), _ptr(self._track_ids), _ptr(self._dropped)))]
+            front += [(fn, args + (born,)) for fn, args in [self._reset_call] + self._reset_more]
+            self._tick_steps = front + self._tick_steps
+            self._reset_more = self._reset_more + [(lib.uu3d_associate_reset, (assoc, _ptr(self._assoc_state)))]
         if self.rate is not None:
             self._tick_steps.append((lib.uu3d_stream_file_keyframe, (h, cfg, rate, state, emit_fresh)))
             self._push_before = mapping + [(lib.uu3d_stream_source_push, (h, cfg, rate, state, kp, active, _ptr(self._valid_in), int(self.missed_detections)))]
@@ -527,6 +585,9 @@ class StreamSession(object):
         try:
             with torch.cuda.stream(side):
                 self._active.zero_()
+                if self.detections is not None:                      # (no detection, no slot alive: the association changes nothing either)
+                    self._det_count.zero_()
+                    self._det_count_full = False
                 self._tick(side)
                 self._active.fill_(1)
             side.synchronize()
@@ -581,6 +642,8 @@ class StreamSession(object):
         torch = self._torch
         m = self.model
         dev = m.device
+        if getattr(self, "detections", None) is not None:
+            raise ValueError("a session built with detections=D takes push_detections(dets, count, valid): the device decides which slot a person is")
         if valid is not None and not self.missed_detections:
             raise ValueError("push(valid=...) needs a session built with missed_detections=True")
         if m._weights_dirty or getattr(m, "_pending_assigns", False):
@@ -618,6 +681,62 @@ class StreamSession(object):
             self._run(self._push_after, cur)                          # (with a rate: read the poses)
         return self._result
 
+    def push_detections(self, dets, count=None, valid=None):
+        """One tick of a session built with ``detections=D``: ``dets`` (D, K, 2) -- the people the detector listed for this frame, in any
+        order, in its own joint layout --, a host array or a tensor on the host or the device; ``count``: how many rows are given -- an int,
+        an int32 tensor (a DEVICE tensor is never read on the host) or None = D; ``valid``: None, (D,) flags, one per detection, or
+        (D, K), one per joint (``scores >= 0.3``).  uu3d_stream_associate matches the people to slots on the device; then the tick of
+        ``push``.  -> (poses (slots, J, 3) float32, fresh (slots,) bool) as ``push``: row i belongs to the track in slot i,
+        ``track_ids[i]``.  In a session without ``repair_joints`` a detection with a joint flag that is not set gives a MISSING frame (as
+        a (T_i, J) entry of ``predict_tracks``' ``valid`` does); with it the joint is filled by the rule.  Enqueues on the current stream
+        and returns; never waits for the device."""
+        torch = self._torch
+        m = self.model
+        dev = m.device
+        if getattr(self, "detections", None) is None:
+            raise ValueError("push_detections needs a session built with detections=D")
+        if m._weights_dirty or getattr(m, "_pending_assigns", False):
+            m._sync_from_trainer()
+            with torch.cuda.device(dev):
+                self._zero_features()
+        if not isinstance(dets, torch.Tensor):
+            dets = torch.from_numpy(np.ascontiguousarray(dets, np.float32))
+        if tuple(dets.shape) != tuple(self._dets.shape):
+            raise ValueError(f"dets must be {tuple(self._dets.shape)}, got {tuple(dets.shape)}")
+        D, K = self._det_flags.shape
+        if valid is not None:
+            f = valid if isinstance(valid, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(valid) != 0).view(np.uint8))
+            f = f.view(torch.uint8) if f.dtype == torch.bool else f.to(torch.uint8)
+            if tuple(f.shape) not in ((D,), (D, K)):
+                raise ValueError(f"valid must be ({D},) or ({D}, {K})")
+            f = f.reshape(D, -1)                                       # ((D, 1) broadcasts over the joints in the copy, on the device)
+            valid = f if f.is_cuda else f.expand(D, K).contiguous().pin_memory()
+        with torch.cuda.device(dev):
+            if not dets.is_cuda:
+                dets = dets.to(torch.float32).contiguous().pin_memory()
+            self._dets.copy_(dets, non_blocking=True)
+            if count is None:
+                if not self._det_count_full:
+                    self._det_count.fill_(int(D))
+                    self._det_count_full = True
+            else:
+                if isinstance(count, torch.Tensor):
+                    self._det_count.copy_(count.reshape(1), non_blocking=True)
+                else:
+                    self._det_count.fill_(min(max(int(count), 0), int(D)))
+                self._det_count_full = False
+            if valid is not None:
+                self._det_flags.copy_(valid, non_blocking=True)
+                self._det_flags_all = False
+            elif not self._det_flags_all:
+                self._det_flags.fill_(1)
+                self._det_flags_all = True
+            if self.graph:
+                self._graph.replay()
+            else:
+                self._tick(torch.cuda.current_stream(dev))
+        return self._result
+
     def _sub_ticks(self, active):
         """How many (sub-)ticks this push needs, advancing the host mirror of the source counters (no rate: none, and one tick per push)."""
         if self._src_host is None:
@@ -637,7 +756,9 @@ class StreamSession(object):
 
     def reset(self, slots=None):
         """The given slots (indices; None = all) start a new track: zero frames, held pose 0, with ``out_fps`` output counter 0, with
-        ``repair_joints`` no observation of any joint.  Stream-ordered like ``push``."""
+        ``repair_joints`` no observation of any joint.  A session with ``detections``: the tracks in those slots END and the slots are
+        free (the next unmatched person takes the lowest one, under a new id); None also sets the id and dropped counters back to 0.
+        Stream-ordered like ``push``."""
         torch = self._torch
         m = self.model
         mask = None
@@ -647,6 +768,12 @@ class StreamSession(object):
                 h[np.asarray(slots, np.int64).reshape(-1)] = 1
                 mask = torch.from_numpy(h).pin_memory().to(m.device, non_blocking=True)
             self._run([(fn, args + (_ptr(mask),)) for fn, args in [self._reset_call] + self._reset_more], torch.cuda.current_stream(m.device))
+            if self.detections is not None:                          # (what the properties show until the next tick)
+                if mask is None:
+                    self._track_ids.fill_(-1)
+                    self._dropped.zero_()
+                else:
+                    self._track_ids.masked_fill_(mask.view(torch.bool), -1)
         self._mirror_reset(slots)
 
     def _mirror_reset(self, slots):
@@ -674,6 +801,28 @@ class StreamSession(object):
         if self.repair_joints is None:
             raise AttributeError("joint_state needs a session with repair_joints")
         return self._joint_state
+
+    def _detections_only(self, name):
+        if self.detections is None:
+            raise AttributeError(f"{name} needs a session with detections")
+
+    @property
+    def track_ids(self):
+        """(slots,) int32 on the device (sessions with ``detections``): the track in each slot after the last tick, -1 for a free slot."""
+        self._detections_only("track_ids")
+        return self._track_ids
+
+    @property
+    def assignment(self):
+        """(D,) int32 on the device (sessions with ``detections``): the slot each detection of the last tick went to, -1: none."""
+        self._detections_only("assignment")
+        return self._assignment
+
+    @property
+    def dropped(self):
+        """(1,) int32 on the device (sessions with ``detections``): detections dropped so far because no slot was free."""
+        self._detections_only("dropped")
+        return self._dropped
 
     @property
     def out_frames(self):
@@ -769,6 +918,46 @@ def replay_tracks(model, config, tracks, resolutions=None, mask_stride=None, fli
                 [counts[:n, i].astype(np.int32) for i, n in enumerate(lens)])
     poses, fresh = poses.cpu().numpy(), fresh.cpu().numpy()
     return [poses[:n, i] for i, n in enumerate(lens)], [fresh[:n, i] for i, n in enumerate(lens)]
+
+
+def replay_detections(model, config, detections, counts=None, valid=None, slots=None, resolutions=None, mask_stride=None, flip=None, lookahead=0,
+                      root_relative=True, graph=True, **options):
+    """Push ONE video's per-frame detections tick by tick through a ``StreamSession(detections=D)`` and collect the poses per track id.
+    ``detections`` (T, D, K, 2); ``counts`` (T,) or None; ``valid``: None, (T, D) or (T, D, K); ``slots`` (None: D); ``resolutions``: None
+    or one (w, h); ``options``: ``max_age`` / ``max_dist`` / ``min_common``, ``repair_joints``, ``keypoints``.
+    -> a list of (track_id, first_frame, poses (n, J, 3) float32, fresh (n,) bool) by track id, host arrays: what the session returned for
+    the track's slot at the ticks first_frame .. first_frame + n - 1, the ticks the track was alive (its trailing missing frames
+    included; ``predict.predict_detections`` ends a track at its last matched frame).  One copy to the host, at the end."""
+    import torch
+    from .predict import _host_array
+    detections = _host_array(detections)
+    if detections.ndim != 4 or detections.shape[3] != 2:
+        raise ValueError(f"detections must be (T, D, K, 2), got {detections.shape}")
+    ticks, D = int(detections.shape[0]), int(detections.shape[1])
+    S = D if slots is None else int(slots)
+    counts = None if counts is None else np.asarray(_host_array(counts)).reshape(ticks)
+    valid = None if valid is None else _host_array(valid)
+    s = StreamSession(model, config, S, resolutions=resolutions, mask_stride=mask_stride, flip=flip, lookahead=lookahead, root_relative=root_relative,
+                      graph=graph, detections=D, **options)
+    J = int(model.arch.num_keypoints)
+    poses = torch.zeros((ticks, S, J, 3), dtype=torch.float32, device=model.device)
+    words = torch.zeros((ticks, 2, S), dtype=torch.int32, device=model.device)            # per tick: the fresh flags, the track ids
+    try:
+        for k in range(ticks):
+            p, f = s.push_detections(detections[k], None if counts is None else int(counts[k]), None if valid is None else valid[k])
+            poses[k].copy_(p)
+            words[k, 0].copy_(f)
+            words[k, 1].copy_(s.track_ids)
+        s.check_range()
+    finally:
+        s.close()
+    poses, words = poses.cpu().numpy(), words.cpu().numpy()
+    fresh, ids = words[:, 0] != 0, words[:, 1]
+    out = []
+    for tid in range(int(ids.max()) + 1 if ids.size else 0):
+        t, slot = np.nonzero(ids == tid)
+        out.append((tid, int(t[0]), poses[t, slot], fresh[t, slot]))
+    return out
 
 
 def parse_args(argv=None):
