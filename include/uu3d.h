@@ -575,6 +575,54 @@ int uu3d_stream_associate(const uu3d_associate_params* params, void* state_dev, 
                           void* stream);
 
 /*
+ * ABSOLUTE ROOT POSITION (predict.solve_roots, predict.predict_tracks(camera=...), predict.predict_detections(camera=...)): every pose these
+ * calls return is root-relative; eight people of one video all sit on the origin.  The 2D keypoints that were uplifted, together with the
+ * camera's intrinsics, determine where each skeleton must stand so that it projects onto them: a linear least-squares problem with three
+ * unknowns per frame.  predict.solve_roots_host and predict.root_trajectory_host are the same rule in numpy, bit for bit.  No accuracy is
+ * claimed: the model's scale error goes 1:1 into the depth.
+ * THE RULE, in float64, every product and sum rounded, no fused multiply-add, sums over the used joints in ascending joint order.
+ * Camera (fx, fy, cx, cy), no distortion, in the units of the 2D coordinates as given; non-finite, fx <= 0 or fy <= 0: the caller refuses
+ * it (a frame of such a camera is not solved).  Joint j of a frame is USED iff its byte of joint_flags_dev (frames, J) u8 is non-zero (NULL:
+ * no flags) and both of its 2D coordinates are finite -- the raw coordinates in the model's layout, behind uu3d_map_keypoints and in
+ * front of uu3d_repair_joints, the normalisation and the resampling: a filled joint is an interpolation, not a measurement, and a frame
+ * the network never saw still fixes its own root from the joints that were seen.  With the frame's pose (X, Y, Z) widened from float32:
+ *     a = (u - cx) / fx    b = (v - cy) / fy    p = a * Z - X    q = b * Z - Y
+ *     n = the used joints; Sa += a; Sb += b; Sq += (a * a + b * b); Sp += p; Sk += q; Sr += (a * p + b * q)
+ *     den = Sq - (Sa * Sa + Sb * Sb) / n        num = (Sa * Sp + Sb * Sk) / n - Sr
+ *     Tz = num / den        Tx = (Sp + Sa * Tz) / n        Ty = (Sk + Sb * Tz) / n
+ * (the normal equations of Tx - a Tz = p, Ty - b Tz = q).  The frame is SOLVED iff n >= min_joints (>= 2), den > 0, Tx, Ty and Tz are
+ * finite, Tz > 0 and Z + Tz > 0 for every used joint; the root of a frame that is not solved is zeros.
+ * TRAJECTORY.  The root motion of a track is the piecewise-linear function through its solved given frames, read at the positions of the
+ * returned frames.  The host hands over each position as an exact rational in given-frame units (predict.root_plan): base_dev (out_frames)
+ * i64 = the global row of the given frame at or before it, wnum_dev / wden_dev (out_frames) i64 = the fraction behind that frame, 0 <= wnum <
+ * wden, every (frames of the track) * wden below 2^53.  With L = the nearest solved frame of the track at or before base and R = the
+ * nearest one behind base:
+ *     wnum == 0 and L == base:  the bits of that frame's root, rounded once to float32                                    root_state 1
+ *     L and R exist:  (float)(root[L] * (1.0 - w) + root[R] * w), w = (double)((base - L) * wden + wnum) / (double)((R - L) * wden)    2
+ *     only one of them exists (before the first solved frame, behind the last one):  its root, held                               2
+ *     the track has no solved frame:  zeros                                                                                       0
+ *
+ *   uu3d_solve_roots(poses_dev (frames, J, 3) f32, kp2d_dev (frames, J, 2) f32 8-byte aligned, joint_flags_dev or NULL, frames, J,
+ *       row_track_dev (frames) i32 or NULL = camera 0 for every frame, num_tracks, cameras_dev (num_tracks, 4) f64, min_joints, roots_dev
+ *       (frames, 3) f64, solved_dev (frames) u8, stream): one launch, one lane per frame.  J > 64: UU3D_ERR_UNSUPPORTED.  frames == 0 is a
+ *       no-op that returns UU3D_OK.  A track id out of range: not solved, nothing is read out of bounds.
+ *   uu3d_root_trajectory_scratch_bytes(frames): two (frames) i32 planes; 0 for arguments out of range (frames < 2^31).
+ *   uu3d_root_trajectory(roots_dev, solved_dev, frames, track_start_dev (num_tracks + 1) i64: track t is given frames [track_start[t],
+ *       track_start[t + 1]), num_tracks, base_dev, wnum_dev, wden_dev, out_frames, out_roots_dev (out_frames, 3) f32, root_state_dev
+ *       (out_frames) u8, scratch_dev 4-byte aligned, scratch_bytes, stream): two segmented scans along the given frames of every track (one
+ *       workgroup per track, the scheme of uu3d_repair_joints: the cost does not depend on the length of a gap), then one lane per returned
+ *       frame.  Two launches.  A plan entry or a scan entry out of range gives NaN and state 0, never a read out of bounds.
+ * Every output element has one writer, no atomics, the caller's memory is only read, nothing copies to the host or waits: bitwise repeatable.
+ */
+int uu3d_solve_roots(const float* poses_dev, const float* kp2d_dev, const uint8_t* joint_flags_dev, int64_t frames, int32_t num_keypoints,
+                     const int32_t* row_track_dev, int32_t num_tracks, const double* cameras_dev, int32_t min_joints, double* roots_dev,
+                     uint8_t* solved_dev, void* stream);
+size_t uu3d_root_trajectory_scratch_bytes(int64_t frames);
+int uu3d_root_trajectory(const double* roots_dev, const uint8_t* solved_dev, int64_t frames, const int64_t* track_start_dev, int32_t num_tracks,
+                         const int64_t* base_dev, const int64_t* wnum_dev, const int64_t* wden_dev, int64_t out_frames, float* out_roots_dev,
+                         uint8_t* root_state_dev, void* scratch_dev, size_t scratch_bytes, void* stream);
+
+/*
  * ANY FRAME RATE (predict.predict_tracks(fps=...)): the front of YOUR OWN 2D TRACKS for tracks that were not filmed at the rate the model
  * was trained for.  The table holds the MODEL's time grid: row `row` (track row_track_dev[row]) is model frame k of its track, which sits at
  * source position p_k = k * fps / model_fps.  The host works the positions out in exact integer arithmetic (predict.resample_plan) and

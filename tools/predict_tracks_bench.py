@@ -13,8 +13,12 @@ to be fast -- run on the host in front of it; the two must agree bit for bit.
 --keypoints NAME [--missing_joints P]: also the same number of tracks in the layout of the preset NAME ("coco17", "body25"), every detector
 joint dropped with probability P (flag 0): predict_tracks(keypoints=NAME, valid=joint flags, repair_joints=G or 5) against the same tracks
 mapped by predict.map_keypoints_host in front of the plain call; the two must agree bit for bit.
+--camera FX FY CX CY: also predict_tracks(camera=...) -- the roots solved and joined on the device -- against the same call without camera
+followed by .cpu() of every pose and predict.solve_roots_host / predict.root_trajectory_host, the rule in numpy (written to be read, not to be
+fast); the two must agree bit for bit.
    python tools/predict_tracks_bench.py [--tracks 40] [--frames 2500] [--batch 512] [--reps 3] [--cases h36m_351:5,h36m_81:4] [--missing 0.3]
-                                        [--fps 30] [--repair_joints 5 --missing_joints 0.1] [--keypoints coco17]"""
+                                        [--fps 30] [--repair_joints 5 --missing_joints 0.1] [--keypoints coco17]
+                                        [--camera 1145 1145 960 540]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -32,6 +36,8 @@ def main():
     ap.add_argument("--repair_joints", type=int, default=None, metavar="G", help="also time predict_tracks(valid=joint flags, repair_joints=G)")
     ap.add_argument("--missing_joints", type=float, default=0.1, metavar="P", help="with --repair_joints: every joint is dropped with probability P")
     ap.add_argument("--keypoints", default=None, metavar="NAME", help="also time predict_tracks(keypoints=NAME) against predict.map_keypoints_host in front")
+    ap.add_argument("--camera", type=float, nargs=4, default=None, metavar=("FX", "FY", "CX", "CY"),
+                    help="also time predict_tracks(camera=...) against .cpu() and the numpy rule behind the plain call")
     args = ap.parse_args()
     import numpy as np, torch
     import uplift_upsample_3dhpe_amd as pkg
@@ -126,6 +132,16 @@ def main():
             return predict.predict_tracks(model, cfg, mapped, resolutions=(W, H), mask_stride=int(msv), flip=True, reuse_frames=reuse, batch_size=args.batch,
                                           valid=mapped_flags, repair_joints=args.repair_joints or 5)
 
+        def camera_path():
+            return predict.predict_tracks(model, cfg, px, resolutions=(W, H), mask_stride=int(msv), flip=True, reuse_frames=reuse, batch_size=args.batch,
+                                          camera=tuple(args.camera))
+
+        def camera_host():
+            poses = np.concatenate([o.cpu().numpy() for o in new_path()], 0)
+            lens = [len(t) for t in px]
+            roots, solved = predict.solve_roots_host(poses, np.concatenate(px, 0), tuple(args.camera), lens=lens)
+            return predict.root_trajectory_host(roots, solved, lens)
+
         row = dict(config=name, mask_stride=int(msv), tracks=args.tracks, frames=total, batch=args.batch, reuse_frames=reuse)
         outs = {}
         cases = [("predict_tracks", new_path), ("predict_tracks_to_host", lambda: new_path(True)), ("composition", composition)]
@@ -141,6 +157,9 @@ def main():
         if kpx is not None:
             row["keypoints"], row["missing_joints"] = args.keypoints, args.missing_joints
             cases += [("predict_tracks_keypoints", keypoints_path), ("host_keypoints", keypoints_host)]
+        if args.camera is not None:
+            row["camera"] = list(args.camera)
+            cases += [("predict_tracks_camera", camera_path), ("host_camera", camera_host)]
         for key, fn in cases:
             fn()
             torch.cuda.synchronize()
@@ -166,6 +185,13 @@ def main():
             row["keypoints_speedup"] = round(row["host_keypoints_ms"] / row["predict_tracks_keypoints_ms"], 3)
             row["keypoints_bits_equal"] = bool(all(torch.equal(a.view(torch.int32), b.view(torch.int32))
                                                    for a, b in zip(outs["predict_tracks_keypoints"], outs["host_keypoints"])))
+        if args.camera is not None:
+            row["camera_speedup"] = round(row["host_camera_ms"] / row["predict_tracks_camera_ms"], 3)
+            row["camera_extra_ms"] = round(row["predict_tracks_camera_ms"] - row["predict_tracks_ms"], 1)
+            roots, state = (torch.cat(x, 0).cpu().numpy() for x in outs["predict_tracks_camera"][1:])
+            row["camera_bits_equal"] = bool(np.array_equal(roots.view(np.uint32), outs["host_camera"][0].view(np.uint32))
+                                            and np.array_equal(state, outs["host_camera"][1]))
+            row["camera_solved_frames"] = int((state == 1).sum())
         row["device"] = torch.cuda.get_device_name(0)
         print(json.dumps(row), flush=True)
         results.append(row)

@@ -43,6 +43,7 @@ EXPORTED_SYMBOLS = (
     "uu3d_stream_repair_bytes", "uu3d_stream_repair_layout", "uu3d_stream_repair_stage", "uu3d_stream_commit_repair", "uu3d_stream_repair_reset",
     "uu3d_keypoint_map_bytes", "uu3d_keypoint_map_pack", "uu3d_map_keypoints",
     "uu3d_associate_state_bytes", "uu3d_associate_reset", "uu3d_associate_detections", "uu3d_stream_associate",
+    "uu3d_solve_roots", "uu3d_root_trajectory_scratch_bytes", "uu3d_root_trajectory",
 )
 # include/uu3d_ops.h
 OPS_SYMBOLS = (
@@ -275,6 +276,13 @@ def load_library(path=None):
     lib.uu3d_associate_detections.argtypes = [apar, vp, vp, vp, i32, vp, i32, i64] + [vp] * 8
     lib.uu3d_stream_associate.restype = C.c_int
     lib.uu3d_stream_associate.argtypes = [apar, vp, vp, vp, vp, i32, vp, vp, i32] + [vp] * 6
+    # absolute root position: the solve per given frame, the trajectory at the returned frames
+    lib.uu3d_solve_roots.restype = C.c_int
+    lib.uu3d_solve_roots.argtypes = [vp, vp, vp, i64, i32, vp, i32, vp, i32, vp, vp, vp]
+    lib.uu3d_root_trajectory_scratch_bytes.restype = sz
+    lib.uu3d_root_trajectory_scratch_bytes.argtypes = [i64]
+    lib.uu3d_root_trajectory.restype = C.c_int
+    lib.uu3d_root_trajectory.argtypes = [vp, vp, i64, vp, i32, vp, vp, vp, i64, vp, vp, vp, sz, vp]
     lib.uu3d_world_to_cam_2d.restype = C.c_int
     lib.uu3d_world_to_cam_2d.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
     lib.uu3d_set_schedule.restype = C.c_int

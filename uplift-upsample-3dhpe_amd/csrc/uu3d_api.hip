@@ -35,6 +35,7 @@
 #include "uu3d_metrics.h"
 #include "uu3d_tracks.h"
 #include "uu3d_repair.h"
+#include "uu3d_root.h"
 #include "uu3d_keypoints.h"
 #include "uu3d_associate.h"
 #include "uu3d_stream.h"
@@ -619,6 +620,46 @@ int uu3d_map_keypoints(uu3d_model* m, const void* map, int32_t inputs, const flo
     hipLaunchKernelGGL(map_keypoints_kernel, dim3((unsigned)((frames * J + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        keypoint_table(map, J), inputs, J, src, flags_in, (long)frames, out, flags_out);
     return hipGetLastError() == hipSuccess ? UU3D_OK : fail(m, UU3D_ERR_HIP, "uu3d_map_keypoints: launch failed");
+}
+
+// ---- ABSOLUTE ROOT POSITION (uu3d_root.h): the solve of every given frame, then the trajectory at the returned frames ----
+int uu3d_solve_roots(const float* poses, const float* kp2d, const uint8_t* joint_flags, int64_t frames, int32_t J, const int32_t* row_track,
+                     int32_t num_tracks, const double* cameras, int32_t min_joints, double* roots, uint8_t* solved, void* stream) {
+    if (J > kRootMaxJoints) return UU3D_ERR_UNSUPPORTED;
+    if (frames < 0 || J < 1 || num_tracks < 1 || min_joints < 2 || frames > (INT64_MAX >> 4) / J || (frames + 255) / 256 > INT32_MAX)
+        return UU3D_ERR_INVALID_ARGUMENT;
+    if (frames == 0) return UU3D_OK;
+    if (!poses || !kp2d || !cameras || !roots || !solved) return UU3D_ERR_INVALID_ARGUMENT;
+    if (((uintptr_t)poses & 3) != 0 || ((uintptr_t)kp2d & 7) != 0 || ((uintptr_t)cameras & 7) != 0 || ((uintptr_t)roots & 7) != 0)
+        return UU3D_ERR_INVALID_ARGUMENT;
+    hipLaunchKernelGGL(solve_roots_kernel, dim3((unsigned)((frames + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       poses, kp2d, joint_flags, (long)frames, J, row_track, num_tracks, cameras, min_joints, roots, solved);
+    return hipGetLastError() == hipSuccess ? UU3D_OK : UU3D_ERR_HIP;
+}
+
+size_t uu3d_root_trajectory_scratch_bytes(int64_t frames) {
+    if (frames < 1 || frames > INT32_MAX) return 0;
+    return (size_t)frames * 2 * sizeof(int32_t);
+}
+
+int uu3d_root_trajectory(const double* roots, const uint8_t* solved, int64_t frames, const int64_t* track_start, int32_t num_tracks,
+                         const int64_t* base, const int64_t* wnum, const int64_t* wden, int64_t out_frames, float* out_roots,
+                         uint8_t* root_state, void* scratch, size_t scratch_bytes, void* stream) {
+    if (!roots || !solved || !track_start || !base || !wnum || !wden || !out_roots || !root_state || !scratch || frames < 1 || num_tracks < 1 ||
+        out_frames < 1)
+        return UU3D_ERR_INVALID_ARGUMENT;
+    if (((uintptr_t)roots & 7) != 0 || ((uintptr_t)out_roots & 3) != 0 || ((uintptr_t)scratch & 3) != 0) return UU3D_ERR_INVALID_ARGUMENT;
+    // frames index the scans as int32; the grid of the last launch stays in range
+    if (frames > INT32_MAX || (out_frames + 255) / 256 > INT32_MAX) return UU3D_ERR_INVALID_ARGUMENT;
+    if (scratch_bytes < uu3d_root_trajectory_scratch_bytes(frames)) return UU3D_ERR_INVALID_ARGUMENT;
+    int32_t* left = static_cast<int32_t*>(scratch);
+    int32_t* right = left + (long)frames;
+    hipLaunchKernelGGL(root_scan_kernel, dim3((unsigned)num_tracks), dim3(kRepairChunk), 0, (hipStream_t)stream,
+                       solved, (long)frames, track_start, left, right);
+    if (hipGetLastError() != hipSuccess) return UU3D_ERR_HIP;
+    hipLaunchKernelGGL(root_trajectory_kernel, dim3((unsigned)((out_frames + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       roots, (long)frames, (const int32_t*)left, (const int32_t*)right, base, wnum, wden, (long)out_frames, out_roots, root_state);
+    return hipGetLastError() == hipSuccess ? UU3D_OK : UU3D_ERR_HIP;
 }
 
 // ---- PER-FRAME DETECTIONS (uu3d_associate.h): the state block, its reset, whole videos, the one frame of a live tick ----

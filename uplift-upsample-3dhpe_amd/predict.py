@@ -24,7 +24,7 @@ synchronises the stream once after the last forward (its pipeline's buffers go a
 
     python -m uplift_upsample_3dhpe_amd.predict --config C --weights W.h5 --input tracks.npz --output out.npz \\
         [--resolution W H] [--mask_stride S] [--keyframes_only] [--mask_missing] [--fps F] [--out_fps F] [--repair_joints G] [--min_score S]
-        [--keypoints NAME]
+        [--keypoints NAME] [--camera FX FY CX CY] [--min_root_joints N]
 
 Per-joint missed detections: ``predict_tracks(..., valid=..., repair_joints=G)`` fills a joint the detector lost for up to G frames by
 linear interpolation between the nearest frames where it was seen (uu3d_repair_joints, in front of the two front kernels above; the rule
@@ -38,9 +38,16 @@ Per-frame detections: ``predict_detections(model, config, detections, counts, va
 per frame a list of people in arbitrary order, (T_v, D, K, 2) per video -- associates people to tracks on the device
 (uu3d_associate_detections; ``associate_detections``; the rule in numpy: ``associate_host`` / ``AssociationHost``: greedy, no motion model,
 S, D, K <= 64) and calls ``predict_tracks`` on the tracks -> per video a list of (track_id, first_frame, poses).
+
+Absolute root position: every pose above is root-relative.  ``predict_tracks(..., camera=(fx, fy, cx, cy))`` also returns, per frame, where
+the skeleton stands in the camera's space: at every given frame the translation that projects the returned pose onto the frame's own 2D
+keypoints (uu3d_solve_roots: linear least squares over the observed joints; ``solve_roots`` is the launch alone; the rule in numpy:
+``solve_roots_host``), joined to a piecewise-linear trajectory that is read at the returned frames (uu3d_root_trajectory;
+``root_trajectory_host``).  ``predict_detections(..., camera=...)`` places every person of a video in the same space.
 """
 import argparse
 import ctypes as C
+from fractions import Fraction
 
 import numpy as np
 
@@ -48,7 +55,8 @@ from . import _capi, evaluation
 from . import eval as ev
 from ._capi import ptr as _ptr
 from .data import PoseTable, SequenceGenerator
-from .rates import _rate_argument, default_mask_stride, frame_rate, frame_rates, output_positions, resample_plan  # noqa: F401 (re-exported)
+from .rates import (_rate_argument, default_mask_stride, frame_rate, frame_rates, given_positions, output_positions,  # noqa: F401 (re-exported)
+                    resample_plan, root_plan)
 
 
 def _upload(a, dtype, device):
@@ -520,12 +528,19 @@ def _map_front(M, model, src, given, valid):
     return out, [f if p else v for p, f, v in zip(per_joint, flags, valid)]
 
 
-def _front_validity(src, given, J, valid, repair):
+def _front_validity(src, given, J, valid, repair, joint_flags=None):
     """What the front kernels take as source and ``valid_in``: as they are, or with ``repair`` = G the repaired source and the frame
-    flags of uu3d_repair_joints -> (src, valid_in, joint state or None)."""
+    flags of uu3d_repair_joints -> (src, valid_in, joint state or None).  ``joint_flags``: ``_source_joint_flags`` where the caller has
+    made them already."""
     if repair is None:
         return src, None if valid is None or isinstance(valid, str) else _device_valid(valid, src.device), None
-    return repair_joints(src, given, repair, None if isinstance(valid, str) else _device_joint_flags(valid, J, src.device))
+    return repair_joints(src, given, repair, _source_joint_flags(valid, J, src.device) if joint_flags is None else joint_flags)
+
+
+def _source_joint_flags(valid, J, device):
+    """``valid`` behind the keypoint map -> the (given frames, J) uint8 per-joint flags on the device, or None where the finite test alone
+    says which joints were observed (None, "finite")."""
+    return None if valid is None or isinstance(valid, str) else _device_joint_flags(valid, J, device)
 
 
 # ---- per-frame detections: people -> tracks (include/uu3d.h, PER-FRAME DETECTIONS) ---------------------------------------------------------
@@ -804,9 +819,14 @@ def predict_detections(model, config, detections, counts=None, valid=None, slots
     The association (``associate_host`` is its rule) runs on the device in one launch; then ONE small copy to the host -- the (frames, D)
     int32 track ids and two counters per video, which say where each track begins and ends -- and the tracks' coordinates and per-joint
     flags are gathered on the device for ``predict_tracks(valid=flags)``.  The result equals ``predict_tracks`` on the tracks of
-    ``association_tracks_host``, bit for bit.  Needs a model with strided input.  Greedy, no motion model: no tracking accuracy is claimed."""
+    ``association_tracks_host``, bit for bit.  Needs a model with strided input.  Greedy, no motion model: no tracking accuracy is claimed.
+    ``camera``: one (fx, fy, cx, cy) or one per VIDEO, handed to ``predict_tracks`` per track the way ``resolutions`` is: the tuples become
+    (track_id, first_frame, poses, roots (n, 3) float32, root_state (n,) uint8) -- every person of a video in the same camera space."""
     import torch
     assoc, options = _association_options(options)
+    camera = options.pop("camera", None)
+    if camera is not None:
+        camera = check_cameras(camera, len(detections), per="video")
     for k in ("keyframes_only", "lengths", "return_valid"):
         if options.get(k):
             raise ValueError(f"predict_detections does not take {k}")
@@ -842,11 +862,199 @@ def predict_detections(model, config, detections, counts=None, valid=None, slots
     res = options.pop("resolutions", None)
     if res is not None:
         res = check_resolutions(res, V, per="video")[[v for v, _, _ in spans]]
+    if camera is not None:
+        options["camera"] = camera[[v for v, _, _ in spans]]
     poses = predict_tracks(model, config, list(torch.split(xy, sizes, 0)), valid=list(torch.split(jf, sizes, 0)), resolutions=res, **options)
     out = [[] for _ in range(V)]
-    for (v, tid, first), p in zip(spans, poses):
-        out[v].append((tid, first, p))
+    for (v, tid, first), *p in zip(spans, *(poses if camera is not None else (poses,))):
+        out[v].append((tid, first, *p))
     return out
+
+
+# ---- absolute root position: every track in the camera's 3D space (include/uu3d.h, ABSOLUTE ROOT POSITION) -----------------------------------
+MAX_ROOT_JOINTS = 64                                                  # kRootMaxJoints
+DEFAULT_MIN_ROOT_JOINTS = 6
+
+
+def check_cameras(camera, count, per="track"):
+    """``camera``: one (fx, fy, cx, cy) or one per track (per video, for ``predict_detections``) -> (count, 4) float64, contiguous.
+    Anything else, a non-finite entry, fx <= 0 or fy <= 0 is a ValueError."""
+    try:
+        c = np.asarray(camera, np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"camera must be one (fx, fy, cx, cy) or one per {per}, got {camera!r}") from None
+    if c.shape == (4,):
+        c = np.tile(c, (int(count), 1))
+    if c.shape != (int(count), 4):
+        raise ValueError(f"camera must be one (fx, fy, cx, cy) or one per {per} ({int(count)}), got shape {c.shape}")
+    if not np.isfinite(c).all() or not (c[:, :2] > 0).all():
+        raise ValueError("camera must be finite (fx, fy, cx, cy) with fx > 0 and fy > 0")
+    return np.ascontiguousarray(c)
+
+
+def check_min_root_joints(min_root_joints):
+    if isinstance(min_root_joints, bool) or not isinstance(min_root_joints, (int, np.integer)) or int(min_root_joints) < 2:
+        raise ValueError(f"min_root_joints must be an int >= 2: the fewest used joints a frame's root is solved from, got {min_root_joints!r}")
+    return int(min_root_joints)
+
+
+def _root_lens(lens, frames):
+    """Frames per track of a root call (None: one track) -> int64 array that adds up to ``frames``."""
+    lens = np.array([int(frames)], np.int64) if lens is None else np.asarray(lens, np.int64).reshape(-1)
+    if (lens < 0).any() or int(lens.sum()) != int(frames):
+        raise ValueError(f"lens must add up to the {int(frames)} frames given")
+    return lens
+
+
+def solve_roots_host(poses, kp2d, camera, flags=None, min_root_joints=DEFAULT_MIN_ROOT_JOINTS, lens=None):
+    """The per-frame rule of ABSOLUTE ROOT POSITION (include/uu3d.h) in numpy, written to be read: what uu3d_solve_roots computes, bit for
+    bit.  ``poses`` (G, J, 3): the 3D pose of every frame, root-relative or not; ``kp2d`` (G, J, 2): the 2D keypoints it was uplifted from,
+    raw, in the model's joint layout; ``camera``: (fx, fy, cx, cy) in the units of ``kp2d``, one or -- with ``lens``, frames per track --
+    one per track; ``flags``: None or (G, J), non-zero = the joint was observed (non-finite coordinates are never used)
+    -> (roots (G, 3) float64, solved (G,) bool); the root of a frame that is not solved is zeros.
+    Everything in float64, every product and sum rounded; the sums run over the used joints in ascending order as a plain loop (np.sum
+    adds pairwise, np.dot in BLAS's order)."""
+    P = np.asarray(_host_array(poses), np.float32)
+    uv = np.asarray(_host_array(kp2d), np.float32)
+    if P.ndim != 3 or P.shape[2] != 3 or uv.shape != P.shape[:2] + (2,):
+        raise ValueError(f"poses must be (G, J, 3) and kp2d (G, J, 2), got {P.shape} and {uv.shape}")
+    G, J = P.shape[:2]
+    m = check_min_root_joints(min_root_joints)
+    lens = _root_lens(lens, G)
+    cam = np.repeat(check_cameras(camera, len(lens)), lens, axis=0)      # (G, 4): the camera of each frame's track
+    fx, fy, cx, cy = cam[:, 0], cam[:, 1], cam[:, 2], cam[:, 3]
+    used = np.isfinite(uv).all(axis=2)
+    if flags is not None:
+        f = np.asarray(_host_array(flags)) != 0
+        if f.shape != (G, J):
+            raise ValueError(f"flags must be ({G}, {J}), got {f.shape}")
+        used &= f
+    P64, uv64 = P.astype(np.float64), uv.astype(np.float64)
+    n = np.zeros(G, np.int64)
+    Sa, Sb, Sq, Sp, Sk, Sr = (np.zeros(G, np.float64) for _ in range(6))
+    with np.errstate(all="ignore"):
+        for j in range(J):
+            X, Y, Z = P64[:, j, 0], P64[:, j, 1], P64[:, j, 2]
+            a = (uv64[:, j, 0] - cx) / fx
+            b = (uv64[:, j, 1] - cy) / fy
+            p = a * Z - X
+            q = b * Z - Y
+            u = used[:, j]
+            n += u
+            Sa = np.where(u, Sa + a, Sa)
+            Sb = np.where(u, Sb + b, Sb)
+            Sq = np.where(u, Sq + (a * a + b * b), Sq)
+            Sp = np.where(u, Sp + p, Sp)
+            Sk = np.where(u, Sk + q, Sk)
+            Sr = np.where(u, Sr + (a * p + b * q), Sr)
+        nd = n.astype(np.float64)
+        den = Sq - (Sa * Sa + Sb * Sb) / nd
+        num = (Sa * Sp + Sb * Sk) / nd - Sr
+        Tz = num / den
+        Tx = (Sp + Sa * Tz) / nd
+        Ty = (Sk + Sb * Tz) / nd
+        solved = (n >= m) & (den > 0) & np.isfinite(Tx) & np.isfinite(Ty) & np.isfinite(Tz) & (Tz > 0)
+        for j in range(J):                                            # every used joint in front of the camera
+            solved &= ~used[:, j] | (P64[:, j, 2] + Tz > 0)
+    roots = np.zeros((G, 3), np.float64)
+    roots[solved] = np.stack([Tx, Ty, Tz], axis=1)[solved]
+    return roots, solved
+
+
+def root_trajectory_host(roots, solved, lens=None, positions=None):
+    """The trajectory rule of ABSOLUTE ROOT POSITION in numpy, written to be read: what uu3d_root_trajectory computes, bit for bit.
+    ``roots`` (G, 3) float64 and ``solved`` (G,) of ``solve_roots_host``, the given frames of all tracks back to back, ``lens`` of them
+    per track (None: one track); ``positions``: (track, num, den) of ``given_positions`` -- returned frame i sits at given-frame position
+    num / den of its track -- or None: every given frame itself -> (roots (R, 3) float32, root_state (R,) uint8: 1 solved here, 2
+    interpolated or held, 0 the track has no solved frame).  Nothing crosses a track boundary."""
+    roots = np.asarray(roots, np.float64).reshape(-1, 3)
+    solved = np.asarray(solved).reshape(-1) != 0
+    lens = _root_lens(lens, len(roots))
+    start = np.concatenate([[0], np.cumsum(lens)])
+    if positions is None:
+        positions = given_positions(lens)
+    base, _, _ = root_plan(lens, positions)                             # (the range checks of the device call)
+    out = np.zeros((len(base), 3), np.float32)
+    state = np.zeros(len(base), np.uint8)
+    for i, (t, num, den) in enumerate(zip(*(np.asarray(a).tolist() for a in positions))):
+        seen = np.flatnonzero(solved[start[t]:start[t + 1]])          # the track's solved frames, by their index in the track
+        b = num // den
+        before, after = seen[seen <= b], seen[seen > b]
+        L = int(before[-1]) if len(before) else None
+        R = int(after[0]) if len(after) else None
+        if L == b and num == b * den:
+            out[i], state[i] = roots[start[t] + L].astype(np.float32), 1
+        elif L is not None and R is not None:
+            w = np.float64(num - L * den) / np.float64((R - L) * den)
+            out[i], state[i] = (roots[start[t] + L] * (1.0 - w) + roots[start[t] + R] * w).astype(np.float32), 2
+        elif L is not None or R is not None:
+            out[i], state[i] = roots[start[t] + (L if L is not None else R)].astype(np.float32), 2
+    return out, state
+
+
+def solve_roots(poses, kp2d, camera, flags=None, min_root_joints=DEFAULT_MIN_ROOT_JOINTS, lens=None):
+    """uu3d_solve_roots on the current stream: ``solve_roots_host`` on device tensors, one launch, nothing copies to the host or waits.
+    ``poses`` (G, J, 3) float32 and ``kp2d`` (G, J, 2) float32 on the device, contiguous (only read); ``camera``: (fx, fy, cx, cy), one or
+    one per track with ``lens`` (frames per track); ``flags`` (G, J) uint8 / bool on the device or None
+    -> (roots (G, 3) float64, solved (G,) bool), fresh device buffers.  ``poses + roots[:, None]`` stands in the camera's space.
+    The live form: a ``StreamSession`` push returns one pose per slot; ``solve_roots`` on those poses and the frame that was pushed places
+    each of them at ``lookahead=0`` (with a lookahead the pose belongs to an earlier frame: a ring of raw frames is a follow-up)."""
+    import torch
+    lib = _capi.load_library()
+    dev = poses.device
+    if poses.dim() != 3 or poses.shape[2] != 3 or poses.dtype != torch.float32 or not poses.is_contiguous() or not poses.is_cuda:
+        raise ValueError(f"poses must be a contiguous (G, J, 3) float32 device tensor, got {tuple(poses.shape)}")
+    G, J = int(poses.shape[0]), int(poses.shape[1])
+    if tuple(kp2d.shape) != (G, J, 2) or kp2d.dtype != torch.float32 or not kp2d.is_contiguous() or kp2d.device != dev:
+        raise ValueError(f"kp2d must be a contiguous ({G}, {J}, 2) float32 tensor on the poses' device, got {tuple(kp2d.shape)}")
+    if flags is not None:
+        if tuple(flags.shape) != (G, J) or flags.dtype not in (torch.uint8, torch.bool) or not flags.is_contiguous() or flags.device != dev:
+            raise ValueError(f"flags must be a contiguous ({G}, {J}) uint8 or bool tensor on the poses' device")
+        flags = flags.view(torch.uint8)
+    m = check_min_root_joints(min_root_joints)
+    lens = _root_lens(lens, G)
+    cams = _upload(check_cameras(camera, len(lens)), np.float64, dev)
+    row_track = None if len(lens) == 1 else _upload(np.repeat(np.arange(len(lens), dtype=np.int32), lens), np.int32, dev)
+    roots = torch.empty((G, 3), dtype=torch.float64, device=dev)
+    solved = torch.empty((G,), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _capi.check(lib, lib.uu3d_solve_roots(_ptr(poses), _ptr(kp2d), _ptr(flags), G, J, _ptr(row_track), len(lens), _ptr(cams), m, _ptr(roots),
+                                              _ptr(solved), C.c_void_p(stream)), None)
+    return roots, solved.view(torch.bool)
+
+
+def root_trajectory(roots, solved, lens=None, positions=None):
+    """uu3d_root_trajectory on the current stream: ``root_trajectory_host`` on the device tensors of ``solve_roots``; the plan
+    (``root_plan``) is made on the host in exact integers and goes up pinned and asynchronously -> (roots (R, 3) float32, root_state (R,)
+    uint8), fresh device buffers."""
+    import torch
+    lib = _capi.load_library()
+    dev = roots.device
+    G = int(roots.shape[0])
+    if tuple(roots.shape) != (G, 3) or roots.dtype != torch.float64 or not roots.is_contiguous() or not roots.is_cuda or G < 1:
+        raise ValueError(f"roots must be a contiguous (G, 3) float64 device tensor, got {tuple(roots.shape)}")
+    if tuple(solved.shape) != (G,) or solved.dtype not in (torch.uint8, torch.bool) or not solved.is_contiguous() or solved.device != dev:
+        raise ValueError(f"solved must be a contiguous ({G},) uint8 or bool tensor on the roots' device")
+    lens = _root_lens(lens, G)
+    base, wnum, wden = root_plan(lens, positions)
+    R = len(base)
+    if R < 1:
+        raise ValueError("no returned frames")
+    track_start = _upload(np.concatenate([[0], np.cumsum(lens)]), np.int64, dev)
+    d_plan = _upload(np.stack([base, wnum, wden]), np.int64, dev)
+    out = torch.empty((R, 3), dtype=torch.float32, device=dev)
+    state = torch.empty((R,), dtype=torch.uint8, device=dev)
+    nbytes = int(lib.uu3d_root_trajectory_scratch_bytes(G))
+    if nbytes == 0:
+        raise ValueError(f"{G} given frames are out of uu3d_root_trajectory's range")
+    scratch = torch.empty((nbytes // 4,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _capi.check(lib, lib.uu3d_root_trajectory(_ptr(roots), _ptr(solved.view(torch.uint8)), G, _ptr(track_start), len(lens), _ptr(d_plan[0]),
+                                                  _ptr(d_plan[1]), _ptr(d_plan[2]), R, _ptr(out), _ptr(state), _ptr(scratch), nbytes,
+                                                  C.c_void_p(stream)), None)
+    return out, state
 
 
 def _device_tracks(tracks, device):
@@ -872,12 +1080,14 @@ def check_resolutions(resolutions, count, per="track"):
     return np.ascontiguousarray(r)
 
 
-def pose_table(tracks, device, resolutions=None, key_stride=0, lengths=None, valid=None, repair_joints=None, keypoints=None, model=None):
+def pose_table(tracks, device, resolutions=None, key_stride=0, lengths=None, valid=None, repair_joints=None, keypoints=None, model=None,
+               keep_source=False):
     """The dense, normalised ``data.PoseTable`` of the tracks (uu3d_normalize_tracks) -> (table, frames per track).  ``valid`` as in
     ``predict_tracks`` (not None: uu3d_normalize_tracks_valid into a fresh buffer; the table carries the per-frame flags).
     ``repair_joints`` = G: uu3d_repair_joints runs on the given frames first; ``table.joint_state`` is its (given frames, J) uint8 state.
     ``keypoints``: a ``KeypointMap`` or a preset's name (with ``model``): the tracks are (T_i, K_in, 2), per-joint entries of ``valid``
-    (T_i, K_in), and uu3d_map_keypoints runs in front of all of that (``_map_front``)."""
+    (T_i, K_in), and uu3d_map_keypoints runs in front of all of that (``_map_front``).  ``keep_source``: ``table.source`` = (the given
+    frames (R, J, 2) raw in the model's layout, their (R, J) uint8 joint flags or None) as the root solve reads them."""
     import torch
     check_repair_joints(repair_joints, valid)
     tr, J, given = _device_tracks(tracks, device)
@@ -902,8 +1112,9 @@ def pose_table(tracks, device, resolutions=None, key_stride=0, lengths=None, val
     if keypoints is not None:
         (src, valid), J = _map_front(keypoints, model, src, given, valid), keypoints.joints
     flags = state = None
+    source = (src, _source_joint_flags(valid, J, src.device)) if keep_source else None
     if valid is not None:
-        src, valid_in, state = _front_validity(src, given, J, valid, repair_joints)
+        src, valid_in, state = _front_validity(src, given, J, valid, repair_joints, None if source is None else source[1])
         kp = torch.empty((int(lens.sum()), J, 2), dtype=torch.float32, device=src.device)      # (never in the caller's own memory)
         flags = torch.empty((int(lens.sum()),), dtype=torch.uint8, device=src.device)
         normalize_tracks(src, kp, lens, resolutions, key_stride, given, valid_in=valid_in, valid_out=flags)
@@ -913,15 +1124,17 @@ def pose_table(tracks, device, resolutions=None, key_stride=0, lengths=None, val
     else:
         kp = src
     table = PoseTable.from_device(kp, lens, valid=flags)
-    table.joint_state = state
+    table.joint_state, table.source = state, source
     return table, lens
 
 
-def resampled_pose_table(tracks, device, fps, resolutions=None, valid=None, model_fps=50, repair_joints=None, keypoints=None, model=None):
+def resampled_pose_table(tracks, device, fps, resolutions=None, valid=None, model_fps=50, repair_joints=None, keypoints=None, model=None,
+                         keep_source=False):
     """``pose_table`` for tracks at ``fps`` frames per second: the dense, normalised table on the MODEL's time grid (``resample_plan``,
     uu3d_resample_tracks; always a fresh buffer) -> (table, model frames per track, source frames per track).  With ``valid`` the table
     carries one flag per model frame.  ``repair_joints`` = G: uu3d_repair_joints runs on the source frames first; ``table.joint_state`` is
-    its (source frames, J) uint8 state.  ``keypoints`` / ``model`` as ``pose_table``: the map runs on the source frames, in front of the rest."""
+    its (source frames, J) uint8 state.  ``keypoints`` / ``model`` / ``keep_source`` as ``pose_table``: the map runs on the source frames, in
+    front of the rest."""
     import torch
     check_repair_joints(repair_joints, valid)
     tr, J, lens = _device_tracks(tracks, device)
@@ -938,16 +1151,17 @@ def resampled_pose_table(tracks, device, fps, resolutions=None, valid=None, mode
         (src, valid), J = _map_front(keypoints, model, src, lens, valid), keypoints.joints
     kp = torch.empty((int(model_lens.sum()), J, 2), dtype=torch.float32, device=src.device)
     flags = None if valid is None else torch.empty((int(model_lens.sum()),), dtype=torch.uint8, device=src.device)
-    src, valid_in, state = _front_validity(src, lens, J, valid, repair_joints)
+    source = (src, _source_joint_flags(valid, J, src.device)) if keep_source else None
+    src, valid_in, state = _front_validity(src, lens, J, valid, repair_joints, None if source is None else source[1])
     resample_tracks(src, kp, model_lens, left, right, weight, resolutions, valid_in=valid_in, valid_out=flags)
     table = PoseTable.from_device(kp, model_lens, valid=flags)
-    table.joint_state = state
+    table.joint_state, table.source = state, source
     return table, model_lens, lens
 
 
 def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, flip=None, keyframes_only=False, reuse_frames=True,
                    batch_size=None, root_relative=True, depth=None, lengths=None, graph=True, valid=None, return_valid=False, fps=None, out_fps=None,
-                   model_fps=50, repair_joints=None, keypoints=None):
+                   model_fps=50, repair_joints=None, keypoints=None, camera=None, min_root_joints=DEFAULT_MIN_ROOT_JOINTS):
     """One 3D pose per frame for each 2D keypoint track -> list of (T_i, J, 3) float32 tensors on the model's device (views of one buffer).
 
     ``tracks``: list of (T_i, J, 2) arrays or tensors, on the host or the device, at the frame rate the config was trained for (nothing is
@@ -1017,8 +1231,31 @@ def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, fl
     entries of ``valid`` are (T_i, K_in), one flag (``scores >= 0.3``) per DETECTOR joint, and "finite" is the finite test per source joint:
     a model joint is observed iff every one of its sources is, and an unobserved one is zeros with flag 0 -- a lost COCO shoulder is a
     lost neck and a lost torso, and nothing else; (T_i,) frame flags pass through.  ``joint_state`` stays per model joint.  The result
-    equals, bit for bit, ``predict_tracks(mapped, valid=flags)`` with the output of ``map_keypoints_host``, the rule in numpy."""
+    equals, bit for bit, ``predict_tracks(mapped, valid=flags)`` with the output of ``map_keypoints_host``, the rule in numpy.
+
+    Absolute root position -- ``camera``: None = today's call, the same bits, no further launch or buffer.  Else the camera's intrinsics
+    (fx, fy, cx, cy), no distortion, in the units of the tracks AS GIVEN (pixels when ``resolutions`` is given), one tuple or one per track
+    (non-finite, fx <= 0 or fy <= 0: ValueError): ``roots``, a list of (T_i, 3) float32 device tensors (views of one buffer), and
+    ``root_state``, a list of (T_i,) uint8 ones, are APPENDED to whatever the call returns -- (poses, roots, root_state), (poses, flags,
+    roots, root_state) or (poses, flags, joint_state, roots, root_state); the poses are those of the call without ``camera``, bit for bit,
+    and ``poses[i] + roots[i][:, None]`` stands in the camera's space.  At every GIVEN frame the root is where the returned pose must stand
+    so that it projects onto the frame's 2D keypoints: linear least squares over the USED joints -- the joint's flag is set (after the
+    ``keypoints`` map; ``valid=None``: all of them) and both raw coordinates are finite; with ``repair_joints`` a filled joint is not used
+    (an interpolation, not a measurement), and a frame the network never saw still fixes its root from the joints that were seen.  A frame
+    is SOLVED with at least ``min_root_joints`` (an int >= 2) used joints that do not share one pixel, a finite root with Tz > 0 and every
+    used joint in front of the camera (uu3d_solve_roots; the rule in numpy: ``solve_roots_host``).  The root motion is the
+    piecewise-linear function through a track's solved given frames, read at the times of the returned frames -- frame i at given-frame
+    position i (plain, ``fps``), i / s_in (``keyframes_only``) or i fps / out_fps (with ``out_fps``; the poses at the given frames' times
+    then come from a second uu3d_assemble_tracks over the same raw predictions, no further forward) -- and held before the first and
+    behind the last solved frame (uu3d_root_trajectory; ``root_trajectory_host``).  ``root_state``: 1 solved here, 2 interpolated or held,
+    0 the track has no solved frame (zeros).  With ``root_relative=False`` the solve takes the pose as returned.  No accuracy is claimed:
+    the model's scale error goes 1:1 into the depth.  ``StreamSession`` and ``replay_tracks`` have no such option: ``solve_roots`` on a
+    push's poses and that push's frame is the live form at ``lookahead=0``; a lookahead ring of raw frames is a follow-up."""
     import torch
+    if camera is not None:
+        cameras, min_root_joints = check_cameras(camera, len(tracks)), check_min_root_joints(min_root_joints)
+        if int(config.NUM_KEYPOINTS) > MAX_ROOT_JOINTS:
+            raise ValueError(f"camera needs a model of at most {MAX_ROOT_JOINTS} joints, this one has {int(config.NUM_KEYPOINTS)}")
     if keypoints is not None:
         keypoints = keypoint_map(keypoints, config.NUM_KEYPOINTS)
         check_keypoint_inputs(keypoints, [_shape(t)[1] if len(_shape(t)) == 3 else -1 for t in tracks])
@@ -1041,12 +1278,13 @@ def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, fl
         raise ValueError("keyframes_only needs a mask stride")
     if fps is None:
         table, lens = pose_table(tracks, dev, resolutions, int(mask_stride) if keyframes_only else 0, lengths, valid=valid,
-                                 repair_joints=repair_joints, keypoints=keypoints, model=model)
+                                 repair_joints=repair_joints, keypoints=keypoints, model=model, keep_source=camera is not None)
         model_lens = lens
     else:
         rates = frame_rates(fps, len(tracks))
         table, model_lens, src_lens = resampled_pose_table(tracks, dev, rates, resolutions, valid=valid, model_fps=model_fps,
-                                                           repair_joints=repair_joints, keypoints=keypoints, model=model)
+                                                           repair_joints=repair_joints, keypoints=keypoints, model=model,
+                                                           keep_source=camera is not None)
         lens, positions = output_positions(src_lens, rates, rates if out_fps is None else out_fps, model_fps)
     gen = SequenceGenerator(table, seq_len=cfg.SEQUENCE_LENGTH, target_frame_rate=50, subsample=1, stride=cfg.SEQUENCE_STRIDE,
                             padding_type=cfg.PADDING_TYPE, flip_augment=False, flip_lr_indices=cfg.AUGM_FLIP_KEYPOINT_ORDER,
@@ -1069,13 +1307,31 @@ def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, fl
     out = assemble_tracks(raw[0], raw[1] if flip else None, left, right, weight, flip_order=cfg.AUGM_FLIP_KEYPOINT_ORDER,
                           root=int(cfg.ROOT_KEYTPOINT) if root_relative else -1)
     poses = list(torch.split(out, [int(n) for n in lens], 0))
+    placed = ()
+    if camera is not None:
+        given = np.array([len(t) for t in tracks], np.int64)
+        at_given, where = out, None                                   # a returned frame is a given frame: the plain call, fps alone
+        if keyframes_only:                                            # given keyframe g is returned frame g s_in
+            first = np.concatenate([[0], np.cumsum(lens)[:-1]])
+            picks = np.concatenate([f + np.arange(n, dtype=np.int64) * int(mask_stride) for f, n in zip(first, given)])
+            at_given = out.index_select(0, _upload(picks, np.int64, out.device))
+            where = given_positions(lens, [Fraction(1, int(mask_stride))] * len(given))
+        elif out_fps is not None:                                     # the same motion read once more, at the given frames' times
+            _, at = output_positions(src_lens, rates, rates, model_fps)
+            at_given = assemble_tracks(raw[0], raw[1] if flip else None, *evaluation.keyframe_plan_at(frame_idx, 1 if stride is None else stride, at, rows=rows),
+                                       flip_order=cfg.AUGM_FLIP_KEYPOINT_ORDER, root=int(cfg.ROOT_KEYTPOINT) if root_relative else -1)
+            where = given_positions(lens, [f / o for f, o in zip(rates, frame_rates(out_fps, len(given)))])
+        solved_roots, solved = solve_roots(at_given, table.source[0], cameras, table.source[1], min_root_joints, lens=given)
+        roots, root_state = root_trajectory(solved_roots, solved, given, where)
+        sizes = [int(n) for n in lens]
+        placed = (list(torch.split(roots, sizes, 0)), list(torch.split(root_state, sizes, 0)))
     if not return_valid:
-        return poses
+        return (poses,) + placed if placed else poses
     flags = table.valid.view(torch.bool) if table.valid is not None else torch.ones((int(model_lens.sum()),), dtype=torch.bool, device=out.device)
     flags = list(torch.split(flags, [int(n) for n in model_lens], 0))
     if repair_joints is None:
-        return poses, flags
-    return poses, flags, list(torch.split(table.joint_state, [int(len(t)) for t in tracks], 0))
+        return (poses, flags) + placed
+    return (poses, flags, list(torch.split(table.joint_state, [int(len(t)) for t in tracks], 0))) + placed
 
 
 def padding_source_is_keyframe(length, config, mask_stride):
@@ -1119,6 +1375,11 @@ def parse_args(argv=None):
     p.add_argument("--keypoints", default=None, metavar="NAME", choices=sorted(KEYPOINT_PRESETS),
                    help="the joint layout of the arrays, (T, K, 2): mapped onto the model's joints on the device; --min_score then reads the "
                         "score channel of (T, K, 3) arrays, one score per detector joint")
+    p.add_argument("--camera", type=float, nargs=4, metavar=("FX", "FY", "CX", "CY"), default=None,
+                   help="the camera's intrinsics in the units of the arrays (pixels with --resolution): the output gains <key>__root (T, 3), the "
+                        "position of the skeleton's root in the camera's space, and <key>__root_state (T,) per track")
+    p.add_argument("--min_root_joints", type=int, default=DEFAULT_MIN_ROOT_JOINTS, metavar="N",
+                   help="the fewest observed joints a frame's root is solved from (with --camera)")
     return p.parse_args(argv)
 
 
@@ -1173,9 +1434,24 @@ def main(argv=None):
         missing = {"valid": "finite"}
     if args.repair_joints is not None:
         missing["repair_joints"] = args.repair_joints
+    place = {}
+    if args.camera is not None:
+        try:
+            check_cameras(tuple(args.camera), 1), check_min_root_joints(args.min_root_joints)
+        except ValueError as e:
+            raise SystemExit(f"--camera: {e}") from None
+        if any(k.endswith(("__root", "__root_state")) for k in names):
+            raise SystemExit(f"{args.input}: a key ending in __root or __root_state would collide with the arrays --camera writes")
+        place = {"camera": tuple(args.camera), "min_root_joints": args.min_root_joints}
     poses = predict_tracks(model, config, tracks, resolutions=None if args.resolution is None else tuple(args.resolution), mask_stride=ms,
-                           keyframes_only=args.keyframes_only, lengths=lengths, **missing, **rate, **skeleton)
-    np.savez(args.output, **{k: np.asarray(p.detach().cpu().numpy(), np.float32) for k, p in zip(names, poses)})
+                           keyframes_only=args.keyframes_only, lengths=lengths, **missing, **rate, **skeleton, **place)
+    arrays = {}
+    if place:
+        poses, roots, root_state = poses
+        arrays.update({k + "__root": r.detach().cpu().numpy() for k, r in zip(names, roots)})
+        arrays.update({k + "__root_state": r.detach().cpu().numpy() for k, r in zip(names, root_state)})
+    arrays.update({k: np.asarray(p.detach().cpu().numpy(), np.float32) for k, p in zip(names, poses)})
+    np.savez(args.output, **arrays)
     print(f"wrote {args.output}: {len(names)} tracks, {sum(int(p.shape[0]) for p in poses)} frames", flush=True)
     return 0
 

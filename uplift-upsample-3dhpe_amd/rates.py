@@ -112,6 +112,47 @@ def output_positions(lens, fps, out_fps, model_fps=50):
     return np.array(out_lens, np.int64), (np.concatenate(track), np.concatenate(num), np.concatenate(den))
 
 
+def given_positions(out_lens, steps=None):
+    """Where the frames a call returns lie among the frames it was GIVEN, for the root trajectory of ``predict_tracks(camera=...)`` ->
+    (track, num, den) int64 arrays, one entry per returned frame: frame i of track t sits at given-frame position i * steps[t] = num / den.
+    ``steps``: None (a returned frame is a given frame: the plain call, ``fps`` alone) or one exact rate per track as ``frame_rates`` takes
+    them -- ``Fraction(1, s_in)`` with ``keyframes_only``, ``fps / out_fps`` with an output rate."""
+    out_lens = np.asarray(out_lens, np.int64).reshape(-1)
+    steps = [Fraction(1)] * len(out_lens) if steps is None else frame_rates(steps, len(out_lens))
+    track, num, den = [], [], []
+    for t, (n, q) in enumerate(zip((int(n) for n in out_lens), steps)):
+        if max(n * q.numerator, q.denominator) >= 2 ** 53:
+            raise ValueError(f"track {t}: {n} returned frames {q} given frames apart: the positions' integers must stay below 2^53")
+        track.append(np.full(n, t, np.int64))
+        num.append(np.arange(n, dtype=np.int64) * q.numerator)
+        den.append(np.full(n, q.denominator, np.int64))
+    return np.concatenate(track), np.concatenate(num), np.concatenate(den)
+
+
+def root_plan(given, positions=None):
+    """The host plan of uu3d_root_trajectory -> (base, wnum, wden) int64 arrays, one entry per returned frame: ``base`` the GLOBAL row (all
+    tracks' given frames back to back) of the given frame at or before the position, ``wnum / wden`` the fraction behind it, 0 <= wnum <
+    wden.  ``given``: given frames per track; ``positions``: (track, num, den) of ``given_positions`` (None: every given frame itself).
+    Exact integer arithmetic.  ValueError: a position whose whole part lies behind its track's last given frame, or a track's given
+    frames times a denominator reaching 2^53 -- the weight's two integers, (base - L) wden + wnum and (R - L) wden, stay below it."""
+    given = np.asarray(given, np.int64).reshape(-1)
+    if (given < 1).any():
+        raise ValueError("every track needs at least one given frame")
+    start = np.concatenate([[0], np.cumsum(given)[:-1]])
+    if positions is None:
+        rows = np.arange(int(given.sum()), dtype=np.int64)
+        return rows, np.zeros_like(rows), np.ones_like(rows)
+    track, num, den = (np.asarray(a, np.int64).reshape(-1) for a in positions)
+    if not (len(track) == len(num) == len(den)) or (track < 0).any() or (track >= len(given)).any() or (den < 1).any() or (num < 0).any():
+        raise ValueError("positions must be (track, num, den) with one entry per returned frame, num >= 0 and den >= 1")
+    if ((given[track].astype(object) * den.astype(object)) >= 2 ** 53).any():
+        raise ValueError("given frames times a position's denominator must stay below 2^53")
+    floor = num // den
+    if (floor >= given[track]).any():
+        raise ValueError("a returned frame lies behind its track's last given frame")
+    return start[track] + floor, num - floor * den, den
+
+
 def default_mask_stride(config):
     """The mask stride a call takes when none is given: the config's first MASK_STRIDE (None: the config has none)."""
     return config.MASK_STRIDE[0] if isinstance(config.MASK_STRIDE, (list, tuple)) else config.MASK_STRIDE
