@@ -814,6 +814,43 @@ int uu3d_stream_repair_reset(uu3d_model* model, const uu3d_stream_config* cfg, i
                              const uint8_t* slot_mask_dev, void* stream);
 
 /*
+ * LIVE ABSOLUTE ROOT (stream.StreamSession(camera=...); stream.LiveRootHost is the same rule in numpy, bit for bit): ABSOLUTE ROOT POSITION
+ * for LIVE TRACKS.  Every push returns, beside each slot's pose, where that pose stands in the camera's space.  With a lookahead the pose
+ * belongs to an earlier frame than the one pushed, so the session keeps the raw 2D it will need.  No model: the calls take the joint count,
+ * like uu3d_solve_roots, and run on any pose / fresh / counter buffers.  No accuracy is claimed (ABSOLUTE ROOT POSITION).
+ * STATE per slot, in one caller-allocated block of uu3d_stream_root_bytes(slots, J, lookahead) bytes, 256-byte aligned, zeroed by
+ * uu3d_stream_root_reset: a ring of the last W = lookahead + 1 raw frames in the model's joint layout (frame f at place f % W) with one
+ * USED byte per joint, the last solved root (3 f64), and the state the slot returned last -- non-zero: a solved root exists.
+ * THE RULE.  frames_dev (slots) i32 holds each slot's frame counter AFTER this push (uu3d_stream_commit has advanced it; a session with a
+ * frame rate passes its source counters): the pushed frame is t = frames - 1.
+ *   filing   active_dev[slot] != 0 (and frames >= 1): joint j of kp2d_dev (slots, J, 2) f32 -- the frame as pushed, behind
+ *            uu3d_map_keypoints, before any normalisation or repair -- goes to place t % W.  USED iff its flag is set and both
+ *            coordinates are finite; flags_dev: NULL (no flags), (slots) u8 with flags_per_joint == 0 (a frame's flag stands for all of its
+ *            joints) or (slots, J) u8.  A joint that a repair fills is not flagged, hence never used; no later push revises the ring.
+ *   solving  active and fresh_dev[slot] != 0: poses_dev (slots, J, 3) f32, the pose the push returns, is solved against frame
+ *            c = t - lookahead by the per-frame rule of ABSOLUTE ROOT POSITION, unchanged (cameras_dev (slots, 4) f64, min_joints >= 2).
+ *            Solved: roots_dev (slots, 3) f32 = the root rounded once, root_state_dev (slots) u8 = 1, and the root is held.  Not solved
+ *            (or c < 0): the held root, state 2; no held root yet: zeros, state 0.  The rule is causal: it holds the last solved root and
+ *            cannot interpolate towards a later solved frame as uu3d_root_trajectory does, because no later pose exists yet.
+ *   any other slot (inactive, or not fresh) returns what it returned last, bit for bit, and nothing of its state changes.
+ *
+ *   uu3d_stream_root_bytes(slots, J, lookahead): 0 for arguments out of range (slots in [1, 2^20], J in [1, 64], lookahead in [0, 2^24]).
+ *   uu3d_stream_root(slots, J, lookahead, root_state_dev, frames_dev, active_dev, fresh_dev, poses_dev, kp2d_dev 8-byte aligned, flags_dev,
+ *       flags_per_joint, cameras_dev, min_joints, roots_dev, root_state_out_dev, stream): one launch, one wave per slot -- lane j files joint
+ *       j, lane 0 solves.  J > 64: UU3D_ERR_UNSUPPORTED.
+ *   uu3d_stream_root_reset(slots, J, lookahead, root_state_dev, slot_mask_dev (slots) u8 or NULL = every slot, stream): the chosen slots
+ *       have no filed frame, no held root and state 0; beside uu3d_stream_reset, with the same mask (host-made or written on the device).
+ * Every output and state element has one writer, no atomics, the caller's buffers are only read: bitwise repeatable, capturable.
+ */
+size_t uu3d_stream_root_bytes(int32_t slots, int32_t num_keypoints, int32_t lookahead);
+int uu3d_stream_root(int32_t slots, int32_t num_keypoints, int32_t lookahead, void* root_state_dev, const int32_t* frames_dev,
+                     const uint8_t* active_dev, const uint8_t* fresh_dev, const float* poses_dev, const float* kp2d_dev, const uint8_t* flags_dev,
+                     int32_t flags_per_joint, const double* cameras_dev, int32_t min_joints, float* roots_dev, uint8_t* root_state_out_dev,
+                     void* stream);
+int uu3d_stream_root_reset(int32_t slots, int32_t num_keypoints, int32_t lookahead, void* root_state_dev, const uint8_t* slot_mask_dev,
+                           void* stream);
+
+/*
  * Per-kernel timing of the next uu3d_forward calls with HIP events on the launch stream.
  * When enabled, uu3d_forward records an event pair around every launch; uu3d_profile_read
  * synchronises those events and returns the per-launch records of the LAST forward.

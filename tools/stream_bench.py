@@ -4,6 +4,7 @@ uploads them with their mirrored copies and calls ``model([x, mask])`` once -- t
 A tick = host clock from the call to the synchronised result (a live consumer reads every pose); host input in all three variants.
 Median (and 90th percentile) over --ticks ticks after --warmup ticks, per config and slot count.
    python tools/stream_bench.py [--slots 1,8,64] [--cases h36m_81:4,h36m_351:5] [--ticks 300] [--warmup 60] [--lookahead 0] [--fps F [--out_fps G]]
+                                [--repair_joints G] [--detections D] [--camera FX FY CX CY]
 --fps F (a float or NUM/DEN): microseconds per PUSH of StreamSession(fps=F) -- one source frame in, one pose out, on average
 model_fps / F sub-ticks -- next to the plain session pushed at the model's rate (the cost of one model tick); the lookahead is raised to
 the smallest one the rate allows.  The numpy baseline is left out.
@@ -17,7 +18,11 @@ baseline is left out.
 the tick of StreamSession(detections=D) fed the lists (det_graph_us) next to the tick of StreamSession(missed_detections=True) on the same
 frames in the same process, fed what predict.associate_host makes of them, worked out before the clock starts (md_graph_us), and next to
 the HOST ROUTE a user takes without the option (host_route_us): the detections start on the device, are copied back, matched in numpy
-(predict.AssociationHost), reset() is called for the slots born, then push().  The numpy baseline is left out."""
+(predict.AssociationHost), reset() is called for the slots born, then push().  The numpy baseline is left out.
+--camera FX FY CX CY (not with the options above): the tick of StreamSession(camera=...) -- one more launch at the end of the captured
+tick, two more buffers returned -- as camera_graph_us next to the tick of the same session without camera (graph_us) on the same frames in
+the same process: both sessions are alive side by side and every tick is pushed into both, the order alternating from tick to tick.
+camera_minus_graph_us is the difference of the two medians.  The numpy baseline is left out."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -34,7 +39,10 @@ def main():
     ap.add_argument("--repair_joints", type=int, default=None)
     ap.add_argument("--missing_joints", type=float, default=0.1)
     ap.add_argument("--detections", type=int, default=None)
+    ap.add_argument("--camera", type=float, nargs=4, metavar=("FX", "FY", "CX", "CY"), default=None)
     args = ap.parse_args()
+    if args.camera is not None and (args.fps is not None or args.repair_joints is not None or args.detections is not None):
+        ap.error("--camera is not measured together with --fps / --repair_joints / --detections")
     if args.repair_joints is not None and args.fps is not None:
         ap.error("--repair_joints is not measured together with --fps")
     if args.detections is not None and (args.fps is not None or args.repair_joints is not None):
@@ -71,7 +79,7 @@ def main():
                 ts = []
                 for k in range(total):
                     t0 = time.perf_counter()
-                    poses, fresh = s.push(px[k], **({} if valid is None else {"valid": valid[k]}))
+                    s.push(px[k], **({} if valid is None else {"valid": valid[k]}))
                     torch.cuda.synchronize()
                     ts.append(time.perf_counter() - t0)
                 s.check_range()
@@ -155,6 +163,22 @@ def main():
                 return (("det_graph", lambda: timed(new(detections=Dn), lambda s, k: s.push_detections(d_dets[k], P))),
                         ("md_graph", lambda: timed(new(missed_detections=True), md_tick)), ("host_route", host_route))
 
+            def camera_variants():
+                new = lambda **kw: stream.StreamSession(model, cfg, slots=T, resolutions=(W, H), mask_stride=ms, flip=True, lookahead=args.lookahead, **kw)
+                pair = {"camera_graph": new(camera=tuple(args.camera)), "graph": new()}
+                ts = {key: [] for key in pair}
+                for k in range(total):
+                    for key in (list(pair) if k % 2 == 0 else list(pair)[::-1]):
+                        t0 = time.perf_counter()
+                        pair[key].push(px[k])
+                        torch.cuda.synchronize()
+                        ts[key].append(time.perf_counter() - t0)
+                for s in pair.values():
+                    s.check_range()
+                    s.close()
+                row.update(camera=list(args.camera))
+                return tuple((key, lambda key=key: ts[key][args.warmup:]) for key in pair)
+
             row = dict(config=name, mask_stride=ms, slots=T, lookahead=args.lookahead, ticks=args.ticks)
             variants = (("graph", lambda: session(True)), ("no_graph", lambda: session(False)), ("baseline", baseline))
             if args.fps is not None:
@@ -173,11 +197,15 @@ def main():
                             ("md_graph", lambda: session(True, valid=seen.all(axis=2), missed_detections=True)))
             if args.detections is not None:
                 variants = detections_variants()
+            if args.camera is not None:
+                variants = camera_variants()
             for key, fn in variants:
                 ts = np.asarray(fn())
                 row[key + "_us"] = round(1e6 * float(np.median(ts)), 1)
                 row[key + "_p90_us"] = round(1e6 * float(np.percentile(ts, 90)), 1)
-            if args.detections is not None:
+            if args.camera is not None:
+                row["camera_minus_graph_us"] = round(row["camera_graph_us"] - row["graph_us"], 1)
+            elif args.detections is not None:
                 row["det_minus_md_us"] = round(row["det_graph_us"] - row["md_graph_us"], 1)
             elif args.repair_joints is not None:
                 row["repair_minus_md_us"] = round(row["repair_graph_us"] - row["md_graph_us"], 1)

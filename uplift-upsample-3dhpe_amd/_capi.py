@@ -44,6 +44,7 @@ EXPORTED_SYMBOLS = (
     "uu3d_keypoint_map_bytes", "uu3d_keypoint_map_pack", "uu3d_map_keypoints",
     "uu3d_associate_state_bytes", "uu3d_associate_reset", "uu3d_associate_detections", "uu3d_stream_associate",
     "uu3d_solve_roots", "uu3d_root_trajectory_scratch_bytes", "uu3d_root_trajectory",
+    "uu3d_stream_root_bytes", "uu3d_stream_root", "uu3d_stream_root_reset",
 )
 # include/uu3d_ops.h
 OPS_SYMBOLS = (
@@ -283,6 +284,13 @@ def load_library(path=None):
     lib.uu3d_root_trajectory_scratch_bytes.argtypes = [i64]
     lib.uu3d_root_trajectory.restype = C.c_int
     lib.uu3d_root_trajectory.argtypes = [vp, vp, i64, vp, i32, vp, vp, vp, i64, vp, vp, vp, sz, vp]
+    # live absolute root: the ring of raw frames and the held root of a session with a camera
+    lib.uu3d_stream_root_bytes.restype = sz
+    lib.uu3d_stream_root_bytes.argtypes = [i32, i32, i32]
+    lib.uu3d_stream_root.restype = C.c_int
+    lib.uu3d_stream_root.argtypes = [i32, i32, i32] + [vp] * 7 + [i32, vp, i32, vp, vp, vp]
+    lib.uu3d_stream_root_reset.restype = C.c_int
+    lib.uu3d_stream_root_reset.argtypes = [i32, i32, i32, vp, vp, vp]
     lib.uu3d_world_to_cam_2d.restype = C.c_int
     lib.uu3d_world_to_cam_2d.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
     lib.uu3d_set_schedule.restype = C.c_int

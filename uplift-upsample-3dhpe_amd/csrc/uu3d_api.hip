@@ -41,6 +41,7 @@
 #include "uu3d_stream.h"
 #include "uu3d_stream_rate.h"
 #include "uu3d_stream_repair.h"
+#include "uu3d_stream_root.h"
 #include "uu3d_train.h"
 #include "uu3d_bwd.h"
 #include "uu3d_launch.h"

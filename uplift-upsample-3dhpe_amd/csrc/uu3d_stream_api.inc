@@ -1,6 +1,6 @@
 // uu3d_stream_api.inc -- the host side of the live sessions (stream.StreamSession; include/uu3d.h, LIVE TRACKS), a piece of uu3d_api.hip: the
-// plain session (uu3d_stream.h), a session with a frame rate and one with an output rate of its own (uu3d_stream_rate.h).  Every entry
-// point is: null model, stream_resolve (one prologue, one order of checks), its own buffer checks, one launch, launched().
+// plain session (uu3d_stream.h), a session with a frame rate and one with an output rate of its own (uu3d_stream_rate.h), and the roots
+// of a session with a camera (uu3d_stream_root.h; no model: the conventions of uu3d_solve_roots).  Every entry point of a model is: null model, stream_resolve (one prologue, one order of checks), its own buffer checks, one launch, launched().
 namespace {
 // the session's settings checked against the model; nullptr = fine, else what is wrong
 const char* stream_config_error(const uu3d_model* m, const uu3d_stream_config* s) {
@@ -377,4 +377,45 @@ int uu3d_stream_out_reset(uu3d_model* m, const uu3d_stream_config* s, const uu3d
     StreamCall c;
     if (const int st = stream_resolve(m, s, r, o, state, kStreamRate | kStreamState | kStreamOut, "uu3d_stream_out_reset", c)) return st;
     return stream_rate_reset(m, s, c, true, slot_mask, stream, "uu3d_stream_out_reset");
+}
+
+// ---- LIVE ABSOLUTE ROOT (uu3d_stream_root.h): the ring of raw frames and the held root per slot, one launch per push, the reset ----
+namespace {
+// slots, joints and lookahead of a root call: UU3D_OK, or what is wrong (J beyond 64: UU3D_ERR_UNSUPPORTED)
+int stream_root_resolve(const int32_t slots, const int32_t J, const int32_t lookahead, const void* state, RootRingLayout& L) {
+    if (J > kRootMaxJoints) return UU3D_ERR_UNSUPPORTED;
+    if (slots < 1 || slots > (1 << 20) || J < 1 || lookahead < 0 || lookahead > (1 << 24)) return UU3D_ERR_INVALID_ARGUMENT;
+    if (!state || ((uintptr_t)state & 255) != 0) return UU3D_ERR_INVALID_ARGUMENT;
+    L = root_ring_layout(slots, J, lookahead);
+    return UU3D_OK;
+}
+}  // namespace
+
+size_t uu3d_stream_root_bytes(int32_t slots, int32_t J, int32_t lookahead) {
+    if (slots < 1 || slots > (1 << 20) || J < 1 || J > kRootMaxJoints || lookahead < 0 || lookahead > (1 << 24)) return 0;
+    return root_ring_layout(slots, J, lookahead).bytes;
+}
+
+int uu3d_stream_root(int32_t slots, int32_t J, int32_t lookahead, void* root_state, const int32_t* frames, const uint8_t* active, const uint8_t* fresh,
+                     const float* poses, const float* kp2d, const uint8_t* flags, int32_t flags_per_joint, const double* cameras, int32_t min_joints,
+                     float* roots, uint8_t* root_state_out, void* stream) {
+    RootRingLayout L;
+    if (const int st = stream_root_resolve(slots, J, lookahead, root_state, L)) return st;
+    if (!frames || !active || !fresh || !poses || !kp2d || !cameras || !roots || !root_state_out || min_joints < 2) return UU3D_ERR_INVALID_ARGUMENT;
+    if (((uintptr_t)frames & 3) != 0 || ((uintptr_t)poses & 3) != 0 || ((uintptr_t)kp2d & 7) != 0 || ((uintptr_t)cameras & 7) != 0 || ((uintptr_t)roots & 3) != 0)
+        return UU3D_ERR_INVALID_ARGUMENT;
+    char* b = (char*)root_state;
+    hipLaunchKernelGGL(stream_root_kernel, dim3((unsigned)slots), dim3(64), 0, (hipStream_t)stream, J, L.W, frames, active, fresh, poses, kp2d, flags,
+                       flags_per_joint != 0 ? 1 : 0, cameras, min_joints, (double*)(b + L.off_held), (float*)(b + L.off_kp), (uint8_t*)(b + L.off_used),
+                       (uint8_t*)(b + L.off_last), roots, root_state_out);
+    return hipGetLastError() == hipSuccess ? UU3D_OK : UU3D_ERR_HIP;
+}
+
+int uu3d_stream_root_reset(int32_t slots, int32_t J, int32_t lookahead, void* root_state, const uint8_t* slot_mask, void* stream) {
+    RootRingLayout L;
+    if (const int st = stream_root_resolve(slots, J, lookahead, root_state, L)) return st;
+    char* b = (char*)root_state;
+    hipLaunchKernelGGL(stream_root_reset_kernel, dim3((unsigned)slots), dim3(256), 0, (hipStream_t)stream, slot_mask, J, L.W, (double*)(b + L.off_held),
+                       (float*)(b + L.off_kp), (uint8_t*)(b + L.off_used), (uint8_t*)(b + L.off_last));
+    return hipGetLastError() == hipSuccess ? UU3D_OK : UU3D_ERR_HIP;
 }

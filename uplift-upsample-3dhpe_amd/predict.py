@@ -997,8 +997,8 @@ def solve_roots(poses, kp2d, camera, flags=None, min_root_joints=DEFAULT_MIN_ROO
     ``poses`` (G, J, 3) float32 and ``kp2d`` (G, J, 2) float32 on the device, contiguous (only read); ``camera``: (fx, fy, cx, cy), one or
     one per track with ``lens`` (frames per track); ``flags`` (G, J) uint8 / bool on the device or None
     -> (roots (G, 3) float64, solved (G,) bool), fresh device buffers.  ``poses + roots[:, None]`` stands in the camera's space.
-    The live form: a ``StreamSession`` push returns one pose per slot; ``solve_roots`` on those poses and the frame that was pushed places
-    each of them at ``lookahead=0`` (with a lookahead the pose belongs to an earlier frame: a ring of raw frames is a follow-up)."""
+    The live form is ``StreamSession(camera=...)``: every push returns the roots beside the poses, at any ``lookahead`` (the session keeps
+    the raw frames an emitted pose belongs to); at ``lookahead=0`` a solved root of it is this call on the push's poses and frame."""
     import torch
     lib = _capi.load_library()
     dev = poses.device
@@ -1249,8 +1249,8 @@ def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, fl
     then come from a second uu3d_assemble_tracks over the same raw predictions, no further forward) -- and held before the first and
     behind the last solved frame (uu3d_root_trajectory; ``root_trajectory_host``).  ``root_state``: 1 solved here, 2 interpolated or held,
     0 the track has no solved frame (zeros).  With ``root_relative=False`` the solve takes the pose as returned.  No accuracy is claimed:
-    the model's scale error goes 1:1 into the depth.  ``StreamSession`` and ``replay_tracks`` have no such option: ``solve_roots`` on a
-    push's poses and that push's frame is the live form at ``lookahead=0``; a lookahead ring of raw frames is a follow-up."""
+    the model's scale error goes 1:1 into the depth.  The live form is ``StreamSession(camera=...)`` / ``replay_tracks(camera=...)``: the
+    same solve per emitted pose at any ``lookahead``, the last solved root held where a frame is not solved (causal: no interpolation)."""
     import torch
     if camera is not None:
         cameras, min_root_joints = check_cameras(camera, len(tracks)), check_min_root_joints(min_root_joints)

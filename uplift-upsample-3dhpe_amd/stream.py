@@ -91,8 +91,29 @@ by ``associate_host`` -- ``reset(born)``, then ``push(frames, active=alive, vali
 runs on the detector's joints, in front of the map) and ``repair_joints``; NOT together with ``fps`` / ``out_fps`` (ValueError: the host
 mirror of the source counters cannot follow births that happen on the device yet).
 
+Live absolute root -- ``StreamSession(..., camera=(fx, fy, cx, cy), min_root_joints=6)``: every push returns, beside the poses, where each
+of them stands in the camera's 3D space -- ``push`` -> (poses, fresh, roots (slots, 3) float32, root_state (slots,) uint8), and
+``poses[i] + roots[i]`` is slot i's skeleton in the camera's space (``predict.predict_tracks(camera=...)`` for a finished video).  The
+intrinsics are in the units of the frames AS PUSHED (pixels with ``resolutions``), one tuple or one per slot.  Per slot the session keeps a
+ring of its last lookahead + 1 raw frames in the model's joint layout (behind the ``keypoints`` map, before normalisation; frame t at place
+t % (lookahead + 1)) with one USED byte per joint -- the joint's flag (none: every joint; ``missed_detections``: the frame's flag for all of
+its joints; ``repair_joints``: the push's per-joint flag, mapped with ``keypoints``) and both raw coordinates finite -- and the last solved
+root.  A joint that ``repair_joints`` fills is never used (an interpolation is not a measurement) and the ring holds the pushed coordinates,
+never the repaired ones, so no push revises it.  Whenever a slot's pose is fresh, the frame it belongs to -- c = t - lookahead, with ``fps``
+source frame q = j - lookahead -- is solved against that pose by ``predict.solve_roots_host``'s rule, unchanged (uu3d_stream_root: lane j of
+one wave per slot files joint j, lane 0 solves).  Solved: the root, state 1, and the slot holds it.  Not solved: the held root, state 2; no
+held root yet: zeros, state 0.  A push that is not fresh returns the previous root and state, like the pose; ``reset`` clears ring, held
+root and state (also on the device, for a slot born at a ``push_detections`` tick).  The rule is CAUSAL: it holds the last solved root and
+cannot interpolate towards a later solved frame as ``predict_tracks(camera=...)`` does, because the poses of later frames do not exist
+yet.  ``LiveRootHost`` is the rule in numpy.  The launch is the LAST step of the one captured tick (behind uu3d_stream_emit); with ``fps``
+it follows uu3d_stream_timed_emit, not captured.  ``captures`` stays 1 and ``push`` never waits.  With ``detections`` one tuple only: the
+people of a video share one space.  Not together with ``out_fps`` (ValueError: those poses are not at source-frame times; a later
+change).  No accuracy is claimed: the model's scale error goes 1:1 into the depth.  ``camera=None`` is the session above, bit for bit: no
+further launch or buffer.
+
     python -m uplift_upsample_3dhpe_amd.stream --config C --weights W.h5 --input tracks.npz --output out.npz [--lookahead A] [--resolution W H]
                                                  [--mask_missing] [--fps F [--out_fps G]] [--repair_joints G [--min_score S]] [--keypoints NAME]
+                                                 [--camera FX FY CX CY [--min_root_joints N]]
 """
 import argparse
 import ctypes as C
@@ -103,8 +124,9 @@ import numpy as np
 
 from . import _capi
 from ._capi import ptr as _ptr
-from .predict import (ASSOCIATION_DEFAULTS, KEYPOINT_PRESETS, _load_model, check_association, check_keypoint_inputs, check_repair_joints,
-                      check_resolutions, check_valid, input_joints, keypoint_map, split_scores)
+from .predict import (ASSOCIATION_DEFAULTS, DEFAULT_MIN_ROOT_JOINTS, KEYPOINT_PRESETS, MAX_ROOT_JOINTS, _load_model, check_association,
+                      check_cameras, check_keypoint_inputs, check_min_root_joints, check_repair_joints, check_resolutions, check_valid,
+                      input_joints, keypoint_map, solve_roots_host, split_scores)
 from .rates import (RatePlan, _rate_argument, max_lookahead, newest_model_frame, out_push_plan, push_plan,  # noqa: F401 (re-exported)
                     rate_plan, session_strides)
 
@@ -170,7 +192,7 @@ def staged_frames(repair_joints, mask_stride):
     return int(repair_joints) // int(mask_stride) + 2
 
 
-LIVE_OPTIONS = ("repair_joints", "keypoints")                        # the keywords ``StreamSession`` and ``replay_tracks`` take from **options
+LIVE_OPTIONS = ("repair_joints", "keypoints", "camera", "min_root_joints")                     # the keywords ``StreamSession`` and ``replay_tracks`` take from **options
 DETECTION_OPTIONS = ("detections",) + tuple(ASSOCIATION_DEFAULTS)    # ... and the ones only ``StreamSession`` takes: per-frame detections
 
 
@@ -277,6 +299,59 @@ class LiveRepairHost(object):
         return self._frame(t, max(0, t - self.G), t)[2]
 
 
+class LiveRootHost(object):
+    """The rule of uu3d_stream_root for ONE slot, in numpy, written to be read: the live form of ``predict.solve_roots_host``.  State --
+        raw, used   the raw coordinates and USED flags of the newest lookahead + 1 frames (frame f at place f % (lookahead + 1));
+        held        the last solved root, float64 (None: no frame was solved yet);
+        root, state what the slot returned last.
+    ``step(frame (J, 2) float32, used_flags, pose)``: one push of the slot while it is active.  ``frame``: the raw frame as pushed, in
+    the model's joint layout; ``used_flags``: None (every joint), one flag for the whole frame, or (J,) flags -- a joint is USED iff its flag
+    is set and both coordinates are finite; ``pose``: the (J, 3) pose the push returned when it is fresh, else None.
+    -> (root (3,) float32, state): a fresh pose is solved against frame c = t - lookahead (t: the frame just filed) -- solved: the root
+    rounded to float32, state 1, and the root is held; not solved (or c < 0): the held root, state 2, or zeros, state 0, when none
+    exists.  ``pose=None`` returns what the last step returned.  A push at which the slot is inactive is no step.  The rule is causal: it
+    holds the last solved root and never interpolates towards a later one (``predict.root_trajectory_host`` does; it sees the whole track)."""
+
+    def __init__(self, J, lookahead, camera, min_root_joints=DEFAULT_MIN_ROOT_JOINTS):
+        self.J, self.W = int(J), int(lookahead) + 1
+        if not 1 <= self.J <= MAX_ROOT_JOINTS or self.W < 1:
+            raise ValueError(f"J must be in [1, {MAX_ROOT_JOINTS}] and lookahead >= 0")
+        self.camera = check_cameras(camera, 1, per="slot")[0]
+        self.min_root_joints = check_min_root_joints(min_root_joints)
+        self.reset()
+
+    def reset(self):
+        self.frames = 0
+        self.raw = np.zeros((self.W, self.J, 2), np.float32)
+        self.used = np.zeros((self.W, self.J), bool)
+        self.held = None
+        self.root, self.state = np.zeros(3, np.float32), 0
+
+    def step(self, frame, used_flags=None, pose=None):
+        J, W, t = self.J, self.W, self.frames
+        frame = np.asarray(frame, np.float32).reshape(J, 2)
+        flags = np.ones(J, bool) if used_flags is None else np.broadcast_to(np.asarray(used_flags) != 0, (J,))
+        # 1. file the pushed frame
+        self.raw[t % W], self.used[t % W] = frame, flags & np.isfinite(frame).all(axis=1)
+        self.frames = t + 1
+        if pose is None:                                              # not fresh: nothing is solved, nothing changes
+            return self.root.copy(), self.state
+        # 2. solve the frame the fresh pose belongs to
+        c = t - (W - 1)
+        solved = False
+        if c >= 0:
+            roots, ok = solve_roots_host(np.asarray(pose, np.float32).reshape(1, J, 3), self.raw[c % W][None], self.camera,
+                                         flags=self.used[c % W][None], min_root_joints=self.min_root_joints)
+            solved = bool(ok[0])
+        # 3. the root of this push: solved here, else the last solved one
+        if solved:
+            self.held, self.state = roots[0], 1
+            self.root = roots[0].astype(np.float32)
+        else:
+            self.state = 2 if self.held is not None else 0
+        return self.root.copy(), self.state
+
+
 class StreamSession(object):
 
     def __init__(self, model, config, slots, resolutions=None, mask_stride=None, flip=None, lookahead=0, root_relative=True, graph=True,
@@ -311,10 +386,15 @@ class StreamSession(object):
         [1, 64], the most people a frame lists: the module docstring's "Per-frame detections" -- ``push_detections`` in place of ``push``,
         ``slots`` <= 64 is the capacity, the joints the detector emits <= 64.  ``max_age`` / ``max_dist`` / ``min_common``: the rule's
         parameters (``predict.ASSOCIATION_DEFAULTS``: 10, 0.5, 3 -- conveniences, not tuned values).  Implies ``missed_detections=True``; not
-        together with ``fps`` / ``out_fps`` (ValueError)."""
-        repair_joints, keypoints, detections, *rule = _live_options(options, "StreamSession", LIVE_OPTIONS + DETECTION_OPTIONS)
+        together with ``fps`` / ``out_fps`` (ValueError).
+        ``camera`` (keyword only, from ``options`` as well): None = root-relative poses only (the session above, bit for bit).  Else the
+        camera's intrinsics (fx, fy, cx, cy) in the units of the pushed frames, one tuple or one per slot (with ``detections`` one tuple
+        only): the module docstring's "Live absolute root" -- ``push`` / ``push_detections`` then return (poses, fresh, roots (slots, 3)
+        float32, root_state (slots,) uint8).  ``min_root_joints`` (default 6, an int >= 2; ValueError without ``camera``): the fewest used
+        joints a frame's root is solved from.  Models of more than ``predict.MAX_ROOT_JOINTS`` joints and ``out_fps``: ValueError."""
+        repair_joints, keypoints, camera, min_root_joints, detections, *rule = _live_options(options, "StreamSession", LIVE_OPTIONS + DETECTION_OPTIONS)
         res = self._init_plan(model, config, slots, resolutions, mask_stride, flip, lookahead, graph, missed_detections, fps, model_fps, out_fps,
-                              repair_joints, keypoints, detections, dict(zip(ASSOCIATION_DEFAULTS, rule)))
+                              repair_joints, keypoints, detections, dict(zip(ASSOCIATION_DEFAULTS, rule)), camera, min_root_joints)
         import torch
         self._torch = torch
         self._lib = _capi.load_library()
@@ -330,11 +410,24 @@ class StreamSession(object):
 
     # ---- construction: checks and plan, layout and state, buffers, launch tables (then the capture) ---------------------------------
     def _init_plan(self, model, config, slots, resolutions, mask_stride, flip, lookahead, graph, missed_detections, fps, model_fps, out_fps,
-                   repair_joints=None, keypoints=None, detections=None, rule=None):
+                   repair_joints=None, keypoints=None, detections=None, rule=None, camera=None, min_root_joints=None):
         """Every refusal that needs no device, and the session's plan.  -> the checked resolutions."""
         slots, lookahead = int(slots), int(lookahead)
         if slots < 1:
             raise ValueError("slots >= 1")
+        self.cameras, self.min_root_joints = None, None
+        if camera is not None:
+            self.cameras = check_cameras(camera, slots, per="slot")
+            self.min_root_joints = check_min_root_joints(DEFAULT_MIN_ROOT_JOINTS if min_root_joints is None else min_root_joints)
+            if int(config.NUM_KEYPOINTS) > MAX_ROOT_JOINTS:
+                raise ValueError(f"camera needs a model of at most {MAX_ROOT_JOINTS} joints, this one has {int(config.NUM_KEYPOINTS)}")
+            if out_fps is not None:
+                raise ValueError("camera together with out_fps is not supported yet: the returned poses are not at source-frame times, so no "
+                                 "pushed frame is theirs to be solved against (a later change)")
+            if detections is not None and np.ndim(camera) != 1:
+                raise ValueError("detections takes ONE camera (fx, fy, cx, cy), not one per slot: every person of a video shares one space")
+        elif min_root_joints is not None:
+            raise ValueError("min_root_joints needs camera=(fx, fy, cx, cy): it is a parameter of the root solve")
         self.detections, self.association = None, None
         if detections is not None:
             rule = {k: (v if (rule or {}).get(k) is None else rule[k]) for k, v in ASSOCIATION_DEFAULTS.items()}
@@ -485,6 +578,16 @@ class StreamSession(object):
             self._poses = zeros((T, self.max_out, J, 3), dtype=torch.float32)
             self._count = zeros((T,), dtype=torch.int32)
             self._result = self._poses, self._count
+        # live absolute root: the cameras, the ring of raw frames and the held root per slot, what push returns beside poses and fresh
+        if self.cameras is not None:
+            self._cams = torch.from_numpy(self.cameras).pin_memory().to(dev, non_blocking=True)
+            size = int(lib.uu3d_stream_root_bytes(T, J, self.lookahead))
+            if size == 0:
+                raise ValueError(f"camera: slots = {T}, joints = {J}, lookahead = {self.lookahead} are out of uu3d_stream_root's range")
+            self._root_state = zeros(size, dtype=torch.uint8)
+            self._roots = zeros((T, 3), dtype=torch.float32)
+            self._root_flag = zeros((T,), dtype=torch.uint8)
+            self._result = self._result + (self._roots, self._root_flag)
 
     def _init_launch_tables(self):
         """All arguments are the same at every push (the buffers never move), so the mode is decided here, once: every launch of the
@@ -492,7 +595,7 @@ class StreamSession(object):
           _tick_steps   the steps of one (sub-)tick, in order -- what the graph captures
           _push_before  / _push_after   the launches of a push around its sub-ticks (a session with a rate; not captured)
           _reset_call   the reset of the session's kind; the slot mask and the stream follow its arguments (_reset_more: what a session
-                        with repair_joints resets beside it)"""
+                        with repair_joints or a camera resets beside it)"""
         lib, m = self._lib, self.model
         h, cfg, state = m._h, C.byref(self._cfg), _ptr(self._state)
         kp, res, order, active, staged = _ptr(self._kp), _ptr(self._res), _ptr(self._order), _ptr(self._active), _ptr(self._staged)
@@ -533,6 +636,13 @@ class StreamSession(object):
             self._tick_steps = mapping + self._tick_steps
         self._reset_call = (lib.uu3d_stream_reset, (h, cfg, state))
         self._reset_more = [] if self.repair_joints is None else [(lib.uu3d_stream_repair_reset, (h, cfg, self.repair_joints, _ptr(self._repair_state)))]
+        root = None
+        if self.cameras is not None:                                 # live absolute root: the frame counters are those the pose's frame is counted in
+            T, J = self.slots, int(self._kp.shape[1])
+            root = (lib.uu3d_stream_root, (T, J, self.lookahead, _ptr(self._root_state), _ptr(self._source_frames), active, _ptr(self._fresh),
+                                           _ptr(self._out), kp, _ptr(self._valid_in), int(self._valid_in is not None and self._valid_in.dim() == 2),
+                                           _ptr(self._cams), self.min_root_joints, _ptr(self._roots), _ptr(self._root_flag)))
+            self._reset_more = self._reset_more + [(lib.uu3d_stream_root_reset, (T, J, self.lookahead, _ptr(self._root_state)))]
         # per-frame detections: the association in front of everything -- it writes the frame, the flags, `active` and the born mask --, then
         # the resets of the slots born at this tick, with the mask on the device
         if self.detections is not None:
@@ -552,6 +662,8 @@ class StreamSession(object):
             outp = C.byref(self._outp)
             self._push_after = [(lib.uu3d_stream_timed_emit_multi, (h, cfg, rate, outp, state, _ptr(self._poses), _ptr(self._count)))]
             self._reset_call = (lib.uu3d_stream_out_reset, (h, cfg, rate, outp, state))
+        if root is not None:                                         # the last step: behind the emit that wrote the pose it solves
+            (self._tick_steps if self.rate is None else self._push_after).append(root)
 
     # ---- the steps of a tick, on ``stream`` ------------------------------------------------------------------------------------------
     def _run(self, steps, stream):
@@ -638,6 +750,9 @@ class StreamSession(object):
         valid until the next ``push``: rows r < count[i] of slot i are the output frames that became due at this push, oldest first (the
         first is output frame ``out_frames[i] - count[i]``), rows r >= count[i] are zeros; an inactive slot has count 0.
         uu3d_stream_timed_emit_multi takes uu3d_stream_timed_emit's place.
+        A session with ``camera``: -> (poses, fresh, roots (slots, 3) float32, root_state (slots,) uint8), the session's own buffers as
+        well: ``poses[i] + roots[i]`` stands in the camera's space; ``root_state[i]``: 1 solved at this push, 2 the slot's last solved
+        root is held, 0 no frame of the slot was solved yet (zeros).  A slot that is not fresh returns its previous root and state.
         Enqueues on the current stream and returns; never waits for the device."""
         torch = self._torch
         m = self.model
@@ -688,7 +803,8 @@ class StreamSession(object):
         (D, K), one per joint (``scores >= 0.3``).  uu3d_stream_associate matches the people to slots on the device; then the tick of
         ``push``.  -> (poses (slots, J, 3) float32, fresh (slots,) bool) as ``push``: row i belongs to the track in slot i,
         ``track_ids[i]``.  In a session without ``repair_joints`` a detection with a joint flag that is not set gives a MISSING frame (as
-        a (T_i, J) entry of ``predict_tracks``' ``valid`` does); with it the joint is filled by the rule.  Enqueues on the current stream
+        a (T_i, J) entry of ``predict_tracks``' ``valid`` does); with it the joint is filled by the rule.  A session with ``camera``
+        appends (roots, root_state) as ``push`` does.  Enqueues on the current stream
         and returns; never waits for the device."""
         torch = self._torch
         m = self.model
@@ -756,7 +872,7 @@ class StreamSession(object):
 
     def reset(self, slots=None):
         """The given slots (indices; None = all) start a new track: zero frames, held pose 0, with ``out_fps`` output counter 0, with
-        ``repair_joints`` no observation of any joint.  A session with ``detections``: the tracks in those slots END and the slots are
+        ``repair_joints`` no observation of any joint, with ``camera`` no filed frame, no held root and root state 0.  A session with ``detections``: the tracks in those slots END and the slots are
         free (the next unmatched person takes the lowest one, under a new id); None also sets the id and dropped counters back to 0.
         Stream-ordered like ``push``."""
         torch = self._torch
@@ -862,9 +978,12 @@ def replay_tracks(model, config, tracks, resolutions=None, mask_stride=None, fli
     0 .. n_out_i - 1 at G per second --, and the number each of its ticks returned, (T_i,) int32; still one copy to the host, at the end.
     ``repair_joints=G`` (keyword only, taken from ``options``): a session with ``repair_joints`` (it needs ``valid``); an entry of ``valid`` may
     then be (T_i, J), one flag per joint.  ``keypoints=M`` (from ``options`` as well): a session with ``keypoints``; the tracks are
-    (T_i, K_in, 2) and per-joint entries of ``valid`` (T_i, K_in)."""
+    (T_i, K_in, 2) and per-joint entries of ``valid`` (T_i, K_in).  ``camera=C, min_root_joints=N`` (from ``options`` as well): a session with
+    ``camera`` -- the roots (T_i, 3) float32 and root states (T_i,) uint8 the session returned at each tick are appended per track:
+    -> (poses, fresh, roots, root_state)."""
     import torch
-    repair_joints, keypoints = _live_options(options, "replay_tracks")
+    repair_joints, keypoints, camera, min_root_joints = _live_options(options, "replay_tracks")
+    place = {} if camera is None and min_root_joints is None else {"camera": camera, "min_root_joints": min_root_joints}
     lens = [int(len(t)) for t in tracks]
     T, ticks = len(tracks), max(lens)
     K = J = int(np.asarray(tracks[0]).shape[1])                      # joints pushed, joints returned
@@ -883,7 +1002,9 @@ def replay_tracks(model, config, tracks, resolutions=None, mask_stride=None, fli
         raise ValueError('valid must be None, "finite" or a list with one (T_i,) array per track')
     s = StreamSession(model, config, T, resolutions=resolutions, mask_stride=mask_stride, flip=flip, lookahead=lookahead,
                       root_relative=root_relative, graph=graph, missed_detections=valid is not None, fps=fps, model_fps=model_fps, out_fps=out_fps,
-                      repair_joints=repair_joints, keypoints=keypoints)
+                      repair_joints=repair_joints, keypoints=keypoints, **place)
+    if camera is not None:                                           # per tick and slot four 32-bit words: the root's bits, the state
+        root_words = torch.zeros((ticks, T, 4), dtype=torch.int32, device=model.device)
     if out_fps is None:
         poses = torch.zeros((ticks, T, J, 3), dtype=torch.float32, device=model.device)
         fresh = torch.zeros((ticks, T), dtype=torch.bool, device=model.device)
@@ -898,9 +1019,12 @@ def replay_tracks(model, config, tracks, resolutions=None, mask_stride=None, fli
                 if act[i]:
                     kp[i] = t[k]
             if flags is None:
-                p, f = s.push(kp, None if act.all() else act)
+                p, f, *rs = s.push(kp, None if act.all() else act)
             else:
-                p, f = s.push(kp, None if act.all() else act, valid=np.array([flags[i][k] & True if act[i] else flags[i][0] & False for i in range(T)]))
+                p, f, *rs = s.push(kp, None if act.all() else act, valid=np.array([flags[i][k] & True if act[i] else flags[i][0] & False for i in range(T)]))
+            if rs:
+                root_words[k, :, :3].copy_(rs[0].view(torch.int32))
+                root_words[k, :, 3].copy_(rs[1])
             if out_fps is None:
                 poses[k].copy_(p)
                 fresh[k].copy_(f)
@@ -917,17 +1041,24 @@ def replay_tracks(model, config, tracks, resolutions=None, mask_stride=None, fli
         return ([np.concatenate([rows[k, i, :counts[k, i]] for k in range(n)] + [np.zeros((0, J, 3), np.float32)]) for i, n in enumerate(lens)],
                 [counts[:n, i].astype(np.int32) for i, n in enumerate(lens)])
     poses, fresh = poses.cpu().numpy(), fresh.cpu().numpy()
-    return [poses[:n, i] for i, n in enumerate(lens)], [fresh[:n, i] for i, n in enumerate(lens)]
+    out = [poses[:n, i] for i, n in enumerate(lens)], [fresh[:n, i] for i, n in enumerate(lens)]
+    if camera is not None:
+        root_words = root_words.cpu().numpy()
+        roots = np.ascontiguousarray(root_words[:, :, :3]).view(np.float32)
+        out += ([roots[:n, i] for i, n in enumerate(lens)], [root_words[:n, i, 3].astype(np.uint8) for i, n in enumerate(lens)])
+    return out
 
 
 def replay_detections(model, config, detections, counts=None, valid=None, slots=None, resolutions=None, mask_stride=None, flip=None, lookahead=0,
                       root_relative=True, graph=True, **options):
     """Push ONE video's per-frame detections tick by tick through a ``StreamSession(detections=D)`` and collect the poses per track id.
     ``detections`` (T, D, K, 2); ``counts`` (T,) or None; ``valid``: None, (T, D) or (T, D, K); ``slots`` (None: D); ``resolutions``: None
-    or one (w, h); ``options``: ``max_age`` / ``max_dist`` / ``min_common``, ``repair_joints``, ``keypoints``.
+    or one (w, h); ``options``: ``max_age`` / ``max_dist`` / ``min_common``, ``repair_joints``, ``keypoints``, ``camera`` (one tuple) /
+    ``min_root_joints``.
     -> a list of (track_id, first_frame, poses (n, J, 3) float32, fresh (n,) bool) by track id, host arrays: what the session returned for
     the track's slot at the ticks first_frame .. first_frame + n - 1, the ticks the track was alive (its trailing missing frames
-    included; ``predict.predict_detections`` ends a track at its last matched frame).  One copy to the host, at the end."""
+    included; ``predict.predict_detections`` ends a track at its last matched frame).  With ``camera`` every tuple carries two more
+    entries: roots (n, 3) float32 and root_state (n,) uint8 of those ticks.  One copy to the host, at the end."""
     import torch
     from .predict import _host_array
     detections = _host_array(detections)
@@ -942,21 +1073,30 @@ def replay_detections(model, config, detections, counts=None, valid=None, slots=
     J = int(model.arch.num_keypoints)
     poses = torch.zeros((ticks, S, J, 3), dtype=torch.float32, device=model.device)
     words = torch.zeros((ticks, 2, S), dtype=torch.int32, device=model.device)            # per tick: the fresh flags, the track ids
+    placed = s.cameras is not None
+    if placed:                                                        # per tick and slot: the root's bits, the state
+        root_words = torch.zeros((ticks, S, 4), dtype=torch.int32, device=model.device)
     try:
         for k in range(ticks):
-            p, f = s.push_detections(detections[k], None if counts is None else int(counts[k]), None if valid is None else valid[k])
+            p, f, *rs = s.push_detections(detections[k], None if counts is None else int(counts[k]), None if valid is None else valid[k])
             poses[k].copy_(p)
             words[k, 0].copy_(f)
             words[k, 1].copy_(s.track_ids)
+            if rs:
+                root_words[k, :, :3].copy_(rs[0].view(torch.int32))
+                root_words[k, :, 3].copy_(rs[1])
         s.check_range()
     finally:
         s.close()
     poses, words = poses.cpu().numpy(), words.cpu().numpy()
     fresh, ids = words[:, 0] != 0, words[:, 1]
+    if placed:
+        root_words = root_words.cpu().numpy()
+        roots, root_state = np.ascontiguousarray(root_words[:, :, :3]).view(np.float32), root_words[:, :, 3].astype(np.uint8)
     out = []
     for tid in range(int(ids.max()) + 1 if ids.size else 0):
         t, slot = np.nonzero(ids == tid)
-        out.append((tid, int(t[0]), poses[t, slot], fresh[t, slot]))
+        out.append((tid, int(t[0]), poses[t, slot], fresh[t, slot]) + ((roots[t, slot], root_state[t, slot]) if placed else ()))
     return out
 
 
@@ -987,9 +1127,18 @@ def parse_args(argv=None):
                         "seen when score >= S")
     p.add_argument("--keypoints", default=None, metavar="NAME", choices=sorted(KEYPOINT_PRESETS),
                    help="the joint layout of the arrays, (T, K, 2): mapped onto the model's joints on the device; scores are then per detector joint")
+    p.add_argument("--camera", type=float, nargs=4, metavar=("FX", "FY", "CX", "CY"), default=None,
+                   help="the camera's intrinsics in the units of the arrays (pixels with --resolution): the output gains NAME__root (T, 3), the "
+                        "position of the skeleton's root in the camera's space at every tick, and NAME__root_state (T,) per track; not with --out_fps")
+    p.add_argument("--min_root_joints", type=int, default=None, metavar="N",
+                   help=f"the fewest observed joints a frame's root is solved from (with --camera; default {DEFAULT_MIN_ROOT_JOINTS})")
     args = p.parse_args(argv)
     if args.out_fps is not None and args.fps is None:
         p.error("--out_fps needs --fps")
+    if args.min_root_joints is not None and args.camera is None:
+        p.error("--min_root_joints needs --camera: it is a parameter of the root solve")
+    if args.camera is not None and args.out_fps is not None:
+        p.error("--camera with --out_fps is not supported yet")
     if args.min_score is not None and args.repair_joints is None:
         p.error("--min_score needs --repair_joints: scores say which joints were seen")
     if args.repair_joints is not None and args.fps is not None:
@@ -1025,11 +1174,24 @@ def main(argv=None):
             rate_plan(config, args.fps, args.lookahead, out_fps=args.out_fps)
         except ValueError as e:
             raise SystemExit(f"--fps / --out_fps / --lookahead: {e}") from None
+    place = {}
+    if args.camera is not None:
+        try:
+            check_cameras(tuple(args.camera), 1)
+            place = {"camera": tuple(args.camera),
+                     "min_root_joints": check_min_root_joints(DEFAULT_MIN_ROOT_JOINTS if args.min_root_joints is None else args.min_root_joints)}
+        except ValueError as e:
+            raise SystemExit(f"--camera: {e}") from None
+        if any(k.endswith(("__root", "__root_state")) for k in names):
+            raise SystemExit(f"{args.input}: a key ending in __root or __root_state would collide with the arrays --camera writes")
     model = _load_model(config, args.weights)
-    poses, fresh = replay_tracks(model, config, tracks, resolutions=None if args.resolution is None else tuple(args.resolution),
-                                 lookahead=args.lookahead, **missing, **skeleton,
-                                 **({} if args.fps is None else {"fps": args.fps}), **({} if args.out_fps is None else {"out_fps": args.out_fps}))
+    poses, fresh, *rs = replay_tracks(model, config, tracks, resolutions=None if args.resolution is None else tuple(args.resolution),
+                                      lookahead=args.lookahead, **missing, **skeleton, **place,
+                                      **({} if args.fps is None else {"fps": args.fps}), **({} if args.out_fps is None else {"out_fps": args.out_fps}))
     out = {}
+    if rs:
+        out.update({k + "__root": np.asarray(r, np.float32) for k, r in zip(names, rs[0])})
+        out.update({k + "__root_state": np.asarray(r, np.uint8) for k, r in zip(names, rs[1])})
     for k, p, f in zip(names, poses, fresh):
         out[k] = np.asarray(p, np.float32)
         if args.out_fps is None:
