@@ -851,6 +851,48 @@ int uu3d_stream_root_reset(int32_t slots, int32_t num_keypoints, int32_t lookahe
                            void* stream);
 
 /*
+ * STEADY OUTPUT (predict.predict_tracks(smooth=...), predict.one_euro; stream.StreamSession(smooth=...), stream.LiveOneEuro): the One-Euro
+ * filter (Casiez, Roussel, Vogel 2012) over the poses and roots a call or a session returns -- an exponential smoother whose cut-off rises
+ * with the speed of the signal.  No model: the calls take the channel count C and run on any (rows, C) f32 buffers.  Nothing is claimed
+ * about accuracy or jitter; the filter is causal and lags.
+ * THE RULE (predict.one_euro_host is it in numpy, bit for bit).  A CHANNEL is one scalar over time; a filter is (min_cutoff > 0, beta >= 0,
+ * d_cutoff > 0) in Hz, 1 / unit speed and Hz.  Per channel the state is xh, dxh (f64) and whether a sample was taken; x is the f32 value
+ * widened, r the sample rate in Hz:
+ *     alpha(fc, r) = 1.0 / (1.0 + r / (6.283185307179586 * fc))
+ *     first sample:   xh = x;  dxh = 0.0
+ *     later samples:  dx = (x - xh) * r;  ad = alpha(d_cutoff, r);  dxh = ad * dx + (1.0 - ad) * dxh
+ *                     a = alpha(min_cutoff + beta * fabs(dxh), r);  xh = a * x + (1.0 - a) * xh
+ *     output = (float) xh, rounded once
+ * Every operation is one IEEE f64 operation in the written order, no fused multiply-add.  r = rate / n, n the whole number of frames
+ * since the channel's previous sample (offline always 1).  A non-finite x is passed through unchanged, takes no sample and touches no
+ * state; so does a row whose state byte is 0 (a root that was never solved: zeros).
+ *
+ *   uu3d_one_euro_tracks(in_dev, out_dev (rows, C) f32, out != in, rows, C in [1, 65536] (beyond: UU3D_ERR_UNSUPPORTED), track_start_dev,
+ *       track_len_dev (num_tracks) i64: the rows of each track, rates_dev (num_tracks) f64: its rate in Hz, num_tracks <= 2^20,
+ *       state_dev (rows) u8 or NULL, min_cutoff, beta, d_cutoff, stream): one launch, one lane per (track, channel) walks the track's rows
+ *       in order; adjacent lanes are adjacent channels of one row.  Rows of no track are not written.
+ *   LIVE.  The state block of uu3d_stream_one_euro_bytes(slots, C) bytes (0: out of range -- slots in [1, 2^20], C in [1, 65536]), 256-byte
+ *   aligned, zeroed by uu3d_stream_one_euro_reset, holds per slot and channel xh, dxh, the frame index of the last sample (i32) and a TAKEN
+ *   byte.  frames_dev (slots) i32 is each slot's frame counter AFTER the push; the fresh value belongs to frame f = frames - 1 - lookahead.
+ *   uu3d_stream_one_euro(slots, C, lookahead, filter_state_dev, frames_dev, active_dev, fresh_dev (slots) u8, values_dev (slots, C) f32 --
+ *       what the push returns, only read --, state_dev (slots) u8 or NULL, rate, min_cutoff, beta, d_cutoff, out_dev (slots, C) f32, a
+ *       buffer of its own, stream): one launch, one workgroup per slot, lanes over channels.  An active slot whose value is fresh takes one
+ *       sample per channel with n = f - (the frame of the channel's last sample), anything below 1 counting as 1.  Any other slot returns
+ *       xh rounded once, zeros before the first sample.
+ *   uu3d_stream_one_euro_reset(slots, C, filter_state_dev, slot_mask_dev (slots) u8 or NULL = every slot, stream): the chosen slots have
+ *       taken no sample; beside uu3d_stream_reset, with the same mask (host-made or written on the device).
+ * Every output and state element has one writer, no atomics, the caller's buffers are only read: bitwise repeatable, capturable.
+ */
+int uu3d_one_euro_tracks(const float* in_dev, float* out_dev, int64_t rows, int32_t channels, const int64_t* track_start_dev,
+                         const int64_t* track_len_dev, const double* rates_dev, int32_t num_tracks, const uint8_t* state_dev, double min_cutoff,
+                         double beta, double d_cutoff, void* stream);
+size_t uu3d_stream_one_euro_bytes(int32_t slots, int32_t channels);
+int uu3d_stream_one_euro(int32_t slots, int32_t channels, int32_t lookahead, void* filter_state_dev, const int32_t* frames_dev,
+                         const uint8_t* active_dev, const uint8_t* fresh_dev, const float* values_dev, const uint8_t* state_dev, double rate,
+                         double min_cutoff, double beta, double d_cutoff, float* out_dev, void* stream);
+int uu3d_stream_one_euro_reset(int32_t slots, int32_t channels, void* filter_state_dev, const uint8_t* slot_mask_dev, void* stream);
+
+/*
  * Per-kernel timing of the next uu3d_forward calls with HIP events on the launch stream.
  * When enabled, uu3d_forward records an event pair around every launch; uu3d_profile_read
  * synchronises those events and returns the per-launch records of the LAST forward.

@@ -16,9 +16,12 @@ mapped by predict.map_keypoints_host in front of the plain call; the two must ag
 --camera FX FY CX CY: also predict_tracks(camera=...) -- the roots solved and joined on the device -- against the same call without camera
 followed by .cpu() of every pose and predict.solve_roots_host / predict.root_trajectory_host, the rule in numpy (written to be read, not to be
 fast); the two must agree bit for bit.
+--smooth: also predict_tracks(smooth=True) -- with --camera predict_tracks(camera=..., smooth=True), poses and roots filtered -- next to the
+same call without smooth in the same process: smooth_extra_ms is the difference of the two medians (one or two more launches, each a serial
+walk over the frames of a track); the result must equal predict.one_euro_host on the unfiltered result bit for bit.
    python tools/predict_tracks_bench.py [--tracks 40] [--frames 2500] [--batch 512] [--reps 3] [--cases h36m_351:5,h36m_81:4] [--missing 0.3]
                                         [--fps 30] [--repair_joints 5 --missing_joints 0.1] [--keypoints coco17]
-                                        [--camera 1145 1145 960 540]"""
+                                        [--camera 1145 1145 960 540] [--smooth]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -38,6 +41,7 @@ def main():
     ap.add_argument("--keypoints", default=None, metavar="NAME", help="also time predict_tracks(keypoints=NAME) against predict.map_keypoints_host in front")
     ap.add_argument("--camera", type=float, nargs=4, default=None, metavar=("FX", "FY", "CX", "CY"),
                     help="also time predict_tracks(camera=...) against .cpu() and the numpy rule behind the plain call")
+    ap.add_argument("--smooth", action="store_true", help="also time predict_tracks(smooth=True) (with --camera: poses and roots) against the same call without")
     args = ap.parse_args()
     import numpy as np, torch
     import uplift_upsample_3dhpe_amd as pkg
@@ -142,6 +146,10 @@ def main():
             roots, solved = predict.solve_roots_host(poses, np.concatenate(px, 0), tuple(args.camera), lens=lens)
             return predict.root_trajectory_host(roots, solved, lens)
 
+        def smooth_path():
+            return predict.predict_tracks(model, cfg, px, resolutions=(W, H), mask_stride=int(msv), flip=True, reuse_frames=reuse, batch_size=args.batch,
+                                          smooth=True, **({} if args.camera is None else {"camera": tuple(args.camera)}))
+
         row = dict(config=name, mask_stride=int(msv), tracks=args.tracks, frames=total, batch=args.batch, reuse_frames=reuse)
         outs = {}
         cases = [("predict_tracks", new_path), ("predict_tracks_to_host", lambda: new_path(True)), ("composition", composition)]
@@ -160,6 +168,8 @@ def main():
         if args.camera is not None:
             row["camera"] = list(args.camera)
             cases += [("predict_tracks_camera", camera_path), ("host_camera", camera_host)]
+        if args.smooth:
+            cases.append(("predict_tracks_smooth", smooth_path))
         for key, fn in cases:
             fn()
             torch.cuda.synchronize()
@@ -192,6 +202,17 @@ def main():
             row["camera_bits_equal"] = bool(np.array_equal(roots.view(np.uint32), outs["host_camera"][0].view(np.uint32))
                                             and np.array_equal(state, outs["host_camera"][1]))
             row["camera_solved_frames"] = int((state == 1).sum())
+        if args.smooth:
+            base = "predict_tracks_camera" if args.camera is not None else "predict_tracks"
+            row["smooth_extra_ms"] = round(row["predict_tracks_smooth_ms"] - row[base + "_ms"], 1)
+            lens, F = [len(t) for t in px], predict.OneEuro()
+            plain, got = outs[base], outs["predict_tracks_smooth"]
+            same = lambda a, b, **kw: np.array_equal(torch.cat(a, 0).cpu().numpy().view(np.uint32),
+                                                     predict.one_euro_host(torch.cat(b, 0).cpu().numpy(), lens, 50, F, **kw).view(np.uint32))
+            if args.camera is None:
+                row["smooth_bits_equal"] = bool(same(got, plain))
+            else:
+                row["smooth_bits_equal"] = bool(same(got[0], plain[0]) and same(got[1], plain[1], state=torch.cat(plain[2], 0).cpu().numpy()))
         row["device"] = torch.cuda.get_device_name(0)
         print(json.dumps(row), flush=True)
         results.append(row)

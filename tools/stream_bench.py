@@ -4,7 +4,7 @@ uploads them with their mirrored copies and calls ``model([x, mask])`` once -- t
 A tick = host clock from the call to the synchronised result (a live consumer reads every pose); host input in all three variants.
 Median (and 90th percentile) over --ticks ticks after --warmup ticks, per config and slot count.
    python tools/stream_bench.py [--slots 1,8,64] [--cases h36m_81:4,h36m_351:5] [--ticks 300] [--warmup 60] [--lookahead 0] [--fps F [--out_fps G]]
-                                [--repair_joints G] [--detections D] [--camera FX FY CX CY]
+                                [--repair_joints G] [--detections D] [--camera FX FY CX CY] [--smooth]
 --fps F (a float or NUM/DEN): microseconds per PUSH of StreamSession(fps=F) -- one source frame in, one pose out, on average
 model_fps / F sub-ticks -- next to the plain session pushed at the model's rate (the cost of one model tick); the lookahead is raised to
 the smallest one the rate allows.  The numpy baseline is left out.
@@ -22,7 +22,11 @@ the HOST ROUTE a user takes without the option (host_route_us): the detections s
 --camera FX FY CX CY (not with the options above): the tick of StreamSession(camera=...) -- one more launch at the end of the captured
 tick, two more buffers returned -- as camera_graph_us next to the tick of the same session without camera (graph_us) on the same frames in
 the same process: both sessions are alive side by side and every tick is pushed into both, the order alternating from tick to tick.
-camera_minus_graph_us is the difference of the two medians.  The numpy baseline is left out."""
+camera_minus_graph_us is the difference of the two medians.  The numpy baseline is left out.
+--smooth (alone or with --camera, not with the other options): the tick of StreamSession(smooth=True) -- one more launch at the end of the
+captured tick, with --camera two (poses and roots) -- as smooth_graph_us next to the tick of the same session without smooth (graph_us;
+with --camera both sessions have the camera), measured side by side in the same way.  smooth_minus_graph_us is the difference of the two
+medians.  The numpy baseline is left out."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -40,7 +44,10 @@ def main():
     ap.add_argument("--missing_joints", type=float, default=0.1)
     ap.add_argument("--detections", type=int, default=None)
     ap.add_argument("--camera", type=float, nargs=4, metavar=("FX", "FY", "CX", "CY"), default=None)
+    ap.add_argument("--smooth", action="store_true")
     args = ap.parse_args()
+    if args.smooth and (args.fps is not None or args.repair_joints is not None or args.detections is not None):
+        ap.error("--smooth is not measured together with --fps / --repair_joints / --detections")
     if args.camera is not None and (args.fps is not None or args.repair_joints is not None or args.detections is not None):
         ap.error("--camera is not measured together with --fps / --repair_joints / --detections")
     if args.repair_joints is not None and args.fps is not None:
@@ -165,7 +172,11 @@ def main():
 
             def camera_variants():
                 new = lambda **kw: stream.StreamSession(model, cfg, slots=T, resolutions=(W, H), mask_stride=ms, flip=True, lookahead=args.lookahead, **kw)
-                pair = {"camera_graph": new(camera=tuple(args.camera)), "graph": new()}
+                if args.smooth:                                       # both with the camera (if any), one of them with the filter behind the tick
+                    place = {} if args.camera is None else {"camera": tuple(args.camera)}
+                    pair = {"smooth_graph": new(smooth=True, **place), "graph": new(**place)}
+                else:
+                    pair = {"camera_graph": new(camera=tuple(args.camera)), "graph": new()}
                 ts = {key: [] for key in pair}
                 for k in range(total):
                     for key in (list(pair) if k % 2 == 0 else list(pair)[::-1]):
@@ -176,7 +187,7 @@ def main():
                 for s in pair.values():
                     s.check_range()
                     s.close()
-                row.update(camera=list(args.camera))
+                row.update(camera=None if args.camera is None else list(args.camera), smooth=bool(args.smooth))
                 return tuple((key, lambda key=key: ts[key][args.warmup:]) for key in pair)
 
             row = dict(config=name, mask_stride=ms, slots=T, lookahead=args.lookahead, ticks=args.ticks)
@@ -197,13 +208,15 @@ def main():
                             ("md_graph", lambda: session(True, valid=seen.all(axis=2), missed_detections=True)))
             if args.detections is not None:
                 variants = detections_variants()
-            if args.camera is not None:
+            if args.camera is not None or args.smooth:
                 variants = camera_variants()
             for key, fn in variants:
                 ts = np.asarray(fn())
                 row[key + "_us"] = round(1e6 * float(np.median(ts)), 1)
                 row[key + "_p90_us"] = round(1e6 * float(np.percentile(ts, 90)), 1)
-            if args.camera is not None:
+            if args.smooth:
+                row["smooth_minus_graph_us"] = round(row["smooth_graph_us"] - row["graph_us"], 1)
+            elif args.camera is not None:
                 row["camera_minus_graph_us"] = round(row["camera_graph_us"] - row["graph_us"], 1)
             elif args.detections is not None:
                 row["det_minus_md_us"] = round(row["det_graph_us"] - row["md_graph_us"], 1)

@@ -45,6 +45,7 @@ EXPORTED_SYMBOLS = (
     "uu3d_associate_state_bytes", "uu3d_associate_reset", "uu3d_associate_detections", "uu3d_stream_associate",
     "uu3d_solve_roots", "uu3d_root_trajectory_scratch_bytes", "uu3d_root_trajectory",
     "uu3d_stream_root_bytes", "uu3d_stream_root", "uu3d_stream_root_reset",
+    "uu3d_one_euro_tracks", "uu3d_stream_one_euro_bytes", "uu3d_stream_one_euro", "uu3d_stream_one_euro_reset",
 )
 # include/uu3d_ops.h
 OPS_SYMBOLS = (
@@ -291,6 +292,16 @@ def load_library(path=None):
     lib.uu3d_stream_root.argtypes = [i32, i32, i32] + [vp] * 7 + [i32, vp, i32, vp, vp, vp]
     lib.uu3d_stream_root_reset.restype = C.c_int
     lib.uu3d_stream_root_reset.argtypes = [i32, i32, i32, vp, vp, vp]
+    # steady output: the One-Euro filter over finished tracks and the live filter of a session
+    f64 = C.c_double
+    lib.uu3d_one_euro_tracks.restype = C.c_int
+    lib.uu3d_one_euro_tracks.argtypes = [vp, vp, i64, i32, vp, vp, vp, i32, vp, f64, f64, f64, vp]
+    lib.uu3d_stream_one_euro_bytes.restype = sz
+    lib.uu3d_stream_one_euro_bytes.argtypes = [i32, i32]
+    lib.uu3d_stream_one_euro.restype = C.c_int
+    lib.uu3d_stream_one_euro.argtypes = [i32, i32, i32] + [vp] * 6 + [f64] * 4 + [vp, vp]
+    lib.uu3d_stream_one_euro_reset.restype = C.c_int
+    lib.uu3d_stream_one_euro_reset.argtypes = [i32, i32, vp, vp, vp]
     lib.uu3d_world_to_cam_2d.restype = C.c_int
     lib.uu3d_world_to_cam_2d.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
     lib.uu3d_set_schedule.restype = C.c_int

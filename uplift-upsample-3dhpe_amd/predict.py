@@ -24,7 +24,7 @@ synchronises the stream once after the last forward (its pipeline's buffers go a
 
     python -m uplift_upsample_3dhpe_amd.predict --config C --weights W.h5 --input tracks.npz --output out.npz \\
         [--resolution W H] [--mask_stride S] [--keyframes_only] [--mask_missing] [--fps F] [--out_fps F] [--repair_joints G] [--min_score S]
-        [--keypoints NAME] [--camera FX FY CX CY] [--min_root_joints N]
+        [--keypoints NAME] [--camera FX FY CX CY] [--min_root_joints N] [--smooth MIN_CUTOFF BETA D_CUTOFF] [--smooth_root MIN_CUTOFF BETA D_CUTOFF]
 
 Per-joint missed detections: ``predict_tracks(..., valid=..., repair_joints=G)`` fills a joint the detector lost for up to G frames by
 linear interpolation between the nearest frames where it was seen (uu3d_repair_joints, in front of the two front kernels above; the rule
@@ -44,6 +44,11 @@ the skeleton stands in the camera's space: at every given frame the translation 
 keypoints (uu3d_solve_roots: linear least squares over the observed joints; ``solve_roots`` is the launch alone; the rule in numpy:
 ``solve_roots_host``), joined to a piecewise-linear trajectory that is read at the returned frames (uu3d_root_trajectory;
 ``root_trajectory_host``).  ``predict_detections(..., camera=...)`` places every person of a video in the same space.
+
+Steady output: the root is solved frame by frame and the poses carry the detector's frame-to-frame noise.  ``predict_tracks(...,
+smooth=OneEuro(min_cutoff, beta, d_cutoff))`` passes the returned poses and roots through the One-Euro filter on the device
+(uu3d_one_euro_tracks: one lane per track and channel walks the frames in order; ``one_euro`` is the launch alone; the rule in numpy:
+``one_euro_host``).  The filter is causal, so the result lags as a live session's does; ``predict_detections(..., smooth=...)`` hands it on.
 """
 import argparse
 import ctypes as C
@@ -821,7 +826,8 @@ def predict_detections(model, config, detections, counts=None, valid=None, slots
     flags are gathered on the device for ``predict_tracks(valid=flags)``.  The result equals ``predict_tracks`` on the tracks of
     ``association_tracks_host``, bit for bit.  Needs a model with strided input.  Greedy, no motion model: no tracking accuracy is claimed.
     ``camera``: one (fx, fy, cx, cy) or one per VIDEO, handed to ``predict_tracks`` per track the way ``resolutions`` is: the tuples become
-    (track_id, first_frame, poses, roots (n, 3) float32, root_state (n,) uint8) -- every person of a video in the same camera space."""
+    (track_id, first_frame, poses, roots (n, 3) float32, root_state (n,) uint8) -- every person of a video in the same camera space.
+    ``smooth``: handed to ``predict_tracks`` as it is -- every track's poses (and roots) filtered from its birth frame on."""
     import torch
     assoc, options = _association_options(options)
     camera = options.pop("camera", None)
@@ -1057,6 +1063,157 @@ def root_trajectory(roots, solved, lens=None, positions=None):
     return out, state
 
 
+# ---- steady output: the One-Euro filter over the returned poses and roots (include/uu3d.h, STEADY OUTPUT) ------------------------------------
+MAX_SMOOTH_CHANNELS = 1 << 16                                         # kSmoothMaxChannels
+TWO_PI = 6.283185307179586
+
+
+class OneEuro(object):
+    """A One-Euro filter (Casiez, Roussel, Vogel 2012): ``min_cutoff`` > 0 in Hz, the cut-off of a channel at rest; ``beta`` >= 0 in 1 / unit
+    speed, how fast the cut-off rises with the channel's speed; ``d_cutoff`` > 0 in Hz, the cut-off of the speed estimate.  Anything else,
+    or a non-finite value, is a ValueError.  The defaults are conveniences for metres and seconds; they are not tuned and claim nothing."""
+    __slots__ = ("min_cutoff", "beta", "d_cutoff")
+
+    def __init__(self, min_cutoff=1.0, beta=0.5, d_cutoff=1.0):
+        try:
+            values = tuple(float(v) for v in (min_cutoff, beta, d_cutoff))
+        except (TypeError, ValueError):
+            raise ValueError(f"OneEuro takes three numbers, got {(min_cutoff, beta, d_cutoff)!r}") from None
+        if not all(np.isfinite(values)) or values[0] <= 0 or values[1] < 0 or values[2] <= 0:
+            raise ValueError(f"OneEuro needs finite min_cutoff > 0, beta >= 0 and d_cutoff > 0, got {values}")
+        self.min_cutoff, self.beta, self.d_cutoff = values
+
+    def __repr__(self):
+        return f"OneEuro(min_cutoff={self.min_cutoff!r}, beta={self.beta!r}, d_cutoff={self.d_cutoff!r})"
+
+    def __eq__(self, other):
+        return isinstance(other, OneEuro) and tuple(self) == tuple(other)
+
+    def __hash__(self):
+        return hash(tuple(self))
+
+    def __iter__(self):
+        return iter((self.min_cutoff, self.beta, self.d_cutoff))
+
+
+def check_smooth(smooth, placed):
+    """``smooth`` of ``predict_tracks`` / ``StreamSession`` -> (pose filter, root filter), each a ``OneEuro`` or None.  None: no filter;
+    True: the defaults; a ``OneEuro``: that filter -- both for the poses and, where the call has a ``camera`` (``placed``), the roots; a
+    pair (pose_filter, root_filter), either of which may be None: exactly those, and a root filter without ``camera`` is a ValueError."""
+    if smooth is None or smooth is False:
+        return None, None
+    if smooth is True:
+        smooth = OneEuro()
+    if isinstance(smooth, OneEuro):
+        return smooth, (smooth if placed else None)
+    if isinstance(smooth, (tuple, list)) and len(smooth) == 2 and all(f is None or isinstance(f, OneEuro) for f in smooth):
+        if smooth[1] is not None and not placed:
+            raise ValueError("a root filter needs camera=(fx, fy, cx, cy): without it the call returns no roots")
+        return smooth[0], smooth[1]
+    raise ValueError(f"smooth must be None, True, a OneEuro or a pair (pose_filter, root_filter) of OneEuro / None, got {smooth!r}")
+
+
+def _one_euro_rates(rate, tracks):
+    """``rate``: one sample rate in Hz or one per track, each as ``frame_rate`` takes it -> (tracks,) float64, each the exact rate rounded once."""
+    many = isinstance(rate, (list, np.ndarray)) or (isinstance(rate, tuple) and not (len(rate) == 2 and all(isinstance(v, (int, np.integer)) for v in rate)))
+    rates = [frame_rate(v) for v in rate] if many else [frame_rate(rate)] * int(tracks)
+    if len(rates) != int(tracks):
+        raise ValueError(f"rate must be one rate or one per track ({int(tracks)}), got {len(rates)}")
+    return np.array([float(r) for r in rates], np.float64)
+
+
+def one_euro_alpha(fc, r):
+    """alpha(fc, r) = 1 / (1 + r / (2 pi fc)): the weight of the new sample at cut-off ``fc`` and sample rate ``r``, both in Hz (float64)."""
+    return 1.0 / (1.0 + r / (TWO_PI * fc))
+
+
+def one_euro_sample(x, r, filt, xh, dxh):
+    """One later sample ``x`` of a channel at sample rate ``r`` -> (xh, dxh).  float64 scalars or arrays of channels alike; every operation
+    is one IEEE operation, in the order written (what csrc/uu3d_smooth.h does, statement for statement)."""
+    dx = (x - xh) * r
+    ad = one_euro_alpha(filt.d_cutoff, r)
+    dxh = ad * dx + (1.0 - ad) * dxh
+    a = one_euro_alpha(filt.min_cutoff + filt.beta * np.abs(dxh), r)
+    xh = a * x + (1.0 - a) * xh
+    return xh, dxh
+
+
+def one_euro_host(x, lens, rate, filt, state=None):
+    """The rule of STEADY OUTPUT (include/uu3d.h) in numpy, written to be read: what uu3d_one_euro_tracks computes, bit for bit.
+    ``x`` (G, ...) float32: the rows of all tracks back to back, everything behind the first axis is the C channels of a row; ``lens``:
+    rows per track (None: one track); ``rate``: the rows' rate in Hz, one or one per track (as ``rates.frame_rate`` takes it); ``filt``: a
+    ``OneEuro``; ``state``: None or (G,), 0 = the row is passed through unchanged and takes no sample (a root that was never solved)
+    -> the filtered rows, float32, the shape of ``x``.
+    Per channel: the first sample is returned as given; a later one moves xh towards it by ``one_euro_sample``; the output is xh rounded
+    once.  A non-finite value is passed through and touches no state.  Rows are walked in a plain loop; the channels of a row are
+    independent, so they go through numpy's element-wise float64 operations side by side."""
+    X = np.asarray(_host_array(x), np.float32)
+    G = int(X.shape[0])
+    flat = X.reshape(G, -1)
+    if not isinstance(filt, OneEuro):
+        raise ValueError(f"filt must be a OneEuro, got {filt!r}")
+    lens = _root_lens(lens, G)
+    rates = _one_euro_rates(rate, len(lens))
+    keep = np.ones(G, bool) if state is None else np.asarray(_host_array(state)).reshape(-1) != 0
+    if len(keep) != G:
+        raise ValueError(f"state must be ({G},)")
+    out = flat.copy()
+    first = 0
+    with np.errstate(all="ignore"):
+        for n, r in zip(lens.tolist(), rates):
+            xh = np.zeros(flat.shape[1], np.float64)
+            dxh = np.zeros(flat.shape[1], np.float64)
+            taken = np.zeros(flat.shape[1], bool)
+            for i in range(first, first + n):
+                if not keep[i]:
+                    continue
+                v = flat[i].astype(np.float64)
+                ok = np.isfinite(v)
+                nxh, ndxh = one_euro_sample(v, r, filt, xh, dxh)
+                later = ok & taken
+                start = ok & ~taken
+                xh = np.where(later, nxh, np.where(start, v, xh))
+                dxh = np.where(later, ndxh, np.where(start, 0.0, dxh))
+                taken |= ok
+                out[i] = np.where(ok, xh.astype(np.float32), flat[i])
+            first += n
+    return out.reshape(X.shape)
+
+
+def one_euro(x, lens, rate, filt, state=None):
+    """uu3d_one_euro_tracks on the current stream: ``one_euro_host`` on a device tensor, one launch, nothing copies to the host or waits
+    (the per-track plan -- first row, length, rate -- is made on the host and goes up pinned and asynchronously).  ``x``: a contiguous
+    (G, ...) float32 device tensor, only read; ``state``: None or a contiguous (G,) uint8 / bool device tensor
+    -> the filtered rows, a fresh device tensor of ``x``'s shape.  One lane per (track, channel) walks the track's rows in order."""
+    import torch
+    lib = _capi.load_library()
+    if not isinstance(x, torch.Tensor) or x.dim() < 1 or x.dtype != torch.float32 or not x.is_contiguous() or not x.is_cuda:
+        raise ValueError("x must be a contiguous (G, ...) float32 device tensor")
+    if not isinstance(filt, OneEuro):
+        raise ValueError(f"filt must be a OneEuro, got {filt!r}")
+    dev = x.device
+    G = int(x.shape[0])
+    Cn = int(x.numel() // G) if G else int(np.prod(x.shape[1:], dtype=np.int64))
+    if not 1 <= Cn <= MAX_SMOOTH_CHANNELS:
+        raise ValueError(f"a row must have 1 to {MAX_SMOOTH_CHANNELS} channels, got {Cn}")
+    lens = _root_lens(lens, G)
+    rates = _one_euro_rates(rate, len(lens))
+    if state is not None:
+        if tuple(state.shape) != (G,) or state.dtype not in (torch.uint8, torch.bool) or not state.is_contiguous() or state.device != dev:
+            raise ValueError(f"state must be a contiguous ({G},) uint8 or bool tensor on x's device")
+        state = state.view(torch.uint8)
+    out = torch.empty_like(x)
+    if G == 0:
+        return out
+    plan = _upload(np.stack([np.concatenate([[0], np.cumsum(lens)[:-1]]), lens]), np.int64, dev)
+    d_rates = _upload(rates, np.float64, dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _capi.check(lib, lib.uu3d_one_euro_tracks(_ptr(x), _ptr(out), G, Cn, _ptr(plan[0]), _ptr(plan[1]), _ptr(d_rates), len(lens), _ptr(state),
+                                                  filt.min_cutoff, filt.beta, filt.d_cutoff, C.c_void_p(stream)), None)
+    return out
+
+
 def _device_tracks(tracks, device):
     """The tracks on the device -> (list of (T_i, J, 2) tensors, J, frames given per track)."""
     tr = [_device_track(t, device) for t in tracks]
@@ -1161,7 +1318,7 @@ def resampled_pose_table(tracks, device, fps, resolutions=None, valid=None, mode
 
 def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, flip=None, keyframes_only=False, reuse_frames=True,
                    batch_size=None, root_relative=True, depth=None, lengths=None, graph=True, valid=None, return_valid=False, fps=None, out_fps=None,
-                   model_fps=50, repair_joints=None, keypoints=None, camera=None, min_root_joints=DEFAULT_MIN_ROOT_JOINTS):
+                   model_fps=50, repair_joints=None, keypoints=None, camera=None, min_root_joints=DEFAULT_MIN_ROOT_JOINTS, smooth=None):
     """One 3D pose per frame for each 2D keypoint track -> list of (T_i, J, 3) float32 tensors on the model's device (views of one buffer).
 
     ``tracks``: list of (T_i, J, 2) arrays or tensors, on the host or the device, at the frame rate the config was trained for (nothing is
@@ -1250,8 +1407,21 @@ def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, fl
     behind the last solved frame (uu3d_root_trajectory; ``root_trajectory_host``).  ``root_state``: 1 solved here, 2 interpolated or held,
     0 the track has no solved frame (zeros).  With ``root_relative=False`` the solve takes the pose as returned.  No accuracy is claimed:
     the model's scale error goes 1:1 into the depth.  The live form is ``StreamSession(camera=...)`` / ``replay_tracks(camera=...)``: the
-    same solve per emitted pose at any ``lookahead``, the last solved root held where a frame is not solved (causal: no interpolation)."""
+    same solve per emitted pose at any ``lookahead``, the last solved root held where a frame is not solved (causal: no interpolation).
+
+    Steady output -- ``smooth``: None = today's call, the same bits, no further launch or buffer.  True (the defaults), a ``OneEuro`` or a
+    pair (pose_filter, root_filter), either of which may be None (``check_smooth``; a root filter without ``camera``: ValueError): the
+    returned poses -- and, with ``camera``, the returned roots -- go once through the One-Euro filter, an exponential smoother whose
+    cut-off rises with the speed of the signal (uu3d_one_euro_tracks, one launch each; ``one_euro`` is the launch alone; the rule in numpy:
+    ``one_euro_host``, and the result equals it on the output of the call without ``smooth``, bit for bit).  A channel is one coordinate of
+    one joint (C = 3 J) or of the root (C = 3); the sample rate is that of the RETURNED frames: ``model_fps`` for the plain call and with
+    ``keyframes_only``, the track's ``fps`` with ``fps``, ``out_fps`` with ``out_fps``.  The roots are solved from the UNFILTERED poses,
+    exactly as without ``smooth``; a root row of state 0 (zeros) is passed through and takes no sample; ``root_state`` and the flags are
+    unchanged, and the root joint of a root-relative pose stays exactly 0.  The filter is CAUSAL: frame i depends on the frames up to i
+    only, so the offline result lags behind the motion exactly as the live one (``StreamSession(smooth=...)``) does.  A zero-lag,
+    two-pass offline smoother is out of scope, and so is any accuracy or jitter figure."""
     import torch
+    pose_filter, root_filter = check_smooth(smooth, camera is not None)
     if camera is not None:
         cameras, min_root_joints = check_cameras(camera, len(tracks)), check_min_root_joints(min_root_joints)
         if int(config.NUM_KEYPOINTS) > MAX_ROOT_JOINTS:
@@ -1306,7 +1476,12 @@ def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, fl
         left, right, weight, _ = evaluation.keyframe_plan(frame_idx, stride, rows=rows)
     out = assemble_tracks(raw[0], raw[1] if flip else None, left, right, weight, flip_order=cfg.AUGM_FLIP_KEYPOINT_ORDER,
                           root=int(cfg.ROOT_KEYTPOINT) if root_relative else -1)
-    poses = list(torch.split(out, [int(n) for n in lens], 0))
+    shown = out                                                       # what is returned: the poses, or the poses filtered
+    if pose_filter is not None or root_filter is not None:
+        out_rate = model_fps if fps is None else (rates if out_fps is None else frame_rates(out_fps, len(tracks)))
+    if pose_filter is not None:
+        shown = one_euro(out, lens, out_rate, pose_filter)
+    poses = list(torch.split(shown, [int(n) for n in lens], 0))
     placed = ()
     if camera is not None:
         given = np.array([len(t) for t in tracks], np.int64)
@@ -1323,6 +1498,8 @@ def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, fl
             where = given_positions(lens, [f / o for f, o in zip(rates, frame_rates(out_fps, len(given)))])
         solved_roots, solved = solve_roots(at_given, table.source[0], cameras, table.source[1], min_root_joints, lens=given)
         roots, root_state = root_trajectory(solved_roots, solved, given, where)
+        if root_filter is not None:
+            roots = one_euro(roots, lens, out_rate, root_filter, state=root_state)
         sizes = [int(n) for n in lens]
         placed = (list(torch.split(roots, sizes, 0)), list(torch.split(root_state, sizes, 0)))
     if not return_valid:
@@ -1380,7 +1557,24 @@ def parse_args(argv=None):
                         "position of the skeleton's root in the camera's space, and <key>__root_state (T,) per track")
     p.add_argument("--min_root_joints", type=int, default=DEFAULT_MIN_ROOT_JOINTS, metavar="N",
                    help="the fewest observed joints a frame's root is solved from (with --camera)")
-    return p.parse_args(argv)
+    p.add_argument("--smooth", type=float, nargs=3, metavar=("MIN_CUTOFF", "BETA", "D_CUTOFF"), default=None,
+                   help="pass the written poses through a One-Euro filter (Hz, 1 / unit speed, Hz) at the rate of the written frames; causal, it lags")
+    p.add_argument("--smooth_root", type=float, nargs=3, metavar=("MIN_CUTOFF", "BETA", "D_CUTOFF"), default=None,
+                   help="the same for the roots (needs --camera)")
+    args = p.parse_args(argv)
+    if args.smooth_root is not None and args.camera is None:
+        p.error("--smooth_root needs --camera: without it no roots are written")
+    return args
+
+
+def smooth_option(args):
+    """--smooth / --smooth_root of a command line -> the ``smooth`` keyword ({} when neither is given)."""
+    if args.smooth is None and args.smooth_root is None:
+        return {}
+    try:
+        return {"smooth": (None if args.smooth is None else OneEuro(*args.smooth), None if args.smooth_root is None else OneEuro(*args.smooth_root))}
+    except ValueError as e:
+        raise SystemExit(f"--smooth / --smooth_root: {e}") from None
 
 
 def split_scores(names, tracks, J, min_score, source="input"):
@@ -1423,6 +1617,7 @@ def main(argv=None):
         if ms is None:
             raise SystemExit("--keyframes_only needs a mask stride")
         lengths = [(len(t) - 1) * int(ms) + 1 for t in tracks]
+    steady = smooth_option(args)
     model = _load_model(config, args.weights)
     if args.out_fps is not None and args.fps is None:
         raise SystemExit("--out_fps needs --fps")
@@ -1444,7 +1639,7 @@ def main(argv=None):
             raise SystemExit(f"{args.input}: a key ending in __root or __root_state would collide with the arrays --camera writes")
         place = {"camera": tuple(args.camera), "min_root_joints": args.min_root_joints}
     poses = predict_tracks(model, config, tracks, resolutions=None if args.resolution is None else tuple(args.resolution), mask_stride=ms,
-                           keyframes_only=args.keyframes_only, lengths=lengths, **missing, **rate, **skeleton, **place)
+                           keyframes_only=args.keyframes_only, lengths=lengths, **missing, **rate, **skeleton, **place, **steady)
     arrays = {}
     if place:
         poses, roots, root_state = poses

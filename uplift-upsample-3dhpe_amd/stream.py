@@ -111,9 +111,27 @@ people of a video share one space.  Not together with ``out_fps`` (ValueError: t
 change).  No accuracy is claimed: the model's scale error goes 1:1 into the depth.  ``camera=None`` is the session above, bit for bit: no
 further launch or buffer.
 
+Steady output -- ``StreamSession(..., smooth=F)``: the root above is solved tick by tick and nothing ties one tick's root to the next, and
+the poses carry the detector's frame-to-frame noise.  ``smooth`` -- True (the defaults), a ``predict.OneEuro(min_cutoff, beta, d_cutoff)``
+for poses and roots alike, or a pair (pose_filter, root_filter), either None -- puts the One-Euro filter (Casiez, Roussel, Vogel 2012)
+behind the tick, on the device: an exponential smoother whose cut-off rises with the speed of the signal, steady while a person stands,
+little lag while they move (the rule: ``predict.one_euro_host``; include/uu3d.h, STEADY OUTPUT).  A channel is one coordinate of one joint
+of one slot, or of its root.  Whenever an active slot's pose is fresh, each of its channels takes ONE sample at rate / n, n the frames
+since the channel's previous sample (the frame counters are ``source_frames``; the rate is ``model_fps``, or ``fps`` in a session with
+``fps``); a root of state 0 (zeros) is passed through and takes no sample, a held root (state 2) is a sample like any other.  A slot that
+is not fresh returns the filter's last output.  ``push`` returns the filtered buffers in place of the poses and, with ``camera``, the
+roots; ``raw_poses`` / ``raw_roots`` are the unfiltered ones, and uu3d_stream_root keeps solving against the unfiltered pose.  The
+launches (uu3d_stream_one_euro, one per filtered buffer) are the LAST steps of the one captured tick -- with ``fps`` behind
+uu3d_stream_timed_emit and the root solve, not captured --; ``push`` never waits.  ``reset`` and a birth at a ``push_detections`` tick
+clear the filter with everything else.  ``LiveOneEuro`` owns the state block and the two launches and runs without a model;
+``LiveOneEuroHost`` is the same state machine in numpy, and the device equals it bit for bit.  Not together with ``out_fps`` (ValueError:
+several rows per push).  No accuracy or jitter figure is claimed.  ``smooth=None`` is the session above, bit for bit: no further launch
+or buffer.
+
     python -m uplift_upsample_3dhpe_amd.stream --config C --weights W.h5 --input tracks.npz --output out.npz [--lookahead A] [--resolution W H]
                                                  [--mask_missing] [--fps F [--out_fps G]] [--repair_joints G [--min_score S]] [--keypoints NAME]
-                                                 [--camera FX FY CX CY [--min_root_joints N]]
+                                                 [--camera FX FY CX CY [--min_root_joints N]] [--smooth MIN_CUTOFF BETA D_CUTOFF]
+                                                 [--smooth_root MIN_CUTOFF BETA D_CUTOFF]
 """
 import argparse
 import ctypes as C
@@ -124,10 +142,10 @@ import numpy as np
 
 from . import _capi
 from ._capi import ptr as _ptr
-from .predict import (ASSOCIATION_DEFAULTS, DEFAULT_MIN_ROOT_JOINTS, KEYPOINT_PRESETS, MAX_ROOT_JOINTS, _load_model, check_association,
-                      check_cameras, check_keypoint_inputs, check_min_root_joints, check_repair_joints, check_resolutions, check_valid,
-                      input_joints, keypoint_map, solve_roots_host, split_scores)
-from .rates import (RatePlan, _rate_argument, max_lookahead, newest_model_frame, out_push_plan, push_plan,  # noqa: F401 (re-exported)
+from .predict import (ASSOCIATION_DEFAULTS, DEFAULT_MIN_ROOT_JOINTS, KEYPOINT_PRESETS, MAX_ROOT_JOINTS, MAX_SMOOTH_CHANNELS, OneEuro, _load_model,
+                      check_association, check_cameras, check_keypoint_inputs, check_min_root_joints, check_repair_joints, check_resolutions,
+                      check_smooth, check_valid, input_joints, keypoint_map, one_euro_sample, smooth_option, solve_roots_host, split_scores)
+from .rates import (RatePlan, _rate_argument, frame_rate, max_lookahead, newest_model_frame, out_push_plan, push_plan,  # noqa: F401 (re-exported)
                     rate_plan, session_strides)
 
 
@@ -192,7 +210,7 @@ def staged_frames(repair_joints, mask_stride):
     return int(repair_joints) // int(mask_stride) + 2
 
 
-LIVE_OPTIONS = ("repair_joints", "keypoints", "camera", "min_root_joints")                     # the keywords ``StreamSession`` and ``replay_tracks`` take from **options
+LIVE_OPTIONS = ("repair_joints", "keypoints", "camera", "min_root_joints", "smooth")           # the keywords ``StreamSession`` and ``replay_tracks`` take from **options
 DETECTION_OPTIONS = ("detections",) + tuple(ASSOCIATION_DEFAULTS)    # ... and the ones only ``StreamSession`` takes: per-frame detections
 
 
@@ -352,6 +370,138 @@ class LiveRootHost(object):
         return self.root.copy(), self.state
 
 
+def _live_filter_arguments(slots, channels, rate, filt, lookahead):
+    slots, channels, lookahead = int(slots), int(channels), int(lookahead)
+    if slots < 1 or not 1 <= channels <= MAX_SMOOTH_CHANNELS or lookahead < 0:
+        raise ValueError(f"slots >= 1, channels in [1, {MAX_SMOOTH_CHANNELS}] and lookahead >= 0, got {slots}, {channels}, {lookahead}")
+    if not isinstance(filt, OneEuro):
+        raise ValueError(f"filt must be a predict.OneEuro, got {filt!r}")
+    return slots, channels, float(frame_rate(rate)), filt, lookahead
+
+
+class LiveOneEuroHost(object):
+    """The rule of uu3d_stream_one_euro in numpy, written to be read: the live form of ``predict.one_euro_host``.  State per slot and
+    channel -- xh, dxh (float64), ``last``: the frame index of the channel's last sample, ``taken``: whether it has taken one.
+    ``step(values (slots, C) float32, frames (slots,), fresh (slots,), active (slots,) or None, state (slots,) or None)`` -> (slots, C)
+    float32.  ``frames``: each slot's frame counter AFTER the push; the fresh value belongs to frame f = frames - 1 - lookahead.
+      an active slot whose value is fresh (and frames >= 1): per channel one sample with n = f - last, anything below 1 counting as 1, at
+          rate / n (``predict.one_euro_sample``); the first one is taken as given.  A non-finite value -- or, with ``state[slot] == 0``,
+          the whole row -- is passed through unchanged and touches nothing.
+      any other slot returns xh rounded once, zeros before the first sample.
+    ``reset(slots=None)``: the chosen slots (None: all) have taken no sample."""
+
+    def __init__(self, slots, channels, rate, filt, lookahead=0):
+        self.slots, self.channels, self.rate, self.filt, self.lookahead = _live_filter_arguments(slots, channels, rate, filt, lookahead)
+        shape = (self.slots, self.channels)
+        self.xh, self.dxh = np.zeros(shape, np.float64), np.zeros(shape, np.float64)
+        self.last, self.taken = np.zeros(shape, np.int64), np.zeros(shape, bool)
+
+    def reset(self, slots=None):
+        which = slice(None) if slots is None else np.asarray(slots, np.int64).reshape(-1)
+        for a in (self.xh, self.dxh, self.last, self.taken):
+            a[which] = 0
+
+    def step(self, values, frames, fresh, active=None, state=None):
+        values = np.asarray(values, np.float32).reshape(self.slots, self.channels)
+        frames = np.asarray(frames, np.int64).reshape(self.slots)
+        fresh = np.asarray(fresh).reshape(self.slots) != 0
+        active = np.ones(self.slots, bool) if active is None else np.asarray(active).reshape(self.slots) != 0
+        keep = np.ones(self.slots, bool) if state is None else np.asarray(state).reshape(self.slots) != 0
+        out = np.zeros((self.slots, self.channels), np.float32)
+        with np.errstate(all="ignore"):
+            for i in range(self.slots):
+                if not (active[i] and fresh[i] and frames[i] >= 1):
+                    out[i] = np.where(self.taken[i], self.xh[i].astype(np.float32), np.float32(0))
+                    continue
+                if not keep[i]:
+                    out[i] = values[i]
+                    continue
+                f = int(frames[i]) - 1 - self.lookahead
+                x = values[i].astype(np.float64)
+                ok = np.isfinite(x)
+                n = np.maximum(f - self.last[i], 1)
+                r = np.float64(self.rate) / n.astype(np.float64)
+                nxh, ndxh = one_euro_sample(x, r, self.filt, self.xh[i], self.dxh[i])
+                later, start = ok & self.taken[i], ok & ~self.taken[i]
+                self.xh[i] = np.where(later, nxh, np.where(start, x, self.xh[i]))
+                self.dxh[i] = np.where(later, ndxh, np.where(start, 0.0, self.dxh[i]))
+                self.last[i] = np.where(ok, f, self.last[i])
+                self.taken[i] |= ok
+                out[i] = np.where(ok, self.xh[i].astype(np.float32), values[i])
+        return out
+
+
+class LiveOneEuro(object):
+    """The live One-Euro filter on the device: the thin owner of the state block of uu3d_stream_one_euro and of its two launches
+    (``LiveOneEuroHost`` is the same state machine in numpy; the device equals it bit for bit).  ``slots`` rows of ``channels`` float32
+    values each; ``rate``: the frames' rate in Hz (as ``rates.frame_rate`` takes it); ``filt``: a ``predict.OneEuro``; ``lookahead``: the
+    fresh value belongs to frame frames - 1 - lookahead.  ``out``: the (slots, channels) float32 buffer every step writes.
+    ``step(values, frames, fresh, active, state=None, stream=None)``: device tensors -- values (slots, channels) float32 contiguous (only
+    read), frames (slots,) int32, fresh / active / state (slots,) uint8 or bool -- -> ``out``; enqueues on ``stream`` (None: the current
+    one) and never waits.  ``reset(slots=None)``: the given slots (indices; None = all) have taken no sample; ``reset_mask(mask)`` takes a
+    (slots,) uint8 device tensor instead.  ``launch(...)`` / ``reset_launch()``: the two calls as launch-table entries (function,
+    arguments up to the slot mask / the stream), for a session that replays them."""
+
+    def __init__(self, slots, channels, rate, filt, lookahead=0, device="cuda"):
+        import torch
+        self.slots, self.channels, self.rate, self.filt, self.lookahead = _live_filter_arguments(slots, channels, rate, filt, lookahead)
+        self._torch, self._lib = torch, _capi.load_library()
+        self.device = torch.device(device)
+        size = int(self._lib.uu3d_stream_one_euro_bytes(self.slots, self.channels))
+        if size == 0:
+            raise ValueError(f"slots = {self.slots}, channels = {self.channels} are out of uu3d_stream_one_euro's range")
+        self._state = torch.zeros(size, dtype=torch.uint8, device=self.device)
+        self.out = torch.zeros((self.slots, self.channels), dtype=torch.float32, device=self.device)
+
+    def _check(self, t, shape, dtypes, name):
+        if tuple(t.shape) != shape or t.dtype not in dtypes or not t.is_contiguous() or t.device != self.out.device:
+            raise ValueError(f"{name} must be a contiguous {shape} tensor of {' / '.join(str(d) for d in dtypes)} on {self.out.device}")
+        return t
+
+    def launch(self, values, frames, fresh, active, state=None):
+        torch = self._torch
+        T, flags = self.slots, (torch.uint8, torch.bool)
+        if values.dim() < 1 or int(values.shape[0]) != T or values.numel() != T * self.channels:       # ((slots, J, 3) passes as (slots, 3 J))
+            raise ValueError(f"values must be ({T}, {self.channels}), got {tuple(values.shape)}")
+        self._check(values, tuple(values.shape), (torch.float32,), "values")
+        self._check(frames, (T,), (torch.int32,), "frames")
+        for t, name in ((fresh, "fresh"), (active, "active")) + (() if state is None else ((state, "state"),)):
+            self._check(t, (T,), flags, name)
+        f = self.filt
+        return (self._lib.uu3d_stream_one_euro, (T, self.channels, self.lookahead, _ptr(self._state), _ptr(frames), _ptr(active), _ptr(fresh),
+                                                 _ptr(values), _ptr(state), self.rate, f.min_cutoff, f.beta, f.d_cutoff, _ptr(self.out)))
+
+    def reset_launch(self):
+        return (self._lib.uu3d_stream_one_euro_reset, (self.slots, self.channels, _ptr(self._state)))
+
+    def _enqueue(self, call, stream):
+        torch = self._torch
+        fn, args = call
+        with torch.cuda.device(self.out.device):
+            st = torch.cuda.current_stream(self.out.device) if stream is None else stream
+            _capi.check(self._lib, fn(*args, C.c_void_p(st.cuda_stream)), None)
+
+    def step(self, values, frames, fresh, active, state=None, stream=None):
+        self._enqueue(self.launch(values, frames, fresh, active, state), stream)
+        return self.out
+
+    def reset_mask(self, mask=None, stream=None):
+        fn, args = self.reset_launch()
+        if mask is not None:
+            self._check(mask, (self.slots,), (self._torch.uint8, self._torch.bool), "mask")
+        self._enqueue((fn, args + (_ptr(mask),)), stream)
+
+    def reset(self, slots=None, stream=None):
+        torch = self._torch
+        mask = None
+        if slots is not None:
+            h = np.zeros(self.slots, np.uint8)
+            h[np.asarray(slots, np.int64).reshape(-1)] = 1
+            with torch.cuda.device(self.out.device):
+                mask = torch.from_numpy(h).pin_memory().to(self.out.device, non_blocking=True)
+        self.reset_mask(mask, stream)
+
+
 class StreamSession(object):
 
     def __init__(self, model, config, slots, resolutions=None, mask_stride=None, flip=None, lookahead=0, root_relative=True, graph=True,
@@ -391,10 +541,14 @@ class StreamSession(object):
         camera's intrinsics (fx, fy, cx, cy) in the units of the pushed frames, one tuple or one per slot (with ``detections`` one tuple
         only): the module docstring's "Live absolute root" -- ``push`` / ``push_detections`` then return (poses, fresh, roots (slots, 3)
         float32, root_state (slots,) uint8).  ``min_root_joints`` (default 6, an int >= 2; ValueError without ``camera``): the fewest used
-        joints a frame's root is solved from.  Models of more than ``predict.MAX_ROOT_JOINTS`` joints and ``out_fps``: ValueError."""
-        repair_joints, keypoints, camera, min_root_joints, detections, *rule = _live_options(options, "StreamSession", LIVE_OPTIONS + DETECTION_OPTIONS)
+        joints a frame's root is solved from.  Models of more than ``predict.MAX_ROOT_JOINTS`` joints and ``out_fps``: ValueError.
+        ``smooth`` (keyword only, from ``options`` as well): None = the poses and roots as they are solved (the session above, bit for
+        bit).  True, a ``predict.OneEuro`` or a pair (pose_filter, root_filter), either of which may be None (``predict.check_smooth``; a
+        root filter without ``camera``: ValueError): the module docstring's "Steady output" -- ``push`` / ``push_detections`` return the
+        filtered buffers in place of poses and roots; ``raw_poses`` / ``raw_roots`` are the unfiltered ones.  With ``out_fps``: ValueError."""
+        repair_joints, keypoints, camera, min_root_joints, smooth, detections, *rule = _live_options(options, "StreamSession", LIVE_OPTIONS + DETECTION_OPTIONS)
         res = self._init_plan(model, config, slots, resolutions, mask_stride, flip, lookahead, graph, missed_detections, fps, model_fps, out_fps,
-                              repair_joints, keypoints, detections, dict(zip(ASSOCIATION_DEFAULTS, rule)), camera, min_root_joints)
+                              repair_joints, keypoints, detections, dict(zip(ASSOCIATION_DEFAULTS, rule)), camera, min_root_joints, smooth)
         import torch
         self._torch = torch
         self._lib = _capi.load_library()
@@ -410,11 +564,16 @@ class StreamSession(object):
 
     # ---- construction: checks and plan, layout and state, buffers, launch tables (then the capture) ---------------------------------
     def _init_plan(self, model, config, slots, resolutions, mask_stride, flip, lookahead, graph, missed_detections, fps, model_fps, out_fps,
-                   repair_joints=None, keypoints=None, detections=None, rule=None, camera=None, min_root_joints=None):
+                   repair_joints=None, keypoints=None, detections=None, rule=None, camera=None, min_root_joints=None, smooth=None):
         """Every refusal that needs no device, and the session's plan.  -> the checked resolutions."""
         slots, lookahead = int(slots), int(lookahead)
         if slots < 1:
             raise ValueError("slots >= 1")
+        self.pose_filter, self.root_filter = check_smooth(smooth, camera is not None)
+        if (self.pose_filter is not None or self.root_filter is not None) and out_fps is not None:
+            raise ValueError("smooth together with out_fps is not supported: a push then returns several rows per slot, and the live filter "
+                             "takes one sample per slot and push (multi-row emits are out of scope)")
+        self.smooth_rate = frame_rate(model_fps if fps is None else fps)     # the rate of the frames a push returns
         self.cameras, self.min_root_joints = None, None
         if camera is not None:
             self.cameras = check_cameras(camera, slots, per="slot")
@@ -588,6 +747,14 @@ class StreamSession(object):
             self._roots = zeros((T, 3), dtype=torch.float32)
             self._root_flag = zeros((T,), dtype=torch.uint8)
             self._result = self._result + (self._roots, self._root_flag)
+        # steady output: a live One-Euro filter per filtered buffer -- its state block and the buffer push returns in the raw one's place
+        self._pose_smoother = self._root_smoother = None
+        if self.pose_filter is not None:
+            self._pose_smoother = LiveOneEuro(T, 3 * J, self.smooth_rate, self.pose_filter, self.lookahead, dev)
+            self._result = (self._pose_smoother.out.view(T, J, 3),) + self._result[1:]
+        if self.root_filter is not None:
+            self._root_smoother = LiveOneEuro(T, 3, self.smooth_rate, self.root_filter, self.lookahead, dev)
+            self._result = self._result[:2] + (self._root_smoother.out,) + self._result[3:]
 
     def _init_launch_tables(self):
         """All arguments are the same at every push (the buffers never move), so the mode is decided here, once: every launch of the
@@ -595,7 +762,7 @@ class StreamSession(object):
           _tick_steps   the steps of one (sub-)tick, in order -- what the graph captures
           _push_before  / _push_after   the launches of a push around its sub-ticks (a session with a rate; not captured)
           _reset_call   the reset of the session's kind; the slot mask and the stream follow its arguments (_reset_more: what a session
-                        with repair_joints or a camera resets beside it)"""
+                        with repair_joints, a camera or smooth resets beside it)"""
         lib, m = self._lib, self.model
         h, cfg, state = m._h, C.byref(self._cfg), _ptr(self._state)
         kp, res, order, active, staged = _ptr(self._kp), _ptr(self._res), _ptr(self._order), _ptr(self._active), _ptr(self._staged)
@@ -643,6 +810,7 @@ class StreamSession(object):
                                            _ptr(self._out), kp, _ptr(self._valid_in), int(self._valid_in is not None and self._valid_in.dim() == 2),
                                            _ptr(self._cams), self.min_root_joints, _ptr(self._roots), _ptr(self._root_flag)))
             self._reset_more = self._reset_more + [(lib.uu3d_stream_root_reset, (T, J, self.lookahead, _ptr(self._root_state)))]
+        self._reset_more = self._reset_more + [f.reset_launch() for f in (self._pose_smoother, self._root_smoother) if f is not None]
         # per-frame detections: the association in front of everything -- it writes the frame, the flags, `active` and the born mask --, then
         # the resets of the slots born at this tick, with the mask on the device
         if self.detections is not None:
@@ -662,8 +830,15 @@ class StreamSession(object):
             outp = C.byref(self._outp)
             self._push_after = [(lib.uu3d_stream_timed_emit_multi, (h, cfg, rate, outp, state, _ptr(self._poses), _ptr(self._count)))]
             self._reset_call = (lib.uu3d_stream_out_reset, (h, cfg, rate, outp, state))
-        if root is not None:                                         # the last step: behind the emit that wrote the pose it solves
-            (self._tick_steps if self.rate is None else self._push_after).append(root)
+        last = self._tick_steps if self.rate is None else self._push_after
+        if root is not None:                                         # behind the emit that wrote the pose it solves
+            last.append(root)
+        # steady output: the last steps of all -- they read what the emit and the root solve wrote and write buffers of their own, so the
+        # root is solved against the unfiltered pose; their resets join the session's (also for a slot born on the device)
+        if self._pose_smoother is not None:
+            last.append(self._pose_smoother.launch(self._out, self._source_frames, self._fresh, self._active))
+        if self._root_smoother is not None:
+            last.append(self._root_smoother.launch(self._roots, self._source_frames, self._fresh, self._active, self._root_flag))
 
     # ---- the steps of a tick, on ``stream`` ------------------------------------------------------------------------------------------
     def _run(self, steps, stream):
@@ -753,6 +928,7 @@ class StreamSession(object):
         A session with ``camera``: -> (poses, fresh, roots (slots, 3) float32, root_state (slots,) uint8), the session's own buffers as
         well: ``poses[i] + roots[i]`` stands in the camera's space; ``root_state[i]``: 1 solved at this push, 2 the slot's last solved
         root is held, 0 no frame of the slot was solved yet (zeros).  A slot that is not fresh returns its previous root and state.
+        A session with ``smooth``: the same tuple with the filtered buffers in place of ``poses`` and, with a root filter, of ``roots``.
         Enqueues on the current stream and returns; never waits for the device."""
         torch = self._torch
         m = self.model
@@ -872,7 +1048,8 @@ class StreamSession(object):
 
     def reset(self, slots=None):
         """The given slots (indices; None = all) start a new track: zero frames, held pose 0, with ``out_fps`` output counter 0, with
-        ``repair_joints`` no observation of any joint, with ``camera`` no filed frame, no held root and root state 0.  A session with ``detections``: the tracks in those slots END and the slots are
+        ``repair_joints`` no observation of any joint, with ``camera`` no filed frame, no held root and root state 0, with ``smooth`` no
+        sample taken.  A session with ``detections``: the tracks in those slots END and the slots are
         free (the next unmatched person takes the lowest one, under a new id); None also sets the id and dropped counters back to 0.
         Stream-ordered like ``push``."""
         torch = self._torch
@@ -909,6 +1086,21 @@ class StreamSession(object):
     def source_frames(self):
         """Source frames pushed per slot since its last reset, (slots,) int32 on the device; without ``fps`` the same tensor as ``frames``."""
         return self._source_frames
+
+    @property
+    def raw_poses(self):
+        """(slots, J, 3) float32 on the device: the poses as the tick emits them, unfiltered -- in a session without ``smooth`` the buffer
+        ``push`` returns.  Not with ``out_fps`` (AttributeError)."""
+        if self.max_out is not None:
+            raise AttributeError("raw_poses: a session with out_fps returns several rows per slot")
+        return self._out
+
+    @property
+    def raw_roots(self):
+        """(slots, 3) float32 on the device (sessions with ``camera``): the roots as they are solved, unfiltered."""
+        if self.cameras is None:
+            raise AttributeError("raw_roots needs a session with camera")
+        return self._roots
 
     @property
     def joint_state(self):
@@ -980,10 +1172,12 @@ def replay_tracks(model, config, tracks, resolutions=None, mask_stride=None, fli
     then be (T_i, J), one flag per joint.  ``keypoints=M`` (from ``options`` as well): a session with ``keypoints``; the tracks are
     (T_i, K_in, 2) and per-joint entries of ``valid`` (T_i, K_in).  ``camera=C, min_root_joints=N`` (from ``options`` as well): a session with
     ``camera`` -- the roots (T_i, 3) float32 and root states (T_i,) uint8 the session returned at each tick are appended per track:
-    -> (poses, fresh, roots, root_state)."""
+    -> (poses, fresh, roots, root_state).  ``smooth=F`` (from ``options`` as well): a session with ``smooth``; the same return, filtered."""
     import torch
-    repair_joints, keypoints, camera, min_root_joints = _live_options(options, "replay_tracks")
+    repair_joints, keypoints, camera, min_root_joints, smooth = _live_options(options, "replay_tracks")
     place = {} if camera is None and min_root_joints is None else {"camera": camera, "min_root_joints": min_root_joints}
+    if smooth is not None:
+        place["smooth"] = smooth
     lens = [int(len(t)) for t in tracks]
     T, ticks = len(tracks), max(lens)
     K = J = int(np.asarray(tracks[0]).shape[1])                      # joints pushed, joints returned
@@ -1054,7 +1248,7 @@ def replay_detections(model, config, detections, counts=None, valid=None, slots=
     """Push ONE video's per-frame detections tick by tick through a ``StreamSession(detections=D)`` and collect the poses per track id.
     ``detections`` (T, D, K, 2); ``counts`` (T,) or None; ``valid``: None, (T, D) or (T, D, K); ``slots`` (None: D); ``resolutions``: None
     or one (w, h); ``options``: ``max_age`` / ``max_dist`` / ``min_common``, ``repair_joints``, ``keypoints``, ``camera`` (one tuple) /
-    ``min_root_joints``.
+    ``min_root_joints``, ``smooth``.
     -> a list of (track_id, first_frame, poses (n, J, 3) float32, fresh (n,) bool) by track id, host arrays: what the session returned for
     the track's slot at the ticks first_frame .. first_frame + n - 1, the ticks the track was alive (its trailing missing frames
     included; ``predict.predict_detections`` ends a track at its last matched frame).  With ``camera`` every tuple carries two more
@@ -1132,7 +1326,15 @@ def parse_args(argv=None):
                         "position of the skeleton's root in the camera's space at every tick, and NAME__root_state (T,) per track; not with --out_fps")
     p.add_argument("--min_root_joints", type=int, default=None, metavar="N",
                    help=f"the fewest observed joints a frame's root is solved from (with --camera; default {DEFAULT_MIN_ROOT_JOINTS})")
+    p.add_argument("--smooth", type=float, nargs=3, metavar=("MIN_CUTOFF", "BETA", "D_CUTOFF"), default=None,
+                   help="pass the poses of every tick through a live One-Euro filter (Hz, 1 / unit speed, Hz); not with --out_fps")
+    p.add_argument("--smooth_root", type=float, nargs=3, metavar=("MIN_CUTOFF", "BETA", "D_CUTOFF"), default=None,
+                   help="the same for the roots (needs --camera)")
     args = p.parse_args(argv)
+    if args.smooth_root is not None and args.camera is None:
+        p.error("--smooth_root needs --camera: without it no roots are written")
+    if (args.smooth is not None or args.smooth_root is not None) and args.out_fps is not None:
+        p.error("--smooth / --smooth_root with --out_fps is not supported")
     if args.out_fps is not None and args.fps is None:
         p.error("--out_fps needs --fps")
     if args.min_root_joints is not None and args.camera is None:
@@ -1184,6 +1386,7 @@ def main(argv=None):
             raise SystemExit(f"--camera: {e}") from None
         if any(k.endswith(("__root", "__root_state")) for k in names):
             raise SystemExit(f"{args.input}: a key ending in __root or __root_state would collide with the arrays --camera writes")
+    place.update(smooth_option(args))
     model = _load_model(config, args.weights)
     poses, fresh, *rs = replay_tracks(model, config, tracks, resolutions=None if args.resolution is None else tuple(args.resolution),
                                       lookahead=args.lookahead, **missing, **skeleton, **place,
