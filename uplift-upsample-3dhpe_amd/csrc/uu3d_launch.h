@@ -160,24 +160,26 @@ inline int launch_colsum(const float* x, int ldx, int R, int C, int period, cons
 // LayerNorm backward in two launches: the row kernel (dx, per-workgroup partial dgamma / dbeta in scratch; returns the number of
 // partial slices) and the combine of the partials, which may run on another stream behind the first.
 // accumulate: dx = res + d x (res == nullptr: dx itself, in place).
+// Returns 0 without a launch when scratch cannot hold even one workgroup's partials (2 D floats) or there are no rows.
 inline int launch_ln_bwd_rows(const float* x, const float* dy, const float2* stats, const float* gamma, int ld, int D, int M, float* dx,
                               int accumulate, const float* res, float* scratch, size_t scratch_floats, hipStream_t stream,
                               const LnBwdGated gated = LnBwdGated{nullptr, 1.f, 1, nullptr}) {
     if (!res) res = dx;
+    if (M < 1 || D < 1 || (size_t)2 * D > scratch_floats) return 0;
     // wide rows (D = 384): >= 500 workgroups at M = 4544 (8 rows per wave left 114 of 256 CUs idle), <= 2048 partial rows;
     // the spatial stack's D = 32 rows are cheap and many (77 k): fewer, longer workgroups keep the combine short
     if ((D == 32 || D == 64) && ld % 4 == 0) {          // narrow rows: D / 4 lanes per row, 256 * 4 / D rows per workgroup at once
         const int RG = 1024 / D;
         int rpg = std::max(4, (M + RG * 512 - 1) / (RG * 512));
         int wgs = (M + RG * rpg - 1) / (RG * rpg);
-        while ((size_t)wgs * 2 * D > scratch_floats) { rpg *= 2; wgs = (M + RG * rpg - 1) / (RG * rpg); }
+        while (wgs > 1 && (size_t)wgs * 2 * D > scratch_floats) { rpg *= 2; wgs = (M + RG * rpg - 1) / (RG * rpg); }
         if (D == 32) hipLaunchKernelGGL(ln_bwd_narrow_kernel<8>, dim3(wgs), dim3(256), 0, stream, x, dy, stats, gamma, ld, M, rpg, dx, res, accumulate, scratch, gated);
         else hipLaunchKernelGGL(ln_bwd_narrow_kernel<16>, dim3(wgs), dim3(256), 0, stream, x, dy, stats, gamma, ld, M, rpg, dx, res, accumulate, scratch, gated);
         return wgs;
     }
     int rpw = (D > 64) ? std::max(2, (M + 4 * 2048 - 1) / (4 * 2048)) : std::max(8, (M + 4 * 512 - 1) / (4 * 512));
     int wgs = (M + 4 * rpw - 1) / (4 * rpw);
-    while ((size_t)wgs * 2 * D > scratch_floats) { rpw *= 2; wgs = (M + 4 * rpw - 1) / (4 * rpw); }
+    while (wgs > 1 && (size_t)wgs * 2 * D > scratch_floats) { rpw *= 2; wgs = (M + 4 * rpw - 1) / (4 * rpw); }
     if (D <= 512) hipLaunchKernelGGL(ln_bwd_kernel<2>, dim3(wgs), dim3(256), 0, stream, x, dy, stats, gamma, ld, D, M, rpw, dx, res, accumulate, scratch, gated);
     else hipLaunchKernelGGL(ln_bwd_kernel<4>, dim3(wgs), dim3(256), 0, stream, x, dy, stats, gamma, ld, D, M, rpw, dx, res, accumulate, scratch, gated);
     return wgs;
@@ -195,6 +197,8 @@ inline void launch_ln_bwd_combine(const float* scratch, int D, int slices, float
 
 inline int launch_ln_bwd(const float* x, const float* dy, const float2* stats, const float* gamma, int ld, int D, int M, float* dx,
                          int accumulate, float* dgamma, float* dbeta, int acc_params, float* scratch, size_t scratch_floats, hipStream_t stream) {
+    if (M < 1 || D < 1) return UU3D_ERR_INVALID_ARGUMENT;
+    if ((size_t)2 * D > scratch_floats) return UU3D_ERR_WORKSPACE;
     const int slices = launch_ln_bwd_rows(x, dy, stats, gamma, ld, D, M, dx, accumulate, nullptr, scratch, scratch_floats, stream);
     launch_ln_bwd_combine(scratch, D, slices, dgamma, dbeta, acc_params, stream);
     return hip_status();
@@ -229,6 +233,8 @@ inline int launch_attn_generic(bool backward, const float* qkv, const float* dO,
         const int pack = std::max(1, 128 / L);                         // (sequence, head) pairs per workgroup
         const dim3 grid((total + pack - 1) / pack);
         const size_t lds = attn_generic_lds_bytes<4>(L, backward) * pack;
+        if (lds > (size_t)160 * 1024) return UU3D_ERR_UNSUPPORTED;
+        if (backward) allow_lds<attn_generic_bwd_kernel<4>>(160 * 1024);      // P and dS of L >= 83 tokens pass the 64 KiB default
         if (backward && L == 17 && mask == nullptr && !drop.on() && !bwd_generic)     // the spatial stack's shape: unrolled, rows in registers
             hipLaunchKernelGGL(attn_small_bwd_kernel<17>, grid, block, attn_small_bwd_lds_bytes<17>() * pack, stream, qkv, dO, ld, D, H, out, ldo, pack, total);
         else if (backward) hipLaunchKernelGGL(attn_generic_bwd_kernel<4>, grid, block, lds, stream, qkv, dO, ld, D, L, H, mask, out, ldo, pack, total, drop);
