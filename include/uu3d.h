@@ -893,6 +893,57 @@ int uu3d_stream_one_euro(int32_t slots, int32_t channels, int32_t lookahead, voi
 int uu3d_stream_one_euro_reset(int32_t slots, int32_t channels, void* filter_state_dev, const uint8_t* slot_mask_dev, void* stream);
 
 /*
+ * LIVE TRACKS: END OF A TRACK (stream.StreamSession.finish): a session with lookahead a answers the push that made frame t the newest with
+ * the pose of frame t - a, so a track that ENDS still owes the poses of its last a frames.  A DRAIN TICK moves the centre of the slot's
+ * window one frame towards its newest frame without filing a frame: for a slot with `frames` frames the k-th drain tick (k = 1 .. a) gives
+ * the pose of frame c = frames - 1 - a + k, and the frames behind the track's end are padded as the end of a video is -- the pose
+ * uu3d_gather_window_frames + uu3d_forward_frames_ex give for frame c of the whole track, and the one a session of lookahead a - k returns
+ * at its last push.  Everything a drain tick reads is still in the session's state: the keyframe ring covers centre - half span .. newest,
+ * the edge row is the last one filed, the root ring of LIVE ABSOLUTE ROOT holds the raw frames newest - a .. newest.  Not for sessions with
+ * a frame rate (their drain needs the model-rate end of the track).
+ * STATE per slot, in one caller-allocated block of uu3d_stream_drain_bytes(slots) bytes, 256-byte aligned, zeroed by
+ * uu3d_stream_drain_reset, apart from the session's state block (a session that never ends a track allocates none):
+ * drained (i32), the drain ticks taken, at most a; virtual_frames (i32) = frames + drained, the counter the drained pose's frame is
+ * counted from (c = virtual_frames - 1 - a): what uu3d_stream_one_euro takes as frames_dev in a drain tick; ticked (u8), whether the slot
+ * advanced at the last drain tick.  uu3d_stream_drain_layout gives the three offsets.
+ * A drain tick: uu3d_stream_drain_commit -> uu3d_forward_frames_ex and uu3d_stream_emit with the session's own arguments ->
+ * uu3d_stream_root_drain -> uu3d_stream_one_euro (frames_dev = virtual_frames, active_dev = chosen) -> uu3d_stream_drain_file; then, after
+ * a ticks, uu3d_stream_reset (and its companions) and uu3d_stream_drain_reset for the chosen slots.  No stage, no uu3d_frame_features.
+ *
+ *   uu3d_stream_drain_bytes(slots): 0 for slots outside [1, 2^20].
+ *   uu3d_stream_drain_commit(model, cfg, state_dev (only read), drain_state_dev, chosen_dev (slots) u8: the slots whose tracks have ended,
+ *       valid_state_dev or NULL: the validity bytes of uu3d_stream_commit_valid / uu3d_stream_commit_repair, only read, rows_dev,
+ *       stride_mask_dev, fresh_dev as uu3d_stream_commit, stream): one launch, one workgroup per slot.  A chosen slot with frames >= 1 and
+ *       drained < lookahead advances drained and gets the window of centre frames - 1 - lookahead + drained (fresh iff the centre is >= 0
+ *       and a multiple of pred_stride); it files nothing and `frames` is unchanged.  Any other slot gets the all-masked, not-fresh window
+ *       of an inactive slot.
+ *   uu3d_stream_root_drain(slots, J, lookahead, root_state_dev, drain_state_dev, chosen_dev, fresh_dev, poses_dev, cameras_dev, min_joints,
+ *       roots_dev, root_state_out_dev, stream): uu3d_stream_root's solve for frame c of a chosen, fresh slot, read from the ring; nothing
+ *       is filed; held root and states by the same rule; any other slot returns what it returned last.  One thread per slot.
+ *   uu3d_stream_drain_file(slots, lookahead >= 1, drain_state_dev, num_buffers in [1, 4], src (HOST array of num_buffers device pointers,
+ *       each (slots, widths[b]) f32), widths (HOST array), dst (HOST array of device pointers, each (slots, lookahead, widths[b]) f32),
+ *       fresh_dev (slots) u8 -> fresh_rows_dev (slots, lookahead) u8, root_state_dev -> root_state_rows_dev likewise or both NULL, stream):
+ *       a slot that advanced at this tick copies its rows into row drained - 1; the row comes from the device counter, so the arguments
+ *       are the same at every drain tick.  One launch, one workgroup per slot; any other slot writes nothing.
+ *   uu3d_stream_drain_reset(slots, drain_state_dev, slot_mask_dev (slots) u8 or NULL = every slot, stream): the chosen slots have drained
+ *       nothing.
+ * Every output and state element has one writer, no atomics: bitwise repeatable, capturable.
+ */
+typedef struct uu3d_stream_drain_state_layout { int64_t drained_offset, virtual_frames_offset, ticked_offset, bytes; } uu3d_stream_drain_state_layout;
+size_t uu3d_stream_drain_bytes(int32_t slots);
+int uu3d_stream_drain_layout(int32_t slots, uu3d_stream_drain_state_layout* out);
+int uu3d_stream_drain_commit(uu3d_model* model, const uu3d_stream_config* cfg, const void* state_dev, void* drain_state_dev,
+                             const uint8_t* chosen_dev, const void* valid_state_dev, int32_t* rows_dev, uint8_t* stride_mask_dev,
+                             uint8_t* fresh_dev, void* stream);
+int uu3d_stream_root_drain(int32_t slots, int32_t num_keypoints, int32_t lookahead, void* root_state_dev, const void* drain_state_dev,
+                           const uint8_t* chosen_dev, const uint8_t* fresh_dev, const float* poses_dev, const double* cameras_dev,
+                           int32_t min_joints, float* roots_dev, uint8_t* root_state_out_dev, void* stream);
+int uu3d_stream_drain_file(int32_t slots, int32_t lookahead, const void* drain_state_dev, int32_t num_buffers, const float* const* src,
+                           const int32_t* widths, float* const* dst, const uint8_t* fresh_dev, uint8_t* fresh_rows_dev,
+                           const uint8_t* root_state_dev, uint8_t* root_state_rows_dev, void* stream);
+int uu3d_stream_drain_reset(int32_t slots, void* drain_state_dev, const uint8_t* slot_mask_dev, void* stream);
+
+/*
  * Per-kernel timing of the next uu3d_forward calls with HIP events on the launch stream.
  * When enabled, uu3d_forward records an event pair around every launch; uu3d_profile_read
  * synchronises those events and returns the per-launch records of the LAST forward.

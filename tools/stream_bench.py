@@ -4,7 +4,7 @@ uploads them with their mirrored copies and calls ``model([x, mask])`` once -- t
 A tick = host clock from the call to the synchronised result (a live consumer reads every pose); host input in all three variants.
 Median (and 90th percentile) over --ticks ticks after --warmup ticks, per config and slot count.
    python tools/stream_bench.py [--slots 1,8,64] [--cases h36m_81:4,h36m_351:5] [--ticks 300] [--warmup 60] [--lookahead 0] [--fps F [--out_fps G]]
-                                [--repair_joints G] [--detections D] [--camera FX FY CX CY] [--smooth]
+                                [--repair_joints G] [--detections D] [--camera FX FY CX CY] [--smooth] [--drain]
 --fps F (a float or NUM/DEN): microseconds per PUSH of StreamSession(fps=F) -- one source frame in, one pose out, on average
 model_fps / F sub-ticks -- next to the plain session pushed at the model's rate (the cost of one model tick); the lookahead is raised to
 the smallest one the rate allows.  The numpy baseline is left out.
@@ -26,7 +26,11 @@ camera_minus_graph_us is the difference of the two medians.  The numpy baseline 
 --smooth (alone or with --camera, not with the other options): the tick of StreamSession(smooth=True) -- one more launch at the end of the
 captured tick, with --camera two (poses and roots) -- as smooth_graph_us next to the tick of the same session without smooth (graph_us;
 with --camera both sessions have the camera), measured side by side in the same way.  smooth_minus_graph_us is the difference of the two
-medians.  The numpy baseline is left out."""
+medians.  The numpy baseline is left out.
+--drain (alone): StreamSession.finish() -- `lookahead` drain ticks and the reset, from the call to the synchronised result -- at lookahead 13
+and at the largest one, as finish_us, beside the plain tick of the same session in the same process (graph_us); finish_over_tick is their
+ratio, finish_per_drain_tick_us = finish_us / lookahead.  Each finish follows 8 pushes of a new track; the first finish (allocation and the
+capture) is not timed.  Use --slots 1,64.  The numpy baseline is left out."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -45,7 +49,10 @@ def main():
     ap.add_argument("--detections", type=int, default=None)
     ap.add_argument("--camera", type=float, nargs=4, metavar=("FX", "FY", "CX", "CY"), default=None)
     ap.add_argument("--smooth", action="store_true")
+    ap.add_argument("--drain", action="store_true")
     args = ap.parse_args()
+    if args.drain and (args.smooth or args.camera is not None or args.fps is not None or args.repair_joints is not None or args.detections is not None):
+        ap.error("--drain is measured alone")
     if args.smooth and (args.fps is not None or args.repair_joints is not None or args.detections is not None):
         ap.error("--smooth is not measured together with --fps / --repair_joints / --detections")
     if args.camera is not None and (args.fps is not None or args.repair_joints is not None or args.detections is not None):
@@ -190,6 +197,33 @@ def main():
                 row.update(camera=None if args.camera is None else list(args.camera), smooth=bool(args.smooth))
                 return tuple((key, lambda key=key: ts[key][args.warmup:]) for key in pair)
 
+            if args.drain:
+                for a in sorted({min(13, stream.max_lookahead(cfg)), stream.max_lookahead(cfg)}):
+                    s = stream.StreamSession(model, cfg, slots=T, resolutions=(W, H), mask_stride=ms, flip=True, lookahead=a)
+                    tick, fin = [], []
+                    k = 0
+                    for rep in range(max(args.ticks // 8, 4) + 1):
+                        for _ in range(8):
+                            t0 = time.perf_counter()
+                            s.push(px[k % total])
+                            torch.cuda.synchronize()
+                            tick.append(time.perf_counter() - t0)
+                            k += 1
+                        t0 = time.perf_counter()
+                        s.finish()
+                        torch.cuda.synchronize()
+                        fin.append(time.perf_counter() - t0)
+                    s.check_range()
+                    s.close()
+                    tick, fin = np.asarray(tick[8:]), np.asarray(fin[1:])
+                    row = dict(config=name, mask_stride=ms, slots=T, lookahead=a, finishes=len(fin), graph_us=round(1e6 * float(np.median(tick)), 1),
+                               finish_us=round(1e6 * float(np.median(fin)), 1), finish_p90_us=round(1e6 * float(np.percentile(fin, 90)), 1))
+                    row["finish_over_tick"] = round(row["finish_us"] / row["graph_us"], 2)
+                    row["finish_per_drain_tick_us"] = round(row["finish_us"] / a, 1)
+                    row["device"] = torch.cuda.get_device_name(0)
+                    print(json.dumps(row), flush=True)
+                    results.append(row)
+                continue
             row = dict(config=name, mask_stride=ms, slots=T, lookahead=args.lookahead, ticks=args.ticks)
             variants = (("graph", lambda: session(True)), ("no_graph", lambda: session(False)), ("baseline", baseline))
             if args.fps is not None:

@@ -46,6 +46,8 @@ EXPORTED_SYMBOLS = (
     "uu3d_solve_roots", "uu3d_root_trajectory_scratch_bytes", "uu3d_root_trajectory",
     "uu3d_stream_root_bytes", "uu3d_stream_root", "uu3d_stream_root_reset",
     "uu3d_one_euro_tracks", "uu3d_stream_one_euro_bytes", "uu3d_stream_one_euro", "uu3d_stream_one_euro_reset",
+    "uu3d_stream_drain_bytes", "uu3d_stream_drain_layout", "uu3d_stream_drain_commit", "uu3d_stream_root_drain", "uu3d_stream_drain_file",
+    "uu3d_stream_drain_reset",
 )
 # include/uu3d_ops.h
 OPS_SYMBOLS = (
@@ -118,6 +120,10 @@ class Uu3dStreamOutLayout(C.Structure):
 class Uu3dStreamRepairLayout(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("window", "staged_frames", "raw_offset", "last_xy_offset", "last_offset", "held_offset", "observed_offset",
                                          "bytes")]
+
+
+class Uu3dStreamDrainLayout(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("drained_offset", "virtual_frames_offset", "ticked_offset", "bytes")]
 
 
 class Uu3dAssociateParams(C.Structure):
@@ -302,6 +308,19 @@ def load_library(path=None):
     lib.uu3d_stream_one_euro.argtypes = [i32, i32, i32] + [vp] * 6 + [f64] * 4 + [vp, vp]
     lib.uu3d_stream_one_euro_reset.restype = C.c_int
     lib.uu3d_stream_one_euro_reset.argtypes = [i32, i32, vp, vp, vp]
+    # live tracks, end of a track: the drain state, the commit of a drain tick, the root solve without filing, the result rows, the reset
+    lib.uu3d_stream_drain_bytes.restype = sz
+    lib.uu3d_stream_drain_bytes.argtypes = [i32]
+    lib.uu3d_stream_drain_layout.restype = C.c_int
+    lib.uu3d_stream_drain_layout.argtypes = [i32, C.POINTER(Uu3dStreamDrainLayout)]
+    lib.uu3d_stream_drain_commit.restype = C.c_int
+    lib.uu3d_stream_drain_commit.argtypes = [vp, scfg] + [vp] * 8
+    lib.uu3d_stream_root_drain.restype = C.c_int
+    lib.uu3d_stream_root_drain.argtypes = [i32, i32, i32] + [vp] * 6 + [i32, vp, vp, vp]
+    lib.uu3d_stream_drain_file.restype = C.c_int
+    lib.uu3d_stream_drain_file.argtypes = [i32, i32, vp, i32, C.POINTER(vp), C.POINTER(i32), C.POINTER(vp)] + [vp] * 5
+    lib.uu3d_stream_drain_reset.restype = C.c_int
+    lib.uu3d_stream_drain_reset.argtypes = [i32, vp, vp, vp]
     lib.uu3d_world_to_cam_2d.restype = C.c_int
     lib.uu3d_world_to_cam_2d.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
     lib.uu3d_set_schedule.restype = C.c_int

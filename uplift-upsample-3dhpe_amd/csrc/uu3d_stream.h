@@ -96,13 +96,15 @@ stream_stage_kernel(const float* __restrict__ kp, const double* __restrict__ res
     else *reinterpret_cast<float2*>(out + p0 * 2) = v[0];
 }
 
-// The window of a tick, for stream_commit_kernel and stream_commit_repair_kernel (uu3d_stream_repair.h): slot `slot` has `len` frames after
-// this tick (act: it took one).  Writes the slot's rows (halves, N), stride masks and fresh byte; valid_state as in stream_commit_kernel.
+// The window of a tick, for stream_commit_kernel, stream_commit_repair_kernel (uu3d_stream_repair.h) and stream_drain_commit_kernel
+// (uu3d_stream_drain.h): slot `slot` has `len` frames after this tick (act: it took one).  Writes the slot's rows (halves, N), stride masks
+// and fresh byte; valid_state as in stream_commit_kernel.  centre_offset: 0 for a push; a drain tick moves the centre that many frames
+// towards the newest frame (0 <= centre_offset <= lookahead, so no frame older than the ring's oldest is read) while `len` stays.
 __device__ __forceinline__ void stream_write_window(const StreamParams& p, const int slot, const int tid, const int len, const bool act,
-                                                    const uint8_t* valid_state, int32_t* __restrict__ rows, uint8_t* __restrict__ stride_mask,
-                                                    uint8_t* __restrict__ fresh)
+                                                    const int centre_offset, const uint8_t* valid_state, int32_t* __restrict__ rows,
+                                                    uint8_t* __restrict__ stride_mask, uint8_t* __restrict__ fresh)
 {
-    const int centre = len - 1 - p.lookahead;
+    const int centre = len - 1 - p.lookahead + centre_offset;
     const bool is_fresh = act && centre >= 0 && centre % p.pred_stride == 0;
     if (tid == 0) fresh[slot] = is_fresh ? 1 : 0;
     const int oldest = centre - (p.N / 2) * p.seq_stride;               // nothing older is still in the ring for certain
@@ -166,7 +168,7 @@ stream_commit_kernel(const StreamParams p, const float* __restrict__ feats, cons
         }
     }
     if (valid_state != nullptr) __syncthreads();                         // (uniform: the bytes filed above are read below by other threads)
-    stream_write_window(p, slot, tid, len, act, valid_state, rows, stride_mask, fresh);
+    stream_write_window(p, slot, tid, len, act, 0, valid_state, rows, stride_mask, fresh);
 }
 
 // central (halves * T, J, 3): the forward's central predictions of this tick's windows.  out (T, J, 3) and held (T, J, 3, in the state

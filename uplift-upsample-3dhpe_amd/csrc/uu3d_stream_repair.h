@@ -263,7 +263,7 @@ stream_commit_repair_kernel(const StreamParams p, const int K, const int G, cons
         }
     }
     __syncthreads();                                                     // the bytes filed above are read below by other threads
-    stream_write_window(p, slot, tid, len, act, valid_state, rows, stride_mask, fresh);
+    stream_write_window(p, slot, tid, len, act, 0, valid_state, rows, stride_mask, fresh);
 }
 
 // slot_mask (T) u8 or nullptr (every slot): the chosen slots forget their last observations and held-frame bits.  The raw ring stays: no

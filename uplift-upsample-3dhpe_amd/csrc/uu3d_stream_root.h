@@ -32,6 +32,33 @@ inline RootRingLayout root_ring_layout(const int slots, const int J, const int l
     return L;
 }
 
+// The root of one slot at one tick, the work of ONE thread; shared by stream_root_kernel and stream_root_drain_kernel
+// (uu3d_stream_drain.h).  solve: the slot's pose is fresh (and the slot takes part in the tick); have_frame: the frame the pose belongs to
+// exists and may be read -- frame_kp (J, 2) as pushed, frame_used (J) u8 or nullptr.  Solved: held = the root, state 1.  Not solved (or no
+// frame): state 2 when a held root exists, else 0.  !solve: what the slot returned last.  roots = the held root rounded once.
+__device__ __forceinline__ void stream_root_settle(const int slot, const int J, const bool solve, const bool have_frame, const float* pose,
+                                                   const float* frame_kp, const uint8_t* frame_used, const double* cam, const int min_joints,
+                                                   double* __restrict__ held, uint8_t* __restrict__ last, float* __restrict__ roots,
+                                                   uint8_t* __restrict__ root_state)
+{
+    uint8_t s = last[slot];
+    double T[3] = {held[slot * 3], held[slot * 3 + 1], held[slot * 3 + 2]};
+    if (solve) {
+        double R[3] = {0.0, 0.0, 0.0};
+        const bool ok = have_frame && solve_root(pose, frame_kp, frame_used, J, cam, min_joints, R);
+        if (ok) {
+            T[0] = R[0]; T[1] = R[1]; T[2] = R[2];
+            held[slot * 3] = R[0]; held[slot * 3 + 1] = R[1]; held[slot * 3 + 2] = R[2];
+            s = 1;
+        } else s = s != 0 ? 2 : 0;
+        last[slot] = s;
+    }
+    roots[slot * 3] = (float)T[0];
+    roots[slot * 3 + 1] = (float)T[1];
+    roots[slot * 3 + 2] = (float)T[2];
+    root_state[slot] = s;
+}
+
 // One wave per slot.  frames (T) i32: the slot's frame counter AFTER this push (the pushed frame is t = frames - 1); active, fresh (T) u8;
 // poses (T, J, 3) f32: the poses the push returns; kp (T, J, 2) f32: the pushed frames, raw; flags: nullptr, (T) u8 (per_joint == 0: a
 // frame's flag stands for all of its joints) or (T, J) u8; cameras (T, 4) f64.
@@ -63,33 +90,11 @@ stream_root_kernel(const int J, const int W, const int32_t* __restrict__ frames,
     }
     if (lane != 0) return;
 
-    uint8_t s = last[slot];
-    double T[3] = {held[slot * 3], held[slot * 3 + 1], held[slot * 3 + 2]};
-    if (act && fresh[slot] != 0) {
-        const int c = t - (W - 1);
-        const float* pose = poses + (long)slot * J * 3;
-        const double* cam = cameras + 4 * (long)slot;
-        double R[3] = {0.0, 0.0, 0.0};
-        bool ok = false;
-        if (c >= 0) {
-            if (W == 1) {
-                ok = frame_flag && solve_root(pose, frame, frame_flags, J, cam, min_joints, R);
-            } else {
-                const long e = ((long)slot * W + c % W) * J;
-                ok = solve_root(pose, ring_kp + 2 * e, ring_used + e, J, cam, min_joints, R);
-            }
-        }
-        if (ok) {
-            T[0] = R[0]; T[1] = R[1]; T[2] = R[2];
-            held[slot * 3] = R[0]; held[slot * 3 + 1] = R[1]; held[slot * 3 + 2] = R[2];
-            s = 1;
-        } else s = s != 0 ? 2 : 0;
-        last[slot] = s;
-    }
-    roots[slot * 3] = (float)T[0];
-    roots[slot * 3 + 1] = (float)T[1];
-    roots[slot * 3 + 2] = (float)T[2];
-    root_state[slot] = s;
+    const int c = t - (W - 1);
+    const long e = ((long)slot * W + (c >= 0 ? c % W : 0)) * J;
+    stream_root_settle(slot, J, act && fresh[slot] != 0, c >= 0 && (W != 1 || frame_flag), poses + (long)slot * J * 3,
+                       W == 1 ? frame : ring_kp + 2 * e, W == 1 ? frame_flags : ring_used + e, cameras + 4 * (long)slot, min_joints, held, last,
+                       roots, root_state);
 }
 
 // slot_mask (T) u8 or nullptr (every slot): the chosen slots have no filed frame, no held root and state 0.  One workgroup per slot.

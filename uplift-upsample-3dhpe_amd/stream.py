@@ -128,8 +128,22 @@ clear the filter with everything else.  ``LiveOneEuro`` owns the state block and
 several rows per push).  No accuracy or jitter figure is claimed.  ``smooth=None`` is the session above, bit for bit: no further launch
 or buffer.
 
+The end of a track -- ``finish(slots)``: a session with lookahead a has not returned the poses of a track's last a frames when the track
+ends (the person leaves, the video stops).  ``finish`` returns them -- (slots, a, J, 3) and (slots, a) on the device -- and resets exactly
+those slots: it enqueues a DRAIN TICKS, each of which moves the centre of the slot's window one frame towards its newest frame and files
+NOTHING (uu3d_stream_drain_commit: the window of centre len - 1 - a + k through the same row rule, the frames behind the track's end padded
+as the end of a video is), then the tick's own forward and emit, the root solve from the ring (uu3d_stream_root_drain), the filters as they
+are at the virtual counter len + k, and uu3d_stream_drain_file, which copies the tick's rows into row k - 1 of the result (include/uu3d.h,
+LIVE TRACKS: END OF A TRACK; csrc/uu3d_stream_drain.h).  No stage, no uu3d_frame_features: everything a drain tick reads is in the ring.
+The one rule, extended: row k - 1 is the pose ``predict_tracks`` gives for frame len - 1 - a + k of the WHOLE track, and the bits a session
+with lookahead a - k returns at its last push.  The drain ticks are a second launch table (``_drain_steps``) captured lazily at the first
+``finish`` as one more linear hipGraph: a session that never finishes a track allocates and launches none of it and ``captures`` stays 1;
+afterwards it is 2.  Slots that were not chosen keep every bit of their state.  ``replay_tracks(drain=True)`` finishes each slot at the
+tick its own track ends; ``window_plan(drained=k)``, ``LiveRootHost.drain`` and ``LiveOneEuroHost.drain`` are the host mirrors.  Not with
+``fps`` / ``out_fps`` (ValueError: a later change).
+
     python -m uplift_upsample_3dhpe_amd.stream --config C --weights W.h5 --input tracks.npz --output out.npz [--lookahead A] [--resolution W H]
-                                                 [--mask_missing] [--fps F [--out_fps G]] [--repair_joints G [--min_score S]] [--keypoints NAME]
+                                                 [--drain] [--mask_missing] [--fps F [--out_fps G]] [--repair_joints G [--min_score S]] [--keypoints NAME]
                                                  [--camera FX FY CX CY [--min_root_joints N]] [--smooth MIN_CUTOFF BETA D_CUTOFF]
                                                  [--smooth_root MIN_CUTOFF BETA D_CUTOFF]
 """
@@ -156,27 +170,34 @@ def ring_capacity(config, mask_stride=None, lookahead=0):
     return (int(lookahead) + max_lookahead(config)) // s_in + 1
 
 
-def emits(frames, lookahead, config, mask_stride=None):
-    """Whether the push that brought a track to ``frames`` frames emits a pose (of frame ``frames - 1 - lookahead``)."""
+def emits(frames, lookahead, config, mask_stride=None, drained=0):
+    """Whether the push that brought a track to ``frames`` frames emits a pose (of frame ``frames - 1 - lookahead``).  ``drained`` = k in
+    1 .. lookahead: whether the k-th drain tick of ``StreamSession.finish`` does, for a track that ended at ``frames`` frames (of frame
+    ``frames - 1 - lookahead + k``)."""
     _, _, pred = session_strides(config, mask_stride)
-    c = int(frames) - 1 - int(lookahead)
+    if not 0 <= int(drained) <= int(lookahead):
+        raise ValueError(f"drained must be in [0, lookahead = {int(lookahead)}], got {drained}")
+    c = int(frames) - 1 - int(lookahead) + int(drained)
     return int(frames) >= 1 and c >= 0 and c % pred == 0
 
 
-def window_plan(frames, lookahead, config, mask_stride=None, valid=None):
+def window_plan(frames, lookahead, config, mask_stride=None, valid=None, drained=0):
     """The host mirror of uu3d_stream_commit's row rule for a track of ``frames`` frames: None when no pose comes out, else a dict of (N,)
     arrays over the window centred on ``frames - 1 - lookahead`` --
         "mask": the stride mask bit; "src": the frame a real token reads (-1: none -- a masked token, or zero padding);
         "kind": 0 masked token, 1 zero row, 2 keyframe ring, 3 edge row; "place": the ring place of kind 2 (-1 otherwise)
     -- and "centre".  ``valid``: (frames,) flags, 0 = a missing frame (uu3d_stream_commit_valid): a token that reads one is masked --
-    mask' = mask and (no frame is read or valid[the frame read])."""
-    if not emits(frames, lookahead, config, mask_stride):
+    mask' = mask and (no frame is read or valid[the frame read]).
+    ``drained`` = k in 1 .. lookahead: the mirror of uu3d_stream_drain_commit's k-th drain tick for a track that ENDED at ``frames`` frames
+    -- the window centred on ``frames - 1 - lookahead + k``, the frames behind the track's end padded as the end of a video is, in the ring
+    of capacity ``ring_capacity(lookahead=lookahead)``: the session files nothing while it drains, so the places are those of its pushes."""
+    if not emits(frames, lookahead, config, mask_stride, drained):
         return None
     S, s_in, _ = session_strides(config, mask_stride)
     N, L = int(config.SEQUENCE_LENGTH), int(frames)
     cap = ring_capacity(config, mask_stride, lookahead)
     pad_edge = config.PADDING_TYPE == "copy"
-    c = L - 1 - int(lookahead)
+    c = L - 1 - int(lookahead) + int(drained)
     n = np.arange(N, dtype=np.int64)
     f = c - ((N - 1) * S) // 2 + n * S
     src = np.where(f < 0, f + ((-f + S - 1) // S) * S, np.where(f >= L, f - ((f - L + S) // S) * S, f))
@@ -339,7 +360,7 @@ class LiveRootHost(object):
         self.reset()
 
     def reset(self):
-        self.frames = 0
+        self.frames = self.drained = 0                                # (drained: drain ticks taken since the track ended)
         self.raw = np.zeros((self.W, self.J, 2), np.float32)
         self.used = np.zeros((self.W, self.J), bool)
         self.held = None
@@ -352,10 +373,24 @@ class LiveRootHost(object):
         # 1. file the pushed frame
         self.raw[t % W], self.used[t % W] = frame, flags & np.isfinite(frame).all(axis=1)
         self.frames = t + 1
+        # 2. solve the frame the fresh pose belongs to
+        return self._settle(t - (W - 1), pose)
+
+    def drain(self, pose=None):
+        """One drain tick of the slot (``StreamSession.finish``; uu3d_stream_root_drain): the track has ENDED, nothing is filed.  The k-th
+        drain tick since the last step (k = 1 .. lookahead; a tick beyond that, or of a slot without frames, changes nothing) solves
+        frame c = frames - 1 - lookahead + k -- one of the last lookahead + 1 frames filed, so it is in the ring -- against ``pose``, the
+        (J, 3) pose of that tick when it is fresh, else None; held root and state by ``step``'s rule.  -> (root, state)."""
+        if self.frames < 1 or self.drained >= self.W - 1:
+            return self.root.copy(), self.state
+        self.drained += 1
+        return self._settle(self.frames - 1 - (self.W - 1) + self.drained, pose)
+
+    def _settle(self, c, pose):
+        """The root of a push or drain tick whose pose (None: not fresh) belongs to frame c -> (root, state)."""
+        J, W = self.J, self.W
         if pose is None:                                              # not fresh: nothing is solved, nothing changes
             return self.root.copy(), self.state
-        # 2. solve the frame the fresh pose belongs to
-        c = t - (W - 1)
         solved = False
         if c >= 0:
             roots, ok = solve_roots_host(np.asarray(pose, np.float32).reshape(1, J, 3), self.raw[c % W][None], self.camera,
@@ -429,6 +464,13 @@ class LiveOneEuroHost(object):
                 self.taken[i] |= ok
                 out[i] = np.where(ok, self.xh[i].astype(np.float32), values[i])
         return out
+
+    def drain(self, values, frames, drained, fresh, chosen=None, state=None):
+        """One drain tick (``StreamSession.finish``): ``step`` at the VIRTUAL counter ``frames + drained`` -- ``frames``: the counters of the
+        ended tracks, ``drained`` (slots,): the drain ticks each slot has taken, this one included --, so the fresh value belongs to frame
+        f = frames - 1 - lookahead + drained; ``chosen``: the slots that drain, as ``step``'s ``active``."""
+        virtual = np.asarray(frames, np.int64).reshape(self.slots) + np.asarray(drained, np.int64).reshape(self.slots)
+        return self.step(values, virtual, fresh, chosen, state)
 
 
 class LiveOneEuro(object):
@@ -755,6 +797,9 @@ class StreamSession(object):
         if self.root_filter is not None:
             self._root_smoother = LiveOneEuro(T, 3, self.smooth_rate, self.root_filter, self.lookahead, dev)
             self._result = self._result[:2] + (self._root_smoother.out,) + self._result[3:]
+        # the end of a track: nothing until the first ``finish`` (_init_drain)
+        self._drain_result = self._drain_state = self._drain_graph = None
+        self._drain_steps = []
 
     def _init_launch_tables(self):
         """All arguments are the same at every push (the buffers never move), so the mode is decided here, once: every launch of the
@@ -762,7 +807,8 @@ class StreamSession(object):
           _tick_steps   the steps of one (sub-)tick, in order -- what the graph captures
           _push_before  / _push_after   the launches of a push around its sub-ticks (a session with a rate; not captured)
           _reset_call   the reset of the session's kind; the slot mask and the stream follow its arguments (_reset_more: what a session
-                        with repair_joints, a camera or smooth resets beside it)"""
+                        with repair_joints, a camera or smooth resets beside it)
+          _drain_steps  the steps of one drain tick (``finish``), built at the first ``finish`` by _init_drain -- a second captured graph"""
         lib, m = self._lib, self.model
         h, cfg, state = m._h, C.byref(self._cfg), _ptr(self._state)
         kp, res, order, active, staged = _ptr(self._kp), _ptr(self._res), _ptr(self._order), _ptr(self._active), _ptr(self._staged)
@@ -791,6 +837,7 @@ class StreamSession(object):
                                      self._central, self._key), None)
         emit = (lib.uu3d_stream_emit, (h, cfg, state, _ptr(self._central), order, emit_fresh, _ptr(self._emit_out)))
         self._tick_steps = [stage, features, commit, forward, emit]
+        self._drain_shared = [forward, emit]                         # what a drain tick takes from the tick as it is (_init_drain)
         self._push_before, self._push_after = [], []
         # any skeleton: the detector's joints -> the session's own frame (with repair_joints: and its joint flags), in front of everything
         mapping = []
@@ -1077,6 +1124,158 @@ class StreamSession(object):
         self._src_host[which] = 0
         self._src_known[which] = True
 
+    # ---- the end of a track: the drain ticks of ``finish`` ----------------------------------------------------------------------------
+    def _init_drain(self):
+        """What ``finish`` needs, made at its first call: the result buffers (one block, so that one fill zeroes them), and with
+        lookahead >= 1 the drain state, the chosen-slots mask, the launch table of a drain tick and its captured graph."""
+        torch, lib, m = self._torch, self._lib, self.model
+        dev, T, a, J = m.device, self.slots, self.lookahead, int(self._kp.shape[1])
+        camera, fp, fr = self.cameras is not None, self._pose_smoother, self._root_smoother
+        # (name, tick buffer or None for a byte buffer, shape of a row, dtype)
+        parts = [("poses", self._out, (J, 3), torch.float32), ("fresh", None, (), torch.uint8)]
+        if camera:
+            parts += [("roots", self._roots, (3,), torch.float32), ("root_state", None, (), torch.uint8)]
+        if fp is not None:
+            parts.append(("filtered_poses", fp.out, (J, 3), torch.float32))
+        if fr is not None:
+            parts.append(("filtered_roots", fr.out, (3,), torch.float32))
+        nbytes = [T * a * int(np.prod(shape, dtype=np.int64)) * (4 if dt == torch.float32 else 1) for _, _, shape, dt in parts]
+        offsets = [int(o) for o in np.cumsum([0] + [(n + 255) // 256 * 256 for n in nbytes])]
+        self._drain_rows = torch.zeros(max(offsets[-1], 1), dtype=torch.uint8, device=dev)
+        rows = {}
+        for (name, _, shape, dt), off, n in zip(parts, offsets, nbytes):
+            rows[name] = (self._drain_rows[off:off + n].view(dt).view((T, a) + shape) if a > 0 else
+                          torch.zeros((T, 0) + shape, dtype=dt, device=dev))
+        self._drain_named = rows
+        result = (rows.get("filtered_poses", rows["poses"]), rows["fresh"].view(torch.bool))
+        if camera:
+            result += (rows.get("filtered_roots", rows["roots"]), rows["root_state"])
+        self._drain_result = result
+        if a == 0:
+            return
+        lay = _capi.Uu3dStreamDrainLayout()
+        _capi.check(lib, lib.uu3d_stream_drain_layout(T, C.byref(lay)), None)
+        self._drain_state = torch.zeros(int(lay.bytes), dtype=torch.uint8, device=dev)
+        self._drained = self._drain_state[int(lay.drained_offset):int(lay.drained_offset) + 4 * T].view(torch.int32)
+        self._virtual_frames = self._drain_state[int(lay.virtual_frames_offset):int(lay.virtual_frames_offset) + 4 * T].view(torch.int32)
+        self._drain_mask = torch.zeros((T,), dtype=torch.uint8, device=dev)
+        h, cfg, dstate, chosen, fresh = m._h, C.byref(self._cfg), _ptr(self._drain_state), _ptr(self._drain_mask), _ptr(self._fresh)
+        steps = [(lib.uu3d_stream_drain_commit, (h, cfg, _ptr(self._state), dstate, chosen, _ptr(self._valid_state), _ptr(self._rows),
+                                                 _ptr(self._mask), _ptr(self._emit_fresh)))] + self._drain_shared
+        if camera:
+            steps.append((lib.uu3d_stream_root_drain, (T, J, a, _ptr(self._root_state), dstate, chosen, fresh, _ptr(self._out), _ptr(self._cams),
+                                                       self.min_root_joints, _ptr(self._roots), _ptr(self._root_flag))))
+        if fp is not None:                                           # the filters as they are: the virtual counter, the chosen slots as `active`
+            steps.append(fp.launch(self._out, self._virtual_frames, self._fresh, self._drain_mask))
+        if fr is not None:
+            steps.append(fr.launch(self._roots, self._virtual_frames, self._fresh, self._drain_mask, self._root_flag))
+        floats = [(src, rows[name], int(np.prod(shape))) for name, src, shape, _ in parts if src is not None]
+        n = len(floats)
+        self._drain_file_args = ((C.c_void_p * n)(*[t.data_ptr() for t, _, _ in floats]), (C.c_int32 * n)(*[w for _, _, w in floats]),
+                                 (C.c_void_p * n)(*[t.data_ptr() for _, t, _ in floats]))
+        src, widths, dst = self._drain_file_args
+        steps.append((lib.uu3d_stream_drain_file, (T, a, dstate, n, src, widths, dst, fresh, _ptr(rows["fresh"]),
+                                                   _ptr(self._root_flag) if camera else None, _ptr(rows["root_state"]) if camera else None)))
+        self._drain_steps = steps
+        # (every slot's `drained` is 0 outside ``finish`` -- it resets the slots it drained --, so the captured tick of a session with
+        # detections, which resets the slots born on the device, needs no launch for the drain state; ``reset`` zeroes it all the same)
+        self._reset_more = self._reset_more + [(lib.uu3d_stream_drain_reset, (T, dstate))]
+        if self.graph:
+            self._capture_drain()
+
+    def _capture_drain(self):
+        """One warm-up drain tick with no slot chosen (nothing advances), then the capture: a linear chain on one stream, as _capture."""
+        torch = self._torch
+        dev = self.model.device
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        gc.collect()
+        gc_was_on = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.stream(side):
+                self._drain_mask.zero_()
+                self._run(self._drain_steps, side)
+            side.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, stream=side):
+                self._run(self._drain_steps, side)
+            self._drain_graph = g
+            self.captures += 1
+        finally:
+            if gc_was_on:
+                gc.enable()
+        torch.cuda.current_stream(dev).wait_stream(side)
+
+    def finish(self, slots=None):
+        """The tracks in the given slots (indices; None = all) have ENDED: the poses of their last ``lookahead`` frames, which no push
+        returned, and then ``reset`` for exactly those slots.  -> (poses (slots, a, J, 3) float32, fresh (slots, a) bool) on the device, a =
+        ``lookahead``: buffers of the session, allocated at the first call and valid until the next ``finish``.  For a chosen slot with
+        ``len`` frames row k - 1 (k = 1 .. a) holds the pose of frame c = len - 1 - a + k, ``fresh`` set iff c >= 0 and c is a multiple of
+        the prediction stride; a row that is not fresh holds the slot's previous pose, as a push does.  Rows of slots that were not chosen
+        are zeros with ``fresh`` 0.  The one rule, extended: row k - 1 is the pose ``predict.predict_tracks`` gives for frame c of the WHOLE
+        track (same ``mask_stride``, ``flip``, ``resolutions``, ``root_relative``, ``valid``, ``repair_joints``, ``keypoints``) -- the
+        frames behind the track's end are padded as the end of a video is --, and the pose a session of the same shape with lookahead
+        a - k, pushed the same frames, returns at its last push.
+        A session with ``camera``: roots (slots, a, 3) float32 and root_state (slots, a) uint8 are appended, by ``push``'s rule at frame c
+        (``LiveRootHost.drain``).  A session with ``smooth``: the filtered rows stand in place of poses and roots (one sample per fresh
+        row, at frame c: ``LiveOneEuroHost.drain``); ``drain_raw_poses`` / ``drain_raw_roots`` are the unfiltered rows.
+        Slots that were not chosen are untouched -- counters, rings, held pose, held root and filter state keep their bits -- and the next
+        ``push`` continues their tracks; but the buffers the previous ``push`` returned are no longer meaningful after ``finish`` (the
+        drain ticks write them).  A session with ``detections``: the tracks end as ``reset`` ends them (ids freed; None also zeroes the
+        counters).  ``lookahead == 0``: empty second dimensions, only the reset is launched.  A session with ``fps`` / ``out_fps``:
+        ValueError (a later change: its drain needs the end of the model-rate track).
+        Enqueues a drain ticks (uu3d_stream_drain_commit, the tick's own forward and emit, uu3d_stream_root_drain, the filters,
+        uu3d_stream_drain_file: no stage, no uu3d_frame_features; with ``graph`` ONE more captured graph, replayed a times) and the reset on
+        the current stream.  The first ``finish`` of a session allocates and captures (``captures`` goes from 1 to 2 and stays), and so
+        waits for the device once; every later one never waits."""
+        if self.rate is not None:
+            raise ValueError("finish in a session with fps / out_fps is not supported yet (a later change): the drain of a source-rate session "
+                             "needs the end of the model-rate track")
+        torch = self._torch
+        m = self.model
+        dev = m.device
+        chosen = None
+        if slots is not None:
+            chosen = np.zeros(self.slots, np.uint8)
+            chosen[np.asarray(slots, np.int64).reshape(-1)] = 1
+        with torch.cuda.device(dev):
+            if m._weights_dirty or getattr(m, "_pending_assigns", False):
+                m._sync_from_trainer()
+                self._zero_features()
+            if self._drain_result is None:
+                self._init_drain()
+            if self.lookahead > 0:
+                if chosen is None:
+                    self._drain_mask.fill_(1)
+                else:
+                    self._drain_mask.copy_(torch.from_numpy(chosen).pin_memory(), non_blocking=True)
+                self._drain_rows.zero_()
+                cur = torch.cuda.current_stream(dev)
+                for _ in range(self.lookahead):
+                    if self.graph:
+                        self._drain_graph.replay()
+                    else:
+                        self._run(self._drain_steps, cur)
+        self.reset(slots)
+        return self._drain_result
+
+    def _drain_rows_of(self, name, needs):
+        if self._drain_result is None or name not in self._drain_named:
+            raise AttributeError(f"drain_raw_{name} needs a session {needs} after its first finish()")
+        return self._drain_named[name]
+
+    @property
+    def drain_raw_poses(self):
+        """(slots, lookahead, J, 3) float32 on the device: the poses of the last ``finish`` as the drain ticks emitted them, unfiltered -- in
+        a session without ``smooth`` the buffer ``finish`` returns."""
+        return self._drain_rows_of("poses", "")
+
+    @property
+    def drain_raw_roots(self):
+        """(slots, lookahead, 3) float32 on the device (sessions with ``camera``): the roots of the last ``finish``, unfiltered."""
+        return self._drain_rows_of("roots", "with camera")
+
     @property
     def frames(self):
         """MODEL frames per slot since its last reset (without ``fps``: the frames pushed): the device counters themselves, (slots,) int32."""
@@ -1149,7 +1348,7 @@ class StreamSession(object):
         """Wait for what is in flight and give the session's workspace back."""
         if getattr(self, "_state", None) is not None:
             self._torch.cuda.synchronize(self.model.device)
-            self._graph = None
+            self._graph = self._drain_graph = None
             self.model._ws.pop(self._key, None)
             self._state = None
 
@@ -1161,7 +1360,7 @@ class StreamSession(object):
 
 
 def replay_tracks(model, config, tracks, resolutions=None, mask_stride=None, flip=None, lookahead=0, root_relative=True, graph=True, valid=None, fps=None,
-                  model_fps=50, out_fps=None, **options):
+                  model_fps=50, out_fps=None, drain=False, **options):
     """Push complete tracks tick by tick, one slot per track (a slot is inactive once its track has ended) -> per track the pose the
     session returned at each of its ticks, (T_i, J, 3) float32, and the fresh flags (T_i,) bool, as host arrays.  One copy to the host,
     at the end.  ``valid`` as ``predict.predict_tracks``: None, "finite" (rows with a NaN / Inf coordinate are missing frames) or one (T_i,)
@@ -1172,7 +1371,13 @@ def replay_tracks(model, config, tracks, resolutions=None, mask_stride=None, fli
     then be (T_i, J), one flag per joint.  ``keypoints=M`` (from ``options`` as well): a session with ``keypoints``; the tracks are
     (T_i, K_in, 2) and per-joint entries of ``valid`` (T_i, K_in).  ``camera=C, min_root_joints=N`` (from ``options`` as well): a session with
     ``camera`` -- the roots (T_i, 3) float32 and root states (T_i,) uint8 the session returned at each tick are appended per track:
-    -> (poses, fresh, roots, root_state).  ``smooth=F`` (from ``options`` as well): a session with ``smooth``; the same return, filtered."""
+    -> (poses, fresh, roots, root_state).  ``smooth=F`` (from ``options`` as well): a session with ``smooth``; the same return, filtered.
+    ``drain=True``: every slot is finished (``StreamSession.finish``) at the tick its own track ends, while the other slots go on; per
+    track the arrays then have T_i + lookahead rows -- row t is the pose of frame t - lookahead (where it is fresh), so all T_i frames of
+    the track come out, as from ``predict_tracks``.  Still one copy to the host, at the end.  Not with ``fps`` / ``out_fps`` (ValueError)."""
+    if drain and (fps is not None or out_fps is not None):
+        raise ValueError("drain=True together with fps / out_fps is not supported yet (a later change): the drain of a source-rate session "
+                         "needs the end of the model-rate track")
     import torch
     repair_joints, keypoints, camera, min_root_joints, smooth = _live_options(options, "replay_tracks")
     place = {} if camera is None and min_root_joints is None else {"camera": camera, "min_root_joints": min_root_joints}
@@ -1199,6 +1404,12 @@ def replay_tracks(model, config, tracks, resolutions=None, mask_stride=None, fli
                       repair_joints=repair_joints, keypoints=keypoints, **place)
     if camera is not None:                                           # per tick and slot four 32-bit words: the root's bits, the state
         root_words = torch.zeros((ticks, T, 4), dtype=torch.int32, device=model.device)
+    tails = None
+    if drain:                                                         # per slot what its finish returned: finish's buffers last until the next one
+        a = int(lookahead)
+        tails = [torch.zeros((T, a, J, 3), dtype=torch.float32, device=model.device), torch.zeros((T, a), dtype=torch.bool, device=model.device)]
+        if camera is not None:
+            tails += [torch.zeros((T, a, 3), dtype=torch.float32, device=model.device), torch.zeros((T, a), dtype=torch.uint8, device=model.device)]
     if out_fps is None:
         poses = torch.zeros((ticks, T, J, 3), dtype=torch.float32, device=model.device)
         fresh = torch.zeros((ticks, T), dtype=torch.bool, device=model.device)
@@ -1225,6 +1436,11 @@ def replay_tracks(model, config, tracks, resolutions=None, mask_stride=None, fli
             else:
                 words[k, :, 0].copy_(f)
                 words[k, :, 1:].copy_(p.view(torch.int32).view(T, -1))
+            ended = [i for i, n in enumerate(lens) if n == k + 1]
+            if drain and ended:                                       # these tracks end here: their last `lookahead` poses, then the slots are reset
+                for dst, src in zip(tails, s.finish(ended)):
+                    for i in ended:
+                        dst[i].copy_(src[i])
         s.check_range()
     finally:
         s.close()
@@ -1240,11 +1456,14 @@ def replay_tracks(model, config, tracks, resolutions=None, mask_stride=None, fli
         root_words = root_words.cpu().numpy()
         roots = np.ascontiguousarray(root_words[:, :, :3]).view(np.float32)
         out += ([roots[:n, i] for i, n in enumerate(lens)], [root_words[:n, i, 3].astype(np.uint8) for i, n in enumerate(lens)])
+    if drain:
+        tails = [t.cpu().numpy() for t in tails]
+        out = tuple([np.concatenate([rows, tail[i]]) for i, rows in enumerate(per_track)] for per_track, tail in zip(out, tails))
     return out
 
 
 def replay_detections(model, config, detections, counts=None, valid=None, slots=None, resolutions=None, mask_stride=None, flip=None, lookahead=0,
-                      root_relative=True, graph=True, **options):
+                      root_relative=True, graph=True, drain=False, **options):
     """Push ONE video's per-frame detections tick by tick through a ``StreamSession(detections=D)`` and collect the poses per track id.
     ``detections`` (T, D, K, 2); ``counts`` (T,) or None; ``valid``: None, (T, D) or (T, D, K); ``slots`` (None: D); ``resolutions``: None
     or one (w, h); ``options``: ``max_age`` / ``max_dist`` / ``min_common``, ``repair_joints``, ``keypoints``, ``camera`` (one tuple) /
@@ -1252,7 +1471,10 @@ def replay_detections(model, config, detections, counts=None, valid=None, slots=
     -> a list of (track_id, first_frame, poses (n, J, 3) float32, fresh (n,) bool) by track id, host arrays: what the session returned for
     the track's slot at the ticks first_frame .. first_frame + n - 1, the ticks the track was alive (its trailing missing frames
     included; ``predict.predict_detections`` ends a track at its last matched frame).  With ``camera`` every tuple carries two more
-    entries: roots (n, 3) float32 and root_state (n,) uint8 of those ticks.  One copy to the host, at the end."""
+    entries: roots (n, 3) float32 and root_state (n,) uint8 of those ticks.  One copy to the host, at the end.
+    ``drain=True``: ``finish()`` runs after the last tick and its ``lookahead`` rows are appended to the arrays of every track alive at the
+    end of the video (n + lookahead rows).  The limit: a track that died in mid-video (``max_age``) still loses the poses of its last
+    ``lookahead`` frames -- the death happens on the device, and no drain is run there."""
     import torch
     from .predict import _host_array
     detections = _host_array(detections)
@@ -1279,9 +1501,12 @@ def replay_detections(model, config, detections, counts=None, valid=None, slots=
             if rs:
                 root_words[k, :, :3].copy_(rs[0].view(torch.int32))
                 root_words[k, :, 3].copy_(rs[1])
+        tails = [t.clone() for t in s.finish()] if drain else None   # (the ids of the last tick say whose rows they are)
         s.check_range()
     finally:
         s.close()
+    if drain:
+        tails = [t.cpu().numpy() for t in tails]
     poses, words = poses.cpu().numpy(), words.cpu().numpy()
     fresh, ids = words[:, 0] != 0, words[:, 1]
     if placed:
@@ -1290,7 +1515,10 @@ def replay_detections(model, config, detections, counts=None, valid=None, slots=
     out = []
     for tid in range(int(ids.max()) + 1 if ids.size else 0):
         t, slot = np.nonzero(ids == tid)
-        out.append((tid, int(t[0]), poses[t, slot], fresh[t, slot]) + ((roots[t, slot], root_state[t, slot]) if placed else ()))
+        arrays = (poses[t, slot], fresh[t, slot]) + ((roots[t, slot], root_state[t, slot]) if placed else ())
+        if drain and ticks and t[-1] == ticks - 1:                    # alive at the end of the video: the rows finish() gave its slot
+            arrays = tuple(np.concatenate([x, tail[slot[-1]]]) for x, tail in zip(arrays, tails))
+        out.append((tid, int(t[0])) + arrays)
     return out
 
 
@@ -1305,6 +1533,9 @@ def parse_args(argv=None):
     p.add_argument("--lookahead", type=int, default=0, help="frames the answer may lag behind the newest one (default 0)")
     p.add_argument("--resolution", type=float, nargs=2, metavar=("W", "H"), default=None,
                    help="image size in pixels of all tracks; without it the coordinates are taken as normalised already")
+    p.add_argument("--drain", action="store_true",
+                   help="finish every track at its end: the arrays get T + lookahead rows, row t the pose of frame t - lookahead, so the last "
+                        "lookahead frames of a track come out as well; not with --fps")
     p.add_argument("--mask_missing", action="store_true",
                    help="a frame with a NaN or Inf coordinate is a missed detection: the track grows by it, the network never sees it")
     p.add_argument("--fps", type=_rate_argument, default=None, metavar="F",
@@ -1337,6 +1568,8 @@ def parse_args(argv=None):
         p.error("--smooth / --smooth_root with --out_fps is not supported")
     if args.out_fps is not None and args.fps is None:
         p.error("--out_fps needs --fps")
+    if args.drain and args.fps is not None:
+        p.error("--drain with --fps is not supported yet")
     if args.min_root_joints is not None and args.camera is None:
         p.error("--min_root_joints needs --camera: it is a parameter of the root solve")
     if args.camera is not None and args.out_fps is not None:
@@ -1389,7 +1622,7 @@ def main(argv=None):
     place.update(smooth_option(args))
     model = _load_model(config, args.weights)
     poses, fresh, *rs = replay_tracks(model, config, tracks, resolutions=None if args.resolution is None else tuple(args.resolution),
-                                      lookahead=args.lookahead, **missing, **skeleton, **place,
+                                      lookahead=args.lookahead, **({"drain": True} if args.drain else {}), **missing, **skeleton, **place,
                                       **({} if args.fps is None else {"fps": args.fps}), **({} if args.out_fps is None else {"out_fps": args.out_fps}))
     out = {}
     if rs:
