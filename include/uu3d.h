@@ -893,6 +893,56 @@ int uu3d_stream_one_euro(int32_t slots, int32_t channels, int32_t lookahead, voi
 int uu3d_stream_one_euro_reset(int32_t slots, int32_t channels, void* filter_state_dev, const uint8_t* slot_mask_dev, void* stream);
 
 /*
+ * CONSTANT BONE LENGTHS (predict.predict_tracks(bones=...), predict.bone_lengths, predict.fix_bones; stream.StreamSession(bones=...)): the
+ * network predicts every frame's skeleton on its own, so a person's bone lengths breathe from frame to frame -- and with them, under
+ * ABSOLUTE ROOT POSITION, the depth.  These calls rebuild every pose from the tree root outwards with each bone scaled to ONE length per
+ * track (or slot): the lengths measured over the track, or lengths the caller knows.  No model: the calls take the joint count J <= 64
+ * (beyond: UU3D_ERR_UNSUPPORTED) and run on any (rows, J, 3) f32 buffers.  No accuracy figure is claimed.
+ * THE TREE.  parents_dev (J) i32: the parent of every joint, -1 for the ONE tree root.  paths_dev (J, depth) i32, depth in [1, 64]: row j
+ * lists the non-root joints on the way from the root down to j, j included, root side first, -1 behind the last one (the root's row is all
+ * -1).  predict.Skeleton makes both.  An entry out of range ends a walk or counts as "no bone": nothing is ever read out of bounds.
+ * THE RULE (predict.bone_lengths_host and predict.fix_bones_host are it in numpy, bit for bit).  All in f64, every operation rounded once in
+ * the written order, no fused multiply-add, IEEE sqrt and division.  For a non-root joint j with parent p in frame f:
+ *     d_c = (double) x[f][j][c] - (double) x[f][p][c];   len = sqrt((d_0 * d_0 + d_1 * d_1) + d_2 * d_2)
+ *     track lengths:  L[t][j] = (sum of len over the track's frames in ascending order, only where len is finite and > 0) / (double) count;
+ *                     count == 0: NaN = "not corrected";  L[t][root] = 0.  Given lengths are taken as they are; an entry that is not
+ *                     finite or <= 0 means not corrected.
+ *     fix:  y[root] = x[root], the input bits.  For every other joint j:  acc_c = (double) x[root][c], then for each joint a of j's path
+ *           acc_c = acc_c + d_c(a) * s(a),  s(a) = L[a] / len(a) where L[a] and len(a) are finite and > 0, else 1.0;  y[j][c] = (float) acc_c.
+ * Directions are kept; a NaN frame stays NaN; a zero-length bone keeps its zero offset; the root joint of a root-relative pose stays 0.
+ *
+ *   uu3d_bone_lengths(poses_dev (rows, J, 3) f32, rows, J, parents_dev, track_start_dev, track_len_dev (num_tracks) i64: the rows of each
+ *       track, num_tracks <= 2^20, lengths_dev (num_tracks, J) f64, counts_dev (num_tracks, J) i64 or NULL, stream): one launch, one lane per
+ *       (track, joint) walks the track's rows in order; adjacent lanes are adjacent joints of one row.  rows == 0: nothing is launched.
+ *   uu3d_fix_bones(in_dev, out_dev (rows, J, 3) f32, out != in, rows <= 2^32, J, parents_dev, paths_dev, depth, row_track_dev (rows) i32 or
+ *       NULL = track 0, num_tracks, lengths_dev (num_tracks, J) f64, stream): one launch, one lane per (row, joint) accumulates its own
+ *       path.  Several lanes recompute a bone's scale; this is intended: no lane holds an array of partial positions, so the kernel uses
+ *       no scratch memory.  A row whose track id is out of range is rebuilt with nothing corrected.
+ *   LIVE.  The state block of uu3d_stream_bones_bytes(slots, J) bytes (0: out of range -- slots in [1, 2^20], J in [1, 64]), 256-byte
+ *   aligned, zeroed by uu3d_stream_bones_reset, holds per slot and joint a sum (f64) and a count (i32).
+ *   uu3d_stream_bones(slots, J, bones_state_dev, parents_dev, paths_dev, depth, active_dev, fresh_dev (slots) u8, poses_dev (slots, J, 3)
+ *       f32 -- what the tick emitted, only read --, given_lengths_dev (slots, J) f64 or NULL, out_dev (slots, J, 3) f32, a buffer of its
+ *       own, lengths_out_dev (slots, J) f64 or NULL, stream): one launch, one wave per slot, lane j owns joint j.  With given_lengths_dev
+ *       NULL an active slot whose pose is fresh first adds its finite, positive len to the sum and increments the count; its L is then
+ *       sum / (double) count.  After that EVERY slot, fresh or not, writes out = fix(poses, L of the slot): the output is a pure function
+ *       of the raw pose and the slot's lengths, so a slot that holds its previous raw pose returns its previous fixed pose bit for bit.
+ *       The running mean is CAUSAL -- the fresh poses seen so far -- and differs from the offline mean over the whole track, which a live
+ *       session cannot know.  With given lengths the state is not touched.
+ *   uu3d_stream_bones_reset(slots, J, bones_state_dev, slot_mask_dev (slots) u8 or NULL = every slot, stream): the chosen slots' sums and
+ *       counts are zero; beside uu3d_stream_reset, with the same mask (host-made or written on the device).
+ * Every output and state element has one writer, no atomics, the caller's buffers are only read: bitwise repeatable, capturable.
+ */
+int uu3d_bone_lengths(const float* poses_dev, int64_t rows, int32_t num_keypoints, const int32_t* parents_dev, const int64_t* track_start_dev,
+                      const int64_t* track_len_dev, int32_t num_tracks, double* lengths_dev, int64_t* counts_dev, void* stream);
+int uu3d_fix_bones(const float* in_dev, float* out_dev, int64_t rows, int32_t num_keypoints, const int32_t* parents_dev, const int32_t* paths_dev,
+                   int32_t depth, const int32_t* row_track_dev, int32_t num_tracks, const double* lengths_dev, void* stream);
+size_t uu3d_stream_bones_bytes(int32_t slots, int32_t num_keypoints);
+int uu3d_stream_bones(int32_t slots, int32_t num_keypoints, void* bones_state_dev, const int32_t* parents_dev, const int32_t* paths_dev,
+                      int32_t depth, const uint8_t* active_dev, const uint8_t* fresh_dev, const float* poses_dev,
+                      const double* given_lengths_dev, float* out_dev, double* lengths_out_dev, void* stream);
+int uu3d_stream_bones_reset(int32_t slots, int32_t num_keypoints, void* bones_state_dev, const uint8_t* slot_mask_dev, void* stream);
+
+/*
  * LIVE TRACKS: END OF A TRACK (stream.StreamSession.finish): a session with lookahead a answers the push that made frame t the newest with
  * the pose of frame t - a, so a track that ENDS still owes the poses of its last a frames.  A DRAIN TICK moves the centre of the slot's
  * window one frame towards its newest frame without filing a frame: for a slot with `frames` frames the k-th drain tick (k = 1 .. a) gives

@@ -19,9 +19,12 @@ fast); the two must agree bit for bit.
 --smooth: also predict_tracks(smooth=True) -- with --camera predict_tracks(camera=..., smooth=True), poses and roots filtered -- next to the
 same call without smooth in the same process: smooth_extra_ms is the difference of the two medians (one or two more launches, each a serial
 walk over the frames of a track); the result must equal predict.one_euro_host on the unfiltered result bit for bit.
+--bones: also predict_tracks(bones="track") -- with --camera predict_tracks(camera=..., bones="track") -- next to the same call without bones in
+the same process: bones_extra_ms is the difference of the two medians (two more launches: the lengths, the fix); the poses must equal
+predict.fix_bones_host with predict.bone_lengths_host on the result without bones, bit for bit.  Informational: no threshold.
    python tools/predict_tracks_bench.py [--tracks 40] [--frames 2500] [--batch 512] [--reps 3] [--cases h36m_351:5,h36m_81:4] [--missing 0.3]
                                         [--fps 30] [--repair_joints 5 --missing_joints 0.1] [--keypoints coco17]
-                                        [--camera 1145 1145 960 540] [--smooth]"""
+                                        [--camera 1145 1145 960 540] [--smooth] [--bones]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -42,6 +45,7 @@ def main():
     ap.add_argument("--camera", type=float, nargs=4, default=None, metavar=("FX", "FY", "CX", "CY"),
                     help="also time predict_tracks(camera=...) against .cpu() and the numpy rule behind the plain call")
     ap.add_argument("--smooth", action="store_true", help="also time predict_tracks(smooth=True) (with --camera: poses and roots) against the same call without")
+    ap.add_argument("--bones", action="store_true", help='also time predict_tracks(bones="track") (with --camera: with the camera) against the same call without')
     args = ap.parse_args()
     import numpy as np, torch
     import uplift_upsample_3dhpe_amd as pkg
@@ -150,6 +154,10 @@ def main():
             return predict.predict_tracks(model, cfg, px, resolutions=(W, H), mask_stride=int(msv), flip=True, reuse_frames=reuse, batch_size=args.batch,
                                           smooth=True, **({} if args.camera is None else {"camera": tuple(args.camera)}))
 
+        def bones_path():
+            return predict.predict_tracks(model, cfg, px, resolutions=(W, H), mask_stride=int(msv), flip=True, reuse_frames=reuse, batch_size=args.batch,
+                                          bones="track", **({} if args.camera is None else {"camera": tuple(args.camera)}))
+
         row = dict(config=name, mask_stride=int(msv), tracks=args.tracks, frames=total, batch=args.batch, reuse_frames=reuse)
         outs = {}
         cases = [("predict_tracks", new_path), ("predict_tracks_to_host", lambda: new_path(True)), ("composition", composition)]
@@ -170,6 +178,8 @@ def main():
             cases += [("predict_tracks_camera", camera_path), ("host_camera", camera_host)]
         if args.smooth:
             cases.append(("predict_tracks_smooth", smooth_path))
+        if args.bones:
+            cases.append(("predict_tracks_bones", bones_path))
         for key, fn in cases:
             fn()
             torch.cuda.synchronize()
@@ -213,6 +223,14 @@ def main():
                 row["smooth_bits_equal"] = bool(same(got, plain))
             else:
                 row["smooth_bits_equal"] = bool(same(got[0], plain[0]) and same(got[1], plain[1], state=torch.cat(plain[2], 0).cpu().numpy()))
+        if args.bones:
+            base = "predict_tracks_camera" if args.camera is not None else "predict_tracks"
+            row["bones_extra_ms"] = round(row["predict_tracks_bones_ms"] - row[base + "_ms"], 1)
+            lens = [len(t) for t in px]
+            plain = torch.cat(outs[base][0] if args.camera is not None else outs[base], 0).cpu().numpy()
+            got = torch.cat(outs["predict_tracks_bones"][0] if args.camera is not None else outs["predict_tracks_bones"], 0).cpu().numpy()
+            want = predict.fix_bones_host(plain, lens, predict.bone_lengths_host(plain, lens))
+            row["bones_bits_equal"] = bool(np.array_equal(got.view(np.uint32), want.view(np.uint32)))
         row["device"] = torch.cuda.get_device_name(0)
         print(json.dumps(row), flush=True)
         results.append(row)

@@ -4,7 +4,7 @@ uploads them with their mirrored copies and calls ``model([x, mask])`` once -- t
 A tick = host clock from the call to the synchronised result (a live consumer reads every pose); host input in all three variants.
 Median (and 90th percentile) over --ticks ticks after --warmup ticks, per config and slot count.
    python tools/stream_bench.py [--slots 1,8,64] [--cases h36m_81:4,h36m_351:5] [--ticks 300] [--warmup 60] [--lookahead 0] [--fps F [--out_fps G]]
-                                [--repair_joints G] [--detections D] [--camera FX FY CX CY] [--smooth] [--drain]
+                                [--repair_joints G] [--detections D] [--camera FX FY CX CY] [--smooth] [--bones] [--drain]
 --fps F (a float or NUM/DEN): microseconds per PUSH of StreamSession(fps=F) -- one source frame in, one pose out, on average
 model_fps / F sub-ticks -- next to the plain session pushed at the model's rate (the cost of one model tick); the lookahead is raised to
 the smallest one the rate allows.  The numpy baseline is left out.
@@ -27,6 +27,10 @@ camera_minus_graph_us is the difference of the two medians.  The numpy baseline 
 captured tick, with --camera two (poses and roots) -- as smooth_graph_us next to the tick of the same session without smooth (graph_us;
 with --camera both sessions have the camera), measured side by side in the same way.  smooth_minus_graph_us is the difference of the two
 medians.  The numpy baseline is left out.
+--bones (alone or with --camera, not with --smooth or the other options): the tick of StreamSession(bones="track") -- one more launch
+behind the emit, in front of the root solve -- as bones_graph_us next to the tick of the same session without bones (graph_us; with
+--camera both sessions have the camera), measured side by side in the same way.  bones_minus_graph_us is the difference of the two
+medians.  Informational: no threshold.  The numpy baseline is left out.
 --drain (alone): StreamSession.finish() -- `lookahead` drain ticks and the reset, from the call to the synchronised result -- at lookahead 13
 and at the largest one, as finish_us, beside the plain tick of the same session in the same process (graph_us); finish_over_tick is their
 ratio, finish_per_drain_tick_us = finish_us / lookahead.  Each finish follows 8 pushes of a new track; the first finish (allocation and the
@@ -49,9 +53,12 @@ def main():
     ap.add_argument("--detections", type=int, default=None)
     ap.add_argument("--camera", type=float, nargs=4, metavar=("FX", "FY", "CX", "CY"), default=None)
     ap.add_argument("--smooth", action="store_true")
+    ap.add_argument("--bones", action="store_true")
     ap.add_argument("--drain", action="store_true")
     args = ap.parse_args()
-    if args.drain and (args.smooth or args.camera is not None or args.fps is not None or args.repair_joints is not None or args.detections is not None):
+    if args.bones and (args.smooth or args.fps is not None or args.repair_joints is not None or args.detections is not None):
+        ap.error("--bones is not measured together with --smooth / --fps / --repair_joints / --detections")
+    if args.drain and (args.bones or args.smooth or args.camera is not None or args.fps is not None or args.repair_joints is not None or args.detections is not None):
         ap.error("--drain is measured alone")
     if args.smooth and (args.fps is not None or args.repair_joints is not None or args.detections is not None):
         ap.error("--smooth is not measured together with --fps / --repair_joints / --detections")
@@ -179,9 +186,11 @@ def main():
 
             def camera_variants():
                 new = lambda **kw: stream.StreamSession(model, cfg, slots=T, resolutions=(W, H), mask_stride=ms, flip=True, lookahead=args.lookahead, **kw)
+                place = {} if args.camera is None else {"camera": tuple(args.camera)}
                 if args.smooth:                                       # both with the camera (if any), one of them with the filter behind the tick
-                    place = {} if args.camera is None else {"camera": tuple(args.camera)}
                     pair = {"smooth_graph": new(smooth=True, **place), "graph": new(**place)}
+                elif args.bones:                                      # ... one of them with the fix behind the emit
+                    pair = {"bones_graph": new(bones="track", **place), "graph": new(**place)}
                 else:
                     pair = {"camera_graph": new(camera=tuple(args.camera)), "graph": new()}
                 ts = {key: [] for key in pair}
@@ -194,7 +203,7 @@ def main():
                 for s in pair.values():
                     s.check_range()
                     s.close()
-                row.update(camera=None if args.camera is None else list(args.camera), smooth=bool(args.smooth))
+                row.update(camera=None if args.camera is None else list(args.camera), smooth=bool(args.smooth), bones=bool(args.bones))
                 return tuple((key, lambda key=key: ts[key][args.warmup:]) for key in pair)
 
             if args.drain:
@@ -242,7 +251,7 @@ def main():
                             ("md_graph", lambda: session(True, valid=seen.all(axis=2), missed_detections=True)))
             if args.detections is not None:
                 variants = detections_variants()
-            if args.camera is not None or args.smooth:
+            if args.camera is not None or args.smooth or args.bones:
                 variants = camera_variants()
             for key, fn in variants:
                 ts = np.asarray(fn())
@@ -250,6 +259,8 @@ def main():
                 row[key + "_p90_us"] = round(1e6 * float(np.percentile(ts, 90)), 1)
             if args.smooth:
                 row["smooth_minus_graph_us"] = round(row["smooth_graph_us"] - row["graph_us"], 1)
+            elif args.bones:
+                row["bones_minus_graph_us"] = round(row["bones_graph_us"] - row["graph_us"], 1)
             elif args.camera is not None:
                 row["camera_minus_graph_us"] = round(row["camera_graph_us"] - row["graph_us"], 1)
             elif args.detections is not None:

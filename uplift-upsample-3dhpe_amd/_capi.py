@@ -48,6 +48,7 @@ EXPORTED_SYMBOLS = (
     "uu3d_one_euro_tracks", "uu3d_stream_one_euro_bytes", "uu3d_stream_one_euro", "uu3d_stream_one_euro_reset",
     "uu3d_stream_drain_bytes", "uu3d_stream_drain_layout", "uu3d_stream_drain_commit", "uu3d_stream_root_drain", "uu3d_stream_drain_file",
     "uu3d_stream_drain_reset",
+    "uu3d_bone_lengths", "uu3d_fix_bones", "uu3d_stream_bones_bytes", "uu3d_stream_bones", "uu3d_stream_bones_reset",
 )
 # include/uu3d_ops.h
 OPS_SYMBOLS = (
@@ -321,6 +322,17 @@ def load_library(path=None):
     lib.uu3d_stream_drain_file.argtypes = [i32, i32, vp, i32, C.POINTER(vp), C.POINTER(i32), C.POINTER(vp)] + [vp] * 5
     lib.uu3d_stream_drain_reset.restype = C.c_int
     lib.uu3d_stream_drain_reset.argtypes = [i32, vp, vp, vp]
+    # constant bone lengths: the lengths of finished tracks, their fix, and the live form of a session
+    lib.uu3d_bone_lengths.restype = C.c_int
+    lib.uu3d_bone_lengths.argtypes = [vp, i64, i32, vp, vp, vp, i32, vp, vp, vp]
+    lib.uu3d_fix_bones.restype = C.c_int
+    lib.uu3d_fix_bones.argtypes = [vp, vp, i64, i32, vp, vp, i32, vp, i32, vp, vp]
+    lib.uu3d_stream_bones_bytes.restype = sz
+    lib.uu3d_stream_bones_bytes.argtypes = [i32, i32]
+    lib.uu3d_stream_bones.restype = C.c_int
+    lib.uu3d_stream_bones.argtypes = [i32, i32, vp, vp, vp, i32] + [vp] * 7
+    lib.uu3d_stream_bones_reset.restype = C.c_int
+    lib.uu3d_stream_bones_reset.argtypes = [i32, i32, vp, vp, vp]
     lib.uu3d_world_to_cam_2d.restype = C.c_int
     lib.uu3d_world_to_cam_2d.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
     lib.uu3d_set_schedule.restype = C.c_int

@@ -25,6 +25,7 @@ synchronises the stream once after the last forward (its pipeline's buffers go a
     python -m uplift_upsample_3dhpe_amd.predict --config C --weights W.h5 --input tracks.npz --output out.npz \\
         [--resolution W H] [--mask_stride S] [--keyframes_only] [--mask_missing] [--fps F] [--out_fps F] [--repair_joints G] [--min_score S]
         [--keypoints NAME] [--camera FX FY CX CY] [--min_root_joints N] [--smooth MIN_CUTOFF BETA D_CUTOFF] [--smooth_root MIN_CUTOFF BETA D_CUTOFF]
+        [--bones track|FILE.npy]
 
 Per-joint missed detections: ``predict_tracks(..., valid=..., repair_joints=G)`` fills a joint the detector lost for up to G frames by
 linear interpolation between the nearest frames where it was seen (uu3d_repair_joints, in front of the two front kernels above; the rule
@@ -49,6 +50,12 @@ Steady output: the root is solved frame by frame and the poses carry the detecto
 smooth=OneEuro(min_cutoff, beta, d_cutoff))`` passes the returned poses and roots through the One-Euro filter on the device
 (uu3d_one_euro_tracks: one lane per track and channel walks the frames in order; ``one_euro`` is the launch alone; the rule in numpy:
 ``one_euro_host``).  The filter is causal, so the result lags as a live session's does; ``predict_detections(..., smooth=...)`` hands it on.
+
+Constant bone lengths: the network predicts every frame's skeleton on its own, so nothing holds a person's bone lengths constant over a
+track.  ``predict_tracks(..., bones="track")`` rebuilds every pose from the root outwards with each bone at the track's mean length;
+``bones=lengths`` does it with lengths that are known -- calibrated once with ``bone_lengths`` on a recording -- which also takes the
+model's scale error out of the depth ``camera`` solves (``Skeleton`` / ``SKELETONS``: the tree; uu3d_bone_lengths, uu3d_fix_bones;
+``bone_lengths`` / ``fix_bones`` are the launches alone; the rule in numpy: ``bone_lengths_host`` / ``fix_bones_host``).
 """
 import argparse
 import ctypes as C
@@ -827,7 +834,9 @@ def predict_detections(model, config, detections, counts=None, valid=None, slots
     ``association_tracks_host``, bit for bit.  Needs a model with strided input.  Greedy, no motion model: no tracking accuracy is claimed.
     ``camera``: one (fx, fy, cx, cy) or one per VIDEO, handed to ``predict_tracks`` per track the way ``resolutions`` is: the tuples become
     (track_id, first_frame, poses, roots (n, 3) float32, root_state (n,) uint8) -- every person of a video in the same camera space.
-    ``smooth``: handed to ``predict_tracks`` as it is -- every track's poses (and roots) filtered from its birth frame on."""
+    ``smooth``: handed to ``predict_tracks`` as it is -- every track's poses (and roots) filtered from its birth frame on.
+    ``bones``: handed to ``predict_tracks`` as it is -- "track" or one (J,) array of lengths for every person (the tracks are only known
+    after the association, so there is no per-track list here)."""
     import torch
     assoc, options = _association_options(options)
     camera = options.pop("camera", None)
@@ -1214,6 +1223,276 @@ def one_euro(x, lens, rate, filt, state=None):
     return out
 
 
+# ---- constant bone lengths: rigid skeletons over a track (include/uu3d.h, CONSTANT BONE LENGTHS) -----------------------------------------------
+MAX_BONE_JOINTS = 64                                                  # kBonesMaxJoints
+
+
+class Skeleton(object):
+    """The tree of a joint layout: ``parents`` is a length-J integer sequence, ``parents[j]`` the joint that joint j hangs on and -1 for the
+    ONE tree root; every other entry in [0, J), no cycles, J <= 64.  Anything else is a ValueError.  Derived --
+        ``root``    the tree root;
+        ``order``   all joints, every parent in front of its children: again and again the lowest joint whose parent is placed already;
+        ``paths``   per joint j the non-root joints on the way from the root down to j, j included, root side first (the root's is empty);
+        ``depth``   the longest path (at least 1: the second dimension of the device table).
+    Immutable; the tables are made once and uploaded once per device (``device_tables``), as a ``KeypointMap``'s."""
+
+    def __init__(self, parents):
+        try:
+            a = np.asarray(parents)
+        except (TypeError, ValueError):
+            raise ValueError(f"Skeleton takes a sequence of J parent indices, got {parents!r}") from None
+        if a.ndim != 1 or a.dtype.kind not in "iu" or not 1 <= len(a) <= MAX_BONE_JOINTS:
+            raise ValueError(f"Skeleton takes a sequence of 1 to {MAX_BONE_JOINTS} integer parent indices (J <= {MAX_BONE_JOINTS}), got "
+                             f"{'shape ' + str(a.shape) + ' of ' + str(a.dtype) if a.ndim else repr(parents)}")
+        p = [int(v) for v in a]
+        J = len(p)
+        roots = [j for j, v in enumerate(p) if v == -1]
+        if len(roots) != 1:
+            raise ValueError(f"Skeleton needs exactly one -1, the tree root, got {len(roots)}")
+        for j, v in enumerate(p):
+            if v != -1 and not 0 <= v < J:
+                raise ValueError(f"Skeleton: the parent of joint {j} must be -1 or in [0, {J}), got {v}")
+        paths = []
+        for j in range(J):
+            up, a_ = [], j
+            while p[a_] != -1:
+                up.append(a_)
+                a_ = p[a_]
+                if len(up) > J:
+                    raise ValueError(f"Skeleton: joint {j} never reaches the root: the parents form a cycle")
+            paths.append(tuple(reversed(up)))
+        placed, order = {roots[0]}, [roots[0]]
+        while len(order) < J:
+            nxt = min(j for j in range(J) if j not in placed and p[j] in placed)
+            placed.add(nxt)
+            order.append(nxt)
+        self.parents, self.joints, self.root = tuple(p), J, roots[0]
+        self.order, self.paths = tuple(order), tuple(paths)
+        self.depth = max(1, max(len(q) for q in paths))
+        self._tables = {}
+
+    def tables(self):
+        """-> (parents (J,) int32, paths (J, depth) int32 with -1 behind a joint's last entry): what the device reads."""
+        paths = np.full((self.joints, self.depth), -1, np.int32)
+        for j, q in enumerate(self.paths):
+            paths[j, :len(q)] = q
+        return np.array(self.parents, np.int32), paths
+
+    def device_tables(self, device):
+        """The two tables on ``device``: uploaded at the first call, which waits for the copy once -- whatever stream uses them later finds
+        them there --, and kept for the life of the skeleton."""
+        import torch
+        key = str(torch.device(device))
+        if key not in self._tables:
+            parents, paths = self.tables()
+            both = _upload(np.concatenate([parents, paths.reshape(-1)]), np.int32, device)
+            torch.cuda.current_stream(device).synchronize()
+            self._tables[key] = (both[:self.joints], both[self.joints:].view(self.joints, self.depth))
+        return self._tables[key]
+
+    def __repr__(self):
+        return f"Skeleton(joints={self.joints}, root={self.root})"
+
+
+# The tree of H36MOrder17P (the layout of ``_h36m17_from``), the pelvis as root: right leg ankle -> knee -> hip -> pelvis, left leg
+# likewise, spine torso -> pelvis, neck -> torso, head -> neck, head top -> head, arms wrist -> elbow -> shoulder -> neck.  It commutes
+# with AUGM_FLIP_KEYPOINT_ORDER: parents[flip[j]] == flip[parents[j]].
+SKELETONS = {
+    "h36m17": Skeleton([1, 2, 6, 6, 3, 4, -1, 8, 6, 7, 9, 12, 13, 7, 7, 14, 15]),
+}
+
+
+def skeleton_of(skeleton, J=None):
+    """A name of ``SKELETONS`` or a ``Skeleton`` -> the ``Skeleton``; ``J``: the joint count it must have (ValueError naming ``Skeleton``)."""
+    if isinstance(skeleton, str):
+        if skeleton not in SKELETONS:
+            raise ValueError(f"skeleton must be a Skeleton or one of {sorted(SKELETONS)}, got {skeleton!r}")
+        sk, what = SKELETONS[skeleton], repr(skeleton)
+    elif isinstance(skeleton, Skeleton):
+        sk, what = skeleton, repr(skeleton)
+    else:
+        raise ValueError(f"skeleton must be a Skeleton or one of {sorted(SKELETONS)}, got {skeleton!r}")
+    if J is not None and sk.joints != int(J):
+        raise ValueError(f"the skeleton {what} has {sk.joints} joints, the poses have {int(J)}: describe the layout's tree with "
+                         f"predict.Skeleton(parents) and pass predict.Bones(lengths, skeleton=...)")
+    return sk
+
+
+class Bones(object):
+    """``bones=`` with a tree of your own: ``lengths`` is "track" (measure every track, or slot, itself), a (J,) array of lengths in the
+    poses' units, indexed by CHILD joint (the root's entry is ignored), or a list of such arrays, one per track or slot; ``skeleton``: a
+    name of ``SKELETONS`` or a ``Skeleton``."""
+    __slots__ = ("lengths", "skeleton")
+
+    def __init__(self, lengths="track", skeleton="h36m17"):
+        self.lengths, self.skeleton = lengths, skeleton_of(skeleton)
+
+    def __repr__(self):
+        return f"Bones(lengths={self.lengths!r}, skeleton={self.skeleton!r})"
+
+
+def check_bones(bones, count, J, root=None, per="track"):
+    """``bones`` of ``predict_tracks`` / ``StreamSession`` -> None (no fix) or (skeleton, lengths): lengths None for "track", else a
+    (count, J) float64 array, the root's column 0.  ``J``: the joints of the poses; ``root``: the joint that is subtracted from the returned
+    poses, or None when they are not root-relative -- the tree root must be that joint, so that it stays exactly 0."""
+    if bones is None:
+        return None
+    b = bones if isinstance(bones, Bones) else Bones.__new__(Bones)
+    if not isinstance(bones, Bones):
+        b.lengths, b.skeleton = bones, "h36m17"
+    sk = skeleton_of(b.skeleton, J)
+    if root is not None and sk.root != int(root):
+        raise ValueError(f"bones: the tree root of the skeleton is joint {sk.root}, but the poses are relative to joint {int(root)} "
+                         f"(ROOT_KEYTPOINT): rebuilt from another root, that joint would not stay 0")
+    if isinstance(b.lengths, str):
+        if b.lengths != "track":
+            raise ValueError(f'bones must be None, "track", a ({int(J)},) array of lengths, one such array per {per} or a predict.Bones, got {b.lengths!r}')
+        return sk, None
+    try:
+        L = np.array([np.asarray(_host_array(v), np.float64) for v in b.lengths] if isinstance(b.lengths, (list, tuple)) and len(b.lengths)
+                     and np.ndim(b.lengths[0]) else _host_array(b.lengths), np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f'bones must be None, "track", a ({int(J)},) array of lengths, one such array per {per} or a predict.Bones') from None
+    if L.shape == (int(J),):
+        L = np.tile(L, (int(count), 1))
+    if L.shape != (int(count), int(J)):
+        raise ValueError(f"bones: the lengths must be ({int(J)},) or one such array per {per} ({int(count)}), got shape {L.shape}")
+    L = np.ascontiguousarray(L)
+    L[:, sk.root] = 0.0
+    return sk, L
+
+
+def _bone_offsets(X, sk):
+    """(G, J, 3) float32 poses -> (d (G, J, 3) float64: x[j] - x[parent of j], zeros for the root; len (G, J) float64)."""
+    X64 = X.astype(np.float64)
+    par = np.array(sk.parents, np.int64)
+    d = X64 - X64[:, np.where(par >= 0, par, np.arange(sk.joints))]
+    return X64, d, np.sqrt((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2])
+
+
+def _bone_poses(poses, skeleton):
+    X = np.asarray(_host_array(poses), np.float32)
+    if X.ndim != 3 or X.shape[2] != 3:
+        raise ValueError(f"poses must be (G, J, 3), got {X.shape}")
+    return X, skeleton_of(skeleton, X.shape[1])
+
+
+def bone_lengths_host(poses, lens=None, skeleton="h36m17", return_counts=False):
+    """The length rule of CONSTANT BONE LENGTHS (include/uu3d.h) in numpy, written to be read: what uu3d_bone_lengths computes, bit for
+    bit.  ``poses`` (G, J, 3) float32: the rows of all tracks back to back; ``lens``: rows per track (None: one track)
+    -> lengths (tracks, J) float64, indexed by CHILD joint: the mean of the bone's length over the track's frames where it is finite
+    and > 0, summed in ascending frame order as a plain loop (np.sum adds pairwise); NaN where there is no such frame ("not corrected");
+    0 for the tree root.  ``return_counts``: -> (lengths, counts (tracks, J) int64)."""
+    X, sk = _bone_poses(poses, skeleton)
+    lens = _root_lens(lens, len(X))
+    is_bone = np.array(sk.parents) >= 0
+    L, N = np.zeros((len(lens), sk.joints), np.float64), np.zeros((len(lens), sk.joints), np.int64)
+    with np.errstate(all="ignore"):
+        _, _, ln = _bone_offsets(X, sk)
+        first = 0
+        for t, n in enumerate(lens.tolist()):
+            total, count = np.zeros(sk.joints, np.float64), np.zeros(sk.joints, np.int64)
+            for i in range(first, first + n):
+                ok = is_bone & np.isfinite(ln[i]) & (ln[i] > 0)
+                total = np.where(ok, total + ln[i], total)
+                count += ok
+            L[t] = np.where(is_bone, np.where(count > 0, total / count.astype(np.float64), np.nan), 0.0)
+            N[t] = count
+            first += n
+    return (L, N) if return_counts else L
+
+
+def _bone_length_table(lengths, tracks, J):
+    L = np.asarray(_host_array(lengths), np.float64)
+    if L.shape == (J,):
+        L = np.tile(L, (tracks, 1))
+    if L.shape != (tracks, J):
+        raise ValueError(f"lengths must be ({J},) or ({tracks}, {J}): one row per track, got {L.shape}")
+    return np.ascontiguousarray(L)
+
+
+def fix_bones_host(poses, lens, lengths, skeleton="h36m17"):
+    """The fix of CONSTANT BONE LENGTHS in numpy, written to be read: what uu3d_fix_bones computes, bit for bit.  ``poses`` (G, J, 3)
+    float32, ``lens`` as ``bone_lengths_host``; ``lengths`` (J,) or (tracks, J) float64 by child joint -> the rebuilt poses, float32.
+    The root keeps its bits.  Every other joint j: acc = x[root] widened, then per joint a on ``skeleton.paths[j]``, root side first,
+    ``acc = acc + d(a) * s(a)`` with ``s(a) = L[a] / len(a)`` where L[a] and len(a) are finite and > 0, else 1.0; the result is acc
+    rounded once.  A product and a sum are two roundings (no fused multiply-add); the joints of a path are a plain loop."""
+    X, sk = _bone_poses(poses, skeleton)
+    lens = _root_lens(lens, len(X))
+    L = np.repeat(_bone_length_table(lengths, len(lens), sk.joints), lens, axis=0)        # (G, J): the lengths of each row's track
+    out = X.copy()
+    with np.errstate(all="ignore"):
+        X64, d, ln = _bone_offsets(X, sk)
+        ok = np.isfinite(L) & (L > 0) & np.isfinite(ln) & (ln > 0)
+        s = np.where(ok, L / np.where(ok, ln, 1.0), 1.0)
+        for j in sk.order[1:]:
+            acc = X64[:, sk.root].copy()
+            for a in sk.paths[j]:
+                acc = acc + d[:, a] * s[:, a, None]
+            out[:, j] = acc.astype(np.float32)
+    return out
+
+
+def _bone_device_poses(poses, skeleton):
+    import torch
+    if not isinstance(poses, torch.Tensor) or poses.dim() != 3 or poses.shape[2] != 3 or poses.dtype != torch.float32 or not poses.is_contiguous() \
+            or not poses.is_cuda:
+        raise ValueError(f"poses must be a contiguous (G, J, 3) float32 device tensor, got {tuple(getattr(poses, 'shape', ()))}")
+    return skeleton_of(skeleton, int(poses.shape[1]))
+
+
+def bone_lengths(poses, lens=None, skeleton="h36m17", return_counts=False):
+    """uu3d_bone_lengths on the current stream: ``bone_lengths_host`` on a device tensor, one launch, nothing copies to the host or waits
+    (the per-track plan goes up pinned and asynchronously).  ``poses``: a contiguous (G, J, 3) float32 device tensor, only read
+    -> lengths (tracks, J) float64 on the device (``return_counts``: and counts (tracks, J) int64).  Also the calibration helper: the
+    lengths of one recording are what ``bones=`` takes for the next."""
+    import torch
+    sk = _bone_device_poses(poses, skeleton)
+    lib = _capi.load_library()
+    dev, G, J = poses.device, int(poses.shape[0]), sk.joints
+    lens = _root_lens(lens, G)
+    T = len(lens)
+    L = torch.zeros((T, J), dtype=torch.float64, device=dev)
+    N = torch.zeros((T, J), dtype=torch.int64, device=dev) if return_counts else None
+    parents, _ = sk.device_tables(dev)
+    plan = _upload(np.stack([np.concatenate([[0], np.cumsum(lens)[:-1]]), lens]), np.int64, dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if G == 0:                                                    # (no rows: the library launches nothing; a track without rows is "not corrected")
+            L.fill_(float("nan"))
+            L[:, sk.root] = 0.0
+        _capi.check(lib, lib.uu3d_bone_lengths(_ptr(poses), G, J, _ptr(parents), _ptr(plan[0]), _ptr(plan[1]), T, _ptr(L), _ptr(N),
+                                               C.c_void_p(stream)), None)
+    return (L, N) if return_counts else L
+
+
+def fix_bones(poses, lens, lengths, skeleton="h36m17"):
+    """uu3d_fix_bones on the current stream: ``fix_bones_host`` on a device tensor, one launch, nothing copies to the host or waits.
+    ``poses``: a contiguous (G, J, 3) float32 device tensor, only read; ``lengths``: what ``bone_lengths`` returned -- a contiguous
+    (tracks, J) float64 device tensor -- or a host array (J,) / (tracks, J) -> the rebuilt poses, a fresh device tensor."""
+    import torch
+    sk = _bone_device_poses(poses, skeleton)
+    lib = _capi.load_library()
+    dev, G, J = poses.device, int(poses.shape[0]), sk.joints
+    lens = _root_lens(lens, G)
+    T = len(lens)
+    if isinstance(lengths, torch.Tensor) and lengths.is_cuda:
+        if tuple(lengths.shape) != (T, J) or lengths.dtype != torch.float64 or not lengths.is_contiguous() or lengths.device != dev:
+            raise ValueError(f"lengths must be a contiguous ({T}, {J}) float64 tensor on the poses' device, got {tuple(lengths.shape)} of {lengths.dtype}")
+    else:
+        lengths = _upload(_bone_length_table(lengths, T, J), np.float64, dev)
+    out = torch.empty_like(poses)
+    if G == 0:
+        return out
+    parents, paths = sk.device_tables(dev)
+    row_track = None if T == 1 else _upload(np.repeat(np.arange(T, dtype=np.int32), lens), np.int32, dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _capi.check(lib, lib.uu3d_fix_bones(_ptr(poses), _ptr(out), G, J, _ptr(parents), _ptr(paths), sk.depth, _ptr(row_track), T, _ptr(lengths),
+                                            C.c_void_p(stream)), None)
+    return out
+
+
 def _device_tracks(tracks, device):
     """The tracks on the device -> (list of (T_i, J, 2) tensors, J, frames given per track)."""
     tr = [_device_track(t, device) for t in tracks]
@@ -1318,7 +1597,8 @@ def resampled_pose_table(tracks, device, fps, resolutions=None, valid=None, mode
 
 def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, flip=None, keyframes_only=False, reuse_frames=True,
                    batch_size=None, root_relative=True, depth=None, lengths=None, graph=True, valid=None, return_valid=False, fps=None, out_fps=None,
-                   model_fps=50, repair_joints=None, keypoints=None, camera=None, min_root_joints=DEFAULT_MIN_ROOT_JOINTS, smooth=None):
+                   model_fps=50, repair_joints=None, keypoints=None, camera=None, min_root_joints=DEFAULT_MIN_ROOT_JOINTS, smooth=None,
+                   bones=None):
     """One 3D pose per frame for each 2D keypoint track -> list of (T_i, J, 3) float32 tensors on the model's device (views of one buffer).
 
     ``tracks``: list of (T_i, J, 2) arrays or tensors, on the host or the device, at the frame rate the config was trained for (nothing is
@@ -1419,9 +1699,24 @@ def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, fl
     exactly as without ``smooth``; a root row of state 0 (zeros) is passed through and takes no sample; ``root_state`` and the flags are
     unchanged, and the root joint of a root-relative pose stays exactly 0.  The filter is CAUSAL: frame i depends on the frames up to i
     only, so the offline result lags behind the motion exactly as the live one (``StreamSession(smooth=...)``) does.  A zero-lag,
-    two-pass offline smoother is out of scope, and so is any accuracy or jitter figure."""
+    two-pass offline smoother is out of scope, and so is any accuracy or jitter figure.
+
+    Constant bone lengths -- ``bones``: None = today's call, the same bits, no further launch or buffer.  The network predicts every
+    frame's skeleton on its own, so a person's bone lengths breathe from frame to frame, and under ``camera`` the depth with them.
+    "track": every track's bones get the track's own mean lengths (uu3d_bone_lengths over the returned frames); a (J,) array of lengths in
+    the poses' units, indexed by CHILD joint (the root's entry is ignored), or a list of such arrays, one per track: a subject whose
+    lengths are known -- calibrated once with ``bone_lengths`` on a recording --, which also takes the model's scale error out of the
+    depth; ``Bones(lengths, skeleton=...)``: the same for a tree of your own (``Skeleton``).  The default tree is ``SKELETONS["h36m17"]``
+    (another joint count: ValueError naming ``Skeleton``), and with ``root_relative`` its root must be ROOT_KEYTPOINT.  Directly behind
+    uu3d_assemble_tracks every pose is rebuilt from the root outwards, each bone scaled to its length and its direction kept
+    (uu3d_fix_bones; ``fix_bones`` is the launch alone; the rule in numpy: ``bone_lengths_host`` / ``fix_bones_host``, and the poses equal
+    ``fix_bones_host`` on the call without ``bones``, bit for bit).  Everything behind reads the fixed poses: the pose filter of
+    ``smooth`` and the root solve of ``camera`` -- with ``out_fps`` its re-assembled poses at the given frames' times are fixed with the
+    same lengths table.  A length that is not finite or <= 0 (a track without a usable frame) leaves that bone as it is; a NaN frame stays
+    NaN; the root joint of a root-relative pose stays exactly 0.  No accuracy figure is claimed."""
     import torch
     pose_filter, root_filter = check_smooth(smooth, camera is not None)
+    rigid = check_bones(bones, len(tracks), config.NUM_KEYPOINTS, int(config.ROOT_KEYTPOINT) if root_relative else None)
     if camera is not None:
         cameras, min_root_joints = check_cameras(camera, len(tracks)), check_min_root_joints(min_root_joints)
         if int(config.NUM_KEYPOINTS) > MAX_ROOT_JOINTS:
@@ -1476,6 +1771,9 @@ def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, fl
         left, right, weight, _ = evaluation.keyframe_plan(frame_idx, stride, rows=rows)
     out = assemble_tracks(raw[0], raw[1] if flip else None, left, right, weight, flip_order=cfg.AUGM_FLIP_KEYPOINT_ORDER,
                           root=int(cfg.ROOT_KEYTPOINT) if root_relative else -1)
+    if rigid is not None:                                             # constant bone lengths: everything behind reads the fixed poses
+        bone_table = bone_lengths(out, lens, rigid[0]) if rigid[1] is None else _upload(rigid[1], np.float64, out.device)
+        out = fix_bones(out, lens, bone_table, rigid[0])
     shown = out                                                       # what is returned: the poses, or the poses filtered
     if pose_filter is not None or root_filter is not None:
         out_rate = model_fps if fps is None else (rates if out_fps is None else frame_rates(out_fps, len(tracks)))
@@ -1495,6 +1793,8 @@ def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, fl
             _, at = output_positions(src_lens, rates, rates, model_fps)
             at_given = assemble_tracks(raw[0], raw[1] if flip else None, *evaluation.keyframe_plan_at(frame_idx, 1 if stride is None else stride, at, rows=rows),
                                        flip_order=cfg.AUGM_FLIP_KEYPOINT_ORDER, root=int(cfg.ROOT_KEYTPOINT) if root_relative else -1)
+            if rigid is not None:                                     # (the same lengths table as the returned poses)
+                at_given = fix_bones(at_given, given, bone_table, rigid[0])
             where = given_positions(lens, [f / o for f, o in zip(rates, frame_rates(out_fps, len(given)))])
         solved_roots, solved = solve_roots(at_given, table.source[0], cameras, table.source[1], min_root_joints, lens=given)
         roots, root_state = root_trajectory(solved_roots, solved, given, where)
@@ -1561,10 +1861,28 @@ def parse_args(argv=None):
                    help="pass the written poses through a One-Euro filter (Hz, 1 / unit speed, Hz) at the rate of the written frames; causal, it lags")
     p.add_argument("--smooth_root", type=float, nargs=3, metavar=("MIN_CUTOFF", "BETA", "D_CUTOFF"), default=None,
                    help="the same for the roots (needs --camera)")
+    p.add_argument("--bones", default=None, metavar="track|FILE.npy",
+                   help="constant bone lengths: 'track' gives every track its own mean lengths, FILE.npy holds a (J,) array of known lengths in "
+                        "the poses' units, indexed by child joint")
     args = p.parse_args(argv)
     if args.smooth_root is not None and args.camera is None:
         p.error("--smooth_root needs --camera: without it no roots are written")
     return args
+
+
+def bones_option(args, J):
+    """--bones of a command line -> the ``bones`` keyword ({} when it is not given): "track", or the (J,) array of an .npy file."""
+    if getattr(args, "bones", None) is None:
+        return {}
+    if args.bones == "track":
+        return {"bones": "track"}
+    try:
+        lengths = np.asarray(np.load(args.bones), np.float64)
+    except (OSError, ValueError) as e:
+        raise SystemExit(f"--bones: {args.bones} is neither 'track' nor a readable .npy file ({e})") from None
+    if lengths.shape != (int(J),):
+        raise SystemExit(f"--bones: {args.bones} holds an array of shape {lengths.shape}, expected ({int(J)},): one length per child joint")
+    return {"bones": lengths}
 
 
 def smooth_option(args):
@@ -1617,7 +1935,7 @@ def main(argv=None):
         if ms is None:
             raise SystemExit("--keyframes_only needs a mask stride")
         lengths = [(len(t) - 1) * int(ms) + 1 for t in tracks]
-    steady = smooth_option(args)
+    steady = {**smooth_option(args), **bones_option(args, config.NUM_KEYPOINTS)}
     model = _load_model(config, args.weights)
     if args.out_fps is not None and args.fps is None:
         raise SystemExit("--out_fps needs --fps")

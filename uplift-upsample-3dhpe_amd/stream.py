@@ -128,6 +128,22 @@ clear the filter with everything else.  ``LiveOneEuro`` owns the state block and
 several rows per push).  No accuracy or jitter figure is claimed.  ``smooth=None`` is the session above, bit for bit: no further launch
 or buffer.
 
+Live constant bone lengths -- ``StreamSession(..., bones=B)``: the network predicts every tick's skeleton on its own, so a person's bone
+lengths breathe from tick to tick, and under ``camera`` the depth with them.  ``bones`` -- "track", a (J,) array of lengths by child joint,
+one such array per slot, or a ``predict.Bones(lengths, skeleton)`` for another tree than ``predict.SKELETONS["h36m17"]`` -- puts ONE more
+launch into the session's launch table, directly behind the emit (with ``fps`` behind uu3d_stream_timed_emit) and in front of the root
+solve and the One-Euro launches: uu3d_stream_bones, one wave per slot, rebuilds the emitted pose from the root outwards with every bone at
+the slot's length, its direction kept (the rule: ``predict.fix_bones_host``; include/uu3d.h, CONSTANT BONE LENGTHS).  It writes a buffer
+of its own, which ``push`` returns and the root solve and the pose filter read; ``raw_poses`` stays the model's output and
+``bone_lengths`` is the slots' (slots, J) float64 table on the device.  With "track" a slot's length is the mean over the FRESH poses it
+has emitted so far: the mean is CAUSAL and therefore differs from ``predict_tracks(bones="track")``, which averages the whole track; early
+in a track it still moves, and a subject whose lengths are known should pass them.  The output is a pure function of the raw pose and the
+slot's lengths: a slot that is not fresh returns its previous rebuilt pose, bit for bit.  ``reset`` and a birth at a ``push_detections``
+tick clear the sums and counts with everything else; ``finish`` runs the same step in every drain tick, the chosen slots as ``active``.
+``LiveBonesHost`` is the rule in numpy, and the device equals it bit for bit.  ``captures`` stays 1 and ``push`` never waits.  Not
+together with ``out_fps`` (ValueError: several rows per push).  No accuracy figure is claimed.  ``bones=None`` is the session above, bit
+for bit: no further launch or buffer.
+
 The end of a track -- ``finish(slots)``: a session with lookahead a has not returned the poses of a track's last a frames when the track
 ends (the person leaves, the video stops).  ``finish`` returns them -- (slots, a, J, 3) and (slots, a) on the device -- and resets exactly
 those slots: it enqueues a DRAIN TICKS, each of which moves the centre of the slot's window one frame towards its newest frame and files
@@ -145,7 +161,7 @@ tick its own track ends; ``window_plan(drained=k)``, ``LiveRootHost.drain`` and 
     python -m uplift_upsample_3dhpe_amd.stream --config C --weights W.h5 --input tracks.npz --output out.npz [--lookahead A] [--resolution W H]
                                                  [--drain] [--mask_missing] [--fps F [--out_fps G]] [--repair_joints G [--min_score S]] [--keypoints NAME]
                                                  [--camera FX FY CX CY [--min_root_joints N]] [--smooth MIN_CUTOFF BETA D_CUTOFF]
-                                                 [--smooth_root MIN_CUTOFF BETA D_CUTOFF]
+                                                 [--smooth_root MIN_CUTOFF BETA D_CUTOFF] [--bones track|FILE.npy]
 """
 import argparse
 import ctypes as C
@@ -156,9 +172,10 @@ import numpy as np
 
 from . import _capi
 from ._capi import ptr as _ptr
-from .predict import (ASSOCIATION_DEFAULTS, DEFAULT_MIN_ROOT_JOINTS, KEYPOINT_PRESETS, MAX_ROOT_JOINTS, MAX_SMOOTH_CHANNELS, OneEuro, _load_model,
-                      check_association, check_cameras, check_keypoint_inputs, check_min_root_joints, check_repair_joints, check_resolutions,
-                      check_smooth, check_valid, input_joints, keypoint_map, one_euro_sample, smooth_option, solve_roots_host, split_scores)
+from .predict import (ASSOCIATION_DEFAULTS, Bones, DEFAULT_MIN_ROOT_JOINTS, KEYPOINT_PRESETS, MAX_ROOT_JOINTS, MAX_SMOOTH_CHANNELS, OneEuro, _bone_offsets,
+                      _load_model, bones_option, check_association, check_bones, check_cameras, check_keypoint_inputs, check_min_root_joints,
+                      check_repair_joints, check_resolutions, check_smooth, check_valid, fix_bones_host, input_joints, keypoint_map,
+                      one_euro_sample, skeleton_of, smooth_option, solve_roots_host, split_scores)
 from .rates import (RatePlan, _rate_argument, frame_rate, max_lookahead, newest_model_frame, out_push_plan, push_plan,  # noqa: F401 (re-exported)
                     rate_plan, session_strides)
 
@@ -231,7 +248,7 @@ def staged_frames(repair_joints, mask_stride):
     return int(repair_joints) // int(mask_stride) + 2
 
 
-LIVE_OPTIONS = ("repair_joints", "keypoints", "camera", "min_root_joints", "smooth")           # the keywords ``StreamSession`` and ``replay_tracks`` take from **options
+LIVE_OPTIONS = ("repair_joints", "keypoints", "camera", "min_root_joints", "smooth", "bones")  # the keywords ``StreamSession`` and ``replay_tracks`` take from **options
 DETECTION_OPTIONS = ("detections",) + tuple(ASSOCIATION_DEFAULTS)    # ... and the ones only ``StreamSession`` takes: per-frame detections
 
 
@@ -473,6 +490,58 @@ class LiveOneEuroHost(object):
         return self.step(values, virtual, fresh, chosen, state)
 
 
+class LiveBonesHost(object):
+    """The rule of uu3d_stream_bones in numpy, written to be read: the live form of ``predict.bone_lengths_host`` / ``fix_bones_host``.
+    State per slot and joint -- ``total`` (float64), the sum of the bone's lengths, and ``count``, how many were added.
+    ``step(poses (slots, J, 3) float32, fresh (slots,), active (slots,) or None)`` -> the rebuilt poses (slots, J, 3) float32.
+      ``lengths=None`` ("track"): an active slot whose pose is fresh first adds the finite, positive length of each of its bones to the
+          sum and counts it; the slot's L is sum / count -- NaN ("not corrected") before the first one, 0 for the tree root.  The mean is
+          CAUSAL: it equals ``predict.bone_lengths_host`` on the fresh poses seen so far, not the mean of the whole track.
+      ``lengths`` (J,) or (slots, J): L is what was given, and there is no state.
+      Then EVERY slot, fresh or not, returns ``predict.fix_bones_host`` of its row with its L: a pure function of the raw pose and the
+      slot's lengths, so a slot that holds its previous raw pose returns its previous fixed pose bit for bit.
+    ``drain(poses, fresh, chosen)``: one drain tick of ``StreamSession.finish`` -- ``step`` with the chosen slots as ``active``.
+    ``lengths``: the (slots, J) float64 table after the last step.  ``reset(slots=None)``: the chosen slots' sums and counts are zero."""
+
+    def __init__(self, slots, skeleton="h36m17", lengths=None):
+        self.slots, self.skeleton = int(slots), skeleton_of(skeleton)
+        J = self.skeleton.joints
+        self.given = None if lengths is None else check_bones(Bones(lengths, self.skeleton), self.slots, J, per="slot")[1]
+        self.total, self.count = np.zeros((self.slots, J), np.float64), np.zeros((self.slots, J), np.int64)
+        self.lengths = self._table()
+
+    def _table(self):
+        if self.given is not None:
+            return self.given.copy()
+        is_bone = np.array(self.skeleton.parents) >= 0
+        with np.errstate(all="ignore"):
+            return np.where(is_bone, np.where(self.count > 0, self.total / self.count.astype(np.float64), np.nan), 0.0)
+
+    def reset(self, slots=None):
+        which = slice(None) if slots is None else np.asarray(slots, np.int64).reshape(-1)
+        self.total[which] = 0
+        self.count[which] = 0
+        self.lengths = self._table()
+
+    def step(self, poses, fresh, active=None):
+        J = self.skeleton.joints
+        X = np.asarray(poses, np.float32).reshape(self.slots, J, 3)
+        fresh = np.asarray(fresh).reshape(self.slots) != 0
+        active = np.ones(self.slots, bool) if active is None else np.asarray(active).reshape(self.slots) != 0
+        if self.given is None:
+            is_bone = np.array(self.skeleton.parents) >= 0
+            with np.errstate(all="ignore"):
+                ln = _bone_offsets(X, self.skeleton)[2]
+                ok = (active & fresh)[:, None] & is_bone & np.isfinite(ln) & (ln > 0)
+                self.total = np.where(ok, self.total + ln, self.total)
+                self.count = self.count + ok
+        self.lengths = self._table()
+        return fix_bones_host(X, np.ones(self.slots, np.int64), self.lengths, self.skeleton)
+
+    def drain(self, poses, fresh, chosen=None):
+        return self.step(poses, fresh, chosen)
+
+
 class LiveOneEuro(object):
     """The live One-Euro filter on the device: the thin owner of the state block of uu3d_stream_one_euro and of its two launches
     (``LiveOneEuroHost`` is the same state machine in numpy; the device equals it bit for bit).  ``slots`` rows of ``channels`` float32
@@ -587,10 +656,16 @@ class StreamSession(object):
         ``smooth`` (keyword only, from ``options`` as well): None = the poses and roots as they are solved (the session above, bit for
         bit).  True, a ``predict.OneEuro`` or a pair (pose_filter, root_filter), either of which may be None (``predict.check_smooth``; a
         root filter without ``camera``: ValueError): the module docstring's "Steady output" -- ``push`` / ``push_detections`` return the
-        filtered buffers in place of poses and roots; ``raw_poses`` / ``raw_roots`` are the unfiltered ones.  With ``out_fps``: ValueError."""
-        repair_joints, keypoints, camera, min_root_joints, smooth, detections, *rule = _live_options(options, "StreamSession", LIVE_OPTIONS + DETECTION_OPTIONS)
+        filtered buffers in place of poses and roots; ``raw_poses`` / ``raw_roots`` are the unfiltered ones.  With ``out_fps``: ValueError.
+        ``bones`` (keyword only, from ``options`` as well): None = the poses as the network gives them (the session above, bit for bit).
+        "track", a (J,) array of lengths by child joint, a list of such arrays, one per slot, or a ``predict.Bones``: the module
+        docstring's "Live constant bone lengths" -- ``push`` returns the rebuilt poses, ``raw_poses`` stays the model's output and
+        ``bone_lengths`` is the slots' lengths table.  With ``out_fps``: ValueError."""
+        (repair_joints, keypoints, camera, min_root_joints, smooth, bones, detections,
+         *rule) = _live_options(options, "StreamSession", LIVE_OPTIONS + DETECTION_OPTIONS)
         res = self._init_plan(model, config, slots, resolutions, mask_stride, flip, lookahead, graph, missed_detections, fps, model_fps, out_fps,
-                              repair_joints, keypoints, detections, dict(zip(ASSOCIATION_DEFAULTS, rule)), camera, min_root_joints, smooth)
+                              repair_joints, keypoints, detections, dict(zip(ASSOCIATION_DEFAULTS, rule)), camera, min_root_joints, smooth,
+                              bones=bones, root_relative=root_relative)
         import torch
         self._torch = torch
         self._lib = _capi.load_library()
@@ -606,11 +681,16 @@ class StreamSession(object):
 
     # ---- construction: checks and plan, layout and state, buffers, launch tables (then the capture) ---------------------------------
     def _init_plan(self, model, config, slots, resolutions, mask_stride, flip, lookahead, graph, missed_detections, fps, model_fps, out_fps,
-                   repair_joints=None, keypoints=None, detections=None, rule=None, camera=None, min_root_joints=None, smooth=None):
+                   repair_joints=None, keypoints=None, detections=None, rule=None, camera=None, min_root_joints=None, smooth=None, bones=None,
+                   root_relative=True):
         """Every refusal that needs no device, and the session's plan.  -> the checked resolutions."""
         slots, lookahead = int(slots), int(lookahead)
         if slots < 1:
             raise ValueError("slots >= 1")
+        self.bones = check_bones(bones, slots, config.NUM_KEYPOINTS, int(config.ROOT_KEYTPOINT) if root_relative else None, per="slot")
+        if self.bones is not None and out_fps is not None:
+            raise ValueError("bones together with out_fps is not supported: a push then returns several rows per slot, and the live fix "
+                             "rebuilds one pose per slot and push (multi-row emits are out of scope)")
         self.pose_filter, self.root_filter = check_smooth(smooth, camera is not None)
         if (self.pose_filter is not None or self.root_filter is not None) and out_fps is not None:
             raise ValueError("smooth together with out_fps is not supported: a push then returns several rows per slot, and the live filter "
@@ -789,6 +869,20 @@ class StreamSession(object):
             self._roots = zeros((T, 3), dtype=torch.float32)
             self._root_flag = zeros((T,), dtype=torch.uint8)
             self._result = self._result + (self._roots, self._root_flag)
+        # constant bone lengths: the tree tables, the state block (sums and counts), the given lengths, and the buffer of rebuilt poses that
+        # push returns in the raw one's place -- the root solve and the pose filter read it
+        self._pose_shown = self._out
+        if self.bones is not None:
+            sk, given = self.bones
+            self._bone_tables = sk.device_tables(dev)
+            size = int(lib.uu3d_stream_bones_bytes(T, J))
+            if size == 0:
+                raise ValueError(f"bones: slots = {T}, joints = {J} are out of uu3d_stream_bones' range")
+            self._bone_state = zeros(size, dtype=torch.uint8)
+            self._bone_given = None if given is None else torch.from_numpy(given).pin_memory().to(dev, non_blocking=True)
+            self._bone_lengths = zeros((T, J), dtype=torch.float64)
+            self._pose_shown = zeros((T, J, 3), dtype=torch.float32)
+            self._result = (self._pose_shown,) + self._result[1:]
         # steady output: a live One-Euro filter per filtered buffer -- its state block and the buffer push returns in the raw one's place
         self._pose_smoother = self._root_smoother = None
         if self.pose_filter is not None:
@@ -854,10 +948,12 @@ class StreamSession(object):
         if self.cameras is not None:                                 # live absolute root: the frame counters are those the pose's frame is counted in
             T, J = self.slots, int(self._kp.shape[1])
             root = (lib.uu3d_stream_root, (T, J, self.lookahead, _ptr(self._root_state), _ptr(self._source_frames), active, _ptr(self._fresh),
-                                           _ptr(self._out), kp, _ptr(self._valid_in), int(self._valid_in is not None and self._valid_in.dim() == 2),
+                                           _ptr(self._pose_shown), kp, _ptr(self._valid_in), int(self._valid_in is not None and self._valid_in.dim() == 2),
                                            _ptr(self._cams), self.min_root_joints, _ptr(self._roots), _ptr(self._root_flag)))
             self._reset_more = self._reset_more + [(lib.uu3d_stream_root_reset, (T, J, self.lookahead, _ptr(self._root_state)))]
         self._reset_more = self._reset_more + [f.reset_launch() for f in (self._pose_smoother, self._root_smoother) if f is not None]
+        if self.bones is not None:
+            self._reset_more = self._reset_more + [(lib.uu3d_stream_bones_reset, (self.slots, int(self._kp.shape[1]), _ptr(self._bone_state)))]
         # per-frame detections: the association in front of everything -- it writes the frame, the flags, `active` and the born mask --, then
         # the resets of the slots born at this tick, with the mask on the device
         if self.detections is not None:
@@ -878,14 +974,24 @@ class StreamSession(object):
             self._push_after = [(lib.uu3d_stream_timed_emit_multi, (h, cfg, rate, outp, state, _ptr(self._poses), _ptr(self._count)))]
             self._reset_call = (lib.uu3d_stream_out_reset, (h, cfg, rate, outp, state))
         last = self._tick_steps if self.rate is None else self._push_after
+        # constant bone lengths: directly behind the emit, in front of the root solve and the filters, which read its buffer
+        if self.bones is not None:
+            last.append(self._bones_launch(active))
         if root is not None:                                         # behind the emit that wrote the pose it solves
             last.append(root)
         # steady output: the last steps of all -- they read what the emit and the root solve wrote and write buffers of their own, so the
         # root is solved against the unfiltered pose; their resets join the session's (also for a slot born on the device)
         if self._pose_smoother is not None:
-            last.append(self._pose_smoother.launch(self._out, self._source_frames, self._fresh, self._active))
+            last.append(self._pose_smoother.launch(self._pose_shown, self._source_frames, self._fresh, self._active))
         if self._root_smoother is not None:
             last.append(self._root_smoother.launch(self._roots, self._source_frames, self._fresh, self._active, self._root_flag))
+
+    def _bones_launch(self, active):
+        """uu3d_stream_bones as a launch-table entry: the emitted poses -> the rebuilt ones; ``active``: the slots that may take a sample."""
+        parents, paths = self._bone_tables
+        return (self._lib.uu3d_stream_bones, (self.slots, int(self._kp.shape[1]), _ptr(self._bone_state), _ptr(parents), _ptr(paths),
+                                              self.bones[0].depth, active, _ptr(self._fresh), _ptr(self._out), _ptr(self._bone_given),
+                                              _ptr(self._pose_shown), _ptr(self._bone_lengths)))
 
     # ---- the steps of a tick, on ``stream`` ------------------------------------------------------------------------------------------
     def _run(self, steps, stream):
@@ -1135,6 +1241,8 @@ class StreamSession(object):
         parts = [("poses", self._out, (J, 3), torch.float32), ("fresh", None, (), torch.uint8)]
         if camera:
             parts += [("roots", self._roots, (3,), torch.float32), ("root_state", None, (), torch.uint8)]
+        if self.bones is not None:
+            parts.append(("fixed_poses", self._pose_shown, (J, 3), torch.float32))
         if fp is not None:
             parts.append(("filtered_poses", fp.out, (J, 3), torch.float32))
         if fr is not None:
@@ -1147,7 +1255,7 @@ class StreamSession(object):
             rows[name] = (self._drain_rows[off:off + n].view(dt).view((T, a) + shape) if a > 0 else
                           torch.zeros((T, 0) + shape, dtype=dt, device=dev))
         self._drain_named = rows
-        result = (rows.get("filtered_poses", rows["poses"]), rows["fresh"].view(torch.bool))
+        result = (rows.get("filtered_poses", rows.get("fixed_poses", rows["poses"])), rows["fresh"].view(torch.bool))
         if camera:
             result += (rows.get("filtered_roots", rows["roots"]), rows["root_state"])
         self._drain_result = result
@@ -1162,20 +1270,26 @@ class StreamSession(object):
         h, cfg, dstate, chosen, fresh = m._h, C.byref(self._cfg), _ptr(self._drain_state), _ptr(self._drain_mask), _ptr(self._fresh)
         steps = [(lib.uu3d_stream_drain_commit, (h, cfg, _ptr(self._state), dstate, chosen, _ptr(self._valid_state), _ptr(self._rows),
                                                  _ptr(self._mask), _ptr(self._emit_fresh)))] + self._drain_shared
+        if self.bones is not None:                                  # the same step as in a tick, the chosen slots as `active`
+            steps.append(self._bones_launch(chosen))
         if camera:
-            steps.append((lib.uu3d_stream_root_drain, (T, J, a, _ptr(self._root_state), dstate, chosen, fresh, _ptr(self._out), _ptr(self._cams),
+            steps.append((lib.uu3d_stream_root_drain, (T, J, a, _ptr(self._root_state), dstate, chosen, fresh, _ptr(self._pose_shown), _ptr(self._cams),
                                                        self.min_root_joints, _ptr(self._roots), _ptr(self._root_flag))))
         if fp is not None:                                           # the filters as they are: the virtual counter, the chosen slots as `active`
-            steps.append(fp.launch(self._out, self._virtual_frames, self._fresh, self._drain_mask))
+            steps.append(fp.launch(self._pose_shown, self._virtual_frames, self._fresh, self._drain_mask))
         if fr is not None:
             steps.append(fr.launch(self._roots, self._virtual_frames, self._fresh, self._drain_mask, self._root_flag))
         floats = [(src, rows[name], int(np.prod(shape))) for name, src, shape, _ in parts if src is not None]
-        n = len(floats)
-        self._drain_file_args = ((C.c_void_p * n)(*[t.data_ptr() for t, _, _ in floats]), (C.c_int32 * n)(*[w for _, _, w in floats]),
-                                 (C.c_void_p * n)(*[t.data_ptr() for _, t, _ in floats]))
-        src, widths, dst = self._drain_file_args
-        steps.append((lib.uu3d_stream_drain_file, (T, a, dstate, n, src, widths, dst, fresh, _ptr(rows["fresh"]),
-                                                   _ptr(self._root_flag) if camera else None, _ptr(rows["root_state"]) if camera else None)))
+        self._drain_file_args = []                                    # (uu3d_stream_drain_file takes four float buffers: a fifth goes in a launch of its own)
+        for first in range(0, len(floats), 4):
+            group = floats[first:first + 4]
+            n = len(group)
+            src, widths, dst = ((C.c_void_p * n)(*[t.data_ptr() for t, _, _ in group]), (C.c_int32 * n)(*[w for _, _, w in group]),
+                                (C.c_void_p * n)(*[t.data_ptr() for _, t, _ in group]))
+            self._drain_file_args.append((src, widths, dst))
+            bytes_too = camera and first == 0
+            steps.append((lib.uu3d_stream_drain_file, (T, a, dstate, n, src, widths, dst, fresh, _ptr(rows["fresh"]),
+                                                       _ptr(self._root_flag) if bytes_too else None, _ptr(rows["root_state"]) if bytes_too else None)))
         self._drain_steps = steps
         # (every slot's `drained` is 0 outside ``finish`` -- it resets the slots it drained --, so the captured tick of a session with
         # detections, which resets the slots born on the device, needs no launch for the drain state; ``reset`` zeroes it all the same)
@@ -1219,7 +1333,10 @@ class StreamSession(object):
         a - k, pushed the same frames, returns at its last push.
         A session with ``camera``: roots (slots, a, 3) float32 and root_state (slots, a) uint8 are appended, by ``push``'s rule at frame c
         (``LiveRootHost.drain``).  A session with ``smooth``: the filtered rows stand in place of poses and roots (one sample per fresh
-        row, at frame c: ``LiveOneEuroHost.drain``); ``drain_raw_poses`` / ``drain_raw_roots`` are the unfiltered rows.
+        row, at frame c: ``LiveOneEuroHost.drain``); ``drain_raw_poses`` / ``drain_raw_roots`` are the unfiltered rows.  A session with
+        ``bones``: every drain tick rebuilds its pose between the emit and the root solve as a push does, the chosen slots as ``active``
+        (``LiveBonesHost.drain``: a fresh drained pose joins the running mean of a "track" session); the rows are the rebuilt poses, roots
+        and filters read them, and ``drain_raw_poses`` stays the model's output.
         Slots that were not chosen are untouched -- counters, rings, held pose, held root and filter state keep their bits -- and the next
         ``push`` continues their tracks; but the buffers the previous ``push`` returned are no longer meaningful after ``finish`` (the
         drain ticks write them).  A session with ``detections``: the tracks end as ``reset`` ends them (ids freed; None also zeroes the
@@ -1288,8 +1405,9 @@ class StreamSession(object):
 
     @property
     def raw_poses(self):
-        """(slots, J, 3) float32 on the device: the poses as the tick emits them, unfiltered -- in a session without ``smooth`` the buffer
-        ``push`` returns.  Not with ``out_fps`` (AttributeError)."""
+        """(slots, J, 3) float32 on the device: the poses as the tick emits them, the model's output, unfiltered and with the bones as
+        the network gave them -- in a session without ``smooth`` and ``bones`` the buffer ``push`` returns.  Not with ``out_fps``
+        (AttributeError)."""
         if self.max_out is not None:
             raise AttributeError("raw_poses: a session with out_fps returns several rows per slot")
         return self._out
@@ -1300,6 +1418,27 @@ class StreamSession(object):
         if self.cameras is None:
             raise AttributeError("raw_roots needs a session with camera")
         return self._roots
+
+    @property
+    def fixed_poses(self):
+        """(slots, J, 3) float32 on the device (sessions with ``bones``): the rebuilt poses, unfiltered -- in a session without ``smooth``
+        the buffer ``push`` returns."""
+        if self.bones is None:
+            raise AttributeError("fixed_poses needs a session with bones")
+        return self._pose_shown
+
+    @property
+    def drain_fixed_poses(self):
+        """(slots, lookahead, J, 3) float32 on the device (sessions with ``bones``): the rebuilt poses of the last ``finish``, unfiltered."""
+        return self._drain_rows_of("fixed_poses", "with bones")
+
+    @property
+    def bone_lengths(self):
+        """(slots, J) float64 on the device (sessions with ``bones``): the lengths every slot's pose was rebuilt with at the last tick, by
+        child joint -- the running means of a "track" session (NaN before a slot's first fresh pose), else the given ones; 0 for the root."""
+        if self.bones is None:
+            raise AttributeError("bone_lengths needs a session with bones")
+        return self._bone_lengths
 
     @property
     def joint_state(self):
@@ -1372,6 +1511,7 @@ def replay_tracks(model, config, tracks, resolutions=None, mask_stride=None, fli
     (T_i, K_in, 2) and per-joint entries of ``valid`` (T_i, K_in).  ``camera=C, min_root_joints=N`` (from ``options`` as well): a session with
     ``camera`` -- the roots (T_i, 3) float32 and root states (T_i,) uint8 the session returned at each tick are appended per track:
     -> (poses, fresh, roots, root_state).  ``smooth=F`` (from ``options`` as well): a session with ``smooth``; the same return, filtered.
+    ``bones=B`` (from ``options`` as well): a session with ``bones``, one slot per track; the same return, the poses rebuilt.
     ``drain=True``: every slot is finished (``StreamSession.finish``) at the tick its own track ends, while the other slots go on; per
     track the arrays then have T_i + lookahead rows -- row t is the pose of frame t - lookahead (where it is fresh), so all T_i frames of
     the track come out, as from ``predict_tracks``.  Still one copy to the host, at the end.  Not with ``fps`` / ``out_fps`` (ValueError)."""
@@ -1379,10 +1519,12 @@ def replay_tracks(model, config, tracks, resolutions=None, mask_stride=None, fli
         raise ValueError("drain=True together with fps / out_fps is not supported yet (a later change): the drain of a source-rate session "
                          "needs the end of the model-rate track")
     import torch
-    repair_joints, keypoints, camera, min_root_joints, smooth = _live_options(options, "replay_tracks")
+    repair_joints, keypoints, camera, min_root_joints, smooth, bones = _live_options(options, "replay_tracks")
     place = {} if camera is None and min_root_joints is None else {"camera": camera, "min_root_joints": min_root_joints}
     if smooth is not None:
         place["smooth"] = smooth
+    if bones is not None:
+        place["bones"] = bones
     lens = [int(len(t)) for t in tracks]
     T, ticks = len(tracks), max(lens)
     K = J = int(np.asarray(tracks[0]).shape[1])                      # joints pushed, joints returned
@@ -1467,7 +1609,7 @@ def replay_detections(model, config, detections, counts=None, valid=None, slots=
     """Push ONE video's per-frame detections tick by tick through a ``StreamSession(detections=D)`` and collect the poses per track id.
     ``detections`` (T, D, K, 2); ``counts`` (T,) or None; ``valid``: None, (T, D) or (T, D, K); ``slots`` (None: D); ``resolutions``: None
     or one (w, h); ``options``: ``max_age`` / ``max_dist`` / ``min_common``, ``repair_joints``, ``keypoints``, ``camera`` (one tuple) /
-    ``min_root_joints``, ``smooth``.
+    ``min_root_joints``, ``smooth``, ``bones`` ("track" or lengths per SLOT: the device decides which person a slot is).
     -> a list of (track_id, first_frame, poses (n, J, 3) float32, fresh (n,) bool) by track id, host arrays: what the session returned for
     the track's slot at the ticks first_frame .. first_frame + n - 1, the ticks the track was alive (its trailing missing frames
     included; ``predict.predict_detections`` ends a track at its last matched frame).  With ``camera`` every tuple carries two more
@@ -1561,11 +1703,16 @@ def parse_args(argv=None):
                    help="pass the poses of every tick through a live One-Euro filter (Hz, 1 / unit speed, Hz); not with --out_fps")
     p.add_argument("--smooth_root", type=float, nargs=3, metavar=("MIN_CUTOFF", "BETA", "D_CUTOFF"), default=None,
                    help="the same for the roots (needs --camera)")
+    p.add_argument("--bones", default=None, metavar="track|FILE.npy",
+                   help="constant bone lengths: 'track' rebuilds every pose with the running mean lengths of its track so far, FILE.npy holds a "
+                        "(J,) array of known lengths in the poses' units, indexed by child joint; not with --out_fps")
     args = p.parse_args(argv)
     if args.smooth_root is not None and args.camera is None:
         p.error("--smooth_root needs --camera: without it no roots are written")
     if (args.smooth is not None or args.smooth_root is not None) and args.out_fps is not None:
         p.error("--smooth / --smooth_root with --out_fps is not supported")
+    if args.bones is not None and args.out_fps is not None:
+        p.error("--bones with --out_fps is not supported")
     if args.out_fps is not None and args.fps is None:
         p.error("--out_fps needs --fps")
     if args.drain and args.fps is not None:
@@ -1620,6 +1767,7 @@ def main(argv=None):
         if any(k.endswith(("__root", "__root_state")) for k in names):
             raise SystemExit(f"{args.input}: a key ending in __root or __root_state would collide with the arrays --camera writes")
     place.update(smooth_option(args))
+    place.update(bones_option(args, config.NUM_KEYPOINTS))
     model = _load_model(config, args.weights)
     poses, fresh, *rs = replay_tracks(model, config, tracks, resolutions=None if args.resolution is None else tuple(args.resolution),
                                       lookahead=args.lookahead, **({"drain": True} if args.drain else {}), **missing, **skeleton, **place,
