@@ -73,30 +73,8 @@ def _reference(cfg, arch, w, x, m, gt, dp=None, bn_train=None):
     return float(loss.detach()), grads, None if full is None else full.detach().numpy(), central.detach().numpy()
 
 
-def _bad_tensors(g, gref, floor=1e-4):
-    """Tensors off by more than 1e-4 of their scale (max |ref|, at least `floor` of the largest gradient element), worst first."""
-    gmax = max(np.abs(v).max() for v in gref.values())
-    bad = []
-    for k in gref:
-        scale = max(np.abs(gref[k]).max(), floor * gmax)
-        if k.endswith("/attn/wk/bias") and np.abs(gref[k]).max() < 1e-12 * gmax:      # structurally zero (softmax shift invariance)
-            scale = max(scale, np.abs(gref[k.replace("/bias", "/kernel")]).max())
-        d = np.abs(g[k] - gref[k]) / scale
-        if d.max() > 1e-4:
-            bad.append((k, float(d.max()), d))
-    bad.sort(key=lambda t: -t[1])
-    return bad
-
-
-def _is_flip(bad):
-    """The signature of ONE hidden unit whose ReLU input sits within rounding of zero and flips against float64
-    (tests/test_random_configs_gpu.py::test_random_config_gradients_match_autograd): an fc1 bias with one element off, its kernel's
-    error in that one column, every other tensor off by far less."""
-    k0, e0, d0 = bad[0] if bad[0][0].endswith("/mlp/fc1/bias") else (bad[1] if len(bad) > 1 else bad[0])
-    kern = [t for t in bad if t[0] == k0.replace("/bias", "/kernel")]
-    return (k0.endswith("/mlp/fc1/bias") and int((d0 > 1e-4).sum()) == 1 and len(kern) == 1
-            and set(np.argwhere(kern[0][2] > 1e-4)[:, -1].tolist()) == set(np.argwhere(d0 > 1e-4)[:, -1].tolist())
-            and all(e <= 0.5 * max(e0, kern[0][1]) for k, e, _ in bad if k not in (k0, kern[0][0])))
+# the error measure and the flipped-hidden-unit recogniser are shared with tests/test_train_step_rows_gpu.py (tests/util.py)
+_bad_tensors, _is_flip = util.bad_tensors, util.is_flip
 
 
 def _check_against_oracle(cfg, B, seed, droppath=False):

@@ -122,22 +122,16 @@ def test_gradients_match_autograd(cfgname, droppath, batch_norm):
     worst = ("", 0.0)
     if rows.all():
         assert loss.cpu().numpy()[0] == pytest.approx(ref["loss"], rel=2e-5)
-    gmax = max(np.abs(v).max() for v in gref.values())
+    # the measure (tests/util.py gradient_errors, shared with tests/test_train_step_rows_gpu.py): max |g - g_ref| / max(max |g_ref|,
+    # floor * gmax) per tensor, the key kernel's scale for a structurally zero key bias.
+    # OUTPUT_BN: the gradient entering a BatchNorm input sums to zero over the batch (and d x . xhat too), and the residual stream
+    # carries that component unchanged through every block below the heads -- each bias / positional-encoding gradient there is a
+    # column sum in which it cancels (the last strided block's conv bias: to exactly zero).  Their rounding error is that of the
+    # summands (elements ~gmax), not of the much smaller sums, so the floor of the scale is 1e-3 gmax for that case (1e-4 elsewhere).
+    gmax, per_tensor = util.gradient_errors(g, gref, floor=1e-3 if droppath == "bn" else 1e-4)
     errs = []
-    for name in gref:
-        # scale floor: the key-bias gradients are identically zero (softmax shift invariance), so a purely
-        # relative measure would compare rounding noise with rounding noise
-        # OUTPUT_BN: the gradient entering a BatchNorm input sums to zero over the batch (and d x . xhat too), and the residual stream
-        # carries that component unchanged through every block below the heads -- each bias / positional-encoding gradient there is a
-        # column sum in which it cancels (the last strided block's conv bias: to exactly zero).  Their rounding error is that of the
-        # summands (elements ~gmax), not of the much smaller sums, so the floor of the scale is 1e-3 gmax for that case (1e-4 elsewhere).
-        scale = max(np.abs(gref[name]).max(), (1e-3 if droppath == "bn" else 1e-4) * gmax)
-        if name.endswith("/attn/wk/bias") and np.abs(gref[name]).max() < 1e-12 * gmax:
-            # structurally zero: what the HIP path holds there is the rounding residue of column sums of d K, so its natural
-            # scale is the key kernel's gradient (the same d K) -- every other tensor keeps the bound above
-            scale = max(scale, np.abs(gref[name.replace("/bias", "/kernel")]).max())
-        err = np.abs(g[name] - gref[name]).max() / scale
-        errs.append((err, name, np.abs(gref[name]).max()))
+    for err, name, refmax, _ in per_tensor:
+        errs.append((err, name, refmax))
         if err > worst[1]:
             worst = (name, err)
     top = sorted(errs, reverse=True)[:12]
