@@ -83,6 +83,51 @@ int uu3d_op_ln_dense_panel(const float* x_dev, int32_t ldx, int32_t M, const flo
                            const void* operand_dev, const float* bias_dev, int32_t N, int32_t relu, void* a_scratch_dev,
                            void* out_dev, int32_t ldo, void* stream);
 
+/* ---- forward operators: every kernel the launch schedule of csrc/uu3d_forward.inc selects for a LayerNorm-fed Dense layer, each on its
+ * own, launched through the forward's own launch helpers (csrc/uu3d_launch.h) -- tests/test_fwd_ops_gpu.py holds them to float64. ---- */
+#define UU3D_EP_BIAS 0              /* out[M][N] f32 (row stride ldo) = v + bias */
+#define UU3D_EP_BIAS_RELU_SPLIT 1   /* ReLU(v + bias) as f16 planes hi[M][N] | lo[M][N] at out_dev (value = hi + lo / 2048) */
+#define UU3D_EP_BIAS_SPLIT_Q 2      /* v + bias, the first N / 3 columns (q of [q | k | v]) times qscale, as the same two planes; N % 3 == 0 */
+#define UU3D_EP_BIAS_RESIDUAL 3     /* residual_dev[M][384] += v + bias in place (row stride 384); N == 384; out_dev is not used */
+#define UU3D_EP_BIAS_RESIDUAL_LN 4  /* the same, then LayerNorm(ln2_gamma, ln2_beta, eps) of the finished rows written to ln_out_dev as A
+                                     * fragments (uu3d_op_panel_a_bytes(M); rows past M of the last panel are not written): 8 waves, splits 1 */
+/* uu3d_op_ln_dense_panel with the schedule spelled out.  waves: 4 (gemm_h3_panel_kernel) or 8 (gemm_h3_panel8_kernel: the contraction
+ * split over wave pairs).  splits = S >= 1: column ranges per row tile, each workgroup takes (N / 32) / S chunks of 32 columns; splits 0
+ * (4 waves only): the choice of uu3d_op_ln_dense_panel, which is this call with (4, 0) and the epilogue 0 or 1.
+ * UU3D_ERR_INVALID_ARGUMENT before any launch, output untouched, for what no kernel is instantiated for: waves not 4 or 8; S not
+ * dividing N / 32; more than 32 chunks per workgroup; 8 waves with (N / 32) / S not one of 4, 6, 8, 9, 12 (or splits 0); the residual
+ * epilogues with N != 384; UU3D_EP_BIAS_RESIDUAL_LN with anything but (8 waves, S = 1).  Both kernels take any M >= 1: rows past M are read
+ * clamped to row M - 1 and never stored, the 8-wave kernel included (its ragged last tile runs the predicated form).
+ * With 4 waves the residual epilogue runs the forms with the chunk loop unrolled for S = 1, 2, 3 (what the forward launches) and the
+ * runtime chunk loop for S = 4, 6, 12. */
+int uu3d_op_ln_dense_panel_ex(const float* x_dev, int32_t ldx, int32_t M, const float* gamma_dev, const float* beta_dev, float eps,
+                              const void* operand_dev, const float* bias_dev, int32_t N, int32_t waves, int32_t splits, int32_t epilogue,
+                              float qscale, void* a_scratch_dev, void* out_dev, int32_t ldo, float* residual_dev,
+                              const float* ln2_gamma_dev, const float* ln2_beta_dev, void* ln_out_dev, void* stream);
+/* HOST: the inverse of the A-fragment order (panel_a_index, the order ln_split_frag and the Ln epilogue write): rows 0 .. M - 1 of a
+ * fragment buffer copied back from the device, as the values of the two planes, hi_host[M][384] and lo_host[M][384] (value = hi + lo / 2048). */
+int uu3d_op_panel_a_unpack(const void* frag_host, int32_t M, float* hi_host, float* lo_host);
+
+/* vit.MLP of a temporal block in one launch (csrc/uu3d_mlp_fused.h; vision_transformer.py:46-68): the three partial sums
+ *   mslab[s][M][384],  sum_s mslab[s] = relu(LayerNorm(x[M][384]) W1 + b1) W2        (W1 384 x 768, W2 768 x 384, Keras (in, out); no b2)
+ * which the forward's next LayerNorm launch adds to the residual stream.  uu3d_op_mlp_pack (HOST arrays in, device operand out) packs W1
+ * as the row-panel operand and W2 in the k order of fc1's accumulator registers, as uu3d_commit_weights does.  M >= 1. */
+size_t uu3d_op_mlp_operand_bytes(void);
+int uu3d_op_mlp_pack(const float* w1_host, const float* w2_host, void* operand_dev, void* stream);
+int uu3d_op_mlp_fused(const float* x_dev, int32_t ldx, int32_t M, const float* gamma_dev, const float* beta_dev, float eps,
+                      const void* operand_dev, const float* b1_dev, void* a_scratch_dev, float* mslab_dev, void* stream);
+
+/* The forward's few-row path (csrc/uu3d_gemm_wt.h: gemm_h3_wt_kernel, LayerNorm in the loader, split-K over the workgroup's waves):
+ *   out = epilogue(LayerNorm(x[M][K]) W[K][N] + bias),  epilogue UU3D_EP_BIAS, UU3D_EP_BIAS_RELU_SPLIT or UU3D_EP_BIAS_SPLIT_Q (as above).
+ * 1 <= M <= 512 (the forward's few-row limit), K 384 or 768, N % 32 == 0, ldx >= K and a multiple of 4.  The operand is the pair of f16
+ * planes hi[N][K] | lo[N][K] (lo scaled by 2048) the model keeps for every Dense kernel, made by uu3d_op_wt_pack from the Keras (in, out)
+ * kernel on the HOST. */
+size_t uu3d_op_wt_operand_bytes(int32_t N, int32_t K);
+int uu3d_op_wt_pack(const float* w_host, int32_t K, int32_t N, void* operand_dev, void* stream);
+int uu3d_op_ln_dense_wt(const float* x_dev, int32_t ldx, int32_t M, int32_t K, const float* gamma_dev, const float* beta_dev, float eps,
+                        const void* operand_dev, const float* bias_dev, int32_t N, int32_t epilogue, float qscale, void* out_dev,
+                        int32_t ldo, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

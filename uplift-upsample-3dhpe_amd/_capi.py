@@ -55,7 +55,11 @@ OPS_SYMBOLS = (
     "uu3d_op_gemm_tn", "uu3d_op_gemm_tn_h3", "uu3d_op_gemm_nt", "uu3d_op_colsum", "uu3d_op_row_stats", "uu3d_op_ln_bwd",
     "uu3d_op_attn_fwd", "uu3d_op_attn_bwd", "uu3d_op_attn_long_fwd", "uu3d_op_attn_long_bwd", "uu3d_op_scratch_floats",
     "uu3d_op_panel_operand_bytes", "uu3d_op_panel_a_bytes", "uu3d_op_panel_pack", "uu3d_op_ln_dense_panel",
+    "uu3d_op_ln_dense_panel_ex", "uu3d_op_panel_a_unpack", "uu3d_op_mlp_operand_bytes", "uu3d_op_mlp_pack", "uu3d_op_mlp_fused",
+    "uu3d_op_wt_operand_bytes", "uu3d_op_wt_pack", "uu3d_op_ln_dense_wt",
 )
+# epilogues of uu3d_op_ln_dense_panel_ex / uu3d_op_ln_dense_wt (include/uu3d_ops.h)
+UU3D_EP_BIAS, UU3D_EP_BIAS_RELU_SPLIT, UU3D_EP_BIAS_SPLIT_Q, UU3D_EP_BIAS_RESIDUAL, UU3D_EP_BIAS_RESIDUAL_LN = range(5)
 
 
 class Uu3dLibraryError(RuntimeError):
@@ -415,6 +419,22 @@ def load_library(path=None):
     lib.uu3d_op_panel_pack.argtypes = [vp, i32, vp, vp]
     lib.uu3d_op_ln_dense_panel.restype = C.c_int
     lib.uu3d_op_ln_dense_panel.argtypes = [vp, i32, i32, vp, vp, C.c_float, vp, vp, i32, i32, vp, vp, i32, vp]
+    lib.uu3d_op_ln_dense_panel_ex.restype = C.c_int
+    lib.uu3d_op_ln_dense_panel_ex.argtypes = [vp, i32, i32, vp, vp, C.c_float, vp, vp, i32, i32, i32, i32, C.c_float, vp, vp, i32, vp, vp, vp, vp, vp]
+    lib.uu3d_op_panel_a_unpack.restype = C.c_int
+    lib.uu3d_op_panel_a_unpack.argtypes = [vp, i32, vp, vp]
+    lib.uu3d_op_mlp_operand_bytes.restype = sz
+    lib.uu3d_op_mlp_operand_bytes.argtypes = []
+    lib.uu3d_op_mlp_pack.restype = C.c_int
+    lib.uu3d_op_mlp_pack.argtypes = [vp, vp, vp, vp]
+    lib.uu3d_op_mlp_fused.restype = C.c_int
+    lib.uu3d_op_mlp_fused.argtypes = [vp, i32, i32, vp, vp, C.c_float, vp, vp, vp, vp, vp]
+    lib.uu3d_op_wt_operand_bytes.restype = sz
+    lib.uu3d_op_wt_operand_bytes.argtypes = [i32, i32]
+    lib.uu3d_op_wt_pack.restype = C.c_int
+    lib.uu3d_op_wt_pack.argtypes = [vp, i32, i32, vp, vp]
+    lib.uu3d_op_ln_dense_wt.restype = C.c_int
+    lib.uu3d_op_ln_dense_wt.argtypes = [vp, i32, i32, i32, vp, vp, C.c_float, vp, vp, i32, i32, C.c_float, vp, i32, vp]
     if path is None:
         _lib = lib
     return lib

@@ -185,9 +185,7 @@ struct Launcher {
     // The 8-wave form of the row-panel GEMM (uu3d_gemm_panel8.h: contraction split over wave pairs, two waves per SIMD) for the chunk
     // counts it is instantiated for; UU3D_PANEL4=1 keeps every launch on the 4-wave kernel (A/B measurements).  Returns false when
     // the caller has to launch the 4-wave kernel.
-    static bool panel8_ok(int cpw) {
-        return !process_switches().panel4 && (cpw == 4 || cpw == 6 || cpw == 8 || cpw == 9 || cpw == 12);      // (9: QKV at 284 row tiles = batch 512, four column ranges)
-    }
+    static bool panel8_ok(int cpw) { return !process_switches().panel4 && panel8_has(cpw); }
     // the profile records' kernel name = the kernel SYMBOL's distinguishing part (bench.py picks the dominant kernel by it)
     template <class EP> static const char* panel_symbol(bool eight) {
         const char* e = std::is_same<EP, PanelEpBiasSplitQ>::value ? "BiasSplitQ" : std::is_same<EP, PanelEpBiasResidual>::value ? "BiasResidual"
@@ -197,27 +195,14 @@ struct Launcher {
         std::snprintf(buf, sizeof buf, "%s<%s>", eight ? "gemm_panel8" : "gemm_panel", e);
         return buf;
     }
+    // the launches themselves: uu3d_launch.h (shared with the operator ABI)
     template <class EP>
     bool launch_panel8(const _Float16* Af, const _Float16* Bf, const float* colv, int M, int mt, int S, int cpw, const EP& ep) {
-        if (!panel8_ok(cpw)) return false;
-        const dim3 grid(8 * S, ((mt * S + 7) / 8 + S - 1) / S);
-#define UU3D_P8_LAUNCH(CPW) { allow_lds<gemm_h3_panel8_kernel<EP, CPW, 3>>(P8_LDS_TOTAL); \
-            hipLaunchKernelGGL((gemm_h3_panel8_kernel<EP, CPW, 3>), grid, dim3(512), P8_LDS_TOTAL, stream, Af, Bf, colv, M, mt, S, ep); return true; }
-        switch (cpw) {
-            case 4: UU3D_P8_LAUNCH(4)
-            case 6: UU3D_P8_LAUNCH(6)
-            case 8: UU3D_P8_LAUNCH(8)
-            case 9: UU3D_P8_LAUNCH(9)
-            case 12: UU3D_P8_LAUNCH(12)
-            default: return false;
-        }
-#undef UU3D_P8_LAUNCH
+        return panel8_ok(cpw) && uu3d::launch_panel8(stream, Af, Bf, colv, M, mt, S, cpw, ep);
     }
-    // the 4-wave kernel; CPW != 0: the chunk loop unrolled for that many chunks per workgroup
-    template <class EP, int CPW = 0>
+    template <class EP>
     void launch_panel4(const _Float16* Af, const _Float16* Bf, const float* colv, int M, int mt, int S, int cpw, const EP& ep) {
-        allow_lds<gemm_h3_panel_kernel<24, EP, CPW>>(PANEL_LDS_TOTAL);
-        hipLaunchKernelGGL((gemm_h3_panel_kernel<24, EP, CPW>), dim3(8 * S, ((mt * S + 7) / 8 + S - 1) / S), dim3(256), PANEL_LDS_TOTAL, stream, Af, Bf, colv, M, mt, S, cpw, ep);
+        uu3d::launch_panel4<EP>(stream, Af, Bf, colv, M, mt, S, cpw, ep);
     }
     // the operand given by address (training: the packs regenerated from the master buffer) -- K = 384, N % 32 == 0; S = 0: panel_splits
     template <class EP>
@@ -266,9 +251,7 @@ struct Launcher {
             if (launch_panel8(Af, m->harena + pf, colv, M, mt, 1, 12, epl)) { end(); return true; }
         }
         if (launch_panel8(Af, m->harena + pf, colv, M, mt, S, 12 / S, ep)) { end(); return false; }
-        if (S == 3) launch_panel4<PanelEpBiasResidual, 4>(Af, m->harena + pf, colv, M, mt, S, 4, ep);
-        else if (S == 2) launch_panel4<PanelEpBiasResidual, 6>(Af, m->harena + pf, colv, M, mt, S, 6, ep);
-        else launch_panel4<PanelEpBiasResidual, 12>(Af, m->harena + pf, colv, M, mt, S, 12, ep);
+        launch_panel4_residual(stream, Af, m->harena + pf, colv, M, mt, S, ep);
         end();
         return false;
     }
@@ -329,11 +312,8 @@ struct Launcher {
     }
     void mlp_fused(const char* name, const _Float16* Af, const BlockDev& b, int M, float* mslab) {
         if (skip_mask() & 8) return;
-        const int mt = (M + 127) / 128, S = MLPF_SLICES;
         begin(name, "mlp_fused", 4.0 * M * (double)m->cfg.d_temporal * m->cfg.h_temporal, 4.0 * ((double)M * 384 + 2.0 * 384 * 768 + 3.0 * M * 384));
-        allow_lds<mlp_fused_h3_kernel>(PANEL_LDS_TOTAL);
-        hipLaunchKernelGGL(mlp_fused_h3_kernel, dim3(8 * S, ((mt * S + 7) / 8 + S - 1) / S), dim3(256), PANEL_LDS_TOTAL, stream,
-                           Af, m->harena + b.w1_pf, m->harena + b.w2_mf, b.b1, mslab, M, mt);
+        launch_mlp_fused(stream, Af, m->harena + b.w1_pf, m->harena + b.w2_mf, b.b1, mslab, M);
         end();
     }
     // One launch of the temporal chain (uu3d_tchain16.h): the row-local stages of a block for every 64-row tile
@@ -375,15 +355,10 @@ struct Launcher {
     }
     template <class AL, class EP>
     void gemm_wt(const char* name, const AL& al, const float* Bt, int M, int N, int K, const EP& ep, double extra_bytes = 0) {
-        const int Kp = round_up(K, 32), slices = Kp / 16;
         const auto it = m->hplanes.find((size_t)(Bt - m->arena));
         const _Float16* Bh = m->harena + it->second.first; const _Float16* Bl = m->harena + it->second.second;
-        const int mt = (M + 31) / 32, nt = (N + 31) / 32;
         begin(name, "gemm_wt", 2.0 * M * (double)N * K, 4.0 * ((double)M * K + (double)N * K + (double)M * N) + extra_bytes);
-        if (slices <= 6 * WT_MAX_WAVES) {                    // K <= 768: one batch of loads per wave
-            const int kw = (slices + 5) / 6;
-            hipLaunchKernelGGL((gemm_h3_wt_kernel<AL, EP, 6>), dim3(mt * nt), dim3(64 * kw), gemm_wt_lds_bytes(kw), stream, al, Bh, Bl, M, N, Kp, nt, ep);
-        } else { status = UU3D_ERR_UNSUPPORTED; m->err = "gemm_wt: contraction longer than 768"; }
+        if (!launch_gemm_wt(stream, al, Bh, Bl, M, N, K, ep)) { status = UU3D_ERR_UNSUPPORTED; m->err = "gemm_wt: contraction longer than 768"; }
         end();
     }
 

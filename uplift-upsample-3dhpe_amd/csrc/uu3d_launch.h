@@ -1,4 +1,4 @@
-// uu3d_launch.h -- host-side launch helpers shared by the ops ABI and the training step.
+// uu3d_launch.h -- host-side launch helpers shared by the ops ABI, the forward and the training step.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -7,6 +7,10 @@
 #include "uu3d_gemm_h3.h"
 #include "uu3d_bwd.h"
 #include "uu3d_attn_long.h"
+#include "uu3d_gemm_panel.h"
+#include "uu3d_gemm_panel8.h"
+#include "uu3d_gemm_wt.h"
+#include "uu3d_mlp_fused.h"
 
 namespace uu3d {
 
@@ -278,6 +282,60 @@ inline int launch_attn_long(bool backward, const float* qkv, const float* O, con
         hipLaunchKernelGGL(attn_long_dkv_kernel<48>, grid, block, 0, stream, qkv, O, dO, stats, ld, D, L, H, mask, out, ldo);
     }
     return hip_status();
+}
+
+// ---- forward: row-panel GEMM, fused MLP, few-row GEMM.  The forward's Launcher (uu3d_forward.inc) and the operator ABI (uu3d_ops.hip) launch
+// through these, so that an operator runs the instantiation the forward runs. ----
+// chunk counts the 8-wave row-panel kernel (uu3d_gemm_panel8.h) is instantiated for      (9: QKV at 284 row tiles = batch 512, four column ranges)
+inline constexpr bool panel8_has(int cpw) { return cpw == 4 || cpw == 6 || cpw == 8 || cpw == 9 || cpw == 12; }
+// (row tiles x S column ranges) work items, dealt to the 8 XCDs in contiguous blocks (gemm_h3_panel_kernel)
+inline dim3 panel_grid(int mt, int S) { return dim3(8 * S, ((mt * S + 7) / 8 + S - 1) / S); }
+// Returns false (nothing launched) when the 8-wave kernel has no instantiation for cpw chunks per workgroup.
+template <class EP>
+bool launch_panel8(hipStream_t stream, const _Float16* Af, const _Float16* Bf, const float* colv, int M, int mt, int S, int cpw, const EP& ep) {
+    const dim3 grid = panel_grid(mt, S);
+#define UU3D_P8_LAUNCH(CPW) { allow_lds<gemm_h3_panel8_kernel<EP, CPW, 3>>(P8_LDS_TOTAL); \
+        hipLaunchKernelGGL((gemm_h3_panel8_kernel<EP, CPW, 3>), grid, dim3(512), P8_LDS_TOTAL, stream, Af, Bf, colv, M, mt, S, ep); return true; }
+    switch (cpw) {
+        case 4: UU3D_P8_LAUNCH(4)
+        case 6: UU3D_P8_LAUNCH(6)
+        case 8: UU3D_P8_LAUNCH(8)
+        case 9: UU3D_P8_LAUNCH(9)
+        case 12: UU3D_P8_LAUNCH(12)
+        default: return false;
+    }
+#undef UU3D_P8_LAUNCH
+}
+// the 4-wave kernel; CPW != 0: the chunk loop unrolled for that many chunks per workgroup
+template <class EP, int CPW = 0>
+void launch_panel4(hipStream_t stream, const _Float16* Af, const _Float16* Bf, const float* colv, int M, int mt, int S, int cpw, const EP& ep) {
+    allow_lds<gemm_h3_panel_kernel<24, EP, CPW>>(PANEL_LDS_TOTAL);
+    hipLaunchKernelGGL((gemm_h3_panel_kernel<24, EP, CPW>), panel_grid(mt, S), dim3(256), PANEL_LDS_TOTAL, stream, Af, Bf, colv, M, mt, S, cpw, ep);
+}
+// x[M][384] += A B + colv on the 4-wave kernel (N = 384, 12 chunks): S = 3 / 2 / 1 column ranges per row tile run the forms with the chunk loop
+// unrolled (CPW = 4 / 6 / 12: uu3d_gemm_panel.h says why an epilogue that loads needs them); any other divisor of 12 the runtime loop
+inline void launch_panel4_residual(hipStream_t stream, const _Float16* Af, const _Float16* Bf, const float* colv, int M, int mt, int S, const PanelEpBiasResidual& ep) {
+    if (S == 3) launch_panel4<PanelEpBiasResidual, 4>(stream, Af, Bf, colv, M, mt, S, 4, ep);
+    else if (S == 2) launch_panel4<PanelEpBiasResidual, 6>(stream, Af, Bf, colv, M, mt, S, 6, ep);
+    else if (S == 1) launch_panel4<PanelEpBiasResidual, 12>(stream, Af, Bf, colv, M, mt, S, 12, ep);
+    else launch_panel4<PanelEpBiasResidual>(stream, Af, Bf, colv, M, mt, S, 12 / S, ep);
+}
+// vit.MLP of a temporal block in one launch (uu3d_mlp_fused.h): the fc2 partial sums of the MLPF_SLICES hidden slices -> mslab[slice][M][384]
+inline void launch_mlp_fused(hipStream_t stream, const _Float16* Af, const _Float16* W1f, const _Float16* W2f, const float* b1, float* mslab, int M) {
+    const int mt = (M + 127) / 128;
+    allow_lds<mlp_fused_h3_kernel<>>(PANEL_LDS_TOTAL);
+    hipLaunchKernelGGL(mlp_fused_h3_kernel<>, panel_grid(mt, MLPF_SLICES), dim3(256), PANEL_LDS_TOTAL, stream, Af, W1f, W2f, b1, mslab, M, mt);
+}
+// Few rows (uu3d_gemm_wt.h): one workgroup per 32 x 32 tile, the contraction split over its waves.  Bh / Bl: the operand's planes [N][Kp].
+// Returns false (nothing launched) when the contraction is longer than one batch of loads per wave holds (K > 768).
+template <class AL, class EP>
+bool launch_gemm_wt(hipStream_t stream, const AL& al, const _Float16* Bh, const _Float16* Bl, int M, int N, int K, const EP& ep) {
+    const int Kp = ru(K, 32), slices = Kp / 16;
+    const int mt = (M + 31) / 32, nt = (N + 31) / 32;
+    if (slices > 6 * WT_MAX_WAVES) return false;             // K <= 768: one batch of loads per wave
+    const int kw = (slices + 5) / 6;
+    hipLaunchKernelGGL((gemm_h3_wt_kernel<AL, EP, 6>), dim3(mt * nt), dim3(64 * kw), gemm_wt_lds_bytes(kw), stream, al, Bh, Bl, M, N, Kp, nt, ep);
+    return true;
 }
 
 }  // namespace uu3d

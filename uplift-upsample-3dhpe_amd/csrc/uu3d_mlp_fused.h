@@ -49,6 +49,8 @@ inline void mlpf_pack_w2(const _Float16* Bh, const _Float16* Bl, int Kp, _Float1
 
 // Af: LayerNorm output, fragment ordered (K = 384).  W1f: the row-panel operand of fc1 (panel_pack_operand: chunk c at
 // c * 48 KiB).  W2f: mlpf_pack_w2.  b1: fc1 bias [768].  slab: [3][M][384] floats.
+// (a template only so that the two translation units that include this header -- the forward and the operator ABI -- may both hold it)
+template <int UNUSED = 0>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 mlp_fused_h3_kernel(const _Float16* __restrict__ Af, const _Float16* __restrict__ W1f, const _Float16* __restrict__ W2f,
                     const float* __restrict__ b1, float* __restrict__ slab, const int M, const int m_tiles)

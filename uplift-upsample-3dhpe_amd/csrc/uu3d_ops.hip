@@ -1,4 +1,4 @@
-// uu3d_ops.hip -- C ABI of the backward building blocks (include/uu3d_ops.h).
+// uu3d_ops.hip -- C ABI of the backward building blocks and of the forward operators (include/uu3d_ops.h).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include "../../include/uu3d.h"
@@ -7,7 +7,6 @@
 #include "uu3d_misc.h"
 #include "uu3d_bwd.h"
 #include "uu3d_launch.h"
-#include "uu3d_gemm_panel.h"
 #include <vector>
 #include <initializer_list>
 
@@ -93,7 +92,21 @@ int uu3d_op_attn_long_bwd(const float* qkv, const float* out, const float* dout,
     return launch_attn_long(true, qkv, out, dout, (const float2*)stats, ld, D, B, L, H, mask, dqkv, nullptr, ldo, (hipStream_t)stream);
 }
 
-// ---- row-panel path of a LayerNorm-fed Dense layer (uu3d_gemm_panel.h) --------------------------------------------
+// ---- forward operators: the LayerNorm-fed Dense layers of the forward, each kernel on its own (launched through uu3d_launch.h, as the forward does) ----
+// Keras (in, out) kernel w[K][N] on the host -> the transposed f16 planes Bt[n][k] the model keeps for every Dense kernel (uu3d_commit_weights: hi, lo * 2048)
+static void split_transposed(const float* w, int K, int N, _Float16* bh, _Float16* bl) {
+    for (int n = 0; n < N; ++n)
+        for (int k = 0; k < K; ++k) {
+            const float x = w[(size_t)k * N + n];
+            const _Float16 h = h3_hi(x);
+            bh[(size_t)n * K + k] = h; bl[(size_t)n * K + k] = (_Float16)((x - (float)h) * H3_SCALE);
+        }
+}
+static int upload_halfs(const std::vector<_Float16>& v, void* dst, hipStream_t stream) {
+    if (hipMemcpyAsync(dst, v.data(), v.size() * sizeof(_Float16), hipMemcpyHostToDevice, stream) != hipSuccess) return UU3D_ERR_HIP;
+    return hipStreamSynchronize(stream) == hipSuccess ? UU3D_OK : UU3D_ERR_HIP;
+}
+
 size_t uu3d_op_panel_operand_bytes(int32_t N) { return (N < 32 || (N & 31)) ? 0 : panel_b_halfs(N, 384) * sizeof(_Float16); }
 size_t uu3d_op_panel_a_bytes(int32_t M) { return M < 1 ? 0 : panel_a_halfs(M, 384) * sizeof(_Float16); }
 
@@ -101,39 +114,120 @@ int uu3d_op_panel_pack(const float* w, int32_t N, void* operand_dev, void* strea
     if (!w || !operand_dev || N < 32 || (N & 31)) return UU3D_ERR_INVALID_ARGUMENT;
     const int K = 384;
     std::vector<_Float16> bh((size_t)N * K), bl((size_t)N * K), out(panel_b_halfs(N, K));
-    for (int n = 0; n < N; ++n)
-        for (int k = 0; k < K; ++k) {
-            const float x = w[(size_t)k * N + n];                     // Keras (in, out) -> Bt[n][k]
-            const _Float16 h = h3_hi(x);
-            bh[(size_t)n * K + k] = h; bl[(size_t)n * K + k] = (_Float16)((x - (float)h) * H3_SCALE);
-        }
+    split_transposed(w, K, N, bh.data(), bl.data());
     panel_pack_operand(bh.data(), bl.data(), N, K, K, out.data());
-    if (hipMemcpyAsync(operand_dev, out.data(), out.size() * sizeof(_Float16), hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess) return UU3D_ERR_HIP;
-    return hipStreamSynchronize((hipStream_t)stream) == hipSuccess ? UU3D_OK : UU3D_ERR_HIP;
+    return upload_halfs(out, operand_dev, (hipStream_t)stream);
+}
+
+int uu3d_op_panel_a_unpack(const void* frag_host, int32_t M, float* hi_host, float* lo_host) {
+    if (!frag_host || !hi_host || !lo_host || M < 1) return UU3D_ERR_INVALID_ARGUMENT;
+    const _Float16* f = reinterpret_cast<const _Float16*>(frag_host);
+    for (int row = 0; row < M; ++row)
+        for (int k = 0; k < 384; ++k) {
+            const size_t at = panel_a_index(row, k, 384);
+            hi_host[(size_t)row * 384 + k] = (float)f[at]; lo_host[(size_t)row * 384 + k] = (float)f[at + 512];
+        }
+    return UU3D_OK;
+}
+
+int uu3d_op_ln_dense_panel_ex(const float* x, int32_t ldx, int32_t M, const float* gamma, const float* beta, float eps, const void* operand,
+                              const float* bias, int32_t N, int32_t waves, int32_t splits, int32_t epilogue, float qscale, void* a_scratch,
+                              void* out, int32_t ldo, float* residual, const float* ln2_gamma, const float* ln2_beta, void* ln_out, void* stream_) {
+    if (!x || !gamma || !beta || !operand || !bias || !a_scratch || M < 1 || N < 32 || (N & 31) || ldx < 384 || (ldx & 3)) return UU3D_ERR_INVALID_ARGUMENT;
+    if ((waves != 4 && waves != 8) || splits < 0 || epilogue < UU3D_EP_BIAS || epilogue > UU3D_EP_BIAS_RESIDUAL_LN) return UU3D_ERR_INVALID_ARGUMENT;
+    const bool res = epilogue == UU3D_EP_BIAS_RESIDUAL || epilogue == UU3D_EP_BIAS_RESIDUAL_LN;
+    if (res ? (!residual || N != 384) : (!out || (epilogue == UU3D_EP_BIAS && ldo < N))) return UU3D_ERR_INVALID_ARGUMENT;
+    if (epilogue == UU3D_EP_BIAS_SPLIT_Q && N % 3 != 0) return UU3D_ERR_INVALID_ARGUMENT;
+    const int mt = (M + 127) / 128, chunks = N / 32;
+    int S = splits;
+    if (S == 0) {                                                     // any divisor that keeps <= 32 chunks per workgroup; prefer ~one round
+        if (waves != 4) return UU3D_ERR_INVALID_ARGUMENT;
+        for (int s = 1; s <= chunks; ++s) if (chunks % s == 0 && chunks / s <= PANEL_COLV_FLOATS / 32 && (S == 0 || (mt * s + 7) / 8 <= 32)) S = s;
+    }
+    if (S < 1 || chunks % S != 0 || chunks / S > PANEL_COLV_FLOATS / 32) return UU3D_ERR_INVALID_ARGUMENT;
+    const int cpw = chunks / S;
+    if (waves == 8 && !panel8_has(cpw)) return UU3D_ERR_INVALID_ARGUMENT;
+    if (epilogue == UU3D_EP_BIAS_RESIDUAL_LN && (waves != 8 || S != 1 || !ln2_gamma || !ln2_beta || !ln_out)) return UU3D_ERR_INVALID_ARGUMENT;
+    if ((double)M * (epilogue == UU3D_EP_BIAS ? ldo : N) * 4.0 >= 4.0e9) return UU3D_ERR_UNSUPPORTED;          // 32-bit byte offsets in the epilogue stores
+    hipStream_t stream = (hipStream_t)stream_;
+    _Float16* Af = reinterpret_cast<_Float16*>(a_scratch);
+    const _Float16* Bf = reinterpret_cast<const _Float16*>(operand);
+    hipLaunchKernelGGL((ln_split_frag_kernel<24, 8>), dim3((M + 7) / 8), dim3(128), 0, stream, x, ldx, M, eps, gamma, beta, Af);
+    auto go = [&](const auto& ep) {
+        if (waves == 8) (void)launch_panel8(stream, Af, Bf, bias, M, mt, S, cpw, ep);      // (panel8_has(cpw) held above)
+        else launch_panel4(stream, Af, Bf, bias, M, mt, S, cpw, ep);
+    };
+    _Float16* oh = reinterpret_cast<_Float16*>(out);
+    switch (epilogue) {
+        case UU3D_EP_BIAS: go(PanelEpBias{reinterpret_cast<float*>(out), ldo}); break;
+        case UU3D_EP_BIAS_RELU_SPLIT: go(PanelEpBiasReluSplit{oh, oh + (size_t)M * N, N}); break;
+        case UU3D_EP_BIAS_SPLIT_Q: go(PanelEpBiasSplitQ{oh, oh + (size_t)M * N, N, N / 3, qscale}); break;
+        case UU3D_EP_BIAS_RESIDUAL: {
+            const PanelEpBiasResidual ep{residual, N};
+            if (waves == 8) (void)launch_panel8(stream, Af, Bf, bias, M, mt, S, cpw, ep);
+            else launch_panel4_residual(stream, Af, Bf, bias, M, mt, S, ep);
+        } break;
+        default: {
+            const PanelEpBiasResidualLn ep{{residual, N}, ln2_gamma, ln2_beta, eps, reinterpret_cast<_Float16*>(ln_out)};
+            (void)launch_panel8(stream, Af, Bf, bias, M, mt, 1, 12, ep);
+        } break;
+    }
+    return hip_status();
 }
 
 int uu3d_op_ln_dense_panel(const float* x, int32_t ldx, int32_t M, const float* gamma, const float* beta, float eps, const void* operand,
-                           const float* bias, int32_t N, int32_t relu, void* a_scratch, void* out, int32_t ldo, void* stream_) {
-    if (!x || !gamma || !beta || !operand || !bias || !a_scratch || !out || M < 1 || N < 32 || (N & 31) || ldx < 384 || (ldx & 3)) return UU3D_ERR_INVALID_ARGUMENT;
-    if ((double)M * (relu ? N : ldo) * 4.0 >= 4.0e9) return UU3D_ERR_UNSUPPORTED;          // 32-bit byte offsets in the epilogue stores
+                           const float* bias, int32_t N, int32_t relu, void* a_scratch, void* out, int32_t ldo, void* stream) {
+    return uu3d_op_ln_dense_panel_ex(x, ldx, M, gamma, beta, eps, operand, bias, N, 4, 0, relu ? UU3D_EP_BIAS_RELU_SPLIT : UU3D_EP_BIAS, 1.0f,
+                                     a_scratch, out, relu ? N : ldo, nullptr, nullptr, nullptr, nullptr, stream);
+}
+
+// ---- fused MLP of a temporal block (uu3d_mlp_fused.h) ----
+size_t uu3d_op_mlp_operand_bytes(void) { return (panel_b_halfs(256 * MLPF_SLICES, 384) + mlpf_w2_halfs()) * sizeof(_Float16); }
+
+int uu3d_op_mlp_pack(const float* w1, const float* w2, void* operand_dev, void* stream) {
+    if (!w1 || !w2 || !operand_dev) return UU3D_ERR_INVALID_ARGUMENT;
+    const int D = 32 * MLPF_OC, H = 256 * MLPF_SLICES;
+    std::vector<_Float16> bh((size_t)D * H), bl((size_t)D * H), out(panel_b_halfs(H, D) + mlpf_w2_halfs());
+    split_transposed(w1, D, H, bh.data(), bl.data());                // fc1: Bt[hidden][384] -> w1_pf
+    panel_pack_operand(bh.data(), bl.data(), H, D, D, out.data());
+    split_transposed(w2, H, D, bh.data(), bl.data());                // fc2: Bt[out][768] -> w2_mf
+    mlpf_pack_w2(bh.data(), bl.data(), H, out.data() + panel_b_halfs(H, D));
+    return upload_halfs(out, operand_dev, (hipStream_t)stream);
+}
+
+int uu3d_op_mlp_fused(const float* x, int32_t ldx, int32_t M, const float* gamma, const float* beta, float eps, const void* operand,
+                      const float* b1, void* a_scratch, float* mslab, void* stream_) {
+    if (!x || !gamma || !beta || !operand || !b1 || !a_scratch || !mslab || M < 1 || ldx < 384 || (ldx & 3)) return UU3D_ERR_INVALID_ARGUMENT;
     hipStream_t stream = (hipStream_t)stream_;
     _Float16* Af = reinterpret_cast<_Float16*>(a_scratch);
+    const _Float16* W1f = reinterpret_cast<const _Float16*>(operand);
     hipLaunchKernelGGL((ln_split_frag_kernel<24, 8>), dim3((M + 7) / 8), dim3(128), 0, stream, x, ldx, M, eps, gamma, beta, Af);
-    const int mt = (M + 127) / 128, chunks = N / 32;
-    int S = 0;                                                        // any divisor that keeps <= 32 chunks per workgroup; prefer ~one round
-    for (int s = 1; s <= chunks; ++s) if (chunks % s == 0 && chunks / s <= 32 && (S == 0 || (mt * s + 7) / 8 <= 32)) S = s;
-    if (S == 0) return UU3D_ERR_UNSUPPORTED;
-    const dim3 grid(8 * S, ((mt * S + 7) / 8 + S - 1) / S);
-    const _Float16* Bf = reinterpret_cast<const _Float16*>(operand);
-    if (relu) {
-        auto kern = gemm_h3_panel_kernel<24, PanelEpBiasReluSplit>;
-        allow_lds<gemm_h3_panel_kernel<24, PanelEpBiasReluSplit>>(PANEL_LDS_TOTAL);
-        _Float16* oh = reinterpret_cast<_Float16*>(out);
-        hipLaunchKernelGGL(kern, grid, dim3(256), PANEL_LDS_TOTAL, stream, Af, Bf, bias, M, mt, S, chunks / S, PanelEpBiasReluSplit{oh, oh + (size_t)M * N, N});
-    } else {
-        auto kern = gemm_h3_panel_kernel<24, PanelEpBias>;
-        allow_lds<gemm_h3_panel_kernel<24, PanelEpBias>>(PANEL_LDS_TOTAL);
-        hipLaunchKernelGGL(kern, grid, dim3(256), PANEL_LDS_TOTAL, stream, Af, Bf, bias, M, mt, S, chunks / S, PanelEpBias{reinterpret_cast<float*>(out), ldo});
-    }
-    return hipGetLastError() == hipSuccess ? UU3D_OK : UU3D_ERR_HIP;
+    launch_mlp_fused(stream, Af, W1f, W1f + panel_b_halfs(256 * MLPF_SLICES, 384), b1, mslab, M);
+    return hip_status();
+}
+
+// ---- few-row GEMM with LayerNorm in its loader (uu3d_gemm_wt.h) ----
+static bool wt_dims_ok(int32_t N, int32_t K) { return N >= 32 && !(N & 31) && (K == 384 || K == 768); }
+size_t uu3d_op_wt_operand_bytes(int32_t N, int32_t K) { return wt_dims_ok(N, K) ? (size_t)2 * N * K * sizeof(_Float16) : 0; }
+
+int uu3d_op_wt_pack(const float* w, int32_t K, int32_t N, void* operand_dev, void* stream) {
+    if (!w || !operand_dev || !wt_dims_ok(N, K)) return UU3D_ERR_INVALID_ARGUMENT;
+    std::vector<_Float16> planes((size_t)2 * N * K);
+    split_transposed(w, K, N, planes.data(), planes.data() + (size_t)N * K);
+    return upload_halfs(planes, operand_dev, (hipStream_t)stream);
+}
+
+int uu3d_op_ln_dense_wt(const float* x, int32_t ldx, int32_t M, int32_t K, const float* gamma, const float* beta, float eps, const void* operand,
+                        const float* bias, int32_t N, int32_t epilogue, float qscale, void* out, int32_t ldo, void* stream_) {
+    if (!x || !gamma || !beta || !operand || !bias || !out || M < 1 || M > 512 || !wt_dims_ok(N, K) || ldx < K || (ldx & 3)) return UU3D_ERR_INVALID_ARGUMENT;
+    if (epilogue < UU3D_EP_BIAS || epilogue > UU3D_EP_BIAS_SPLIT_Q || (epilogue == UU3D_EP_BIAS && ldo < N) || (epilogue == UU3D_EP_BIAS_SPLIT_Q && N % 3 != 0)) return UU3D_ERR_INVALID_ARGUMENT;
+    hipStream_t stream = (hipStream_t)stream_;
+    const _Float16* Bh = reinterpret_cast<const _Float16*>(operand); const _Float16* Bl = Bh + (size_t)N * K;
+    const WtLoadF32 al{x, ldx, M, K, gamma, beta, eps, 1};
+    _Float16* oh = reinterpret_cast<_Float16*>(out);
+    bool ok;
+    if (epilogue == UU3D_EP_BIAS) ok = launch_gemm_wt(stream, al, Bh, Bl, M, N, K, EpBias{reinterpret_cast<float*>(out), bias, ldo});
+    else if (epilogue == UU3D_EP_BIAS_RELU_SPLIT) ok = launch_gemm_wt(stream, al, Bh, Bl, M, N, K, EpBiasReluSplit{oh, oh + (size_t)M * N, bias, N});
+    else ok = launch_gemm_wt(stream, al, Bh, Bl, M, N, K, EpBiasSplitQ{oh, oh + (size_t)M * N, bias, N, N / 3, qscale});
+    return ok ? hip_status() : UU3D_ERR_UNSUPPORTED;
 }
