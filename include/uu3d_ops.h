@@ -128,6 +128,41 @@ int uu3d_op_ln_dense_wt(const float* x_dev, int32_t ldx, int32_t M, int32_t K, c
                         const void* operand_dev, const float* bias_dev, int32_t N, int32_t epilogue, float qscale, void* out_dev,
                         int32_t ldo, void* stream);
 
+/* ---- the forward's temporal attention kernels, each on its own (csrc/uu3d_attn.h, csrc/uu3d_attn_h3.h), launched through the helper the
+ * forward's Launcher::attn launches through (launch_attn_infer, csrc/uu3d_launch.h) -- tests/test_attn_infer_gpu.py holds them to float64.
+ * B sequences of L tokens, H heads of 48 channels: D == 48 H.  key_mask_dev (optional): B * L bytes, 0 = masked key (its logit gets -1e9);
+ * a sequence with every key masked attends uniformly: its context rows are the mean of v. ---- */
+#define UU3D_ATTN_AUTO 0        /* the forward's rule (attn_choose) at precision f16x3 with no switch set */
+#define UU3D_ATTN_F32_WG 1      /* attn_f32_kernel<ceil(L / 16), 48, SPLIT>: exact f32, one workgroup per (sequence, head); L <= 128 */
+#define UU3D_ATTN_HEAD_WAVE 2   /* attn_head_wave_kernel<4 | 5, 48, SPLIT>: exact f32, one wave per (sequence, head); 49 <= L <= 80, H % 4 == 0 */
+#define UU3D_ATTN_H3 3          /* attn_h3_kernel<48, MAXW, WPE, MASKED>: f16x3 products, online softmax over 32-key tiles; L <= 416 */
+#define UU3D_ATTN_IN_F32 0      /* qkv_dev: [B L][3 D] floats, rows [q | k | v]; the kernel scales the logits by 1 / sqrt(48) itself */
+#define UU3D_ATTN_IN_PLANES 1   /* qkv_dev: two f16 planes, hi [B L][3 D] halfs and lo directly behind it (value = hi + lo / 2048), 4 B L 3 D
+                                 * bytes; q PRESCALED: already multiplied by log2(e) / sqrt(48), as the QKV projection's epilogue leaves it */
+#define UU3D_ATTN_IN_QFRAG 2    /* qkv_dev: the same planes in the temporal chain's fragment order, uu3d_op_attn_qf_bytes(B L) bytes made by
+                                 * uu3d_op_attn_qf_pack; q prescaled likewise.  The channels inside a 16-channel group arrive in lane order,
+                                 * which q . k does not see and which v carries to the output: output channel 16 u + 8 g + j of a row holds
+                                 * what lane 32 g, half j of v's piece (group u) held.  D == 384 */
+#define UU3D_ATTN_OUT_F32 0     /* out_dev: [B L][D] floats */
+#define UU3D_ATTN_OUT_PLANES 1  /* out_dev: hi [B L][D] halfs, lo directly behind it: 4 B L D bytes */
+#define UU3D_ATTN_OUT_FRAG 2    /* out_dev: the row-panel GEMM's A-fragment order, uu3d_op_panel_a_bytes(B L) bytes, read back with
+                                 * uu3d_op_panel_a_unpack; rows past B L of the last 32-row panel are not written.  D == 384 */
+/* The exact-f32 kernels read UU3D_ATTN_IN_F32 and write any output form; attn_h3_kernel reads planes (either order) and writes planes
+ * (either order).  Every device pointer 16-byte aligned.  Returned before any launch, the output untouched:
+ *   UU3D_ERR_INVALID_ARGUMENT: a null qkv_dev / out_dev, misaligned pointers, B, L or H < 1, D != 48 H, an unknown kernel or layout;
+ *     UU3D_ATTN_F32_WG / _HEAD_WAVE with plane input; UU3D_ATTN_H3 with UU3D_ATTN_IN_F32 or UU3D_ATTN_OUT_F32; UU3D_ATTN_HEAD_WAVE outside
+ *     49 .. 80 tokens or with H % 4 != 0; UU3D_ATTN_IN_QFRAG or UU3D_ATTN_OUT_FRAG with D != 384 (the fragment strides are written for 72
+ *     groups / 384 columns); UU3D_ATTN_AUTO with layouts the kernel its rule names cannot take (plane input up to 48 tokens in row-major
+ *     order; f32 input with plane output above 48 tokens; plane input with f32 output);
+ *   UU3D_ERR_UNSUPPORTED (as the forward answers): the exact-f32 kernels above 128 tokens, attn_h3_kernel above 416. */
+int uu3d_op_attn_infer(const void* qkv_dev, int32_t in_layout, int32_t D, int32_t B, int32_t L, int32_t H, const uint8_t* key_mask_dev,
+                       int32_t kernel, void* out_dev, int32_t out_layout, void* stream);
+/* bytes of the fragment-ordered q | k | v buffer of `rows` tokens: whole 128-row tiles, as the temporal chain allocates it (0: rows < 1) */
+size_t uu3d_op_attn_qf_bytes(int32_t rows);
+/* HOST: hi_host / lo_host, f16 planes [rows][1152] of [q | k | v] rows (D = 384), into frag_host (uu3d_op_attn_qf_bytes(rows)) through the
+ * producer's own index function (tchain_qf_index, csrc/uu3d_tchain16.h).  Elements of rows past `rows` in the last tile are left as they are. */
+int uu3d_op_attn_qf_pack(const void* hi_host, const void* lo_host, int32_t rows, void* frag_host);
+
 #ifdef __cplusplus
 }
 #endif

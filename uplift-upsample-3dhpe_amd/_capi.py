@@ -57,9 +57,14 @@ OPS_SYMBOLS = (
     "uu3d_op_panel_operand_bytes", "uu3d_op_panel_a_bytes", "uu3d_op_panel_pack", "uu3d_op_ln_dense_panel",
     "uu3d_op_ln_dense_panel_ex", "uu3d_op_panel_a_unpack", "uu3d_op_mlp_operand_bytes", "uu3d_op_mlp_pack", "uu3d_op_mlp_fused",
     "uu3d_op_wt_operand_bytes", "uu3d_op_wt_pack", "uu3d_op_ln_dense_wt",
+    "uu3d_op_attn_infer", "uu3d_op_attn_qf_bytes", "uu3d_op_attn_qf_pack",
 )
 # epilogues of uu3d_op_ln_dense_panel_ex / uu3d_op_ln_dense_wt (include/uu3d_ops.h)
 UU3D_EP_BIAS, UU3D_EP_BIAS_RELU_SPLIT, UU3D_EP_BIAS_SPLIT_Q, UU3D_EP_BIAS_RESIDUAL, UU3D_EP_BIAS_RESIDUAL_LN = range(5)
+# kernels and layouts of uu3d_op_attn_infer (include/uu3d_ops.h)
+UU3D_ATTN_AUTO, UU3D_ATTN_F32_WG, UU3D_ATTN_HEAD_WAVE, UU3D_ATTN_H3 = range(4)
+UU3D_ATTN_IN_F32, UU3D_ATTN_IN_PLANES, UU3D_ATTN_IN_QFRAG = range(3)
+UU3D_ATTN_OUT_F32, UU3D_ATTN_OUT_PLANES, UU3D_ATTN_OUT_FRAG = range(3)
 
 
 class Uu3dLibraryError(RuntimeError):
@@ -435,6 +440,12 @@ def load_library(path=None):
     lib.uu3d_op_wt_pack.argtypes = [vp, i32, i32, vp, vp]
     lib.uu3d_op_ln_dense_wt.restype = C.c_int
     lib.uu3d_op_ln_dense_wt.argtypes = [vp, i32, i32, i32, vp, vp, C.c_float, vp, vp, i32, i32, C.c_float, vp, i32, vp]
+    lib.uu3d_op_attn_infer.restype = C.c_int
+    lib.uu3d_op_attn_infer.argtypes = [vp, i32, i32, i32, i32, i32, vp, i32, vp, i32, vp]
+    lib.uu3d_op_attn_qf_bytes.restype = sz
+    lib.uu3d_op_attn_qf_bytes.argtypes = [i32]
+    lib.uu3d_op_attn_qf_pack.restype = C.c_int
+    lib.uu3d_op_attn_qf_pack.argtypes = [vp, vp, i32, vp]
     if path is None:
         _lib = lib
     return lib

@@ -368,12 +368,10 @@ struct Launcher {
         end();
     }
 
-    // sequences served by attn_h3_kernel (f16x3 products, online softmax; q / k / v as f16 planes from the QKV epilogue): everything
-    // the exact-f32 kernels cannot hold (> 128 tokens) and, measured faster, 49-128 tokens as well
-    // (shorter sequences, h36m_81's 41 tokens: the split epilogue of the QKV projection costs more than the attention gains -- 242.1 k
-    // sequences/s with the exact-f32 kernels there against 240.2 k)
-    bool attn_is_h3(int L, bool planes_out) const { return planes_out && L <= ATTN_H3_MAX_L && (L > 128 || (L > 48 && !m->sw.attn_f32)); }
-    bool attn_h3_any(int L) const { return precision == UU3D_PREC_F16X3 && L <= ATTN_H3_MAX_L && !m->sw.attn_f32; }
+    // which attention kernel a launch takes: attn_choose (uu3d_launch.h) on this call's precision and the handle's switches
+    AttnRule attn_rule() const { AttnRule r; r.precision = precision; r.attn_f32 = m->sw.attn_f32; r.attn_wg = m->sw.attn_wg; return r; }
+    bool attn_is_h3(int L, bool planes_out) const { return uu3d::attn_is_h3(attn_rule(), L, planes_out); }
+    bool attn_h3_any(int L) const { return uu3d::attn_h3_any(attn_rule(), L); }
     float attn_qscale() const { return 1.44269504088896341f / sqrtf((float)kDH); }
     // split_lo_off != 0: the context rows go out as f16 planes (hi at out, lo split_lo_off halfs further)
     // frag: the context rows in the row-panel GEMM's A-fragment order instead of row-major planes (split_lo_off != 0 only)
@@ -381,54 +379,13 @@ struct Launcher {
     void attn(const char* name, const float* qkv, int B, int L, const uint8_t* mask, float* out, size_t split_lo_off = 0, bool frag = false, bool qfrag = false) {
         if (skip_mask() & 16) return;
         const int D = m->cfg.d_temporal, H = m->cfg.num_heads;
-        const int NT = (L + 15) / 16;
-        const bool h3a = attn_is_h3(L, split_lo_off != 0) || (qfrag && attn_h3_any(L));          // (the chain's fragment-ordered planes cost no split epilogue: attn_h3_kernel below 49 tokens too)
-        begin(name, h3a ? "attn_h3" : "attn_f32", 4.0 * B * (double)H * L * L * kDH, 4.0 * 4.0 * B * (double)L * D);
-        const int items = B * H;
-        const dim3 grid(items);
-        if (qfrag && !h3a) { status = UU3D_ERR_UNSUPPORTED; m->err = "fragment-ordered q | k | v need attn_h3_kernel"; end(); return; }
-        if (h3a) {                                                 // qkv = hi plane [B L][3 D] halfs, lo plane behind it
-            const int nt = (L + 31) / 32;
-            const size_t lds = attn_h3_lds_bytes(L, kDH);
-            _Float16* oh = reinterpret_cast<_Float16*>(out);
-            const _Float16* qh = reinterpret_cast<const _Float16*>(qkv); const _Float16* ql = qh + (size_t)B * L * 3 * D;
-#define UU3D_ATTN_H3(MW, WPE, MASKED, waves) { allow_lds<attn_h3_kernel<kDH, MW, WPE, MASKED>>(attn_h3_lds_bytes(ATTN_H3_MAX_L, kDH)); \
-                hipLaunchKernelGGL((attn_h3_kernel<kDH, MW, WPE, MASKED>), grid, dim3(64 * (waves)), lds, stream, qh, ql, 3 * D, D, L, H, mask, oh, frag ? (size_t)512 : split_lo_off, D, frag ? 1 : 0, qfrag ? 1 : 0); }
-            // 4 .. 12 key tiles (dense-351: 11): one wave per query tile, three per SIMD (dense-351: 35.4 vs 36.8 us with 8 waves x 2 tiles)
-            if (nt <= 3) { if (mask) UU3D_ATTN_H3(3, 3, true, nt) else UU3D_ATTN_H3(3, 3, false, nt) }
-            else if (nt <= 12) { if (mask) UU3D_ATTN_H3(12, 3, true, nt) else UU3D_ATTN_H3(12, 3, false, nt) }
-            else { if (mask) UU3D_ATTN_H3(8, 2, true, std::min(nt, 8)) else UU3D_ATTN_H3(8, 2, false, std::min(nt, 8)) }
-#undef UU3D_ATTN_H3
-            end();
-            return;
+        const AttnRule rule = attn_rule();
+        begin(name, attn_class_name(attn_choose(rule, L, H, split_lo_off != 0, qfrag)), 4.0 * B * (double)H * L * L * kDH, 4.0 * 4.0 * B * (double)L * D);
+        if (launch_attn_infer(stream, qkv, D, B, L, H, mask, out, split_lo_off, frag, qfrag, rule) != UU3D_OK) {
+            status = UU3D_ERR_UNSUPPORTED;
+            m->err = qfrag ? "fragment-ordered q | k | v need attn_h3_kernel"
+                           : "attention over more than 128 tokens needs the f16x3 path (precision f16x3, d_t and h_t multiples of 32)";
         }
-        // one wave per (sequence, head), four heads per workgroup (attn_head_wave_kernel): whenever the heads come in fours and the
-        // K / V tiles of four heads fit the LDS; UU3D_ATTN_WG=1 keeps the workgroup-per-item kernel
-        // NT <= 3: more, smaller workgroups hide latency better (measured)
-        if (!m->sw.attn_wg && H % 4 == 0 && NT >= 4 && NT <= 5) {
-            const dim3 hgrid((items + 3) / 4);
-#define UU3D_ATTN_HW(nt) case nt: { \
-            constexpr size_t lds = attn_head_wave_lds_bytes<nt, kDH>(); \
-            if (split_lo_off) { allow_lds<attn_head_wave_kernel<nt, kDH, true>>(lds); \
-                hipLaunchKernelGGL((attn_head_wave_kernel<nt, kDH, true>), hgrid, dim3(256), lds, stream, qkv, 3 * D, D, L, H, mask, out, D, frag ? (size_t)512 : split_lo_off, items); } \
-            else { allow_lds<attn_head_wave_kernel<nt, kDH, false>>(lds); \
-                hipLaunchKernelGGL((attn_head_wave_kernel<nt, kDH, false>), hgrid, dim3(256), lds, stream, qkv, 3 * D, D, L, H, mask, out, D, (size_t)0, items); } \
-            } break;
-            switch (NT) { UU3D_ATTN_HW(4) UU3D_ATTN_HW(5) default: break; }
-#undef UU3D_ATTN_HW
-            end();
-            return;
-        }
-#define UU3D_ATTN_CASE(nt) case nt: \
-        if (split_lo_off) hipLaunchKernelGGL((attn_f32_kernel<nt, kDH, true>), grid, dim3(64 * nt), 0, stream, qkv, 3 * D, D, L, H, mask, out, D, frag ? (size_t)512 : split_lo_off); \
-        else hipLaunchKernelGGL((attn_f32_kernel<nt, kDH, false>), grid, dim3(64 * nt), 0, stream, qkv, 3 * D, D, L, H, mask, out, D, (size_t)0); \
-        break;
-        switch (NT) {
-            UU3D_ATTN_CASE(1) UU3D_ATTN_CASE(2) UU3D_ATTN_CASE(3) UU3D_ATTN_CASE(4)
-            UU3D_ATTN_CASE(5) UU3D_ATTN_CASE(6) UU3D_ATTN_CASE(7) UU3D_ATTN_CASE(8)
-            default: status = UU3D_ERR_UNSUPPORTED; m->err = "attention over more than 128 tokens needs the f16x3 path (precision f16x3, d_t and h_t multiples of 32)"; break;
-        }
-#undef UU3D_ATTN_CASE
         end();
     }
 };

@@ -11,6 +11,8 @@
 #include "uu3d_gemm_panel8.h"
 #include "uu3d_gemm_wt.h"
 #include "uu3d_mlp_fused.h"
+#include "uu3d_attn.h"
+#include "uu3d_attn_h3.h"
 
 namespace uu3d {
 
@@ -336,6 +338,95 @@ bool launch_gemm_wt(hipStream_t stream, const AL& al, const _Float16* Bh, const 
     const int kw = (slices + 5) / 6;
     hipLaunchKernelGGL((gemm_h3_wt_kernel<AL, EP, 6>), dim3(mt * nt), dim3(64 * kw), gemm_wt_lds_bytes(kw), stream, al, Bh, Bl, M, N, Kp, nt, ep);
     return true;
+}
+
+// ---- forward: temporal self-attention, head dim 48 (uu3d_attn.h, uu3d_attn_h3.h).  Which kernel a launch takes is decided HERE and nowhere else. ----
+constexpr int kAttnDH = 48;
+enum AttnKernel : int { ATTN_AUTO = 0, ATTN_F32_WG = 1, ATTN_HEAD_WAVE = 2, ATTN_H3 = 3 };      // = UU3D_ATTN_* of include/uu3d_ops.h
+// what the choice depends on besides the shape: the call's precision, UU3D_ATTN_F32 / UU3D_ATTN_WG (uu3d_switches.h), and a kernel forced by the caller
+struct AttnRule { int precision = UU3D_PREC_F16X3; bool attn_f32 = false, attn_wg = false; int forced = ATTN_AUTO; };
+// sequences served by attn_h3_kernel (f16x3 products, online softmax; q / k / v as f16 planes from the QKV epilogue): everything
+// the exact-f32 kernels cannot hold (> 128 tokens) and, measured faster, 49-128 tokens as well
+// (shorter sequences, h36m_81's 41 tokens: the split epilogue of the QKV projection costs more than the attention gains -- 242.1 k
+// sequences/s with the exact-f32 kernels there against 240.2 k)
+inline bool attn_is_h3(const AttnRule& r, int L, bool planes_out) { return planes_out && L <= ATTN_H3_MAX_L && (L > 128 || (L > 48 && !r.attn_f32)); }
+inline bool attn_h3_any(const AttnRule& r, int L) { return r.precision == UU3D_PREC_F16X3 && L <= ATTN_H3_MAX_L && !r.attn_f32; }
+// The kernel family of one launch; ATTN_AUTO (= 0) when the rule, or the forced kernel, has none for the shape.
+//   planes_out: the context rows leave as f16 planes;  qfrag: q | k | v arrive in the temporal chain's fragment order
+inline int attn_choose(const AttnRule& r, int L, int H, bool planes_out, bool qfrag) {
+    const int NT = (L + 15) / 16;
+    const bool hw_fits = H % 4 == 0 && NT >= 4 && NT <= 5;
+    switch (r.forced) {
+        case ATTN_H3: return planes_out && L <= ATTN_H3_MAX_L ? ATTN_H3 : ATTN_AUTO;
+        case ATTN_HEAD_WAVE: return !qfrag && hw_fits ? ATTN_HEAD_WAVE : ATTN_AUTO;
+        case ATTN_F32_WG: return !qfrag && NT <= 8 ? ATTN_F32_WG : ATTN_AUTO;
+        default: break;
+    }
+    // (the chain's fragment-ordered planes cost no split epilogue: attn_h3_kernel below 49 tokens too)
+    if (attn_is_h3(r, L, planes_out) || (qfrag && attn_h3_any(r, L))) return ATTN_H3;
+    if (qfrag) return ATTN_AUTO;
+    // one wave per (sequence, head), four heads per workgroup (attn_head_wave_kernel): whenever the heads come in fours and the
+    // K / V tiles of four heads fit the LDS; UU3D_ATTN_WG=1 keeps the workgroup-per-item kernel
+    // NT <= 3: more, smaller workgroups hide latency better (measured)
+    if (!r.attn_wg && hw_fits) return ATTN_HEAD_WAVE;
+    return NT <= 8 ? ATTN_F32_WG : ATTN_AUTO;
+}
+// the kernel class a profile records for a family (both exact-f32 kernels are "attn_f32")
+inline const char* attn_class_name(int kernel) { return kernel == ATTN_H3 ? "attn_h3" : "attn_f32"; }
+
+// One attention launch over B sequences of L tokens, H heads of 48 channels (D = 48 H).
+//   attn_h3_kernel: qkv = the hi plane [B L][3 D] halfs with the lo plane directly behind it, or (qfrag) the fragment-ordered buffer; the
+//   exact-f32 kernels: qkv = [B L][3 D] floats.
+//   split_lo_off != 0: the context rows go out as f16 planes (hi at out, lo split_lo_off halfs further); frag: in the row-panel GEMM's
+//   A-fragment order instead of row-major planes (split_lo_off != 0 only)
+// Returns UU3D_OK after the launch (the caller reads the launch error), UU3D_ERR_UNSUPPORTED without one; *klass = the kernel class name.
+inline int launch_attn_infer(hipStream_t stream, const float* qkv, int D, int B, int L, int H, const uint8_t* mask, float* out, size_t split_lo_off,
+                             bool frag, bool qfrag, const AttnRule& rule, const char** klass = nullptr) {
+    constexpr int kDH = kAttnDH;
+    const int kernel = attn_choose(rule, L, H, split_lo_off != 0, qfrag);
+    if (klass) *klass = attn_class_name(kernel);
+    if (kernel == ATTN_AUTO) return UU3D_ERR_UNSUPPORTED;
+    const int NT = (L + 15) / 16;
+    const int items = B * H;
+    const dim3 grid(items);
+    if (kernel == ATTN_H3) {                                       // qkv = hi plane [B L][3 D] halfs, lo plane behind it
+        const int nt = (L + 31) / 32;
+        const size_t lds = attn_h3_lds_bytes(L, kDH);
+        _Float16* oh = reinterpret_cast<_Float16*>(out);
+        const _Float16* qh = reinterpret_cast<const _Float16*>(qkv); const _Float16* ql = qh + (size_t)B * L * 3 * D;
+#define UU3D_ATTN_H3_LAUNCH(MW, WPE, MASKED, waves) { allow_lds<attn_h3_kernel<kDH, MW, WPE, MASKED>>(attn_h3_lds_bytes(ATTN_H3_MAX_L, kDH)); \
+            hipLaunchKernelGGL((attn_h3_kernel<kDH, MW, WPE, MASKED>), grid, dim3(64 * (waves)), lds, stream, qh, ql, 3 * D, D, L, H, mask, oh, frag ? (size_t)512 : split_lo_off, D, frag ? 1 : 0, qfrag ? 1 : 0); }
+        // 4 .. 12 key tiles (dense-351: 11): one wave per query tile, three per SIMD (dense-351: 35.4 vs 36.8 us with 8 waves x 2 tiles)
+        if (nt <= 3) { if (mask) UU3D_ATTN_H3_LAUNCH(3, 3, true, nt) else UU3D_ATTN_H3_LAUNCH(3, 3, false, nt) }
+        else if (nt <= 12) { if (mask) UU3D_ATTN_H3_LAUNCH(12, 3, true, nt) else UU3D_ATTN_H3_LAUNCH(12, 3, false, nt) }
+        else { if (mask) UU3D_ATTN_H3_LAUNCH(8, 2, true, std::min(nt, 8)) else UU3D_ATTN_H3_LAUNCH(8, 2, false, std::min(nt, 8)) }
+#undef UU3D_ATTN_H3_LAUNCH
+        return UU3D_OK;
+    }
+    if (kernel == ATTN_HEAD_WAVE) {
+        const dim3 hgrid((items + 3) / 4);
+#define UU3D_ATTN_HW(nt) case nt: { \
+        constexpr size_t lds = attn_head_wave_lds_bytes<nt, kDH>(); \
+        if (split_lo_off) { allow_lds<attn_head_wave_kernel<nt, kDH, true>>(lds); \
+            hipLaunchKernelGGL((attn_head_wave_kernel<nt, kDH, true>), hgrid, dim3(256), lds, stream, qkv, 3 * D, D, L, H, mask, out, D, frag ? (size_t)512 : split_lo_off, items); } \
+        else { allow_lds<attn_head_wave_kernel<nt, kDH, false>>(lds); \
+            hipLaunchKernelGGL((attn_head_wave_kernel<nt, kDH, false>), hgrid, dim3(256), lds, stream, qkv, 3 * D, D, L, H, mask, out, D, (size_t)0, items); } \
+        } break;
+        switch (NT) { UU3D_ATTN_HW(4) UU3D_ATTN_HW(5) default: break; }
+#undef UU3D_ATTN_HW
+        return UU3D_OK;
+    }
+#define UU3D_ATTN_CASE(nt) case nt: \
+    if (split_lo_off) hipLaunchKernelGGL((attn_f32_kernel<nt, kDH, true>), grid, dim3(64 * nt), 0, stream, qkv, 3 * D, D, L, H, mask, out, D, frag ? (size_t)512 : split_lo_off); \
+    else hipLaunchKernelGGL((attn_f32_kernel<nt, kDH, false>), grid, dim3(64 * nt), 0, stream, qkv, 3 * D, D, L, H, mask, out, D, (size_t)0); \
+    break;
+    switch (NT) {
+        UU3D_ATTN_CASE(1) UU3D_ATTN_CASE(2) UU3D_ATTN_CASE(3) UU3D_ATTN_CASE(4)
+        UU3D_ATTN_CASE(5) UU3D_ATTN_CASE(6) UU3D_ATTN_CASE(7) UU3D_ATTN_CASE(8)
+        default: break;
+    }
+#undef UU3D_ATTN_CASE
+    return UU3D_OK;
 }
 
 }  // namespace uu3d

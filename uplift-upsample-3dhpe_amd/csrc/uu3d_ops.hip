@@ -7,6 +7,7 @@
 #include "uu3d_misc.h"
 #include "uu3d_bwd.h"
 #include "uu3d_launch.h"
+#include "uu3d_tchain16.h"      // tchain_qf_index, tchain_qf_halfs
 #include <vector>
 #include <initializer_list>
 
@@ -230,4 +231,41 @@ int uu3d_op_ln_dense_wt(const float* x, int32_t ldx, int32_t M, int32_t K, const
     else if (epilogue == UU3D_EP_BIAS_RELU_SPLIT) ok = launch_gemm_wt(stream, al, Bh, Bl, M, N, K, EpBiasReluSplit{oh, oh + (size_t)M * N, bias, N});
     else ok = launch_gemm_wt(stream, al, Bh, Bl, M, N, K, EpBiasSplitQ{oh, oh + (size_t)M * N, bias, N, N / 3, qscale});
     return ok ? hip_status() : UU3D_ERR_UNSUPPORTED;
+}
+
+// ---- the forward's temporal attention kernels (launch_attn_infer, uu3d_launch.h: the launch Launcher::attn makes) ----
+size_t uu3d_op_attn_qf_bytes(int32_t rows) { return rows < 1 ? 0 : tchain_qf_halfs((rows + 127) / 128) * sizeof(_Float16); }
+
+int uu3d_op_attn_qf_pack(const void* hi_host, const void* lo_host, int32_t rows, void* frag_host) {
+    if (!hi_host || !lo_host || !frag_host || rows < 1) return UU3D_ERR_INVALID_ARGUMENT;
+    const _Float16* hi = reinterpret_cast<const _Float16*>(hi_host); const _Float16* lo = reinterpret_cast<const _Float16*>(lo_host);
+    _Float16* f = reinterpret_cast<_Float16*>(frag_host);
+    for (int r = 0; r < rows; ++r)
+        for (int k = 0; k < 1152; ++k) {
+            f[tchain_qf_index((size_t)r, k, 0)] = hi[(size_t)r * 1152 + k];
+            f[tchain_qf_index((size_t)r, k, 1)] = lo[(size_t)r * 1152 + k];
+        }
+    return UU3D_OK;
+}
+
+int uu3d_op_attn_infer(const void* qkv, int32_t in_layout, int32_t D, int32_t B, int32_t L, int32_t H, const uint8_t* mask, int32_t kernel,
+                       void* out, int32_t out_layout, void* stream) {
+    static_assert(UU3D_ATTN_AUTO == ATTN_AUTO && UU3D_ATTN_F32_WG == ATTN_F32_WG && UU3D_ATTN_HEAD_WAVE == ATTN_HEAD_WAVE && UU3D_ATTN_H3 == ATTN_H3, "uu3d_ops.h and uu3d_launch.h name the kernels alike");
+    if (!qkv || !out || ((uintptr_t)qkv & 15) || ((uintptr_t)out & 15) || B < 1 || L < 1 || H < 1 || (int64_t)D != (int64_t)kAttnDH * H) return UU3D_ERR_INVALID_ARGUMENT;
+    if (kernel < UU3D_ATTN_AUTO || kernel > UU3D_ATTN_H3 || in_layout < UU3D_ATTN_IN_F32 || in_layout > UU3D_ATTN_IN_QFRAG ||
+        out_layout < UU3D_ATTN_OUT_F32 || out_layout > UU3D_ATTN_OUT_FRAG) return UU3D_ERR_INVALID_ARGUMENT;
+    const bool planes_in = in_layout != UU3D_ATTN_IN_F32, planes_out = out_layout != UU3D_ATTN_OUT_F32;
+    const bool qfrag = in_layout == UU3D_ATTN_IN_QFRAG, frag = out_layout == UU3D_ATTN_OUT_FRAG;
+    if ((qfrag || frag) && D != 384) return UU3D_ERR_INVALID_ARGUMENT;
+    if ((double)B * L * 3.0 * D * 4.0 >= 2.0e9) return UU3D_ERR_UNSUPPORTED;                 // 32-bit element offsets in the exact-f32 kernels
+    AttnRule rule;                                                                          // precision f16x3, no switch set
+    rule.forced = kernel;
+    if (kernel == UU3D_ATTN_H3 ? (!planes_in || !planes_out) : (kernel != UU3D_ATTN_AUTO && planes_in)) return UU3D_ERR_INVALID_ARGUMENT;
+    if (kernel == UU3D_ATTN_HEAD_WAVE && (L < 49 || L > 80 || H % 4 != 0)) return UU3D_ERR_INVALID_ARGUMENT;
+    const int chosen = attn_choose(rule, L, H, planes_out, qfrag);
+    if (chosen == ATTN_AUTO) return UU3D_ERR_UNSUPPORTED;                                    // beyond every kernel's length, as the forward answers
+    if ((chosen == ATTN_H3) != planes_in) return UU3D_ERR_INVALID_ARGUMENT;                  // (UU3D_ATTN_AUTO only: the forced forms were checked above)
+    const size_t lo_off = planes_out ? (size_t)B * L * D : 0;
+    const int st = launch_attn_infer((hipStream_t)stream, reinterpret_cast<const float*>(qkv), D, B, L, H, mask, reinterpret_cast<float*>(out), lo_off, frag, qfrag, rule);
+    return st != UU3D_OK ? st : hip_status();
 }
