@@ -1,0 +1,41 @@
+"""The options of the track stages, checked once for ``predict.predict_tracks`` (``per="track"``) and ``stream.StreamSession``
+(``per="slot"``): ``stage_options`` runs the refusals the two share -- none of them touches a model or a device -- and returns what the
+stages take.  A refusal only one of the two has stays with it (``fps`` with ``keyframes_only`` offline; the "together with out_fps"
+family, ``MAX_LIVE_REPAIR`` and the one camera of ``detections`` live).  Wraps no library call."""
+import collections
+
+from .bones import check_bones
+from .keypoints import keypoint_map
+from .roots import DEFAULT_MIN_ROOT_JOINTS, MAX_ROOT_JOINTS, check_cameras, check_min_root_joints
+from .smooth import check_smooth
+from .validity import check_repair_joints
+
+# cameras: (count, 4) float64 or None; min_root_joints: the checked int (a session without a camera: None); pose_filter / root_filter: a
+# ``OneEuro`` or None each; rigid: None or (skeleton, (count, J) lengths or None for "track"); keypoints: a ``KeypointMap`` or None
+StageOptions = collections.namedtuple("StageOptions", "cameras min_root_joints pose_filter root_filter rigid keypoints")
+
+OUT_FPS_NEEDS_FPS = {"track": "out_fps needs fps: the rate the tracks were filmed at", "slot": "out_fps needs fps: the rate of the pushed frames"}
+
+
+def stage_options(config, count, per, root_relative, keypoints, camera, min_root_joints, smooth, bones, repair_joints, fps, out_fps):
+    """``count`` tracks (``per="track"``) or slots (``per="slot"``) of a model of ``config``; the other arguments as ``predict_tracks`` and
+    ``StreamSession`` take them -> a ``StageOptions``.  Every refusal is a ValueError in the words of the stage's own check.
+    ``min_root_joints``: a session passes None for "not given" -- the default with a camera, and anything else without one is refused (it
+    is a parameter of the root solve); the offline call has the default in its signature and passes what it got.
+    ``repair_joints`` is checked for its type only: whether it has the ``valid`` it needs is the caller's to say."""
+    pose_filter, root_filter = check_smooth(smooth, camera is not None)
+    rigid = check_bones(bones, count, config.NUM_KEYPOINTS, int(config.ROOT_KEYTPOINT) if root_relative else None, per=per)
+    cameras = None
+    if camera is not None:
+        cameras = check_cameras(camera, count, per=per)
+        min_root_joints = check_min_root_joints(DEFAULT_MIN_ROOT_JOINTS if min_root_joints is None and per == "slot" else min_root_joints)
+        if int(config.NUM_KEYPOINTS) > MAX_ROOT_JOINTS:
+            raise ValueError(f"camera needs a model of at most {MAX_ROOT_JOINTS} joints, this one has {int(config.NUM_KEYPOINTS)}")
+    elif per == "slot" and min_root_joints is not None:
+        raise ValueError("min_root_joints needs camera=(fx, fy, cx, cy): it is a parameter of the root solve")
+    if keypoints is not None:
+        keypoints = keypoint_map(keypoints, config.NUM_KEYPOINTS)
+    if fps is None and out_fps is not None:
+        raise ValueError(OUT_FPS_NEEDS_FPS[per])
+    check_repair_joints(repair_joints, "finite")
+    return StageOptions(cameras, min_root_joints, pose_filter, root_filter, rigid, keypoints)

@@ -27,796 +27,45 @@ synchronises the stream once after the last forward (its pipeline's buffers go a
         [--keypoints NAME] [--camera FX FY CX CY] [--min_root_joints N] [--smooth MIN_CUTOFF BETA D_CUTOFF] [--smooth_root MIN_CUTOFF BETA D_CUTOFF]
         [--bones track|FILE.npy]
 
-Per-joint missed detections: ``predict_tracks(..., valid=..., repair_joints=G)`` fills a joint the detector lost for up to G frames by
-linear interpolation between the nearest frames where it was seen (uu3d_repair_joints, in front of the two front kernels above; the rule
-in numpy: ``repair_joints_host``) instead of giving up the whole frame.
-
-Any skeleton: ``predict_tracks(..., keypoints="coco17")`` takes tracks in the DETECTOR's joint layout, (T_i, K_in, 2), and maps them onto the
-model's joints on the device before anything else looks at them (uu3d_map_keypoints; ``KeypointMap``, ``KEYPOINT_PRESETS``; the rule in
-numpy: ``map_keypoints_host``); per-joint flags and scores are then per detector joint.
-
-Per-frame detections: ``predict_detections(model, config, detections, counts, valid, slots=S)`` takes what a multi-person detector emits --
-per frame a list of people in arbitrary order, (T_v, D, K, 2) per video -- associates people to tracks on the device
-(uu3d_associate_detections; ``associate_detections``; the rule in numpy: ``associate_host`` / ``AssociationHost``: greedy, no motion model,
-S, D, K <= 64) and calls ``predict_tracks`` on the tracks -> per video a list of (track_id, first_frame, poses).
-
-Absolute root position: every pose above is root-relative.  ``predict_tracks(..., camera=(fx, fy, cx, cy))`` also returns, per frame, where
-the skeleton stands in the camera's space: at every given frame the translation that projects the returned pose onto the frame's own 2D
-keypoints (uu3d_solve_roots: linear least squares over the observed joints; ``solve_roots`` is the launch alone; the rule in numpy:
-``solve_roots_host``), joined to a piecewise-linear trajectory that is read at the returned frames (uu3d_root_trajectory;
-``root_trajectory_host``).  ``predict_detections(..., camera=...)`` places every person of a video in the same space.
-
-Steady output: the root is solved frame by frame and the poses carry the detector's frame-to-frame noise.  ``predict_tracks(...,
-smooth=OneEuro(min_cutoff, beta, d_cutoff))`` passes the returned poses and roots through the One-Euro filter on the device
-(uu3d_one_euro_tracks: one lane per track and channel walks the frames in order; ``one_euro`` is the launch alone; the rule in numpy:
-``one_euro_host``).  The filter is causal, so the result lags as a live session's does; ``predict_detections(..., smooth=...)`` hands it on.
-
-Constant bone lengths: the network predicts every frame's skeleton on its own, so nothing holds a person's bone lengths constant over a
-track.  ``predict_tracks(..., bones="track")`` rebuilds every pose from the root outwards with each bone at the track's mean length;
-``bones=lengths`` does it with lengths that are known -- calibrated once with ``bone_lengths`` on a recording -- which also takes the
-model's scale error out of the depth ``camera`` solves (``Skeleton`` / ``SKELETONS``: the tree; uu3d_bone_lengths, uu3d_fix_bones;
-``bone_lengths`` / ``fix_bones`` are the launches alone; the rule in numpy: ``bone_lengths_host`` / ``fix_bones_host``).
+The stages behind the options, one module each -- what an option does, its launches and its rule in numpy stand in the module's docstring;
+every name is importable from here as before:
+    validity.py   per-joint missed detections: ``predict_tracks(..., valid=..., repair_joints=G)`` (uu3d_repair_joints)
+    keypoints.py  any skeleton: ``predict_tracks(..., keypoints="coco17")`` (uu3d_map_keypoints; ``KeypointMap``, ``KEYPOINT_PRESETS``)
+    associate.py  per-frame detections: ``predict_detections`` (uu3d_associate_detections), then ``predict_tracks`` on the tracks
+    roots.py      absolute root position: ``predict_tracks(..., camera=(fx, fy, cx, cy))`` (uu3d_solve_roots, uu3d_root_trajectory)
+    smooth.py     steady output: ``predict_tracks(..., smooth=OneEuro(min_cutoff, beta, d_cutoff))`` (uu3d_one_euro_tracks)
+    bones.py      constant bone lengths: ``predict_tracks(..., bones="track")`` (uu3d_bone_lengths, uu3d_fix_bones)
+    tracks.py     the pose table and the three uu3d_*_tracks launches above; options.py: the checks of all these options, shared with a live
+                  session; cli.py: the command-line options, shared with ``stream``
 """
 import argparse
-import ctypes as C
-from fractions import Fraction
+# (noqa: F401 below -- re-exported: every name this module had before the stages became modules of their own)
+from fractions import Fraction  # noqa: F401
 
 import numpy as np
 
-from . import _capi, evaluation
+from . import _capi, evaluation  # noqa: F401
 from . import eval as ev
-from ._capi import ptr as _ptr
-from .data import PoseTable, SequenceGenerator
-from .rates import (_rate_argument, default_mask_stride, frame_rate, frame_rates, given_positions, output_positions,  # noqa: F401 (re-exported)
+from ._capi import ptr as _ptr  # noqa: F401
+from .associate import (ASSOCIATION_DEFAULTS, MAX_ASSOCIATION, Association, AssociationHost, _association_options,  # noqa: F401
+                        _detection_flags, _device_detections, associate_detections, associate_host, association_tracks_host, check_association)
+from .bones import (MAX_BONE_JOINTS, SKELETONS, Bones, Skeleton, _bone_device_poses, _bone_length_table, _bone_offsets, _bone_poses,  # noqa: F401
+                    bone_lengths, bone_lengths_host, check_bones, fix_bones, fix_bones_host, skeleton_of)
+from .cli import add_track_options, bones_option, input_joints, smooth_option, split_scores, track_keywords  # noqa: F401
+from .data import PoseTable, SequenceGenerator  # noqa: F401
+from .keypoints import (KEYPOINT_PRESETS, MAX_KEYPOINT_SOURCES, KeypointMap, _h36m17_from, _map_front, check_keypoint_inputs,  # noqa: F401
+                        keypoint_map, map_keypoints, map_keypoints_host)
+from .options import stage_options
+from .rates import (_rate_argument, default_mask_stride, frame_rate, frame_rates, given_positions, output_positions,  # noqa: F401
                     resample_plan, root_plan)
-
-
-def _upload(a, dtype, device):
-    """Host array -> device tensor through pinned memory, asynchronously: the host never waits for the stream."""
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype)).pin_memory().to(device, non_blocking=True)
-
-
-def normalize_tracks(src, table, lens, resolutions=None, key_stride=0, src_lens=None, valid_in=None, valid_out=None):
-    """uu3d_normalize_tracks on the current stream.  ``src`` (R, J, 2) float32 on the device; ``table`` (sum(lens), J, 2) float32 (may be
-    ``src`` when ``key_stride`` is 0); ``lens``: frames per track; ``resolutions`` (T, 2) (w, h) per track or None (no conversion);
-    ``key_stride`` > 0: ``src`` holds ``src_lens[t]`` keyframes of track t (frames 0, key_stride, ...), scattered into the zero-filled table.
-    ``valid_out`` (sum(lens),) uint8 on the device: uu3d_normalize_tracks_valid -- it receives the per-frame flags (``valid_in`` (R,) uint8 or
-    None AND all coordinates finite) and the table rows of missing frames are zeros."""
-    import torch
-    lib = _capi.load_library()
-    dev = table.device
-    lens = np.asarray(lens, np.int64)
-    T, rows, J = len(lens), int(lens.sum()), int(table.shape[1])
-    row_track = _upload(np.repeat(np.arange(T, dtype=np.int32), lens), np.int32, dev)
-    res = None if resolutions is None else _upload(np.asarray(resolutions, np.float64).reshape(T, 2), np.float64, dev)
-    tstart = sstart = None
-    if key_stride > 0:
-        src_lens = np.asarray(src_lens, np.int64)
-        tstart = _upload(np.concatenate([[0], np.cumsum(lens)[:-1]]), np.int64, dev)
-        sstart = _upload(np.concatenate([[0], np.cumsum(src_lens)[:-1]]), np.int64, dev)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        if valid_out is None:
-            _capi.check(lib, lib.uu3d_normalize_tracks(_ptr(src), int(src.shape[0]), _ptr(table), rows, J, _ptr(row_track), T, _ptr(res),
-                                                       _ptr(tstart), _ptr(sstart), int(key_stride), C.c_void_p(stream)), None)
-        else:
-            _capi.check(lib, lib.uu3d_normalize_tracks_valid(_ptr(src), int(src.shape[0]), _ptr(table), rows, J, _ptr(row_track), T, _ptr(res),
-                                                             _ptr(tstart), _ptr(sstart), int(key_stride), _ptr(valid_in), _ptr(valid_out),
-                                                             C.c_void_p(stream)), None)
-    return table
-
-
-def resample_tracks(src, table, model_lens, left, right, weight, resolutions=None, valid_in=None, valid_out=None):
-    """uu3d_resample_tracks on the current stream.  ``src`` (R, J, 2) float32 on the device; ``table`` (sum(model_lens), J, 2) float32, never
-    ``src``; ``left`` / ``right`` / ``weight``: the plan of ``resample_plan`` (host arrays); ``resolutions`` (T, 2) (w, h) per track or None
-    (no conversion).  ``valid_out`` (sum(model_lens),) uint8 on the device receives the per-model-frame flags (``valid_in`` (R,) uint8 or
-    None, ANDed with all coordinates finite, of the left source frame and, where weight > 0, the right one) and the table rows of missing
-    frames are zeros."""
-    import torch
-    lib = _capi.load_library()
-    dev = table.device
-    model_lens = np.asarray(model_lens, np.int64)
-    T, rows, J = len(model_lens), int(model_lens.sum()), int(table.shape[1])
-    if not (len(left) == len(right) == len(weight) == rows == int(table.shape[0])):
-        raise ValueError("the plan must have one entry per table row")
-    row_track = _upload(np.repeat(np.arange(T, dtype=np.int32), model_lens), np.int32, dev)
-    res = None if resolutions is None else _upload(np.asarray(resolutions, np.float64).reshape(T, 2), np.float64, dev)
-    d_left, d_right, d_weight = _upload(left, np.int64, dev), _upload(right, np.int64, dev), _upload(weight, np.float64, dev)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _capi.check(lib, lib.uu3d_resample_tracks(_ptr(src), int(src.shape[0]), _ptr(table), rows, J, _ptr(row_track), T, _ptr(res), _ptr(d_left),
-                                                  _ptr(d_right), _ptr(d_weight), _ptr(valid_in), _ptr(valid_out), C.c_void_p(stream)), None)
-    return table
-
-
-def assemble_tracks(plain, flipped, left, right, weight, flip_order=None, root=-1):
-    """uu3d_assemble_tracks on the current stream.  ``plain`` / ``flipped`` (W, J, 3) float32 on the device (``flipped`` None: no flip);
-    ``left`` / ``right`` / ``weight``: the plan of ``evaluation.keyframe_plan`` with rows of those arrays (host arrays of F entries);
-    ``root`` >= 0: that joint is subtracted.  -> (F, J, 3) float32 on the device."""
-    import torch
-    lib = _capi.load_library()
-    dev = plain.device
-    W, J = int(plain.shape[0]), int(plain.shape[1])
-    F = len(left)
-    if plain.dtype != torch.float32 or not plain.is_contiguous() or plain.dim() != 3 or plain.shape[2] != 3:
-        raise ValueError("plain must be a contiguous (W, J, 3) float32 device tensor")
-    if flipped is not None and (flipped.shape != plain.shape or flipped.dtype != torch.float32 or not flipped.is_contiguous()):
-        raise ValueError("flipped must match plain")
-    if flipped is not None and (flip_order is None or len(flip_order) != J):
-        raise ValueError("flipped predictions need the J entries of AUGM_FLIP_KEYPOINT_ORDER")
-    d_left, d_right = _upload(left, np.int32, dev), _upload(right, np.int32, dev)
-    d_weight = _upload(weight, np.float64, dev)
-    d_order = None if flipped is None else _upload(flip_order, np.int32, dev)
-    out = torch.empty((F, J, 3), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _capi.check(lib, lib.uu3d_assemble_tracks(_ptr(plain), _ptr(flipped), W, _ptr(d_order), _ptr(d_left), _ptr(d_right), _ptr(d_weight),
-                                                  F, J, int(root), _ptr(out), C.c_void_p(stream)), None)
-    return out
-
-
-def _device_track(t, device):
-    import torch
-    if isinstance(t, torch.Tensor):
-        t = t.to(device=device, dtype=torch.float32)
-    else:
-        t = _upload(np.asarray(t), np.float32, device)
-    if t.dim() != 3 or t.shape[2] != 2:
-        raise ValueError(f"a track must be (T, J, 2), got {tuple(t.shape)}")
-    return t
-
-
-def keyframe_count(length, stride):
-    """Frames 0, stride, 2 stride, ... of a track of ``length`` frames."""
-    return (int(length) + int(stride) - 1) // int(stride)
-
-
-def _shape(a):
-    return tuple(a.shape) if hasattr(a, "shape") else np.asarray(a).shape
-
-
-def check_valid(valid, given, joints=None):
-    """``predict_tracks``' ``valid`` argument against the frames given per track (``given``; keyframes with ``keyframes_only``): None,
-    "finite" or one (T_i,) array / tensor per track -- with ``joints`` = J (``predict_tracks``) an entry may also be (T_i, J), one flag per
-    joint; without it (a session, ``replay_tracks``) only (T_i,) passes.  Shapes only: nothing touches a device."""
-    if valid is None or (isinstance(valid, str) and valid == "finite"):
-        return
-    if isinstance(valid, str) or not isinstance(valid, (list, tuple)):
-        raise ValueError('valid must be None, "finite" or a list with one (T_i,) array per track')
-    if len(valid) != len(given):
-        raise ValueError(f"valid must have one entry per track: {len(given)} tracks, {len(valid)} entries")
-    for i, (v, n) in enumerate(zip(valid, given)):
-        shape = _shape(v)
-        if shape != (int(n),) and (joints is None or shape != (int(n), int(joints))):
-            per_joint = "" if joints is None else f" or ({int(n)}, {int(joints)}): one per joint"
-            raise ValueError(f"valid[{i}] must be ({int(n)},): one flag per given frame of track {i}{per_joint}, got {shape}")
-
-
-def check_repair_joints(repair_joints, valid):
-    """``predict_tracks``' ``repair_joints`` argument: None, or an int G >= 1 together with ``valid``."""
-    if repair_joints is None:
-        return
-    if isinstance(repair_joints, bool) or not isinstance(repair_joints, (int, np.integer)) or int(repair_joints) < 1:
-        raise ValueError(f"repair_joints must be None or an int >= 1: the longest run of frames a joint is filled over, got {repair_joints!r}")
-    if valid is None:
-        raise ValueError('repair_joints needs valid: "finite" or per-frame / per-joint flags say which joints were observed')
-
-
-def _device_valid(valid, device):
-    """The list form of ``valid`` -> one (sum of given frames,) uint8 device tensor; host arrays go up in one pinned, asynchronous copy.
-    A (T_i, J) entry counts per frame here: all of its joints."""
-    import torch
-
-    def frames(v):
-        v = np.asarray(v) != 0
-        return v.all(axis=1) if v.ndim == 2 else v.reshape(-1)
-    if not any(isinstance(v, torch.Tensor) for v in valid):
-        return _upload(np.concatenate([frames(v) for v in valid]).view(np.uint8), np.uint8, device)
-    parts = []
-    for v in valid:
-        if isinstance(v, torch.Tensor):
-            v = v if v.is_cuda else v.contiguous().pin_memory().to(device, non_blocking=True)
-            v = v != 0
-            parts.append((v.all(dim=1) if v.dim() == 2 else v).to(device=device, dtype=torch.uint8))
-        else:
-            parts.append(_upload(frames(v).view(np.uint8), np.uint8, device))
-    return torch.cat(parts, 0)
-
-
-def _device_joint_flags(valid, J, device):
-    """The list form of ``valid`` -> one (sum of given frames, J) uint8 device tensor, one flag per joint; a (T_i,) entry stands for all
-    joints of its frames.  Host arrays go up in one pinned, asynchronous copy."""
-    import torch
-
-    def joints(v):
-        v = np.asarray(v) != 0
-        return v if v.ndim == 2 else np.repeat(v.reshape(-1, 1), J, axis=1)
-    if not any(isinstance(v, torch.Tensor) for v in valid):
-        return _upload(np.concatenate([joints(v) for v in valid], 0).view(np.uint8), np.uint8, device)
-    parts = []
-    for v in valid:
-        if isinstance(v, torch.Tensor):
-            v = v if v.is_cuda else v.contiguous().pin_memory().to(device, non_blocking=True)
-            v = (v != 0).to(device=device, dtype=torch.uint8)
-            parts.append(v if v.dim() == 2 else v.reshape(-1, 1).expand(-1, J))
-        else:
-            parts.append(_upload(joints(v).view(np.uint8), np.uint8, device))
-    return torch.cat(parts, 0).contiguous()
-
-
-def repair_joints_host(tracks, joint_flags, G):
-    """The rule of ``predict_tracks(repair_joints=G)`` (include/uu3d.h, PER-JOINT MISSED DETECTIONS) in numpy, written to be read: what
-    uu3d_repair_joints computes, bit for bit.  ``tracks``: list of (T_i, J, 2) arrays; ``joint_flags``: None (no flags given: the finite test
-    alone) or a list with one (T_i,) or (T_i, J) array per track -> (repaired, frame_flags, state): per track (T_i, J, 2) float32,
-    (T_i,) bool and (T_i, J) uint8 (1 observed, 2 filled, 0 neither).  Nothing crosses a track boundary."""
-    G = int(G)
-    if G < 1:
-        raise ValueError("G must be >= 1")
-    repaired, frame_flags, states = [], [], []
-    for i, track in enumerate(tracks):
-        src = np.asarray(track, np.float32)
-        T, J = src.shape[:2]
-        observed = np.isfinite(src).all(axis=2)
-        if joint_flags is not None:
-            f = np.asarray(joint_flags[i]) != 0
-            observed &= f if f.ndim == 2 else f[:, None]
-        out = np.zeros((T, J, 2), np.float32)
-        state = np.zeros((T, J), np.uint8)
-        for j in range(J):
-            seen = np.flatnonzero(observed[:, j])
-            for t in range(T):
-                if observed[t, j]:
-                    out[t, j], state[t, j] = src[t, j], 1
-                    continue
-                before, after = seen[seen < t], seen[seen > t]
-                l = int(before[-1]) if len(before) else None
-                r = int(after[0]) if len(after) else None
-                if l is not None and r is not None:
-                    if r - l - 1 <= G:
-                        w = np.float64(t - l) / np.float64(r - l)
-                        out[t, j] = (src[l, j].astype(np.float64) * (1.0 - w) + src[r, j].astype(np.float64) * w).astype(np.float32)
-                        state[t, j] = 2
-                elif r is not None:
-                    if r - t <= G:
-                        out[t, j], state[t, j] = src[r, j], 2
-                elif l is not None:
-                    if t - l <= G:
-                        out[t, j], state[t, j] = src[l, j], 2
-        repaired.append(out)
-        states.append(state)
-        frame_flags.append((state == 1).any(axis=1) & (state != 0).all(axis=1))
-    return repaired, frame_flags, states
-
-
-def repair_joints(src, lens, G, joint_flags=None):
-    """uu3d_repair_joints on the current stream.  ``src`` (R, J, 2) float32 on the device, the given frames of all tracks back to back
-    (only read); ``lens``: given frames per track; ``joint_flags`` (R, J) uint8 on the device or None -> (repaired (R, J, 2) float32,
-    frame flags (R,) uint8, joint state (R, J) uint8), fresh device buffers."""
-    import torch
-    lib = _capi.load_library()
-    dev = src.device
-    lens = np.asarray(lens, np.int64)
-    R, J = int(src.shape[0]), int(src.shape[1])
-    if int(lens.sum()) != R:
-        raise ValueError("lens must add up to the rows of src")
-    track_start = _upload(np.concatenate([[0], np.cumsum(lens)]), np.int64, dev)
-    out = torch.empty((R, J, 2), dtype=torch.float32, device=dev)
-    frame_flags = torch.empty((R,), dtype=torch.uint8, device=dev)
-    state = torch.empty((R, J), dtype=torch.uint8, device=dev)
-    nbytes = int(lib.uu3d_repair_joints_scratch_bytes(R, J))
-    if nbytes == 0:
-        raise ValueError(f"{R} frames of {J} joints are out of uu3d_repair_joints' range")
-    scratch = torch.empty((nbytes // 4,), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _capi.check(lib, lib.uu3d_repair_joints(_ptr(src), R, J, _ptr(joint_flags), _ptr(track_start), len(lens), min(int(G), 2 ** 31 - 1), _ptr(out),
-                                                _ptr(frame_flags), _ptr(state), _ptr(scratch), nbytes, C.c_void_p(stream)), None)
-    return out, frame_flags, state
-
-
-MAX_KEYPOINT_SOURCES = 8                                              # sources per model joint: the fixed stride of the device table
-
-
-class KeypointMap(object):
-    """An affine map from a detector's joints onto the model's (include/uu3d.h, ANY SKELETON): ``inputs`` = K_in joints come in; model joint
-    j is ``sum_k weights[j][k] * in[sources[j][k]]``, summed in the listed order.  ``sources``: per model joint 1 to 8 distinct indices in
-    [0, inputs); ``weights``: as many float64 weights each, finite, non-zero, summing to 1 within 1e-12 (negative ones allowed: the map is
-    affine, so it commutes, mathematically, with the screen normalisation).  Anything else is a ValueError.  ``joints`` = J = len(sources).
-    Immutable; the packed table is made once and uploaded once per device (``device_table``)."""
-
-    def __init__(self, inputs, sources, weights):
-        if isinstance(inputs, bool) or not isinstance(inputs, (int, np.integer)) or int(inputs) < 1:
-            raise ValueError(f"inputs must be an int >= 1: the joints the detector emits, got {inputs!r}")
-        sources, weights = list(sources), list(weights)
-        if len(sources) < 1 or len(sources) != len(weights):
-            raise ValueError(f"sources and weights need one entry per model joint, got {len(sources)} and {len(weights)}")
-        self.inputs, self.joints = int(inputs), len(sources)
-        src, wts = [], []
-        for j, (s, w) in enumerate(zip(sources, weights)):
-            s, w = [int(i) for i in np.asarray(s).reshape(-1)], [float(x) for x in np.asarray(w, np.float64).reshape(-1)]
-            if not 1 <= len(s) <= MAX_KEYPOINT_SOURCES or len(s) != len(w):
-                raise ValueError(f"model joint {j} needs 1 to {MAX_KEYPOINT_SOURCES} sources and as many weights, got {len(s)} and {len(w)}")
-            if len(set(s)) != len(s) or min(s) < 0 or max(s) >= self.inputs:
-                raise ValueError(f"model joint {j}: sources must be distinct indices in [0, {self.inputs}), got {s}")
-            if not all(np.isfinite(x) and x != 0.0 for x in w):
-                raise ValueError(f"model joint {j}: weights must be finite and non-zero, got {w}")
-            total = 0.0
-            for x in w:
-                total = total + x
-            if not abs(total - 1.0) <= 1e-12:
-                raise ValueError(f"model joint {j}: weights must sum to 1 (an affine map), they sum to {total!r}")
-            src.append(tuple(s))
-            wts.append(tuple(w))
-        self.sources, self.weights = tuple(src), tuple(wts)
-        self._packed, self._tables = None, {}
-
-    def planes(self):
-        """-> (counts (J,) int32, sources (J, 8) int32 with -1 behind a joint's last source, weights (J, 8) float64 with 0 there)."""
-        counts = np.array([len(s) for s in self.sources], np.int32)
-        src = np.full((self.joints, MAX_KEYPOINT_SOURCES), -1, np.int32)
-        w = np.zeros((self.joints, MAX_KEYPOINT_SOURCES), np.float64)
-        for j, (s, x) in enumerate(zip(self.sources, self.weights)):
-            src[j, :len(s)], w[j, :len(s)] = s, x
-        return counts, src, w
-
-    def packed(self):
-        """The table of uu3d_keypoint_map_pack as a host uint8 array (the library checks the map once more, the index range included)."""
-        if self._packed is None:
-            lib = _capi.load_library()
-            nbytes = int(lib.uu3d_keypoint_map_bytes(self.inputs, self.joints))
-            if nbytes == 0:
-                raise ValueError(f"a map from {self.inputs} onto {self.joints} joints is out of uu3d_keypoint_map_pack's range")
-            counts, src, w = self.planes()
-            out = np.zeros(nbytes // 8, np.float64)                   # (8-byte aligned)
-            _capi.check(lib, lib.uu3d_keypoint_map_pack(self.inputs, self.joints, counts.ctypes.data, src.ctypes.data, w.ctypes.data,
-                                                        out.ctypes.data, nbytes), None)
-            self._packed = out.view(np.uint8)
-        return self._packed
-
-    def device_table(self, device):
-        """The packed table on ``device``: uploaded at the first call, which waits for the copy once -- whatever stream uses it later finds
-        it there --, and kept for the life of the map: no call does host work per frame."""
-        import torch
-        key = str(torch.device(device))
-        if key not in self._tables:
-            self._tables[key] = _upload(self.packed(), np.uint8, device)
-            torch.cuda.current_stream(device).synchronize()
-        return self._tables[key]
-
-    def __repr__(self):
-        return f"KeypointMap(inputs={self.inputs}, joints={self.joints})"
-
-
-def _h36m17_from(inputs, r_leg, l_leg, r_arm, l_arm, pelvis, neck, torso, head, head_top):
-    """A ``KeypointMap`` onto ``H36MOrder17P``: 0-2 right ankle, knee, hip; 3-5 left hip, knee, ankle; 6 pelvis; 7 neck; 8 torso; 9 head;
-    10 head top; 11-13 right wrist, elbow, shoulder; 14-16 left shoulder, elbow, wrist.  Limbs are (ankle, knee, hip) / (wrist, elbow,
-    shoulder) source indices; the other five are (sources, weights)."""
-    one = lambda i: ((i,), (1.0,))
-    rows = [one(r_leg[0]), one(r_leg[1]), one(r_leg[2]), one(l_leg[2]), one(l_leg[1]), one(l_leg[0]), pelvis, neck, torso, head, head_top,
-            one(r_arm[0]), one(r_arm[1]), one(r_arm[2]), one(l_arm[2]), one(l_arm[1]), one(l_arm[0])]
-    return KeypointMap(inputs, [r[0] for r in rows], [r[1] for r in rows])
-
-
-# Named maps onto H36MOrder17P (J = 17), the layout of the shipped configs.  They are GEOMETRIC APPROXIMATIONS of joints the detector does
-# not emit (a pelvis between the hips, a head top beyond the eyes): the shipped weights were trained on Human3.6M 2D detections and no
-# accuracy figure is claimed for these tables -- the mechanism is the feature, the tables are a convenience.
-# Left-right consistency: mirroring the input (x negated, joints permuted by the detector's own left-right order) and then mapping gives the
-# bits of mapping and then mirroring by AUGM_FLIP_KEYPOINT_ORDER.  The sources are ORDERED for that: a mirrored pair comes first, left then
-# right (its sum, the first one of the expression, is the same either way round: a + b == b + a), unpaired sources behind it -- the nose
-# last in head_top.  The torso of "coco17" sums two pairs; mirrored, the hips arrive in the other order behind the shoulders' sum, which
-# gives the same bits wherever the float64 partial sums are exact -- four float32 coordinates within a factor of 2^26 of each other, or
-# zero -- and elsewhere the same value up to one float64 rounding, which reaches the float32 result about once in 2^29 times.
-KEYPOINT_PRESETS = {
-    # COCO-17: 0 nose, 1 l_eye, 2 r_eye, 3 l_ear, 4 r_ear, 5 l_sho, 6 r_sho, 7 l_elb, 8 r_elb, 9 l_wri, 10 r_wri, 11 l_hip, 12 r_hip,
-    # 13 l_knee, 14 r_knee, 15 l_ank, 16 r_ank
-    "coco17": _h36m17_from(17, r_leg=(16, 14, 12), l_leg=(15, 13, 11), r_arm=(10, 8, 6), l_arm=(9, 7, 5),
-                           pelvis=((11, 12), (0.5, 0.5)), neck=((5, 6), (0.5, 0.5)), torso=((5, 6, 11, 12), (0.25, 0.25, 0.25, 0.25)),
-                           head=((0,), (1.0,)), head_top=((1, 2, 0), (1.0, 1.0, -1.0))),
-    # OpenPose BODY_25: 0 Nose, 1 Neck, 2 RShoulder, 3 RElbow, 4 RWrist, 5 LShoulder, 6 LElbow, 7 LWrist, 8 MidHip, 9 RHip, 10 RKnee,
-    # 11 RAnkle, 12 LHip, 13 LKnee, 14 LAnkle, 15 REye, 16 LEye, 17 REar, 18 LEar, 19 LBigToe, 20 LSmallToe, 21 LHeel, 22 RBigToe,
-    # 23 RSmallToe, 24 RHeel
-    "body25": _h36m17_from(25, r_leg=(11, 10, 9), l_leg=(14, 13, 12), r_arm=(4, 3, 2), l_arm=(7, 6, 5),
-                           pelvis=((8,), (1.0,)), neck=((1,), (1.0,)), torso=((1, 8), (0.5, 0.5)),
-                           head=((0,), (1.0,)), head_top=((16, 15, 0), (1.0, 1.0, -1.0))),
-}
-
-
-def keypoint_map(name_or_map, J=None):
-    """``predict_tracks``' ``keypoints`` argument -> a ``KeypointMap``: a name of ``KEYPOINT_PRESETS`` or a map of your own.  ``J``: the
-    model's joint count; a map onto another number of joints is a ValueError (the presets target 17)."""
-    if isinstance(name_or_map, KeypointMap):
-        M, what = name_or_map, repr(name_or_map)
-    elif isinstance(name_or_map, str):
-        if name_or_map not in KEYPOINT_PRESETS:
-            raise ValueError(f"keypoints must be a KeypointMap or one of {sorted(KEYPOINT_PRESETS)}, got {name_or_map!r}")
-        M, what = KEYPOINT_PRESETS[name_or_map], repr(name_or_map)
-    else:
-        raise ValueError(f"keypoints must be a KeypointMap or one of {sorted(KEYPOINT_PRESETS)}, got {name_or_map!r}")
-    if J is not None and M.joints != int(J):
-        raise ValueError(f"keypoints={what} maps onto {M.joints} joints, the model has {int(J)}")
-    return M
-
-
-def check_keypoint_inputs(M, counts, what="track"):
-    """Every track (slot, array) has the K_in joints ``M`` takes: ValueError naming both numbers otherwise."""
-    for i, k in enumerate(counts):
-        if int(k) != M.inputs:
-            raise ValueError(f"{what} {i} has {int(k)} keypoints, keypoints={M!r} takes {M.inputs}")
-
-
-def _host_array(a):
-    return a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
-
-
-def map_keypoints_host(M, tracks, valid=None):
-    """The rule of ``predict_tracks(keypoints=M)`` (include/uu3d.h, ANY SKELETON) in numpy, written to be read: what uu3d_map_keypoints
-    computes, bit for bit.  ``tracks``: list of (T_i, K_in, 2) arrays; ``valid``: None, "finite" or a list with one (T_i,) or (T_i, K_in)
-    entry per track -> (mapped, flags): per track (T_i, J, 2) float32, and ``flags`` as the call behind the map takes them --
-        None            -> None: the expression alone, a NaN source gives a NaN joint;
-        (T_i, K_in)     -> (T_i, J) bool: a source is observed when its flag is non-zero and both coordinates are finite, a model joint iff
-                           every one of its sources is; an unobserved joint's coordinates are zeros ("finite": every flag set);
-        (T_i,)          -> the entry itself, unchanged: frame flags pass through, the coordinates are the expression.
-    So ``predict_tracks(model, cfg, tracks, keypoints=M, valid=V, **kw)`` equals ``predict_tracks(model, cfg, mapped, valid=flags, **kw)``."""
-    M = keypoint_map(M)
-    tracks = [np.asarray(_host_array(t), np.float32) for t in tracks]
-    check_keypoint_inputs(M, [t.shape[1] for t in tracks])
-    if valid is not None and not isinstance(valid, str):
-        check_valid(valid, [len(t) for t in tracks], joints=M.inputs)
-    elif valid is not None and valid != "finite":
-        raise ValueError('valid must be None, "finite" or a list with one entry per track')
-    mapped, flags = [], None if valid is None else []
-    for i, src in enumerate(tracks):
-        T = len(src)
-        v = None if valid is None else np.ones((T, M.inputs), bool) if isinstance(valid, str) else _host_array(valid[i]) != 0
-        per_joint = v is not None and v.ndim == 2
-        if per_joint:
-            observed = v & np.isfinite(src).all(axis=2)
-        out = np.zeros((T, M.joints, 2), np.float32)
-        joint_flags = np.zeros((T, M.joints), bool)
-        for j, (sources, weights) in enumerate(zip(M.sources, M.weights)):
-            with np.errstate(invalid="ignore", over="ignore"):
-                acc = np.float64(weights[0]) * src[:, sources[0]].astype(np.float64)
-                for s, w in zip(sources[1:], weights[1:]):
-                    acc = acc + np.float64(w) * src[:, s].astype(np.float64)
-                r = acc.astype(np.float32)
-            r[np.isnan(r)] = np.float32(np.nan)                       # THE quiet NaN 0x7fc00000, as the device stores it
-            if per_joint:
-                joint_flags[:, j] = observed[:, list(sources)].all(axis=1)
-                r[~joint_flags[:, j]] = 0.0
-            out[:, j] = r
-        mapped.append(out)
-        if flags is not None:
-            flags.append(joint_flags if per_joint else valid[i])
-    return mapped, flags
-
-
-def map_keypoints(src, flags, M, model):
-    """uu3d_map_keypoints on the current stream.  ``src`` (F, K_in, 2) float32 on the device, contiguous (only read); ``flags`` (F, K_in)
-    uint8 on the device or None; ``M``: a ``KeypointMap`` onto the joints of ``model`` (its handle says J) -> (mapped (F, J, 2) float32,
-    joint flags (F, J) uint8 or None), fresh device buffers."""
-    import torch
-    lib = _capi.load_library()
-    dev = src.device
-    F, J = int(src.shape[0]), M.joints
-    if src.dtype != torch.float32 or not src.is_contiguous() or tuple(src.shape) != (F, M.inputs, 2):
-        raise ValueError(f"src must be a contiguous (F, {M.inputs}, 2) float32 device tensor, got {tuple(src.shape)}")
-    if flags is not None and (flags.dtype != torch.uint8 or not flags.is_contiguous() or tuple(flags.shape) != (F, M.inputs)):
-        raise ValueError(f"flags must be a contiguous ({F}, {M.inputs}) uint8 device tensor")
-    if int(model.arch.num_keypoints) != J:
-        raise ValueError(f"keypoints={M!r} maps onto {J} joints, the model has {int(model.arch.num_keypoints)}")
-    table = M.device_table(dev)
-    out = torch.empty((F, J, 2), dtype=torch.float32, device=dev)
-    flags_out = None if flags is None else torch.empty((F, J), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _capi.check(lib, lib.uu3d_map_keypoints(model._h, _ptr(table), M.inputs, _ptr(src), _ptr(flags), F, _ptr(out), _ptr(flags_out),
-                                                C.c_void_p(stream)), model._h)
-    return out, flags_out
-
-
-def _map_front(M, model, src, given, valid):
-    """The map in front of everything else: the given frames of all tracks (R, K_in, 2) and ``valid`` per detector joint -> (the frames
-    (R, J, 2), ``valid`` per model joint, as ``_front_validity`` takes it).  One launch; a list that mixes (T_i, K_in) and (T_i,) entries
-    takes one launch with and one without flags, and every track the rows of its own kind."""
-    import torch
-    if model is None:
-        raise ValueError("keypoints needs the model: its handle says which joints the map must give")
-    K, dev, sizes = M.inputs, src.device, [int(n) for n in given]
-    if valid is None:
-        return map_keypoints(src, None, M, model)[0], None
-    if isinstance(valid, str):                                        # "finite": the finite test per SOURCE joint, every flag set
-        out, flags = map_keypoints(src, torch.ones((int(src.shape[0]), K), dtype=torch.uint8, device=dev), M, model)
-        return out, list(torch.split(flags, sizes, 0))
-    per_joint = [len(_shape(v)) == 2 for v in valid]
-    if not any(per_joint):                                            # frame flags pass through unchanged
-        return map_keypoints(src, None, M, model)[0], valid
-    out, flags = map_keypoints(src, _device_joint_flags(valid, K, dev), M, model)
-    flags = list(torch.split(flags, sizes, 0))
-    if all(per_joint):
-        return out, flags
-    plain = torch.split(map_keypoints(src, None, M, model)[0], sizes, 0)
-    out = torch.cat([a if p else b for p, a, b in zip(per_joint, torch.split(out, sizes, 0), plain)], 0)
-    return out, [f if p else v for p, f, v in zip(per_joint, flags, valid)]
-
-
-def _front_validity(src, given, J, valid, repair, joint_flags=None):
-    """What the front kernels take as source and ``valid_in``: as they are, or with ``repair`` = G the repaired source and the frame
-    flags of uu3d_repair_joints -> (src, valid_in, joint state or None).  ``joint_flags``: ``_source_joint_flags`` where the caller has
-    made them already."""
-    if repair is None:
-        return src, None if valid is None or isinstance(valid, str) else _device_valid(valid, src.device), None
-    return repair_joints(src, given, repair, _source_joint_flags(valid, J, src.device) if joint_flags is None else joint_flags)
-
-
-def _source_joint_flags(valid, J, device):
-    """``valid`` behind the keypoint map -> the (given frames, J) uint8 per-joint flags on the device, or None where the finite test alone
-    says which joints were observed (None, "finite")."""
-    return None if valid is None or isinstance(valid, str) else _device_joint_flags(valid, J, device)
-
-
-# ---- per-frame detections: people -> tracks (include/uu3d.h, PER-FRAME DETECTIONS) ---------------------------------------------------------
-MAX_ASSOCIATION = 64                                                  # the largest slots, detections per frame and joints (kAssocMax)
-# conveniences, not tuned values: frames a track survives without a match, the largest normalised distance, the fewest common joints
-ASSOCIATION_DEFAULTS = {"max_age": 10, "max_dist": 0.5, "min_common": 3}
-
-
-class Association(object):
-    """What ``associate_host`` (host arrays for ONE video) and ``associate_detections`` (lists with one device tensor per video) return --
-        assignment (T, D) int32   the slot of each detection, -1: none (no candidate, or dropped)
-        track_of   (T, D) int32   the track id of each detection, -1: none
-        track_ids  (T, S) int32   the track in each slot after the frame, -1: a free slot
-        born, alive (T, S) uint8  slots born at the frame; slots alive after it
-        num_tracks, dropped       ids handed out (they are 0 .. num_tracks - 1) and detections dropped for want of a free slot: ints on
-                                  the host; on the device ``counters`` (V, 2) int32 holds both per video
-    and, from ``associate_host`` only, slot_det (T, S) int32: the detection that is the slot's frame of the tick (-1: none), and slot_full
-    (T, S) bool: it has one and every joint flag of it is set."""
-
-    def __init__(self, **fields):
-        self.__dict__.update(fields)
-
-
-def check_association(slots, detections, joints, max_age, max_dist, min_common):
-    """The capacities (each in [1, 64]) and the three parameters of the rule: ValueError naming what is wrong."""
-    for name, v in (("slots", slots), ("detections per frame", detections), ("joints", joints)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= MAX_ASSOCIATION:
-            raise ValueError(f"{name} must be an int in [1, {MAX_ASSOCIATION}] (the association runs in one workgroup's LDS), got {v!r}")
-    if isinstance(max_age, bool) or not isinstance(max_age, (int, np.integer)) or int(max_age) < 0:
-        raise ValueError(f"max_age must be an int >= 0: frames a track survives without a match, got {max_age!r}")
-    if isinstance(min_common, bool) or not isinstance(min_common, (int, np.integer)) or int(min_common) < 1:
-        raise ValueError(f"min_common must be an int >= 1: joints a detection needs, and a pair needs in common, got {min_common!r}")
-    if isinstance(max_dist, bool) or not isinstance(max_dist, (int, float, np.integer, np.floating)) or not float(max_dist) >= 0.0:
-        raise ValueError(f"max_dist must be a number >= 0: the largest normalised distance of a match, got {max_dist!r}")
-
-
-def _association_options(options):
-    """max_age / max_dist / min_common out of keyword options, the defaults where one is not given -> (the three, the other options)."""
-    rest = dict(options)
-    return {k: rest.pop(k, v) for k, v in ASSOCIATION_DEFAULTS.items()}, rest
-
-
-def _detection_flags(valid, T, D, K):
-    """``valid`` of one video -> (frame flags (T, D) bool, joint flags (T, D, K) bool): None / "finite" = every flag set (the finite test
-    always applies), (T, D) = one flag per detection, (T, D, K) = one per joint."""
-    if valid is None or (isinstance(valid, str) and valid == "finite"):
-        return np.ones((T, D), bool), np.ones((T, D, K), bool)
-    v = _host_array(valid) != 0
-    if v.shape == (T, D):
-        return v, np.ones((T, D, K), bool)
-    if v.shape == (T, D, K):
-        return np.ones((T, D), bool), v
-    raise ValueError(f"valid must be None, ({T}, {D}) or ({T}, {D}, {K}), got {v.shape}")
-
-
-class AssociationHost(object):
-    """The rule of PER-FRAME DETECTIONS (include/uu3d.h) in numpy, written to be read, one frame per ``step``: the state machine that
-    uu3d_associate_detections and uu3d_stream_associate run, bit for bit.  State per slot: ``alive``, ``track`` (-1: free), ``age``
-    (consecutive frames without a match), ``ref`` (K, 2) float32 with ``seen`` (K,): the last observed position of each joint since the
-    slot's birth; ``next_id``, ``dropped``.  Greedy, no motion model, no Hungarian step: the simplest rule that can be stated exactly."""
-
-    def __init__(self, slots, detections, joints, max_age=10, max_dist=0.5, min_common=3):
-        check_association(slots, detections, joints, max_age, max_dist, min_common)
-        self.S, self.D, self.K = int(slots), int(detections), int(joints)
-        self.max_age, self.min_common = int(max_age), int(min_common)
-        self.max_dist2 = np.float64(max_dist) * np.float64(max_dist)  # the right side of the test, computed once
-        S, K = self.S, self.K
-        self.alive, self.track, self.age = np.zeros(S, bool), np.full(S, -1, np.int64), np.zeros(S, np.int64)
-        self.ref, self.seen = np.zeros((S, K, 2), np.float32), np.zeros((S, K), bool)
-        self.next_id = self.dropped = 0
-
-    def end(self, slots=None):
-        """``uu3d_associate_reset``: the tracks in the given slots end (None: all of them, and the two counters start again)."""
-        which = slice(None) if slots is None else np.asarray(slots, np.int64).reshape(-1)
-        self.alive[which], self.track[which], self.age[which], self.seen[which] = False, -1, 0, False
-        if slots is None:
-            self.next_id = self.dropped = 0
-
-    def step(self, det, count=None, frame_flag=None, joint_flag=None):
-        """One frame: ``det`` (D, K, 2) float32, ``count`` given rows (None: D), ``frame_flag`` (D,) / ``joint_flag`` (D, K) bools or None
-        -> (det_slot (D,) the assignment, slot_det (S,) the detection that is each slot's frame of this tick or -1, born (S,) bool)."""
-        S, D, K, min_common = self.S, self.D, self.K, self.min_common
-        alive, track, age, ref, seen = self.alive, self.track, self.age, self.ref, self.seen
-        det = np.asarray(det, np.float32).reshape(D, K, 2)
-        frame_flag = np.ones(D, bool) if frame_flag is None else np.asarray(frame_flag).reshape(D) != 0
-        joint_flag = np.ones((D, K), bool) if joint_flag is None else np.asarray(joint_flag).reshape(D, K) != 0
-        observed = joint_flag & np.isfinite(det).all(axis=2)
-        cand = (np.arange(D) < (D if count is None else min(max(int(count), 0), D))) & frame_flag & (observed.sum(axis=1) >= min_common)
-        # 1. the cost of every (alive slot, candidate) pair: the joint sum is an explicit left-to-right accumulation in float64 (np.sum
-        #    adds pairwise), every product and sum rounded; unobserved joints never enter it
-        cost, allowed = np.zeros((S, D), np.float64), np.zeros((S, D), bool)
-        det64, ref64 = det.astype(np.float64), ref.astype(np.float64)
-        d2, common = np.zeros((S, D), np.float64), np.zeros((S, D), np.int64)
-        with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
-            for j in range(K):
-                both = seen[:, None, j] & observed[None, :, j]
-                dx = det64[None, :, j, 0] - ref64[:, None, j, 0]
-                dy = det64[None, :, j, 1] - ref64[:, None, j, 1]
-                d2 = np.where(both, d2 + (dx * dx + dy * dy), d2)
-                common += both
-            for s in np.flatnonzero(alive & seen.any(axis=1)):
-                box = ref[s][seen[s]]                                   # the bounding box of the slot's seen reference joints
-                w = np.float64(box[:, 0].max()) - np.float64(box[:, 0].min())
-                h = np.float64(box[:, 1].max()) - np.float64(box[:, 1].min())
-                scale2 = w * w + h * h
-                if scale2 == 0:
-                    continue
-                pairs = cand & (common[s] >= min_common)
-                cost[s, pairs] = d2[s, pairs] / (common[s, pairs].astype(np.float64) * scale2)
-                allowed[s] = pairs & (cost[s] <= self.max_dist2)
-        # 2. greedy: the smallest allowed cost among unmatched slots and candidates; ties to the smaller s, then the smaller d
-        slot_det, det_slot = np.full(S, -1, np.int64), np.full(D, -1, np.int64)
-        while True:
-            open_pairs = allowed & (slot_det < 0)[:, None] & (det_slot < 0)[None, :]
-            if not open_pairs.any():
-                break
-            s, d = divmod(int(np.flatnonzero(open_pairs)[np.argmin(cost[open_pairs])]), D)      # (row-major: the first minimum)
-            slot_det[s], det_slot[d] = d, s
-        # 3. / 4. matched slots are young again; unmatched ones age and die
-        born = np.zeros(S, bool)
-        for s in np.flatnonzero(alive):
-            if slot_det[s] >= 0:
-                age[s] = 0
-            else:
-                age[s] += 1
-                if age[s] > self.max_age:
-                    alive[s], track[s], age[s], seen[s] = False, -1, 0, False
-        # 5. births: unmatched candidates in ascending d take the lowest free slot (one that has just died included)
-        for d in np.flatnonzero(cand & (det_slot < 0)):
-            free = np.flatnonzero(~alive)
-            if len(free) == 0:
-                self.dropped += 1
-                continue
-            s = int(free[0])
-            alive[s], born[s], track[s], age[s], seen[s] = True, True, self.next_id, 0, False
-            slot_det[s], det_slot[d] = d, s
-            self.next_id += 1
-        # 3. / 5. the reference pose takes the bits of the joints observed in the slot's detection
-        for s in np.flatnonzero(slot_det >= 0):
-            o = observed[slot_det[s]]
-            ref[s][o] = det[slot_det[s]][o]
-            seen[s] |= o
-        return det_slot, slot_det, born
-
-
-def associate_host(dets, counts=None, valid=None, slots=None, max_age=10, max_dist=0.5, min_common=3):
-    """``AssociationHost`` over ONE whole video: what uu3d_associate_detections computes, bit for bit.  ``dets`` (T, D, K, 2): per frame
-    the people a detector listed, in any order; ``counts`` (T,) or None = D: how many rows of each frame are given; ``valid``: None,
-    (T, D) or (T, D, K) flags; ``slots`` = S (None: D) -> an ``Association`` of host arrays."""
-    dets = np.asarray(_host_array(dets), np.float32)
-    if dets.ndim != 4 or dets.shape[3] != 2:
-        raise ValueError(f"dets must be (T, D, K, 2), got {dets.shape}")
-    T, D, K = (int(n) for n in dets.shape[:3])
-    rule = AssociationHost(D if slots is None else slots, D, K, max_age, max_dist, min_common)
-    S = rule.S
-    counts = np.full(T, D, np.int64) if counts is None else np.asarray(_host_array(counts), np.int64).reshape(-1)
-    if len(counts) != T:
-        raise ValueError(f"counts must have one entry per frame: {T} frames, {len(counts)} entries")
-    frame_flag, joint_flag = _detection_flags(valid, T, D, K)
-    out = {k: np.full((T, n), -1, np.int32) for k, n in (("assignment", D), ("track_of", D), ("track_ids", S), ("slot_det", S))}
-    out.update({k: np.zeros((T, S), np.uint8) for k in ("born", "alive")})
-    out["slot_full"] = np.zeros((T, S), bool)
-    for t in range(T):
-        det_slot, slot_det, born = rule.step(dets[t], counts[t], frame_flag[t], joint_flag[t])
-        out["assignment"][t], out["slot_det"][t], out["track_ids"][t] = det_slot, slot_det, rule.track
-        out["track_of"][t] = np.where(det_slot >= 0, rule.track[np.maximum(det_slot, 0)], -1)
-        out["born"][t], out["alive"][t] = born, rule.alive
-        out["slot_full"][t] = (slot_det >= 0) & joint_flag[t][np.maximum(slot_det, 0)].all(axis=1)
-    return Association(num_tracks=rule.next_id, dropped=rule.dropped, **out)
-
-
-def association_tracks_host(dets, valid, result):
-    """The tracks of one video out of ``associate_host``'s result, as ``predict_detections`` builds them on the device -> list of
-    (track_id, first_frame, coordinates (n, K, 2) float32, joint flags (n, K) bool), by track id: a track runs from its birth frame to
-    its last matched frame; a frame in between without a match is missing (zeros, no flag set)."""
-    dets = np.asarray(_host_array(dets), np.float32)
-    T, D, K = dets.shape[:3]
-    _, joint_flag = _detection_flags(valid, T, D, K)
-    tracks = []
-    for tid in range(result.num_tracks):
-        frames, which = np.nonzero(result.track_of == tid)
-        first, n = int(frames[0]), int(frames[-1]) - int(frames[0]) + 1
-        xy, flags = np.zeros((n, K, 2), np.float32), np.zeros((n, K), bool)
-        xy[frames - first], flags[frames - first] = dets[frames, which], joint_flag[frames, which]
-        tracks.append((tid, first, xy, flags))
-    return tracks
-
-
-def _device_detections(detections, counts, valid, device):
-    """The videos' detections on the device, back to back -> (dets (F, D, K, 2) f32, counts (F,) i32 or None, flags u8 or None, whether
-    the flags are per joint, frames per video)."""
-    import torch
-    vids = []
-    for v in detections:
-        v = v.to(device=device, dtype=torch.float32) if isinstance(v, torch.Tensor) else _upload(np.asarray(v), np.float32, device)
-        if v.dim() != 4 or v.shape[3] != 2:
-            raise ValueError(f"a video's detections must be (T, D, K, 2), got {tuple(v.shape)}")
-        vids.append(v)
-    if not vids:
-        raise ValueError("no videos")
-    D, K = int(vids[0].shape[1]), int(vids[0].shape[2])
-    if any(tuple(v.shape[1:3]) != (D, K) for v in vids):
-        raise ValueError("all videos must have the same detections per frame and joints")
-    lens = np.array([int(v.shape[0]) for v in vids], np.int64)
-    if (lens < 1).any():
-        raise ValueError("every video needs at least one frame")
-    dets = (torch.cat(vids, 0) if len(vids) > 1 else vids[0]).contiguous()
-    d_counts = None
-    if counts is not None:
-        if len(counts) != len(vids) or any(_shape(c) != (int(n),) for c, n in zip(counts, lens)):
-            raise ValueError("counts must be None or a list with one (T_v,) entry per video")
-        parts = [c.to(device=device, dtype=torch.int32) if isinstance(c, torch.Tensor) else _upload(np.asarray(c), np.int32, device) for c in counts]
-        d_counts = torch.cat(parts, 0).contiguous()
-    flags, per_joint = None, False
-    if valid is not None and not isinstance(valid, str):
-        if not isinstance(valid, (list, tuple)) or len(valid) != len(vids):
-            raise ValueError('valid must be None, "finite" or a list with one (T_v, D) or (T_v, D, K) entry per video')
-        shapes = [_shape(f) for f in valid]
-        per_joint = any(len(sh) == 3 for sh in shapes)
-        for sh, n in zip(shapes, lens):
-            if sh != (int(n), D) and sh != (int(n), D, K):
-                raise ValueError(f"an entry of valid must be ({int(n)}, {D}) or ({int(n)}, {D}, {K}), got {sh}")
-        parts = []
-        for f in valid:
-            f = ((f if f.is_cuda else f.contiguous().pin_memory().to(device, non_blocking=True)) != 0).to(torch.uint8) if isinstance(f, torch.Tensor) \
-                else _upload(np.asarray(f) != 0, np.uint8, device)
-            parts.append(f.reshape(f.shape[0], D, 1).expand(-1, -1, K) if per_joint and f.dim() == 2 else f)
-        flags = torch.cat(parts, 0).contiguous()
-    elif valid is not None and valid != "finite":
-        raise ValueError('valid must be None, "finite" or a list with one (T_v, D) or (T_v, D, K) entry per video')
-    return dets, d_counts, flags, per_joint, lens
-
-
-def associate_detections(detections, counts=None, valid=None, slots=None, max_age=10, max_dist=0.5, min_common=3, device="cuda"):
-    """``associate_host`` on the device for a list of videos (uu3d_associate_detections: one launch, one workgroup per video).
-    ``detections``: list of (T_v, D, K, 2) arrays or tensors, on the host or the device; ``counts``: None or a list of (T_v,) ints;
-    ``valid``: None, "finite" or a list of (T_v, D) / (T_v, D, K) flags -> an ``Association`` whose fields are lists with one device
-    tensor per video, and ``counters`` (V, 2) int32 on the device: (tracks, dropped) per video.  Nothing waits for the device."""
-    import torch
-    lib = _capi.load_library()
-    device = torch.device(device)
-    shape = _shape(detections[0]) if len(detections) else (0, 1, 1, 2)
-    if len(shape) == 4:
-        check_association(shape[1] if slots is None else slots, int(shape[1]), int(shape[2]), max_age, max_dist, min_common)
-    dets, d_counts, flags, per_joint, lens = _device_detections(detections, counts, valid, device)
-    F, D, K = int(dets.shape[0]), int(dets.shape[1]), int(dets.shape[2])
-    S, V = D if slots is None else int(slots), len(lens)
-    params = _capi.Uu3dAssociateParams(S, D, K, int(max_age), int(min_common), 0, float(max_dist))
-    start = _upload(np.concatenate([[0], np.cumsum(lens)]), np.int64, device)
-    state = torch.zeros((V * int(lib.uu3d_associate_state_bytes(S, K)),), dtype=torch.uint8, device=device)
-    i32 = lambda n: torch.empty((F, n), dtype=torch.int32, device=device)
-    u8 = lambda n: torch.empty((F, n), dtype=torch.uint8, device=device)
-    assignment, track_of, track_ids, born, alive = i32(D), i32(D), i32(S), u8(S), u8(S)
-    counters = torch.empty((V, 2), dtype=torch.int32, device=device)
-    with torch.cuda.device(device):
-        stream = torch.cuda.current_stream(device).cuda_stream
-        _capi.check(lib, lib.uu3d_associate_detections(C.byref(params), _ptr(dets), _ptr(d_counts), _ptr(flags), int(per_joint), _ptr(start), V, F,
-                                                       _ptr(state), _ptr(assignment), _ptr(track_of), _ptr(track_ids), _ptr(born), _ptr(alive),
-                                                       _ptr(counters), C.c_void_p(stream)), None)
-    split = lambda a: list(torch.split(a, [int(n) for n in lens], 0))
-    r = Association(assignment=split(assignment), track_of=split(track_of), track_ids=split(track_ids), born=split(born), alive=split(alive),
-                    counters=counters)
-    r._flat = (dets, flags, per_joint, lens, track_of)
-    return r
+from .roots import (DEFAULT_MIN_ROOT_JOINTS, MAX_ROOT_JOINTS, _root_lens, check_cameras, check_min_root_joints, poses_at_given_frames,  # noqa: F401
+                    root_trajectory, root_trajectory_host, solve_roots, solve_roots_host)
+from .smooth import (MAX_SMOOTH_CHANNELS, TWO_PI, OneEuro, _one_euro_rates, check_smooth, one_euro, one_euro_alpha, one_euro_host,  # noqa: F401
+                     one_euro_sample)
+from .tracks import (_device_track, _device_tracks, _host_array, _shape, _upload, assemble_tracks, check_resolutions, keyframe_count,  # noqa: F401
+                     normalize_tracks, pose_table, resample_tracks, resampled_pose_table)
+from .validity import (_device_joint_flags, _device_valid, _front_validity, _source_joint_flags, check_repair_joints, check_valid,  # noqa: F401
+                       repair_joints, repair_joints_host)
 
 
 def predict_detections(model, config, detections, counts=None, valid=None, slots=None, **options):
@@ -884,715 +133,6 @@ def predict_detections(model, config, detections, counts=None, valid=None, slots
     for (v, tid, first), *p in zip(spans, *(poses if camera is not None else (poses,))):
         out[v].append((tid, first, *p))
     return out
-
-
-# ---- absolute root position: every track in the camera's 3D space (include/uu3d.h, ABSOLUTE ROOT POSITION) -----------------------------------
-MAX_ROOT_JOINTS = 64                                                  # kRootMaxJoints
-DEFAULT_MIN_ROOT_JOINTS = 6
-
-
-def check_cameras(camera, count, per="track"):
-    """``camera``: one (fx, fy, cx, cy) or one per track (per video, for ``predict_detections``) -> (count, 4) float64, contiguous.
-    Anything else, a non-finite entry, fx <= 0 or fy <= 0 is a ValueError."""
-    try:
-        c = np.asarray(camera, np.float64)
-    except (TypeError, ValueError):
-        raise ValueError(f"camera must be one (fx, fy, cx, cy) or one per {per}, got {camera!r}") from None
-    if c.shape == (4,):
-        c = np.tile(c, (int(count), 1))
-    if c.shape != (int(count), 4):
-        raise ValueError(f"camera must be one (fx, fy, cx, cy) or one per {per} ({int(count)}), got shape {c.shape}")
-    if not np.isfinite(c).all() or not (c[:, :2] > 0).all():
-        raise ValueError("camera must be finite (fx, fy, cx, cy) with fx > 0 and fy > 0")
-    return np.ascontiguousarray(c)
-
-
-def check_min_root_joints(min_root_joints):
-    if isinstance(min_root_joints, bool) or not isinstance(min_root_joints, (int, np.integer)) or int(min_root_joints) < 2:
-        raise ValueError(f"min_root_joints must be an int >= 2: the fewest used joints a frame's root is solved from, got {min_root_joints!r}")
-    return int(min_root_joints)
-
-
-def _root_lens(lens, frames):
-    """Frames per track of a root call (None: one track) -> int64 array that adds up to ``frames``."""
-    lens = np.array([int(frames)], np.int64) if lens is None else np.asarray(lens, np.int64).reshape(-1)
-    if (lens < 0).any() or int(lens.sum()) != int(frames):
-        raise ValueError(f"lens must add up to the {int(frames)} frames given")
-    return lens
-
-
-def solve_roots_host(poses, kp2d, camera, flags=None, min_root_joints=DEFAULT_MIN_ROOT_JOINTS, lens=None):
-    """The per-frame rule of ABSOLUTE ROOT POSITION (include/uu3d.h) in numpy, written to be read: what uu3d_solve_roots computes, bit for
-    bit.  ``poses`` (G, J, 3): the 3D pose of every frame, root-relative or not; ``kp2d`` (G, J, 2): the 2D keypoints it was uplifted from,
-    raw, in the model's joint layout; ``camera``: (fx, fy, cx, cy) in the units of ``kp2d``, one or -- with ``lens``, frames per track --
-    one per track; ``flags``: None or (G, J), non-zero = the joint was observed (non-finite coordinates are never used)
-    -> (roots (G, 3) float64, solved (G,) bool); the root of a frame that is not solved is zeros.
-    Everything in float64, every product and sum rounded; the sums run over the used joints in ascending order as a plain loop (np.sum
-    adds pairwise, np.dot in BLAS's order)."""
-    P = np.asarray(_host_array(poses), np.float32)
-    uv = np.asarray(_host_array(kp2d), np.float32)
-    if P.ndim != 3 or P.shape[2] != 3 or uv.shape != P.shape[:2] + (2,):
-        raise ValueError(f"poses must be (G, J, 3) and kp2d (G, J, 2), got {P.shape} and {uv.shape}")
-    G, J = P.shape[:2]
-    m = check_min_root_joints(min_root_joints)
-    lens = _root_lens(lens, G)
-    cam = np.repeat(check_cameras(camera, len(lens)), lens, axis=0)      # (G, 4): the camera of each frame's track
-    fx, fy, cx, cy = cam[:, 0], cam[:, 1], cam[:, 2], cam[:, 3]
-    used = np.isfinite(uv).all(axis=2)
-    if flags is not None:
-        f = np.asarray(_host_array(flags)) != 0
-        if f.shape != (G, J):
-            raise ValueError(f"flags must be ({G}, {J}), got {f.shape}")
-        used &= f
-    P64, uv64 = P.astype(np.float64), uv.astype(np.float64)
-    n = np.zeros(G, np.int64)
-    Sa, Sb, Sq, Sp, Sk, Sr = (np.zeros(G, np.float64) for _ in range(6))
-    with np.errstate(all="ignore"):
-        for j in range(J):
-            X, Y, Z = P64[:, j, 0], P64[:, j, 1], P64[:, j, 2]
-            a = (uv64[:, j, 0] - cx) / fx
-            b = (uv64[:, j, 1] - cy) / fy
-            p = a * Z - X
-            q = b * Z - Y
-            u = used[:, j]
-            n += u
-            Sa = np.where(u, Sa + a, Sa)
-            Sb = np.where(u, Sb + b, Sb)
-            Sq = np.where(u, Sq + (a * a + b * b), Sq)
-            Sp = np.where(u, Sp + p, Sp)
-            Sk = np.where(u, Sk + q, Sk)
-            Sr = np.where(u, Sr + (a * p + b * q), Sr)
-        nd = n.astype(np.float64)
-        den = Sq - (Sa * Sa + Sb * Sb) / nd
-        num = (Sa * Sp + Sb * Sk) / nd - Sr
-        Tz = num / den
-        Tx = (Sp + Sa * Tz) / nd
-        Ty = (Sk + Sb * Tz) / nd
-        solved = (n >= m) & (den > 0) & np.isfinite(Tx) & np.isfinite(Ty) & np.isfinite(Tz) & (Tz > 0)
-        for j in range(J):                                            # every used joint in front of the camera
-            solved &= ~used[:, j] | (P64[:, j, 2] + Tz > 0)
-    roots = np.zeros((G, 3), np.float64)
-    roots[solved] = np.stack([Tx, Ty, Tz], axis=1)[solved]
-    return roots, solved
-
-
-def root_trajectory_host(roots, solved, lens=None, positions=None):
-    """The trajectory rule of ABSOLUTE ROOT POSITION in numpy, written to be read: what uu3d_root_trajectory computes, bit for bit.
-    ``roots`` (G, 3) float64 and ``solved`` (G,) of ``solve_roots_host``, the given frames of all tracks back to back, ``lens`` of them
-    per track (None: one track); ``positions``: (track, num, den) of ``given_positions`` -- returned frame i sits at given-frame position
-    num / den of its track -- or None: every given frame itself -> (roots (R, 3) float32, root_state (R,) uint8: 1 solved here, 2
-    interpolated or held, 0 the track has no solved frame).  Nothing crosses a track boundary."""
-    roots = np.asarray(roots, np.float64).reshape(-1, 3)
-    solved = np.asarray(solved).reshape(-1) != 0
-    lens = _root_lens(lens, len(roots))
-    start = np.concatenate([[0], np.cumsum(lens)])
-    if positions is None:
-        positions = given_positions(lens)
-    base, _, _ = root_plan(lens, positions)                             # (the range checks of the device call)
-    out = np.zeros((len(base), 3), np.float32)
-    state = np.zeros(len(base), np.uint8)
-    for i, (t, num, den) in enumerate(zip(*(np.asarray(a).tolist() for a in positions))):
-        seen = np.flatnonzero(solved[start[t]:start[t + 1]])          # the track's solved frames, by their index in the track
-        b = num // den
-        before, after = seen[seen <= b], seen[seen > b]
-        L = int(before[-1]) if len(before) else None
-        R = int(after[0]) if len(after) else None
-        if L == b and num == b * den:
-            out[i], state[i] = roots[start[t] + L].astype(np.float32), 1
-        elif L is not None and R is not None:
-            w = np.float64(num - L * den) / np.float64((R - L) * den)
-            out[i], state[i] = (roots[start[t] + L] * (1.0 - w) + roots[start[t] + R] * w).astype(np.float32), 2
-        elif L is not None or R is not None:
-            out[i], state[i] = roots[start[t] + (L if L is not None else R)].astype(np.float32), 2
-    return out, state
-
-
-def solve_roots(poses, kp2d, camera, flags=None, min_root_joints=DEFAULT_MIN_ROOT_JOINTS, lens=None):
-    """uu3d_solve_roots on the current stream: ``solve_roots_host`` on device tensors, one launch, nothing copies to the host or waits.
-    ``poses`` (G, J, 3) float32 and ``kp2d`` (G, J, 2) float32 on the device, contiguous (only read); ``camera``: (fx, fy, cx, cy), one or
-    one per track with ``lens`` (frames per track); ``flags`` (G, J) uint8 / bool on the device or None
-    -> (roots (G, 3) float64, solved (G,) bool), fresh device buffers.  ``poses + roots[:, None]`` stands in the camera's space.
-    The live form is ``StreamSession(camera=...)``: every push returns the roots beside the poses, at any ``lookahead`` (the session keeps
-    the raw frames an emitted pose belongs to); at ``lookahead=0`` a solved root of it is this call on the push's poses and frame."""
-    import torch
-    lib = _capi.load_library()
-    dev = poses.device
-    if poses.dim() != 3 or poses.shape[2] != 3 or poses.dtype != torch.float32 or not poses.is_contiguous() or not poses.is_cuda:
-        raise ValueError(f"poses must be a contiguous (G, J, 3) float32 device tensor, got {tuple(poses.shape)}")
-    G, J = int(poses.shape[0]), int(poses.shape[1])
-    if tuple(kp2d.shape) != (G, J, 2) or kp2d.dtype != torch.float32 or not kp2d.is_contiguous() or kp2d.device != dev:
-        raise ValueError(f"kp2d must be a contiguous ({G}, {J}, 2) float32 tensor on the poses' device, got {tuple(kp2d.shape)}")
-    if flags is not None:
-        if tuple(flags.shape) != (G, J) or flags.dtype not in (torch.uint8, torch.bool) or not flags.is_contiguous() or flags.device != dev:
-            raise ValueError(f"flags must be a contiguous ({G}, {J}) uint8 or bool tensor on the poses' device")
-        flags = flags.view(torch.uint8)
-    m = check_min_root_joints(min_root_joints)
-    lens = _root_lens(lens, G)
-    cams = _upload(check_cameras(camera, len(lens)), np.float64, dev)
-    row_track = None if len(lens) == 1 else _upload(np.repeat(np.arange(len(lens), dtype=np.int32), lens), np.int32, dev)
-    roots = torch.empty((G, 3), dtype=torch.float64, device=dev)
-    solved = torch.empty((G,), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _capi.check(lib, lib.uu3d_solve_roots(_ptr(poses), _ptr(kp2d), _ptr(flags), G, J, _ptr(row_track), len(lens), _ptr(cams), m, _ptr(roots),
-                                              _ptr(solved), C.c_void_p(stream)), None)
-    return roots, solved.view(torch.bool)
-
-
-def root_trajectory(roots, solved, lens=None, positions=None):
-    """uu3d_root_trajectory on the current stream: ``root_trajectory_host`` on the device tensors of ``solve_roots``; the plan
-    (``root_plan``) is made on the host in exact integers and goes up pinned and asynchronously -> (roots (R, 3) float32, root_state (R,)
-    uint8), fresh device buffers."""
-    import torch
-    lib = _capi.load_library()
-    dev = roots.device
-    G = int(roots.shape[0])
-    if tuple(roots.shape) != (G, 3) or roots.dtype != torch.float64 or not roots.is_contiguous() or not roots.is_cuda or G < 1:
-        raise ValueError(f"roots must be a contiguous (G, 3) float64 device tensor, got {tuple(roots.shape)}")
-    if tuple(solved.shape) != (G,) or solved.dtype not in (torch.uint8, torch.bool) or not solved.is_contiguous() or solved.device != dev:
-        raise ValueError(f"solved must be a contiguous ({G},) uint8 or bool tensor on the roots' device")
-    lens = _root_lens(lens, G)
-    base, wnum, wden = root_plan(lens, positions)
-    R = len(base)
-    if R < 1:
-        raise ValueError("no returned frames")
-    track_start = _upload(np.concatenate([[0], np.cumsum(lens)]), np.int64, dev)
-    d_plan = _upload(np.stack([base, wnum, wden]), np.int64, dev)
-    out = torch.empty((R, 3), dtype=torch.float32, device=dev)
-    state = torch.empty((R,), dtype=torch.uint8, device=dev)
-    nbytes = int(lib.uu3d_root_trajectory_scratch_bytes(G))
-    if nbytes == 0:
-        raise ValueError(f"{G} given frames are out of uu3d_root_trajectory's range")
-    scratch = torch.empty((nbytes // 4,), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _capi.check(lib, lib.uu3d_root_trajectory(_ptr(roots), _ptr(solved.view(torch.uint8)), G, _ptr(track_start), len(lens), _ptr(d_plan[0]),
-                                                  _ptr(d_plan[1]), _ptr(d_plan[2]), R, _ptr(out), _ptr(state), _ptr(scratch), nbytes,
-                                                  C.c_void_p(stream)), None)
-    return out, state
-
-
-# ---- steady output: the One-Euro filter over the returned poses and roots (include/uu3d.h, STEADY OUTPUT) ------------------------------------
-MAX_SMOOTH_CHANNELS = 1 << 16                                         # kSmoothMaxChannels
-TWO_PI = 6.283185307179586
-
-
-class OneEuro(object):
-    """A One-Euro filter (Casiez, Roussel, Vogel 2012): ``min_cutoff`` > 0 in Hz, the cut-off of a channel at rest; ``beta`` >= 0 in 1 / unit
-    speed, how fast the cut-off rises with the channel's speed; ``d_cutoff`` > 0 in Hz, the cut-off of the speed estimate.  Anything else,
-    or a non-finite value, is a ValueError.  The defaults are conveniences for metres and seconds; they are not tuned and claim nothing."""
-    __slots__ = ("min_cutoff", "beta", "d_cutoff")
-
-    def __init__(self, min_cutoff=1.0, beta=0.5, d_cutoff=1.0):
-        try:
-            values = tuple(float(v) for v in (min_cutoff, beta, d_cutoff))
-        except (TypeError, ValueError):
-            raise ValueError(f"OneEuro takes three numbers, got {(min_cutoff, beta, d_cutoff)!r}") from None
-        if not all(np.isfinite(values)) or values[0] <= 0 or values[1] < 0 or values[2] <= 0:
-            raise ValueError(f"OneEuro needs finite min_cutoff > 0, beta >= 0 and d_cutoff > 0, got {values}")
-        self.min_cutoff, self.beta, self.d_cutoff = values
-
-    def __repr__(self):
-        return f"OneEuro(min_cutoff={self.min_cutoff!r}, beta={self.beta!r}, d_cutoff={self.d_cutoff!r})"
-
-    def __eq__(self, other):
-        return isinstance(other, OneEuro) and tuple(self) == tuple(other)
-
-    def __hash__(self):
-        return hash(tuple(self))
-
-    def __iter__(self):
-        return iter((self.min_cutoff, self.beta, self.d_cutoff))
-
-
-def check_smooth(smooth, placed):
-    """``smooth`` of ``predict_tracks`` / ``StreamSession`` -> (pose filter, root filter), each a ``OneEuro`` or None.  None: no filter;
-    True: the defaults; a ``OneEuro``: that filter -- both for the poses and, where the call has a ``camera`` (``placed``), the roots; a
-    pair (pose_filter, root_filter), either of which may be None: exactly those, and a root filter without ``camera`` is a ValueError."""
-    if smooth is None or smooth is False:
-        return None, None
-    if smooth is True:
-        smooth = OneEuro()
-    if isinstance(smooth, OneEuro):
-        return smooth, (smooth if placed else None)
-    if isinstance(smooth, (tuple, list)) and len(smooth) == 2 and all(f is None or isinstance(f, OneEuro) for f in smooth):
-        if smooth[1] is not None and not placed:
-            raise ValueError("a root filter needs camera=(fx, fy, cx, cy): without it the call returns no roots")
-        return smooth[0], smooth[1]
-    raise ValueError(f"smooth must be None, True, a OneEuro or a pair (pose_filter, root_filter) of OneEuro / None, got {smooth!r}")
-
-
-def _one_euro_rates(rate, tracks):
-    """``rate``: one sample rate in Hz or one per track, each as ``frame_rate`` takes it -> (tracks,) float64, each the exact rate rounded once."""
-    many = isinstance(rate, (list, np.ndarray)) or (isinstance(rate, tuple) and not (len(rate) == 2 and all(isinstance(v, (int, np.integer)) for v in rate)))
-    rates = [frame_rate(v) for v in rate] if many else [frame_rate(rate)] * int(tracks)
-    if len(rates) != int(tracks):
-        raise ValueError(f"rate must be one rate or one per track ({int(tracks)}), got {len(rates)}")
-    return np.array([float(r) for r in rates], np.float64)
-
-
-def one_euro_alpha(fc, r):
-    """alpha(fc, r) = 1 / (1 + r / (2 pi fc)): the weight of the new sample at cut-off ``fc`` and sample rate ``r``, both in Hz (float64)."""
-    return 1.0 / (1.0 + r / (TWO_PI * fc))
-
-
-def one_euro_sample(x, r, filt, xh, dxh):
-    """One later sample ``x`` of a channel at sample rate ``r`` -> (xh, dxh).  float64 scalars or arrays of channels alike; every operation
-    is one IEEE operation, in the order written (what csrc/uu3d_smooth.h does, statement for statement)."""
-    dx = (x - xh) * r
-    ad = one_euro_alpha(filt.d_cutoff, r)
-    dxh = ad * dx + (1.0 - ad) * dxh
-    a = one_euro_alpha(filt.min_cutoff + filt.beta * np.abs(dxh), r)
-    xh = a * x + (1.0 - a) * xh
-    return xh, dxh
-
-
-def one_euro_host(x, lens, rate, filt, state=None):
-    """The rule of STEADY OUTPUT (include/uu3d.h) in numpy, written to be read: what uu3d_one_euro_tracks computes, bit for bit.
-    ``x`` (G, ...) float32: the rows of all tracks back to back, everything behind the first axis is the C channels of a row; ``lens``:
-    rows per track (None: one track); ``rate``: the rows' rate in Hz, one or one per track (as ``rates.frame_rate`` takes it); ``filt``: a
-    ``OneEuro``; ``state``: None or (G,), 0 = the row is passed through unchanged and takes no sample (a root that was never solved)
-    -> the filtered rows, float32, the shape of ``x``.
-    Per channel: the first sample is returned as given; a later one moves xh towards it by ``one_euro_sample``; the output is xh rounded
-    once.  A non-finite value is passed through and touches no state.  Rows are walked in a plain loop; the channels of a row are
-    independent, so they go through numpy's element-wise float64 operations side by side."""
-    X = np.asarray(_host_array(x), np.float32)
-    G = int(X.shape[0])
-    flat = X.reshape(G, -1)
-    if not isinstance(filt, OneEuro):
-        raise ValueError(f"filt must be a OneEuro, got {filt!r}")
-    lens = _root_lens(lens, G)
-    rates = _one_euro_rates(rate, len(lens))
-    keep = np.ones(G, bool) if state is None else np.asarray(_host_array(state)).reshape(-1) != 0
-    if len(keep) != G:
-        raise ValueError(f"state must be ({G},)")
-    out = flat.copy()
-    first = 0
-    with np.errstate(all="ignore"):
-        for n, r in zip(lens.tolist(), rates):
-            xh = np.zeros(flat.shape[1], np.float64)
-            dxh = np.zeros(flat.shape[1], np.float64)
-            taken = np.zeros(flat.shape[1], bool)
-            for i in range(first, first + n):
-                if not keep[i]:
-                    continue
-                v = flat[i].astype(np.float64)
-                ok = np.isfinite(v)
-                nxh, ndxh = one_euro_sample(v, r, filt, xh, dxh)
-                later = ok & taken
-                start = ok & ~taken
-                xh = np.where(later, nxh, np.where(start, v, xh))
-                dxh = np.where(later, ndxh, np.where(start, 0.0, dxh))
-                taken |= ok
-                out[i] = np.where(ok, xh.astype(np.float32), flat[i])
-            first += n
-    return out.reshape(X.shape)
-
-
-def one_euro(x, lens, rate, filt, state=None):
-    """uu3d_one_euro_tracks on the current stream: ``one_euro_host`` on a device tensor, one launch, nothing copies to the host or waits
-    (the per-track plan -- first row, length, rate -- is made on the host and goes up pinned and asynchronously).  ``x``: a contiguous
-    (G, ...) float32 device tensor, only read; ``state``: None or a contiguous (G,) uint8 / bool device tensor
-    -> the filtered rows, a fresh device tensor of ``x``'s shape.  One lane per (track, channel) walks the track's rows in order."""
-    import torch
-    lib = _capi.load_library()
-    if not isinstance(x, torch.Tensor) or x.dim() < 1 or x.dtype != torch.float32 or not x.is_contiguous() or not x.is_cuda:
-        raise ValueError("x must be a contiguous (G, ...) float32 device tensor")
-    if not isinstance(filt, OneEuro):
-        raise ValueError(f"filt must be a OneEuro, got {filt!r}")
-    dev = x.device
-    G = int(x.shape[0])
-    Cn = int(x.numel() // G) if G else int(np.prod(x.shape[1:], dtype=np.int64))
-    if not 1 <= Cn <= MAX_SMOOTH_CHANNELS:
-        raise ValueError(f"a row must have 1 to {MAX_SMOOTH_CHANNELS} channels, got {Cn}")
-    lens = _root_lens(lens, G)
-    rates = _one_euro_rates(rate, len(lens))
-    if state is not None:
-        if tuple(state.shape) != (G,) or state.dtype not in (torch.uint8, torch.bool) or not state.is_contiguous() or state.device != dev:
-            raise ValueError(f"state must be a contiguous ({G},) uint8 or bool tensor on x's device")
-        state = state.view(torch.uint8)
-    out = torch.empty_like(x)
-    if G == 0:
-        return out
-    plan = _upload(np.stack([np.concatenate([[0], np.cumsum(lens)[:-1]]), lens]), np.int64, dev)
-    d_rates = _upload(rates, np.float64, dev)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _capi.check(lib, lib.uu3d_one_euro_tracks(_ptr(x), _ptr(out), G, Cn, _ptr(plan[0]), _ptr(plan[1]), _ptr(d_rates), len(lens), _ptr(state),
-                                                  filt.min_cutoff, filt.beta, filt.d_cutoff, C.c_void_p(stream)), None)
-    return out
-
-
-# ---- constant bone lengths: rigid skeletons over a track (include/uu3d.h, CONSTANT BONE LENGTHS) -----------------------------------------------
-MAX_BONE_JOINTS = 64                                                  # kBonesMaxJoints
-
-
-class Skeleton(object):
-    """The tree of a joint layout: ``parents`` is a length-J integer sequence, ``parents[j]`` the joint that joint j hangs on and -1 for the
-    ONE tree root; every other entry in [0, J), no cycles, J <= 64.  Anything else is a ValueError.  Derived --
-        ``root``    the tree root;
-        ``order``   all joints, every parent in front of its children: again and again the lowest joint whose parent is placed already;
-        ``paths``   per joint j the non-root joints on the way from the root down to j, j included, root side first (the root's is empty);
-        ``depth``   the longest path (at least 1: the second dimension of the device table).
-    Immutable; the tables are made once and uploaded once per device (``device_tables``), as a ``KeypointMap``'s."""
-
-    def __init__(self, parents):
-        try:
-            a = np.asarray(parents)
-        except (TypeError, ValueError):
-            raise ValueError(f"Skeleton takes a sequence of J parent indices, got {parents!r}") from None
-        if a.ndim != 1 or a.dtype.kind not in "iu" or not 1 <= len(a) <= MAX_BONE_JOINTS:
-            raise ValueError(f"Skeleton takes a sequence of 1 to {MAX_BONE_JOINTS} integer parent indices (J <= {MAX_BONE_JOINTS}), got "
-                             f"{'shape ' + str(a.shape) + ' of ' + str(a.dtype) if a.ndim else repr(parents)}")
-        p = [int(v) for v in a]
-        J = len(p)
-        roots = [j for j, v in enumerate(p) if v == -1]
-        if len(roots) != 1:
-            raise ValueError(f"Skeleton needs exactly one -1, the tree root, got {len(roots)}")
-        for j, v in enumerate(p):
-            if v != -1 and not 0 <= v < J:
-                raise ValueError(f"Skeleton: the parent of joint {j} must be -1 or in [0, {J}), got {v}")
-        paths = []
-        for j in range(J):
-            up, a_ = [], j
-            while p[a_] != -1:
-                up.append(a_)
-                a_ = p[a_]
-                if len(up) > J:
-                    raise ValueError(f"Skeleton: joint {j} never reaches the root: the parents form a cycle")
-            paths.append(tuple(reversed(up)))
-        placed, order = {roots[0]}, [roots[0]]
-        while len(order) < J:
-            nxt = min(j for j in range(J) if j not in placed and p[j] in placed)
-            placed.add(nxt)
-            order.append(nxt)
-        self.parents, self.joints, self.root = tuple(p), J, roots[0]
-        self.order, self.paths = tuple(order), tuple(paths)
-        self.depth = max(1, max(len(q) for q in paths))
-        self._tables = {}
-
-    def tables(self):
-        """-> (parents (J,) int32, paths (J, depth) int32 with -1 behind a joint's last entry): what the device reads."""
-        paths = np.full((self.joints, self.depth), -1, np.int32)
-        for j, q in enumerate(self.paths):
-            paths[j, :len(q)] = q
-        return np.array(self.parents, np.int32), paths
-
-    def device_tables(self, device):
-        """The two tables on ``device``: uploaded at the first call, which waits for the copy once -- whatever stream uses them later finds
-        them there --, and kept for the life of the skeleton."""
-        import torch
-        key = str(torch.device(device))
-        if key not in self._tables:
-            parents, paths = self.tables()
-            both = _upload(np.concatenate([parents, paths.reshape(-1)]), np.int32, device)
-            torch.cuda.current_stream(device).synchronize()
-            self._tables[key] = (both[:self.joints], both[self.joints:].view(self.joints, self.depth))
-        return self._tables[key]
-
-    def __repr__(self):
-        return f"Skeleton(joints={self.joints}, root={self.root})"
-
-
-# The tree of H36MOrder17P (the layout of ``_h36m17_from``), the pelvis as root: right leg ankle -> knee -> hip -> pelvis, left leg
-# likewise, spine torso -> pelvis, neck -> torso, head -> neck, head top -> head, arms wrist -> elbow -> shoulder -> neck.  It commutes
-# with AUGM_FLIP_KEYPOINT_ORDER: parents[flip[j]] == flip[parents[j]].
-SKELETONS = {
-    "h36m17": Skeleton([1, 2, 6, 6, 3, 4, -1, 8, 6, 7, 9, 12, 13, 7, 7, 14, 15]),
-}
-
-
-def skeleton_of(skeleton, J=None):
-    """A name of ``SKELETONS`` or a ``Skeleton`` -> the ``Skeleton``; ``J``: the joint count it must have (ValueError naming ``Skeleton``)."""
-    if isinstance(skeleton, str):
-        if skeleton not in SKELETONS:
-            raise ValueError(f"skeleton must be a Skeleton or one of {sorted(SKELETONS)}, got {skeleton!r}")
-        sk, what = SKELETONS[skeleton], repr(skeleton)
-    elif isinstance(skeleton, Skeleton):
-        sk, what = skeleton, repr(skeleton)
-    else:
-        raise ValueError(f"skeleton must be a Skeleton or one of {sorted(SKELETONS)}, got {skeleton!r}")
-    if J is not None and sk.joints != int(J):
-        raise ValueError(f"the skeleton {what} has {sk.joints} joints, the poses have {int(J)}: describe the layout's tree with "
-                         f"predict.Skeleton(parents) and pass predict.Bones(lengths, skeleton=...)")
-    return sk
-
-
-class Bones(object):
-    """``bones=`` with a tree of your own: ``lengths`` is "track" (measure every track, or slot, itself), a (J,) array of lengths in the
-    poses' units, indexed by CHILD joint (the root's entry is ignored), or a list of such arrays, one per track or slot; ``skeleton``: a
-    name of ``SKELETONS`` or a ``Skeleton``."""
-    __slots__ = ("lengths", "skeleton")
-
-    def __init__(self, lengths="track", skeleton="h36m17"):
-        self.lengths, self.skeleton = lengths, skeleton_of(skeleton)
-
-    def __repr__(self):
-        return f"Bones(lengths={self.lengths!r}, skeleton={self.skeleton!r})"
-
-
-def check_bones(bones, count, J, root=None, per="track"):
-    """``bones`` of ``predict_tracks`` / ``StreamSession`` -> None (no fix) or (skeleton, lengths): lengths None for "track", else a
-    (count, J) float64 array, the root's column 0.  ``J``: the joints of the poses; ``root``: the joint that is subtracted from the returned
-    poses, or None when they are not root-relative -- the tree root must be that joint, so that it stays exactly 0."""
-    if bones is None:
-        return None
-    b = bones if isinstance(bones, Bones) else Bones.__new__(Bones)
-    if not isinstance(bones, Bones):
-        b.lengths, b.skeleton = bones, "h36m17"
-    sk = skeleton_of(b.skeleton, J)
-    if root is not None and sk.root != int(root):
-        raise ValueError(f"bones: the tree root of the skeleton is joint {sk.root}, but the poses are relative to joint {int(root)} "
-                         f"(ROOT_KEYTPOINT): rebuilt from another root, that joint would not stay 0")
-    if isinstance(b.lengths, str):
-        if b.lengths != "track":
-            raise ValueError(f'bones must be None, "track", a ({int(J)},) array of lengths, one such array per {per} or a predict.Bones, got {b.lengths!r}')
-        return sk, None
-    try:
-        L = np.array([np.asarray(_host_array(v), np.float64) for v in b.lengths] if isinstance(b.lengths, (list, tuple)) and len(b.lengths)
-                     and np.ndim(b.lengths[0]) else _host_array(b.lengths), np.float64)
-    except (TypeError, ValueError):
-        raise ValueError(f'bones must be None, "track", a ({int(J)},) array of lengths, one such array per {per} or a predict.Bones') from None
-    if L.shape == (int(J),):
-        L = np.tile(L, (int(count), 1))
-    if L.shape != (int(count), int(J)):
-        raise ValueError(f"bones: the lengths must be ({int(J)},) or one such array per {per} ({int(count)}), got shape {L.shape}")
-    L = np.ascontiguousarray(L)
-    L[:, sk.root] = 0.0
-    return sk, L
-
-
-def _bone_offsets(X, sk):
-    """(G, J, 3) float32 poses -> (d (G, J, 3) float64: x[j] - x[parent of j], zeros for the root; len (G, J) float64)."""
-    X64 = X.astype(np.float64)
-    par = np.array(sk.parents, np.int64)
-    d = X64 - X64[:, np.where(par >= 0, par, np.arange(sk.joints))]
-    return X64, d, np.sqrt((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2])
-
-
-def _bone_poses(poses, skeleton):
-    X = np.asarray(_host_array(poses), np.float32)
-    if X.ndim != 3 or X.shape[2] != 3:
-        raise ValueError(f"poses must be (G, J, 3), got {X.shape}")
-    return X, skeleton_of(skeleton, X.shape[1])
-
-
-def bone_lengths_host(poses, lens=None, skeleton="h36m17", return_counts=False):
-    """The length rule of CONSTANT BONE LENGTHS (include/uu3d.h) in numpy, written to be read: what uu3d_bone_lengths computes, bit for
-    bit.  ``poses`` (G, J, 3) float32: the rows of all tracks back to back; ``lens``: rows per track (None: one track)
-    -> lengths (tracks, J) float64, indexed by CHILD joint: the mean of the bone's length over the track's frames where it is finite
-    and > 0, summed in ascending frame order as a plain loop (np.sum adds pairwise); NaN where there is no such frame ("not corrected");
-    0 for the tree root.  ``return_counts``: -> (lengths, counts (tracks, J) int64)."""
-    X, sk = _bone_poses(poses, skeleton)
-    lens = _root_lens(lens, len(X))
-    is_bone = np.array(sk.parents) >= 0
-    L, N = np.zeros((len(lens), sk.joints), np.float64), np.zeros((len(lens), sk.joints), np.int64)
-    with np.errstate(all="ignore"):
-        _, _, ln = _bone_offsets(X, sk)
-        first = 0
-        for t, n in enumerate(lens.tolist()):
-            total, count = np.zeros(sk.joints, np.float64), np.zeros(sk.joints, np.int64)
-            for i in range(first, first + n):
-                ok = is_bone & np.isfinite(ln[i]) & (ln[i] > 0)
-                total = np.where(ok, total + ln[i], total)
-                count += ok
-            L[t] = np.where(is_bone, np.where(count > 0, total / count.astype(np.float64), np.nan), 0.0)
-            N[t] = count
-            first += n
-    return (L, N) if return_counts else L
-
-
-def _bone_length_table(lengths, tracks, J):
-    L = np.asarray(_host_array(lengths), np.float64)
-    if L.shape == (J,):
-        L = np.tile(L, (tracks, 1))
-    if L.shape != (tracks, J):
-        raise ValueError(f"lengths must be ({J},) or ({tracks}, {J}): one row per track, got {L.shape}")
-    return np.ascontiguousarray(L)
-
-
-def fix_bones_host(poses, lens, lengths, skeleton="h36m17"):
-    """The fix of CONSTANT BONE LENGTHS in numpy, written to be read: what uu3d_fix_bones computes, bit for bit.  ``poses`` (G, J, 3)
-    float32, ``lens`` as ``bone_lengths_host``; ``lengths`` (J,) or (tracks, J) float64 by child joint -> the rebuilt poses, float32.
-    The root keeps its bits.  Every other joint j: acc = x[root] widened, then per joint a on ``skeleton.paths[j]``, root side first,
-    ``acc = acc + d(a) * s(a)`` with ``s(a) = L[a] / len(a)`` where L[a] and len(a) are finite and > 0, else 1.0; the result is acc
-    rounded once.  A product and a sum are two roundings (no fused multiply-add); the joints of a path are a plain loop."""
-    X, sk = _bone_poses(poses, skeleton)
-    lens = _root_lens(lens, len(X))
-    L = np.repeat(_bone_length_table(lengths, len(lens), sk.joints), lens, axis=0)        # (G, J): the lengths of each row's track
-    out = X.copy()
-    with np.errstate(all="ignore"):
-        X64, d, ln = _bone_offsets(X, sk)
-        ok = np.isfinite(L) & (L > 0) & np.isfinite(ln) & (ln > 0)
-        s = np.where(ok, L / np.where(ok, ln, 1.0), 1.0)
-        for j in sk.order[1:]:
-            acc = X64[:, sk.root].copy()
-            for a in sk.paths[j]:
-                acc = acc + d[:, a] * s[:, a, None]
-            out[:, j] = acc.astype(np.float32)
-    return out
-
-
-def _bone_device_poses(poses, skeleton):
-    import torch
-    if not isinstance(poses, torch.Tensor) or poses.dim() != 3 or poses.shape[2] != 3 or poses.dtype != torch.float32 or not poses.is_contiguous() \
-            or not poses.is_cuda:
-        raise ValueError(f"poses must be a contiguous (G, J, 3) float32 device tensor, got {tuple(getattr(poses, 'shape', ()))}")
-    return skeleton_of(skeleton, int(poses.shape[1]))
-
-
-def bone_lengths(poses, lens=None, skeleton="h36m17", return_counts=False):
-    """uu3d_bone_lengths on the current stream: ``bone_lengths_host`` on a device tensor, one launch, nothing copies to the host or waits
-    (the per-track plan goes up pinned and asynchronously).  ``poses``: a contiguous (G, J, 3) float32 device tensor, only read
-    -> lengths (tracks, J) float64 on the device (``return_counts``: and counts (tracks, J) int64).  Also the calibration helper: the
-    lengths of one recording are what ``bones=`` takes for the next."""
-    import torch
-    sk = _bone_device_poses(poses, skeleton)
-    lib = _capi.load_library()
-    dev, G, J = poses.device, int(poses.shape[0]), sk.joints
-    lens = _root_lens(lens, G)
-    T = len(lens)
-    L = torch.zeros((T, J), dtype=torch.float64, device=dev)
-    N = torch.zeros((T, J), dtype=torch.int64, device=dev) if return_counts else None
-    parents, _ = sk.device_tables(dev)
-    plan = _upload(np.stack([np.concatenate([[0], np.cumsum(lens)[:-1]]), lens]), np.int64, dev)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        if G == 0:                                                    # (no rows: the library launches nothing; a track without rows is "not corrected")
-            L.fill_(float("nan"))
-            L[:, sk.root] = 0.0
-        _capi.check(lib, lib.uu3d_bone_lengths(_ptr(poses), G, J, _ptr(parents), _ptr(plan[0]), _ptr(plan[1]), T, _ptr(L), _ptr(N),
-                                               C.c_void_p(stream)), None)
-    return (L, N) if return_counts else L
-
-
-def fix_bones(poses, lens, lengths, skeleton="h36m17"):
-    """uu3d_fix_bones on the current stream: ``fix_bones_host`` on a device tensor, one launch, nothing copies to the host or waits.
-    ``poses``: a contiguous (G, J, 3) float32 device tensor, only read; ``lengths``: what ``bone_lengths`` returned -- a contiguous
-    (tracks, J) float64 device tensor -- or a host array (J,) / (tracks, J) -> the rebuilt poses, a fresh device tensor."""
-    import torch
-    sk = _bone_device_poses(poses, skeleton)
-    lib = _capi.load_library()
-    dev, G, J = poses.device, int(poses.shape[0]), sk.joints
-    lens = _root_lens(lens, G)
-    T = len(lens)
-    if isinstance(lengths, torch.Tensor) and lengths.is_cuda:
-        if tuple(lengths.shape) != (T, J) or lengths.dtype != torch.float64 or not lengths.is_contiguous() or lengths.device != dev:
-            raise ValueError(f"lengths must be a contiguous ({T}, {J}) float64 tensor on the poses' device, got {tuple(lengths.shape)} of {lengths.dtype}")
-    else:
-        lengths = _upload(_bone_length_table(lengths, T, J), np.float64, dev)
-    out = torch.empty_like(poses)
-    if G == 0:
-        return out
-    parents, paths = sk.device_tables(dev)
-    row_track = None if T == 1 else _upload(np.repeat(np.arange(T, dtype=np.int32), lens), np.int32, dev)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _capi.check(lib, lib.uu3d_fix_bones(_ptr(poses), _ptr(out), G, J, _ptr(parents), _ptr(paths), sk.depth, _ptr(row_track), T, _ptr(lengths),
-                                            C.c_void_p(stream)), None)
-    return out
-
-
-def _device_tracks(tracks, device):
-    """The tracks on the device -> (list of (T_i, J, 2) tensors, J, frames given per track)."""
-    tr = [_device_track(t, device) for t in tracks]
-    if not tr:
-        raise ValueError("no tracks")
-    J = int(tr[0].shape[1])
-    if any(int(t.shape[1]) != J for t in tr):
-        raise ValueError("all tracks must have the same number of keypoints")
-    return tr, J, np.array([int(t.shape[0]) for t in tr], np.int64)
-
-
-def check_resolutions(resolutions, count, per="track"):
-    """None, one (w, h) or one per track (per slot, for a session) -> None or (count, 2) float64, contiguous."""
-    if resolutions is None:
-        return None
-    r = np.asarray(resolutions, np.float64)
-    if r.shape == (2,):
-        r = np.tile(r, (count, 1))
-    if r.shape != (count, 2) or not np.isfinite(r).all() or not (r > 0).all():
-        raise ValueError(f"resolutions must be one positive (w, h) or one per {per}")
-    return np.ascontiguousarray(r)
-
-
-def pose_table(tracks, device, resolutions=None, key_stride=0, lengths=None, valid=None, repair_joints=None, keypoints=None, model=None,
-               keep_source=False):
-    """The dense, normalised ``data.PoseTable`` of the tracks (uu3d_normalize_tracks) -> (table, frames per track).  ``valid`` as in
-    ``predict_tracks`` (not None: uu3d_normalize_tracks_valid into a fresh buffer; the table carries the per-frame flags).
-    ``repair_joints`` = G: uu3d_repair_joints runs on the given frames first; ``table.joint_state`` is its (given frames, J) uint8 state.
-    ``keypoints``: a ``KeypointMap`` or a preset's name (with ``model``): the tracks are (T_i, K_in, 2), per-joint entries of ``valid``
-    (T_i, K_in), and uu3d_map_keypoints runs in front of all of that (``_map_front``).  ``keep_source``: ``table.source`` = (the given
-    frames (R, J, 2) raw in the model's layout, their (R, J) uint8 joint flags or None) as the root solve reads them."""
-    import torch
-    check_repair_joints(repair_joints, valid)
-    tr, J, given = _device_tracks(tracks, device)
-    if keypoints is not None:
-        keypoints = keypoint_map(keypoints)
-        check_keypoint_inputs(keypoints, [J])
-    check_valid(valid, given, joints=J)
-    if key_stride > 0:
-        if lengths is None or len(lengths) != len(tr):
-            raise ValueError("keyframes_only needs `lengths`: the number of frames of every track")
-        lens = np.asarray(lengths, np.int64)
-        want = np.array([keyframe_count(n, key_stride) for n in lens], np.int64)
-        if (given != want).any():
-            i = int(np.flatnonzero(given != want)[0])
-            raise ValueError(f"track {i}: {int(lens[i])} frames at keyframe stride {key_stride} are {int(want[i])} keyframes, got {int(given[i])}")
-    else:
-        lens = given
-    if (lens < 1).any():
-        raise ValueError("every track needs at least one frame")
-    resolutions = check_resolutions(resolutions, len(tr))
-    src = torch.cat(tr, 0).contiguous() if len(tr) > 1 else tr[0].contiguous()
-    if keypoints is not None:
-        (src, valid), J = _map_front(keypoints, model, src, given, valid), keypoints.joints
-    flags = state = None
-    source = (src, _source_joint_flags(valid, J, src.device)) if keep_source else None
-    if valid is not None:
-        src, valid_in, state = _front_validity(src, given, J, valid, repair_joints, None if source is None else source[1])
-        kp = torch.empty((int(lens.sum()), J, 2), dtype=torch.float32, device=src.device)      # (never in the caller's own memory)
-        flags = torch.empty((int(lens.sum()),), dtype=torch.uint8, device=src.device)
-        normalize_tracks(src, kp, lens, resolutions, key_stride, given, valid_in=valid_in, valid_out=flags)
-    elif key_stride > 0 or resolutions is not None:
-        kp = torch.empty((int(lens.sum()), J, 2), dtype=torch.float32, device=src.device)      # (never in the caller's own memory)
-        normalize_tracks(src, kp, lens, resolutions, key_stride, given)
-    else:
-        kp = src
-    table = PoseTable.from_device(kp, lens, valid=flags)
-    table.joint_state, table.source = state, source
-    return table, lens
-
-
-def resampled_pose_table(tracks, device, fps, resolutions=None, valid=None, model_fps=50, repair_joints=None, keypoints=None, model=None,
-                         keep_source=False):
-    """``pose_table`` for tracks at ``fps`` frames per second: the dense, normalised table on the MODEL's time grid (``resample_plan``,
-    uu3d_resample_tracks; always a fresh buffer) -> (table, model frames per track, source frames per track).  With ``valid`` the table
-    carries one flag per model frame.  ``repair_joints`` = G: uu3d_repair_joints runs on the source frames first; ``table.joint_state`` is
-    its (source frames, J) uint8 state.  ``keypoints`` / ``model`` / ``keep_source`` as ``pose_table``: the map runs on the source frames, in
-    front of the rest."""
-    import torch
-    check_repair_joints(repair_joints, valid)
-    tr, J, lens = _device_tracks(tracks, device)
-    if keypoints is not None:
-        keypoints = keypoint_map(keypoints)
-        check_keypoint_inputs(keypoints, [J])
-    check_valid(valid, lens, joints=J)
-    if (lens < 1).any():
-        raise ValueError("every track needs at least one frame")
-    resolutions = check_resolutions(resolutions, len(tr))
-    model_lens, left, right, weight = resample_plan(lens, fps, model_fps)
-    src = torch.cat(tr, 0).contiguous() if len(tr) > 1 else tr[0].contiguous()
-    if keypoints is not None:
-        (src, valid), J = _map_front(keypoints, model, src, lens, valid), keypoints.joints
-    kp = torch.empty((int(model_lens.sum()), J, 2), dtype=torch.float32, device=src.device)
-    flags = None if valid is None else torch.empty((int(model_lens.sum()),), dtype=torch.uint8, device=src.device)
-    source = (src, _source_joint_flags(valid, J, src.device)) if keep_source else None
-    src, valid_in, state = _front_validity(src, lens, J, valid, repair_joints, None if source is None else source[1])
-    resample_tracks(src, kp, model_lens, left, right, weight, resolutions, valid_in=valid_in, valid_out=flags)
-    table = PoseTable.from_device(kp, model_lens, valid=flags)
-    table.joint_state, table.source = state, source
-    return table, model_lens, lens
 
 
 def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, flip=None, keyframes_only=False, reuse_frames=True,
@@ -1715,17 +255,10 @@ def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, fl
     same lengths table.  A length that is not finite or <= 0 (a track without a usable frame) leaves that bone as it is; a NaN frame stays
     NaN; the root joint of a root-relative pose stays exactly 0.  No accuracy figure is claimed."""
     import torch
-    pose_filter, root_filter = check_smooth(smooth, camera is not None)
-    rigid = check_bones(bones, len(tracks), config.NUM_KEYPOINTS, int(config.ROOT_KEYTPOINT) if root_relative else None)
-    if camera is not None:
-        cameras, min_root_joints = check_cameras(camera, len(tracks)), check_min_root_joints(min_root_joints)
-        if int(config.NUM_KEYPOINTS) > MAX_ROOT_JOINTS:
-            raise ValueError(f"camera needs a model of at most {MAX_ROOT_JOINTS} joints, this one has {int(config.NUM_KEYPOINTS)}")
-    if keypoints is not None:
-        keypoints = keypoint_map(keypoints, config.NUM_KEYPOINTS)
-        check_keypoint_inputs(keypoints, [_shape(t)[1] if len(_shape(t)) == 3 else -1 for t in tracks])
-    if fps is None and out_fps is not None:
-        raise ValueError("out_fps needs fps: the rate the tracks were filmed at")
+    # options: the refusals shared with a live session (``options.stage_options``), then the ones only this call has
+    opts = stage_options(config, len(tracks), "track", root_relative, keypoints, camera, min_root_joints, smooth, bones, repair_joints, fps, out_fps)
+    if opts.keypoints is not None:
+        check_keypoint_inputs(opts.keypoints, [_shape(t)[1] if len(_shape(t)) == 3 else -1 for t in tracks])
     if fps is not None and keyframes_only:
         raise ValueError("fps and keyframes_only exclude each other: for a detector that ran on every k-th frame pass the given frames with "
                          "fps=video_rate / k and out_fps=video_rate")
@@ -1733,7 +266,6 @@ def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, fl
         raise ValueError("valid needs a model with strided input: a missing frame becomes the learned masked token, which this model does not have")
     check_repair_joints(repair_joints, valid)
     check_valid(valid, [len(t) for t in tracks], joints=_shape(tracks[0])[1] if len(tracks) and len(_shape(tracks[0])) == 3 else None)
-    dev = model.device
     cfg = config.copy()
     if mask_stride is None:
         mask_stride = default_mask_stride(cfg)
@@ -1741,74 +273,88 @@ def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, fl
     flip = bool(cfg.EVAL_FLIP) if flip is None else bool(flip)
     if keyframes_only and mask_stride is None:
         raise ValueError("keyframes_only needs a mask stride")
+    # table: the given frames -> the pose table on the model's time grid; ``lens``: returned frames per track
+    given = np.array([len(t) for t in tracks], np.int64)
+    front = dict(valid=valid, repair_joints=repair_joints, keypoints=opts.keypoints, model=model, keep_source=camera is not None)
     if fps is None:
-        table, lens = pose_table(tracks, dev, resolutions, int(mask_stride) if keyframes_only else 0, lengths, valid=valid,
-                                 repair_joints=repair_joints, keypoints=keypoints, model=model, keep_source=camera is not None)
+        table, lens = pose_table(tracks, model.device, resolutions, int(mask_stride) if keyframes_only else 0, lengths, **front)
         model_lens = lens
     else:
         rates = frame_rates(fps, len(tracks))
-        table, model_lens, src_lens = resampled_pose_table(tracks, dev, rates, resolutions, valid=valid, model_fps=model_fps,
-                                                           repair_joints=repair_joints, keypoints=keypoints, model=model,
-                                                           keep_source=camera is not None)
-        lens, positions = output_positions(src_lens, rates, rates if out_fps is None else out_fps, model_fps)
+        table, model_lens, _ = resampled_pose_table(tracks, model.device, rates, resolutions, model_fps=model_fps, **front)
+        lens, positions = output_positions(given, rates, rates if out_fps is None else out_fps, model_fps)
+    # windows + forward: the raw predictions of the windows that are run, and the row of each frame's window among them (-1: not run)
+    raw, frame_idx, rows = _predicted_windows(model, cfg, table, mask_stride, flip, batch_size, depth, graph, reuse_frames)
+    # assemble plan: which two predicted frames every returned frame is read from, and how
+    stride = ev.prediction_stride(cfg)
+    if fps is not None:
+        plan = evaluation.keyframe_plan_at(frame_idx, 1 if stride is None else stride, positions, rows=rows)
+    elif stride is None:
+        plan = rows, rows, np.zeros(len(rows), np.float64)
+    else:
+        plan = evaluation.keyframe_plan(frame_idx, stride, rows=rows)[:3]
+
+    def assemble(plan):
+        return assemble_tracks(raw[0], raw[1] if flip else None, *plan, flip_order=cfg.AUGM_FLIP_KEYPOINT_ORDER,
+                               root=int(cfg.ROOT_KEYTPOINT) if root_relative else -1)
+    out = assemble(plan)
+    # bones: constant bone lengths -- everything behind reads the fixed poses
+    if opts.rigid is not None:
+        skeleton, known = opts.rigid
+        bone_table = bone_lengths(out, lens, skeleton) if known is None else _upload(known, np.float64, out.device)
+        out = fix_bones(out, lens, bone_table, skeleton)
+    # pose filter: what is returned is the poses, or the poses filtered; the roots are solved from the unfiltered ones
+    shown = out
+    if opts.pose_filter is not None or opts.root_filter is not None:
+        out_rate = model_fps if fps is None else (rates if out_fps is None else frame_rates(out_fps, len(tracks)))
+    if opts.pose_filter is not None:
+        shown = one_euro(out, lens, out_rate, opts.pose_filter)
+    sizes = [int(n) for n in lens]
+    poses = list(torch.split(shown, sizes, 0))
+    # roots: solved at the given frames, joined to a trajectory that is read at the returned frames
+    placed = ()
+    if camera is not None:
+        def reread(at):                                               # the same motion at the given frames' times (``out_fps``)
+            again = assemble(evaluation.keyframe_plan_at(frame_idx, 1 if stride is None else stride, at, rows=rows))
+            return again if opts.rigid is None else fix_bones(again, given, bone_table, skeleton)
+        at_given, where = poses_at_given_frames(out, lens, given, int(mask_stride) if keyframes_only else 0, rates if fps is not None else None,
+                                                out_fps, model_fps, reread)
+        solved_roots, solved = solve_roots(at_given, table.source[0], opts.cameras, table.source[1], opts.min_root_joints, lens=given)
+        roots, root_state = root_trajectory(solved_roots, solved, given, where)
+        if opts.root_filter is not None:
+            roots = one_euro(roots, lens, out_rate, opts.root_filter, state=root_state)
+        placed = (list(torch.split(roots, sizes, 0)), list(torch.split(root_state, sizes, 0)))
+    return _returned(poses, placed, table, model_lens, given, return_valid, repair_joints is not None)
+
+
+def _predicted_windows(model, cfg, table, mask_stride, flip, batch_size, depth, graph, reuse_frames):
+    """One window per frame of ``table``, in table order (position p is table row p); the ones ``eval.needed_windows`` keeps go through
+    ``eval.predict_windows``' pipeline -> (raw predictions (plain, flipped), the frame index of every window, its row among the raw
+    predictions or -1)."""
     gen = SequenceGenerator(table, seq_len=cfg.SEQUENCE_LENGTH, target_frame_rate=50, subsample=1, stride=cfg.SEQUENCE_STRIDE,
                             padding_type=cfg.PADDING_TYPE, flip_augment=False, flip_lr_indices=cfg.AUGM_FLIP_KEYPOINT_ORDER,
                             mask_stride=mask_stride, stride_mask_align_global=True, rand_shift_stride_mask=False, shuffle=False)
-    desc = gen.descriptors()                                         # one window per frame, in table order: position p is table row p
-    frame_idx = desc[:, 1]
-    run = np.flatnonzero(ev.needed_windows(frame_idx, cfg))
+    desc = gen.descriptors()
+    run = np.flatnonzero(ev.needed_windows(desc[:, 1], cfg))
     raw = ev._predict_windows_raw(model, gen, desc[run], int(batch_size or cfg.BATCH_SIZE), flip, depth, graph,
                                   bool(reuse_frames) and bool(model.arch.compiled_dims))
     rows = np.full(len(desc), -1, np.int64)
     rows[run] = np.arange(len(run))
-    stride = ev.prediction_stride(cfg)
-    if fps is not None:
-        left, right, weight = evaluation.keyframe_plan_at(frame_idx, 1 if stride is None else stride, positions, rows=rows)
-    elif stride is None:
-        left = right = rows
-        weight = np.zeros(len(desc), np.float64)
-    else:
-        left, right, weight, _ = evaluation.keyframe_plan(frame_idx, stride, rows=rows)
-    out = assemble_tracks(raw[0], raw[1] if flip else None, left, right, weight, flip_order=cfg.AUGM_FLIP_KEYPOINT_ORDER,
-                          root=int(cfg.ROOT_KEYTPOINT) if root_relative else -1)
-    if rigid is not None:                                             # constant bone lengths: everything behind reads the fixed poses
-        bone_table = bone_lengths(out, lens, rigid[0]) if rigid[1] is None else _upload(rigid[1], np.float64, out.device)
-        out = fix_bones(out, lens, bone_table, rigid[0])
-    shown = out                                                       # what is returned: the poses, or the poses filtered
-    if pose_filter is not None or root_filter is not None:
-        out_rate = model_fps if fps is None else (rates if out_fps is None else frame_rates(out_fps, len(tracks)))
-    if pose_filter is not None:
-        shown = one_euro(out, lens, out_rate, pose_filter)
-    poses = list(torch.split(shown, [int(n) for n in lens], 0))
-    placed = ()
-    if camera is not None:
-        given = np.array([len(t) for t in tracks], np.int64)
-        at_given, where = out, None                                   # a returned frame is a given frame: the plain call, fps alone
-        if keyframes_only:                                            # given keyframe g is returned frame g s_in
-            first = np.concatenate([[0], np.cumsum(lens)[:-1]])
-            picks = np.concatenate([f + np.arange(n, dtype=np.int64) * int(mask_stride) for f, n in zip(first, given)])
-            at_given = out.index_select(0, _upload(picks, np.int64, out.device))
-            where = given_positions(lens, [Fraction(1, int(mask_stride))] * len(given))
-        elif out_fps is not None:                                     # the same motion read once more, at the given frames' times
-            _, at = output_positions(src_lens, rates, rates, model_fps)
-            at_given = assemble_tracks(raw[0], raw[1] if flip else None, *evaluation.keyframe_plan_at(frame_idx, 1 if stride is None else stride, at, rows=rows),
-                                       flip_order=cfg.AUGM_FLIP_KEYPOINT_ORDER, root=int(cfg.ROOT_KEYTPOINT) if root_relative else -1)
-            if rigid is not None:                                     # (the same lengths table as the returned poses)
-                at_given = fix_bones(at_given, given, bone_table, rigid[0])
-            where = given_positions(lens, [f / o for f, o in zip(rates, frame_rates(out_fps, len(given)))])
-        solved_roots, solved = solve_roots(at_given, table.source[0], cameras, table.source[1], min_root_joints, lens=given)
-        roots, root_state = root_trajectory(solved_roots, solved, given, where)
-        if root_filter is not None:
-            roots = one_euro(roots, lens, out_rate, root_filter, state=root_state)
-        sizes = [int(n) for n in lens]
-        placed = (list(torch.split(roots, sizes, 0)), list(torch.split(root_state, sizes, 0)))
+    return raw, desc[:, 1], rows
+
+
+def _returned(poses, placed, table, model_lens, given, return_valid, joint_state):
+    """The return value of ``predict_tracks``: ``poses``; with ``return_valid`` (poses, flags) -- the table's per-frame flags on the model's
+    grid, all True where it has none -- or, with ``repair_joints``, (poses, flags, joint_state); with ``camera`` the two lists of
+    ``placed`` (roots, root_state) are appended to whichever it is."""
+    import torch
     if not return_valid:
         return (poses,) + placed if placed else poses
-    flags = table.valid.view(torch.bool) if table.valid is not None else torch.ones((int(model_lens.sum()),), dtype=torch.bool, device=out.device)
+    flags = table.valid.view(torch.bool) if table.valid is not None else torch.ones((int(model_lens.sum()),), dtype=torch.bool, device=poses[0].device)
     flags = list(torch.split(flags, [int(n) for n in model_lens], 0))
-    if repair_joints is None:
+    if not joint_state:
         return (poses, flags) + placed
-    return (poses, flags, list(torch.split(table.joint_state, [int(len(t)) for t in tracks], 0))) + placed
+    return (poses, flags, list(torch.split(table.joint_state, [int(n) for n in given], 0))) + placed
 
 
 def padding_source_is_keyframe(length, config, mask_stride):
@@ -1835,87 +381,16 @@ def parse_args(argv=None):
     p.add_argument("--weights", required=True, help="weights (.h5)")
     p.add_argument("--input", required=True, help=".npz with one (T, J, 2) array per track")
     p.add_argument("--output", required=True, help=".npz to write")
-    p.add_argument("--resolution", type=float, nargs=2, metavar=("W", "H"), default=None,
-                   help="image size in pixels of all tracks; without it the coordinates are taken as normalised already")
+    add_track_options(p, False, "resolution")
     p.add_argument("--mask_stride", type=int, default=None, help="input stride s_in (default: the config's first MASK_STRIDE)")
     p.add_argument("--keyframes_only", action="store_true",
                    help="the arrays hold frames 0, s_in, 2 s_in, ... only; a track of K keyframes is taken to have (K - 1) * s_in + 1 frames")
-    p.add_argument("--mask_missing", action="store_true",
-                   help="a frame with a NaN or Inf coordinate is a missed detection: never shown to the network, its pose is still predicted")
-    p.add_argument("--repair_joints", type=int, default=None, metavar="G",
-                   help="fill a joint that is missing for up to G consecutive frames from the nearest frames where it was seen; implies --mask_missing")
-    p.add_argument("--min_score", type=float, default=None, metavar="S",
-                   help="the arrays may be (T, J, 3) with the detector's score in the third channel: a joint counts as seen when score >= S")
-    p.add_argument("--fps", type=_rate_argument, default=None, metavar="F",
-                   help="frame rate of the tracks, a float or NUM/DEN (29.97, 30000/1001); without it they are taken at the model's rate")
-    p.add_argument("--out_fps", type=_rate_argument, default=None, metavar="F", help="frame rate of the poses written (default: --fps)")
-    p.add_argument("--keypoints", default=None, metavar="NAME", choices=sorted(KEYPOINT_PRESETS),
-                   help="the joint layout of the arrays, (T, K, 2): mapped onto the model's joints on the device; --min_score then reads the "
-                        "score channel of (T, K, 3) arrays, one score per detector joint")
-    p.add_argument("--camera", type=float, nargs=4, metavar=("FX", "FY", "CX", "CY"), default=None,
-                   help="the camera's intrinsics in the units of the arrays (pixels with --resolution): the output gains <key>__root (T, 3), the "
-                        "position of the skeleton's root in the camera's space, and <key>__root_state (T,) per track")
-    p.add_argument("--min_root_joints", type=int, default=DEFAULT_MIN_ROOT_JOINTS, metavar="N",
-                   help="the fewest observed joints a frame's root is solved from (with --camera)")
-    p.add_argument("--smooth", type=float, nargs=3, metavar=("MIN_CUTOFF", "BETA", "D_CUTOFF"), default=None,
-                   help="pass the written poses through a One-Euro filter (Hz, 1 / unit speed, Hz) at the rate of the written frames; causal, it lags")
-    p.add_argument("--smooth_root", type=float, nargs=3, metavar=("MIN_CUTOFF", "BETA", "D_CUTOFF"), default=None,
-                   help="the same for the roots (needs --camera)")
-    p.add_argument("--bones", default=None, metavar="track|FILE.npy",
-                   help="constant bone lengths: 'track' gives every track its own mean lengths, FILE.npy holds a (J,) array of known lengths in "
-                        "the poses' units, indexed by child joint")
+    add_track_options(p, False, "mask_missing", "repair_joints", "min_score", "fps", "out_fps", "keypoints", "camera", "min_root_joints", "smooth",
+                      "smooth_root", "bones")
     args = p.parse_args(argv)
     if args.smooth_root is not None and args.camera is None:
         p.error("--smooth_root needs --camera: without it no roots are written")
     return args
-
-
-def bones_option(args, J):
-    """--bones of a command line -> the ``bones`` keyword ({} when it is not given): "track", or the (J,) array of an .npy file."""
-    if getattr(args, "bones", None) is None:
-        return {}
-    if args.bones == "track":
-        return {"bones": "track"}
-    try:
-        lengths = np.asarray(np.load(args.bones), np.float64)
-    except (OSError, ValueError) as e:
-        raise SystemExit(f"--bones: {args.bones} is neither 'track' nor a readable .npy file ({e})") from None
-    if lengths.shape != (int(J),):
-        raise SystemExit(f"--bones: {args.bones} holds an array of shape {lengths.shape}, expected ({int(J)},): one length per child joint")
-    return {"bones": lengths}
-
-
-def smooth_option(args):
-    """--smooth / --smooth_root of a command line -> the ``smooth`` keyword ({} when neither is given)."""
-    if args.smooth is None and args.smooth_root is None:
-        return {}
-    try:
-        return {"smooth": (None if args.smooth is None else OneEuro(*args.smooth), None if args.smooth_root is None else OneEuro(*args.smooth_root))}
-    except ValueError as e:
-        raise SystemExit(f"--smooth / --smooth_root: {e}") from None
-
-
-def split_scores(names, tracks, J, min_score, source="input"):
-    """The arrays of the command line -> (list of (T, J, 2) tracks, per-joint flags or None).  With ``min_score`` = S an array may be
-    (T, J, 3), the detector's score in the third channel: the joint is flagged when score >= S (a NaN score fails) and the score is
-    stripped; a (T, J, 2) array next to it has every joint flagged.  Without it only (T, J, 2) passes."""
-    for k, t in zip(names, tracks):
-        if t.ndim != 3 or t.shape[1] != J or t.shape[2] not in ((2,) if min_score is None else (2, 3)):
-            raise SystemExit(f"{source}[{k}] has shape {t.shape}, expected (T, {J}, 2)" + ("" if min_score is None else f" or (T, {J}, 3)"))
-    if min_score is None:
-        return tracks, None
-    flags = [t[:, :, 2] >= min_score if t.shape[2] == 3 else np.ones(t.shape[:2], bool) for t in tracks]
-    return [np.ascontiguousarray(t[:, :, :2]) for t in tracks], flags
-
-
-def input_joints(config, keypoints):
-    """The joint count of the command line's arrays -> (K, the keyword for ``predict_tracks`` / ``replay_tracks``)."""
-    if keypoints is None:
-        return config.NUM_KEYPOINTS, {}
-    try:
-        return keypoint_map(keypoints, config.NUM_KEYPOINTS).inputs, {"keypoints": keypoints}
-    except ValueError as e:
-        raise SystemExit(f"--keypoints: {e}") from None
 
 
 def main(argv=None):
@@ -1927,7 +402,7 @@ def main(argv=None):
         tracks = [np.asarray(z[k], np.float32) for k in names]
     if not names:
         raise SystemExit(f"{args.input} holds no arrays")
-    K, skeleton = input_joints(config, args.keypoints)
+    K, _ = input_joints(config, args.keypoints)
     tracks, joint_flags = split_scores(names, tracks, K, args.min_score, args.input)
     ms = default_mask_stride(config) if args.mask_stride is None else args.mask_stride
     lengths = None
@@ -1935,31 +410,12 @@ def main(argv=None):
         if ms is None:
             raise SystemExit("--keyframes_only needs a mask stride")
         lengths = [(len(t) - 1) * int(ms) + 1 for t in tracks]
-    steady = {**smooth_option(args), **bones_option(args, config.NUM_KEYPOINTS)}
+    options = track_keywords(args, config, names, joint_flags, live=False)
     model = _load_model(config, args.weights)
-    if args.out_fps is not None and args.fps is None:
-        raise SystemExit("--out_fps needs --fps")
-    rate = {} if args.fps is None else {"fps": args.fps, **({} if args.out_fps is None else {"out_fps": args.out_fps})}
-    missing = {}
-    if joint_flags is not None:
-        missing = {"valid": joint_flags}
-    elif args.mask_missing or args.repair_joints is not None:
-        missing = {"valid": "finite"}
-    if args.repair_joints is not None:
-        missing["repair_joints"] = args.repair_joints
-    place = {}
-    if args.camera is not None:
-        try:
-            check_cameras(tuple(args.camera), 1), check_min_root_joints(args.min_root_joints)
-        except ValueError as e:
-            raise SystemExit(f"--camera: {e}") from None
-        if any(k.endswith(("__root", "__root_state")) for k in names):
-            raise SystemExit(f"{args.input}: a key ending in __root or __root_state would collide with the arrays --camera writes")
-        place = {"camera": tuple(args.camera), "min_root_joints": args.min_root_joints}
     poses = predict_tracks(model, config, tracks, resolutions=None if args.resolution is None else tuple(args.resolution), mask_stride=ms,
-                           keyframes_only=args.keyframes_only, lengths=lengths, **missing, **rate, **skeleton, **place, **steady)
+                           keyframes_only=args.keyframes_only, lengths=lengths, **options)
     arrays = {}
-    if place:
+    if "camera" in options:
         poses, roots, root_state = poses
         arrays.update({k + "__root": r.detach().cpu().numpy() for k, r in zip(names, roots)})
         arrays.update({k + "__root_state": r.detach().cpu().numpy() for k, r in zip(names, root_state)})

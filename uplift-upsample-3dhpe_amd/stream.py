@@ -57,92 +57,15 @@ poses a second, five per push.  Input and model sides, ``lookahead`` (SOURCE fra
           frame is later than source frame q -- which the enumeration checks as well (``rate_plan``, ``out_push_plan``).
 One launch (uu3d_stream_timed_emit_multi) in place of uu3d_stream_timed_emit; ``out_fps=None`` is the session above, bit for bit.
 
-Live per-joint missed detections -- ``StreamSession(..., repair_joints=G)``: ``push(valid=...)`` takes one flag per JOINT and a joint the
-detector lost is filled by the rule of ``predict.repair_joints_host``.  The one rule above is unchanged: the pose of frame t - lookahead is
-what ``predict_tracks(track[:t + 1], valid=flags[:t + 1], repair_joints=G)`` gives for it -- a closed gap interpolated, a trailing or leading
-gap held for up to G frames.  The rule looks ahead, so a push may REVISE frames the session has filed, within bounds:
-  near    coordinates change only for frames t - G .. t (a gap of at most G frames closes at t: held -> interpolated; a joint is seen for
-          the first time at t: unfilled -> held from t).  Of those the ring keeps the multiples of s_in and the edge frame, at most
-          K = G // s_in + 2 frames: the tick re-stages them (uu3d_stream_repair_stage), runs uu3d_frame_features over slots x K (x 2
-          with flip) frames and files K rows (uu3d_stream_commit_repair).
-  far     an older frame only ever goes from valid to missing (a gap longer than G closes at t: the frames held from its left end become
-          unfillable): a byte of the validity state, no features.
-The state this needs is bounded; ``LiveRepairHost`` is the state machine the device runs, in numpy.  G <= 32 (``MAX_LIVE_REPAIR``: K and
-the buffers are fixed at construction).  Not together with ``fps`` / ``out_fps``: a revised source frame would re-make model frames that
-were filed already (a later change).  ``repair_joints=None`` is the session above, bit for bit.
-
-Any skeleton -- ``StreamSession(..., keypoints=M)`` (a name of ``predict.KEYPOINT_PRESETS`` or a ``predict.KeypointMap``): ``push`` takes
-frames in the DETECTOR's joint layout, (slots, K_in, 2), and one more launch in front of the stage (uu3d_map_keypoints) writes the session's
-own (slots, J, 2) frame -- with ``repair_joints`` its (slots, J) joint flags as well, from (slots, K_in) flags per detector joint.  In a
-session without ``fps`` that launch is the first step of the ONE captured tick graph; with ``fps`` it sits in front of
-uu3d_stream_source_push, not captured, like the launches around it.  ``captures`` stays 1 and ``push`` still never waits.  The session's
-contract is its usual one with the mapped track: the same session without ``keypoints``, pushed ``predict.map_keypoints_host``'s frames and
-flags, returns the same bits.  ``keypoints=None`` is the session above, bit for bit.
-
-Per-frame detections -- ``StreamSession(..., detections=D, max_age=, max_dist=, min_common=)``: the session takes what a multi-person
-detector emits, ``push_detections(dets (D, K, 2), count, valid)`` -- per frame a list of people in ANY order, people entering, leaving and
-being missed -- and matches people to slots on the device: ``slots`` is the capacity, a slot is born, fed and freed by the rule of
-``predict.associate_host`` (include/uu3d.h, PER-FRAME DETECTIONS: greedy, no motion model).  The captured tick begins with
-uu3d_stream_associate -- it scatters the detections into the session's frame, flag and ``active`` buffers and writes the ``born`` mask --,
-then uu3d_stream_reset (and uu3d_stream_repair_reset) with that mask ON THE DEVICE, then the steps above unchanged: still ONE linear
-captured graph, ``push_detections`` never waits, ``count`` may be a device tensor.  Implies ``missed_detections=True``: an alive slot
-without a match gets a MISSING frame.  The contract: the session equals, bit for bit, a ``StreamSession(missed_detections=True)`` driven
-by ``associate_host`` -- ``reset(born)``, then ``push(frames, active=alive, valid=matched)``.  Works with ``keypoints`` (the association
-runs on the detector's joints, in front of the map) and ``repair_joints``; NOT together with ``fps`` / ``out_fps`` (ValueError: the host
-mirror of the source counters cannot follow births that happen on the device yet).
-
-Live absolute root -- ``StreamSession(..., camera=(fx, fy, cx, cy), min_root_joints=6)``: every push returns, beside the poses, where each
-of them stands in the camera's 3D space -- ``push`` -> (poses, fresh, roots (slots, 3) float32, root_state (slots,) uint8), and
-``poses[i] + roots[i]`` is slot i's skeleton in the camera's space (``predict.predict_tracks(camera=...)`` for a finished video).  The
-intrinsics are in the units of the frames AS PUSHED (pixels with ``resolutions``), one tuple or one per slot.  Per slot the session keeps a
-ring of its last lookahead + 1 raw frames in the model's joint layout (behind the ``keypoints`` map, before normalisation; frame t at place
-t % (lookahead + 1)) with one USED byte per joint -- the joint's flag (none: every joint; ``missed_detections``: the frame's flag for all of
-its joints; ``repair_joints``: the push's per-joint flag, mapped with ``keypoints``) and both raw coordinates finite -- and the last solved
-root.  A joint that ``repair_joints`` fills is never used (an interpolation is not a measurement) and the ring holds the pushed coordinates,
-never the repaired ones, so no push revises it.  Whenever a slot's pose is fresh, the frame it belongs to -- c = t - lookahead, with ``fps``
-source frame q = j - lookahead -- is solved against that pose by ``predict.solve_roots_host``'s rule, unchanged (uu3d_stream_root: lane j of
-one wave per slot files joint j, lane 0 solves).  Solved: the root, state 1, and the slot holds it.  Not solved: the held root, state 2; no
-held root yet: zeros, state 0.  A push that is not fresh returns the previous root and state, like the pose; ``reset`` clears ring, held
-root and state (also on the device, for a slot born at a ``push_detections`` tick).  The rule is CAUSAL: it holds the last solved root and
-cannot interpolate towards a later solved frame as ``predict_tracks(camera=...)`` does, because the poses of later frames do not exist
-yet.  ``LiveRootHost`` is the rule in numpy.  The launch is the LAST step of the one captured tick (behind uu3d_stream_emit); with ``fps``
-it follows uu3d_stream_timed_emit, not captured.  ``captures`` stays 1 and ``push`` never waits.  With ``detections`` one tuple only: the
-people of a video share one space.  Not together with ``out_fps`` (ValueError: those poses are not at source-frame times; a later
-change).  No accuracy is claimed: the model's scale error goes 1:1 into the depth.  ``camera=None`` is the session above, bit for bit: no
-further launch or buffer.
-
-Steady output -- ``StreamSession(..., smooth=F)``: the root above is solved tick by tick and nothing ties one tick's root to the next, and
-the poses carry the detector's frame-to-frame noise.  ``smooth`` -- True (the defaults), a ``predict.OneEuro(min_cutoff, beta, d_cutoff)``
-for poses and roots alike, or a pair (pose_filter, root_filter), either None -- puts the One-Euro filter (Casiez, Roussel, Vogel 2012)
-behind the tick, on the device: an exponential smoother whose cut-off rises with the speed of the signal, steady while a person stands,
-little lag while they move (the rule: ``predict.one_euro_host``; include/uu3d.h, STEADY OUTPUT).  A channel is one coordinate of one joint
-of one slot, or of its root.  Whenever an active slot's pose is fresh, each of its channels takes ONE sample at rate / n, n the frames
-since the channel's previous sample (the frame counters are ``source_frames``; the rate is ``model_fps``, or ``fps`` in a session with
-``fps``); a root of state 0 (zeros) is passed through and takes no sample, a held root (state 2) is a sample like any other.  A slot that
-is not fresh returns the filter's last output.  ``push`` returns the filtered buffers in place of the poses and, with ``camera``, the
-roots; ``raw_poses`` / ``raw_roots`` are the unfiltered ones, and uu3d_stream_root keeps solving against the unfiltered pose.  The
-launches (uu3d_stream_one_euro, one per filtered buffer) are the LAST steps of the one captured tick -- with ``fps`` behind
-uu3d_stream_timed_emit and the root solve, not captured --; ``push`` never waits.  ``reset`` and a birth at a ``push_detections`` tick
-clear the filter with everything else.  ``LiveOneEuro`` owns the state block and the two launches and runs without a model;
-``LiveOneEuroHost`` is the same state machine in numpy, and the device equals it bit for bit.  Not together with ``out_fps`` (ValueError:
-several rows per push).  No accuracy or jitter figure is claimed.  ``smooth=None`` is the session above, bit for bit: no further launch
-or buffer.
-
-Live constant bone lengths -- ``StreamSession(..., bones=B)``: the network predicts every tick's skeleton on its own, so a person's bone
-lengths breathe from tick to tick, and under ``camera`` the depth with them.  ``bones`` -- "track", a (J,) array of lengths by child joint,
-one such array per slot, or a ``predict.Bones(lengths, skeleton)`` for another tree than ``predict.SKELETONS["h36m17"]`` -- puts ONE more
-launch into the session's launch table, directly behind the emit (with ``fps`` behind uu3d_stream_timed_emit) and in front of the root
-solve and the One-Euro launches: uu3d_stream_bones, one wave per slot, rebuilds the emitted pose from the root outwards with every bone at
-the slot's length, its direction kept (the rule: ``predict.fix_bones_host``; include/uu3d.h, CONSTANT BONE LENGTHS).  It writes a buffer
-of its own, which ``push`` returns and the root solve and the pose filter read; ``raw_poses`` stays the model's output and
-``bone_lengths`` is the slots' (slots, J) float64 table on the device.  With "track" a slot's length is the mean over the FRESH poses it
-has emitted so far: the mean is CAUSAL and therefore differs from ``predict_tracks(bones="track")``, which averages the whole track; early
-in a track it still moves, and a subject whose lengths are known should pass them.  The output is a pure function of the raw pose and the
-slot's lengths: a slot that is not fresh returns its previous rebuilt pose, bit for bit.  ``reset`` and a birth at a ``push_detections``
-tick clear the sums and counts with everything else; ``finish`` runs the same step in every drain tick, the chosen slots as ``active``.
-``LiveBonesHost`` is the rule in numpy, and the device equals it bit for bit.  ``captures`` stays 1 and ``push`` never waits.  Not
-together with ``out_fps`` (ValueError: several rows per push).  No accuracy figure is claimed.  ``bones=None`` is the session above, bit
-for bit: no further launch or buffer.
+The options of a session, one stage module each -- what the option does live, its launches in the tick and its host mirror stand in the
+module's docstring; every name is importable from here as before:
+    validity.py   live per-joint missed detections: ``StreamSession(..., repair_joints=G)`` (``LiveRepairHost``, ``MAX_LIVE_REPAIR``)
+    keypoints.py  any skeleton: ``StreamSession(..., keypoints=M)``
+    associate.py  per-frame detections: ``StreamSession(..., detections=D, max_age=, max_dist=, min_common=)`` and ``push_detections``
+    roots.py      live absolute root: ``StreamSession(..., camera=(fx, fy, cx, cy), min_root_joints=6)`` (``LiveRootHost``)
+    smooth.py     steady output: ``StreamSession(..., smooth=F)`` (``LiveOneEuro``, ``LiveOneEuroHost``)
+    bones.py      live constant bone lengths: ``StreamSession(..., bones=B)`` (``LiveBonesHost``)
+The refusals these options share with ``predict_tracks`` are ``options.stage_options``; the ones only a session has are ``_init_plan``'s.
 
 The end of a track -- ``finish(slots)``: a session with lookahead a has not returned the poses of a track's last a frames when the track
 ends (the person leaves, the video stops).  ``finish`` returns them -- (slots, a, J, 3) and (slots, a) on the device -- and resets exactly
@@ -172,12 +95,20 @@ import numpy as np
 
 from . import _capi
 from ._capi import ptr as _ptr
-from .predict import (ASSOCIATION_DEFAULTS, Bones, DEFAULT_MIN_ROOT_JOINTS, KEYPOINT_PRESETS, MAX_ROOT_JOINTS, MAX_SMOOTH_CHANNELS, OneEuro, _bone_offsets,
-                      _load_model, bones_option, check_association, check_bones, check_cameras, check_keypoint_inputs, check_min_root_joints,
-                      check_repair_joints, check_resolutions, check_smooth, check_valid, fix_bones_host, input_joints, keypoint_map,
-                      one_euro_sample, skeleton_of, smooth_option, solve_roots_host, split_scores)
-from .rates import (RatePlan, _rate_argument, frame_rate, max_lookahead, newest_model_frame, out_push_plan, push_plan,  # noqa: F401 (re-exported)
+# (noqa: F401 below -- re-exported: every name this module had before the stages became modules of their own)
+from .associate import ASSOCIATION_DEFAULTS, check_association
+from .bones import Bones, LiveBonesHost, _bone_offsets, check_bones, fix_bones_host, skeleton_of  # noqa: F401
+from .cli import add_track_options, bones_option, input_joints, smooth_option, split_scores, track_keywords  # noqa: F401
+from .keypoints import KEYPOINT_PRESETS, check_keypoint_inputs, keypoint_map  # noqa: F401
+from .options import stage_options
+from .predict import _load_model
+from .rates import (RatePlan, _rate_argument, frame_rate, max_lookahead, newest_model_frame, out_push_plan, push_plan,  # noqa: F401
                     rate_plan, session_strides)
+from .roots import DEFAULT_MIN_ROOT_JOINTS, MAX_ROOT_JOINTS, LiveRootHost, check_cameras, check_min_root_joints, solve_roots_host  # noqa: F401
+from .smooth import (MAX_SMOOTH_CHANNELS, LiveOneEuro, LiveOneEuroHost, OneEuro, _live_filter_arguments, check_smooth,  # noqa: F401
+                     one_euro_sample)
+from .tracks import _host_array, check_resolutions
+from .validity import MAX_LIVE_REPAIR, LiveRepairHost, check_repair_joints, check_valid, staged_frames  # noqa: F401
 
 
 def ring_capacity(config, mask_stride=None, lookahead=0):
@@ -239,15 +170,6 @@ def window_plan(frames, lookahead, config, mask_stride=None, valid=None, drained
             "place": np.where(kind == 2, (src // s_in) % cap, -1)}
 
 
-MAX_LIVE_REPAIR = 32                                                  # the largest repair_joints of a live session (kLiveRepairMaxGap)
-
-
-def staged_frames(repair_joints, mask_stride):
-    """K: frames a session with ``repair_joints`` re-stages per slot and tick -- the multiples of s_in among G + 1 consecutive frames and
-    the edge frame."""
-    return int(repair_joints) // int(mask_stride) + 2
-
-
 LIVE_OPTIONS = ("repair_joints", "keypoints", "camera", "min_root_joints", "smooth", "bones")  # the keywords ``StreamSession`` and ``replay_tracks`` take from **options
 DETECTION_OPTIONS = ("detections",) + tuple(ASSOCIATION_DEFAULTS)    # ... and the ones only ``StreamSession`` takes: per-frame detections
 
@@ -259,358 +181,6 @@ def _live_options(options, who, names=LIVE_OPTIONS):
     if unknown:
         raise TypeError(f"{who}() got an unexpected keyword argument {unknown[0]!r}")
     return tuple(options.get(name) for name in names)
-
-
-class LiveRepairHost(object):
-    """The incremental state machine of uu3d_stream_repair_stage for ONE slot, in numpy, written to be read: ``predict.repair_joints_host``
-    on the growing track, one frame per ``step``, from a bounded state --
-        raw, observed   the raw coordinates and observed flags of the newest G + 1 frames (frame f at place f % (G + 1));
-        last, last_xy   per joint the last observation that has LEFT that window, as index (-1: the joint was not seen before the window)
-                        and coordinates;
-        held            per joint G bits: bit k = frame last + 1 + k has left the window as a valid frame in which the joint was held
-                        from ``last`` -- the frames a gap longer than G turns missing when it closes.
-    ``step(frame (J, 2) float32, flags (J,) bool)`` -> (staged, far): ``staged`` lists (frame index, repaired raw (J, 2) float32,
-    frame_valid, state (J,) uint8) for the frames this tick re-stages -- with t the frame pushed, the multiples of ``s_in`` in
-    [max(0, t - G), t], oldest first, then the edge frame (t // seq_stride * seq_stride) where it lies in that range and is no multiple
-    of ``s_in``; with s_in = 1 every frame of the range --, ``far`` the older frames that this tick turns from valid to missing, ascending.
-    The repaired frame is ``repair_joints_host``'s (zeros for a joint it cannot fill); the device stages zeros for a frame that is not valid."""
-
-    def __init__(self, J, G, s_in=1, seq_stride=1):
-        self.J, self.G, self.W, self.s_in, self.seq_stride = int(J), int(G), int(G) + 1, int(s_in), int(seq_stride)
-        if not 1 <= self.G <= MAX_LIVE_REPAIR:
-            raise ValueError(f"G must be in [1, {MAX_LIVE_REPAIR}]")
-        self.frames = 0
-        self.raw = np.zeros((self.W, self.J, 2), np.float32)
-        self.observed = np.zeros((self.W, self.J), bool)
-        self.last = np.full(self.J, -1, np.int64)
-        self.last_xy = np.zeros((self.J, 2), np.float32)
-        self.held = [0] * self.J
-
-    def _joint(self, f, j, lo, newest):
-        """Joint j of frame f under the rule, seen from the frames lo .. newest of the window and ``last`` -> (xy, state)."""
-        G, W, src = self.G, self.W, self.raw
-        if self.observed[f % W, j]:
-            return src[f % W, j], 1
-        before = [g for g in range(lo, f) if self.observed[g % W, j]]
-        after = [g for g in range(f + 1, newest + 1) if self.observed[g % W, j]]
-        l, a = (before[-1], src[before[-1] % W, j]) if before else (int(self.last[j]), self.last_xy[j])
-        r = after[0] if after else None
-        if l >= 0 and r is not None:
-            if r - l - 1 <= G:
-                w = np.float64(f - l) / np.float64(r - l)
-                return (a.astype(np.float64) * (1.0 - w) + src[r % W, j].astype(np.float64) * w).astype(np.float32), 2
-        elif r is not None:
-            if r - f <= G:
-                return src[r % W, j], 2
-        elif l >= 0:
-            if f - l <= G:
-                return a, 2
-        return np.zeros(2, np.float32), 0
-
-    def _frame(self, f, lo, newest):
-        """Frame f under the rule -> (repaired (J, 2) float32, frame_valid, state (J,) uint8)."""
-        out, state = np.zeros((self.J, 2), np.float32), np.zeros(self.J, np.uint8)
-        for j in range(self.J):
-            out[j], state[j] = self._joint(f, j, lo, newest)
-        valid = bool((state == 1).any() and (state != 0).all())
-        return out, valid, state
-
-    def step(self, frame, flags):
-        G, W, J, t = self.G, self.W, self.J, self.frames
-        frame = np.asarray(frame, np.float32).reshape(J, 2)
-        seen_now = (np.asarray(flags).reshape(J) != 0) & np.isfinite(frame).all(axis=1)
-        # 1. frame e leaves the window: what it is under the frames up to t - 1 stays, but for the far list
-        e = t - G - 1
-        if e >= 0:
-            _, valid_e, _ = self._frame(e, e, t - 1)
-            for j in range(J):
-                if self.observed[e % W, j]:
-                    self.last[j], self.last_xy[j], self.held[j] = e, self.raw[e % W, j], 0
-                elif valid_e and self.last[j] >= 0 and e - self.last[j] <= G:
-                    self.held[j] |= 1 << (e - int(self.last[j]) - 1)
-        # 2. file the pushed frame (the place frame e had)
-        self.raw[t % W], self.observed[t % W] = frame, seen_now
-        # 3. a joint seen again after more than G frames: the frames it was held in turn missing
-        lo = max(0, t - G)
-        far = set()
-        for j in range(J):
-            if seen_now[j] and self.last[j] >= 0 and t - self.last[j] - 1 > G and not self.observed[[g % W for g in range(lo, t)], j].any():
-                far |= {int(self.last[j]) + 1 + k for k in range(G) if self.held[j] >> k & 1}
-                self.held[j] = 0
-        for f in far:                                                 # no longer valid frames, for any joint's bits
-            for j in range(J):
-                if self.last[j] >= 0 and 0 <= f - self.last[j] - 1 < G:
-                    self.held[j] &= ~(1 << (f - int(self.last[j]) - 1))
-        # 4. the frames to re-stage
-        cand = [f for f in range(lo, t + 1) if f % self.s_in == 0]
-        edge = t // self.seq_stride * self.seq_stride
-        if edge >= lo and edge % self.s_in != 0:
-            cand.append(edge)
-        self.frames = t + 1
-        return [(f,) + self._frame(f, lo, t) for f in cand], sorted(far)
-
-    def newest_state(self):
-        """(J,) uint8: the state of the newest frame (``StreamSession.joint_state``)."""
-        t = self.frames - 1
-        return self._frame(t, max(0, t - self.G), t)[2]
-
-
-class LiveRootHost(object):
-    """The rule of uu3d_stream_root for ONE slot, in numpy, written to be read: the live form of ``predict.solve_roots_host``.  State --
-        raw, used   the raw coordinates and USED flags of the newest lookahead + 1 frames (frame f at place f % (lookahead + 1));
-        held        the last solved root, float64 (None: no frame was solved yet);
-        root, state what the slot returned last.
-    ``step(frame (J, 2) float32, used_flags, pose)``: one push of the slot while it is active.  ``frame``: the raw frame as pushed, in
-    the model's joint layout; ``used_flags``: None (every joint), one flag for the whole frame, or (J,) flags -- a joint is USED iff its flag
-    is set and both coordinates are finite; ``pose``: the (J, 3) pose the push returned when it is fresh, else None.
-    -> (root (3,) float32, state): a fresh pose is solved against frame c = t - lookahead (t: the frame just filed) -- solved: the root
-    rounded to float32, state 1, and the root is held; not solved (or c < 0): the held root, state 2, or zeros, state 0, when none
-    exists.  ``pose=None`` returns what the last step returned.  A push at which the slot is inactive is no step.  The rule is causal: it
-    holds the last solved root and never interpolates towards a later one (``predict.root_trajectory_host`` does; it sees the whole track)."""
-
-    def __init__(self, J, lookahead, camera, min_root_joints=DEFAULT_MIN_ROOT_JOINTS):
-        self.J, self.W = int(J), int(lookahead) + 1
-        if not 1 <= self.J <= MAX_ROOT_JOINTS or self.W < 1:
-            raise ValueError(f"J must be in [1, {MAX_ROOT_JOINTS}] and lookahead >= 0")
-        self.camera = check_cameras(camera, 1, per="slot")[0]
-        self.min_root_joints = check_min_root_joints(min_root_joints)
-        self.reset()
-
-    def reset(self):
-        self.frames = self.drained = 0                                # (drained: drain ticks taken since the track ended)
-        self.raw = np.zeros((self.W, self.J, 2), np.float32)
-        self.used = np.zeros((self.W, self.J), bool)
-        self.held = None
-        self.root, self.state = np.zeros(3, np.float32), 0
-
-    def step(self, frame, used_flags=None, pose=None):
-        J, W, t = self.J, self.W, self.frames
-        frame = np.asarray(frame, np.float32).reshape(J, 2)
-        flags = np.ones(J, bool) if used_flags is None else np.broadcast_to(np.asarray(used_flags) != 0, (J,))
-        # 1. file the pushed frame
-        self.raw[t % W], self.used[t % W] = frame, flags & np.isfinite(frame).all(axis=1)
-        self.frames = t + 1
-        # 2. solve the frame the fresh pose belongs to
-        return self._settle(t - (W - 1), pose)
-
-    def drain(self, pose=None):
-        """One drain tick of the slot (``StreamSession.finish``; uu3d_stream_root_drain): the track has ENDED, nothing is filed.  The k-th
-        drain tick since the last step (k = 1 .. lookahead; a tick beyond that, or of a slot without frames, changes nothing) solves
-        frame c = frames - 1 - lookahead + k -- one of the last lookahead + 1 frames filed, so it is in the ring -- against ``pose``, the
-        (J, 3) pose of that tick when it is fresh, else None; held root and state by ``step``'s rule.  -> (root, state)."""
-        if self.frames < 1 or self.drained >= self.W - 1:
-            return self.root.copy(), self.state
-        self.drained += 1
-        return self._settle(self.frames - 1 - (self.W - 1) + self.drained, pose)
-
-    def _settle(self, c, pose):
-        """The root of a push or drain tick whose pose (None: not fresh) belongs to frame c -> (root, state)."""
-        J, W = self.J, self.W
-        if pose is None:                                              # not fresh: nothing is solved, nothing changes
-            return self.root.copy(), self.state
-        solved = False
-        if c >= 0:
-            roots, ok = solve_roots_host(np.asarray(pose, np.float32).reshape(1, J, 3), self.raw[c % W][None], self.camera,
-                                         flags=self.used[c % W][None], min_root_joints=self.min_root_joints)
-            solved = bool(ok[0])
-        # 3. the root of this push: solved here, else the last solved one
-        if solved:
-            self.held, self.state = roots[0], 1
-            self.root = roots[0].astype(np.float32)
-        else:
-            self.state = 2 if self.held is not None else 0
-        return self.root.copy(), self.state
-
-
-def _live_filter_arguments(slots, channels, rate, filt, lookahead):
-    slots, channels, lookahead = int(slots), int(channels), int(lookahead)
-    if slots < 1 or not 1 <= channels <= MAX_SMOOTH_CHANNELS or lookahead < 0:
-        raise ValueError(f"slots >= 1, channels in [1, {MAX_SMOOTH_CHANNELS}] and lookahead >= 0, got {slots}, {channels}, {lookahead}")
-    if not isinstance(filt, OneEuro):
-        raise ValueError(f"filt must be a predict.OneEuro, got {filt!r}")
-    return slots, channels, float(frame_rate(rate)), filt, lookahead
-
-
-class LiveOneEuroHost(object):
-    """The rule of uu3d_stream_one_euro in numpy, written to be read: the live form of ``predict.one_euro_host``.  State per slot and
-    channel -- xh, dxh (float64), ``last``: the frame index of the channel's last sample, ``taken``: whether it has taken one.
-    ``step(values (slots, C) float32, frames (slots,), fresh (slots,), active (slots,) or None, state (slots,) or None)`` -> (slots, C)
-    float32.  ``frames``: each slot's frame counter AFTER the push; the fresh value belongs to frame f = frames - 1 - lookahead.
-      an active slot whose value is fresh (and frames >= 1): per channel one sample with n = f - last, anything below 1 counting as 1, at
-          rate / n (``predict.one_euro_sample``); the first one is taken as given.  A non-finite value -- or, with ``state[slot] == 0``,
-          the whole row -- is passed through unchanged and touches nothing.
-      any other slot returns xh rounded once, zeros before the first sample.
-    ``reset(slots=None)``: the chosen slots (None: all) have taken no sample."""
-
-    def __init__(self, slots, channels, rate, filt, lookahead=0):
-        self.slots, self.channels, self.rate, self.filt, self.lookahead = _live_filter_arguments(slots, channels, rate, filt, lookahead)
-        shape = (self.slots, self.channels)
-        self.xh, self.dxh = np.zeros(shape, np.float64), np.zeros(shape, np.float64)
-        self.last, self.taken = np.zeros(shape, np.int64), np.zeros(shape, bool)
-
-    def reset(self, slots=None):
-        which = slice(None) if slots is None else np.asarray(slots, np.int64).reshape(-1)
-        for a in (self.xh, self.dxh, self.last, self.taken):
-            a[which] = 0
-
-    def step(self, values, frames, fresh, active=None, state=None):
-        values = np.asarray(values, np.float32).reshape(self.slots, self.channels)
-        frames = np.asarray(frames, np.int64).reshape(self.slots)
-        fresh = np.asarray(fresh).reshape(self.slots) != 0
-        active = np.ones(self.slots, bool) if active is None else np.asarray(active).reshape(self.slots) != 0
-        keep = np.ones(self.slots, bool) if state is None else np.asarray(state).reshape(self.slots) != 0
-        out = np.zeros((self.slots, self.channels), np.float32)
-        with np.errstate(all="ignore"):
-            for i in range(self.slots):
-                if not (active[i] and fresh[i] and frames[i] >= 1):
-                    out[i] = np.where(self.taken[i], self.xh[i].astype(np.float32), np.float32(0))
-                    continue
-                if not keep[i]:
-                    out[i] = values[i]
-                    continue
-                f = int(frames[i]) - 1 - self.lookahead
-                x = values[i].astype(np.float64)
-                ok = np.isfinite(x)
-                n = np.maximum(f - self.last[i], 1)
-                r = np.float64(self.rate) / n.astype(np.float64)
-                nxh, ndxh = one_euro_sample(x, r, self.filt, self.xh[i], self.dxh[i])
-                later, start = ok & self.taken[i], ok & ~self.taken[i]
-                self.xh[i] = np.where(later, nxh, np.where(start, x, self.xh[i]))
-                self.dxh[i] = np.where(later, ndxh, np.where(start, 0.0, self.dxh[i]))
-                self.last[i] = np.where(ok, f, self.last[i])
-                self.taken[i] |= ok
-                out[i] = np.where(ok, self.xh[i].astype(np.float32), values[i])
-        return out
-
-    def drain(self, values, frames, drained, fresh, chosen=None, state=None):
-        """One drain tick (``StreamSession.finish``): ``step`` at the VIRTUAL counter ``frames + drained`` -- ``frames``: the counters of the
-        ended tracks, ``drained`` (slots,): the drain ticks each slot has taken, this one included --, so the fresh value belongs to frame
-        f = frames - 1 - lookahead + drained; ``chosen``: the slots that drain, as ``step``'s ``active``."""
-        virtual = np.asarray(frames, np.int64).reshape(self.slots) + np.asarray(drained, np.int64).reshape(self.slots)
-        return self.step(values, virtual, fresh, chosen, state)
-
-
-class LiveBonesHost(object):
-    """The rule of uu3d_stream_bones in numpy, written to be read: the live form of ``predict.bone_lengths_host`` / ``fix_bones_host``.
-    State per slot and joint -- ``total`` (float64), the sum of the bone's lengths, and ``count``, how many were added.
-    ``step(poses (slots, J, 3) float32, fresh (slots,), active (slots,) or None)`` -> the rebuilt poses (slots, J, 3) float32.
-      ``lengths=None`` ("track"): an active slot whose pose is fresh first adds the finite, positive length of each of its bones to the
-          sum and counts it; the slot's L is sum / count -- NaN ("not corrected") before the first one, 0 for the tree root.  The mean is
-          CAUSAL: it equals ``predict.bone_lengths_host`` on the fresh poses seen so far, not the mean of the whole track.
-      ``lengths`` (J,) or (slots, J): L is what was given, and there is no state.
-      Then EVERY slot, fresh or not, returns ``predict.fix_bones_host`` of its row with its L: a pure function of the raw pose and the
-      slot's lengths, so a slot that holds its previous raw pose returns its previous fixed pose bit for bit.
-    ``drain(poses, fresh, chosen)``: one drain tick of ``StreamSession.finish`` -- ``step`` with the chosen slots as ``active``.
-    ``lengths``: the (slots, J) float64 table after the last step.  ``reset(slots=None)``: the chosen slots' sums and counts are zero."""
-
-    def __init__(self, slots, skeleton="h36m17", lengths=None):
-        self.slots, self.skeleton = int(slots), skeleton_of(skeleton)
-        J = self.skeleton.joints
-        self.given = None if lengths is None else check_bones(Bones(lengths, self.skeleton), self.slots, J, per="slot")[1]
-        self.total, self.count = np.zeros((self.slots, J), np.float64), np.zeros((self.slots, J), np.int64)
-        self.lengths = self._table()
-
-    def _table(self):
-        if self.given is not None:
-            return self.given.copy()
-        is_bone = np.array(self.skeleton.parents) >= 0
-        with np.errstate(all="ignore"):
-            return np.where(is_bone, np.where(self.count > 0, self.total / self.count.astype(np.float64), np.nan), 0.0)
-
-    def reset(self, slots=None):
-        which = slice(None) if slots is None else np.asarray(slots, np.int64).reshape(-1)
-        self.total[which] = 0
-        self.count[which] = 0
-        self.lengths = self._table()
-
-    def step(self, poses, fresh, active=None):
-        J = self.skeleton.joints
-        X = np.asarray(poses, np.float32).reshape(self.slots, J, 3)
-        fresh = np.asarray(fresh).reshape(self.slots) != 0
-        active = np.ones(self.slots, bool) if active is None else np.asarray(active).reshape(self.slots) != 0
-        if self.given is None:
-            is_bone = np.array(self.skeleton.parents) >= 0
-            with np.errstate(all="ignore"):
-                ln = _bone_offsets(X, self.skeleton)[2]
-                ok = (active & fresh)[:, None] & is_bone & np.isfinite(ln) & (ln > 0)
-                self.total = np.where(ok, self.total + ln, self.total)
-                self.count = self.count + ok
-        self.lengths = self._table()
-        return fix_bones_host(X, np.ones(self.slots, np.int64), self.lengths, self.skeleton)
-
-    def drain(self, poses, fresh, chosen=None):
-        return self.step(poses, fresh, chosen)
-
-
-class LiveOneEuro(object):
-    """The live One-Euro filter on the device: the thin owner of the state block of uu3d_stream_one_euro and of its two launches
-    (``LiveOneEuroHost`` is the same state machine in numpy; the device equals it bit for bit).  ``slots`` rows of ``channels`` float32
-    values each; ``rate``: the frames' rate in Hz (as ``rates.frame_rate`` takes it); ``filt``: a ``predict.OneEuro``; ``lookahead``: the
-    fresh value belongs to frame frames - 1 - lookahead.  ``out``: the (slots, channels) float32 buffer every step writes.
-    ``step(values, frames, fresh, active, state=None, stream=None)``: device tensors -- values (slots, channels) float32 contiguous (only
-    read), frames (slots,) int32, fresh / active / state (slots,) uint8 or bool -- -> ``out``; enqueues on ``stream`` (None: the current
-    one) and never waits.  ``reset(slots=None)``: the given slots (indices; None = all) have taken no sample; ``reset_mask(mask)`` takes a
-    (slots,) uint8 device tensor instead.  ``launch(...)`` / ``reset_launch()``: the two calls as launch-table entries (function,
-    arguments up to the slot mask / the stream), for a session that replays them."""
-
-    def __init__(self, slots, channels, rate, filt, lookahead=0, device="cuda"):
-        import torch
-        self.slots, self.channels, self.rate, self.filt, self.lookahead = _live_filter_arguments(slots, channels, rate, filt, lookahead)
-        self._torch, self._lib = torch, _capi.load_library()
-        self.device = torch.device(device)
-        size = int(self._lib.uu3d_stream_one_euro_bytes(self.slots, self.channels))
-        if size == 0:
-            raise ValueError(f"slots = {self.slots}, channels = {self.channels} are out of uu3d_stream_one_euro's range")
-        self._state = torch.zeros(size, dtype=torch.uint8, device=self.device)
-        self.out = torch.zeros((self.slots, self.channels), dtype=torch.float32, device=self.device)
-
-    def _check(self, t, shape, dtypes, name):
-        if tuple(t.shape) != shape or t.dtype not in dtypes or not t.is_contiguous() or t.device != self.out.device:
-            raise ValueError(f"{name} must be a contiguous {shape} tensor of {' / '.join(str(d) for d in dtypes)} on {self.out.device}")
-        return t
-
-    def launch(self, values, frames, fresh, active, state=None):
-        torch = self._torch
-        T, flags = self.slots, (torch.uint8, torch.bool)
-        if values.dim() < 1 or int(values.shape[0]) != T or values.numel() != T * self.channels:       # ((slots, J, 3) passes as (slots, 3 J))
-            raise ValueError(f"values must be ({T}, {self.channels}), got {tuple(values.shape)}")
-        self._check(values, tuple(values.shape), (torch.float32,), "values")
-        self._check(frames, (T,), (torch.int32,), "frames")
-        for t, name in ((fresh, "fresh"), (active, "active")) + (() if state is None else ((state, "state"),)):
-            self._check(t, (T,), flags, name)
-        f = self.filt
-        return (self._lib.uu3d_stream_one_euro, (T, self.channels, self.lookahead, _ptr(self._state), _ptr(frames), _ptr(active), _ptr(fresh),
-                                                 _ptr(values), _ptr(state), self.rate, f.min_cutoff, f.beta, f.d_cutoff, _ptr(self.out)))
-
-    def reset_launch(self):
-        return (self._lib.uu3d_stream_one_euro_reset, (self.slots, self.channels, _ptr(self._state)))
-
-    def _enqueue(self, call, stream):
-        torch = self._torch
-        fn, args = call
-        with torch.cuda.device(self.out.device):
-            st = torch.cuda.current_stream(self.out.device) if stream is None else stream
-            _capi.check(self._lib, fn(*args, C.c_void_p(st.cuda_stream)), None)
-
-    def step(self, values, frames, fresh, active, state=None, stream=None):
-        self._enqueue(self.launch(values, frames, fresh, active, state), stream)
-        return self.out
-
-    def reset_mask(self, mask=None, stream=None):
-        fn, args = self.reset_launch()
-        if mask is not None:
-            self._check(mask, (self.slots,), (self._torch.uint8, self._torch.bool), "mask")
-        self._enqueue((fn, args + (_ptr(mask),)), stream)
-
-    def reset(self, slots=None, stream=None):
-        torch = self._torch
-        mask = None
-        if slots is not None:
-            h = np.zeros(self.slots, np.uint8)
-            h[np.asarray(slots, np.int64).reshape(-1)] = 1
-            with torch.cuda.device(self.out.device):
-                mask = torch.from_numpy(h).pin_memory().to(self.out.device, non_blocking=True)
-        self.reset_mask(mask, stream)
 
 
 class StreamSession(object):
@@ -687,32 +257,26 @@ class StreamSession(object):
         slots, lookahead = int(slots), int(lookahead)
         if slots < 1:
             raise ValueError("slots >= 1")
-        self.bones = check_bones(bones, slots, config.NUM_KEYPOINTS, int(config.ROOT_KEYTPOINT) if root_relative else None, per="slot")
+        # the refusals shared with ``predict_tracks`` (``options.stage_options``), then the ones only a session has
+        opts = stage_options(config, slots, "slot", root_relative, keypoints, camera, min_root_joints, smooth, bones, repair_joints, fps, out_fps)
+        self.bones, self.pose_filter, self.root_filter, self.keypoints = opts.rigid, opts.pose_filter, opts.root_filter, opts.keypoints
+        self.cameras, self.min_root_joints = opts.cameras, opts.min_root_joints
+        self.smooth_rate = frame_rate(model_fps if fps is None else fps)     # the rate of the frames a push returns
         if self.bones is not None and out_fps is not None:
             raise ValueError("bones together with out_fps is not supported: a push then returns several rows per slot, and the live fix "
                              "rebuilds one pose per slot and push (multi-row emits are out of scope)")
-        self.pose_filter, self.root_filter = check_smooth(smooth, camera is not None)
         if (self.pose_filter is not None or self.root_filter is not None) and out_fps is not None:
             raise ValueError("smooth together with out_fps is not supported: a push then returns several rows per slot, and the live filter "
                              "takes one sample per slot and push (multi-row emits are out of scope)")
-        self.smooth_rate = frame_rate(model_fps if fps is None else fps)     # the rate of the frames a push returns
-        self.cameras, self.min_root_joints = None, None
-        if camera is not None:
-            self.cameras = check_cameras(camera, slots, per="slot")
-            self.min_root_joints = check_min_root_joints(DEFAULT_MIN_ROOT_JOINTS if min_root_joints is None else min_root_joints)
-            if int(config.NUM_KEYPOINTS) > MAX_ROOT_JOINTS:
-                raise ValueError(f"camera needs a model of at most {MAX_ROOT_JOINTS} joints, this one has {int(config.NUM_KEYPOINTS)}")
-            if out_fps is not None:
-                raise ValueError("camera together with out_fps is not supported yet: the returned poses are not at source-frame times, so no "
-                                 "pushed frame is theirs to be solved against (a later change)")
-            if detections is not None and np.ndim(camera) != 1:
-                raise ValueError("detections takes ONE camera (fx, fy, cx, cy), not one per slot: every person of a video shares one space")
-        elif min_root_joints is not None:
-            raise ValueError("min_root_joints needs camera=(fx, fy, cx, cy): it is a parameter of the root solve")
+        if camera is not None and out_fps is not None:
+            raise ValueError("camera together with out_fps is not supported yet: the returned poses are not at source-frame times, so no "
+                             "pushed frame is theirs to be solved against (a later change)")
+        if camera is not None and detections is not None and np.ndim(camera) != 1:
+            raise ValueError("detections takes ONE camera (fx, fy, cx, cy), not one per slot: every person of a video shares one space")
         self.detections, self.association = None, None
         if detections is not None:
             rule = {k: (v if (rule or {}).get(k) is None else rule[k]) for k, v in ASSOCIATION_DEFAULTS.items()}
-            joints = config.NUM_KEYPOINTS if keypoints is None else keypoint_map(keypoints, config.NUM_KEYPOINTS).inputs
+            joints = config.NUM_KEYPOINTS if self.keypoints is None else self.keypoints.inputs
             check_association(slots, detections, int(joints), **rule)
             if fps is not None or out_fps is not None:
                 raise ValueError("detections together with fps / out_fps is not supported yet: the host mirror of the source counters cannot "
@@ -720,15 +284,12 @@ class StreamSession(object):
             self.detections, self.association = int(detections), rule
         elif rule is not None and any(v is not None for v in rule.values()):
             raise ValueError("max_age / max_dist / min_common need detections=D: they are the parameters of the association")
-        check_repair_joints(repair_joints, "finite")
         if repair_joints is not None and int(repair_joints) > MAX_LIVE_REPAIR:
             raise ValueError(f"repair_joints must be at most {MAX_LIVE_REPAIR} in a live session (the frames a tick re-stages and its buffers are "
                              f"fixed when the session is made), got {repair_joints}")
         if repair_joints is not None and (fps is not None or out_fps is not None):
             raise ValueError("repair_joints together with fps / out_fps is not supported yet: a revised source frame would re-make model frames "
                              "that were filed already")
-        if out_fps is not None and fps is None:
-            raise ValueError("out_fps needs fps: the rate of the pushed frames")
         S, s_in, pred = session_strides(config, mask_stride)
         self.rate = None if fps is None else rate_plan(config, fps, lookahead, mask_stride, model_fps, out_fps)
         self.max_out = None if out_fps is None else self.rate.max_out
@@ -738,7 +299,6 @@ class StreamSession(object):
         if not model.arch.compiled_dims:
             raise NotImplementedError("StreamSession needs the frames form of the forward (uu3d_frame_features / uu3d_forward_frames_ex), "
                                       "which models with generic dims do not have")
-        self.keypoints = None if keypoints is None else keypoint_map(keypoints, config.NUM_KEYPOINTS)
         self.repair_joints = None if repair_joints is None else int(repair_joints)
         self.staged_frames = 1 if repair_joints is None else staged_frames(repair_joints, s_in)     # K: frames staged per slot and tick
         self.missed_detections = bool(missed_detections) or repair_joints is not None or detections is not None
@@ -1520,11 +1080,6 @@ def replay_tracks(model, config, tracks, resolutions=None, mask_stride=None, fli
                          "needs the end of the model-rate track")
     import torch
     repair_joints, keypoints, camera, min_root_joints, smooth, bones = _live_options(options, "replay_tracks")
-    place = {} if camera is None and min_root_joints is None else {"camera": camera, "min_root_joints": min_root_joints}
-    if smooth is not None:
-        place["smooth"] = smooth
-    if bones is not None:
-        place["bones"] = bones
     lens = [int(len(t)) for t in tracks]
     T, ticks = len(tracks), max(lens)
     K = J = int(np.asarray(tracks[0]).shape[1])                      # joints pushed, joints returned
@@ -1543,7 +1098,7 @@ def replay_tracks(model, config, tracks, resolutions=None, mask_stride=None, fli
         raise ValueError('valid must be None, "finite" or a list with one (T_i,) array per track')
     s = StreamSession(model, config, T, resolutions=resolutions, mask_stride=mask_stride, flip=flip, lookahead=lookahead,
                       root_relative=root_relative, graph=graph, missed_detections=valid is not None, fps=fps, model_fps=model_fps, out_fps=out_fps,
-                      repair_joints=repair_joints, keypoints=keypoints, **place)
+                      repair_joints=repair_joints, keypoints=keypoints, camera=camera, min_root_joints=min_root_joints, smooth=smooth, bones=bones)
     if camera is not None:                                           # per tick and slot four 32-bit words: the root's bits, the state
         root_words = torch.zeros((ticks, T, 4), dtype=torch.int32, device=model.device)
     tails = None
@@ -1618,7 +1173,6 @@ def replay_detections(model, config, detections, counts=None, valid=None, slots=
     end of the video (n + lookahead rows).  The limit: a track that died in mid-video (``max_age``) still loses the poses of its last
     ``lookahead`` frames -- the death happens on the device, and no drain is run there."""
     import torch
-    from .predict import _host_array
     detections = _host_array(detections)
     if detections.ndim != 4 or detections.shape[3] != 2:
         raise ValueError(f"detections must be (T, D, K, 2), got {detections.shape}")
@@ -1673,39 +1227,12 @@ def parse_args(argv=None):
     p.add_argument("--input", required=True, help=".npz with one (T, J, 2) array per track")
     p.add_argument("--output", required=True, help=".npz to write")
     p.add_argument("--lookahead", type=int, default=0, help="frames the answer may lag behind the newest one (default 0)")
-    p.add_argument("--resolution", type=float, nargs=2, metavar=("W", "H"), default=None,
-                   help="image size in pixels of all tracks; without it the coordinates are taken as normalised already")
+    add_track_options(p, True, "resolution")
     p.add_argument("--drain", action="store_true",
                    help="finish every track at its end: the arrays get T + lookahead rows, row t the pose of frame t - lookahead, so the last "
                         "lookahead frames of a track come out as well; not with --fps")
-    p.add_argument("--mask_missing", action="store_true",
-                   help="a frame with a NaN or Inf coordinate is a missed detection: the track grows by it, the network never sees it")
-    p.add_argument("--fps", type=_rate_argument, default=None, metavar="F",
-                   help="frame rate of the tracks, a float or NUM/DEN (29.97, 30000/1001); without it they are taken at the model's rate.  "
-                        "--lookahead then counts frames of the tracks")
-    p.add_argument("--out_fps", type=_rate_argument, default=None, metavar="G",
-                   help="rate of the poses written, a float or NUM/DEN (needs --fps): NAME then holds every pose the session emitted, in order "
-                        "(n_out, J, 3), and NAME_count the number each tick returned")
-    p.add_argument("--repair_joints", type=int, default=None, metavar="G",
-                   help="fill a joint that is missing for up to G <= 32 consecutive frames from the nearest frames where it was seen, as "
-                        "predict --repair_joints on the track so far; implies --mask_missing; not with --fps")
-    p.add_argument("--min_score", type=float, default=None, metavar="S",
-                   help="with --repair_joints the arrays may be (T, J, 3) with the detector's score in the third channel: a joint counts as "
-                        "seen when score >= S")
-    p.add_argument("--keypoints", default=None, metavar="NAME", choices=sorted(KEYPOINT_PRESETS),
-                   help="the joint layout of the arrays, (T, K, 2): mapped onto the model's joints on the device; scores are then per detector joint")
-    p.add_argument("--camera", type=float, nargs=4, metavar=("FX", "FY", "CX", "CY"), default=None,
-                   help="the camera's intrinsics in the units of the arrays (pixels with --resolution): the output gains NAME__root (T, 3), the "
-                        "position of the skeleton's root in the camera's space at every tick, and NAME__root_state (T,) per track; not with --out_fps")
-    p.add_argument("--min_root_joints", type=int, default=None, metavar="N",
-                   help=f"the fewest observed joints a frame's root is solved from (with --camera; default {DEFAULT_MIN_ROOT_JOINTS})")
-    p.add_argument("--smooth", type=float, nargs=3, metavar=("MIN_CUTOFF", "BETA", "D_CUTOFF"), default=None,
-                   help="pass the poses of every tick through a live One-Euro filter (Hz, 1 / unit speed, Hz); not with --out_fps")
-    p.add_argument("--smooth_root", type=float, nargs=3, metavar=("MIN_CUTOFF", "BETA", "D_CUTOFF"), default=None,
-                   help="the same for the roots (needs --camera)")
-    p.add_argument("--bones", default=None, metavar="track|FILE.npy",
-                   help="constant bone lengths: 'track' rebuilds every pose with the running mean lengths of its track so far, FILE.npy holds a "
-                        "(J,) array of known lengths in the poses' units, indexed by child joint; not with --out_fps")
+    add_track_options(p, True, "mask_missing", "fps", "out_fps", "repair_joints", "min_score", "keypoints", "camera", "min_root_joints", "smooth",
+                      "smooth_root", "bones")
     args = p.parse_args(argv)
     if args.smooth_root is not None and args.camera is None:
         p.error("--smooth_root needs --camera: without it no roots are written")
@@ -1737,18 +1264,12 @@ def main(argv=None):
         tracks = [np.asarray(z[k], np.float32) for k in names]
     if not names:
         raise SystemExit(f"{args.input} holds no arrays")
-    K, skeleton = input_joints(config, args.keypoints)
+    K, _ = input_joints(config, args.keypoints)
     tracks, joint_flags = split_scores(names, tracks, K, args.min_score, args.input)
     for k, t in zip(names, tracks):
         if t.shape[0] < 1:
             raise SystemExit(f"{args.input}[{k}] has shape {t.shape}, expected (T >= 1, {K}, 2)")
-    missing = {"valid": "finite"} if args.mask_missing or args.repair_joints is not None else {}
-    if joint_flags is not None:
-        missing = {"valid": joint_flags}
-    if args.repair_joints is not None:
-        if not 1 <= args.repair_joints <= MAX_LIVE_REPAIR:
-            raise SystemExit(f"--repair_joints must be in [1, {MAX_LIVE_REPAIR}]")
-        missing["repair_joints"] = args.repair_joints
+    options = track_keywords(args, config, names, joint_flags, live=True)
     if args.fps is None and not 0 <= args.lookahead <= max_lookahead(config):
         raise SystemExit(f"--lookahead must be in [0, {max_lookahead(config)}]")
     if args.fps is not None:
@@ -1756,22 +1277,9 @@ def main(argv=None):
             rate_plan(config, args.fps, args.lookahead, out_fps=args.out_fps)
         except ValueError as e:
             raise SystemExit(f"--fps / --out_fps / --lookahead: {e}") from None
-    place = {}
-    if args.camera is not None:
-        try:
-            check_cameras(tuple(args.camera), 1)
-            place = {"camera": tuple(args.camera),
-                     "min_root_joints": check_min_root_joints(DEFAULT_MIN_ROOT_JOINTS if args.min_root_joints is None else args.min_root_joints)}
-        except ValueError as e:
-            raise SystemExit(f"--camera: {e}") from None
-        if any(k.endswith(("__root", "__root_state")) for k in names):
-            raise SystemExit(f"{args.input}: a key ending in __root or __root_state would collide with the arrays --camera writes")
-    place.update(smooth_option(args))
-    place.update(bones_option(args, config.NUM_KEYPOINTS))
     model = _load_model(config, args.weights)
     poses, fresh, *rs = replay_tracks(model, config, tracks, resolutions=None if args.resolution is None else tuple(args.resolution),
-                                      lookahead=args.lookahead, **({"drain": True} if args.drain else {}), **missing, **skeleton, **place,
-                                      **({} if args.fps is None else {"fps": args.fps}), **({} if args.out_fps is None else {"out_fps": args.out_fps}))
+                                      lookahead=args.lookahead, **({"drain": True} if args.drain else {}), **options)
     out = {}
     if rs:
         out.update({k + "__root": np.asarray(r, np.float32) for k, r in zip(names, rs[0])})
