@@ -299,9 +299,13 @@ int uu3d_world_to_cam_2d(const float* world_dev, const float* cams_dev, int32_t 
  *     value is UU3D_ERR_RANGE when the word was set, UU3D_OK otherwise -- the forward itself stays asynchronous and keeps returning
  *     launch errors only;
  *   - OR-ing UU3D_SCHEDULE_EXACT_F32 into `schedule` runs THIS call on the exact-f32 kernels whatever the handle's precision (f32-input
- *     MFMA: the whole float32 range; sequences of <= 128 tokens): the fallback for a batch that overflowed.
+ *     MFMA: the whole float32 range; every sequence length a compiled-dims handle takes, up to 416 tokens -- above 128 the attention is
+ *     the training step's tiled exact-f32 forward without its statistics, csrc/uu3d_attn_long.h): the fallback for a batch that
+ *     overflowed.  Handles with generic dims have no such path (UU3D_ERR_UNSUPPORTED).  The per-CALL bit reaches 416 tokens; the
+ *     handle-wide uu3d_create(precision = f32) is still refused above 128.
  * The Python model(...) does all three: it checks after the call and repeats an overflowed batch in exact f32 (or raises Uu3dRangeError
- * where that path does not exist); pipelines check once, at ForwardPipeline.check_range() / the end of run_eval.
+ * where that path does not exist: generic dims); pipelines check once, at ForwardPipeline.check_range() / the end of run_eval, or run
+ * every forward under the bit (ForwardPipeline(exact_f32=True), predict_windows(exact_f32=True)): nothing to check then.
  */
 #define UU3D_SCHEDULE_EXACT_F32 0x100
 int uu3d_range_status(uu3d_model* model, void* stream, int32_t* out_flag);

@@ -68,6 +68,13 @@ int uu3d_op_attn_long_fwd(const float* qkv_dev, int32_t ld, int32_t D, int32_t B
                           float* out_dev, int32_t ldo, float* stats_dev, void* stream);
 int uu3d_op_attn_long_bwd(const float* qkv_dev, const float* out_dev, const float* dout_dev, const float* stats_dev, int32_t ld, int32_t D,
                           int32_t B, int32_t L, int32_t H, const uint8_t* key_mask_dev, float* dqkv_dev, int32_t ldo, void* stream);
+/* The forward of uu3d_op_attn_long_fwd without the statistics: the kernel an exact-f32 inference call (UU3D_SCHEDULE_EXACT_F32) takes for
+ * its attention layers of 129 .. 416 tokens (attn_long_fwd_kernel<48, false>, launched through the helper the forward launches through).
+ * Same shapes, same argument rules and the same bits in out as uu3d_op_attn_long_fwd: D == 48 H and 1 <= L <= 416
+ * (UU3D_ERR_UNSUPPORTED otherwise); ld and ldo multiples of 4, both pointers 16-byte aligned (UU3D_ERR_INVALID_ARGUMENT otherwise, before
+ * any launch).  Columns of out beyond D (ldo > D) are not written. */
+int uu3d_op_attn_long_infer(const float* qkv_dev, int32_t ld, int32_t D, int32_t B, int32_t L, int32_t H, const uint8_t* key_mask_dev,
+                            float* out_dev, int32_t ldo, void* stream);
 size_t uu3d_op_scratch_floats(void);
 
 /* The forward's row-panel path for a LayerNorm-fed Dense layer on its own (csrc/uu3d_gemm_panel.h; in the model:
@@ -154,7 +161,8 @@ int uu3d_op_ln_dense_wt(const float* x_dev, int32_t ldx, int32_t M, int32_t K, c
  *     49 .. 80 tokens or with H % 4 != 0; UU3D_ATTN_IN_QFRAG or UU3D_ATTN_OUT_FRAG with D != 384 (the fragment strides are written for 72
  *     groups / 384 columns); UU3D_ATTN_AUTO with layouts the kernel its rule names cannot take (plane input up to 48 tokens in row-major
  *     order; f32 input with plane output above 48 tokens; plane input with f32 output);
- *   UU3D_ERR_UNSUPPORTED (as the forward answers): the exact-f32 kernels above 128 tokens, attn_h3_kernel above 416. */
+ *   UU3D_ERR_UNSUPPORTED (as the forward answers at precision f16x3): the exact-f32 kernels above 128 tokens, attn_h3_kernel above 416.
+ *   (A forward CALL at precision f32 takes the tiled exact-f32 kernel there, which is no kernel of this entry: uu3d_op_attn_long_infer.) */
 int uu3d_op_attn_infer(const void* qkv_dev, int32_t in_layout, int32_t D, int32_t B, int32_t L, int32_t H, const uint8_t* key_mask_dev,
                        int32_t kernel, void* out_dev, int32_t out_layout, void* stream);
 /* bytes of the fragment-ordered q | k | v buffer of `rows` tokens: whole 128-row tiles, as the temporal chain allocates it (0: rows < 1) */

@@ -53,7 +53,7 @@ EXPORTED_SYMBOLS = (
 # include/uu3d_ops.h
 OPS_SYMBOLS = (
     "uu3d_op_gemm_tn", "uu3d_op_gemm_tn_h3", "uu3d_op_gemm_nt", "uu3d_op_colsum", "uu3d_op_row_stats", "uu3d_op_ln_bwd",
-    "uu3d_op_attn_fwd", "uu3d_op_attn_bwd", "uu3d_op_attn_long_fwd", "uu3d_op_attn_long_bwd", "uu3d_op_scratch_floats",
+    "uu3d_op_attn_fwd", "uu3d_op_attn_bwd", "uu3d_op_attn_long_fwd", "uu3d_op_attn_long_bwd", "uu3d_op_attn_long_infer", "uu3d_op_scratch_floats",
     "uu3d_op_panel_operand_bytes", "uu3d_op_panel_a_bytes", "uu3d_op_panel_pack", "uu3d_op_ln_dense_panel",
     "uu3d_op_ln_dense_panel_ex", "uu3d_op_panel_a_unpack", "uu3d_op_mlp_operand_bytes", "uu3d_op_mlp_pack", "uu3d_op_mlp_fused",
     "uu3d_op_wt_operand_bytes", "uu3d_op_wt_pack", "uu3d_op_ln_dense_wt",
@@ -416,6 +416,8 @@ def load_library(path=None):
     lib.uu3d_op_attn_long_fwd.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp]
     lib.uu3d_op_attn_long_bwd.restype = C.c_int
     lib.uu3d_op_attn_long_bwd.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp]
+    lib.uu3d_op_attn_long_infer.restype = C.c_int
+    lib.uu3d_op_attn_long_infer.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, i32, vp]
     lib.uu3d_op_panel_operand_bytes.restype = sz
     lib.uu3d_op_panel_operand_bytes.argtypes = [i32]
     lib.uu3d_op_panel_a_bytes.restype = sz

@@ -20,6 +20,8 @@
 //   attn_long_dkv_kernel   wave = key tile: S and dP in the other orientation, [key = lane & 15][query = 16 j + 4 g + r];
 //                          dK += dS^T Q, dV += P^T dO.
 // delta = rowsum(dO o O) is formed by each backward kernel from O and dO as it loads them (no extra buffer, no pre-pass).
+// Inference: attn_long_fwd_kernel<48, false>, the forward without the statistics, is the attention of an exact-f32 forward call
+// (UU3D_SCHEDULE_EXACT_F32) above 128 tokens -- attn_choose / launch_attn_infer in uu3d_launch.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -50,14 +52,22 @@ __device__ inline float key_add(const uint8_t* key_mask, int b, int key, int L) 
     if (key >= L) return -INFINITY;
     return (key_mask != nullptr) ? (key_mask[(size_t)b * L + key] ? 0.0f : 1.0f) * -1e9f : 0.0f;
 }
+// the statistics argument of attn_long_fwd_kernel<DH, STATS>: the [B][H][L] {max, sum} buffer, or nothing at all
+struct NoStats {};
+template <bool STATS> struct StatsArg { using type = float2* __restrict__; };
+template <> struct StatsArg<false> { using type = NoStats; };
+template <bool STATS> using stats_arg_t = typename StatsArg<STATS>::type;
 }  // namespace attn_long
 
 // O (f32, row stride ldo, head h at channels h * 48) and stats[(b H + h) L + q] = {row max, row sum}.
 // grid (B * H, ceil(NT / 4)), block 256.
-template <int DH>
+// STATS = false: the inference instantiation (the exact-f32 forward above 128 tokens, launch_attn_infer) -- the statistics are what only
+// the backward reads, so the last argument is an empty attn_long::NoStats instead of a pointer and nothing is stored for it; the body,
+// and with it every bit of O, is the training instantiation's.
+template <int DH, bool STATS = true>
 __global__ void __launch_bounds__(64 * ATTN_LONG_WAVES)
 attn_long_fwd_kernel(const float* __restrict__ qkv, const int ld, const int D, const int L, const int H,
-                     const uint8_t* __restrict__ key_mask, float* __restrict__ out, const int ldo, float2* __restrict__ stats)
+                     const uint8_t* __restrict__ key_mask, float* __restrict__ out, const int ldo, attn_long::stats_arg_t<STATS> stats)
 {
     using namespace attn_long;
     static_assert(DH == 48, "staging: four threads of 12 channels per row");
@@ -155,8 +165,10 @@ attn_long_fwd_kernel(const float* __restrict__ qkv, const int ld, const int D, c
             const int q = 16 * qt + 4 * g + r;
             if (q < L) out[((size_t)b * L + q) * ldo + h * DH + 16 * t + qi] = ot[t][r] * rr[r];
         }
-    const int q = 16 * qt + qi;
-    if (g == 0 && q < L) stats[(size_t)bh * L + q] = make_float2(m_run, l_run);
+    if constexpr (STATS) {
+        const int q = 16 * qt + qi;
+        if (g == 0 && q < L) stats[(size_t)bh * L + q] = make_float2(m_run, l_run);
+    }
 }
 
 // dQ into dqkv (the layout and row stride ld of qkv, channels h * 48 of the q third).  grid (B * H, ceil(NT / 4)), block 256.

@@ -384,7 +384,7 @@ struct Launcher {
         if (launch_attn_infer(stream, qkv, D, B, L, H, mask, out, split_lo_off, frag, qfrag, rule) != UU3D_OK) {
             status = UU3D_ERR_UNSUPPORTED;
             m->err = qfrag ? "fragment-ordered q | k | v need attn_h3_kernel"
-                           : "attention over more than 128 tokens needs the f16x3 path (precision f16x3, d_t and h_t multiples of 32)";
+                           : "attention over more than 128 tokens needs the f16x3 path (precision f16x3, d_t and h_t multiples of 32) or, up to 416 tokens, a call under UU3D_SCHEDULE_EXACT_F32";
         }
         end();
     }
@@ -708,7 +708,6 @@ int forward_impl(uu3d_model* m, const float* kp2d, const FramesIn* frames, const
     uu3d_config c = m->cfg;                                // (a copy: UU3D_SCHEDULE_EXACT_F32 changes THIS call's arithmetic, not the handle's)
     if (exact_f32) {
         if (m->generic) return fail(m, UU3D_ERR_UNSUPPORTED, "UU3D_SCHEDULE_EXACT_F32: handles with generic dims have no exact-f32 forward");
-        if (c.num_frames > 128) return fail(m, UU3D_ERR_UNSUPPORTED, "UU3D_SCHEDULE_EXACT_F32: the exact-f32 attention holds sequences of <= 128 tokens");
         c.precision = UU3D_PREC_F32;
     }
     if ((c.has_strided_input != 0) != (mask != nullptr))

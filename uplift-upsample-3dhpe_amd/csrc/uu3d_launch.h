@@ -273,10 +273,13 @@ inline int launch_attn_generic(bool backward, const float* qkv, const float* dO,
 // Exact-f32 attention over 1 .. ATTN_LONG_MAX_L tokens, head dim 48, without attention Dropout (uu3d_attn_long.h): the training step's
 // layers of more than 128 tokens.  Forward: O (row stride ldo) and the row statistics stats[B][H][L] = {max, sum}.  Backward: dQ, dK, dV
 // into dqkv in the layout and row stride ld of qkv, from O and dO (both row stride ldo) and the forward's statistics.
+inline bool attn_long_shape_ok(int D, int B, int L, int H) { return B >= 1 && H >= 1 && L >= 1 && L <= ATTN_LONG_MAX_L && D == 48 * H; }
+// one workgroup per (sequence, head) and ATTN_LONG_WAVES query (backward: key) tiles: the grid of all three kernels and of the inference forward
+inline dim3 attn_long_grid(int B, int L, int H) { return dim3(B * H, (L + 16 * ATTN_LONG_WAVES - 1) / (16 * ATTN_LONG_WAVES)); }
 inline int launch_attn_long(bool backward, const float* qkv, const float* O, const float* dO, const float2* stats, int ld, int D, int B, int L,
                             int H, const uint8_t* mask, float* out, float2* stats_out, int ldo, hipStream_t stream) {
-    if (B < 1 || H < 1 || L < 1 || L > ATTN_LONG_MAX_L || D != 48 * H) return UU3D_ERR_UNSUPPORTED;
-    const dim3 grid(B * H, (L + 16 * ATTN_LONG_WAVES - 1) / (16 * ATTN_LONG_WAVES)), block(64 * ATTN_LONG_WAVES);
+    if (!attn_long_shape_ok(D, B, L, H)) return UU3D_ERR_UNSUPPORTED;
+    const dim3 grid = attn_long_grid(B, L, H), block(64 * ATTN_LONG_WAVES);
     if (!backward) {
         hipLaunchKernelGGL(attn_long_fwd_kernel<48>, grid, block, 0, stream, qkv, ld, D, L, H, mask, out, ldo, stats_out);
     } else {
@@ -284,6 +287,14 @@ inline int launch_attn_long(bool backward, const float* qkv, const float* O, con
         hipLaunchKernelGGL(attn_long_dkv_kernel<48>, grid, block, 0, stream, qkv, O, dO, stats, ld, D, L, H, mask, out, ldo);
     }
     return hip_status();
+}
+// The same forward without the statistics (attn_long_fwd_kernel<48, false>: the same bits in O): the inference forward's exact-f32 attention
+// above 128 tokens (launch_attn_infer below) and uu3d_op_attn_long_infer.  Launches only; the caller reads the launch error.
+inline int launch_attn_long_infer(const float* qkv, int ld, int D, int B, int L, int H, const uint8_t* mask, float* out, int ldo, hipStream_t stream) {
+    if (!attn_long_shape_ok(D, B, L, H)) return UU3D_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL((attn_long_fwd_kernel<48, false>), attn_long_grid(B, L, H), dim3(64 * ATTN_LONG_WAVES), 0, stream, qkv, ld, D, L, H, mask, out, ldo,
+                       attn_long::NoStats{});
+    return UU3D_OK;
 }
 
 // ---- forward: row-panel GEMM, fused MLP, few-row GEMM.  The forward's Launcher (uu3d_forward.inc) and the operator ABI (uu3d_ops.hip) launch
@@ -342,7 +353,8 @@ bool launch_gemm_wt(hipStream_t stream, const AL& al, const _Float16* Bh, const 
 
 // ---- forward: temporal self-attention, head dim 48 (uu3d_attn.h, uu3d_attn_h3.h).  Which kernel a launch takes is decided HERE and nowhere else. ----
 constexpr int kAttnDH = 48;
-enum AttnKernel : int { ATTN_AUTO = 0, ATTN_F32_WG = 1, ATTN_HEAD_WAVE = 2, ATTN_H3 = 3 };      // = UU3D_ATTN_* of include/uu3d_ops.h
+enum AttnKernel : int { ATTN_AUTO = 0, ATTN_F32_WG = 1, ATTN_HEAD_WAVE = 2, ATTN_H3 = 3,         // = UU3D_ATTN_* of include/uu3d_ops.h
+                        ATTN_F32_LONG = 4 };     // internal (no UU3D_ATTN_* value, never forced): attn_long_fwd_kernel<48, false>, a CALL at precision f32 above 128 tokens
 // what the choice depends on besides the shape: the call's precision, UU3D_ATTN_F32 / UU3D_ATTN_WG (uu3d_switches.h), and a kernel forced by the caller
 struct AttnRule { int precision = UU3D_PREC_F16X3; bool attn_f32 = false, attn_wg = false; int forced = ATTN_AUTO; };
 // sequences served by attn_h3_kernel (f16x3 products, online softmax; q / k / v as f16 planes from the QKV epilogue): everything
@@ -365,13 +377,16 @@ inline int attn_choose(const AttnRule& r, int L, int H, bool planes_out, bool qf
     // (the chain's fragment-ordered planes cost no split epilogue: attn_h3_kernel below 49 tokens too)
     if (attn_is_h3(r, L, planes_out) || (qfrag && attn_h3_any(r, L))) return ATTN_H3;
     if (qfrag) return ATTN_AUTO;
+    // a call at precision f32 (UU3D_SCHEDULE_EXACT_F32; no planes there) above the register-resident kernels' 128 tokens: the tiled exact-f32
+    // forward of the training step without its statistics (uu3d_attn_long.h).  A rule at precision f16x3 has no exact-f32 kernel up there.
+    if (r.precision == UU3D_PREC_F32 && !planes_out && L > 128 && L <= ATTN_LONG_MAX_L) return ATTN_F32_LONG;
     // one wave per (sequence, head), four heads per workgroup (attn_head_wave_kernel): whenever the heads come in fours and the
     // K / V tiles of four heads fit the LDS; UU3D_ATTN_WG=1 keeps the workgroup-per-item kernel
     // NT <= 3: more, smaller workgroups hide latency better (measured)
     if (!r.attn_wg && hw_fits) return ATTN_HEAD_WAVE;
     return NT <= 8 ? ATTN_F32_WG : ATTN_AUTO;
 }
-// the kernel class a profile records for a family (both exact-f32 kernels are "attn_f32")
+// the kernel class a profile records for a family (every exact-f32 kernel is "attn_f32")
 inline const char* attn_class_name(int kernel) { return kernel == ATTN_H3 ? "attn_h3" : "attn_f32"; }
 
 // One attention launch over B sequences of L tokens, H heads of 48 channels (D = 48 H).
@@ -386,6 +401,7 @@ inline int launch_attn_infer(hipStream_t stream, const float* qkv, int D, int B,
     const int kernel = attn_choose(rule, L, H, split_lo_off != 0, qfrag);
     if (klass) *klass = attn_class_name(kernel);
     if (kernel == ATTN_AUTO) return UU3D_ERR_UNSUPPORTED;
+    if (kernel == ATTN_F32_LONG) return launch_attn_long_infer(qkv, 3 * D, D, B, L, H, mask, out, D, stream);     // qkv = [B L][3 D] floats, out = [B L][D] floats
     const int NT = (L + 15) / 16;
     const int items = B * H;
     const dim3 grid(items);

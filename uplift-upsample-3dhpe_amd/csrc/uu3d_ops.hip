@@ -86,6 +86,14 @@ int uu3d_op_attn_long_fwd(const float* qkv, int32_t ld, int32_t D, int32_t B, in
     if (D != 48 * H || L < 1 || L > ATTN_LONG_MAX_L) return UU3D_ERR_UNSUPPORTED;
     return launch_attn_long(false, qkv, nullptr, nullptr, nullptr, ld, D, B, L, H, mask, out, (float2*)stats, ldo, (hipStream_t)stream);
 }
+// the inference instantiation (no statistics), launched through launch_attn_long_infer as the exact-f32 forward above 128 tokens launches it
+int uu3d_op_attn_long_infer(const float* qkv, int32_t ld, int32_t D, int32_t B, int32_t L, int32_t H, const uint8_t* mask, float* out,
+                            int32_t ldo, void* stream) {
+    if (!qkv || !out || B < 1 || H < 1 || !attn_long_aligned(ld, ldo, {qkv, out})) return UU3D_ERR_INVALID_ARGUMENT;
+    if (D != 48 * H || L < 1 || L > ATTN_LONG_MAX_L) return UU3D_ERR_UNSUPPORTED;
+    const int st = launch_attn_long_infer(qkv, ld, D, B, L, H, mask, out, ldo, (hipStream_t)stream);
+    return st != UU3D_OK ? st : hip_status();
+}
 int uu3d_op_attn_long_bwd(const float* qkv, const float* out, const float* dout, const float* stats, int32_t ld, int32_t D, int32_t B, int32_t L,
                           int32_t H, const uint8_t* mask, float* dqkv, int32_t ldo, void* stream) {
     if (!qkv || !out || !dout || !stats || !dqkv || B < 1 || H < 1 || !attn_long_aligned(ld, ldo, {qkv, out, dout, stats, dqkv})) return UU3D_ERR_INVALID_ARGUMENT;

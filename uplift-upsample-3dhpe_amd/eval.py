@@ -94,7 +94,18 @@ def _window_spans(desc, seq_len, starts, lens):
     return base + np.clip(first, 0, hi), base + np.clip(last, 0, hi)
 
 
-def _predict_windows_reuse(model, generator, descriptors, batch_size, flip, depth, graph, finish, table_bytes):
+def _check_pipeline_range(pipe):
+    """``pipe.check_range()`` at the end of an evaluation; its ``Uu3dRangeError`` names the way out."""
+    from . import _capi
+    try:
+        pipe.check_range()
+    except _capi.Uu3dRangeError as e:
+        what = str(e).split(": ", 1)[-1]
+        raise _capi.Uu3dRangeError(e.status, what + " -- exact_f32=True (predict_windows, evaluate_windows, run_eval) repeats the evaluation with every "
+                                   "forward on the exact-f32 kernels (compiled dims, any sequence length the model takes; slower)") from None
+
+
+def _predict_windows_reuse(model, generator, descriptors, batch_size, flip, depth, graph, finish, table_bytes, exact_f32=False):
     """predict_windows(reuse_frames=True): the spatial stack and spatial_to_temporal_fc once per frame the windows read (uu3d_frame_features),
     the windows forwarded from that table (uu3d_gather_window_frames + uu3d_forward_frames_ex in a ForwardPipeline of the frames form).
 
@@ -130,7 +141,7 @@ def _predict_windows_reuse(model, generator, descriptors, batch_size, flip, dept
     zero_row = halves * S
     table = torch.zeros((zero_row + 1, dt), dtype=torch.float32, device=dev)   # (zeros: the pipeline's warm-up forwards read it)
     rows = min(batch_size, W) * halves
-    pipe = model.pipeline(rows, depth=depth, graph=graph, features=table)
+    pipe = model.pipeline(rows, depth=depth, graph=graph, features=table, exact_f32=exact_f32)
     depth = pipe.depth
     d_vs = torch.empty(len(t.starts), dtype=torch.int64, device=dev)
     fb = 16384                                                         # frames per uu3d_frame_features call
@@ -175,12 +186,12 @@ def _predict_windows_reuse(model, generator, descriptors, batch_size, flip, dept
             _capi.check(lib, lib.uu3d_gather_windows(C.c_void_p(t.kp2d.data_ptr()), C.c_void_p(t.d_starts.data_ptr()), C.c_void_p(t.d_lens.data_ptr()),
                                                      C.c_void_p(fd.data_ptr()), fl_order, n, 1, J, 2, 0, 0, C.c_void_p(kp.data_ptr()),
                                                      C.c_void_p(sm.data_ptr()), None, C.c_void_p(cur.cuda_stream)), None)
-            model._frame_features(kp[:n], feats[:n], cur)
+            model._frame_features(kp[:n], feats[:n], cur, exact_f32=exact_f32)
             table.index_copy_(0, rid, feats[:n])
 
     # the all-zero frame (zero padding), once: its row is the table's last
     kp[:1].zero_()
-    model._frame_features(kp[:1], table[zero_row:], cur)
+    model._frame_features(kp[:1], table[zero_row:], cur, exact_f32=exact_f32)
 
     def take(lo, n, ticket):
         pipe.after(ticket, lambda full, cen: finish(lo, n, cen))
@@ -215,13 +226,13 @@ def _predict_windows_reuse(model, generator, descriptors, batch_size, flip, dept
             take(*p)
         pipe.join()
         torch.cuda.current_stream(dev).synchronize()
-        pipe.check_range()                                             # f16x3 range guard: once per evaluation (features and forwards)
+        _check_pipeline_range(pipe)                                    # f16x3 range guard: once per evaluation (features and forwards)
     finally:
         pipe.close()
 
 
 def predict_windows(model, generator, descriptors, config, batch_size, flip=True, depth=None, graph=True, reuse_frames=False,
-                    frame_table_bytes=FRAME_TABLE_BYTES):
+                    frame_table_bytes=FRAME_TABLE_BYTES, exact_f32=False):
     """Central 3D predictions (W, J, 3) float32 on the device for the given window descriptors: batches of ``batch_size``
     windows, each forwarded together with its mirrored copy when ``flip`` (one launch chain over 2B sequences).
 
@@ -234,15 +245,20 @@ def predict_windows(model, generator, descriptors, config, batch_size, flip=True
     ``reuse_frames=True``: every frame the windows read goes through the spatial stack and spatial_to_temporal_fc ONCE (uu3d_frame_features)
     instead of once per window it sits in; the windows are forwarded from that feature table (uu3d_forward_frames_ex, always through a
     pipeline, graphs as ``graph`` says).  Within ~3e-5 of the default (the s2t GEMM sums in another split-K order).  The table is bounded by
-    ``frame_table_bytes``: windows run in chunks whose frames fit."""
+    ``frame_table_bytes``: windows run in chunks whose frames fit.
+
+    ``exact_f32=True``: every forward (and, with ``reuse_frames``, every feature row) on the exact-f32 kernels whatever the model's precision
+    (``ForwardPipeline(exact_f32=True)``, ``frame_features(exact_f32=True)``): the way out after the ``Uu3dRangeError`` this function raises at
+    its end when the weights' activations left the f16 range.  Always through a pipeline; several times slower than the default."""
     import torch
     if len(descriptors) == 0:
         return torch.empty((0, generator.table.J, 3), dtype=torch.float32, device=generator.table.device)
-    raw = _predict_windows_raw(model, generator, descriptors, batch_size, flip, depth, graph, reuse_frames, frame_table_bytes)
+    raw = _predict_windows_raw(model, generator, descriptors, batch_size, flip, depth, graph, reuse_frames, frame_table_bytes, exact_f32=exact_f32)
     return _unflip(raw, config, flip)
 
 
-def _predict_windows_raw(model, generator, descriptors, batch_size, flip, depth, graph, reuse_frames, frame_table_bytes=FRAME_TABLE_BYTES):
+def _predict_windows_raw(model, generator, descriptors, batch_size, flip, depth, graph, reuse_frames, frame_table_bytes=FRAME_TABLE_BYTES,
+                         exact_f32=False):
     """The body of ``predict_windows`` up to its un-flip: the central predictions as the pipeline leaves them, (1 | 2, W, J, 3) float32 on the
     device -- [0] of the windows, [1] (``flip``) of their mirrored copies, still mirrored.  ``predict.predict_tracks`` un-flips, averages and
     interpolates them in one kernel (uu3d_assemble_tracks).  W >= 1."""
@@ -263,9 +279,10 @@ def _predict_windows_raw(model, generator, descriptors, batch_size, flip, depth,
         raw[:, lo:lo + n].copy_(cen.view(raw.shape[0], n, J, 3))
 
     if reuse_frames:
-        _predict_windows_reuse(model, generator, descriptors, batch_size, flip, depth, graph, finish, frame_table_bytes)
+        _predict_windows_reuse(model, generator, descriptors, batch_size, flip, depth, graph, finish, frame_table_bytes, exact_f32=exact_f32)
         return raw
-    pipe = model.pipeline(rows, depth=depth, graph=graph) if (depth is None or depth > 1 or graph) else None
+    # (exact_f32: through a pipeline even at depth 1 without a graph -- the same launches as the eager loop, with the bit set)
+    pipe = model.pipeline(rows, depth=depth, graph=graph, exact_f32=exact_f32) if (depth is None or depth > 1 or graph or exact_f32) else None
     if pipe is not None:
         depth = pipe.depth
 
@@ -303,7 +320,7 @@ def _predict_windows_raw(model, generator, descriptors, batch_size, flip, depth,
         pipe.join()
         torch.cuda.current_stream(dev).synchronize()               # the slots' buffers go away with the pipeline
         try:
-            pipe.check_range()                                     # f16x3 range guard (include/uu3d.h): once per evaluation, never per batch
+            _check_pipeline_range(pipe)                            # f16x3 range guard (include/uu3d.h): once per evaluation, never per batch
         finally:
             pipe.close()
     return raw
@@ -320,7 +337,7 @@ def _unflip(raw, config, flip):
 
 
 def evaluate_windows(model, generator, desc, config, action_wise=True, batch_size=None, skip_unused_windows=True, log=_log, depth=None,
-                     graph=True, reuse_frames=False, device_metrics=False):
+                     graph=True, reuse_frames=False, device_metrics=False, exact_f32=False):
     """The timed part of ``run_eval``: the windows ``desc`` of ``generator`` (whose table holds the 3D ground truth) forwarded, gathered over
     the ranks and reported.  -> the report dict with "num_windows", "num_forwarded" and "seconds" (this function's wall time)."""
     import torch
@@ -337,7 +354,7 @@ def evaluate_windows(model, generator, desc, config, action_wise=True, batch_siz
     lo, hi = udist.shard_bounds(len(run), rank, world)
     bs = int(batch_size or config.BATCH_SIZE)
     local = predict_windows(model, gen, desc[run[lo:hi]], config, bs, flip=bool(config.EVAL_FLIP), depth=depth, graph=graph,
-                            reuse_frames=reuse_frames)
+                            reuse_frames=reuse_frames, exact_f32=exact_f32)
     allp = udist.allgather_errors(local)                             # (len(run), J, 3) in rank order: the payload is a few KB per rank
     # ground truth of the window centres, root shifted (eval.py:183-186); the centre of a window is frame `index` of its video
     mid = desc[:, 1].astype(np.int64) + table.starts[desc[:, 0]]
@@ -373,7 +390,8 @@ def evaluate_windows(model, generator, desc, config, action_wise=True, batch_siz
 
 
 def run_eval(config, dataset_name, dataset_path, dataset2d_path, test_subset, weights_path=None, model=None, action_wise=True,
-             batch_size=None, skip_unused_windows=True, log=_log, depth=None, graph=True, reuse_frames=False, device_metrics=False):
+             batch_size=None, skip_unused_windows=True, log=_log, depth=None, graph=True, reuse_frames=False, device_metrics=False,
+             exact_f32=False):
     """eval.py:34-253.  Returns ``evaluation.evaluate_predictions``'s dict (+ "num_windows", "num_forwarded", "seconds").
 
     ``device_metrics=True``: the report (keyframe interpolation, MPJPE / N-MPJPE / P-MPJPE, per-action means) is computed on the device
@@ -382,7 +400,8 @@ def run_eval(config, dataset_name, dataset_path, dataset2d_path, test_subset, we
 
     ``batch_size`` defaults to ``config.BATCH_SIZE``; ``depth`` / ``graph``: batches in flight and hipGraph replay of the forward
     (``predict_windows``; depth 1 without graph = the reference's eager loop, same numbers); ``reuse_frames``: each frame's spatial
-    features computed once (``predict_windows``).  With torch.distributed initialised, the windows to run are split
+    features computed once (``predict_windows``); ``exact_f32``: every forward on the exact-f32 kernels (``predict_windows``: after a
+    ``Uu3dRangeError``).  With torch.distributed initialised, the windows to run are split
     contiguously over the ranks and the predictions all-gathered; every rank returns the same report."""
     from .net.uplift_upsample_transformer_constructor import build_uplift_upsample_transformer
     assert not (weights_path is None and model is None)
@@ -408,7 +427,8 @@ def run_eval(config, dataset_name, dataset_path, dataset2d_path, test_subset, we
     log(f"Sequences: {len(desc)}")
     log(f"Running evaluation on '{test_subset}' with {len(desc)} examples")
     return evaluate_windows(model, gen, desc, config, action_wise=action_wise, batch_size=batch_size, skip_unused_windows=skip_unused_windows,
-                            log=log, depth=depth, graph=graph, reuse_frames=reuse_frames, device_metrics=device_metrics)
+                            log=log, depth=depth, graph=graph, reuse_frames=reuse_frames, device_metrics=device_metrics,
+                            exact_f32=exact_f32)
 
 
 def run_eval_multi_mask_stride(config, *args, log=_log, **kwargs):

@@ -376,7 +376,8 @@ class UpliftUpsampleTransformer(object):
         return bool(flag.value)
 
     def _exact_f32_available(self):
-        return bool(self.arch.compiled_dims) and self.arch.num_frames <= 128
+        # every length a compiled-dims handle takes (<= 416 tokens): above 128 the call's attention is the tiled exact-f32 kernel
+        return bool(self.arch.compiled_dims)
 
     def _mask_u8(self, stride_mask):
         """(B, N) bool / uint8 mask as uint8 bytes on the model's device.  A bool tensor is reinterpreted (torch bools are
@@ -560,7 +561,7 @@ class UpliftUpsampleTransformer(object):
         if guard and self.check_range(main, raise_error=False):
             if not self._exact_f32_available():
                 raise _capi.Uu3dRangeError(_capi.UU3D_ERR_RANGE, "activations beyond the f16 range of the f16x3 products (or non-finite inputs), and "
-                                           "this model has no exact-f32 forward to fall back to (generic dims or > 128 tokens)")
+                                           "this model has no exact-f32 forward to fall back to (generic dims)")
             if not self._range_warned:
                 self._range_warned = True
                 import warnings
@@ -667,12 +668,13 @@ class UpliftUpsampleTransformer(object):
         return full, central
 
     # ---- graph replay / several batches in flight ------------------------------------------------
-    def pipeline(self, batch, depth=None, graph=True, post=None, features=None):
+    def pipeline(self, batch, depth=None, graph=True, post=None, features=None, exact_f32=False):
         """``depth`` independent batches in flight on ``depth`` HIP streams, each replaying its own hipGraph of the forward
         (pipeline.ForwardPipeline): the throughput path of an evaluation loop (eval.py:147-152).  ``features``: the frames form
-        (a per-frame feature table, fixed for the pipeline's life; the slots take rows instead of 2D windows)."""
+        (a per-frame feature table, fixed for the pipeline's life; the slots take rows instead of 2D windows).  ``exact_f32``: every
+        slot's forward on the exact-f32 kernels (weights whose activations leave the f16 range; slower, nothing for ``check_range()`` to find)."""
         from ..pipeline import ForwardPipeline
-        return ForwardPipeline(self, batch, depth=depth, graph=graph, post=post, features=features)
+        return ForwardPipeline(self, batch, depth=depth, graph=graph, post=post, features=features, exact_f32=exact_f32)
 
     def capture(self, batch):
         """One forward at a fixed batch size as a hipGraph: ``f = model.capture(128); full, central = f([x, mask])`` replays

@@ -95,7 +95,7 @@ class _Slot(object):
 
 class ForwardPipeline(object):
 
-    def __init__(self, model, batch, depth=None, graph=True, post=None, streams=None, features=None):
+    def __init__(self, model, batch, depth=None, graph=True, post=None, streams=None, features=None, exact_f32=False):
         """``depth``: batches in flight; None = TWO per HIP hardware queue for batches up to 128 sequences, one above (``distinct_queue_streams(per_queue=2)``: 8 / 4 -- round 5: with the temporal
         chain's launches of one workgroup per 128 rows, eight forwards in flight keep the chip full where four do not: 187 k against 181 k
         sequences/s at batch 128; the round-4 launches measure the same with four and eight), an int up to that number takes that many of
@@ -106,7 +106,12 @@ class ForwardPipeline(object):
         ``features``: the FRAMES FORM (include/uu3d.h, uu3d_forward_frames_ex): a (R, d_t) float32 table of per-frame features
         (``model.frame_features``), fixed for the pipeline's life -- the graphs hold its address; its contents may be rewritten between
         batches on a stream the slots wait for.  The slots' static inputs are then (batch, N) int32 table rows (``uu3d_gather_window_frames``)
-        and the stride masks: ``acquire`` / ``preload`` / ``submit`` take rows where the 2D form takes windows."""
+        and the stride masks: ``acquire`` / ``preload`` / ``submit`` take rows where the 2D form takes windows.
+        ``exact_f32``: every slot's forward (either form, captured in the slot's graph like any other) runs on the exact-f32 kernels whatever
+        the model's precision -- UU3D_SCHEDULE_EXACT_F32 of include/uu3d.h OR-ed into the schedule the slot passes anyway.  For weights whose
+        activations leave the f16 range of the f16x3 products (``check_range()`` raised): the whole float32 range at every length the model
+        takes, several times slower, and no range check to fail (the library checks f16x3 forwards only).  The default is the pipeline as it
+        was: the same launches, the same bits.  Models with generic dims have no exact-f32 forward: the first launch raises."""
         import torch
         if depth is not None and depth < 1:
             raise ValueError("depth >= 1")
@@ -126,6 +131,7 @@ class ForwardPipeline(object):
                                      or not features.is_contiguous() or features.device != model.device):
             raise ValueError(f"features must be a contiguous (R, {model.arch.d_temporal}) float32 tensor on {model.device}")
         self.features = features
+        self.exact_f32 = bool(exact_f32)
         a = model.arch
         dev = model.device
         self._slots = []
@@ -175,10 +181,10 @@ class ForwardPipeline(object):
         # (include/uu3d.h, uu3d_forward_ex), so a model(...) call on another thread keeps its own schedule
         if self.features is not None:
             self.model._forward_frames(self.features, s.x[:n], s.m[:n] if s.m is not None else None, s.full[:n] if s.full is not None else None,
-                                       s.central[:n], self._keys[i], s.stream, schedule=1 if self.depth > 1 else 0)
+                                       s.central[:n], self._keys[i], s.stream, schedule=1 if self.depth > 1 else 0, exact_f32=self.exact_f32)
         else:
             self.model._forward(s.x[:n], s.m[:n] if s.m is not None else None, s.full[:n] if s.full is not None else None,
-                                s.central[:n], self._keys[i], s.stream, schedule=1 if self.depth > 1 else 0)
+                                s.central[:n], self._keys[i], s.stream, schedule=1 if self.depth > 1 else 0, exact_f32=self.exact_f32)
         if self.post is not None:
             s.extra = self.post(s.full[:n] if s.full is not None else None, s.central[:n], i)
 
@@ -286,7 +292,8 @@ class ForwardPipeline(object):
     def check_range(self):
         """Range guard of precision f16x3 (include/uu3d.h, RANGE CONTRACT) for everything submitted so far: waits for every slot, then raises
         ``Uu3dRangeError`` if a forward produced non-finite outputs (activations beyond the f16 range, or non-finite inputs).  Pipelines do
-        not check per batch (that would be a host synchronisation per batch); callers check once -- ``eval.predict_windows`` at its end."""
+        not check per batch (that would be a host synchronisation per batch); callers check once -- ``eval.predict_windows`` at its end.
+        A pipeline built with ``exact_f32=True`` sets no flag (its forwards are not f16x3 forwards): the check returns clean."""
         for s in self._slots:
             s.stream.synchronize()
         return self.model.check_range()
