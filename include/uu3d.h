@@ -315,10 +315,26 @@ int uu3d_forward_ex(uu3d_model* model, const float* kp2d_dev, const uint8_t* str
 int uu3d_set_schedule(uu3d_model* model, int32_t schedule);
 
 /*
- * FRAMES FORM of the forward (evaluation over overlapping windows; compiled dims only -- handles with generic dims return
- * UU3D_ERR_UNSUPPORTED).  The spatial stack and spatial_to_temporal_fc work on one frame at a time: a frame's d_t features do not depend
- * on the window it sits in, only the token blend and the temporal PE that follow do.  So features are computed once per frame and every
- * window reads them from a table:
+ * FRAMES FORM of the forward (evaluation over overlapping windows; live tracks).  The spatial stack and spatial_to_temporal_fc work on
+ * one frame at a time: a frame's d_t features do not depend on the window it sits in, only the token blend and the temporal PE that
+ * follow do.  So features are computed once per frame and every window reads them from a table.
+ *
+ * Handles with generic dims (anything but J = 17, d_s = 32, d_t = 384, 8 heads, MLP ratio 2) have the form under ONE rule: the spatial
+ * stack of a frame runs in one workgroup (csrc/uu3d_spatial_generic.h), so the frame has to fit a workgroup's 160 KiB of LDS --
+ *     4 * (2 J d_s + J (max(3 d_s, h_s) + 1) + hg J (J | 1)) <= 163840 bytes,   hg = clamp(2048 / (J (J | 1)), 1, heads)  (integer division)
+ * (the residual stream, a LayerNorm / attention-output buffer, q | k | v or the hidden layer, the logits of hg heads).  Every J <= 32 with
+ * d_s <= 128 and MLP ratio <= 4 fits; J = 128 with d_s = 128 does not.  A handle whose frame does not fit HAS NO FRAMES FORM:
+ * uu3d_frame_features_bytes returns 0, and uu3d_frame_features, uu3d_forward_frames_ex and every uu3d_stream_* entry return
+ * UU3D_ERR_UNSUPPORTED before anything is launched, with the needed and the available bytes in uu3d_last_error.  Its window forward
+ * (uu3d_forward_ex) is unaffected.  There is no second path.  On a generic handle uu3d_frame_features is that kernel (exact f32, weights
+ * read from the handle's master buffer) followed by spatial_to_temporal_fc as the generic GEMM; uu3d_forward_frames_ex is the generic
+ * forward from its temporal stack on, under the same rules (workspace uu3d_workspace_bytes(batch)); UU3D_SCHEDULE_EXACT_F32 stays refused.
+ * CAPTURED GRAPHS AND TRAINING on a generic handle: the operand packs of the generic GEMMs (spatial_to_temporal_fc, the temporal and strided
+ * blocks, the heads) are shared with the training step, and the test "are the packs the handle's, else repack" runs on the HOST when a call
+ * is enqueued -- so it is part of a capture, not of its replays.  A training step on the same handle (uu3d_train_forward_backward with a
+ * Trainer's own parameter buffer) repacks from that buffer; a graph captured before it (a pipeline's, a live session's tick) then replays on
+ * the Trainer's packs without an error.  Direct calls are safe (they repack).  After training on a handle, capture again: build a new
+ * pipeline / StreamSession.  (As for the window form of a generic handle in a captured pipeline.)
  *
  *   uu3d_frame_features(model, frames_dev (F, J, 2) f32, F, features_dev (F, d_t) f32, workspace, bytes, schedule, stream)
  *       the spatial stack and spatial_to_temporal_fc with its bias on F frames -- no blend, no PE.  The kernel choice of the forward
@@ -351,7 +367,8 @@ int uu3d_forward_frames_ex(uu3d_model* model, const float* features_dev, int64_t
                            float* const* attention_out, void* workspace_dev, size_t workspace_bytes, int32_t schedule, void* stream);
 
 /*
- * LIVE TRACKS (stream.StreamSession; compiled dims only -- handles with generic dims return UU3D_ERR_UNSUPPORTED).  `slots` tracks grow by
+ * LIVE TRACKS (stream.StreamSession; every handle that has the FRAMES FORM above -- a generic handle whose frame does not fit the LDS
+ * returns UU3D_ERR_UNSUPPORTED; the root, bone and association stages keep their own limit of 64 joints).  `slots` tracks grow by
  * one frame of 2D keypoints per tick; after the push that made frame t the newest of a slot, the pose of frame c = t - lookahead comes out
  * when c >= 0 and c % pred_stride == 0 (the windows eval.needed_windows keeps), computed from the window uu3d_gather_window_frames writes
  * for a video of t + 1 frames centred on c with a globally aligned stride mask: frames that do not exist yet are padded as the end of a

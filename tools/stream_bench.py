@@ -3,6 +3,8 @@ way to get the same pose without it: the host builds this tick's window and stri
 uploads them with their mirrored copies and calls ``model([x, mask])`` once -- the spatial stack over all frames of every window, every tick.
 A tick = host clock from the call to the synchronised result (a live consumer reads every pose); host input in all three variants.
 Median (and 90th percentile) over --ticks ticks after --warmup ticks, per config and slot count.
+A case is CONFIG:s_in, or generic:J,d_s,d_t,heads,N:s_in for a model with generic dims (e.g. --cases generic:25,16,64,4,27:4): its tick
+(the one-workgroup-per-frame spatial stack + the generic forward's second stage in the graph) beside the same baseline.
    python tools/stream_bench.py [--slots 1,8,64] [--cases h36m_81:4,h36m_351:5] [--ticks 300] [--warmup 60] [--lookahead 0] [--fps F [--out_fps G]]
                                 [--repair_joints G] [--detections D] [--camera FX FY CX CY] [--smooth] [--bones] [--drain]
 --fps F (a float or NUM/DEN): microseconds per PUSH of StreamSession(fps=F) -- one source frame in, one pose out, on average
@@ -35,7 +37,7 @@ medians.  Informational: no threshold.  The numpy baseline is left out.
 and at the largest one, as finish_us, beside the plain tick of the same session in the same process (graph_us); finish_over_tick is their
 ratio, finish_per_drain_tick_us = finish_us / lookahead.  Each finish follows 8 pushes of a new track; the first finish (allocation and the
 capture) is not timed.  Use --slots 1,64.  The numpy baseline is left out."""
-import argparse, json, os, sys, time
+import argparse, json, os, re, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
@@ -79,13 +81,33 @@ def main():
     W, H = 1920, 1080
     total = args.warmup + args.ticks
     results = []
-    for case in args.cases.split(","):
-        name, msv = case.split(":")
+    for case in re.findall(r"generic:[\d,]+:\d+|[^,]+", args.cases):      # (a generic case has commas of its own)
+        name, msv = case.rsplit(":", 1)
         ms = int(msv)
-        cfg = util.load_config(name)
+        if name.startswith("generic:"):
+            # generic:J,d_s,d_t,heads,N:s_in -- a model with generic dims on h36m_81's other settings (two spatial and two temporal blocks,
+            # MLP ratio 2; STRIDES: N's prime factors; the flip table: joint 0 stays, the others swap in pairs)
+            gJ, gds, gdt, gh, gN = (int(v) for v in name.split(":", 1)[1].split(","))
+            cfg = util.load_config("h36m_81")
+            strides, rest = [], gN
+            for p in (3, 5, 7):
+                while rest % p == 0:
+                    strides.append(p); rest //= p
+            if rest != 1 or not strides:
+                ap.error("generic: N must be a product of 3s, 5s and 7s")
+            cfg.NUM_KEYPOINTS, cfg.SPATIAL_EMBED_DIM, cfg.TEMPORAL_EMBED_DIM, cfg.NUM_HEADS = gJ, gds, gdt, gh
+            cfg.SEQUENCE_LENGTH, cfg.STRIDES, cfg.PADDINGS, cfg.MLP_RATIO, cfg.MASK_STRIDE = gN, strides, None, 2.0, ms
+            cfg.SPATIAL_TRANSFORMER_BLOCKS, cfg.TEMPORAL_TRANSFORMER_BLOCKS = 2, 2
+            cfg.ROOT_KEYTPOINT = min(int(cfg.ROOT_KEYTPOINT), gJ - 1)
+            flip_order = list(range(gJ))
+            for i in range(1, gJ - 1, 2):
+                flip_order[i], flip_order[i + 1] = i + 1, i
+            cfg.AUGM_FLIP_KEYPOINT_ORDER = flip_order
+        else:
+            cfg = util.load_config(name)
         arch = pkg.arch_from_config(cfg)
         model = pkg.build_uplift_upsample_transformer(cfg, weights=pkg.init_weights(arch, seed=0, perturb=0.1))
-        N, S, J = cfg.SEQUENCE_LENGTH, cfg.SEQUENCE_STRIDE, 17
+        N, S, J = cfg.SEQUENCE_LENGTH, cfg.SEQUENCE_STRIDE, int(cfg.NUM_KEYPOINTS)
         order = np.asarray(cfg.AUGM_FLIP_KEYPOINT_ORDER)
         d_order = torch.as_tensor(order, dtype=torch.long, device=model.device)
         for T in (int(v) for v in args.slots.split(",")):

@@ -31,6 +31,7 @@
 #include "uu3d_spatial.h"
 #include "uu3d_spatial_h3.h"
 #include "uu3d_spatial_p16.h"
+#include "uu3d_spatial_generic.h"
 #include "uu3d_misc.h"
 #include "uu3d_metrics.h"
 #include "uu3d_tracks.h"
@@ -157,6 +158,20 @@ int fail(uu3d_model* m, int code, const std::string& msg) {
         if (e__ != hipSuccess)                                                                  \
             return fail(m, UU3D_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__));   \
     } while (0)
+
+// The frames form of a handle with generic dims (include/uu3d.h, FRAMES FORM): the spatial stack of a frame runs in one workgroup
+// (uu3d_spatial_generic.h), so the frame has to fit the CU's LDS.  One rule, asked by every entry point of the frames form before it
+// launches anything; compiled dims always have the form.
+inline bool has_frames_form(const uu3d_model* m) {
+    const uu3d_config& c = m->cfg;
+    return !m->generic || spatial_generic_lds_bytes(c.num_keypoints, c.d_spatial, c.h_spatial, c.num_heads) <= SG_LDS_LIMIT;
+}
+int no_frames_form(uu3d_model* m, const std::string& who) {
+    const uu3d_config& c = m->cfg;
+    return fail(m, UU3D_ERR_UNSUPPORTED, who + ": this handle with generic dims has no frames form: the spatial stack of one frame needs " +
+                std::to_string(spatial_generic_lds_bytes(c.num_keypoints, c.d_spatial, c.h_spatial, c.num_heads)) + " bytes of LDS, a workgroup has " +
+                std::to_string(SG_LDS_LIMIT) + " (the window forward is unaffected)");
+}
 
 void add_weight(uu3d_model* m, const std::string& name, std::vector<int64_t> dims) {
     WeightRec r;
@@ -349,6 +364,12 @@ int uu3d_create(const uu3d_config* c, int device, uu3d_model** out) {
 static void train_free(uu3d_model* m);
 static int generic_forward(uu3d_model* m, const float* kp2d, const uint8_t* mask, int32_t B, float* full_out, float* central_out,
                            float* const* attn_out, void* workspace, size_t workspace_bytes, void* stream);      // uu3d_train_entry.inc
+namespace { struct FramesIn; }
+static int generic_forward_frames(uu3d_model* m, const FramesIn& frames, const uint8_t* mask, int32_t B, float* full_out, float* central_out,
+                                  float* const* attn_out, void* workspace, size_t workspace_bytes, void* stream);   // uu3d_train_entry.inc
+static size_t generic_frame_features_bytes(const uu3d_model* m, long F);                                                // uu3d_train_entry.inc
+static int generic_frame_features(uu3d_model* m, const float* frames_dev, int32_t F, float* features, void* workspace, size_t workspace_bytes,
+                                  void* stream);                                                                        // uu3d_train_entry.inc
 void uu3d_destroy(uu3d_model* m) {
     if (!m) return;
     (void)hipSetDevice(m->device);

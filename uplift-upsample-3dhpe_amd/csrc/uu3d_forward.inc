@@ -701,7 +701,7 @@ int forward_impl(uu3d_model* m, const float* kp2d, const FramesIn* frames, const
     if (!m->committed) return fail(m, UU3D_ERR_NOT_READY, "uu3d_commit_weights has not been called");
     if ((!kp2d && !frames) || !central_out || !workspace || B < 1) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "null buffer or batch < 1");
     if (frames != nullptr) {
-        if (m->generic) return fail(m, UU3D_ERR_UNSUPPORTED, "uu3d_forward_frames_ex: handles with generic dims have no frames form (compiled dims only)");
+        if (!has_frames_form(m)) return no_frames_form(m, "uu3d_forward_frames_ex");
         if (!frames->features || !frames->rows || frames->num_rows < 1) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_forward_frames_ex: null features / rows or no feature rows");
         if (((uintptr_t)frames->features & 15) != 0 || (m->cfg.d_temporal % 4) != 0) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_forward_frames_ex: features must be 16-byte aligned");
     }
@@ -717,7 +717,8 @@ int forward_impl(uu3d_model* m, const float* kp2d, const FramesIn* frames, const
     if (m->generic) {
         // dims other than the compiled ones: the training-mode chain, forward only, with every stochastic layer off (no DropPath draws, no token
         // mask, Dropout rates 0): vit / u_u_t in inference mode
-        const int r = generic_forward(m, kp2d, mask, B, full_out, central_out, attn_out, workspace, workspace_bytes, stream_);
+        const int r = frames != nullptr ? generic_forward_frames(m, *frames, mask, B, full_out, central_out, attn_out, workspace, workspace_bytes, stream_)
+                                        : generic_forward(m, kp2d, mask, B, full_out, central_out, attn_out, workspace, workspace_bytes, stream_);
         if (r == UU3D_OK && c.precision == UU3D_PREC_F16X3) {
             const bool has_full = c.full_output && c.temporal_depth > 0 && full_out != nullptr;
             hipLaunchKernelGGL(range_check_kernel, dim3(256), dim3(256), 0, (hipStream_t)stream_, has_full ? full_out : central_out,
@@ -777,8 +778,8 @@ FrameWorkspace carve_frames(const uu3d_model* m, long F, char* base) {
 }  // namespace
 
 size_t uu3d_frame_features_bytes(const uu3d_model* m, int32_t frames) {
-    if (!m || frames < 1 || m->generic) return 0;
-    return carve_frames(m, frames, nullptr).bytes;
+    if (!m || frames < 1 || !has_frames_form(m)) return 0;
+    return m->generic ? generic_frame_features_bytes(m, frames) : carve_frames(m, frames, nullptr).bytes;
 }
 
 int uu3d_frame_features(uu3d_model* m, const float* frames_dev, int32_t F, float* features, void* workspace, size_t workspace_bytes,
@@ -787,11 +788,13 @@ int uu3d_frame_features(uu3d_model* m, const float* frames_dev, int32_t F, float
     const bool exact_f32 = (schedule & UU3D_SCHEDULE_EXACT_F32) != 0;
     schedule &= ~UU3D_SCHEDULE_EXACT_F32;
     if (schedule != UU3D_SCHEDULE_LATENCY && schedule != UU3D_SCHEDULE_THROUGHPUT) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "schedule must be UU3D_SCHEDULE_LATENCY or UU3D_SCHEDULE_THROUGHPUT");
-    if (m->generic) return fail(m, UU3D_ERR_UNSUPPORTED, "uu3d_frame_features: handles with generic dims have no frames form (compiled dims only)");
+    if (!has_frames_form(m)) return no_frames_form(m, "uu3d_frame_features");
+    if (m->generic && exact_f32) return fail(m, UU3D_ERR_UNSUPPORTED, "UU3D_SCHEDULE_EXACT_F32: handles with generic dims have no exact-f32 forward");
     if (!m->committed) return fail(m, UU3D_ERR_NOT_READY, "uu3d_commit_weights has not been called");
     if (!frames_dev || !features || !workspace || F < 1) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "null buffer or frames < 1");
     if ((long)F * m->cfg.num_keypoints > (1L << 30)) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "too many frames");
     if (((uintptr_t)workspace & 255) != 0) return fail(m, UU3D_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+    if (m->generic) return generic_frame_features(m, frames_dev, F, features, workspace, workspace_bytes, stream_);
     const FrameWorkspace w = carve_frames(m, F, (char*)workspace);
     if (workspace_bytes < w.bytes) return fail(m, UU3D_ERR_WORKSPACE, "workspace smaller than uu3d_frame_features_bytes(frames)");
     uu3d_config c = m->cfg;

@@ -40,7 +40,7 @@ enum : int { kStreamRate = 1, kStreamState = 2, kStreamOut = 4 };   // the argum
 // point takes them (`parts`) -- the rate, the state block, the output rate, checked in this order; then the layouts and kernel parameters.
 int stream_resolve(uu3d_model* m, const uu3d_stream_config* s, const uu3d_stream_rate* r, const uu3d_stream_out* o, const void* state,
                    const int parts, const char* who, StreamCall& c) {
-    if (m->generic) return fail(m, UU3D_ERR_UNSUPPORTED, std::string(who) + ": handles with generic dims have no frames form (compiled dims only)");
+    if (!has_frames_form(m)) return no_frames_form(m, who);
     if (const char* e = stream_config_error(m, s)) return fail(m, UU3D_ERR_INVALID_ARGUMENT, std::string(who) + ": " + e);
     if (parts & kStreamRate) if (const char* e = stream_rate_error(r)) return fail(m, UU3D_ERR_INVALID_ARGUMENT, std::string(who) + ": " + e);
     if ((parts & kStreamState) && (!state || ((uintptr_t)state & 255) != 0))

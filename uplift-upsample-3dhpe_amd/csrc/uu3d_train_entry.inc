@@ -31,6 +31,72 @@ static int generic_forward(uu3d_model* m, const float* kp2d, const uint8_t* mask
     return train_forward_only(m, k, false, (hipStream_t)stream);
 }
 
+// uu3d_forward_frames_ex on a generic handle: the same call with its input tokens written from a feature table (TrainCtx::forward_frames);
+// generic_forward's rules -- every stochastic layer off, OUTPUT_BN in inference mode, the training lock, the repack when the packs are not
+// the handle's
+static int generic_forward_frames(uu3d_model* m, const FramesIn& frames, const uint8_t* mask, int32_t B, float* full_out, float* central_out,
+                                  float* const* attn_out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (m->ts == nullptr || m->gparams == nullptr) return fail(m, UU3D_ERR_NOT_READY, "uu3d_commit_weights has not been called");
+    std::lock_guard<std::recursive_mutex> lock(m->train_mu);
+    TrainCall k = train_call(m, m->gparams, nullptr, mask, B, nullptr, nullptr, nullptr, 0.f, full_out, central_out, workspace, workspace_bytes);
+    k.drop_rate = 0.f; k.attn_drop_rate = 0.f; k.bn_inference = true; k.attn_out = attn_out;
+    const int chk = train_check(m, k, false);
+    if (chk != UU3D_OK) return chk;
+    HIPCHK(m, hipSetDevice(m->device));
+    int st = TrainCtx(m, k, (hipStream_t)stream).forward_frames(frames);
+    if (hipGetLastError() != hipSuccess && st == UU3D_OK) st = UU3D_ERR_HIP;
+    return st == UU3D_OK ? UU3D_OK : fail(m, st, "uu3d_forward_frames_ex: launch failed");
+}
+
+// uu3d_frame_features on a generic handle: the spatial stack of every frame in one workgroup (uu3d_spatial_generic.h, reads the handle's
+// master buffer) -> S (F, J d_s), then spatial_to_temporal_fc with its bias as the tiled GEMM on the handle's operand pack.  The workspace:
+// S and the GEMM's split-K slab -- not the training workspace.
+namespace {
+struct GenericFrameWs { float *S, *slab; size_t bytes; };
+GenericFrameWs generic_frame_carve(const uu3d_model* m, long F, char* base) {
+    const size_t nS = align_up((size_t)F * m->cfg.num_keypoints * m->cfg.d_spatial * 4, 256);
+    GenericFrameWs w{};
+    w.bytes = nS + kSlabFloats * 4;
+    if (base) { w.S = (float*)base; w.slab = (float*)(base + nS); }
+    return w;
+}
+}  // namespace
+static size_t generic_frame_features_bytes(const uu3d_model* m, long F) { return generic_frame_carve(m, F, nullptr).bytes; }
+
+static int generic_frame_features(uu3d_model* m, const float* frames_dev, int32_t F, float* features, void* workspace, size_t workspace_bytes,
+                                  void* stream_) {
+    if (m->ts == nullptr || m->gparams == nullptr) return fail(m, UU3D_ERR_NOT_READY, "uu3d_commit_weights has not been called");
+    const GenericFrameWs w = generic_frame_carve(m, F, (char*)workspace);
+    if (workspace_bytes < w.bytes) return fail(m, UU3D_ERR_WORKSPACE, "workspace smaller than uu3d_frame_features_bytes(frames)");
+    std::lock_guard<std::recursive_mutex> lock(m->train_mu);        // (the s2t operand pack and its repack are the handle's)
+    TrainState& t = *m->ts;
+    const uu3d_config& c = m->cfg;
+    hipStream_t stream = (hipStream_t)stream_;
+    HIPCHK(m, hipSetDevice(m->device));
+    if (t.packed_from != m->gparams) {
+        const int r = uu3d_train_repack(m, m->gparams, stream_);
+        if (r != UU3D_OK) return fail(m, r, "uu3d_frame_features: repack failed");
+    }
+    m->prof_used = 0;
+    const int J = c.num_keypoints, ds = c.d_spatial, dt = c.d_temporal;
+    const NetW& nw = t.nw;
+    SpatialGenericParams p{};
+    p.params = m->gparams; p.blocks = t.d_sg_blocks;
+    p.emb_w = nw.emb_w; p.emb_b = nw.emb_b; p.pe = nw.pe_s; p.norm_g = nw.sn_g; p.norm_b = nw.sn_b;
+    p.J = J; p.ds = ds; p.hs = c.h_spatial; p.H = c.num_heads; p.depth = c.spatial_depth; p.hg = spatial_generic_head_group(J, c.num_heads);
+    const size_t lds = spatial_generic_lds_bytes(J, ds, c.h_spatial, c.num_heads);      // (<= 160 KiB: has_frames_form, asked by the caller)
+    allow_lds<spatial_generic_kernel<SG_ROWS>>(SG_LDS_LIMIT);
+    hipLaunchKernelGGL(spatial_generic_kernel<SG_ROWS>, dim3((unsigned)F), dim3(SG_THREADS), lds, stream, frames_dev, p, w.S);
+    const float* Bt = t.tarena + nw.s2t.fwd;
+    const _Float16* Bh = t.tarena_h ? t.tarena_h + nw.s2t.fwd : nullptr;
+    const _Float16* Bl = t.tarena_h ? Bh + t.tarena_floats : nullptr;
+    int st = launch_gemm(ALoadPlain{w.S, J * ds, F, J * ds}, Bt, F, dt, J * ds, EpBias{features, m->gparams + nw.s2t_b, dt}, w.slab, kSlabFloats, stream, Bh, Bl);
+    if (c.precision == UU3D_PREC_F16X3)           // range guard (include/uu3d.h): non-finite features set the model's sticky word
+        hipLaunchKernelGGL(range_check_kernel, dim3(256), dim3(256), 0, stream, (const float*)features, (long)F * dt, (const float*)features, 0L, m->d_range);
+    if (hipGetLastError() != hipSuccess && st == UU3D_OK) st = UU3D_ERR_HIP;
+    return st == UU3D_OK ? UU3D_OK : fail(m, st, "uu3d_frame_features: launch failed");
+}
+
 int uu3d_train_forward_backward(uu3d_model* m, const float* params, const float* kp2d, const uint8_t* mask, const float* gt3d,
                                 int32_t B, int32_t batch_size_norm, float w_center, float w_seq, int32_t root,
                                 const float* dp_rates3, const float* dp_u, float* loss_out, float* full_out, float* central_out,

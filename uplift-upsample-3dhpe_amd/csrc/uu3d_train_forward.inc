@@ -173,7 +173,11 @@ struct TrainCtx {
     }
     void droppath_gates();
     void block_forward(int L, const BlockAct& a, const BlockW& bw, const uint8_t* amask, float* maps, const Gates& g, unsigned site);
+    int forward_begin();
+    void forward_spatial();
+    int forward_temporal();
     int forward();
+    int forward_frames(const FramesIn& frames);
     int backward(float* grads, float gscale, const float* inv_scale_dev, float* grad_kp2d, bool ready, float* accum = nullptr);
 };
 
@@ -235,8 +239,26 @@ void TrainCtx::block_forward(int L, const BlockAct& a, const BlockW& bw, const u
 }
 
 // The training-mode forward of a call, activations kept in the workspace: DropPath gates, the network, both heads -- everything up to
-// where the loss starts.  Returns the status of its launches (hipGetLastError is the caller's).
+// where the loss starts.  Returns the status of its launches (hipGetLastError is the caller's).  Two stages: the spatial stage (the spatial
+// stack, spatial_to_temporal_fc with the token blend and the temporal PE -> t_in) and everything from the temporal stack on
+// (forward_temporal); the frames form of a generic handle (forward_frames) writes t_in from a feature table and runs the second stage alone.
 int TrainCtx::forward() {
+    const int r = forward_begin();
+    if (r != UU3D_OK) return r;
+    forward_spatial();
+    return forward_temporal();
+}
+
+// uu3d_forward_frames_ex on a generic handle: t_in = (masked ? token : features[rows]) + temporal PE, then the second stage
+int TrainCtx::forward_frames(const FramesIn& frames) {
+    const int r = forward_begin();
+    if (r != UU3D_OK) return r;
+    hipLaunchKernelGGL(frames_to_tokens_kernel, ew_grid((long long)Mt * (dt / 4)), dim3(256), 0, stream, frames.features, frames.num_rows, frames.rows,
+                       k.mask, P(nw.in_token), P(nw.pe_t), (long)Mt, N, dt, w.t_in);
+    return forward_temporal();
+}
+
+int TrainCtx::forward_begin() {
     // The operand packs belong to whichever parameter buffer was repacked last.  On a generic-dims handle the model's inference forward (its own
     // buffer, uu3d_commit_weights) and a Trainer's step (its master buffer) alternate: a call whose `params` is not the packs' source
     // regenerates them first (ADVICE round 4: an EMA export left EMA-valued kernels under the trained biases of the next step).
@@ -244,12 +266,13 @@ int TrainCtx::forward() {
         const int r = uu3d_train_repack(m, k.params, stream);
         if (r != UU3D_OK) return r;
     }
-    float* full = k.full_out ? k.full_out : w.full;
-    float* central = k.central_out ? k.central_out : w.central;
     m->prof_used = 0;
-    const bool dropping = k.drop_rate > 0.f || k.attn_drop_rate > 0.f;
     droppath_gates();
+    return UU3D_OK;
+}
 
+void TrainCtx::forward_spatial() {
+    const bool dropping = k.drop_rate > 0.f || k.attn_drop_rate > 0.f;
     // =============================== forward (activations kept) ===============================
     if (t.sp_frag != nullptr && !dropping) {               // (the Dropout sites of the spatial stack exist in the unfused chain only)
         // the whole spatial stack in ONE launch (uu3d_spatial_h3.h, TRAIN = true): same arithmetic as the inference kernel, plus the
@@ -297,6 +320,11 @@ int TrainCtx::forward() {
     const float* mtoken = keep_rows != nullptr ? P(nw.mtoken) : nullptr;      // (nullptr without LEARNABLE_MASKED_TOKEN: value 0)
     gemm(ALoadPlain{w.S, J * ds, Mt, J * ds}, TA(nw.s2t.fwd), Mt, dt, J * ds,
          EpSpatialToTemporal{w.t_in, P(nw.s2t_b), dt, k.mask, P(nw.in_token), P(nw.pe_t), N, keep_rows, mtoken});
+}
+
+int TrainCtx::forward_temporal() {
+    float* full = k.full_out ? k.full_out : w.full;
+    float* central = k.central_out ? k.central_out : w.central;
     const float* pe_x0 = ns > 0 ? P(t.bw_x[0].pe) : nullptr;      // strided block 1 reads the temporal stack's output + its positional encoding
     for (int i = 0; i < Lt; ++i) {
         const BlockAct& a = w.tb[i]; const BlockW& bw = t.bw_t[i];

@@ -573,6 +573,12 @@ class UpliftUpsampleTransformer(object):
                 raise _capi.Uu3dRangeError(_capi.UU3D_ERR_RANGE, "non-finite outputs even in exact f32: the inputs or weights are not finite")
 
     # ---- frames form (include/uu3d.h, FRAMES FORM): features once per frame, windows read them from a table -------------------
+    @property
+    def has_frames_form(self):
+        """Whether ``frame_features`` / ``forward_frames`` / ``StreamSession`` exist for this model: always with the compiled dims; with generic
+        dims when one frame's spatial stack fits a workgroup's LDS (the rule of include/uu3d.h, FRAMES FORM)."""
+        return bool(self.arch.compiled_dims) or int(self._lib.uu3d_frame_features_bytes(self._h, 1)) > 0
+
     def _frame_features(self, frames, out, stream, exact_f32=False):
         """One uu3d_frame_features call: (F, J, 2) float32 frames -> ``out`` (F, d_t) float32, on ``stream``."""
         torch = self._torch

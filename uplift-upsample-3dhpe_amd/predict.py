@@ -157,7 +157,7 @@ def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, fl
     Frames are predicted by the model where ``eval.needed_windows`` keeps their window (every SEQUENCE_STRIDE-th with TEST_STRIDED_EVAL) and
     interpolated linearly in between by the rules of ``evaluation.interpolate_between_keyframes``; frames behind the last predicted one
     repeat it.  ``reuse_frames`` / ``batch_size`` (default config.BATCH_SIZE) / ``depth`` / ``graph`` go to ``eval.predict_windows``; a
-    model with generic dimensions has no frames form and runs the window forward.  One rank only.
+    model with generic dimensions runs the window forward here whatever ``reuse_frames`` says (its results stay what they were).  One rank only.
 
     Missed detections -- ``valid``: None = every frame is an observation (today's call, the same bits).  "finite": a frame with a NaN or
     Inf coordinate is MISSING.  A list with one (T_i,) array or tensor per track (host or device; with ``keyframes_only`` one entry per given

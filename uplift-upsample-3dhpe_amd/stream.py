@@ -191,7 +191,10 @@ class StreamSession(object):
         are normalised already, else one (w, h) in pixels or one per slot.  ``mask_stride`` / ``flip`` / ``root_relative`` as
         ``predict.predict_tracks``.  ``lookahead`` = a: frames the answer may lag behind the newest one, 0 <= a <=
         (SEQUENCE_LENGTH // 2) * SEQUENCE_STRIDE; with a at its maximum every window is complete.  ``graph``: replay one captured hipGraph
-        per tick instead of enqueueing the five steps.  Models with generic dims have no frames form: NotImplementedError.
+        per tick instead of enqueueing the five steps.  A model with generic dims whose frame does not fit a workgroup's LDS has no
+        frames form (``model.has_frames_form``): NotImplementedError; with ``flip`` its config's AUGM_FLIP_KEYPOINT_ORDER must permute its joints.
+        A session on a generic model must be rebuilt after a Trainer has stepped on that model: the captured tick replays on whatever the
+        shared operand packs hold (include/uu3d.h, FRAMES FORM).
         ``missed_detections=True``: a pushed frame may be MISSING (``push(valid=...)``, or a row with a NaN / Inf coordinate) -- the slot's
         track still grows by that frame, but no window ever shows it to the network (``predict.predict_tracks(valid=...)``); the tick runs
         uu3d_stream_stage_valid / uu3d_stream_commit_valid.  Needs a model with strided input (ValueError).  False: today's session.
@@ -296,9 +299,16 @@ class StreamSession(object):
         if self.rate is None and not 0 <= lookahead <= max_lookahead(config):
             raise ValueError(f"lookahead must be in [0, {max_lookahead(config)}] = (SEQUENCE_LENGTH // 2) * SEQUENCE_STRIDE, got {lookahead}")
         res = check_resolutions(resolutions, slots, per="slot")
-        if not model.arch.compiled_dims:
+        if not getattr(model, "has_frames_form", model.arch.compiled_dims):
             raise NotImplementedError("StreamSession needs the frames form of the forward (uu3d_frame_features / uu3d_forward_frames_ex), "
-                                      "which models with generic dims do not have")
+                                      "which this model with generic dims does not have: one frame's spatial stack does not fit a workgroup's "
+                                      "LDS (include/uu3d.h, FRAMES FORM)")
+        J = int(getattr(model.arch, "num_keypoints", 17))
+        if (bool(config.EVAL_FLIP) if flip is None else bool(flip)) and not model.arch.compiled_dims:
+            order = np.asarray(config.AUGM_FLIP_KEYPOINT_ORDER).reshape(-1)
+            if order.shape[0] != J or sorted(int(v) for v in order) != list(range(J)):
+                raise ValueError(f"flip=True on a model with {J} keypoints: config.AUGM_FLIP_KEYPOINT_ORDER must be a permutation of range({J}), "
+                                 f"got {order.shape[0]} entries")
         self.repair_joints = None if repair_joints is None else int(repair_joints)
         self.staged_frames = 1 if repair_joints is None else staged_frames(repair_joints, s_in)     # K: frames staged per slot and tick
         self.missed_detections = bool(missed_detections) or repair_joints is not None or detections is not None
