@@ -964,6 +964,57 @@ int uu3d_stream_bones(int32_t slots, int32_t num_keypoints, void* bones_state_de
 int uu3d_stream_bones_reset(int32_t slots, int32_t num_keypoints, void* bones_state_dev, const uint8_t* slot_mask_dev, void* stream);
 
 /*
+ * JOINT ROTATIONS (rotations.joint_rotations, predict.predict_tracks(rotations=...), stream.StreamSession(rotations=...), bvh.write_bvh):
+ * joint positions are not what a character rig, a game engine or a BVH file takes -- they take ROTATIONS.  This call turns every pose into
+ * one unit quaternion (w, x, y, z; v' = q v q*) per joint: joint j's rotation relative to its parent's frame, the root's relative to the
+ * pose's space, such that the REST POSE turned by them points every bone where the pose has it.  No model, no state: the call takes the
+ * joint count J <= 64 (beyond: UU3D_ERR_UNSUPPORTED) and runs on any (frames, J, 3) f32 buffer.  No accuracy figure is claimed.
+ * THE TABLES (rotations.Rotations makes them, uploaded once per device).  tree_dev (4, J) i32: row 0 the parents (-1: the ONE tree root),
+ * row 1 every joint's PRIMARY child, row 2 its SECONDARY child (-1: none; by default the two lowest child indices), row 3 its level, the
+ * number of bones between it and the root; depth: the largest level, in [0, 63].  rest_dev (J, 3) f64: the UNIT direction of the bone from
+ * joint j's parent to j in the rest pose, by child joint (the root's row is not read).  An index out of range counts as "none", a joint
+ * whose level is outside [0, depth] gets the identity and flag 0: nothing is ever read or written out of bounds.
+ * THE RULE (rotations.joint_rotations_host is it in numpy, bit for bit; its docstring is the normative text).  All in f64, every operation
+ * rounded once in the written order, no fused multiply-add, IEEE sqrt and division, no trigonometry.
+ *     dot(a, b) = (a0 b0 + a1 b1) + a2 b2;   cross(a, b) = (a1 b2 - a2 b1, a2 b0 - a0 b2, a0 b1 - a1 b0);   |a| = sqrt(dot(a, a))
+ *     mul(a, b):  w = ((aw bw - ax bx) - ay by) - az bz;   x = ((aw bx + ax bw) + ay bz) - az by;
+ *                 y = ((aw by - ax bz) + ay bw) + az bx;   z = ((aw bz + ax by) - ay bx) + az bw
+ *     unit(q) = q / sqrt(((w w + x x) + y y) + z z), component by component
+ *     rotate(q, v):  t = 2 cross(q.xyz, v);  v'_c = (v_c + q.w t_c) + cross(q.xyz, t)_c
+ *     arc(a, b; axis) = unit((|a| |b| + dot(a, b), cross(a, b))).  ANTIPARALLEL -- the scalar part <= 0 and all three cross components
+ *         == 0 --: unit((0, axis)) where an axis is given (the twist below), else unit((0, cross(a, e))), e the coordinate axis of a's
+ *         smallest-magnitude component, ties to the lowest index.
+ * Per frame, level by level from the root outwards; Qpar is the parent's global quaternion Q, (1, 0, 0, 0) for the root:
+ *     p has no child:  Q[p] = Qpar, local = (1, 0, 0, 0) exactly, flag 1.
+ *     else  b = (double) x[c1] - (double) x[p] per coordinate, c1 the primary child.  |b| not finite or not > 0 (DEGENERATE):  Q[p] = Qpar,
+ *           local = (1, 0, 0, 0) exactly, flag 0.  Otherwise flag 1 and
+ *           Q1 = unit(mul(arc(rotate(Qpar, rest[c1]), b), Qpar)).
+ *     p has a secondary child c2:  u = b / |b|;  s = rotate(Q1, rest[c2]),  t = x[c2] - x[p];  both are projected onto the plane across
+ *           the primary bone, s_c = s_c - u_c dot(s, u), t likewise.  Where both are finite and neither is all == 0:
+ *           Q[p] = unit(mul(arc(s, t; u), Q1)) -- a TWIST about the primary bone, which it leaves where it is (hence the half turn of the
+ *           antiparallel case about u).  Otherwise the twist is the identity, Q[p] = Q1, and the flag stays 1.
+ *     local[p] = unit(mul(conj(Qpar), Q[p])), negated as a whole where w < 0, or w == 0 and the first non-zero of x, y, z is negative;
+ *           then each component rounded once to f32.  global[p] = Q[p] rounded to f32, its sign as it came out.
+ * WHAT THE RULE CANNOT SEE: positions do not show the twist about a bone with one child -- it is zero relative to the parent, so the
+ * orientation of end segments (head, hands, feet) is limited.
+ *
+ *   uu3d_joint_rotations(poses_dev (frames, J, 3) f32, frames <= 2^32, J, tree_dev, depth, rest_dev, row_mask_dev (frames) u8 or NULL:
+ *       a frame whose entry is 0 is left untouched -- the live session's "not fresh", local_out_dev (frames, J, 4) f32, global_out_dev
+ *       (frames, J, 4) f32 or NULL, flags_out_dev (frames, J) u8 or NULL: 1 = determined from the pose, 0 = fell back, stream): one
+ *       launch, one wave per frame (four frames per workgroup), lane j owns joint j; a parent's Q reaches its children through LDS.  The
+ *       quaternion buffers are 16-byte aligned and written with 16-byte stores.  frames == 0: nothing is launched.
+ *   uu3d_joint_rotations_reset(slots, J, local_dev, global_dev or NULL, flags_dev or NULL, slot_mask_dev (slots) u8 or NULL = every slot,
+ *       stream): the chosen slots' quaternions are (1, 0, 0, 0) and their flags 0; beside uu3d_stream_reset, with the same mask.
+ * LIVE: no state block.  A session's tick ends with uu3d_joint_rotations on the pose buffer push returns, row_mask_dev = fresh.
+ * Every output element has one writer, no atomics, the caller's buffers are only read: bitwise repeatable, capturable.
+ */
+int uu3d_joint_rotations(const float* poses_dev, int64_t frames, int32_t num_keypoints, const int32_t* tree_dev, int32_t depth,
+                         const double* rest_dev, const uint8_t* row_mask_dev, float* local_out_dev, float* global_out_dev,
+                         uint8_t* flags_out_dev, void* stream);
+int uu3d_joint_rotations_reset(int32_t slots, int32_t num_keypoints, float* local_dev, float* global_dev, uint8_t* flags_dev,
+                               const uint8_t* slot_mask_dev, void* stream);
+
+/*
  * LIVE TRACKS: END OF A TRACK (stream.StreamSession.finish): a session with lookahead a answers the push that made frame t the newest with
  * the pose of frame t - a, so a track that ENDS still owes the poses of its last a frames.  A DRAIN TICK moves the centre of the slot's
  * window one frame towards its newest frame without filing a frame: for a slot with `frames` frames the k-th drain tick (k = 1 .. a) gives

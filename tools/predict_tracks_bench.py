@@ -22,9 +22,12 @@ walk over the frames of a track); the result must equal predict.one_euro_host on
 --bones: also predict_tracks(bones="track") -- with --camera predict_tracks(camera=..., bones="track") -- next to the same call without bones in
 the same process: bones_extra_ms is the difference of the two medians (two more launches: the lengths, the fix); the poses must equal
 predict.fix_bones_host with predict.bone_lengths_host on the result without bones, bit for bit.  Informational: no threshold.
+--rotations: also predict_tracks(rotations=True) next to the plain call in the same process: rotations_extra_ms is the difference of the two
+medians (one more launch), host_rotations_ms the plain call followed by .cpu() of the poses and the numpy rule
+(predict.joint_rotations_host); the quaternions must equal that rule on the returned poses bit for bit.  Informational: no threshold.
    python tools/predict_tracks_bench.py [--tracks 40] [--frames 2500] [--batch 512] [--reps 3] [--cases h36m_351:5,h36m_81:4] [--missing 0.3]
                                         [--fps 30] [--repair_joints 5 --missing_joints 0.1] [--keypoints coco17]
-                                        [--camera 1145 1145 960 540] [--smooth] [--bones]"""
+                                        [--camera 1145 1145 960 540] [--smooth] [--bones] [--rotations]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -46,6 +49,7 @@ def main():
                     help="also time predict_tracks(camera=...) against .cpu() and the numpy rule behind the plain call")
     ap.add_argument("--smooth", action="store_true", help="also time predict_tracks(smooth=True) (with --camera: poses and roots) against the same call without")
     ap.add_argument("--bones", action="store_true", help='also time predict_tracks(bones="track") (with --camera: with the camera) against the same call without')
+    ap.add_argument("--rotations", action="store_true", help="also time predict_tracks(rotations=True) against the plain call and against .cpu() and the numpy rule")
     args = ap.parse_args()
     import numpy as np, torch
     import uplift_upsample_3dhpe_amd as pkg
@@ -158,6 +162,13 @@ def main():
             return predict.predict_tracks(model, cfg, px, resolutions=(W, H), mask_stride=int(msv), flip=True, reuse_frames=reuse, batch_size=args.batch,
                                           bones="track", **({} if args.camera is None else {"camera": tuple(args.camera)}))
 
+        def rotations_path():
+            return predict.predict_tracks(model, cfg, px, resolutions=(W, H), mask_stride=int(msv), flip=True, reuse_frames=reuse, batch_size=args.batch,
+                                          rotations=True)
+
+        def rotations_host():
+            return predict.joint_rotations_host(torch.cat(new_path(), 0).cpu().numpy())[0]
+
         row = dict(config=name, mask_stride=int(msv), tracks=args.tracks, frames=total, batch=args.batch, reuse_frames=reuse)
         outs = {}
         cases = [("predict_tracks", new_path), ("predict_tracks_to_host", lambda: new_path(True)), ("composition", composition)]
@@ -180,6 +191,8 @@ def main():
             cases.append(("predict_tracks_smooth", smooth_path))
         if args.bones:
             cases.append(("predict_tracks_bones", bones_path))
+        if args.rotations:
+            cases += [("predict_tracks_rotations", rotations_path), ("host_rotations", rotations_host)]
         for key, fn in cases:
             fn()
             torch.cuda.synchronize()
@@ -231,6 +244,10 @@ def main():
             got = torch.cat(outs["predict_tracks_bones"][0] if args.camera is not None else outs["predict_tracks_bones"], 0).cpu().numpy()
             want = predict.fix_bones_host(plain, lens, predict.bone_lengths_host(plain, lens))
             row["bones_bits_equal"] = bool(np.array_equal(got.view(np.uint32), want.view(np.uint32)))
+        if args.rotations:
+            row["rotations_extra_ms"] = round(row["predict_tracks_rotations_ms"] - row["predict_tracks_ms"], 1)
+            got = torch.cat(outs["predict_tracks_rotations"][1], 0).cpu().numpy()
+            row["rotations_bits_equal"] = bool(np.array_equal(got.view(np.uint32), outs["host_rotations"].view(np.uint32)))
         row["device"] = torch.cuda.get_device_name(0)
         print(json.dumps(row), flush=True)
         results.append(row)

@@ -6,7 +6,7 @@ Median (and 90th percentile) over --ticks ticks after --warmup ticks, per config
 A case is CONFIG:s_in, or generic:J,d_s,d_t,heads,N:s_in for a model with generic dims (e.g. --cases generic:25,16,64,4,27:4): its tick
 (the one-workgroup-per-frame spatial stack + the generic forward's second stage in the graph) beside the same baseline.
    python tools/stream_bench.py [--slots 1,8,64] [--cases h36m_81:4,h36m_351:5] [--ticks 300] [--warmup 60] [--lookahead 0] [--fps F [--out_fps G]]
-                                [--repair_joints G] [--detections D] [--camera FX FY CX CY] [--smooth] [--bones] [--drain]
+                                [--repair_joints G] [--detections D] [--camera FX FY CX CY] [--smooth] [--bones] [--rotations] [--drain]
 --fps F (a float or NUM/DEN): microseconds per PUSH of StreamSession(fps=F) -- one source frame in, one pose out, on average
 model_fps / F sub-ticks -- next to the plain session pushed at the model's rate (the cost of one model tick); the lookahead is raised to
 the smallest one the rate allows.  The numpy baseline is left out.
@@ -29,6 +29,10 @@ camera_minus_graph_us is the difference of the two medians.  The numpy baseline 
 captured tick, with --camera two (poses and roots) -- as smooth_graph_us next to the tick of the same session without smooth (graph_us;
 with --camera both sessions have the camera), measured side by side in the same way.  smooth_minus_graph_us is the difference of the two
 medians.  The numpy baseline is left out.
+--rotations (alone or with --camera, not with --smooth, --bones or the other options): the tick of StreamSession(rotations=True) -- one
+more launch, the last of the captured tick -- as rotations_graph_us next to the tick of the same session without it (graph_us) and next
+to that tick followed by .cpu() of the poses and the numpy rule, rotations.joint_rotations_host (rotations_host_us), measured side by
+side in the same way.  rotations_minus_graph_us is the difference of the first two medians.  Informational: no threshold.
 --bones (alone or with --camera, not with --smooth or the other options): the tick of StreamSession(bones="track") -- one more launch
 behind the emit, in front of the root solve -- as bones_graph_us next to the tick of the same session without bones (graph_us; with
 --camera both sessions have the camera), measured side by side in the same way.  bones_minus_graph_us is the difference of the two
@@ -56,11 +60,14 @@ def main():
     ap.add_argument("--camera", type=float, nargs=4, metavar=("FX", "FY", "CX", "CY"), default=None)
     ap.add_argument("--smooth", action="store_true")
     ap.add_argument("--bones", action="store_true")
+    ap.add_argument("--rotations", action="store_true")
     ap.add_argument("--drain", action="store_true")
     args = ap.parse_args()
     if args.bones and (args.smooth or args.fps is not None or args.repair_joints is not None or args.detections is not None):
         ap.error("--bones is not measured together with --smooth / --fps / --repair_joints / --detections")
-    if args.drain and (args.bones or args.smooth or args.camera is not None or args.fps is not None or args.repair_joints is not None or args.detections is not None):
+    if args.rotations and (args.bones or args.smooth or args.fps is not None or args.repair_joints is not None or args.detections is not None):
+        ap.error("--rotations is not measured together with --bones / --smooth / --fps / --repair_joints / --detections")
+    if args.drain and (args.rotations or args.bones or args.smooth or args.camera is not None or args.fps is not None or args.repair_joints is not None or args.detections is not None):
         ap.error("--drain is measured alone")
     if args.smooth and (args.fps is not None or args.repair_joints is not None or args.detections is not None):
         ap.error("--smooth is not measured together with --fps / --repair_joints / --detections")
@@ -213,19 +220,24 @@ def main():
                     pair = {"smooth_graph": new(smooth=True, **place), "graph": new(**place)}
                 elif args.bones:                                      # ... one of them with the fix behind the emit
                     pair = {"bones_graph": new(bones="track", **place), "graph": new(**place)}
+                elif args.rotations:                                  # ... one with the launch at the tick's end, one followed by the host rule
+                    pair = {"rotations_graph": new(rotations=True, **place), "graph": new(**place), "rotations_host": new(**place)}
                 else:
                     pair = {"camera_graph": new(camera=tuple(args.camera)), "graph": new()}
                 ts = {key: [] for key in pair}
                 for k in range(total):
                     for key in (list(pair) if k % 2 == 0 else list(pair)[::-1]):
                         t0 = time.perf_counter()
-                        pair[key].push(px[k])
+                        out = pair[key].push(px[k])
+                        if key == "rotations_host":                   # the poses to the host (it waits), then the rule in numpy
+                            stream.joint_rotations_host(out[0].cpu().numpy())
                         torch.cuda.synchronize()
                         ts[key].append(time.perf_counter() - t0)
                 for s in pair.values():
                     s.check_range()
                     s.close()
-                row.update(camera=None if args.camera is None else list(args.camera), smooth=bool(args.smooth), bones=bool(args.bones))
+                row.update(camera=None if args.camera is None else list(args.camera), smooth=bool(args.smooth), bones=bool(args.bones),
+                           rotations=bool(args.rotations))
                 return tuple((key, lambda key=key: ts[key][args.warmup:]) for key in pair)
 
             if args.drain:
@@ -273,7 +285,7 @@ def main():
                             ("md_graph", lambda: session(True, valid=seen.all(axis=2), missed_detections=True)))
             if args.detections is not None:
                 variants = detections_variants()
-            if args.camera is not None or args.smooth or args.bones:
+            if args.camera is not None or args.smooth or args.bones or args.rotations:
                 variants = camera_variants()
             for key, fn in variants:
                 ts = np.asarray(fn())
@@ -283,6 +295,8 @@ def main():
                 row["smooth_minus_graph_us"] = round(row["smooth_graph_us"] - row["graph_us"], 1)
             elif args.bones:
                 row["bones_minus_graph_us"] = round(row["bones_graph_us"] - row["graph_us"], 1)
+            elif args.rotations:
+                row["rotations_minus_graph_us"] = round(row["rotations_graph_us"] - row["graph_us"], 1)
             elif args.camera is not None:
                 row["camera_minus_graph_us"] = round(row["camera_graph_us"] - row["graph_us"], 1)
             elif args.detections is not None:

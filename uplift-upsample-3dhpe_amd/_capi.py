@@ -49,6 +49,7 @@ EXPORTED_SYMBOLS = (
     "uu3d_stream_drain_bytes", "uu3d_stream_drain_layout", "uu3d_stream_drain_commit", "uu3d_stream_root_drain", "uu3d_stream_drain_file",
     "uu3d_stream_drain_reset",
     "uu3d_bone_lengths", "uu3d_fix_bones", "uu3d_stream_bones_bytes", "uu3d_stream_bones", "uu3d_stream_bones_reset",
+    "uu3d_joint_rotations", "uu3d_joint_rotations_reset",
 )
 # include/uu3d_ops.h
 OPS_SYMBOLS = (
@@ -342,6 +343,10 @@ def load_library(path=None):
     lib.uu3d_stream_bones.argtypes = [i32, i32, vp, vp, vp, i32] + [vp] * 7
     lib.uu3d_stream_bones_reset.restype = C.c_int
     lib.uu3d_stream_bones_reset.argtypes = [i32, i32, vp, vp, vp]
+    lib.uu3d_joint_rotations.restype = C.c_int
+    lib.uu3d_joint_rotations.argtypes = [vp, i64, i32, vp, i32] + [vp] * 6
+    lib.uu3d_joint_rotations_reset.restype = C.c_int
+    lib.uu3d_joint_rotations_reset.argtypes = [i32, i32] + [vp] * 5
     lib.uu3d_world_to_cam_2d.restype = C.c_int
     lib.uu3d_world_to_cam_2d.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
     lib.uu3d_set_schedule.restype = C.c_int

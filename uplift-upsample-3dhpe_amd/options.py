@@ -6,18 +6,21 @@ import collections
 
 from .bones import check_bones
 from .keypoints import keypoint_map
+from .rotations import check_rotations
 from .roots import DEFAULT_MIN_ROOT_JOINTS, MAX_ROOT_JOINTS, check_cameras, check_min_root_joints
 from .smooth import check_smooth
 from .validity import check_repair_joints
 
 # cameras: (count, 4) float64 or None; min_root_joints: the checked int (a session without a camera: None); pose_filter / root_filter: a
-# ``OneEuro`` or None each; rigid: None or (skeleton, (count, J) lengths or None for "track"); keypoints: a ``KeypointMap`` or None
-StageOptions = collections.namedtuple("StageOptions", "cameras min_root_joints pose_filter root_filter rigid keypoints")
+# ``OneEuro`` or None each; rigid: None or (skeleton, (count, J) lengths or None for "track"); keypoints: a ``KeypointMap`` or None;
+# rotations: a ``Rotations`` or None
+StageOptions = collections.namedtuple("StageOptions", "cameras min_root_joints pose_filter root_filter rigid keypoints rotations")
 
 OUT_FPS_NEEDS_FPS = {"track": "out_fps needs fps: the rate the tracks were filmed at", "slot": "out_fps needs fps: the rate of the pushed frames"}
 
 
-def stage_options(config, count, per, root_relative, keypoints, camera, min_root_joints, smooth, bones, repair_joints, fps, out_fps):
+def stage_options(config, count, per, root_relative, keypoints, camera, min_root_joints, smooth, bones, repair_joints, fps, out_fps,
+                  rotations=None):
     """``count`` tracks (``per="track"``) or slots (``per="slot"``) of a model of ``config``; the other arguments as ``predict_tracks`` and
     ``StreamSession`` take them -> a ``StageOptions``.  Every refusal is a ValueError in the words of the stage's own check.
     ``min_root_joints``: a session passes None for "not given" -- the default with a camera, and anything else without one is refused (it
@@ -38,4 +41,4 @@ def stage_options(config, count, per, root_relative, keypoints, camera, min_root
     if fps is None and out_fps is not None:
         raise ValueError(OUT_FPS_NEEDS_FPS[per])
     check_repair_joints(repair_joints, "finite")
-    return StageOptions(cameras, min_root_joints, pose_filter, root_filter, rigid, keypoints)
+    return StageOptions(cameras, min_root_joints, pose_filter, root_filter, rigid, keypoints, check_rotations(rotations, config.NUM_KEYPOINTS))

@@ -34,6 +34,7 @@ every name is importable from here as before:
     associate.py  per-frame detections: ``predict_detections`` (uu3d_associate_detections), then ``predict_tracks`` on the tracks
     roots.py      absolute root position: ``predict_tracks(..., camera=(fx, fy, cx, cy))`` (uu3d_solve_roots, uu3d_root_trajectory)
     smooth.py     steady output: ``predict_tracks(..., smooth=OneEuro(min_cutoff, beta, d_cutoff))`` (uu3d_one_euro_tracks)
+    rotations.py  joint rotations: ``predict_tracks(..., rotations=True)`` (uu3d_joint_rotations; ``bvh.write_bvh``)
     bones.py      constant bone lengths: ``predict_tracks(..., bones="track")`` (uu3d_bone_lengths, uu3d_fix_bones)
     tracks.py     the pose table and the three uu3d_*_tracks launches above; options.py: the checks of all these options, shared with a live
                   session; cli.py: the command-line options, shared with ``stream``
@@ -58,6 +59,8 @@ from .keypoints import (KEYPOINT_PRESETS, MAX_KEYPOINT_SOURCES, KeypointMap, _h3
 from .options import stage_options
 from .rates import (_rate_argument, default_mask_stride, frame_rate, frame_rates, given_positions, output_positions,  # noqa: F401
                     resample_plan, root_plan)
+from .rotations import (REST_POSES, Rotations, check_rotations, forward_kinematics, joint_rotations, joint_rotations_host,  # noqa: F401
+                        quat_to_matrix)
 from .roots import (DEFAULT_MIN_ROOT_JOINTS, MAX_ROOT_JOINTS, _root_lens, check_cameras, check_min_root_joints, poses_at_given_frames,  # noqa: F401
                     root_trajectory, root_trajectory_host, solve_roots, solve_roots_host)
 from .smooth import (MAX_SMOOTH_CHANNELS, TWO_PI, OneEuro, _one_euro_rates, check_smooth, one_euro, one_euro_alpha, one_euro_host,  # noqa: F401
@@ -85,7 +88,9 @@ def predict_detections(model, config, detections, counts=None, valid=None, slots
     (track_id, first_frame, poses, roots (n, 3) float32, root_state (n,) uint8) -- every person of a video in the same camera space.
     ``smooth``: handed to ``predict_tracks`` as it is -- every track's poses (and roots) filtered from its birth frame on.
     ``bones``: handed to ``predict_tracks`` as it is -- "track" or one (J,) array of lengths for every person (the tracks are only known
-    after the association, so there is no per-track list here)."""
+    after the association, so there is no per-track list here).
+    ``rotations``: handed to ``predict_tracks`` as it is -- every tuple carries the track's (n, J, 4) quaternions behind what it has
+    otherwise (and, with ``return_global``, the global ones behind those)."""
     import torch
     assoc, options = _association_options(options)
     camera = options.pop("camera", None)
@@ -130,7 +135,7 @@ def predict_detections(model, config, detections, counts=None, valid=None, slots
         options["camera"] = camera[[v for v, _, _ in spans]]
     poses = predict_tracks(model, config, list(torch.split(xy, sizes, 0)), valid=list(torch.split(jf, sizes, 0)), resolutions=res, **options)
     out = [[] for _ in range(V)]
-    for (v, tid, first), *p in zip(spans, *(poses if camera is not None else (poses,))):
+    for (v, tid, first), *p in zip(spans, *(poses if isinstance(poses, tuple) else (poses,))):
         out[v].append((tid, first, *p))
     return out
 
@@ -138,7 +143,7 @@ def predict_detections(model, config, detections, counts=None, valid=None, slots
 def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, flip=None, keyframes_only=False, reuse_frames=True,
                    batch_size=None, root_relative=True, depth=None, lengths=None, graph=True, valid=None, return_valid=False, fps=None, out_fps=None,
                    model_fps=50, repair_joints=None, keypoints=None, camera=None, min_root_joints=DEFAULT_MIN_ROOT_JOINTS, smooth=None,
-                   bones=None):
+                   bones=None, rotations=None):
     """One 3D pose per frame for each 2D keypoint track -> list of (T_i, J, 3) float32 tensors on the model's device (views of one buffer).
 
     ``tracks``: list of (T_i, J, 2) arrays or tensors, on the host or the device, at the frame rate the config was trained for (nothing is
@@ -253,10 +258,21 @@ def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, fl
     ``fix_bones_host`` on the call without ``bones``, bit for bit).  Everything behind reads the fixed poses: the pose filter of
     ``smooth`` and the root solve of ``camera`` -- with ``out_fps`` its re-assembled poses at the given frames' times are fixed with the
     same lengths table.  A length that is not finite or <= 0 (a track without a usable frame) leaves that bone as it is; a NaN frame stays
-    NaN; the root joint of a root-relative pose stays exactly 0.  No accuracy figure is claimed."""
+    NaN; the root joint of a root-relative pose stays exactly 0.  No accuracy figure is claimed.
+
+    Joint rotations -- ``rotations``: None = today's call, the same bits, no further launch or buffer.  True (``Rotations("h36m17")``) or
+    a ``Rotations(rest, skeleton=..., primary=..., secondary=..., return_global=...)``: the call appends ``rotations``, a list of
+    (T_i, J, 4) float32 device tensors, behind whatever it returns otherwise -- per returned frame and joint the unit quaternion
+    (w, x, y, z) of the joint relative to its parent's frame, the root's relative to the pose's space -- and with ``return_global`` the
+    list ``global_rotations`` behind that.  They are computed from the RETURNED poses (behind ``bones``, behind ``smooth``, at the returned
+    frame times) in one launch over all tracks' rows (uu3d_joint_rotations; ``joint_rotations`` is the launch alone; the rule in numpy:
+    ``joint_rotations_host``, and the result equals it on the returned poses bit for bit).  A model whose joint count is not the
+    skeleton's: ValueError.  Positions do not show the twist about a bone with a single child: it is zero relative to the parent.  No
+    accuracy figure is claimed (``rotations.py``)."""
     import torch
     # options: the refusals shared with a live session (``options.stage_options``), then the ones only this call has
-    opts = stage_options(config, len(tracks), "track", root_relative, keypoints, camera, min_root_joints, smooth, bones, repair_joints, fps, out_fps)
+    opts = stage_options(config, len(tracks), "track", root_relative, keypoints, camera, min_root_joints, smooth, bones, repair_joints, fps, out_fps,
+                         rotations)
     if opts.keypoints is not None:
         check_keypoint_inputs(opts.keypoints, [_shape(t)[1] if len(_shape(t)) == 3 else -1 for t in tracks])
     if fps is not None and keyframes_only:
@@ -324,7 +340,13 @@ def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, fl
         if opts.root_filter is not None:
             roots = one_euro(roots, lens, out_rate, opts.root_filter, state=root_state)
         placed = (list(torch.split(roots, sizes, 0)), list(torch.split(root_state, sizes, 0)))
-    return _returned(poses, placed, table, model_lens, given, return_valid, repair_joints is not None)
+    result = _returned(poses, placed, table, model_lens, given, return_valid, repair_joints is not None)
+    # rotations: the quaternions of the RETURNED poses, one launch over all tracks' rows, appended behind whatever the call returns
+    if opts.rotations is not None:
+        turned = joint_rotations(shown, opts.rotations)
+        more = (list(torch.split(turned[0], sizes, 0)),) + ((list(torch.split(turned[2], sizes, 0)),) if opts.rotations.return_global else ())
+        result = (result if isinstance(result, tuple) else (result,)) + more
+    return result
 
 
 def _predicted_windows(model, cfg, table, mask_stride, flip, batch_size, depth, graph, reuse_frames):

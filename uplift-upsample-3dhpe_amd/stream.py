@@ -65,6 +65,7 @@ module's docstring; every name is importable from here as before:
     roots.py      live absolute root: ``StreamSession(..., camera=(fx, fy, cx, cy), min_root_joints=6)`` (``LiveRootHost``)
     smooth.py     steady output: ``StreamSession(..., smooth=F)`` (``LiveOneEuro``, ``LiveOneEuroHost``)
     bones.py      live constant bone lengths: ``StreamSession(..., bones=B)`` (``LiveBonesHost``)
+    rotations.py  live joint rotations: ``StreamSession(..., rotations=R)`` (uu3d_joint_rotations as the tick's last launch)
 The refusals these options share with ``predict_tracks`` are ``options.stage_options``; the ones only a session has are ``_init_plan``'s.
 
 The end of a track -- ``finish(slots)``: a session with lookahead a has not returned the poses of a track's last a frames when the track
@@ -104,6 +105,7 @@ from .options import stage_options
 from .predict import _load_model
 from .rates import (RatePlan, _rate_argument, frame_rate, max_lookahead, newest_model_frame, out_push_plan, push_plan,  # noqa: F401
                     rate_plan, session_strides)
+from .rotations import Rotations, check_rotations, joint_rotations_host  # noqa: F401
 from .roots import DEFAULT_MIN_ROOT_JOINTS, MAX_ROOT_JOINTS, LiveRootHost, check_cameras, check_min_root_joints, solve_roots_host  # noqa: F401
 from .smooth import (MAX_SMOOTH_CHANNELS, LiveOneEuro, LiveOneEuroHost, OneEuro, _live_filter_arguments, check_smooth,  # noqa: F401
                      one_euro_sample)
@@ -170,7 +172,7 @@ def window_plan(frames, lookahead, config, mask_stride=None, valid=None, drained
             "place": np.where(kind == 2, (src // s_in) % cap, -1)}
 
 
-LIVE_OPTIONS = ("repair_joints", "keypoints", "camera", "min_root_joints", "smooth", "bones")  # the keywords ``StreamSession`` and ``replay_tracks`` take from **options
+LIVE_OPTIONS = ("repair_joints", "keypoints", "camera", "min_root_joints", "smooth", "bones", "rotations")  # the keywords ``StreamSession`` and ``replay_tracks`` take from **options
 DETECTION_OPTIONS = ("detections",) + tuple(ASSOCIATION_DEFAULTS)    # ... and the ones only ``StreamSession`` takes: per-frame detections
 
 
@@ -233,12 +235,17 @@ class StreamSession(object):
         ``bones`` (keyword only, from ``options`` as well): None = the poses as the network gives them (the session above, bit for bit).
         "track", a (J,) array of lengths by child joint, a list of such arrays, one per slot, or a ``predict.Bones``: the module
         docstring's "Live constant bone lengths" -- ``push`` returns the rebuilt poses, ``raw_poses`` stays the model's output and
-        ``bone_lengths`` is the slots' lengths table.  With ``out_fps``: ValueError."""
-        (repair_joints, keypoints, camera, min_root_joints, smooth, bones, detections,
+        ``bone_lengths`` is the slots' lengths table.  With ``out_fps``: ValueError.
+        ``rotations`` (keyword only, from ``options`` as well): None = positions only (the session above, bit for bit).  True or a
+        ``predict.Rotations``: "Live joint rotations" (``rotations.py``) -- ``push`` / ``push_detections`` append ``rotations``
+        (slots, J, 4) float32, per slot and joint the unit quaternion (w, x, y, z) of the pose they return, behind what they return
+        otherwise (with ``return_global`` the global quaternions behind that); ``rotation_flags`` is the (slots, J) uint8 table of the
+        last tick.  uu3d_joint_rotations is the last launch of the captured tick.  With ``out_fps``: ValueError."""
+        (repair_joints, keypoints, camera, min_root_joints, smooth, bones, rotations, detections,
          *rule) = _live_options(options, "StreamSession", LIVE_OPTIONS + DETECTION_OPTIONS)
         res = self._init_plan(model, config, slots, resolutions, mask_stride, flip, lookahead, graph, missed_detections, fps, model_fps, out_fps,
                               repair_joints, keypoints, detections, dict(zip(ASSOCIATION_DEFAULTS, rule)), camera, min_root_joints, smooth,
-                              bones=bones, root_relative=root_relative)
+                              bones=bones, root_relative=root_relative, rotations=rotations)
         import torch
         self._torch = torch
         self._lib = _capi.load_library()
@@ -255,13 +262,15 @@ class StreamSession(object):
     # ---- construction: checks and plan, layout and state, buffers, launch tables (then the capture) ---------------------------------
     def _init_plan(self, model, config, slots, resolutions, mask_stride, flip, lookahead, graph, missed_detections, fps, model_fps, out_fps,
                    repair_joints=None, keypoints=None, detections=None, rule=None, camera=None, min_root_joints=None, smooth=None, bones=None,
-                   root_relative=True):
+                   root_relative=True, rotations=None):
         """Every refusal that needs no device, and the session's plan.  -> the checked resolutions."""
         slots, lookahead = int(slots), int(lookahead)
         if slots < 1:
             raise ValueError("slots >= 1")
         # the refusals shared with ``predict_tracks`` (``options.stage_options``), then the ones only a session has
-        opts = stage_options(config, slots, "slot", root_relative, keypoints, camera, min_root_joints, smooth, bones, repair_joints, fps, out_fps)
+        opts = stage_options(config, slots, "slot", root_relative, keypoints, camera, min_root_joints, smooth, bones, repair_joints, fps, out_fps,
+                             rotations)
+        self.rotations = opts.rotations
         self.bones, self.pose_filter, self.root_filter, self.keypoints = opts.rigid, opts.pose_filter, opts.root_filter, opts.keypoints
         self.cameras, self.min_root_joints = opts.cameras, opts.min_root_joints
         self.smooth_rate = frame_rate(model_fps if fps is None else fps)     # the rate of the frames a push returns
@@ -271,6 +280,9 @@ class StreamSession(object):
         if (self.pose_filter is not None or self.root_filter is not None) and out_fps is not None:
             raise ValueError("smooth together with out_fps is not supported: a push then returns several rows per slot, and the live filter "
                              "takes one sample per slot and push (multi-row emits are out of scope)")
+        if self.rotations is not None and out_fps is not None:
+            raise ValueError("rotations together with out_fps is not supported: a push then returns several rows per slot, and the live "
+                             "rotations are those of one pose per slot and push (multi-row emits are out of scope)")
         if camera is not None and out_fps is not None:
             raise ValueError("camera together with out_fps is not supported yet: the returned poses are not at source-frame times, so no "
                              "pushed frame is theirs to be solved against (a later change)")
@@ -461,6 +473,17 @@ class StreamSession(object):
         if self.root_filter is not None:
             self._root_smoother = LiveOneEuro(T, 3, self.smooth_rate, self.root_filter, self.lookahead, dev)
             self._result = self._result[:2] + (self._root_smoother.out,) + self._result[3:]
+        # joint rotations: the tables of the rest pose and the quaternion buffers push appends -- identities before a slot's first pose
+        self._rot_local = self._rot_global = self._rot_flags = None
+        if self.rotations is not None:
+            self._rot_tables = self.rotations.device_tables(dev)
+            self._rot_local = zeros((T, J, 4), dtype=torch.float32)
+            self._rot_flags = zeros((T, J), dtype=torch.uint8)
+            self._rot_global = zeros((T, J, 4), dtype=torch.float32) if self.rotations.return_global else None
+            for q in (self._rot_local, self._rot_global):
+                if q is not None:
+                    q[:, :, 0] = 1.0
+            self._result = self._result + (self._rot_local,) + ((self._rot_global,) if self._rot_global is not None else ())
         # the end of a track: nothing until the first ``finish`` (_init_drain)
         self._drain_result = self._drain_state = self._drain_graph = None
         self._drain_steps = []
@@ -524,6 +547,9 @@ class StreamSession(object):
         self._reset_more = self._reset_more + [f.reset_launch() for f in (self._pose_smoother, self._root_smoother) if f is not None]
         if self.bones is not None:
             self._reset_more = self._reset_more + [(lib.uu3d_stream_bones_reset, (self.slots, int(self._kp.shape[1]), _ptr(self._bone_state)))]
+        if self.rotations is not None:                              # (no state: the reset writes identities into the returned buffers)
+            self._reset_more = self._reset_more + [(lib.uu3d_joint_rotations_reset, (self.slots, int(self._kp.shape[1]), _ptr(self._rot_local),
+                                                                                     _ptr(self._rot_global), _ptr(self._rot_flags)))]
         # per-frame detections: the association in front of everything -- it writes the frame, the flags, `active` and the born mask --, then
         # the resets of the slots born at this tick, with the mask on the device
         if self.detections is not None:
@@ -555,6 +581,16 @@ class StreamSession(object):
             last.append(self._pose_smoother.launch(self._pose_shown, self._source_frames, self._fresh, self._active))
         if self._root_smoother is not None:
             last.append(self._root_smoother.launch(self._roots, self._source_frames, self._fresh, self._active, self._root_flag))
+        # joint rotations: the last step of all -- it reads the pose buffer push returns, whichever stage wrote it
+        if self.rotations is not None:
+            last.append(self._rotations_launch())
+
+    def _rotations_launch(self):
+        """uu3d_joint_rotations as a launch-table entry: the returned poses -> their quaternions, the fresh slots only."""
+        tree, rest = self._rot_tables
+        return (self._lib.uu3d_joint_rotations, (_ptr(self._result[0]), self.slots, int(self._kp.shape[1]), _ptr(tree), self.rotations.depth,
+                                                 _ptr(rest), _ptr(self._fresh), _ptr(self._rot_local), _ptr(self._rot_global),
+                                                 _ptr(self._rot_flags)))
 
     def _bones_launch(self, active):
         """uu3d_stream_bones as a launch-table entry: the emitted poses -> the rebuilt ones; ``active``: the slots that may take a sample."""
@@ -817,6 +853,10 @@ class StreamSession(object):
             parts.append(("filtered_poses", fp.out, (J, 3), torch.float32))
         if fr is not None:
             parts.append(("filtered_roots", fr.out, (3,), torch.float32))
+        if self.rotations is not None:
+            parts.append(("rotations", self._rot_local, (J, 4), torch.float32))
+            if self._rot_global is not None:
+                parts.append(("global_rotations", self._rot_global, (J, 4), torch.float32))
         nbytes = [T * a * int(np.prod(shape, dtype=np.int64)) * (4 if dt == torch.float32 else 1) for _, _, shape, dt in parts]
         offsets = [int(o) for o in np.cumsum([0] + [(n + 255) // 256 * 256 for n in nbytes])]
         self._drain_rows = torch.zeros(max(offsets[-1], 1), dtype=torch.uint8, device=dev)
@@ -828,6 +868,7 @@ class StreamSession(object):
         result = (rows.get("filtered_poses", rows.get("fixed_poses", rows["poses"])), rows["fresh"].view(torch.bool))
         if camera:
             result += (rows.get("filtered_roots", rows["roots"]), rows["root_state"])
+        result += tuple(rows[name] for name in ("rotations", "global_rotations") if name in rows)
         self._drain_result = result
         if a == 0:
             return
@@ -849,6 +890,8 @@ class StreamSession(object):
             steps.append(fp.launch(self._pose_shown, self._virtual_frames, self._fresh, self._drain_mask))
         if fr is not None:
             steps.append(fr.launch(self._roots, self._virtual_frames, self._fresh, self._drain_mask, self._root_flag))
+        if self.rotations is not None:                               # the same step as in a tick
+            steps.append(self._rotations_launch())
         floats = [(src, rows[name], int(np.prod(shape))) for name, src, shape, _ in parts if src is not None]
         self._drain_file_args = []                                    # (uu3d_stream_drain_file takes four float buffers: a fifth goes in a launch of its own)
         for first in range(0, len(floats), 4):
@@ -1011,6 +1054,14 @@ class StreamSession(object):
         return self._bone_lengths
 
     @property
+    def rotation_flags(self):
+        """(slots, J) uint8 on the device (sessions with ``rotations``): per slot and joint 1 = the quaternion was determined from the slot's
+        last fresh pose, 0 = it fell back (or the slot has had no pose since its reset)."""
+        if self.rotations is None:
+            raise AttributeError("rotation_flags needs a session with rotations")
+        return self._rot_flags
+
+    @property
     def joint_state(self):
         """(slots, J) uint8 on the device (sessions with ``repair_joints``): what became of the joints of each slot's newest frame, in the
         coding of ``predict_tracks(return_valid=True)`` -- 1 observed, 2 filled (held from its last observation), 0 neither."""
@@ -1082,6 +1133,8 @@ def replay_tracks(model, config, tracks, resolutions=None, mask_stride=None, fli
     ``camera`` -- the roots (T_i, 3) float32 and root states (T_i,) uint8 the session returned at each tick are appended per track:
     -> (poses, fresh, roots, root_state).  ``smooth=F`` (from ``options`` as well): a session with ``smooth``; the same return, filtered.
     ``bones=B`` (from ``options`` as well): a session with ``bones``, one slot per track; the same return, the poses rebuilt.
+    ``rotations=R`` (from ``options`` as well): a session with ``rotations``; per track the quaternions (T_i, J, 4) float32 the session
+    returned at each tick are appended (with ``return_global`` the global ones behind them): one row per pushed frame.
     ``drain=True``: every slot is finished (``StreamSession.finish``) at the tick its own track ends, while the other slots go on; per
     track the arrays then have T_i + lookahead rows -- row t is the pose of frame t - lookahead (where it is fresh), so all T_i frames of
     the track come out, as from ``predict_tracks``.  Still one copy to the host, at the end.  Not with ``fps`` / ``out_fps`` (ValueError)."""
@@ -1089,7 +1142,7 @@ def replay_tracks(model, config, tracks, resolutions=None, mask_stride=None, fli
         raise ValueError("drain=True together with fps / out_fps is not supported yet (a later change): the drain of a source-rate session "
                          "needs the end of the model-rate track")
     import torch
-    repair_joints, keypoints, camera, min_root_joints, smooth, bones = _live_options(options, "replay_tracks")
+    repair_joints, keypoints, camera, min_root_joints, smooth, bones, rotations = _live_options(options, "replay_tracks")
     lens = [int(len(t)) for t in tracks]
     T, ticks = len(tracks), max(lens)
     K = J = int(np.asarray(tracks[0]).shape[1])                      # joints pushed, joints returned
@@ -1108,7 +1161,10 @@ def replay_tracks(model, config, tracks, resolutions=None, mask_stride=None, fli
         raise ValueError('valid must be None, "finite" or a list with one (T_i,) array per track')
     s = StreamSession(model, config, T, resolutions=resolutions, mask_stride=mask_stride, flip=flip, lookahead=lookahead,
                       root_relative=root_relative, graph=graph, missed_detections=valid is not None, fps=fps, model_fps=model_fps, out_fps=out_fps,
-                      repair_joints=repair_joints, keypoints=keypoints, camera=camera, min_root_joints=min_root_joints, smooth=smooth, bones=bones)
+                      repair_joints=repair_joints, keypoints=keypoints, camera=camera, min_root_joints=min_root_joints, smooth=smooth, bones=bones,
+                      rotations=rotations)
+    turned = 0 if s.rotations is None else 2 if s.rotations.return_global else 1          # quaternion buffers a push appends
+    quats = [torch.zeros((ticks, T, J, 4), dtype=torch.float32, device=model.device) for _ in range(turned)]
     if camera is not None:                                           # per tick and slot four 32-bit words: the root's bits, the state
         root_words = torch.zeros((ticks, T, 4), dtype=torch.int32, device=model.device)
     tails = None
@@ -1117,6 +1173,7 @@ def replay_tracks(model, config, tracks, resolutions=None, mask_stride=None, fli
         tails = [torch.zeros((T, a, J, 3), dtype=torch.float32, device=model.device), torch.zeros((T, a), dtype=torch.bool, device=model.device)]
         if camera is not None:
             tails += [torch.zeros((T, a, 3), dtype=torch.float32, device=model.device), torch.zeros((T, a), dtype=torch.uint8, device=model.device)]
+        tails += [torch.zeros((T, a, J, 4), dtype=torch.float32, device=model.device) for _ in range(turned)]
     if out_fps is None:
         poses = torch.zeros((ticks, T, J, 3), dtype=torch.float32, device=model.device)
         fresh = torch.zeros((ticks, T), dtype=torch.bool, device=model.device)
@@ -1134,7 +1191,9 @@ def replay_tracks(model, config, tracks, resolutions=None, mask_stride=None, fli
                 p, f, *rs = s.push(kp, None if act.all() else act)
             else:
                 p, f, *rs = s.push(kp, None if act.all() else act, valid=np.array([flags[i][k] & True if act[i] else flags[i][0] & False for i in range(T)]))
-            if rs:
+            for dst, src in zip(quats, rs[len(rs) - turned:]):
+                dst[k].copy_(src)
+            if camera is not None:
                 root_words[k, :, :3].copy_(rs[0].view(torch.int32))
                 root_words[k, :, 3].copy_(rs[1])
             if out_fps is None:
@@ -1163,6 +1222,9 @@ def replay_tracks(model, config, tracks, resolutions=None, mask_stride=None, fli
         root_words = root_words.cpu().numpy()
         roots = np.ascontiguousarray(root_words[:, :, :3]).view(np.float32)
         out += ([roots[:n, i] for i, n in enumerate(lens)], [root_words[:n, i, 3].astype(np.uint8) for i, n in enumerate(lens)])
+    for q in quats:
+        q = q.cpu().numpy()
+        out += ([q[:n, i] for i, n in enumerate(lens)],)
     if drain:
         tails = [t.cpu().numpy() for t in tails]
         out = tuple([np.concatenate([rows, tail[i]]) for i, rows in enumerate(per_track)] for per_track, tail in zip(out, tails))
@@ -1178,7 +1240,8 @@ def replay_detections(model, config, detections, counts=None, valid=None, slots=
     -> a list of (track_id, first_frame, poses (n, J, 3) float32, fresh (n,) bool) by track id, host arrays: what the session returned for
     the track's slot at the ticks first_frame .. first_frame + n - 1, the ticks the track was alive (its trailing missing frames
     included; ``predict.predict_detections`` ends a track at its last matched frame).  With ``camera`` every tuple carries two more
-    entries: roots (n, 3) float32 and root_state (n,) uint8 of those ticks.  One copy to the host, at the end.
+    entries: roots (n, 3) float32 and root_state (n,) uint8 of those ticks; with ``rotations`` the quaternions (n, J, 4) float32 of those
+    ticks behind them (one row per pushed frame).  One copy to the host, at the end.
     ``drain=True``: ``finish()`` runs after the last tick and its ``lookahead`` rows are appended to the arrays of every track alive at the
     end of the video (n + lookahead rows).  The limit: a track that died in mid-video (``max_age``) still loses the poses of its last
     ``lookahead`` frames -- the death happens on the device, and no drain is run there."""
@@ -1196,6 +1259,8 @@ def replay_detections(model, config, detections, counts=None, valid=None, slots=
     poses = torch.zeros((ticks, S, J, 3), dtype=torch.float32, device=model.device)
     words = torch.zeros((ticks, 2, S), dtype=torch.int32, device=model.device)            # per tick: the fresh flags, the track ids
     placed = s.cameras is not None
+    turned = 0 if s.rotations is None else 2 if s.rotations.return_global else 1          # quaternion buffers a push appends
+    quats = [torch.zeros((ticks, S, J, 4), dtype=torch.float32, device=model.device) for _ in range(turned)]
     if placed:                                                        # per tick and slot: the root's bits, the state
         root_words = torch.zeros((ticks, S, 4), dtype=torch.int32, device=model.device)
     try:
@@ -1204,7 +1269,9 @@ def replay_detections(model, config, detections, counts=None, valid=None, slots=
             poses[k].copy_(p)
             words[k, 0].copy_(f)
             words[k, 1].copy_(s.track_ids)
-            if rs:
+            for dst, src in zip(quats, rs[len(rs) - turned:]):
+                dst[k].copy_(src)
+            if placed:
                 root_words[k, :, :3].copy_(rs[0].view(torch.int32))
                 root_words[k, :, 3].copy_(rs[1])
         tails = [t.clone() for t in s.finish()] if drain else None   # (the ids of the last tick say whose rows they are)
@@ -1218,10 +1285,11 @@ def replay_detections(model, config, detections, counts=None, valid=None, slots=
     if placed:
         root_words = root_words.cpu().numpy()
         roots, root_state = np.ascontiguousarray(root_words[:, :, :3]).view(np.float32), root_words[:, :, 3].astype(np.uint8)
+    quats = [q.cpu().numpy() for q in quats]
     out = []
     for tid in range(int(ids.max()) + 1 if ids.size else 0):
         t, slot = np.nonzero(ids == tid)
-        arrays = (poses[t, slot], fresh[t, slot]) + ((roots[t, slot], root_state[t, slot]) if placed else ())
+        arrays = (poses[t, slot], fresh[t, slot]) + ((roots[t, slot], root_state[t, slot]) if placed else ()) + tuple(q[t, slot] for q in quats)
         if drain and ticks and t[-1] == ticks - 1:                    # alive at the end of the video: the rows finish() gave its slot
             arrays = tuple(np.concatenate([x, tail[slot[-1]]]) for x, tail in zip(arrays, tails))
         out.append((tid, int(t[0])) + arrays)
