@@ -171,6 +171,57 @@ size_t uu3d_op_attn_qf_bytes(int32_t rows);
  * producer's own index function (tchain_qf_index, csrc/uu3d_tchain16.h).  Elements of rows past `rows` in the last tile are left as they are. */
 int uu3d_op_attn_qf_pack(const void* hi_host, const void* lo_host, int32_t rows, void* frag_host);
 
+/* ---- the forward's TILED GEMMs, each on its own (csrc/uu3d_gemm.h: gemm_f32_kernel, splitk_reduce_kernel; csrc/uu3d_gemm_h3.h: gemm_h3_kernel,
+ * gemm_h3g_kernel), launched through the functions the forward's Launcher::gemm / gemm_g launch through (launch_fwd_gemm, launch_fwd_gemm_g,
+ * csrc/uu3d_launch.h): tile shape, DEEP form and split are the forward's -- tests/test_fwd_tiled_gpu.py holds them to float64. ----
+ * The operand: what uu3d_commit_weights keeps for a Dense / Conv1D kernel, made by the commit's own pack and split functions
+ * (csrc/uu3d_pack.h) from the Keras (in, out) kernel w_host[K][N] on the HOST (a Conv1D (3, C, N) kernel flattened: k = j C + c):
+ *   Bt[Np][Kp] f32, zero padded, Np = round_up(N, 128), Kp = round_up(K, 32) | its f16 hi plane | its lo * 2048 plane  = 8 Np Kp bytes.
+ * uu3d_op_tiled_operand_bytes: 0 for N or K < 1.  uu3d_op_tiled_pack: UU3D_ERR_RANGE (nothing uploaded) for a value of magnitude >= 65504. */
+size_t uu3d_op_tiled_operand_bytes(int32_t N, int32_t K);
+int uu3d_op_tiled_pack(const float* w_host, int32_t K, int32_t N, void* operand_dev, void* stream);
+
+#define UU3D_A_F32 0            /* ALoadPlain: a_dev = f32 rows [M][lda]; K % 4 == 0, lda >= K, lda % 4 == 0 */
+#define UU3D_A_F32_LN 1         /* ALoadLayerNorm: the same rows, LayerNorm in the loader from ln_stats_dev ((mean, rstd) per row, made by
+                                 * uu3d_op_row_stats(a_dev, lda, K, M, eps): the launch the forward makes in front of such a layer), ln_gamma_dev, ln_beta_dev */
+#define UU3D_A_PLANES 2         /* GLoadPlain: a_dev / a_lo_dev = f16 planes [M][lda] (value = hi + lo / 2048); K % 32 == 0, lda >= K, lda % 8 == 0 */
+#define UU3D_A_CONV3_F32 3      /* ALoadConv3: a_dev = f32 rows [B L_in][C]; output row (b, t), M = B L_out, contracts over k = j C + c with row
+                                 * t stride + j - pad_left of sequence b, zero outside [0, L_in); K == 3 C, C % 4 == 0 */
+#define UU3D_A_CONV3_PLANES 4   /* GLoadConv3: the same gather over f16 planes [B L_in][C]; C % 32 == 0.  The zero source is the operator's */
+#define UU3D_EP_BIAS_RELU 5     /* out[M][N] f32 (row stride ldo) = max(v + bias, 0) */
+#define UU3D_EP_CONV_RESIDUAL 6 /* EpConvResidual, inference form: out[M][N] = xin[b L_in + t stride + lo][.] + v + bias (+ pe_dev[t][.] when pe_dev != NULL),
+                                 * lo = 1 when stride > 1 and pad_left == 0, else 0; every row stride N; (L_out - 1) stride + lo < L_in */
+#define UU3D_EP_S2T 7           /* EpSpatialToTemporal, inference form: out[M][N] = (mask_dev == NULL || mask_dev[row] ? v + bias : token_dev[.]) + pe_dev[row % period][.] */
+/* UU3D_EP_BIAS, _BIAS_RELU_SPLIT, _BIAS_SPLIT_Q as above (planes: hi[M][N] | lo[M][N] at out_dev).  UU3D_EP_BIAS_RESIDUAL here: out_dev[M][N] += v + bias in place
+ * (row stride N, any N); out2_dev != NULL: out2_dev[M][N] = that sum + pe_dev[row % period][.] as well. */
+typedef struct uu3d_tiled_dense_args {
+    const void* a_dev; const void* a_lo_dev;                  /* the A source (a_lo_dev: plane sources only) */
+    const float* ln_stats_dev; const float* ln_gamma_dev; const float* ln_beta_dev;
+    const void* operand_dev; const float* bias_dev;           /* uu3d_op_tiled_pack's operand; bias[N] */
+    void* out_dev; float* out2_dev;
+    const float* xin_dev; const float* pe_dev; const float* token_dev; const uint8_t* mask_dev;
+    float* slab_dev; size_t slab_floats;                      /* split-K partial sums and their capacity in floats; 0 forces the unsplit form */
+    int32_t a_source, epilogue, precision, splitk_target;    /* UU3D_PREC_F16X3 | UU3D_PREC_F32; the workgroups a split aims for (the forward: 768, or UU3D_THR_SPLITK_TARGET) */
+    int32_t M, N, K, lda, ldo;                                /* ldo: UU3D_EP_BIAS / _BIAS_RELU only (>= N) */
+    int32_t conv_C, conv_L_in, conv_L_out, conv_stride, conv_pad_left;
+    int32_t period; float qscale;
+} uu3d_tiled_dense_args;
+/* out = epilogue(A-op W + bias).  The (A source, epilogue, precision) combinations csrc/uu3d_forward.inc launches, and no other:
+ *   UU3D_A_F32        x UU3D_EP_BIAS (head1, head2), _BIAS_RESIDUAL (proj_res, fc2_res), _S2T (s2t)              f16x3 (gemm_h3_kernel) and f32 (gemm_f32_kernel)
+ *   UU3D_A_F32_LN     x UU3D_EP_BIAS (ln_qkv), _BIAS_RELU (ln_fc1)                                               f16x3 and f32
+ *   UU3D_A_F32_LN     x UU3D_EP_BIAS_SPLIT_Q (ln_qkv), _BIAS_RELU_SPLIT (ln_fc1)                                 f16x3
+ *   UU3D_A_PLANES     x UU3D_EP_BIAS_RESIDUAL (proj_res, fc2_res), _S2T (s2t)                                    f16x3 (gemm_h3g_kernel)
+ *   UU3D_A_CONV3_F32  x UU3D_EP_CONV_RESIDUAL (s*.conv_res)                                                      f16x3 and f32
+ *   UU3D_A_CONV3_PLANES x UU3D_EP_CONV_RESIDUAL (s*.conv_res)                                                    f16x3 (gemm_h3g_kernel)
+ * Anything else, a null pointer the combination needs, a violated shape rule above, M, N or K < 1, M not a multiple of L_out, period < 1 where
+ * pe_dev is read, slab_floats != 0 with slab_dev NULL, splitk_target < 1: UU3D_ERR_INVALID_ARGUMENT.  M round_up(max(N, lda), 4) >= 2^29 elements:
+ * UU3D_ERR_UNSUPPORTED.  Both before any launch, every output untouched.  Every pointer 16-byte aligned (not checked).  Rows and columns beyond
+ * M and N of every buffer are not written. */
+int uu3d_op_tiled_dense(const uu3d_tiled_dense_args* args, void* stream);
+/* HOST: {slices, k-tiles per slice} the launch of (M, N, K) takes under the forward's split rule (splitk_rule with its exception), for a test to
+ * hold its own restatement of the rule against. */
+int uu3d_op_tiled_split(int32_t M, int32_t N, int32_t K, int32_t splitk_target, size_t slab_floats, int32_t* slices, int32_t* k_tiles_per_slice);
+
 #ifdef __cplusplus
 }
 #endif

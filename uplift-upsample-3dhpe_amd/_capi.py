@@ -59,6 +59,7 @@ OPS_SYMBOLS = (
     "uu3d_op_ln_dense_panel_ex", "uu3d_op_panel_a_unpack", "uu3d_op_mlp_operand_bytes", "uu3d_op_mlp_pack", "uu3d_op_mlp_fused",
     "uu3d_op_wt_operand_bytes", "uu3d_op_wt_pack", "uu3d_op_ln_dense_wt",
     "uu3d_op_attn_infer", "uu3d_op_attn_qf_bytes", "uu3d_op_attn_qf_pack",
+    "uu3d_op_tiled_operand_bytes", "uu3d_op_tiled_pack", "uu3d_op_tiled_dense", "uu3d_op_tiled_split",
 )
 # epilogues of uu3d_op_ln_dense_panel_ex / uu3d_op_ln_dense_wt (include/uu3d_ops.h)
 UU3D_EP_BIAS, UU3D_EP_BIAS_RELU_SPLIT, UU3D_EP_BIAS_SPLIT_Q, UU3D_EP_BIAS_RESIDUAL, UU3D_EP_BIAS_RESIDUAL_LN = range(5)
@@ -66,6 +67,19 @@ UU3D_EP_BIAS, UU3D_EP_BIAS_RELU_SPLIT, UU3D_EP_BIAS_SPLIT_Q, UU3D_EP_BIAS_RESIDU
 UU3D_ATTN_AUTO, UU3D_ATTN_F32_WG, UU3D_ATTN_HEAD_WAVE, UU3D_ATTN_H3 = range(4)
 UU3D_ATTN_IN_F32, UU3D_ATTN_IN_PLANES, UU3D_ATTN_IN_QFRAG = range(3)
 UU3D_ATTN_OUT_F32, UU3D_ATTN_OUT_PLANES, UU3D_ATTN_OUT_FRAG = range(3)
+# A sources and further epilogues of uu3d_op_tiled_dense (include/uu3d_ops.h)
+UU3D_A_F32, UU3D_A_F32_LN, UU3D_A_PLANES, UU3D_A_CONV3_F32, UU3D_A_CONV3_PLANES = range(5)
+UU3D_EP_BIAS_RELU, UU3D_EP_CONV_RESIDUAL, UU3D_EP_S2T = 5, 6, 7
+
+
+class Uu3dTiledDenseArgs(C.Structure):
+    """``uu3d_tiled_dense_args`` of include/uu3d_ops.h."""
+    _fields_ = ([(n, C.c_void_p) for n in ("a_dev", "a_lo_dev", "ln_stats_dev", "ln_gamma_dev", "ln_beta_dev", "operand_dev", "bias_dev", "out_dev", "out2_dev",
+                                           "xin_dev", "pe_dev", "token_dev", "mask_dev", "slab_dev")]
+                + [("slab_floats", C.c_size_t)]
+                + [(n, C.c_int32) for n in ("a_source", "epilogue", "precision", "splitk_target", "M", "N", "K", "lda", "ldo",
+                                            "conv_C", "conv_L_in", "conv_L_out", "conv_stride", "conv_pad_left", "period")]
+                + [("qscale", C.c_float)])
 
 
 class Uu3dLibraryError(RuntimeError):
@@ -453,6 +467,14 @@ def load_library(path=None):
     lib.uu3d_op_attn_qf_bytes.argtypes = [i32]
     lib.uu3d_op_attn_qf_pack.restype = C.c_int
     lib.uu3d_op_attn_qf_pack.argtypes = [vp, vp, i32, vp]
+    lib.uu3d_op_tiled_operand_bytes.restype = sz
+    lib.uu3d_op_tiled_operand_bytes.argtypes = [i32, i32]
+    lib.uu3d_op_tiled_pack.restype = C.c_int
+    lib.uu3d_op_tiled_pack.argtypes = [vp, i32, i32, vp, vp]
+    lib.uu3d_op_tiled_dense.restype = C.c_int
+    lib.uu3d_op_tiled_dense.argtypes = [C.POINTER(Uu3dTiledDenseArgs), vp]
+    lib.uu3d_op_tiled_split.restype = C.c_int
+    lib.uu3d_op_tiled_split.argtypes = [i32, i32, i32, i32, sz, C.POINTER(i32), C.POINTER(i32)]
     if path is None:
         _lib = lib
     return lib

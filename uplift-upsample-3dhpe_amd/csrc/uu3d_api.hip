@@ -21,6 +21,7 @@
 #include "uu3d_switches.h"
 #include "uu3d_gemm.h"
 #include "uu3d_gemm_h3.h"
+#include "uu3d_pack.h"
 #include "uu3d_gemm_panel.h"
 #include "uu3d_gemm_panel8.h"
 #include "uu3d_gemm_wt.h"

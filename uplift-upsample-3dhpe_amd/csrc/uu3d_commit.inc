@@ -19,11 +19,8 @@ const float* W(const uu3d_model* m, const std::string& name) {
     return it == m->index.end() ? nullptr : m->weights[it->second].host.data();
 }
 
-// Keras Dense kernel (K, N) -> Bt[Np][Kp], Np = round_up(N,128), Kp = round_up(K,32); row offset n0.
-void pack_dense_t(std::vector<float>& buf, size_t off, const float* w, int K, int N, int Kp, int n0) {
-    for (int k = 0; k < K; ++k)
-        for (int n = 0; n < N; ++n) buf[off + (size_t)(n0 + n) * Kp + k] = w[(size_t)k * N + n];
-}
+// Keras Dense kernel (K, N) -> Bt[Np][Kp]: uu3d_pack.h (shared with the operator ABI)
+void pack_dense_t(std::vector<float>& buf, size_t off, const float* w, int K, int N, int Kp, int n0) { uu3d::pack_dense_t(buf.data(), off, w, K, N, Kp, n0); }
 
 }  // namespace
 
@@ -259,13 +256,8 @@ int uu3d_commit_weights(uu3d_model* m, void* stream_) {
         for (auto& d : P.dense) {
             const size_t hi = align_up(hb.size(), 64); hb.resize(hi + d.second);
             const size_t lo = align_up(hb.size(), 64); hb.resize(lo + d.second);
-            for (size_t i = 0; i < d.second; ++i) {
-                const float x = P.buf[d.first + i];
-                if (!(std::fabs(x) < 65504.0f))            // (include/uu3d.h, RANGE CONTRACT: the hi plane of such a weight is Inf)
-                    return fail(m, UU3D_ERR_RANGE, "a Dense / Conv1D kernel holds a value of magnitude >= 65504 (or a non-finite one): not representable by the f16x3 operand planes; build the model with precision f32");
-                const _Float16 h = h3_hi(x);
-                hb[hi + i] = h; hb[lo + i] = (_Float16)((x - (float)h) * H3_SCALE);
-            }
+            if (!split_operand_planes(P.buf.data() + d.first, d.second, hb.data() + hi, hb.data() + lo))      // (uu3d_pack.h; include/uu3d.h, RANGE CONTRACT: the hi plane of such a weight is Inf)
+                return fail(m, UU3D_ERR_RANGE, "a Dense / Conv1D kernel holds a value of magnitude >= 65504 (or a non-finite one): not representable by the f16x3 operand planes; build the model with precision f32");
             m->hplanes[d.first] = {hi, lo};
         }
         {   // spatial stack: A-operand fragments of W^T (uu3d_spatial_h3.h), [n-tile][kk][plane][lane][8]

@@ -97,38 +97,6 @@ struct Launcher {
         if (e != hipSuccess && status == UU3D_OK) { status = UU3D_ERR_HIP; m->err = std::string("kernel launch failed: ") + hipGetErrorString(e); }
     }
 
-    template <int BM, int BN, class AL, class EP>
-    void gemm_tile(const AL& al, const float* Bt, int M, int N, int Kp, int slices, int kt_per_split, const EP& ep) {
-        auto kern = gemm_f32_kernel<BM, BN, AL, EP>;
-        constexpr size_t lds = gemm_lds_bytes(BM, BN);
-        allow_lds<gemm_f32_kernel<BM, BN, AL, EP>>(lds);
-        const int mt = (M + BM - 1) / BM, nt = (N + BN - 1) / BN;
-        const int grid = round_up(mt, 8) * nt;
-        hipLaunchKernelGGL(kern, dim3(grid, slices), dim3(256), lds, stream, al, Bt, M, N, Kp, mt, nt, kt_per_split, ep);
-    }
-
-    template <int TM, int TN, class AL, class EP>
-    void gemm_h3_tile(const AL& al, const _Float16* Bh, const _Float16* Bl, int M, int N, int Kp, int slices, int kt_per_split, const EP& ep) {
-        auto kern = gemm_h3_kernel<TM, TN, AL, EP>;
-        auto kern_deep = gemm_h3_kernel<TM, TN, AL, EP, 1>;     // few workgroups per CU: loads three k-tiles ahead (uu3d_gemm_h3.h)
-        constexpr size_t lds = gemm_h3_lds_bytes(64 * TM, 64 * TN);
-        allow_lds<gemm_h3_kernel<TM, TN, AL, EP>>(lds); allow_lds<gemm_h3_kernel<TM, TN, AL, EP, 1>>(lds);
-        const int mt = (M + 64 * TM - 1) / (64 * TM), nt = (N + 64 * TN - 1) / (64 * TN);
-        const int grid = round_up(mt, 8) * nt;
-        if (gemm_h3_deep(grid * slices)) hipLaunchKernelGGL(kern_deep, dim3(grid, slices), dim3(256), lds, stream, al, Bh, Bl, M, N, Kp, mt, nt, kt_per_split, ep);
-        else hipLaunchKernelGGL(kern, dim3(grid, slices), dim3(256), lds, stream, al, Bh, Bl, M, N, Kp, mt, nt, kt_per_split, ep);
-    }
-
-    template <int TM, int TN, class GL, class EP>
-    void gemm_h3g_tile(const GL& gl, const _Float16* Bh, const _Float16* Bl, int M, int N, int Kp, int slices, int kt_per_split, const EP& ep) {
-        auto kern = gemm_h3g_kernel<TM, TN, GL, EP>;
-        constexpr size_t lds = gemm_h3g_lds_bytes(64 * TM, 64 * TN);
-        allow_lds<gemm_h3g_kernel<TM, TN, GL, EP>>(lds);
-        const int mt = (M + 64 * TM - 1) / (64 * TM), nt = (N + 64 * TN - 1) / (64 * TN);
-        const int grid = round_up(mt, 8) * nt;
-        hipLaunchKernelGGL(kern, dim3(grid, slices), dim3(256), lds, stream, gl, Bh, Bl, M, N, Kp, mt, nt, kt_per_split, ep);
-    }
-
     // Workgroups a split-K GEMM aims for: enough to fill the chip three times over when the launch has it to itself (latency); under the throughput
     // schedule the chip is shared and a launch costs its CU-microseconds -- hundreds of workgroups that each wait ten microseconds for a few
     // hundred kilobytes are expensive then (round 5: strided blocks 2 and 3, 7 GFLOP, cost 9 % of the pipelined step)
@@ -140,27 +108,10 @@ struct Launcher {
     // epilogue): LDS-DMA staged kernel, K % 32 == 0.  Same split-K policy as gemm().
     template <class GL, class EP>
     void gemm_g(const char* name, const GL& gl, const float* Bt, int M, int N, int K, const EP& ep, double extra_bytes = 0) {
-        const int KT = K / 32;
-        const int tiles = ((M + 63) / 64) * ((N + 63) / 64);
-        const auto [slices, kps] = splitk_rule(M, N, KT, splitk_target(), slab_floats, true);
-        const int ldslab = round_up(N, 4);
         begin(name, "gemm_h3", 2.0 * M * (double)N * K, 4.0 * ((double)M * K + (double)N * K + (double)M * N) + extra_bytes);
         const auto it = m->hplanes.find((size_t)(Bt - m->arena));
         if ((K % 32) != 0 || it == m->hplanes.end()) { status = UU3D_ERR_INVALID_ARGUMENT; m->err = "gemm_g: operand without f16 planes or K % 32 != 0"; end(); return; }
-        const _Float16* Bh = m->harena + it->second.first; const _Float16* Bl = m->harena + it->second.second;
-        if (slices == 1) {
-            // measured (tools/gemm_bench, M = 4544 / 1472 rows): 64x128 is the fastest LDS-DMA tile down to ~200 tiles
-            if (N % 128 == 0 && tiles >= 256) gemm_h3g_tile<1, 2>(gl, Bh, Bl, M, N, K, 1, KT, ep);
-            else gemm_h3g_tile<1, 1>(gl, Bh, Bl, M, N, K, 1, KT, ep);
-        } else {
-            EpSlab es{slab, ldslab, (size_t)M * ldslab};
-            // split K with many tiles (strided block 1's convolution: 276 tiles x 3 slices of K = 768): 64 x 128 tiles move a
-            // quarter less through L2 -> LDS than 64 x 64 (41.6 -> 36.5 us); with few tiles the 64 x 64 grid fills more CUs
-            if (N % 128 == 0 && tiles >= 200) gemm_h3g_tile<1, 2>(gl, Bh, Bl, M, N, K, slices, kps, es);
-            else gemm_h3g_tile<1, 1>(gl, Bh, Bl, M, N, K, slices, kps, es);
-            hipLaunchKernelGGL(splitk_reduce_kernel<EP>, dim3((M * N + 255) / 256), dim3(256), 0, stream,
-                               slab, slices, (size_t)M * ldslab, M, N, ldslab, ep);
-        }
+        launch_fwd_gemm_g(stream, gl, m->harena + it->second.first, m->harena + it->second.second, M, N, K, ep, slab, slab_floats, splitk_target());      // tile shape and split: uu3d_launch.h
         end();
     }
 
@@ -268,41 +219,19 @@ struct Launcher {
         end();
     }
 
-    // C[M][N] = A[M][K] * W.  64x64 tiles (4 workgroups per CU) measured fastest on every shape
-    // of this model (tools/gemm_bench.hip).  Problems with too few tiles to fill the chip are
-    // split along K into slabs and combined deterministically (splitk_reduce_kernel).
+    // C[M][N] = A[M][K] * W on the tiled kernels: f16x3 (gemm_h3_kernel, the loader's rows split while they are staged) or exact f32
+    // (gemm_f32_kernel) by this call's precision.  Tile shape, DEEP form and split: launch_fwd_gemm (uu3d_launch.h).
     template <class AL, class EP>
     void gemm(const char* name, const AL& al, const float* Bt, int M, int N, int K, const EP& ep, double extra_bytes = 0) {
-        const int Kp = round_up(K, 32), KT = Kp / 32;
-        const int tiles = ((M + 63) / 64) * ((N + 63) / 64);
-        const auto [slices, kps] = splitk_rule(M, N, KT, splitk_target(), slab_floats, true);
-        const int ldslab = round_up(N, 4);
         const bool h3 = (precision == UU3D_PREC_F16X3);
         begin(name, h3 ? "gemm_h3" : "gemm_f32", 2.0 * M * (double)N * K, 4.0 * ((double)M * K + (double)N * K + (double)M * N) + extra_bytes);
+        const _Float16* Bh = nullptr; const _Float16* Bl = nullptr;
         if (h3) {
             const auto it = m->hplanes.find((size_t)(Bt - m->arena));
             if (it == m->hplanes.end()) { status = UU3D_ERR_INVALID_ARGUMENT; m->err = "operand without f16 planes"; end(); return; }
-            const _Float16* Bh = m->harena + it->second.first; const _Float16* Bl = m->harena + it->second.second;
-            if (slices == 1) {
-                // measured (tools/gemm_bench): 64x128 is the fastest f16x3 tile on every shape of the model
-                if (N % 128 == 0 && tiles >= 512) gemm_h3_tile<1, 2>(al, Bh, Bl, M, N, Kp, 1, KT, ep);
-                else gemm_h3_tile<1, 1>(al, Bh, Bl, M, N, Kp, 1, KT, ep);
-            } else {
-                EpSlab es{slab, ldslab, (size_t)M * ldslab};
-                gemm_h3_tile<1, 1>(al, Bh, Bl, M, N, Kp, slices, kps, es);
-                hipLaunchKernelGGL(splitk_reduce_kernel<EP>, dim3((M * N + 255) / 256), dim3(256), 0, stream,
-                                   slab, slices, (size_t)M * ldslab, M, N, ldslab, ep);
-            }
-        } else if (slices == 1) {
-            // measured (tools/gemm_bench): 64x128 beats 64x64 by ~8 % on the N = 384 GEMMs, loses elsewhere
-            if (N % 128 == 0 && N <= 512 && tiles >= 512) gemm_tile<64, 128>(al, Bt, M, N, Kp, 1, KT, ep);
-            else gemm_tile<64, 64>(al, Bt, M, N, Kp, 1, KT, ep);
-        } else {
-            EpSlab es{slab, ldslab, (size_t)M * ldslab};
-            gemm_tile<64, 64>(al, Bt, M, N, Kp, slices, kps, es);
-            hipLaunchKernelGGL(splitk_reduce_kernel<EP>, dim3((M * N + 255) / 256), dim3(256), 0, stream,
-                               slab, slices, (size_t)M * ldslab, M, N, ldslab, ep);
+            Bh = m->harena + it->second.first; Bl = m->harena + it->second.second;
         }
+        launch_fwd_gemm(stream, al, Bt, Bh, Bl, M, N, K, ep, slab, slab_floats, splitk_target(), precision);
         end();
     }
 

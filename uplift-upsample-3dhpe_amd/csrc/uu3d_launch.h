@@ -351,6 +351,98 @@ bool launch_gemm_wt(hipStream_t stream, const AL& al, const _Float16* Bh, const 
     return true;
 }
 
+// ---- forward: the tiled GEMMs (uu3d_gemm.h, uu3d_gemm_h3.h).  Tile shape, DEEP form and split are decided HERE and nowhere else: the forward's
+// Launcher::gemm / gemm_g and the operator ABI (uu3d_op_tiled_dense) both launch through launch_fwd_gemm / launch_fwd_gemm_g. ----
+template <int BM, int BN, class AL, class EP>
+void launch_gemm_f32_tile(hipStream_t stream, const AL& al, const float* Bt, int M, int N, int Kp, int slices, int kt_per_split, const EP& ep) {
+    auto kern = gemm_f32_kernel<BM, BN, AL, EP>;
+    constexpr size_t lds = gemm_lds_bytes(BM, BN);
+    allow_lds<gemm_f32_kernel<BM, BN, AL, EP>>(lds);
+    const int mt = (M + BM - 1) / BM, nt = (N + BN - 1) / BN;
+    const int grid = ru(mt, 8) * nt;
+    hipLaunchKernelGGL(kern, dim3(grid, slices), dim3(256), lds, stream, al, Bt, M, N, Kp, mt, nt, kt_per_split, ep);
+}
+template <int TM, int TN, class AL, class EP>
+void launch_gemm_h3_tile(hipStream_t stream, const AL& al, const _Float16* Bh, const _Float16* Bl, int M, int N, int Kp, int slices, int kt_per_split, const EP& ep) {
+    auto kern = gemm_h3_kernel<TM, TN, AL, EP>;
+    auto kern_deep = gemm_h3_kernel<TM, TN, AL, EP, 1>;     // few workgroups per CU: loads three k-tiles ahead (uu3d_gemm_h3.h)
+    constexpr size_t lds = gemm_h3_lds_bytes(64 * TM, 64 * TN);
+    allow_lds<gemm_h3_kernel<TM, TN, AL, EP>>(lds); allow_lds<gemm_h3_kernel<TM, TN, AL, EP, 1>>(lds);
+    const int mt = (M + 64 * TM - 1) / (64 * TM), nt = (N + 64 * TN - 1) / (64 * TN);
+    const int grid = ru(mt, 8) * nt;
+    if (gemm_h3_deep(grid * slices)) hipLaunchKernelGGL(kern_deep, dim3(grid, slices), dim3(256), lds, stream, al, Bh, Bl, M, N, Kp, mt, nt, kt_per_split, ep);
+    else hipLaunchKernelGGL(kern, dim3(grid, slices), dim3(256), lds, stream, al, Bh, Bl, M, N, Kp, mt, nt, kt_per_split, ep);
+}
+template <int TM, int TN, class GL, class EP>
+void launch_gemm_h3g_tile(hipStream_t stream, const GL& gl, const _Float16* Bh, const _Float16* Bl, int M, int N, int Kp, int slices, int kt_per_split, const EP& ep) {
+    auto kern = gemm_h3g_kernel<TM, TN, GL, EP>;
+    constexpr size_t lds = gemm_h3g_lds_bytes(64 * TM, 64 * TN);
+    allow_lds<gemm_h3g_kernel<TM, TN, GL, EP>>(lds);
+    const int mt = (M + 64 * TM - 1) / (64 * TM), nt = (N + 64 * TN - 1) / (64 * TN);
+    const int grid = ru(mt, 8) * nt;
+    hipLaunchKernelGGL(kern, dim3(grid, slices), dim3(256), lds, stream, gl, Bh, Bl, M, N, Kp, mt, nt, kt_per_split, ep);
+}
+template <class EP>
+void launch_splitk_reduce(hipStream_t stream, const float* slab, int slices, int M, int N, const EP& ep) {
+    const int ldslab = ru(N, 4);
+    hipLaunchKernelGGL(splitk_reduce_kernel<EP>, dim3((M * N + 255) / 256), dim3(256), 0, stream, slab, slices, (size_t)M * ldslab, M, N, ldslab, ep);
+}
+// C[M][N] = A-op[M][K] W with the A operand read by a loader of uu3d_gemm.h (f32 rows; the f16x3 kernel splits them while it stages them).
+//   precision f16x3: gemm_h3_kernel on the operand's planes Bh / Bl;  f32: gemm_f32_kernel on Bt.  All three [Np][Kp], Kp = round_up(K, 32).
+//   64 x 64 tiles (4 workgroups per CU) measured fastest on every shape of the model but the ones named below (tools/gemm_bench.hip).
+//   Problems with too few tiles to fill the chip are split along K into slabs and combined deterministically (splitk_reduce_kernel):
+//   splitk_rule with the forward's exception, aiming for `target` workgroups, the slab holding slab_floats floats.
+// Launches only; the caller reads the launch error.
+template <class AL, class EP>
+void launch_fwd_gemm(hipStream_t stream, const AL& al, const float* Bt, const _Float16* Bh, const _Float16* Bl, int M, int N, int K, const EP& ep,
+                     float* slab, size_t slab_floats, int target, int precision) {
+    const int Kp = ru(K, 32), KT = Kp / 32;
+    const int tiles = ((M + 63) / 64) * ((N + 63) / 64);
+    const auto [slices, kps] = splitk_rule(M, N, KT, target, slab_floats, true);
+    const int ldslab = ru(N, 4);
+    if (precision == UU3D_PREC_F16X3) {
+        if (slices == 1) {
+            // measured (tools/gemm_bench): 64x128 is the fastest f16x3 tile on every shape of the model
+            if (N % 128 == 0 && tiles >= 512) launch_gemm_h3_tile<1, 2>(stream, al, Bh, Bl, M, N, Kp, 1, KT, ep);
+            else launch_gemm_h3_tile<1, 1>(stream, al, Bh, Bl, M, N, Kp, 1, KT, ep);
+        } else {
+            EpSlab es{slab, ldslab, (size_t)M * ldslab};
+            launch_gemm_h3_tile<1, 1>(stream, al, Bh, Bl, M, N, Kp, slices, kps, es);
+            launch_splitk_reduce(stream, slab, slices, M, N, ep);
+        }
+    } else if (slices == 1) {
+        // measured (tools/gemm_bench): 64x128 beats 64x64 by ~8 % on the N = 384 GEMMs, loses elsewhere
+        if (N % 128 == 0 && N <= 512 && tiles >= 512) launch_gemm_f32_tile<64, 128>(stream, al, Bt, M, N, Kp, 1, KT, ep);
+        else launch_gemm_f32_tile<64, 64>(stream, al, Bt, M, N, Kp, 1, KT, ep);
+    } else {
+        EpSlab es{slab, ldslab, (size_t)M * ldslab};
+        launch_gemm_f32_tile<64, 64>(stream, al, Bt, M, N, Kp, slices, kps, es);
+        launch_splitk_reduce(stream, slab, slices, M, N, ep);
+    }
+}
+// The f16x3 GEMM whose A operand already is a pair of f16 planes (written by ln_split / attention / the ReLU epilogue / the spatial stack):
+// the LDS-DMA kernel gemm_h3g_kernel, K % 32 == 0 (the caller checks).  Same split-K policy as launch_fwd_gemm.
+template <class GL, class EP>
+void launch_fwd_gemm_g(hipStream_t stream, const GL& gl, const _Float16* Bh, const _Float16* Bl, int M, int N, int K, const EP& ep,
+                       float* slab, size_t slab_floats, int target) {
+    const int KT = K / 32;
+    const int tiles = ((M + 63) / 64) * ((N + 63) / 64);
+    const auto [slices, kps] = splitk_rule(M, N, KT, target, slab_floats, true);
+    const int ldslab = ru(N, 4);
+    if (slices == 1) {
+        // measured (tools/gemm_bench, M = 4544 / 1472 rows): 64x128 is the fastest LDS-DMA tile down to ~200 tiles
+        if (N % 128 == 0 && tiles >= 256) launch_gemm_h3g_tile<1, 2>(stream, gl, Bh, Bl, M, N, K, 1, KT, ep);
+        else launch_gemm_h3g_tile<1, 1>(stream, gl, Bh, Bl, M, N, K, 1, KT, ep);
+    } else {
+        EpSlab es{slab, ldslab, (size_t)M * ldslab};
+        // split K with many tiles (strided block 1's convolution: 276 tiles x 3 slices of K = 768): 64 x 128 tiles move a
+        // quarter less through L2 -> LDS than 64 x 64 (41.6 -> 36.5 us); with few tiles the 64 x 64 grid fills more CUs
+        if (N % 128 == 0 && tiles >= 200) launch_gemm_h3g_tile<1, 2>(stream, gl, Bh, Bl, M, N, K, slices, kps, es);
+        else launch_gemm_h3g_tile<1, 1>(stream, gl, Bh, Bl, M, N, K, slices, kps, es);
+        launch_splitk_reduce(stream, slab, slices, M, N, ep);
+    }
+}
+
 // ---- forward: temporal self-attention, head dim 48 (uu3d_attn.h, uu3d_attn_h3.h).  Which kernel a launch takes is decided HERE and nowhere else. ----
 constexpr int kAttnDH = 48;
 enum AttnKernel : int { ATTN_AUTO = 0, ATTN_F32_WG = 1, ATTN_HEAD_WAVE = 2, ATTN_H3 = 3,         // = UU3D_ATTN_* of include/uu3d_ops.h

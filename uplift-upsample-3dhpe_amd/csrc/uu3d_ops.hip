@@ -7,6 +7,7 @@
 #include "uu3d_misc.h"
 #include "uu3d_bwd.h"
 #include "uu3d_launch.h"
+#include "uu3d_pack.h"
 #include "uu3d_tchain16.h"      // tchain_qf_index, tchain_qf_halfs
 #include <vector>
 #include <initializer_list>
@@ -276,4 +277,118 @@ int uu3d_op_attn_infer(const void* qkv, int32_t in_layout, int32_t D, int32_t B,
     const size_t lo_off = planes_out ? (size_t)B * L * D : 0;
     const int st = launch_attn_infer((hipStream_t)stream, reinterpret_cast<const float*>(qkv), D, B, L, H, mask, reinterpret_cast<float*>(out), lo_off, frag, qfrag, rule);
     return st != UU3D_OK ? st : hip_status();
+}
+
+// ---- the forward's tiled GEMMs (launch_fwd_gemm / launch_fwd_gemm_g, uu3d_launch.h: the launches Launcher::gemm / gemm_g make) ----
+size_t uu3d_op_tiled_operand_bytes(int32_t N, int32_t K) { return (N < 1 || K < 1) ? 0 : (size_t)ru(N, 128) * ru(K, 32) * (sizeof(float) + 2 * sizeof(_Float16)); }
+
+int uu3d_op_tiled_pack(const float* w, int32_t K, int32_t N, void* operand_dev, void* stream_) {
+    if (!w || !operand_dev || K < 1 || N < 1) return UU3D_ERR_INVALID_ARGUMENT;
+    const int Kp = ru(K, 32);
+    const size_t n = (size_t)ru(N, 128) * Kp;
+    std::vector<float> bt(n, 0.f);
+    pack_dense_t(bt.data(), 0, w, K, N, Kp, 0);                      // the commit's pack and split (uu3d_pack.h)
+    std::vector<_Float16> planes(2 * n);
+    if (!split_operand_planes(bt.data(), n, planes.data(), planes.data() + n)) return UU3D_ERR_RANGE;
+    hipStream_t stream = (hipStream_t)stream_;
+    if (hipMemcpyAsync(operand_dev, bt.data(), n * sizeof(float), hipMemcpyHostToDevice, stream) != hipSuccess) return UU3D_ERR_HIP;
+    if (hipMemcpyAsync(reinterpret_cast<float*>(operand_dev) + n, planes.data(), 2 * n * sizeof(_Float16), hipMemcpyHostToDevice, stream) != hipSuccess) return UU3D_ERR_HIP;
+    return hipStreamSynchronize(stream) == hipSuccess ? UU3D_OK : UU3D_ERR_HIP;
+}
+
+int uu3d_op_tiled_split(int32_t M, int32_t N, int32_t K, int32_t target, size_t slab_floats, int32_t* slices, int32_t* kps) {
+    if (M < 1 || N < 1 || K < 1 || target < 1 || !slices || !kps) return UU3D_ERR_INVALID_ARGUMENT;
+    const SplitK s = splitk_rule(M, N, ru(K, 32) / 32, target, slab_floats, true);
+    *slices = s.slices; *kps = s.kps;
+    return UU3D_OK;
+}
+
+// >= 16 bytes of zeros on the device: what an out-of-range tap of GLoadConv3 reads (the forward's: the head of the model's f16 arena)
+static const _Float16* conv_zero_source() {
+    static const _Float16* const z = [] {
+        void* p = nullptr;
+        if (hipMalloc(&p, 128) != hipSuccess) return (const _Float16*)nullptr;
+        if (hipMemset(p, 0, 128) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { (void)hipFree(p); return (const _Float16*)nullptr; }
+        return (const _Float16*)p;
+    }();
+    return z;
+}
+
+int uu3d_op_tiled_dense(const uu3d_tiled_dense_args* a, void* stream_) {
+    if (!a) return UU3D_ERR_INVALID_ARGUMENT;
+    const int M = a->M, N = a->N, K = a->K, src = a->a_source, epi = a->epilogue;
+    if (!a->a_dev || !a->operand_dev || !a->bias_dev || !a->out_dev || M < 1 || N < 1 || K < 1) return UU3D_ERR_INVALID_ARGUMENT;
+    if ((a->precision != UU3D_PREC_F16X3 && a->precision != UU3D_PREC_F32) || a->splitk_target < 1 || (a->slab_floats != 0 && !a->slab_dev)) return UU3D_ERR_INVALID_ARGUMENT;
+    const bool h3 = a->precision == UU3D_PREC_F16X3;
+    const bool conv = src == UU3D_A_CONV3_F32 || src == UU3D_A_CONV3_PLANES, planes = src == UU3D_A_PLANES || src == UU3D_A_CONV3_PLANES;
+    // the combinations uu3d_forward.inc launches (include/uu3d_ops.h lists them by call site)
+    bool known = false;
+    switch (src) {
+        case UU3D_A_F32: known = epi == UU3D_EP_BIAS || epi == UU3D_EP_BIAS_RESIDUAL || epi == UU3D_EP_S2T; break;
+        case UU3D_A_F32_LN: known = epi == UU3D_EP_BIAS || epi == UU3D_EP_BIAS_RELU || (h3 && (epi == UU3D_EP_BIAS_SPLIT_Q || epi == UU3D_EP_BIAS_RELU_SPLIT)); break;
+        case UU3D_A_PLANES: known = h3 && (epi == UU3D_EP_BIAS_RESIDUAL || epi == UU3D_EP_S2T); break;
+        case UU3D_A_CONV3_F32: known = epi == UU3D_EP_CONV_RESIDUAL; break;
+        case UU3D_A_CONV3_PLANES: known = h3 && epi == UU3D_EP_CONV_RESIDUAL; break;
+        default: break;
+    }
+    if (!known) return UU3D_ERR_INVALID_ARGUMENT;
+    // the A source
+    int lda = a->lda;
+    if (conv) {
+        const int Cc = a->conv_C;
+        if (Cc < 1 || (Cc % (planes ? 32 : 4)) != 0 || (int64_t)K != (int64_t)3 * Cc || a->conv_L_in < 1 || a->conv_L_out < 1 || a->conv_stride < 1 || a->conv_pad_left < 0 ||
+            M % a->conv_L_out != 0 || !a->xin_dev) return UU3D_ERR_INVALID_ARGUMENT;
+        const int lo = (a->conv_stride > 1 && a->conv_pad_left == 0) ? 1 : 0;
+        if ((int64_t)(a->conv_L_out - 1) * a->conv_stride + lo >= a->conv_L_in) return UU3D_ERR_INVALID_ARGUMENT;      // the identity row of the last output row
+        if ((double)(M / a->conv_L_out) * a->conv_L_in * std::max(Cc, N) >= 536870912.0) return UU3D_ERR_UNSUPPORTED;
+        lda = Cc;
+    } else if (planes ? (K % 32 != 0 || lda < K || lda % 8 != 0) : (K % 4 != 0 || lda < K || lda % 4 != 0)) return UU3D_ERR_INVALID_ARGUMENT;
+    if (planes && !a->a_lo_dev) return UU3D_ERR_INVALID_ARGUMENT;
+    if (src == UU3D_A_F32_LN && (!a->ln_stats_dev || !a->ln_gamma_dev || !a->ln_beta_dev)) return UU3D_ERR_INVALID_ARGUMENT;
+    // the epilogue
+    if ((epi == UU3D_EP_BIAS || epi == UU3D_EP_BIAS_RELU) && a->ldo < N) return UU3D_ERR_INVALID_ARGUMENT;
+    if (epi == UU3D_EP_BIAS_SPLIT_Q && N % 3 != 0) return UU3D_ERR_INVALID_ARGUMENT;
+    const bool reads_pe = epi == UU3D_EP_S2T || (epi == UU3D_EP_BIAS_RESIDUAL && a->out2_dev != nullptr);
+    if (reads_pe && (!a->pe_dev || a->period < 1)) return UU3D_ERR_INVALID_ARGUMENT;
+    if (epi == UU3D_EP_S2T && a->mask_dev != nullptr && !a->token_dev) return UU3D_ERR_INVALID_ARGUMENT;
+    if ((double)M * ru(std::max(std::max(N, lda), (epi == UU3D_EP_BIAS || epi == UU3D_EP_BIAS_RELU) ? a->ldo : N), 4) >= 536870912.0) return UU3D_ERR_UNSUPPORTED;   // 32-bit M * N in the combine's grid
+    const _Float16* zero = nullptr;
+    if (src == UU3D_A_CONV3_PLANES && (zero = conv_zero_source()) == nullptr) return UU3D_ERR_HIP;
+
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t nb = (size_t)ru(N, 128) * ru(K, 32);
+    const float* Bt = reinterpret_cast<const float*>(a->operand_dev);
+    const _Float16* Bh = reinterpret_cast<const _Float16*>(Bt + nb); const _Float16* Bl = Bh + nb;
+    const float* Af = reinterpret_cast<const float*>(a->a_dev);
+    const _Float16* Ah = reinterpret_cast<const _Float16*>(a->a_dev); const _Float16* Al = reinterpret_cast<const _Float16*>(a->a_lo_dev);
+    float* outf = reinterpret_cast<float*>(a->out_dev);
+    _Float16* oh = reinterpret_cast<_Float16*>(a->out_dev);
+    auto rows = [&](const auto& al, const auto& ep) { launch_fwd_gemm(stream, al, Bt, Bh, Bl, M, N, K, ep, a->slab_dev, a->slab_floats, a->splitk_target, a->precision); };
+    auto dma = [&](const auto& gl, const auto& ep) { launch_fwd_gemm_g(stream, gl, Bh, Bl, M, N, K, ep, a->slab_dev, a->slab_floats, a->splitk_target); };
+    const EpBias ep_bias{outf, a->bias_dev, a->ldo};
+    const EpBiasResidual ep_res{outf, a->bias_dev, N, a->out2_dev, a->out2_dev ? a->pe_dev : nullptr, a->out2_dev ? a->period : 1};
+    const EpSpatialToTemporal ep_s2t{outf, a->bias_dev, N, a->mask_dev, a->token_dev, a->pe_dev, a->period};
+    // MaxPool1D(pool 1, stride s) on the trimmed sequence; stride 1 keeps x untrimmed (the forward's strided_blocks)
+    const int lo = (a->conv_stride > 1 && a->conv_pad_left == 0) ? 1 : 0;
+    const EpConvResidual ep_conv{outf, a->bias_dev, N, a->xin_dev, a->conv_L_in, a->conv_L_out, a->conv_stride, lo, a->pe_dev};
+    switch (src) {
+        case UU3D_A_F32: {
+            const ALoadPlain al{Af, lda, M, K};
+            if (epi == UU3D_EP_BIAS) rows(al, ep_bias); else if (epi == UU3D_EP_BIAS_RESIDUAL) rows(al, ep_res); else rows(al, ep_s2t);
+        } break;
+        case UU3D_A_F32_LN: {
+            const ALoadLayerNorm al{Af, reinterpret_cast<const float2*>(a->ln_stats_dev), a->ln_gamma_dev, a->ln_beta_dev, lda, M, K};
+            if (epi == UU3D_EP_BIAS) rows(al, ep_bias);
+            else if (epi == UU3D_EP_BIAS_RELU) rows(al, EpBiasRelu{outf, a->bias_dev, a->ldo});
+            else if (epi == UU3D_EP_BIAS_RELU_SPLIT) rows(al, EpBiasReluSplit{oh, oh + (size_t)M * N, a->bias_dev, N});
+            else rows(al, EpBiasSplitQ{oh, oh + (size_t)M * N, a->bias_dev, N, N / 3, a->qscale});
+        } break;
+        case UU3D_A_PLANES: {
+            const GLoadPlain gl{Ah, Al, lda, M};
+            if (epi == UU3D_EP_BIAS_RESIDUAL) dma(gl, ep_res); else dma(gl, ep_s2t);
+        } break;
+        case UU3D_A_CONV3_F32: rows(ALoadConv3{Af, a->conv_C, a->conv_L_in, a->conv_L_out, a->conv_stride, a->conv_pad_left, M, K}, ep_conv); break;
+        default: dma(GLoadConv3{Ah, Al, zero, a->conv_C, a->conv_L_in, a->conv_L_out, a->conv_stride, a->conv_pad_left, M}, ep_conv); break;
+    }
+    return hip_status();
 }
