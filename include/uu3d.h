@@ -875,7 +875,7 @@ int uu3d_stream_root_reset(int32_t slots, int32_t num_keypoints, int32_t lookahe
  * STEADY OUTPUT (predict.predict_tracks(smooth=...), predict.one_euro; stream.StreamSession(smooth=...), stream.LiveOneEuro): the One-Euro
  * filter (Casiez, Roussel, Vogel 2012) over the poses and roots a call or a session returns -- an exponential smoother whose cut-off rises
  * with the speed of the signal.  No model: the calls take the channel count C and run on any (rows, C) f32 buffers.  Nothing is claimed
- * about accuracy or jitter; the filter is causal and lags.
+ * about accuracy or jitter; the filter is causal and lags -- offline, the two-pass form below takes the lag out.
  * THE RULE (predict.one_euro_host is it in numpy, bit for bit).  A CHANNEL is one scalar over time; a filter is (min_cutoff > 0, beta >= 0,
  * d_cutoff > 0) in Hz, 1 / unit speed and Hz.  Per channel the state is xh, dxh (f64) and whether a sample was taken; x is the f32 value
  * widened, r the sample rate in Hz:
@@ -892,6 +892,16 @@ int uu3d_stream_root_reset(int32_t slots, int32_t num_keypoints, int32_t lookahe
  *       track_len_dev (num_tracks) i64: the rows of each track, rates_dev (num_tracks) f64: its rate in Hz, num_tracks <= 2^20,
  *       state_dev (rows) u8 or NULL, min_cutoff, beta, d_cutoff, stream): one launch, one lane per (track, channel) walks the track's rows
  *       in order; adjacent lanes are adjacent channels of one row.  Rows of no track are not written.
+ *   ZERO LAG, OFFLINE ONLY (predict.OneEuro(zero_lag=True)).  A finished track is filtered in two passes: pass 1 is the walk above and
+ *   yields the f32 rows y; pass 2 is the same walk over y with the track's rows taken LAST TO FIRST -- the same rate, the same parameters,
+ *   the same state bytes reversed with the rows, xh / dxh / taken fresh -- and its output, put back in row order, is the result.  A row
+ *   with state 0, or a non-finite sample, is passed through unchanged by both passes and takes no sample in either; each pass takes its
+ *   first usable sample as given, so a track's last usable row comes out as pass 1 left it.  The intermediate is the f32 y: per track
+ *   the result is reverse(walk(reverse(walk(x)))), bit for bit (predict.one_euro_host with such a filter).  On a ramp the forward and the
+ *   backward lag are one constant and cancel.  A live filter cannot do this -- it has no last row -- and the wrappers refuse it.
+ *   uu3d_one_euro_tracks_two_pass(the arguments and status codes of uu3d_one_euro_tracks): one launch, the same grid; behind its forward
+ *       walk the lane walks back from the track's last row to its first over the values it wrote to out_dev itself and writes the final
+ *       value in place.  No scratch buffer, no atomics, every element still has one writer; in_dev is only read, out != in.
  *   LIVE.  The state block of uu3d_stream_one_euro_bytes(slots, C) bytes (0: out of range -- slots in [1, 2^20], C in [1, 65536]), 256-byte
  *   aligned, zeroed by uu3d_stream_one_euro_reset, holds per slot and channel xh, dxh, the frame index of the last sample (i32) and a TAKEN
  *   byte.  frames_dev (slots) i32 is each slot's frame counter AFTER the push; the fresh value belongs to frame f = frames - 1 - lookahead.
@@ -907,6 +917,9 @@ int uu3d_stream_root_reset(int32_t slots, int32_t num_keypoints, int32_t lookahe
 int uu3d_one_euro_tracks(const float* in_dev, float* out_dev, int64_t rows, int32_t channels, const int64_t* track_start_dev,
                          const int64_t* track_len_dev, const double* rates_dev, int32_t num_tracks, const uint8_t* state_dev, double min_cutoff,
                          double beta, double d_cutoff, void* stream);
+int uu3d_one_euro_tracks_two_pass(const float* in_dev, float* out_dev, int64_t rows, int32_t channels, const int64_t* track_start_dev,
+                                  const int64_t* track_len_dev, const double* rates_dev, int32_t num_tracks, const uint8_t* state_dev,
+                                  double min_cutoff, double beta, double d_cutoff, void* stream);
 size_t uu3d_stream_one_euro_bytes(int32_t slots, int32_t channels);
 int uu3d_stream_one_euro(int32_t slots, int32_t channels, int32_t lookahead, void* filter_state_dev, const int32_t* frames_dev,
                          const uint8_t* active_dev, const uint8_t* fresh_dev, const float* values_dev, const uint8_t* state_dev, double rate,

@@ -19,6 +19,10 @@ fast); the two must agree bit for bit.
 --smooth: also predict_tracks(smooth=True) -- with --camera predict_tracks(camera=..., smooth=True), poses and roots filtered -- next to the
 same call without smooth in the same process: smooth_extra_ms is the difference of the two medians (one or two more launches, each a serial
 walk over the frames of a track); the result must equal predict.one_euro_host on the unfiltered result bit for bit.
+--zero_lag (with --smooth): also predict_tracks(smooth=OneEuro(zero_lag=True)), the two-pass filter, beside the causal call and the plain call
+in the same process: zero_lag_extra_ms is its median minus the plain call's, zero_lag_over_causal_ms its median minus the causal call's (the
+same launches, each lane walking its track twice); the result must equal predict.one_euro_host with that filter bit for bit.  Informational:
+no threshold.
 --bones: also predict_tracks(bones="track") -- with --camera predict_tracks(camera=..., bones="track") -- next to the same call without bones in
 the same process: bones_extra_ms is the difference of the two medians (two more launches: the lengths, the fix); the poses must equal
 predict.fix_bones_host with predict.bone_lengths_host on the result without bones, bit for bit.  Informational: no threshold.
@@ -27,7 +31,7 @@ medians (one more launch), host_rotations_ms the plain call followed by .cpu() o
 (predict.joint_rotations_host); the quaternions must equal that rule on the returned poses bit for bit.  Informational: no threshold.
    python tools/predict_tracks_bench.py [--tracks 40] [--frames 2500] [--batch 512] [--reps 3] [--cases h36m_351:5,h36m_81:4] [--missing 0.3]
                                         [--fps 30] [--repair_joints 5 --missing_joints 0.1] [--keypoints coco17]
-                                        [--camera 1145 1145 960 540] [--smooth] [--bones] [--rotations]"""
+                                        [--camera 1145 1145 960 540] [--smooth [--zero_lag]] [--bones] [--rotations]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -48,9 +52,12 @@ def main():
     ap.add_argument("--camera", type=float, nargs=4, default=None, metavar=("FX", "FY", "CX", "CY"),
                     help="also time predict_tracks(camera=...) against .cpu() and the numpy rule behind the plain call")
     ap.add_argument("--smooth", action="store_true", help="also time predict_tracks(smooth=True) (with --camera: poses and roots) against the same call without")
+    ap.add_argument("--zero_lag", action="store_true", help="with --smooth: also time predict_tracks(smooth=OneEuro(zero_lag=True)) beside the causal call")
     ap.add_argument("--bones", action="store_true", help='also time predict_tracks(bones="track") (with --camera: with the camera) against the same call without')
     ap.add_argument("--rotations", action="store_true", help="also time predict_tracks(rotations=True) against the plain call and against .cpu() and the numpy rule")
     args = ap.parse_args()
+    if args.zero_lag and not args.smooth:
+        ap.error("--zero_lag is used together with --smooth")
     import numpy as np, torch
     import uplift_upsample_3dhpe_amd as pkg
     from uplift_upsample_3dhpe_amd import synthetic as util
@@ -158,6 +165,10 @@ def main():
             return predict.predict_tracks(model, cfg, px, resolutions=(W, H), mask_stride=int(msv), flip=True, reuse_frames=reuse, batch_size=args.batch,
                                           smooth=True, **({} if args.camera is None else {"camera": tuple(args.camera)}))
 
+        def zero_lag_path():
+            return predict.predict_tracks(model, cfg, px, resolutions=(W, H), mask_stride=int(msv), flip=True, reuse_frames=reuse, batch_size=args.batch,
+                                          smooth=predict.OneEuro(zero_lag=True), **({} if args.camera is None else {"camera": tuple(args.camera)}))
+
         def bones_path():
             return predict.predict_tracks(model, cfg, px, resolutions=(W, H), mask_stride=int(msv), flip=True, reuse_frames=reuse, batch_size=args.batch,
                                           bones="track", **({} if args.camera is None else {"camera": tuple(args.camera)}))
@@ -189,6 +200,8 @@ def main():
             cases += [("predict_tracks_camera", camera_path), ("host_camera", camera_host)]
         if args.smooth:
             cases.append(("predict_tracks_smooth", smooth_path))
+        if args.zero_lag:
+            cases.append(("predict_tracks_zero_lag", zero_lag_path))
         if args.bones:
             cases.append(("predict_tracks_bones", bones_path))
         if args.rotations:
@@ -230,12 +243,21 @@ def main():
             row["smooth_extra_ms"] = round(row["predict_tracks_smooth_ms"] - row[base + "_ms"], 1)
             lens, F = [len(t) for t in px], predict.OneEuro()
             plain, got = outs[base], outs["predict_tracks_smooth"]
-            same = lambda a, b, **kw: np.array_equal(torch.cat(a, 0).cpu().numpy().view(np.uint32),
-                                                     predict.one_euro_host(torch.cat(b, 0).cpu().numpy(), lens, 50, F, **kw).view(np.uint32))
+            same = lambda a, b, F=F, **kw: np.array_equal(torch.cat(a, 0).cpu().numpy().view(np.uint32),
+                                                          predict.one_euro_host(torch.cat(b, 0).cpu().numpy(), lens, 50, F, **kw).view(np.uint32))
             if args.camera is None:
                 row["smooth_bits_equal"] = bool(same(got, plain))
             else:
                 row["smooth_bits_equal"] = bool(same(got[0], plain[0]) and same(got[1], plain[1], state=torch.cat(plain[2], 0).cpu().numpy()))
+            if args.zero_lag:
+                row["zero_lag_extra_ms"] = round(row["predict_tracks_zero_lag_ms"] - row[base + "_ms"], 1)
+                row["zero_lag_over_causal_ms"] = round(row["predict_tracks_zero_lag_ms"] - row["predict_tracks_smooth_ms"], 1)
+                got, Z = outs["predict_tracks_zero_lag"], predict.OneEuro(zero_lag=True)
+                if args.camera is None:
+                    row["zero_lag_bits_equal"] = bool(same(got, plain, F=Z))
+                else:
+                    row["zero_lag_bits_equal"] = bool(same(got[0], plain[0], F=Z)
+                                                      and same(got[1], plain[1], F=Z, state=torch.cat(plain[2], 0).cpu().numpy()))
         if args.bones:
             base = "predict_tracks_camera" if args.camera is not None else "predict_tracks"
             row["bones_extra_ms"] = round(row["predict_tracks_bones_ms"] - row[base + "_ms"], 1)

@@ -45,7 +45,7 @@ EXPORTED_SYMBOLS = (
     "uu3d_associate_state_bytes", "uu3d_associate_reset", "uu3d_associate_detections", "uu3d_stream_associate",
     "uu3d_solve_roots", "uu3d_root_trajectory_scratch_bytes", "uu3d_root_trajectory",
     "uu3d_stream_root_bytes", "uu3d_stream_root", "uu3d_stream_root_reset",
-    "uu3d_one_euro_tracks", "uu3d_stream_one_euro_bytes", "uu3d_stream_one_euro", "uu3d_stream_one_euro_reset",
+    "uu3d_one_euro_tracks", "uu3d_one_euro_tracks_two_pass", "uu3d_stream_one_euro_bytes", "uu3d_stream_one_euro", "uu3d_stream_one_euro_reset",
     "uu3d_stream_drain_bytes", "uu3d_stream_drain_layout", "uu3d_stream_drain_commit", "uu3d_stream_root_drain", "uu3d_stream_drain_file",
     "uu3d_stream_drain_reset",
     "uu3d_bone_lengths", "uu3d_fix_bones", "uu3d_stream_bones_bytes", "uu3d_stream_bones", "uu3d_stream_bones_reset",
@@ -327,6 +327,8 @@ def load_library(path=None):
     f64 = C.c_double
     lib.uu3d_one_euro_tracks.restype = C.c_int
     lib.uu3d_one_euro_tracks.argtypes = [vp, vp, i64, i32, vp, vp, vp, i32, vp, f64, f64, f64, vp]
+    lib.uu3d_one_euro_tracks_two_pass.restype = C.c_int
+    lib.uu3d_one_euro_tracks_two_pass.argtypes = lib.uu3d_one_euro_tracks.argtypes
     lib.uu3d_stream_one_euro_bytes.restype = sz
     lib.uu3d_stream_one_euro_bytes.argtypes = [i32, i32]
     lib.uu3d_stream_one_euro.restype = C.c_int

@@ -4,10 +4,14 @@
 file writer, nothing here is bit-pinned.
 
     python -m uplift_upsample_3dhpe_amd.bvh --input out.npz --output DIR [--fps F] [--skeleton h36m17] [--lengths FILE.npy]
+                                            [--smooth MIN_CUTOFF BETA D_CUTOFF] [--smooth_root MIN_CUTOFF BETA D_CUTOFF]
 
 takes the .npz the predict command writes (per track NAME a (T, J, 3) array of poses, and NAME__root where a camera placed them),
 measures each track's bone lengths (``bone_lengths``) unless ``--lengths`` gives them, makes the skeleton rigid (``fix_bones``) and takes
-its rotations (``joint_rotations``) on the device, and writes DIR/NAME.bvh per track.
+its rotations (``joint_rotations``) on the device, and writes DIR/NAME.bvh per track.  The command is offline by nature, so its filters are
+the zero-lag ones (``smooth.OneEuro(..., zero_lag=True)``, ``smooth.one_euro``): ``--smooth`` passes the track's poses through the two-pass
+One-Euro filter at ``--fps`` BEFORE bone lengths, the rigid rebuild and the rotations; ``--smooth_root`` does the same for NAME__root, with
+NAME__root_state as the filter's state where the file has it.  Without them the files are what they were.
 
 The hierarchy is the tree of the ``Skeleton``: joint j is called ``joint<j>``, its OFFSET is ``rest[j] * lengths[j] * scale`` (the rest
 pose's unit direction of the bone above j, at the bone's length; ``scale`` 100: metres -> centimetres), leaves end in an ``End Site``
@@ -22,9 +26,11 @@ import numpy as np
 
 from .bones import skeleton_of
 from .rotations import Rotations, quat_to_matrix, rotations_of
+from .smooth import OneEuro
 from .tracks import _host_array
 
 _AXES = "XYZ"
+_FILTER = dict(type=float, nargs=3, metavar=("MIN_CUTOFF", "BETA", "D_CUTOFF"), default=None)      # --smooth / --smooth_root
 
 
 def _check_order(order):
@@ -184,7 +190,15 @@ def parse_args(argv=None):
     p.add_argument("--fps", type=float, default=50.0, help="frame rate of the poses (default 50)")
     p.add_argument("--skeleton", default="h36m17", help="name of the skeleton and its rest pose (default h36m17)")
     p.add_argument("--lengths", default=None, help=".npy with (J,) bone lengths by child joint (default: measured per track)")
-    return p.parse_args(argv)
+    p.add_argument("--smooth", **_FILTER, help="pass the poses through a zero-lag (two-pass) One-Euro filter (Hz, 1 / unit speed, Hz) at --fps, "
+                                               "before bone lengths and rotations")
+    p.add_argument("--smooth_root", **_FILTER, help="the same for NAME__root (NAME__root_state, where the file has it, says which rows are roots)")
+    args = p.parse_args(argv)
+    try:
+        args.pose_filter, args.root_filter = (None if v is None else OneEuro(*v, zero_lag=True) for v in (args.smooth, args.smooth_root))
+    except ValueError as e:
+        raise SystemExit(f"--smooth / --smooth_root: {e}") from None
+    return args
 
 
 def main(argv=None):
@@ -192,6 +206,7 @@ def main(argv=None):
 
     from .bones import bone_lengths, fix_bones
     from .rotations import joint_rotations
+    from .smooth import one_euro
     args = parse_args(argv)
     R = Rotations(args.skeleton, skeleton_of(args.skeleton))
     data = np.load(args.input)
@@ -200,11 +215,17 @@ def main(argv=None):
     os.makedirs(args.output, exist_ok=True)
     for name in names:
         poses = torch.from_numpy(np.ascontiguousarray(data[name], np.float32)).to("cuda:0")
+        if args.pose_filter is not None:
+            poses = one_euro(poses, None, args.fps, args.pose_filter)
         lengths = bone_lengths(poses, None, R.skeleton) if given is None else given
         local = joint_rotations(fix_bones(poses, None, lengths, R.skeleton), R)[0]
         L = (lengths[0].cpu().numpy() if given is None else given).copy()
         L[~np.isfinite(L)] = 0.0
         roots = data[name + "__root"] if name + "__root" in data.files else None
+        if roots is not None and args.root_filter is not None:
+            state = data[name + "__root_state"] if name + "__root_state" in data.files else None
+            roots = one_euro(torch.from_numpy(np.ascontiguousarray(roots, np.float32).reshape(-1, 3)).to("cuda:0"), None, args.fps, args.root_filter,
+                             None if state is None else torch.from_numpy(np.ascontiguousarray(state != 0).reshape(-1)).to("cuda:0"))
         path = write_bvh(os.path.join(args.output, name + ".bvh"), R.skeleton, R, L, local, roots, fps=args.fps)
         print(f"wrote {path}: {int(poses.shape[0])} frames", flush=True)
     return 0

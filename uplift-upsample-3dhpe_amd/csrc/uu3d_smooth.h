@@ -3,6 +3,7 @@
 // returns.  A CHANNEL is one scalar over time; the filter is an exponential smoother whose cut-off rises with the channel's speed.
 //     one_euro_tracks_kernel        offline: one lane per (track, channel) walks the track's rows in order -- adjacent lanes are adjacent
 //                                   channels of one row, so every step of the walk is one coalesced row read and one row write
+//     one_euro_tracks_two_pass_kernel  offline, zero lag: the same lane then walks back over the rows it wrote, in place, in the same launch
 //     stream_one_euro_kernel        live: one workgroup per slot, lanes over channels, one sample per fresh pose, the state kept per slot
 //     stream_one_euro_reset_kernel  chosen slots: back to no sample taken
 // The rule is predict.one_euro_host's, statement for statement, in float64 with every operation rounded (no fused multiply-add, IEEE
@@ -76,6 +77,68 @@ one_euro_tracks_kernel(const float* __restrict__ in, float* __restrict__ out, co
             y = (float)xh;
         }
         dst[i * C] = y;
+    }
+}
+
+// The zero-lag form (OneEuro(zero_lag=True); offline only): the arguments, the grid and pass 1 of one_euro_tracks_kernel -- a kernel of its
+// own, so the causal one stays instruction for instruction what it is.  Behind its forward walk the lane walks BACK from row n - 1 to row
+// 0 over the f32 values it wrote to out itself and writes the final value in place: the same walk with the rows taken last to first, the
+// same rate, parameters and state bytes, xh / dxh / taken fresh.  Per track the result is reverse(walk(reverse(walk(in)))), bit for bit
+// (predict.one_euro_host).  A lane reads back only its own stores, in program order: no barrier, no fence, no scratch buffer, every
+// element still has one writer.  in stays read-only (out != in).  The next row -- the one BEFORE this one on the way back -- is read
+// before this one is worked on, in both directions.
+static __global__ void __launch_bounds__(kSmoothLanes)
+one_euro_tracks_two_pass_kernel(const float* __restrict__ in, float* out, const long rows, const int C, const int64_t* __restrict__ track_start,
+                                const int64_t* __restrict__ track_len, const double* __restrict__ rates, const uint8_t* __restrict__ state,
+                                const double min_cutoff, const double beta, const double d_cutoff)
+{
+    const int c = blockIdx.y * kSmoothLanes + threadIdx.x;
+    if (c >= C) return;
+    const int track = blockIdx.x;
+    long first = track_start[track], n = track_len[track];
+    if (first < 0 || n < 1 || first >= rows) return;
+    if (n > rows - first) n = rows - first;                              // (nothing is read or written beyond the buffers)
+    const double r = rates[track];
+    const double ad = one_euro_alpha(d_cutoff, r);
+    const float* src = in + first * C + c;
+    float* dst = out + first * C + c;
+    const uint8_t* st = state == nullptr ? nullptr : state + first;
+    // pass 1: one_euro_tracks_kernel's walk, statement for statement
+    double xh = 0.0, dxh = 0.0;
+    bool taken = false;
+    float v = src[0];
+    for (long i = 0; i < n; ++i) {
+        const float cur = v;
+        if (i + 1 < n) v = src[(i + 1) * C];
+        float y = cur;
+        if ((st == nullptr || st[i] != 0) && finite_float(cur)) {
+            const double x = (double)cur;
+            if (!taken) {
+                xh = x;
+                dxh = 0.0;
+                taken = true;
+            } else one_euro_sample(x, r, ad, min_cutoff, beta, xh, dxh);
+            y = (float)xh;
+        }
+        dst[i * C] = y;
+    }
+    // pass 2: the same walk over this lane's own rows of out, last to first, in place
+    xh = 0.0;
+    dxh = 0.0;
+    taken = false;
+    v = dst[(n - 1) * C];
+    for (long i = n - 1; i >= 0; --i) {
+        const float cur = v;
+        if (i > 0) v = dst[(i - 1) * C];
+        if ((st == nullptr || st[i] != 0) && finite_float(cur)) {
+            const double x = (double)cur;
+            if (!taken) {
+                xh = x;
+                dxh = 0.0;
+                taken = true;
+            } else one_euro_sample(x, r, ad, min_cutoff, beta, xh, dxh);
+            dst[i * C] = (float)xh;
+        }
     }
 }
 

@@ -33,6 +33,24 @@ int uu3d_one_euro_tracks(const float* in, float* out, int64_t rows, int32_t C, c
     return hipGetLastError() == hipSuccess ? UU3D_OK : UU3D_ERR_HIP;
 }
 
+// The zero-lag form: the arguments, the checks (in their order) and the grid of uu3d_one_euro_tracks, which stays as it is; the other kernel.
+int uu3d_one_euro_tracks_two_pass(const float* in, float* out, int64_t rows, int32_t C, const int64_t* track_start, const int64_t* track_len,
+                                  const double* rates, int32_t num_tracks, const uint8_t* state, double min_cutoff, double beta, double d_cutoff,
+                                  void* stream) {
+    if (C > kSmoothMaxChannels) return UU3D_ERR_UNSUPPORTED;
+    if (rows < 0 || C < 1 || num_tracks < 0 || num_tracks > (1 << 20) || rows > (INT64_MAX >> 4) / C) return UU3D_ERR_INVALID_ARGUMENT;
+    if (!one_euro_params_ok(min_cutoff, beta, d_cutoff)) return UU3D_ERR_INVALID_ARGUMENT;
+    if (rows == 0 || num_tracks == 0) return UU3D_OK;
+    if (!in || !out || !track_start || !track_len || !rates || (const void*)in == (const void*)out) return UU3D_ERR_INVALID_ARGUMENT;
+    if (((uintptr_t)in & 3) != 0 || ((uintptr_t)out & 3) != 0 || ((uintptr_t)track_start & 7) != 0 || ((uintptr_t)track_len & 7) != 0 ||
+        ((uintptr_t)rates & 7) != 0)
+        return UU3D_ERR_INVALID_ARGUMENT;
+    hipLaunchKernelGGL(one_euro_tracks_two_pass_kernel, dim3((unsigned)num_tracks, (unsigned)((C + kSmoothLanes - 1) / kSmoothLanes)),
+                       dim3(kSmoothLanes), 0, (hipStream_t)stream, in, out, (long)rows, C, track_start, track_len, rates, state, min_cutoff, beta,
+                       d_cutoff);
+    return hipGetLastError() == hipSuccess ? UU3D_OK : UU3D_ERR_HIP;
+}
+
 size_t uu3d_stream_one_euro_bytes(int32_t slots, int32_t C) {
     if (slots < 1 || slots > (1 << 20) || C < 1 || C > kSmoothMaxChannels) return 0;
     return one_euro_layout(slots, C).bytes;

@@ -8,7 +8,7 @@ from .bones import check_bones
 from .keypoints import keypoint_map
 from .rotations import check_rotations
 from .roots import DEFAULT_MIN_ROOT_JOINTS, MAX_ROOT_JOINTS, check_cameras, check_min_root_joints
-from .smooth import check_smooth
+from .smooth import check_causal, check_smooth
 from .validity import check_repair_joints
 
 # cameras: (count, 4) float64 or None; min_root_joints: the checked int (a session without a camera: None); pose_filter / root_filter: a
@@ -27,6 +27,8 @@ def stage_options(config, count, per, root_relative, keypoints, camera, min_root
     is a parameter of the root solve); the offline call has the default in its signature and passes what it got.
     ``repair_joints`` is checked for its type only: whether it has the ``valid`` it needs is the caller's to say."""
     pose_filter, root_filter = check_smooth(smooth, camera is not None)
+    if per == "slot":
+        check_causal(pose_filter, root_filter)                       # (a zero-lag filter needs the whole track: offline only)
     rigid = check_bones(bones, count, config.NUM_KEYPOINTS, int(config.ROOT_KEYTPOINT) if root_relative else None, per=per)
     cameras = None
     if camera is not None:

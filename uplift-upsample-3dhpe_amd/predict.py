@@ -33,7 +33,7 @@ every name is importable from here as before:
     keypoints.py  any skeleton: ``predict_tracks(..., keypoints="coco17")`` (uu3d_map_keypoints; ``KeypointMap``, ``KEYPOINT_PRESETS``)
     associate.py  per-frame detections: ``predict_detections`` (uu3d_associate_detections), then ``predict_tracks`` on the tracks
     roots.py      absolute root position: ``predict_tracks(..., camera=(fx, fy, cx, cy))`` (uu3d_solve_roots, uu3d_root_trajectory)
-    smooth.py     steady output: ``predict_tracks(..., smooth=OneEuro(min_cutoff, beta, d_cutoff))`` (uu3d_one_euro_tracks)
+    smooth.py     steady output: ``predict_tracks(..., smooth=OneEuro(min_cutoff, beta, d_cutoff))`` (uu3d_one_euro_tracks; ``zero_lag=True``: uu3d_one_euro_tracks_two_pass)
     rotations.py  joint rotations: ``predict_tracks(..., rotations=True)`` (uu3d_joint_rotations; ``bvh.write_bvh``)
     bones.py      constant bone lengths: ``predict_tracks(..., bones="track")`` (uu3d_bone_lengths, uu3d_fix_bones)
     tracks.py     the pose table and the three uu3d_*_tracks launches above; options.py: the checks of all these options, shared with a live
@@ -86,7 +86,8 @@ def predict_detections(model, config, detections, counts=None, valid=None, slots
     ``association_tracks_host``, bit for bit.  Needs a model with strided input.  Greedy, no motion model: no tracking accuracy is claimed.
     ``camera``: one (fx, fy, cx, cy) or one per VIDEO, handed to ``predict_tracks`` per track the way ``resolutions`` is: the tuples become
     (track_id, first_frame, poses, roots (n, 3) float32, root_state (n,) uint8) -- every person of a video in the same camera space.
-    ``smooth``: handed to ``predict_tracks`` as it is -- every track's poses (and roots) filtered from its birth frame on.
+    ``smooth``: handed to ``predict_tracks`` as it is -- every track's poses (and roots) filtered from its birth frame on (a ``OneEuro``
+    with ``zero_lag`` as well: forwards from the birth frame, then back from the track's last frame).
     ``bones``: handed to ``predict_tracks`` as it is -- "track" or one (J,) array of lengths for every person (the tracks are only known
     after the association, so there is no per-track list here).
     ``rotations``: handed to ``predict_tracks`` as it is -- every tuple carries the track's (n, J, 4) quaternions behind what it has
@@ -242,9 +243,14 @@ def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, fl
     one joint (C = 3 J) or of the root (C = 3); the sample rate is that of the RETURNED frames: ``model_fps`` for the plain call and with
     ``keyframes_only``, the track's ``fps`` with ``fps``, ``out_fps`` with ``out_fps``.  The roots are solved from the UNFILTERED poses,
     exactly as without ``smooth``; a root row of state 0 (zeros) is passed through and takes no sample; ``root_state`` and the flags are
-    unchanged, and the root joint of a root-relative pose stays exactly 0.  The filter is CAUSAL: frame i depends on the frames up to i
-    only, so the offline result lags behind the motion exactly as the live one (``StreamSession(smooth=...)``) does.  A zero-lag,
-    two-pass offline smoother is out of scope, and so is any accuracy or jitter figure.
+    unchanged, and the root joint of a root-relative pose stays exactly 0.  A plain ``OneEuro`` is CAUSAL: frame i depends on the frames
+    up to i only, so the result lags behind the motion exactly as the live one (``StreamSession(smooth=...)``) does.
+    ``OneEuro(..., zero_lag=True)`` -- offline only, for either member of the pair independently, at every returned rate -- filters a
+    track in two passes (uu3d_one_euro_tracks_two_pass, still one launch each): pass 1 is the causal walk, pass 2 the same walk over pass
+    1's float32 rows taken last to first, with the same rate, parameters and ``root_state`` bytes and fresh filter state, each pass
+    taking its first usable sample as given; per track the result is reverse(one_euro_host(reverse(one_euro_host(x)))) with the causal
+    filter, bit for bit, which is what ``one_euro_host`` computes for such a filter.  On a ramp the forward and the backward lag are one
+    constant and cancel.  A live session cannot do this and refuses such a filter.  No accuracy or jitter figure is claimed.
 
     Constant bone lengths -- ``bones``: None = today's call, the same bits, no further launch or buffer.  The network predicts every
     frame's skeleton on its own, so a person's bone lengths breathe from frame to frame, and under ``camera`` the depth with them.

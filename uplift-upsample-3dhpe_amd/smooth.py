@@ -6,6 +6,11 @@ Steady output: the root is solved frame by frame and the poses carry the detecto
 smooth=OneEuro(min_cutoff, beta, d_cutoff))`` passes the returned poses and roots through the One-Euro filter on the device
 (uu3d_one_euro_tracks: one lane per track and channel walks the frames in order; ``one_euro`` is the launch alone; the rule in numpy:
 ``one_euro_host``).  The filter is causal, so the result lags as a live session's does; ``predict_detections(..., smooth=...)`` hands it on.
+``OneEuro(..., zero_lag=True)`` is the offline answer to the lag (uu3d_one_euro_tracks_two_pass, still one launch): pass 1 is the causal
+walk, pass 2 the same walk over pass 1's float32 rows taken last to first -- the same rate, parameters and ``state`` bytes, fresh filter
+state, the first usable sample of each pass taken as given -- and the result is, per track and bit for bit,
+reverse(one_euro_host(reverse(one_euro_host(x)))) with the causal filter.  On a ramp the two lags are one constant and cancel.
+``zero_lag`` is OFFLINE ONLY: a session, ``replay_tracks`` / ``replay_detections`` and the live filters below refuse it (``check_causal``).
 
 Steady output -- ``StreamSession(..., smooth=F)``: the root above is solved tick by tick and nothing ties one tick's root to the next, and
 the poses carry the detector's frame-to-frame noise.  ``smooth`` -- True (the defaults), a ``predict.OneEuro(min_cutoff, beta, d_cutoff)``
@@ -41,26 +46,32 @@ TWO_PI = 6.283185307179586
 class OneEuro(object):
     """A One-Euro filter (Casiez, Roussel, Vogel 2012): ``min_cutoff`` > 0 in Hz, the cut-off of a channel at rest; ``beta`` >= 0 in 1 / unit
     speed, how fast the cut-off rises with the channel's speed; ``d_cutoff`` > 0 in Hz, the cut-off of the speed estimate.  Anything else,
-    or a non-finite value, is a ValueError.  The defaults are conveniences for metres and seconds; they are not tuned and claim nothing."""
-    __slots__ = ("min_cutoff", "beta", "d_cutoff")
+    or a non-finite value, is a ValueError.  The defaults are conveniences for metres and seconds; they are not tuned and claim nothing.
+    ``zero_lag`` (keyword only, a bool; OFFLINE only): the track is filtered in two passes, forwards and then backwards over the result, so
+    the two lags cancel (``one_euro_host``); ``tuple(f)`` stays the three numbers, ``==`` and ``hash`` tell the two kinds apart."""
+    __slots__ = ("min_cutoff", "beta", "d_cutoff", "zero_lag")
 
-    def __init__(self, min_cutoff=1.0, beta=0.5, d_cutoff=1.0):
+    def __init__(self, min_cutoff=1.0, beta=0.5, d_cutoff=1.0, *, zero_lag=False):
         try:
             values = tuple(float(v) for v in (min_cutoff, beta, d_cutoff))
         except (TypeError, ValueError):
             raise ValueError(f"OneEuro takes three numbers, got {(min_cutoff, beta, d_cutoff)!r}") from None
         if not all(np.isfinite(values)) or values[0] <= 0 or values[1] < 0 or values[2] <= 0:
             raise ValueError(f"OneEuro needs finite min_cutoff > 0, beta >= 0 and d_cutoff > 0, got {values}")
+        if not isinstance(zero_lag, (bool, np.bool_)):
+            raise ValueError(f"OneEuro's zero_lag must be True or False, got {zero_lag!r}")
         self.min_cutoff, self.beta, self.d_cutoff = values
+        self.zero_lag = bool(zero_lag)
 
     def __repr__(self):
-        return f"OneEuro(min_cutoff={self.min_cutoff!r}, beta={self.beta!r}, d_cutoff={self.d_cutoff!r})"
+        return (f"OneEuro(min_cutoff={self.min_cutoff!r}, beta={self.beta!r}, d_cutoff={self.d_cutoff!r}"
+                + (", zero_lag=True)" if self.zero_lag else ")"))
 
     def __eq__(self, other):
-        return isinstance(other, OneEuro) and tuple(self) == tuple(other)
+        return isinstance(other, OneEuro) and tuple(self) == tuple(other) and self.zero_lag == other.zero_lag
 
     def __hash__(self):
-        return hash(tuple(self))
+        return hash(tuple(self) + (self.zero_lag,))
 
     def __iter__(self):
         return iter((self.min_cutoff, self.beta, self.d_cutoff))
@@ -81,6 +92,15 @@ def check_smooth(smooth, placed):
             raise ValueError("a root filter needs camera=(fx, fy, cx, cy): without it the call returns no roots")
         return smooth[0], smooth[1]
     raise ValueError(f"smooth must be None, True, a OneEuro or a pair (pose_filter, root_filter) of OneEuro / None, got {smooth!r}")
+
+
+def check_causal(*filters):
+    """The filters of a live session or a live filter (each a ``OneEuro`` or None): a ``zero_lag`` one is a ValueError -- its second pass
+    walks a track from its last row back, and a live track has no last row yet."""
+    for f in filters:
+        if isinstance(f, OneEuro) and f.zero_lag:
+            raise ValueError(f"live filtering is causal: {f!r} needs the whole track for its backward pass; filter the finished track "
+                             "offline with predict_tracks(smooth=...) / predict_detections(smooth=...)")
 
 
 def _one_euro_rates(rate, tracks):
@@ -116,7 +136,12 @@ def one_euro_host(x, lens, rate, filt, state=None):
     -> the filtered rows, float32, the shape of ``x``.
     Per channel: the first sample is returned as given; a later one moves xh towards it by ``one_euro_sample``; the output is xh rounded
     once.  A non-finite value is passed through and touches no state.  Rows are walked in a plain loop; the channels of a row are
-    independent, so they go through numpy's element-wise float64 operations side by side."""
+    independent, so they go through numpy's element-wise float64 operations side by side.
+    ``filt.zero_lag`` (uu3d_one_euro_tracks_two_pass): two passes per track.  Pass 1 is the walk above and yields the float32 rows y;
+    pass 2 is the same walk over y with the track's rows taken last to first -- the same rate and parameters, the ``state`` bytes reversed
+    with the rows, xh / dxh / taken fresh -- and its output, put back in row order, is the result: per track
+    reverse(walk(reverse(walk(x)))).  A passed-through row is passed through by both passes; each pass takes its first usable sample as
+    given, so a track's last usable row comes out as pass 1 left it.  On a ramp the two lags are one constant and cancel."""
     X = np.asarray(_host_array(x), np.float32)
     G = int(X.shape[0])
     flat = X.reshape(G, -1)
@@ -127,6 +152,16 @@ def one_euro_host(x, lens, rate, filt, state=None):
     keep = np.ones(G, bool) if state is None else np.asarray(_host_array(state)).reshape(-1) != 0
     if len(keep) != G:
         raise ValueError(f"state must be ({G},)")
+    out = _one_euro_walk(flat, lens, rates, filt, keep)
+    if filt.zero_lag:
+        ends = np.cumsum(lens)
+        back = np.concatenate([np.arange(e - 1, e - n - 1, -1) for n, e in zip(lens.tolist(), ends.tolist())] + [np.zeros(0, np.int64)]).astype(np.int64)
+        out = _one_euro_walk(out[back], lens, rates, filt, keep[back])[back]      # (``back`` reverses every track in place: its own inverse)
+    return out.reshape(X.shape)
+
+
+def _one_euro_walk(flat, lens, rates, filt, keep):
+    """One causal pass of ``one_euro_host``: ``flat`` (G, C) float32, ``keep`` (G,) bool -> (G, C) float32, a fresh array."""
     out = flat.copy()
     first = 0
     with np.errstate(all="ignore"):
@@ -147,14 +182,15 @@ def one_euro_host(x, lens, rate, filt, state=None):
                 taken |= ok
                 out[i] = np.where(ok, xh.astype(np.float32), flat[i])
             first += n
-    return out.reshape(X.shape)
+    return out
 
 
 def one_euro(x, lens, rate, filt, state=None):
     """uu3d_one_euro_tracks on the current stream: ``one_euro_host`` on a device tensor, one launch, nothing copies to the host or waits
     (the per-track plan -- first row, length, rate -- is made on the host and goes up pinned and asynchronously).  ``x``: a contiguous
     (G, ...) float32 device tensor, only read; ``state``: None or a contiguous (G,) uint8 / bool device tensor
-    -> the filtered rows, a fresh device tensor of ``x``'s shape.  One lane per (track, channel) walks the track's rows in order."""
+    -> the filtered rows, a fresh device tensor of ``x``'s shape.  One lane per (track, channel) walks the track's rows in order.  A
+    ``filt`` with ``zero_lag`` is uu3d_one_euro_tracks_two_pass: still one launch, the same lane walks back over the rows it wrote."""
     import torch
     lib = _capi.load_library()
     if not isinstance(x, torch.Tensor) or x.dim() < 1 or x.dtype != torch.float32 or not x.is_contiguous() or not x.is_cuda:
@@ -179,8 +215,9 @@ def one_euro(x, lens, rate, filt, state=None):
     d_rates = _upload(rates, np.float64, dev)
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
-        _capi.check(lib, lib.uu3d_one_euro_tracks(_ptr(x), _ptr(out), G, Cn, _ptr(plan[0]), _ptr(plan[1]), _ptr(d_rates), len(lens), _ptr(state),
-                                                  filt.min_cutoff, filt.beta, filt.d_cutoff, C.c_void_p(stream)), None)
+        launch = lib.uu3d_one_euro_tracks_two_pass if filt.zero_lag else lib.uu3d_one_euro_tracks
+        _capi.check(lib, launch(_ptr(x), _ptr(out), G, Cn, _ptr(plan[0]), _ptr(plan[1]), _ptr(d_rates), len(lens), _ptr(state),
+                                filt.min_cutoff, filt.beta, filt.d_cutoff, C.c_void_p(stream)), None)
     return out
 
 
@@ -190,6 +227,7 @@ def _live_filter_arguments(slots, channels, rate, filt, lookahead):
         raise ValueError(f"slots >= 1, channels in [1, {MAX_SMOOTH_CHANNELS}] and lookahead >= 0, got {slots}, {channels}, {lookahead}")
     if not isinstance(filt, OneEuro):
         raise ValueError(f"filt must be a predict.OneEuro, got {filt!r}")
+    check_causal(filt)
     return slots, channels, float(frame_rate(rate)), filt, lookahead
 
 

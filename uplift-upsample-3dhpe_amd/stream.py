@@ -232,6 +232,8 @@ class StreamSession(object):
         bit).  True, a ``predict.OneEuro`` or a pair (pose_filter, root_filter), either of which may be None (``predict.check_smooth``; a
         root filter without ``camera``: ValueError): the module docstring's "Steady output" -- ``push`` / ``push_detections`` return the
         filtered buffers in place of poses and roots; ``raw_poses`` / ``raw_roots`` are the unfiltered ones.  With ``out_fps``: ValueError.
+        A ``OneEuro(zero_lag=True)`` in either place: ValueError -- live filtering is causal, the two-pass form needs the whole track
+        (``predict.predict_tracks(smooth=...)``).
         ``bones`` (keyword only, from ``options`` as well): None = the poses as the network gives them (the session above, bit for bit).
         "track", a (J,) array of lengths by child joint, a list of such arrays, one per slot, or a ``predict.Bones``: the module
         docstring's "Live constant bone lengths" -- ``push`` returns the rebuilt poses, ``raw_poses`` stays the model's output and
