@@ -251,6 +251,18 @@ int uu3d_gather_windows(const float* poses_dev, const int64_t* video_start_dev, 
  *   operation rounded, stored as float32 -- evaluation.interpolate_between_keyframes on float32 predictions bit for bit.  root_index >= 0:
  *   that joint of the frame is subtracted in float32 afterwards (it comes out exactly 0); -1: absolute predictions.  A plan row outside
  *   [0, num_windows) yields NaN.
+ *
+ *   uu3d_assemble_tracks_cubic (predict_tracks(interpolation="cubic")): the same launch with a C1 cubic between the predicted frames in
+ *   place of the line -- the plan of evaluation.keyframe_plan_cubic: before_dev / after_dev (num_frames) i32 name the predicted frame in front
+ *   of left and the one behind right, in the same track, or -1 where there is none (and wherever left == right).  pred[left] where
+ *   left == right: the bits of uu3d_assemble_tracks.  Else, with P0..P3 = pred[before], pred[left], pred[right], pred[after] and t = weight,
+ *   all in float64 with every operation rounded and no fused multiply-add, in this order:
+ *     m1 = (P2 - P0) * 0.5 (before == -1: P2 - P1);  m2 = (P3 - P1) * 0.5 (after == -1: P2 - P1);  t2 = t * t;  t3 = t2 * t;
+ *     h01 = 3.0 * t2 - 2.0 * t3;  h00 = 1.0 - h01;  h11 = t3 - t2;  h10 = (h11 - t2) + t;
+ *     value = ((h00 * P1 + h01 * P2) + h10 * m1) + h11 * m2, stored as float32
+ *   -- the Hermite segment with Catmull-Rom tangents over equally spaced predicted frames; evaluation.interpolate_cubic_host bit for bit.
+ *   The un-flip, the average and root_index are those of uu3d_assemble_tracks.  left or right outside [0, num_windows), or before / after
+ *   outside [-1, num_windows) where left != right, yields NaN, never a read out of bounds.  Argument checks as uu3d_assemble_tracks.
  */
 int uu3d_normalize_tracks(const float* src_dev, int64_t src_rows, float* table_dev, int64_t rows, int32_t num_keypoints,
                           const int32_t* row_track_dev, int32_t num_tracks, const double* resolution_dev,
@@ -258,6 +270,10 @@ int uu3d_normalize_tracks(const float* src_dev, int64_t src_rows, float* table_d
 int uu3d_assemble_tracks(const float* plain_dev, const float* flipped_dev, int64_t num_windows, const int32_t* flip_order_dev,
                          const int32_t* left_dev, const int32_t* right_dev, const double* weight_dev, int64_t num_frames,
                          int32_t num_keypoints, int32_t root_index, float* out_dev, void* stream);
+int uu3d_assemble_tracks_cubic(const float* plain_dev, const float* flipped_dev, int64_t num_windows, const int32_t* flip_order_dev,
+                               const int32_t* before_dev, const int32_t* left_dev, const int32_t* right_dev, const int32_t* after_dev,
+                               const double* weight_dev, int64_t num_frames, int32_t num_keypoints, int32_t root_index, float* out_dev,
+                               void* stream);
 
 /*
  * World -> camera coordinates -> 2D projection with the Human3.6M camera model, one camera per window: replaces

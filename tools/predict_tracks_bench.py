@@ -29,9 +29,13 @@ predict.fix_bones_host with predict.bone_lengths_host on the result without bone
 --rotations: also predict_tracks(rotations=True) next to the plain call in the same process: rotations_extra_ms is the difference of the two
 medians (one more launch), host_rotations_ms the plain call followed by .cpu() of the poses and the numpy rule
 (predict.joint_rotations_host); the quaternions must equal that rule on the returned poses bit for bit.  Informational: no threshold.
+--interpolation cubic: also predict_tracks(interpolation="cubic") next to the plain (linear) call on the same tracks in the same process:
+cubic_extra_ms is the difference of the two medians (uu3d_assemble_tracks_cubic in place of uu3d_assemble_tracks: four predictions read per
+interpolated value in place of two); every predicted frame must carry the linear call's bits (cubic_keyframe_bits_equal) and the frames between
+must not (cubic_max_abs_diff_to_linear).  Informational: no threshold.
    python tools/predict_tracks_bench.py [--tracks 40] [--frames 2500] [--batch 512] [--reps 3] [--cases h36m_351:5,h36m_81:4] [--missing 0.3]
                                         [--fps 30] [--repair_joints 5 --missing_joints 0.1] [--keypoints coco17]
-                                        [--camera 1145 1145 960 540] [--smooth [--zero_lag]] [--bones] [--rotations]"""
+                                        [--camera 1145 1145 960 540] [--smooth [--zero_lag]] [--bones] [--rotations] [--interpolation cubic]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -55,6 +59,8 @@ def main():
     ap.add_argument("--zero_lag", action="store_true", help="with --smooth: also time predict_tracks(smooth=OneEuro(zero_lag=True)) beside the causal call")
     ap.add_argument("--bones", action="store_true", help='also time predict_tracks(bones="track") (with --camera: with the camera) against the same call without')
     ap.add_argument("--rotations", action="store_true", help="also time predict_tracks(rotations=True) against the plain call and against .cpu() and the numpy rule")
+    ap.add_argument("--interpolation", choices=["linear", "cubic"], default="linear",
+                    help='cubic: also time predict_tracks(interpolation="cubic") beside the plain (linear) call')
     args = ap.parse_args()
     if args.zero_lag and not args.smooth:
         ap.error("--zero_lag is used together with --smooth")
@@ -180,6 +186,10 @@ def main():
         def rotations_host():
             return predict.joint_rotations_host(torch.cat(new_path(), 0).cpu().numpy())[0]
 
+        def cubic_path():
+            return predict.predict_tracks(model, cfg, px, resolutions=(W, H), mask_stride=int(msv), flip=True, reuse_frames=reuse, batch_size=args.batch,
+                                          interpolation="cubic")
+
         row = dict(config=name, mask_stride=int(msv), tracks=args.tracks, frames=total, batch=args.batch, reuse_frames=reuse)
         outs = {}
         cases = [("predict_tracks", new_path), ("predict_tracks_to_host", lambda: new_path(True)), ("composition", composition)]
@@ -206,6 +216,8 @@ def main():
             cases.append(("predict_tracks_bones", bones_path))
         if args.rotations:
             cases += [("predict_tracks_rotations", rotations_path), ("host_rotations", rotations_host)]
+        if args.interpolation == "cubic":
+            cases.append(("predict_tracks_cubic", cubic_path))
         for key, fn in cases:
             fn()
             torch.cuda.synchronize()
@@ -270,6 +282,13 @@ def main():
             row["rotations_extra_ms"] = round(row["predict_tracks_rotations_ms"] - row["predict_tracks_ms"], 1)
             got = torch.cat(outs["predict_tracks_rotations"][1], 0).cpu().numpy()
             row["rotations_bits_equal"] = bool(np.array_equal(got.view(np.uint32), outs["host_rotations"].view(np.uint32)))
+        if args.interpolation == "cubic":
+            row["cubic_extra_ms"] = round(row["predict_tracks_cubic_ms"] - row["predict_tracks_ms"], 1)
+            stride = ev.prediction_stride(cfg)
+            keys = torch.arange(args.frames, device=model.device) % (stride or 1) == 0
+            row["cubic_keyframe_bits_equal"] = bool(all(torch.equal(a[keys].view(torch.int32), b[keys].view(torch.int32))
+                                                        for a, b in zip(outs["predict_tracks_cubic"], outs["predict_tracks"])))
+            row["cubic_max_abs_diff_to_linear"] = float(max((a - b).abs().max() for a, b in zip(outs["predict_tracks_cubic"], outs["predict_tracks"])))
         row["device"] = torch.cuda.get_device_name(0)
         print(json.dumps(row), flush=True)
         results.append(row)

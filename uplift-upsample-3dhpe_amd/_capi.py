@@ -50,6 +50,7 @@ EXPORTED_SYMBOLS = (
     "uu3d_stream_drain_reset",
     "uu3d_bone_lengths", "uu3d_fix_bones", "uu3d_stream_bones_bytes", "uu3d_stream_bones", "uu3d_stream_bones_reset",
     "uu3d_joint_rotations", "uu3d_joint_rotations_reset",
+    "uu3d_assemble_tracks_cubic",
 )
 # include/uu3d_ops.h
 OPS_SYMBOLS = (
@@ -220,6 +221,8 @@ def load_library(path=None):
     lib.uu3d_normalize_tracks.argtypes = [vp, i64, vp, i64, i32, vp, i32, vp, vp, vp, i32, vp]
     lib.uu3d_assemble_tracks.restype = C.c_int
     lib.uu3d_assemble_tracks.argtypes = [vp, vp, i64, vp, vp, vp, vp, i64, i32, i32, vp, vp]
+    lib.uu3d_assemble_tracks_cubic.restype = C.c_int
+    lib.uu3d_assemble_tracks_cubic.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp, i64, i32, i32, vp, vp]
     lib.uu3d_frame_features_bytes.restype = sz
     lib.uu3d_frame_features_bytes.argtypes = [vp, i32]
     lib.uu3d_frame_features.restype = C.c_int

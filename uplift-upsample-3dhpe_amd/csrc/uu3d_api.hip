@@ -753,6 +753,20 @@ int uu3d_assemble_tracks(const float* plain, const float* flipped, int64_t num_w
     return hipGetLastError() == hipSuccess ? UU3D_OK : UU3D_ERR_HIP;
 }
 
+int uu3d_assemble_tracks_cubic(const float* plain, const float* flipped, int64_t num_windows, const int32_t* flip_order, const int32_t* before,
+                               const int32_t* left, const int32_t* right, const int32_t* after, const double* weight, int64_t num_frames, int32_t J,
+                               int32_t root_index, float* out, void* stream) {
+    if (!plain || !before || !left || !right || !after || !weight || !out || num_windows < 1 || num_frames < 1 || J < 1 || root_index >= J)
+        return UU3D_ERR_INVALID_ARGUMENT;
+    if (flipped != nullptr && !flip_order) return UU3D_ERR_INVALID_ARGUMENT;
+    if (((uintptr_t)out & 15) != 0) return UU3D_ERR_INVALID_ARGUMENT;
+    const long threads = ((long)num_frames * J * 3 + 3) / 4;
+    hipLaunchKernelGGL(assemble_tracks_cubic_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       plain, flipped, (long)num_windows, flip_order, before, left, right, after, weight, (long)num_frames, J,
+                       root_index < 0 ? -1 : root_index, out);
+    return hipGetLastError() == hipSuccess ? UU3D_OK : UU3D_ERR_HIP;
+}
+
 #include "uu3d_stream_api.inc"
 #include "uu3d_stream_drain_api.inc"
 #include "uu3d_smooth_api.inc"

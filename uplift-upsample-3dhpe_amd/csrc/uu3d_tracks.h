@@ -1,6 +1,7 @@
 // uu3d_tracks.h -- the front and the back of predict.predict_tracks (include/uu3d.h, "YOUR OWN 2D TRACKS"): pixel coordinates of the
 // caller's keypoint tracks -> the pose table the window gather reads, and the central predictions of the forwarded windows -> one 3D pose
-// per frame of every track; resample_tracks_kernel is the front for tracks at another frame rate.  All three: one launch for all tracks of
+// per frame of every track; resample_tracks_kernel is the front for tracks at another frame rate, assemble_tracks_cubic_kernel the back with
+// a C1 cubic between the predicted frames in place of the line.  All four: one launch for all tracks of
 // a call, one thread per 16 bytes of the flattened output, every output element written by exactly one thread from inputs nobody writes
 // (bitwise repeatable; the in-place form of the first kernel reads only what the same thread overwrites).
 #pragma once
@@ -227,6 +228,70 @@ assemble_tracks_kernel(const float* __restrict__ plain, const float* __restrict_
         const double w = weight[f];
         v[k] = frame_value(plain, flipped, order, num_windows, l, rr, w, J, j, c);
         if (root >= 0) v[k] = v[k] - frame_value(plain, flipped, order, num_windows, l, rr, w, J, root, c);
+    }
+    if (e0 + 4 <= total) *reinterpret_cast<float4*>(out + e0) = make_float4(v[0], v[1], v[2], v[3]);
+    else for (int k = 0; e0 + k < total; ++k) out[e0 + k] = v[k];
+}
+
+// C1 MOTION BETWEEN KEYFRAMES (predict_tracks(interpolation="cubic")): the cubic Hermite segment from p1 (weight 0) to p2 (weight 1) with
+// Catmull-Rom tangents over equally spaced keyframes -- half the difference of the two neighbours, or the segment's own difference
+// where the outer keyframe p0 / p3 does not exist.  All in float64 on the float32 predictions, every operation rounded (no fused
+// multiply-add), in the order of evaluation.interpolate_cubic_host, rounded once to float32: a numpy restatement gives the same bits.
+__device__ __forceinline__ float hermite_mix(const float p0, const float p1, const float p2, const float p3, const bool has0, const bool has3,
+                                             const double t)
+{
+#pragma clang fp contract(off)
+    const double P1 = (double)p1, P2 = (double)p2;
+    const double m1 = has0 ? (P2 - (double)p0) * 0.5 : P2 - P1;
+    const double m2 = has3 ? ((double)p3 - P1) * 0.5 : P2 - P1;
+    const double t2 = t * t;
+    const double t3 = t2 * t;
+    const double h01 = 3.0 * t2 - 2.0 * t3;
+    const double h00 = 1.0 - h01;
+    const double h11 = t3 - t2;
+    const double h10 = (h11 - t2) + t;
+    return (float)(((h00 * P1 + h01 * P2) + h10 * m1) + h11 * m2);
+}
+
+// Coordinate c of joint j of frame f by the plan of evaluation.keyframe_plan_cubic: the prediction of window l where l == r (frame_value's
+// own bits; b and a are not looked at), else hermite_mix of the windows b, l, r, a -- b / a == -1: no such keyframe.  l or r outside
+// [0, num_windows), or b / a outside [-1, num_windows) where they count, gives NaN; nothing is read then.
+__device__ __forceinline__ float frame_value_cubic(const float* __restrict__ plain, const float* __restrict__ flipped, const int32_t* __restrict__ order,
+                                                   const long num_windows, const long b, const long l, const long r, const long a, const double w,
+                                                   const int J, const int j, const int c)
+{
+    if (l < 0 || l >= num_windows || r < 0 || r >= num_windows) return __builtin_nanf("");
+    const float p1 = window_prediction(plain, flipped, order, l, J, j, c);
+    if (l == r) return p1;
+    if (b < -1 || b >= num_windows || a < -1 || a >= num_windows) return __builtin_nanf("");
+    const float p2 = window_prediction(plain, flipped, order, r, J, j, c);
+    const float p0 = (b >= 0) ? window_prediction(plain, flipped, order, b, J, j, c) : p1;
+    const float p3 = (a >= 0) ? window_prediction(plain, flipped, order, a, J, j, c) : p2;
+    return hermite_mix(p0, p1, p2, p3, b >= 0, a >= 0, w);
+}
+
+// assemble_tracks_kernel with the cubic rule: out (frames, J, 3), flattened, one thread per four consecutive floats; before / left /
+// right / after (frames) i32, weight (frames) f64.  root >= 0: the frame's root joint -- its own interpolated float32 value -- is subtracted
+// in float32 (that joint comes out exactly 0).
+static __global__ void __launch_bounds__(256)
+assemble_tracks_cubic_kernel(const float* __restrict__ plain, const float* __restrict__ flipped, const long num_windows,
+                             const int32_t* __restrict__ order, const int32_t* __restrict__ before, const int32_t* __restrict__ left,
+                             const int32_t* __restrict__ right, const int32_t* __restrict__ after, const double* __restrict__ weight,
+                             const long frames, const int J, const int root, float* __restrict__ out)
+{
+    const long per = (long)J * 3, total = frames * per;
+    const long e0 = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (e0 >= total) return;
+    float v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const long e = (e0 + k < total) ? e0 + k : e0;
+        const long f = e / per;
+        const int r = (int)(e - f * per), j = r / 3, c = r - j * 3;
+        const long b = before[f], l = left[f], rr = right[f], a = after[f];
+        const double w = weight[f];
+        v[k] = frame_value_cubic(plain, flipped, order, num_windows, b, l, rr, a, w, J, j, c);
+        if (root >= 0) v[k] = v[k] - frame_value_cubic(plain, flipped, order, num_windows, b, l, rr, a, w, J, root, c);
     }
     if (e0 + 4 <= total) *reinterpret_cast<float4*>(out + e0) = make_float4(v[0], v[1], v[2], v[3]);
     else for (int k = 0; e0 + k < total; ++k) out[e0 + k] = v[k];

@@ -225,6 +225,106 @@ def keyframe_plan_at(frame_indices, keyframe_stride, positions, rows=None):
     return left, right, weight
 
 
+def _outer_keyframes(frame_indices, keyframe_stride, left, right, rows, where):
+    """What the cubic plans add to the linear ones.  ``left`` / ``right``: a linear plan as PLACES in ``frame_indices`` -> (before, after):
+    per entry with ``left != right`` the keyframe in front of ``left`` and the one behind ``right`` in the same video, -1 where the video
+    has none; -1 wherever ``left == right``.  With ``rows`` they are returned as rows, as ``keyframe_plan`` returns left and right.
+    ``where(i)`` names entry i in an error message."""
+    f = np.asarray(frame_indices).astype(np.int64)
+    n = len(f)
+    pos = np.arange(n, dtype=np.int64)
+    key = np.equal(np.mod(f, keyframe_stride), 0)
+    new = np.ones(n, bool)
+    new[1:] = f[1:] <= f[:-1]                                        # a drop (or repeat) of the frame index starts a new video
+    video = np.cumsum(new) - 1
+    last = np.maximum.accumulate(np.where(key, pos, -1)) if n else pos
+    nxt = np.minimum.accumulate(np.where(key, pos, n)[::-1])[::-1] if n else pos
+    in_front = np.concatenate([[-1], last[:-1]]).astype(np.int64)    # the last keyframe strictly in front of a place (-1: none)
+    behind = np.concatenate([nxt[1:], [n]]).astype(np.int64)         # the first keyframe strictly behind a place (n: none)
+    mixed = np.flatnonzero(left != right)
+    L, N = left[mixed], right[mixed]
+    b, a = in_front[L], behind[N]
+    b = np.where((b >= 0) & (video[np.maximum(b, 0)] == video[L]), b, -1)
+    a = np.where((a < n) & (video[np.minimum(a, n - 1)] == video[N]), a, -1)
+    uneven = np.flatnonzero(((b >= 0) & (L - b != N - L)) | ((a >= 0) & (a - N != N - L)))
+    if len(uneven):
+        u = uneven[0]
+        raise ValueError(f"the cubic rule needs equally spaced keyframes: around {where(int(mixed[u]))} they lie at places "
+                         f"{[int(x) for x in (b[u], L[u], N[u], a[u]) if x >= 0]}")
+    if rows is not None:
+        rows = np.asarray(rows).astype(np.int64)
+        has_b, has_a = b >= 0, a >= 0
+        b, a = np.where(has_b, rows[np.maximum(b, 0)], -1), np.where(has_a, rows[np.maximum(a, 0)], -1)
+        missing = np.flatnonzero((has_b & (b < 0)) | (has_a & (a < 0)))
+        if len(missing):
+            raise ValueError(f"{len(missing)} positions need a prediction that was not forwarded (first: {where(int(mixed[missing[0]]))})")
+    before, after = np.full(len(left), -1, np.int64), np.full(len(left), -1, np.int64)
+    before[mixed], after[mixed] = b, a
+    return before, after
+
+
+def keyframe_plan_cubic(frame_indices, keyframe_stride, rows=None):
+    """``keyframe_plan`` for the C1 cubic through the keyframes (``interpolate_cubic_host``) -> (before, left, right, after, weight).
+    ``left`` / ``right`` / ``weight`` are ``keyframe_plan``'s own; ``before`` / ``after``: the keyframe in front of ``left`` and the one
+    behind ``right`` in the same video, -1 where there is none and wherever ``left == right``.  The rule takes the four keyframes as
+    equally spaced in positions: ValueError where they are not.  ``rows`` as in ``keyframe_plan``, for all four."""
+    left, right, weight, _ = keyframe_plan(frame_indices, keyframe_stride, rows=rows)
+    pl, pr = (left, right) if rows is None else keyframe_plan(frame_indices, keyframe_stride)[:2]
+    f = np.asarray(frame_indices)
+    before, after = _outer_keyframes(f, keyframe_stride, pl, pr, rows, lambda i: f"position {i}, frame {int(f[i])}")
+    return before, left, right, after, weight
+
+
+def keyframe_plan_cubic_at(frame_indices, keyframe_stride, positions, rows=None):
+    """``keyframe_plan_at`` for the C1 cubic through the keyframes -> (before, left, right, after, weight), one entry per position:
+    ``left`` / ``right`` / ``weight`` are ``keyframe_plan_at``'s own, ``before`` / ``after`` as in ``keyframe_plan_cubic``."""
+    left, right, weight = keyframe_plan_at(frame_indices, keyframe_stride, positions, rows=rows)
+    pl, pr = (left, right) if rows is None else keyframe_plan_at(frame_indices, keyframe_stride, positions)[:2]
+    video, num, den = (np.asarray(a).astype(np.int64).reshape(-1) for a in positions)
+    before, after = _outer_keyframes(frame_indices, keyframe_stride, pl, pr, rows,
+                                     lambda i: f"position {int(num[i])}/{int(den[i])} of video {int(video[i])}")
+    return before, left, right, after, weight
+
+
+def interpolate_cubic_host(pred3d, plan):
+    """The C1 motion through the keyframes, in numpy: ``pred3d`` (W, ...) float32 predictions, ``plan`` = (before, left, right, after,
+    weight) of ``keyframe_plan_cubic`` / ``keyframe_plan_cubic_at`` as rows of ``pred3d`` -> (F, ...) float32.
+
+    Where ``left == right`` the value is that prediction, its own bits (a keyframe, a frame behind the last keyframe of its video, one in
+    front of the first).  Else it lies on the cubic Hermite segment from P1 = pred[left] (t = 0) to P2 = pred[right] (t = 1), t = weight,
+    whose tangents are Catmull-Rom's over equally spaced keyframes: half the difference of the two neighbours, with P0 = pred[before]
+    and P3 = pred[after], or the segment's own difference where before / after is -1.  Consecutive segments share the tangent at
+    their common keyframe, so the motion has a continuous velocity; a quadratic in time is reproduced where all four keyframes exist.
+    All in float64 on the float32 predictions, every operation rounded on its own, in exactly this order, rounded once to float32 --
+    uu3d_assemble_tracks_cubic computes the same bits.  A row outside the predictions gives NaN (before / after: other than -1)."""
+    pred = np.asarray(pred3d)
+    if pred.dtype != np.float32:
+        raise ValueError("interpolate_cubic_host takes float32 predictions")
+    before, left, right, after = (np.asarray(a).astype(np.int64) for a in plan[:4])
+    weight = np.asarray(plan[4], np.float64)
+    W = len(pred)
+    out = np.full((len(left),) + pred.shape[1:], np.nan, np.float32)
+    inside = (left >= 0) & (left < W) & (right >= 0) & (right < W)
+    own = inside & (left == right)
+    out[own] = pred[left[own]]
+    mix = np.flatnonzero(inside & (left != right) & (before >= -1) & (before < W) & (after >= -1) & (after < W))
+    each = (-1,) + (1,) * (pred.ndim - 1)                              # one value per frame, for all of its joints and coordinates
+    has0, has3 = (before[mix] >= 0).reshape(each), (after[mix] >= 0).reshape(each)
+    t = weight[mix].reshape(each)
+    P0, P1 = pred[np.maximum(before[mix], 0)].astype(np.float64), pred[left[mix]].astype(np.float64)
+    P2, P3 = pred[right[mix]].astype(np.float64), pred[np.maximum(after[mix], 0)].astype(np.float64)
+    m1 = np.where(has0, (P2 - P0) * 0.5, P2 - P1)
+    m2 = np.where(has3, (P3 - P1) * 0.5, P2 - P1)
+    t2 = t * t
+    t3 = t2 * t
+    h01 = 3.0 * t2 - 2.0 * t3
+    h00 = 1.0 - h01
+    h11 = t3 - t2
+    h10 = (h11 - t2) + t
+    out[mix] = ((h00 * P1 + h01 * P2) + h10 * m1) + h11 * m2
+    return out
+
+
 def report_from_sums(sums, action_wise=True, action_set=None):
     """The report of ``h36_action_wise_eval`` / ``frame_wise_eval`` from a table ``sums[a, m] = (sum of the errors >= 0 in metres, their
     count)`` with the actions of ``action_set`` in rows 0 .. A-1 and all poses in the last row (uu3d_pose_errors / uu3d_error_sums):

@@ -13,19 +13,29 @@ from .validity import check_repair_joints
 
 # cameras: (count, 4) float64 or None; min_root_joints: the checked int (a session without a camera: None); pose_filter / root_filter: a
 # ``OneEuro`` or None each; rigid: None or (skeleton, (count, J) lengths or None for "track"); keypoints: a ``KeypointMap`` or None;
-# rotations: a ``Rotations`` or None
-StageOptions = collections.namedtuple("StageOptions", "cameras min_root_joints pose_filter root_filter rigid keypoints rotations")
+# rotations: a ``Rotations`` or None; interpolation: "linear" or "cubic" (a session is always "linear": live sessions have no such option)
+StageOptions = collections.namedtuple("StageOptions", "cameras min_root_joints pose_filter root_filter rigid keypoints rotations interpolation")
+INTERPOLATIONS = ("linear", "cubic")
 
 OUT_FPS_NEEDS_FPS = {"track": "out_fps needs fps: the rate the tracks were filmed at", "slot": "out_fps needs fps: the rate of the pushed frames"}
 
 
+def check_interpolation(interpolation):
+    """``predict_tracks(interpolation=...)``: how a returned frame between two predicted ones is read -> the checked name."""
+    if not isinstance(interpolation, str) or interpolation not in INTERPOLATIONS:
+        raise ValueError(f"interpolation must be one of {', '.join(repr(n) for n in INTERPOLATIONS)}, got {interpolation!r}")
+    return interpolation
+
+
 def stage_options(config, count, per, root_relative, keypoints, camera, min_root_joints, smooth, bones, repair_joints, fps, out_fps,
-                  rotations=None):
+                  interpolation="linear", rotations=None):
     """``count`` tracks (``per="track"``) or slots (``per="slot"``) of a model of ``config``; the other arguments as ``predict_tracks`` and
     ``StreamSession`` take them -> a ``StageOptions``.  Every refusal is a ValueError in the words of the stage's own check.
     ``min_root_joints``: a session passes None for "not given" -- the default with a camera, and anything else without one is refused (it
     is a parameter of the root solve); the offline call has the default in its signature and passes what it got.
-    ``repair_joints`` is checked for its type only: whether it has the ``valid`` it needs is the caller's to say."""
+    ``repair_joints`` is checked for its type only: whether it has the ``valid`` it needs is the caller's to say.
+    ``interpolation``: offline only (``check_interpolation``); a session does not pass it."""
+    interpolation = check_interpolation(interpolation)
     pose_filter, root_filter = check_smooth(smooth, camera is not None)
     if per == "slot":
         check_causal(pose_filter, root_filter)                       # (a zero-lag filter needs the whole track: offline only)
@@ -43,4 +53,5 @@ def stage_options(config, count, per, root_relative, keypoints, camera, min_root
     if fps is None and out_fps is not None:
         raise ValueError(OUT_FPS_NEEDS_FPS[per])
     check_repair_joints(repair_joints, "finite")
-    return StageOptions(cameras, min_root_joints, pose_filter, root_filter, rigid, keypoints, check_rotations(rotations, config.NUM_KEYPOINTS))
+    return StageOptions(cameras, min_root_joints, pose_filter, root_filter, rigid, keypoints, check_rotations(rotations, config.NUM_KEYPOINTS),
+                        interpolation)

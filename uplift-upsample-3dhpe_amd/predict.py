@@ -36,7 +36,8 @@ every name is importable from here as before:
     smooth.py     steady output: ``predict_tracks(..., smooth=OneEuro(min_cutoff, beta, d_cutoff))`` (uu3d_one_euro_tracks; ``zero_lag=True``: uu3d_one_euro_tracks_two_pass)
     rotations.py  joint rotations: ``predict_tracks(..., rotations=True)`` (uu3d_joint_rotations; ``bvh.write_bvh``)
     bones.py      constant bone lengths: ``predict_tracks(..., bones="track")`` (uu3d_bone_lengths, uu3d_fix_bones)
-    tracks.py     the pose table and the three uu3d_*_tracks launches above; options.py: the checks of all these options, shared with a live
+    tracks.py     the pose table and the three uu3d_*_tracks launches above, and uu3d_assemble_tracks_cubic: C1 motion between the predicted
+                  frames, ``predict_tracks(..., interpolation="cubic")`` (``evaluation.keyframe_plan_cubic``, ``interpolate_cubic_host``); options.py: the checks of all these options, shared with a live
                   session; cli.py: the command-line options, shared with ``stream``
 """
 import argparse
@@ -56,7 +57,7 @@ from .cli import add_track_options, bones_option, input_joints, smooth_option, s
 from .data import PoseTable, SequenceGenerator  # noqa: F401
 from .keypoints import (KEYPOINT_PRESETS, MAX_KEYPOINT_SOURCES, KeypointMap, _h36m17_from, _map_front, check_keypoint_inputs,  # noqa: F401
                         keypoint_map, map_keypoints, map_keypoints_host)
-from .options import stage_options
+from .options import INTERPOLATIONS, check_interpolation, stage_options  # noqa: F401
 from .rates import (_rate_argument, default_mask_stride, frame_rate, frame_rates, given_positions, output_positions,  # noqa: F401
                     resample_plan, root_plan)
 from .rotations import (REST_POSES, Rotations, check_rotations, forward_kinematics, joint_rotations, joint_rotations_host,  # noqa: F401
@@ -65,8 +66,8 @@ from .roots import (DEFAULT_MIN_ROOT_JOINTS, MAX_ROOT_JOINTS, _root_lens, check_
                     root_trajectory, root_trajectory_host, solve_roots, solve_roots_host)
 from .smooth import (MAX_SMOOTH_CHANNELS, TWO_PI, OneEuro, _one_euro_rates, check_smooth, one_euro, one_euro_alpha, one_euro_host,  # noqa: F401
                      one_euro_sample)
-from .tracks import (_device_track, _device_tracks, _host_array, _shape, _upload, assemble_tracks, check_resolutions, keyframe_count,  # noqa: F401
-                     normalize_tracks, pose_table, resample_tracks, resampled_pose_table)
+from .tracks import (_device_track, _device_tracks, _host_array, _shape, _upload, assemble_tracks, assemble_tracks_cubic,  # noqa: F401
+                     check_resolutions, keyframe_count, normalize_tracks, pose_table, resample_tracks, resampled_pose_table)
 from .validity import (_device_joint_flags, _device_valid, _front_validity, _source_joint_flags, check_repair_joints, check_valid,  # noqa: F401
                        repair_joints, repair_joints_host)
 
@@ -91,9 +92,12 @@ def predict_detections(model, config, detections, counts=None, valid=None, slots
     ``bones``: handed to ``predict_tracks`` as it is -- "track" or one (J,) array of lengths for every person (the tracks are only known
     after the association, so there is no per-track list here).
     ``rotations``: handed to ``predict_tracks`` as it is -- every tuple carries the track's (n, J, 4) quaternions behind what it has
-    otherwise (and, with ``return_global``, the global ones behind those)."""
+    otherwise (and, with ``return_global``, the global ones behind those).
+    ``interpolation``: "linear" (the default) or "cubic", handed to ``predict_tracks`` as it is; anything else is refused here, before the
+    association runs."""
     import torch
     assoc, options = _association_options(options)
+    check_interpolation(options.get("interpolation", "linear"))
     camera = options.pop("camera", None)
     if camera is not None:
         camera = check_cameras(camera, len(detections), per="video")
@@ -144,7 +148,7 @@ def predict_detections(model, config, detections, counts=None, valid=None, slots
 def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, flip=None, keyframes_only=False, reuse_frames=True,
                    batch_size=None, root_relative=True, depth=None, lengths=None, graph=True, valid=None, return_valid=False, fps=None, out_fps=None,
                    model_fps=50, repair_joints=None, keypoints=None, camera=None, min_root_joints=DEFAULT_MIN_ROOT_JOINTS, smooth=None,
-                   bones=None, rotations=None):
+                   bones=None, rotations=None, interpolation="linear"):
     """One 3D pose per frame for each 2D keypoint track -> list of (T_i, J, 3) float32 tensors on the model's device (views of one buffer).
 
     ``tracks``: list of (T_i, J, 2) arrays or tensors, on the host or the device, at the frame rate the config was trained for (nothing is
@@ -274,11 +278,26 @@ def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, fl
     frame times) in one launch over all tracks' rows (uu3d_joint_rotations; ``joint_rotations`` is the launch alone; the rule in numpy:
     ``joint_rotations_host``, and the result equals it on the returned poses bit for bit).  A model whose joint count is not the
     skeleton's: ValueError.  Positions do not show the twist about a bone with a single child: it is zero relative to the parent.  No
-    accuracy figure is claimed (``rotations.py``)."""
+    accuracy figure is claimed (``rotations.py``).
+
+    C1 motion between keyframes -- ``interpolation``: "linear" = today's call, the same launches, buffers and bits: a returned frame
+    between two predicted ones lies on the line through them (the evaluation's protocol), so the velocity jumps at every predicted frame.
+    "cubic": it lies on the C1 cubic through the same predictions instead -- the Hermite segment between the two with Catmull-Rom
+    tangents, which reads the predicted frame in front of the left one and the one behind the right one as well (at a track's first and
+    last segment the segment's own difference stands in).  uu3d_assemble_tracks_cubic replaces uu3d_assemble_tracks, one launch for one
+    launch, no further forward (``assemble_tracks_cubic`` is the launch alone; the plan: ``evaluation.keyframe_plan_cubic`` /
+    ``keyframe_plan_cubic_at``; the rule in numpy: ``evaluation.interpolate_cubic_host``, and the poses equal it on the raw window
+    predictions bit for bit).  A predicted frame, a frame behind a track's last predicted one and the root joint of a root-relative pose
+    keep the linear call's bits; a model that predicts every frame returns the linear call's bits everywhere.  It holds in every form of
+    the call -- ``keyframes_only``, ``fps``, ``out_fps``, ``valid`` / ``repair_joints``, ``keypoints`` -- and everything behind reads the
+    cubic poses: ``bones``, ``smooth``, ``rotations``, and the root solve of ``camera`` (with ``out_fps`` its poses at the given frames'
+    times are read from the same cubic); the root trajectory itself stays piecewise linear through the solved frames, which lie at every
+    given frame, not at keyframes.  Anything else: ValueError.  Offline only: a live session would need one more predicted frame of
+    lookahead, and ``run_eval``'s report keeps the reference's protocol.  No accuracy figure is claimed."""
     import torch
     # options: the refusals shared with a live session (``options.stage_options``), then the ones only this call has
     opts = stage_options(config, len(tracks), "track", root_relative, keypoints, camera, min_root_joints, smooth, bones, repair_joints, fps, out_fps,
-                         rotations)
+                         interpolation=interpolation, rotations=rotations)
     if opts.keypoints is not None:
         check_keypoint_inputs(opts.keypoints, [_shape(t)[1] if len(_shape(t)) == 3 else -1 for t in tracks])
     if fps is not None and keyframes_only:
@@ -309,16 +328,20 @@ def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, fl
     raw, frame_idx, rows = _predicted_windows(model, cfg, table, mask_stride, flip, batch_size, depth, graph, reuse_frames)
     # assemble plan: which two predicted frames every returned frame is read from, and how
     stride = ev.prediction_stride(cfg)
+    cubic = opts.interpolation == "cubic" and stride is not None and stride > 1      # (every frame predicted: nothing lies between keyframes)
+    plan_at = evaluation.keyframe_plan_cubic_at if cubic else evaluation.keyframe_plan_at
     if fps is not None:
-        plan = evaluation.keyframe_plan_at(frame_idx, 1 if stride is None else stride, positions, rows=rows)
+        plan = plan_at(frame_idx, 1 if stride is None else stride, positions, rows=rows)
+    elif cubic:
+        plan = evaluation.keyframe_plan_cubic(frame_idx, stride, rows=rows)
     elif stride is None:
         plan = rows, rows, np.zeros(len(rows), np.float64)
     else:
         plan = evaluation.keyframe_plan(frame_idx, stride, rows=rows)[:3]
 
-    def assemble(plan):
-        return assemble_tracks(raw[0], raw[1] if flip else None, *plan, flip_order=cfg.AUGM_FLIP_KEYPOINT_ORDER,
-                               root=int(cfg.ROOT_KEYTPOINT) if root_relative else -1)
+    def assemble(plan):                                               # (a cubic plan has five arrays, a linear one three)
+        return (assemble_tracks_cubic if cubic else assemble_tracks)(raw[0], raw[1] if flip else None, *plan, flip_order=cfg.AUGM_FLIP_KEYPOINT_ORDER,
+                                                                     root=int(cfg.ROOT_KEYTPOINT) if root_relative else -1)
     out = assemble(plan)
     # bones: constant bone lengths -- everything behind reads the fixed poses
     if opts.rigid is not None:
@@ -337,7 +360,7 @@ def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, fl
     placed = ()
     if camera is not None:
         def reread(at):                                               # the same motion at the given frames' times (``out_fps``)
-            again = assemble(evaluation.keyframe_plan_at(frame_idx, 1 if stride is None else stride, at, rows=rows))
+            again = assemble(plan_at(frame_idx, 1 if stride is None else stride, at, rows=rows))
             return again if opts.rigid is None else fix_bones(again, given, bone_table, skeleton)
         at_given, where = poses_at_given_frames(out, lens, given, int(mask_stride) if keyframes_only else 0, rates if fps is not None else None,
                                                 out_fps, model_fps, reread)

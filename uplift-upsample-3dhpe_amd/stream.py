@@ -271,7 +271,7 @@ class StreamSession(object):
             raise ValueError("slots >= 1")
         # the refusals shared with ``predict_tracks`` (``options.stage_options``), then the ones only a session has
         opts = stage_options(config, slots, "slot", root_relative, keypoints, camera, min_root_joints, smooth, bones, repair_joints, fps, out_fps,
-                             rotations)
+                             rotations=rotations)
         self.rotations = opts.rotations
         self.bones, self.pose_filter, self.root_filter, self.keypoints = opts.rigid, opts.pose_filter, opts.root_filter, opts.keypoints
         self.cameras, self.min_root_joints = opts.cameras, opts.min_root_joints

@@ -1,7 +1,7 @@
 """The table stage of the track pipeline: the tracks' 2D keypoints become the dense, normalised ``data.PoseTable`` the windows are cut from,
 and the network's raw predictions become one pose per returned frame.  Wraps uu3d_normalize_tracks / uu3d_normalize_tracks_valid
-(``normalize_tracks``), uu3d_resample_tracks (``resample_tracks``) and uu3d_assemble_tracks (``assemble_tracks``); ``pose_table`` and
-``resampled_pose_table`` put the validity and keypoint stages in front of the first two.  Also the small helpers every stage uploads and
+(``normalize_tracks``), uu3d_resample_tracks (``resample_tracks``), uu3d_assemble_tracks (``assemble_tracks``) and
+uu3d_assemble_tracks_cubic (``assemble_tracks_cubic``: ``interpolation="cubic"``); ``pose_table`` and ``resampled_pose_table`` put the validity and keypoint stages in front of the first two.  Also the small helpers every stage uploads and
 checks shapes with (``_upload``: pinned, asynchronous, never waits)."""
 import ctypes as C
 
@@ -119,6 +119,19 @@ def resample_tracks(src, table, model_lens, left, right, weight, resolutions=Non
     return table
 
 
+def _check_predictions(plain, flipped, flip_order):
+    """The raw predictions as the two assemble launches take them -> (W, J)."""
+    import torch
+    if plain.dtype != torch.float32 or not plain.is_contiguous() or plain.dim() != 3 or plain.shape[2] != 3:
+        raise ValueError("plain must be a contiguous (W, J, 3) float32 device tensor")
+    J = int(plain.shape[1])
+    if flipped is not None and (flipped.shape != plain.shape or flipped.dtype != torch.float32 or not flipped.is_contiguous()):
+        raise ValueError("flipped must match plain")
+    if flipped is not None and (flip_order is None or len(flip_order) != J):
+        raise ValueError("flipped predictions need the J entries of AUGM_FLIP_KEYPOINT_ORDER")
+    return int(plain.shape[0]), J
+
+
 def assemble_tracks(plain, flipped, left, right, weight, flip_order=None, root=-1):
     """uu3d_assemble_tracks on the current stream.  ``plain`` / ``flipped`` (W, J, 3) float32 on the device (``flipped`` None: no flip);
     ``left`` / ``right`` / ``weight``: the plan of ``evaluation.keyframe_plan`` with rows of those arrays (host arrays of F entries);
@@ -126,14 +139,8 @@ def assemble_tracks(plain, flipped, left, right, weight, flip_order=None, root=-
     import torch
     lib = _capi.load_library()
     dev = plain.device
-    W, J = int(plain.shape[0]), int(plain.shape[1])
     F = len(left)
-    if plain.dtype != torch.float32 or not plain.is_contiguous() or plain.dim() != 3 or plain.shape[2] != 3:
-        raise ValueError("plain must be a contiguous (W, J, 3) float32 device tensor")
-    if flipped is not None and (flipped.shape != plain.shape or flipped.dtype != torch.float32 or not flipped.is_contiguous()):
-        raise ValueError("flipped must match plain")
-    if flipped is not None and (flip_order is None or len(flip_order) != J):
-        raise ValueError("flipped predictions need the J entries of AUGM_FLIP_KEYPOINT_ORDER")
+    W, J = _check_predictions(plain, flipped, flip_order)
     d_left, d_right = _upload(left, np.int32, dev), _upload(right, np.int32, dev)
     d_weight = _upload(weight, np.float64, dev)
     d_order = None if flipped is None else _upload(flip_order, np.int32, dev)
@@ -142,6 +149,29 @@ def assemble_tracks(plain, flipped, left, right, weight, flip_order=None, root=-
         stream = torch.cuda.current_stream(dev).cuda_stream
         _capi.check(lib, lib.uu3d_assemble_tracks(_ptr(plain), _ptr(flipped), W, _ptr(d_order), _ptr(d_left), _ptr(d_right), _ptr(d_weight),
                                                   F, J, int(root), _ptr(out), C.c_void_p(stream)), None)
+    return out
+
+
+def assemble_tracks_cubic(plain, flipped, before, left, right, after, weight, flip_order=None, root=-1):
+    """uu3d_assemble_tracks_cubic on the current stream: ``assemble_tracks`` with the plan of ``evaluation.keyframe_plan_cubic`` /
+    ``keyframe_plan_cubic_at`` -- ``before`` / ``after``: the predicted frame in front of ``left`` and the one behind ``right``, -1: none
+    (host arrays of F entries each) -- and a C1 cubic between the predicted frames (``evaluation.interpolate_cubic_host`` is the rule in
+    numpy, and the result equals it bit for bit).  -> (F, J, 3) float32 on the device."""
+    import torch
+    lib = _capi.load_library()
+    dev = plain.device
+    F = len(left)
+    W, J = _check_predictions(plain, flipped, flip_order)
+    if not (len(before) == len(right) == len(after) == len(weight) == F):
+        raise ValueError("the plan must have one entry per frame in each of its five arrays")
+    d_plan = [_upload(a, np.int32, dev) for a in (before, left, right, after)]
+    d_weight = _upload(weight, np.float64, dev)
+    d_order = None if flipped is None else _upload(flip_order, np.int32, dev)
+    out = torch.empty((F, J, 3), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _capi.check(lib, lib.uu3d_assemble_tracks_cubic(_ptr(plain), _ptr(flipped), W, _ptr(d_order), *(_ptr(a) for a in d_plan), _ptr(d_weight),
+                                                        F, J, int(root), _ptr(out), C.c_void_p(stream)), None)
     return out
 
 
