@@ -13,6 +13,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "uu3d.h" /* uu3d_model, UU3D_SCHEDULE_*: the operators of the spatial stack run on a handle */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -221,6 +223,53 @@ int uu3d_op_tiled_dense(const uu3d_tiled_dense_args* args, void* stream);
 /* HOST: {slices, k-tiles per slice} the launch of (M, N, K) takes under the forward's split rule (splitk_rule with its exception), for a test to
  * hold its own restatement of the rule against. */
 int uu3d_op_tiled_split(int32_t M, int32_t N, int32_t K, int32_t splitk_target, size_t slab_floats, int32_t* slices, int32_t* k_tiles_per_slice);
+
+/* ---- stage 1 of the forward, the SPATIAL STACK, each kernel form on its own (UpliftUpsampleTransformer.spatial_transformation up to, not
+ * including, spatial_to_temporal_fc, u_u_t.py:313-330: keypoint embedding + spatial PE, spatial_depth pre-LN blocks of attention over the J
+ * joints and an exact-erf GELU MLP, spatial_norm), launched through the helpers the forward's spatial_stage and generic_frame_features launch
+ * through (launch_spatial_stack, launch_compact_frames, csrc/uu3d_forward.inc; generic_spatial_launch, csrc/uu3d_train_entry.inc): grid, block,
+ * LDS bytes, SpatialParams and fragment arenas are the forward's -- tests/test_spatial_ops_gpu.py holds them to float64. ---- */
+#define UU3D_SPATIAL_AUTO 0      /* spatial_stage's own choice for this handle and frame count: uu3d_op_spatial_choice(model, F, UU3D_SCHEDULE_LATENCY) */
+#define UU3D_SPATIAL_F32 1       /* spatial_stack_mfma_kernel<17, 3> (csrc/uu3d_spatial.h): exact f32, one wave per 3 frames */
+#define UU3D_SPATIAL_H3_TILES 2  /* spatial_stack_h3_kernel<17, 3, kSpatialMT> (csrc/uu3d_spatial_h3.h, inference form): f16x3, 3 frames per workgroup */
+#define UU3D_SPATIAL_P16 3       /* spatial_stack_p16_kernel<17, 7, 1> (csrc/uu3d_spatial_p16.h): f16x3, 7 frames per workgroup */
+#define UU3D_SPATIAL_OUT_F32 0   /* out_dev: S[F][J d_s] f32 */
+#define UU3D_SPATIAL_OUT_PLANES 1/* out_dev: hi[F][J d_s] halfs, lo directly behind it (value = hi + lo / 2048), 4 F J d_s bytes; f16x3 kernels only */
+/* S = the spatial stack of frames_dev[F][J][2] on a COMMITTED handle: the kernel reads the handle's own SpatialParams and weight fragments as
+ * uu3d_commit_weights packed them (a handle with generic dims: its master parameter buffer).
+ *   mask_dev == NULL: every frame is computed.  mask_dev != NULL (F bytes, any nonzero byte = compute): compact_frames_kernel first writes the
+ *     list of the frames to compute into frame_list_dev (F + 1 ints, required then; see uu3d_op_compact_frames), as spatial_stage does; the rows
+ *     of out_dev of the other frames are NOT written (both planes likewise).
+ *   Handles with the compiled dims (J 17, d_s 32, h_s 64, 8 heads, d_t 384): any kernel; the f16x3 kernels need a handle of precision f16x3
+ *     (a handle of precision f32 holds no f16 fragments).  UU3D_SPATIAL_AUTO on a handle of precision f32 is UU3D_SPATIAL_F32.
+ *   Handles with generic dims: UU3D_SPATIAL_AUTO only, which launches spatial_generic_kernel (csrc/uu3d_spatial_generic.h, exact f32, one
+ *     workgroup per frame, any J / d_s / heads / h_s that fits 160 KiB of LDS) exactly as uu3d_frame_features does, the repack of the operand
+ *     packs included; no mask (that kernel has no frame list), no planes.
+ * Returned before any launch, out_dev untouched:
+ *   UU3D_ERR_INVALID_ARGUMENT: a null model, frames_dev or out_dev; F < 1 or F J > 2^30; a mask without frame_list_dev; an unknown kernel or
+ *     layout; UU3D_SPATIAL_OUT_PLANES with UU3D_SPATIAL_F32 (or with AUTO where AUTO is that kernel) or on a generic handle; a forced kernel or a
+ *     mask on a generic handle; an f16x3 kernel on a handle of precision f32;
+ *   UU3D_ERR_NOT_READY: uu3d_commit_weights has not run since the last uu3d_set_weight;
+ *   UU3D_ERR_UNSUPPORTED: a generic handle whose frame does not fit the LDS (include/uu3d.h, FRAMES FORM).
+ * Rows of out_dev beyond F are not written.  A frame's result does not depend on F, on its index or on the other frames: the same bits.
+ * frames_dev 8-byte aligned, out_dev 16-byte aligned (not checked).  The model's range word is not touched. */
+int uu3d_op_spatial_stack(uu3d_model* model, const float* frames_dev, int32_t F, const uint8_t* mask_dev, int32_t* frame_list_dev,
+                          int32_t kernel, int32_t out_layout, void* out_dev, void* stream);
+/* compact_frames_kernel (csrc/uu3d_misc.h) on its own, the launch spatial_stage makes for a masked batch: list_dev[0 .. n - 1] = the indices i
+ * of the nonzero bytes mask_dev[i], i < total, in rising order; list_dev[total] = n.  list_dev holds total + 1 ints; its entries n .. total - 1
+ * are not written.  One workgroup; mask_dev needs no alignment (16-byte aligned runs of 16 bytes are read as one piece).  total >= 1 and both
+ * pointers non-null, else UU3D_ERR_INVALID_ARGUMENT before any launch. */
+int uu3d_op_compact_frames(const uint8_t* mask_dev, int32_t total, int32_t* list_dev /* total + 1 ints */, void* stream);
+/* HOST: the decision of spatial_stage for a launch of F frames under `schedule` (UU3D_SCHEDULE_LATENCY or _THROUGHPUT, optionally with
+ * UU3D_SCHEDULE_EXACT_F32), restated for a test to hold its own statement of the rule against: *kernel = UU3D_SPATIAL_F32, _H3_TILES or _P16,
+ * *planes = 1 when the stack leaves S as the f16 planes the spatial-to-temporal GEMM reads.  The rule: an f16x3 kernel iff the call's precision
+ * is f16x3 (the handle's, unless the exact-f32 bit is set), UU3D_SPATIAL is not f32, and either UU3D_SPATIAL=h3 or the launch is small enough
+ * that the f16x3 rounds are no longer than the exact-f32 kernel's (spatial_h3_pays: ceil(F / 3) workgroups, 1536 per round of 68 us against
+ * 1792 per round of 133 us); of the two, UU3D_SPATIAL=h3tiles takes _H3_TILES, anything else _P16; planes iff f16x3, UU3D_NO_PLANES is not 1
+ * and J d_s % 32 == 0.  The switches are the handle's, read by uu3d_create.  The handle need not be committed.
+ * UU3D_ERR_INVALID_ARGUMENT: a null pointer, F < 1, another schedule value, a handle with generic dims (it has one spatial kernel); the handle is
+ * const here: uu3d_last_error is not written. */
+int uu3d_op_spatial_choice(const uu3d_model* model, int32_t F, int32_t schedule, int32_t* kernel, int32_t* planes); /* HOST: what spatial_stage takes */
 
 #ifdef __cplusplus
 }

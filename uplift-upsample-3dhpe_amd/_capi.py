@@ -61,6 +61,7 @@ OPS_SYMBOLS = (
     "uu3d_op_wt_operand_bytes", "uu3d_op_wt_pack", "uu3d_op_ln_dense_wt",
     "uu3d_op_attn_infer", "uu3d_op_attn_qf_bytes", "uu3d_op_attn_qf_pack",
     "uu3d_op_tiled_operand_bytes", "uu3d_op_tiled_pack", "uu3d_op_tiled_dense", "uu3d_op_tiled_split",
+    "uu3d_op_spatial_stack", "uu3d_op_compact_frames", "uu3d_op_spatial_choice",
 )
 # epilogues of uu3d_op_ln_dense_panel_ex / uu3d_op_ln_dense_wt (include/uu3d_ops.h)
 UU3D_EP_BIAS, UU3D_EP_BIAS_RELU_SPLIT, UU3D_EP_BIAS_SPLIT_Q, UU3D_EP_BIAS_RESIDUAL, UU3D_EP_BIAS_RESIDUAL_LN = range(5)
@@ -71,6 +72,9 @@ UU3D_ATTN_OUT_F32, UU3D_ATTN_OUT_PLANES, UU3D_ATTN_OUT_FRAG = range(3)
 # A sources and further epilogues of uu3d_op_tiled_dense (include/uu3d_ops.h)
 UU3D_A_F32, UU3D_A_F32_LN, UU3D_A_PLANES, UU3D_A_CONV3_F32, UU3D_A_CONV3_PLANES = range(5)
 UU3D_EP_BIAS_RELU, UU3D_EP_CONV_RESIDUAL, UU3D_EP_S2T = 5, 6, 7
+# kernels and output layouts of uu3d_op_spatial_stack (include/uu3d_ops.h)
+UU3D_SPATIAL_AUTO, UU3D_SPATIAL_F32, UU3D_SPATIAL_H3_TILES, UU3D_SPATIAL_P16 = range(4)
+UU3D_SPATIAL_OUT_F32, UU3D_SPATIAL_OUT_PLANES = range(2)
 
 
 class Uu3dTiledDenseArgs(C.Structure):
@@ -480,6 +484,12 @@ def load_library(path=None):
     lib.uu3d_op_tiled_dense.argtypes = [C.POINTER(Uu3dTiledDenseArgs), vp]
     lib.uu3d_op_tiled_split.restype = C.c_int
     lib.uu3d_op_tiled_split.argtypes = [i32, i32, i32, i32, sz, C.POINTER(i32), C.POINTER(i32)]
+    lib.uu3d_op_spatial_stack.restype = C.c_int
+    lib.uu3d_op_spatial_stack.argtypes = [vp, vp, i32, vp, vp, i32, i32, vp, vp]
+    lib.uu3d_op_compact_frames.restype = C.c_int
+    lib.uu3d_op_compact_frames.argtypes = [vp, i32, vp, vp]
+    lib.uu3d_op_spatial_choice.restype = C.c_int
+    lib.uu3d_op_spatial_choice.argtypes = [vp, i32, i32, C.POINTER(i32), C.POINTER(i32)]
     if path is None:
         _lib = lib
     return lib

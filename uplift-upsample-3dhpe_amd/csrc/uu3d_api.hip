@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/uu3d.h"
+#include "../../include/uu3d_ops.h"      // the operators that need the model: uu3d_op_spatial_* (uu3d_forward.inc)
 #include "uu3d_switches.h"
 #include "uu3d_gemm.h"
 #include "uu3d_gemm_h3.h"
@@ -372,6 +373,7 @@ static int generic_forward_frames(uu3d_model* m, const FramesIn& frames, const u
 static size_t generic_frame_features_bytes(const uu3d_model* m, long F);                                                // uu3d_train_entry.inc
 static int generic_frame_features(uu3d_model* m, const float* frames_dev, int32_t F, float* features, void* workspace, size_t workspace_bytes,
                                   void* stream);                                                                        // uu3d_train_entry.inc
+static int generic_op_spatial_stack(uu3d_model* m, const float* frames_dev, int32_t F, float* S, void* stream);         // uu3d_train_entry.inc
 void uu3d_destroy(uu3d_model* m) {
     if (!m) return;
     (void)hipSetDevice(m->device);

@@ -324,42 +324,56 @@ struct Launcher {
 // Which spatial kernel runs, and whether it leaves S as the two f16 planes the LDS-DMA GEMM reads (no split in the GEMM's loader:
 // 32.6 -> 29.6 us for the GEMM, the spatial kernel unchanged), is decided HERE and nowhere else.
 // c: the call's configuration (precision: the handle's, or f32 under UU3D_SCHEDULE_EXACT_F32).  timing_skip: the launch honours UU3D_SKIP bit 1.
+// The three launch helpers below are shared by spatial_stage and the operator ABI (uu3d_op_spatial_choice, uu3d_op_compact_frames,
+// uu3d_op_spatial_stack at the end of this file): the rule, the grids, the LDS sizes and the arena pointers exist once.
+enum SpatialKernel : int { SPATIAL_AUTO = 0, SPATIAL_F32 = 1, SPATIAL_H3_TILES = 2, SPATIAL_P16 = 3 };      // = UU3D_SPATIAL_* of include/uu3d_ops.h
+struct SpatialChoice { int kernel; bool planes; };
+inline const char* spatial_class_name(int kernel) { return kernel == SPATIAL_H3_TILES ? "spatial_h3" : kernel == SPATIAL_P16 ? "spatial_p16" : "spatial_mfma"; }
+// c: the call's configuration (precision: the handle's, or f32 under UU3D_SCHEDULE_EXACT_F32); M: the frames of the launch
+inline SpatialChoice spatial_choose(const uu3d_model* m, const uu3d_config& c, int M) {
+    const bool h3 = c.precision == UU3D_PREC_F16X3 && !m->sw.spatial_f32 && (m->sw.spatial_h3_always || spatial_h3_pays(M));
+    const bool planes = h3 && !m->sw.no_planes && (c.num_keypoints * c.d_spatial) % 32 == 0;
+    return SpatialChoice{!h3 ? SPATIAL_F32 : m->sw.spatial_h3_tiles ? SPATIAL_H3_TILES : SPATIAL_P16, planes};
+}
+// mask[M] bytes -> list[M + 1]: the indices of the nonzero bytes in order, their count at list[M].  Launch only.
+inline void launch_compact_frames(hipStream_t stream, const uint8_t* mask, int M, int* list) {
+    hipLaunchKernelGGL(compact_frames_kernel, dim3(1), dim3(1024), 0, stream, mask, M, list);
+}
+// One spatial kernel (SPATIAL_F32 / _H3_TILES / _P16) over M frames on the handle's committed SpatialParams and fragment arenas.
+// frame_list: launch_compact_frames' list, or nullptr for every frame.  s_lo != nullptr (f16x3 kernels): the result as f16 planes at s_hi / s_lo
+// instead of f32 at S.  Launch only; the caller reads the launch error.
+inline void launch_spatial_stack(const uu3d_model* m, hipStream_t stream, int kernel, const float* kp2d, int M, const int* frame_list, float* S, _Float16* s_hi, _Float16* s_lo) {
+    SpatialParams sp = m->sp;
+    sp.total_frames = M;
+    sp.frame_list = frame_list;
+    if (kernel == SPATIAL_H3_TILES)
+        hipLaunchKernelGGL((spatial_stack_h3_kernel<kJ, kFR, kSpatialMT>), dim3((M + kFR - 1) / kFR), dim3(64 * (2 / kSpatialMT)), sh3::lds_bytes(), stream, kp2d, sp,
+                           m->harena + m->sp_frag_off, S, s_hi, s_lo, SpatialTrainIO{});
+    else if (kernel == SPATIAL_P16)
+        hipLaunchKernelGGL((spatial_stack_p16_kernel<kJ, kP16FR, kP16PW>), dim3((M + kP16FR - 1) / kP16FR), dim3(64 * p16_waves(kJ, kP16FR, kP16PW)), sp16::lds_bytes<kP16FR>(m->cfg.spatial_depth),
+                           stream, kp2d, sp, m->harena + m->sp_frag16_off, S, s_hi, s_lo);
+    else
+        hipLaunchKernelGGL((spatial_stack_mfma_kernel<kJ, kFR>), dim3((M + kFR - 1) / kFR), dim3(64), spatial_v2_lds_bytes(), stream, kp2d, sp, S);
+}
+
 template <class EP>
 void spatial_stage(Launcher& Lh, const uu3d_config& c, const float* kp2d, int M, const uint8_t* mask, int* frame_list, float* S, bool timing_skip, const EP& ep) {
     uu3d_model* const m = Lh.m;
     const int J = c.num_keypoints, ds = c.d_spatial, dt = c.d_temporal;
-    const bool h3 = c.precision == UU3D_PREC_F16X3 && !m->sw.spatial_f32 && (m->sw.spatial_h3_always || spatial_h3_pays(M));
-    const bool planes = h3 && !m->sw.no_planes && (J * ds) % 32 == 0;
-    const bool skip = timing_skip && (skip_mask() & 1);
-    SpatialParams sp = m->sp;
-    sp.total_frames = M;
-    sp.frame_list = nullptr;
+    const SpatialChoice ch = spatial_choose(m, c, M);
+    const bool planes = ch.planes;
+    const bool skip = timing_skip && (skip_mask() & 1) && ch.kernel != SPATIAL_F32;
     if (mask != nullptr) {
         Lh.begin("compact_frames", "compact_frames", 0.0, (double)M * 5.0);
-        hipLaunchKernelGGL(compact_frames_kernel, dim3(1), dim3(1024), 0, Lh.stream, mask, M, frame_list);
+        launch_compact_frames(Lh.stream, mask, M, frame_list);
         Lh.end();
-        sp.frame_list = frame_list;
     }
     const double fl = (double)M * (2.0 * J * 2 * ds + c.spatial_depth * (4.0 * 2 * J * ds * ds + 8.0 * 4 * J * J * (ds / 8) + 2.0 * 2 * J * ds * kHS));
     _Float16* const s_hi = planes ? reinterpret_cast<_Float16*>(S) : (_Float16*)nullptr;
     _Float16* const s_lo = planes ? reinterpret_cast<_Float16*>(S) + (size_t)M * J * ds : (_Float16*)nullptr;
-    if (h3 && m->sw.spatial_h3_tiles) {
-        Lh.begin("spatial_stack", "spatial_h3", fl, 4.0 * M * J * (2.0 + ds));
-        if (!skip)
-        hipLaunchKernelGGL((spatial_stack_h3_kernel<kJ, kFR, kSpatialMT>), dim3((M + kFR - 1) / kFR), dim3(64 * (2 / kSpatialMT)), sh3::lds_bytes(), Lh.stream, kp2d, sp,
-                           m->harena + m->sp_frag_off, S, s_hi, s_lo, SpatialTrainIO{});
-        Lh.end();
-    } else if (h3) {
-        Lh.begin("spatial_stack", "spatial_p16", fl, 4.0 * M * J * (2.0 + ds));
-        if (!skip)
-        hipLaunchKernelGGL((spatial_stack_p16_kernel<kJ, kP16FR, kP16PW>), dim3((M + kP16FR - 1) / kP16FR), dim3(64 * p16_waves(kJ, kP16FR, kP16PW)), sp16::lds_bytes<kP16FR>(c.spatial_depth),
-                           Lh.stream, kp2d, sp, m->harena + m->sp_frag16_off, S, s_hi, s_lo);
-        Lh.end();
-    } else {
-        Lh.begin("spatial_stack", "spatial_mfma", fl, 4.0 * M * J * (2.0 + ds));
-        hipLaunchKernelGGL((spatial_stack_mfma_kernel<kJ, kFR>), dim3((M + kFR - 1) / kFR), dim3(64), spatial_v2_lds_bytes(), Lh.stream, kp2d, sp, S);
-        Lh.end();
-    }
+    Lh.begin("spatial_stack", spatial_class_name(ch.kernel), fl, 4.0 * M * J * (2.0 + ds));
+    if (!skip) launch_spatial_stack(m, Lh.stream, ch.kernel, kp2d, M, mask != nullptr ? frame_list : nullptr, S, s_hi, s_lo);
+    Lh.end();
     if (planes) Lh.gemm_g("s2t", GLoadPlain{s_hi, s_lo, J * ds, M}, m->s2t_wt, M, dt, J * ds, ep);
     else Lh.gemm("s2t", ALoadPlain{S, J * ds, M, J * ds}, m->s2t_wt, M, dt, J * ds, ep);
 }
@@ -740,4 +754,60 @@ int uu3d_frame_features(uu3d_model* m, const float* frames_dev, int32_t F, float
         Lh.end();
     }
     return Lh.status;
+}
+
+// ---- operator ABI of stage 1 (include/uu3d_ops.h): the spatial kernels and the frame compaction on their own, through the helpers
+// spatial_stage launches through -- tests/test_spatial_ops_gpu.py holds them to float64 ----
+static_assert(UU3D_SPATIAL_AUTO == SPATIAL_AUTO && UU3D_SPATIAL_F32 == SPATIAL_F32 && UU3D_SPATIAL_H3_TILES == SPATIAL_H3_TILES && UU3D_SPATIAL_P16 == SPATIAL_P16,
+              "uu3d_ops.h and uu3d_forward.inc name the spatial kernels alike");
+
+// (a host query on a const handle: the status alone says what was wrong, the handle's last-error text is not written)
+int uu3d_op_spatial_choice(const uu3d_model* m, int32_t F, int32_t schedule, int32_t* kernel, int32_t* planes) {
+    if (!m || !kernel || !planes || F < 1) return UU3D_ERR_INVALID_ARGUMENT;
+    const bool exact_f32 = (schedule & UU3D_SCHEDULE_EXACT_F32) != 0;
+    schedule &= ~UU3D_SCHEDULE_EXACT_F32;
+    if (schedule != UU3D_SCHEDULE_LATENCY && schedule != UU3D_SCHEDULE_THROUGHPUT) return UU3D_ERR_INVALID_ARGUMENT;
+    if (m->generic) return UU3D_ERR_INVALID_ARGUMENT;      // a handle with generic dims has one spatial kernel
+    uu3d_config c = m->cfg;
+    if (exact_f32) c.precision = UU3D_PREC_F32;
+    const SpatialChoice ch = spatial_choose(m, c, F);
+    *kernel = ch.kernel; *planes = ch.planes ? 1 : 0;
+    return UU3D_OK;
+}
+
+int uu3d_op_compact_frames(const uint8_t* mask_dev, int32_t total, int32_t* list_dev, void* stream) {
+    if (!mask_dev || !list_dev || total < 1) return UU3D_ERR_INVALID_ARGUMENT;
+    launch_compact_frames((hipStream_t)stream, mask_dev, total, list_dev);
+    return hipGetLastError() == hipSuccess ? UU3D_OK : UU3D_ERR_HIP;
+}
+
+int uu3d_op_spatial_stack(uu3d_model* m, const float* frames_dev, int32_t F, const uint8_t* mask_dev, int32_t* frame_list_dev, int32_t kernel,
+                          int32_t out_layout, void* out_dev, void* stream_) {
+    if (!m) return UU3D_ERR_INVALID_ARGUMENT;
+    if (!frames_dev || !out_dev || F < 1) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_op_spatial_stack: null buffer or frames < 1");
+    if (mask_dev != nullptr && frame_list_dev == nullptr) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_op_spatial_stack: a mask needs frame_list_dev (frames + 1 ints)");
+    if (kernel < SPATIAL_AUTO || kernel > SPATIAL_P16) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_op_spatial_stack: unknown kernel");
+    if (out_layout != UU3D_SPATIAL_OUT_F32 && out_layout != UU3D_SPATIAL_OUT_PLANES) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_op_spatial_stack: unknown output layout");
+    if ((long)F * m->cfg.num_keypoints > (1L << 30)) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "too many frames");
+    if (!m->committed) return fail(m, UU3D_ERR_NOT_READY, "uu3d_commit_weights has not been called");
+    const bool want_planes = out_layout == UU3D_SPATIAL_OUT_PLANES;
+    if (m->generic) {
+        if (kernel != SPATIAL_AUTO) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_op_spatial_stack: the f32 / f16x3 spatial kernels are compiled for 17 joints, d_s 32, h_s 64, 8 heads; this handle has generic dims");
+        if (mask_dev != nullptr) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_op_spatial_stack: spatial_generic_kernel takes no frame list");
+        if (want_planes) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_op_spatial_stack: spatial_generic_kernel writes f32");
+        if (!has_frames_form(m)) return no_frames_form(m, "uu3d_op_spatial_stack");
+        return generic_op_spatial_stack(m, frames_dev, F, (float*)out_dev, stream_);
+    }
+    if (kernel == SPATIAL_AUTO) kernel = spatial_choose(m, m->cfg, F).kernel;
+    if (kernel != SPATIAL_F32 && m->cfg.precision != UU3D_PREC_F16X3)
+        return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_op_spatial_stack: a handle of precision f32 holds no f16 weight fragments for the f16x3 spatial kernels");
+    if (kernel == SPATIAL_F32 && want_planes) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_op_spatial_stack: spatial_stack_mfma_kernel writes f32");
+    HIPCHK(m, hipSetDevice(m->device));
+    hipStream_t stream = (hipStream_t)stream_;
+    if (mask_dev != nullptr) launch_compact_frames(stream, mask_dev, F, frame_list_dev);
+    const size_t n = (size_t)F * m->cfg.num_keypoints * m->cfg.d_spatial;
+    launch_spatial_stack(m, stream, kernel, frames_dev, F, mask_dev != nullptr ? frame_list_dev : nullptr, (float*)out_dev,      // (planes: hi over S, lo behind it, as spatial_stage places them)
+                         want_planes ? (_Float16*)out_dev : nullptr, want_planes ? (_Float16*)out_dev + n : nullptr);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? UU3D_OK : fail(m, UU3D_ERR_HIP, std::string("uu3d_op_spatial_stack: launch failed: ") + hipGetErrorString(e));
 }

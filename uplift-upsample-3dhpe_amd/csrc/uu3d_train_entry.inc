@@ -63,6 +63,37 @@ GenericFrameWs generic_frame_carve(const uu3d_model* m, long F, char* base) {
 }  // namespace
 static size_t generic_frame_features_bytes(const uu3d_model* m, long F) { return generic_frame_carve(m, F, nullptr).bytes; }
 
+// The spatial launch of a generic handle, shared by generic_frame_features and the operator ABI (uu3d_op_spatial_stack): the repack when the
+// packs are not the handle's, then spatial_generic_kernel, one workgroup per frame -> S (F, J d_s).  The training lock is held, the device set.
+static int generic_spatial_launch(uu3d_model* m, const float* frames_dev, int32_t F, float* S, void* stream_, const char* who) {
+    TrainState& t = *m->ts;
+    const uu3d_config& c = m->cfg;
+    if (t.packed_from != m->gparams) {
+        const int r = uu3d_train_repack(m, m->gparams, stream_);
+        if (r != UU3D_OK) return fail(m, r, std::string(who) + ": repack failed");
+    }
+    const int J = c.num_keypoints, ds = c.d_spatial;
+    const NetW& nw = t.nw;
+    SpatialGenericParams p{};
+    p.params = m->gparams; p.blocks = t.d_sg_blocks;
+    p.emb_w = nw.emb_w; p.emb_b = nw.emb_b; p.pe = nw.pe_s; p.norm_g = nw.sn_g; p.norm_b = nw.sn_b;
+    p.J = J; p.ds = ds; p.hs = c.h_spatial; p.H = c.num_heads; p.depth = c.spatial_depth; p.hg = spatial_generic_head_group(J, c.num_heads);
+    const size_t lds = spatial_generic_lds_bytes(J, ds, c.h_spatial, c.num_heads);      // (<= 160 KiB: has_frames_form, asked by the caller)
+    allow_lds<spatial_generic_kernel<SG_ROWS>>(SG_LDS_LIMIT);
+    hipLaunchKernelGGL(spatial_generic_kernel<SG_ROWS>, dim3((unsigned)F), dim3(SG_THREADS), lds, (hipStream_t)stream_, frames_dev, p, S);
+    return UU3D_OK;
+}
+
+// uu3d_op_spatial_stack on a generic handle (arguments checked by the caller in uu3d_forward.inc)
+static int generic_op_spatial_stack(uu3d_model* m, const float* frames_dev, int32_t F, float* S, void* stream_) {
+    if (m->ts == nullptr || m->gparams == nullptr) return fail(m, UU3D_ERR_NOT_READY, "uu3d_commit_weights has not been called");
+    std::lock_guard<std::recursive_mutex> lock(m->train_mu);
+    HIPCHK(m, hipSetDevice(m->device));
+    const int st = generic_spatial_launch(m, frames_dev, F, S, stream_, "uu3d_op_spatial_stack");
+    if (st != UU3D_OK) return st;
+    return hipGetLastError() == hipSuccess ? UU3D_OK : fail(m, UU3D_ERR_HIP, "uu3d_op_spatial_stack: launch failed");
+}
+
 static int generic_frame_features(uu3d_model* m, const float* frames_dev, int32_t F, float* features, void* workspace, size_t workspace_bytes,
                                   void* stream_) {
     if (m->ts == nullptr || m->gparams == nullptr) return fail(m, UU3D_ERR_NOT_READY, "uu3d_commit_weights has not been called");
@@ -73,20 +104,11 @@ static int generic_frame_features(uu3d_model* m, const float* frames_dev, int32_
     const uu3d_config& c = m->cfg;
     hipStream_t stream = (hipStream_t)stream_;
     HIPCHK(m, hipSetDevice(m->device));
-    if (t.packed_from != m->gparams) {
-        const int r = uu3d_train_repack(m, m->gparams, stream_);
-        if (r != UU3D_OK) return fail(m, r, "uu3d_frame_features: repack failed");
-    }
     m->prof_used = 0;
+    const int launched = generic_spatial_launch(m, frames_dev, F, w.S, stream_, "uu3d_frame_features");
+    if (launched != UU3D_OK) return launched;
     const int J = c.num_keypoints, ds = c.d_spatial, dt = c.d_temporal;
     const NetW& nw = t.nw;
-    SpatialGenericParams p{};
-    p.params = m->gparams; p.blocks = t.d_sg_blocks;
-    p.emb_w = nw.emb_w; p.emb_b = nw.emb_b; p.pe = nw.pe_s; p.norm_g = nw.sn_g; p.norm_b = nw.sn_b;
-    p.J = J; p.ds = ds; p.hs = c.h_spatial; p.H = c.num_heads; p.depth = c.spatial_depth; p.hg = spatial_generic_head_group(J, c.num_heads);
-    const size_t lds = spatial_generic_lds_bytes(J, ds, c.h_spatial, c.num_heads);      // (<= 160 KiB: has_frames_form, asked by the caller)
-    allow_lds<spatial_generic_kernel<SG_ROWS>>(SG_LDS_LIMIT);
-    hipLaunchKernelGGL(spatial_generic_kernel<SG_ROWS>, dim3((unsigned)F), dim3(SG_THREADS), lds, stream, frames_dev, p, w.S);
     const float* Bt = t.tarena + nw.s2t.fwd;
     const _Float16* Bh = t.tarena_h ? t.tarena_h + nw.s2t.fwd : nullptr;
     const _Float16* Bl = t.tarena_h ? Bh + t.tarena_floats : nullptr;
