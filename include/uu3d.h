@@ -791,6 +791,29 @@ int uu3d_stream_out_reset(uu3d_model* model, const uu3d_stream_config* cfg, cons
                           void* state_dev, const uint8_t* slot_mask_dev, void* stream);
 
 /*
+ * LIVE C1 MOTION (stream.StreamSession(fps=F, interpolation="cubic"), with or without out_fps): the poses of the two sessions above read
+ * from the C1 Catmull-Rom cubic through the emitted keyframes in place of the line -- the rule of C1 MOTION BETWEEN KEYFRAMES
+ * (evaluation.interpolate_cubic_host), live.  A pose at model position u = num / den has k0, k1 and the weight w exactly as above.
+ * u == k0: keyframe k0's bits, as above.  Elsewhere the cubic Hermite segment from p1 = keyframe k0 to p2 = keyframe k1 = k0 + P at
+ * t = w -- the same single float64 division of two integers -- with Catmull-Rom tangents from p0 = keyframe k0 - P and p3 = keyframe
+ * k1 + P: m1 = (p2 - p0) / 2, or p2 - p1 in a slot's first segment (k0 < P: there is no keyframe in front, and its ring place is not
+ * read), m2 = (p3 - p1) / 2 always -- a live track has no last segment.  float64 on the float32 keyframes, every operation rounded on
+ * its own (no fused multiply-add), rounded once to float32: the bits of the numpy rule.  The root joint of a root-relative pose stays 0.
+ * The plan has two more requirements than the linear one (stream.rate_plan(interpolation="cubic") enumerates both over the same
+ * period): the newest emitted centre must have reached k1 + P wherever a pose is not on a keyframe, which raises the smallest lookahead
+ * and lowers a_m; and rate->key_ring must still hold k0 - P of the oldest pose a push reads while the newest centre is filed.
+ * The ring, the state layouts, every other launch and the resets are those above; only the emit of a push changes:
+ *   uu3d_stream_timed_emit_cubic(model, cfg, rate, state_dev, out_dev, fresh_out_dev, stream) IN PLACE OF uu3d_stream_timed_emit, and
+ *   uu3d_stream_timed_emit_multi_cubic(model, cfg, rate, out, state_dev, poses_dev, count_dev, stream) IN PLACE OF
+ *   uu3d_stream_timed_emit_multi: the arguments, the status codes, the held pose and fresh_out, the counter discipline, the zero rows behind
+ *   count and the stores of their linear siblings.  Each reads the four ring places (k0 / P - 1) .. (k0 / P + 2) modulo key_ring.
+ */
+int uu3d_stream_timed_emit_cubic(uu3d_model* model, const uu3d_stream_config* cfg, const uu3d_stream_rate* rate, void* state_dev,
+                                 float* out_dev, uint8_t* fresh_out_dev, void* stream);
+int uu3d_stream_timed_emit_multi_cubic(uu3d_model* model, const uu3d_stream_config* cfg, const uu3d_stream_rate* rate,
+                                       const uu3d_stream_out* out, void* state_dev, float* poses_dev, int32_t* count_dev, void* stream);
+
+/*
  * LIVE PER-JOINT MISSED DETECTIONS (stream.StreamSession(repair_joints=G)): PER-JOINT MISSED DETECTIONS for LIVE TRACKS.  The contract of
  * LIVE TRACKS is unchanged: after the push that made frame t the newest of a slot, the pose of frame t - lookahead is the one of the track
  * cut at t with uu3d_repair_joints (max_gap = G) in front.  The rule looks ahead (a gap is interpolated once it has closed), so a push may

@@ -5,13 +5,16 @@ A tick = host clock from the call to the synchronised result (a live consumer re
 Median (and 90th percentile) over --ticks ticks after --warmup ticks, per config and slot count.
 A case is CONFIG:s_in, or generic:J,d_s,d_t,heads,N:s_in for a model with generic dims (e.g. --cases generic:25,16,64,4,27:4): its tick
 (the one-workgroup-per-frame spatial stack + the generic forward's second stage in the graph) beside the same baseline.
-   python tools/stream_bench.py [--slots 1,8,64] [--cases h36m_81:4,h36m_351:5] [--ticks 300] [--warmup 60] [--lookahead 0] [--fps F [--out_fps G]]
+   python tools/stream_bench.py [--slots 1,8,64] [--cases h36m_81:4,h36m_351:5] [--ticks 300] [--warmup 60] [--lookahead 0] [--fps F [--out_fps G] [--interpolation cubic]]
                                 [--repair_joints G] [--detections D] [--camera FX FY CX CY] [--smooth] [--bones] [--rotations] [--drain]
 --fps F (a float or NUM/DEN): microseconds per PUSH of StreamSession(fps=F) -- one source frame in, one pose out, on average
 model_fps / F sub-ticks -- next to the plain session pushed at the model's rate (the cost of one model tick); the lookahead is raised to
 the smallest one the rate allows.  The numpy baseline is left out.
 --out_fps G (with --fps): the push of StreamSession(fps=F, out_fps=G) -- every due pose per push, up to ceil(G / F) -- as out_fps_graph_us,
 next to the fps-only push (one pose per push) and the plain session.
+--interpolation cubic (with --fps, with or without --out_fps): the push of StreamSession(fps=F[, out_fps=G], interpolation="cubic") -- the
+emit reads four ring rows in place of two, at the cubic's own smallest lookahead -- as cubic_graph_us beside the linear session of the same
+rates in the same process (fps_graph_us / out_fps_graph_us); cubic_minus_linear_us is the difference of the two medians.  Informational.
 --repair_joints G [--missing_joints P] (not with --fps): the tick of StreamSession(repair_joints=G) as repair_graph_us -- per-joint flags
 with a share P (default 0.1) of the joints unobserved, K = G // s_in + 2 frames of spatial features per slot and tick -- next to the
 tick of StreamSession(missed_detections=True) fed the same frames with the per-frame flags those joints imply (md_graph_us).  The numpy
@@ -54,6 +57,7 @@ def main():
     ap.add_argument("--lookahead", type=int, default=0)
     ap.add_argument("--fps", default=None)
     ap.add_argument("--out_fps", default=None)
+    ap.add_argument("--interpolation", default="linear", choices=("linear", "cubic"))
     ap.add_argument("--repair_joints", type=int, default=None)
     ap.add_argument("--missing_joints", type=float, default=0.1)
     ap.add_argument("--detections", type=int, default=None)
@@ -79,6 +83,8 @@ def main():
         ap.error("--detections is not measured together with --fps / --repair_joints")
     if args.out_fps is not None and args.fps is None:
         ap.error("--out_fps needs --fps")
+    if args.interpolation == "cubic" and args.fps is None:
+        ap.error("--interpolation cubic needs --fps")
     import numpy as np, torch
     import uplift_upsample_3dhpe_amd as pkg
     from uplift_upsample_3dhpe_amd import synthetic as util
@@ -278,6 +284,12 @@ def main():
                     out_plan = stream.rate_plan(cfg, args.fps, la, ms, out_fps=args.out_fps)
                     row.update(out_fps=args.out_fps, max_out=out_plan.max_out, key_ring=out_plan.D)
                     variants = (("out_fps_graph", lambda: session(True, fps=args.fps, out_fps=args.out_fps, lookahead=la)),) + variants
+                if args.interpolation == "cubic":
+                    cubic_la = max(args.lookahead, stream.rate_plan(cfg, args.fps, None, ms, out_fps=args.out_fps, interpolation="cubic").min_lookahead)
+                    cubic_plan = stream.rate_plan(cfg, args.fps, cubic_la, ms, out_fps=args.out_fps, interpolation="cubic")
+                    row.update(interpolation="cubic", cubic_lookahead=cubic_la, cubic_model_lookahead=cubic_plan.a_m, cubic_key_ring=cubic_plan.D)
+                    variants = (("cubic_graph", lambda: session(True, fps=args.fps, lookahead=cubic_la, interpolation="cubic",
+                                                                **({} if args.out_fps is None else {"out_fps": args.out_fps}))),) + variants
             if args.repair_joints is not None:
                 row.update(repair_joints=args.repair_joints, missing_joints=args.missing_joints,
                            staged_frames=stream.staged_frames(args.repair_joints, ms))
@@ -309,6 +321,8 @@ def main():
                 row["push_over_model_tick"] = round(row["fps_graph_us"] / row["graph_us"], 2)
                 if args.out_fps is not None:
                     row["out_fps_minus_fps_us"] = round(row["out_fps_graph_us"] - row["fps_graph_us"], 1)
+                if args.interpolation == "cubic":
+                    row["cubic_minus_linear_us"] = round(row["cubic_graph_us"] - row["fps_graph_us" if args.out_fps is None else "out_fps_graph_us"], 1)
             row["device"] = torch.cuda.get_device_name(0)
             print(json.dumps(row), flush=True)
             results.append(row)

@@ -51,6 +51,7 @@ EXPORTED_SYMBOLS = (
     "uu3d_bone_lengths", "uu3d_fix_bones", "uu3d_stream_bones_bytes", "uu3d_stream_bones", "uu3d_stream_bones_reset",
     "uu3d_joint_rotations", "uu3d_joint_rotations_reset",
     "uu3d_assemble_tracks_cubic",
+    "uu3d_stream_timed_emit_cubic", "uu3d_stream_timed_emit_multi_cubic",
 )
 # include/uu3d_ops.h
 OPS_SYMBOLS = (
@@ -266,6 +267,8 @@ def load_library(path=None):
     lib.uu3d_stream_file_keyframe.argtypes = [vp, scfg, srate, vp, vp, vp]
     lib.uu3d_stream_timed_emit.restype = C.c_int
     lib.uu3d_stream_timed_emit.argtypes = [vp, scfg, srate, vp, vp, vp, vp]
+    lib.uu3d_stream_timed_emit_cubic.restype = C.c_int
+    lib.uu3d_stream_timed_emit_cubic.argtypes = [vp, scfg, srate, vp, vp, vp, vp]
     lib.uu3d_stream_rate_reset.restype = C.c_int
     lib.uu3d_stream_rate_reset.argtypes = [vp, scfg, srate, vp, vp, vp]
     sout = C.POINTER(Uu3dStreamOut)
@@ -273,6 +276,8 @@ def load_library(path=None):
     lib.uu3d_stream_out_state_layout.argtypes = [vp, scfg, srate, sout, C.POINTER(Uu3dStreamOutLayout)]
     lib.uu3d_stream_timed_emit_multi.restype = C.c_int
     lib.uu3d_stream_timed_emit_multi.argtypes = [vp, scfg, srate, sout, vp, vp, vp, vp]
+    lib.uu3d_stream_timed_emit_multi_cubic.restype = C.c_int
+    lib.uu3d_stream_timed_emit_multi_cubic.argtypes = [vp, scfg, srate, sout, vp, vp, vp, vp]
     lib.uu3d_stream_out_reset.restype = C.c_int
     lib.uu3d_stream_out_reset.argtypes = [vp, scfg, srate, sout, vp, vp, vp]
     lib.uu3d_stream_repair_bytes.restype = sz

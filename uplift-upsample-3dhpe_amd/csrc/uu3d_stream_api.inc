@@ -329,6 +329,18 @@ int uu3d_stream_timed_emit(uu3d_model* m, const uu3d_stream_config* s, const uu3
     return launched(m, "uu3d_stream_timed_emit");
 }
 
+int uu3d_stream_timed_emit_cubic(uu3d_model* m, const uu3d_stream_config* s, const uu3d_stream_rate* r, void* state, float* out, uint8_t* fresh_out,
+                                 void* stream) {
+    if (!m) return UU3D_ERR_INVALID_ARGUMENT;
+    StreamCall c;
+    if (const int st = stream_resolve(m, s, r, nullptr, state, kStreamRate | kStreamState, "uu3d_stream_timed_emit_cubic", c)) return st;
+    if (!out || !fresh_out || ((uintptr_t)out & 15) != 0) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_timed_emit_cubic: out (16-byte aligned) and fresh_out must be given");
+    hipLaunchKernelGGL(stream_timed_emit_cubic_kernel, blocks_of(((long)s->slots * c.L.per_pose + 3) / 4), dim3(256), 0, (hipStream_t)stream,
+                       c.rate, (const int32_t*)(c.base + c.R.off_source_frames), (const uint8_t*)(c.base + c.R.off_pushed),
+                       (const float*)(c.base + c.R.off_keys), (float*)(c.base + c.R.off_out_held), out, fresh_out);
+    return launched(m, "uu3d_stream_timed_emit_cubic");
+}
+
 namespace {
 // uu3d_stream_rate_reset and uu3d_stream_out_reset (with_out), behind their checks: one launch over the chosen slots
 int stream_rate_reset(uu3d_model* m, const uu3d_stream_config* s, const StreamCall& c, const bool with_out, const uint8_t* slot_mask, void* stream,
@@ -369,6 +381,18 @@ int uu3d_stream_timed_emit_multi(uu3d_model* m, const uu3d_stream_config* s, con
                        (const int32_t*)(c.base + c.R.off_source_frames), (const uint8_t*)(c.base + c.R.off_pushed), (const float*)(c.base + c.R.off_keys),
                        (int32_t*)(c.base + out_frames_offset(c.R)), poses, count);
     return launched(m, "uu3d_stream_timed_emit_multi");
+}
+
+int uu3d_stream_timed_emit_multi_cubic(uu3d_model* m, const uu3d_stream_config* s, const uu3d_stream_rate* r, const uu3d_stream_out* o, void* state,
+                                       float* poses, int32_t* count, void* stream) {
+    if (!m) return UU3D_ERR_INVALID_ARGUMENT;
+    StreamCall c;
+    if (const int st = stream_resolve(m, s, r, o, state, kStreamRate | kStreamState | kStreamOut, "uu3d_stream_timed_emit_multi_cubic", c)) return st;
+    if (!poses || !count || ((uintptr_t)poses & 15) != 0) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_stream_timed_emit_multi_cubic: poses (16-byte aligned) and count must be given");
+    hipLaunchKernelGGL(stream_timed_emit_multi_cubic_kernel, dim3(s->slots), dim3(256), 0, (hipStream_t)stream, c.rate, c.out,
+                       (const int32_t*)(c.base + c.R.off_source_frames), (const uint8_t*)(c.base + c.R.off_pushed), (const float*)(c.base + c.R.off_keys),
+                       (int32_t*)(c.base + out_frames_offset(c.R)), poses, count);
+    return launched(m, "uu3d_stream_timed_emit_multi_cubic");
 }
 
 int uu3d_stream_out_reset(uu3d_model* m, const uu3d_stream_config* s, const uu3d_stream_rate* r, const uu3d_stream_out* o, void* state,

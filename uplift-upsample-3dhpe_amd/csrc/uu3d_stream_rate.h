@@ -10,7 +10,9 @@
 //                                 piecewise-linear motion through the kept keyframes (evaluation.keyframe_plan_at's rule)
 // and, for a session with an output rate of its own (StreamSession(fps=F, out_fps=G)), in place of stream_timed_emit_kernel:
 //   stream_timed_emit_multi_kernel  once per push: EVERY output frame that became due at this push, up to R = ceil(G / F) poses per slot
-// Both read a pose from the kept keyframes with keyframe_read.  For either kind of session:
+// Both read a pose from the kept keyframes with keyframe_read.  A session with interpolation="cubic" launches
+//   stream_timed_emit_cubic_kernel / stream_timed_emit_multi_cubic_kernel
+// in their places: the same launches reading through keyframe_read_cubic, the C1 cubic through four kept keyframes.  For either kind of session:
 //   stream_rate_reset_kernel      chosen slots: every counter 0 (model, source, output), both held poses 0
 // The new state lies behind the plain session's (StreamLayout) in the same caller-allocated block.  No atomics, one writer per output
 // element, every counter is read and advanced on the device, all arguments are the same at every push: a sub-tick in which no slot is due
@@ -265,6 +267,96 @@ stream_timed_emit_multi_kernel(const RateParams p, const OutParams o, const int3
             const long r = rel / per;
             if (r >= n) continue;
             v[k] = keyframe_read(ring, p.key_ring, p.key_stride, p.pred_stride, (done + r) * o.un, o.ud, (int)(rel - r * per));
+        }
+        if (e0 >= start && e0 + 4 <= end) *reinterpret_cast<float4*>(poses + e0) = make_float4(v[0], v[1], v[2], v[3]);
+        else for (int k = 0; k < 4; ++k) if (e0 + k >= start && e0 + k < end) poses[e0 + k] = v[k];
+    }
+}
+
+// LIVE C1 MOTION (StreamSession(fps=F, interpolation="cubic")): keyframe_read with the C1 cubic through the kept keyframes in place of the
+// line (rates.push_plan_cubic on the host; evaluation.interpolate_cubic_host is the rule).  u == k0 gives keyframe k0's bits as before;
+// anything else hermite_mix (uu3d_tracks.h: float64, no contraction, rounded once) of the four ring places (k0 / P - 1) .. (k0 / P + 2)
+// modulo the ring with keyframe_read's own weight.  A slot's first segment (k0 < P) has no keyframe in front: its place is not read -- it
+// may hold a pose of the slot's previous track -- and the tangent at k0 is the segment's own difference.  A live track has no last
+// segment: k0 + 2 P always counts, and the host's plan (rates.rate_plan(interpolation="cubic")) guarantees that it has been emitted and
+// that k0 - P is still in the ring.
+__device__ __forceinline__ float keyframe_read_cubic(const float* __restrict__ ring, const int key_ring, const int key_stride, const long P,
+                                                     const long num, const long den, const int col)
+{
+    const long k0 = num / den / P * P;
+    const long off = num - k0 * den;                                      // (u - k0) den, in [0, P den)
+    const long i1 = k0 / P;
+    const float p1 = ring[i1 % key_ring * key_stride + col];
+    if (off == 0) return p1;
+    const bool has0 = k0 >= P;                                            // (then i1 >= 1: the place below is not negative)
+    const float p0 = has0 ? ring[(i1 - 1) % key_ring * key_stride + col] : p1;
+    const float p2 = ring[(i1 + 1) % key_ring * key_stride + col];
+    const float p3 = ring[(i1 + 2) % key_ring * key_stride + col];
+    return hermite_mix(p0, p1, p2, p3, has0, true, (double)off / (double)(P * den));
+}
+
+// stream_timed_emit_kernel with keyframe_read_cubic: the same arguments, the same held pose and fresh_out, one thread per four
+// consecutive floats.
+static __global__ void __launch_bounds__(256)
+stream_timed_emit_cubic_kernel(const RateParams p, const int32_t* __restrict__ source_frames, const uint8_t* __restrict__ pushed,
+                               const float* __restrict__ keys, float* __restrict__ out_held, float* __restrict__ out, uint8_t* __restrict__ fresh_out)
+{
+    const long per = p.per_pose, total = (long)p.slots * per;
+    const long e0 = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (e0 >= total) return;
+    float v[4];
+    bool any_fresh = false;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const long e = (e0 + k < total) ? e0 + k : e0;
+        const long t = e / per;
+        const int r = (int)(e - t * per);
+        const long q = (long)source_frames[t] - 1 - p.lookahead;
+        const bool is_fresh = pushed[t] != 0 && q >= 0;
+        if (e == e0 + k && r == 0) fresh_out[t] = is_fresh ? 1 : 0;
+        if (!is_fresh) { v[k] = out_held[e]; continue; }
+        any_fresh = true;
+        v[k] = keyframe_read_cubic(keys + t * p.key_ring * p.key_stride, p.key_ring, p.key_stride, p.pred_stride, q * p.a, p.b, r);
+    }
+    if (e0 + 4 <= total) {
+        *reinterpret_cast<float4*>(out + e0) = make_float4(v[0], v[1], v[2], v[3]);
+        if (any_fresh) *reinterpret_cast<float4*>(out_held + e0) = make_float4(v[0], v[1], v[2], v[3]);
+    } else for (int k = 0; e0 + k < total; ++k) { out[e0 + k] = v[k]; if (any_fresh) out_held[e0 + k] = v[k]; }
+}
+
+// stream_timed_emit_multi_kernel with keyframe_read_cubic: the same arguments, one workgroup per slot, the same counter discipline (read
+// by the slot's workgroup, advanced by lane 0 behind the barrier, stopped at INT32_MAX), the same zero rows behind count and the same walk
+// over the 16-byte quads of the slot's rows.
+static __global__ void __launch_bounds__(256)
+stream_timed_emit_multi_cubic_kernel(const RateParams p, const OutParams o, const int32_t* __restrict__ source_frames, const uint8_t* __restrict__ pushed,
+                                     const float* __restrict__ keys, int32_t* __restrict__ out_frames, float* __restrict__ poses,
+                                     int32_t* __restrict__ count)
+{
+    const int slot = blockIdx.x;
+    const long done = out_frames[slot];
+    const long q = (long)source_frames[slot] - 1 - p.lookahead;
+    long n = 0;
+    if (pushed[slot] != 0 && q >= 0 && done >= 0) {
+        n = q * o.c / o.d + 1 - done;
+        n = n < 0 ? 0 : (n > o.max_out ? o.max_out : n);
+        if (n > (long)INT32_MAX - done) n = (long)INT32_MAX - done;
+    }
+    __syncthreads();                                                     // every read of the counter is done
+    if (threadIdx.x == 0) { out_frames[slot] = (int32_t)(done + n); count[slot] = (int32_t)n; }
+    const long per = p.per_pose;
+    const long start = (long)slot * o.max_out * per, end = start + (long)o.max_out * per;
+    const float* ring = keys + (long)slot * p.key_ring * p.key_stride;
+    for (long quad = start / 4 + threadIdx.x; quad * 4 < end; quad += 256) {
+        const long e0 = quad * 4;
+        float v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            v[k] = 0.f;
+            const long rel = e0 + k - start;
+            if (rel < 0 || e0 + k >= end) continue;
+            const long r = rel / per;
+            if (r >= n) continue;
+            v[k] = keyframe_read_cubic(ring, p.key_ring, p.key_stride, p.pred_stride, (done + r) * o.un, o.ud, (int)(rel - r * per));
         }
         if (e0 >= start && e0 + 4 <= end) *reinterpret_cast<float4*>(poses + e0) = make_float4(v[0], v[1], v[2], v[3]);
         else for (int k = 0; k < 4; ++k) if (e0 + k >= start && e0 + k < end) poses[e0 + k] = v[k];

@@ -13,7 +13,7 @@ from .validity import check_repair_joints
 
 # cameras: (count, 4) float64 or None; min_root_joints: the checked int (a session without a camera: None); pose_filter / root_filter: a
 # ``OneEuro`` or None each; rigid: None or (skeleton, (count, J) lengths or None for "track"); keypoints: a ``KeypointMap`` or None;
-# rotations: a ``Rotations`` or None; interpolation: "linear" or "cubic" (a session is always "linear": live sessions have no such option)
+# rotations: a ``Rotations`` or None; interpolation: "linear" or "cubic" (of the offline call; a session checks its own with ``check_interpolation``)
 StageOptions = collections.namedtuple("StageOptions", "cameras min_root_joints pose_filter root_filter rigid keypoints rotations interpolation")
 INTERPOLATIONS = ("linear", "cubic")
 
@@ -21,7 +21,8 @@ OUT_FPS_NEEDS_FPS = {"track": "out_fps needs fps: the rate the tracks were filme
 
 
 def check_interpolation(interpolation):
-    """``predict_tracks(interpolation=...)``: how a returned frame between two predicted ones is read -> the checked name."""
+    """``predict_tracks(interpolation=...)`` / ``StreamSession(interpolation=...)``: how a returned frame between two predicted ones is
+    read -> the checked name."""
     if not isinstance(interpolation, str) or interpolation not in INTERPOLATIONS:
         raise ValueError(f"interpolation must be one of {', '.join(repr(n) for n in INTERPOLATIONS)}, got {interpolation!r}")
     return interpolation
@@ -34,7 +35,7 @@ def stage_options(config, count, per, root_relative, keypoints, camera, min_root
     ``min_root_joints``: a session passes None for "not given" -- the default with a camera, and anything else without one is refused (it
     is a parameter of the root solve); the offline call has the default in its signature and passes what it got.
     ``repair_joints`` is checked for its type only: whether it has the ``valid`` it needs is the caller's to say.
-    ``interpolation``: offline only (``check_interpolation``); a session does not pass it."""
+    ``interpolation``: the offline call's (``check_interpolation``); a session does not pass it here and checks its own."""
     interpolation = check_interpolation(interpolation)
     pose_filter, root_filter = check_smooth(smooth, camera is not None)
     if per == "slot":

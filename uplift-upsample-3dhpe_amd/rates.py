@@ -210,11 +210,62 @@ def _output_ring_depth(A, B, c, d, un, ud, P, lookahead, a_m, period):
     return 1 + int(((newest - k0_lo) // P)[due].max()), int((newest - k1_hi)[due].min())
 
 
+def _output_reads_cubic(A, B, c, d, un, ud, P, period):
+    """What the pushes q + lookahead, q = 0 .. period, of a cubic session with an output rate read, in numpy int64 -> (due, oldest,
+    newest): a mixed output frame (off != 0) reads keyframes k0 - P .. k0 + 2 P, one on a keyframe k0 alone.  Of the frames i_lo .. i_hi
+    of a push the oldest read is that of i_lo or of i_lo + 1 (a mixed frame just behind a keyframe), the newest that of i_hi or of
+    i_hi - 1.  ``oldest`` is not clamped at 0: the one-sided first segment reads less, and the value is the one a period later."""
+    q = np.arange(period + 1, dtype=np.int64)
+    hi = q * c // d
+    lo = np.where(q == 0, 0, (q - 1) * c // d + 1)
+    due = hi >= lo
+
+    def reads(i):
+        k0, _, off, _ = keyframe_bracket(i * un, ud, P)
+        mixed = off != 0
+        return k0 - P * mixed, k0 + 2 * P * mixed
+    oldest = np.minimum(reads(lo)[0], reads(np.minimum(lo + 1, hi))[0])
+    newest = np.maximum(reads(hi)[1], reads(np.maximum(hi - 1, lo))[1])
+    return due, oldest, newest
+
+
 RatePlan = collections.namedtuple("RatePlan", "A B n_max a_m D min_lookahead pred_stride lookahead out_c out_d pos_num pos_den max_out",
                                   defaults=(None, None, None, None, None))
 
 
-def rate_plan(config, fps, lookahead, mask_stride=None, model_fps=50, out_fps=None):
+def _rate_plan_cubic(config, fps, lookahead, A, B, P, keys, out):
+    """``rate_plan(interpolation="cubic")`` behind its checks.  ``keys``: ``keyframe_bracket`` of the source frames of one period B P;
+    ``out``: () or (c, d, un, ud, R, common period) of the output rate."""
+    if out:
+        due, oldest, need = _output_reads_cubic(A, B, *out[:4], P, out[5])
+        pushes = np.arange(out[5] + 1, dtype=np.int64)
+        oldest, need, pushes = oldest[due], need[due], pushes[due]
+    else:                                                             # (a mixed pose reads k0 - P .. k1 + P = k0 + 2 P, a keyframe k0 alone)
+        oldest = np.array([k[0] - P * (k[2] != 0) for k in keys], np.int64)
+        need = np.array([k[1] + P * (k[2] != 0) for k in keys], np.int64)
+        pushes = np.arange(len(keys), dtype=np.int64)
+
+    def slack(L):                                                      # min over one period of K(q + L) - the newest keyframe read
+        return int((newest_model_frame(pushes + L, A, B) - need).min())
+    min_lookahead = 0
+    while slack(min_lookahead) < 0:
+        min_lookahead += 1
+    lookahead = min_lookahead if lookahead is None else int(lookahead)
+    if lookahead < min_lookahead:
+        raise ValueError(f"lookahead {lookahead} is too small at {frame_rate(fps)} fps with interpolation=\"cubic\": a pose between two model "
+                         f"keyframes {P} model frames apart is read from the cubic through four of them, one behind the pair, and the "
+                         f"cubic's minimum is a lookahead of at least {min_lookahead} source frames")
+    a_m = min(max_lookahead(config), slack(lookahead))
+    newest = (newest_model_frame(pushes + lookahead, A, B) - a_m) // P * P
+    if int((newest - need).min()) < 0:
+        raise AssertionError("a pose due at a push reads a keyframe that has not been emitted")
+    D = 1 + int(((newest - oldest) // P).max())
+    if D > 4096:
+        raise ValueError(f"lookahead {lookahead} would keep {D} keyframes per slot; at most 4096")
+    return RatePlan(A, B, -(-A // B), a_m, D, min_lookahead, P, lookahead, *out[:5])
+
+
+def rate_plan(config, fps, lookahead, mask_stride=None, model_fps=50, out_fps=None, interpolation="linear"):
     """The plan of ``StreamSession(fps=fps, lookahead=lookahead)`` -> RatePlan(A, B, n_max, a_m, D, min_lookahead, pred_stride, lookahead,
     ...); integers and ``Fraction`` only.  A / B = model_fps / fps in lowest terms; n_max = ceil(A / B), the most model frames one push makes;
     a_m the model lookahead and D the places of the keyframe ring (``stream``'s module docstring), both by exact enumeration over one
@@ -225,7 +276,17 @@ def rate_plan(config, fps, lookahead, mask_stride=None, model_fps=50, out_fps=No
     unchanged -- an output frame due at a push is never later than the push's source frame q -- and D is enumerated over one common
     period of the source frames, the output frames and the keyframes (an lcm of Fractions), the oldest output frame of every push
     included; the enumeration also checks the claim about a_m.  ValueError, naming the quantity: more than 2^24 source frames per
-    period, a term of out_fps / fps or of model_fps / out_fps >= 2^20, more than 64 poses per push."""
+    period, a term of out_fps / fps or of model_fps / out_fps >= 2^20, more than 64 poses per push.
+    ``interpolation="cubic"`` (``StreamSession(interpolation="cubic")``; "linear": everything above, unchanged): a pose between two
+    keyframes is read from the C1 cubic through FOUR of them, k0 - P (none in a slot's first segment), k0, k1 and k1 + P
+    (``evaluation.interpolate_cubic_host``); a pose on a keyframe still reads k0 alone.  Two requirements change, both enumerated the same
+    way.  The newest emitted centre must reach k1 + P wherever the position is not a keyframe: min_lookahead and a_m come from that slack
+    -- without ``out_fps`` over the source frames of one period B P, with it over the output frames of every push of one common period,
+    because an output frame just in front of a source frame that sits on a keyframe needs the keyframe behind it (the ValueError names
+    the new minimum as the cubic's).  And the ring keeps k0 - P of the oldest pose a push reads: D is one deeper wherever that read
+    decides it.  The fields are the same; the session remembers the interpolation itself."""
+    from .options import check_interpolation                       # (options imports the stage modules, which import this one)
+    cubic = check_interpolation(interpolation) == "cubic"
     rho = frame_rate(model_fps) / frame_rate(fps)
     A, B = rho.numerator, rho.denominator
     if max(A, B) >= 2 ** 20:
@@ -250,6 +311,8 @@ def rate_plan(config, fps, lookahead, mask_stride=None, model_fps=50, out_fps=No
         out = (c, d, un, ud, R, int(span))
     period = B * P
     keys = [keyframe_bracket(q * A, B, P) for q in range(period)]
+    if cubic:
+        return _rate_plan_cubic(config, fps, lookahead, A, B, P, keys, out)
 
     def slack(L):                                                      # min over one period of K(q + L) - k1(q)
         return min(newest_model_frame(q + L, A, B) - k[1] for q, k in enumerate(keys))
@@ -306,3 +369,22 @@ def out_push_plan(j, plan):
         k0, k1, off, den = keyframe_bracket(i * plan.pos_num, plan.pos_den, plan.pred_stride)
         frames.append((i, k0, k1, float(np.float64(off) / np.float64(den))))
     return frames
+
+
+def push_plan_cubic(j, plan):
+    """``push_plan`` for a session with ``interpolation="cubic"`` (``plan``: ``rate_plan(..., interpolation="cubic")``): the same dict
+    plus "before" and "after", the two outer keyframes of ``evaluation.interpolate_cubic_host`` as model frames -- k0 - P and k1 + P;
+    None where there is none (before: the slot's first segment, k0 == 0) and wherever k0 == k1 (a keyframe's own bits, or no pose yet)."""
+    pp = push_plan(j, plan)
+    P = plan.pred_stride
+    mixed = pp["q"] is not None and pp["k0"] != pp["k1"]
+    pp["before"] = pp["k0"] - P if mixed and pp["k0"] >= P else None
+    pp["after"] = pp["k1"] + P if mixed else None
+    return pp
+
+
+def out_push_plan_cubic(j, plan):
+    """``out_push_plan`` for a session with ``interpolation="cubic"``: [(i, before, k0, k1, after, weight), ...] -- ``out_push_plan``'s
+    frames with the two outer keyframes as in ``push_plan_cubic``."""
+    P = plan.pred_stride
+    return [(i, k0 - P if k0 != k1 and k0 >= P else None, k0, k1, k1 + P if k0 != k1 else None, w) for i, k0, k1, w in out_push_plan(j, plan)]

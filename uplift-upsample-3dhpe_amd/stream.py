@@ -57,6 +57,24 @@ poses a second, five per push.  Input and model sides, ``lookahead`` (SOURCE fra
           frame is later than source frame q -- which the enumeration checks as well (``rate_plan``, ``out_push_plan``).
 One launch (uu3d_stream_timed_emit_multi) in place of uu3d_stream_timed_emit; ``out_fps=None`` is the session above, bit for bit.
 
+Live C1 motion -- ``StreamSession(..., fps=F, interpolation="cubic")``, with or without ``out_fps``: the poses of the two sessions above
+read from the C1 Catmull-Rom cubic through the emitted keyframes in place of the line, as ``predict_tracks(interpolation="cubic")`` reads
+them offline; the velocity of the returned motion no longer jumps at every keyframe.  One rule everywhere (``rates.keyframe_bracket``,
+``evaluation.interpolate_cubic_host``; ``rates.push_plan_cubic`` / ``out_push_plan_cubic`` are the host mirrors):
+  rule    k0, k1 and the weight w as above.  u == k0 gives keyframe k0's bits.  Anything else is the Hermite segment from keyframe k0 to
+          keyframe k1 at t = w whose tangents come from keyframe k0 - P (a slot's first segment, k0 == 0, has none and takes the
+          segment's own difference, as the offline rule does at a track's first segment) and keyframe k1 + P (always: a live track has no
+          last segment, and ``finish`` stays refused with ``fps``): float64 on the float32 keyframes, every operation rounded, no fused
+          multiply-add, rounded once to float32 -- the device equals numpy bit for bit.  The root joint of a root-relative pose stays 0.
+  plan    ``rate_plan(..., interpolation="cubic")``: the newest emitted centre must reach k1 + P wherever a pose is not on a keyframe, so
+          the smallest ``lookahead`` rises (ValueError naming the cubic's minimum) and a_m falls; with ``out_fps`` that slack is taken
+          over the output frames of every push, because a frame just in front of a source frame that sits on a keyframe needs the
+          keyframe behind it.  The ring keeps k0 - P of the oldest pose a push reads: D grows, through ``rate->key_ring`` alone.
+  launch  uu3d_stream_timed_emit_cubic / uu3d_stream_timed_emit_multi_cubic in place of the linear emit, a plain launch as before; the
+          ring, the state, the sub-tick graph (``captures`` stays 1), the resets and everything appended behind the emit (bones, root
+          solve, filters, rotations: they read the buffer it wrote) are unchanged.  ``interpolation="linear"`` is the session above, bit for
+          bit.  Without ``fps``: ValueError -- a plain session holds the previous pose between keyframes.
+
 The options of a session, one stage module each -- what the option does live, its launches in the tick and its host mirror stand in the
 module's docstring; every name is importable from here as before:
     validity.py   live per-joint missed detections: ``StreamSession(..., repair_joints=G)`` (``LiveRepairHost``, ``MAX_LIVE_REPAIR``)
@@ -101,10 +119,10 @@ from .associate import ASSOCIATION_DEFAULTS, check_association
 from .bones import Bones, LiveBonesHost, _bone_offsets, check_bones, fix_bones_host, skeleton_of  # noqa: F401
 from .cli import add_track_options, bones_option, input_joints, smooth_option, split_scores, track_keywords  # noqa: F401
 from .keypoints import KEYPOINT_PRESETS, check_keypoint_inputs, keypoint_map  # noqa: F401
-from .options import stage_options
+from .options import check_interpolation, stage_options
 from .predict import _load_model
-from .rates import (RatePlan, _rate_argument, frame_rate, max_lookahead, newest_model_frame, out_push_plan, push_plan,  # noqa: F401
-                    rate_plan, session_strides)
+from .rates import (RatePlan, _rate_argument, frame_rate, max_lookahead, newest_model_frame, out_push_plan, out_push_plan_cubic,  # noqa: F401
+                    push_plan, push_plan_cubic, rate_plan, session_strides)
 from .rotations import Rotations, check_rotations, joint_rotations_host  # noqa: F401
 from .roots import DEFAULT_MIN_ROOT_JOINTS, MAX_ROOT_JOINTS, LiveRootHost, check_cameras, check_min_root_joints, solve_roots_host  # noqa: F401
 from .smooth import (MAX_SMOOTH_CHANNELS, LiveOneEuro, LiveOneEuroHost, OneEuro, _live_filter_arguments, check_smooth,  # noqa: F401
@@ -188,7 +206,7 @@ def _live_options(options, who, names=LIVE_OPTIONS):
 class StreamSession(object):
 
     def __init__(self, model, config, slots, resolutions=None, mask_stride=None, flip=None, lookahead=0, root_relative=True, graph=True,
-                 missed_detections=False, fps=None, model_fps=50, out_fps=None, **options):
+                 missed_detections=False, fps=None, model_fps=50, out_fps=None, interpolation="linear", **options):
         """``slots``: tracks served side by side (a slot is a track: ``reset`` starts a new one).  ``resolutions``: None = the coordinates
         are normalised already, else one (w, h) in pixels or one per slot.  ``mask_stride`` / ``flip`` / ``root_relative`` as
         ``predict.predict_tracks``.  ``lookahead`` = a: frames the answer may lag behind the newest one, 0 <= a <=
@@ -211,6 +229,10 @@ class StreamSession(object):
         the session returns, parsed like ``fps`` (which it needs: ValueError without): the module docstring's "Live upsampling".  ``push``
         then returns (poses (slots, max_out, J, 3), count (slots,) int32), ``max_out`` = ceil(out_fps / fps) <= 64, and ``out_frames``
         counts the output frames per slot.
+        ``interpolation``: "linear" (the default: the sessions above, bit for bit -- the same launches, buffers and bits) or "cubic": the
+        module docstring's "Live C1 motion" -- with ``fps`` (ValueError without: a plain session holds the previous pose between keyframes,
+        there is nothing to interpolate), with or without ``out_fps``; ``lookahead`` must then be at least
+        ``rate_plan(..., interpolation="cubic").min_lookahead``, the cubic's own minimum.  ``s.interpolation`` tells which.
         ``repair_joints`` (keyword only, taken from ``options``; any other name there is a TypeError): None = a missing joint makes its frame missing (the session above, bit for bit).  Else G, an int in
         [1, ``MAX_LIVE_REPAIR``]: the module docstring's "Live per-joint missed detections".  Implies ``missed_detections=True``;
         ``push(valid=...)`` may then hold one flag per joint and ``joint_state`` tells what became of the newest frame's joints.  Not
@@ -247,7 +269,7 @@ class StreamSession(object):
          *rule) = _live_options(options, "StreamSession", LIVE_OPTIONS + DETECTION_OPTIONS)
         res = self._init_plan(model, config, slots, resolutions, mask_stride, flip, lookahead, graph, missed_detections, fps, model_fps, out_fps,
                               repair_joints, keypoints, detections, dict(zip(ASSOCIATION_DEFAULTS, rule)), camera, min_root_joints, smooth,
-                              bones=bones, root_relative=root_relative, rotations=rotations)
+                              bones=bones, root_relative=root_relative, rotations=rotations, interpolation=interpolation)
         import torch
         self._torch = torch
         self._lib = _capi.load_library()
@@ -264,7 +286,7 @@ class StreamSession(object):
     # ---- construction: checks and plan, layout and state, buffers, launch tables (then the capture) ---------------------------------
     def _init_plan(self, model, config, slots, resolutions, mask_stride, flip, lookahead, graph, missed_detections, fps, model_fps, out_fps,
                    repair_joints=None, keypoints=None, detections=None, rule=None, camera=None, min_root_joints=None, smooth=None, bones=None,
-                   root_relative=True, rotations=None):
+                   root_relative=True, rotations=None, interpolation="linear"):
         """Every refusal that needs no device, and the session's plan.  -> the checked resolutions."""
         slots, lookahead = int(slots), int(lookahead)
         if slots < 1:
@@ -273,6 +295,10 @@ class StreamSession(object):
         opts = stage_options(config, slots, "slot", root_relative, keypoints, camera, min_root_joints, smooth, bones, repair_joints, fps, out_fps,
                              rotations=rotations)
         self.rotations = opts.rotations
+        self.interpolation = check_interpolation(interpolation)
+        if self.interpolation == "cubic" and fps is None:
+            raise ValueError('interpolation="cubic" needs fps: a session without a frame rate holds the previous pose between keyframes, so there '
+                             'is nothing to interpolate')
         self.bones, self.pose_filter, self.root_filter, self.keypoints = opts.rigid, opts.pose_filter, opts.root_filter, opts.keypoints
         self.cameras, self.min_root_joints = opts.cameras, opts.min_root_joints
         self.smooth_rate = frame_rate(model_fps if fps is None else fps)     # the rate of the frames a push returns
@@ -308,7 +334,7 @@ class StreamSession(object):
             raise ValueError("repair_joints together with fps / out_fps is not supported yet: a revised source frame would re-make model frames "
                              "that were filed already")
         S, s_in, pred = session_strides(config, mask_stride)
-        self.rate = None if fps is None else rate_plan(config, fps, lookahead, mask_stride, model_fps, out_fps)
+        self.rate = None if fps is None else rate_plan(config, fps, lookahead, mask_stride, model_fps, out_fps, interpolation=self.interpolation)
         self.max_out = None if out_fps is None else self.rate.max_out
         if self.rate is None and not 0 <= lookahead <= max_lookahead(config):
             raise ValueError(f"lookahead must be in [0, {max_lookahead(config)}] = (SEQUENCE_LENGTH // 2) * SEQUENCE_STRIDE, got {lookahead}")
@@ -565,11 +591,14 @@ class StreamSession(object):
         if self.rate is not None:
             self._tick_steps.append((lib.uu3d_stream_file_keyframe, (h, cfg, rate, state, emit_fresh)))
             self._push_before = mapping + [(lib.uu3d_stream_source_push, (h, cfg, rate, state, kp, active, _ptr(self._valid_in), int(self.missed_detections)))]
-            self._push_after = [(lib.uu3d_stream_timed_emit, (h, cfg, rate, state, _ptr(self._out), _ptr(self._fresh)))]
+            cubic = self.interpolation == "cubic"                   # the C1 cubic through four kept keyframes: the emit's cubic sibling
+            self._push_after = [(lib.uu3d_stream_timed_emit_cubic if cubic else lib.uu3d_stream_timed_emit,
+                                 (h, cfg, rate, state, _ptr(self._out), _ptr(self._fresh)))]
             self._reset_call = (lib.uu3d_stream_rate_reset, (h, cfg, rate, state))
         if self.max_out is not None:
             outp = C.byref(self._outp)
-            self._push_after = [(lib.uu3d_stream_timed_emit_multi, (h, cfg, rate, outp, state, _ptr(self._poses), _ptr(self._count)))]
+            self._push_after = [(lib.uu3d_stream_timed_emit_multi_cubic if cubic else lib.uu3d_stream_timed_emit_multi,
+                                 (h, cfg, rate, outp, state, _ptr(self._poses), _ptr(self._count)))]
             self._reset_call = (lib.uu3d_stream_out_reset, (h, cfg, rate, outp, state))
         last = self._tick_steps if self.rate is None else self._push_after
         # constant bone lengths: directly behind the emit, in front of the root solve and the filters, which read its buffer
@@ -686,6 +715,8 @@ class StreamSession(object):
         valid until the next ``push``: rows r < count[i] of slot i are the output frames that became due at this push, oldest first (the
         first is output frame ``out_frames[i] - count[i]``), rows r >= count[i] are zeros; an inactive slot has count 0.
         uu3d_stream_timed_emit_multi takes uu3d_stream_timed_emit's place.
+        A session with ``interpolation="cubic"``: the same returns, read from the C1 cubic through the keyframes;
+        uu3d_stream_timed_emit_cubic / uu3d_stream_timed_emit_multi_cubic take the emit's place, still a plain launch.
         A session with ``camera``: -> (poses, fresh, roots (slots, 3) float32, root_state (slots,) uint8), the session's own buffers as
         well: ``poses[i] + roots[i]`` stands in the camera's space; ``root_state[i]``: 1 solved at this push, 2 the slot's last solved
         root is held, 0 no frame of the slot was solved yet (zeros).  A slot that is not fresh returns its previous root and state.
@@ -1122,7 +1153,7 @@ class StreamSession(object):
 
 
 def replay_tracks(model, config, tracks, resolutions=None, mask_stride=None, flip=None, lookahead=0, root_relative=True, graph=True, valid=None, fps=None,
-                  model_fps=50, out_fps=None, drain=False, **options):
+                  model_fps=50, out_fps=None, drain=False, interpolation="linear", **options):
     """Push complete tracks tick by tick, one slot per track (a slot is inactive once its track has ended) -> per track the pose the
     session returned at each of its ticks, (T_i, J, 3) float32, and the fresh flags (T_i,) bool, as host arrays.  One copy to the host,
     at the end.  ``valid`` as ``predict.predict_tracks``: None, "finite" (rows with a NaN / Inf coordinate are missing frames) or one (T_i,)
@@ -1139,7 +1170,8 @@ def replay_tracks(model, config, tracks, resolutions=None, mask_stride=None, fli
     returned at each tick are appended (with ``return_global`` the global ones behind them): one row per pushed frame.
     ``drain=True``: every slot is finished (``StreamSession.finish``) at the tick its own track ends, while the other slots go on; per
     track the arrays then have T_i + lookahead rows -- row t is the pose of frame t - lookahead (where it is fresh), so all T_i frames of
-    the track come out, as from ``predict_tracks``.  Still one copy to the host, at the end.  Not with ``fps`` / ``out_fps`` (ValueError)."""
+    the track come out, as from ``predict_tracks``.  Still one copy to the host, at the end.  Not with ``fps`` / ``out_fps`` (ValueError).
+    ``interpolation``: handed to ``StreamSession`` as it is ("cubic" needs ``fps``)."""
     if drain and (fps is not None or out_fps is not None):
         raise ValueError("drain=True together with fps / out_fps is not supported yet (a later change): the drain of a source-rate session "
                          "needs the end of the model-rate track")
@@ -1164,7 +1196,7 @@ def replay_tracks(model, config, tracks, resolutions=None, mask_stride=None, fli
     s = StreamSession(model, config, T, resolutions=resolutions, mask_stride=mask_stride, flip=flip, lookahead=lookahead,
                       root_relative=root_relative, graph=graph, missed_detections=valid is not None, fps=fps, model_fps=model_fps, out_fps=out_fps,
                       repair_joints=repair_joints, keypoints=keypoints, camera=camera, min_root_joints=min_root_joints, smooth=smooth, bones=bones,
-                      rotations=rotations)
+                      rotations=rotations, interpolation=interpolation)
     turned = 0 if s.rotations is None else 2 if s.rotations.return_global else 1          # quaternion buffers a push appends
     quats = [torch.zeros((ticks, T, J, 4), dtype=torch.float32, device=model.device) for _ in range(turned)]
     if camera is not None:                                           # per tick and slot four 32-bit words: the root's bits, the state
