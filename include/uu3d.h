@@ -660,6 +660,35 @@ int uu3d_root_trajectory(const double* roots_dev, const uint8_t* solved_dev, int
                          uint8_t* root_state_dev, void* scratch_dev, size_t scratch_bytes, void* stream);
 
 /*
+ * LENS DISTORTION (predict.undistort_points, predict.predict_tracks(camera=Camera(..., distortion=...)), predict.predict_detections,
+ * stream.StreamSession): the calls above read a camera as an ideal pinhole.  A real lens puts a keypoint near the image border tens of
+ * pixels from where a pinhole would; this call takes the raw pixels a detector saw back to the pixels a pinhole with the same intrinsics
+ * would have seen, on the device, in front of everything else that looks at a track (uu3d_map_keypoints included: an affine joint map does
+ * not commute with distortion).  predict.undistort_points_host is the same rule in numpy, bit for bit.  No accuracy is claimed.
+ * THE RULE, in float64, every operation rounded once, no fused multiply-add, one final rounding to float32.  A camera is ten doubles: fx,
+ * fy, cx, cy, then k1, k2, p1, p2, k3 in OpenCV's Brown-Conrady order, then tol in pixels.  For a raw point (u, v) widened from float32:
+ *     x0 = (u - cx) / fx    y0 = (v - cy) / fy    x = x0    y = y0
+ *     exactly 20 times, no early exit (the fixed-point iteration of OpenCV's undistortPoints):
+ *         r2 = x * x + y * y                                   ic = 1.0 / (1.0 + ((k3 * r2 + k2) * r2 + k1) * r2)
+ *         dx = 2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x)      dy = p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y
+ *         x = (x0 - dx) * ic                                   y = (y0 - dy) * ic
+ *     then r2, dx, dy once more from the final (x, y), rad = 1.0 + ((k3 * r2 + k2) * r2 + k1) * r2, xd = x * rad + dx, yd = y * rad + dy.
+ * The point is ACCEPTED iff u, v, x and y are finite, |xd - x0| * fx <= tol and |yd - y0| * fy <= tol, and the result, (fx * x + cx,
+ * fy * y + cy) rounded once to float32, is finite.  Any other point -- a non-finite input, an observation outside the region where the
+ * model can be inverted (with strong barrel distortion that region does not cover the plane), a camera with a non-finite intrinsic or
+ * fx <= 0 or fy <= 0 -- is (NaN, NaN), the quiet NaN 0x7fc00000: a lost joint for the finite tests of everything behind.
+ *
+ *   uu3d_undistort_points(in_dev (rows, points_per_row, 2) f32, out_dev the same shape, never in_dev, both 8-byte aligned, rows,
+ *       points_per_row, row_track_dev (rows) i32 or NULL = camera 0 for every row, num_tracks, cameras_dev (num_tracks, 10) f64, stream):
+ *       one launch, one lane per point, one 8-byte load and one 8-byte store.  rows == 0 is a no-op that returns UU3D_OK.  A track id out
+ *       of range writes NaN, nothing is read out of bounds.  The same arguments at every tick: it replays from a live tick's captured
+ *       graph, where it is the first launch (in_dev the staged push, out_dev a buffer of the session).
+ * Every output element has one writer, no atomics, in_dev is only read, nothing copies to the host or waits: bitwise repeatable.
+ */
+int uu3d_undistort_points(const float* in_dev, float* out_dev, int64_t rows, int32_t points_per_row, const int32_t* row_track_dev,
+                          int32_t num_tracks, const double* cameras_dev, void* stream);
+
+/*
  * ANY FRAME RATE (predict.predict_tracks(fps=...)): the front of YOUR OWN 2D TRACKS for tracks that were not filmed at the rate the model
  * was trained for.  The table holds the MODEL's time grid: row `row` (track row_track_dev[row]) is model frame k of its track, which sits at
  * source position p_k = k * fps / model_fps.  The host works the positions out in exact integer arithmetic (predict.resample_plan) and

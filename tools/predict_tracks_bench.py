@@ -33,9 +33,14 @@ medians (one more launch), host_rotations_ms the plain call followed by .cpu() o
 cubic_extra_ms is the difference of the two medians (uu3d_assemble_tracks_cubic in place of uu3d_assemble_tracks: four predictions read per
 interpolated value in place of two); every predicted frame must carry the linear call's bits (cubic_keyframe_bits_equal) and the frames between
 must not (cubic_max_abs_diff_to_linear).  Informational: no threshold.
+--distortion K1 K2 P1 P2 K3 (with --camera): also predict_tracks(camera=Camera(FX, FY, CX, CY, distortion=...)) on the tracks as that lens shows
+them (predict.distort_points_host) beside predict_tracks(camera=(FX, FY, CX, CY)) in the same process: distortion_extra_ms is the difference of
+the two medians (one more launch: uu3d_undistort_points in front of everything), host_distortion_ms the tuple's call with
+predict.undistort_points_host, the rule in numpy, in front of it; the two must agree bit for bit.  Informational: no threshold.
    python tools/predict_tracks_bench.py [--tracks 40] [--frames 2500] [--batch 512] [--reps 3] [--cases h36m_351:5,h36m_81:4] [--missing 0.3]
                                         [--fps 30] [--repair_joints 5 --missing_joints 0.1] [--keypoints coco17]
-                                        [--camera 1145 1145 960 540] [--smooth [--zero_lag]] [--bones] [--rotations] [--interpolation cubic]"""
+                                        [--camera 1145 1145 960 540] [--smooth [--zero_lag]] [--bones] [--rotations] [--interpolation cubic]
+                                        [--distortion -0.28 0.09 0.0005 -0.0003 -0.012]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -61,9 +66,13 @@ def main():
     ap.add_argument("--rotations", action="store_true", help="also time predict_tracks(rotations=True) against the plain call and against .cpu() and the numpy rule")
     ap.add_argument("--interpolation", choices=["linear", "cubic"], default="linear",
                     help='cubic: also time predict_tracks(interpolation="cubic") beside the plain (linear) call')
+    ap.add_argument("--distortion", type=float, nargs=5, default=None, metavar=("K1", "K2", "P1", "P2", "K3"),
+                    help="with --camera: also time predict_tracks(camera=Camera(..., distortion=...)) beside the call with the plain tuple")
     args = ap.parse_args()
     if args.zero_lag and not args.smooth:
         ap.error("--zero_lag is used together with --smooth")
+    if args.distortion is not None and args.camera is None:
+        ap.error("--distortion is used together with --camera")
     import numpy as np, torch
     import uplift_upsample_3dhpe_amd as pkg
     from uplift_upsample_3dhpe_amd import synthetic as util
@@ -87,6 +96,10 @@ def main():
         kpx = [(np.cumsum(rng.normal(0, 2.0, size=(args.frames, K, 2)), 0) + rng.uniform(0.25, 0.75, size=(1, K, 2)) * [W, H]).astype(np.float32)
                for _ in range(args.tracks)]
         kflags = [rng.random((args.frames, K)) >= args.missing_joints for _ in range(args.tracks)]
+    lens_camera = seen = None
+    if args.distortion is not None:                                     # the same tracks as the lens shows them to a detector
+        lens_camera = predict.Camera(*args.camera, distortion=args.distortion)
+        seen = [predict.distort_points_host(t, lens_camera).astype(np.float32) for t in px]
     reuse = not args.no_reuse
     fps = None if args.fps is None else predict.frame_rate(args.fps)
     results = []
@@ -167,6 +180,14 @@ def main():
             roots, solved = predict.solve_roots_host(poses, np.concatenate(px, 0), tuple(args.camera), lens=lens)
             return predict.root_trajectory_host(roots, solved, lens)
 
+        def distortion_path():
+            return predict.predict_tracks(model, cfg, seen, resolutions=(W, H), mask_stride=int(msv), flip=True, reuse_frames=reuse, batch_size=args.batch,
+                                          camera=lens_camera)
+
+        def distortion_host():
+            return predict.predict_tracks(model, cfg, predict.undistort_points_host(seen, lens_camera), resolutions=(W, H), mask_stride=int(msv),
+                                          flip=True, reuse_frames=reuse, batch_size=args.batch, camera=tuple(args.camera))
+
         def smooth_path():
             return predict.predict_tracks(model, cfg, px, resolutions=(W, H), mask_stride=int(msv), flip=True, reuse_frames=reuse, batch_size=args.batch,
                                           smooth=True, **({} if args.camera is None else {"camera": tuple(args.camera)}))
@@ -208,6 +229,9 @@ def main():
         if args.camera is not None:
             row["camera"] = list(args.camera)
             cases += [("predict_tracks_camera", camera_path), ("host_camera", camera_host)]
+        if lens_camera is not None:
+            row["distortion"] = list(args.distortion)
+            cases += [("predict_tracks_distortion", distortion_path), ("host_distortion", distortion_host)]
         if args.smooth:
             cases.append(("predict_tracks_smooth", smooth_path))
         if args.zero_lag:
@@ -250,6 +274,12 @@ def main():
             row["camera_bits_equal"] = bool(np.array_equal(roots.view(np.uint32), outs["host_camera"][0].view(np.uint32))
                                             and np.array_equal(state, outs["host_camera"][1]))
             row["camera_solved_frames"] = int((state == 1).sum())
+        if lens_camera is not None:
+            row["distortion_extra_ms"] = round(row["predict_tracks_distortion_ms"] - row["predict_tracks_camera_ms"], 1)
+            row["distortion_bits_equal"] = bool(all(torch.equal(torch.cat(a, 0).view(torch.int32) if a[0].dtype == torch.float32 else torch.cat(a, 0),
+                                                                torch.cat(b, 0).view(torch.int32) if b[0].dtype == torch.float32 else torch.cat(b, 0))
+                                                    for a, b in zip(outs["predict_tracks_distortion"], outs["host_distortion"])))
+            row["distortion_lost_points"] = int(sum(np.isnan(t).any(axis=2).sum() for t in predict.undistort_points_host(seen, lens_camera)))
         if args.smooth:
             base = "predict_tracks_camera" if args.camera is not None else "predict_tracks"
             row["smooth_extra_ms"] = round(row["predict_tracks_smooth_ms"] - row[base + "_ms"], 1)

@@ -6,7 +6,7 @@ Median (and 90th percentile) over --ticks ticks after --warmup ticks, per config
 A case is CONFIG:s_in, or generic:J,d_s,d_t,heads,N:s_in for a model with generic dims (e.g. --cases generic:25,16,64,4,27:4): its tick
 (the one-workgroup-per-frame spatial stack + the generic forward's second stage in the graph) beside the same baseline.
    python tools/stream_bench.py [--slots 1,8,64] [--cases h36m_81:4,h36m_351:5] [--ticks 300] [--warmup 60] [--lookahead 0] [--fps F [--out_fps G] [--interpolation cubic]]
-                                [--repair_joints G] [--detections D] [--camera FX FY CX CY] [--smooth] [--bones] [--rotations] [--drain]
+                                [--repair_joints G] [--detections D] [--camera FX FY CX CY [--distortion K1 K2 P1 P2 K3]] [--smooth] [--bones] [--rotations] [--drain]
 --fps F (a float or NUM/DEN): microseconds per PUSH of StreamSession(fps=F) -- one source frame in, one pose out, on average
 model_fps / F sub-ticks -- next to the plain session pushed at the model's rate (the cost of one model tick); the lookahead is raised to
 the smallest one the rate allows.  The numpy baseline is left out.
@@ -28,6 +28,10 @@ the HOST ROUTE a user takes without the option (host_route_us): the detections s
 tick, two more buffers returned -- as camera_graph_us next to the tick of the same session without camera (graph_us) on the same frames in
 the same process: both sessions are alive side by side and every tick is pushed into both, the order alternating from tick to tick.
 camera_minus_graph_us is the difference of the two medians.  The numpy baseline is left out.
+--distortion K1 K2 P1 P2 K3 (with --camera, not with the other options): the tick of StreamSession(camera=Camera(FX, FY, CX, CY, distortion=...))
+-- one more launch, uu3d_undistort_points, the first of the captured tick -- as distortion_graph_us next to the tick of the session with the
+plain tuple (camera_graph_us) on the same frames in the same process, measured side by side in the same way.  distortion_minus_camera_us is
+the difference of the two medians.  Informational: no threshold.  The numpy baseline is left out.
 --smooth (alone or with --camera, not with the other options): the tick of StreamSession(smooth=True) -- one more launch at the end of the
 captured tick, with --camera two (poses and roots) -- as smooth_graph_us next to the tick of the same session without smooth (graph_us;
 with --camera both sessions have the camera), measured side by side in the same way.  smooth_minus_graph_us is the difference of the two
@@ -62,6 +66,7 @@ def main():
     ap.add_argument("--missing_joints", type=float, default=0.1)
     ap.add_argument("--detections", type=int, default=None)
     ap.add_argument("--camera", type=float, nargs=4, metavar=("FX", "FY", "CX", "CY"), default=None)
+    ap.add_argument("--distortion", type=float, nargs=5, metavar=("K1", "K2", "P1", "P2", "K3"), default=None)
     ap.add_argument("--smooth", action="store_true")
     ap.add_argument("--bones", action="store_true")
     ap.add_argument("--rotations", action="store_true")
@@ -81,6 +86,8 @@ def main():
         ap.error("--repair_joints is not measured together with --fps")
     if args.detections is not None and (args.fps is not None or args.repair_joints is not None):
         ap.error("--detections is not measured together with --fps / --repair_joints")
+    if args.distortion is not None and (args.camera is None or args.smooth or args.bones or args.rotations):
+        ap.error("--distortion is measured with --camera alone")
     if args.out_fps is not None and args.fps is None:
         ap.error("--out_fps needs --fps")
     if args.interpolation == "cubic" and args.fps is None:
@@ -228,6 +235,9 @@ def main():
                     pair = {"bones_graph": new(bones="track", **place), "graph": new(**place)}
                 elif args.rotations:                                  # ... one with the launch at the tick's end, one followed by the host rule
                     pair = {"rotations_graph": new(rotations=True, **place), "graph": new(**place), "rotations_host": new(**place)}
+                elif args.distortion is not None:                     # both with the camera, one of them with the lens in front of the tick
+                    pair = {"distortion_graph": new(camera=stream.Camera(*args.camera, distortion=args.distortion)),
+                            "camera_graph": new(camera=tuple(args.camera))}
                 else:
                     pair = {"camera_graph": new(camera=tuple(args.camera)), "graph": new()}
                 ts = {key: [] for key in pair}
@@ -243,7 +253,7 @@ def main():
                     s.check_range()
                     s.close()
                 row.update(camera=None if args.camera is None else list(args.camera), smooth=bool(args.smooth), bones=bool(args.bones),
-                           rotations=bool(args.rotations))
+                           rotations=bool(args.rotations), **({} if args.distortion is None else {"distortion": list(args.distortion)}))
                 return tuple((key, lambda key=key: ts[key][args.warmup:]) for key in pair)
 
             if args.drain:
@@ -309,6 +319,8 @@ def main():
                 row["bones_minus_graph_us"] = round(row["bones_graph_us"] - row["graph_us"], 1)
             elif args.rotations:
                 row["rotations_minus_graph_us"] = round(row["rotations_graph_us"] - row["graph_us"], 1)
+            elif args.distortion is not None:
+                row["distortion_minus_camera_us"] = round(row["distortion_graph_us"] - row["camera_graph_us"], 1)
             elif args.camera is not None:
                 row["camera_minus_graph_us"] = round(row["camera_graph_us"] - row["graph_us"], 1)
             elif args.detections is not None:

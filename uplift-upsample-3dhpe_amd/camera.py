@@ -1,0 +1,225 @@
+"""The lens stage of the track pipeline: a camera with radial and tangential distortion (include/uu3d.h, LENS DISTORTION).  ``Camera``
+is what ``camera=`` takes beside a plain (fx, fy, cx, cy); wraps uu3d_undistort_points (``undistort_points``; the rule in numpy:
+``undistort_points_host``); ``distort_points_host`` is the forward model, for building inputs.
+
+Lens distortion -- ``predict_tracks(..., camera=Camera(fx, fy, cx, cy, distortion=(k1, k2, p1, p2, k3)))``: everything else in this package
+reads a camera as an ideal pinhole -- the root solve back-projects raw pixels through (u - cx) / fx, the network reads raw pixels scaled by
+the resolution.  A real lens puts a keypoint near the image border tens of pixels from where a pinhole would, and for a person off centre
+that goes straight into the root's depth and lateral position.  With a ``Camera`` that has distortion the given 2D points are taken back,
+on the device and before anything else looks at them, to the pixels a pinhole with the same intrinsics would have seen:
+uu3d_undistort_points is the FIRST launch of the call -- on the given frames in the detector's layout, in front of uu3d_map_keypoints (an
+affine joint map does not commute with distortion) -- and everything behind reads the undistorted points: the map, ``repair_joints``, the
+normalisation or resampling, and the root solve.  The caller's memory is never written.  ``predict_detections`` undistorts all D x K points
+of a frame before the association (one camera per video); ``StreamSession`` runs the launch as the first step of its one captured tick
+(with ``fps`` in front of uu3d_stream_source_push, with ``detections`` in front of the association), from the staged push into a buffer
+of the session: ``push`` still never waits and ``captures`` stays 1.  A point the rule does not accept comes back (NaN, NaN) and is a lost
+joint for the finite tests behind: ``valid="finite"`` (and ``repair_joints``) is the companion option offline, ``missed_detections=True``
+live; the root solve never uses it.  The result equals, bit for bit, the same call on ``undistort_points_host(tracks, camera)`` with
+``camera=(fx, fy, cx, cy)``.  A ``Camera`` without distortion (None, or all coefficients zero) is the plain tuple: the same launches,
+buffers and bits.  No accuracy is claimed: the mechanism is the feature."""
+import ctypes as C
+
+import numpy as np
+
+from . import _capi
+from ._capi import ptr as _ptr
+from .roots import _root_lens, check_cameras
+from .tracks import _host_array, _upload
+
+
+class Camera(object):
+    """A camera's intrinsics with lens distortion: ``Camera(fx, fy, cx, cy, distortion=(k1, k2, p1, p2, k3), tol=1e-3)``, in the units of
+    the 2D points as given (pixels).  The coefficients follow OpenCV's Brown-Conrady order and model, which is what a calibration tool
+    hands over (``cv2.calibrateCamera``'s ``distCoeffs``): with r2 = x x + y y on normalised coordinates,
+        xd = x (1 + k1 r2 + k2 r2^2 + k3 r2^3) + 2 p1 x y + p2 (r2 + 2 x x)      yd = y (...) + p1 (r2 + 2 y y) + 2 p2 x y.
+    Human3.6M's ``project_to_2d`` (and ``utils/h36m_cameras.json`` with it) uses a DIFFERENT tangential form -- with t = p1 x + p2 y it
+    is ``xd = x (radial + t) + p1 r2`` -- so its coefficients cannot be passed here as they are; converting them is out of scope.
+    ``distortion``: None or five finite numbers (anything else: ValueError); None and all zeros are "without distortion" -- the plain
+    tuple.  ``tol`` (finite, > 0): the largest re-distortion residual, in pixels, at which an undistorted point is accepted.
+    THE RULE (``undistort_points_host``; float64, every operation rounded once, one final rounding to float32) runs exactly ``ITERATIONS``
+    = 20 steps of OpenCV's fixed-point iteration with no early exit.  20 is a constant of the rule, not a measurement: on a 41 x 41 grid
+    over a 1920 x 1080 image at fx = 1145 the worst residual after 20 steps is 2.4e-9 normalised units (3e-6 px) for moderate
+    coefficient sets (k1 down to -0.35 at a normalised radius of 1.17) and still 9e-6 units after 10; the default ``tol`` of 1e-3 px sits
+    far above that noise and far below a detector's precision."""
+    ITERATIONS = 20
+
+    def __init__(self, fx, fy, cx, cy, distortion=None, tol=1e-3):
+        self.intrinsics = tuple(float(v) for v in check_cameras((fx, fy, cx, cy), 1, per="track")[0])
+        if distortion is None:
+            d = np.zeros(5, np.float64)
+        else:
+            try:
+                d = np.asarray(distortion, np.float64)
+            except (TypeError, ValueError):
+                raise ValueError(f"distortion must be five numbers (k1, k2, p1, p2, k3), got {distortion!r}") from None
+            if d.shape != (5,):
+                raise ValueError(f"distortion must be five numbers (k1, k2, p1, p2, k3), got shape {d.shape}")
+            if not np.isfinite(d).all():
+                raise ValueError("distortion must be finite (k1, k2, p1, p2, k3)")
+        try:
+            t = float(tol)
+        except (TypeError, ValueError):
+            raise ValueError(f"tol must be a finite number of pixels > 0, got {tol!r}") from None
+        if isinstance(tol, bool) or not np.isfinite(t) or not t > 0:
+            raise ValueError(f"tol must be a finite number of pixels > 0, got {tol!r}")
+        self.distortion, self.tol = d, t
+
+    @property
+    def has_distortion(self):
+        return bool((self.distortion != 0).any())
+
+    def row(self):
+        """The ten doubles of the device call: fx, fy, cx, cy, k1, k2, p1, p2, k3, tol."""
+        return np.concatenate([self.intrinsics, self.distortion, [self.tol]]).astype(np.float64)
+
+    def __repr__(self):
+        fx, fy, cx, cy = self.intrinsics
+        return f"Camera({fx!r}, {fy!r}, {cx!r}, {cy!r}, distortion={tuple(self.distortion.tolist())!r}, tol={self.tol!r})"
+
+
+def _is_camera_list(camera):
+    return isinstance(camera, (list, tuple)) and any(isinstance(c, Camera) for c in camera)
+
+
+def split_cameras(camera, count, per="track"):
+    """What ``camera=`` was given -> (the plain camera ``check_cameras`` takes, lens): ``lens`` is None -- nothing to undistort: None, plain
+    tuples, ``Camera``s without distortion -- or the (count, 10) float64 rows of uu3d_undistort_points.  A list that mixes tuples and
+    ``Camera``s, or ``Camera``s with and without distortion, is a ValueError; counts and intrinsics stay ``check_cameras``' to refuse."""
+    if isinstance(camera, Camera):
+        return camera.intrinsics, (np.tile(camera.row(), (int(count), 1)) if camera.has_distortion else None)
+    if not _is_camera_list(camera):
+        return camera, None
+    if not all(isinstance(c, Camera) for c in camera):
+        raise ValueError(f"camera must be plain (fx, fy, cx, cy) tuples or Camera objects, one or one per {per}, not a mix of the two")
+    if len({c.has_distortion for c in camera}) > 1:
+        raise ValueError(f"camera: the Camera objects of a list, one per {per}, must all have distortion or all have none")
+    plain = [c.intrinsics for c in camera]
+    if not camera[0].has_distortion:
+        return plain, None
+    check_cameras(plain, count, per=per)                                 # (a wrong count is refused in check_cameras' words)
+    return plain, np.ascontiguousarray(np.stack([c.row() for c in camera]))
+
+
+def plain_camera(camera):
+    """``camera=`` as the checks that only look at its shape take it: a ``Camera`` as its (fx, fy, cx, cy), a list of them as a list."""
+    if isinstance(camera, Camera):
+        return camera.intrinsics
+    if _is_camera_list(camera):
+        return [c.intrinsics if isinstance(c, Camera) else c for c in camera]
+    return camera
+
+
+def _lens_rows(camera, lens, rows):
+    """One ``Camera`` or one per track of ``lens`` rows -> ((tracks, 10) float64, rows per track)."""
+    lens = _root_lens(lens, rows)
+    cams = [camera] * len(lens) if isinstance(camera, Camera) else list(camera) if isinstance(camera, (list, tuple)) else None
+    if cams is None or len(cams) != len(lens) or not all(isinstance(c, Camera) for c in cams):
+        raise ValueError(f"camera must be one Camera or one per track ({len(lens)})")
+    return np.ascontiguousarray(np.stack([c.row() for c in cams])), lens
+
+
+def _radial_tangential(x, y, k1, k2, p1, p2, k3):
+    """r2, the radial polynomial's inner sum and the two tangential terms at (x, y): the parenthesisation of the rule, written out."""
+    r2 = x * x + y * y
+    poly = ((k3 * r2 + k2) * r2 + k1) * r2
+    dx = 2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x)
+    dy = p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y
+    return poly, dx, dy
+
+
+def undistort_rows_host(kp, rows):
+    """``undistort_points_host`` with the camera of every row of ``kp`` given as a (R, 10) float64 row of the device call."""
+    uv = np.asarray(_host_array(kp), np.float32)
+    cam = np.asarray(rows, np.float64).reshape((uv.shape[0], 10) + (1,) * (uv.ndim - 2))
+    fx, fy, cx, cy, k1, k2, p1, p2, k3, tol = (cam[:, i] for i in range(10))
+    with np.errstate(all="ignore"):
+        u, v = uv[..., 0].astype(np.float64), uv[..., 1].astype(np.float64)
+        x0 = (u - cx) / fx
+        y0 = (v - cy) / fy
+        x, y = x0, y0
+        for _ in range(Camera.ITERATIONS):                               # exactly, no early exit
+            poly, dx, dy = _radial_tangential(x, y, k1, k2, p1, p2, k3)
+            ic = 1.0 / (1.0 + poly)
+            x = (x0 - dx) * ic
+            y = (y0 - dy) * ic
+        # the acceptance check: the forward model on (x, y) must land on the observation
+        poly, dx, dy = _radial_tangential(x, y, k1, k2, p1, p2, k3)
+        rad = 1.0 + poly
+        xd = x * rad + dx
+        yd = y * rad + dy
+        ex = np.abs(xd - x0) * fx
+        ey = np.abs(yd - y0) * fy
+        ok = np.isfinite(uv).all(axis=-1) & np.isfinite(x) & np.isfinite(y) & (ex <= tol) & (ey <= tol)
+        out = np.stack([(fx * x + cx).astype(np.float32), (fy * y + cy).astype(np.float32)], axis=-1)
+        ok &= np.isfinite(out).all(axis=-1)
+    out[~ok] = np.float32(np.nan)
+    return out
+
+
+def undistort_points_host(kp, camera, lens=None):
+    """The rule of LENS DISTORTION (include/uu3d.h) in numpy, written to be read: what uu3d_undistort_points computes, bit for bit.
+    ``kp`` (R, ..., 2): raw points as a detector saw them (read as float32), or a list of such arrays, one per track (-> a list);
+    ``camera``: one ``Camera`` or -- with ``lens``, rows per track; for a list its arrays -- one per track -> float32 of the same shape: the pixel an ideal pinhole with the same intrinsics would have seen, or (NaN, NaN).
+    Per point, in float64, every operation rounded once (no fused multiply-add):
+        x0 = (u - cx) / fx, y0 = (v - cy) / fy, x = x0, y = y0; then exactly ``Camera.ITERATIONS`` times
+            r2 = x*x + y*y;  ic = 1.0 / (1.0 + ((k3*r2 + k2)*r2 + k1)*r2)
+            dx = 2.0*p1*x*y + p2*(r2 + 2.0*x*x);  dy = p1*(r2 + 2.0*y*y) + 2.0*p2*x*y
+            x = (x0 - dx)*ic;  y = (y0 - dy)*ic
+    and the forward model once on the result: rad = 1.0 + ((k3*r2 + k2)*r2 + k1)*r2, xd = x*rad + dx, yd = y*rad + dy.  ACCEPTED iff
+    everything is finite, |xd - x0|*fx <= tol and |yd - y0|*fy <= tol: (fx*x + cx, fy*y + cy), rounded once to float32.  Anything else
+    -- a non-finite input, an observation outside the region where the model can be inverted -- is (NaN, NaN)."""
+    if isinstance(kp, (list, tuple)) and len(kp) and all(hasattr(t, "shape") for t in kp):      # a list of tracks: one camera or one each
+        parts = [np.asarray(_host_array(t), np.float32) for t in kp]
+        sizes = [len(t) for t in parts]
+        return np.split(undistort_points_host(np.concatenate(parts), camera, sizes if lens is None else lens), np.cumsum(sizes)[:-1])
+    uv = np.asarray(_host_array(kp), np.float32)
+    if uv.ndim < 2 or uv.shape[-1] != 2:
+        raise ValueError(f"kp must be (R, ..., 2), got {uv.shape}")
+    if lens is None and isinstance(camera, (list, tuple)) and len(camera) == 1:
+        camera = camera[0]
+    rows, lens = _lens_rows(camera, lens, uv.shape[0])
+    return undistort_rows_host(uv, np.repeat(rows, lens, axis=0))
+
+
+def distort_points_host(kp, camera):
+    """The forward model in numpy, float64 in and out: ``kp`` (..., 2) ideal pinhole pixels -> the pixels the lens of ``camera`` (one
+    ``Camera``) puts them at.  For building test inputs and for users; ``undistort_points_host`` inverts it where it can be inverted."""
+    if not isinstance(camera, Camera):
+        raise ValueError("camera must be a Camera")
+    p = np.asarray(_host_array(kp), np.float64)
+    if p.ndim < 1 or p.shape[-1] != 2:
+        raise ValueError(f"kp must be (..., 2), got {p.shape}")
+    fx, fy, cx, cy = camera.intrinsics
+    x = (p[..., 0] - cx) / fx
+    y = (p[..., 1] - cy) / fy
+    poly, dx, dy = _radial_tangential(x, y, *camera.distortion.tolist())
+    rad = 1.0 + poly
+    return np.stack([fx * (x * rad + dx) + cx, fy * (y * rad + dy) + cy], axis=-1)
+
+
+def undistort_rows(kp, rows, lens=None):
+    """uu3d_undistort_points on the current stream with the cameras given as (tracks, 10) float64 rows (host); ``lens``: rows of ``kp``
+    per track, None: one track.  ``kp`` (R, P, 2) float32 on the device, contiguous, only read -> a fresh (R, P, 2) buffer."""
+    import torch
+    lib = _capi.load_library()
+    if not isinstance(kp, torch.Tensor) or not kp.is_cuda or kp.dim() != 3 or kp.shape[2] != 2 or kp.dtype != torch.float32 or not kp.is_contiguous():
+        raise ValueError(f"kp must be a contiguous (R, P, 2) float32 device tensor, got {tuple(getattr(kp, 'shape', ()))}")
+    dev = kp.device
+    R, P = int(kp.shape[0]), int(kp.shape[1])
+    lens = _root_lens(lens, R)
+    rows = np.ascontiguousarray(np.asarray(rows, np.float64).reshape(len(lens), 10))
+    cams = _upload(rows, np.float64, dev)
+    row_track = None if len(lens) == 1 else _upload(np.repeat(np.arange(len(lens), dtype=np.int32), lens), np.int32, dev)
+    out = torch.empty_like(kp)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _capi.check(lib, lib.uu3d_undistort_points(_ptr(kp), _ptr(out), R, P, _ptr(row_track), len(lens), _ptr(cams), C.c_void_p(stream)), None)
+    return out
+
+
+def undistort_points(kp, camera, lens=None):
+    """uu3d_undistort_points on the current stream: ``undistort_points_host`` on a device tensor, one launch, nothing copies to the host
+    or waits.  ``kp`` (R, P, 2) float32 on the device, contiguous (only read); ``camera``: one ``Camera`` or one per track with ``lens``
+    (rows per track) -> a fresh (R, P, 2) float32 device buffer.  Needs no model."""
+    rows, lens = _lens_rows(camera, lens, int(kp.shape[0]) if hasattr(kp, "shape") and len(kp.shape) else 0)
+    return undistort_rows(kp, rows, lens)

@@ -39,6 +39,8 @@ every name is importable from here as before:
     tracks.py     the pose table and the three uu3d_*_tracks launches above, and uu3d_assemble_tracks_cubic: C1 motion between the predicted
                   frames, ``predict_tracks(..., interpolation="cubic")`` (``evaluation.keyframe_plan_cubic``, ``interpolate_cubic_host``); options.py: the checks of all these options, shared with a live
                   session; cli.py: the command-line options, shared with ``stream``
+    camera.py     lens distortion: ``predict_tracks(..., camera=Camera(fx, fy, cx, cy, distortion=(k1, k2, p1, p2, k3)))`` (uu3d_undistort_points;
+                  ``undistort_points``, ``undistort_points_host``, ``distort_points_host``)
 """
 import argparse
 # (noqa: F401 below -- re-exported: every name this module had before the stages became modules of their own)
@@ -53,6 +55,7 @@ from .associate import (ASSOCIATION_DEFAULTS, MAX_ASSOCIATION, Association, Asso
                         _detection_flags, _device_detections, associate_detections, associate_host, association_tracks_host, check_association)
 from .bones import (MAX_BONE_JOINTS, SKELETONS, Bones, Skeleton, _bone_device_poses, _bone_length_table, _bone_offsets, _bone_poses,  # noqa: F401
                     bone_lengths, bone_lengths_host, check_bones, fix_bones, fix_bones_host, skeleton_of)
+from .camera import Camera, distort_points_host, split_cameras, undistort_points, undistort_points_host, undistort_rows  # noqa: F401
 from .cli import add_track_options, bones_option, input_joints, smooth_option, split_scores, track_keywords  # noqa: F401
 from .data import PoseTable, SequenceGenerator  # noqa: F401
 from .keypoints import (KEYPOINT_PRESETS, MAX_KEYPOINT_SOURCES, KeypointMap, _h36m17_from, _map_front, check_keypoint_inputs,  # noqa: F401
@@ -87,6 +90,9 @@ def predict_detections(model, config, detections, counts=None, valid=None, slots
     ``association_tracks_host``, bit for bit.  Needs a model with strided input.  Greedy, no motion model: no tracking accuracy is claimed.
     ``camera``: one (fx, fy, cx, cy) or one per VIDEO, handed to ``predict_tracks`` per track the way ``resolutions`` is: the tuples become
     (track_id, first_frame, poses, roots (n, 3) float32, root_state (n,) uint8) -- every person of a video in the same camera space.
+    A ``Camera`` with distortion (one, or one per video): uu3d_undistort_points takes all D x K points of every frame back to the pinhole's
+    pixels before the association looks at them (``camera.py``); the result equals the call on ``undistort_points_host`` of the
+    detections with the plain tuple, bit for bit.
     ``smooth``: handed to ``predict_tracks`` as it is -- every track's poses (and roots) filtered from its birth frame on (a ``OneEuro``
     with ``zero_lag`` as well: forwards from the birth frame, then back from the track's last frame).
     ``bones``: handed to ``predict_tracks`` as it is -- "track" or one (J,) array of lengths for every person (the tracks are only known
@@ -98,14 +104,19 @@ def predict_detections(model, config, detections, counts=None, valid=None, slots
     import torch
     assoc, options = _association_options(options)
     check_interpolation(options.get("interpolation", "linear"))
-    camera = options.pop("camera", None)
+    camera, lens = options.pop("camera", None), None
     if camera is not None:
+        camera, lens = split_cameras(camera, len(detections), per="video")
         camera = check_cameras(camera, len(detections), per="video")
     for k in ("keyframes_only", "lengths", "return_valid"):
         if options.get(k):
             raise ValueError(f"predict_detections does not take {k}")
     if not model.has_strided_input:
         raise ValueError("predict_detections needs a model with strided input: a frame without a match becomes the learned masked token")
+    if lens is not None:                                              # lens distortion: all D x K points of every frame, before the association
+        flat, _, _, _, frames = _device_detections(detections, None, None, torch.device(model.device))
+        flat = undistort_rows(flat.reshape(flat.shape[0], -1, 2), lens, frames).reshape(flat.shape)
+        detections = list(torch.split(flat, [int(n) for n in frames], 0))
     r = associate_detections(detections, counts, valid, slots=slots, device=model.device, **assoc)
     dets, flags, per_joint, lens, track_of = r._flat
     F, D, K = int(dets.shape[0]), int(dets.shape[1]), int(dets.shape[2])
@@ -221,7 +232,7 @@ def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, fl
     equals, bit for bit, ``predict_tracks(mapped, valid=flags)`` with the output of ``map_keypoints_host``, the rule in numpy.
 
     Absolute root position -- ``camera``: None = today's call, the same bits, no further launch or buffer.  Else the camera's intrinsics
-    (fx, fy, cx, cy), no distortion, in the units of the tracks AS GIVEN (pixels when ``resolutions`` is given), one tuple or one per track
+    (fx, fy, cx, cy), in the units of the tracks AS GIVEN (pixels when ``resolutions`` is given), one tuple or one per track
     (non-finite, fx <= 0 or fy <= 0: ValueError): ``roots``, a list of (T_i, 3) float32 device tensors (views of one buffer), and
     ``root_state``, a list of (T_i,) uint8 ones, are APPENDED to whatever the call returns -- (poses, roots, root_state), (poses, flags,
     roots, root_state) or (poses, flags, joint_state, roots, root_state); the poses are those of the call without ``camera``, bit for bit,
@@ -238,6 +249,18 @@ def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, fl
     0 the track has no solved frame (zeros).  With ``root_relative=False`` the solve takes the pose as returned.  No accuracy is claimed:
     the model's scale error goes 1:1 into the depth.  The live form is ``StreamSession(camera=...)`` / ``replay_tracks(camera=...)``: the
     same solve per emitted pose at any ``lookahead``, the last solved root held where a frame is not solved (causal: no interpolation).
+
+    Lens distortion -- ``camera=Camera(fx, fy, cx, cy, distortion=(k1, k2, p1, p2, k3), tol=1e-3)``, one or one per track (a list that
+    mixes tuples and ``Camera``s, or ``Camera``s with and without distortion: ValueError): the intrinsics as above, and the given points
+    are first taken back to the pixels an ideal pinhole would have seen -- uu3d_undistort_points, the FIRST launch of the call, on the
+    given frames in the detector's layout, in front of uu3d_map_keypoints; one lane per point, 20 steps of OpenCV's fixed-point iteration
+    in float64 and an acceptance check against the forward model (``camera.py``; ``undistort_points`` is the launch alone; the rule in
+    numpy: ``undistort_points_host``).  Everything behind reads the undistorted points: the ``keypoints`` map, ``repair_joints``, the
+    normalisation or resampling, and the root solve; the caller's memory is never written.  A point that is not accepted -- non-finite,
+    or outside the region where the model can be inverted -- becomes (NaN, NaN): ``valid="finite"`` is the companion option, which makes
+    it a lost joint (``repair_joints``) or a missing frame; the root solve never uses it.  The result equals, bit for bit,
+    ``predict_tracks(undistort_points_host(tracks, camera), camera=(fx, fy, cx, cy))`` in every form of the call.  A ``Camera`` without
+    distortion (None or all zeros) is the plain tuple: the same launches, buffers and bits.  No accuracy is claimed.
 
     Steady output -- ``smooth``: None = today's call, the same bits, no further launch or buffer.  True (the defaults), a ``OneEuro`` or a
     pair (pose_filter, root_filter), either of which may be None (``check_smooth``; a root filter without ``camera``: ValueError): the
@@ -316,7 +339,8 @@ def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, fl
         raise ValueError("keyframes_only needs a mask stride")
     # table: the given frames -> the pose table on the model's time grid; ``lens``: returned frames per track
     given = np.array([len(t) for t in tracks], np.int64)
-    front = dict(valid=valid, repair_joints=repair_joints, keypoints=opts.keypoints, model=model, keep_source=camera is not None)
+    front = dict(valid=valid, repair_joints=repair_joints, keypoints=opts.keypoints, model=model, keep_source=camera is not None,
+                 distortion=opts.lens)
     if fps is None:
         table, lens = pose_table(tracks, model.device, resolutions, int(mask_stride) if keyframes_only else 0, lengths, **front)
         model_lens = lens

@@ -84,6 +84,7 @@ module's docstring; every name is importable from here as before:
     smooth.py     steady output: ``StreamSession(..., smooth=F)`` (``LiveOneEuro``, ``LiveOneEuroHost``)
     bones.py      live constant bone lengths: ``StreamSession(..., bones=B)`` (``LiveBonesHost``)
     rotations.py  live joint rotations: ``StreamSession(..., rotations=R)`` (uu3d_joint_rotations as the tick's last launch)
+    camera.py     lens distortion: ``StreamSession(..., camera=Camera(fx, fy, cx, cy, distortion=...))`` (uu3d_undistort_points as the tick's first launch)
 The refusals these options share with ``predict_tracks`` are ``options.stage_options``; the ones only a session has are ``_init_plan``'s.
 
 The end of a track -- ``finish(slots)``: a session with lookahead a has not returned the poses of a track's last a frames when the track
@@ -117,6 +118,7 @@ from ._capi import ptr as _ptr
 # (noqa: F401 below -- re-exported: every name this module had before the stages became modules of their own)
 from .associate import ASSOCIATION_DEFAULTS, check_association
 from .bones import Bones, LiveBonesHost, _bone_offsets, check_bones, fix_bones_host, skeleton_of  # noqa: F401
+from .camera import Camera, distort_points_host, plain_camera, undistort_points, undistort_points_host  # noqa: F401
 from .cli import add_track_options, bones_option, input_joints, smooth_option, split_scores, track_keywords  # noqa: F401
 from .keypoints import KEYPOINT_PRESETS, check_keypoint_inputs, keypoint_map  # noqa: F401
 from .options import check_interpolation, stage_options
@@ -250,6 +252,14 @@ class StreamSession(object):
         only): the module docstring's "Live absolute root" -- ``push`` / ``push_detections`` then return (poses, fresh, roots (slots, 3)
         float32, root_state (slots,) uint8).  ``min_root_joints`` (default 6, an int >= 2; ValueError without ``camera``): the fewest used
         joints a frame's root is solved from.  Models of more than ``predict.MAX_ROOT_JOINTS`` joints and ``out_fps``: ValueError.
+        A ``predict.Camera(fx, fy, cx, cy, distortion=(k1, k2, p1, p2, k3), tol=1e-3)`` in the tuple's place -- one, one per slot, or with
+        ``detections`` one; a mix of tuples and ``Camera``s or of ``Camera``s with and without distortion: ValueError --: "Lens distortion"
+        (``camera.py``).  ``push`` files the raw points in a buffer of the session and uu3d_undistort_points is the FIRST step of the one
+        captured tick -- in front of uu3d_map_keypoints; with ``fps`` a plain launch in front of uu3d_stream_source_push; with
+        ``detections`` on all D x K points in front of the association -- so every push returns, bit for bit, what a session with
+        ``camera=(fx, fy, cx, cy)`` returns for ``predict.undistort_points_host`` of the frames.  A point that is not accepted is
+        (NaN, NaN): ``missed_detections=True`` (or ``repair_joints``) is the companion option.  ``push`` still never waits, ``captures``
+        stays 1; ``reset``, ``finish`` and the replays need nothing new.  Without distortion: the tuple's session, bit for bit.
         ``smooth`` (keyword only, from ``options`` as well): None = the poses and roots as they are solved (the session above, bit for
         bit).  True, a ``predict.OneEuro`` or a pair (pose_filter, root_filter), either of which may be None (``predict.check_smooth``; a
         root filter without ``camera``: ValueError): the module docstring's "Steady output" -- ``push`` / ``push_detections`` return the
@@ -301,6 +311,7 @@ class StreamSession(object):
                              'is nothing to interpolate')
         self.bones, self.pose_filter, self.root_filter, self.keypoints = opts.rigid, opts.pose_filter, opts.root_filter, opts.keypoints
         self.cameras, self.min_root_joints = opts.cameras, opts.min_root_joints
+        self.lens = opts.lens                                        # (slots, 10) rows of uu3d_undistort_points, or None: nothing to undistort
         self.smooth_rate = frame_rate(model_fps if fps is None else fps)     # the rate of the frames a push returns
         if self.bones is not None and out_fps is not None:
             raise ValueError("bones together with out_fps is not supported: a push then returns several rows per slot, and the live fix "
@@ -314,7 +325,7 @@ class StreamSession(object):
         if camera is not None and out_fps is not None:
             raise ValueError("camera together with out_fps is not supported yet: the returned poses are not at source-frame times, so no "
                              "pushed frame is theirs to be solved against (a later change)")
-        if camera is not None and detections is not None and np.ndim(camera) != 1:
+        if camera is not None and detections is not None and np.ndim(plain_camera(camera)) != 1:
             raise ValueError("detections takes ONE camera (fx, fy, cx, cy), not one per slot: every person of a video shares one space")
         self.detections, self.association = None, None
         if detections is not None:
@@ -406,6 +417,7 @@ class StreamSession(object):
         if self.keypoints is not None:
             self._kp_in = zeros((T, self.keypoints.inputs, 2), dtype=torch.float32)
             self._map_table = self.keypoints.device_table(dev)
+        self._push_in = self._kp_in                                  # where push copies the frame
         self._active = torch.ones((T,), dtype=torch.uint8, device=dev)
         self._active_all = True
         self._res = None if res is None else torch.from_numpy(res).pin_memory().to(dev, non_blocking=True)
@@ -453,6 +465,15 @@ class StreamSession(object):
             self._assignment = torch.full((D,), -1, dtype=torch.int32, device=dev)
             self._track_ids = torch.full((T,), -1, dtype=torch.int32, device=dev)
             self._dropped = zeros((1,), dtype=torch.int32)
+            self._dets_in = self._dets                                # where push_detections copies the frame's list
+        # lens distortion: push files the raw points in a buffer of their own; the tick's first launch writes the undistorted ones where
+        # push filed them otherwise -- per slot its own camera, with detections the one camera for all D x K points
+        if self.lens is not None:
+            self._lens = torch.from_numpy(np.ascontiguousarray(self.lens)).pin_memory().to(dev, non_blocking=True)
+            if self.detections is not None:
+                self._dets_in, self._lens_track = torch.zeros_like(self._dets), None
+            else:
+                self._push_in, self._lens_track = torch.zeros_like(self._kp_in), torch.arange(T, dtype=torch.int32, device=dev)
         # what a (sub-)tick takes as `active` and where its emit writes: with a rate the sub-ticks' own buffers, else the session's
         self._tick_active, self._emit_out, self._emit_fresh = self._active, self._out, self._fresh
         self._source_frames, self._src_host, self._src_known = self._frames, None, None
@@ -561,8 +582,14 @@ class StreamSession(object):
             mapping = [(lib.uu3d_map_keypoints, (h, _ptr(self._map_table), self.keypoints.inputs, _ptr(self._kp_in),
                                                  _ptr(self._flags_in) if per_joint else None, self.slots, kp,
                                                  _ptr(self._valid_in) if per_joint else None))]
+        # lens distortion: the raw points as pushed -> the pinhole's pixels, in front of the map (and of the source push, and of the association)
+        lens = []
+        if self.lens is not None:
+            raw, to = (self._push_in, self._kp_in) if self.detections is None else (self._dets_in, self._dets)
+            lens = [(lib.uu3d_undistort_points, (_ptr(raw), _ptr(to), int(raw.shape[0]), int(raw.shape[1]), _ptr(self._lens_track),
+                                                 self.slots if self.detections is None else 1, _ptr(self._lens)))]
         if self.rate is None:
-            self._tick_steps = mapping + self._tick_steps
+            self._tick_steps = (lens if self.detections is None else []) + mapping + self._tick_steps
         self._reset_call = (lib.uu3d_stream_reset, (h, cfg, state))
         self._reset_more = [] if self.repair_joints is None else [(lib.uu3d_stream_repair_reset, (h, cfg, self.repair_joints, _ptr(self._repair_state)))]
         root = None
@@ -586,11 +613,11 @@ class StreamSession(object):
                                                   _ptr(self._kp_in), _ptr(self._flags_in), int(self._flags_in.dim() == 2), active, born,
                                                   _ptr(self._assignment), _ptr(self._track_ids), _ptr(self._dropped)))]
             front += [(fn, args + (born,)) for fn, args in [self._reset_call] + self._reset_more]
-            self._tick_steps = front + self._tick_steps
+            self._tick_steps = lens + front + self._tick_steps
             self._reset_more = self._reset_more + [(lib.uu3d_associate_reset, (assoc, _ptr(self._assoc_state)))]
         if self.rate is not None:
             self._tick_steps.append((lib.uu3d_stream_file_keyframe, (h, cfg, rate, state, emit_fresh)))
-            self._push_before = mapping + [(lib.uu3d_stream_source_push, (h, cfg, rate, state, kp, active, _ptr(self._valid_in), int(self.missed_detections)))]
+            self._push_before = lens + mapping + [(lib.uu3d_stream_source_push, (h, cfg, rate, state, kp, active, _ptr(self._valid_in), int(self.missed_detections)))]
             cubic = self.interpolation == "cubic"                   # the C1 cubic through four kept keyframes: the emit's cubic sibling
             self._push_after = [(lib.uu3d_stream_timed_emit_cubic if cubic else lib.uu3d_stream_timed_emit,
                                  (h, cfg, rate, state, _ptr(self._out), _ptr(self._fresh)))]
@@ -740,7 +767,7 @@ class StreamSession(object):
         with torch.cuda.device(dev):
             if not kp2d.is_cuda:
                 kp2d = kp2d.to(torch.float32).contiguous().pin_memory()       # host input goes through pinned memory, asynchronously
-            self._kp_in.copy_(kp2d, non_blocking=True)
+            self._push_in.copy_(kp2d, non_blocking=True)
             if active is None:
                 if not self._active_all:
                     self._active.fill_(1)
@@ -798,7 +825,7 @@ class StreamSession(object):
         with torch.cuda.device(dev):
             if not dets.is_cuda:
                 dets = dets.to(torch.float32).contiguous().pin_memory()
-            self._dets.copy_(dets, non_blocking=True)
+            self._dets_in.copy_(dets, non_blocking=True)
             if count is None:
                 if not self._det_count_full:
                     self._det_count.fill_(int(D))

@@ -175,9 +175,11 @@ def assemble_tracks_cubic(plain, flipped, before, left, right, after, weight, fl
     return out
 
 
-def _table_front(tracks, device, resolutions, valid, repair_joints, keypoints, model, keep_source, frames, write):
+def _table_front(tracks, device, resolutions, valid, repair_joints, keypoints, model, keep_source, frames, write, distortion=None):
     """What ``pose_table`` and ``resampled_pose_table`` share, in the order of the launches: the tracks on the device, the checks of
-    ``valid`` / ``repair_joints`` / ``keypoints`` / ``resolutions``, the given frames back to back, uu3d_map_keypoints (``_map_front``),
+    ``valid`` / ``repair_joints`` / ``keypoints`` / ``resolutions``, the given frames back to back, with ``distortion`` -- the (tracks, 10)
+    rows of a ``camera.Camera`` with distortion per track -- uu3d_undistort_points on them in the detector's layout (a fresh buffer: the
+    caller's memory is never written; everything behind reads the undistorted points), uu3d_map_keypoints (``_map_front``),
     ``table.source`` for the root solve, uu3d_repair_joints and the ``valid_in`` flags (``_front_validity``), then the entry's own front
     kernel and the ``data.PoseTable``.  ``frames(given)`` -> the frames per track the given ones stand for (every track needs one);
     ``write(src, J, given, lens, resolutions, valid_in)`` -> (the table's rows (R', J, 2), their (R',) uint8 flags or None, rows per track).
@@ -196,6 +198,9 @@ def _table_front(tracks, device, resolutions, valid, repair_joints, keypoints, m
         raise ValueError("every track needs at least one frame")
     resolutions = check_resolutions(resolutions, len(tr))
     src = torch.cat(tr, 0).contiguous() if len(tr) > 1 else tr[0].contiguous()
+    if distortion is not None:
+        from .camera import undistort_rows
+        src = undistort_rows(src, distortion, given)
     if keypoints is not None:
         (src, valid), J = _map_front(keypoints, model, src, given, valid), keypoints.joints
     source = (src, _source_joint_flags(valid, J, src.device)) if keep_source else None
@@ -207,13 +212,14 @@ def _table_front(tracks, device, resolutions, valid, repair_joints, keypoints, m
 
 
 def pose_table(tracks, device, resolutions=None, key_stride=0, lengths=None, valid=None, repair_joints=None, keypoints=None, model=None,
-               keep_source=False):
+               keep_source=False, distortion=None):
     """The dense, normalised ``data.PoseTable`` of the tracks (uu3d_normalize_tracks) -> (table, frames per track).  ``valid`` as in
     ``predict_tracks`` (not None: uu3d_normalize_tracks_valid into a fresh buffer; the table carries the per-frame flags).
     ``repair_joints`` = G: uu3d_repair_joints runs on the given frames first; ``table.joint_state`` is its (given frames, J) uint8 state.
     ``keypoints``: a ``KeypointMap`` or a preset's name (with ``model``): the tracks are (T_i, K_in, 2), per-joint entries of ``valid``
     (T_i, K_in), and uu3d_map_keypoints runs in front of all of that (``_map_front``).  ``keep_source``: ``table.source`` = (the given
-    frames (R, J, 2) raw in the model's layout, their (R, J) uint8 joint flags or None) as the root solve reads them."""
+    frames (R, J, 2) raw in the model's layout, their (R, J) uint8 joint flags or None) as the root solve reads them.
+    ``distortion``: the (tracks, 10) float64 rows of ``options.stage_options(...).lens``: uu3d_undistort_points runs first of all."""
     import torch
 
     def frames(given):
@@ -236,16 +242,16 @@ def pose_table(tracks, device, resolutions=None, key_stride=0, lengths=None, val
         normalize_tracks(src, kp, lens, resolutions, key_stride, given, valid_in=valid_in, valid_out=flags)
         return kp, flags, lens
 
-    return _table_front(tracks, device, resolutions, valid, repair_joints, keypoints, model, keep_source, frames, write)[:2]
+    return _table_front(tracks, device, resolutions, valid, repair_joints, keypoints, model, keep_source, frames, write, distortion)[:2]
 
 
 def resampled_pose_table(tracks, device, fps, resolutions=None, valid=None, model_fps=50, repair_joints=None, keypoints=None, model=None,
-                         keep_source=False):
+                         keep_source=False, distortion=None):
     """``pose_table`` for tracks at ``fps`` frames per second: the dense, normalised table on the MODEL's time grid (``resample_plan``,
     uu3d_resample_tracks; always a fresh buffer) -> (table, model frames per track, source frames per track).  With ``valid`` the table
     carries one flag per model frame.  ``repair_joints`` = G: uu3d_repair_joints runs on the source frames first; ``table.joint_state`` is
-    its (source frames, J) uint8 state.  ``keypoints`` / ``model`` / ``keep_source`` as ``pose_table``: the map runs on the source frames, in
-    front of the rest."""
+    its (source frames, J) uint8 state.  ``keypoints`` / ``model`` / ``keep_source`` / ``distortion`` as ``pose_table``: the undistortion
+    and the map run on the source frames, in front of the rest."""
     import torch
 
     def write(src, J, given, lens, resolutions, valid_in):
@@ -255,4 +261,4 @@ def resampled_pose_table(tracks, device, fps, resolutions=None, valid=None, mode
         resample_tracks(src, kp, model_lens, left, right, weight, resolutions, valid_in=valid_in, valid_out=flags)
         return kp, flags, model_lens
 
-    return _table_front(tracks, device, resolutions, valid, repair_joints, keypoints, model, keep_source, lambda given: given, write)
+    return _table_front(tracks, device, resolutions, valid, repair_joints, keypoints, model, keep_source, lambda given: given, write, distortion)
