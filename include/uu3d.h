@@ -689,6 +689,37 @@ int uu3d_undistort_points(const float* in_dev, float* out_dev, int64_t rows, int
                           int32_t num_tracks, const double* cameras_dev, void* stream);
 
 /*
+ * WORLD SPACE (predict.camera_to_world, predict.predict_tracks(camera=Camera(..., orientation=, translation=)), predict.predict_detections,
+ * stream.StreamSession): the scene the calls above return -- root-relative poses and a root per frame -- stands in the camera's own space,
+ * where "up" is a slanted direction for every camera that is tilted or rolled.  This call takes it to world axes with the extrinsics a
+ * calibration hands over beside the intrinsics: behind the root solve (which stays in camera space), in front of the One-Euro filters
+ * (which then steady the floor's axes, not the camera's) and of the joint rotations.  predict.camera_to_world_host is the same rule in
+ * numpy, bit for bit.  The convention is h36m.camera_to_world's: X_world = qrot(q, X_cam) + t, q the camera's orientation, t its position.
+ * THE RULE, in float64 on the float32 inputs, every operation rounded once, no fused multiply-add, one final rounding to float32.  A
+ * camera is seven doubles: the UNIT quaternion q = (w, x, y, z) (normalised once on the host, in float64), then t.  For a point
+ * v = (a, b, c):
+ *     uv  = (y * c - z * b,        z * a - x * c,        x * b - y * a)
+ *     uuv = (y * uv2 - z * uv1,    z * uv0 - x * uv2,    x * uv1 - y * uv0)
+ *     r_i = v_i + 2.0 * (w * uv_i + uuv_i)
+ * A JOINT of a pose becomes (float) r_i: poses are rotated only, they stay relative to their root, and the exact zeros of the root joint
+ * stay +0.0 (poses that are not root-relative are rotated only as well; poses + roots[:, None] is the world scene in both cases).  A ROOT
+ * whose root_state is not 0 becomes (float) (r_i + t_i); a root with state 0 stays zeros.  NaN in, NaN out.  root_state is only read.
+ *
+ *   uu3d_camera_to_world(poses_dev (rows, J, 3) f32 and poses_out_dev the same shape -- both NULL: roots only --, roots_dev (rows, 3) f32,
+ *       root_state_dev (rows) u8 and roots_out_dev (rows, 3) f32 -- all three NULL: poses only --, rows, J, row_track_dev (rows) i32 or
+ *       NULL = camera 0 for every row, num_tracks, extrinsics_dev (num_tracks, 7) f64, stream): one launch of 256-thread blocks, one lane
+ *       per (row, point), the points of a row being its J joints and, as point J, its root; one 12-byte load and one 12-byte store per
+ *       lane.  An output pointer MAY equal its input pointer: a lane reads its own element before it writes it.  rows == 0 is a no-op that
+ *       returns UU3D_OK.  A track id out of range writes NaN, nothing is read out of bounds.  The same arguments at every tick: it replays
+ *       from a live tick's captured graph, directly behind uu3d_stream_root (out of place, stateless, all slots: a slot that is not fresh
+ *       gets its previous bits again from the held camera-space buffers), and from the drain graph behind uu3d_stream_root_drain.
+ * Every output element has one writer, no LDS, no atomics, nothing copies to the host or waits: bitwise repeatable.
+ */
+int uu3d_camera_to_world(const float* poses_dev, float* poses_out_dev, const float* roots_dev, const uint8_t* root_state_dev,
+                         float* roots_out_dev, int64_t rows, int32_t J, const int32_t* row_track_dev, int32_t num_tracks,
+                         const double* extrinsics_dev, void* stream);
+
+/*
  * ANY FRAME RATE (predict.predict_tracks(fps=...)): the front of YOUR OWN 2D TRACKS for tracks that were not filmed at the rate the model
  * was trained for.  The table holds the MODEL's time grid: row `row` (track row_track_dev[row]) is model frame k of its track, which sits at
  * source position p_k = k * fps / model_fps.  The host works the positions out in exact integer arithmetic (predict.resample_plan) and

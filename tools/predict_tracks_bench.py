@@ -37,10 +37,14 @@ must not (cubic_max_abs_diff_to_linear).  Informational: no threshold.
 them (predict.distort_points_host) beside predict_tracks(camera=(FX, FY, CX, CY)) in the same process: distortion_extra_ms is the difference of
 the two medians (one more launch: uu3d_undistort_points in front of everything), host_distortion_ms the tuple's call with
 predict.undistort_points_host, the rule in numpy, in front of it; the two must agree bit for bit.  Informational: no threshold.
+--extrinsics QW QX QY QZ TX TY TZ (with --camera): also predict_tracks(camera=Camera(FX, FY, CX, CY, orientation=(QW, QX, QY, QZ),
+translation=(TX, TY, TZ))) beside predict_tracks(camera=(FX, FY, CX, CY)) in the same process: world_extra_ms is the difference of the two
+medians (one more launch: uu3d_camera_to_world behind the root solve), host_world_ms the tuple's call followed by .cpu() and
+predict.camera_to_world_host, the rule in numpy; the two must agree bit for bit.  Informational: no threshold.
    python tools/predict_tracks_bench.py [--tracks 40] [--frames 2500] [--batch 512] [--reps 3] [--cases h36m_351:5,h36m_81:4] [--missing 0.3]
                                         [--fps 30] [--repair_joints 5 --missing_joints 0.1] [--keypoints coco17]
                                         [--camera 1145 1145 960 540] [--smooth [--zero_lag]] [--bones] [--rotations] [--interpolation cubic]
-                                        [--distortion -0.28 0.09 0.0005 -0.0003 -0.012]"""
+                                        [--distortion -0.28 0.09 0.0005 -0.0003 -0.012] [--extrinsics 0.81 -0.53 0.2 0.15 1.8 4.9 1.6]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -68,7 +72,11 @@ def main():
                     help='cubic: also time predict_tracks(interpolation="cubic") beside the plain (linear) call')
     ap.add_argument("--distortion", type=float, nargs=5, default=None, metavar=("K1", "K2", "P1", "P2", "K3"),
                     help="with --camera: also time predict_tracks(camera=Camera(..., distortion=...)) beside the call with the plain tuple")
+    ap.add_argument("--extrinsics", type=float, nargs=7, default=None, metavar=("QW", "QX", "QY", "QZ", "TX", "TY", "TZ"),
+                    help="with --camera: also time predict_tracks(camera=Camera(..., orientation=, translation=)) beside the call with the plain tuple")
     args = ap.parse_args()
+    if args.extrinsics is not None and args.camera is None:
+        ap.error("--extrinsics is used together with --camera")
     if args.zero_lag and not args.smooth:
         ap.error("--zero_lag is used together with --smooth")
     if args.distortion is not None and args.camera is None:
@@ -100,6 +108,9 @@ def main():
     if args.distortion is not None:                                     # the same tracks as the lens shows them to a detector
         lens_camera = predict.Camera(*args.camera, distortion=args.distortion)
         seen = [predict.distort_points_host(t, lens_camera).astype(np.float32) for t in px]
+    world_camera = None
+    if args.extrinsics is not None:
+        world_camera = predict.Camera(*args.camera, orientation=args.extrinsics[:4], translation=args.extrinsics[4:])
     reuse = not args.no_reuse
     fps = None if args.fps is None else predict.frame_rate(args.fps)
     results = []
@@ -188,6 +199,16 @@ def main():
             return predict.predict_tracks(model, cfg, predict.undistort_points_host(seen, lens_camera), resolutions=(W, H), mask_stride=int(msv),
                                           flip=True, reuse_frames=reuse, batch_size=args.batch, camera=tuple(args.camera))
 
+        def world_path():
+            return predict.predict_tracks(model, cfg, px, resolutions=(W, H), mask_stride=int(msv), flip=True, reuse_frames=reuse, batch_size=args.batch,
+                                          camera=world_camera)
+
+        def world_host():
+            poses, roots, state = camera_path()
+            sizes = [len(p) for p in poses]
+            return predict.camera_to_world_host(torch.cat(poses, 0).cpu().numpy(), torch.cat(roots, 0).cpu().numpy(), torch.cat(state, 0).cpu().numpy(),
+                                                world_camera, lens=[sum(sizes)])
+
         def smooth_path():
             return predict.predict_tracks(model, cfg, px, resolutions=(W, H), mask_stride=int(msv), flip=True, reuse_frames=reuse, batch_size=args.batch,
                                           smooth=True, **({} if args.camera is None else {"camera": tuple(args.camera)}))
@@ -232,6 +253,9 @@ def main():
         if lens_camera is not None:
             row["distortion"] = list(args.distortion)
             cases += [("predict_tracks_distortion", distortion_path), ("host_distortion", distortion_host)]
+        if world_camera is not None:
+            row["extrinsics"] = list(args.extrinsics)
+            cases += [("predict_tracks_world", world_path), ("host_world", world_host)]
         if args.smooth:
             cases.append(("predict_tracks_smooth", smooth_path))
         if args.zero_lag:
@@ -280,6 +304,11 @@ def main():
                                                                 torch.cat(b, 0).view(torch.int32) if b[0].dtype == torch.float32 else torch.cat(b, 0))
                                                     for a, b in zip(outs["predict_tracks_distortion"], outs["host_distortion"])))
             row["distortion_lost_points"] = int(sum(np.isnan(t).any(axis=2).sum() for t in predict.undistort_points_host(seen, lens_camera)))
+        if world_camera is not None:
+            row["world_extra_ms"] = round(row["predict_tracks_world_ms"] - row["predict_tracks_camera_ms"], 1)
+            same = lambda a, b: bool(np.array_equal(np.isnan(a), np.isnan(b)) and np.array_equal(a[~np.isnan(a)].view(np.uint32), b[~np.isnan(b)].view(np.uint32)))
+            got = [torch.cat(x, 0).cpu().numpy() for x in outs["predict_tracks_world"][:2]]
+            row["world_bits_equal"] = same(got[0], outs["host_world"][0]) and same(got[1], outs["host_world"][1])
         if args.smooth:
             base = "predict_tracks_camera" if args.camera is not None else "predict_tracks"
             row["smooth_extra_ms"] = round(row["predict_tracks_smooth_ms"] - row[base + "_ms"], 1)

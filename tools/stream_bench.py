@@ -6,7 +6,7 @@ Median (and 90th percentile) over --ticks ticks after --warmup ticks, per config
 A case is CONFIG:s_in, or generic:J,d_s,d_t,heads,N:s_in for a model with generic dims (e.g. --cases generic:25,16,64,4,27:4): its tick
 (the one-workgroup-per-frame spatial stack + the generic forward's second stage in the graph) beside the same baseline.
    python tools/stream_bench.py [--slots 1,8,64] [--cases h36m_81:4,h36m_351:5] [--ticks 300] [--warmup 60] [--lookahead 0] [--fps F [--out_fps G] [--interpolation cubic]]
-                                [--repair_joints G] [--detections D] [--camera FX FY CX CY [--distortion K1 K2 P1 P2 K3]] [--smooth] [--bones] [--rotations] [--drain]
+                                [--repair_joints G] [--detections D] [--camera FX FY CX CY [--distortion K1 K2 P1 P2 K3 | --extrinsics QW QX QY QZ TX TY TZ]] [--smooth] [--bones] [--rotations] [--drain]
 --fps F (a float or NUM/DEN): microseconds per PUSH of StreamSession(fps=F) -- one source frame in, one pose out, on average
 model_fps / F sub-ticks -- next to the plain session pushed at the model's rate (the cost of one model tick); the lookahead is raised to
 the smallest one the rate allows.  The numpy baseline is left out.
@@ -32,6 +32,10 @@ camera_minus_graph_us is the difference of the two medians.  The numpy baseline 
 -- one more launch, uu3d_undistort_points, the first of the captured tick -- as distortion_graph_us next to the tick of the session with the
 plain tuple (camera_graph_us) on the same frames in the same process, measured side by side in the same way.  distortion_minus_camera_us is
 the difference of the two medians.  Informational: no threshold.  The numpy baseline is left out.
+--extrinsics QW QX QY QZ TX TY TZ (with --camera, not with the other options): the tick of StreamSession(camera=Camera(FX, FY, CX, CY,
+orientation=(QW, QX, QY, QZ), translation=(TX, TY, TZ))) -- one more launch, uu3d_camera_to_world, directly behind uu3d_stream_root -- as
+world_graph_us next to the tick of the session with the plain tuple (camera_graph_us) on the same frames in the same process, measured side
+by side in the same way.  world_minus_camera_us is the difference of the two medians.  Informational: no threshold.
 --smooth (alone or with --camera, not with the other options): the tick of StreamSession(smooth=True) -- one more launch at the end of the
 captured tick, with --camera two (poses and roots) -- as smooth_graph_us next to the tick of the same session without smooth (graph_us;
 with --camera both sessions have the camera), measured side by side in the same way.  smooth_minus_graph_us is the difference of the two
@@ -67,6 +71,7 @@ def main():
     ap.add_argument("--detections", type=int, default=None)
     ap.add_argument("--camera", type=float, nargs=4, metavar=("FX", "FY", "CX", "CY"), default=None)
     ap.add_argument("--distortion", type=float, nargs=5, metavar=("K1", "K2", "P1", "P2", "K3"), default=None)
+    ap.add_argument("--extrinsics", type=float, nargs=7, metavar=("QW", "QX", "QY", "QZ", "TX", "TY", "TZ"), default=None)
     ap.add_argument("--smooth", action="store_true")
     ap.add_argument("--bones", action="store_true")
     ap.add_argument("--rotations", action="store_true")
@@ -88,6 +93,8 @@ def main():
         ap.error("--detections is not measured together with --fps / --repair_joints")
     if args.distortion is not None and (args.camera is None or args.smooth or args.bones or args.rotations):
         ap.error("--distortion is measured with --camera alone")
+    if args.extrinsics is not None and (args.camera is None or args.smooth or args.bones or args.rotations or args.distortion is not None):
+        ap.error("--extrinsics is measured with --camera alone")
     if args.out_fps is not None and args.fps is None:
         ap.error("--out_fps needs --fps")
     if args.interpolation == "cubic" and args.fps is None:
@@ -238,6 +245,9 @@ def main():
                 elif args.distortion is not None:                     # both with the camera, one of them with the lens in front of the tick
                     pair = {"distortion_graph": new(camera=stream.Camera(*args.camera, distortion=args.distortion)),
                             "camera_graph": new(camera=tuple(args.camera))}
+                elif args.extrinsics is not None:                     # both with the camera, one of them with the world launch behind the root solve
+                    pair = {"world_graph": new(camera=stream.Camera(*args.camera, orientation=args.extrinsics[:4], translation=args.extrinsics[4:])),
+                            "camera_graph": new(camera=tuple(args.camera))}
                 else:
                     pair = {"camera_graph": new(camera=tuple(args.camera)), "graph": new()}
                 ts = {key: [] for key in pair}
@@ -253,7 +263,8 @@ def main():
                     s.check_range()
                     s.close()
                 row.update(camera=None if args.camera is None else list(args.camera), smooth=bool(args.smooth), bones=bool(args.bones),
-                           rotations=bool(args.rotations), **({} if args.distortion is None else {"distortion": list(args.distortion)}))
+                           rotations=bool(args.rotations), **({} if args.distortion is None else {"distortion": list(args.distortion)}),
+                           **({} if args.extrinsics is None else {"extrinsics": list(args.extrinsics)}))
                 return tuple((key, lambda key=key: ts[key][args.warmup:]) for key in pair)
 
             if args.drain:
@@ -321,6 +332,8 @@ def main():
                 row["rotations_minus_graph_us"] = round(row["rotations_graph_us"] - row["graph_us"], 1)
             elif args.distortion is not None:
                 row["distortion_minus_camera_us"] = round(row["distortion_graph_us"] - row["camera_graph_us"], 1)
+            elif args.extrinsics is not None:
+                row["world_minus_camera_us"] = round(row["world_graph_us"] - row["camera_graph_us"], 1)
             elif args.camera is not None:
                 row["camera_minus_graph_us"] = round(row["camera_graph_us"] - row["graph_us"], 1)
             elif args.detections is not None:

@@ -53,6 +53,7 @@ EXPORTED_SYMBOLS = (
     "uu3d_assemble_tracks_cubic",
     "uu3d_stream_timed_emit_cubic", "uu3d_stream_timed_emit_multi_cubic",
     "uu3d_undistort_points",
+    "uu3d_camera_to_world",
 )
 # include/uu3d_ops.h
 OPS_SYMBOLS = (
@@ -374,6 +375,8 @@ def load_library(path=None):
     lib.uu3d_stream_bones_reset.argtypes = [i32, i32, vp, vp, vp]
     lib.uu3d_undistort_points.restype = C.c_int
     lib.uu3d_undistort_points.argtypes = [vp, vp, i64, i32, vp, i32, vp, vp]
+    lib.uu3d_camera_to_world.restype = C.c_int
+    lib.uu3d_camera_to_world.argtypes = [vp, vp, vp, vp, vp, i64, i32, vp, i32, vp, vp]
     lib.uu3d_joint_rotations.restype = C.c_int
     lib.uu3d_joint_rotations.argtypes = [vp, i64, i32, vp, i32] + [vp] * 6
     lib.uu3d_joint_rotations_reset.restype = C.c_int

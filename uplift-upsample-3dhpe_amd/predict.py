@@ -40,7 +40,9 @@ every name is importable from here as before:
                   frames, ``predict_tracks(..., interpolation="cubic")`` (``evaluation.keyframe_plan_cubic``, ``interpolate_cubic_host``); options.py: the checks of all these options, shared with a live
                   session; cli.py: the command-line options, shared with ``stream``
     camera.py     lens distortion: ``predict_tracks(..., camera=Camera(fx, fy, cx, cy, distortion=(k1, k2, p1, p2, k3)))`` (uu3d_undistort_points;
-                  ``undistort_points``, ``undistort_points_host``, ``distort_points_host``)
+                  ``undistort_points``, ``undistort_points_host``, ``distort_points_host``); world space: ``camera=Camera(..., orientation=(w, x,
+                  y, z), translation=(tx, ty, tz))`` (uu3d_camera_to_world; ``camera_to_world``, ``camera_to_world_host``,
+                  ``world_to_camera_host``, ``extrinsics_from_opencv``)
 """
 import argparse
 # (noqa: F401 below -- re-exported: every name this module had before the stages became modules of their own)
@@ -55,7 +57,8 @@ from .associate import (ASSOCIATION_DEFAULTS, MAX_ASSOCIATION, Association, Asso
                         _detection_flags, _device_detections, associate_detections, associate_host, association_tracks_host, check_association)
 from .bones import (MAX_BONE_JOINTS, SKELETONS, Bones, Skeleton, _bone_device_poses, _bone_length_table, _bone_offsets, _bone_poses,  # noqa: F401
                     bone_lengths, bone_lengths_host, check_bones, fix_bones, fix_bones_host, skeleton_of)
-from .camera import Camera, distort_points_host, split_cameras, undistort_points, undistort_points_host, undistort_rows  # noqa: F401
+from .camera import (Camera, camera_to_world, camera_to_world_host, camera_to_world_rows, distort_points_host, extrinsics_from_opencv,  # noqa: F401
+                     split_cameras, undistort_points, undistort_points_host, undistort_rows, world_to_camera_host)
 from .cli import add_track_options, bones_option, input_joints, smooth_option, split_scores, track_keywords  # noqa: F401
 from .data import PoseTable, SequenceGenerator  # noqa: F401
 from .keypoints import (KEYPOINT_PRESETS, MAX_KEYPOINT_SOURCES, KeypointMap, _h36m17_from, _map_front, check_keypoint_inputs,  # noqa: F401
@@ -92,7 +95,9 @@ def predict_detections(model, config, detections, counts=None, valid=None, slots
     (track_id, first_frame, poses, roots (n, 3) float32, root_state (n,) uint8) -- every person of a video in the same camera space.
     A ``Camera`` with distortion (one, or one per video): uu3d_undistort_points takes all D x K points of every frame back to the pinhole's
     pixels before the association looks at them (``camera.py``); the result equals the call on ``undistort_points_host`` of the
-    detections with the plain tuple, bit for bit.
+    detections with the plain tuple, bit for bit.  A ``Camera`` with extrinsics (one, or one per video): every track of a video goes
+    to that video's world axes by uu3d_camera_to_world, behind the root solve and in front of ``smooth`` and ``rotations``, as in
+    ``predict_tracks`` ("World space").
     ``smooth``: handed to ``predict_tracks`` as it is -- every track's poses (and roots) filtered from its birth frame on (a ``OneEuro``
     with ``zero_lag`` as well: forwards from the birth frame, then back from the track's last frame).
     ``bones``: handed to ``predict_tracks`` as it is -- "track" or one (J,) array of lengths for every person (the tracks are only known
@@ -104,10 +109,14 @@ def predict_detections(model, config, detections, counts=None, valid=None, slots
     import torch
     assoc, options = _association_options(options)
     check_interpolation(options.get("interpolation", "linear"))
-    camera, lens = options.pop("camera", None), None
+    camera, lens, placed = options.pop("camera", None), None, None
     if camera is not None:
+        given = camera
         camera, lens = split_cameras(camera, len(detections), per="video")
         camera = check_cameras(camera, len(detections), per="video")
+        cams = [given] * len(detections) if isinstance(given, Camera) else given
+        if isinstance(cams[0], Camera) and cams[0].has_extrinsics:     # world space: each video's extrinsics go on to its tracks
+            placed = [c.without(distortion=True) for c in cams]      # (the lens is taken off here, in front of the association)
     for k in ("keyframes_only", "lengths", "return_valid"):
         if options.get(k):
             raise ValueError(f"predict_detections does not take {k}")
@@ -148,7 +157,7 @@ def predict_detections(model, config, detections, counts=None, valid=None, slots
     if res is not None:
         res = check_resolutions(res, V, per="video")[[v for v, _, _ in spans]]
     if camera is not None:
-        options["camera"] = camera[[v for v, _, _ in spans]]
+        options["camera"] = camera[[v for v, _, _ in spans]] if placed is None else [placed[v] for v, _, _ in spans]
     poses = predict_tracks(model, config, list(torch.split(xy, sizes, 0)), valid=list(torch.split(jf, sizes, 0)), resolutions=res, **options)
     out = [[] for _ in range(V)]
     for (v, tid, first), *p in zip(spans, *(poses if isinstance(poses, tuple) else (poses,))):
@@ -262,6 +271,21 @@ def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, fl
     ``predict_tracks(undistort_points_host(tracks, camera), camera=(fx, fy, cx, cy))`` in every form of the call.  A ``Camera`` without
     distortion (None or all zeros) is the plain tuple: the same launches, buffers and bits.  No accuracy is claimed.
 
+    World space -- ``camera=Camera(fx, fy, cx, cy, orientation=(w, x, y, z), translation=(tx, ty, tz))``, one or one per track (with or
+    without ``distortion``; a list of ``Camera``s with and without extrinsics: ValueError): the camera's extrinsics in the convention of
+    ``h36m.camera_to_world``, ``X_world = qrot(orientation, X_cam) + translation`` (``extrinsics_from_opencv`` makes them from OpenCV's
+    (R, tvec)).  The stages then run in this order: assembly, ``bones``, the root solve and the trajectory in camera space as without
+    extrinsics, then uu3d_camera_to_world -- one launch over all tracks' returned rows, one lane per joint and per root, float64 with
+    every operation rounded once (``camera.py``; ``camera_to_world`` is the launch alone; the rule in numpy: ``camera_to_world_host``) --,
+    then the pose filter and the root filter of ``smooth``, then ``rotations``.  Poses are rotated only and stay root-relative (the root
+    joint's zeros stay +0.0; ``poses + roots[:, None]`` is the world scene, with ``root_relative=False`` as well), a root with state 1 or
+    2 is rotated and translated, a root with state 0 stays zeros.  So the filters steady the world's axes, and the quaternions -- and a
+    BVH written from them -- stand in world axes.  It holds in every form of the call (``keyframes_only``, ``fps``, ``out_fps``,
+    ``valid`` / ``repair_joints``, ``keypoints``, ``interpolation="cubic"``; the poses re-read at the given frames' times for the root
+    solve with ``out_fps`` stay in camera space).  The result equals, bit for bit, ``one_euro_host`` and ``joint_rotations_host`` applied
+    to ``camera_to_world_host`` of the call with the ``Camera`` minus extrinsics and ``smooth=None, rotations=None``.  A ``Camera``
+    without extrinsics: the same launches, buffers and bits as before.  No accuracy is claimed.
+
     Steady output -- ``smooth``: None = today's call, the same bits, no further launch or buffer.  True (the defaults), a ``OneEuro`` or a
     pair (pose_filter, root_filter), either of which may be None (``check_smooth``; a root filter without ``camera``: ValueError): the
     returned poses -- and, with ``camera``, the returned roots -- go once through the One-Euro filter, an exponential smoother whose
@@ -372,16 +396,12 @@ def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, fl
         skeleton, known = opts.rigid
         bone_table = bone_lengths(out, lens, skeleton) if known is None else _upload(known, np.float64, out.device)
         out = fix_bones(out, lens, bone_table, skeleton)
-    # pose filter: what is returned is the poses, or the poses filtered; the roots are solved from the unfiltered ones
     shown = out
     if opts.pose_filter is not None or opts.root_filter is not None:
         out_rate = model_fps if fps is None else (rates if out_fps is None else frame_rates(out_fps, len(tracks)))
-    if opts.pose_filter is not None:
-        shown = one_euro(out, lens, out_rate, opts.pose_filter)
     sizes = [int(n) for n in lens]
-    poses = list(torch.split(shown, sizes, 0))
-    # roots: solved at the given frames, joined to a trajectory that is read at the returned frames
-    placed = ()
+    # roots: solved at the given frames, joined to a trajectory that is read at the returned frames -- in camera space, from the unfiltered poses
+    roots = root_state = None
     if camera is not None:
         def reread(at):                                               # the same motion at the given frames' times (``out_fps``)
             again = assemble(plan_at(frame_idx, 1 if stride is None else stride, at, rows=rows))
@@ -390,6 +410,15 @@ def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, fl
                                                 out_fps, model_fps, reread)
         solved_roots, solved = solve_roots(at_given, table.source[0], opts.cameras, table.source[1], opts.min_root_joints, lens=given)
         roots, root_state = root_trajectory(solved_roots, solved, given, where)
+    # world space: poses and roots to world axes, one launch over all tracks' returned rows -- everything behind reads the world scene
+    if opts.world is not None:
+        shown, roots = camera_to_world_rows(out, roots, root_state, opts.world, lens)
+    # filters: what is returned is the poses and roots, or the same filtered
+    if opts.pose_filter is not None:
+        shown = one_euro(shown, lens, out_rate, opts.pose_filter)
+    poses = list(torch.split(shown, sizes, 0))
+    placed = ()
+    if camera is not None:
         if opts.root_filter is not None:
             roots = one_euro(roots, lens, out_rate, opts.root_filter, state=root_state)
         placed = (list(torch.split(roots, sizes, 0)), list(torch.split(root_state, sizes, 0)))

@@ -84,7 +84,8 @@ module's docstring; every name is importable from here as before:
     smooth.py     steady output: ``StreamSession(..., smooth=F)`` (``LiveOneEuro``, ``LiveOneEuroHost``)
     bones.py      live constant bone lengths: ``StreamSession(..., bones=B)`` (``LiveBonesHost``)
     rotations.py  live joint rotations: ``StreamSession(..., rotations=R)`` (uu3d_joint_rotations as the tick's last launch)
-    camera.py     lens distortion: ``StreamSession(..., camera=Camera(fx, fy, cx, cy, distortion=...))`` (uu3d_undistort_points as the tick's first launch)
+    camera.py     lens distortion: ``StreamSession(..., camera=Camera(fx, fy, cx, cy, distortion=...))`` (uu3d_undistort_points as the tick's first launch);
+                  world space: ``StreamSession(..., camera=Camera(..., orientation=, translation=))`` (uu3d_camera_to_world behind uu3d_stream_root)
 The refusals these options share with ``predict_tracks`` are ``options.stage_options``; the ones only a session has are ``_init_plan``'s.
 
 The end of a track -- ``finish(slots)``: a session with lookahead a has not returned the poses of a track's last a frames when the track
@@ -118,7 +119,8 @@ from ._capi import ptr as _ptr
 # (noqa: F401 below -- re-exported: every name this module had before the stages became modules of their own)
 from .associate import ASSOCIATION_DEFAULTS, check_association
 from .bones import Bones, LiveBonesHost, _bone_offsets, check_bones, fix_bones_host, skeleton_of  # noqa: F401
-from .camera import Camera, distort_points_host, plain_camera, undistort_points, undistort_points_host  # noqa: F401
+from .camera import (Camera, camera_to_world_host, distort_points_host, extrinsics_from_opencv, plain_camera, undistort_points,  # noqa: F401
+                     undistort_points_host, world_to_camera_host)
 from .cli import add_track_options, bones_option, input_joints, smooth_option, split_scores, track_keywords  # noqa: F401
 from .keypoints import KEYPOINT_PRESETS, check_keypoint_inputs, keypoint_map  # noqa: F401
 from .options import check_interpolation, stage_options
@@ -260,6 +262,16 @@ class StreamSession(object):
         ``camera=(fx, fy, cx, cy)`` returns for ``predict.undistort_points_host`` of the frames.  A point that is not accepted is
         (NaN, NaN): ``missed_detections=True`` (or ``repair_joints``) is the companion option.  ``push`` still never waits, ``captures``
         stays 1; ``reset``, ``finish`` and the replays need nothing new.  Without distortion: the tuple's session, bit for bit.
+        A ``predict.Camera(..., orientation=(w, x, y, z), translation=(tx, ty, tz))`` -- one, one per slot, or with ``detections`` one; a
+        list of ``Camera``s with and without extrinsics: ValueError --: "World space" (``camera.py``).  uu3d_camera_to_world joins the
+        launch table directly behind uu3d_stream_root, in front of the smoothers and the rotations: out of place and stateless, all
+        slots at every tick, from the camera-space pose the root solve read and ``_roots`` / ``_root_flag`` into two buffers of the
+        session, which the filters and uu3d_joint_rotations read and ``push`` / ``push_detections`` return.  The root solve's held
+        state stays in camera space; a slot that is not fresh gets its previous bits again.  ``raw_poses`` / ``raw_roots`` are then the
+        unfiltered WORLD buffers, ``camera_poses`` / ``camera_roots`` the camera-space ones; ``finish`` runs the same step behind
+        uu3d_stream_root_drain (``drain_raw_*`` / ``drain_camera_*`` likewise).  ``push`` still never waits, ``captures`` stays 1,
+        ``reset`` and births need nothing new.  Every push returns, bit for bit, ``predict.camera_to_world_host`` of what the session
+        without extrinsics returns.  Without extrinsics: that session, the same launches, buffers and bits.
         ``smooth`` (keyword only, from ``options`` as well): None = the poses and roots as they are solved (the session above, bit for
         bit).  True, a ``predict.OneEuro`` or a pair (pose_filter, root_filter), either of which may be None (``predict.check_smooth``; a
         root filter without ``camera``: ValueError): the module docstring's "Steady output" -- ``push`` / ``push_detections`` return the
@@ -312,6 +324,7 @@ class StreamSession(object):
         self.bones, self.pose_filter, self.root_filter, self.keypoints = opts.rigid, opts.pose_filter, opts.root_filter, opts.keypoints
         self.cameras, self.min_root_joints = opts.cameras, opts.min_root_joints
         self.lens = opts.lens                                        # (slots, 10) rows of uu3d_undistort_points, or None: nothing to undistort
+        self.world = opts.world                                      # (slots, 7) rows of uu3d_camera_to_world, or None: the scene stays in camera space
         self.smooth_rate = frame_rate(model_fps if fps is None else fps)     # the rate of the frames a push returns
         if self.bones is not None and out_fps is not None:
             raise ValueError("bones together with out_fps is not supported: a push then returns several rows per slot, and the live fix "
@@ -514,6 +527,14 @@ class StreamSession(object):
             self._bone_lengths = zeros((T, J), dtype=torch.float64)
             self._pose_shown = zeros((T, J, 3), dtype=torch.float32)
             self._result = (self._pose_shown,) + self._result[1:]
+        # world space: the extrinsics per slot and the two buffers of the world scene, which push returns in the camera-space ones' place
+        # and which the filters and the rotations read; the root solve and its held state stay in camera space
+        self._pose_world, self._roots_world = self._pose_shown, self._roots if self.cameras is not None else None
+        if self.world is not None:
+            self._world = torch.from_numpy(np.ascontiguousarray(self.world)).pin_memory().to(dev, non_blocking=True)
+            self._world_track = torch.arange(T, dtype=torch.int32, device=dev)
+            self._pose_world, self._roots_world = zeros((T, J, 3), dtype=torch.float32), zeros((T, 3), dtype=torch.float32)
+            self._result = (self._pose_world, self._result[1], self._roots_world) + self._result[3:]
         # steady output: a live One-Euro filter per filtered buffer -- its state block and the buffer push returns in the raw one's place
         self._pose_smoother = self._root_smoother = None
         if self.pose_filter is not None:
@@ -633,12 +654,16 @@ class StreamSession(object):
             last.append(self._bones_launch(active))
         if root is not None:                                         # behind the emit that wrote the pose it solves
             last.append(root)
-        # steady output: the last steps of all -- they read what the emit and the root solve wrote and write buffers of their own, so the
-        # root is solved against the unfiltered pose; their resets join the session's (also for a slot born on the device)
+        # world space: directly behind the root solve, in front of the filters and the rotations, which read its two buffers
+        if self.world is not None:
+            last.append(self._world_launch())
+        # steady output: the last steps of all -- they read what the emit and the root solve (with extrinsics: the world launch) wrote and
+        # write buffers of their own, so the root is solved against the unfiltered pose; their resets join the session's (also for a slot
+        # born on the device)
         if self._pose_smoother is not None:
-            last.append(self._pose_smoother.launch(self._pose_shown, self._source_frames, self._fresh, self._active))
+            last.append(self._pose_smoother.launch(self._pose_world, self._source_frames, self._fresh, self._active))
         if self._root_smoother is not None:
-            last.append(self._root_smoother.launch(self._roots, self._source_frames, self._fresh, self._active, self._root_flag))
+            last.append(self._root_smoother.launch(self._roots_world, self._source_frames, self._fresh, self._active, self._root_flag))
         # joint rotations: the last step of all -- it reads the pose buffer push returns, whichever stage wrote it
         if self.rotations is not None:
             last.append(self._rotations_launch())
@@ -649,6 +674,14 @@ class StreamSession(object):
         return (self._lib.uu3d_joint_rotations, (_ptr(self._result[0]), self.slots, int(self._kp.shape[1]), _ptr(tree), self.rotations.depth,
                                                  _ptr(rest), _ptr(self._fresh), _ptr(self._rot_local), _ptr(self._rot_global),
                                                  _ptr(self._rot_flags)))
+
+    def _world_launch(self):
+        """uu3d_camera_to_world as a launch-table entry: the camera-space pose the root solve read and the root it wrote -> the session's
+        two world buffers.  Out of place and stateless, all slots at every tick: a slot that is not fresh holds its camera-space bits, so
+        it gets its world bits again -- nothing is transformed twice."""
+        T, J = self.slots, int(self._kp.shape[1])
+        return (self._lib.uu3d_camera_to_world, (_ptr(self._pose_shown), _ptr(self._pose_world), _ptr(self._roots), _ptr(self._root_flag),
+                                                 _ptr(self._roots_world), T, J, _ptr(self._world_track), T, _ptr(self._world)))
 
     def _bones_launch(self, active):
         """uu3d_stream_bones as a launch-table entry: the emitted poses -> the rebuilt ones; ``active``: the slots that may take a sample."""
@@ -909,6 +942,8 @@ class StreamSession(object):
             parts += [("roots", self._roots, (3,), torch.float32), ("root_state", None, (), torch.uint8)]
         if self.bones is not None:
             parts.append(("fixed_poses", self._pose_shown, (J, 3), torch.float32))
+        if self.world is not None:
+            parts += [("world_poses", self._pose_world, (J, 3), torch.float32), ("world_roots", self._roots_world, (3,), torch.float32)]
         if fp is not None:
             parts.append(("filtered_poses", fp.out, (J, 3), torch.float32))
         if fr is not None:
@@ -925,9 +960,9 @@ class StreamSession(object):
             rows[name] = (self._drain_rows[off:off + n].view(dt).view((T, a) + shape) if a > 0 else
                           torch.zeros((T, 0) + shape, dtype=dt, device=dev))
         self._drain_named = rows
-        result = (rows.get("filtered_poses", rows.get("fixed_poses", rows["poses"])), rows["fresh"].view(torch.bool))
+        result = (rows.get("filtered_poses", rows.get("world_poses", rows.get("fixed_poses", rows["poses"]))), rows["fresh"].view(torch.bool))
         if camera:
-            result += (rows.get("filtered_roots", rows["roots"]), rows["root_state"])
+            result += (rows.get("filtered_roots", rows.get("world_roots", rows["roots"])), rows["root_state"])
         result += tuple(rows[name] for name in ("rotations", "global_rotations") if name in rows)
         self._drain_result = result
         if a == 0:
@@ -946,10 +981,12 @@ class StreamSession(object):
         if camera:
             steps.append((lib.uu3d_stream_root_drain, (T, J, a, _ptr(self._root_state), dstate, chosen, fresh, _ptr(self._pose_shown), _ptr(self._cams),
                                                        self.min_root_joints, _ptr(self._roots), _ptr(self._root_flag))))
+        if self.world is not None:                                   # the same step as in a tick, behind the drain's root solve
+            steps.append(self._world_launch())
         if fp is not None:                                           # the filters as they are: the virtual counter, the chosen slots as `active`
-            steps.append(fp.launch(self._pose_shown, self._virtual_frames, self._fresh, self._drain_mask))
+            steps.append(fp.launch(self._pose_world, self._virtual_frames, self._fresh, self._drain_mask))
         if fr is not None:
-            steps.append(fr.launch(self._roots, self._virtual_frames, self._fresh, self._drain_mask, self._root_flag))
+            steps.append(fr.launch(self._roots_world, self._virtual_frames, self._fresh, self._drain_mask, self._root_flag))
         if self.rotations is not None:                               # the same step as in a tick
             steps.append(self._rotations_launch())
         floats = [(src, rows[name], int(np.prod(shape))) for name, src, shape, _ in parts if src is not None]
@@ -1058,12 +1095,26 @@ class StreamSession(object):
     @property
     def drain_raw_poses(self):
         """(slots, lookahead, J, 3) float32 on the device: the poses of the last ``finish`` as the drain ticks emitted them, unfiltered -- in
-        a session without ``smooth`` the buffer ``finish`` returns."""
-        return self._drain_rows_of("poses", "")
+        a session without ``smooth`` the buffer ``finish`` returns.  A session with extrinsics: the unfiltered WORLD rows, as ``raw_poses``."""
+        return self._drain_rows_of("poses" if self.world is None else "world_poses", "")
 
     @property
     def drain_raw_roots(self):
-        """(slots, lookahead, 3) float32 on the device (sessions with ``camera``): the roots of the last ``finish``, unfiltered."""
+        """(slots, lookahead, 3) float32 on the device (sessions with ``camera``): the roots of the last ``finish``, unfiltered; with
+        extrinsics the unfiltered WORLD rows, as ``raw_roots``."""
+        return self._drain_rows_of("roots" if self.world is None else "world_roots", "with camera")
+
+    @property
+    def drain_camera_poses(self):
+        """(slots, lookahead, J, 3) float32 on the device (sessions with ``camera``): the poses of the last ``finish`` in camera space, as
+        the drain's root solve read them -- ``camera_poses`` per drained row."""
+        if self.cameras is None:
+            raise AttributeError("drain_camera_poses needs a session with camera")
+        return self._drain_rows_of("poses" if self.bones is None else "fixed_poses", "")
+
+    @property
+    def drain_camera_roots(self):
+        """(slots, lookahead, 3) float32 on the device (sessions with ``camera``): the roots of the last ``finish`` in camera space."""
         return self._drain_rows_of("roots", "with camera")
 
     @property
@@ -1080,16 +1131,34 @@ class StreamSession(object):
     def raw_poses(self):
         """(slots, J, 3) float32 on the device: the poses as the tick emits them, the model's output, unfiltered and with the bones as
         the network gave them -- in a session without ``smooth`` and ``bones`` the buffer ``push`` returns.  Not with ``out_fps``
-        (AttributeError)."""
+        (AttributeError).  A session whose ``Camera`` has extrinsics: the unfiltered WORLD poses -- what uu3d_camera_to_world wrote and
+        the pose filter reads (with ``bones`` the rebuilt poses in world axes); ``camera_poses`` is the camera-space buffer."""
         if self.max_out is not None:
             raise AttributeError("raw_poses: a session with out_fps returns several rows per slot")
-        return self._out
+        return self._out if self.world is None else self._pose_world
 
     @property
     def raw_roots(self):
-        """(slots, 3) float32 on the device (sessions with ``camera``): the roots as they are solved, unfiltered."""
+        """(slots, 3) float32 on the device (sessions with ``camera``): the roots as they are solved, unfiltered; with extrinsics the
+        unfiltered WORLD roots, which the root filter reads (``camera_roots`` is the camera-space buffer)."""
         if self.cameras is None:
             raise AttributeError("raw_roots needs a session with camera")
+        return self._roots_world
+
+    @property
+    def camera_poses(self):
+        """(slots, J, 3) float32 on the device (sessions with ``camera``): the poses in CAMERA space as the root solve read them (with
+        ``bones`` the rebuilt ones), unfiltered -- without extrinsics the buffer the pose filter reads."""
+        if self.cameras is None:
+            raise AttributeError("camera_poses needs a session with camera")
+        return self._pose_shown
+
+    @property
+    def camera_roots(self):
+        """(slots, 3) float32 on the device (sessions with ``camera``): the roots in CAMERA space as they are solved, unfiltered --
+        without extrinsics the same tensor as ``raw_roots``."""
+        if self.cameras is None:
+            raise AttributeError("camera_roots needs a session with camera")
         return self._roots
 
     @property
