@@ -720,6 +720,53 @@ int uu3d_camera_to_world(const float* poses_dev, float* poses_out_dev, const flo
                          const double* extrinsics_dev, void* stream);
 
 /*
+ * SEVERAL VIEWS (predict.fuse_views, predict.solve_view_roots, predict.predict_views): V calibrated cameras, 1 <= V <= 8, see the same
+ * person at the same, time-synchronised frames.  WORLD SPACE has put every view's root-relative pose into one frame; the two calls here
+ * join them to one pose per frame and solve ONE world root per frame from all views' 2D keypoints at once, which takes the depth
+ * ambiguity of ABSOLUTE ROOT POSITION away: with a second view the model's scale error no longer goes into the depth.
+ * predict.fuse_views_host and predict.solve_view_roots_host are the same rules in numpy, bit for bit.  No accuracy is claimed.
+ * All buffers are view-major: poses_dev (V, rows, J, 3) f32 in world axes, kp2d_dev (V, rows, J, 2) f32 -- the raw, undistorted
+ * coordinates in the model's layout, as ABSOLUTE ROOT POSITION reads them --, joint_flags_dev (V, rows, J) u8 or NULL.  Joint j of view v
+ * at frame f is USED iff its flag is non-zero (NULL: every joint) and both of its coordinates are finite.  View v SEES frame f iff at
+ * least min_joints (>= 2) of its joints are used there.  In float64 on the float32 inputs, every operation rounded once, no fused
+ * multiply-add, one final rounding to float32 (the poses) or none (the roots).
+ * FUSION.  Per frame, joint and channel: s = 0.0; for v ascending over the seeing views s = s + (double) pose_v; the fused value is
+ * (float)(s / (double) n), n the number of seeing views, and view_count = n.  No view sees the frame: the same mean over ALL V views and
+ * view_count = 0 (the network has upsampled over the gap in every view).  The root joint's zeros stay +0.0; NaN in, NaN out.
+ * ROOT.  The unknown is the world root T.  A camera is sixteen doubles: fx, fy, cx, cy, then the camera's axes in world coordinates r1,
+ * r2, r3 (the unit quaternion of WORLD SPACE applied to e_1, e_2, e_3 on the host), then its position t.  Over the seeing views in
+ * ascending order and their used joints in ascending order, with P the frame's fused pose widened from float32:
+ *     a = (u - cx) / fx    b = (v - cy) / fy    n = r1 - a * r3    m = r2 - b * r3    d = t - P_j
+ *     e = (n0 * d0 + n1 * d1) + n2 * d2        g = (m0 * d0 + m1 * d1) + m2 * d2
+ *     A_ik += (n_i * n_k + m_i * m_k) for ik = 00, 01, 02, 11, 12, 22        B_i += (n_i * e + m_i * g)
+ * (the normal equations of n . (T + P_j - t) = 0, m . (T + P_j - t) = 0), solved by cofactors:
+ *     c00 = A11 * A22 - A12 * A12    c01 = A02 * A12 - A01 * A22    c02 = A01 * A12 - A02 * A11
+ *     c11 = A00 * A22 - A02 * A02    c12 = A01 * A02 - A00 * A12    c22 = A00 * A11 - A01 * A01
+ *     det = (A00 * c00 + A01 * c01) + A02 * c02
+ *     x0 = (c00 * B0 + c01 * B1) + c02 * B2    x1 = (c01 * B0 + c11 * B1) + c12 * B2    x2 = (c02 * B0 + c12 * B1) + c22 * B2
+ *     T_i = x_i / det
+ * The frame is SOLVED iff at least one view sees it, det is finite and > 0, det > 2^-40 * ((A00 * A11) * A22), T is finite and every used
+ * joint of every seeing view lies in front of its camera: with w = (T + P_j) - t, (r3_0 * w0 + r3_1 * w1) + r3_2 * w2 > 0.  The root of
+ * a frame that is not solved is zeros.  (The rank guard: one view whose used joints share one pixel gives a matrix of rank 2, whose det
+ * is zero in exact arithmetic and rounding noise of either sign here, about 2^-52 of Hadamard's bound A00 * A11 * A22.)  uu3d_root_trajectory joins the solved frames of a person as it joins those of a track.
+ *
+ *   uu3d_fuse_views(poses_dev, kp2d_dev 8-byte aligned, joint_flags_dev or NULL, views, rows, J, min_joints, fused_dev (rows, J, 3) f32,
+ *       never poses_dev, view_count_dev (rows) u8, sees_dev (views, rows) u8, stream): one launch of 256-thread blocks, one lane per (frame,
+ *       joint), one 12-byte store per lane; the lane of joint 0 also writes the frame's view_count and sees bytes.
+ *   uu3d_solve_view_roots(fused_dev (rows, J, 3) f32, kp2d_dev, joint_flags_dev or NULL, views, rows, J, cameras_dev (views, 16) f64,
+ *       min_joints, roots_dev (rows, 3) f64, solved_dev (rows) u8, stream): one launch, one lane per frame, the shape of uu3d_solve_roots.
+ *       A camera with a non-finite intrinsic, fx <= 0 or fy <= 0: the frames it sees are not solved.  The cameras belong to the views,
+ *       not to the rows, so there is no per-row index that could leave their range.
+ * Both: views > 8 or J > 64: UU3D_ERR_UNSUPPORTED.  rows == 0 is a no-op that returns UU3D_OK.  Every output element has one writer, no
+ * LDS, no atomics, the inputs are only read, nothing copies to the host or waits: bitwise repeatable.
+ */
+int uu3d_fuse_views(const float* poses_dev, const float* kp2d_dev, const uint8_t* joint_flags_dev, int32_t views, int64_t rows,
+                    int32_t num_keypoints, int32_t min_joints, float* fused_dev, uint8_t* view_count_dev, uint8_t* sees_dev, void* stream);
+int uu3d_solve_view_roots(const float* fused_dev, const float* kp2d_dev, const uint8_t* joint_flags_dev, int32_t views, int64_t rows,
+                          int32_t num_keypoints, const double* cameras_dev, int32_t min_joints, double* roots_dev, uint8_t* solved_dev,
+                          void* stream);
+
+/*
  * ANY FRAME RATE (predict.predict_tracks(fps=...)): the front of YOUR OWN 2D TRACKS for tracks that were not filmed at the rate the model
  * was trained for.  The table holds the MODEL's time grid: row `row` (track row_track_dev[row]) is model frame k of its track, which sits at
  * source position p_k = k * fps / model_fps.  The host works the positions out in exact integer arithmetic (predict.resample_plan) and

@@ -54,6 +54,7 @@ EXPORTED_SYMBOLS = (
     "uu3d_stream_timed_emit_cubic", "uu3d_stream_timed_emit_multi_cubic",
     "uu3d_undistort_points",
     "uu3d_camera_to_world",
+    "uu3d_fuse_views", "uu3d_solve_view_roots",
 )
 # include/uu3d_ops.h
 OPS_SYMBOLS = (
@@ -377,6 +378,10 @@ def load_library(path=None):
     lib.uu3d_undistort_points.argtypes = [vp, vp, i64, i32, vp, i32, vp, vp]
     lib.uu3d_camera_to_world.restype = C.c_int
     lib.uu3d_camera_to_world.argtypes = [vp, vp, vp, vp, vp, i64, i32, vp, i32, vp, vp]
+    lib.uu3d_fuse_views.restype = C.c_int
+    lib.uu3d_fuse_views.argtypes = [vp, vp, vp, i32, i64, i32, i32, vp, vp, vp, vp]
+    lib.uu3d_solve_view_roots.restype = C.c_int
+    lib.uu3d_solve_view_roots.argtypes = [vp, vp, vp, i32, i64, i32, vp, i32, vp, vp, vp]
     lib.uu3d_joint_rotations.restype = C.c_int
     lib.uu3d_joint_rotations.argtypes = [vp, i64, i32, vp, i32] + [vp] * 6
     lib.uu3d_joint_rotations_reset.restype = C.c_int

@@ -43,8 +43,11 @@ every name is importable from here as before:
                   ``undistort_points``, ``undistort_points_host``, ``distort_points_host``); world space: ``camera=Camera(..., orientation=(w, x,
                   y, z), translation=(tx, ty, tz))`` (uu3d_camera_to_world; ``camera_to_world``, ``camera_to_world_host``,
                   ``world_to_camera_host``, ``extrinsics_from_opencv``)
+    views.py      several calibrated cameras, one scene: ``predict_views(model, config, views, cameras)`` (uu3d_fuse_views, uu3d_solve_view_roots;
+                  ``fuse_views``, ``solve_view_roots``, ``fuse_views_host``, ``solve_view_roots_host``)
 """
 import argparse
+import types
 # (noqa: F401 below -- re-exported: every name this module had before the stages became modules of their own)
 from fractions import Fraction  # noqa: F401
 
@@ -74,6 +77,8 @@ from .smooth import (MAX_SMOOTH_CHANNELS, TWO_PI, OneEuro, _one_euro_rates, chec
                      one_euro_sample)
 from .tracks import (_device_track, _device_tracks, _host_array, _shape, _upload, assemble_tracks, assemble_tracks_cubic,  # noqa: F401
                      check_resolutions, keyframe_count, normalize_tracks, pose_table, resample_tracks, resampled_pose_table)
+from .views import (MAX_VIEWS, check_view_cameras, fuse_views, fuse_views_host, predict_views, solve_view_roots, solve_view_roots_host,  # noqa: F401
+                    view_rows)
 from .validity import (_device_joint_flags, _device_valid, _front_validity, _source_joint_flags, check_repair_joints, check_valid,  # noqa: F401
                        repair_joints, repair_joints_host)
 
@@ -342,55 +347,11 @@ def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, fl
     given frame, not at keyframes.  Anything else: ValueError.  Offline only: a live session would need one more predicted frame of
     lookahead, and ``run_eval``'s report keeps the reference's protocol.  No accuracy figure is claimed."""
     import torch
-    # options: the refusals shared with a live session (``options.stage_options``), then the ones only this call has
-    opts = stage_options(config, len(tracks), "track", root_relative, keypoints, camera, min_root_joints, smooth, bones, repair_joints, fps, out_fps,
-                         interpolation=interpolation, rotations=rotations)
-    if opts.keypoints is not None:
-        check_keypoint_inputs(opts.keypoints, [_shape(t)[1] if len(_shape(t)) == 3 else -1 for t in tracks])
-    if fps is not None and keyframes_only:
-        raise ValueError("fps and keyframes_only exclude each other: for a detector that ran on every k-th frame pass the given frames with "
-                         "fps=video_rate / k and out_fps=video_rate")
-    if valid is not None and not model.has_strided_input:
-        raise ValueError("valid needs a model with strided input: a missing frame becomes the learned masked token, which this model does not have")
-    check_repair_joints(repair_joints, valid)
-    check_valid(valid, [len(t) for t in tracks], joints=_shape(tracks[0])[1] if len(tracks) and len(_shape(tracks[0])) == 3 else None)
-    cfg = config.copy()
-    if mask_stride is None:
-        mask_stride = default_mask_stride(cfg)
-    cfg.MASK_STRIDE = mask_stride
-    flip = bool(cfg.EVAL_FLIP) if flip is None else bool(flip)
-    if keyframes_only and mask_stride is None:
-        raise ValueError("keyframes_only needs a mask stride")
-    # table: the given frames -> the pose table on the model's time grid; ``lens``: returned frames per track
-    given = np.array([len(t) for t in tracks], np.int64)
-    front = dict(valid=valid, repair_joints=repair_joints, keypoints=opts.keypoints, model=model, keep_source=camera is not None,
-                 distortion=opts.lens)
-    if fps is None:
-        table, lens = pose_table(tracks, model.device, resolutions, int(mask_stride) if keyframes_only else 0, lengths, **front)
-        model_lens = lens
-    else:
-        rates = frame_rates(fps, len(tracks))
-        table, model_lens, _ = resampled_pose_table(tracks, model.device, rates, resolutions, model_fps=model_fps, **front)
-        lens, positions = output_positions(given, rates, rates if out_fps is None else out_fps, model_fps)
-    # windows + forward: the raw predictions of the windows that are run, and the row of each frame's window among them (-1: not run)
-    raw, frame_idx, rows = _predicted_windows(model, cfg, table, mask_stride, flip, batch_size, depth, graph, reuse_frames)
-    # assemble plan: which two predicted frames every returned frame is read from, and how
-    stride = ev.prediction_stride(cfg)
-    cubic = opts.interpolation == "cubic" and stride is not None and stride > 1      # (every frame predicted: nothing lies between keyframes)
-    plan_at = evaluation.keyframe_plan_cubic_at if cubic else evaluation.keyframe_plan_at
-    if fps is not None:
-        plan = plan_at(frame_idx, 1 if stride is None else stride, positions, rows=rows)
-    elif cubic:
-        plan = evaluation.keyframe_plan_cubic(frame_idx, stride, rows=rows)
-    elif stride is None:
-        plan = rows, rows, np.zeros(len(rows), np.float64)
-    else:
-        plan = evaluation.keyframe_plan(frame_idx, stride, rows=rows)[:3]
-
-    def assemble(plan):                                               # (a cubic plan has five arrays, a linear one three)
-        return (assemble_tracks_cubic if cubic else assemble_tracks)(raw[0], raw[1] if flip else None, *plan, flip_order=cfg.AUGM_FLIP_KEYPOINT_ORDER,
-                                                                     root=int(cfg.ROOT_KEYTPOINT) if root_relative else -1)
-    out = assemble(plan)
+    front = _assembled_tracks(model, config, tracks, resolutions, mask_stride, flip, keyframes_only, reuse_frames, batch_size, root_relative, depth,
+                              lengths, graph, valid, fps, out_fps, model_fps, repair_joints, keypoints, camera, min_root_joints, smooth, bones,
+                              rotations, interpolation)
+    opts, table, given, lens, model_lens, rates, mask_stride = front.opts, front.table, front.given, front.lens, front.model_lens, front.rates, front.mask_stride
+    assemble, plan_at, frame_idx, rows, stride, out = front.assemble, front.plan_at, front.frame_idx, front.rows, front.stride, front.out
     # bones: constant bone lengths -- everything behind reads the fixed poses
     if opts.rigid is not None:
         skeleton, known = opts.rigid
@@ -429,6 +390,68 @@ def predict_tracks(model, config, tracks, resolutions=None, mask_stride=None, fl
         more = (list(torch.split(turned[0], sizes, 0)),) + ((list(torch.split(turned[2], sizes, 0)),) if opts.rotations.return_global else ())
         result = (result if isinstance(result, tuple) else (result,)) + more
     return result
+
+
+def _assembled_tracks(model, config, tracks, resolutions, mask_stride, flip, keyframes_only, reuse_frames, batch_size, root_relative, depth, lengths,
+                      graph, valid, fps, out_fps, model_fps, repair_joints, keypoints, camera, min_root_joints, smooth, bones, rotations, interpolation):
+    """The part of ``predict_tracks`` up to the assembly, shared with ``views.predict_views``: the options' checks, the front (undistort,
+    keypoint map, repair, normalise or resample), the windows, the forwards and uu3d_assemble_tracks -- the arguments as ``predict_tracks``
+    takes them -> a namespace: ``opts`` (``options.StageOptions``), ``table`` (``table.source``: the undistorted, mapped raw points and
+    the per-joint used flags, with ``camera``), ``given`` / ``lens`` / ``model_lens`` (frames given, returned and on the model's grid, per
+    track), ``rates`` (None without ``fps``), ``mask_stride``, ``out`` (the assembled poses of all tracks, (sum(lens), J, 3)) and what a
+    second assembly at other frame times needs (``assemble``, ``plan_at``, ``frame_idx``, ``rows``, ``stride``)."""
+    # options: the refusals shared with a live session (``options.stage_options``), then the ones only this call has
+    opts = stage_options(config, len(tracks), "track", root_relative, keypoints, camera, min_root_joints, smooth, bones, repair_joints, fps, out_fps,
+                         interpolation=interpolation, rotations=rotations)
+    if opts.keypoints is not None:
+        check_keypoint_inputs(opts.keypoints, [_shape(t)[1] if len(_shape(t)) == 3 else -1 for t in tracks])
+    if fps is not None and keyframes_only:
+        raise ValueError("fps and keyframes_only exclude each other: for a detector that ran on every k-th frame pass the given frames with "
+                         "fps=video_rate / k and out_fps=video_rate")
+    if valid is not None and not model.has_strided_input:
+        raise ValueError("valid needs a model with strided input: a missing frame becomes the learned masked token, which this model does not have")
+    check_repair_joints(repair_joints, valid)
+    check_valid(valid, [len(t) for t in tracks], joints=_shape(tracks[0])[1] if len(tracks) and len(_shape(tracks[0])) == 3 else None)
+    cfg = config.copy()
+    if mask_stride is None:
+        mask_stride = default_mask_stride(cfg)
+    cfg.MASK_STRIDE = mask_stride
+    flip = bool(cfg.EVAL_FLIP) if flip is None else bool(flip)
+    if keyframes_only and mask_stride is None:
+        raise ValueError("keyframes_only needs a mask stride")
+    # table: the given frames -> the pose table on the model's time grid; ``lens``: returned frames per track
+    given = np.array([len(t) for t in tracks], np.int64)
+    front = dict(valid=valid, repair_joints=repair_joints, keypoints=opts.keypoints, model=model, keep_source=camera is not None,
+                 distortion=opts.lens)
+    rates = None
+    if fps is None:
+        table, lens = pose_table(tracks, model.device, resolutions, int(mask_stride) if keyframes_only else 0, lengths, **front)
+        model_lens = lens
+    else:
+        rates = frame_rates(fps, len(tracks))
+        table, model_lens, _ = resampled_pose_table(tracks, model.device, rates, resolutions, model_fps=model_fps, **front)
+        lens, positions = output_positions(given, rates, rates if out_fps is None else out_fps, model_fps)
+    # windows + forward: the raw predictions of the windows that are run, and the row of each frame's window among them (-1: not run)
+    raw, frame_idx, rows = _predicted_windows(model, cfg, table, mask_stride, flip, batch_size, depth, graph, reuse_frames)
+    # assemble plan: which two predicted frames every returned frame is read from, and how
+    stride = ev.prediction_stride(cfg)
+    cubic = opts.interpolation == "cubic" and stride is not None and stride > 1      # (every frame predicted: nothing lies between keyframes)
+    plan_at = evaluation.keyframe_plan_cubic_at if cubic else evaluation.keyframe_plan_at
+    if fps is not None:
+        plan = plan_at(frame_idx, 1 if stride is None else stride, positions, rows=rows)
+    elif cubic:
+        plan = evaluation.keyframe_plan_cubic(frame_idx, stride, rows=rows)
+    elif stride is None:
+        plan = rows, rows, np.zeros(len(rows), np.float64)
+    else:
+        plan = evaluation.keyframe_plan(frame_idx, stride, rows=rows)[:3]
+
+    def assemble(plan):                                               # (a cubic plan has five arrays, a linear one three)
+        return (assemble_tracks_cubic if cubic else assemble_tracks)(raw[0], raw[1] if flip else None, *plan, flip_order=cfg.AUGM_FLIP_KEYPOINT_ORDER,
+                                                                     root=int(cfg.ROOT_KEYTPOINT) if root_relative else -1)
+    out = assemble(plan)
+    return types.SimpleNamespace(opts=opts, table=table, given=given, lens=lens, model_lens=model_lens, rates=rates, mask_stride=mask_stride,
+                                 out=out, assemble=assemble, plan_at=plan_at, frame_idx=frame_idx, rows=rows, stride=stride)
 
 
 def _predicted_windows(model, cfg, table, mask_stride, flip, batch_size, depth, graph, reuse_frames):
