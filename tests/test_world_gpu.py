@@ -248,8 +248,9 @@ def test_a_camera_without_extrinsics_launches_nothing_new():
     s = stream.StreamSession(model, cfg, slots=S, resolutions=RES, mask_stride=MS, flip=True, lookahead=2, camera=cams, smooth=True)
     try:
         names = [fn.__name__ for fn, args in s._tick_steps if args is not None]
-        assert "uu3d_camera_to_world" not in names and s.world is None and not hasattr(s, "_world")
-        assert s._pose_world is s._pose_shown and s._roots_world is s._roots and s.raw_roots is s.camera_roots and s.raw_poses is s.camera_poses
+        assert "uu3d_camera_to_world" not in names and s.world is None and not any(isinstance(st, stream.LiveWorld) for st in s._post)
+        world, camera = s._scenes["world"], s._scenes["camera"]
+        assert world.poses is camera.poses and world.roots is camera.roots and s.raw_roots is s.camera_roots and s.raw_poses is s.camera_poses
     finally:
         s.close()
     plain = stream.StreamSession(model, cfg, slots=S, resolutions=RES, mask_stride=MS, flip=True)

@@ -352,3 +352,29 @@ class LiveBonesHost(object):
 
     def drain(self, poses, fresh, chosen=None):
         return self.step(poses, fresh, chosen)
+
+
+class LiveBones(object):
+    """uu3d_stream_bones as an output-side stage of a ``StreamSession`` (the interface: ``smooth.LiveOneEuro``); ``given``: None = "track"."""
+
+    def __init__(self, slots, joints, skeleton, given, device):
+        import torch
+        self._lib = _capi.load_library()
+        size = int(self._lib.uu3d_stream_bones_bytes(slots, joints))
+        if size == 0:
+            raise ValueError(f"bones: slots = {slots}, joints = {joints} are out of uu3d_stream_bones' range")
+        self.slots, self.joints, self.depth = slots, joints, skeleton.depth
+        self._tables = skeleton.device_tables(device)
+        self._state = torch.zeros(size, dtype=torch.uint8, device=device)
+        self._given = None if given is None else _upload(given, given.dtype, device)
+        self.lengths = torch.zeros((slots, joints), dtype=torch.float64, device=device)
+        self.out = torch.zeros((slots, joints, 3), dtype=torch.float32, device=device)
+        self.outputs = (("poses", "fixed_poses", self.out),)
+
+    def launch(self, active, frames=None, drain_state=None):
+        parents, paths = self._tables
+        return (self._lib.uu3d_stream_bones, (self.slots, self.joints, _ptr(self._state), _ptr(parents), _ptr(paths), self.depth, _ptr(active),
+                                              _ptr(self.read.fresh), _ptr(self.read.poses), _ptr(self._given), _ptr(self.out), _ptr(self.lengths)))
+
+    def reset_launch(self):
+        return (self._lib.uu3d_stream_bones_reset, (self.slots, self.joints, _ptr(self._state)))

@@ -475,3 +475,22 @@ def camera_to_world(poses, roots, root_state, camera, lens=None):
     given = poses if poses is not None else roots
     rows, lens = _world_rows(camera, lens, int(given.shape[0]) if hasattr(given, "shape") and len(given.shape) else 0)
     return camera_to_world_rows(poses, roots, root_state, rows, lens)
+
+
+class LiveWorld(object):
+    """uu3d_camera_to_world as an output-side stage of a ``StreamSession`` (``smooth.LiveOneEuro``'s interface): stateless, all slots at every tick, nothing to reset."""
+
+    def __init__(self, slots, joints, rows, device):
+        import torch
+        self._lib = _capi.load_library()
+        self.slots, self.joints = slots, joints
+        self._world = _upload(rows, rows.dtype, device)
+        self._track = torch.arange(slots, dtype=torch.int32, device=device)
+        self.poses = torch.zeros((slots, joints, 3), dtype=torch.float32, device=device)
+        self.roots = torch.zeros((slots, 3), dtype=torch.float32, device=device)
+        self.outputs = (("poses", "world_poses", self.poses), ("roots", "world_roots", self.roots))
+
+    def launch(self, active=None, frames=None, drain_state=None):
+        read = self.read
+        return (self._lib.uu3d_camera_to_world, (_ptr(read.poses), _ptr(self.poses), _ptr(read.roots), _ptr(read.root_state), _ptr(self.roots),
+                                                 self.slots, self.joints, _ptr(self._track), self.slots, _ptr(self._world)))

@@ -307,3 +307,33 @@ class LiveRootHost(object):
         else:
             self.state = 2 if self.held is not None else 0
         return self.root.copy(), self.state
+
+
+class LiveRoot(object):
+    """uu3d_stream_root as an output-side stage of a ``StreamSession`` (the interface: ``smooth.LiveOneEuro``).  ``keypoints`` / ``flags``
+    (or None): the session's buffers of the pushed frame and its validity flags, which the tick's solve files -- no part of a scene."""
+
+    def __init__(self, slots, joints, lookahead, cameras, min_root_joints, keypoints, flags, device):
+        import torch
+        self._lib = _capi.load_library()
+        size = int(self._lib.uu3d_stream_root_bytes(slots, joints, lookahead))
+        if size == 0:
+            raise ValueError(f"camera: slots = {slots}, joints = {joints}, lookahead = {lookahead} are out of uu3d_stream_root's range")
+        self._shape, self.min_root_joints, self._keypoints, self._flags = (slots, joints, lookahead), min_root_joints, keypoints, flags
+        self._cams = _upload(cameras, cameras.dtype, device)
+        self._state = torch.zeros(size, dtype=torch.uint8, device=device)
+        self.roots = torch.zeros((slots, 3), dtype=torch.float32, device=device)
+        self.state = torch.zeros((slots,), dtype=torch.uint8, device=device)
+        self.outputs = (("roots", "roots", self.roots), ("root_state", "root_state", self.state))
+
+    def launch(self, active, frames, drain_state=None):
+        read, solve = self.read, (_ptr(self._cams), self.min_root_joints, _ptr(self.roots), _ptr(self.state))
+        if drain_state is not None:                                  # a drain tick files nothing and solves from the ring
+            return (self._lib.uu3d_stream_root_drain, self._shape + (_ptr(self._state), _ptr(drain_state), _ptr(active), _ptr(read.fresh),
+                                                                     _ptr(read.poses)) + solve)
+        per_joint = int(self._flags is not None and self._flags.dim() == 2)
+        return (self._lib.uu3d_stream_root, self._shape + (_ptr(self._state), _ptr(frames), _ptr(active), _ptr(read.fresh), _ptr(read.poses),
+                                                           _ptr(self._keypoints), _ptr(self._flags), per_joint) + solve)
+
+    def reset_launch(self):
+        return (self._lib.uu3d_stream_root_reset, self._shape + (_ptr(self._state),))

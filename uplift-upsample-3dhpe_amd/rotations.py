@@ -344,6 +344,30 @@ def joint_rotations(poses, skeleton="h36m17", rest="h36m17", primary=None, secon
     return (local, flags, glob) if want_global else (local, flags)
 
 
+class LiveRotations(object):
+    """uu3d_joint_rotations as an output-side stage of a ``StreamSession`` (``smooth.LiveOneEuro``'s interface): no state, the reset writes identities."""
+
+    def __init__(self, slots, joints, rotations, device):
+        import torch
+        self._lib = _capi.load_library()
+        self.slots, self.joints, self.depth = slots, joints, rotations.depth
+        self._tables = rotations.device_tables(device)
+        self.local = torch.zeros((slots, joints, 4), dtype=torch.float32, device=device)
+        self.flags = torch.zeros((slots, joints), dtype=torch.uint8, device=device)
+        self.glob = torch.zeros((slots, joints, 4), dtype=torch.float32, device=device) if rotations.return_global else None
+        self.outputs = (("extras", "rotations", self.local),) + (() if self.glob is None else (("extras", "global_rotations", self.glob),))
+        for _, _, q in self.outputs:
+            q[:, :, 0] = 1.0
+
+    def launch(self, active=None, frames=None, drain_state=None):
+        tree, rest = self._tables
+        return (self._lib.uu3d_joint_rotations, (_ptr(self.read.poses), self.slots, self.joints, _ptr(tree), self.depth, _ptr(rest),
+                                                 _ptr(self.read.fresh), _ptr(self.local), _ptr(self.glob), _ptr(self.flags)))
+
+    def reset_launch(self):
+        return (self._lib.uu3d_joint_rotations_reset, (self.slots, self.joints, _ptr(self.local), _ptr(self.glob), _ptr(self.flags)))
+
+
 # ---- host helpers ---------------------------------------------------------------------------------------------------------------------
 def quat_to_matrix(q):
     """(..., 4) unit quaternions (w, x, y, z) -> (..., 3, 3) float64 rotation matrices M with v' = M v (numpy, on the host)."""

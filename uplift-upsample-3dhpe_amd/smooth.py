@@ -298,10 +298,13 @@ class LiveOneEuro(object):
     ``step(values, frames, fresh, active, state=None, stream=None)``: device tensors -- values (slots, channels) float32 contiguous (only
     read), frames (slots,) int32, fresh / active / state (slots,) uint8 or bool -- -> ``out``; enqueues on ``stream`` (None: the current
     one) and never waits.  ``reset(slots=None)``: the given slots (indices; None = all) have taken no sample; ``reset_mask(mask)`` takes a
-    (slots,) uint8 device tensor instead.  ``launch(...)`` / ``reset_launch()``: the two calls as launch-table entries (function,
-    arguments up to the slot mask / the stream), for a session that replays them."""
+    (slots,) uint8 device tensor instead.
+    The interface of an output-side stage of a ``StreamSession`` (``field``: "poses" or "roots", what of a ``stream.Scene`` it filters):
+    ``outputs``, ((scene field, name of the drained rows, buffer), ...): what it puts into the scene; ``read``: the scene in front of
+    it, set by the session; ``launch(active, frames, drain_state=None)`` / ``reset_launch()``: the two calls as launch-table entries
+    (function, arguments up to the slot mask / the stream) -- with ``drain_state`` the one of a drain tick of ``finish``."""
 
-    def __init__(self, slots, channels, rate, filt, lookahead=0, device="cuda"):
+    def __init__(self, slots, channels, rate, filt, lookahead=0, device="cuda", field="poses"):
         import torch
         self.slots, self.channels, self.rate, self.filt, self.lookahead = _live_filter_arguments(slots, channels, rate, filt, lookahead)
         self._torch, self._lib = torch, _capi.load_library()
@@ -311,13 +314,19 @@ class LiveOneEuro(object):
             raise ValueError(f"slots = {self.slots}, channels = {self.channels} are out of uu3d_stream_one_euro's range")
         self._state = torch.zeros(size, dtype=torch.uint8, device=self.device)
         self.out = torch.zeros((self.slots, self.channels), dtype=torch.float32, device=self.device)
+        self.field = field                                            # (a scene's (slots, J, 3) poses are (slots, 3 J) channels)
+        self.outputs = ((field, "filtered_" + field, self.out.view(self.slots, -1, 3) if field == "poses" else self.out),)
 
     def _check(self, t, shape, dtypes, name):
         if tuple(t.shape) != shape or t.dtype not in dtypes or not t.is_contiguous() or t.device != self.out.device:
             raise ValueError(f"{name} must be a contiguous {shape} tensor of {' / '.join(str(d) for d in dtypes)} on {self.out.device}")
         return t
 
-    def launch(self, values, frames, fresh, active, state=None):
+    def launch(self, active, frames, drain_state=None):
+        read = self.read
+        return self._entry(getattr(read, self.field), frames, read.fresh, active, read.root_state if self.field == "roots" else None)
+
+    def _entry(self, values, frames, fresh, active, state=None):
         torch = self._torch
         T, flags = self.slots, (torch.uint8, torch.bool)
         if values.dim() < 1 or int(values.shape[0]) != T or values.numel() != T * self.channels:       # ((slots, J, 3) passes as (slots, 3 J))
@@ -341,7 +350,7 @@ class LiveOneEuro(object):
             _capi.check(self._lib, fn(*args, C.c_void_p(st.cuda_stream)), None)
 
     def step(self, values, frames, fresh, active, state=None, stream=None):
-        self._enqueue(self.launch(values, frames, fresh, active, state), stream)
+        self._enqueue(self._entry(values, frames, fresh, active, state), stream)
         return self.out
 
     def reset_mask(self, mask=None, stream=None):

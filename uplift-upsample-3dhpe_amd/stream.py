@@ -80,13 +80,15 @@ module's docstring; every name is importable from here as before:
     validity.py   live per-joint missed detections: ``StreamSession(..., repair_joints=G)`` (``LiveRepairHost``, ``MAX_LIVE_REPAIR``)
     keypoints.py  any skeleton: ``StreamSession(..., keypoints=M)``
     associate.py  per-frame detections: ``StreamSession(..., detections=D, max_age=, max_dist=, min_common=)`` and ``push_detections``
-    roots.py      live absolute root: ``StreamSession(..., camera=(fx, fy, cx, cy), min_root_joints=6)`` (``LiveRootHost``)
+    roots.py      live absolute root: ``StreamSession(..., camera=(fx, fy, cx, cy), min_root_joints=6)`` (``LiveRoot``, ``LiveRootHost``)
     smooth.py     steady output: ``StreamSession(..., smooth=F)`` (``LiveOneEuro``, ``LiveOneEuroHost``)
-    bones.py      live constant bone lengths: ``StreamSession(..., bones=B)`` (``LiveBonesHost``)
-    rotations.py  live joint rotations: ``StreamSession(..., rotations=R)`` (uu3d_joint_rotations as the tick's last launch)
+    bones.py      live constant bone lengths: ``StreamSession(..., bones=B)`` (``LiveBones``, ``LiveBonesHost``)
+    rotations.py  live joint rotations: ``StreamSession(..., rotations=R)`` (``LiveRotations``: uu3d_joint_rotations as the tick's last launch)
     camera.py     lens distortion: ``StreamSession(..., camera=Camera(fx, fy, cx, cy, distortion=...))`` (uu3d_undistort_points as the tick's first launch);
-                  world space: ``StreamSession(..., camera=Camera(..., orientation=, translation=))`` (uu3d_camera_to_world behind uu3d_stream_root)
+                  world space: ``StreamSession(..., camera=Camera(..., orientation=, translation=))`` (``LiveWorld``: uu3d_camera_to_world behind uu3d_stream_root)
 The refusals these options share with ``predict_tracks`` are ``options.stage_options``; the ones only a session has are ``_init_plan``'s.
+The output-side options (bones, root, world, the two filters, rotations) are device objects of one shape (``smooth.LiveOneEuro``); the
+session hands a ``Scene`` through them in that order and walks the list for its launch tables.  The input-side ones stay inline.
 
 The end of a track -- ``finish(slots)``: a session with lookahead a has not returned the poses of a track's last a frames when the track
 ends (the person leaves, the video stops).  ``finish`` returns them -- (slots, a, J, 3) and (slots, a) on the device -- and resets exactly
@@ -108,6 +110,7 @@ tick its own track ends; ``window_plan(drained=k)``, ``LiveRootHost.drain`` and 
                                                  [--smooth_root MIN_CUTOFF BETA D_CUTOFF] [--bones track|FILE.npy]
 """
 import argparse
+import collections
 import ctypes as C
 import functools
 import gc
@@ -118,8 +121,8 @@ from . import _capi
 from ._capi import ptr as _ptr
 # (noqa: F401 below -- re-exported: every name this module had before the stages became modules of their own)
 from .associate import ASSOCIATION_DEFAULTS, check_association
-from .bones import Bones, LiveBonesHost, _bone_offsets, check_bones, fix_bones_host, skeleton_of  # noqa: F401
-from .camera import (Camera, camera_to_world_host, distort_points_host, extrinsics_from_opencv, plain_camera, undistort_points,  # noqa: F401
+from .bones import Bones, LiveBones, LiveBonesHost, _bone_offsets, check_bones, fix_bones_host, skeleton_of  # noqa: F401
+from .camera import (Camera, LiveWorld, camera_to_world_host, distort_points_host, extrinsics_from_opencv, plain_camera, undistort_points,  # noqa: F401
                      undistort_points_host, world_to_camera_host)
 from .cli import add_track_options, bones_option, input_joints, smooth_option, split_scores, track_keywords  # noqa: F401
 from .keypoints import KEYPOINT_PRESETS, check_keypoint_inputs, keypoint_map  # noqa: F401
@@ -127,8 +130,8 @@ from .options import check_interpolation, stage_options
 from .predict import _load_model
 from .rates import (RatePlan, _rate_argument, frame_rate, max_lookahead, newest_model_frame, out_push_plan, out_push_plan_cubic,  # noqa: F401
                     push_plan, push_plan_cubic, rate_plan, session_strides)
-from .rotations import Rotations, check_rotations, joint_rotations_host  # noqa: F401
-from .roots import DEFAULT_MIN_ROOT_JOINTS, MAX_ROOT_JOINTS, LiveRootHost, check_cameras, check_min_root_joints, solve_roots_host  # noqa: F401
+from .rotations import LiveRotations, Rotations, check_rotations, joint_rotations_host  # noqa: F401
+from .roots import DEFAULT_MIN_ROOT_JOINTS, MAX_ROOT_JOINTS, LiveRoot, LiveRootHost, check_cameras, check_min_root_joints, solve_roots_host  # noqa: F401
 from .smooth import (MAX_SMOOTH_CHANNELS, LiveOneEuro, LiveOneEuroHost, OneEuro, _live_filter_arguments, check_smooth,  # noqa: F401
                      one_euro_sample)
 from .tracks import _host_array, check_resolutions
@@ -207,6 +210,30 @@ def _live_options(options, who, names=LIVE_OPTIONS):
     return tuple(options.get(name) for name in names)
 
 
+class Scene(collections.namedtuple("Scene", "poses fresh roots root_state extras")):
+    """What a push returns so far, as the output-side stages hand it on: ``poses`` (slots, J, 3) float32, ``fresh`` (slots,) uint8, ``roots``
+    (slots, 3) float32 and ``root_state`` (slots,) uint8 or both None (no camera), ``extras``: buffers appended behind them (quaternions)."""
+    __slots__ = ()
+
+    def as_result(self):
+        import torch
+        return (self.poses, self.fresh.view(torch.bool)) + (() if self.roots is None else (self.roots, self.root_state)) + self.extras
+
+
+def scenes(raw, stages, rows=None):
+    """Hand the raw scene through ``stages``, [(name of the scene it leaves, stage or None = absent)] in the tick's order -> {name: scene}: a stage
+    reads the scene in front of it and puts its ``outputs`` in place.  ``rows``: the drained rows of ``finish`` by name stand in for the buffers."""
+    named, scene = {"raw": raw}, raw
+    for name, stage in stages:
+        if stage is not None and rows is None:
+            stage.read = scene
+        for field, row, buffer in (() if stage is None else stage.outputs):
+            value = buffer if rows is None else rows[row]
+            scene = scene._replace(**{field: scene.extras + (value,) if field == "extras" else value})
+        named[name] = scene
+    return named
+
+
 class StreamSession(object):
 
     def __init__(self, model, config, slots, resolutions=None, mask_stride=None, flip=None, lookahead=0, root_relative=True, graph=True,
@@ -265,7 +292,7 @@ class StreamSession(object):
         A ``predict.Camera(..., orientation=(w, x, y, z), translation=(tx, ty, tz))`` -- one, one per slot, or with ``detections`` one; a
         list of ``Camera``s with and without extrinsics: ValueError --: "World space" (``camera.py``).  uu3d_camera_to_world joins the
         launch table directly behind uu3d_stream_root, in front of the smoothers and the rotations: out of place and stateless, all
-        slots at every tick, from the camera-space pose the root solve read and ``_roots`` / ``_root_flag`` into two buffers of the
+        slots at every tick, from the camera-space pose the root solve read and the root and state it wrote into two buffers of the
         session, which the filters and uu3d_joint_rotations read and ``push`` / ``push_detections`` return.  The root solve's held
         state stays in camera space; a slot that is not fresh gets its previous bits again.  ``raw_poses`` / ``raw_roots`` are then the
         unfiltered WORLD buffers, ``camera_poses`` / ``camera_roots`` the camera-space ones; ``finish`` runs the same step behind
@@ -415,7 +442,7 @@ class StreamSession(object):
         return lay, rlay, olay
 
     def _init_buffers(self, config, res, lay, rlay, olay):
-        """The state block and the buffers of a tick; then what a session with missed detections, with a rate and with an output rate adds."""
+        """The state block and the buffers of a tick; what missed detections, the input-side options and the rates add; the output-side stages and their scenes."""
         torch, lib, m = self._torch, self._lib, self.model
         a, dev = m.arch, m.device
         T, J, N, dt, H, K = self.slots, a.num_keypoints, a.num_frames, a.d_temporal, 2 if self.flip else 1, self.staged_frames
@@ -497,63 +524,23 @@ class StreamSession(object):
             self._emit_fresh = zeros((T,), dtype=torch.uint8)
             self._src_host = np.zeros(T, np.int64)                    # host mirror of the source counters; exact where _src_known
             self._src_known = np.ones(T, bool)
-        self._result = self._out, self._fresh.view(torch.bool)        # what push returns: the session's own buffers
-        if olay is not None:
+        if olay is not None:                                         # (a case of its own: every output-side option is refused with it)
             self._out_frames = view(int(olay.out_frames_offset), T, torch.int32)
             self._poses = zeros((T, self.max_out, J, 3), dtype=torch.float32)
             self._count = zeros((T,), dtype=torch.int32)
-            self._result = self._poses, self._count
-        # live absolute root: the cameras, the ring of raw frames and the held root per slot, what push returns beside poses and fresh
-        if self.cameras is not None:
-            self._cams = torch.from_numpy(self.cameras).pin_memory().to(dev, non_blocking=True)
-            size = int(lib.uu3d_stream_root_bytes(T, J, self.lookahead))
-            if size == 0:
-                raise ValueError(f"camera: slots = {T}, joints = {J}, lookahead = {self.lookahead} are out of uu3d_stream_root's range")
-            self._root_state = zeros(size, dtype=torch.uint8)
-            self._roots = zeros((T, 3), dtype=torch.float32)
-            self._root_flag = zeros((T,), dtype=torch.uint8)
-            self._result = self._result + (self._roots, self._root_flag)
-        # constant bone lengths: the tree tables, the state block (sums and counts), the given lengths, and the buffer of rebuilt poses that
-        # push returns in the raw one's place -- the root solve and the pose filter read it
-        self._pose_shown = self._out
-        if self.bones is not None:
-            sk, given = self.bones
-            self._bone_tables = sk.device_tables(dev)
-            size = int(lib.uu3d_stream_bones_bytes(T, J))
-            if size == 0:
-                raise ValueError(f"bones: slots = {T}, joints = {J} are out of uu3d_stream_bones' range")
-            self._bone_state = zeros(size, dtype=torch.uint8)
-            self._bone_given = None if given is None else torch.from_numpy(given).pin_memory().to(dev, non_blocking=True)
-            self._bone_lengths = zeros((T, J), dtype=torch.float64)
-            self._pose_shown = zeros((T, J, 3), dtype=torch.float32)
-            self._result = (self._pose_shown,) + self._result[1:]
-        # world space: the extrinsics per slot and the two buffers of the world scene, which push returns in the camera-space ones' place
-        # and which the filters and the rotations read; the root solve and its held state stay in camera space
-        self._pose_world, self._roots_world = self._pose_shown, self._roots if self.cameras is not None else None
-        if self.world is not None:
-            self._world = torch.from_numpy(np.ascontiguousarray(self.world)).pin_memory().to(dev, non_blocking=True)
-            self._world_track = torch.arange(T, dtype=torch.int32, device=dev)
-            self._pose_world, self._roots_world = zeros((T, J, 3), dtype=torch.float32), zeros((T, 3), dtype=torch.float32)
-            self._result = (self._pose_world, self._result[1], self._roots_world) + self._result[3:]
-        # steady output: a live One-Euro filter per filtered buffer -- its state block and the buffer push returns in the raw one's place
-        self._pose_smoother = self._root_smoother = None
-        if self.pose_filter is not None:
-            self._pose_smoother = LiveOneEuro(T, 3 * J, self.smooth_rate, self.pose_filter, self.lookahead, dev)
-            self._result = (self._pose_smoother.out.view(T, J, 3),) + self._result[1:]
-        if self.root_filter is not None:
-            self._root_smoother = LiveOneEuro(T, 3, self.smooth_rate, self.root_filter, self.lookahead, dev)
-            self._result = self._result[:2] + (self._root_smoother.out,) + self._result[3:]
-        # joint rotations: the tables of the rest pose and the quaternion buffers push appends -- identities before a slot's first pose
-        self._rot_local = self._rot_global = self._rot_flags = None
-        if self.rotations is not None:
-            self._rot_tables = self.rotations.device_tables(dev)
-            self._rot_local = zeros((T, J, 4), dtype=torch.float32)
-            self._rot_flags = zeros((T, J), dtype=torch.uint8)
-            self._rot_global = zeros((T, J, 4), dtype=torch.float32) if self.rotations.return_global else None
-            for q in (self._rot_local, self._rot_global):
-                if q is not None:
-                    q[:, :, 0] = 1.0
-            self._result = self._result + (self._rot_local,) + ((self._rot_global,) if self._rot_global is not None else ())
+            self._result = self._poses, self._count                   # what push returns: the session's own buffers
+        # the output-side options in the one order a tick runs them, each under the scene it leaves: ``push`` returns the last one
+        live = lambda option, make, *args, **field: None if option is None else make(T, *args, device=dev, **field)
+        self._pose_smoother = live(self.pose_filter, LiveOneEuro, 3 * J, self.smooth_rate, self.pose_filter, self.lookahead)
+        self._root_smoother = live(self.root_filter, LiveOneEuro, 3, self.smooth_rate, self.root_filter, self.lookahead, field="roots")
+        self._stages = [("fixed", live(self.bones, LiveBones, J, *(self.bones or ()))),
+                        ("camera", live(self.cameras, LiveRoot, J, self.lookahead, self.cameras, self.min_root_joints, self._kp, self._valid_in)),
+                        ("world", live(self.world, LiveWorld, J, self.world)), ("shown", self._pose_smoother), ("shown", self._root_smoother),
+                        ("shown", live(self.rotations, LiveRotations, J, self.rotations))]
+        self._post = [stage for _, stage in self._stages if stage is not None]
+        if olay is None:
+            self._scenes = scenes(Scene(self._out, self._fresh, None, None, ()), self._stages)
+            self._result = self._scenes["shown"].as_result()
         # the end of a track: nothing until the first ``finish`` (_init_drain)
         self._drain_result = self._drain_state = self._drain_graph = None
         self._drain_steps = []
@@ -564,8 +551,8 @@ class StreamSession(object):
           _tick_steps   the steps of one (sub-)tick, in order -- what the graph captures
           _push_before  / _push_after   the launches of a push around its sub-ticks (a session with a rate; not captured)
           _reset_call   the reset of the session's kind; the slot mask and the stream follow its arguments (_reset_more: what a session
-                        with repair_joints, a camera or smooth resets beside it)
-          _drain_steps  the steps of one drain tick (``finish``), built at the first ``finish`` by _init_drain -- a second captured graph"""
+                        with repair_joints, output-side stages, detections or a drain resets beside it)
+          _drain_steps  the steps of one drain tick (``finish``), built at the first ``finish`` by _init_drain -- a second captured graph; the output-side stages (``_post``) give their own entries"""
         lib, m = self._lib, self.model
         h, cfg, state = m._h, C.byref(self._cfg), _ptr(self._state)
         kp, res, order, active, staged = _ptr(self._kp), _ptr(self._res), _ptr(self._order), _ptr(self._active), _ptr(self._staged)
@@ -612,20 +599,10 @@ class StreamSession(object):
         if self.rate is None:
             self._tick_steps = (lens if self.detections is None else []) + mapping + self._tick_steps
         self._reset_call = (lib.uu3d_stream_reset, (h, cfg, state))
+        # the resets beside it: repair, then the stages in the order the options joined the session, which tests pin (each clears a block of its own; world has none)
         self._reset_more = [] if self.repair_joints is None else [(lib.uu3d_stream_repair_reset, (h, cfg, self.repair_joints, _ptr(self._repair_state)))]
-        root = None
-        if self.cameras is not None:                                 # live absolute root: the frame counters are those the pose's frame is counted in
-            T, J = self.slots, int(self._kp.shape[1])
-            root = (lib.uu3d_stream_root, (T, J, self.lookahead, _ptr(self._root_state), _ptr(self._source_frames), active, _ptr(self._fresh),
-                                           _ptr(self._pose_shown), kp, _ptr(self._valid_in), int(self._valid_in is not None and self._valid_in.dim() == 2),
-                                           _ptr(self._cams), self.min_root_joints, _ptr(self._roots), _ptr(self._root_flag)))
-            self._reset_more = self._reset_more + [(lib.uu3d_stream_root_reset, (T, J, self.lookahead, _ptr(self._root_state)))]
-        self._reset_more = self._reset_more + [f.reset_launch() for f in (self._pose_smoother, self._root_smoother) if f is not None]
-        if self.bones is not None:
-            self._reset_more = self._reset_more + [(lib.uu3d_stream_bones_reset, (self.slots, int(self._kp.shape[1]), _ptr(self._bone_state)))]
-        if self.rotations is not None:                              # (no state: the reset writes identities into the returned buffers)
-            self._reset_more = self._reset_more + [(lib.uu3d_joint_rotations_reset, (self.slots, int(self._kp.shape[1]), _ptr(self._rot_local),
-                                                                                     _ptr(self._rot_global), _ptr(self._rot_flags)))]
+        bones, root, _, pose_filter, root_filter, rotations = (stage for _, stage in self._stages)
+        self._reset_more += [stage.reset_launch() for stage in (root, pose_filter, root_filter, bones, rotations) if stage is not None]
         # per-frame detections: the association in front of everything -- it writes the frame, the flags, `active` and the born mask --, then
         # the resets of the slots born at this tick, with the mask on the device
         if self.detections is not None:
@@ -648,47 +625,9 @@ class StreamSession(object):
             self._push_after = [(lib.uu3d_stream_timed_emit_multi_cubic if cubic else lib.uu3d_stream_timed_emit_multi,
                                  (h, cfg, rate, outp, state, _ptr(self._poses), _ptr(self._count)))]
             self._reset_call = (lib.uu3d_stream_out_reset, (h, cfg, rate, outp, state))
+        # the output-side stages behind the emit that wrote the pose they read (with a rate: the timed emit), in the tick's order
         last = self._tick_steps if self.rate is None else self._push_after
-        # constant bone lengths: directly behind the emit, in front of the root solve and the filters, which read its buffer
-        if self.bones is not None:
-            last.append(self._bones_launch(active))
-        if root is not None:                                         # behind the emit that wrote the pose it solves
-            last.append(root)
-        # world space: directly behind the root solve, in front of the filters and the rotations, which read its two buffers
-        if self.world is not None:
-            last.append(self._world_launch())
-        # steady output: the last steps of all -- they read what the emit and the root solve (with extrinsics: the world launch) wrote and
-        # write buffers of their own, so the root is solved against the unfiltered pose; their resets join the session's (also for a slot
-        # born on the device)
-        if self._pose_smoother is not None:
-            last.append(self._pose_smoother.launch(self._pose_world, self._source_frames, self._fresh, self._active))
-        if self._root_smoother is not None:
-            last.append(self._root_smoother.launch(self._roots_world, self._source_frames, self._fresh, self._active, self._root_flag))
-        # joint rotations: the last step of all -- it reads the pose buffer push returns, whichever stage wrote it
-        if self.rotations is not None:
-            last.append(self._rotations_launch())
-
-    def _rotations_launch(self):
-        """uu3d_joint_rotations as a launch-table entry: the returned poses -> their quaternions, the fresh slots only."""
-        tree, rest = self._rot_tables
-        return (self._lib.uu3d_joint_rotations, (_ptr(self._result[0]), self.slots, int(self._kp.shape[1]), _ptr(tree), self.rotations.depth,
-                                                 _ptr(rest), _ptr(self._fresh), _ptr(self._rot_local), _ptr(self._rot_global),
-                                                 _ptr(self._rot_flags)))
-
-    def _world_launch(self):
-        """uu3d_camera_to_world as a launch-table entry: the camera-space pose the root solve read and the root it wrote -> the session's
-        two world buffers.  Out of place and stateless, all slots at every tick: a slot that is not fresh holds its camera-space bits, so
-        it gets its world bits again -- nothing is transformed twice."""
-        T, J = self.slots, int(self._kp.shape[1])
-        return (self._lib.uu3d_camera_to_world, (_ptr(self._pose_shown), _ptr(self._pose_world), _ptr(self._roots), _ptr(self._root_flag),
-                                                 _ptr(self._roots_world), T, J, _ptr(self._world_track), T, _ptr(self._world)))
-
-    def _bones_launch(self, active):
-        """uu3d_stream_bones as a launch-table entry: the emitted poses -> the rebuilt ones; ``active``: the slots that may take a sample."""
-        parents, paths = self._bone_tables
-        return (self._lib.uu3d_stream_bones, (self.slots, int(self._kp.shape[1]), _ptr(self._bone_state), _ptr(parents), _ptr(paths),
-                                              self.bones[0].depth, active, _ptr(self._fresh), _ptr(self._out), _ptr(self._bone_given),
-                                              _ptr(self._pose_shown), _ptr(self._bone_lengths)))
+        last += [stage.launch(self._active, self._source_frames) for stage in self._post]
 
     # ---- the steps of a tick, on ``stream`` ------------------------------------------------------------------------------------------
     def _run(self, steps, stream):
@@ -707,11 +646,8 @@ class StreamSession(object):
         self._run([(lib.uu3d_frame_features, (m._h, _ptr(zero), 1, _ptr(self._table[self._zero_row:]), _ptr(self._fws),
                                               C.c_size_t(self._fws.numel()), 0))], torch.cuda.current_stream(m.device))
 
-    def _tick(self, stream):
-        self._run(self._tick_steps, stream)
-
-    def _capture(self):
-        """One warm-up tick with every slot inactive (nothing advances), then the capture: a linear chain on one stream."""
+    def _capture_steps(self, steps, warm):
+        """``warm(side)``, a warm-up run in which nothing advances, on a side stream, then the capture of ``steps``: a linear chain on it -> the graph."""
         torch = self._torch
         dev = self.model.device
         side = torch.cuda.Stream(device=dev)
@@ -721,38 +657,62 @@ class StreamSession(object):
         gc.disable()
         try:
             with torch.cuda.stream(side):
-                self._active.zero_()
-                if self.detections is not None:                      # (no detection, no slot alive: the association changes nothing either)
-                    self._det_count.zero_()
-                    self._det_count_full = False
-                self._tick(side)
-                self._active.fill_(1)
+                warm(side)
             side.synchronize()
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, stream=side):
-                self._tick(side)
-            self._graph = g
+                self._run(steps, side)
             self.captures += 1
         finally:
             if gc_was_on:
                 gc.enable()
         torch.cuda.current_stream(dev).wait_stream(side)
+        return g
+
+    def _capture(self):
+        """The tick's graph; the warm-up tick has every slot inactive."""
+        def warm(side):
+            self._active.zero_()
+            if self.detections is not None:                          # (no detection, no slot alive: the association changes nothing either)
+                self._det_count.zero_()
+                self._det_count_full = False
+            self._run(self._tick_steps, side)
+            self._active.fill_(1)
+        self._graph = self._capture_steps(self._tick_steps, warm)
         self.reset()
 
     # ---- public ---------------------------------------------------------------------------------------------------------------------
-    def _flags(self, flags, name, joints=None):
-        """(slots,) flags from the host or the device -> a uint8 tensor, pinned when it is on the host.  ``joints`` = J: (slots, J) passes as
-        well and (slots,) comes back as (slots, 1) -- one flag for all joints of a slot, for a copy that broadcasts on the device."""
+    def _flags(self, flags, name, joints=None, rows=None):
+        """(rows,) flags from the host or the device (``rows``: None = slots) -> a uint8 tensor, pinned when it is on the host.  ``joints`` = J:
+        (rows, J) passes as well and (rows,) comes back as (rows, 1) -- one flag for all joints of a row, for a copy that broadcasts on the device."""
         torch = self._torch
+        n = self.slots if rows is None else rows
         if isinstance(flags, torch.Tensor):
             f = flags.to(torch.uint8) if flags.dtype != torch.bool else flags.view(torch.uint8)
         else:
             f = torch.from_numpy(np.ascontiguousarray(np.asarray(flags) != 0).view(np.uint8))
-        if tuple(f.shape) != (self.slots,) and (joints is None or tuple(f.shape) != (self.slots, joints)):
-            raise ValueError(f"{name} must be ({self.slots},)" + ("" if joints is None else f" or ({self.slots}, {joints})"))
+        if tuple(f.shape) != (n,) and (joints is None or tuple(f.shape) != (n, joints)):
+            raise ValueError(f"{name} must be ({n},)" + ("" if joints is None else f" or ({n}, {joints})"))
         if joints is not None and f.dim() == 1:
-            f = f.reshape(self.slots, 1) if f.is_cuda else f.reshape(self.slots, 1).repeat(1, joints)
+            f = f.reshape(n, 1) if f.is_cuda else f.reshape(n, 1).repeat(1, joints)
         return f if f.is_cuda else f.contiguous().pin_memory()
+
+    def _sync_weights(self):
+        """Weights changed since the last tick: the packs are rewritten on this stream, and the zero row's features with them."""
+        m = self.model
+        if m._weights_dirty or getattr(m, "_pending_assigns", False):
+            m._sync_from_trainer()
+            with self._torch.cuda.device(m.device):
+                self._zero_features()
+
+    def _host_frame(self, x, like, name):
+        """What a push files, checked against the buffer ``like`` -> a tensor to copy from: host input goes through pinned memory."""
+        torch = self._torch
+        if not isinstance(x, torch.Tensor):
+            x = torch.from_numpy(np.ascontiguousarray(x, np.float32))
+        if tuple(x.shape) != tuple(like.shape):
+            raise ValueError(f"{name} must be {tuple(like.shape)}, got {tuple(x.shape)}")
+        return x if x.is_cuda else x.to(torch.float32).contiguous().pin_memory()
 
     def push(self, kp2d, active=None, valid=None):
         """One tick: ``kp2d`` (slots, J, 2) -- (slots, K_in, 2) in a session with ``keypoints`` --, a host array or a tensor on the host or the device; ``active`` (slots,) bools or None = every slot
@@ -783,24 +743,14 @@ class StreamSession(object):
         A session with ``smooth``: the same tuple with the filtered buffers in place of ``poses`` and, with a root filter, of ``roots``.
         Enqueues on the current stream and returns; never waits for the device."""
         torch = self._torch
-        m = self.model
-        dev = m.device
+        dev = self.model.device
         if getattr(self, "detections", None) is not None:
             raise ValueError("a session built with detections=D takes push_detections(dets, count, valid): the device decides which slot a person is")
         if valid is not None and not self.missed_detections:
             raise ValueError("push(valid=...) needs a session built with missed_detections=True")
-        if m._weights_dirty or getattr(m, "_pending_assigns", False):
-            m._sync_from_trainer()                                    # (weights changed: the packs are rewritten on this stream)
-            with torch.cuda.device(dev):
-                self._zero_features()
-        if not isinstance(kp2d, torch.Tensor):
-            kp2d = torch.from_numpy(np.ascontiguousarray(kp2d, np.float32))
-        if tuple(kp2d.shape) != tuple(self._kp_in.shape):
-            raise ValueError(f"kp2d must be {tuple(self._kp_in.shape)}, got {tuple(kp2d.shape)}")
+        self._sync_weights()
         with torch.cuda.device(dev):
-            if not kp2d.is_cuda:
-                kp2d = kp2d.to(torch.float32).contiguous().pin_memory()       # host input goes through pinned memory, asynchronously
-            self._push_in.copy_(kp2d, non_blocking=True)
+            self._push_in.copy_(self._host_frame(kp2d, self._kp_in, "kp2d"), non_blocking=True)
             if active is None:
                 if not self._active_all:
                     self._active.fill_(1)
@@ -820,7 +770,7 @@ class StreamSession(object):
                 if self.graph:
                     self._graph.replay()
                 else:
-                    self._tick(cur)
+                    self._run(self._tick_steps, cur)
             self._run(self._push_after, cur)                          # (with a rate: read the poses)
         return self._result
 
@@ -835,29 +785,15 @@ class StreamSession(object):
         appends (roots, root_state) as ``push`` does.  Enqueues on the current stream
         and returns; never waits for the device."""
         torch = self._torch
-        m = self.model
-        dev = m.device
+        dev = self.model.device
         if getattr(self, "detections", None) is None:
             raise ValueError("push_detections needs a session built with detections=D")
-        if m._weights_dirty or getattr(m, "_pending_assigns", False):
-            m._sync_from_trainer()
-            with torch.cuda.device(dev):
-                self._zero_features()
-        if not isinstance(dets, torch.Tensor):
-            dets = torch.from_numpy(np.ascontiguousarray(dets, np.float32))
-        if tuple(dets.shape) != tuple(self._dets.shape):
-            raise ValueError(f"dets must be {tuple(self._dets.shape)}, got {tuple(dets.shape)}")
+        self._sync_weights()
         D, K = self._det_flags.shape
-        if valid is not None:
-            f = valid if isinstance(valid, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(valid) != 0).view(np.uint8))
-            f = f.view(torch.uint8) if f.dtype == torch.bool else f.to(torch.uint8)
-            if tuple(f.shape) not in ((D,), (D, K)):
-                raise ValueError(f"valid must be ({D},) or ({D}, {K})")
-            f = f.reshape(D, -1)                                       # ((D, 1) broadcasts over the joints in the copy, on the device)
-            valid = f if f.is_cuda else f.expand(D, K).contiguous().pin_memory()
         with torch.cuda.device(dev):
-            if not dets.is_cuda:
-                dets = dets.to(torch.float32).contiguous().pin_memory()
+            dets = self._host_frame(dets, self._dets, "dets")
+            if valid is not None:                                     # ((D, 1) broadcasts over the joints in the copy, on the device)
+                valid = self._flags(valid, "valid", int(K), int(D))
             self._dets_in.copy_(dets, non_blocking=True)
             if count is None:
                 if not self._det_count_full:
@@ -878,7 +814,7 @@ class StreamSession(object):
             if self.graph:
                 self._graph.replay()
             else:
-                self._tick(torch.cuda.current_stream(dev))
+                self._run(self._tick_steps, torch.cuda.current_stream(dev))
         return self._result
 
     def _sub_ticks(self, active):
@@ -931,27 +867,15 @@ class StreamSession(object):
 
     # ---- the end of a track: the drain ticks of ``finish`` ----------------------------------------------------------------------------
     def _init_drain(self):
-        """What ``finish`` needs, made at its first call: the result buffers (one block, so that one fill zeroes them), and with
-        lookahead >= 1 the drain state, the chosen-slots mask, the launch table of a drain tick and its captured graph."""
+        """What ``finish`` needs, made at its first call: the result buffers (one block, so that one fill zeroes them: the raw scene's rows
+        and every stage's), and with lookahead >= 1 the drain state, the chosen-slots mask, the launch table of a drain tick (the drain
+        commit, the tick's forward and emit, every stage's launch, the filing) and its captured graph."""
         torch, lib, m = self._torch, self._lib, self.model
         dev, T, a, J = m.device, self.slots, self.lookahead, int(self._kp.shape[1])
-        camera, fp, fr = self.cameras is not None, self._pose_smoother, self._root_smoother
         # (name, tick buffer or None for a byte buffer, shape of a row, dtype)
         parts = [("poses", self._out, (J, 3), torch.float32), ("fresh", None, (), torch.uint8)]
-        if camera:
-            parts += [("roots", self._roots, (3,), torch.float32), ("root_state", None, (), torch.uint8)]
-        if self.bones is not None:
-            parts.append(("fixed_poses", self._pose_shown, (J, 3), torch.float32))
-        if self.world is not None:
-            parts += [("world_poses", self._pose_world, (J, 3), torch.float32), ("world_roots", self._roots_world, (3,), torch.float32)]
-        if fp is not None:
-            parts.append(("filtered_poses", fp.out, (J, 3), torch.float32))
-        if fr is not None:
-            parts.append(("filtered_roots", fr.out, (3,), torch.float32))
-        if self.rotations is not None:
-            parts.append(("rotations", self._rot_local, (J, 4), torch.float32))
-            if self._rot_global is not None:
-                parts.append(("global_rotations", self._rot_global, (J, 4), torch.float32))
+        # (the stages' rows follow in the tick's order, a byte buffer as None; until the stages were objects the roots came before fixed_poses)
+        parts += [(row, None if b.dtype == torch.uint8 else b, tuple(b.shape[1:]), b.dtype) for stage in self._post for _, row, b in stage.outputs]
         nbytes = [T * a * int(np.prod(shape, dtype=np.int64)) * (4 if dt == torch.float32 else 1) for _, _, shape, dt in parts]
         offsets = [int(o) for o in np.cumsum([0] + [(n + 255) // 256 * 256 for n in nbytes])]
         self._drain_rows = torch.zeros(max(offsets[-1], 1), dtype=torch.uint8, device=dev)
@@ -960,11 +884,7 @@ class StreamSession(object):
             rows[name] = (self._drain_rows[off:off + n].view(dt).view((T, a) + shape) if a > 0 else
                           torch.zeros((T, 0) + shape, dtype=dt, device=dev))
         self._drain_named = rows
-        result = (rows.get("filtered_poses", rows.get("world_poses", rows.get("fixed_poses", rows["poses"]))), rows["fresh"].view(torch.bool))
-        if camera:
-            result += (rows.get("filtered_roots", rows.get("world_roots", rows["roots"])), rows["root_state"])
-        result += tuple(rows[name] for name in ("rotations", "global_rotations") if name in rows)
-        self._drain_result = result
+        self._drain_result = scenes(Scene(rows["poses"], rows["fresh"], None, None, ()), self._stages, rows)["shown"].as_result()
         if a == 0:
             return
         lay = _capi.Uu3dStreamDrainLayout()
@@ -976,19 +896,8 @@ class StreamSession(object):
         h, cfg, dstate, chosen, fresh = m._h, C.byref(self._cfg), _ptr(self._drain_state), _ptr(self._drain_mask), _ptr(self._fresh)
         steps = [(lib.uu3d_stream_drain_commit, (h, cfg, _ptr(self._state), dstate, chosen, _ptr(self._valid_state), _ptr(self._rows),
                                                  _ptr(self._mask), _ptr(self._emit_fresh)))] + self._drain_shared
-        if self.bones is not None:                                  # the same step as in a tick, the chosen slots as `active`
-            steps.append(self._bones_launch(chosen))
-        if camera:
-            steps.append((lib.uu3d_stream_root_drain, (T, J, a, _ptr(self._root_state), dstate, chosen, fresh, _ptr(self._pose_shown), _ptr(self._cams),
-                                                       self.min_root_joints, _ptr(self._roots), _ptr(self._root_flag))))
-        if self.world is not None:                                   # the same step as in a tick, behind the drain's root solve
-            steps.append(self._world_launch())
-        if fp is not None:                                           # the filters as they are: the virtual counter, the chosen slots as `active`
-            steps.append(fp.launch(self._pose_world, self._virtual_frames, self._fresh, self._drain_mask))
-        if fr is not None:
-            steps.append(fr.launch(self._roots_world, self._virtual_frames, self._fresh, self._drain_mask, self._root_flag))
-        if self.rotations is not None:                               # the same step as in a tick
-            steps.append(self._rotations_launch())
+        # the stages' launches of a drain tick: the chosen slots as `active`, the virtual counter as the frames, the root from the ring
+        steps += [stage.launch(self._drain_mask, self._virtual_frames, self._drain_state) for stage in self._post]
         floats = [(src, rows[name], int(np.prod(shape))) for name, src, shape, _ in parts if src is not None]
         self._drain_file_args = []                                    # (uu3d_stream_drain_file takes four float buffers: a fifth goes in a launch of its own)
         for first in range(0, len(floats), 4):
@@ -997,39 +906,18 @@ class StreamSession(object):
             src, widths, dst = ((C.c_void_p * n)(*[t.data_ptr() for t, _, _ in group]), (C.c_int32 * n)(*[w for _, _, w in group]),
                                 (C.c_void_p * n)(*[t.data_ptr() for _, t, _ in group]))
             self._drain_file_args.append((src, widths, dst))
-            bytes_too = camera and first == 0
+            bytes_too = self.cameras is not None and first == 0
             steps.append((lib.uu3d_stream_drain_file, (T, a, dstate, n, src, widths, dst, fresh, _ptr(rows["fresh"]),
-                                                       _ptr(self._root_flag) if bytes_too else None, _ptr(rows["root_state"]) if bytes_too else None)))
+                                                       *((_ptr(self._scenes["camera"].root_state), _ptr(rows["root_state"])) if bytes_too else (None, None)))))
         self._drain_steps = steps
         # (every slot's `drained` is 0 outside ``finish`` -- it resets the slots it drained --, so the captured tick of a session with
         # detections, which resets the slots born on the device, needs no launch for the drain state; ``reset`` zeroes it all the same)
         self._reset_more = self._reset_more + [(lib.uu3d_stream_drain_reset, (T, dstate))]
-        if self.graph:
-            self._capture_drain()
-
-    def _capture_drain(self):
-        """One warm-up drain tick with no slot chosen (nothing advances), then the capture: a linear chain on one stream, as _capture."""
-        torch = self._torch
-        dev = self.model.device
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        gc.collect()
-        gc_was_on = gc.isenabled()
-        gc.disable()
-        try:
-            with torch.cuda.stream(side):
+        if self.graph:                                               # (the warm-up drain tick has no slot chosen: nothing advances)
+            def warm(side):
                 self._drain_mask.zero_()
                 self._run(self._drain_steps, side)
-            side.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=side):
-                self._run(self._drain_steps, side)
-            self._drain_graph = g
-            self.captures += 1
-        finally:
-            if gc_was_on:
-                gc.enable()
-        torch.cuda.current_stream(dev).wait_stream(side)
+            self._drain_graph = self._capture_steps(self._drain_steps, warm)
 
     def finish(self, slots=None):
         """The tracks in the given slots (indices; None = all) have ENDED: the poses of their last ``lookahead`` frames, which no push
@@ -1067,9 +955,7 @@ class StreamSession(object):
             chosen = np.zeros(self.slots, np.uint8)
             chosen[np.asarray(slots, np.int64).reshape(-1)] = 1
         with torch.cuda.device(dev):
-            if m._weights_dirty or getattr(m, "_pending_assigns", False):
-                m._sync_from_trainer()
-                self._zero_features()
+            self._sync_weights()
             if self._drain_result is None:
                 self._init_drain()
             if self.lookahead > 0:
@@ -1135,7 +1021,7 @@ class StreamSession(object):
         the pose filter reads (with ``bones`` the rebuilt poses in world axes); ``camera_poses`` is the camera-space buffer."""
         if self.max_out is not None:
             raise AttributeError("raw_poses: a session with out_fps returns several rows per slot")
-        return self._out if self.world is None else self._pose_world
+        return self._scenes["raw" if self.world is None else "world"].poses
 
     @property
     def raw_roots(self):
@@ -1143,7 +1029,7 @@ class StreamSession(object):
         unfiltered WORLD roots, which the root filter reads (``camera_roots`` is the camera-space buffer)."""
         if self.cameras is None:
             raise AttributeError("raw_roots needs a session with camera")
-        return self._roots_world
+        return self._scenes["world"].roots
 
     @property
     def camera_poses(self):
@@ -1151,7 +1037,7 @@ class StreamSession(object):
         ``bones`` the rebuilt ones), unfiltered -- without extrinsics the buffer the pose filter reads."""
         if self.cameras is None:
             raise AttributeError("camera_poses needs a session with camera")
-        return self._pose_shown
+        return self._scenes["camera"].poses
 
     @property
     def camera_roots(self):
@@ -1159,7 +1045,7 @@ class StreamSession(object):
         without extrinsics the same tensor as ``raw_roots``."""
         if self.cameras is None:
             raise AttributeError("camera_roots needs a session with camera")
-        return self._roots
+        return self._scenes["camera"].roots
 
     @property
     def fixed_poses(self):
@@ -1167,7 +1053,7 @@ class StreamSession(object):
         the buffer ``push`` returns."""
         if self.bones is None:
             raise AttributeError("fixed_poses needs a session with bones")
-        return self._pose_shown
+        return self._scenes["fixed"].poses
 
     @property
     def drain_fixed_poses(self):
@@ -1180,7 +1066,7 @@ class StreamSession(object):
         child joint -- the running means of a "track" session (NaN before a slot's first fresh pose), else the given ones; 0 for the root."""
         if self.bones is None:
             raise AttributeError("bone_lengths needs a session with bones")
-        return self._bone_lengths
+        return self._stages[0][1].lengths
 
     @property
     def rotation_flags(self):
@@ -1188,7 +1074,7 @@ class StreamSession(object):
         last fresh pose, 0 = it fell back (or the slot has had no pose since its reset)."""
         if self.rotations is None:
             raise AttributeError("rotation_flags needs a session with rotations")
-        return self._rot_flags
+        return self._stages[-1][1].flags
 
     @property
     def joint_state(self):
@@ -1248,6 +1134,30 @@ class StreamSession(object):
             pass
 
 
+class _TickRecorder(object):
+    """What the replays keep per tick beside poses and fresh flags: with ``placed`` four 32-bit words per slot -- the root's bits, the
+    root state --, and ``turned`` quaternion buffers, the last ones a push appends.  One copy to the host, at the end."""
+
+    def __init__(self, torch, ticks, slots, joints, placed, turned, device):
+        self.words = torch.zeros((ticks, slots, 4), dtype=torch.int32, device=device) if placed else None
+        self.quats = [torch.zeros((ticks, slots, joints, 4), dtype=torch.float32, device=device) for _ in range(turned)]
+
+    def record(self, k, rs):
+        for dst, src in zip(self.quats, rs[len(rs) - len(self.quats):]):
+            dst[k].copy_(src)
+        if self.words is not None:
+            self.words[k, :, :3].copy_(rs[0].view(self.words.dtype))
+            self.words[k, :, 3].copy_(rs[1])
+
+    def host(self):
+        """-> ((roots (ticks, slots, 3) float32, root_state (ticks, slots) uint8: a slot's ticks contiguous) or (), [quaternions])."""
+        placed = ()
+        if self.words is not None:
+            words = self.words.cpu().numpy()
+            placed = np.ascontiguousarray(words[:, :, :3]).view(np.float32), np.asfortranarray(words[:, :, 3].astype(np.uint8))
+        return placed, [q.cpu().numpy() for q in self.quats]
+
+
 def replay_tracks(model, config, tracks, resolutions=None, mask_stride=None, flip=None, lookahead=0, root_relative=True, graph=True, valid=None, fps=None,
                   model_fps=50, out_fps=None, drain=False, interpolation="linear", **options):
     """Push complete tracks tick by tick, one slot per track (a slot is inactive once its track has ended) -> per track the pose the
@@ -1294,9 +1204,7 @@ def replay_tracks(model, config, tracks, resolutions=None, mask_stride=None, fli
                       repair_joints=repair_joints, keypoints=keypoints, camera=camera, min_root_joints=min_root_joints, smooth=smooth, bones=bones,
                       rotations=rotations, interpolation=interpolation)
     turned = 0 if s.rotations is None else 2 if s.rotations.return_global else 1          # quaternion buffers a push appends
-    quats = [torch.zeros((ticks, T, J, 4), dtype=torch.float32, device=model.device) for _ in range(turned)]
-    if camera is not None:                                           # per tick and slot four 32-bit words: the root's bits, the state
-        root_words = torch.zeros((ticks, T, 4), dtype=torch.int32, device=model.device)
+    more = _TickRecorder(torch, ticks, T, J, camera is not None, turned, model.device)
     tails = None
     if drain:                                                         # per slot what its finish returned: finish's buffers last until the next one
         a = int(lookahead)
@@ -1321,11 +1229,7 @@ def replay_tracks(model, config, tracks, resolutions=None, mask_stride=None, fli
                 p, f, *rs = s.push(kp, None if act.all() else act)
             else:
                 p, f, *rs = s.push(kp, None if act.all() else act, valid=np.array([flags[i][k] & True if act[i] else flags[i][0] & False for i in range(T)]))
-            for dst, src in zip(quats, rs[len(rs) - turned:]):
-                dst[k].copy_(src)
-            if camera is not None:
-                root_words[k, :, :3].copy_(rs[0].view(torch.int32))
-                root_words[k, :, 3].copy_(rs[1])
+            more.record(k, rs)
             if out_fps is None:
                 poses[k].copy_(p)
                 fresh[k].copy_(f)
@@ -1348,13 +1252,9 @@ def replay_tracks(model, config, tracks, resolutions=None, mask_stride=None, fli
                 [counts[:n, i].astype(np.int32) for i, n in enumerate(lens)])
     poses, fresh = poses.cpu().numpy(), fresh.cpu().numpy()
     out = [poses[:n, i] for i, n in enumerate(lens)], [fresh[:n, i] for i, n in enumerate(lens)]
-    if camera is not None:
-        root_words = root_words.cpu().numpy()
-        roots = np.ascontiguousarray(root_words[:, :, :3]).view(np.float32)
-        out += ([roots[:n, i] for i, n in enumerate(lens)], [root_words[:n, i, 3].astype(np.uint8) for i, n in enumerate(lens)])
-    for q in quats:
-        q = q.cpu().numpy()
-        out += ([q[:n, i] for i, n in enumerate(lens)],)
+    placed, quats = more.host()
+    for x in placed + tuple(quats):
+        out += ([x[:n, i] for i, n in enumerate(lens)],)
     if drain:
         tails = [t.cpu().numpy() for t in tails]
         out = tuple([np.concatenate([rows, tail[i]]) for i, rows in enumerate(per_track)] for per_track, tail in zip(out, tails))
@@ -1388,22 +1288,15 @@ def replay_detections(model, config, detections, counts=None, valid=None, slots=
     J = int(model.arch.num_keypoints)
     poses = torch.zeros((ticks, S, J, 3), dtype=torch.float32, device=model.device)
     words = torch.zeros((ticks, 2, S), dtype=torch.int32, device=model.device)            # per tick: the fresh flags, the track ids
-    placed = s.cameras is not None
     turned = 0 if s.rotations is None else 2 if s.rotations.return_global else 1          # quaternion buffers a push appends
-    quats = [torch.zeros((ticks, S, J, 4), dtype=torch.float32, device=model.device) for _ in range(turned)]
-    if placed:                                                        # per tick and slot: the root's bits, the state
-        root_words = torch.zeros((ticks, S, 4), dtype=torch.int32, device=model.device)
+    more = _TickRecorder(torch, ticks, S, J, s.cameras is not None, turned, model.device)
     try:
         for k in range(ticks):
             p, f, *rs = s.push_detections(detections[k], None if counts is None else int(counts[k]), None if valid is None else valid[k])
             poses[k].copy_(p)
             words[k, 0].copy_(f)
             words[k, 1].copy_(s.track_ids)
-            for dst, src in zip(quats, rs[len(rs) - turned:]):
-                dst[k].copy_(src)
-            if placed:
-                root_words[k, :, :3].copy_(rs[0].view(torch.int32))
-                root_words[k, :, 3].copy_(rs[1])
+            more.record(k, rs)
         tails = [t.clone() for t in s.finish()] if drain else None   # (the ids of the last tick say whose rows they are)
         s.check_range()
     finally:
@@ -1412,14 +1305,11 @@ def replay_detections(model, config, detections, counts=None, valid=None, slots=
         tails = [t.cpu().numpy() for t in tails]
     poses, words = poses.cpu().numpy(), words.cpu().numpy()
     fresh, ids = words[:, 0] != 0, words[:, 1]
-    if placed:
-        root_words = root_words.cpu().numpy()
-        roots, root_state = np.ascontiguousarray(root_words[:, :, :3]).view(np.float32), root_words[:, :, 3].astype(np.uint8)
-    quats = [q.cpu().numpy() for q in quats]
+    placed, quats = more.host()
     out = []
     for tid in range(int(ids.max()) + 1 if ids.size else 0):
         t, slot = np.nonzero(ids == tid)
-        arrays = (poses[t, slot], fresh[t, slot]) + ((roots[t, slot], root_state[t, slot]) if placed else ()) + tuple(q[t, slot] for q in quats)
+        arrays = (poses[t, slot], fresh[t, slot]) + tuple(x[t, slot] for x in placed + tuple(quats))
         if drain and ticks and t[-1] == ticks - 1:                    # alive at the end of the video: the rows finish() gave its slot
             arrays = tuple(np.concatenate([x, tail[slot[-1]]]) for x, tail in zip(arrays, tails))
         out.append((tid, int(t[0])) + arrays)
