@@ -116,6 +116,9 @@ int uu3d_op_ln_dense_panel_ex(const float* x_dev, int32_t ldx, int32_t M, const 
 /* HOST: the inverse of the A-fragment order (panel_a_index, the order ln_split_frag and the Ln epilogue write): rows 0 .. M - 1 of a
  * fragment buffer copied back from the device, as the values of the two planes, hi_host[M][384] and lo_host[M][384] (value = hi + lo / 2048). */
 int uu3d_op_panel_a_unpack(const void* frag_host, int32_t M, float* hi_host, float* lo_host);
+/* HOST: its inverse: rows 0 .. M - 1 of the two planes, given as floats that halfs can hold, into frag_host (uu3d_op_panel_a_bytes(M)) through
+ * panel_a_index; the elements of rows past M in the last 32-row panel are left as they are. */
+int uu3d_op_panel_a_pack(const float* hi_host, const float* lo_host, int32_t M, void* frag_host);
 
 /* vit.MLP of a temporal block in one launch (csrc/uu3d_mlp_fused.h; vision_transformer.py:46-68): the three partial sums
  *   mslab[s][M][384],  sum_s mslab[s] = relu(LayerNorm(x[M][384]) W1 + b1) W2        (W1 384 x 768, W2 768 x 384, Keras (in, out); no b2)
@@ -172,6 +175,8 @@ size_t uu3d_op_attn_qf_bytes(int32_t rows);
 /* HOST: hi_host / lo_host, f16 planes [rows][1152] of [q | k | v] rows (D = 384), into frag_host (uu3d_op_attn_qf_bytes(rows)) through the
  * producer's own index function (tchain_qf_index, csrc/uu3d_tchain16.h).  Elements of rows past `rows` in the last tile are left as they are. */
 int uu3d_op_attn_qf_pack(const void* hi_host, const void* lo_host, int32_t rows, void* frag_host);
+/* HOST: its inverse: rows 0 .. rows - 1 of frag_host (rows may reach into the tile rows past the live ones) as f16 planes [rows][1152]. */
+int uu3d_op_attn_qf_unpack(const void* frag_host, int32_t rows, void* hi_host, void* lo_host);
 
 /* ---- the forward's TILED GEMMs, each on its own (csrc/uu3d_gemm.h: gemm_f32_kernel, splitk_reduce_kernel; csrc/uu3d_gemm_h3.h: gemm_h3_kernel,
  * gemm_h3g_kernel), launched through the functions the forward's Launcher::gemm / gemm_g launch through (launch_fwd_gemm, launch_fwd_gemm_g,
@@ -270,6 +275,49 @@ int uu3d_op_compact_frames(const uint8_t* mask_dev, int32_t total, int32_t* list
  * UU3D_ERR_INVALID_ARGUMENT: a null pointer, F < 1, another schedule value, a handle with generic dims (it has one spatial kernel); the handle is
  * const here: uu3d_last_error is not written. */
 int uu3d_op_spatial_choice(const uu3d_model* model, int32_t F, int32_t schedule, int32_t* kernel, int32_t* planes); /* HOST: what spatial_stage takes */
+
+/* ---- the TEMPORAL CHAIN, one launch on its own (csrc/uu3d_tchain16.h: tchain16_kernel<FLAGS>, every row-local stage of a temporal block for the
+ * 64 token rows a workgroup owns), launched through the helper the forward's Launcher::tchain launches through (launch_tchain, csrc/uu3d_launch.h):
+ * grid, block, LDS bytes and the kernel's argument record are the forward's -- tests/test_tchain_ops_gpu.py holds every stage set to float64. ---- */
+#define UU3D_TC_PROJ 1          /* x += attention output . Wp + bp */
+#define UU3D_TC_MLP 2           /* x += fc2(relu(fc1(LayerNorm 2 (x)))) */
+#define UU3D_TC_QKV 4           /* q | k | v = wqkv(LayerNorm 1 (x)) of the NEXT block, fragment order, q prescaled by log2(e) / sqrt(48) */
+#define UU3D_TC_FC1_PLANES 8    /* relu(fc1(LayerNorm 2 (x))) of the first strided block as row-major f16 planes */
+#define UU3D_TC_PE 16           /* x + pe[token % period] of the first strided block is what the final LayerNorm 1 reads */
+/* Launch `launch` of the chain of a COMMITTED handle, on the handle's own weight stream and parameter table exactly as uu3d_commit_weights folded
+ * (LayerNorm's affine part, q's scale) and packed them; uu3d_op_tchain_launches gives the stage set of every launch (launch 0: UU3D_TC_QKV;
+ * 1 .. T: PROJ | MLP [| QKV [| PE]]; T + 1 with strided blocks: PROJ | FC1_PLANES).  M >= 1 token rows, any value: whole 64-row tiles run, rows
+ * past M read row M - 1 (the attention output: the rows of the last written 16-row group) and store to a trash page inside the scratch.
+ *   scratch_dev (uu3d_op_tchain_scratch_bytes(M)): the lane-linear residual tiles between two launches, slot 0 = the temporal stack's, slot 1 = the
+ *     first strided block's (x + pe), each ceil(M / 64) tiles of 64 x 384 floats in the order of uu3d_op_tchain_xs_pack, then the trash page.
+ *     A launch WITHOUT UU3D_TC_PROJ reads x_dev and stores the tile into slot 0; a launch WITH it reads its residual tile from the scratch (slot 1
+ *     for PROJ | FC1_PLANES, else slot 0: whole tiles, the rows past M included); a launch with UU3D_TC_QKV stores the tile its LayerNorm 1 reads
+ *     (slot 1 with UU3D_TC_PE, else slot 0), whole tiles.  So launch i + 1 runs on the scratch launch i left, with no host repack.
+ *   attn_out_frag_dev (UU3D_TC_PROJ): the attention output as attn_h3_kernel leaves it for fragment-ordered q | k | v (UU3D_ATTN_IN_QFRAG,
+ *     UU3D_ATTN_OUT_FRAG): A-fragment order (uu3d_op_panel_a_pack, uu3d_op_panel_a_bytes(M)), channel 16 u + 8 g + j of a row holding context
+ *     channel 16 u + 8 (j >> 2) + 4 g + (j & 3) -- the projection's rows are packed in that order.  The rows past M of the last 32-row panel are read
+ *     (dead lanes only): initialised memory.
+ *   x_dev [M][384]: read by a launch without UU3D_TC_PROJ; written (rows < M) by a launch with UU3D_TC_MLP that has no UU3D_TC_QKV or has UU3D_TC_PE.
+ *   xa_dev [M][384], h_dev (hi [M][768] halfs | lo [M][768] halfs): written (rows < M) by PROJ | FC1_PLANES: x + projection, and relu(fc1).
+ *   q_dev (UU3D_TC_QKV): uu3d_op_attn_qf_bytes(M) bytes; the 64-row tiles that hold a live row are written whole.
+ *   The positional encoding and its period of UU3D_TC_PE are the handle's: the first strided block's, num_frames rows; M need not be a multiple.
+ * Pointers a launch's stage set does not use may be NULL.  Returned before any launch, every buffer untouched:
+ *   UU3D_ERR_INVALID_ARGUMENT: a null model; M < 1 (or M 1152 4 >= 4e9, the forward's limit); launch < 0 or >= the number of launches; a null
+ *     scratch_dev or a null pointer the stage set reads or writes;
+ *   UU3D_ERR_NOT_READY: uu3d_commit_weights has not run since the last uu3d_set_weight;
+ *   UU3D_ERR_UNSUPPORTED: the handle has no chain (precision f32, or d_t / h_t / heads other than 384 / 768 / 8, or no temporal block).
+ * Every pointer 16-byte aligned (not checked).  A row's results do not depend on M, on its place in the tile or on the other rows: the same bits.
+ * The model's range word is not touched. */
+int uu3d_op_tchain(uu3d_model* model, int32_t launch, int32_t M, const void* attn_out_frag_dev, float* x_dev, float* xa_dev, void* q_dev,
+                   void* h_dev, void* scratch_dev, void* stream);
+size_t uu3d_op_tchain_scratch_bytes(int32_t M);      /* tchain16_scratch_bytes(ceil(M / 64)); 0 for M < 1 */
+/* HOST: flags_out[i] = the stage set (UU3D_TC_*) of launch i for i < capacity; returns the number of launches (0: the handle has no chain or is
+ * not committed), -1 for a null handle, capacity < 0 or a null flags_out with capacity > 0.  uu3d_last_error is not written. */
+int uu3d_op_tchain_launches(const uu3d_model* model, int32_t* flags_out, int32_t capacity);
+/* HOST: rows 0 .. rows - 1 of x_host[rows][384] to / from the lane-linear residual tiles of slot 0 or 1 of a scratch for M rows, through
+ * tchain16_xs_index.  rows <= 64 ceil(M / 64): the tile rows past M can be given and read.  Other elements of the scratch are left as they are. */
+int uu3d_op_tchain_xs_pack(const float* x_host, int32_t M, int32_t slot, int32_t rows, void* scratch_host);
+int uu3d_op_tchain_xs_unpack(const void* scratch_host, int32_t M, int32_t slot, int32_t rows, float* x_host);
 
 #ifdef __cplusplus
 }

@@ -84,7 +84,7 @@ def test_pipelined_forwards_stay_bitwise_right_over_many_batches():
 
 
 def test_pipelined_temporal_chain_stays_bitwise_right_over_many_batches(monkeypatch):
-    """The temporal chain (csrc/uu3d_tchain.h; forced on at this batch, UU3D_TCHAIN=1) through the four-queue pipeline: 600 batches cycling
+    """The temporal chain (csrc/uu3d_tchain16.h; forced on at this batch, UU3D_TCHAIN=1) through the four-queue pipeline: 600 batches cycling
     through six inputs, every result equal to what a quiet throughput-schedule forward returned for that input -- the chain's lane-private
     scratch slabs belong to a slot's workspace, its ring and counted waits are hand-scheduled: a slot reading another slot's scratch, or a
     wait that counts one operation too few, shows up here as a rare mismatch."""

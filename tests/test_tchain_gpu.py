@@ -1,4 +1,4 @@
-"""GPU: the temporal chain (csrc/uu3d_tchain.h; the throughput schedule's path from 1024 token rows on, UU3D_TCHAIN=0 switches it off) -- every row-local stage of a
+"""GPU: the temporal chain (csrc/uu3d_tchain16.h; the throughput schedule's path from 1024 token rows on, UU3D_TCHAIN=0 switches it off) -- every row-local stage of a
 vit.TransformerBlock (common/net/vision_transformer.py:176-195: projection + residual, LayerNorm 2, fc1, ReLU, fc2 + residual, the next
 block's LayerNorm 1 + QKV) as ONE launch per block -- against the CPU oracle, against the launch chain it replaces, run to run, with
 whole and ragged row tiles, with and without key masks, with return_attention, and for the structural variants of the constructor

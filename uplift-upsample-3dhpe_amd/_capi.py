@@ -66,6 +66,8 @@ OPS_SYMBOLS = (
     "uu3d_op_attn_infer", "uu3d_op_attn_qf_bytes", "uu3d_op_attn_qf_pack",
     "uu3d_op_tiled_operand_bytes", "uu3d_op_tiled_pack", "uu3d_op_tiled_dense", "uu3d_op_tiled_split",
     "uu3d_op_spatial_stack", "uu3d_op_compact_frames", "uu3d_op_spatial_choice",
+    "uu3d_op_panel_a_pack", "uu3d_op_attn_qf_unpack",
+    "uu3d_op_tchain", "uu3d_op_tchain_scratch_bytes", "uu3d_op_tchain_launches", "uu3d_op_tchain_xs_pack", "uu3d_op_tchain_xs_unpack",
 )
 # epilogues of uu3d_op_ln_dense_panel_ex / uu3d_op_ln_dense_wt (include/uu3d_ops.h)
 UU3D_EP_BIAS, UU3D_EP_BIAS_RELU_SPLIT, UU3D_EP_BIAS_SPLIT_Q, UU3D_EP_BIAS_RESIDUAL, UU3D_EP_BIAS_RESIDUAL_LN = range(5)
@@ -79,6 +81,8 @@ UU3D_EP_BIAS_RELU, UU3D_EP_CONV_RESIDUAL, UU3D_EP_S2T = 5, 6, 7
 # kernels and output layouts of uu3d_op_spatial_stack (include/uu3d_ops.h)
 UU3D_SPATIAL_AUTO, UU3D_SPATIAL_F32, UU3D_SPATIAL_H3_TILES, UU3D_SPATIAL_P16 = range(4)
 UU3D_SPATIAL_OUT_F32, UU3D_SPATIAL_OUT_PLANES = range(2)
+# stage sets of the temporal chain's launches (uu3d_op_tchain, include/uu3d_ops.h)
+UU3D_TC_PROJ, UU3D_TC_MLP, UU3D_TC_QKV, UU3D_TC_FC1_PLANES, UU3D_TC_PE = 1, 2, 4, 8, 16
 
 
 class Uu3dTiledDenseArgs(C.Structure):
@@ -506,6 +510,20 @@ def load_library(path=None):
     lib.uu3d_op_compact_frames.argtypes = [vp, i32, vp, vp]
     lib.uu3d_op_spatial_choice.restype = C.c_int
     lib.uu3d_op_spatial_choice.argtypes = [vp, i32, i32, C.POINTER(i32), C.POINTER(i32)]
+    lib.uu3d_op_panel_a_pack.restype = C.c_int
+    lib.uu3d_op_panel_a_pack.argtypes = [vp, vp, i32, vp]
+    lib.uu3d_op_attn_qf_unpack.restype = C.c_int
+    lib.uu3d_op_attn_qf_unpack.argtypes = [vp, i32, vp, vp]
+    lib.uu3d_op_tchain.restype = C.c_int
+    lib.uu3d_op_tchain.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.uu3d_op_tchain_scratch_bytes.restype = sz
+    lib.uu3d_op_tchain_scratch_bytes.argtypes = [i32]
+    lib.uu3d_op_tchain_launches.restype = C.c_int
+    lib.uu3d_op_tchain_launches.argtypes = [vp, C.POINTER(i32), i32]
+    lib.uu3d_op_tchain_xs_pack.restype = C.c_int
+    lib.uu3d_op_tchain_xs_pack.argtypes = [vp, i32, i32, i32, vp]
+    lib.uu3d_op_tchain_xs_unpack.restype = C.c_int
+    lib.uu3d_op_tchain_xs_unpack.argtypes = [vp, i32, i32, i32, vp]
     if path is None:
         _lib = lib
     return lib

@@ -249,23 +249,11 @@ struct Launcher {
     void tchain(const char* name, const uu3d_model::TcLaunch& t, int M, const _Float16* Of, float* X, float* XA, const float* pe, int period,
                 _Float16* Q, _Float16* H, unsigned char* scratch) {
         if (skip_mask() & 128) return;
-        const int mt = (M + 63) / 64;
-        TChainArgs a{};
-        a.M = M; a.m_tiles = mt; a.period = period; a.qscale = attn_qscale();
-        a.Of = Of; a.X = X; a.XA = XA; a.pe = pe; a.W = m->harena + t.w_off; a.P = m->arena + t.p_off; a.Q = Q; a.H = H; a.scratch = scratch;
         const double cols = ((t.flags & TC_PROJ) ? 384.0 : 0.0) + ((t.flags & TC_MLP) ? 1536.0 : 0.0) + ((t.flags & TC_FC1_PLANES) ? 768.0 : 0.0) + ((t.flags & TC_QKV) ? 1152.0 : 0.0);
         begin(name, "tchain", 2.0 * M * 384.0 * cols, 4.0 * (384.0 * cols + 2.0 * M * 384.0 + ((t.flags & TC_QKV) ? M * 1152.0 : 0.0) + ((t.flags & TC_FC1_PLANES) ? M * 768.0 : 0.0)));
-#define UU3D_T16_LAUNCH(F) case F: { allow_lds<tchain16_kernel<F>>(T16_LDS_TOTAL); \
-            hipLaunchKernelGGL(tchain16_kernel<F>, dim3(mt), dim3(512), T16_LDS_TOTAL, stream, a); } break;
-        switch (t.flags) {
-            UU3D_T16_LAUNCH(TC_QKV)
-            UU3D_T16_LAUNCH(TC_PROJ | TC_MLP | TC_QKV)
-            UU3D_T16_LAUNCH(TC_PROJ | TC_MLP | TC_QKV | TC_PE)
-            UU3D_T16_LAUNCH(TC_PROJ | TC_MLP)
-            UU3D_T16_LAUNCH(TC_PROJ | TC_FC1_PLANES)
-            default: status = UU3D_ERR_UNSUPPORTED; m->err = "temporal chain: unknown stage set"; break;
+        if (!launch_tchain(stream, t.flags, M, m->harena + t.w_off, m->arena + t.p_off, attn_qscale(), Of, X, XA, pe, period, Q, H, scratch)) {
+            status = UU3D_ERR_UNSUPPORTED; m->err = "temporal chain: unknown stage set";
         }
-#undef UU3D_T16_LAUNCH
         end();
     }
     // the fused MLP's combine (x += b2 + slabs; optionally xa = x + pe) + LayerNorm + split into A fragments
@@ -810,4 +798,46 @@ int uu3d_op_spatial_stack(uu3d_model* m, const float* frames_dev, int32_t F, con
                          want_planes ? (_Float16*)out_dev : nullptr, want_planes ? (_Float16*)out_dev + n : nullptr);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? UU3D_OK : fail(m, UU3D_ERR_HIP, std::string("uu3d_op_spatial_stack: launch failed: ") + hipGetErrorString(e));
+}
+
+// ---- the temporal chain, one launch on its own (uu3d_tchain16.h), through the helper Launcher::tchain launches through (launch_tchain,
+// uu3d_launch.h), on the handle's own weight stream and parameter table -- tests/test_tchain_ops_gpu.py holds every stage set to float64 ----
+size_t uu3d_op_tchain_scratch_bytes(int32_t M) { return M < 1 ? 0 : tchain16_scratch_bytes((M + 63) / 64); }
+
+// (a host query on a const handle: the handle's last-error text is not written)  Returns the number of launches, -1 for a null handle or buffer
+int uu3d_op_tchain_launches(const uu3d_model* m, int32_t* flags_out, int32_t capacity) {
+    if (!m || capacity < 0 || (capacity > 0 && !flags_out)) return -1;
+    if (!m->committed || m->generic || !tchain_possible(m->cfg)) return 0;
+    for (size_t i = 0; i < m->tchain.size() && (int32_t)i < capacity; ++i) flags_out[i] = m->tchain[i].flags;
+    return (int)m->tchain.size();
+}
+
+int uu3d_op_tchain(uu3d_model* m, int32_t launch, int32_t M, const void* attn_out_frag_dev, float* x_dev, float* xa_dev, void* q_dev, void* h_dev,
+                   void* scratch_dev, void* stream_) {
+    if (!m) return UU3D_ERR_INVALID_ARGUMENT;
+    if (M < 1 || launch < 0 || !scratch_dev) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_op_tchain: rows < 1, a negative launch or no scratch");
+    if ((double)M * 1152 * 4.0 >= 4.0e9) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_op_tchain: too many rows");      // (the forward's limit for the chain)
+    if (!m->committed) return fail(m, UU3D_ERR_NOT_READY, "uu3d_commit_weights has not been called");
+    if (m->generic || !tchain_possible(m->cfg) || m->tchain.empty())
+        return fail(m, UU3D_ERR_UNSUPPORTED, "uu3d_op_tchain: this handle has no temporal chain (precision f16x3, d_t 384, h_t 768, 8 heads, >= 1 temporal block)");
+    if ((size_t)launch >= m->tchain.size()) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_op_tchain: no such launch");
+    const uu3d_model::TcLaunch& t = m->tchain[launch];
+    const int f = t.flags;
+    const bool stores_x = (f & TC_MLP) != 0 && ((f & TC_QKV) == 0 || (f & TC_PE) != 0);      // (tchain16_kernel: the temporal stack's result)
+    const float* pe = nullptr;
+    if ((f & TC_PROJ) != 0 && !attn_out_frag_dev) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_op_tchain: this launch reads attn_out_frag_dev");
+    if (((f & TC_PROJ) == 0 || stores_x) && !x_dev) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_op_tchain: this launch reads or writes x_dev");
+    if ((f & TC_FC1_PLANES) != 0 && (!xa_dev || !h_dev)) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_op_tchain: this launch writes xa_dev and h_dev");
+    if ((f & TC_QKV) != 0 && !q_dev) return fail(m, UU3D_ERR_INVALID_ARGUMENT, "uu3d_op_tchain: this launch writes q_dev");
+    if ((f & TC_PE) != 0) {
+        if (m->sblocks.empty() || m->sblocks[0].pe == nullptr || m->cfg.num_frames < 1) return fail(m, UU3D_ERR_UNSUPPORTED, "uu3d_op_tchain: no strided positional encoding");
+        pe = m->sblocks[0].pe;
+    }
+    HIPCHK(m, hipSetDevice(m->device));
+    const float qscale = 1.44269504088896341f / sqrtf((float)kDH);                          // = Launcher::attn_qscale()
+    if (!launch_tchain((hipStream_t)stream_, f, M, m->harena + t.w_off, m->arena + t.p_off, qscale, (const _Float16*)attn_out_frag_dev, x_dev, xa_dev, pe,
+                       (f & TC_PE) != 0 ? m->cfg.num_frames : 1, (_Float16*)q_dev, (_Float16*)h_dev, (unsigned char*)scratch_dev))
+        return fail(m, UU3D_ERR_UNSUPPORTED, "temporal chain: unknown stage set");
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? UU3D_OK : fail(m, UU3D_ERR_HIP, std::string("uu3d_op_tchain: launch failed: ") + hipGetErrorString(e));
 }

@@ -13,6 +13,7 @@
 #include "uu3d_mlp_fused.h"
 #include "uu3d_attn.h"
 #include "uu3d_attn_h3.h"
+#include "uu3d_tchain16.h"
 
 namespace uu3d {
 
@@ -535,6 +536,31 @@ inline int launch_attn_infer(hipStream_t stream, const float* qkv, int D, int B,
     }
 #undef UU3D_ATTN_CASE
     return UU3D_OK;
+}
+
+// ---- forward: the temporal chain (uu3d_tchain16.h).  One launch = the stage set `flags` over every 64-row tile of M token rows; the forward's
+// Launcher::tchain and the operator ABI (uu3d_op_tchain) both launch through this: grid, block, LDS bytes and the TChainArgs fill exist once. ----
+// W / P: the launch's weight stream and parameter table as uu3d_commit_weights packed them.  Returns false (nothing launched) for a stage set the
+// kernel is not instantiated for.  Launches only; the caller reads the launch error.  (A template, so that only a translation unit that calls it
+// compiles the five kernels.)
+template <class Args = TChainArgs>
+bool launch_tchain(hipStream_t stream, int flags, int M, const _Float16* W, const float* P, float qscale, const _Float16* Of, float* X, float* XA,
+                          const float* pe, int period, _Float16* Q, _Float16* H, unsigned char* scratch) {
+    const int mt = (M + 63) / 64;
+    Args a{};
+    a.M = M; a.m_tiles = mt; a.period = period; a.qscale = qscale;
+    a.Of = Of; a.X = X; a.XA = XA; a.pe = pe; a.W = W; a.P = P; a.Q = Q; a.H = H; a.scratch = scratch;
+#define UU3D_T16_LAUNCH(F) case F: { allow_lds<tchain16_kernel<F>>(T16_LDS_TOTAL); \
+            hipLaunchKernelGGL(tchain16_kernel<F>, dim3(mt), dim3(512), T16_LDS_TOTAL, stream, a); } return true;
+    switch (flags) {
+        UU3D_T16_LAUNCH(TC_QKV)
+        UU3D_T16_LAUNCH(TC_PROJ | TC_MLP | TC_QKV)
+        UU3D_T16_LAUNCH(TC_PROJ | TC_MLP | TC_QKV | TC_PE)
+        UU3D_T16_LAUNCH(TC_PROJ | TC_MLP)
+        UU3D_T16_LAUNCH(TC_PROJ | TC_FC1_PLANES)
+        default: return false;
+    }
+#undef UU3D_T16_LAUNCH
 }
 
 }  // namespace uu3d

@@ -257,6 +257,45 @@ int uu3d_op_attn_qf_pack(const void* hi_host, const void* lo_host, int32_t rows,
     return UU3D_OK;
 }
 
+int uu3d_op_attn_qf_unpack(const void* frag_host, int32_t rows, void* hi_host, void* lo_host) {
+    if (!hi_host || !lo_host || !frag_host || rows < 1) return UU3D_ERR_INVALID_ARGUMENT;
+    const _Float16* f = reinterpret_cast<const _Float16*>(frag_host);
+    _Float16* hi = reinterpret_cast<_Float16*>(hi_host); _Float16* lo = reinterpret_cast<_Float16*>(lo_host);
+    for (int r = 0; r < rows; ++r)
+        for (int k = 0; k < 1152; ++k) {
+            hi[(size_t)r * 1152 + k] = f[tchain_qf_index((size_t)r, k, 0)];
+            lo[(size_t)r * 1152 + k] = f[tchain_qf_index((size_t)r, k, 1)];
+        }
+    return UU3D_OK;
+}
+
+// ---- the temporal chain's layouts (uu3d_tchain16.h) on the HOST, through the kernel's own index functions ----
+int uu3d_op_tchain_xs_pack(const float* x_host, int32_t M, int32_t slot, int32_t rows, void* scratch_host) {
+    if (!x_host || !scratch_host || M < 1 || slot < 0 || slot > 1 || rows < 1 || rows > (M + 63) / 64 * 64) return UU3D_ERR_INVALID_ARGUMENT;
+    float* s = reinterpret_cast<float*>(scratch_host) + (size_t)slot * ((M + 63) / 64) * T16_X_FLOATS_PER_TILE;
+    for (int row = 0; row < rows; ++row)
+        for (int ch = 0; ch < 384; ++ch) s[tchain16_xs_index(row, ch)] = x_host[(size_t)row * 384 + ch];
+    return UU3D_OK;
+}
+int uu3d_op_tchain_xs_unpack(const void* scratch_host, int32_t M, int32_t slot, int32_t rows, float* x_host) {
+    if (!x_host || !scratch_host || M < 1 || slot < 0 || slot > 1 || rows < 1 || rows > (M + 63) / 64 * 64) return UU3D_ERR_INVALID_ARGUMENT;
+    const float* s = reinterpret_cast<const float*>(scratch_host) + (size_t)slot * ((M + 63) / 64) * T16_X_FLOATS_PER_TILE;
+    for (int row = 0; row < rows; ++row)
+        for (int ch = 0; ch < 384; ++ch) x_host[(size_t)row * 384 + ch] = s[tchain16_xs_index(row, ch)];
+    return UU3D_OK;
+}
+int uu3d_op_panel_a_pack(const float* hi_host, const float* lo_host, int32_t M, void* frag_host) {
+    if (!frag_host || !hi_host || !lo_host || M < 1) return UU3D_ERR_INVALID_ARGUMENT;
+    const float* hi = hi_host; const float* lo = lo_host;
+    _Float16* f = reinterpret_cast<_Float16*>(frag_host);
+    for (int row = 0; row < M; ++row)
+        for (int k = 0; k < 384; ++k) {
+            const size_t at = panel_a_index(row, k, 384);
+            f[at] = (_Float16)hi[(size_t)row * 384 + k]; f[at + 512] = (_Float16)lo[(size_t)row * 384 + k];
+        }
+    return UU3D_OK;
+}
+
 int uu3d_op_attn_infer(const void* qkv, int32_t in_layout, int32_t D, int32_t B, int32_t L, int32_t H, const uint8_t* mask, int32_t kernel,
                        void* out, int32_t out_layout, void* stream) {
     static_assert(UU3D_ATTN_AUTO == ATTN_AUTO && UU3D_ATTN_F32_WG == ATTN_F32_WG && UU3D_ATTN_HEAD_WAVE == ATTN_HEAD_WAVE && UU3D_ATTN_H3 == ATTN_H3, "uu3d_ops.h and uu3d_launch.h name the kernels alike");
