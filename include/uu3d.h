@@ -767,6 +767,57 @@ int uu3d_solve_view_roots(const float* fused_dev, const float* kp2d_dev, const u
                           void* stream);
 
 /*
+ * WHO IS WHO (predict.view_pair_sums, predict.group_views, predict.gather_view_tracks, predict.match_views,
+ * predict.predict_views(match=...)): SEVERAL VIEWS wants the same index to be the same person in every camera, but every camera's tracker
+ * numbers people in the order it meets them.  The three calls here find the correspondence from the geometry alone and lay the tracks
+ * out per person.  predict.view_pair_sums_host, predict.group_views_host and predict.gather_view_tracks_host are the same rules in
+ * numpy, bit for bit.  Greedy, view by view, dependent on the order of the views: no matching accuracy is claimed.
+ * M tracks in all, 1 <= M <= 64, view-major: view_of_host (M) i32 in HOST memory, ascending, every entry in 0 .. views - 1 (a view may be
+ * empty); all tracks on one clock with one length T.  kp_dev (M, T, J, 2) f32: the detector's own joints, undistorted -- the same joint
+ * index in two views is all the rule needs --, joint_flags_dev (M, T, J) u8 or NULL; a joint is USED as in SEVERAL VIEWS.  cameras_dev
+ * (views, 16) f64: the rows of SEVERAL VIEWS.  In float64 on the float32 inputs, every operation rounded once, no fused multiply-add.
+ * PAIR SUMS.  For tracks p < q of different views v, w: o = t_w - t_v, oo = (o0 * o0 + o1 * o1) + o2 * o2; oo not finite or not > 0
+ * (coincident cameras cannot be matched by geometry): no terms.  Else per frame f and joint j used in both tracks, per track
+ *     a = (u - cx) / fx    b = (v - cy) / fy    d_i = (r1_i * a + r2_i * b) + r3_i            (the pixel's ray in world axes)
+ * and with dp, dq the two rays
+ *     c = dp x dq (c0 = dp1 * dq2 - dp2 * dq1, ...)    cc = (c0 * c0 + c1 * c1) + c2 * c2    pp, qq: the same expression of dp, dq
+ *     oc = (o0 * c0 + o1 * c1) + o2 * c2               e = (oc * oc) / cc                    (the squared distance of the two LINES)
+ * The term counts iff cc > 2^-20 * (pp * qq) -- rays closer than about 1e-3 rad carry no distance information -- and e is finite.  The
+ * rays are lines, not half-lines: an intersection behind a camera is not rejected.  Order: per frame s_f = 0.0, s_f = s_f + e over the
+ * counted joints ascending, n_f their number; lane l of 256 sums s_f for f = l, l + 256, ... ascending from 0.0; then for stride = 128,
+ * 64, ..., 1: x[l] = x[l] + x[l + stride] for l < stride; sums[p][q] = sums[q][p] = x[0], terms[p][q] = terms[q][p] = the sum of n_f.
+ * Same-view pairs, the diagonal and pairs without terms hold 0.0 and 0.
+ * GROUPING.  Persons start as the tracks of the first non-empty view, in track order, ids from 0.  For each later view w ascending: for
+ * person k (members m_1 < m_2 < ..., at most one per view) and track b of view w, S = 0.0, S = S + sums[m][b] over the members with
+ * terms[m][b] > 0 ascending, n = the sum of those terms; the pair is allowed iff n >= min_terms and S / (double) n <= max_dist * max_dist.
+ * Repeatedly the allowed pair of smallest S / n among the persons without a track in view w and the unmatched tracks of view w is
+ * taken; ties go to the smaller k, then the smaller b.  Only persons that existed before the step compete; the tracks of view w left
+ * over then become new persons in ascending track order.
+ *
+ *   uu3d_view_pair_sums(kp_dev 8-byte aligned, joint_flags_dev or NULL, view_of_host, tracks, frames, J, views, cameras_dev,
+ *       sums_dev (M, M) f64, terms_dev (M, M) i32, stream): one launch, one workgroup of 256 lanes per unordered pair p <= q, which writes
+ *       both mirrored elements; the fixed tree runs through LDS.  frames * J must stay below 2^31.
+ *   uu3d_group_views(sums_dev, terms_dev, view_of_host, tracks, views, max_dist >= 0, min_terms >= 1, person_dev (M) i32,
+ *       n_persons_dev (1) i32, table_dev (views, M) i32, stream): one launch of one wave.  table[v][k] = the track of person k in view v
+ *       or -1; columns >= n_persons are -1.
+ *   uu3d_gather_view_tracks(src_dev (views * persons) i32, poses_dev (M * T, J, 3) f32, kp2d_dev (M * T, J, 2) f32 8-byte aligned,
+ *       joint_flags_dev (M * T, J) u8 or NULL, views, persons, frames, J, tracks, out_poses_dev (views, persons * T, J, 3) f32,
+ *       out_kp2d_dev (views, persons * T, J, 2) f32, out_flags_dev (views, persons * T, J) u8, stream): one launch, one lane per (view,
+ *       person row, joint); src[v * persons + k] = the track whose rows become person k's block of view v, or -1 (as is anything outside
+ *       0 .. M - 1): zero poses, NaN keypoints and flags 0, so that view does not SEE the frame.  A NULL joint_flags_dev reads as ones.
+ * All: views > 8, tracks or persons > 64 or J > 64: UU3D_ERR_UNSUPPORTED; bad counts, NULLs, misalignment or a view_of_host that does not
+ * ascend: UU3D_ERR_INVALID_ARGUMENT -- every guard before any device call.  Every output element has one writer, no atomics, the inputs
+ * are only read, nothing copies to the host or waits: bitwise repeatable.
+ */
+int uu3d_view_pair_sums(const float* kp_dev, const uint8_t* joint_flags_dev, const int32_t* view_of_host, int32_t tracks, int64_t frames,
+                        int32_t num_keypoints, int32_t views, const double* cameras_dev, double* sums_dev, int32_t* terms_dev, void* stream);
+int uu3d_group_views(const double* sums_dev, const int32_t* terms_dev, const int32_t* view_of_host, int32_t tracks, int32_t views,
+                     double max_dist, int32_t min_terms, int32_t* person_dev, int32_t* n_persons_dev, int32_t* table_dev, void* stream);
+int uu3d_gather_view_tracks(const int32_t* src_dev, const float* poses_dev, const float* kp2d_dev, const uint8_t* joint_flags_dev,
+                            int32_t views, int32_t persons, int64_t frames, int32_t num_keypoints, int32_t tracks, float* out_poses_dev,
+                            float* out_kp2d_dev, uint8_t* out_flags_dev, void* stream);
+
+/*
  * ANY FRAME RATE (predict.predict_tracks(fps=...)): the front of YOUR OWN 2D TRACKS for tracks that were not filmed at the rate the model
  * was trained for.  The table holds the MODEL's time grid: row `row` (track row_track_dev[row]) is model frame k of its track, which sits at
  * source position p_k = k * fps / model_fps.  The host works the positions out in exact integer arithmetic (predict.resample_plan) and

@@ -2,7 +2,11 @@
 ``.cpu()``, then the rules in numpy (``fuse_views_host``, ``solve_view_roots_host``, ``root_trajectory_host``).  Median of 3 in one
 process, seeded weights, synthetic tracks.  Informational: no threshold.
 
-    python tools/predict_views_bench.py [--config h36m_81] [--persons 2] [--frames 1000]
+``--match`` times ``predict_views(match=True)`` on shuffled views (3 cameras; every person in camera 0, all but one in the others) beside
+``match_views_host`` followed by today's ``predict_views`` on the views regrouped per person (a person a camera does not see: an all-NaN
+track there, ``valid="finite"``), and ``match_views`` alone at M = 16 and 64 tracks of 2500 frames beside its mirror (the mirror once).
+
+    python tools/predict_views_bench.py [--config h36m_81] [--persons 2] [--frames 1000] [--match]
 """
 import argparse
 import json
@@ -45,6 +49,75 @@ def _views(cams, persons, frames, J):
     return views
 
 
+def _shuffled(cams, persons, frames, J, seed=1):
+    """Persons 1.2 m apart on steps of 0.6 m (the scenes of tests/view_match_util.py): camera 0 sees all, camera v > 0 all but person
+    v - 1 (where there are that many), each view in an order of its own -> views, the true person of every track."""
+    from uplift_upsample_3dhpe_amd import predict
+    rng = np.random.default_rng(seed)
+    fx, fy, cx, cy = cams[0].intrinsics
+    t = np.arange(frames)[:, None, None]
+    world = []
+    for i in range(persons):
+        ang = 2.0 * np.pi * i / max(persons, 3) + 0.4
+        centre = np.array([np.cos(ang), np.sin(ang), 0.0]) * 1.2 / (2.0 * np.sin(np.pi / max(persons, 3))) + [0.0, 0.0, 0.9 + 0.6 * (i % 4)]
+        world.append(centre + rng.normal(0.0, 0.25, (J, 3)) + t * np.array([0.0004, -0.0003, 0.0]) + rng.normal(0.0, 0.004, (frames, J, 3)))
+    views, truth = [], []
+    for v, c in enumerate(cams):
+        who = [int(i) for i in rng.permutation(persons) if v == 0 or i != v - 1 or persons == 1]
+        tracks = []
+        for i in who:
+            p = predict.world_to_camera_host(world[i], c)
+            px = np.stack([fx * p[..., 0] / p[..., 2] + cx, fy * p[..., 1] / p[..., 2] + cy], axis=-1) + rng.normal(0.0, 0.5, (frames, J, 2))
+            tracks.append(px.astype(np.float32))
+        views.append(tracks)
+        truth.append(who)
+    return views, truth
+
+
+def _match_rows(model, cfg, args):
+    import torch
+    from uplift_upsample_3dhpe_amd import predict
+    J, N, T = int(cfg.NUM_KEYPOINTS), max(args.persons, 2), args.frames
+    kw = dict(resolutions=(1024, 1024))
+    cams = _cameras(3)
+    views, truth = _shuffled(cams, N, T, J)
+
+    def device():
+        r = predict.predict_views(model, cfg, views, cams, match=True, **kw)
+        return [torch.cat(a, 0).cpu() for a in r[:4]], r[-1]
+
+    def host():
+        person, n, table, _, _ = predict.match_views_host(views, cams)
+        flat = [t for tracks in views for t in tracks]
+        gone = np.full((T, J, 2), np.nan, np.float32)
+        regrouped = [[flat[m] if m >= 0 else gone for m in table[v, :int(n[0])]] for v in range(len(cams))]
+        return [torch.cat(a, 0).cpu() for a in predict.predict_views(model, cfg, regrouped, cams, valid="finite", **kw)], person
+
+    device(), host()
+    a, b = device(), host()
+    ok = [k for per_view in a[1] for k in per_view] == [int(k) for k in b[1]]
+    pairs = set(zip([k for per_view in a[1] for k in per_view], [k for per_view in truth for k in per_view]))
+    rows = [dict(row="predict_views(match=True)", views=3, persons=N, tracks=sum(len(v) for v in views), frames=T,
+                 device_ms=round(_median(lambda: device()), 2), host_match_then_predict_views_ms=round(_median(lambda: host()), 2),
+                 same_persons_as_host=bool(ok), true_partition=len(pairs) == len({g for g, _ in pairs}) == len({w for _, w in pairs}),
+                 max_abs_root_diff=float(np.nanmax(np.abs(a[0][1].numpy() - b[0][1].numpy()))))]
+    for M in (16, 64):                                                   # match_views alone: 8 cameras, M / 8 tracks each, 2500 frames
+        cams8 = _cameras(8)
+        per = M // 8
+        v8, _ = _shuffled(cams8, per + 1, 2500, J, seed=M)
+        v8 = [tracks[:per] for tracks in v8]
+        dev8 = [[torch.from_numpy(t).cuda() for t in tracks] for tracks in v8]
+        got = [r.cpu().numpy() for r in predict.match_views(dev8, cams8)]
+        t0 = time.perf_counter()
+        want = predict.match_views_host(v8, cams8)
+        mirror_ms = (time.perf_counter() - t0) * 1e3
+        same = all(np.array_equal(g.view(np.uint8), w.view(np.uint8)) for g, w in zip(got, want))
+        rows.append(dict(row="match_views", tracks=M, frames=2500, joints=J, device_ms=round(_median(lambda: predict.match_views(dev8, cams8)), 3),
+                         device_then_cpu_ms=round(_median(lambda: [r.cpu() for r in predict.match_views(dev8, cams8)]), 3),
+                         mirror_ms_one_run=round(mirror_ms, 1), bits_equal=bool(same), persons=int(want[1][0])))
+    return rows
+
+
 def _median(fn, n=3):
     import torch
     times = []
@@ -62,6 +135,7 @@ def main(argv=None):
     p.add_argument("--config", default="h36m_81")
     p.add_argument("--persons", type=int, default=2)
     p.add_argument("--frames", type=int, default=1000)
+    p.add_argument("--match", action="store_true", help="time predict_views(match=True) and match_views instead")
     args = p.parse_args(argv)
     import torch
     import uplift_upsample_3dhpe_amd as pkg
@@ -70,6 +144,9 @@ def main(argv=None):
     cfg = util.load_config(args.config)
     arch = pkg.arch_from_config(cfg)
     model = pkg.build_uplift_upsample_transformer(cfg, weights=pkg.init_weights(arch, seed=2, perturb=0.1))
+    if args.match:
+        print(json.dumps(dict(config=args.config, rows=_match_rows(model, cfg, args))))
+        return 0
     J, N = int(cfg.NUM_KEYPOINTS), args.persons
     kw = dict(resolutions=(1024, 1024))
     rows = []

@@ -55,6 +55,7 @@ EXPORTED_SYMBOLS = (
     "uu3d_undistort_points",
     "uu3d_camera_to_world",
     "uu3d_fuse_views", "uu3d_solve_view_roots",
+    "uu3d_view_pair_sums", "uu3d_group_views", "uu3d_gather_view_tracks",
 )
 # include/uu3d_ops.h
 OPS_SYMBOLS = (
@@ -386,6 +387,13 @@ def load_library(path=None):
     lib.uu3d_fuse_views.argtypes = [vp, vp, vp, i32, i64, i32, i32, vp, vp, vp, vp]
     lib.uu3d_solve_view_roots.restype = C.c_int
     lib.uu3d_solve_view_roots.argtypes = [vp, vp, vp, i32, i64, i32, vp, i32, vp, vp, vp]
+    # who is who: view_of is HOST memory (its order is a guard), everything else device memory
+    lib.uu3d_view_pair_sums.restype = C.c_int
+    lib.uu3d_view_pair_sums.argtypes = [vp, vp, C.POINTER(i32), i32, i64, i32, i32, vp, vp, vp, vp]
+    lib.uu3d_group_views.restype = C.c_int
+    lib.uu3d_group_views.argtypes = [vp, vp, C.POINTER(i32), i32, i32, C.c_double, i32, vp, vp, vp, vp]
+    lib.uu3d_gather_view_tracks.restype = C.c_int
+    lib.uu3d_gather_view_tracks.argtypes = [vp, vp, vp, vp, i32, i32, i64, i32, i32, vp, vp, vp, vp]
     lib.uu3d_joint_rotations.restype = C.c_int
     lib.uu3d_joint_rotations.argtypes = [vp, i64, i32, vp, i32] + [vp] * 6
     lib.uu3d_joint_rotations_reset.restype = C.c_int

@@ -17,8 +17,21 @@ is the same person, and person i has the same number of frames in every view) th
      fused world scene, with the launches and in the order of ``predict_tracks``.
 View v SEES frame f iff at least ``min_root_joints`` of its joints are USED there: the joint's flag is set and its raw coordinates are
 finite; a joint ``repair_joints`` filled is not used, exactly as in uu3d_solve_roots.  A view that does not see a person at a frame
-passes NaN coordinates (with ``valid="finite"``) or cleared flags there.  Out of scope: finding which detection of one camera is which
-of another, time alignment, per-view confidence weights, estimating extrinsics, a live form.  No accuracy is claimed."""
+passes NaN coordinates (with ``valid="finite"``) or cleared flags there.
+
+Who is who -- ``predict_views(..., match=True)`` / ``match_views(views, cameras)``: every camera's tracker numbers people in the order it
+meets them, so the same index is NOT the same person.  With ``match`` the views may hold different numbers of tracks in any order (all of
+one length T, on one clock), and in front of everything above
+  0a. uu3d_view_pair_sums measures every pair of tracks of different views: the mean squared distance between the LINES through the two
+      cameras and the pixels of the same joint at the same frame, in float64 with a fixed order of summation (``view_pair_sums_host``),
+  0b. uu3d_group_views groups the tracks to persons, greedily and view by view (``group_views_host``),
+  0c. ONE small copy tells the host who is who (it shapes every buffer behind it), all M tracks run through the one front as given -- no
+      forward is spent on a view that did not see a person --, and uu3d_gather_view_tracks lays the world poses, keypoints and flags out
+      per person, view-major; a (view, person) pair without a track is NaN keypoints and cleared flags, which the fusion does not SEE.
+The lines are not half-lines (a meeting point behind a camera is not rejected), the grouping depends on the order of the views, and
+``MATCH_DEFAULTS`` are conveniences for metres, not tuned values: no matching accuracy is claimed.
+
+Out of scope: time alignment, per-view confidence weights, estimating extrinsics, a live form.  No accuracy is claimed."""
 import ctypes as C
 
 import numpy as np
@@ -31,6 +44,10 @@ from .tracks import _device_tracks, _host_array, _shape, _upload
 
 MAX_VIEWS = 8                                                          # kViewsMax
 VIEW_RANK = 2.0 ** -40                                                 # kViewRank
+MAX_MATCH_TRACKS = 64                                                  # kMatchMaxTracks: the tracks of all views together
+MATCH_LANES = 256                                                      # kMatchLanes: part of the rule's order of summation
+VIEW_PARALLEL = 2.0 ** -20                                             # kViewParallel: sin^2 of 1e-3 rad -- closer rays carry no distance information
+MATCH_DEFAULTS = dict(max_dist=0.2, min_terms=50)                      # conveniences for metres, not tuned values
 
 
 def check_view_cameras(cameras, views=None):
@@ -241,6 +258,439 @@ def solve_view_roots(poses, kp2d, cameras, flags=None, min_root_joints=DEFAULT_M
     return roots, solved.view(torch.bool)
 
 
+# ---- who is who: which track of one camera is which of another (include/uu3d.h, WHO IS WHO) ---------------------------------------------
+class MatchViews(object):
+    """The parameters of ``predict_views(match=...)`` / ``match_views``: ``max_dist``, the largest root-mean-square distance between the
+    joints' rays, in world units, at which two tracks may be one person (finite, >= 0), and ``min_terms``, the least number of (frame,
+    joint) terms such a judgement needs (an int >= 1).  The defaults are conveniences for metres, not tuned values."""
+
+    def __init__(self, max_dist=MATCH_DEFAULTS["max_dist"], min_terms=MATCH_DEFAULTS["min_terms"]):
+        self.max_dist, self.min_terms = _match_parameters(max_dist, min_terms)
+
+    def __repr__(self):
+        return f"MatchViews(max_dist={self.max_dist!r}, min_terms={self.min_terms!r})"
+
+
+def _match_parameters(max_dist, min_terms):
+    try:
+        d = float(max_dist)
+    except (TypeError, ValueError):
+        raise ValueError(f"max_dist must be a finite number >= 0, got {max_dist!r}") from None
+    if isinstance(max_dist, bool) or not np.isfinite(d) or d < 0:
+        raise ValueError(f"max_dist must be a finite number >= 0, got {max_dist!r}")
+    if isinstance(min_terms, bool) or not isinstance(min_terms, (int, np.integer)) or not 1 <= int(min_terms) < 2 ** 31:
+        raise ValueError(f"min_terms must be an int >= 1, got {min_terms!r}")
+    return d, int(min_terms)
+
+
+def check_match(match):
+    """``predict_views(match=...)`` -> None (the views are given person by person) or a ``MatchViews``; True is the defaults."""
+    if match is None or match is False:
+        return None
+    if match is True:
+        return MatchViews()
+    if not isinstance(match, MatchViews):
+        raise ValueError(f"match must be None, True or a MatchViews(max_dist=, min_terms=), got {match!r}")
+    return match
+
+
+def check_view_of(view_of, views=None):
+    """``view_of`` (M,): the view of every track, view-major -> (int32 array, V).  1 <= M <= ``MAX_MATCH_TRACKS``, ascending, every entry in
+    0 .. V - 1 (``views`` = V; None: the last entry + 1); a view may be empty."""
+    v = np.asarray(_host_array(view_of))
+    if v.ndim != 1 or not 1 <= v.shape[0] or not np.issubdtype(v.dtype, np.integer):
+        raise ValueError(f"view_of must be (M,) integers with M >= 1, got {v.dtype} {v.shape}")
+    if v.shape[0] > MAX_MATCH_TRACKS:
+        raise ValueError(f"at most {MAX_MATCH_TRACKS} tracks in all views together are matched, got {v.shape[0]}")
+    V = int(v[-1]) + 1 if views is None else int(views)
+    if not 1 <= V <= MAX_VIEWS:
+        raise ValueError(f"between 1 and {MAX_VIEWS} views are taken, got {V}")
+    if (np.diff(v) < 0).any() or v[0] < 0 or v[-1] >= V:
+        raise ValueError(f"view_of must ascend (the tracks are view-major) within 0 .. {V - 1}, got {v.tolist()}")
+    return np.ascontiguousarray(v, np.int32), V
+
+
+def _pair_shapes(kp_shape, flags_shape, view_of, cams_shape):
+    """The shapes of a pair-sums call, checked -> (view_of int32, V, M, T, J)."""
+    if len(kp_shape) != 4 or kp_shape[3] != 2 or kp_shape[1] < 1 or not 1 <= kp_shape[2] <= MAX_ROOT_JOINTS:
+        raise ValueError(f"kp must be (M, T, J, 2) with T >= 1 and 1 <= J <= {MAX_ROOT_JOINTS}, got {tuple(kp_shape)}")
+    M, T, J = (int(n) for n in kp_shape[:3])
+    view_of, V = check_view_of(view_of, cams_shape[0])
+    if len(view_of) != M:
+        raise ValueError(f"view_of must hold one view per track ({M}), got {len(view_of)}")
+    if T * J >= 2 ** 31:
+        raise ValueError(f"T * J must stay below 2^31 (the int32 terms of a pair), got {T} * {J}")
+    if flags_shape is not None and tuple(flags_shape) != (M, T, J):
+        raise ValueError(f"flags must be ({M}, {T}, {J}), got {tuple(flags_shape)}")
+    return view_of, V, M, T, J
+
+
+def _camera_rows(cameras):
+    """V ``Camera`` objects with extrinsics, or their ``view_rows`` already -> (V, 16) float64."""
+    if isinstance(cameras, np.ndarray):
+        if cameras.ndim != 2 or cameras.shape[1] != 16 or not 1 <= cameras.shape[0] <= MAX_VIEWS:
+            raise ValueError(f"camera rows must be (V, 16) with V <= {MAX_VIEWS}, got {cameras.shape}")
+        return np.ascontiguousarray(cameras, np.float64)
+    return view_rows(cameras)
+
+
+def view_pair_sums_host(kp, view_of, cameras, flags=None):
+    """The geometry test of WHO IS WHO (include/uu3d.h) in numpy, written to be read: what uu3d_view_pair_sums computes, bit for bit.
+    ``kp`` (M, T, J, 2): M tracks of T frames, view-major, in the detector's own joints, undistorted (read as float32); ``view_of`` (M,):
+    the view of every track, ascending; ``cameras``: V ``Camera`` objects with extrinsics (or their ``view_rows``); ``flags``: None or
+    (M, T, J), non-zero = the joint was observed -> (sums (M, M) float64, terms (M, M) int32), both symmetric.
+    Everything in float64, every operation rounded once.  A joint is USED in a track iff its flag is set and both coordinates are finite.
+    For tracks p < q of different views v, w, with o = t_w - t_v: oo = (o0 o0 + o1 o1) + o2 o2 not finite or not > 0 -- coincident cameras
+    cannot be matched by geometry --: no terms.  Else per frame and per joint used in both tracks, per track
+        a = (u - cx) / fx;  b = (v - cy) / fy;  d_i = (r1_i a + r2_i b) + r3_i                  (the pixel's ray in world axes)
+    and with dp, dq the two rays
+        c = dp x dq;  cc = (c0 c0 + c1 c1) + c2 c2;  pp, qq: the same of dp, dq;  oc = (o0 c0 + o1 c1) + o2 c2;  e = (oc oc) / cc
+    -- e is the squared distance between the two LINES in world units; the rays are lines, not half-lines, so an intersection behind a
+    camera is not rejected.  The term counts iff cc > ``VIEW_PARALLEL`` (pp qq) and e is finite: 2^-20 is sin^2 of 1e-3 rad, and rays
+    closer than that carry no distance information.  The order of summation is fixed: per frame s_f = 0.0; s_f = s_f + e over the counted
+    joints ascending, n_f their number; lane l of ``MATCH_LANES`` = 256 sums s_f for f = l, l + 256, ... ascending from 0.0; then for
+    stride = 128, 64, ..., 1: x[l] = x[l] + x[l + stride] for l < stride.  sums[p][q] = sums[q][p] = x[0]; terms[p][q] = terms[q][p] = the
+    sum of n_f.  Same-view pairs, the diagonal and pairs without terms hold 0.0 and 0."""
+    uv = np.asarray(_host_array(kp), np.float32)
+    cam = _camera_rows(cameras)
+    f = None if flags is None else np.asarray(_host_array(flags)) != 0
+    view_of, V, M, T, J = _pair_shapes(uv.shape, None if f is None else f.shape, view_of, cam.shape)
+    used = np.isfinite(uv).all(axis=3)
+    if f is not None:
+        used &= f
+    sums, terms = np.zeros((M, M), np.float64), np.zeros((M, M), np.int32)
+    uv64 = uv.astype(np.float64)
+    with np.errstate(all="ignore"):
+        rays = np.empty((M, T, J, 3), np.float64)                        # every track's rays, once
+        for m in range(M):
+            fx, fy, cx, cy = cam[view_of[m], :4]
+            r1, r2, r3 = cam[view_of[m], 4:7], cam[view_of[m], 7:10], cam[view_of[m], 10:13]
+            a = (uv64[m, :, :, 0] - cx) / fx
+            b = (uv64[m, :, :, 1] - cy) / fy
+            for i in range(3):
+                rays[m, :, :, i] = (r1[i] * a + r2[i] * b) + r3[i]
+        for p in range(M):
+            for q in range(p + 1, M):
+                v, w = view_of[p], view_of[q]
+                if v == w:
+                    continue
+                o = cam[w, 13:16] - cam[v, 13:16]
+                oo = (o[0] * o[0] + o[1] * o[1]) + o[2] * o[2]
+                if not np.isfinite(oo) or not oo > 0:
+                    continue
+                s, n = np.zeros(T, np.float64), np.zeros(T, np.int64)
+                for j in range(J):
+                    dp, dq = rays[p, :, j], rays[q, :, j]
+                    c0 = dp[:, 1] * dq[:, 2] - dp[:, 2] * dq[:, 1]
+                    c1 = dp[:, 2] * dq[:, 0] - dp[:, 0] * dq[:, 2]
+                    c2 = dp[:, 0] * dq[:, 1] - dp[:, 1] * dq[:, 0]
+                    cc = (c0 * c0 + c1 * c1) + c2 * c2
+                    pp = (dp[:, 0] * dp[:, 0] + dp[:, 1] * dp[:, 1]) + dp[:, 2] * dp[:, 2]
+                    qq = (dq[:, 0] * dq[:, 0] + dq[:, 1] * dq[:, 1]) + dq[:, 2] * dq[:, 2]
+                    oc = (o[0] * c0 + o[1] * c1) + o[2] * c2
+                    e = (oc * oc) / cc
+                    counts = used[p, :, j] & used[q, :, j] & (cc > VIEW_PARALLEL * (pp * qq)) & np.isfinite(e)
+                    s = np.where(counts, s + e, s)
+                    n += counts
+                x = np.zeros(MATCH_LANES, np.float64)                    # lane l: frames l, l + 256, ... in ascending order
+                for first in range(0, T, MATCH_LANES):
+                    part = s[first:first + MATCH_LANES]
+                    x[:len(part)] = x[:len(part)] + part
+                stride = MATCH_LANES // 2
+                while stride >= 1:                                       # the fixed tree
+                    x[:stride] = x[:stride] + x[stride:2 * stride]
+                    stride //= 2
+                sums[p, q] = sums[q, p] = x[0]
+                terms[p, q] = terms[q, p] = int(n.sum())
+    return sums, terms
+
+
+def _group_shapes(sums_shape, terms_shape, view_of, views):
+    view_of, V = check_view_of(view_of, views)
+    M = len(view_of)
+    if tuple(sums_shape) != (M, M) or tuple(terms_shape) != (M, M):
+        raise ValueError(f"sums and terms must be ({M}, {M}) beside view_of, got {tuple(sums_shape)} and {tuple(terms_shape)}")
+    return view_of, V, M
+
+
+def group_views_host(sums, terms, view_of, views=None, max_dist=MATCH_DEFAULTS["max_dist"], min_terms=MATCH_DEFAULTS["min_terms"]):
+    """The grouping of WHO IS WHO (include/uu3d.h) in plain Python, written to be read: what uu3d_group_views computes.
+    ``sums`` (M, M) float64 and ``terms`` (M, M) int32 of ``view_pair_sums_host``; ``view_of`` (M,) ascending; ``views`` = V (None: the
+    last entry of ``view_of`` + 1) -> (person (M,) int32, n_persons (1,) int32, table (V, M) int32: the track of person k in view v or -1;
+    columns >= n_persons are -1).
+    Greedy and view by view, in the spirit of ``associate_host``; the result depends on the order of the views.  Persons start as the
+    tracks of the first non-empty view, in track order, ids from 0.  For each later view w, ascending: for person k -- members
+    m_1 < m_2 < ..., at most one per view -- and track b of view w: S = 0.0; S = S + sums[m][b] over the members with terms[m][b] > 0 in
+    ascending order; n = the sum of those terms.  The pair is ALLOWED iff n >= ``min_terms`` and S / float(n) <= max_dist * max_dist.
+    Repeatedly the allowed pair (k, b) of smallest S / n among the persons without a track in view w and the unmatched tracks of view w is
+    taken; ties go to the smaller k, then the smaller b.  Persons that existed before the step compete, persons born in it do not.  The
+    unmatched tracks of view w then become new persons, in ascending track order."""
+    S_, N_ = np.asarray(_host_array(sums), np.float64), np.asarray(_host_array(terms), np.int32)
+    view_of, V, M = _group_shapes(S_.shape, N_.shape, view_of, views)
+    max_dist, min_terms = _match_parameters(max_dist, min_terms)
+    limit = np.float64(max_dist) * np.float64(max_dist)
+    person = np.full(M, -1, np.int32)
+    table = np.full((V, M), -1, np.int32)
+    P = 0
+    for w in range(V):
+        tracks = [int(b) for b in np.flatnonzero(view_of == w)]
+        before = P
+        cost = {}
+        for k in range(before):
+            for b in tracks:
+                S, n = np.float64(0.0), 0
+                for u in range(w):                                       # the members in ascending order: one per earlier view
+                    m = int(table[u, k])
+                    if m >= 0 and N_[m, b] > 0:
+                        S = S + S_[m, b]
+                        n += int(N_[m, b])
+                if n >= min_terms and n > 0:
+                    mean = S / np.float64(n)
+                    if mean <= limit:
+                        cost[(k, b)] = mean
+        free_k, free_b = set(range(before)), set(tracks)
+        while True:
+            allowed = [(c, k, b) for (k, b), c in cost.items() if k in free_k and b in free_b]
+            if not allowed:
+                break
+            _, k, b = min(allowed)                                       # smallest cost, then smaller k, then smaller b
+            person[b], table[w, k] = k, b
+            free_k.discard(k)
+            free_b.discard(b)
+        for b in tracks:
+            if b in free_b:
+                person[b], table[w, P] = P, b
+                P += 1
+    return person, np.array([P], np.int32), table
+
+
+def _gather_shapes(src_shape, poses_shape, kp_shape, flags_shape, frames):
+    if len(src_shape) != 2 or not 1 <= src_shape[0] <= MAX_VIEWS or not 1 <= src_shape[1] <= MAX_MATCH_TRACKS:
+        raise ValueError(f"src must be (V, P) with V <= {MAX_VIEWS} and P <= {MAX_MATCH_TRACKS}, got {tuple(src_shape)}")
+    T = int(frames)
+    if len(kp_shape) != 3 or kp_shape[2] != 2 or not 1 <= kp_shape[1] <= MAX_ROOT_JOINTS or T < 1 or kp_shape[0] < T or kp_shape[0] % T:
+        raise ValueError(f"kp2d must be (M * {T}, J, 2) with J <= {MAX_ROOT_JOINTS}, got {tuple(kp_shape)}")
+    rows, J = int(kp_shape[0]), int(kp_shape[1])
+    if rows // T > MAX_MATCH_TRACKS or T * J >= 2 ** 31:
+        raise ValueError(f"at most {MAX_MATCH_TRACKS} tracks with T * J below 2^31 are taken, got {rows // T} tracks of {T} frames")
+    if tuple(poses_shape) != (rows, J, 3):
+        raise ValueError(f"poses must be ({rows}, {J}, 3) beside kp2d, got {tuple(poses_shape)}")
+    if flags_shape is not None and tuple(flags_shape) != (rows, J):
+        raise ValueError(f"flags must be ({rows}, {J}), got {tuple(flags_shape)}")
+    return int(src_shape[0]), int(src_shape[1]), T, J, rows // T
+
+
+def gather_view_tracks_host(src, poses, kp2d, flags=None, frames=1):
+    """The layout step of WHO IS WHO in numpy: what uu3d_gather_view_tracks writes, bit for bit.  ``src`` (V, P) int: the track of person
+    k in view v, or -1 (``table[:, :P]`` of ``group_views_host``); ``poses`` (M * T, J, 3), ``kp2d`` (M * T, J, 2) and ``flags`` None or
+    (M * T, J): the M tracks back to back, ``frames`` = T each -> the padded view-major buffers of ``fuse_views_host``: (V, P * T, J, 3)
+    float32, (V, P * T, J, 2) float32 and (V, P * T, J) uint8.  An absent (view, person) block -- -1, or anything outside 0 .. M - 1 --
+    gets zero poses, NaN keypoints and flags 0: that view then does not SEE the frame.  Without ``flags`` a present block's flags are 1."""
+    idx = np.asarray(_host_array(src))
+    P_, uv = np.asarray(_host_array(poses), np.float32), np.asarray(_host_array(kp2d), np.float32)
+    f = None if flags is None else (np.asarray(_host_array(flags)) != 0).astype(np.uint8)
+    V, P, T, J, M = _gather_shapes(idx.shape, P_.shape, uv.shape, None if f is None else f.shape, frames)
+    out_p = np.zeros((V, P * T, J, 3), np.float32)
+    out_k = np.full((V, P * T, J, 2), np.nan, np.float32)
+    out_f = np.zeros((V, P * T, J), np.uint8)
+    for v in range(V):
+        for k in range(P):
+            m = int(idx[v, k])
+            if 0 <= m < M:
+                out_p[v, k * T:(k + 1) * T] = P_[m * T:(m + 1) * T]
+                out_k[v, k * T:(k + 1) * T] = uv[m * T:(m + 1) * T]
+                out_f[v, k * T:(k + 1) * T] = 1 if f is None else f[m * T:(m + 1) * T]
+    return out_p, out_k, out_f
+
+
+def _is_device(t, dtype, dev=None):
+    import torch
+    return isinstance(t, torch.Tensor) and t.is_cuda and t.dtype in (dtype if isinstance(dtype, tuple) else (dtype,)) and t.is_contiguous() \
+        and (dev is None or t.device == dev)
+
+
+def view_pair_sums(kp, view_of, cameras, flags=None):
+    """uu3d_view_pair_sums on the current stream: ``view_pair_sums_host`` on device tensors, one launch, nothing copies to the host or
+    waits (the camera rows go up pinned and asynchronously; ``view_of`` is a host array).  ``kp`` (M, T, J, 2) float32 on the device,
+    contiguous (only read); ``flags`` (M, T, J) uint8 / bool on the device or None -> (sums (M, M) float64, terms (M, M) int32), fresh
+    device buffers.  Needs no model."""
+    import torch
+    lib = _capi.load_library()
+    if not _is_device(kp, torch.float32):
+        raise ValueError(f"kp must be a contiguous (M, T, J, 2) float32 device tensor, got {tuple(getattr(kp, 'shape', ()))}")
+    if flags is not None and not _is_device(flags, (torch.uint8, torch.bool), kp.device):
+        raise ValueError("flags must be a contiguous (M, T, J) uint8 or bool tensor on kp's device")
+    rows = _camera_rows(cameras)
+    view_of, V, M, T, J = _pair_shapes(tuple(kp.shape), None if flags is None else tuple(flags.shape), view_of, rows.shape)
+    dev = kp.device
+    cams = _upload(rows, np.float64, dev)
+    sums = torch.empty((M, M), dtype=torch.float64, device=dev)
+    terms = torch.empty((M, M), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _capi.check(lib, lib.uu3d_view_pair_sums(_ptr(kp), _ptr(None if flags is None else flags.view(torch.uint8)),
+                                                 view_of.ctypes.data_as(C.POINTER(C.c_int32)), M, T, J, V, _ptr(cams), _ptr(sums), _ptr(terms),
+                                                 C.c_void_p(stream)), None)
+    return sums, terms
+
+
+def group_views(sums, terms, view_of, views=None, max_dist=MATCH_DEFAULTS["max_dist"], min_terms=MATCH_DEFAULTS["min_terms"]):
+    """uu3d_group_views on the current stream: ``group_views_host`` on device tensors, one launch of one wave, nothing copies to the host
+    or waits.  ``sums`` (M, M) float64 and ``terms`` (M, M) int32 on the device, contiguous (only read)
+    -> (person (M,) int32, n_persons (1,) int32, table (V, M) int32), fresh device buffers.  Needs no model."""
+    import torch
+    lib = _capi.load_library()
+    if not _is_device(sums, torch.float64) or not _is_device(terms, torch.int32, sums.device):
+        raise ValueError("sums must be a contiguous (M, M) float64 device tensor and terms an int32 one on its device")
+    view_of, V, M = _group_shapes(tuple(sums.shape), tuple(terms.shape), view_of, views)
+    max_dist, min_terms = _match_parameters(max_dist, min_terms)
+    dev = sums.device
+    person = torch.empty((M,), dtype=torch.int32, device=dev)
+    count = torch.empty((1,), dtype=torch.int32, device=dev)
+    table = torch.empty((V, M), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _capi.check(lib, lib.uu3d_group_views(_ptr(sums), _ptr(terms), view_of.ctypes.data_as(C.POINTER(C.c_int32)), M, V, max_dist, min_terms,
+                                              _ptr(person), _ptr(count), _ptr(table), C.c_void_p(stream)), None)
+    return person, count, table
+
+
+def gather_view_tracks(src, poses, kp2d, flags=None, frames=1):
+    """uu3d_gather_view_tracks on the current stream: ``gather_view_tracks_host`` on device tensors, one launch, nothing copies to the
+    host or waits.  ``src`` (V, P) int32, ``poses`` (M * T, J, 3) float32, ``kp2d`` (M * T, J, 2) float32 and ``flags`` (M * T, J) uint8 /
+    bool or None, on the device, contiguous (only read) -> the three padded view-major buffers, fresh.  Needs no model."""
+    import torch
+    lib = _capi.load_library()
+    if not _is_device(kp2d, torch.float32) or not _is_device(poses, torch.float32, kp2d.device) or not _is_device(src, torch.int32, kp2d.device):
+        raise ValueError("src (V, P) int32, poses (M * T, J, 3) float32 and kp2d (M * T, J, 2) float32 must be contiguous tensors on one device")
+    if flags is not None and not _is_device(flags, (torch.uint8, torch.bool), kp2d.device):
+        raise ValueError("flags must be a contiguous (M * T, J) uint8 or bool tensor on kp2d's device")
+    V, P, T, J, M = _gather_shapes(tuple(src.shape), tuple(poses.shape), tuple(kp2d.shape), None if flags is None else tuple(flags.shape), frames)
+    dev = kp2d.device
+    out_p = torch.empty((V, P * T, J, 3), dtype=torch.float32, device=dev)
+    out_k = torch.empty((V, P * T, J, 2), dtype=torch.float32, device=dev)
+    out_f = torch.empty((V, P * T, J), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _capi.check(lib, lib.uu3d_gather_view_tracks(_ptr(src), _ptr(poses), _ptr(kp2d), _ptr(None if flags is None else flags.view(torch.uint8)),
+                                                     V, P, T, J, M, _ptr(out_p), _ptr(out_k), _ptr(out_f), C.c_void_p(stream)), None)
+    return out_p, out_k, out_f
+
+
+def _match_inputs(views, cameras, valid):
+    """The refusals of ``match_views`` that need no device -> (the cameras, tracks per view, the M tracks view-major, their ``valid``
+    entries or None / "finite", T)."""
+    if not isinstance(views, (list, tuple)) or not 1 <= len(views) <= MAX_VIEWS or not all(isinstance(v, (list, tuple)) for v in views):
+        raise ValueError(f"views must be a list of 1 to {MAX_VIEWS} lists of tracks, one list per camera, got "
+                         f"{len(views) if isinstance(views, (list, tuple)) else type(views).__name__}")
+    cams = check_view_cameras(cameras, len(views))
+    counts = [len(v) for v in views]
+    flat = [t for tracks in views for t in tracks]
+    if not flat:
+        raise ValueError("match: at least one view must hold a track")
+    if len(flat) > MAX_MATCH_TRACKS:
+        raise ValueError(f"match: at most {MAX_MATCH_TRACKS} tracks in all views together are matched, got {len(flat)}")
+    shapes = [_shape(t) for t in flat]
+    if any(len(s) != 3 or s[2] != 2 for s in shapes):
+        raise ValueError(f"a track must be (T, K, 2), got {[tuple(s) for s in shapes if len(s) != 3 or s[2] != 2][0]}")
+    if len({int(s[0]) for s in shapes}) != 1 or int(shapes[0][0]) < 1:
+        raise ValueError(f"match: all tracks are on one clock and need one common number of frames T >= 1, got {sorted({int(s[0]) for s in shapes})}")
+    if len({int(s[1]) for s in shapes}) != 1 or not 1 <= int(shapes[0][1]) <= MAX_ROOT_JOINTS:
+        raise ValueError(f"match: all tracks need the same 1 to {MAX_ROOT_JOINTS} joints, got {sorted({int(s[1]) for s in shapes})}")
+    flat_valid = valid
+    if valid is not None and not isinstance(valid, str):
+        if not isinstance(valid, (list, tuple)) or len(valid) != len(views) or \
+                not all(isinstance(f, (list, tuple)) and len(f) == n for f, n in zip(valid, counts)):
+            raise ValueError(f"valid must be None, \"finite\" or a list of {len(views)} lists, one per view, of {counts} entries")
+        flat_valid = [f for per_view in valid for f in per_view]
+    elif isinstance(valid, str) and valid != "finite":
+        raise ValueError(f"valid must be None, \"finite\" or a list of lists, got {valid!r}")
+    return cams, counts, flat, flat_valid, int(shapes[0][0])
+
+
+def _joint_flags_host(flat_valid, T, K):
+    """Per-track ``valid`` entries, (T,) or (T, K) -> (M, T, K) uint8, or None without a list (the finite test alone)."""
+    if flat_valid is None or isinstance(flat_valid, str):
+        return None
+    out = []
+    for f in flat_valid:
+        a = np.asarray(_host_array(f)) != 0
+        if a.shape not in ((T,), (T, K)):
+            raise ValueError(f"an entry of valid must be ({T},) or ({T}, {K}), got {a.shape}")
+        out.append(np.broadcast_to(a[:, None] if a.ndim == 1 else a, (T, K)))
+    return np.ascontiguousarray(np.stack(out), np.uint8)
+
+
+def match_views_host(views, cameras, valid=None, max_dist=MATCH_DEFAULTS["max_dist"], min_terms=MATCH_DEFAULTS["min_terms"]):
+    """``match_views`` built from the mirrors -- ``undistort_points_host``, ``view_pair_sums_host``, ``group_views_host`` -- on host arrays
+    -> (person (M,) int32, n_persons (1,) int32, table (V, M) int32, sums (M, M) float64, terms (M, M) int32)."""
+    from .camera import undistort_points_host
+    cams, counts, flat, flat_valid, T = _match_inputs(views, cameras, valid)
+    view_of = np.repeat(np.arange(len(cams), dtype=np.int32), counts)
+    flat = [undistort_points_host(np.asarray(_host_array(t), np.float32), cams[v]) if cams[v].has_distortion else np.asarray(_host_array(t), np.float32)
+            for t, v in zip(flat, view_of)]
+    kp = np.stack(flat)
+    sums, terms = view_pair_sums_host(kp, view_of, cams, _joint_flags_host(flat_valid, T, kp.shape[2]))
+    return group_views_host(sums, terms, view_of, len(cams), max_dist, min_terms) + (sums, terms)
+
+
+def _undistorted_tracks(flat, cams, counts, device):
+    """The M tracks on the device, those of cameras with distortion undistorted by ONE uu3d_undistort_points -> (list of (T, K, 2) tensors,
+    frames per track)."""
+    import torch
+    tr, _, given = _device_tracks(flat, device)
+    view_of = np.repeat(np.arange(len(cams)), counts)
+    bent = [m for m in range(len(tr)) if cams[view_of[m]].has_distortion]
+    if bent:
+        src = torch.cat([tr[m] for m in bent], 0).contiguous() if len(bent) > 1 else tr[bent[0]].contiguous()
+        src = undistort_rows(src, np.stack([cams[view_of[m]].row() for m in bent]), given[bent])
+        for m, t in zip(bent, torch.split(src, [int(n) for n in given[bent]], 0)):
+            tr[m] = t
+    return tr, given
+
+
+def _match_device(tr, cams, counts, flat_valid, params):
+    """The two launches of ``match_views`` on undistorted device tracks -> (person, n_persons, table, sums, terms)."""
+    import torch
+    dev = tr[0].device
+    kp = torch.stack(tr).contiguous()
+    M, T, K = (int(n) for n in kp.shape[:3])
+    flags = None
+    if flat_valid is not None and not isinstance(flat_valid, str):
+        if all(isinstance(f, torch.Tensor) for f in flat_valid):
+            per = []
+            for f in flat_valid:
+                if tuple(f.shape) not in ((T,), (T, K)):
+                    raise ValueError(f"an entry of valid must be ({T},) or ({T}, {K}), got {tuple(f.shape)}")
+                f = (f.to(dev) != 0).to(torch.uint8)
+                per.append(f[:, None].expand(T, K) if f.dim() == 1 else f)
+            flags = torch.stack(per).contiguous()
+        else:
+            flags = _upload(_joint_flags_host(flat_valid, T, K), np.uint8, dev)
+    view_of = np.repeat(np.arange(len(cams), dtype=np.int32), counts)
+    sums, terms = view_pair_sums(kp, view_of, cams, flags)
+    return group_views(sums, terms, view_of, len(cams), params.max_dist, params.min_terms) + (sums, terms)
+
+
+def match_views(views, cameras, valid=None, max_dist=MATCH_DEFAULTS["max_dist"], min_terms=MATCH_DEFAULTS["min_terms"], device=None):
+    """Who is who across V calibrated cameras, on the device: ``views[v]`` is a list of N_v tracks (T, K, 2) -- any number per view, an
+    empty view included, in any order, on the host or the device, all of one length T and one clock --, ``cameras`` V ``Camera`` objects
+    with extrinsics, ``valid`` as ``predict_views`` takes it (None, "finite" -- the finite test always holds -- or a list of V lists of
+    (T,) or (T, K) flags).  The tracks of cameras with distortion are undistorted (uu3d_undistort_points), then uu3d_view_pair_sums and
+    uu3d_group_views run -> (person (M,) int32: the person of every track, view-major, n_persons (1,) int32, table (V, M) int32, sums
+    (M, M) float64, terms (M, M) int32) on the device; nothing copies to the host or waits.  The rules stand in ``view_pair_sums_host``
+    and ``group_views_host``; ``match_views_host`` is the same call on the host, and the two agree bit for bit.  ``max_dist`` (world
+    units) and ``min_terms`` default to ``MATCH_DEFAULTS``: conveniences for metres, not tuned values.  Needs no model."""
+    import torch
+    params = MatchViews(max_dist, min_terms)
+    cams, counts, flat, flat_valid, _ = _match_inputs(views, cameras, valid)
+    if device is None:
+        on = [t.device for t in flat if isinstance(t, torch.Tensor) and t.is_cuda]
+        device = on[0] if on else torch.device("cuda", torch.cuda.current_device())
+    tr, _ = _undistorted_tracks(flat, cams, counts, torch.device(device))
+    return _match_device(tr, cams, counts, flat_valid, params)
+
+
 def _check_views(views, cameras, valid, keyframes_only, out_fps):
     """The refusals of ``predict_views`` that need no device -> (the cameras, V, N, frames per person)."""
     if keyframes_only:
@@ -266,9 +716,42 @@ def _check_views(views, cameras, valid, keyframes_only, out_fps):
     return cams, V, N, frames
 
 
+def _fused_scene(pt, person, world, kp2d, flags, cams, lens, rates, model_fps, return_views):
+    """Stages 3 to 6 of the module's docstring, behind uu3d_camera_to_world: ``world`` (V, R, J, 3), ``kp2d`` (V, R, J, 2) and ``flags`` None
+    or (V, R, J), view-major, the same person at the same rows of every view; ``person``: the ``StageOptions`` of the persons; ``lens``:
+    frames per person -> what ``predict_views`` returns."""
+    import torch
+    # 4. the fusion
+    fused, view_count, _ = fuse_views(world, kp2d, flags, person.min_root_joints)
+    # 5. bones on the fused poses of the N persons
+    if person.rigid is not None:
+        skeleton, known = person.rigid
+        bone_table = pt.bone_lengths(fused, lens, skeleton) if known is None else _upload(known, np.float64, fused.device)
+        fused = pt.fix_bones(fused, lens, bone_table, skeleton)
+    # 6. + 7. one world root per frame from all views, joined to each person's trajectory
+    solved_roots, solved = solve_view_roots(fused, kp2d, cams, flags, person.min_root_joints)
+    roots, root_state = pt.root_trajectory(solved_roots, solved, lens, None)
+    # 8. filters and rotations on the fused world scene, in the order of predict_tracks
+    shown = fused
+    if person.pose_filter is not None or person.root_filter is not None:
+        out_rate = model_fps if rates is None else rates
+    if person.pose_filter is not None:
+        shown = pt.one_euro(shown, lens, out_rate, person.pose_filter)
+    if person.root_filter is not None:
+        roots = pt.one_euro(roots, lens, out_rate, person.root_filter, state=root_state)
+    sizes = [int(n) for n in lens]
+    result = tuple(list(torch.split(a, sizes, 0)) for a in (shown, roots, root_state, view_count))
+    if person.rotations is not None:
+        turned = pt.joint_rotations(shown, person.rotations)
+        result += (list(torch.split(turned[0], sizes, 0)),) + ((list(torch.split(turned[2], sizes, 0)),) if person.rotations.return_global else ())
+    if return_views:
+        result += ([list(torch.split(block, sizes, 0)) for block in world],)
+    return result
+
+
 def predict_views(model, config, views, cameras, resolutions=None, mask_stride=None, flip=None, reuse_frames=True, batch_size=None, depth=None,
                   graph=True, valid=None, fps=None, model_fps=50, repair_joints=None, keypoints=None, min_root_joints=DEFAULT_MIN_ROOT_JOINTS,
-                  smooth=None, bones=None, rotations=None, interpolation="linear", return_views=False, keyframes_only=False, out_fps=None):
+                  smooth=None, bones=None, rotations=None, interpolation="linear", return_views=False, keyframes_only=False, out_fps=None, match=None):
     """One world scene from V calibrated views of the same N persons -> (poses, roots, root_state, view_count): per person ``poses``
     (T_i, J, 3) float32 in world axes and root-relative, ``roots`` (T_i, 3) float32 in world coordinates, ``root_state`` (T_i,) uint8 (1
     solved here, 2 interpolated or held, 0 no solved frame) and ``view_count`` (T_i,) uint8, the views that saw the frame; on the model's
@@ -277,7 +760,7 @@ def predict_views(model, config, views, cameras, resolutions=None, mask_stride=N
 
     ``views``: a list of V lists, 1 <= V <= 8; ``views[v][i]`` is person i's 2D track in camera v, (T_i, J, 2), or (T_i, K_in, 2) with
     ``keypoints``.  The same index is the same person, frames are time-synchronised and person i has the same T_i in every view (anything
-    else: ValueError; finding who is who across cameras and aligning clocks are out of scope).  A view that does not see the person at a
+    else: ValueError, unless ``match`` finds who is who across cameras, below; aligning clocks is out of scope).  A view that does not see the person at a
     frame passes NaN coordinates there (with ``valid="finite"``) or cleared flags.  ``cameras``: V ``Camera`` objects, all with
     extrinsics, each with or without distortion, one per view and shared by its persons.  ``resolutions``: None, one (w, h) or one per
     view.  ``valid``: as in ``predict_tracks``, per view -- None, "finite" or a list of V lists.  ``fps``: one rate, or one per person.
@@ -291,9 +774,26 @@ def predict_views(model, config, views, cameras, resolutions=None, mask_stride=N
     here, which the front of ``predict_tracks`` refuses).  The result equals, bit for bit, the host composition on
     ``predict_tracks(flattened tracks, camera=the cameras minus extrinsics, one per track)``: ``camera_to_world_host``,
     ``fuse_views_host``, ``fix_bones_host``, ``solve_view_roots_host``, ``root_trajectory_host``, ``one_euro_host``,
-    ``joint_rotations_host``.  No accuracy is claimed."""
+    ``joint_rotations_host``.  No accuracy is claimed.
+
+    Who is who -- ``match``: None = the call above, the same launches, buffers, refusals and bits.  True (``MATCH_DEFAULTS``) or a
+    ``MatchViews(max_dist=, min_terms=)``: ``views[v]`` is the list of camera v's N_v tracks in ANY order -- other counts per view, an
+    empty view as long as one is not --, M = sum N_v <= 64 tracks, all with the same T (anything else: ValueError) and one ``fps``.
+    ``bones`` as a per-person list is refused (the persons are not known beforehand); "track", one array and a ``Bones`` stay.  The
+    tracks are undistorted and matched on the detector's joints, in front of any ``keypoints`` map (``match_views``); then ``person``,
+    ``n_persons`` and ``table`` are copied to the host -- the ONE copy of the call, M + 1 + V M int32, which waits for the two launches:
+    the number of persons P shapes every buffer behind it.  All M tracks run through the front as given, go to world axes (block sizes
+    N_v T), uu3d_gather_view_tracks lays them out per person, and the fusion, ``bones``, the root solve, the trajectory, ``smooth`` and
+    ``rotations`` run unchanged on P persons.  -> today's tuple with P persons, followed by ``person``: per view a list of N_v ints, the
+    person of each given track.  A person seen by one camera comes out with ``view_count`` <= 1 and the monocular root.  The result
+    equals, bit for bit, the host composition with ``match_views_host`` and ``gather_view_tracks_host`` in front of the fusion."""
     import torch
     from . import predict as pt
+    match = check_match(match)
+    if match is not None:
+        return _predict_matched_views(pt, match, model, config, views, cameras, resolutions, mask_stride, flip, reuse_frames, batch_size, depth, graph,
+                                      valid, fps, model_fps, repair_joints, keypoints, min_root_joints, smooth, bones, rotations, interpolation,
+                                      return_views, keyframes_only, out_fps)
     cams, V, N, frames = _check_views(views, cameras, valid, keyframes_only, out_fps)
     # the options of the N persons: what runs behind the fusion (the flattened front takes none of them)
     person = pt.stage_options(config, N, "track", True, keypoints, cams[0].without(distortion=True, extrinsics=True), min_root_joints, smooth,
@@ -323,30 +823,58 @@ def predict_views(model, config, views, cameras, resolutions=None, mask_stride=N
     kp2d, flags = front.table.source
     # 3. every view's poses to world axes: the existing launch, poses only, one row of extrinsics per view block
     world, _ = camera_to_world_rows(front.out, None, None, np.stack([c.pose_row() for c in cams]), [R] * V)
-    # 4. the fusion
-    kp2d, flags = kp2d.reshape(V, R, J, 2), None if flags is None else flags.reshape(V, R, J)
-    fused, view_count, _ = fuse_views(world.view(V, R, J, 3), kp2d, flags, person.min_root_joints)
-    # 5. bones on the fused poses of the N persons
-    if person.rigid is not None:
-        skeleton, known = person.rigid
-        bone_table = pt.bone_lengths(fused, lens, skeleton) if known is None else _upload(known, np.float64, fused.device)
-        fused = pt.fix_bones(fused, lens, bone_table, skeleton)
-    # 6. + 7. one world root per frame from all views, joined to each person's trajectory
-    solved_roots, solved = solve_view_roots(fused, kp2d, cams, flags, person.min_root_joints)
-    roots, root_state = pt.root_trajectory(solved_roots, solved, lens, None)
-    # 8. filters and rotations on the fused world scene, in the order of predict_tracks
-    shown = fused
-    if person.pose_filter is not None or person.root_filter is not None:
-        out_rate = model_fps if rates is None else rates
-    if person.pose_filter is not None:
-        shown = pt.one_euro(shown, lens, out_rate, person.pose_filter)
-    if person.root_filter is not None:
-        roots = pt.one_euro(roots, lens, out_rate, person.root_filter, state=root_state)
-    sizes = [int(n) for n in lens]
-    result = tuple(list(torch.split(a, sizes, 0)) for a in (shown, roots, root_state, view_count))
-    if person.rotations is not None:
-        turned = pt.joint_rotations(shown, person.rotations)
-        result += (list(torch.split(turned[0], sizes, 0)),) + ((list(torch.split(turned[2], sizes, 0)),) if person.rotations.return_global else ())
-    if return_views:
-        result += ([list(torch.split(block, sizes, 0)) for block in world.view(V, R, J, 3)],)
-    return result
+    return _fused_scene(pt, person, world.view(V, R, J, 3), kp2d.reshape(V, R, J, 2), None if flags is None else flags.reshape(V, R, J), cams, lens,
+                        rates, model_fps, return_views)
+
+
+def _predict_matched_views(pt, match, model, config, views, cameras, resolutions, mask_stride, flip, reuse_frames, batch_size, depth, graph, valid,
+                           fps, model_fps, repair_joints, keypoints, min_root_joints, smooth, bones, rotations, interpolation, return_views,
+                           keyframes_only, out_fps):
+    """``predict_views(match=...)``: the steps of its docstring, "Who is who"."""
+    import torch
+    if keyframes_only:
+        raise ValueError("predict_views does not take keyframes_only: the fusion needs one returned frame per given frame of every view")
+    if out_fps is not None:
+        raise ValueError("predict_views does not take out_fps: the fusion needs one returned frame per given frame of every view")
+    cams, counts, flat, flat_valid, T = _match_inputs(views, cameras, valid)
+    V, M = len(cams), len(flat)
+    if isinstance(bones, (list, tuple)):
+        raise ValueError("predict_views(match=...) does not take bones as a per-person list: the persons are not known beforehand; "
+                         "pass \"track\", one array of lengths or a Bones")
+    rate = None
+    if fps is not None:
+        if isinstance(fps, (list, np.ndarray)):
+            raise ValueError("predict_views(match=...) takes one fps for all tracks, not a list: they are on one clock")
+        rate = pt.frame_rates(fps, 1)[0]
+    # every refusal of the persons' options before any device work (they are checked again for the P persons found)
+    pinhole0 = cams[0].without(distortion=True, extrinsics=True)
+    pt.stage_options(config, 1, "track", True, keypoints, pinhole0, min_root_joints, smooth, bones, repair_joints, fps, None,
+                     interpolation=interpolation, rotations=rotations)
+    view_of = np.repeat(np.arange(V), counts)
+    res = None if resolutions is None else pt.check_resolutions(resolutions, V, per="view")[view_of]
+    # 0a. + 0b. undistort, then who is who on the detector's joints; the one copy of the call
+    tr, _ = _undistorted_tracks(flat, cams, counts, torch.device(model.device))
+    person_dev, count_dev, table_dev, _, _ = _match_device(tr, cams, counts, flat_valid, match)
+    back = torch.cat([person_dev, count_dev, table_dev.reshape(-1)]).cpu().numpy()
+    who, P, table = back[:M], int(back[M]), back[M + 1:].reshape(V, M)
+    person = pt.stage_options(config, P, "track", True, keypoints, pinhole0, min_root_joints, smooth, bones, repair_joints, fps, None,
+                              interpolation=interpolation, rotations=rotations)
+    # 1. one run of the front, the windows, the forwards and the assembly over the M tracks as given
+    pinhole = [cams[v].without(distortion=True, extrinsics=True) for v in view_of]
+    front = pt._assembled_tracks(model, config, tr, res, mask_stride, flip, False, reuse_frames, batch_size, True, depth, None, graph, flat_valid,
+                                 None if rate is None else [rate] * M, None, model_fps, repair_joints, keypoints, pinhole, min_root_joints, None, None,
+                                 None, interpolation)
+    if [int(n) for n in front.lens] != [T] * M or tuple(front.out.shape[:1]) != (M * T,):
+        raise ValueError("predict_views: the assembly did not return one frame per given frame")      # (cannot happen without out_fps / keyframes_only)
+    J = int(front.out.shape[1])
+    kp2d, flags = front.table.source
+    # 2. every track's poses to world axes: one row of extrinsics per non-empty view block of N_v T rows
+    seen = [v for v in range(V) if counts[v] > 0]
+    world, _ = camera_to_world_rows(front.out, None, None, np.stack([cams[v].pose_row() for v in seen]), [counts[v] * T for v in seen])
+    # 0c. the persons' tracks, view-major and padded
+    src = _upload(table[:, :P], np.int32, world.device)
+    world, kp2d, flags = gather_view_tracks(src, world, kp2d.contiguous(), None if flags is None else flags.contiguous(), T)
+    lens = np.full(P, T, np.int64)
+    result = _fused_scene(pt, person, world, kp2d, flags, cams, lens, None if rate is None else [rate] * P, model_fps, return_views)
+    starts = np.concatenate([[0], np.cumsum(counts)])
+    return result + ([[int(k) for k in who[starts[v]:starts[v + 1]]] for v in range(V)],)
