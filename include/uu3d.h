@@ -818,6 +818,59 @@ int uu3d_gather_view_tracks(const int32_t* src_dev, const float* poses_dev, cons
                             float* out_kp2d_dev, uint8_t* out_flags_dev, void* stream);
 
 /*
+ * ONE CLOCK (predict.view_lag_sums, predict.view_offsets, predict.align_views, predict.crop_views, predict.predict_views(align=...)):
+ * SEVERAL VIEWS and WHO IS WHO take frame f of every view for the same instant, but cameras started by hand are seconds apart.  The two
+ * calls here find every camera's clock offset, in whole frames, from the geometry alone: the squared distance between the lines of PAIR
+ * SUMS is smallest when the two frames belong together.  predict.view_lag_sums_host and predict.view_offsets_host are the same rules in
+ * numpy, bit for bit.  In float64 on the float32 inputs, every operation rounded once, no fused multiply-add.  Alignment is against the
+ * reference view only: a camera that shares no person with it cannot be aligned, and there is no chaining through a third camera.
+ * Offsets are whole frames of one common rate (up to half a frame remains; no sub-frame refinement, no per-camera frame rates).  Periodic
+ * or standing motion is ambiguous: ties go to the smallest shift, and no claim is made for such scenes.  No accuracy is claimed.
+ * TRACKS AND CLOCKS.  M tracks in all, 1 <= M <= 64, view-major, view_of_host (M) i32 ascending as in WHO IS WHO.  Every track starts at
+ * frame 0 of its camera's clock and has its own length frames[m] >= 1: track m is rows first_row_host[m] .. first_row_host[m + 1] - 1 of
+ * kp_dev (rows, J, 2) f32 -- the detector's own joints, undistorted --, first_row_host (M + 1) i64 in HOST memory, strictly ascending,
+ * rows = first_row_host[M]; joint_flags_dev (rows, J) u8 or NULL; a joint is USED as in SEVERAL VIEWS.  View v's frame f was taken at
+ * common time f + o_v.  The reference view r is the first non-empty view and o_r = 0; its tracks are 0 .. N_r - 1.
+ * LAG SUMS.  For every track p of the reference view, every track q of a later view w and every lag l in -L .. L (l stands for
+ * o_w - o_r): frame f of p pairs with frame g = f - l of q.  Per paired frame and per joint used in both, the term is e exactly as PAIR
+ * SUMS defines it: the rays, c, cc, oc, the 2^-20 parallel test, the finite test, and no terms for coincident cameras.  The order is that
+ * of PAIR SUMS over p's frames: s_f = 0.0, s_f = s_f + e over the counted joints ascending, n_f their number; a frame f without a
+ * partner (g < 0 or g >= q's length) has s_f = 0.0 and n_f = 0; lane i of 256 sums s_f for f = i, i + 256, ... ascending from 0.0; then
+ * for stride = 128, 64, ..., 1: x[i] = x[i] + x[i + stride] for i < stride.  sums[p][q][l + L] = x[0], terms[p][q][l + L] = the sum of
+ * n_f: sums (N_r, M, 2L + 1) f64, terms (N_r, M, 2L + 1) i32.  The columns q of the reference view hold 0.0 and 0.  For two tracks of
+ * equal length the slice at l = 0 is uu3d_view_pair_sums' sums[p][q] and terms[p][q], bit for bit.
+ * OFFSETS.  For each later non-empty view w and each lag: S = 0.0, n = 0 (a 64-bit integer); for each reference track p ascending, the
+ * candidates are the tracks q of w with terms[p][q][l + L] >= min_terms -- with same_index != 0 only the track with p's index inside its
+ * view --; among them the one of smallest sums / (double) terms is taken, ties to the smaller q, and S = S + sums, n = n + terms.  The lag
+ * is ALLOWED iff some p had a candidate; its score is S / (double) n.  The view takes the allowed lag of smallest score, ties to the
+ * smaller |l|, then to the smaller l: offset[w] = l, state[w] = 1, score[w].  A view without an allowed lag: offset 0, state 0, score
+ * 0.0.  The reference view and empty views: offset 0, state 1, score 0.0.
+ *
+ *   uu3d_view_lag_scratch_bytes(rows, J): the rays of every row's joints, three f64 each, then a byte per joint; 0 for arguments out of
+ *       range.
+ *   uu3d_view_lag_sums(kp_dev 8-byte aligned, joint_flags_dev or NULL, view_of_host, first_row_host, tracks, J, views, cameras_dev
+ *       (views, 16) f64 as in SEVERAL VIEWS, max_lag = L, scratch_dev 8-byte aligned of uu3d_view_lag_scratch_bytes(rows, J) bytes,
+ *       sums_dev, terms_dev, stream): two launches.  The first writes every joint's ray and whether it is used into scratch_dev, one lane
+ *       per (row, joint), so that the divisions and the rotation are not repeated 2L + 1 times; the second runs one workgroup of 256
+ *       lanes per (p, q, lag), the fixed tree through LDS.  The per-joint expression is one device function shared with
+ *       uu3d_view_pair_sums.
+ *   uu3d_view_offsets(sums_dev, terms_dev, view_of_host, tracks, views, max_lag, min_terms >= 1, same_index, offset_dev (views) i32,
+ *       state_dev (views) i32, score_dev (views) f64, stream): one launch of one wave, the lags over the lanes, the minimum by a butterfly
+ *       of exact comparisons.
+ * Both: views > 8, tracks > 64, J > 64 or max_lag > 512: UU3D_ERR_UNSUPPORTED; max_lag < 1, min_terms < 1, bad counts, NULLs,
+ * misalignment, a view_of_host that does not ascend, a first_row_host that does not ascend strictly, a track with frames * J >= 2^31 or
+ * same_index with unequal non-empty view sizes: UU3D_ERR_INVALID_ARGUMENT -- every guard before any device call.  Every output element
+ * has one writer, no atomics, the inputs are only read, nothing copies to the host or waits: bitwise repeatable.
+ */
+size_t uu3d_view_lag_scratch_bytes(int64_t rows, int32_t num_keypoints);
+int uu3d_view_lag_sums(const float* kp_dev, const uint8_t* joint_flags_dev, const int32_t* view_of_host, const int64_t* first_row_host,
+                       int32_t tracks, int32_t num_keypoints, int32_t views, const double* cameras_dev, int32_t max_lag, void* scratch_dev,
+                       double* sums_dev, int32_t* terms_dev, void* stream);
+int uu3d_view_offsets(const double* sums_dev, const int32_t* terms_dev, const int32_t* view_of_host, int32_t tracks, int32_t views,
+                      int32_t max_lag, int32_t min_terms, int32_t same_index, int32_t* offset_dev, int32_t* state_dev, double* score_dev,
+                      void* stream);
+
+/*
  * ANY FRAME RATE (predict.predict_tracks(fps=...)): the front of YOUR OWN 2D TRACKS for tracks that were not filmed at the rate the model
  * was trained for.  The table holds the MODEL's time grid: row `row` (track row_track_dev[row]) is model frame k of its track, which sits at
  * source position p_k = k * fps / model_fps.  The host works the positions out in exact integer arithmetic (predict.resample_plan) and

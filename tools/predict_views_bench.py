@@ -6,7 +6,11 @@ process, seeded weights, synthetic tracks.  Informational: no threshold.
 ``match_views_host`` followed by today's ``predict_views`` on the views regrouped per person (a person a camera does not see: an all-NaN
 track there, ``valid="finite"``), and ``match_views`` alone at M = 16 and 64 tracks of 2500 frames beside its mirror (the mirror once).
 
-    python tools/predict_views_bench.py [--config h36m_81] [--persons 2] [--frames 1000] [--match]
+``--align [--max_lag L]`` times ``align_views`` (3 cameras, ``--persons`` swaying persons, views of ``--frames`` -10 / +0 / -20 frames with
+clock offsets 0 / -3 / +5, and 16 tracks of 2500 frames at ``max_lag`` 50) beside ``align_views_host`` (the mirror once), and
+``predict_views(align=True)`` beside ``predict_views`` on the views cropped beforehand.
+
+    python tools/predict_views_bench.py [--config h36m_81] [--persons 2] [--frames 1000] [--match | --align [--max_lag 50]]
 """
 import argparse
 import json
@@ -118,6 +122,70 @@ def _match_rows(model, cfg, args):
     return rows
 
 
+def _swaying(cams, persons, lengths, offsets, J, seed=1):
+    """Persons on steps whose centres sway by 0.3 m per axis, periods of 35 to 90 frames (the scenes of tests/view_align_util.py); view v
+    is cut from the common timeline at offsets[v] with lengths[v] frames, every person in every view, in order."""
+    from uplift_upsample_3dhpe_amd import predict
+    rng = np.random.default_rng(seed)
+    fx, fy, cx, cy = cams[0].intrinsics
+    base = min(offsets)
+    Tc = max(n + o - base for n, o in zip(lengths, offsets))
+    t = np.arange(Tc)[:, None]
+    world = []
+    for i in range(persons):
+        ang = 2.0 * np.pi * i / max(persons, 3) + 0.4
+        centre = np.array([np.cos(ang), np.sin(ang), 0.0]) * 1.2 / (2.0 * np.sin(np.pi / max(persons, 3))) + [0.0, 0.0, 0.9 + 0.6 * (i % 4)]
+        sway = 0.3 * np.sin(2.0 * np.pi * t / rng.uniform(35.0, 90.0, 3) + rng.uniform(0.0, 2.0 * np.pi, 3))
+        world.append(centre + rng.normal(0.0, 0.25, (J, 3)) + sway[:, None, :] + rng.normal(0.0, 0.004, (Tc, J, 3)))
+    views = []
+    for v, c in enumerate(cams):
+        start = offsets[v] - base
+        tracks = []
+        for i in range(persons):
+            p = predict.world_to_camera_host(world[i][start:start + lengths[v]], c)
+            px = np.stack([fx * p[..., 0] / p[..., 2] + cx, fy * p[..., 1] / p[..., 2] + cy], axis=-1) + rng.normal(0.0, 0.5, (lengths[v], J, 2))
+            tracks.append(px.astype(np.float32))
+        views.append(tracks)
+    return views
+
+
+def _align_rows(model, cfg, args):
+    import torch
+    from uplift_upsample_3dhpe_amd import predict
+    J, N, T, L = int(cfg.NUM_KEYPOINTS), max(args.persons, 1), args.frames, args.max_lag
+    kw = dict(resolutions=(1024, 1024))
+    params = predict.AlignViews(max_lag=L)
+    rows = []
+    for cams, persons, lengths, offsets in ((_cameras(3), N, [T - 10, T, T - 20], [0, -3, 5]), (_cameras(8), 2, [2500] * 8, [0, 3, -4, 7, -9, 12, -15, 20])):
+        views = _swaying(cams, persons, lengths, offsets, J)
+        dev = [[torch.from_numpy(t).cuda() for t in tracks] for tracks in views]
+        got = [r.cpu().numpy() for r in predict.align_views(dev, cams, max_lag=L, same_index=True)]
+        t0 = time.perf_counter()
+        want = predict.align_views_host(views, cams, max_lag=L, same_index=True)
+        mirror_ms = (time.perf_counter() - t0) * 1e3
+        same = all(np.array_equal(g.view(np.uint8), w.view(np.uint8)) for g, w in zip(got, want))
+        rows.append(dict(row="align_views", views=len(cams), tracks=persons * len(cams), frames=lengths[1], joints=J, max_lag=L,
+                         device_ms=round(_median(lambda: predict.align_views(dev, cams, max_lag=L, same_index=True)), 3),
+                         device_then_cpu_ms=round(_median(lambda: [r.cpu() for r in predict.align_views(dev, cams, max_lag=L, same_index=True)]), 3),
+                         mirror_ms_one_run=round(mirror_ms, 1), bits_equal=bool(same), offsets=[int(o) for o in want[0]],
+                         true_offsets=bool([int(o) for o in want[0]] == offsets)))
+        if len(cams) == 3:
+            cropped = predict.crop_views(views, offsets)[0]
+
+            def aligned():
+                return [torch.cat(a, 0).cpu() for a in predict.predict_views(model, cfg, views, cams, align=params, **kw)[:4]]
+
+            def precropped():
+                return [torch.cat(a, 0).cpu() for a in predict.predict_views(model, cfg, cropped, cams, **kw)]
+
+            aligned(), precropped()
+            a, b = aligned(), precropped()
+            rows.append(dict(row="predict_views(align=True)", views=3, persons=persons, frames=lengths, max_lag=L,
+                             device_ms=round(_median(aligned), 2), precropped_predict_views_ms=round(_median(precropped), 2),
+                             bits_equal=all(torch.equal(x.view(torch.uint8), y.view(torch.uint8)) for x, y in zip(a, b))))
+    return rows
+
+
 def _median(fn, n=3):
     import torch
     times = []
@@ -136,6 +204,8 @@ def main(argv=None):
     p.add_argument("--persons", type=int, default=2)
     p.add_argument("--frames", type=int, default=1000)
     p.add_argument("--match", action="store_true", help="time predict_views(match=True) and match_views instead")
+    p.add_argument("--align", action="store_true", help="time align_views and predict_views(align=True) instead")
+    p.add_argument("--max_lag", type=int, default=50, help="the largest clock offset looked for with --align, in frames")
     args = p.parse_args(argv)
     import torch
     import uplift_upsample_3dhpe_amd as pkg
@@ -146,6 +216,9 @@ def main(argv=None):
     model = pkg.build_uplift_upsample_transformer(cfg, weights=pkg.init_weights(arch, seed=2, perturb=0.1))
     if args.match:
         print(json.dumps(dict(config=args.config, rows=_match_rows(model, cfg, args))))
+        return 0
+    if args.align:
+        print(json.dumps(dict(config=args.config, rows=_align_rows(model, cfg, args))))
         return 0
     J, N = int(cfg.NUM_KEYPOINTS), args.persons
     kw = dict(resolutions=(1024, 1024))

@@ -41,6 +41,23 @@ __device__ __forceinline__ void view_ray(const float2 uv, const double* __restri
     d[2] = (c[6] * a + c[9] * b) + c[12];
 }
 
+// The per-joint expression of PAIR SUMS, shared with ONE CLOCK (uu3d_view_align.h) so that the bits cannot drift: dp, dq the two rays, o the
+// way from the first camera to the second -> whether the term counts, and e = the squared distance between the two lines.
+__device__ __forceinline__ bool view_line_term(const double dp[3], const double dq[3], const double o[3], double* e_out)
+{
+#pragma clang fp contract(off)
+    const double c0 = dp[1] * dq[2] - dp[2] * dq[1];
+    const double c1 = dp[2] * dq[0] - dp[0] * dq[2];
+    const double c2 = dp[0] * dq[1] - dp[1] * dq[0];
+    const double cc = (c0 * c0 + c1 * c1) + c2 * c2;
+    const double pp = (dp[0] * dp[0] + dp[1] * dp[1]) + dp[2] * dp[2];
+    const double qq = (dq[0] * dq[0] + dq[1] * dq[1]) + dq[2] * dq[2];
+    const double oc = (o[0] * c0 + o[1] * c1) + o[2] * c2;
+    const double e = (oc * oc) / cc;
+    *e_out = e;
+    return cc > kViewParallel * (pp * qq) && finite_double(e);
+}
+
 // Block i = the pair (p, q), p <= q, in row-major order of the upper triangle.  kp (M, T, J, 2) f32, flags (M, T, J) u8 or nullptr,
 // cams (views, 16) f64 -> sums (M, M) f64, terms (M, M) i32, both symmetric.
 static __global__ void __launch_bounds__(kMatchLanes)
@@ -83,15 +100,8 @@ view_pair_sums_kernel(const float* __restrict__ kp, const uint8_t* __restrict__ 
             double dp[3], dq[3];
             view_ray(*reinterpret_cast<const float2*>(kp + 2 * (ap + j)), cp, dp);
             view_ray(*reinterpret_cast<const float2*>(kp + 2 * (aq + j)), cq, dq);
-            const double c0 = dp[1] * dq[2] - dp[2] * dq[1];
-            const double c1 = dp[2] * dq[0] - dp[0] * dq[2];
-            const double c2 = dp[0] * dq[1] - dp[1] * dq[0];
-            const double cc = (c0 * c0 + c1 * c1) + c2 * c2;
-            const double pp = (dp[0] * dp[0] + dp[1] * dp[1]) + dp[2] * dp[2];
-            const double qq = (dq[0] * dq[0] + dq[1] * dq[1]) + dq[2] * dq[2];
-            const double oc = (o[0] * c0 + o[1] * c1) + o[2] * c2;
-            const double e = (oc * oc) / cc;
-            if (cc > kViewParallel * (pp * qq) && finite_double(e)) {
+            double e;
+            if (view_line_term(dp, dq, o, &e)) {
                 s = s + e;
                 n += 1;
             }

@@ -46,7 +46,9 @@ every name is importable from here as before:
     views.py      several calibrated cameras, one scene: ``predict_views(model, config, views, cameras)`` (uu3d_fuse_views, uu3d_solve_view_roots;
                   ``fuse_views``, ``solve_view_roots``, ``fuse_views_host``, ``solve_view_roots_host``); who is who across cameras:
                   ``predict_views(..., match=True)`` / ``match_views`` (uu3d_view_pair_sums, uu3d_group_views, uu3d_gather_view_tracks;
-                  ``view_pair_sums``, ``group_views``, ``gather_view_tracks`` and their ``_host`` mirrors, ``MatchViews``)
+                  ``view_pair_sums``, ``group_views``, ``gather_view_tracks`` and their ``_host`` mirrors, ``MatchViews``); one clock:
+                  ``predict_views(..., align=True)`` / ``align_views`` / ``crop_views`` (uu3d_view_lag_sums, uu3d_view_offsets;
+                  ``view_lag_sums``, ``view_offsets`` and their ``_host`` mirrors, ``AlignViews``)
 """
 import argparse
 import types
@@ -79,10 +81,10 @@ from .smooth import (MAX_SMOOTH_CHANNELS, TWO_PI, OneEuro, _one_euro_rates, chec
                      one_euro_sample)
 from .tracks import (_device_track, _device_tracks, _host_array, _shape, _upload, assemble_tracks, assemble_tracks_cubic,  # noqa: F401
                      check_resolutions, keyframe_count, normalize_tracks, pose_table, resample_tracks, resampled_pose_table)
-from .views import (MATCH_DEFAULTS, MATCH_LANES, MAX_MATCH_TRACKS, MAX_VIEWS, VIEW_PARALLEL, MatchViews, check_match, check_view_cameras,  # noqa: F401
-                    check_view_of, fuse_views, fuse_views_host, gather_view_tracks, gather_view_tracks_host, group_views, group_views_host,
-                    match_views, match_views_host, predict_views, solve_view_roots, solve_view_roots_host, view_pair_sums, view_pair_sums_host,
-                    view_rows)
+from .views import (ALIGN_DEFAULTS, MATCH_DEFAULTS, MATCH_LANES, MAX_ALIGN_LAG, MAX_MATCH_TRACKS, MAX_VIEWS, VIEW_PARALLEL, AlignViews,  # noqa: F401
+                    MatchViews, align_views, align_views_host, check_align, check_match, check_view_cameras, check_view_of, crop_views, fuse_views, fuse_views_host, gather_view_tracks, gather_view_tracks_host, group_views, group_views_host,
+                    match_views, match_views_host, predict_views, solve_view_roots, solve_view_roots_host, view_lag_sums, view_lag_sums_host,
+                    view_offsets, view_offsets_host, view_pair_sums, view_pair_sums_host, view_rows)
 from .validity import (_device_joint_flags, _device_valid, _front_validity, _source_joint_flags, check_repair_joints, check_valid,  # noqa: F401
                        repair_joints, repair_joints_host)
 

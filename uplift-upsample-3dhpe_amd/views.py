@@ -21,7 +21,7 @@ passes NaN coordinates (with ``valid="finite"``) or cleared flags there.
 
 Who is who -- ``predict_views(..., match=True)`` / ``match_views(views, cameras)``: every camera's tracker numbers people in the order it
 meets them, so the same index is NOT the same person.  With ``match`` the views may hold different numbers of tracks in any order (all of
-one length T, on one clock), and in front of everything above
+one length T, on one clock -- see ``align`` below for cameras that are not), and in front of everything above
   0a. uu3d_view_pair_sums measures every pair of tracks of different views: the mean squared distance between the LINES through the two
       cameras and the pixels of the same joint at the same frame, in float64 with a fixed order of summation (``view_pair_sums_host``),
   0b. uu3d_group_views groups the tracks to persons, greedily and view by view (``group_views_host``),
@@ -31,7 +31,18 @@ one length T, on one clock), and in front of everything above
 The lines are not half-lines (a meeting point behind a camera is not rejected), the grouping depends on the order of the views, and
 ``MATCH_DEFAULTS`` are conveniences for metres, not tuned values: no matching accuracy is claimed.
 
-Out of scope: time alignment, per-view confidence weights, estimating extrinsics, a live form.  No accuracy is claimed."""
+One clock -- ``predict_views(..., align=True)`` / ``align_views(views, cameras)`` / ``crop_views``: cameras started by hand are seconds
+apart, so frame f of one view is not frame f of another.  With ``align`` every view has its own length and clock, and in front of
+everything above
+  -a. uu3d_view_lag_sums sums the same squared line distance for every track of the reference view (the first non-empty one), every
+      track of a later view and every lag in -L .. L, after writing every joint's ray once (``view_lag_sums_host``),
+  -b. uu3d_view_offsets takes, per view, the lag of the smallest mean (``view_offsets_host``),
+  -c. ONE small copy (2 V int32) tells the host the offsets, and ``crop_views`` slices every view to the common time window.
+Whole frames, against the reference view only, one common frame rate; ``ALIGN_DEFAULTS`` are conveniences, not tuned values: no alignment
+accuracy is claimed.
+
+Out of scope: sub-frame offsets and per-camera frame rates, per-view confidence weights, estimating extrinsics, a live form.  No accuracy
+is claimed."""
 import ctypes as C
 
 import numpy as np
@@ -48,6 +59,8 @@ MAX_MATCH_TRACKS = 64                                                  # kMatchM
 MATCH_LANES = 256                                                      # kMatchLanes: part of the rule's order of summation
 VIEW_PARALLEL = 2.0 ** -20                                             # kViewParallel: sin^2 of 1e-3 rad -- closer rays carry no distance information
 MATCH_DEFAULTS = dict(max_dist=0.2, min_terms=50)                      # conveniences for metres, not tuned values
+MAX_ALIGN_LAG = 512                                                    # kAlignMaxLag: the largest clock offset looked for, in frames
+ALIGN_DEFAULTS = dict(max_lag=50, min_terms=50)                        # conveniences for 50 Hz and metres, not tuned values
 
 
 def check_view_cameras(cameras, views=None):
@@ -577,9 +590,10 @@ def gather_view_tracks(src, poses, kp2d, flags=None, frames=1):
     return out_p, out_k, out_f
 
 
-def _match_inputs(views, cameras, valid):
-    """The refusals of ``match_views`` that need no device -> (the cameras, tracks per view, the M tracks view-major, their ``valid``
-    entries or None / "finite", T)."""
+def _match_inputs(views, cameras, valid, word="match", one_length=True):
+    """The refusals of ``match_views`` (and, with ``word`` = "align" and tracks of any length, of ``align_views``) that need no device
+    -> (the cameras, tracks per view, the M tracks view-major, their ``valid`` entries or None / "finite", T -- the list of the tracks'
+    lengths without ``one_length``)."""
     if not isinstance(views, (list, tuple)) or not 1 <= len(views) <= MAX_VIEWS or not all(isinstance(v, (list, tuple)) for v in views):
         raise ValueError(f"views must be a list of 1 to {MAX_VIEWS} lists of tracks, one list per camera, got "
                          f"{len(views) if isinstance(views, (list, tuple)) else type(views).__name__}")
@@ -587,16 +601,19 @@ def _match_inputs(views, cameras, valid):
     counts = [len(v) for v in views]
     flat = [t for tracks in views for t in tracks]
     if not flat:
-        raise ValueError("match: at least one view must hold a track")
+        raise ValueError(f"{word}: at least one view must hold a track")
     if len(flat) > MAX_MATCH_TRACKS:
-        raise ValueError(f"match: at most {MAX_MATCH_TRACKS} tracks in all views together are matched, got {len(flat)}")
+        raise ValueError(f"{word}: at most {MAX_MATCH_TRACKS} tracks in all views together are matched, got {len(flat)}")
     shapes = [_shape(t) for t in flat]
     if any(len(s) != 3 or s[2] != 2 for s in shapes):
         raise ValueError(f"a track must be (T, K, 2), got {[tuple(s) for s in shapes if len(s) != 3 or s[2] != 2][0]}")
-    if len({int(s[0]) for s in shapes}) != 1 or int(shapes[0][0]) < 1:
+    if not one_length:
+        if any(int(s[0]) < 1 or int(s[0]) * int(s[1]) >= 2 ** 31 for s in shapes):
+            raise ValueError(f"{word}: every track needs at least one frame and T * K below 2^31, got {sorted({int(s[0]) for s in shapes})}")
+    elif len({int(s[0]) for s in shapes}) != 1 or int(shapes[0][0]) < 1:
         raise ValueError(f"match: all tracks are on one clock and need one common number of frames T >= 1, got {sorted({int(s[0]) for s in shapes})}")
     if len({int(s[1]) for s in shapes}) != 1 or not 1 <= int(shapes[0][1]) <= MAX_ROOT_JOINTS:
-        raise ValueError(f"match: all tracks need the same 1 to {MAX_ROOT_JOINTS} joints, got {sorted({int(s[1]) for s in shapes})}")
+        raise ValueError(f"{word}: all tracks need the same 1 to {MAX_ROOT_JOINTS} joints, got {sorted({int(s[1]) for s in shapes})}")
     flat_valid = valid
     if valid is not None and not isinstance(valid, str):
         if not isinstance(valid, (list, tuple)) or len(valid) != len(views) or \
@@ -605,7 +622,7 @@ def _match_inputs(views, cameras, valid):
         flat_valid = [f for per_view in valid for f in per_view]
     elif isinstance(valid, str) and valid != "finite":
         raise ValueError(f"valid must be None, \"finite\" or a list of lists, got {valid!r}")
-    return cams, counts, flat, flat_valid, int(shapes[0][0])
+    return cams, counts, flat, flat_valid, int(shapes[0][0]) if one_length else [int(s[0]) for s in shapes]
 
 
 def _joint_flags_host(flat_valid, T, K):
@@ -691,6 +708,436 @@ def match_views(views, cameras, valid=None, max_dist=MATCH_DEFAULTS["max_dist"],
     return _match_device(tr, cams, counts, flat_valid, params)
 
 
+# ---- one clock: which frame of one camera is which of another (include/uu3d.h, ONE CLOCK) ----------------------------------------------
+class AlignViews(object):
+    """The parameters of ``predict_views(align=...)`` / ``align_views``: ``max_lag`` = L, the largest clock offset looked for, in frames
+    (an int in 1 .. ``MAX_ALIGN_LAG``), and ``min_terms``, the least number of (frame, joint) terms a pair of tracks needs at a lag to
+    speak for it (an int >= 1).  The defaults are conveniences for 50 Hz and metres, not tuned values."""
+
+    def __init__(self, max_lag=ALIGN_DEFAULTS["max_lag"], min_terms=ALIGN_DEFAULTS["min_terms"]):
+        self.max_lag, self.min_terms = _align_parameters(max_lag, min_terms)
+
+    def __repr__(self):
+        return f"AlignViews(max_lag={self.max_lag!r}, min_terms={self.min_terms!r})"
+
+
+def _is_int(n):
+    return isinstance(n, (int, np.integer)) and not isinstance(n, (bool, np.bool_))
+
+
+def _align_parameters(max_lag, min_terms):
+    if not _is_int(max_lag) or not 1 <= int(max_lag) <= MAX_ALIGN_LAG:
+        raise ValueError(f"max_lag must be an int in 1 .. {MAX_ALIGN_LAG}, got {max_lag!r}")
+    if not _is_int(min_terms) or not 1 <= int(min_terms) < 2 ** 31:
+        raise ValueError(f"min_terms must be an int >= 1, got {min_terms!r}")
+    return int(max_lag), int(min_terms)
+
+
+def check_align(align):
+    """``predict_views(align=...)`` -> None (the views are on one clock), an ``AlignViews`` (True is the defaults: the offsets are
+    estimated) or a list of ints (the known offsets, one per view)."""
+    if align is None or align is False:
+        return None
+    if align is True:
+        return AlignViews()
+    if isinstance(align, AlignViews):
+        return align
+    if isinstance(align, (list, tuple, np.ndarray)) and len(align) >= 1 and all(_is_int(o) for o in align):
+        return [int(o) for o in align]
+    raise ValueError(f"align must be None, True, an AlignViews(max_lag=, min_terms=) or a list of one int offset per view, got {align!r}")
+
+
+def _reference_view(view_of, V):
+    """-> (the first non-empty view r, its number of tracks N_r, the tracks of every view)."""
+    counts = np.bincount(view_of, minlength=V)
+    r = int(np.flatnonzero(counts)[0])
+    return r, int(counts[r]), counts
+
+
+def _lag_shapes(kp_shape, flags_shape, view_of, cams_shape, frames, max_lag):
+    """The shapes of a lag-sums call, checked -> (view_of int32, V, M, J, first_row (M + 1) int64, L)."""
+    if len(kp_shape) != 3 or kp_shape[2] != 2 or not 1 <= kp_shape[1] <= MAX_ROOT_JOINTS:
+        raise ValueError(f"kp must be (rows, J, 2) with 1 <= J <= {MAX_ROOT_JOINTS}, got {tuple(kp_shape)}")
+    rows, J = int(kp_shape[0]), int(kp_shape[1])
+    view_of, V = check_view_of(view_of, cams_shape[0])
+    M = len(view_of)
+    n = np.asarray(frames)
+    if n.shape != (M,) or not np.issubdtype(n.dtype, np.integer) or (n < 1).any() or int(n.sum()) != rows:
+        raise ValueError(f"frames must hold one length >= 1 per track ({M}) that add up to kp's {rows} rows, got {n.tolist() if n.ndim == 1 else n.shape}")
+    if (n.astype(np.int64) * J >= 2 ** 31).any():
+        raise ValueError(f"T * J must stay below 2^31 for every track (the int32 terms of a pair), got {int(n.max())} * {J}")
+    L, _ = _align_parameters(max_lag, 1)
+    if flags_shape is not None and tuple(flags_shape) != (rows, J):
+        raise ValueError(f"flags must be ({rows}, {J}), got {tuple(flags_shape)}")
+    return view_of, V, M, J, np.concatenate([[0], np.cumsum(n, dtype=np.int64)]).astype(np.int64), L
+
+
+def _flat_tracks(kp, frames, flags, cat, length):
+    """``kp`` / ``flags`` as a list of M tracks or flat already -> (flat kp, frames, flat flags or None)."""
+    if isinstance(kp, (list, tuple)):
+        lens = [int(length(t)) for t in kp]
+        if frames is not None and [int(n) for n in np.asarray(frames).reshape(-1)] != lens:
+            raise ValueError(f"frames must be the lengths of the tracks given, {lens}, got {np.asarray(frames).tolist()}")
+        kp, frames = cat(list(kp)), np.asarray(lens, np.int64)
+    elif frames is None:
+        raise ValueError("frames: a flat (rows, J, 2) kp needs the length of every track")
+    if isinstance(flags, (list, tuple)):
+        flags = cat(list(flags))
+    return kp, np.asarray(frames), flags
+
+
+def view_lag_sums_host(kp, view_of, cameras, frames=None, max_lag=ALIGN_DEFAULTS["max_lag"], flags=None):
+    """The lag sums of ONE CLOCK (include/uu3d.h) in numpy, written to be read: what uu3d_view_lag_sums computes, bit for bit.
+    ``kp``: a list of M tracks (T_m, J, 2) or their rows back to back, (rows, J, 2), view-major, in the detector's own joints, undistorted
+    (read as float32); ``view_of`` (M,) ascending; ``cameras``: V ``Camera`` objects with extrinsics (or their ``view_rows``); ``frames``
+    (M,): every track's length (None with a list); ``max_lag`` = L; ``flags``: None, (rows, J) or a list of (T_m, J), non-zero = observed
+    -> (sums (N_r, M, 2 L + 1) float64, terms (N_r, M, 2 L + 1) int32), N_r the tracks of the reference view = the first non-empty view.
+    Every track starts at frame 0 of its camera's clock; view v's frame f was taken at common time f + o_v.  For track p of the reference
+    view, track q of a later view w and lag l in -L .. L (l stands for o_w - o_r), frame f of p pairs with frame g = f - l of q.  Per
+    paired frame and per joint used in both, the term is e of ``view_pair_sums_host``: the rays, c, cc, oc, the ``VIEW_PARALLEL`` test,
+    the finite test, no terms for coincident cameras.  The order is that of ``view_pair_sums_host`` over p's frames: s_f over the counted
+    joints ascending; a frame without a partner (g < 0 or g >= q's length) has s_f = 0.0 and no terms; lane i of ``MATCH_LANES`` sums s_f
+    for f = i, i + 256, ... from 0.0; then the fixed tree.  Lag l is index l + L; the columns q of the reference view hold 0.0 and 0.
+    For two tracks of equal length the slice at l = 0 is ``view_pair_sums_host``'s element, bit for bit."""
+    kp, frames, flags = _flat_tracks(kp, frames, flags, lambda a: np.concatenate([np.asarray(_host_array(t)) for t in a]), lambda t: _shape(t)[0])
+    uv = np.asarray(_host_array(kp), np.float32)
+    cam = _camera_rows(cameras)
+    f = None if flags is None else np.asarray(_host_array(flags)) != 0
+    view_of, V, M, J, first, L = _lag_shapes(uv.shape, None if f is None else f.shape, view_of, cam.shape, frames, max_lag)
+    r, n_ref, _ = _reference_view(view_of, V)
+    used = np.isfinite(uv).all(axis=2)
+    if f is not None:
+        used &= f
+    sums, terms = np.zeros((n_ref, M, 2 * L + 1), np.float64), np.zeros((n_ref, M, 2 * L + 1), np.int32)
+    uv64 = uv.astype(np.float64)
+    with np.errstate(all="ignore"):
+        rays = np.empty(uv.shape[:2] + (3,), np.float64)                 # every joint's ray, once
+        for m in range(M):
+            rows = slice(first[m], first[m + 1])
+            fx, fy, cx, cy = cam[view_of[m], :4]
+            r1, r2, r3 = cam[view_of[m], 4:7], cam[view_of[m], 7:10], cam[view_of[m], 10:13]
+            a = (uv64[rows, :, 0] - cx) / fx
+            b = (uv64[rows, :, 1] - cy) / fy
+            for i in range(3):
+                rays[rows, :, i] = (r1[i] * a + r2[i] * b) + r3[i]
+        for p in range(n_ref):
+            Tp = int(first[p + 1] - first[p])
+            for q in range(n_ref, M):
+                Tq = int(first[q + 1] - first[q])
+                o = cam[view_of[q], 13:16] - cam[r, 13:16]
+                oo = (o[0] * o[0] + o[1] * o[1]) + o[2] * o[2]
+                if not np.isfinite(oo) or not oo > 0:
+                    continue
+                for l in range(-L, L + 1):
+                    s, n = np.zeros(Tp, np.float64), 0
+                    f0, f1 = max(0, l), min(Tp, Tq + l)                  # the frames f of p with a partner g = f - l in 0 .. Tq - 1
+                    if f1 > f0:
+                        at_p, at_q = slice(first[p] + f0, first[p] + f1), slice(first[q] + f0 - l, first[q] + f1 - l)
+                        dp, dq = rays[at_p], rays[at_q]                  # (frames, J, 3)
+                        c0 = dp[..., 1] * dq[..., 2] - dp[..., 2] * dq[..., 1]
+                        c1 = dp[..., 2] * dq[..., 0] - dp[..., 0] * dq[..., 2]
+                        c2 = dp[..., 0] * dq[..., 1] - dp[..., 1] * dq[..., 0]
+                        cc = (c0 * c0 + c1 * c1) + c2 * c2
+                        pp = (dp[..., 0] * dp[..., 0] + dp[..., 1] * dp[..., 1]) + dp[..., 2] * dp[..., 2]
+                        qq = (dq[..., 0] * dq[..., 0] + dq[..., 1] * dq[..., 1]) + dq[..., 2] * dq[..., 2]
+                        oc = (o[0] * c0 + o[1] * c1) + o[2] * c2
+                        e = (oc * oc) / cc
+                        counts = used[at_p] & used[at_q] & (cc > VIEW_PARALLEL * (pp * qq)) & np.isfinite(e)
+                        part = np.zeros(f1 - f0, np.float64)
+                        for j in range(J):                               # the counted joints in ascending order
+                            part = np.where(counts[:, j], part + e[:, j], part)
+                        s[f0:f1] = part
+                        n = int(counts.sum())
+                    x = np.zeros(MATCH_LANES, np.float64)                # lane i: frames i, i + 256, ... in ascending order
+                    for start in range(0, Tp, MATCH_LANES):
+                        part = s[start:start + MATCH_LANES]
+                        x[:len(part)] = x[:len(part)] + part
+                    stride = MATCH_LANES // 2
+                    while stride >= 1:                                   # the fixed tree
+                        x[:stride] = x[:stride] + x[stride:2 * stride]
+                        stride //= 2
+                    sums[p, q, l + L] = x[0]
+                    terms[p, q, l + L] = n
+    return sums, terms
+
+
+def _offset_shapes(sums_shape, terms_shape, view_of, views, max_lag, min_terms, same_index):
+    """The shapes of an offsets call, checked -> (view_of int32, V, M, r, N_r, tracks per view, L, min_terms)."""
+    view_of, V = check_view_of(view_of, views)
+    M = len(view_of)
+    L, min_terms = _align_parameters(max_lag, min_terms)
+    r, n_ref, counts = _reference_view(view_of, V)
+    want = (n_ref, M, 2 * L + 1)
+    if tuple(sums_shape) != want or tuple(terms_shape) != want:
+        raise ValueError(f"sums and terms must be {want} beside view_of and max_lag, got {tuple(sums_shape)} and {tuple(terms_shape)}")
+    if same_index and any(n not in (0, n_ref) for n in counts):
+        raise ValueError(f"same_index needs the same number of tracks in every non-empty view, got {[int(n) for n in counts]}")
+    return view_of, V, M, r, n_ref, counts, L, min_terms
+
+
+def _lag_before(a, la, b, lb):
+    """(score a, lag la) before (score b, lag lb): the smaller score, then the smaller |l|, then the smaller l."""
+    if a < b:
+        return True
+    if not a == b:
+        return False
+    return abs(la) < abs(lb) or (abs(la) == abs(lb) and la < lb)
+
+
+def view_offsets_host(sums, terms, view_of, views=None, max_lag=ALIGN_DEFAULTS["max_lag"], min_terms=ALIGN_DEFAULTS["min_terms"], same_index=False):
+    """The offsets of ONE CLOCK (include/uu3d.h) in plain Python, written to be read: what uu3d_view_offsets computes, bit for bit.
+    ``sums`` (N_r, M, 2 L + 1) float64 and ``terms`` int32 of ``view_lag_sums_host``; ``view_of`` (M,) ascending; ``views`` = V (None: the
+    last entry of ``view_of`` + 1) -> (offset (V,) int32, state (V,) int32, score (V,) float64).
+    For each later non-empty view w and each lag: S = 0.0, n = 0; for each reference track p ascending, the candidates are the tracks q
+    of w with terms >= ``min_terms`` -- with ``same_index`` only the track with p's index inside its view (every non-empty view then needs
+    N_r tracks) --; the candidate of smallest sums / float(terms) is taken, ties to the smaller q, and S = S + sums, n = n + terms.  The
+    lag is ALLOWED iff some p had a candidate; its score is S / float(n).  The view takes the allowed lag of smallest score, ties to the
+    smaller |l|, then the smaller l: offset l, state 1 and the score.  A view without an allowed lag: offset 0, state 0, score 0.0; the
+    reference view and empty views: offset 0, state 1, score 0.0.  Alignment is against the reference view only; periodic or standing
+    motion is ambiguous, and the ties then go to the smallest shift."""
+    S_, N_ = np.asarray(_host_array(sums), np.float64), np.asarray(_host_array(terms), np.int32)
+    view_of, V, M, r, n_ref, counts, L, min_terms = _offset_shapes(S_.shape, N_.shape, view_of, views, max_lag, min_terms, same_index)
+    starts = np.concatenate([[0], np.cumsum(counts)])
+    offset, state, score = np.zeros(V, np.int32), np.ones(V, np.int32), np.zeros(V, np.float64)
+    with np.errstate(all="ignore"):
+        for w in range(V):
+            lo, nb = int(starts[w]), int(counts[w])
+            if w == r or nb == 0:
+                continue
+            best = None
+            for l in range(-L, L + 1):
+                S, n, allowed = np.float64(0.0), 0, False
+                for p in range(n_ref):
+                    bq, bm = -1, None
+                    for q in ([lo + p] if same_index else range(lo, lo + nb)):
+                        t = int(N_[p, q, l + L])
+                        if t < min_terms:
+                            continue
+                        mean = S_[p, q, l + L] / np.float64(t)
+                        if bq < 0 or mean < bm:                          # strict: ties go to the smaller q
+                            bq, bm = q, mean
+                    if bq < 0:
+                        continue
+                    S, n, allowed = S + S_[p, bq, l + L], n + int(N_[p, bq, l + L]), True
+                if allowed and (best is None or _lag_before(S / np.float64(n), l, best[0], best[1])):
+                    best = (S / np.float64(n), l)
+            if best is None:
+                state[w] = 0
+            else:
+                score[w], offset[w] = best
+    return offset, state, score
+
+
+def view_lag_sums(kp, view_of, cameras, frames=None, max_lag=ALIGN_DEFAULTS["max_lag"], flags=None):
+    """uu3d_view_lag_sums on the current stream: ``view_lag_sums_host`` on device tensors, two launches (every joint's ray once, then one
+    workgroup per (p, q, lag)), nothing copies to the host or waits (the camera rows go up pinned and asynchronously; ``view_of`` and
+    ``frames`` are host arrays).  ``kp``: a list of M contiguous (T_m, J, 2) float32 device tensors (joined by one ``torch.cat``) or their
+    rows back to back, (rows, J, 2) (only read); ``flags``: None, (rows, J) uint8 / bool on the device or a list of (T_m, J)
+    -> (sums (N_r, M, 2 L + 1) float64, terms (N_r, M, 2 L + 1) int32), fresh device buffers.  Needs no model."""
+    import torch
+    lib = _capi.load_library()
+    kp, frames, flags = _flat_tracks(kp, frames, flags, lambda a: torch.cat(a, 0), lambda t: t.shape[0])
+    if not _is_device(kp, torch.float32):
+        raise ValueError(f"kp must be contiguous float32 device tensors, (rows, J, 2) in all, got {tuple(getattr(kp, 'shape', ()))}")
+    if flags is not None and not _is_device(flags, (torch.uint8, torch.bool), kp.device):
+        raise ValueError("flags must be a contiguous (rows, J) uint8 or bool tensor on kp's device")
+    rows = _camera_rows(cameras)
+    view_of, V, M, J, first, L = _lag_shapes(tuple(kp.shape), None if flags is None else tuple(flags.shape), view_of, rows.shape, frames, max_lag)
+    _, n_ref, _ = _reference_view(view_of, V)
+    dev = kp.device
+    cams = _upload(rows, np.float64, dev)
+    scratch = torch.empty((int(lib.uu3d_view_lag_scratch_bytes(int(first[-1]), J)),), dtype=torch.uint8, device=dev)
+    sums = torch.empty((n_ref, M, 2 * L + 1), dtype=torch.float64, device=dev)
+    terms = torch.empty((n_ref, M, 2 * L + 1), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _capi.check(lib, lib.uu3d_view_lag_sums(_ptr(kp), _ptr(None if flags is None else flags.view(torch.uint8)),
+                                                view_of.ctypes.data_as(C.POINTER(C.c_int32)), first.ctypes.data_as(C.POINTER(C.c_int64)), M, J, V,
+                                                _ptr(cams), L, _ptr(scratch), _ptr(sums), _ptr(terms), C.c_void_p(stream)), None)
+    return sums, terms
+
+
+def view_offsets(sums, terms, view_of, views=None, max_lag=ALIGN_DEFAULTS["max_lag"], min_terms=ALIGN_DEFAULTS["min_terms"], same_index=False):
+    """uu3d_view_offsets on the current stream: ``view_offsets_host`` on device tensors, one launch of one wave, nothing copies to the
+    host or waits.  ``sums`` (N_r, M, 2 L + 1) float64 and ``terms`` int32 on the device, contiguous (only read)
+    -> (offset (V,) int32, state (V,) int32, score (V,) float64), fresh device buffers.  Needs no model."""
+    import torch
+    lib = _capi.load_library()
+    if not _is_device(sums, torch.float64) or not _is_device(terms, torch.int32, sums.device):
+        raise ValueError("sums must be a contiguous (N_r, M, 2 L + 1) float64 device tensor and terms an int32 one on its device")
+    view_of, V, M, _, _, _, L, min_terms = _offset_shapes(tuple(sums.shape), tuple(terms.shape), view_of, views, max_lag, min_terms, same_index)
+    dev = sums.device
+    offset = torch.empty((V,), dtype=torch.int32, device=dev)
+    state = torch.empty((V,), dtype=torch.int32, device=dev)
+    score = torch.empty((V,), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _capi.check(lib, lib.uu3d_view_offsets(_ptr(sums), _ptr(terms), view_of.ctypes.data_as(C.POINTER(C.c_int32)), M, V, L, min_terms,
+                                               1 if same_index else 0, _ptr(offset), _ptr(state), _ptr(score), C.c_void_p(stream)), None)
+    return offset, state, score
+
+
+def _joint_flags_rows(flat_valid, frames, K):
+    """Per-track ``valid`` entries, (T_m,) or (T_m, K) -> (rows, K) uint8, or None without a list (the finite test alone)."""
+    if flat_valid is None or isinstance(flat_valid, str):
+        return None
+    return np.concatenate([_joint_flags_host([f], T, K)[0] for f, T in zip(flat_valid, frames)])
+
+
+def align_views_host(views, cameras, valid=None, max_lag=ALIGN_DEFAULTS["max_lag"], min_terms=ALIGN_DEFAULTS["min_terms"], same_index=False):
+    """``align_views`` built from the mirrors -- ``undistort_points_host``, ``view_lag_sums_host``, ``view_offsets_host`` -- on host arrays
+    -> (offset (V,) int32, state (V,) int32, score (V,) float64, sums (N_r, M, 2 L + 1) float64, terms int32)."""
+    from .camera import undistort_points_host
+    params = AlignViews(max_lag, min_terms)
+    cams, counts, flat, flat_valid, frames = _match_inputs(views, cameras, valid, "align", False)
+    view_of = np.repeat(np.arange(len(cams), dtype=np.int32), counts)
+    _same_index_counts(counts, same_index)
+    flat = [undistort_points_host(np.asarray(_host_array(t), np.float32), cams[v]) if cams[v].has_distortion else np.asarray(_host_array(t), np.float32)
+            for t, v in zip(flat, view_of)]
+    sums, terms = view_lag_sums_host(flat, view_of, cams, frames, params.max_lag, _joint_flags_rows(flat_valid, frames, flat[0].shape[1]))
+    return view_offsets_host(sums, terms, view_of, len(cams), params.max_lag, params.min_terms, same_index) + (sums, terms)
+
+
+def _align_device(tr, cams, counts, flat_valid, params, same_index):
+    """The launches of ``align_views`` on undistorted device tracks -> (offset, state, score, sums, terms)."""
+    import torch
+    dev = tr[0].device
+    frames = [int(t.shape[0]) for t in tr]
+    K = int(tr[0].shape[1])
+    kp = torch.cat(tr, 0).contiguous() if len(tr) > 1 else tr[0].contiguous()
+    flags = None
+    if flat_valid is not None and not isinstance(flat_valid, str):
+        if all(isinstance(f, torch.Tensor) for f in flat_valid):
+            per = []
+            for f, T in zip(flat_valid, frames):
+                if tuple(f.shape) not in ((T,), (T, K)):
+                    raise ValueError(f"an entry of valid must be ({T},) or ({T}, {K}), got {tuple(f.shape)}")
+                f = (f.to(dev) != 0).to(torch.uint8)
+                per.append(f[:, None].expand(T, K) if f.dim() == 1 else f)
+            flags = torch.cat(per, 0).contiguous()
+        else:
+            flags = _upload(_joint_flags_rows(flat_valid, frames, K), np.uint8, dev)
+    view_of = np.repeat(np.arange(len(cams), dtype=np.int32), counts)
+    sums, terms = view_lag_sums(kp, view_of, cams, frames, params.max_lag, flags)
+    return view_offsets(sums, terms, view_of, len(cams), params.max_lag, params.min_terms, same_index) + (sums, terms)
+
+
+def _same_index_counts(counts, same_index):
+    if same_index and len({n for n in counts if n > 0}) > 1:
+        raise ValueError(f"same_index needs the same number of tracks in every non-empty view, got {[int(n) for n in counts]}")
+
+
+def align_views(views, cameras, valid=None, max_lag=ALIGN_DEFAULTS["max_lag"], min_terms=ALIGN_DEFAULTS["min_terms"], same_index=False, device=None):
+    """Every camera's clock offset against the first non-empty view, on the device: ``views[v]`` is a list of N_v tracks (T, K, 2), each
+    with its own length and starting at frame 0 of its camera's clock -- any number per view, an empty view included, on the host or the
+    device --, ``cameras`` V ``Camera`` objects with extrinsics, ``valid`` as ``match_views`` takes it.  The tracks of cameras with
+    distortion are undistorted (uu3d_undistort_points), then uu3d_view_lag_sums and uu3d_view_offsets run
+    -> (offset (V,) int32: view v's frame f was taken at common time f + offset[v], state (V,) int32: 0 = no lag of this view had
+    ``min_terms`` terms with the reference view, score (V,) float64: the mean squared distance between the lines at the lag taken, sums
+    (N_r, M, 2 max_lag + 1) float64, terms int32) on the device; nothing copies to the host or waits.  ``same_index=True``: track i of a
+    view is person i of every view (the views then hold the same number of tracks); False: every reference track takes, per lag, its
+    best partner in the view (a reference track whose person the view does not hold takes a stranger, which can spoil that view's score).
+    The rules stand in ``view_lag_sums_host`` and ``view_offsets_host``; ``align_views_host`` is the same call
+    on the host, and the two agree bit for bit.  ``max_lag`` and ``min_terms`` default to ``ALIGN_DEFAULTS``: conveniences for 50 Hz
+    and metres, not tuned values.  Whole frames against the reference view only; no accuracy is claimed.  Needs no model."""
+    import torch
+    params = AlignViews(max_lag, min_terms)
+    cams, counts, flat, flat_valid, _ = _match_inputs(views, cameras, valid, "align", False)
+    _same_index_counts(counts, same_index)
+    if device is None:
+        on = [t.device for t in flat if isinstance(t, torch.Tensor) and t.is_cuda]
+        device = on[0] if on else torch.device("cuda", torch.cuda.current_device())
+    tr, _ = _undistorted_tracks(flat, cams, counts, torch.device(device))
+    return _align_device(tr, cams, counts, flat_valid, params, same_index)
+
+
+def _view_lengths(views):
+    """The one length T_v of every view's tracks, None for an empty view; a view whose tracks differ in length is a ValueError."""
+    if not isinstance(views, (list, tuple)) or not 1 <= len(views) <= MAX_VIEWS or not all(isinstance(v, (list, tuple)) for v in views):
+        raise ValueError(f"views must be a list of 1 to {MAX_VIEWS} lists of tracks, one list per camera, got "
+                         f"{len(views) if isinstance(views, (list, tuple)) else type(views).__name__}")
+    lengths = []
+    for v, tracks in enumerate(views):
+        here = [int(_shape(t)[0]) if len(_shape(t)) else -1 for t in tracks]
+        if len(set(here)) > 1 or (here and here[0] < 1):
+            raise ValueError(f"align: every track of a view needs the same number of frames T_v >= 1 (they share the camera's clock): view {v} has {here}")
+        lengths.append(here[0] if here else None)
+    return lengths
+
+
+def crop_views(views, offsets, valid=None):
+    """The common time window of V views with known clock offsets, on the host and without a copy (slices): ``views[v]``: a list of
+    tracks (T_v, K, 2), all of view v's of one length, on the host or the device; ``offsets``: V ints, view v's frame f was taken at
+    common time f + offsets[v]; ``valid``: None, "finite" or a list of V lists of per-track entries, arrays of T_v rows (anything else in
+    an entry passes through) -> (the cropped views, the cropped ``valid``, first: V ints).  Over the non-empty views lo = max o_v and
+    hi = min (T_v + o_v); view v keeps its frames lo - o_v .. hi - o_v - 1, and first[v] = lo - o_v (0 for an empty view).  A window of
+    less than one frame (hi - lo < 1) is a ValueError."""
+    lengths = _view_lengths(views)
+    V = len(views)
+    if not isinstance(offsets, (list, tuple, np.ndarray)) or len(offsets) != V or not all(_is_int(o) for o in offsets):
+        raise ValueError(f"offsets must hold one int per view ({V}), got {offsets!r}")
+    live = [v for v in range(V) if lengths[v] is not None]
+    if not live:
+        raise ValueError("align: at least one view must hold a track")
+    lo, hi = max(int(offsets[v]) for v in live), min(lengths[v] + int(offsets[v]) for v in live)
+    if hi - lo < 1:
+        raise ValueError(f"align: the views share no frame: offsets {[int(o) for o in offsets]} and lengths {lengths} leave a window of {hi - lo} frames")
+    first = [lo - int(offsets[v]) if lengths[v] is not None else 0 for v in range(V)]
+    cropped = [[t[first[v]:first[v] + hi - lo] for t in views[v]] for v in range(V)]
+    if valid is None or isinstance(valid, str):
+        return cropped, valid, first
+    if not isinstance(valid, (list, tuple)) or len(valid) != V or not all(isinstance(f, (list, tuple)) and len(f) == len(t) for f, t in zip(valid, views)):
+        raise ValueError(f"valid must be None, \"finite\" or a list of {V} lists, one per view, of {[len(t) for t in views]} entries")
+    kept = []
+    for v in range(V):
+        row = []
+        for f in valid[v]:
+            if f is None or isinstance(f, str):
+                row.append(f)
+                continue
+            if not len(_shape(f)) or int(_shape(f)[0]) != lengths[v]:
+                raise ValueError(f"an entry of valid must have one row per frame of its track ({lengths[v]}), got {tuple(_shape(f))}")
+            row.append(f[first[v]:first[v] + hi - lo])
+        kept.append(row)
+    return cropped, kept, first
+
+
+def _predict_aligned_views(align, match, model, views, cameras, valid, fps, keyframes_only, out_fps, call):
+    """``predict_views(align=...)``: the steps of its docstring, "One clock"; ``call(views, valid)`` is the call without ``align``."""
+    import torch
+    if keyframes_only:
+        raise ValueError("predict_views does not take keyframes_only: the fusion needs one returned frame per given frame of every view")
+    if out_fps is not None:
+        raise ValueError("predict_views does not take out_fps: the fusion needs one returned frame per given frame of every view")
+    lengths = _view_lengths(views)
+    V = len(views)
+    check_view_cameras(cameras, V)
+    if isinstance(fps, (list, tuple, np.ndarray)):
+        raise ValueError("predict_views(align=...) takes one fps for all tracks, not a list: the offsets are frames of one common rate")
+    counts = [len(v) for v in views]
+    if match is None and (counts[0] < 1 or any(n != counts[0] for n in counts)):
+        raise ValueError(f"every view must hold the same persons, at least one: got {counts} tracks per view")
+    if isinstance(align, AlignViews):
+        cams, counts, flat, flat_valid, _ = _match_inputs(views, cameras, valid, "align", False)
+        shortest = min(n for n in lengths if n is not None)
+        if align.max_lag >= 2 * shortest:
+            raise ValueError(f"align: max_lag must stay below twice the shortest view's frames ({shortest}), got {align.max_lag}")
+        tr, _ = _undistorted_tracks(flat, cams, counts, torch.device(model.device))
+        offset, state, _, _, _ = _align_device(tr, cams, counts, flat_valid, align, match is None)
+        back = torch.stack([offset, state]).cpu().numpy()                # the ONE copy: the window's length shapes every buffer behind it
+        lost = [v for v in range(V) if back[1, v] == 0]
+        if lost:
+            raise ValueError(f"align: view {lost[0]} shares no lag of at least {align.min_terms} terms with the reference view and cannot be "
+                             f"aligned (views without an offset: {lost})")
+        offsets = [int(o) for o in back[0]]
+    else:
+        if len(align) != V:
+            raise ValueError(f"align: one offset per view ({V}) is needed, got {len(align)}")
+        offsets = list(align)
+    cropped, kept, first = crop_views(views, offsets, valid)
+    return tuple(call(cropped, kept)) + (offsets, first)
+
+
 def _check_views(views, cameras, valid, keyframes_only, out_fps):
     """The refusals of ``predict_views`` that need no device -> (the cameras, V, N, frames per person)."""
     if keyframes_only:
@@ -751,7 +1198,8 @@ def _fused_scene(pt, person, world, kp2d, flags, cams, lens, rates, model_fps, r
 
 def predict_views(model, config, views, cameras, resolutions=None, mask_stride=None, flip=None, reuse_frames=True, batch_size=None, depth=None,
                   graph=True, valid=None, fps=None, model_fps=50, repair_joints=None, keypoints=None, min_root_joints=DEFAULT_MIN_ROOT_JOINTS,
-                  smooth=None, bones=None, rotations=None, interpolation="linear", return_views=False, keyframes_only=False, out_fps=None, match=None):
+                  smooth=None, bones=None, rotations=None, interpolation="linear", return_views=False, keyframes_only=False, out_fps=None, match=None,
+                  align=None):
     """One world scene from V calibrated views of the same N persons -> (poses, roots, root_state, view_count): per person ``poses``
     (T_i, J, 3) float32 in world axes and root-relative, ``roots`` (T_i, 3) float32 in world coordinates, ``root_state`` (T_i,) uint8 (1
     solved here, 2 interpolated or held, 0 no solved frame) and ``view_count`` (T_i,) uint8, the views that saw the frame; on the model's
@@ -760,7 +1208,7 @@ def predict_views(model, config, views, cameras, resolutions=None, mask_stride=N
 
     ``views``: a list of V lists, 1 <= V <= 8; ``views[v][i]`` is person i's 2D track in camera v, (T_i, J, 2), or (T_i, K_in, 2) with
     ``keypoints``.  The same index is the same person, frames are time-synchronised and person i has the same T_i in every view (anything
-    else: ValueError, unless ``match`` finds who is who across cameras, below; aligning clocks is out of scope).  A view that does not see the person at a
+    else: ValueError, unless ``match`` finds who is who across cameras and ``align`` the cameras' clock offsets, below).  A view that does not see the person at a
     frame passes NaN coordinates there (with ``valid="finite"``) or cleared flags.  ``cameras``: V ``Camera`` objects, all with
     extrinsics, each with or without distortion, one per view and shared by its persons.  ``resolutions``: None, one (w, h) or one per
     view.  ``valid``: as in ``predict_tracks``, per view -- None, "finite" or a list of V lists.  ``fps``: one rate, or one per person.
@@ -786,10 +1234,34 @@ def predict_views(model, config, views, cameras, resolutions=None, mask_stride=N
     N_v T), uu3d_gather_view_tracks lays them out per person, and the fusion, ``bones``, the root solve, the trajectory, ``smooth`` and
     ``rotations`` run unchanged on P persons.  -> today's tuple with P persons, followed by ``person``: per view a list of N_v ints, the
     person of each given track.  A person seen by one camera comes out with ``view_count`` <= 1 and the monocular root.  The result
-    equals, bit for bit, the host composition with ``match_views_host`` and ``gather_view_tracks_host`` in front of the fusion."""
+    equals, bit for bit, the host composition with ``match_views_host`` and ``gather_view_tracks_host`` in front of the fusion.
+
+    One clock -- ``align``: None = the call above, the same launches, buffers, refusals and bits.  With ``align`` every track of view v
+    has one length T_v and starts at frame 0 of camera v's clock; the views may differ in length (this replaces "the same T in every
+    view" for this call only), and view v's frame f was taken at common time f + o_v.  A list of V ints gives the offsets o_v as known:
+    no device work and no copy, only the crop.  True (``ALIGN_DEFAULTS``) or an ``AlignViews(max_lag=, min_terms=)`` estimates them: the
+    tracks are undistorted, uu3d_view_lag_sums and uu3d_view_offsets run on the detector's joints (``align_views``; with ``match`` None
+    the same index is the same person, ``same_index=True``; with ``match`` every reference track takes its best partner per lag), and
+    ``offset`` and ``state``, 2 V int32, are copied to the host -- ONE small copy, which waits for the launches: the window's length
+    shapes every buffer behind it.  A view that cannot be aligned (state 0) is a ValueError that names it.  ``crop_views`` then cuts the
+    views, and the entries of ``valid`` given as arrays, to the common window by slicing, and the call proceeds as above on the cropped
+    tracks, through the ``match`` path or the plain one (the cropped tracks of a camera with distortion are undistorted there once more:
+    per point, the same bits) -> that call's tuple followed by ``offsets`` and ``first``, two lists of V ints: the clock offsets, and
+    the given frame of every view that became frame 0.  Refused with ``align``: ``fps`` as a per-person list, a view whose tracks differ
+    in length, ``max_lag`` of twice the shortest view's frames or more; ``keyframes_only`` and ``out_fps`` stay refused in their words.
+    The result minus its last two items equals, bit for bit, ``predict_views(*crop_views(views, offsets, valid)[:2], align=None)``.
+    Whole frames against the first non-empty view only: no sub-frame refinement, no per-camera frame rates, no chaining through a third
+    camera; periodic or standing motion is ambiguous.  No alignment accuracy is claimed."""
     import torch
     from . import predict as pt
     match = check_match(match)
+    align = check_align(align)
+    if align is not None:
+        def call(cropped, kept):
+            return predict_views(model, config, cropped, cameras, resolutions, mask_stride, flip, reuse_frames, batch_size, depth, graph, kept, fps,
+                                 model_fps, repair_joints, keypoints, min_root_joints, smooth, bones, rotations, interpolation, return_views,
+                                 keyframes_only, out_fps, match, None)
+        return _predict_aligned_views(align, match, model, views, cameras, valid, fps, keyframes_only, out_fps, call)
     if match is not None:
         return _predict_matched_views(pt, match, model, config, views, cameras, resolutions, mask_stride, flip, reuse_frames, batch_size, depth, graph,
                                       valid, fps, model_fps, repair_joints, keypoints, min_root_joints, smooth, bones, rotations, interpolation,
