@@ -871,6 +871,60 @@ int uu3d_view_offsets(const double* sums_dev, const int32_t* terms_dev, const in
                       void* stream);
 
 /*
+ * WHERE RAYS MEET (predict.triangulate_joints, predict.place_joints, predict.predict_views(triangulate=...)): the fused pose of SEVERAL
+ * VIEWS is a mean of V monocular lifts, and only the root is solved from the rays of all cameras; the network's scale and depth errors,
+ * which all views share, stay in the pose.  Where two or more cameras see the same joint, its world position is fixed by geometry alone.
+ * The two calls here place such joints there and leave every other joint -- one camera saw it, the frame's root joint cannot be
+ * triangulated, only one camera saw the person -- to the fused lift: a hybrid pose, behind which bones, the root solve, the trajectory,
+ * the filters and the rotations run unchanged.  predict.triangulate_joints_host and predict.place_joints_host are the same rules in
+ * numpy, bit for bit.  In float64 on the float32 inputs, every operation rounded once, no fused multiply-add.  The camera rows
+ * cameras_dev (views, 16) f64, USED and SEES are those of SEVERAL VIEWS; sees_dev (views, rows) u8 is the output of uu3d_fuse_views.
+ * TRIANGULATION.  Per frame f and joint j the candidate set C holds the views v with sees[v][f] set and joint j USED in v.  A round:
+ *   |C| < min_views: the joint is not triangulated.
+ *   PASS 1, over v in C ascending, with q_v = 1.0:
+ *     a = (u - cx) / fx;  b = (v - cy) / fy;  n_i = (r1_i - a r3_i) q_v;  m_i = (r2_i - b r3_i) q_v
+ *     e = (n0 t0 + n1 t1) + n2 t2;  g = (m0 t0 + m1 t1) + m2 t2
+ *     A_ik += (n_i n_k + m_i m_k) for ik = 00, 01, 02, 11, 12, 22;  B_i += (n_i e + m_i g)
+ *   -- the normal equations of n . (X - t) = 0 and m . (X - t) = 0: the joint lies on the line of its pixel --, solved by the cofactor
+ *   statements of SEVERAL VIEWS, term for term: c00 .. c22, det, x_i, X_i = x_i / det.  The solve is ACCEPTED iff det is finite and > 0,
+ *   det > 2^-20 * ((A00 A11) A22) -- the 2^-20 of PAIR SUMS with its meaning: rays closer than about 1e-3 rad carry no distance
+ *   information (two coincident cameras give rounding noise; cameras on a ring 0.037 or more with three views, 0.49 with two) -- and X
+ *   is finite.  With w = X - t, z_v = (r3_0 w0 + r3_1 w1) + r3_2 w2; a z_v that is not > 0 or a solve that is not accepted: the joint is
+ *   not triangulated (no view is dropped for it).
+ *   PASS 2: the same statements with q_v = 1.0 / z_v, which turns the depth-weighted algebraic error into one in normalised image units;
+ *   the same guards, z_v recomputed from the new X.
+ *   RESIDUAL, per view of C: xc = (r1_0 w0 + r1_1 w1) + r1_2 w2, yc likewise with r2; du = |(fx (xc / z_v) + cx) - u|, dv likewise;
+ *   rho_v = max(du, dv), +infinity when either is NaN.
+ *   Every rho_v <= max_residual: the joint is triangulated, X and count = |C|.  Otherwise the view of the largest rho_v leaves C (ties:
+ *   the larger view index) and another round runs.
+ * A joint that is not triangulated gets X = zeros and count = 0.  At most views - min_views + 1 rounds, exactly two passes per round, no
+ * early exit (the spirit of Camera.ITERATIONS).
+ * PLACEMENT.  With r the root joint, for every frame f and joint j: count[f][r] > 0 and count[f][j] > 0: the pose is (float)(X_j - X_r)
+ * per channel, +0.0 for j == r, and joint_views[f][j] = count[f][j].  Otherwise the joint keeps the fused pose's bits (NaN included) and
+ * joint_views[f][j] = 0.
+ * LIMITS.  With exactly two views an error along the epipolar line cannot be seen; with three views and an outlier the honest view can
+ * be the one dropped, and the remaining two agree on a wrong point.  The lines are lines, apart from the z > 0 test.  A kept lifted joint
+ * stays relative to the root, not to its triangulated parent, so bones across the seam can stretch (bones= runs behind the stage and
+ * fixes lengths).  A frame without a triangulated root joint stays lifted as a whole.  max_residual is in pixels of the tracks as given;
+ * the defaults of predict.Triangulate are conveniences, not tuned values.  No accuracy is claimed.
+ *
+ *   uu3d_triangulate_joints(kp2d_dev (views, rows, J, 2) f32, 8-byte aligned, joint_flags_dev (views, rows, J) u8 or NULL, sees_dev,
+ *       views, rows, J, cameras_dev, min_views, max_residual, points_dev (rows, J, 3) f64, count_dev (rows, J) u8, stream): one launch, one
+ *       lane per (frame, joint) in blocks of 256.  The views are walked through a bitmask; a view's weight is recomputed from pass 1's X.
+ *   uu3d_place_joints(fused_dev (rows, J, 3) f32, points_dev, count_dev, rows, J, root, placed_dev (rows, J, 3) f32 -- not fused_dev --,
+ *       joint_views_dev (rows, J) u8, stream): one launch, one lane per (frame, joint), one 12-byte store and one byte.
+ * views > 8 or J > 64: UU3D_ERR_UNSUPPORTED; views < 1, J < 1, rows < 0, root outside 0 .. J - 1, min_views outside 2 .. 8, max_residual
+ * not finite or not > 0, NULLs, misalignment: UU3D_ERR_INVALID_ARGUMENT -- every guard before any device call; rows == 0 is UU3D_OK and
+ * launches nothing.  Every output element has one writer, no LDS, no atomics, the inputs are only read, nothing copies to the host or
+ * waits: bitwise repeatable.
+ */
+int uu3d_triangulate_joints(const float* kp2d_dev, const uint8_t* joint_flags_dev, const uint8_t* sees_dev, int32_t views, int64_t rows,
+                            int32_t num_keypoints, const double* cameras_dev, int32_t min_views, double max_residual, double* points_dev,
+                            uint8_t* count_dev, void* stream);
+int uu3d_place_joints(const float* fused_dev, const double* points_dev, const uint8_t* count_dev, int64_t rows, int32_t num_keypoints,
+                      int32_t root, float* placed_dev, uint8_t* joint_views_dev, void* stream);
+
+/*
  * ANY FRAME RATE (predict.predict_tracks(fps=...)): the front of YOUR OWN 2D TRACKS for tracks that were not filmed at the rate the model
  * was trained for.  The table holds the MODEL's time grid: row `row` (track row_track_dev[row]) is model frame k of its track, which sits at
  * source position p_k = k * fps / model_fps.  The host works the positions out in exact integer arithmetic (predict.resample_plan) and

@@ -10,7 +10,11 @@ track there, ``valid="finite"``), and ``match_views`` alone at M = 16 and 64 tra
 clock offsets 0 / -3 / +5, and 16 tracks of 2500 frames at ``max_lag`` 50) beside ``align_views_host`` (the mirror once), and
 ``predict_views(align=True)`` beside ``predict_views`` on the views cropped beforehand.
 
-    python tools/predict_views_bench.py [--config h36m_81] [--persons 2] [--frames 1000] [--match | --align [--max_lag 50]]
+``--triangulate`` times ``predict_views(triangulate=True)`` (3 cameras, 0.5 px of pixel noise) beside the call without it, and beside the
+host route: the call without it with ``return_views=True``, ``.cpu()``, then ``fuse_views_host``, ``triangulate_joints_host``,
+``place_joints_host``, ``solve_view_roots_host`` and ``root_trajectory_host``.
+
+    python tools/predict_views_bench.py [--config h36m_81] [--persons 2] [--frames 1000] [--match | --align [--max_lag 50] | --triangulate]
 """
 import argparse
 import json
@@ -186,6 +190,41 @@ def _align_rows(model, cfg, args):
     return rows
 
 
+def _triangulate_rows(model, cfg, args):
+    import torch
+    from uplift_upsample_3dhpe_amd import predict
+    J, N, T, V = int(cfg.NUM_KEYPOINTS), max(args.persons, 1), args.frames, 3
+    kw = dict(resolutions=(1024, 1024))
+    cams = _cameras(V)
+    rng = np.random.default_rng(3)
+    views = [[(t + rng.normal(0.0, 0.5, t.shape)).astype(np.float32) for t in tracks] for tracks in _views(cams, N, T, J)]
+    kp = np.stack([np.concatenate(views[v]) for v in range(V)])
+    lens = [T] * N
+
+    def with_stage():
+        return [torch.cat(r, 0).cpu() for r in predict.predict_views(model, cfg, views, cams, triangulate=True, **kw)]
+
+    def without():
+        return [torch.cat(r, 0).cpu() for r in predict.predict_views(model, cfg, views, cams, **kw)]
+
+    def host():
+        r = predict.predict_views(model, cfg, views, cams, return_views=True, **kw)
+        world = np.stack([torch.cat(per_view, 0).cpu().numpy() for per_view in r[-1]])
+        fused, count, sees = predict.fuse_views_host(world, kp)
+        X, agreed = predict.triangulate_joints_host(kp, cams, sees)
+        hybrid, joint_views = predict.place_joints_host(fused, X, agreed, int(cfg.ROOT_KEYTPOINT))
+        roots, solved = predict.solve_view_roots_host(hybrid, kp, cams)
+        return hybrid, predict.root_trajectory_host(roots, solved, lens), count, joint_views
+
+    with_stage(), without(), host()
+    a, b = with_stage(), host()
+    same = all(np.array_equal(x.numpy().view(np.uint8), np.ascontiguousarray(y).view(np.uint8))
+               for x, y in zip(a, (b[0], b[1][0], b[1][1], b[2], b[3])))
+    return [dict(row="predict_views(triangulate=True)", views=V, persons=N, frames=T, joints=J, with_triangulate_ms=round(_median(with_stage), 2),
+                 without_ms=round(_median(without), 2), host_route_ms=round(_median(host), 2), bits_equal_to_host_route=bool(same),
+                 placed_share=round(float((b[3] > 0).mean()), 4))]
+
+
 def _median(fn, n=3):
     import torch
     times = []
@@ -205,6 +244,7 @@ def main(argv=None):
     p.add_argument("--frames", type=int, default=1000)
     p.add_argument("--match", action="store_true", help="time predict_views(match=True) and match_views instead")
     p.add_argument("--align", action="store_true", help="time align_views and predict_views(align=True) instead")
+    p.add_argument("--triangulate", action="store_true", help="time predict_views(triangulate=True) beside the call without it and the host route")
     p.add_argument("--max_lag", type=int, default=50, help="the largest clock offset looked for with --align, in frames")
     args = p.parse_args(argv)
     import torch
@@ -219,6 +259,9 @@ def main(argv=None):
         return 0
     if args.align:
         print(json.dumps(dict(config=args.config, rows=_align_rows(model, cfg, args))))
+        return 0
+    if args.triangulate:
+        print(json.dumps(dict(config=args.config, rows=_triangulate_rows(model, cfg, args))))
         return 0
     J, N = int(cfg.NUM_KEYPOINTS), args.persons
     kw = dict(resolutions=(1024, 1024))

@@ -48,7 +48,9 @@ every name is importable from here as before:
                   ``predict_views(..., match=True)`` / ``match_views`` (uu3d_view_pair_sums, uu3d_group_views, uu3d_gather_view_tracks;
                   ``view_pair_sums``, ``group_views``, ``gather_view_tracks`` and their ``_host`` mirrors, ``MatchViews``); one clock:
                   ``predict_views(..., align=True)`` / ``align_views`` / ``crop_views`` (uu3d_view_lag_sums, uu3d_view_offsets;
-                  ``view_lag_sums``, ``view_offsets`` and their ``_host`` mirrors, ``AlignViews``)
+                  ``view_lag_sums``, ``view_offsets`` and their ``_host`` mirrors, ``AlignViews``); where rays meet:
+                  ``predict_views(..., triangulate=True)`` (uu3d_triangulate_joints, uu3d_place_joints; ``triangulate_joints``,
+                  ``place_joints`` and their ``_host`` mirrors, ``Triangulate``)
 """
 import argparse
 import types
@@ -81,10 +83,12 @@ from .smooth import (MAX_SMOOTH_CHANNELS, TWO_PI, OneEuro, _one_euro_rates, chec
                      one_euro_sample)
 from .tracks import (_device_track, _device_tracks, _host_array, _shape, _upload, assemble_tracks, assemble_tracks_cubic,  # noqa: F401
                      check_resolutions, keyframe_count, normalize_tracks, pose_table, resample_tracks, resampled_pose_table)
-from .views import (ALIGN_DEFAULTS, MATCH_DEFAULTS, MATCH_LANES, MAX_ALIGN_LAG, MAX_MATCH_TRACKS, MAX_VIEWS, VIEW_PARALLEL, AlignViews,  # noqa: F401
-                    MatchViews, align_views, align_views_host, check_align, check_match, check_view_cameras, check_view_of, crop_views, fuse_views, fuse_views_host, gather_view_tracks, gather_view_tracks_host, group_views, group_views_host,
-                    match_views, match_views_host, predict_views, solve_view_roots, solve_view_roots_host, view_lag_sums, view_lag_sums_host,
-                    view_offsets, view_offsets_host, view_pair_sums, view_pair_sums_host, view_rows)
+from .views import (ALIGN_DEFAULTS, MATCH_DEFAULTS, MATCH_LANES, MAX_ALIGN_LAG, MAX_MATCH_TRACKS, MAX_VIEWS, MIN_TRIANGULATE_VIEWS,  # noqa: F401
+                    TRIANGULATE_DEFAULTS, VIEW_PARALLEL, AlignViews, MatchViews, Triangulate, align_views, align_views_host, check_align, check_match,
+                    check_triangulate, check_view_cameras, check_view_of, crop_views, fuse_views, fuse_views_host, gather_view_tracks,
+                    gather_view_tracks_host, group_views, group_views_host, match_views, match_views_host, place_joints, place_joints_host,
+                    predict_views, solve_view_roots, solve_view_roots_host, triangulate_joints, triangulate_joints_host, view_lag_sums,
+                    view_lag_sums_host, view_offsets, view_offsets_host, view_pair_sums, view_pair_sums_host, view_rows)
 from .validity import (_device_joint_flags, _device_valid, _front_validity, _source_joint_flags, check_repair_joints, check_valid,  # noqa: F401
                        repair_joints, repair_joints_host)
 

@@ -41,8 +41,22 @@ everything above
 Whole frames, against the reference view only, one common frame rate; ``ALIGN_DEFAULTS`` are conveniences, not tuned values: no alignment
 accuracy is claimed.
 
-Out of scope: sub-frame offsets and per-camera frame rates, per-view confidence weights, estimating extrinsics, a live form.  No accuracy
-is claimed."""
+Where rays meet -- ``predict_views(..., triangulate=True)`` / ``triangulate_joints`` / ``place_joints``: the fused pose of step 3 is a
+mean of V monocular lifts, and the model's scale and depth errors, which all views share, stay in it.  With ``triangulate``, directly
+behind the fusion and in front of ``bones``,
+  3a. uu3d_triangulate_joints solves every joint that at least ``min_views`` seeing cameras observed from their rays alone: two weighted
+      3 x 3 solves per round, the view of the largest reprojection residual dropped between rounds until all that remain agree within
+      ``max_residual`` pixels (``triangulate_joints_host``),
+  3b. uu3d_place_joints writes the HYBRID pose: X_j - X_root where both are triangulated, the fused lift's bits for every other joint --
+      one camera saw it, the frame's root joint is lost, one camera saw the person (``place_joints_host``).
+Everything behind (``bones``, the root solve, the trajectory, ``smooth``, ``rotations``) runs unchanged on that pose, and ``joint_views``
+says per frame and joint how many cameras placed it (0: the lift).  With two views an error along the epipolar line cannot be seen; with
+three views and an outlier the honest view can be the one dropped; the lines are lines apart from the z > 0 test; a kept lifted joint
+stays relative to the root, not to its triangulated parent, so bones across the seam can stretch (``bones`` fixes lengths behind the
+stage).  ``TRIANGULATE_DEFAULTS`` are conveniences, not tuned values.
+
+Out of scope: sub-frame offsets and per-camera frame rates, per-view confidence weights, estimating extrinsics, a live form, command-line
+flags.  No accuracy is claimed."""
 import ctypes as C
 
 import numpy as np
@@ -61,6 +75,8 @@ VIEW_PARALLEL = 2.0 ** -20                                             # kViewPa
 MATCH_DEFAULTS = dict(max_dist=0.2, min_terms=50)                      # conveniences for metres, not tuned values
 MAX_ALIGN_LAG = 512                                                    # kAlignMaxLag: the largest clock offset looked for, in frames
 ALIGN_DEFAULTS = dict(max_lag=50, min_terms=50)                        # conveniences for 50 Hz and metres, not tuned values
+MIN_TRIANGULATE_VIEWS = 2                                              # kTriangulateMinViews: two lines meet in a point, one does not
+TRIANGULATE_DEFAULTS = dict(max_residual=8.0, min_views=2)             # pixels of the tracks as given; conveniences, not tuned values
 
 
 def check_view_cameras(cameras, views=None):
@@ -269,6 +285,241 @@ def solve_view_roots(poses, kp2d, cameras, flags=None, min_root_joints=DEFAULT_M
         _capi.check(lib, lib.uu3d_solve_view_roots(_ptr(poses), _ptr(kp2d), _ptr(flags), V, R, J, _ptr(cams), m, _ptr(roots), _ptr(solved),
                                                    C.c_void_p(stream)), None)
     return roots, solved.view(torch.bool)
+
+
+# ---- where rays meet: joints placed by geometry where two or more cameras agree (include/uu3d.h, WHERE RAYS MEET) ------------------------
+class Triangulate(object):
+    """The parameters of ``predict_views(triangulate=...)`` / ``triangulate_joints``: ``max_residual``, the largest reprojection error, in
+    pixels of the tracks as given, a view may show at a triangulated joint (finite, > 0), and ``min_views``, the least number of cameras
+    that must agree on a joint (an int in 2 .. 8).  The defaults are conveniences, not tuned values."""
+
+    def __init__(self, max_residual=TRIANGULATE_DEFAULTS["max_residual"], min_views=TRIANGULATE_DEFAULTS["min_views"]):
+        self.max_residual, self.min_views = _triangulate_parameters(max_residual, min_views)
+
+    def __repr__(self):
+        return f"Triangulate(max_residual={self.max_residual!r}, min_views={self.min_views!r})"
+
+
+def _triangulate_parameters(max_residual, min_views):
+    try:
+        r = float(max_residual)
+    except (TypeError, ValueError):
+        raise ValueError(f"max_residual must be a finite number > 0, got {max_residual!r}") from None
+    if isinstance(max_residual, bool) or not np.isfinite(r) or not r > 0:
+        raise ValueError(f"max_residual must be a finite number > 0, got {max_residual!r}")
+    if isinstance(min_views, bool) or not isinstance(min_views, (int, np.integer)) or not MIN_TRIANGULATE_VIEWS <= int(min_views) <= MAX_VIEWS:
+        raise ValueError(f"min_views must be an int in {MIN_TRIANGULATE_VIEWS} .. {MAX_VIEWS}, got {min_views!r}")
+    return r, int(min_views)
+
+
+def check_triangulate(triangulate):
+    """``predict_views(triangulate=...)`` -> None (the fused lifts stay as they are) or a ``Triangulate``; True is the defaults."""
+    if triangulate is None:
+        return None
+    if triangulate is True:
+        return Triangulate()
+    if not isinstance(triangulate, Triangulate):
+        raise ValueError(f"triangulate must be None, True or a Triangulate(max_residual=, min_views=), got {triangulate!r}")
+    return triangulate
+
+
+def _check_root_joint(root, J):
+    if isinstance(root, bool) or not isinstance(root, (int, np.integer)) or not 0 <= int(root) < J:
+        raise ValueError(f"root must be a joint in 0 .. {J - 1}, got {root!r}")
+    return int(root)
+
+
+def _weighted_solve(uv64, cam, cand, q):
+    """One pass of ``triangulate_joints_host``: ``uv64`` (V, R, J, 2), ``cam`` the ``view_rows``, ``cand`` (V, R, J) bool, ``q`` (V, R, J)
+    -> (X (R, J, 3), accepted (R, J)).  The cofactor statements are those of ``solve_view_roots_host``, term for term."""
+    a00, a01, a02, a11, a12, a22, b0, b1, b2 = (np.zeros(cand.shape[1:], np.float64) for _ in range(9))
+    for v in range(cand.shape[0]):
+        fx, fy, cx, cy = cam[v, :4]
+        r1, r2, r3, t = cam[v, 4:7], cam[v, 7:10], cam[v, 10:13], cam[v, 13:16]
+        a = (uv64[v, :, :, 0] - cx) / fx
+        b = (uv64[v, :, :, 1] - cy) / fy
+        n0, n1, n2 = (r1[0] - a * r3[0]) * q[v], (r1[1] - a * r3[1]) * q[v], (r1[2] - a * r3[2]) * q[v]
+        m0, m1, m2 = (r2[0] - b * r3[0]) * q[v], (r2[1] - b * r3[1]) * q[v], (r2[2] - b * r3[2]) * q[v]
+        e = (n0 * t[0] + n1 * t[1]) + n2 * t[2]
+        g = (m0 * t[0] + m1 * t[1]) + m2 * t[2]
+        u = cand[v]
+        a00 = np.where(u, a00 + (n0 * n0 + m0 * m0), a00)
+        a01 = np.where(u, a01 + (n0 * n1 + m0 * m1), a01)
+        a02 = np.where(u, a02 + (n0 * n2 + m0 * m2), a02)
+        a11 = np.where(u, a11 + (n1 * n1 + m1 * m1), a11)
+        a12 = np.where(u, a12 + (n1 * n2 + m1 * m2), a12)
+        a22 = np.where(u, a22 + (n2 * n2 + m2 * m2), a22)
+        b0 = np.where(u, b0 + (n0 * e + m0 * g), b0)
+        b1 = np.where(u, b1 + (n1 * e + m1 * g), b1)
+        b2 = np.where(u, b2 + (n2 * e + m2 * g), b2)
+    c00 = a11 * a22 - a12 * a12
+    c01 = a02 * a12 - a01 * a22
+    c02 = a01 * a12 - a02 * a11
+    c11 = a00 * a22 - a02 * a02
+    c12 = a01 * a02 - a00 * a12
+    c22 = a00 * a11 - a01 * a01
+    det = (a00 * c00 + a01 * c01) + a02 * c02
+    x0 = (c00 * b0 + c01 * b1) + c02 * b2
+    x1 = (c01 * b0 + c11 * b1) + c12 * b2
+    x2 = (c02 * b0 + c12 * b1) + c22 * b2
+    X = np.stack([x0 / det, x1 / det, x2 / det], axis=-1)
+    accepted = np.isfinite(det) & (det > 0) & (det > VIEW_PARALLEL * ((a00 * a11) * a22)) & np.isfinite(X).all(axis=-1)
+    return X, accepted
+
+
+def _view_depths(X, cam):
+    """z_v = (r3_0 w0 + r3_1 w1) + r3_2 w2 with w = X - t, for every view -> (z (V, R, J), w (V, R, J, 3))."""
+    w = X[None] - cam[:, None, None, 13:16]
+    r3 = cam[:, None, None, 10:13]
+    return (r3[..., 0] * w[..., 0] + r3[..., 1] * w[..., 1]) + r3[..., 2] * w[..., 2], w
+
+
+def triangulate_joints_host(kp2d, cameras, sees, flags=None, max_residual=TRIANGULATE_DEFAULTS["max_residual"],
+                            min_views=TRIANGULATE_DEFAULTS["min_views"]):
+    """The triangulation of WHERE RAYS MEET (include/uu3d.h) in numpy, written to be read: what uu3d_triangulate_joints computes, bit for
+    bit.  ``kp2d`` (V, R, J, 2): the raw 2D keypoints in the model's layout, undistorted (read as float32); ``cameras``: V ``Camera``
+    objects with extrinsics; ``sees`` (V, R): the third output of ``fuse_views_host``; ``flags``: None or (V, R, J)
+    -> (X (R, J, 3) float64 in world coordinates, count (R, J) uint8: the cameras that agree on the joint, 0 = not triangulated, X zeros).
+    Everything in float64, every operation rounded once; per view a row of ``view_rows``.  Per frame and joint the candidate set C holds
+    the views that SEE the frame and in which the joint is USED (the definitions of ``fuse_views_host``).  A round:
+      * fewer than ``min_views`` candidates: not triangulated.
+      * pass 1, over the candidates in ascending order, with q_v = 1.0:
+            a = (u - cx) / fx;  b = (v - cy) / fy;  n_i = (r1_i - a r3_i) q_v;  m_i = (r2_i - b r3_i) q_v
+            e = (n0 t0 + n1 t1) + n2 t2;  g = (m0 t0 + m1 t1) + m2 t2
+            A_ik += (n_i n_k + m_i m_k) for ik = 00, 01, 02, 11, 12, 22;  B_i += (n_i e + m_i g)
+        -- n . (X - t) = 0 and m . (X - t) = 0: the joint lies on the line of its pixel --, solved by the cofactors of
+        ``solve_view_roots_host``.  ACCEPTED iff det is finite and > 0, det > ``VIEW_PARALLEL`` * ((A00 A11) A22) and X is finite: 2^-20
+        with the meaning it has in ``view_pair_sums_host`` -- rays closer than about 1e-3 rad carry no distance information; two
+        coincident cameras give rounding noise, ring cameras 0.037 or more with three views and 0.49 with two.  With w = X - t,
+        z_v = (r3_0 w0 + r3_1 w1) + r3_2 w2 must be > 0 for every candidate, else the joint is not triangulated: no view is dropped for
+        lying behind.
+      * pass 2: the same statements with q_v = 1.0 / z_v -- the depth-weighted algebraic error becomes one in normalised image units --,
+        the same guards, z_v from the new X.
+      * the residual per candidate: xc = (r1_0 w0 + r1_1 w1) + r1_2 w2, yc with r2; du = |(fx (xc / z_v) + cx) - u|, dv likewise;
+        rho_v = max(du, dv), +inf if either is NaN.
+      * every rho_v <= ``max_residual``: triangulated, X with count = |C|.  Otherwise the view of the largest rho_v leaves C (ties: the
+        larger view index) and the next round runs.
+    At most V - min_views + 1 rounds of exactly two passes, without an early exit (the spirit of ``Camera.ITERATIONS``).  With exactly
+    two views an error along the epipolar line cannot be seen; the lines are lines apart from the z > 0 test."""
+    uv = np.asarray(_host_array(kp2d), np.float32)
+    if uv.ndim != 4 or uv.shape[3] != 2 or not 1 <= uv.shape[0] <= MAX_VIEWS or not 1 <= uv.shape[2] <= MAX_ROOT_JOINTS:
+        raise ValueError(f"kp2d must be (V, R, J, 2) with V <= {MAX_VIEWS} and J <= {MAX_ROOT_JOINTS}, got {uv.shape}")
+    V, R, J = uv.shape[:3]
+    max_residual, min_views = _triangulate_parameters(max_residual, min_views)
+    cam = view_rows(check_view_cameras(cameras, V))
+    S = np.asarray(_host_array(sees)) != 0
+    if S.shape != (V, R):
+        raise ValueError(f"sees must be ({V}, {R}), got {S.shape}")
+    used = np.isfinite(uv).all(axis=3)
+    if flags is not None:
+        f = np.asarray(_host_array(flags)) != 0
+        if f.shape != (V, R, J):
+            raise ValueError(f"flags must be ({V}, {R}, {J}), got {f.shape}")
+        used &= f
+    cand = used & S[:, :, None]
+    uv64 = uv.astype(np.float64)
+    X = np.zeros((R, J, 3), np.float64)
+    count = np.zeros((R, J), np.uint8)
+    open_ = np.ones((R, J), bool)                                        # neither triangulated nor given up
+    with np.errstate(all="ignore"):
+        for _ in range(V - min_views + 1):
+            size = cand.sum(axis=0)
+            open_ &= size >= min_views
+            if not open_.any():
+                break
+            X1, ok = _weighted_solve(uv64, cam, cand, np.ones(cand.shape, np.float64))
+            z, _ = _view_depths(X1, cam)
+            ok &= (~cand | (z > 0)).all(axis=0)
+            X2, ok2 = _weighted_solve(uv64, cam, cand, 1.0 / z)
+            z, w = _view_depths(X2, cam)
+            ok &= ok2 & (~cand | (z > 0)).all(axis=0)
+            r1, r2 = cam[:, None, None, 4:7], cam[:, None, None, 7:10]
+            xc = (r1[..., 0] * w[..., 0] + r1[..., 1] * w[..., 1]) + r1[..., 2] * w[..., 2]
+            yc = (r2[..., 0] * w[..., 0] + r2[..., 1] * w[..., 1]) + r2[..., 2] * w[..., 2]
+            du = np.abs((cam[:, None, None, 0] * (xc / z) + cam[:, None, None, 2]) - uv64[..., 0])
+            dv = np.abs((cam[:, None, None, 1] * (yc / z) + cam[:, None, None, 3]) - uv64[..., 1])
+            rho = np.where(np.isnan(du) | np.isnan(dv), np.inf, np.maximum(du, dv))
+            rho = np.where(cand, rho, -1.0)                              # (the residuals are >= 0)
+            fits = (rho <= max_residual).all(axis=0)
+            done = open_ & ok & fits
+            X[done], count[done] = X2[done], size[done]
+            open_ &= ok & ~fits                                          # a refused solve or a joint behind a camera: given up
+            drop = V - 1 - np.argmax(rho[::-1], axis=0)                  # the largest residual, ties to the larger view index
+            cand &= ~(open_[None] & (np.arange(V)[:, None, None] == drop[None]))
+    return X, count
+
+
+def place_joints_host(fused, points, count, root=0):
+    """The placement of WHERE RAYS MEET (include/uu3d.h) in numpy: what uu3d_place_joints computes, bit for bit.  ``fused`` (R, J, 3): the
+    fused world pose of every frame, root-relative (read as float32); ``points`` (R, J, 3) float64 and ``count`` (R, J) of
+    ``triangulate_joints_host``; ``root``: the root joint -> (placed (R, J, 3) float32, joint_views (R, J) uint8).
+    Where both the joint and the frame's root joint are triangulated the pose is float32(X_j - X_root) per channel -- +0.0 for the root
+    joint itself -- and joint_views is the joint's count; every other joint keeps the fused pose's bits, NaN included, and joint_views 0.
+    A frame without a triangulated root joint stays lifted as a whole.  A kept lifted joint stays relative to the root, not to its
+    triangulated parent: bones across the seam can stretch, and ``bones`` runs behind this stage."""
+    P = np.ascontiguousarray(np.asarray(_host_array(fused), np.float32))
+    X = np.asarray(_host_array(points), np.float64)
+    n = np.asarray(_host_array(count), np.uint8)
+    if P.ndim != 3 or P.shape[2] != 3 or not 1 <= P.shape[1] <= MAX_ROOT_JOINTS or X.shape != P.shape or n.shape != P.shape[:2]:
+        raise ValueError(f"fused and points must be (R, J, 3) with J <= {MAX_ROOT_JOINTS} and count (R, J), got {P.shape}, {X.shape} and {n.shape}")
+    root = _check_root_joint(root, P.shape[1])
+    take = (n > 0) & (n[:, root] > 0)[:, None]
+    with np.errstate(all="ignore"):
+        moved = (X - X[:, root][:, None, :]).astype(np.float32)
+    moved[:, root] = 0.0
+    placed = np.where(take[:, :, None], moved, P)
+    return placed, np.where(take, n, 0).astype(np.uint8)
+
+
+def triangulate_joints(kp2d, cameras, sees, flags=None, max_residual=TRIANGULATE_DEFAULTS["max_residual"],
+                       min_views=TRIANGULATE_DEFAULTS["min_views"]):
+    """uu3d_triangulate_joints on the current stream: ``triangulate_joints_host`` on device tensors, one launch, nothing copies to the
+    host or waits (the V camera rows go up pinned and asynchronously).  ``kp2d`` (V, R, J, 2) float32, ``sees`` (V, R) uint8 / bool and
+    ``flags`` (V, R, J) uint8 / bool or None on the device, contiguous (only read) -> (X (R, J, 3) float64, count (R, J) uint8), fresh
+    device buffers.  Needs no model."""
+    import torch
+    lib = _capi.load_library()
+    if not _is_device(kp2d, torch.float32) or kp2d.dim() != 4 or kp2d.shape[3] != 2:
+        raise ValueError(f"kp2d must be a contiguous (V, R, J, 2) float32 device tensor, got {tuple(getattr(kp2d, 'shape', ()))}")
+    V, R, J = (int(n) for n in kp2d.shape[:3])
+    if not 1 <= V <= MAX_VIEWS or not 1 <= J <= MAX_ROOT_JOINTS:
+        raise ValueError(f"between 1 and {MAX_VIEWS} views and 1 and {MAX_ROOT_JOINTS} joints are taken, got {V} and {J}")
+    dev = kp2d.device
+    if not _is_device(sees, (torch.uint8, torch.bool), dev) or tuple(sees.shape) != (V, R):
+        raise ValueError(f"sees must be a contiguous ({V}, {R}) uint8 or bool tensor on kp2d's device")
+    if flags is not None and (not _is_device(flags, (torch.uint8, torch.bool), dev) or tuple(flags.shape) != (V, R, J)):
+        raise ValueError(f"flags must be a contiguous ({V}, {R}, {J}) uint8 or bool tensor on kp2d's device")
+    max_residual, min_views = _triangulate_parameters(max_residual, min_views)
+    cams = _upload(view_rows(check_view_cameras(cameras, V)), np.float64, dev)
+    X = torch.empty((R, J, 3), dtype=torch.float64, device=dev)
+    count = torch.empty((R, J), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _capi.check(lib, lib.uu3d_triangulate_joints(_ptr(kp2d), _ptr(None if flags is None else flags.view(torch.uint8)), _ptr(sees.view(torch.uint8)),
+                                                     V, R, J, _ptr(cams), min_views, max_residual, _ptr(X), _ptr(count), C.c_void_p(stream)), None)
+    return X, count
+
+
+def place_joints(fused, points, count, root=0):
+    """uu3d_place_joints on the current stream: ``place_joints_host`` on device tensors, one launch, nothing copies to the host or waits.
+    ``fused`` (R, J, 3) float32, ``points`` (R, J, 3) float64 and ``count`` (R, J) uint8 on the device, contiguous (only read)
+    -> (placed (R, J, 3) float32, joint_views (R, J) uint8), fresh device buffers.  Needs no model."""
+    import torch
+    lib = _capi.load_library()
+    if not _is_device(fused, torch.float32) or fused.dim() != 3 or fused.shape[2] != 3 or not 1 <= fused.shape[1] <= MAX_ROOT_JOINTS:
+        raise ValueError(f"fused must be a contiguous (R, J, 3) float32 device tensor with J <= {MAX_ROOT_JOINTS}, got {tuple(getattr(fused, 'shape', ()))}")
+    R, J = int(fused.shape[0]), int(fused.shape[1])
+    dev = fused.device
+    if not _is_device(points, torch.float64, dev) or tuple(points.shape) != (R, J, 3) or not _is_device(count, torch.uint8, dev) or tuple(count.shape) != (R, J):
+        raise ValueError(f"points must be a contiguous ({R}, {J}, 3) float64 tensor and count a ({R}, {J}) uint8 one on fused's device")
+    root = _check_root_joint(root, J)
+    placed = torch.empty((R, J, 3), dtype=torch.float32, device=dev)
+    joint_views = torch.empty((R, J), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _capi.check(lib, lib.uu3d_place_joints(_ptr(fused), _ptr(points), _ptr(count), R, J, root, _ptr(placed), _ptr(joint_views), C.c_void_p(stream)),
+                    None)
+    return placed, joint_views
 
 
 # ---- who is who: which track of one camera is which of another (include/uu3d.h, WHO IS WHO) ---------------------------------------------
@@ -1163,13 +1414,18 @@ def _check_views(views, cameras, valid, keyframes_only, out_fps):
     return cams, V, N, frames
 
 
-def _fused_scene(pt, person, world, kp2d, flags, cams, lens, rates, model_fps, return_views):
+def _fused_scene(pt, person, world, kp2d, flags, cams, lens, rates, model_fps, return_views, triangulate=None, root=0):
     """Stages 3 to 6 of the module's docstring, behind uu3d_camera_to_world: ``world`` (V, R, J, 3), ``kp2d`` (V, R, J, 2) and ``flags`` None
     or (V, R, J), view-major, the same person at the same rows of every view; ``person``: the ``StageOptions`` of the persons; ``lens``:
-    frames per person -> what ``predict_views`` returns."""
+    frames per person; ``triangulate``: None or a ``Triangulate``, ``root`` the root joint -> what ``predict_views`` returns."""
     import torch
     # 4. the fusion
-    fused, view_count, _ = fuse_views(world, kp2d, flags, person.min_root_joints)
+    fused, view_count, sees = fuse_views(world, kp2d, flags, person.min_root_joints)
+    # 4a. + 4b. where rays meet: the joints two or more seeing cameras agree on, placed by geometry
+    joint_views = None
+    if triangulate is not None:
+        points, agreed = triangulate_joints(kp2d, cams, sees, flags, triangulate.max_residual, triangulate.min_views)
+        fused, joint_views = place_joints(fused, points, agreed, root)
     # 5. bones on the fused poses of the N persons
     if person.rigid is not None:
         skeleton, known = person.rigid
@@ -1187,7 +1443,7 @@ def _fused_scene(pt, person, world, kp2d, flags, cams, lens, rates, model_fps, r
     if person.root_filter is not None:
         roots = pt.one_euro(roots, lens, out_rate, person.root_filter, state=root_state)
     sizes = [int(n) for n in lens]
-    result = tuple(list(torch.split(a, sizes, 0)) for a in (shown, roots, root_state, view_count))
+    result = tuple(list(torch.split(a, sizes, 0)) for a in (shown, roots, root_state, view_count) + (() if joint_views is None else (joint_views,)))
     if person.rotations is not None:
         turned = pt.joint_rotations(shown, person.rotations)
         result += (list(torch.split(turned[0], sizes, 0)),) + ((list(torch.split(turned[2], sizes, 0)),) if person.rotations.return_global else ())
@@ -1199,7 +1455,7 @@ def _fused_scene(pt, person, world, kp2d, flags, cams, lens, rates, model_fps, r
 def predict_views(model, config, views, cameras, resolutions=None, mask_stride=None, flip=None, reuse_frames=True, batch_size=None, depth=None,
                   graph=True, valid=None, fps=None, model_fps=50, repair_joints=None, keypoints=None, min_root_joints=DEFAULT_MIN_ROOT_JOINTS,
                   smooth=None, bones=None, rotations=None, interpolation="linear", return_views=False, keyframes_only=False, out_fps=None, match=None,
-                  align=None):
+                  align=None, triangulate=None):
     """One world scene from V calibrated views of the same N persons -> (poses, roots, root_state, view_count): per person ``poses``
     (T_i, J, 3) float32 in world axes and root-relative, ``roots`` (T_i, 3) float32 in world coordinates, ``root_state`` (T_i,) uint8 (1
     solved here, 2 interpolated or held, 0 no solved frame) and ``view_count`` (T_i,) uint8, the views that saw the frame; on the model's
@@ -1251,21 +1507,34 @@ def predict_views(model, config, views, cameras, resolutions=None, mask_stride=N
     in length, ``max_lag`` of twice the shortest view's frames or more; ``keyframes_only`` and ``out_fps`` stay refused in their words.
     The result minus its last two items equals, bit for bit, ``predict_views(*crop_views(views, offsets, valid)[:2], align=None)``.
     Whole frames against the first non-empty view only: no sub-frame refinement, no per-camera frame rates, no chaining through a third
-    camera; periodic or standing motion is ambiguous.  No alignment accuracy is claimed."""
+    camera; periodic or standing motion is ambiguous.  No alignment accuracy is claimed.
+
+    Where rays meet -- ``triangulate``: None = the call above, the same launches, buffers, refusals and bits.  True
+    (``TRIANGULATE_DEFAULTS``) or a ``Triangulate(max_residual=, min_views=)``; anything else is a ValueError.  Directly behind the fusion
+    and in front of ``bones`` -- on the plain, the ``match`` and the ``align`` route alike -- uu3d_triangulate_joints solves every joint
+    that at least ``min_views`` seeing cameras observed from their rays alone, and uu3d_place_joints writes the hybrid pose: a joint the
+    cameras agree on within ``max_residual`` pixels (of the tracks as given, undistorted) is X_j - X_root, with ``config.ROOT_KEYTPOINT``
+    the root; every other joint, and every joint of a frame whose root joint is not triangulated, keeps the fused lift.  Two launches,
+    nothing copies to the host or waits; everything behind runs unchanged on that pose.  -> ``joint_views`` directly behind
+    ``view_count``: per person (T_i, J) uint8, the cameras that placed the joint, 0 where it is the lift; ``rotations``, ``return_views``
+    (still the per-view lifts), ``person``, ``offsets`` and ``first`` follow as before.  One view is taken, and nothing is triangulated.
+    The result equals, bit for bit, the host composition with ``triangulate_joints_host`` and ``place_joints_host`` behind
+    ``fuse_views_host``.  The limits stand in the module's docstring; the defaults are not tuned, and no accuracy is claimed."""
     import torch
     from . import predict as pt
     match = check_match(match)
     align = check_align(align)
+    triangulate = check_triangulate(triangulate)
     if align is not None:
         def call(cropped, kept):
             return predict_views(model, config, cropped, cameras, resolutions, mask_stride, flip, reuse_frames, batch_size, depth, graph, kept, fps,
                                  model_fps, repair_joints, keypoints, min_root_joints, smooth, bones, rotations, interpolation, return_views,
-                                 keyframes_only, out_fps, match, None)
+                                 keyframes_only, out_fps, match, None, triangulate)
         return _predict_aligned_views(align, match, model, views, cameras, valid, fps, keyframes_only, out_fps, call)
     if match is not None:
         return _predict_matched_views(pt, match, model, config, views, cameras, resolutions, mask_stride, flip, reuse_frames, batch_size, depth, graph,
                                       valid, fps, model_fps, repair_joints, keypoints, min_root_joints, smooth, bones, rotations, interpolation,
-                                      return_views, keyframes_only, out_fps)
+                                      return_views, keyframes_only, out_fps, triangulate)
     cams, V, N, frames = _check_views(views, cameras, valid, keyframes_only, out_fps)
     # the options of the N persons: what runs behind the fusion (the flattened front takes none of them)
     person = pt.stage_options(config, N, "track", True, keypoints, cams[0].without(distortion=True, extrinsics=True), min_root_joints, smooth,
@@ -1296,12 +1565,12 @@ def predict_views(model, config, views, cameras, resolutions=None, mask_stride=N
     # 3. every view's poses to world axes: the existing launch, poses only, one row of extrinsics per view block
     world, _ = camera_to_world_rows(front.out, None, None, np.stack([c.pose_row() for c in cams]), [R] * V)
     return _fused_scene(pt, person, world.view(V, R, J, 3), kp2d.reshape(V, R, J, 2), None if flags is None else flags.reshape(V, R, J), cams, lens,
-                        rates, model_fps, return_views)
+                        rates, model_fps, return_views, triangulate, int(config.ROOT_KEYTPOINT))
 
 
 def _predict_matched_views(pt, match, model, config, views, cameras, resolutions, mask_stride, flip, reuse_frames, batch_size, depth, graph, valid,
                            fps, model_fps, repair_joints, keypoints, min_root_joints, smooth, bones, rotations, interpolation, return_views,
-                           keyframes_only, out_fps):
+                           keyframes_only, out_fps, triangulate=None):
     """``predict_views(match=...)``: the steps of its docstring, "Who is who"."""
     import torch
     if keyframes_only:
@@ -1347,6 +1616,7 @@ def _predict_matched_views(pt, match, model, config, views, cameras, resolutions
     src = _upload(table[:, :P], np.int32, world.device)
     world, kp2d, flags = gather_view_tracks(src, world, kp2d.contiguous(), None if flags is None else flags.contiguous(), T)
     lens = np.full(P, T, np.int64)
-    result = _fused_scene(pt, person, world, kp2d, flags, cams, lens, None if rate is None else [rate] * P, model_fps, return_views)
+    result = _fused_scene(pt, person, world, kp2d, flags, cams, lens, None if rate is None else [rate] * P, model_fps, return_views, triangulate,
+                          int(config.ROOT_KEYTPOINT))
     starts = np.concatenate([[0], np.cumsum(counts)])
     return result + ([[int(k) for k in who[starts[v]:starts[v + 1]]] for v in range(V)],)
