@@ -925,6 +925,77 @@ int uu3d_place_joints(const float* fused_dev, const double* points_dev, const ui
                       int32_t root, float* placed_dev, uint8_t* joint_views_dev, void* stream);
 
 /*
+ * WHERE THE CAMERAS STAND (predict.calibrate_views, predict.view_moment_sums, predict.view_position_sums, predict.solve_view_pose,
+ * predict.predict_views(calibrate=...)): SEVERAL VIEWS takes every camera's extrinsics as given, and who puts two phones and a webcam on
+ * tripods has none.  Every view's lift is the same skeleton in that camera's own axes, so the rotation between two cameras is the rotation
+ * between their lifts; every view's rays and the lifts' metric size then fix where the second camera stands.  The calls here find the pose
+ * of views 1 .. views - 1 in the space of view 0: a unit quaternion q_v and a position c_v with X_0 = qrot(q_v, X_v) + c_v, the convention
+ * of WORLD SPACE.  predict.view_moment_sums_host, predict.view_position_sums_host and predict.solve_view_pose_host are the same rules in
+ * numpy, bit for bit.  In float64 on the float32 inputs, every operation rounded once, no fused multiply-add, correctly rounded square root
+ * and division; the order of every sum is part of the rule.  The buffers are view-major: poses_dev (views, rows, J, 3) f32 -- the lifts,
+ * root-relative, in each camera's OWN axes --, kp2d_dev (views, rows, J, 2) f32, joint_flags_dev (views, rows, J) u8 or NULL; USED is the
+ * test of SEVERAL VIEWS.
+ * SEES.  View v sees row r iff at least min_joints of its joints are USED there -- the rule of uu3d_fuse_views, counted here because the
+ * fusion runs later.  Row r is a TERM of view v >= 1 iff view 0 and view v both see it.
+ * THE ORDER OF SUMMATION, for both sums: the rows are cut into chunks of 4096; within chunk k lane l of 256 adds the values of the terms
+ * among rows 4096 k + l, + 256, ... ascending to 0.0; then for stride = 128, 64, ..., 1: x[l] = x[l] + x[l + stride] for l < stride (the
+ * tree of PAIR SUMS), one value after the other; x[0] is the chunk's partial, partial_dev (views, chunks, 10) f64, the tenth value the
+ * number of terms.  The solve adds a view's chunks ascending to 0.0.  View 0's partials are zeros.
+ * 1. ROTATION (uu3d_view_moment_sums).  A term's values: s_ik = 0.0; s_ik = s_ik + p_v[j][i] * p_0[j][k] over ALL J joints ascending, p the
+ *   lift of the row (an unobserved joint's lift is still read); ik = 00, 01, 02, 10, ..., 22.  Their sum is M_v.
+ * 2. QUATERNION (uu3d_solve_view_pose, stage 0; one wave, a view per lane).  Horn's symmetric matrix
+ *     N00 = (M00 + M11) + M22;  N01 = M12 - M21;  N02 = M20 - M02;  N03 = M01 - M10;  N11 = (M00 - M11) - M22;  N12 = M01 + M10
+ *     N13 = M20 + M02;  N22 = (M11 - M00) - M22;  N23 = M12 + M21;  N33 = (M22 - M00) - M11
+ *   goes through 10 sweeps of cyclic Jacobi, no early exit, the pairs (p, q) in the order (0,1) (0,2) (0,3) (1,2) (1,3) (2,3); E starts as
+ *   the identity.  A rotation:
+ *     th = (Nqq - Npp) / (2.0 Npq);  tt = (th >= 0.0 ? 1.0 : -1.0) / (|th| + sqrt(th th + 1.0));  t = Npq == 0.0 ? 0.0 : tt
+ *     c = 1.0 / sqrt(t t + 1.0);  s = t c;  Npp = Npp - t Npq;  Nqq = Nqq + t Npq;  Npq = 0.0
+ *     for the two other indices r ascending: (Nrp, Nrq) = (c Nrp - s Nrq, s Nrp + c Nrq);  for i = 0 .. 3: (Eip, Eiq) likewise
+ *   -- the smaller-root tangent; a zero off-diagonal rotates nothing.  The eigenvalues are the diagonal; the column e of the largest is
+ *   taken, ties to the smaller index; len = sqrt(((e0 e0 + e1 e1) + e2 e2) + e3 e3), q = e / len, negated as a whole when q0 < 0.0.  The
+ *   view is REFUSED (state 0, the identity quaternion) when its terms are fewer than min_terms, an eigenvalue or q is not finite, or
+ *   top - next > 2^-20 |top| does not hold for the two largest eigenvalues: the lifts then do not fix a rotation (all zeros, one point).
+ * 3. POSITION (uu3d_view_position_sums; behind stage 0, whose quaternions it reads from device memory).  Per term, per view u in {0, v}, over
+ *   u's USED joints ascending, the root-solve rows of SEVERAL VIEWS:
+ *     a = (u - cx) / fx;  b = (v - cy) / fy;  n_i = r1_i - a r3_i;  m_i = r2_i - b r3_i;  e = (n0 P0 + n1 P1) + n2 P2;  g likewise with m
+ *     A_ik += (n_i n_k + m_i m_k) for ik = 00, 01, 02, 11, 12, 22;  B_i += (n_i e + m_i g)
+ *   View 0: r1, r2, r3 = e_1, e_2, e_3 and P = its own lift.  View v: r_i = qrot(q_v, e_i) and P = qrot(q_v, lift), qrot the statements of
+ *   WORLD SPACE before their final rounding.  With the row's unknown root T: A0 T = -B0 and Av (T - c) = -Bv.  T is eliminated:
+ *     A = A0 + Av, its cofactors c00 .. c22 and det by the statements of SEVERAL VIEWS; det not finite, not > 0 or not above
+ *     2^-40 ((A00 A11) A22): the row is not a term.  K_ik = c_ik / det
+ *     W_ik = (Av_i0 K_0k + Av_i1 K_1k) + Av_i2 K_2k, all nine
+ *     S_ik = Av_ik - ((W_i0 Av_0k + W_i1 Av_1k) + W_i2 Av_2k) for ik = 00, 01, 02, 11, 12, 22
+ *     h = B0 + Bv;  g_i = Bv_i - ((W_i0 h0 + W_i1 h1) + W_i2 h2)
+ *   A view whose state is not 1, and a view whose or view 0's fx, fy, cx, cy are not finite with fx, fy > 0, has no terms.
+ * 4. SOLVE (uu3d_solve_view_pose, stage 1: a second launch of the same kernel).  S c = g by the same cofactors, c_i = x_i / det; det not
+ *   finite, not > 0, not above 2^-40 ((S00 S11) S22), or c not finite: state 0, position zeros, the quaternion stays.
+ * pose_dev (views, 8) f64: q (4), c (3), the state as 1.0 / 0.0.  Row 0 is the identity, zeros and 1.  terms_dev (views) i32: the terms
+ * of the stage's sums.
+ * LIMITS.  The rig's scale is the model's: lifts scaled by s put every camera s times too far away, and nothing here rescales.  Every
+ * view is calibrated against view 0 only; nothing is chained through a third camera.  Every term has unit weight in an algebraic error:
+ * near and far frames count alike.  A person who only stands still fixes the position poorly.  The view-dependent depth errors of real
+ * lifts are not modelled.  No accuracy is claimed.
+ *
+ *   uu3d_view_calibrate_chunks(rows): (rows + 4095) / 4096, 0 for rows outside 1 .. 2^31 - 1.
+ *   uu3d_view_moment_sums(poses_dev, kp2d_dev, joint_flags_dev or NULL, views, rows, J, min_joints, partial_dev, stream): one launch, one
+ *       workgroup per (chunk, view).
+ *   uu3d_view_position_sums(..., J, intrinsics_dev (views, 4) f64, min_joints, pose_dev of stage 0, partial_dev, stream): likewise.
+ *   uu3d_solve_view_pose(partial_dev, views, chunks, stage, min_terms, pose_in_dev (stage 1; not pose_out_dev), pose_out_dev, terms_dev,
+ *       stream): one launch of one wave.
+ * views > 8 or J > 64: UU3D_ERR_UNSUPPORTED; views < 1, J < 1, rows or chunks < 1, rows >= 2^31, min_joints < 2, min_terms < 1, another
+ * stage, NULLs, misalignment: UU3D_ERR_INVALID_ARGUMENT -- every guard before any device call.  Every output element has one writer, no
+ * atomics, the inputs are only read, nothing copies to the host or waits: bitwise repeatable.
+ */
+int64_t uu3d_view_calibrate_chunks(int64_t rows);
+int uu3d_view_moment_sums(const float* poses_dev, const float* kp2d_dev, const uint8_t* joint_flags_dev, int32_t views, int64_t rows,
+                          int32_t num_keypoints, int32_t min_joints, double* partial_dev, void* stream);
+int uu3d_view_position_sums(const float* poses_dev, const float* kp2d_dev, const uint8_t* joint_flags_dev, int32_t views, int64_t rows,
+                            int32_t num_keypoints, const double* intrinsics_dev, int32_t min_joints, const double* pose_dev, double* partial_dev,
+                            void* stream);
+int uu3d_solve_view_pose(const double* partial_dev, int32_t views, int64_t chunks, int32_t stage, int32_t min_terms, const double* pose_in_dev,
+                         double* pose_out_dev, int32_t* terms_dev, void* stream);
+
+/*
  * ANY FRAME RATE (predict.predict_tracks(fps=...)): the front of YOUR OWN 2D TRACKS for tracks that were not filmed at the rate the model
  * was trained for.  The table holds the MODEL's time grid: row `row` (track row_track_dev[row]) is model frame k of its track, which sits at
  * source position p_k = k * fps / model_fps.  The host works the positions out in exact integer arithmetic (predict.resample_plan) and

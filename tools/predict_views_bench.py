@@ -14,7 +14,12 @@ clock offsets 0 / -3 / +5, and 16 tracks of 2500 frames at ``max_lag`` 50) besid
 host route: the call without it with ``return_views=True``, ``.cpu()``, then ``fuse_views_host``, ``triangulate_joints_host``,
 ``place_joints_host``, ``solve_view_roots_host`` and ``root_trajectory_host``.
 
-    python tools/predict_views_bench.py [--config h36m_81] [--persons 2] [--frames 1000] [--match | --align [--max_lag 50] | --triangulate]
+``--calibrate`` times ``predict_views(calibrate=True)`` (3 cameras without extrinsics, 0.5 px of pixel noise) beside the call on the
+cameras it returns, and ``calibrate_views`` on that call's lifts and keypoints beside ``calibrate_views_host`` (the mirror once).  With
+seeded weights the lifts are not poses, so the cameras found are not the true ones: only the time is read.
+
+    python tools/predict_views_bench.py [--config h36m_81] [--persons 2] [--frames 1000]
+                                        [--match | --align [--max_lag 50] | --triangulate | --calibrate]
 """
 import argparse
 import json
@@ -225,6 +230,49 @@ def _triangulate_rows(model, cfg, args):
                  placed_share=round(float((b[3] > 0).mean()), 4))]
 
 
+def _calibrate_rows(model, cfg, args):
+    import torch
+    from uplift_upsample_3dhpe_amd import predict
+    J, N, T, V = int(cfg.NUM_KEYPOINTS), max(args.persons, 1), args.frames, 3
+    kw = dict(resolutions=(1024, 1024))
+    true = _cameras(V)
+    bare = [c.without(extrinsics=True) for c in true]
+    rng = np.random.default_rng(3)
+    views = [[(t + rng.normal(0.0, 0.5, t.shape)).astype(np.float32) for t in tracks] for tracks in _views(true, N, T, J)]
+    found = predict.predict_views(model, cfg, views, bare, calibrate=True, **kw)
+    cams, calibration = found[-2], found[-1]
+
+    def with_stage():
+        return [torch.cat(r, 0).cpu() for r in predict.predict_views(model, cfg, views, bare, calibrate=True, **kw)[:-2]]
+
+    def on_returned():
+        return [torch.cat(r, 0).cpu() for r in predict.predict_views(model, cfg, views, cams, **kw)]
+
+    with_stage(), on_returned()
+    a, b = with_stage(), on_returned()
+    same = all(np.array_equal(x.numpy().view(np.uint8), y.numpy().view(np.uint8)) for x, y in zip(a, b))
+    rows = [dict(row="predict_views(calibrate=True)", views=V, persons=N, frames=T, joints=J, with_calibrate_ms=round(_median(with_stage), 2),
+                 on_returned_cameras_ms=round(_median(on_returned), 2), bits_equal=bool(same), states=[s for s, _ in calibration],
+                 terms=[n for _, n in calibration])]
+    # the stage alone, on the lifts (camera axes) and the keypoints of a call: the per-view lifts of return_views, taken back by each camera
+    lifts = predict.predict_views(model, cfg, views, cams, return_views=True, **kw)[-1]
+    poses = torch.stack([torch.cat(per_view, 0) for per_view in lifts]).contiguous()      # world axes of the cameras found: any axes time alike
+    kp = torch.stack([torch.cat([torch.from_numpy(t) for t in tracks], 0) for tracks in views]).cuda().contiguous()
+
+    def device():
+        pose, terms = predict.calibrate_views(poses, kp, bare)
+        return pose.cpu(), terms.cpu()
+
+    device()
+    got = device()
+    t0 = time.perf_counter()
+    want = predict.calibrate_views_host(poses.cpu().numpy(), kp.cpu().numpy(), bare)
+    host_ms = (time.perf_counter() - t0) * 1e3
+    rows.append(dict(row="calibrate_views", views=V, rows=N * T, joints=J, device_ms=round(_median(device), 3), mirror_ms_once=round(host_ms, 1),
+                     bits_equal=bool(np.array_equal(got[0].numpy().view(np.uint8), want[0].view(np.uint8)) and np.array_equal(got[1].numpy(), want[1]))))
+    return rows
+
+
 def _median(fn, n=3):
     import torch
     times = []
@@ -245,6 +293,7 @@ def main(argv=None):
     p.add_argument("--match", action="store_true", help="time predict_views(match=True) and match_views instead")
     p.add_argument("--align", action="store_true", help="time align_views and predict_views(align=True) instead")
     p.add_argument("--triangulate", action="store_true", help="time predict_views(triangulate=True) beside the call without it and the host route")
+    p.add_argument("--calibrate", action="store_true", help="time predict_views(calibrate=True) beside the call on the returned cameras, and calibrate_views beside its mirror")
     p.add_argument("--max_lag", type=int, default=50, help="the largest clock offset looked for with --align, in frames")
     args = p.parse_args(argv)
     import torch
@@ -262,6 +311,9 @@ def main(argv=None):
         return 0
     if args.triangulate:
         print(json.dumps(dict(config=args.config, rows=_triangulate_rows(model, cfg, args))))
+        return 0
+    if args.calibrate:
+        print(json.dumps(dict(config=args.config, rows=_calibrate_rows(model, cfg, args))))
         return 0
     J, N = int(cfg.NUM_KEYPOINTS), args.persons
     kw = dict(resolutions=(1024, 1024))

@@ -50,7 +50,10 @@ every name is importable from here as before:
                   ``predict_views(..., align=True)`` / ``align_views`` / ``crop_views`` (uu3d_view_lag_sums, uu3d_view_offsets;
                   ``view_lag_sums``, ``view_offsets`` and their ``_host`` mirrors, ``AlignViews``); where rays meet:
                   ``predict_views(..., triangulate=True)`` (uu3d_triangulate_joints, uu3d_place_joints; ``triangulate_joints``,
-                  ``place_joints`` and their ``_host`` mirrors, ``Triangulate``)
+                  ``place_joints`` and their ``_host`` mirrors, ``Triangulate``); where the cameras stand:
+                  ``predict_views(..., calibrate=True)`` / ``calibrate_views`` / ``calibrated_cameras`` (uu3d_view_moment_sums,
+                  uu3d_view_position_sums, uu3d_solve_view_pose; ``view_moment_sums``, ``view_position_sums``, ``solve_view_pose`` and their
+                  ``_host`` mirrors, ``calibrate_views_host``, ``CalibrateViews``)
 """
 import argparse
 import types
@@ -89,6 +92,8 @@ from .views import (ALIGN_DEFAULTS, MATCH_DEFAULTS, MATCH_LANES, MAX_ALIGN_LAG, 
                     gather_view_tracks_host, group_views, group_views_host, match_views, match_views_host, place_joints, place_joints_host,
                     predict_views, solve_view_roots, solve_view_roots_host, triangulate_joints, triangulate_joints_host, view_lag_sums,
                     view_lag_sums_host, view_offsets, view_offsets_host, view_pair_sums, view_pair_sums_host, view_rows)
+from .views import (VIEW_CALIBRATE_DEFAULTS, CalibrateViews, calibrate_views, calibrate_views_host, calibrated_cameras, check_calibrate,  # noqa: F401
+                    solve_view_pose, solve_view_pose_host, view_moment_sums, view_moment_sums_host, view_position_sums, view_position_sums_host)
 from .validity import (_device_joint_flags, _device_valid, _front_validity, _source_joint_flags, check_repair_joints, check_valid,  # noqa: F401
                        repair_joints, repair_joints_host)
 

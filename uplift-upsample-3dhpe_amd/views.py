@@ -55,8 +55,25 @@ three views and an outlier the honest view can be the one dropped; the lines are
 stays relative to the root, not to its triangulated parent, so bones across the seam can stretch (``bones`` fixes lengths behind the
 stage).  ``TRIANGULATE_DEFAULTS`` are conveniences, not tuned values.
 
-Out of scope: sub-frame offsets and per-camera frame rates, per-view confidence weights, estimating extrinsics, a live form, command-line
-flags.  No accuracy is claimed."""
+Where the cameras stand -- ``predict_views(..., calibrate=True)`` / ``calibrate_views`` / ``calibrated_cameras``: everything above needs
+every camera's extrinsics, and nobody who puts two phones and a webcam on tripods has them.  With ``calibrate`` cameras 1 .. V - 1 come
+without extrinsics (camera 0 may keep its own, which then define the world; without, the world is camera 0's own space), and behind step
+1, in front of step 2,
+  1a. uu3d_view_moment_sums sums p_v (x) p_0 over the rows view 0 and view v both see -- every view's lift is the same skeleton in that
+      camera's own axes, so the rotation between two cameras is the rotation between their lifts (``view_moment_sums_host``),
+  1b. uu3d_solve_view_pose takes the quaternion from Horn's 4 x 4 matrix by a fixed number of Jacobi sweeps (``solve_view_pose_host``),
+  1c. uu3d_view_position_sums adds, per row, both cameras' normal equations of the root solve with the row's unknown root eliminated --
+      the rays and the lifts' metric size fix where the second camera stands (``view_position_sums_host``),
+  1d. uu3d_solve_view_pose, its second stage, solves the 3 x 3 system for the position,
+  1e. ONE small copy (V x 9 float64: quaternion, position, state, terms) tells the host the poses: ``Camera`` is a host object, and every
+      buffer behind it is shaped by it.
+The rig comes out at the MODEL's scale: lifts scaled by s put every camera s times too far away, and ``bones`` with known lengths, which
+runs behind the stage, does not rescale it.  Calibration is against view 0 only, without chaining through a third camera; every term has
+unit weight in an algebraic error, so near and far frames count alike; a person who only stands still fixes the position poorly; the
+view-dependent depth errors of real lifts are not modelled.  ``VIEW_CALIBRATE_DEFAULTS`` is a convenience, not a tuned value.
+
+Out of scope: sub-frame offsets and per-camera frame rates, per-view confidence weights, rescaling a calibrated rig to known lengths,
+calibration chained through a third camera, estimating intrinsics, a live form, command-line flags.  No accuracy is claimed."""
 import ctypes as C
 
 import numpy as np
@@ -77,6 +94,12 @@ MAX_ALIGN_LAG = 512                                                    # kAlignM
 ALIGN_DEFAULTS = dict(max_lag=50, min_terms=50)                        # conveniences for 50 Hz and metres, not tuned values
 MIN_TRIANGULATE_VIEWS = 2                                              # kTriangulateMinViews: two lines meet in a point, one does not
 TRIANGULATE_DEFAULTS = dict(max_residual=8.0, min_views=2)             # pixels of the tracks as given; conveniences, not tuned values
+VIEW_CALIBRATE_DEFAULTS = dict(min_terms=50)                           # rows view 0 and a view must both see; a convenience, not a tuned value
+CALIBRATE_CHUNK = 4096                                                 # kCalibrateChunk: rows per workgroup, part of the rule's order of summation
+CALIBRATE_SUMS = 10                                                    # kCalibrateSums: nine sums and the number of terms per (view, chunk)
+CALIBRATE_SWEEPS = 10                                                  # kCalibrateSweeps: cyclic Jacobi sweeps of the 4 x 4, no early exit
+CALIBRATE_POSE = 8                                                     # kCalibratePose: the quaternion, the position, the state
+CALIBRATE_GAP = 2.0 ** -20                                             # kCalibrateGap: the two largest eigenvalues must differ by this share
 
 
 def check_view_cameras(cameras, views=None):
@@ -520,6 +543,461 @@ def place_joints(fused, points, count, root=0):
         _capi.check(lib, lib.uu3d_place_joints(_ptr(fused), _ptr(points), _ptr(count), R, J, root, _ptr(placed), _ptr(joint_views), C.c_void_p(stream)),
                     None)
     return placed, joint_views
+
+
+# ---- where the cameras stand: every view's pose against view 0 from lifts and rays (include/uu3d.h, WHERE THE CAMERAS STAND) -------------
+class CalibrateViews(object):
+    """The parameter of ``predict_views(calibrate=...)`` / ``calibrate_views``: ``min_terms``, the least number of rows (frames) view 0
+    and a view must both see for that view to be calibrated (an int >= 1).  The default is a convenience, not a tuned value."""
+
+    def __init__(self, min_terms=VIEW_CALIBRATE_DEFAULTS["min_terms"]):
+        self.min_terms = _calibrate_parameters(min_terms)
+
+    def __repr__(self):
+        return f"CalibrateViews(min_terms={self.min_terms!r})"
+
+
+def _calibrate_parameters(min_terms):
+    if isinstance(min_terms, (bool, np.bool_)) or not isinstance(min_terms, (int, np.integer)) or not 1 <= int(min_terms) < 2 ** 31:
+        raise ValueError(f"min_terms must be an int >= 1, got {min_terms!r}")
+    return int(min_terms)
+
+
+def check_calibrate(calibrate):
+    """``predict_views(calibrate=...)`` -> None (every camera comes with extrinsics) or a ``CalibrateViews``; True is the defaults."""
+    if calibrate is None:
+        return None
+    if calibrate is True:
+        return CalibrateViews()
+    if not isinstance(calibrate, CalibrateViews):
+        raise ValueError(f"calibrate must be None, True or a CalibrateViews(min_terms=), got {calibrate!r}")
+    return calibrate
+
+
+def check_calibrate_cameras(cameras, views=None):
+    """``cameras`` of ``predict_views(calibrate=...)`` -> the list of V ``Camera`` objects: intrinsics, with or without distortion; camera 0
+    with or without extrinsics (with: they define the world; without: the world is camera 0's own space), cameras 1 .. V - 1 WITHOUT --
+    extrinsics on one of them is a ValueError that names it, since the call is there to find them."""
+    if not isinstance(cameras, (list, tuple)) or not all(isinstance(c, Camera) for c in cameras):
+        raise ValueError("calibrate: cameras must be a list of Camera objects (intrinsics, distortion or none), one per view, not plain "
+                         "(fx, fy, cx, cy) tuples or a mix")
+    if not 1 <= len(cameras) <= MAX_VIEWS:
+        raise ValueError(f"cameras: between 1 and {MAX_VIEWS} views are taken, got {len(cameras)}")
+    for v, c in enumerate(cameras):
+        if v > 0 and c.has_extrinsics:
+            raise ValueError(f"calibrate: camera {v} comes with extrinsics (orientation=, translation=); only camera 0 may, and they then define "
+                             f"the world -- pass the others without, or call without calibrate")
+    if views is not None and len(cameras) != int(views):
+        raise ValueError(f"cameras must hold one Camera per view ({int(views)}), got {len(cameras)}")
+    return list(cameras)
+
+
+def _with_identity(camera):
+    """A copy of ``camera`` that stands at the origin of the world and looks along its axes."""
+    fx, fy, cx, cy = camera.intrinsics
+    return Camera(fx, fy, cx, cy, distortion=camera.distortion, tol=camera.tol, orientation=(1.0, 0.0, 0.0, 0.0), translation=(0.0, 0.0, 0.0))
+
+
+def calibrated_cameras(cameras, pose):
+    """The cameras ``predict_views(calibrate=...)`` returns, on the host: ``cameras`` as ``check_calibrate_cameras`` takes them; ``pose``
+    (V, 8) float64 of ``calibrate_views`` / ``calibrate_views_host`` (the state is not looked at) -> V ``Camera`` objects with extrinsics.
+    Camera 0 without extrinsics: it gets the identity pose, and camera v orientation q_v and translation c_v as they are.  Camera 0 with
+    extrinsics (q_0, t_0): it is returned as it is, and camera v gets the Hamilton product q_0 q_v, every component a sum of four products
+    added left to right, and ``_rotate_f64(q_0, c_v) + t_0``, in float64.  ``Camera`` normalises the quaternion once more."""
+    cams = check_calibrate_cameras(cameras)
+    rows = np.asarray(_host_array(pose), np.float64)
+    if rows.shape != (len(cams), 8):
+        raise ValueError(f"pose must be ({len(cams)}, 8), got {rows.shape}")
+    first = cams[0] if cams[0].has_extrinsics else _with_identity(cams[0])
+    out = [first]
+    for v in range(1, len(cams)):
+        q, c = rows[v, :4], rows[v, 4:7]
+        if cams[0].has_extrinsics:
+            w0, x0, y0, z0 = (np.float64(a) for a in first.orientation)
+            w1, x1, y1, z1 = q
+            q = np.array([((w0 * w1 - x0 * x1) - y0 * y1) - z0 * z1, ((w0 * x1 + x0 * w1) + y0 * z1) - z0 * y1,
+                          ((w0 * y1 - x0 * z1) + y0 * w1) + z0 * x1, ((w0 * z1 + x0 * y1) - y0 * x1) + z0 * w1], np.float64)
+            c = np.array(_rotate_f64((w0, x0, y0, z0), c[0], c[1], c[2]), np.float64) + first.translation
+        fx, fy, cx, cy = cams[v].intrinsics
+        out.append(Camera(fx, fy, cx, cy, distortion=cams[v].distortion, tol=cams[v].tol, orientation=q, translation=c))
+    return out
+
+
+def _intrinsic_rows(cameras, V):
+    """V ``Camera`` objects (any extrinsics), or their (V, 4) rows already -> (V, 4) float64: fx, fy, cx, cy."""
+    if isinstance(cameras, np.ndarray):
+        rows = np.ascontiguousarray(cameras, np.float64)
+    else:
+        if not isinstance(cameras, (list, tuple)) or not all(isinstance(c, Camera) for c in cameras):
+            raise ValueError("cameras must be a list of Camera objects, one per view, or their (V, 4) rows fx, fy, cx, cy")
+        rows = np.ascontiguousarray(np.array([c.intrinsics for c in cameras], np.float64).reshape(len(cameras), 4))
+    if rows.shape != (V, 4):
+        raise ValueError(f"cameras must hold one camera per view ({V}), got {rows.shape[0] if rows.ndim else 0}")
+    return rows
+
+
+def calibrate_chunks(rows):
+    """The chunks of ``CALIBRATE_CHUNK`` rows the sums of WHERE THE CAMERAS STAND are cut into."""
+    return (int(rows) + CALIBRATE_CHUNK - 1) // CALIBRATE_CHUNK
+
+
+def _chunk_sums(values, term):
+    """The order of summation of WHERE THE CAMERAS STAND: ``values`` (R, 10) float64, ``term`` (R,) bool -> (C, 10) float64.  Per chunk of
+    4096 rows, lane l of 256 adds the values of the terms among its rows l, l + 256, ... ascending to 0.0, then the fixed tree."""
+    R = values.shape[0]
+    out = np.zeros((calibrate_chunks(R), CALIBRATE_SUMS), np.float64)
+    with np.errstate(all="ignore"):
+        for c in range(out.shape[0]):
+            x = np.zeros((MATCH_LANES, CALIBRATE_SUMS), np.float64)
+            for first in range(c * CALIBRATE_CHUNK, min(R, (c + 1) * CALIBRATE_CHUNK), MATCH_LANES):
+                part, t = values[first:first + MATCH_LANES], term[first:first + MATCH_LANES]
+                x[:len(part)] = np.where(t[:, None], x[:len(part)] + part, x[:len(part)])
+            stride = MATCH_LANES // 2
+            while stride >= 1:                                           # the fixed tree
+                x[:stride] = x[:stride] + x[stride:2 * stride]
+                stride //= 2
+            out[c] = x[0]
+    return out
+
+
+def _calibrate_arrays(poses, kp2d, flags, min_root_joints):
+    P, uv, used = _view_arrays(poses, kp2d, flags, False)
+    m = check_min_root_joints(min_root_joints)
+    if not 1 <= P.shape[1] < 2 ** 31:
+        raise ValueError(f"between 1 and 2^31 - 1 rows are taken, got {P.shape[1]}")
+    return P.astype(np.float64), uv.astype(np.float64), used, used.sum(axis=2) >= m
+
+
+def view_moment_sums_host(poses, kp2d, flags=None, min_root_joints=DEFAULT_MIN_ROOT_JOINTS):
+    """The rotation sums of WHERE THE CAMERAS STAND (include/uu3d.h) in numpy, written to be read: what uu3d_view_moment_sums computes, bit
+    for bit.  ``poses`` (V, R, J, 3): every view's lift of every row, root-relative, in that camera's OWN axes (read as float32); ``kp2d``
+    (V, R, J, 2) and ``flags`` None or (V, R, J) as ``fuse_views_host`` takes them -> partial (V, C, 10) float64, C = ``calibrate_chunks(R)``.
+    View v SEES row r iff at least ``min_root_joints`` of its joints are used there (``fuse_views_host``); row r is a TERM of view v >= 1
+    iff view 0 and view v both see it.  A term's values: s_ik = 0.0; s_ik = s_ik + p_v[j][i] * p_0[j][k] over ALL J joints ascending (an
+    unobserved joint's lift is still read), ik = 00, 01, 02, 10, ..., 22, and 1.0 as the tenth.  The order of summation is fixed: chunks of
+    ``CALIBRATE_CHUNK`` = 4096 rows; in a chunk lane l of ``MATCH_LANES`` = 256 adds the values of the terms among its rows l, l + 256, ...
+    ascending to 0.0; then for stride = 128, 64, ..., 1: x[l] = x[l] + x[l + stride] for l < stride.  View 0's partials are zeros."""
+    P, _, _, sees = _calibrate_arrays(poses, kp2d, flags, min_root_joints)
+    V, R, J = P.shape[:3]
+    out = np.zeros((V, calibrate_chunks(R), CALIBRATE_SUMS), np.float64)
+    with np.errstate(all="ignore"):
+        for v in range(1, V):
+            s = np.zeros((R, CALIBRATE_SUMS), np.float64)
+            for j in range(J):
+                for i in range(3):
+                    for k in range(3):
+                        s[:, 3 * i + k] = s[:, 3 * i + k] + P[v, :, j, i] * P[0, :, j, k]
+            s[:, 9] = 1.0
+            out[v] = _chunk_sums(s, sees[0] & sees[v])
+    return out
+
+
+def _normal_sums(uv, used, lift, intrinsics, axes):
+    """One view's normal equations of every row: ``uv`` (R, J, 2), ``used`` (R, J), ``lift`` (R, J, 3) float64, ``axes`` nine doubles r1, r2,
+    r3 -> (A (6, R), B (3, R)); the statements of ``solve_view_roots_host`` with e = n . P_j and g = m . P_j."""
+    fx, fy, cx, cy = intrinsics
+    R, J = used.shape
+    a00, a01, a02, a11, a12, a22, b0, b1, b2 = (np.zeros(R, np.float64) for _ in range(9))
+    for j in range(J):
+        a = (uv[:, j, 0] - cx) / fx
+        b = (uv[:, j, 1] - cy) / fy
+        n0, n1, n2 = axes[0] - a * axes[6], axes[1] - a * axes[7], axes[2] - a * axes[8]
+        m0, m1, m2 = axes[3] - b * axes[6], axes[4] - b * axes[7], axes[5] - b * axes[8]
+        e = (n0 * lift[:, j, 0] + n1 * lift[:, j, 1]) + n2 * lift[:, j, 2]
+        g = (m0 * lift[:, j, 0] + m1 * lift[:, j, 1]) + m2 * lift[:, j, 2]
+        u = used[:, j]
+        a00 = np.where(u, a00 + (n0 * n0 + m0 * m0), a00)
+        a01 = np.where(u, a01 + (n0 * n1 + m0 * m1), a01)
+        a02 = np.where(u, a02 + (n0 * n2 + m0 * m2), a02)
+        a11 = np.where(u, a11 + (n1 * n1 + m1 * m1), a11)
+        a12 = np.where(u, a12 + (n1 * n2 + m1 * m2), a12)
+        a22 = np.where(u, a22 + (n2 * n2 + m2 * m2), a22)
+        b0 = np.where(u, b0 + (n0 * e + m0 * g), b0)
+        b1 = np.where(u, b1 + (n1 * e + m1 * g), b1)
+        b2 = np.where(u, b2 + (n2 * e + m2 * g), b2)
+    return (a00, a01, a02, a11, a12, a22), (b0, b1, b2)
+
+
+def _cofactors(a00, a01, a02, a11, a12, a22):
+    """The cofactor statements of ``solve_view_roots_host`` -> (c00, c01, c02, c11, c12, c22, det)."""
+    c00 = a11 * a22 - a12 * a12
+    c01 = a02 * a12 - a01 * a22
+    c02 = a01 * a12 - a02 * a11
+    c11 = a00 * a22 - a02 * a02
+    c12 = a01 * a02 - a00 * a12
+    c22 = a00 * a11 - a01 * a01
+    return c00, c01, c02, c11, c12, c22, (a00 * c00 + a01 * c01) + a02 * c02
+
+
+def _pose_rows(pose, V):
+    rows = np.asarray(_host_array(pose), np.float64)
+    if rows.shape != (V, CALIBRATE_POSE):
+        raise ValueError(f"pose must be ({V}, {CALIBRATE_POSE}), got {rows.shape}")
+    return rows
+
+
+def view_position_sums_host(poses, kp2d, cameras, pose, flags=None, min_root_joints=DEFAULT_MIN_ROOT_JOINTS):
+    """The position sums of WHERE THE CAMERAS STAND (include/uu3d.h) in numpy, written to be read: what uu3d_view_position_sums computes, bit
+    for bit.  ``poses``, ``kp2d``, ``flags`` as ``view_moment_sums_host`` takes them; ``cameras``: V ``Camera`` objects, read for their
+    intrinsics (or (V, 4) rows fx, fy, cx, cy); ``pose`` (V, 8) float64: the rows of ``solve_view_pose_host``'s first stage
+    -> partial (V, C, 10) float64.
+    Per term (a row view 0 and view v both see) and per view u in {0, v}, over u's used joints ascending:
+        a = (u - cx) / fx;  b = (v - cy) / fy;  n_i = r1_i - a r3_i;  m_i = r2_i - b r3_i
+        e = (n0 P0 + n1 P1) + n2 P2;  g = (m0 P0 + m1 P1) + m2 P2;  A_ik += (n_i n_k + m_i m_k);  B_i += (n_i e + m_i g)
+    with, for view 0, r1, r2, r3 = e_1, e_2, e_3 and P the view's own lift, and for view v r_i = ``_rotate_f64(q_v, e_i)`` and
+    P = ``_rotate_f64(q_v, lift)``.  The row's root T obeys A0 T = -B0 and Av (T - c) = -Bv, c the camera's position; T is eliminated:
+        A = A0 + Av; its cofactors and det by ``solve_view_roots_host``'s statements; det not finite, not > 0 or not above
+        ``VIEW_RANK`` ((A00 A11) A22): the row is not a term.  K_ik = c_ik / det
+        W_ik = (Av_i0 K_0k + Av_i1 K_1k) + Av_i2 K_2k, all nine
+        S_ik = Av_ik - ((W_i0 Av_0k + W_i1 Av_1k) + W_i2 Av_2k) for ik = 00, 01, 02, 11, 12, 22
+        h = B0 + Bv;  g_i = Bv_i - ((W_i0 h0 + W_i1 h1) + W_i2 h2)
+    The ten values S (6), g (3) and 1.0 go through the order of summation of ``view_moment_sums_host``.  View 0, a view whose state is not
+    1 and a view whose (or view 0's) intrinsics are not finite with fx, fy > 0 hold zeros."""
+    P, uv, used, sees = _calibrate_arrays(poses, kp2d, flags, min_root_joints)
+    V, R, J = P.shape[:3]
+    intr = _intrinsic_rows(cameras, V)
+    rows = _pose_rows(pose, V)
+    out = np.zeros((V, calibrate_chunks(R), CALIBRATE_SUMS), np.float64)
+    one, zero = np.float64(1.0), np.float64(0.0)
+    fine = np.isfinite(intr).all(axis=1) & (intr[:, 0] > 0) & (intr[:, 1] > 0)
+    with np.errstate(all="ignore"):
+        A0, B0 = _normal_sums(uv[0], used[0], P[0], intr[0], [one, zero, zero, zero, one, zero, zero, zero, one])
+        for v in range(1, V):
+            if rows[v, 7] != 1.0 or not fine[0] or not fine[v]:
+                continue
+            q = [np.float64(a) for a in rows[v, :4]]
+            axes = [a for e in ((one, zero, zero), (zero, one, zero), (zero, zero, one)) for a in _rotate_f64(q, *e)]
+            turned = np.stack(_rotate_f64(q, P[v, :, :, 0], P[v, :, :, 1], P[v, :, :, 2]), axis=-1)
+            Av, Bv = _normal_sums(uv[v], used[v], turned, intr[v], axes)
+            a = [x + y for x, y in zip(A0, Av)]
+            c00, c01, c02, c11, c12, c22, det = _cofactors(*a)
+            term = sees[0] & sees[v] & np.isfinite(det) & (det > 0) & (det > VIEW_RANK * ((a[0] * a[3]) * a[5]))
+            k00, k01, k02, k11, k12, k22 = c00 / det, c01 / det, c02 / det, c11 / det, c12 / det, c22 / det
+            v00, v01, v02, v11, v12, v22 = Av
+            w00 = (v00 * k00 + v01 * k01) + v02 * k02
+            w01 = (v00 * k01 + v01 * k11) + v02 * k12
+            w02 = (v00 * k02 + v01 * k12) + v02 * k22
+            w10 = (v01 * k00 + v11 * k01) + v12 * k02
+            w11 = (v01 * k01 + v11 * k11) + v12 * k12
+            w12 = (v01 * k02 + v11 * k12) + v12 * k22
+            w20 = (v02 * k00 + v12 * k01) + v22 * k02
+            w21 = (v02 * k01 + v12 * k11) + v22 * k12
+            w22 = (v02 * k02 + v12 * k12) + v22 * k22
+            h0, h1, h2 = B0[0] + Bv[0], B0[1] + Bv[1], B0[2] + Bv[2]
+            s = np.stack([v00 - ((w00 * v00 + w01 * v01) + w02 * v02),
+                          v01 - ((w00 * v01 + w01 * v11) + w02 * v12),
+                          v02 - ((w00 * v02 + w01 * v12) + w02 * v22),
+                          v11 - ((w10 * v01 + w11 * v11) + w12 * v12),
+                          v12 - ((w10 * v02 + w11 * v12) + w12 * v22),
+                          v22 - ((w20 * v02 + w21 * v12) + w22 * v22),
+                          Bv[0] - ((w00 * h0 + w01 * h1) + w02 * h2),
+                          Bv[1] - ((w10 * h0 + w11 * h1) + w12 * h2),
+                          Bv[2] - ((w20 * h0 + w21 * h1) + w22 * h2),
+                          np.ones(R, np.float64)], axis=1)
+            out[v] = _chunk_sums(s, term)
+    return out
+
+
+_JACOBI_PAIRS = ((0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3))
+
+
+def horn_matrix(M):
+    """Horn's symmetric 4 x 4 matrix of M = sum of p_v (x) p_0, nine doubles M00, M01, ..., M22 -> (4, 4) float64: its largest eigenvector
+    is the quaternion (w, x, y, z) that turns the p_v onto the p_0."""
+    m00, m01, m02, m10, m11, m12, m20, m21, m22 = (np.float64(a) for a in M)
+    N = np.zeros((4, 4), np.float64)
+    with np.errstate(all="ignore"):
+        N[0, 0], N[0, 1], N[0, 2], N[0, 3] = (m00 + m11) + m22, m12 - m21, m20 - m02, m01 - m10
+        N[1, 1], N[1, 2], N[1, 3] = (m00 - m11) - m22, m01 + m10, m20 + m02
+        N[2, 2], N[2, 3] = (m11 - m00) - m22, m12 + m21
+        N[3, 3] = (m22 - m00) - m11
+    return N + np.triu(N, 1).T
+
+
+def jacobi_eigen4(N, sweeps=None):
+    """Cyclic Jacobi on a symmetric (4, 4) float64 matrix, ``CALIBRATE_SWEEPS`` sweeps (or ``sweeps``) without an early exit, the pairs in
+    the order (0,1) (0,2) (0,3) (1,2) (1,3) (2,3), every operation rounded once -> (eigenvalues (4,), eigenvectors (4, 4), a column each).
+    A rotation in the plane (p, q): th = (Nqq - Npp) / (2.0 Npq); tt = (1.0 if th >= 0.0 else -1.0) / (|th| + sqrt(th th + 1.0)); t = 0.0
+    if Npq == 0.0 else tt; c = 1.0 / sqrt(t t + 1.0); s = t c; Npp = Npp - t Npq; Nqq = Nqq + t Npq; Npq = 0.0; for the two other indices
+    r: (Nrp, Nrq) = (c Nrp - s Nrq, s Nrp + c Nrq); for every row i of E the same."""
+    b = np.array(N, np.float64)
+    E = np.eye(4, dtype=np.float64)
+    two, one = np.float64(2.0), np.float64(1.0)
+    with np.errstate(all="ignore"):
+        for _ in range(CALIBRATE_SWEEPS if sweeps is None else int(sweeps)):
+            for p, q in _JACOBI_PAIRS:
+                bpq = b[min(p, q), max(p, q)]
+                th = (b[q, q] - b[p, p]) / (two * bpq)
+                tt = (one if th >= 0.0 else -one) / (np.abs(th) + np.sqrt(th * th + one))
+                t = np.float64(0.0) if bpq == 0.0 else tt
+                c = one / np.sqrt(t * t + one)
+                s = t * c
+                b[p, p] = b[p, p] - t * bpq
+                b[q, q] = b[q, q] + t * bpq
+                b[p, q] = b[q, p] = 0.0
+                for r in range(4):
+                    if r in (p, q):
+                        continue
+                    x, y = b[r, p], b[r, q]
+                    b[r, p] = b[p, r] = c * x - s * y
+                    b[r, q] = b[q, r] = s * x + c * y
+                for i in range(4):
+                    x, y = E[i, p], E[i, q]
+                    E[i, p] = c * x - s * y
+                    E[i, q] = s * x + c * y
+    return np.diag(b).copy(), E
+
+
+def solve_view_pose_host(sums, pose=None, min_terms=VIEW_CALIBRATE_DEFAULTS["min_terms"], sweeps=None):
+    """The two solves of WHERE THE CAMERAS STAND (include/uu3d.h) in numpy, written to be read: what uu3d_solve_view_pose computes, bit for
+    bit.  ``sums`` (V, C, 10) float64: the partials of ``view_moment_sums_host`` (``pose`` None: the first stage) or of
+    ``view_position_sums_host`` (``pose``: the first stage's rows: the second stage) -> (pose (V, 8) float64: the quaternion (w, x, y, z),
+    the position, the state as 1.0 / 0.0; terms (V,) int32: the terms of the sums).  A view's chunks are added ascending to 0.0.
+    FIRST STAGE.  ``horn_matrix`` of the nine sums, ``jacobi_eigen4``, the column e of the largest eigenvalue (ties: the smaller index),
+    len = sqrt(((e0 e0 + e1 e1) + e2 e2) + e3 e3), q = e / len, negated as a whole when q0 < 0.0; X_0 = qrot(q, X_v).  The view is REFUSED
+    -- state 0, the identity quaternion -- when its terms are fewer than ``min_terms``, an eigenvalue or q is not finite, or
+    top - next > ``CALIBRATE_GAP`` |top| does not hold for the two largest eigenvalues: the lifts then do not fix a rotation.  Row 0 is the
+    identity, zeros and state 1; its terms are 0.
+    SECOND STAGE.  For a view whose state is 1: S c = g by the cofactors of ``solve_view_roots_host``, c_i = x_i / det; det not finite, not
+    > 0, not above ``VIEW_RANK`` ((S00 S11) S22), or c not finite: state 0 and zeros; the quaternion stays either way."""
+    S = np.asarray(_host_array(sums), np.float64)
+    if S.ndim != 3 or S.shape[2] != CALIBRATE_SUMS or not 1 <= S.shape[0] <= MAX_VIEWS or S.shape[1] < 1:
+        raise ValueError(f"sums must be (V, C, {CALIBRATE_SUMS}) with V <= {MAX_VIEWS} and C >= 1, got {S.shape}")
+    V = S.shape[0]
+    min_terms = _calibrate_parameters(min_terms)
+    x = np.zeros((V, CALIBRATE_SUMS), np.float64)
+    with np.errstate(all="ignore"):
+        for c in range(S.shape[1]):
+            x = x + S[:, c]
+    terms = x[:, 9].astype(np.int32)
+    out = np.zeros((V, CALIBRATE_POSE), np.float64)
+    if pose is not None:
+        out[:] = _pose_rows(pose, V)
+        with np.errstate(all="ignore"):
+            for v in range(1, V):
+                if out[v, 7] != 1.0:
+                    continue
+                a = [np.float64(t) for t in x[v, :6]]
+                b0, b1, b2 = (np.float64(t) for t in x[v, 6:9])
+                c00, c01, c02, c11, c12, c22, det = _cofactors(*a)
+                y0 = (c00 * b0 + c01 * b1) + c02 * b2
+                y1 = (c01 * b0 + c11 * b1) + c12 * b2
+                y2 = (c02 * b0 + c12 * b1) + c22 * b2
+                c = np.array([y0 / det, y1 / det, y2 / det], np.float64)
+                ok = np.isfinite(det) and det > 0 and det > VIEW_RANK * ((a[0] * a[3]) * a[5]) and np.isfinite(c).all()
+                out[v, 4:7] = c if ok else 0.0
+                out[v, 7] = 1.0 if ok else 0.0
+        return out, terms
+    out[:, 0] = 1.0
+    out[0, 7] = 1.0
+    with np.errstate(all="ignore"):
+        for v in range(1, V):
+            lam, E = jacobi_eigen4(horn_matrix(x[v, :9]), sweeps)
+            k = 0
+            for i in range(1, 4):
+                if lam[i] > lam[k]:
+                    k = i
+            nxt = -np.inf
+            for i in range(4):
+                if i != k and lam[i] > nxt:
+                    nxt = lam[i]
+            e = E[:, k]
+            q = e / np.sqrt(((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]) + e[3] * e[3])
+            if q[0] < 0.0:
+                q = -q
+            ok = int(terms[v]) >= min_terms and np.isfinite(lam).all() and np.isfinite(q).all() and bool(lam[k] - nxt > CALIBRATE_GAP * np.abs(lam[k]))
+            if ok:
+                out[v, :4], out[v, 7] = q, 1.0
+    return out, terms
+
+
+def calibrate_views_host(poses, kp2d, cameras, flags=None, min_root_joints=DEFAULT_MIN_ROOT_JOINTS, min_terms=VIEW_CALIBRATE_DEFAULTS["min_terms"]):
+    """``calibrate_views`` built from the mirrors -- ``view_moment_sums_host``, ``solve_view_pose_host``, ``view_position_sums_host``,
+    ``solve_view_pose_host`` once more -- on host arrays -> (pose (V, 8) float64, terms (V,) int32: the rows view 0 and the view both see)."""
+    first, terms = solve_view_pose_host(view_moment_sums_host(poses, kp2d, flags, min_root_joints), None, min_terms)
+    placed, _ = solve_view_pose_host(view_position_sums_host(poses, kp2d, cameras, first, flags, min_root_joints), first, min_terms)
+    return placed, terms
+
+
+def _calibrate_tensors(poses, kp2d, flags, min_root_joints):
+    V, R, J, flags = _view_tensors(poses, kp2d, flags, False)
+    if not 1 <= R < 2 ** 31:
+        raise ValueError(f"between 1 and 2^31 - 1 rows are taken, got {R}")
+    return V, R, J, flags, check_min_root_joints(min_root_joints)
+
+
+def view_moment_sums(poses, kp2d, flags=None, min_root_joints=DEFAULT_MIN_ROOT_JOINTS):
+    """uu3d_view_moment_sums on the current stream: ``view_moment_sums_host`` on device tensors, one launch, nothing copies to the host or
+    waits.  ``poses`` (V, R, J, 3) float32 and ``kp2d`` (V, R, J, 2) float32 on the device, contiguous (only read); ``flags`` (V, R, J)
+    uint8 / bool on the device or None -> partial (V, C, 10) float64, a fresh device buffer.  Needs no model."""
+    import torch
+    lib = _capi.load_library()
+    V, R, J, flags, m = _calibrate_tensors(poses, kp2d, flags, min_root_joints)
+    partial = torch.empty((V, calibrate_chunks(R), CALIBRATE_SUMS), dtype=torch.float64, device=kp2d.device)
+    with torch.cuda.device(kp2d.device):
+        stream = torch.cuda.current_stream(kp2d.device).cuda_stream
+        _capi.check(lib, lib.uu3d_view_moment_sums(_ptr(poses), _ptr(kp2d), _ptr(flags), V, R, J, m, _ptr(partial), C.c_void_p(stream)), None)
+    return partial
+
+
+def view_position_sums(poses, kp2d, cameras, pose, flags=None, min_root_joints=DEFAULT_MIN_ROOT_JOINTS):
+    """uu3d_view_position_sums on the current stream: ``view_position_sums_host`` on device tensors, one launch, nothing copies to the host
+    or waits (the V intrinsics go up pinned and asynchronously).  ``pose`` (V, 8) float64 on the device: the first stage of
+    ``solve_view_pose`` (only read) -> partial (V, C, 10) float64, a fresh device buffer.  Needs no model."""
+    import torch
+    lib = _capi.load_library()
+    V, R, J, flags, m = _calibrate_tensors(poses, kp2d, flags, min_root_joints)
+    dev = kp2d.device
+    if not _is_device(pose, torch.float64, dev) or tuple(pose.shape) != (V, CALIBRATE_POSE):
+        raise ValueError(f"pose must be a contiguous ({V}, {CALIBRATE_POSE}) float64 tensor on kp2d's device")
+    intr = _upload(_intrinsic_rows(cameras, V), np.float64, dev)
+    partial = torch.empty((V, calibrate_chunks(R), CALIBRATE_SUMS), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _capi.check(lib, lib.uu3d_view_position_sums(_ptr(poses), _ptr(kp2d), _ptr(flags), V, R, J, _ptr(intr), m, _ptr(pose), _ptr(partial),
+                                                     C.c_void_p(stream)), None)
+    return partial
+
+
+def solve_view_pose(sums, pose=None, min_terms=VIEW_CALIBRATE_DEFAULTS["min_terms"]):
+    """uu3d_solve_view_pose on the current stream: ``solve_view_pose_host`` on device tensors, one launch of one wave, nothing copies to
+    the host or waits.  ``sums`` (V, C, 10) float64 on the device, contiguous (only read); ``pose`` None (the first stage, on the moment
+    sums) or the first stage's (V, 8) float64 rows (the second stage, on the position sums; only read)
+    -> (pose (V, 8) float64, terms (V,) int32), fresh device buffers.  Needs no model."""
+    import torch
+    lib = _capi.load_library()
+    if not _is_device(sums, torch.float64) or sums.dim() != 3 or sums.shape[2] != CALIBRATE_SUMS or not 1 <= sums.shape[0] <= MAX_VIEWS or sums.shape[1] < 1:
+        raise ValueError(f"sums must be a contiguous (V, C, {CALIBRATE_SUMS}) float64 device tensor with V <= {MAX_VIEWS} and C >= 1, "
+                         f"got {tuple(getattr(sums, 'shape', ()))}")
+    V, chunks = int(sums.shape[0]), int(sums.shape[1])
+    dev = sums.device
+    if pose is not None and (not _is_device(pose, torch.float64, dev) or tuple(pose.shape) != (V, CALIBRATE_POSE)):
+        raise ValueError(f"pose must be None or a contiguous ({V}, {CALIBRATE_POSE}) float64 tensor on the sums' device")
+    min_terms = _calibrate_parameters(min_terms)
+    out = torch.empty((V, CALIBRATE_POSE), dtype=torch.float64, device=dev)
+    terms = torch.empty((V,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _capi.check(lib, lib.uu3d_solve_view_pose(_ptr(sums), V, chunks, 0 if pose is None else 1, min_terms, _ptr(pose), _ptr(out), _ptr(terms),
+                                                  C.c_void_p(stream)), None)
+    return out, terms
+
+
+def calibrate_views(poses, kp2d, cameras, flags=None, min_root_joints=DEFAULT_MIN_ROOT_JOINTS, min_terms=VIEW_CALIBRATE_DEFAULTS["min_terms"]):
+    """Where the cameras stand, on the device: the pose of views 1 .. V - 1 in the space of view 0 from every view's lifts and rays --
+    uu3d_view_moment_sums, uu3d_solve_view_pose, uu3d_view_position_sums, uu3d_solve_view_pose once more: four launches, nothing copies to
+    the host or waits.  ``poses`` (V, R, J, 3) float32: every view's lift of every row, root-relative, in that camera's OWN axes (the output
+    of the model, not taken to world axes); ``kp2d`` (V, R, J, 2) float32: the raw 2D keypoints in the model's layout, undistorted;
+    ``flags`` (V, R, J) uint8 / bool or None, all on the device, contiguous (only read); ``cameras``: V ``Camera`` objects, read for their
+    intrinsics (or (V, 4) rows).  The same row of every view is the same person at the same instant
+    -> (pose (V, 8) float64: per view the quaternion (w, x, y, z) and the position with X_0 = qrot(q, X_v) + c, and the state, 1.0 =
+    calibrated; terms (V,) int32: the rows view 0 and the view both see), fresh device buffers; ``calibrated_cameras`` turns the rows,
+    once on the host, into ``Camera`` objects.  The rules stand in the three mirrors; ``calibrate_views_host`` is the same call on the host,
+    and the two agree bit for bit.  The rig comes out at the model's scale, against view 0 only, every term with unit weight; a person who
+    stands still fixes the position poorly: no accuracy is claimed.  Needs no model."""
+    first, terms = solve_view_pose(view_moment_sums(poses, kp2d, flags, min_root_joints), None, min_terms)
+    placed, _ = solve_view_pose(view_position_sums(poses, kp2d, cameras, first, flags, min_root_joints), first, min_terms)
+    return placed, terms
 
 
 # ---- who is who: which track of one camera is which of another (include/uu3d.h, WHO IS WHO) ---------------------------------------------
@@ -1455,7 +1933,7 @@ def _fused_scene(pt, person, world, kp2d, flags, cams, lens, rates, model_fps, r
 def predict_views(model, config, views, cameras, resolutions=None, mask_stride=None, flip=None, reuse_frames=True, batch_size=None, depth=None,
                   graph=True, valid=None, fps=None, model_fps=50, repair_joints=None, keypoints=None, min_root_joints=DEFAULT_MIN_ROOT_JOINTS,
                   smooth=None, bones=None, rotations=None, interpolation="linear", return_views=False, keyframes_only=False, out_fps=None, match=None,
-                  align=None, triangulate=None):
+                  align=None, triangulate=None, calibrate=None):
     """One world scene from V calibrated views of the same N persons -> (poses, roots, root_state, view_count): per person ``poses``
     (T_i, J, 3) float32 in world axes and root-relative, ``roots`` (T_i, 3) float32 in world coordinates, ``root_state`` (T_i,) uint8 (1
     solved here, 2 interpolated or held, 0 no solved frame) and ``view_count`` (T_i,) uint8, the views that saw the frame; on the model's
@@ -1519,18 +1997,47 @@ def predict_views(model, config, views, cameras, resolutions=None, mask_stride=N
     ``view_count``: per person (T_i, J) uint8, the cameras that placed the joint, 0 where it is the lift; ``rotations``, ``return_views``
     (still the per-view lifts), ``person``, ``offsets`` and ``first`` follow as before.  One view is taken, and nothing is triangulated.
     The result equals, bit for bit, the host composition with ``triangulate_joints_host`` and ``place_joints_host`` behind
-    ``fuse_views_host``.  The limits stand in the module's docstring; the defaults are not tuned, and no accuracy is claimed."""
+    ``fuse_views_host``.  The limits stand in the module's docstring; the defaults are not tuned, and no accuracy is claimed.
+
+    Where the cameras stand -- ``calibrate``: None = the call above, the same launches, buffers, refusals and bits.  True
+    (``VIEW_CALIBRATE_DEFAULTS``) or a ``CalibrateViews(min_terms=)``; anything else is a ValueError.  ``cameras`` are V ``Camera`` objects
+    with intrinsics, each with or without distortion; cameras 1 .. V - 1 come WITHOUT extrinsics (one that has them is a ValueError that
+    names it), camera 0 may keep its own, which then define the world -- without, the world is camera 0's own space.  The same index is
+    the same person on one clock: ``match`` and an ``align`` that estimates (True, an ``AlignViews``) are refused, since both need the rays
+    in one world; ``align=[o_0, ...]`` with known offsets is taken, it only crops.  Behind the assembly, which runs on pinhole cameras
+    anyway, and in front of uu3d_camera_to_world the four launches of ``calibrate_views`` run on the lifts in camera axes and the
+    keypoints in the model's layout; then the poses are copied to the host -- the ONE copy of the stage, V x 9 float64 (quaternion,
+    position, state, terms), which waits for the launches -- and ``calibrated_cameras`` builds every view's ``Camera``.  A view that
+    cannot be calibrated (state 0: fewer than ``min_terms`` rows shared with view 0, lifts that fix no rotation, a position the rows do
+    not fix) is a ValueError that names it.  The call proceeds unchanged -> its tuple followed by ``cameras``, the V ``Camera`` objects
+    with extrinsics, ready for a later call without ``calibrate``, and ``calibration``, per view (state, terms); with ``align=[...]``
+    the two stand behind ``offsets`` and ``first``.  One view calibrates nothing and returns camera 0 as the world.  The result minus
+    its last two items equals, bit for bit, ``predict_views(views, the returned cameras, ...)``.  The rig's scale is the model's; the
+    limits stand in the module's docstring, and no accuracy is claimed."""
     import torch
     from . import predict as pt
     match = check_match(match)
     align = check_align(align)
     triangulate = check_triangulate(triangulate)
+    calibrate = check_calibrate(calibrate)
+    as_given = cameras
+    if calibrate is not None:
+        if match is not None:
+            raise ValueError("predict_views(calibrate=...) does not take match: matching needs the rays in one world, which is what the call is "
+                             "there to find; the same index must be the same person")
+        if isinstance(align, AlignViews):
+            raise ValueError("predict_views(calibrate=...) does not take align=True or an AlignViews: estimating offsets needs the rays in one "
+                             "world; pass known offsets as a list, which only crops")
+        # the cameras of every check and launch in front of the stage: where one has no extrinsics, the identity stands in
+        cameras = [c if c.has_extrinsics else _with_identity(c)
+                   for c in check_calibrate_cameras(cameras, len(views) if isinstance(views, (list, tuple)) else None)]
     if align is not None:
         def call(cropped, kept):
-            return predict_views(model, config, cropped, cameras, resolutions, mask_stride, flip, reuse_frames, batch_size, depth, graph, kept, fps,
+            return predict_views(model, config, cropped, as_given, resolutions, mask_stride, flip, reuse_frames, batch_size, depth, graph, kept, fps,
                                  model_fps, repair_joints, keypoints, min_root_joints, smooth, bones, rotations, interpolation, return_views,
-                                 keyframes_only, out_fps, match, None, triangulate)
-        return _predict_aligned_views(align, match, model, views, cameras, valid, fps, keyframes_only, out_fps, call)
+                                 keyframes_only, out_fps, match, None, triangulate, calibrate)
+        got = _predict_aligned_views(align, match, model, views, cameras, valid, fps, keyframes_only, out_fps, call)
+        return got if calibrate is None else got[:-4] + got[-2:] + got[-4:-2]      # cameras and calibration stay the last two items
     if match is not None:
         return _predict_matched_views(pt, match, model, config, views, cameras, resolutions, mask_stride, flip, reuse_frames, batch_size, depth, graph,
                                       valid, fps, model_fps, repair_joints, keypoints, min_root_joints, smooth, bones, rotations, interpolation,
@@ -1562,10 +2069,26 @@ def predict_views(model, config, views, cameras, resolutions=None, mask_stride=N
         raise ValueError("predict_views: the assembly did not return one frame per given frame")      # (cannot happen without out_fps / keyframes_only)
     J = int(front.out.shape[1])
     kp2d, flags = front.table.source
+    kp2d, flags = kp2d.reshape(V, R, J, 2), None if flags is None else flags.reshape(V, R, J)
+    # 2a. - 2e. where the cameras stand: every view's pose against view 0 from the lifts in camera axes, then the one copy
+    calibration = None
+    if calibrate is not None:
+        rows = np.zeros((V, CALIBRATE_POSE + 1), np.float64)
+        rows[0, 0] = rows[0, 7] = 1.0
+        if V > 1:
+            pose_dev, terms_dev = calibrate_views(front.out.reshape(V, R, J, 3), kp2d, as_given, flags, person.min_root_joints, calibrate.min_terms)
+            rows = torch.cat([pose_dev, terms_dev.to(torch.float64)[:, None]], 1).cpu().numpy()
+        lost = [v for v in range(V) if rows[v, 7] != 1.0]
+        if lost:
+            raise ValueError(f"calibrate: view {lost[0]} cannot be calibrated against view 0 ({int(rows[lost[0], 8])} shared rows, {calibrate.min_terms} "
+                             f"needed; or its lifts fix no rotation, or the rows fix no position) (views without a pose: {lost})")
+        cams = calibrated_cameras(as_given, rows[:, :CALIBRATE_POSE])
+        calibration = [(int(rows[v, 7]), int(rows[v, 8])) for v in range(V)]
     # 3. every view's poses to world axes: the existing launch, poses only, one row of extrinsics per view block
     world, _ = camera_to_world_rows(front.out, None, None, np.stack([c.pose_row() for c in cams]), [R] * V)
-    return _fused_scene(pt, person, world.view(V, R, J, 3), kp2d.reshape(V, R, J, 2), None if flags is None else flags.reshape(V, R, J), cams, lens,
-                        rates, model_fps, return_views, triangulate, int(config.ROOT_KEYTPOINT))
+    result = _fused_scene(pt, person, world.view(V, R, J, 3), kp2d, flags, cams, lens, rates, model_fps, return_views, triangulate,
+                          int(config.ROOT_KEYTPOINT))
+    return result if calibration is None else result + (cams, calibration)
 
 
 def _predict_matched_views(pt, match, model, config, views, cameras, resolutions, mask_stride, flip, reuse_frames, batch_size, depth, graph, valid,
