@@ -319,6 +319,109 @@ int uu3d_op_tchain_launches(const uu3d_model* model, int32_t* flags_out, int32_t
 int uu3d_op_tchain_xs_pack(const float* x_host, int32_t M, int32_t slot, int32_t rows, void* scratch_host);
 int uu3d_op_tchain_xs_unpack(const void* scratch_host, int32_t M, int32_t slot, int32_t rows, float* x_host);
 
+/* ---- TRAINING GEMMS: every loader and epilogue the training step (csrc/uu3d_train_forward.inc, csrc/uu3d_train_backward.inc) hands to its tiled
+ * GEMMs, each on its own, launched through the step's own host dispatch (launch_gemm, launch_gemm_tn, launch_colsum, launch_ln_bwd_rows,
+ * launch_ln_bwd_combine, csrc/uu3d_launch.h): kernel, DEEP form, slice count and combine are the step's -- tests/test_train_gemm_ops_gpu.py
+ * holds them to float64. ----
+ * The operand: one PackDesc of csrc/uu3d_train_kernels.h run through repack_kernel itself, from the Keras (in, out) kernel w_dev[K][N] on the DEVICE
+ * into a block this call zeroes first, padded as csrc/uu3d_train_state.inc allocates it:
+ *   kind 1 (forward)        Bt[round_up(N, 128)][round_up(K, 32)],        Bt[n][k] = W[k][n]
+ *   kind 4 (backward)       WK[round_up(K, 64)][round_up(N, 32)],         WK[k][n] = W[k][n]            (dX = dY W^T reads rows of W)
+ *   kind 5 (conv-transpose) WT[round_up(C, 128)][round_up(3 N, 32)],      WT[c][j N + n] = W[j C + c][n]   (K == 3 C)
+ * The block is the f32 operand | its f16 hi plane | its lo * 2048 plane (written by the same pass), 8 bytes per padded element.
+ * uu3d_op_train_operand_bytes: 0 for K or N < 1, K N >= 2^28, an unknown kind, kind 5 with K != 3 C (uu3d_op_train_pack refuses the same with
+ * UU3D_ERR_INVALID_ARGUMENT).  uu3d_op_train_pack synchronises the stream. */
+size_t uu3d_op_train_operand_bytes(int32_t kind, int32_t K, int32_t N, int32_t C);
+int uu3d_op_train_pack(const float* w_dev, int32_t kind, int32_t K, int32_t N, int32_t C, void* operand_dev, void* stream);
+
+#define UU3D_TA_PLAIN 0         /* ALoadPlain / TnLoadPlain: a_dev = f32 rows, row stride lda (a multiple of 4, >= the row's width) */
+#define UU3D_TA_LN 1            /* ALoadLayerNorm / TnLoadLayerNorm: the same rows, LayerNorm in the loader from ln_stats_dev (uu3d_op_row_stats), ln_gamma_dev, ln_beta_dev */
+#define UU3D_TA_GELU 2          /* ALoadGelu / TnLoadGelu: gelu(a_dev), exact erf */
+#define UU3D_TA_CONV3 3         /* ALoadConv3 / TnLoadConv3: a_dev = f32 rows [B L_in][conv_C]; row (b, t) of B L_out rows contracts over k = j C + c with row
+                                 * t stride + j - pad_left of sequence b, zero outside [0, L_in); the contraction length is 3 C, C % 4 == 0 */
+#define UU3D_TA_CONVT 4         /* ALoadConvT: the transposed strided convolution as a gather; a_dev = f32 rows [B L_out][conv_C]; row (b, src) of M = B L_in rows
+                                 * contracts over k = j C + n with row t = (src + pad_left - j) / stride of sequence b where that divides and t < L_out, else zero */
+#define UU3D_TEP_STORE 0         /* EpStore: out[M][N] = v (row stride ldo) */
+#define UU3D_TEP_BIAS 1          /* EpBias: v + bias */
+#define UU3D_TEP_BIAS_RELU 2     /* EpBiasRelu: max(v + bias, 0) */
+#define UU3D_TEP_BIAS_RES_GATE 3 /* EpBiasResGate: out = aux + (((v + bias) * dropout factor) / keep) * gate[row / rps]; aux_dev = the residual stream (row stride
+                                  * ldo, as out); gate_dev NULL: no division, no gate; drop_rate 0: no Dropout, else the factor of oracle/dropout_oracle.py at
+                                  * (drop_seed, drop_site, element row * ldo + col); out2_dev != NULL: out2 = out + pe_dev[row % period][.] (row stride ldo) */
+#define UU3D_TEP_ADD 4           /* EpAdd: out += v */
+#define UU3D_TEP_RELU_MASK 5     /* EpReluMask: out = aux > 0 ? v * scale : 0; aux_dev = H, the ReLU output (row stride ldo) */
+#define UU3D_TEP_GELU_GRAD 6     /* EpGeluGrad: out = v * gelu'(aux); aux_dev = the GELU's input (row stride ldo) */
+#define UU3D_TEP_CONV_RESIDUAL 7 /* EpConvResidual, training form: out = aux[b L_in + t stride + lo][.] + (((v + bias) * dropout factor) / keep) * gate[row / L_out]
+                                  * (+ pe_dev[t][.] when pe_dev != NULL); lo = 1 when stride > 1 and pad_left == 0, else 0; (L_out - 1) stride + lo < L_in;
+                                  * a gate needs rps == conv_L_out; every row stride ldo */
+typedef struct uu3d_train_dense_args {
+    const float* a_dev;
+    const float* ln_stats_dev; const float* ln_gamma_dev; const float* ln_beta_dev;
+    const void* operand_dev; const float* bias_dev;           /* uu3d_op_train_pack's block of kind operand_kind; bias[N] */
+    float* out_dev; float* out2_dev;
+    const float* aux_dev; const float* pe_dev; const float* gate_dev;
+    float* slab_dev; size_t slab_floats;                      /* split-K partial sums and their capacity in floats; 0 (or NULL) forces the unsplit form */
+    uint64_t drop_seed;
+    int32_t a_source, epilogue, precision, operand_kind;     /* UU3D_PREC_F16X3 (the block's planes) | UU3D_PREC_F32 (Bh = Bl = NULL) */
+    int32_t M, N, K, lda, ldo;                                /* the GEMM's dims: round_up(K, 32) is the block's row stride, N at most its rows */
+    int32_t conv_C, conv_L_in, conv_L_out, conv_stride, conv_pad_left;
+    int32_t rps, period; uint32_t drop_site;
+    float keep, scale, drop_rate;
+} uu3d_train_dense_args;
+/* out = epilogue(A-op W) through launch_gemm (64 x 64 tiles; f16x3: gemm_h3_kernel, DEEP at up to UU3D_GEMM_DEEP_WGS workgroups; f32: gemm_f32_kernel;
+ * split along K under splitk_rule(target 768) with EpSlab and splitk_reduce_kernel<epilogue>).  The (A source, epilogue, operand kind) combinations the
+ * step launches, and no other, each at both precisions:
+ *   UU3D_TA_GELU  x UU3D_TEP_BIAS_RES_GATE, kind 1      the unfused spatial fc2                                 uu3d_train_forward.inc: forward_spatial
+ *   UU3D_TA_PLAIN x UU3D_TEP_BIAS_RES_GATE, kind 1      projections and fc2 (out2 / pe: the last temporal fc2)  block_forward, forward_spatial, forward_temporal
+ *   UU3D_TA_LN    x UU3D_TEP_BIAS, _BIAS_RELU, kind 1   q | k | v and fc1 below 1024 rows                       block_forward
+ *   UU3D_TA_CONV3 x UU3D_TEP_CONV_RESIDUAL, kind 1      the strided convolution                                 forward_temporal
+ *   UU3D_TA_CONVT x UU3D_TEP_RELU_MASK, kind 5          d hidden of a strided block                             uu3d_train_backward.inc: the strided loop
+ *   UU3D_TA_PLAIN x UU3D_TEP_GELU_GRAD, _RELU_MASK, kind 4   d hidden of a spatial / temporal block             block_backward
+ *   UU3D_TA_PLAIN x UU3D_TEP_ADD, kind 4                head1's input gradient added to d t_out                 backward
+ *   UU3D_TA_PLAIN x UU3D_TEP_STORE, kind 4              every other input-gradient GEMM                         attn_half, block_backward, backward
+ * Anything else, a null pointer the combination needs, M or N < 1, K < 4 or K % 4 != 0, lda < K or lda % 4 != 0 (row sources), conv_C % 4 != 0 or
+ * K != 3 conv_C, M not a multiple of L_out (CONV3) / L_in (CONVT), ldo < N, a gate with keep <= 0 or rps < 1, drop_rate outside [0, 1), out2 without
+ * pe_dev or with period < 1, slab_floats != 0 with slab_dev NULL: UU3D_ERR_INVALID_ARGUMENT.  2^29 elements or more in a buffer: UU3D_ERR_UNSUPPORTED.
+ * Both before any launch, every output untouched.  Every pointer 16-byte aligned (not checked).  Rows and columns beyond M and N are not written. */
+int uu3d_op_train_dense(const uu3d_train_dense_args* args, void* stream);
+
+#define UU3D_WEP_STORE 0        /* EpStore: out[P][Q], row stride ldo */
+#define UU3D_WEP_STORE3 1       /* EpStore3: the three column blocks of Q / 3 columns to out_dev, out1_dev, out2_dev, each [P][Q / 3] contiguous */
+typedef struct uu3d_train_wgrad_args {
+    const float* a_dev;                                       /* [R][lda]; UU3D_TA_CONV3: [B L_in][conv_C] */
+    const float* ln_stats_dev; const float* ln_gamma_dev; const float* ln_beta_dev;
+    const float* b_dev;                                       /* [R][ldb] */
+    float* out_dev; float* out1_dev; float* out2_dev;
+    float* slab_dev; size_t slab_floats;                      /* a smaller capacity cuts the number of slabs (P round_up(Q, 4) floats each) down to none */
+    int32_t a_source, epilogue, h3;                           /* h3 1: gemm_tn_h3_kernel when P, Q >= 128, else gemm_tn_kernel (exact f32) */
+    int32_t R, P, Q, lda, ldb, ldo;
+    int32_t conv_C, conv_L_in, conv_L_out, conv_stride, conv_pad_left;
+} uu3d_train_wgrad_args;
+/* C[P][Q] = A-op[R][P]^T B[R][Q] through launch_gemm_tn.  The combinations the step launches, and no other:
+ *   UU3D_TA_LN x UU3D_WEP_STORE3 (d Wq | Wk | Wv, attn_half), UU3D_TA_LN x UU3D_WEP_STORE (d W1), UU3D_TA_GELU x UU3D_WEP_STORE (d W2 of a spatial
+ *   block), UU3D_TA_CONV3 x UU3D_WEP_STORE (d of the strided convolution's kernel), UU3D_TA_PLAIN x UU3D_WEP_STORE (uu3d_op_gemm_tn / _h3).
+ * R >= 1; P, Q >= 4 and multiples of 4; lda >= P, ldb >= Q, both multiples of 4; UU3D_WEP_STORE: ldo >= Q; UU3D_WEP_STORE3: Q % 3 == 0 and three outputs;
+ * UU3D_TA_CONV3: P == 3 conv_C, conv_C % 4 == 0, R a multiple of L_out.  UU3D_ERR_INVALID_ARGUMENT otherwise, before any launch. */
+int uu3d_op_train_wgrad(const uu3d_train_wgrad_args* args, void* stream);
+
+/* launch_colsum into ReduceOut{out0, out1, out2, seg} (the q | k | v bias gradients of attn_half): out_s[c] (+)= sum_r X[r][s seg + c], s < 3, c < seg.
+ * R, seg >= 1; ldx >= 3 seg.  scratch_floats below 3 seg: UU3D_ERR_WORKSPACE, nothing is written. */
+int uu3d_op_colsum3(const float* x_dev, int32_t ldx, int32_t R, int32_t seg, float* out0_dev, float* out1_dev, float* out2_dev, int32_t accumulate,
+                    float* scratch_dev, size_t scratch_floats, void* stream);
+/* uu3d_op_ln_bwd as the step launches it (launch_ln_bwd_rows + launch_ln_bwd_combine): dx = d x, or res + d x when res_dev != NULL (res_dev may be
+ * dx_dev: each element is read by the lane that writes it); gate_dev != NULL: gated_out_dev = (dx / keep) * gate[row / rps] as well (LnBwdGated: the
+ * copy the next Dense-layer backward reads), row stride ld; gate_dev and gated_out_dev both or neither, keep > 0, rps >= 1.  dgamma, dbeta written.
+ * Shapes and scratch as uu3d_op_ln_bwd. */
+int uu3d_op_ln_bwd_ex(const float* x_dev, const float* dy_dev, const float* stats_dev, const float* gamma_dev, int32_t ld, int32_t D, int32_t M,
+                      float* dx_dev, const float* res_dev, const float* gate_dev, float keep, int32_t rps, float* gated_out_dev, float* dgamma_dev,
+                      float* dbeta_dev, float* scratch_dev, size_t scratch_floats, void* stream);
+/* identity_bwd_kernel (the gradient of trim + MaxPool1D(1, stride) as a gather): dmid[b L_in + r][.] = dout[b L_out + (r - lo) / stride][.] where
+ * r >= lo, stride divides r - lo and the quotient is below L_out, else 0.  Dense rows of D floats.  B, L_in, L_out, stride, D >= 1, lo >= 0. */
+int uu3d_op_identity_bwd(const float* dout_dev, int32_t B, int32_t L_in, int32_t L_out, int32_t stride, int32_t lo, int32_t D, float* dmid_dev, void* stream);
+/* scale_rows_kernel: out[r][.] = in[r][.], divided by keep and times gate[r / rps] when gate_dev != NULL, then 0 where row_mask_dev != NULL and
+ * (row_mask_dev[r] != 0) != want.  Dense rows of D floats.  rows, D >= 1; want 0 or 1; a gate needs keep > 0 and rps >= 1. */
+int uu3d_op_scale_rows(const float* in_dev, int32_t rows, int32_t D, const float* gate_dev, float keep, int32_t rps, const uint8_t* row_mask_dev,
+                       int32_t want, float* out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -56,6 +56,26 @@ def test_create_rejects_bad_arguments_without_compute(lib):
     assert lib.uu3d_mpjpe(None, None, 1, 17, 6, None, None) == _capi.UU3D_ERR_INVALID_ARGUMENT
 
 
+def test_training_gemm_operators_refuse_null_arguments_without_compute(lib):
+    """The operator entries of the training step's GEMM forms (include/uu3d_ops.h): the ctypes argument records have the size of the
+    fields the header lists (a hand count, not read from the header), and NULL records, NULL buffers and unknown kinds are refused before
+    any launch."""
+    from uplift_upsample_3dhpe_amd import _capi
+    INVALID = _capi.UU3D_ERR_INVALID_ARGUMENT
+    assert C.sizeof(_capi.Uu3dTrainDenseArgs) == 12 * 8 + 8 + 8 + 16 * 4 + 4 + 3 * 4 and C.sizeof(_capi.Uu3dTrainWgradArgs) == 9 * 8 + 8 + 14 * 4
+    assert lib.uu3d_op_train_operand_bytes(1, 51, 40, 0) == 8 * 128 * 64 and lib.uu3d_op_train_operand_bytes(4, 51, 40, 0) == 8 * 64 * 64
+    assert lib.uu3d_op_train_operand_bytes(5, 72, 40, 24) == 8 * 128 * 128
+    assert lib.uu3d_op_train_operand_bytes(5, 72, 40, 25) == 0 and lib.uu3d_op_train_operand_bytes(2, 51, 40, 0) == 0 and lib.uu3d_op_train_operand_bytes(1, 0, 40, 0) == 0
+    assert lib.uu3d_op_train_pack(None, 1, 51, 40, 0, None, None) == INVALID
+    assert lib.uu3d_op_train_dense(None, None) == INVALID and lib.uu3d_op_train_wgrad(None, None) == INVALID
+    assert lib.uu3d_op_train_dense(C.byref(_capi.Uu3dTrainDenseArgs()), None) == INVALID
+    assert lib.uu3d_op_train_wgrad(C.byref(_capi.Uu3dTrainWgradArgs()), None) == INVALID
+    assert lib.uu3d_op_colsum3(None, 96, 8, 32, None, None, None, 0, None, 0, None) == INVALID
+    assert lib.uu3d_op_ln_bwd_ex(None, None, None, None, 32, 32, 8, None, None, None, 1.0, 1, None, None, None, None, 0, None) == INVALID
+    assert lib.uu3d_op_identity_bwd(None, 1, 9, 3, 3, 1, 32, None, None) == INVALID
+    assert lib.uu3d_op_scale_rows(None, 8, 32, None, 1.0, 1, None, 0, None, None) == INVALID
+
+
 def test_missing_library_fails_loudly(tmp_path):
     from uplift_upsample_3dhpe_amd import _capi
     with pytest.raises(_capi.Uu3dLibraryError):

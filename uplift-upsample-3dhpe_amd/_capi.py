@@ -72,6 +72,8 @@ OPS_SYMBOLS = (
     "uu3d_op_spatial_stack", "uu3d_op_compact_frames", "uu3d_op_spatial_choice",
     "uu3d_op_panel_a_pack", "uu3d_op_attn_qf_unpack",
     "uu3d_op_tchain", "uu3d_op_tchain_scratch_bytes", "uu3d_op_tchain_launches", "uu3d_op_tchain_xs_pack", "uu3d_op_tchain_xs_unpack",
+    "uu3d_op_train_operand_bytes", "uu3d_op_train_pack", "uu3d_op_train_dense", "uu3d_op_train_wgrad", "uu3d_op_colsum3", "uu3d_op_ln_bwd_ex",
+    "uu3d_op_identity_bwd", "uu3d_op_scale_rows",
 )
 # epilogues of uu3d_op_ln_dense_panel_ex / uu3d_op_ln_dense_wt (include/uu3d_ops.h)
 UU3D_EP_BIAS, UU3D_EP_BIAS_RELU_SPLIT, UU3D_EP_BIAS_SPLIT_Q, UU3D_EP_BIAS_RESIDUAL, UU3D_EP_BIAS_RESIDUAL_LN = range(5)
@@ -87,6 +89,11 @@ UU3D_SPATIAL_AUTO, UU3D_SPATIAL_F32, UU3D_SPATIAL_H3_TILES, UU3D_SPATIAL_P16 = r
 UU3D_SPATIAL_OUT_F32, UU3D_SPATIAL_OUT_PLANES = range(2)
 # stage sets of the temporal chain's launches (uu3d_op_tchain, include/uu3d_ops.h)
 UU3D_TC_PROJ, UU3D_TC_MLP, UU3D_TC_QKV, UU3D_TC_FC1_PLANES, UU3D_TC_PE = 1, 2, 4, 8, 16
+# A sources and epilogues of uu3d_op_train_dense / uu3d_op_train_wgrad (include/uu3d_ops.h)
+UU3D_TA_PLAIN, UU3D_TA_LN, UU3D_TA_GELU, UU3D_TA_CONV3, UU3D_TA_CONVT = range(5)
+(UU3D_TEP_STORE, UU3D_TEP_BIAS, UU3D_TEP_BIAS_RELU, UU3D_TEP_BIAS_RES_GATE, UU3D_TEP_ADD, UU3D_TEP_RELU_MASK, UU3D_TEP_GELU_GRAD,
+ UU3D_TEP_CONV_RESIDUAL) = range(8)
+UU3D_WEP_STORE, UU3D_WEP_STORE3 = range(2)
 
 
 class Uu3dTiledDenseArgs(C.Structure):
@@ -97,6 +104,25 @@ class Uu3dTiledDenseArgs(C.Structure):
                 + [(n, C.c_int32) for n in ("a_source", "epilogue", "precision", "splitk_target", "M", "N", "K", "lda", "ldo",
                                             "conv_C", "conv_L_in", "conv_L_out", "conv_stride", "conv_pad_left", "period")]
                 + [("qscale", C.c_float)])
+
+
+class Uu3dTrainDenseArgs(C.Structure):
+    """``uu3d_train_dense_args`` of include/uu3d_ops.h."""
+    _fields_ = ([(n, C.c_void_p) for n in ("a_dev", "ln_stats_dev", "ln_gamma_dev", "ln_beta_dev", "operand_dev", "bias_dev", "out_dev", "out2_dev",
+                                           "aux_dev", "pe_dev", "gate_dev", "slab_dev")]
+                + [("slab_floats", C.c_size_t), ("drop_seed", C.c_uint64)]
+                + [(n, C.c_int32) for n in ("a_source", "epilogue", "precision", "operand_kind", "M", "N", "K", "lda", "ldo",
+                                            "conv_C", "conv_L_in", "conv_L_out", "conv_stride", "conv_pad_left", "rps", "period")]
+                + [("drop_site", C.c_uint32)]
+                + [(n, C.c_float) for n in ("keep", "scale", "drop_rate")])
+
+
+class Uu3dTrainWgradArgs(C.Structure):
+    """``uu3d_train_wgrad_args`` of include/uu3d_ops.h."""
+    _fields_ = ([(n, C.c_void_p) for n in ("a_dev", "ln_stats_dev", "ln_gamma_dev", "ln_beta_dev", "b_dev", "out_dev", "out1_dev", "out2_dev", "slab_dev")]
+                + [("slab_floats", C.c_size_t)]
+                + [(n, C.c_int32) for n in ("a_source", "epilogue", "h3", "R", "P", "Q", "lda", "ldb", "ldo",
+                                            "conv_C", "conv_L_in", "conv_L_out", "conv_stride", "conv_pad_left")])
 
 
 class Uu3dLibraryError(RuntimeError):
@@ -553,6 +579,22 @@ def load_library(path=None):
     lib.uu3d_op_tchain_xs_pack.argtypes = [vp, i32, i32, i32, vp]
     lib.uu3d_op_tchain_xs_unpack.restype = C.c_int
     lib.uu3d_op_tchain_xs_unpack.argtypes = [vp, i32, i32, i32, vp]
+    lib.uu3d_op_train_operand_bytes.restype = sz
+    lib.uu3d_op_train_operand_bytes.argtypes = [i32, i32, i32, i32]
+    lib.uu3d_op_train_pack.restype = C.c_int
+    lib.uu3d_op_train_pack.argtypes = [vp, i32, i32, i32, i32, vp, vp]
+    lib.uu3d_op_train_dense.restype = C.c_int
+    lib.uu3d_op_train_dense.argtypes = [C.POINTER(Uu3dTrainDenseArgs), vp]
+    lib.uu3d_op_train_wgrad.restype = C.c_int
+    lib.uu3d_op_train_wgrad.argtypes = [C.POINTER(Uu3dTrainWgradArgs), vp]
+    lib.uu3d_op_colsum3.restype = C.c_int
+    lib.uu3d_op_colsum3.argtypes = [vp, i32, i32, i32, vp, vp, vp, i32, vp, sz, vp]
+    lib.uu3d_op_ln_bwd_ex.restype = C.c_int
+    lib.uu3d_op_ln_bwd_ex.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, C.c_float, i32, vp, vp, vp, vp, sz, vp]
+    lib.uu3d_op_identity_bwd.restype = C.c_int
+    lib.uu3d_op_identity_bwd.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, vp]
+    lib.uu3d_op_scale_rows.restype = C.c_int
+    lib.uu3d_op_scale_rows.argtypes = [vp, i32, i32, vp, C.c_float, i32, vp, i32, vp, vp]
     if path is None:
         _lib = lib
     return lib

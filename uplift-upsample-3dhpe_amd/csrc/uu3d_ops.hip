@@ -1,4 +1,4 @@
-// uu3d_ops.hip -- C ABI of the backward building blocks and of the forward operators (include/uu3d_ops.h).
+// uu3d_ops.hip -- C ABI of the backward building blocks, of the forward operators and of the training step's GEMM forms (include/uu3d_ops.h).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include "../../include/uu3d.h"
@@ -9,6 +9,7 @@
 #include "uu3d_launch.h"
 #include "uu3d_pack.h"
 #include "uu3d_tchain16.h"      // tchain_qf_index, tchain_qf_halfs
+#include "uu3d_train_kernels.h" // the training step's loaders, epilogues and small kernels
 #include <vector>
 #include <initializer_list>
 
@@ -429,5 +430,204 @@ int uu3d_op_tiled_dense(const uu3d_tiled_dense_args* a, void* stream_) {
         case UU3D_A_CONV3_F32: rows(ALoadConv3{Af, a->conv_C, a->conv_L_in, a->conv_L_out, a->conv_stride, a->conv_pad_left, M, K}, ep_conv); break;
         default: dma(GLoadConv3{Ah, Al, zero, a->conv_C, a->conv_L_in, a->conv_L_out, a->conv_stride, a->conv_pad_left, M}, ep_conv); break;
     }
+    return hip_status();
+}
+
+// ---- the training step's GEMM forms, each on its own (include/uu3d_ops.h: TRAINING GEMMS), through the step's own host dispatch ----
+namespace {
+
+// rows x ld of an operand block (uu3d_train_state.inc: dense / block): the GEMM reads it as Bt[rows][ld] with N <= rows, round_up(K, 32) == ld
+struct TrainOperandDims { int rows, ld; };
+bool train_operand_dims(int kind, int K, int N, int Cc, TrainOperandDims* d) {
+    if (K < 1 || N < 1) return false;
+    if ((double)K * N >= 268435456.0) return false;
+    if (kind == 1) { *d = {ru(N, 128), ru(K, 32)}; return true; }                      // forward: Bt[round128(N)][Kp]
+    if (kind == 4) { *d = {ru(K, 64), ru(N, 32)}; return true; }                       // backward: WK[round64(K)][round32(N)]
+    if (kind == 5 && Cc >= 1 && K == 3 * Cc) { *d = {ru(Cc, 128), ru(3 * N, 32)}; return true; }   // conv-transpose: WT[round128(C)][round32(3 N)]
+    return false;
+}
+// rows of the block a GEMM of output width N reads, by the kind of its operand
+int train_operand_rows(int kind, int N) { return kind == 4 ? ru(N, 64) : ru(N, 128); }
+
+dim3 ew_grid(long long n) { return dim3((unsigned)((n + 255) / 256)); }
+
+}  // namespace
+
+size_t uu3d_op_train_operand_bytes(int32_t kind, int32_t K, int32_t N, int32_t Cc) {
+    TrainOperandDims d;
+    return train_operand_dims(kind, K, N, Cc, &d) ? (size_t)d.rows * d.ld * (sizeof(float) + 2 * sizeof(_Float16)) : 0;
+}
+
+int uu3d_op_train_pack(const float* w_dev, int32_t kind, int32_t K, int32_t N, int32_t Cc, void* operand_dev, void* stream_) {
+    TrainOperandDims d;
+    if (!w_dev || !operand_dev || !train_operand_dims(kind, K, N, Cc, &d)) return UU3D_ERR_INVALID_ARGUMENT;
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t n = (size_t)d.rows * d.ld;
+    const PackDesc desc{0, 0, kind, K, N, d.ld, 0, kind == 5 ? Cc : 0};
+    const int first = 0;
+    char* table = nullptr;                                           // the one-entry descriptor table of this call
+    if (hipMalloc((void**)&table, 256) != hipSuccess) return UU3D_ERR_HIP;
+    int st = UU3D_OK;
+    if (hipMemcpyAsync(table, &desc, sizeof(desc), hipMemcpyHostToDevice, stream) != hipSuccess ||
+        hipMemcpyAsync(table + 128, &first, sizeof(first), hipMemcpyHostToDevice, stream) != hipSuccess ||
+        hipMemsetAsync(operand_dev, 0, n * (sizeof(float) + 2 * sizeof(_Float16)), stream) != hipSuccess) st = UU3D_ERR_HIP;
+    if (st == UU3D_OK) {
+        float* arena = reinterpret_cast<float*>(operand_dev);
+        hipLaunchKernelGGL(repack_kernel, dim3(repack_blocks(kind, K, N)), dim3(256), 0, stream, w_dev, arena, reinterpret_cast<const PackDesc*>(table),
+                           reinterpret_cast<const int*>(table + 128), 1, reinterpret_cast<_Float16*>(arena + n), (long long)n);
+        st = hip_status();
+    }
+    if (hipStreamSynchronize(stream) != hipSuccess && st == UU3D_OK) st = UU3D_ERR_HIP;      // (the table is the call's own)
+    (void)hipFree(table);
+    return st;
+}
+
+int uu3d_op_train_dense(const uu3d_train_dense_args* a, void* stream_) {
+    if (!a) return UU3D_ERR_INVALID_ARGUMENT;
+    const int M = a->M, N = a->N, K = a->K, src = a->a_source, epi = a->epilogue, kind = a->operand_kind;
+    if (!a->a_dev || !a->operand_dev || !a->out_dev || M < 1 || N < 1 || K < 4 || (K & 3)) return UU3D_ERR_INVALID_ARGUMENT;
+    if ((a->precision != UU3D_PREC_F16X3 && a->precision != UU3D_PREC_F32) || (a->slab_floats != 0 && !a->slab_dev)) return UU3D_ERR_INVALID_ARGUMENT;
+    // the combinations the training step launches (include/uu3d_ops.h lists them by call site)
+    bool known = false;
+    switch (src) {
+        case UU3D_TA_PLAIN: known = (kind == 1 && epi == UU3D_TEP_BIAS_RES_GATE) ||
+                                    (kind == 4 && (epi == UU3D_TEP_STORE || epi == UU3D_TEP_ADD || epi == UU3D_TEP_RELU_MASK || epi == UU3D_TEP_GELU_GRAD)); break;
+        case UU3D_TA_LN: known = kind == 1 && (epi == UU3D_TEP_BIAS || epi == UU3D_TEP_BIAS_RELU); break;
+        case UU3D_TA_GELU: known = kind == 1 && epi == UU3D_TEP_BIAS_RES_GATE; break;
+        case UU3D_TA_CONV3: known = kind == 1 && epi == UU3D_TEP_CONV_RESIDUAL; break;
+        case UU3D_TA_CONVT: known = kind == 5 && epi == UU3D_TEP_RELU_MASK; break;
+        default: break;
+    }
+    if (!known) return UU3D_ERR_INVALID_ARGUMENT;
+    const bool conv = src == UU3D_TA_CONV3 || src == UU3D_TA_CONVT;
+    int lda = a->lda;
+    if (conv) {
+        const int Cc = a->conv_C;                                    // channels of a gathered row
+        if (Cc < 4 || (Cc & 3) || (int64_t)K != (int64_t)3 * Cc || a->conv_L_in < 1 || a->conv_L_out < 1 || a->conv_stride < 1 || a->conv_pad_left < 0) return UU3D_ERR_INVALID_ARGUMENT;
+        if (M % (src == UU3D_TA_CONV3 ? a->conv_L_out : a->conv_L_in) != 0) return UU3D_ERR_INVALID_ARGUMENT;
+        lda = Cc;
+    } else if (lda < K || (lda & 3)) return UU3D_ERR_INVALID_ARGUMENT;
+    if (src == UU3D_TA_LN && (!a->ln_stats_dev || !a->ln_gamma_dev || !a->ln_beta_dev)) return UU3D_ERR_INVALID_ARGUMENT;
+    const int ldo = a->ldo;
+    if (ldo < N) return UU3D_ERR_INVALID_ARGUMENT;
+    const bool bias = epi == UU3D_TEP_BIAS || epi == UU3D_TEP_BIAS_RELU || epi == UU3D_TEP_BIAS_RES_GATE || epi == UU3D_TEP_CONV_RESIDUAL;
+    if (bias && !a->bias_dev) return UU3D_ERR_INVALID_ARGUMENT;
+    const bool aux = epi == UU3D_TEP_BIAS_RES_GATE || epi == UU3D_TEP_CONV_RESIDUAL || epi == UU3D_TEP_RELU_MASK || epi == UU3D_TEP_GELU_GRAD;
+    if (aux && !a->aux_dev) return UU3D_ERR_INVALID_ARGUMENT;
+    const bool gated = epi == UU3D_TEP_BIAS_RES_GATE || epi == UU3D_TEP_CONV_RESIDUAL;
+    if (gated && ((a->gate_dev != nullptr && (!(a->keep > 0.f) || a->rps < 1)) || !(a->drop_rate >= 0.f) || !(a->drop_rate < 1.f))) return UU3D_ERR_INVALID_ARGUMENT;
+    if (epi == UU3D_TEP_BIAS_RES_GATE && a->out2_dev != nullptr && (!a->pe_dev || a->period < 1)) return UU3D_ERR_INVALID_ARGUMENT;
+    int lo = 0;
+    if (epi == UU3D_TEP_CONV_RESIDUAL) {
+        lo = (a->conv_stride > 1 && a->conv_pad_left == 0) ? 1 : 0;
+        if ((int64_t)(a->conv_L_out - 1) * a->conv_stride + lo >= a->conv_L_in) return UU3D_ERR_INVALID_ARGUMENT;      // the identity row of the last output row
+        if (a->gate_dev != nullptr && a->rps != a->conv_L_out) return UU3D_ERR_INVALID_ARGUMENT;                      // one gate per sequence
+    }
+    const int Kp = ru(K, 32);
+    const double in_rows = src == UU3D_TA_CONV3 ? (double)(M / a->conv_L_out) * a->conv_L_in : (src == UU3D_TA_CONVT ? (double)(M / a->conv_L_in) * a->conv_L_out : (double)M);
+    if ((double)M * ru(std::max(N, ldo), 4) >= 536870912.0 || in_rows * std::max(lda, ldo) >= 536870912.0) return UU3D_ERR_UNSUPPORTED;   // 32-bit M * N in the combine's grid
+
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t nb = (size_t)train_operand_rows(kind, N) * Kp;
+    const float* Bt = reinterpret_cast<const float*>(a->operand_dev);
+    const bool h3 = a->precision == UU3D_PREC_F16X3;
+    const _Float16* Bh = h3 ? reinterpret_cast<const _Float16*>(Bt + nb) : nullptr; const _Float16* Bl = h3 ? Bh + nb : nullptr;
+    int st = UU3D_OK;
+    auto go = [&](const auto& al, const auto& ep) { st = launch_gemm(al, Bt, M, N, K, ep, a->slab_dev, a->slab_floats, stream, Bh, Bl); };
+    const DropCfg drop = drop_cfg(gated ? a->drop_rate : 0.f, a->drop_seed, a->drop_site);
+    const EpBiasResGate ep_gate{a->out_dev, a->aux_dev, a->bias_dev, ldo, a->gate_dev, a->keep, a->rps, a->out2_dev, a->out2_dev ? a->pe_dev : nullptr,
+                                a->out2_dev ? a->period : 1, drop};
+    const float scale = a->scale;
+    switch (src) {
+        case UU3D_TA_PLAIN: {
+            const ALoadPlain al{a->a_dev, lda, M, K};
+            if (epi == UU3D_TEP_BIAS_RES_GATE) go(al, ep_gate);
+            else if (epi == UU3D_TEP_STORE) go(al, EpStore{a->out_dev, ldo});
+            else if (epi == UU3D_TEP_ADD) go(al, EpAdd{a->out_dev, ldo});
+            else if (epi == UU3D_TEP_RELU_MASK) go(al, EpReluMask{a->out_dev, a->aux_dev, ldo, scale});
+            else go(al, EpGeluGrad{a->out_dev, a->aux_dev, ldo});
+        } break;
+        case UU3D_TA_LN: {
+            const ALoadLayerNorm al{a->a_dev, reinterpret_cast<const float2*>(a->ln_stats_dev), a->ln_gamma_dev, a->ln_beta_dev, lda, M, K};
+            if (epi == UU3D_TEP_BIAS) go(al, EpBias{a->out_dev, a->bias_dev, ldo}); else go(al, EpBiasRelu{a->out_dev, a->bias_dev, ldo});
+        } break;
+        case UU3D_TA_GELU: go(ALoadGelu{a->a_dev, lda, M, K}, ep_gate); break;
+        case UU3D_TA_CONV3:
+            go(ALoadConv3{a->a_dev, a->conv_C, a->conv_L_in, a->conv_L_out, a->conv_stride, a->conv_pad_left, M, K},
+               EpConvResidual{a->out_dev, a->bias_dev, ldo, a->aux_dev, a->conv_L_in, a->conv_L_out, a->conv_stride, lo, a->pe_dev, a->gate_dev, a->keep, drop});
+            break;
+        default:
+            go(ALoadConvT{a->a_dev, a->conv_C, a->conv_L_in, a->conv_L_out, a->conv_stride, a->conv_pad_left, M, K}, EpReluMask{a->out_dev, a->aux_dev, ldo, scale});
+            break;
+    }
+    return st;
+}
+
+int uu3d_op_train_wgrad(const uu3d_train_wgrad_args* a, void* stream_) {
+    if (!a) return UU3D_ERR_INVALID_ARGUMENT;
+    const int R = a->R, P = a->P, Q = a->Q, src = a->a_source, epi = a->epilogue;
+    if (!a->a_dev || !a->b_dev || !a->out_dev || R < 1 || P < 4 || Q < 4 || (P & 3) || (Q & 3) || a->ldb < Q || (a->ldb & 3)) return UU3D_ERR_INVALID_ARGUMENT;
+    if ((a->slab_floats != 0 && !a->slab_dev) || (a->h3 != 0 && a->h3 != 1)) return UU3D_ERR_INVALID_ARGUMENT;
+    // the combinations the training step launches
+    const bool known = (epi == UU3D_WEP_STORE && (src == UU3D_TA_PLAIN || src == UU3D_TA_LN || src == UU3D_TA_GELU || src == UU3D_TA_CONV3)) ||
+                       (epi == UU3D_WEP_STORE3 && src == UU3D_TA_LN);
+    if (!known) return UU3D_ERR_INVALID_ARGUMENT;
+    if (src == UU3D_TA_CONV3) {
+        const int Cc = a->conv_C;
+        if (Cc < 4 || (Cc & 3) || (int64_t)P != (int64_t)3 * Cc || a->conv_L_in < 1 || a->conv_L_out < 1 || a->conv_stride < 1 || a->conv_pad_left < 0 ||
+            R % a->conv_L_out != 0) return UU3D_ERR_INVALID_ARGUMENT;
+        if ((double)(R / a->conv_L_out) * a->conv_L_in * Cc >= 536870912.0) return UU3D_ERR_UNSUPPORTED;
+    } else if (a->lda < P || (a->lda & 3)) return UU3D_ERR_INVALID_ARGUMENT;
+    if (src == UU3D_TA_LN && (!a->ln_stats_dev || !a->ln_gamma_dev || !a->ln_beta_dev)) return UU3D_ERR_INVALID_ARGUMENT;
+    if (epi == UU3D_WEP_STORE3 ? (!a->out1_dev || !a->out2_dev || Q % 3 != 0) : a->ldo < Q) return UU3D_ERR_INVALID_ARGUMENT;
+    if ((double)R * std::max(a->lda, a->ldb) >= 536870912.0 || (double)P * std::max(Q, a->ldo) >= 536870912.0) return UU3D_ERR_UNSUPPORTED;
+
+    hipStream_t stream = (hipStream_t)stream_;
+    int st = UU3D_OK;
+    auto go = [&](const auto& al, const auto& ep) { st = launch_gemm_tn(al, a->b_dev, a->ldb, R, P, Q, ep, a->slab_dev, a->slab_dev ? a->slab_floats : 0, stream, a->h3 != 0); };
+    const EpStore ep{a->out_dev, a->ldo};
+    switch (src) {
+        case UU3D_TA_PLAIN: go(TnLoadPlain{a->a_dev, a->lda, R, P}, ep); break;
+        case UU3D_TA_LN: {
+            const TnLoadLayerNorm al{a->a_dev, reinterpret_cast<const float2*>(a->ln_stats_dev), a->ln_gamma_dev, a->ln_beta_dev, a->lda, R, P};
+            if (epi == UU3D_WEP_STORE3) go(al, EpStore3{a->out_dev, a->out1_dev, a->out2_dev, Q / 3}); else go(al, ep);
+        } break;
+        case UU3D_TA_GELU: go(TnLoadGelu{a->a_dev, a->lda, R, P}, ep); break;
+        default: go(TnLoadConv3{a->a_dev, a->conv_C, a->conv_L_in, a->conv_L_out, a->conv_stride, a->conv_pad_left, R, P}, ep); break;
+    }
+    return st;
+}
+
+int uu3d_op_colsum3(const float* x, int32_t ldx, int32_t R, int32_t seg, float* out0, float* out1, float* out2, int32_t accumulate,
+                    float* scratch, size_t scratch_floats, void* stream) {
+    if (!x || !out0 || !out1 || !out2 || !scratch || R < 1 || seg < 1 || seg > 178956970 || ldx < 3 * seg) return UU3D_ERR_INVALID_ARGUMENT;
+    return launch_colsum(x, ldx, R, 3 * seg, 0, nullptr, 0, ReduceOut{out0, out1, out2, seg}, accumulate, scratch, scratch_floats, (hipStream_t)stream);
+}
+
+int uu3d_op_ln_bwd_ex(const float* x, const float* dy, const float* stats, const float* gamma, int32_t ld, int32_t D, int32_t M, float* dx,
+                      const float* res, const float* gate, float keep, int32_t rps, float* gated_out, float* dgamma, float* dbeta,
+                      float* scratch, size_t scratch_floats, void* stream_) {
+    if (!x || !dy || !stats || !gamma || !dx || !dgamma || !dbeta || !scratch || D < 4 || (D & 3) || D > 1024 || M < 1 || ld < D || (ld & 3)) return UU3D_ERR_INVALID_ARGUMENT;
+    if ((gate != nullptr) != (gated_out != nullptr) || (gate != nullptr && (!(keep > 0.f) || rps < 1))) return UU3D_ERR_INVALID_ARGUMENT;
+    if ((size_t)2 * D > scratch_floats) return UU3D_ERR_WORKSPACE;
+    hipStream_t stream = (hipStream_t)stream_;
+    const LnBwdGated gated = gate != nullptr ? LnBwdGated{gate, keep, rps, gated_out} : LnBwdGated{nullptr, 1.f, 1, nullptr};
+    const int slices = launch_ln_bwd_rows(x, dy, (const float2*)stats, gamma, ld, D, M, dx, res != nullptr, res, scratch, scratch_floats, stream, gated);
+    launch_ln_bwd_combine(scratch, D, slices, dgamma, dbeta, 0, stream);
+    return hip_status();
+}
+
+int uu3d_op_identity_bwd(const float* dout, int32_t B, int32_t L_in, int32_t L_out, int32_t stride, int32_t lo, int32_t D, float* dmid, void* stream) {
+    if (!dout || !dmid || B < 1 || L_in < 1 || L_out < 1 || stride < 1 || lo < 0 || D < 1) return UU3D_ERR_INVALID_ARGUMENT;
+    if ((double)B * std::max(L_in, L_out) * D >= 2147483648.0) return UU3D_ERR_UNSUPPORTED;       // 32-bit element index in the kernel
+    hipLaunchKernelGGL(identity_bwd_kernel, ew_grid((long long)B * L_in * D), dim3(256), 0, (hipStream_t)stream, dout, B, L_in, L_out, stride, lo, D, dmid);
+    return hip_status();
+}
+
+int uu3d_op_scale_rows(const float* in, int32_t rows, int32_t D, const float* gate, float keep, int32_t rps, const uint8_t* row_mask, int32_t want,
+                       float* out, void* stream) {
+    if (!in || !out || rows < 1 || D < 1 || (gate != nullptr && (!(keep > 0.f) || rps < 1)) || (want != 0 && want != 1)) return UU3D_ERR_INVALID_ARGUMENT;
+    if ((double)rows * D >= 2147483648.0) return UU3D_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(scale_rows_kernel, ew_grid((long long)rows * D), dim3(256), 0, (hipStream_t)stream, in, rows, D, gate, keep, rps, row_mask, want, out);
     return hip_status();
 }
