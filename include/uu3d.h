@@ -996,6 +996,46 @@ int uu3d_solve_view_pose(const double* partial_dev, int32_t views, int64_t chunk
                          double* pose_out_dev, int32_t* terms_dev, void* stream);
 
 /*
+ * WHO IS WHO WITHOUT A WORLD (predict.lift_pair_sums, predict.match_lifts, predict.predict_views(match=MatchLifts(...))): WHO IS WHO
+ * compares pixel rays in world axes, and cameras that WHERE THE CAMERAS STAND has yet to place share no world.  Matching does not need
+ * rays: every view's lift is the same skeleton in that camera's own axes, so two tracks of different views are the same person iff their
+ * lifts agree up to ONE rotation over the whole track, and Horn's largest eigenvalue gives the residual of that best rotation in closed
+ * form.  The call here fills the (M, M) tables uu3d_group_views takes; uu3d_gather_view_tracks lays the tracks out as before.
+ * predict.lift_pair_sums_host is the same rule in numpy, bit for bit.  In float64 on the float32 inputs, every operation rounded once, no
+ * fused multiply-add, correctly rounded square root and division; the order of every sum is part of the rule.
+ * INPUTS.  M tracks of one common length T, 1 <= M <= 64, view-major: view_of_host (M) i32 in HOST memory, ascending, as in WHO IS WHO.
+ * poses_dev (M, T, J, 3) f32: every track's lifts, root-relative, in its camera's OWN axes; kp2d_dev (M, T, J, 2) f32 in the model's
+ * layout; joint_flags_dev (M, T, J) u8 or NULL.  USED and SEES are the tests of SEVERAL VIEWS: track p sees frame f iff at least
+ * min_joints of its joints are used there.
+ * TERMS.  For tracks p < q of DIFFERENT views, frame f is a term iff both see it.  Eleven values per term, a the lift of p and b the lift
+ * of q at the frame:
+ *     s_ik = 0.0;  s_ik = s_ik + a[j][i] * b[j][k] over ALL J joints ascending, ik = 00, 01, 02, 10, ..., 22 -- the per-term values of
+ *         uu3d_view_moment_sums, the same device function (an unobserved joint's lift is still read)
+ *     e = 0.0;  e = e + (((a0 a0 + a1 a1) + a2 a2) + ((b0 b0 + b1 b1) + b2 b2)) over the joints ascending
+ *     1.0
+ * ORDER.  That of PAIR SUMS: lane l of 256 adds the values of the terms among frames l, l + 256, ... ascending to 0.0; then for stride =
+ * 128, 64, ..., 1: x[l] = x[l] + x[l + stride] for l < stride, one value after the other.  There are no chunks.  x[0]: M (nine), E, n.
+ * FINISH.  Horn's matrix of M and the 10 Jacobi sweeps of WHERE THE CAMERAS STAND, step 2 -- the same device function --; top = the
+ * largest diagonal entry (top = N00; for i = 1, 2, 3: N_ii > top replaces it).  S = (E - 2.0 top) / (double) J; S < 0.0 becomes 0.0; top
+ * or S not finite: S = 0.0 and no terms.  sums[p][q] = sums[q][p] = S, terms[p][q] = terms[q][p] = n, the number of term FRAMES.
+ * Same-view pairs and the diagonal hold 0.0 and 0.
+ * MEANING.  S / n is the mean over the term frames of the mean squared joint distance, in the poses' units, after the best common
+ * rotation: what uu3d_group_views compares with max_dist * max_dist; its min_terms counts frames here.  Two persons with the same body
+ * who move alike cannot be told apart, and short or noisy tracks close the gap between a true and a wrong pair; the lifts of a real model
+ * carry view-dependent errors that are not modelled.  No matching accuracy is claimed.
+ *
+ *   uu3d_lift_pair_sums(poses_dev, kp2d_dev 8-byte aligned, joint_flags_dev or NULL, view_of_host, tracks, frames, J, views, min_joints,
+ *       sums_dev (M, M) f64, terms_dev (M, M) i32, stream): one launch, one workgroup of 256 lanes per unordered pair p <= q; the fixed
+ *       tree runs through LDS, lane 0 finishes and writes both mirrored elements.  frames * J must stay below 2^31.
+ * tracks > 64, J > 64 or views > 8: UU3D_ERR_UNSUPPORTED; tracks < 1, frames < 1, J < 1, min_joints < 2, NULLs, misalignment or a
+ * view_of_host that does not ascend: UU3D_ERR_INVALID_ARGUMENT -- every guard before any device call.  Every output element has one
+ * writer, no atomics, the inputs are only read, nothing copies to the host or waits: bitwise repeatable.
+ */
+int uu3d_lift_pair_sums(const float* poses_dev, const float* kp2d_dev, const uint8_t* joint_flags_dev, const int32_t* view_of_host,
+                        int32_t tracks, int64_t frames, int32_t num_keypoints, int32_t views, int32_t min_joints, double* sums_dev,
+                        int32_t* terms_dev, void* stream);
+
+/*
  * ANY FRAME RATE (predict.predict_tracks(fps=...)): the front of YOUR OWN 2D TRACKS for tracks that were not filmed at the rate the model
  * was trained for.  The table holds the MODEL's time grid: row `row` (track row_track_dev[row]) is model frame k of its track, which sits at
  * source position p_k = k * fps / model_fps.  The host works the positions out in exact integer arithmetic (predict.resample_plan) and

@@ -18,8 +18,12 @@ host route: the call without it with ``return_views=True``, ``.cpu()``, then ``f
 cameras it returns, and ``calibrate_views`` on that call's lifts and keypoints beside ``calibrate_views_host`` (the mirror once).  With
 seeded weights the lifts are not poses, so the cameras found are not the true ones: only the time is read.
 
+``--match_lifts`` times ``predict_views(match=MatchLifts(...))`` on the shuffled views of ``--match`` beside ``predict_tracks``, ``.cpu()``,
+``match_lifts_host`` and today's ``predict_views`` on the views regrouped per person, and ``match_lifts`` on that call's lifts beside its
+mirror (the mirror once).  With seeded weights the lifts are not poses, so ``max_dist`` allows every pair: only the time is read.
+
     python tools/predict_views_bench.py [--config h36m_81] [--persons 2] [--frames 1000]
-                                        [--match | --align [--max_lag 50] | --triangulate | --calibrate]
+                                        [--match | --align [--max_lag 50] | --triangulate | --calibrate | --match_lifts]
 """
 import argparse
 import json
@@ -273,6 +277,51 @@ def _calibrate_rows(model, cfg, args):
     return rows
 
 
+def _match_lifts_rows(model, cfg, args):
+    import torch
+    from uplift_upsample_3dhpe_amd import predict
+    J, N, T = int(cfg.NUM_KEYPOINTS), max(args.persons, 2), args.frames
+    kw = dict(resolutions=(1024, 1024))
+    cams = _cameras(3)
+    views, _ = _shuffled(cams, N, T, J)
+    counts = [len(v) for v in views]
+    view_of = np.repeat(np.arange(3, dtype=np.int32), counts)
+    flat = [t for tracks in views for t in tracks]
+    M = len(flat)
+    pinhole = [cams[v].without(distortion=True, extrinsics=True) for v in view_of]
+    params = dict(max_dist=10.0, min_terms=50)                           # seeded weights: the lifts are not poses, so every pair is allowed
+
+    def lifts():
+        return torch.cat(predict.predict_tracks(model, cfg, flat, camera=pinhole, **kw)[0], 0).reshape(M, T, J, 3)
+
+    def device():
+        r = predict.predict_views(model, cfg, views, cams, match=predict.MatchLifts(**params), **kw)
+        return [torch.cat(a, 0).cpu() for a in r[:4]], r[-1]
+
+    def host():
+        person, n, table, _, _ = predict.match_lifts_host(lifts().cpu().numpy(), np.stack(flat), view_of, None, 3, **params)
+        gone = np.full((T, J, 2), np.nan, np.float32)
+        regrouped = [[flat[m] if m >= 0 else gone for m in table[v, :int(n[0])]] for v in range(len(cams))]
+        return [torch.cat(a, 0).cpu() for a in predict.predict_views(model, cfg, regrouped, cams, valid="finite", **kw)], person
+
+    device(), host()
+    a, b = device(), host()
+    ok = [k for per_view in a[1] for k in per_view] == [int(k) for k in b[1]]
+    rows = [dict(row="predict_views(match=MatchLifts)", views=3, persons=N, tracks=M, frames=T, device_ms=round(_median(lambda: device()), 2),
+                 host_match_then_predict_views_ms=round(_median(lambda: host()), 2), same_persons_as_host=bool(ok))]
+    # match_lifts alone on that call's lifts and keypoints, beside its mirror (the mirror once)
+    poses, kp = lifts().contiguous(), torch.from_numpy(np.stack(flat)).cuda()
+    got = [r.cpu().numpy() for r in predict.match_lifts(poses, kp, view_of, **params)]
+    t0 = time.perf_counter()
+    want = predict.match_lifts_host(poses.cpu().numpy(), kp.cpu().numpy(), view_of, **params)
+    mirror_ms = (time.perf_counter() - t0) * 1e3
+    same = all(np.array_equal(g.view(np.uint8), w.view(np.uint8)) for g, w in zip(got, want))
+    rows.append(dict(row="match_lifts", tracks=M, frames=T, joints=J, device_ms=round(_median(lambda: predict.match_lifts(poses, kp, view_of, **params)), 3),
+                     device_then_cpu_ms=round(_median(lambda: [r.cpu() for r in predict.match_lifts(poses, kp, view_of, **params)]), 3),
+                     mirror_ms_one_run=round(mirror_ms, 1), bits_equal=bool(same), persons=int(want[1][0])))
+    return rows
+
+
 def _median(fn, n=3):
     import torch
     times = []
@@ -294,6 +343,7 @@ def main(argv=None):
     p.add_argument("--align", action="store_true", help="time align_views and predict_views(align=True) instead")
     p.add_argument("--triangulate", action="store_true", help="time predict_views(triangulate=True) beside the call without it and the host route")
     p.add_argument("--calibrate", action="store_true", help="time predict_views(calibrate=True) beside the call on the returned cameras, and calibrate_views beside its mirror")
+    p.add_argument("--match_lifts", action="store_true", help="time predict_views(match=MatchLifts(...)) beside match_lifts_host and the regrouped call, and match_lifts beside its mirror")
     p.add_argument("--max_lag", type=int, default=50, help="the largest clock offset looked for with --align, in frames")
     args = p.parse_args(argv)
     import torch
@@ -314,6 +364,9 @@ def main(argv=None):
         return 0
     if args.calibrate:
         print(json.dumps(dict(config=args.config, rows=_calibrate_rows(model, cfg, args))))
+        return 0
+    if args.match_lifts:
+        print(json.dumps(dict(config=args.config, rows=_match_lifts_rows(model, cfg, args))))
         return 0
     J, N = int(cfg.NUM_KEYPOINTS), args.persons
     kw = dict(resolutions=(1024, 1024))

@@ -59,6 +59,7 @@ EXPORTED_SYMBOLS = (
     "uu3d_view_lag_scratch_bytes", "uu3d_view_lag_sums", "uu3d_view_offsets",
     "uu3d_triangulate_joints", "uu3d_place_joints",
     "uu3d_view_calibrate_chunks", "uu3d_view_moment_sums", "uu3d_view_position_sums", "uu3d_solve_view_pose",
+    "uu3d_lift_pair_sums",
 )
 # include/uu3d_ops.h
 OPS_SYMBOLS = (
@@ -441,6 +442,9 @@ def load_library(path=None):
     lib.uu3d_view_position_sums.argtypes = [vp, vp, vp, i32, i64, i32, vp, i32, vp, vp, vp]
     lib.uu3d_solve_view_pose.restype = C.c_int
     lib.uu3d_solve_view_pose.argtypes = [vp, i32, i64, i32, i32, vp, vp, vp, vp]
+    # who is who without a world: view_of is HOST memory, as in who is who
+    lib.uu3d_lift_pair_sums.restype = C.c_int
+    lib.uu3d_lift_pair_sums.argtypes = [vp, vp, vp, C.POINTER(i32), i32, i64, i32, i32, i32, vp, vp, vp]
     lib.uu3d_joint_rotations.restype = C.c_int
     lib.uu3d_joint_rotations.argtypes = [vp, i64, i32, vp, i32] + [vp] * 6
     lib.uu3d_joint_rotations_reset.restype = C.c_int

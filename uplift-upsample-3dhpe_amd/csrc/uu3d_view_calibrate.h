@@ -14,7 +14,8 @@
 // lifts in each camera's own axes, root-relative --, kp (V, R, J, 2), flags (V, R, J).  Float64 on the float32 inputs, every operation rounded
 // once (contraction off), sqrt and division correctly rounded.  Every output element has one writer, no atomics, the inputs are only read,
 // nothing per lane is indexed by a run-time view number: bitwise repeatable.  The statements are those of predict.view_moment_sums_host /
-// predict.view_position_sums_host / predict.solve_view_pose_host, one for one.
+// predict.view_position_sums_host / predict.solve_view_pose_host, one for one.  lift_moment_products (a term's nine moment products) and
+// horn_jacobi (Horn's matrix through the Jacobi sweeps) are shared with uu3d_lift_match.h, which matches tracks by the same lifts.
 #pragma once
 #include "uu3d_views.h"
 
@@ -75,7 +76,26 @@ __device__ __forceinline__ void calibrate_chunk_zeros(double* __restrict__ out)
     if (threadIdx.x < kCalibrateSums) out[threadIdx.x] = 0.0;
 }
 
-// A row of the rotation: s_ik = sum over ALL J joints ascending of p_v[i] * p_0[k] (an unobserved joint's lift is still read), s_9 = 1.
+// The nine moment products of one term, shared with WHO IS WHO WITHOUT A WORLD (uu3d_lift_match.h) so that the bits cannot drift: a, b = the
+// index of joint 0 of the two lifts in poses; s_ik = 0.0; s_ik = s_ik + p_a[j][i] * p_b[j][k] over ALL J joints ascending (an unobserved
+// joint's lift is still read), ik = 00, 01, 02, 10, ..., 22.
+__device__ __forceinline__ void lift_moment_products(const float* __restrict__ poses, const long a, const long b, const int J, double s[9])
+{
+#pragma clang fp contract(off)
+    double m00 = 0.0, m01 = 0.0, m02 = 0.0, m10 = 0.0, m11 = 0.0, m12 = 0.0, m20 = 0.0, m21 = 0.0, m22 = 0.0;
+    for (int j = 0; j < J; ++j) {
+        const WorldTrio p = *reinterpret_cast<const WorldTrio*>(poses + (a + j) * 3);
+        const WorldTrio q = *reinterpret_cast<const WorldTrio*>(poses + (b + j) * 3);
+        const double p0 = (double)p.a, p1 = (double)p.b, p2 = (double)p.c;
+        const double q0 = (double)q.a, q1 = (double)q.b, q2 = (double)q.c;
+        m00 = m00 + p0 * q0; m01 = m01 + p0 * q1; m02 = m02 + p0 * q2;
+        m10 = m10 + p1 * q0; m11 = m11 + p1 * q1; m12 = m12 + p1 * q2;
+        m20 = m20 + p2 * q0; m21 = m21 + p2 * q1; m22 = m22 + p2 * q2;
+    }
+    s[0] = m00; s[1] = m01; s[2] = m02; s[3] = m10; s[4] = m11; s[5] = m12; s[6] = m20; s[7] = m21; s[8] = m22;
+}
+
+// A row of the rotation: the moment products of view v's lift and view 0's, s_9 = 1.
 struct ViewMomentTerm {
     const float* __restrict__ poses;
     const float* __restrict__ kp;
@@ -84,20 +104,9 @@ struct ViewMomentTerm {
     int J, v, min_joints;
     __device__ __forceinline__ bool operator()(const long r, double (&s)[kCalibrateSums]) const
     {
-#pragma clang fp contract(off)
         const long a0 = r * J, av = ((long)v * rows + r) * J;
         if (!view_sees_row(kp, flags, a0, J, min_joints) || !view_sees_row(kp, flags, av, J, min_joints)) return false;
-        double m00 = 0.0, m01 = 0.0, m02 = 0.0, m10 = 0.0, m11 = 0.0, m12 = 0.0, m20 = 0.0, m21 = 0.0, m22 = 0.0;
-        for (int j = 0; j < J; ++j) {
-            const WorldTrio p = *reinterpret_cast<const WorldTrio*>(poses + (av + j) * 3);
-            const WorldTrio q = *reinterpret_cast<const WorldTrio*>(poses + (a0 + j) * 3);
-            const double p0 = (double)p.a, p1 = (double)p.b, p2 = (double)p.c;
-            const double q0 = (double)q.a, q1 = (double)q.b, q2 = (double)q.c;
-            m00 = m00 + p0 * q0; m01 = m01 + p0 * q1; m02 = m02 + p0 * q2;
-            m10 = m10 + p1 * q0; m11 = m11 + p1 * q1; m12 = m12 + p1 * q2;
-            m20 = m20 + p2 * q0; m21 = m21 + p2 * q1; m22 = m22 + p2 * q2;
-        }
-        s[0] = m00; s[1] = m01; s[2] = m02; s[3] = m10; s[4] = m11; s[5] = m12; s[6] = m20; s[7] = m21; s[8] = m22;
+        lift_moment_products(poses, av, a0, J, s);
         s[9] = 1.0;
         return true;
     }
@@ -275,6 +284,35 @@ view_position_sums_kernel(const float* __restrict__ poses, const float* __restri
         x_ = v3p; y_ = v3q; v3p = c * x_ - sn * y_; v3q = sn * x_ + c * y_;                         \
     }
 
+// Horn's symmetric 4x4 matrix from M = sum of p (x) p' (nine doubles M00, M01, ..., M22) -- its largest eigenvector is the quaternion that
+// turns the p onto the p' --, then kCalibrateSweeps sweeps of cyclic Jacobi without an early exit: the eigenvalues b00 .. b33 (the diagonal)
+// and the eigenvectors, a column each.  Shared by solve_view_pose_kernel and lift_pair_sums_kernel (uu3d_lift_match.h).
+struct HornEigen { double b00, b11, b22, b33, v00, v01, v02, v03, v10, v11, v12, v13, v20, v21, v22, v23, v30, v31, v32, v33; };
+
+__device__ __forceinline__ void horn_jacobi(const double m[9], HornEigen& h)
+{
+#pragma clang fp contract(off)
+    const double m00 = m[0], m01 = m[1], m02 = m[2], m10 = m[3], m11 = m[4], m12 = m[5], m20 = m[6], m21 = m[7], m22 = m[8];
+    double b00 = (m00 + m11) + m22, b01 = m12 - m21, b02 = m20 - m02, b03 = m01 - m10;
+    double b11 = (m00 - m11) - m22, b12 = m01 + m10, b13 = m20 + m02;
+    double b22 = (m11 - m00) - m22, b23 = m12 + m21;
+    double b33 = (m22 - m00) - m11;
+    double v00 = 1.0, v01 = 0.0, v02 = 0.0, v03 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v13 = 0.0;
+    double v20 = 0.0, v21 = 0.0, v22 = 1.0, v23 = 0.0, v30 = 0.0, v31 = 0.0, v32 = 0.0, v33 = 1.0;
+#pragma unroll 1
+    for (int sweep = 0; sweep < kCalibrateSweeps; ++sweep) {
+        UU3D_JACOBI_ROT4(b00, b11, b01, b02, b12, b03, b13, v00, v01, v10, v11, v20, v21, v30, v31)
+        UU3D_JACOBI_ROT4(b00, b22, b02, b01, b12, b03, b23, v00, v02, v10, v12, v20, v22, v30, v32)
+        UU3D_JACOBI_ROT4(b00, b33, b03, b01, b13, b02, b23, v00, v03, v10, v13, v20, v23, v30, v33)
+        UU3D_JACOBI_ROT4(b11, b22, b12, b01, b02, b13, b23, v01, v02, v11, v12, v21, v22, v31, v32)
+        UU3D_JACOBI_ROT4(b11, b33, b13, b01, b03, b12, b23, v01, v03, v11, v13, v21, v23, v31, v33)
+        UU3D_JACOBI_ROT4(b22, b33, b23, b02, b03, b12, b13, v02, v03, v12, v13, v22, v23, v32, v33)
+    }
+    h.b00 = b00; h.b11 = b11; h.b22 = b22; h.b33 = b33;
+    h.v00 = v00; h.v01 = v01; h.v02 = v02; h.v03 = v03; h.v10 = v10; h.v11 = v11; h.v12 = v12; h.v13 = v13;
+    h.v20 = v20; h.v21 = v21; h.v22 = v22; h.v23 = v23; h.v30 = v30; h.v31 = v31; h.v32 = v32; h.v33 = v33;
+}
+
 // One wave, lane v = view v.  partial (V, C, 10) f64 of one of the sum kernels; the lane adds its chunks in ascending order from 0.0.
 // stage 0 (partial = the moment sums; pose_in unused): pose_out[v] = the quaternion that turns view v's axes onto view 0's, zeros, the state;
 //     terms[v] = the rows both views see.  View 0: the identity, state 1, terms 0.  A refused view: the identity, state 0.
@@ -323,23 +361,12 @@ solve_view_pose_kernel(const double* __restrict__ partial, const int views, cons
     }
     double q0 = 1.0, q1 = 0.0, q2 = 0.0, q3 = 0.0, state = 1.0;
     if (v != 0) {
-        // Horn's matrix from M = sum of p_v (x) p_0: its largest eigenvector is the quaternion that turns p_v onto p_0
-        const double m00 = x0, m01 = x1, m02 = x2, m10 = x3, m11 = x4, m12 = x5, m20 = x6, m21 = x7, m22 = x8;
-        double b00 = (m00 + m11) + m22, b01 = m12 - m21, b02 = m20 - m02, b03 = m01 - m10;
-        double b11 = (m00 - m11) - m22, b12 = m01 + m10, b13 = m20 + m02;
-        double b22 = (m11 - m00) - m22, b23 = m12 + m21;
-        double b33 = (m22 - m00) - m11;
-        double v00 = 1.0, v01 = 0.0, v02 = 0.0, v03 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v13 = 0.0;
-        double v20 = 0.0, v21 = 0.0, v22 = 1.0, v23 = 0.0, v30 = 0.0, v31 = 0.0, v32 = 0.0, v33 = 1.0;
-#pragma unroll 1
-        for (int sweep = 0; sweep < kCalibrateSweeps; ++sweep) {
-            UU3D_JACOBI_ROT4(b00, b11, b01, b02, b12, b03, b13, v00, v01, v10, v11, v20, v21, v30, v31)
-            UU3D_JACOBI_ROT4(b00, b22, b02, b01, b12, b03, b23, v00, v02, v10, v12, v20, v22, v30, v32)
-            UU3D_JACOBI_ROT4(b00, b33, b03, b01, b13, b02, b23, v00, v03, v10, v13, v20, v23, v30, v33)
-            UU3D_JACOBI_ROT4(b11, b22, b12, b01, b02, b13, b23, v01, v02, v11, v12, v21, v22, v31, v32)
-            UU3D_JACOBI_ROT4(b11, b33, b13, b01, b03, b12, b23, v01, v03, v11, v13, v21, v23, v31, v33)
-            UU3D_JACOBI_ROT4(b22, b33, b23, b02, b03, b12, b13, v02, v03, v12, v13, v22, v23, v32, v33)
-        }
+        const double m[9] = {x0, x1, x2, x3, x4, x5, x6, x7, x8};
+        HornEigen h;
+        horn_jacobi(m, h);
+        const double b00 = h.b00, b11 = h.b11, b22 = h.b22, b33 = h.b33;
+        const double v00 = h.v00, v01 = h.v01, v02 = h.v02, v03 = h.v03, v10 = h.v10, v11 = h.v11, v12 = h.v12, v13 = h.v13;
+        const double v20 = h.v20, v21 = h.v21, v22 = h.v22, v23 = h.v23, v30 = h.v30, v31 = h.v31, v32 = h.v32, v33 = h.v33;
         // the column of the largest eigenvalue, ties to the smaller index; `next` = the largest of the others
         double top = b00, next = -__builtin_huge_val();
         double e0 = v00, e1 = v10, e2 = v20, e3 = v30;

@@ -53,7 +53,9 @@ every name is importable from here as before:
                   ``place_joints`` and their ``_host`` mirrors, ``Triangulate``); where the cameras stand:
                   ``predict_views(..., calibrate=True)`` / ``calibrate_views`` / ``calibrated_cameras`` (uu3d_view_moment_sums,
                   uu3d_view_position_sums, uu3d_solve_view_pose; ``view_moment_sums``, ``view_position_sums``, ``solve_view_pose`` and their
-                  ``_host`` mirrors, ``calibrate_views_host``, ``CalibrateViews``)
+                  ``_host`` mirrors, ``calibrate_views_host``, ``CalibrateViews``); who is who without a world:
+                  ``predict_views(..., match=MatchLifts(...))`` / ``match_lifts`` (uu3d_lift_pair_sums; ``lift_pair_sums`` and the ``_host``
+                  mirrors, ``MatchLifts``)
 """
 import argparse
 import types
@@ -94,6 +96,7 @@ from .views import (ALIGN_DEFAULTS, MATCH_DEFAULTS, MATCH_LANES, MAX_ALIGN_LAG, 
                     view_lag_sums_host, view_offsets, view_offsets_host, view_pair_sums, view_pair_sums_host, view_rows)
 from .views import (VIEW_CALIBRATE_DEFAULTS, CalibrateViews, calibrate_views, calibrate_views_host, calibrated_cameras, check_calibrate,  # noqa: F401
                     solve_view_pose, solve_view_pose_host, view_moment_sums, view_moment_sums_host, view_position_sums, view_position_sums_host)
+from .views import LIFT_MATCH_DEFAULTS, MatchLifts, lift_pair_sums, lift_pair_sums_host, match_lifts, match_lifts_host  # noqa: F401
 from .validity import (_device_joint_flags, _device_valid, _front_validity, _source_joint_flags, check_repair_joints, check_valid,  # noqa: F401
                        repair_joints, repair_joints_host)
 

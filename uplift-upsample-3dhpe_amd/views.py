@@ -72,7 +72,20 @@ runs behind the stage, does not rescale it.  Calibration is against view 0 only,
 unit weight in an algebraic error, so near and far frames count alike; a person who only stands still fixes the position poorly; the
 view-dependent depth errors of real lifts are not modelled.  ``VIEW_CALIBRATE_DEFAULTS`` is a convenience, not a tuned value.
 
-Out of scope: sub-frame offsets and per-camera frame rates, per-view confidence weights, rescaling a calibrated rig to known lengths,
+Who is who without a world -- ``predict_views(..., match=MatchLifts(...))`` / ``match_lifts`` / ``lift_pair_sums``: ``match=True`` compares
+pixel rays in world axes, and cameras that ``calibrate`` has yet to place share no world.  Matching does not need rays: every view's lift
+is the same skeleton in that camera's own axes, so two tracks of different views are the same person iff their lifts agree up to ONE
+rotation over the whole track.  With a ``MatchLifts``, with or without ``calibrate``, the M tracks run through the one front as given, and
+  1'. uu3d_lift_pair_sums sums, per pair of tracks of different views and over the frames both see, p (x) q, |p|^2 + |q|^2 and the frames;
+      Horn's largest eigenvalue (the Jacobi sweeps of step 1b) gives the squared joint distance left after the best common rotation in
+      closed form (``lift_pair_sums_host``),
+  2'. uu3d_group_views groups the tracks as in step 0b, ``min_terms`` counting frames, and the ONE copy of step 0c tells the host,
+  3'. uu3d_gather_view_tracks lays the lifts out per person while they are still in camera axes; ``calibrate`` then runs steps 1a to 1e
+      on those buffers -- a (view, person) pair without a track is rows the view does not SEE --, and the lifts go to world axes.
+Two persons with one body who move alike cannot be told apart, and short or noisy tracks close the gap between a true and a wrong pair;
+``LIFT_MATCH_DEFAULTS`` are conveniences for metres and frames, not tuned values: no matching accuracy is claimed.
+
+Out of scope: estimating ``align`` without a world, sub-frame offsets and per-camera frame rates, per-view confidence weights, rescaling a calibrated rig to known lengths,
 calibration chained through a third camera, estimating intrinsics, a live form, command-line flags.  No accuracy is claimed."""
 import ctypes as C
 
@@ -100,6 +113,8 @@ CALIBRATE_SUMS = 10                                                    # kCalibr
 CALIBRATE_SWEEPS = 10                                                  # kCalibrateSweeps: cyclic Jacobi sweeps of the 4 x 4, no early exit
 CALIBRATE_POSE = 8                                                     # kCalibratePose: the quaternion, the position, the state
 CALIBRATE_GAP = 2.0 ** -20                                             # kCalibrateGap: the two largest eigenvalues must differ by this share
+LIFT_MATCH_DEFAULTS = dict(max_dist=0.1, min_terms=50)                 # metres and frames; conveniences, not tuned values
+LIFT_PAIR_SUMS = 11                                                    # kLiftPairSums: nine moment products, the squared size, 1.0
 
 
 def check_view_cameras(cameras, views=None):
@@ -646,18 +661,37 @@ def _chunk_sums(values, term):
     4096 rows, lane l of 256 adds the values of the terms among its rows l, l + 256, ... ascending to 0.0, then the fixed tree."""
     R = values.shape[0]
     out = np.zeros((calibrate_chunks(R), CALIBRATE_SUMS), np.float64)
-    with np.errstate(all="ignore"):
-        for c in range(out.shape[0]):
-            x = np.zeros((MATCH_LANES, CALIBRATE_SUMS), np.float64)
-            for first in range(c * CALIBRATE_CHUNK, min(R, (c + 1) * CALIBRATE_CHUNK), MATCH_LANES):
-                part, t = values[first:first + MATCH_LANES], term[first:first + MATCH_LANES]
-                x[:len(part)] = np.where(t[:, None], x[:len(part)] + part, x[:len(part)])
-            stride = MATCH_LANES // 2
-            while stride >= 1:                                           # the fixed tree
-                x[:stride] = x[:stride] + x[stride:2 * stride]
-                stride //= 2
-            out[c] = x[0]
+    for c in range(out.shape[0]):
+        out[c] = _lane_sums(values[c * CALIBRATE_CHUNK:(c + 1) * CALIBRATE_CHUNK], term[c * CALIBRATE_CHUNK:(c + 1) * CALIBRATE_CHUNK])
     return out
+
+
+def _lane_sums(values, term):
+    """One workgroup's sums, shared by WHERE THE CAMERAS STAND (per chunk) and WHO IS WHO WITHOUT A WORLD (per pair): ``values`` (R, n)
+    float64, ``term`` (R,) bool -> (n,) float64.  Lane l of 256 adds the values of the terms among its rows l, l + 256, ... ascending to
+    0.0, then for stride = 128, 64, ..., 1: x[l] = x[l] + x[l + stride] for l < stride."""
+    x = np.zeros((MATCH_LANES, values.shape[1]), np.float64)
+    with np.errstate(all="ignore"):
+        for first in range(0, values.shape[0], MATCH_LANES):
+            part, t = values[first:first + MATCH_LANES], term[first:first + MATCH_LANES]
+            x[:len(part)] = np.where(t[:, None], x[:len(part)] + part, x[:len(part)])
+        stride = MATCH_LANES // 2
+        while stride >= 1:                                               # the fixed tree
+            x[:stride] = x[:stride] + x[stride:2 * stride]
+            stride //= 2
+    return x[0].copy()
+
+
+def _moment_products(a, b):
+    """The nine moment products of every row, shared by ``view_moment_sums_host`` and ``lift_pair_sums_host``: ``a``, ``b`` (R, J, 3)
+    float64 -> (R, 9): s_ik = 0.0; s_ik = s_ik + a[j][i] * b[j][k] over ALL J joints ascending, ik = 00, 01, 02, 10, ..., 22."""
+    s = np.zeros((a.shape[0], 9), np.float64)
+    with np.errstate(all="ignore"):
+        for j in range(a.shape[1]):
+            for i in range(3):
+                for k in range(3):
+                    s[:, 3 * i + k] = s[:, 3 * i + k] + a[:, j, i] * b[:, j, k]
+    return s
 
 
 def _calibrate_arrays(poses, kp2d, flags, min_root_joints):
@@ -682,12 +716,8 @@ def view_moment_sums_host(poses, kp2d, flags=None, min_root_joints=DEFAULT_MIN_R
     out = np.zeros((V, calibrate_chunks(R), CALIBRATE_SUMS), np.float64)
     with np.errstate(all="ignore"):
         for v in range(1, V):
-            s = np.zeros((R, CALIBRATE_SUMS), np.float64)
-            for j in range(J):
-                for i in range(3):
-                    for k in range(3):
-                        s[:, 3 * i + k] = s[:, 3 * i + k] + P[v, :, j, i] * P[0, :, j, k]
-            s[:, 9] = 1.0
+            s = np.ones((R, CALIBRATE_SUMS), np.float64)                 # (the tenth value: 1.0)
+            s[:, :9] = _moment_products(P[v], P[0])
             out[v] = _chunk_sums(s, sees[0] & sees[v])
     return out
 
@@ -1026,13 +1056,15 @@ def _match_parameters(max_dist, min_terms):
 
 
 def check_match(match):
-    """``predict_views(match=...)`` -> None (the views are given person by person) or a ``MatchViews``; True is the defaults."""
+    """``predict_views(match=...)`` -> None (the views are given person by person), a ``MatchViews`` (True is its defaults: the rays are
+    matched in the world) or a ``MatchLifts`` (the lifts are matched, which needs no world)."""
     if match is None or match is False:
         return None
     if match is True:
         return MatchViews()
-    if not isinstance(match, MatchViews):
-        raise ValueError(f"match must be None, True or a MatchViews(max_dist=, min_terms=), got {match!r}")
+    if not isinstance(match, (MatchViews, MatchLifts)):
+        raise ValueError(f"match must be None, True or a MatchViews(max_dist=, min_terms=) -- or a MatchLifts(max_dist=, min_terms=), which "
+                         f"needs no world --, got {match!r}")
     return match
 
 
@@ -1435,6 +1467,138 @@ def match_views(views, cameras, valid=None, max_dist=MATCH_DEFAULTS["max_dist"],
         device = on[0] if on else torch.device("cuda", torch.cuda.current_device())
     tr, _ = _undistorted_tracks(flat, cams, counts, torch.device(device))
     return _match_device(tr, cams, counts, flat_valid, params)
+
+
+# ---- who is who without a world: tracks matched by their lifts (include/uu3d.h, WHO IS WHO WITHOUT A WORLD) ------------------------------
+class MatchLifts(object):
+    """The parameters of ``predict_views(match=MatchLifts(...))`` / ``match_lifts``: ``max_dist``, the largest root-mean-square distance
+    between the joints of two tracks' lifts after the best common rotation, in the poses' units, at which the two may be one person
+    (finite, >= 0), and ``min_terms``, the least number of FRAMES both tracks must see (an int >= 1).  The defaults are conveniences for
+    metres and frames, not tuned values."""
+
+    def __init__(self, max_dist=LIFT_MATCH_DEFAULTS["max_dist"], min_terms=LIFT_MATCH_DEFAULTS["min_terms"]):
+        self.max_dist, self.min_terms = _match_parameters(max_dist, min_terms)
+
+    def __repr__(self):
+        return f"MatchLifts(max_dist={self.max_dist!r}, min_terms={self.min_terms!r})"
+
+
+def _lift_shapes(poses_shape, kp_shape, flags_shape, view_of, views):
+    """The shapes of a lift-pair-sums call, checked -> (view_of int32, V, M, T, J)."""
+    view_of, V, M, T, J = _pair_shapes(kp_shape, flags_shape, view_of, (views,))
+    if tuple(poses_shape) != (M, T, J, 3):
+        raise ValueError(f"poses must be ({M}, {T}, {J}, 3) beside kp2d, got {tuple(poses_shape)}")
+    return view_of, V, M, T, J
+
+
+def lift_pair_sums_host(poses, kp2d, view_of, flags=None, views=None, min_root_joints=DEFAULT_MIN_ROOT_JOINTS, totals=False):
+    """The lift test of WHO IS WHO WITHOUT A WORLD (include/uu3d.h) in numpy, written to be read: what uu3d_lift_pair_sums computes, bit
+    for bit.  ``poses`` (M, T, J, 3): M tracks of T frames, view-major, every track's lifts, root-relative, in its camera's OWN axes
+    (read as float32); ``kp2d`` (M, T, J, 2): the 2D keypoints in the model's layout; ``view_of`` (M,): the view of every track, ascending;
+    ``flags``: None or (M, T, J), non-zero = the joint was observed; ``views`` = V (None: the last entry of ``view_of`` + 1)
+    -> (sums (M, M) float64, terms (M, M) int32), both symmetric; with ``totals`` also the eleven sums of every pair p < q, (M, M, 11).
+    Everything in float64, every operation rounded once.  Track p SEES frame f iff at least ``min_root_joints`` of its joints are used
+    there (``fuse_views_host``).  For tracks p < q of DIFFERENT views, frame f is a TERM iff both see it; its eleven values, a the lift
+    of p and b the lift of q: the nine moment products s_ik = sum over ALL J joints ascending of a[j][i] * b[j][k] (the per-term values
+    of ``view_moment_sums_host``, the same function); e = 0.0; e = e + (((a0 a0 + a1 a1) + a2 a2) + ((b0 b0 + b1 b1) + b2 b2)) over the
+    joints ascending; and 1.0.  The order of summation is that of ``view_pair_sums_host``: lane l of ``MATCH_LANES`` = 256 adds the
+    terms among frames l, l + 256, ... ascending to 0.0, then the fixed tree; there are no chunks.  With M (nine), E and n the sums:
+    ``horn_matrix`` of M, ``jacobi_eigen4``, top = the largest eigenvalue (top = lam_0; for i = 1, 2, 3: lam_i > top replaces it);
+    S = (E - 2.0 top) / float(J); S < 0.0 becomes 0.0; top or S not finite: S = 0.0 and no terms.  sums[p][q] = sums[q][p] = S,
+    terms[p][q] = terms[q][p] = n, the number of term FRAMES.  Same-view pairs and the diagonal hold 0.0 and 0.
+    S / n is the mean squared joint distance after the best common rotation: sum |a_j - R b_j|^2 = E - 2 max_R sum a_j . R b_j, and
+    Horn's largest eigenvalue is that maximum.  Two persons with one body who move alike cannot be told apart."""
+    P = np.asarray(_host_array(poses), np.float32)
+    uv = np.asarray(_host_array(kp2d), np.float32)
+    f = None if flags is None else np.asarray(_host_array(flags)) != 0
+    view_of, V, M, T, J = _lift_shapes(P.shape, uv.shape, None if f is None else f.shape, view_of, views)
+    m = check_min_root_joints(min_root_joints)
+    used = np.isfinite(uv).all(axis=3)
+    if f is not None:
+        used &= f
+    sees = used.sum(axis=2) >= m                                         # (M, T)
+    P64 = P.astype(np.float64)
+    sums, terms = np.zeros((M, M), np.float64), np.zeros((M, M), np.int32)
+    every = np.zeros((M, M, LIFT_PAIR_SUMS), np.float64)
+    two = np.float64(2.0)
+    with np.errstate(all="ignore"):
+        for p in range(M):
+            for q in range(p + 1, M):
+                if view_of[p] == view_of[q]:
+                    continue
+                a, b = P64[p], P64[q]
+                s = np.ones((T, LIFT_PAIR_SUMS), np.float64)             # (the eleventh value: 1.0)
+                s[:, :9] = _moment_products(a, b)
+                e = np.zeros(T, np.float64)
+                for j in range(J):
+                    e = e + (((a[:, j, 0] * a[:, j, 0] + a[:, j, 1] * a[:, j, 1]) + a[:, j, 2] * a[:, j, 2]) +
+                             ((b[:, j, 0] * b[:, j, 0] + b[:, j, 1] * b[:, j, 1]) + b[:, j, 2] * b[:, j, 2]))
+                s[:, 9] = e
+                x = _lane_sums(s, sees[p] & sees[q])
+                every[p, q] = x
+                lam, _ = jacobi_eigen4(horn_matrix(x[:9]))
+                top = lam[0]
+                for i in range(1, 4):
+                    if lam[i] > top:
+                        top = lam[i]
+                S = (x[9] - two * top) / np.float64(J)
+                if S < 0.0:
+                    S = np.float64(0.0)
+                n = int(x[10])
+                if not np.isfinite(top) or not np.isfinite(S):
+                    S, n = np.float64(0.0), 0
+                sums[p, q] = sums[q, p] = S
+                terms[p, q] = terms[q, p] = n
+    return (sums, terms, every) if totals else (sums, terms)
+
+
+def lift_pair_sums(poses, kp2d, view_of, flags=None, views=None, min_root_joints=DEFAULT_MIN_ROOT_JOINTS):
+    """uu3d_lift_pair_sums on the current stream: ``lift_pair_sums_host`` on device tensors, one launch, nothing copies to the host or
+    waits (``view_of`` is a host array).  ``poses`` (M, T, J, 3) float32 and ``kp2d`` (M, T, J, 2) float32 on the device, contiguous (only
+    read); ``flags`` (M, T, J) uint8 / bool on the device or None -> (sums (M, M) float64, terms (M, M) int32), fresh device buffers.
+    Needs no model."""
+    import torch
+    lib = _capi.load_library()
+    if not _is_device(kp2d, torch.float32) or not _is_device(poses, torch.float32, kp2d.device):
+        raise ValueError(f"poses (M, T, J, 3) and kp2d (M, T, J, 2) must be contiguous float32 tensors on one device, got "
+                         f"{tuple(getattr(poses, 'shape', ()))} and {tuple(getattr(kp2d, 'shape', ()))}")
+    if flags is not None and not _is_device(flags, (torch.uint8, torch.bool), kp2d.device):
+        raise ValueError("flags must be a contiguous (M, T, J) uint8 or bool tensor on kp2d's device")
+    view_of, V, M, T, J = _lift_shapes(tuple(poses.shape), tuple(kp2d.shape), None if flags is None else tuple(flags.shape), view_of, views)
+    m = check_min_root_joints(min_root_joints)
+    dev = kp2d.device
+    sums = torch.empty((M, M), dtype=torch.float64, device=dev)
+    terms = torch.empty((M, M), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _capi.check(lib, lib.uu3d_lift_pair_sums(_ptr(poses), _ptr(kp2d), _ptr(None if flags is None else flags.view(torch.uint8)),
+                                                 view_of.ctypes.data_as(C.POINTER(C.c_int32)), M, T, J, V, m, _ptr(sums), _ptr(terms),
+                                                 C.c_void_p(stream)), None)
+    return sums, terms
+
+
+def match_lifts_host(poses, kp2d, view_of, flags=None, views=None, min_root_joints=DEFAULT_MIN_ROOT_JOINTS,
+                     max_dist=LIFT_MATCH_DEFAULTS["max_dist"], min_terms=LIFT_MATCH_DEFAULTS["min_terms"]):
+    """``match_lifts`` built from the mirrors -- ``lift_pair_sums_host``, ``group_views_host`` -- on host arrays
+    -> (person (M,) int32, n_persons (1,) int32, table (V, M) int32, sums (M, M) float64, terms (M, M) int32)."""
+    params = MatchLifts(max_dist, min_terms)
+    sums, terms = lift_pair_sums_host(poses, kp2d, view_of, flags, views, min_root_joints)
+    return group_views_host(sums, terms, view_of, views, params.max_dist, params.min_terms) + (sums, terms)
+
+
+def match_lifts(poses, kp2d, view_of, flags=None, views=None, min_root_joints=DEFAULT_MIN_ROOT_JOINTS,
+                max_dist=LIFT_MATCH_DEFAULTS["max_dist"], min_terms=LIFT_MATCH_DEFAULTS["min_terms"]):
+    """Who is who across V cameras that share no world, on the device: uu3d_lift_pair_sums, then uu3d_group_views -- two launches, nothing
+    copies to the host or waits.  ``poses`` (M, T, J, 3) float32: the lifts of M tracks of one length and one clock, view-major, each in
+    its camera's OWN axes (the output of the model, not taken to world axes); ``kp2d`` (M, T, J, 2) float32 in the model's layout and
+    ``flags`` (M, T, J) uint8 / bool or None, on the device, contiguous (only read); ``view_of`` (M,): the view of every track, ascending,
+    on the host -> (person (M,) int32: the person of every track, n_persons (1,) int32, table (V, M) int32, sums (M, M) float64, terms
+    (M, M) int32) on the device.  The rules stand in ``lift_pair_sums_host`` and ``group_views_host``; ``match_lifts_host`` is the same
+    call on the host, and the two agree bit for bit.  ``max_dist`` (the poses' units) and ``min_terms`` (frames) default to
+    ``LIFT_MATCH_DEFAULTS``: conveniences, not tuned values; no matching accuracy is claimed.  Needs no model."""
+    params = MatchLifts(max_dist, min_terms)
+    sums, terms = lift_pair_sums(poses, kp2d, view_of, flags, views, min_root_joints)
+    return group_views(sums, terms, view_of, views, params.max_dist, params.min_terms) + (sums, terms)
 
 
 # ---- one clock: which frame of one camera is which of another (include/uu3d.h, ONE CLOCK) ----------------------------------------------
@@ -2003,8 +2167,8 @@ def predict_views(model, config, views, cameras, resolutions=None, mask_stride=N
     (``VIEW_CALIBRATE_DEFAULTS``) or a ``CalibrateViews(min_terms=)``; anything else is a ValueError.  ``cameras`` are V ``Camera`` objects
     with intrinsics, each with or without distortion; cameras 1 .. V - 1 come WITHOUT extrinsics (one that has them is a ValueError that
     names it), camera 0 may keep its own, which then define the world -- without, the world is camera 0's own space.  The same index is
-    the same person on one clock: ``match`` and an ``align`` that estimates (True, an ``AlignViews``) are refused, since both need the rays
-    in one world; ``align=[o_0, ...]`` with known offsets is taken, it only crops.  Behind the assembly, which runs on pinhole cameras
+    the same person on one clock: ``match=True``, a ``MatchViews`` and an ``align`` that estimates (True, an ``AlignViews``) are refused,
+    since they need the rays in one world (a ``MatchLifts`` does not, see below); ``align=[o_0, ...]`` with known offsets is taken, it only crops.  Behind the assembly, which runs on pinhole cameras
     anyway, and in front of uu3d_camera_to_world the four launches of ``calibrate_views`` run on the lifts in camera axes and the
     keypoints in the model's layout; then the poses are copied to the host -- the ONE copy of the stage, V x 9 float64 (quaternion,
     position, state, terms), which waits for the launches -- and ``calibrated_cameras`` builds every view's ``Camera``.  A view that
@@ -2013,7 +2177,23 @@ def predict_views(model, config, views, cameras, resolutions=None, mask_stride=N
     with extrinsics, ready for a later call without ``calibrate``, and ``calibration``, per view (state, terms); with ``align=[...]``
     the two stand behind ``offsets`` and ``first``.  One view calibrates nothing and returns camera 0 as the world.  The result minus
     its last two items equals, bit for bit, ``predict_views(views, the returned cameras, ...)``.  The rig's scale is the model's; the
-    limits stand in the module's docstring, and no accuracy is claimed."""
+    limits stand in the module's docstring, and no accuracy is claimed.
+
+    Who is who without a world -- ``match=MatchLifts(max_dist=, min_terms=)`` (``LIFT_MATCH_DEFAULTS``: 0.1 m, 50 frames), with or without
+    ``calibrate``: the tracks are matched by their LIFTS, which needs no extrinsics -- two tracks of different views are one person iff
+    their lifts agree up to one rotation over the whole track (``match_lifts``; ``max_dist`` is the root-mean-square joint distance after
+    that rotation, ``min_terms`` the frames both tracks must see).  ``views``, ``fps`` and ``bones`` are taken and refused as ``match=True``
+    takes and refuses them; with ``calibrate`` view 0 must hold a track, since it defines the world.  The M tracks are undistorted and run
+    through the front as given; uu3d_lift_pair_sums and uu3d_group_views run on the lifts in camera axes and the keypoints in the model's
+    layout; ``person``, ``n_persons`` and ``table`` are copied to the host, the ONE copy of the matched route; uu3d_gather_view_tracks lays
+    the lifts out per person BEFORE they go to world axes; with ``calibrate`` the four launches of ``calibrate_views`` run on the gathered
+    (V, P T, ...) buffers, followed by its V x 9 copy and its ValueError that names a view without a pose; uu3d_camera_to_world takes one
+    row per view block, and everything behind runs unchanged on P persons.  -> today's tuple, then ``person``, then, with ``calibrate``,
+    ``cameras`` and ``calibration``, which stay last (``align=[o_0, ...]`` puts ``offsets`` and ``first`` in front of them).  ``align=True``
+    or an ``AlignViews`` is refused with a ``MatchLifts``.  The result equals, bit for bit, the host composition ``match_lifts_host``,
+    ``gather_view_tracks_host``, ``calibrate_views_host``, ``camera_to_world_host``, ``fuse_views_host``, ``solve_view_roots_host``,
+    ``root_trajectory_host`` on ``predict_tracks`` of the flattened tracks.  Two persons with one body who move alike cannot be told
+    apart; no matching accuracy is claimed."""
     import torch
     from . import predict as pt
     match = check_match(match)
@@ -2021,8 +2201,12 @@ def predict_views(model, config, views, cameras, resolutions=None, mask_stride=N
     triangulate = check_triangulate(triangulate)
     calibrate = check_calibrate(calibrate)
     as_given = cameras
+    lifts = isinstance(match, MatchLifts)
+    if lifts and isinstance(align, AlignViews):
+        raise ValueError("predict_views(match=MatchLifts(...)) does not take align=True or an AlignViews: the lifts are matched frame by frame on "
+                         "one clock, and estimating offsets needs tracks that are matched already; pass known offsets as a list, which only crops")
     if calibrate is not None:
-        if match is not None:
+        if match is not None and not lifts:
             raise ValueError("predict_views(calibrate=...) does not take match: matching needs the rays in one world, which is what the call is "
                              "there to find; the same index must be the same person")
         if isinstance(align, AlignViews):
@@ -2038,6 +2222,10 @@ def predict_views(model, config, views, cameras, resolutions=None, mask_stride=N
                                  keyframes_only, out_fps, match, None, triangulate, calibrate)
         got = _predict_aligned_views(align, match, model, views, cameras, valid, fps, keyframes_only, out_fps, call)
         return got if calibrate is None else got[:-4] + got[-2:] + got[-4:-2]      # cameras and calibration stay the last two items
+    if lifts:
+        return _predict_lift_matched_views(pt, match, model, config, views, cameras, resolutions, mask_stride, flip, reuse_frames, batch_size, depth,
+                                           graph, valid, fps, model_fps, repair_joints, keypoints, min_root_joints, smooth, bones, rotations,
+                                           interpolation, return_views, keyframes_only, out_fps, triangulate, calibrate, as_given)
     if match is not None:
         return _predict_matched_views(pt, match, model, config, views, cameras, resolutions, mask_stride, flip, reuse_frames, batch_size, depth, graph,
                                       valid, fps, model_fps, repair_joints, keypoints, min_root_joints, smooth, bones, rotations, interpolation,
@@ -2073,21 +2261,93 @@ def predict_views(model, config, views, cameras, resolutions=None, mask_stride=N
     # 2a. - 2e. where the cameras stand: every view's pose against view 0 from the lifts in camera axes, then the one copy
     calibration = None
     if calibrate is not None:
-        rows = np.zeros((V, CALIBRATE_POSE + 1), np.float64)
-        rows[0, 0] = rows[0, 7] = 1.0
-        if V > 1:
-            pose_dev, terms_dev = calibrate_views(front.out.reshape(V, R, J, 3), kp2d, as_given, flags, person.min_root_joints, calibrate.min_terms)
-            rows = torch.cat([pose_dev, terms_dev.to(torch.float64)[:, None]], 1).cpu().numpy()
-        lost = [v for v in range(V) if rows[v, 7] != 1.0]
-        if lost:
-            raise ValueError(f"calibrate: view {lost[0]} cannot be calibrated against view 0 ({int(rows[lost[0], 8])} shared rows, {calibrate.min_terms} "
-                             f"needed; or its lifts fix no rotation, or the rows fix no position) (views without a pose: {lost})")
-        cams = calibrated_cameras(as_given, rows[:, :CALIBRATE_POSE])
-        calibration = [(int(rows[v, 7]), int(rows[v, 8])) for v in range(V)]
+        cams, calibration = _calibrated_views(calibrate, as_given, front.out.reshape(V, R, J, 3), kp2d, flags, person.min_root_joints)
     # 3. every view's poses to world axes: the existing launch, poses only, one row of extrinsics per view block
     world, _ = camera_to_world_rows(front.out, None, None, np.stack([c.pose_row() for c in cams]), [R] * V)
     result = _fused_scene(pt, person, world.view(V, R, J, 3), kp2d, flags, cams, lens, rates, model_fps, return_views, triangulate,
                           int(config.ROOT_KEYTPOINT))
+    return result if calibration is None else result + (cams, calibration)
+
+
+def _calibrated_views(calibrate, as_given, lifts, kp2d, flags, min_joints):
+    """Steps 1a. to 1e. of the module's docstring, "Where the cameras stand": ``lifts`` (V, R, J, 3) in camera axes, ``kp2d`` (V, R, J, 2) and
+    ``flags`` None or (V, R, J) on the device; ``as_given``: the cameras of the call -> (the V cameras with extrinsics, per view (state,
+    terms)).  A view without a pose is a ValueError that names it."""
+    import torch
+    V = int(kp2d.shape[0])
+    rows = np.zeros((V, CALIBRATE_POSE + 1), np.float64)
+    rows[0, 0] = rows[0, 7] = 1.0
+    if V > 1:
+        pose_dev, terms_dev = calibrate_views(lifts, kp2d, as_given, flags, min_joints, calibrate.min_terms)
+        rows = torch.cat([pose_dev, terms_dev.to(torch.float64)[:, None]], 1).cpu().numpy()
+    lost = [v for v in range(V) if rows[v, 7] != 1.0]
+    if lost:
+        raise ValueError(f"calibrate: view {lost[0]} cannot be calibrated against view 0 ({int(rows[lost[0], 8])} shared rows, {calibrate.min_terms} "
+                         f"needed; or its lifts fix no rotation, or the rows fix no position) (views without a pose: {lost})")
+    return calibrated_cameras(as_given, rows[:, :CALIBRATE_POSE]), [(int(rows[v, 7]), int(rows[v, 8])) for v in range(V)]
+
+
+def _predict_lift_matched_views(pt, match, model, config, views, cameras, resolutions, mask_stride, flip, reuse_frames, batch_size, depth, graph,
+                                valid, fps, model_fps, repair_joints, keypoints, min_root_joints, smooth, bones, rotations, interpolation,
+                                return_views, keyframes_only, out_fps, triangulate, calibrate, as_given):
+    """``predict_views(match=MatchLifts(...))``: the steps of its docstring, "Who is who without a world".  ``cameras``: every view's camera
+    with extrinsics (under ``calibrate`` the identity stands in where one has none); ``as_given``: the cameras of the call."""
+    import torch
+    if keyframes_only:
+        raise ValueError("predict_views does not take keyframes_only: the fusion needs one returned frame per given frame of every view")
+    if out_fps is not None:
+        raise ValueError("predict_views does not take out_fps: the fusion needs one returned frame per given frame of every view")
+    cams, counts, flat, flat_valid, T = _match_inputs(views, cameras, valid)
+    V, M = len(cams), len(flat)
+    if calibrate is not None and counts[0] < 1:
+        raise ValueError("calibrate: view 0 holds no track, and view 0 defines the world: put a camera that saw somebody first")
+    if isinstance(bones, (list, tuple)):
+        raise ValueError("predict_views(match=...) does not take bones as a per-person list: the persons are not known beforehand; "
+                         "pass \"track\", one array of lengths or a Bones")
+    rate = None
+    if fps is not None:
+        if isinstance(fps, (list, np.ndarray)):
+            raise ValueError("predict_views(match=...) takes one fps for all tracks, not a list: they are on one clock")
+        rate = pt.frame_rates(fps, 1)[0]
+    # every refusal of the persons' options before any device work (they are checked again for the P persons found)
+    pinhole0 = cams[0].without(distortion=True, extrinsics=True)
+    first = pt.stage_options(config, 1, "track", True, keypoints, pinhole0, min_root_joints, smooth, bones, repair_joints, fps, None,
+                             interpolation=interpolation, rotations=rotations)
+    view_of = np.repeat(np.arange(V, dtype=np.int32), counts)
+    res = None if resolutions is None else pt.check_resolutions(resolutions, V, per="view")[view_of]
+    # 0. undistort; 1. one run of the front, the windows, the forwards and the assembly over the M tracks as given
+    tr, _ = _undistorted_tracks(flat, cams, counts, torch.device(model.device))
+    pinhole = [cams[v].without(distortion=True, extrinsics=True) for v in view_of]
+    front = pt._assembled_tracks(model, config, tr, res, mask_stride, flip, False, reuse_frames, batch_size, True, depth, None, graph, flat_valid,
+                                 None if rate is None else [rate] * M, None, model_fps, repair_joints, keypoints, pinhole, min_root_joints, None, None,
+                                 None, interpolation)
+    if [int(n) for n in front.lens] != [T] * M or tuple(front.out.shape[:1]) != (M * T,):
+        raise ValueError("predict_views: the assembly did not return one frame per given frame")      # (cannot happen without out_fps / keyframes_only)
+    J = int(front.out.shape[1])
+    kp2d, flags = front.table.source
+    kp2d, flags = kp2d.contiguous(), None if flags is None else flags.contiguous()
+    # 2. who is who from the lifts in camera axes and the keypoints in the model's layout; the one copy of the route
+    person_dev, count_dev, table_dev, _, _ = match_lifts(front.out.view(M, T, J, 3), kp2d.view(M, T, J, 2), view_of,
+                                                         None if flags is None else flags.view(M, T, J), V, first.min_root_joints, match.max_dist,
+                                                         match.min_terms)
+    back = torch.cat([person_dev, count_dev, table_dev.reshape(-1)]).cpu().numpy()
+    who, P, table = back[:M], int(back[M]), back[M + 1:].reshape(V, M)
+    person = pt.stage_options(config, P, "track", True, keypoints, pinhole0, min_root_joints, smooth, bones, repair_joints, fps, None,
+                              interpolation=interpolation, rotations=rotations)
+    # 3. the persons' tracks, view-major and padded, still in camera axes: this route gathers before it turns the lifts to world axes
+    src = _upload(table[:, :P], np.int32, front.out.device)
+    lifts, kp2d, flags = gather_view_tracks(src, front.out, kp2d, flags, T)
+    # 4. where the cameras stand, on the gathered buffers: a (view, person) pair without a track is rows the view does not SEE
+    calibration = None
+    if calibrate is not None:
+        cams, calibration = _calibrated_views(calibrate, as_given, lifts, kp2d, flags, person.min_root_joints)
+    # 5. every view's poses to world axes: one row of extrinsics per view block of P T rows
+    world, _ = camera_to_world_rows(lifts.view(V * P * T, J, 3), None, None, np.stack([c.pose_row() for c in cams]), [P * T] * V)
+    lens = np.full(P, T, np.int64)
+    result = _fused_scene(pt, person, world.view(V, P * T, J, 3), kp2d, flags, cams, lens, None if rate is None else [rate] * P, model_fps,
+                          return_views, triangulate, int(config.ROOT_KEYTPOINT))
+    starts = np.concatenate([[0], np.cumsum(counts)])
+    result += ([[int(k) for k in who[starts[v]:starts[v + 1]]] for v in range(V)],)
     return result if calibration is None else result + (cams, calibration)
 
 
