@@ -1287,6 +1287,49 @@ int uu3d_stream_root_reset(int32_t slots, int32_t num_keypoints, int32_t lookahe
                            void* stream);
 
 /*
+ * LIVE SEVERAL VIEWS (stream.StreamSession(views=V); stream.LiveViews, and stream.LiveViewsHost, the same rule in numpy, bit for bit):
+ * SEVERAL VIEWS for LIVE TRACKS.  A rig of V calibrated cameras, 1 <= V <= 8, watches N persons; the session's V N slots are VIEW-MAJOR:
+ * slot v N + i is person i in camera v.  The input side, LIVE ABSOLUTE ROOT and WORLD SPACE run on all slots as they are; this stage joins
+ * the V slots of every person to ONE pose and ONE world root per push, on the device.  No model: the calls take the counts.  No accuracy
+ * is claimed (SEVERAL VIEWS).  A push is the clock: the frames the slots received at one push are one instant, whatever their counters say.
+ * STATE per person, in one caller-allocated block of uu3d_stream_views_bytes(views, persons) bytes, 256-byte aligned, zeroed by
+ * uu3d_stream_views_reset: the last solved world root (3 f64), the state the person returned last, the person's tick counter.  The stage
+ * READS the ring of LIVE ABSOLUTE ROOT (root_state_dev: the block of uu3d_stream_root for slots = V N, the same J and lookahead) and files
+ * nothing itself; it runs in a later launch than the filing, so lookahead 0 needs no special case.
+ * THE RULE.  frames_dev / active_dev / fresh_dev (V N): what uu3d_stream_root took; view_poses_dev (V N, J, 3) f32: the slots' poses in
+ * world axes (uu3d_camera_to_world); cameras_dev (V, 16) f64: the rows of SEVERAL VIEWS.
+ *   taking part  view v takes part in person i's tick iff its slot is active (frames >= 1) and its pose is fresh.
+ *   seeing       view v sees the person iff it takes part and at least min_joints USED bytes are set in its own frame
+ *                c_v = frames[slot] - 1 - lookahead >= 0 of the ring.
+ *   fresh        fresh_out_dev[i] = some view takes part.  poses_dev (N, J, 3) f32 then is the fusion rule of SEVERAL VIEWS over the seeing
+ *                views in ascending order, view_count_dev[i] their number; nobody sees: the mean over the views that take part,
+ *                view_count 0.  The root is the root rule of SEVERAL VIEWS -- the same statements, the 2^-40 rank guard, the in-front test --
+ *                over the seeing views, against the fused pose and each view's own ring frame.  Solved: roots_dev (N, 3) f32 = the root
+ *                rounded once, root_state_out_dev[i] = 1, and the root is held (f64).  Not solved: the held root, state 2; no held root
+ *                yet: zeros, state 0.
+ *   not fresh    the pose row keeps its bits, the held root and the last state are returned, view_count 0.
+ *   counter      the person's tick counter grows by one iff any of its slots is active; person_frames_dev (N) i32 is its value after
+ *                this push and person_active_dev (N) u8 that flag: what the stages behind (STEADY OUTPUT) take where they take a slot's
+ *                counter and active flag.
+ *
+ *   uu3d_stream_views_bytes(views, persons): 0 for arguments out of range (views in [1, 8], persons >= 1, views * persons <= 2^20).
+ *   uu3d_stream_views(views, persons, J, lookahead, views_state_dev, root_state_dev, frames_dev, active_dev, fresh_dev, view_poses_dev,
+ *       cameras_dev, min_joints, poses_dev != view_poses_dev, fresh_out_dev, roots_dev, root_state_out_dev, view_count_dev,
+ *       person_frames_dev, person_active_dev, stream): one launch, one wave per person -- lane j fuses joint j with one 12-byte store, the
+ *       fused pose goes through LDS to lane 0, which solves in the summation order of SEVERAL VIEWS.  views > 8 or J > 64: UU3D_ERR_UNSUPPORTED.
+ *   uu3d_stream_views_reset(views, persons, views_state_dev, slot_mask_dev (V N) u8 or NULL = every slot, stream): a person ALL of whose V
+ *       slots are chosen has no held root, state 0 and tick counter 0; beside uu3d_stream_reset, with the same mask.
+ * Every output and state element has one writer, no atomics, the caller's buffers and the ring are only read: bitwise repeatable,
+ * capturable.  Out of scope live: who is who, one clock, where rays meet, where the cameras stand, constant bone lengths on the fused pose.
+ */
+size_t uu3d_stream_views_bytes(int32_t views, int32_t persons);
+int uu3d_stream_views(int32_t views, int32_t persons, int32_t num_keypoints, int32_t lookahead, void* views_state_dev, const void* root_state_dev,
+                      const int32_t* frames_dev, const uint8_t* active_dev, const uint8_t* fresh_dev, const float* view_poses_dev,
+                      const double* cameras_dev, int32_t min_joints, float* poses_dev, uint8_t* fresh_out_dev, float* roots_dev,
+                      uint8_t* root_state_out_dev, uint8_t* view_count_dev, int32_t* person_frames_dev, uint8_t* person_active_dev, void* stream);
+int uu3d_stream_views_reset(int32_t views, int32_t persons, void* views_state_dev, const uint8_t* slot_mask_dev, void* stream);
+
+/*
  * STEADY OUTPUT (predict.predict_tracks(smooth=...), predict.one_euro; stream.StreamSession(smooth=...), stream.LiveOneEuro): the One-Euro
  * filter (Casiez, Roussel, Vogel 2012) over the poses and roots a call or a session returns -- an exponential smoother whose cut-off rises
  * with the speed of the signal.  No model: the calls take the channel count C and run on any (rows, C) f32 buffers.  Nothing is claimed

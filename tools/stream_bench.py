@@ -6,7 +6,7 @@ Median (and 90th percentile) over --ticks ticks after --warmup ticks, per config
 A case is CONFIG:s_in, or generic:J,d_s,d_t,heads,N:s_in for a model with generic dims (e.g. --cases generic:25,16,64,4,27:4): its tick
 (the one-workgroup-per-frame spatial stack + the generic forward's second stage in the graph) beside the same baseline.
    python tools/stream_bench.py [--slots 1,8,64] [--cases h36m_81:4,h36m_351:5] [--ticks 300] [--warmup 60] [--lookahead 0] [--fps F [--out_fps G] [--interpolation cubic]]
-                                [--repair_joints G] [--detections D] [--camera FX FY CX CY [--distortion K1 K2 P1 P2 K3 | --extrinsics QW QX QY QZ TX TY TZ]] [--smooth] [--bones] [--rotations] [--drain]
+                                [--repair_joints G] [--detections D] [--camera FX FY CX CY [--distortion K1 K2 P1 P2 K3 | --extrinsics QW QX QY QZ TX TY TZ]] [--smooth] [--bones] [--rotations] [--drain] [--views V]
 --fps F (a float or NUM/DEN): microseconds per PUSH of StreamSession(fps=F) -- one source frame in, one pose out, on average
 model_fps / F sub-ticks -- next to the plain session pushed at the model's rate (the cost of one model tick); the lookahead is raised to
 the smallest one the rate allows.  The numpy baseline is left out.
@@ -36,6 +36,11 @@ the difference of the two medians.  Informational: no threshold.  The numpy base
 orientation=(QW, QX, QY, QZ), translation=(TX, TY, TZ))) -- one more launch, uu3d_camera_to_world, directly behind uu3d_stream_root -- as
 world_graph_us next to the tick of the session with the plain tuple (camera_graph_us) on the same frames in the same process, measured side
 by side in the same way.  world_minus_camera_us is the difference of the two medians.  Informational: no threshold.
+--views V (alone; --slots must be multiples of V): the tick of StreamSession(camera=[V Cameras with extrinsics], views=V) -- one more launch,
+uu3d_stream_views, directly behind uu3d_camera_to_world, the slots view-major, slots / V persons returned -- as views_graph_us next to the
+tick of the same session without views (one Camera per slot: world_graph_us) on the same frames in the same process, measured side by side
+in the same way.  views_minus_world_us is the difference of the two medians.  The cameras stand on a ring of 4 m around the origin, 1145
+pixels of focal length.  Informational: no threshold.
 --smooth (alone or with --camera, not with the other options): the tick of StreamSession(smooth=True) -- one more launch at the end of the
 captured tick, with --camera two (poses and roots) -- as smooth_graph_us next to the tick of the same session without smooth (graph_us;
 with --camera both sessions have the camera), measured side by side in the same way.  smooth_minus_graph_us is the difference of the two
@@ -76,6 +81,7 @@ def main():
     ap.add_argument("--bones", action="store_true")
     ap.add_argument("--rotations", action="store_true")
     ap.add_argument("--drain", action="store_true")
+    ap.add_argument("--views", type=int, default=None)
     args = ap.parse_args()
     if args.bones and (args.smooth or args.fps is not None or args.repair_joints is not None or args.detections is not None):
         ap.error("--bones is not measured together with --smooth / --fps / --repair_joints / --detections")
@@ -95,6 +101,11 @@ def main():
         ap.error("--distortion is measured with --camera alone")
     if args.extrinsics is not None and (args.camera is None or args.smooth or args.bones or args.rotations or args.distortion is not None):
         ap.error("--extrinsics is measured with --camera alone")
+    if args.views is not None and (args.drain or args.rotations or args.bones or args.smooth or args.camera is not None or args.fps is not None
+                                   or args.repair_joints is not None or args.detections is not None):
+        ap.error("--views is measured alone")
+    if args.views is not None and (not 1 <= args.views <= 8 or any(int(v) % args.views for v in args.slots.split(","))):
+        ap.error("--views takes V in 1 .. 8 and --slots that are multiples of V")
     if args.out_fps is not None and args.fps is None:
         ap.error("--out_fps needs --fps")
     if args.interpolation == "cubic" and args.fps is None:
@@ -267,6 +278,26 @@ def main():
                            **({} if args.extrinsics is None else {"extrinsics": list(args.extrinsics)}))
                 return tuple((key, lambda key=key: ts[key][args.warmup:]) for key in pair)
 
+            def views_variants():
+                V = args.views
+                half = [0.5 * np.pi * (v + 0.5) / V for v in range(V)]        # camera v: yawed about the world's z, 4 m from the origin
+                rig = [stream.Camera(1145.0, 1145.0, 0.5 * W, 0.5 * H, orientation=(np.cos(h), 0.0, 0.0, np.sin(h)),
+                                     translation=(4.0 * np.cos(2.0 * h), 4.0 * np.sin(2.0 * h), 1.5)) for h in half]
+                new = lambda **kw: stream.StreamSession(model, cfg, slots=T, resolutions=(W, H), mask_stride=ms, flip=True, lookahead=args.lookahead, **kw)
+                pair = {"views_graph": new(camera=rig, views=V), "world_graph": new(camera=[c for c in rig for _ in range(T // V)])}
+                ts = {key: [] for key in pair}
+                for k in range(total):
+                    for key in (list(pair) if k % 2 == 0 else list(pair)[::-1]):
+                        t0 = time.perf_counter()
+                        pair[key].push(px[k])
+                        torch.cuda.synchronize()
+                        ts[key].append(time.perf_counter() - t0)
+                for s in pair.values():
+                    s.check_range()
+                    s.close()
+                row.update(views=V, persons=T // V)
+                return tuple((key, lambda key=key: ts[key][args.warmup:]) for key in pair)
+
             if args.drain:
                 for a in sorted({min(13, stream.max_lookahead(cfg)), stream.max_lookahead(cfg)}):
                     s = stream.StreamSession(model, cfg, slots=T, resolutions=(W, H), mask_stride=ms, flip=True, lookahead=a)
@@ -320,11 +351,15 @@ def main():
                 variants = detections_variants()
             if args.camera is not None or args.smooth or args.bones or args.rotations:
                 variants = camera_variants()
+            if args.views is not None:
+                variants = views_variants()
             for key, fn in variants:
                 ts = np.asarray(fn())
                 row[key + "_us"] = round(1e6 * float(np.median(ts)), 1)
                 row[key + "_p90_us"] = round(1e6 * float(np.percentile(ts, 90)), 1)
-            if args.smooth:
+            if args.views is not None:
+                row["views_minus_world_us"] = round(row["views_graph_us"] - row["world_graph_us"], 1)
+            elif args.smooth:
                 row["smooth_minus_graph_us"] = round(row["smooth_graph_us"] - row["graph_us"], 1)
             elif args.bones:
                 row["bones_minus_graph_us"] = round(row["bones_graph_us"] - row["graph_us"], 1)

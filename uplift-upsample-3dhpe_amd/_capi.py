@@ -60,6 +60,7 @@ EXPORTED_SYMBOLS = (
     "uu3d_triangulate_joints", "uu3d_place_joints",
     "uu3d_view_calibrate_chunks", "uu3d_view_moment_sums", "uu3d_view_position_sums", "uu3d_solve_view_pose",
     "uu3d_lift_pair_sums",
+    "uu3d_stream_views_bytes", "uu3d_stream_views", "uu3d_stream_views_reset",
 )
 # include/uu3d_ops.h
 OPS_SYMBOLS = (
@@ -373,6 +374,13 @@ def load_library(path=None):
     lib.uu3d_stream_root.argtypes = [i32, i32, i32] + [vp] * 7 + [i32, vp, i32, vp, vp, vp]
     lib.uu3d_stream_root_reset.restype = C.c_int
     lib.uu3d_stream_root_reset.argtypes = [i32, i32, i32, vp, vp, vp]
+    # live several views: the V slots of a person joined to one pose and one world root per push
+    lib.uu3d_stream_views_bytes.restype = sz
+    lib.uu3d_stream_views_bytes.argtypes = [i32, i32]
+    lib.uu3d_stream_views.restype = C.c_int
+    lib.uu3d_stream_views.argtypes = [i32, i32, i32, i32] + [vp] * 7 + [i32] + [vp] * 8
+    lib.uu3d_stream_views_reset.restype = C.c_int
+    lib.uu3d_stream_views_reset.argtypes = [i32, i32, vp, vp, vp]
     # steady output: the One-Euro filter over finished tracks and the live filter of a session
     f64 = C.c_double
     lib.uu3d_one_euro_tracks.restype = C.c_int

@@ -57,6 +57,7 @@
 #include "uu3d_triangulate.h"
 #include "uu3d_view_calibrate.h"
 #include "uu3d_lift_match.h"
+#include "uu3d_stream_views.h"
 #include "uu3d_train.h"
 #include "uu3d_bwd.h"
 #include "uu3d_launch.h"
@@ -790,6 +791,7 @@ int uu3d_assemble_tracks_cubic(const float* plain, const float* flipped, int64_t
 #include "uu3d_triangulate_api.inc"
 #include "uu3d_view_calibrate_api.inc"
 #include "uu3d_lift_match_api.inc"
+#include "uu3d_stream_views_api.inc"
 
 int uu3d_world_to_cam_2d(const float* world, const float* cams, int32_t B, int32_t N, int32_t J, float* cam3d, float* kp2d, void* stream) {
     if (!world || !cams || B < 1 || N < 1 || J < 1 || (!cam3d && !kp2d)) return UU3D_ERR_INVALID_ARGUMENT;

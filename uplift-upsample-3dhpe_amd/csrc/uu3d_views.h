@@ -24,17 +24,34 @@ __device__ __forceinline__ bool view_joint_used(const float* __restrict__ kp, co
     return finite_pair(*reinterpret_cast<const float2*>(kp + 2 * at));
 }
 
+// Where joint 0 of view v's frame lies in the (.., J) planes -- the offline buffers: `first` = the index of the frame's joint 0 in view 0,
+// `step` = R * J.  The live stage has a functor of its own (uu3d_stream_views.h: every view's frame at its own place of a ring).
+struct ViewBlocks {
+    long first, step;
+    __device__ __forceinline__ long operator()(const int v) const { return first + v * step; }
+};
+
+// The views among `allowed` (a bit per view) that see their frame, as a bit per view; at(v) = the index of that frame's joint 0.
+template <class At>
+__device__ __forceinline__ unsigned seeing_views_at(const float* __restrict__ kp, const uint8_t* __restrict__ flags, const At at, const unsigned allowed,
+                                                    const int views, const int J, const int min_joints)
+{
+    unsigned mask = 0;
+    for (int v = 0; v < views; ++v) {
+        if (((allowed >> v) & 1u) == 0) continue;
+        const long first = at(v);
+        int n = 0;
+        for (int j = 0; j < J; ++j) n += view_joint_used(kp, flags, first + j) ? 1 : 0;
+        if (n >= min_joints) mask |= 1u << v;
+    }
+    return mask;
+}
+
 // The views that see a frame, as a bit per view; `first` = the index of the frame's joint 0 in view 0, `step` = R * J.
 __device__ __forceinline__ unsigned seeing_views(const float* __restrict__ kp, const uint8_t* __restrict__ flags, const long first, const long step,
                                                  const int views, const int J, const int min_joints)
 {
-    unsigned mask = 0;
-    for (int v = 0; v < views; ++v) {
-        int n = 0;
-        for (int j = 0; j < J; ++j) n += view_joint_used(kp, flags, first + v * step + j) ? 1 : 0;
-        if (n >= min_joints) mask |= 1u << v;
-    }
-    return mask;
+    return seeing_views_at(kp, flags, ViewBlocks{first, step}, (1u << views) - 1u, views, J, min_joints);
 }
 
 // Lane p = frame * J + joint.  fused[frame][joint] = (float)(s / (double)n), s the float64 sum of the seeing views' poses in ascending view
@@ -75,14 +92,15 @@ fuse_views_kernel(const float* __restrict__ poses, const float* __restrict__ kp,
 }
 
 // The solve of one frame: the statements of predict.solve_view_roots_host, one for one, every operation rounded once.  pose (J, 3) f32: the
-// fused world pose of the frame; `first` / `step` as in seeing_views; cams (views, 16) f64.  -> solved; T = the world root, zeros when not.
-__device__ __forceinline__ bool solve_view_root(const float* __restrict__ pose, const float* __restrict__ kp, const uint8_t* __restrict__ flags,
-                                                const long first, const long step, const int views, const int J,
-                                                const double* __restrict__ cams, const int min_joints, double T[3])
+// fused world pose of the frame; `mask`: the seeing views, at(v) = the index of joint 0 of view v's frame (seeing_views_at); cams
+// (views, 16) f64.  -> solved; T = the world root, zeros when not.
+template <class At>
+__device__ __forceinline__ bool solve_view_root_at(const float* __restrict__ pose, const float* __restrict__ kp, const uint8_t* __restrict__ flags,
+                                                   const At at, const unsigned mask, const int views, const int J,
+                                                   const double* __restrict__ cams, double T[3])
 {
 #pragma clang fp contract(off)
     T[0] = T[1] = T[2] = 0.0;
-    const unsigned mask = seeing_views(kp, flags, first, step, views, J, min_joints);
     if (mask == 0) return false;
     double a00 = 0.0, a01 = 0.0, a02 = 0.0, a11 = 0.0, a12 = 0.0, a22 = 0.0, b0 = 0.0, b1 = 0.0, b2 = 0.0;
     for (int v = 0; v < views; ++v) {
@@ -90,10 +108,11 @@ __device__ __forceinline__ bool solve_view_root(const float* __restrict__ pose, 
         const double* __restrict__ c = cams + kViewCamera * v;
         const double fx = c[0], fy = c[1], cx = c[2], cy = c[3];
         if (!finite_double(fx) || !finite_double(fy) || !finite_double(cx) || !finite_double(cy) || !(fx > 0.0) || !(fy > 0.0)) return false;
+        const long first = at(v);
         for (int j = 0; j < J; ++j) {
-            const long at = first + v * step + j;
-            if (!view_joint_used(kp, flags, at)) continue;
-            const float2 uv = *reinterpret_cast<const float2*>(kp + 2 * at);
+            const long q = first + j;
+            if (!view_joint_used(kp, flags, q)) continue;
+            const float2 uv = *reinterpret_cast<const float2*>(kp + 2 * q);
             const double a = ((double)uv.x - cx) / fx;
             const double b = ((double)uv.y - cy) / fy;
             const double n0 = c[4] - a * c[10], n1 = c[5] - a * c[11], n2 = c[6] - a * c[12];
@@ -129,8 +148,9 @@ __device__ __forceinline__ bool solve_view_root(const float* __restrict__ pose, 
     for (int v = 0; v < views; ++v) {                                    // every used joint of every seeing view in front of its camera
         if (((mask >> v) & 1u) == 0) continue;
         const double* __restrict__ c = cams + kViewCamera * v;
+        const long first = at(v);
         for (int j = 0; j < J; ++j) {
-            if (!view_joint_used(kp, flags, first + v * step + j)) continue;
+            if (!view_joint_used(kp, flags, first + j)) continue;
             const double w0 = (T0 + (double)pose[3 * j]) - c[13];
             const double w1 = (T1 + (double)pose[3 * j + 1]) - c[14];
             const double w2 = (T2 + (double)pose[3 * j + 2]) - c[15];
@@ -140,6 +160,16 @@ __device__ __forceinline__ bool solve_view_root(const float* __restrict__ pose, 
     }
     T[0] = T0; T[1] = T1; T[2] = T2;
     return true;
+}
+
+// The solve of one frame of the offline buffers; `first` / `step` as in seeing_views.
+__device__ __forceinline__ bool solve_view_root(const float* __restrict__ pose, const float* __restrict__ kp, const uint8_t* __restrict__ flags,
+                                                const long first, const long step, const int views, const int J,
+                                                const double* __restrict__ cams, const int min_joints, double T[3])
+{
+    const ViewBlocks at{first, step};
+    const unsigned mask = seeing_views_at(kp, flags, at, (1u << views) - 1u, views, J, min_joints);
+    return solve_view_root_at(pose, kp, flags, at, mask, views, J, cams, T);
 }
 
 // roots (rows, 3) f64 and solved (rows) u8: one lane per frame, the shape of solve_roots_kernel.

@@ -84,10 +84,12 @@ module's docstring; every name is importable from here as before:
     smooth.py     steady output: ``StreamSession(..., smooth=F)`` (``LiveOneEuro``, ``LiveOneEuroHost``)
     bones.py      live constant bone lengths: ``StreamSession(..., bones=B)`` (``LiveBones``, ``LiveBonesHost``)
     rotations.py  live joint rotations: ``StreamSession(..., rotations=R)`` (``LiveRotations``: uu3d_joint_rotations as the tick's last launch)
+    live_views.py live several views: ``StreamSession(..., slots=V * N, camera=[V Cameras with extrinsics], views=V)`` (``LiveViews``: uu3d_stream_views
+                  behind uu3d_camera_to_world; ``LiveViewsHost``, ``replay_views``)
     camera.py     lens distortion: ``StreamSession(..., camera=Camera(fx, fy, cx, cy, distortion=...))`` (uu3d_undistort_points as the tick's first launch);
                   world space: ``StreamSession(..., camera=Camera(..., orientation=, translation=))`` (``LiveWorld``: uu3d_camera_to_world behind uu3d_stream_root)
 The refusals these options share with ``predict_tracks`` are ``options.stage_options``; the ones only a session has are ``_init_plan``'s.
-The output-side options (bones, root, world, the two filters, rotations) are device objects of one shape (``smooth.LiveOneEuro``); the
+The output-side options (bones, root, world, views, the two filters, rotations) are device objects of one shape (``smooth.LiveOneEuro``); the
 session hands a ``Scene`` through them in that order and walks the list for its launch tables.  The input-side ones stay inline.
 
 The end of a track -- ``finish(slots)``: a session with lookahead a has not returned the poses of a track's last a frames when the track
@@ -126,6 +128,7 @@ from .camera import (Camera, LiveWorld, camera_to_world_host, distort_points_hos
                      undistort_points_host, world_to_camera_host)
 from .cli import add_track_options, bones_option, input_joints, smooth_option, split_scores, track_keywords  # noqa: F401
 from .keypoints import KEYPOINT_PRESETS, check_keypoint_inputs, keypoint_map  # noqa: F401
+from .live_views import LiveViews, LiveViewsHost, check_live_views, person_mask, replay_views  # noqa: F401
 from .options import check_interpolation, stage_options
 from .predict import _load_model
 from .rates import (RatePlan, _rate_argument, frame_rate, max_lookahead, newest_model_frame, out_push_plan, out_push_plan_cubic,  # noqa: F401
@@ -199,6 +202,7 @@ def window_plan(frames, lookahead, config, mask_stride=None, valid=None, drained
 
 LIVE_OPTIONS = ("repair_joints", "keypoints", "camera", "min_root_joints", "smooth", "bones", "rotations")  # the keywords ``StreamSession`` and ``replay_tracks`` take from **options
 DETECTION_OPTIONS = ("detections",) + tuple(ASSOCIATION_DEFAULTS)    # ... and the ones only ``StreamSession`` takes: per-frame detections
+VIEW_OPTIONS = ("views",)                                             # ... and the cameras of a rig (``live_views.py``)
 
 
 def _live_options(options, who, names=LIVE_OPTIONS):
@@ -313,12 +317,20 @@ class StreamSession(object):
         ``predict.Rotations``: "Live joint rotations" (``rotations.py``) -- ``push`` / ``push_detections`` append ``rotations``
         (slots, J, 4) float32, per slot and joint the unit quaternion (w, x, y, z) of the pose they return, behind what they return
         otherwise (with ``return_global`` the global quaternions behind that); ``rotation_flags`` is the (slots, J) uint8 table of the
-        last tick.  uu3d_joint_rotations is the last launch of the captured tick.  With ``out_fps``: ValueError."""
+        last tick.  uu3d_joint_rotations is the last launch of the captured tick.  With ``out_fps``: ValueError.
+        ``views`` (keyword only, from ``options`` as well): None = every slot is a scene of its own (the session above, bit for bit: the
+        same launches, buffers, refusals and bits).  Else V in [1, 8], the cameras of a calibrated rig: "Live several views"
+        (``live_views.py``) -- ``slots`` = V N is VIEW-MAJOR, slot v N + i is person i in camera v, and ``camera`` is a list of V
+        ``Camera`` objects with extrinsics, one per VIEW (all with distortion or all without).  uu3d_stream_views joins the launch table
+        directly behind uu3d_camera_to_world; the filters and the rotations run behind it on N person rows.  ``push`` ->
+        (poses (N, J, 3), fresh (N,), roots (N, 3), root_state (N,), view_count (N,) uint8, then ``rotations``); ``view_poses`` /
+        ``view_roots`` are the per-slot world scene, ``raw_poses`` / ``raw_roots`` the unfiltered fused buffers.  ``reset(slots)`` resets a
+        person iff all V of its slots are chosen.  With ``detections``, ``out_fps``, ``bones``: ValueError; ``finish``: ValueError."""
         (repair_joints, keypoints, camera, min_root_joints, smooth, bones, rotations, detections,
-         *rule) = _live_options(options, "StreamSession", LIVE_OPTIONS + DETECTION_OPTIONS)
+         *rule, views) = _live_options(options, "StreamSession", LIVE_OPTIONS + DETECTION_OPTIONS + VIEW_OPTIONS)
         res = self._init_plan(model, config, slots, resolutions, mask_stride, flip, lookahead, graph, missed_detections, fps, model_fps, out_fps,
                               repair_joints, keypoints, detections, dict(zip(ASSOCIATION_DEFAULTS, rule)), camera, min_root_joints, smooth,
-                              bones=bones, root_relative=root_relative, rotations=rotations, interpolation=interpolation)
+                              bones=bones, root_relative=root_relative, rotations=rotations, interpolation=interpolation, views=views)
         import torch
         self._torch = torch
         self._lib = _capi.load_library()
@@ -335,11 +347,15 @@ class StreamSession(object):
     # ---- construction: checks and plan, layout and state, buffers, launch tables (then the capture) ---------------------------------
     def _init_plan(self, model, config, slots, resolutions, mask_stride, flip, lookahead, graph, missed_detections, fps, model_fps, out_fps,
                    repair_joints=None, keypoints=None, detections=None, rule=None, camera=None, min_root_joints=None, smooth=None, bones=None,
-                   root_relative=True, rotations=None, interpolation="linear"):
+                   root_relative=True, rotations=None, interpolation="linear", views=None):
         """Every refusal that needs no device, and the session's plan.  -> the checked resolutions."""
         slots, lookahead = int(slots), int(lookahead)
         if slots < 1:
             raise ValueError("slots >= 1")
+        # several views: the rig's own refusals, then ``camera`` is one Camera per slot, view-major, for everything below
+        self.views = self.view_cameras = None
+        if views is not None:
+            self.views, self.view_cameras, camera = check_live_views(views, camera, slots, detections, out_fps, bones)
         # the refusals shared with ``predict_tracks`` (``options.stage_options``), then the ones only a session has
         opts = stage_options(config, slots, "slot", root_relative, keypoints, camera, min_root_joints, smooth, bones, repair_joints, fps, out_fps,
                              rotations=rotations)
@@ -530,13 +546,16 @@ class StreamSession(object):
             self._count = zeros((T,), dtype=torch.int32)
             self._result = self._poses, self._count                   # what push returns: the session's own buffers
         # the output-side options in the one order a tick runs them, each under the scene it leaves: ``push`` returns the last one
-        live = lambda option, make, *args, **field: None if option is None else make(T, *args, device=dev, **field)
-        self._pose_smoother = live(self.pose_filter, LiveOneEuro, 3 * J, self.smooth_rate, self.pose_filter, self.lookahead)
-        self._root_smoother = live(self.root_filter, LiveOneEuro, 3, self.smooth_rate, self.root_filter, self.lookahead, field="roots")
-        self._stages = [("fixed", live(self.bones, LiveBones, J, *(self.bones or ()))),
-                        ("camera", live(self.cameras, LiveRoot, J, self.lookahead, self.cameras, self.min_root_joints, self._kp, self._valid_in)),
-                        ("world", live(self.world, LiveWorld, J, self.world)), ("shown", self._pose_smoother), ("shown", self._root_smoother),
-                        ("shown", live(self.rotations, LiveRotations, J, self.rotations))]
+        # (with ``views`` the stages behind the fusion have one row per PERSON)
+        live = lambda option, make, *args, rows=T, **field: None if option is None else make(rows, *args, device=dev, **field)
+        P = T // (self.views or 1)
+        self._pose_smoother = live(self.pose_filter, LiveOneEuro, 3 * J, self.smooth_rate, self.pose_filter, self.lookahead, rows=P)
+        self._root_smoother = live(self.root_filter, LiveOneEuro, 3, self.smooth_rate, self.root_filter, self.lookahead, rows=P, field="roots")
+        root = live(self.cameras, LiveRoot, J, self.lookahead, self.cameras, self.min_root_joints, self._kp, self._valid_in)
+        self._stages = [("fixed", live(self.bones, LiveBones, J, *(self.bones or ()))), ("camera", root),
+                        ("world", live(self.world, LiveWorld, J, self.world)), ("fused", live(self.views, LiveViews, J, self.views, root, self.view_cameras)),
+                        ("shown", self._pose_smoother), ("shown", self._root_smoother),
+                        ("shown", live(self.rotations, LiveRotations, J, self.rotations, rows=P))]
         self._post = [stage for _, stage in self._stages if stage is not None]
         if olay is None:
             self._scenes = scenes(Scene(self._out, self._fresh, None, None, ()), self._stages)
@@ -551,7 +570,8 @@ class StreamSession(object):
           _tick_steps   the steps of one (sub-)tick, in order -- what the graph captures
           _push_before  / _push_after   the launches of a push around its sub-ticks (a session with a rate; not captured)
           _reset_call   the reset of the session's kind; the slot mask and the stream follow its arguments (_reset_more: what a session
-                        with repair_joints, output-side stages, detections or a drain resets beside it)
+                        with repair_joints, output-side stages, detections or a drain resets beside it; _reset_persons: with ``views`` the
+                        stages behind the fusion, whose rows are persons -- they take the mask of the persons all of whose slots are chosen)
           _drain_steps  the steps of one drain tick (``finish``), built at the first ``finish`` by _init_drain -- a second captured graph; the output-side stages (``_post``) give their own entries"""
         lib, m = self._lib, self.model
         h, cfg, state = m._h, C.byref(self._cfg), _ptr(self._state)
@@ -601,8 +621,10 @@ class StreamSession(object):
         self._reset_call = (lib.uu3d_stream_reset, (h, cfg, state))
         # the resets beside it: repair, then the stages in the order the options joined the session, which tests pin (each clears a block of its own; world has none)
         self._reset_more = [] if self.repair_joints is None else [(lib.uu3d_stream_repair_reset, (h, cfg, self.repair_joints, _ptr(self._repair_state)))]
-        bones, root, _, pose_filter, root_filter, rotations = (stage for _, stage in self._stages)
-        self._reset_more += [stage.reset_launch() for stage in (root, pose_filter, root_filter, bones, rotations) if stage is not None]
+        bones, root, _, fused, pose_filter, root_filter, rotations = (stage for _, stage in self._stages)
+        behind = [stage.reset_launch() for stage in (pose_filter, root_filter, bones, rotations) if stage is not None]
+        self._reset_more += [stage.reset_launch() for stage in (root, fused) if stage is not None] + ([] if fused is not None else behind)
+        self._reset_persons = behind if fused is not None else []
         # per-frame detections: the association in front of everything -- it writes the frame, the flags, `active` and the born mask --, then
         # the resets of the slots born at this tick, with the mask on the device
         if self.detections is not None:
@@ -627,7 +649,11 @@ class StreamSession(object):
             self._reset_call = (lib.uu3d_stream_out_reset, (h, cfg, rate, outp, state))
         # the output-side stages behind the emit that wrote the pose they read (with a rate: the timed emit), in the tick's order
         last = self._tick_steps if self.rate is None else self._push_after
-        last += [stage.launch(self._active, self._source_frames) for stage in self._post]
+        active, frames = self._active, self._source_frames
+        for stage in self._post:
+            last.append(stage.launch(active, frames))
+            if isinstance(stage, LiveViews):                         # behind the fusion a row is a person: its own counter and flag
+                active, frames = stage.active, stage.frames
 
     # ---- the steps of a tick, on ``stream`` ------------------------------------------------------------------------------------------
     def _run(self, steps, stream):
@@ -849,6 +875,10 @@ class StreamSession(object):
                 h[np.asarray(slots, np.int64).reshape(-1)] = 1
                 mask = torch.from_numpy(h).pin_memory().to(m.device, non_blocking=True)
             self._run([(fn, args + (_ptr(mask),)) for fn, args in [self._reset_call] + self._reset_more], torch.cuda.current_stream(m.device))
+            if self._reset_persons:                                   # (several views: a person is reset iff all of its slots are)
+                persons = person_mask(slots, self.views, self.slots)
+                pmask = None if persons is None else torch.from_numpy(persons).pin_memory().to(m.device, non_blocking=True)
+                self._run([(fn, args + (_ptr(pmask),)) for fn, args in self._reset_persons], torch.cuda.current_stream(m.device))
             if self.detections is not None:                          # (what the properties show until the next tick)
                 if mask is None:
                     self._track_ids.fill_(-1)
@@ -947,6 +977,9 @@ class StreamSession(object):
         if self.rate is not None:
             raise ValueError("finish in a session with fps / out_fps is not supported yet (a later change): the drain of a source-rate session "
                              "needs the end of the model-rate track")
+        if self.views is not None:
+            raise ValueError("finish in a session with views is not supported yet (a later change): the drain ticks of a person's V slots "
+                             "would have to be fused as its pushes are")
         torch = self._torch
         m = self.model
         dev = m.device
@@ -1018,17 +1051,34 @@ class StreamSession(object):
         """(slots, J, 3) float32 on the device: the poses as the tick emits them, the model's output, unfiltered and with the bones as
         the network gave them -- in a session without ``smooth`` and ``bones`` the buffer ``push`` returns.  Not with ``out_fps``
         (AttributeError).  A session whose ``Camera`` has extrinsics: the unfiltered WORLD poses -- what uu3d_camera_to_world wrote and
-        the pose filter reads (with ``bones`` the rebuilt poses in world axes); ``camera_poses`` is the camera-space buffer."""
+        the pose filter reads (with ``bones`` the rebuilt poses in world axes); ``camera_poses`` is the camera-space buffer.  A session
+        with ``views``: the unfiltered FUSED poses, (N, J, 3); ``view_poses`` is the per-slot world buffer."""
         if self.max_out is not None:
             raise AttributeError("raw_poses: a session with out_fps returns several rows per slot")
-        return self._scenes["raw" if self.world is None else "world"].poses
+        return self._scenes["fused" if self.views is not None else "raw" if self.world is None else "world"].poses
 
     @property
     def raw_roots(self):
         """(slots, 3) float32 on the device (sessions with ``camera``): the roots as they are solved, unfiltered; with extrinsics the
-        unfiltered WORLD roots, which the root filter reads (``camera_roots`` is the camera-space buffer)."""
+        unfiltered WORLD roots, which the root filter reads (``camera_roots`` is the camera-space buffer).  A session with ``views``:
+        the unfiltered world roots of the N persons, (N, 3); ``view_roots`` is the per-slot world buffer."""
         if self.cameras is None:
             raise AttributeError("raw_roots needs a session with camera")
+        return self._scenes["fused"].roots
+
+    @property
+    def view_poses(self):
+        """(slots, J, 3) float32 on the device (sessions with ``views``): the per-slot world poses the fusion reads, slot v N + i person i in
+        camera v -- what the session without ``views`` returns."""
+        if self.views is None:
+            raise AttributeError("view_poses needs a session with views")
+        return self._scenes["world"].poses
+
+    @property
+    def view_roots(self):
+        """(slots, 3) float32 on the device (sessions with ``views``): every slot's own monocular root in world coordinates."""
+        if self.views is None:
+            raise AttributeError("view_roots needs a session with views")
         return self._scenes["world"].roots
 
     @property

@@ -86,7 +86,7 @@ Two persons with one body who move alike cannot be told apart, and short or nois
 ``LIFT_MATCH_DEFAULTS`` are conveniences for metres and frames, not tuned values: no matching accuracy is claimed.
 
 Out of scope: estimating ``align`` without a world, sub-frame offsets and per-camera frame rates, per-view confidence weights, rescaling a calibrated rig to known lengths,
-calibration chained through a third camera, estimating intrinsics, a live form, command-line flags.  No accuracy is claimed."""
+calibration chained through a third camera, estimating intrinsics, command-line flags.  The live form of the fusion and the root solve is ``StreamSession(views=V)`` (``live_views.py``); ``match``, ``align``, ``triangulate`` and ``calibrate`` have none.  No accuracy is claimed."""
 import ctypes as C
 
 import numpy as np
